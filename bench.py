@@ -113,9 +113,17 @@ def main():
                     help='N > 1, --dp-collective rccl: what the all-reduce carries -- the split-K slabs (2 MB, three launches) or the flat '
                          'bucket (0.5 MB, four launches: the default at N > 1, or $FNN_DP_PAYLOAD); p2p always carries the bucket')
     ap.add_argument('--cpu-seconds', type=float, default=12.0)
+    ap.add_argument('--dump-outputs', default=None, metavar='DIR',
+                    help='fnn / snn workloads: after the timed steps, write what they left a caller (the embedding table, or the rows '
+                         'the last step updated; the dense layers; the last step\'s logloss) as DIR/<name>.npy (float32 / float64), '
+                         'rank 0\'s state at N > 1')
     args = ap.parse_args()
     if args.gpus < 1:
         raise SystemExit("--gpus must be >= 1")
+    if args.steps < 1 or args.warmup < 0:
+        raise SystemExit("--steps must be >= 1 and --warmup >= 0")
+    if args.dump_outputs and args.workload not in ('fnn', 'snn'):
+        raise SystemExit("--dump-outputs: the fnn / snn workloads only")
     if args.gpus > 1 and 'WORLD_SIZE' not in os.environ:
         if args.workload not in ('fnn', 'snn'):   # (e2e, pretrain included: one process)
             raise SystemExit("--gpus %d: only the fnn / snn steps shard (replicas of %s are not launched)" % (args.gpus, args.workload))
@@ -141,6 +149,7 @@ def main():
         if out is not None and world == 1 and args.workload == 'fnn' and not args.no_extras:
             import copy
             short = copy.copy(args)
+            short.dump_outputs = None                     # the headline leg's outputs only
             # the steps of these legs cost microseconds (their set-up dominates): same step counts as the headline, shorter CPU samples
             short.cpu_seconds = min(args.cpu_seconds, 4.0)
 
@@ -223,6 +232,35 @@ def in_step_gather(B):
     ach = (64 + 704) * B / (us * 1e-6) / 1e9
     return {'phase_us_median': us, 'achieved': ach, 'frac': ach / HBM_PEAK_GBS, 'unit': 'GB/s', 'algorithmic_per_example': 64 + 704,
             'source': os.path.basename(files[-1]), 'ids': d.get('ids')}
+
+
+DUMP_LIMIT = 64 << 20                                    # --dump-outputs: bytes in all
+
+
+def dump_outputs(out_dir, eng, last_ids, last_loss):
+    """--dump-outputs: the state the timed fnn_train_step loop leaves its caller, read back after the last timed step.  The
+    FNN table (937,670 x 11 f32, 41 MB) is written whole; a larger one (the SNN bag table, 750 MB) as the rows the last step
+    updated (`last_ids`: its batch), a seeded sample of them if those exceed 32 MB.  Dense layers w1 b1 w2 b2 w3 b3 (f32), the
+    bag bias in bag mode, and the last step's mean logloss (f64)."""
+    arrays = {'loss': np.array([last_loss], np.float64)}
+    for k, v in eng.get_dense().items():
+        arrays[k] = np.atleast_1d(np.asarray(v, np.float32))
+    if eng.bag:
+        arrays['bag_bias'] = eng.get_bag_bias()
+    row_bytes = eng.K * 4
+    if eng.n_rows * row_bytes <= 48 << 20:
+        arrays['table'] = eng.get_table()
+    else:
+        rows = np.unique(last_ids[last_ids >= 0]).astype(np.int64)
+        cap = (32 << 20) // row_bytes
+        if len(rows) > cap:
+            rows = np.sort(np.random.RandomState(0).choice(rows, cap, replace=False))
+        arrays['table_rows_last_step'] = eng.get_rows(rows)
+    total = sum(a.nbytes for a in arrays.values())
+    assert total <= DUMP_LIMIT, total
+    os.makedirs(out_dir, exist_ok=True)
+    for k, a in arrays.items():
+        np.save(os.path.join(out_dir, k + '.npy'), a)
 
 
 def bench_fnn(args, precision, snn):
@@ -362,6 +400,10 @@ def bench_fnn(args, precision, snn):
         dt = time.perf_counter() - t0
     eng.sync()
     last_loss = eng.last_loss() / B
+    if args.dump_outputs and rank == 0:
+        # before the profiled steps below move the state on; the last timed step trained on batch `last`
+        last = (args.warmup + args.steps - 1) % NB
+        dump_outputs(args.dump_outputs, eng, ids_np[last * B:(last + 1) * B], last_loss)
     if dist is not None:
         t = torch.tensor([dt], dtype=torch.float64, device=dev if not rehearse else 'cpu')
         dist.all_reduce(t, op=dist.ReduceOp.MAX)

@@ -333,6 +333,51 @@ def test_bench_refuses_to_run_fewer_ranks_than_asked(built):
     assert r.returncode != 0 and 'WORLD_SIZE=4' in (r.stderr + r.stdout)
 
 
+def test_bench_dump_outputs_files(tmp_path):
+    """bench.py --dump-outputs: float32 / float64 .npy files, 64 MB at most -- the whole FNN table (41 MB), and of the SNN bag
+    table (750 MB) the rows the last batch updated; the workloads it does not cover are refused before any GPU work."""
+    import subprocess
+    import sys
+    import bench
+
+    class Engine:                                             # what dump_outputs reads of an FNNEngine, in host memory
+        def __init__(self, bag, k, n_rows):
+            self.bag, self.K, self.n_rows = bag, k, n_rows
+            self.table = np.arange(n_rows, dtype=np.float32)[:, None] + np.zeros(k, np.float32)
+
+        def get_dense(self):
+            x = self.K if self.bag else XDIM
+            return {'w1': np.ones((x, H1), np.float32), 'b1': np.ones(H1, np.float32), 'w2': np.ones((H1, H2), np.float32),
+                    'b2': np.ones(H2, np.float32), 'w3': np.ones(H2, np.float32), 'b3': 0.5}
+
+        def get_bag_bias(self):
+            return np.zeros(self.K, np.float32)
+
+        def get_table(self):
+            return self.table
+
+        def get_rows(self, rows):
+            assert rows.dtype == np.int64 and np.all(np.diff(rows) > 0)
+            return self.table[rows]
+
+    sizes = synth.field_sizes_ipinyou()
+    ids = synth.zipf_ids(4096, sizes, 1.1, 1234)
+    for bag, k, table in ((False, K, 'table'), (True, 200, 'table_rows_last_step')):
+        eng = Engine(bag, k, sum(sizes))
+        out = tmp_path / ('bag' if bag else 'fm')
+        bench.dump_outputs(str(out), eng, ids, 0.25)
+        got = {f[:-4]: np.load(str(out / f)) for f in os.listdir(str(out))}
+        assert set(got) == {'loss', 'w1', 'b1', 'w2', 'b2', 'w3', 'b3', table} | ({'bag_bias'} if bag else set())
+        assert all(a.dtype in (np.float32, np.float64) for a in got.values())
+        assert sum(a.nbytes for a in got.values()) <= 64 << 20
+        assert got['loss'].tolist() == [0.25] and got['b3'].tolist() == [0.5]
+        want = np.unique(ids) if bag else np.arange(sum(sizes))
+        assert np.array_equal(got[table], eng.table[want])
+    r = subprocess.run([sys.executable, os.path.join(ROOT, 'bench.py'), '--workload', 'ipnn', '--dump-outputs', str(tmp_path / 'x')],
+                       capture_output=True, text=True, timeout=300)
+    assert r.returncode != 0 and 'fnn / snn' in r.stderr and not (tmp_path / 'x').exists()
+
+
 def test_mask_rows_drawn_ahead_equal_per_step_draws():
     """FNN.py draws an epoch's dropout rows in one call (_BinomialOp.draw_rows): the same rows as one draw per `train` call
     (python/FNN_wnzh.py:154,166 through theano's RandomStreams), for the script's dropout rates."""
