@@ -23,11 +23,14 @@ def field_sizes_ipinyou(total=IPINYOU_DIMS):
 
 
 def field_sizes_tiny(total=1000, n_fields=16):
-    base = [7, 24, 20, 300, 35, 120, 5, 150, 200, 21, 14, 11, 4, 70, 9, 4][:n_fields]
+    """Per-field row counts summing to `total`; more than 16 fields repeat the 16-field pattern (Criteo-like 39, the
+    library's 64), fewer take its head.  The remainder goes to field 3 (IP), or to field 0 when there are fewer fields."""
+    pattern = [7, 24, 20, 300, 35, 120, 5, 150, 200, 21, 14, 11, 4, 70, 9, 4]
+    base = [pattern[f % 16] for f in range(n_fields)]
     if total < sum(base):
         scale = float(total) / sum(base)
         base = [max(2, int(b * scale)) for b in base]
-    base[3] += total - sum(base)
+    base[3 if n_fields > 3 else 0] += total - sum(base)
     assert min(base) >= 1
     return base
 
