@@ -23,6 +23,7 @@ class IPNNEngine(object):
         self.device = torch.device('cuda', device)
         self.stream = torch.cuda.Stream(device=self.device)
         self.F, self.K, self.hidden = n_fields, k, list(hidden)
+        self.max_batch = max_batch
         self.d = [n_fields * k + (n_fields * (n_fields - 1) // 2 if pairs else 0) + 1] + self.hidden + [1]
         hid = (C.c_int32 * 8)(*(self.hidden + [0] * (8 - len(self.hidden))))
         cfg = _capi.ipnn_cfg(n_fields, k, len(self.hidden), hid, _capi.IPNN_ACTS[act], 1 if pairs else 0, max_batch,
@@ -108,8 +109,8 @@ class IPNNEngine(object):
         ids_t = self._dev(ids, torch.int32)
         out = torch.empty(ids_t.shape[0], dtype=torch.float32, device=self.device)
         self.stream.wait_stream(torch.cuda.current_stream(self.device))
-        for lo in range(0, ids_t.shape[0], 4096):
-            hi = min(ids_t.shape[0], lo + 4096)
+        for lo in range(0, ids_t.shape[0], self.max_batch):          # ipnn_predict takes at most max_batch examples a call
+            hi = min(ids_t.shape[0], lo + self.max_batch)
             self._ck(self.lib.ipnn_predict(self.h, ids_t[lo:hi].data_ptr(), hi - lo, out[lo:hi].data_ptr()))
         torch.cuda.current_stream(self.device).wait_stream(self.stream)
         return out
