@@ -3,6 +3,7 @@
 (`W`, `V`, `b`) and the roles of its graph outputs (`train_step` = ptmzr + loss + train_preds,
 `forward` = test_preds).  `write_fm_model` closes the loop the reference leaves open: it writes the
 `fm.model.txt` text format that python/FNN_wnzh.py:62-84 parses, so that FM -> FNN runs end to end.
+Optimisers: plain SGD, Adam and FTRL as python/tf_util.py:15-29 builds them (`parse_ptmzr`).
 Random init uses NumPy RandomState(seed) streams (TensorFlow's cannot be reproduced here)."""
 import ctypes as C
 import pickle
@@ -12,29 +13,44 @@ import numpy as np
 from . import _capi
 from .engine import FNNError
 
+OPTIMIZERS = {'sgd': 0, 'adam': 1, 'ftrl': 2}                      # FM_OPT_* of include/fm_hip.h
+
+
+def parse_ptmzr(_ptmzr_argv):
+    """python/tf_util.py:15-29's layouts: ['sgd', lr(, 'sum')], ['adam', lr, eps(, 'sum')], ['ftrl', lr(, 'sum')].
+    Returns (FM_OPT_* code, lr, Adam's eps, reduce_mean); the loss is reduce_sum only when 'sum' is the LAST element
+    (python/FM.py:38-41)."""
+    name = _ptmzr_argv[0]
+    if name not in OPTIMIZERS:
+        raise NotImplementedError("optimizer %r: sgd, adam and ftrl are built (python/tf_util.py:15-29)" % (name,))
+    if name == 'adam' and len(_ptmzr_argv) < 3:
+        raise ValueError("adam needs ['adam', learning_rate, epsilon(, 'sum')] (python/tf_util.py:17)")
+    eps = float(_ptmzr_argv[2]) if name == 'adam' else 1e-8
+    return OPTIMIZERS[name], float(_ptmzr_argv[1]), eps, 0 if _ptmzr_argv[-1] == 'sum' else 1
+
 
 class FM(object):
     def __init__(self, batch_size, _rch_argv, _init_argv, _ptmzr_argv, _reg_argv, mode='train', eval_size=0, device=0):
         import torch
+        X_dim, X_feas, rank = _rch_argv                              # python/FM.py:7
+        self.optimizer, self.lr, self.eps, self.reduce_mean = parse_ptmzr(_ptmzr_argv)
         if not torch.cuda.is_available():
             raise FNNError(_capi.FNN_ERR_HIP, "no HIP device visible to PyTorch-ROCm; no CPU fallback")
-        X_dim, X_feas, rank = _rch_argv                              # python/FM.py:7
-        if _ptmzr_argv[0] != 'sgd':
-            raise NotImplementedError("only plain SGD is built (the reference's Adam/FTRL: python/tf_util.py:15-29)")
         self._torch, self.lib = torch, _capi.load()
         self.device = torch.device('cuda', device)
         self.stream = torch.cuda.Stream(device=self.device)
         self.X_dim, self.X_feas, self.rank = X_dim, X_feas, rank
-        self.lr = float(_ptmzr_argv[1])
-        self.reduce_mean = 0 if _ptmzr_argv[-1] == 'sum' else 1      # :38-41
         self.lam = float(_reg_argv[0]) if mode == 'train' else 0.0
         self.log = 'input dim: %d, features: %d, rank: %d, ' % (X_dim, X_feas, rank)
         h = C.c_void_p()
-        rc = self.lib.fm_create(X_feas, rank + 1, min(4096, max(batch_size, eval_size, 1)), device,
+        self.max_batch = min(4096, max(batch_size, eval_size, 1))
+        rc = self.lib.fm_create(X_feas, rank + 1, self.max_batch, device,
                                 C.c_void_p(self.stream.cuda_stream), C.byref(h))
         if rc != 0:
             raise FNNError(rc, (self.lib.fm_last_error(None) or b'').decode())
         self.h = h
+        if self.optimizer:                                          # tf.train.AdamOptimizer's beta1 / beta2 defaults
+            self._ck(self.lib.fm_set_optimizer(h, self.optimizer, 0.9, 0.999, self.eps))
         lo, hi, seeds, path = _init_argv[1], _init_argv[2], _init_argv[3], _init_argv[-1]
         var_map = pickle.load(open(path, 'rb')) if path else {}     # python/tf_util.py:41-82
         W = var_map['W'] if 'W' in var_map else np.random.RandomState(seeds[0]).uniform(lo, hi, (X_dim, 1))
@@ -96,11 +112,28 @@ class FM(object):
         ids_t = self._dev(ids, torch.int32)
         out = torch.empty(ids_t.shape[0], dtype=torch.float32, device=self.device)
         self.stream.wait_stream(torch.cuda.current_stream(self.device))
-        for lo in range(0, ids_t.shape[0], 4096):
-            hi = min(ids_t.shape[0], lo + 4096)
+        for lo in range(0, ids_t.shape[0], self.max_batch):
+            hi = min(ids_t.shape[0], lo + self.max_batch)
             self._ck(self.lib.fm_predict(self.h, ids_t[lo:hi].data_ptr(), hi - lo, out[lo:hi].data_ptr()))
         self._ck(self.lib.fm_sync(self.h))
         return out
+
+    def evaluate(self, ids, y):
+        """Predictions and (auc, rmse, logloss) on the device (fm_eval): exact AUC, ties at 1/2."""
+        torch = self._torch
+        ids_t, y_t = self._dev(ids, torch.int32), self._dev(y, torch.int32)
+        auc, rmse, ll = C.c_double(), C.c_double(), C.c_double()
+        self.stream.wait_stream(torch.cuda.current_stream(self.device))
+        self._ck(self.lib.fm_eval(self.h, ids_t.data_ptr(), y_t.data_ptr(), ids_t.shape[0], C.byref(auc), C.byref(rmse), C.byref(ll)))
+        return auc.value, rmse.value, ll.value
+
+    def get_opt_state(self):
+        """Adam (m, v) or FTRL (accum, linear) of the rows [X_dim, rank + 1] and of the bias [2], and the step count."""
+        K = self.rank + 1
+        s0, s1 = np.empty((self.X_dim, K), np.float32), np.empty((self.X_dim, K), np.float32)
+        sb, t = np.empty(2, np.float32), C.c_int64()
+        self._ck(self.lib.fm_get_opt_state(self.h, s0.ctypes.data, s1.ctypes.data, sb.ctypes.data, C.byref(t)))
+        return s0, s1, sb, t.value
 
     def dump(self, model_path):                                      # python/FM.py:66-69
         rows, b = self.get_params()

@@ -1,6 +1,8 @@
 // fm_api.hip -- factorisation-machine pre-training on gfx950 behind include/fm_hip.h (row N3):
 // python/FM.py:55-64 (factorization), :36-41 (loss) and plain SGD, on the FNN path's building
-// blocks: padded 64-byte rows, the split sort + two-level segmented sparse-row update.
+// blocks: padded 64-byte rows, the split sort + two-level segmented sparse-row update.  Adam and
+// FTRL (python/tf_util.py:15-24): the same sorted sums into a zeroed gradient store, then one
+// streaming pass over the live elements of the table and its compact state (k_fm_opt_pass).
 #include <hip/hip_runtime.h>
 
 #include <cmath>
@@ -11,6 +13,8 @@
 #include "../../include/fm_hip.h"
 #include "../../include/fnn_hip.h"
 #include "fnn_step_kernels.hip.h"
+#include "metrics.hip.h"
+#include "optim.hip.h"
 
 using namespace fnn;
 
@@ -25,6 +29,7 @@ struct FmArgs {
     const int32_t* ids; const float* y; int B, F, K; const float* table16; int64_t n_rows; const float* b;
     float scale, dscale; int train; float* gxp; int K1p; float* p_out; float* loss_t; float* gb_part; int* err;
     bool wt;                   // gx' written through (see store4_wt in fnn_kernels.hip.h)
+    int* stamp; int step;      // Adam / FTRL: stamp[row] = step for every row the batch touches (null: not kept)
 };
 
 __device__ __forceinline__ void fm_body(const FmArgs& a, const int blk, float* s_gb)
@@ -35,6 +40,7 @@ __device__ __forceinline__ void fm_body(const FmArgs& a, const int blk, float* s
     if (t < a.B && f < a.F) {
         id = a.ids[(size_t)t * a.F + f];
         if (id < -1 || id >= a.n_rows) { atomicOr(a.err, 1); id = -1; }
+        if (a.stamp && id >= 0) a.stamp[id] = a.step;
     }
     float r[16];
 #pragma unroll
@@ -99,9 +105,15 @@ __global__ __launch_bounds__(256) void k_fm_merge_fwd(const SortArgs so, const F
     fm_body(a, (int)blockIdx.x - so.nblk, s_gb);
 }
 
-// b <- b (1 - lr lambda) - lr sum(delta); loss sum (fixed-shape tree)
+// The bias under Adam / FTRL: the state beside it (sb [2]) and this step's learning rate (Adam: lr_t).  opt = 0: SGD.
+struct FmBiasOpt { int opt; float* sb; float lr, b1, b2, eps; };
+__device__ __forceinline__ float fm_opt_step(int opt, float w, float g, float& s0, float& s1, float lr, float b1, float b2, float eps) {
+    return opt == FM_OPT_FTRL ? ftrl_step(w, g, s0, s1, lr) : adam_step(w, g, s0, s1, lr, b1, b2, eps);
+}
+
+// b <- b (1 - lr lambda) - lr sum(delta) (Adam / FTRL: the optimiser on g = sum(delta) + lambda b); loss sum (fixed-shape tree)
 __device__ __forceinline__ void fm_tail_body(float* b, const float* gb_part, int n, float lr, float lambda, const float* loss_t, int Ba, float lscale,
-                                             float* loss_out, float* sl)
+                                             float* loss_out, float* sl, const FmBiasOpt& bo)
 {   // both sums as 256 strided partial sums and a fixed-shape tree (one thread walking the n partials paid a memory round trip
     // per element: 19 us for 256 of them)
     float v = strided_sum256(gb_part, n);
@@ -112,13 +124,17 @@ __device__ __forceinline__ void fm_tail_body(float* b, const float* gb_part, int
     v = strided_sum256(loss_t, Ba);
     sl[threadIdx.x] = v; __syncthreads();
     for (int o = 128; o > 0; o >>= 1) { if ((int)threadIdx.x < o) sl[threadIdx.x] += sl[threadIdx.x + o]; __syncthreads(); }
-    if (threadIdx.x == 0) { *b = *b * (1.0f - lr * lambda) - lr * gsum; *loss_out = sl[0] * lscale; }
+    if (threadIdx.x == 0) {
+        if (bo.opt) *b = fm_opt_step(bo.opt, *b, gsum + lambda * *b, bo.sb[0], bo.sb[1], bo.lr, bo.b1, bo.b2, bo.eps);
+        else *b = *b * (1.0f - lr * lambda) - lr * gsum;
+        *loss_out = sl[0] * lscale;
+    }
 }
 __global__ __launch_bounds__(256) void k_fm_scat2_tail(const ScatArgs sa, float* b, const float* gb_part, int n, float lr, float lambda,
-                                                       const float* loss_t, int Ba, float lscale, float* loss_out)
+                                                       const float* loss_t, int Ba, float lscale, float* loss_out, const FmBiasOpt bo)
 {
     __shared__ double s_sum[16][16];
-    if (blockIdx.x == 0) { fm_tail_body(b, gb_part, n, lr, lambda, loss_t, Ba, lscale, loss_out, reinterpret_cast<float*>(&s_sum[0][0])); return; }
+    if (blockIdx.x == 0) { fm_tail_body(b, gb_part, n, lr, lambda, loss_t, Ba, lscale, loss_out, reinterpret_cast<float*>(&s_sum[0][0]), bo); return; }
     scat2_body(sa, (int)blockIdx.x - 1, (int)gridDim.x - 1, s_sum);
 }
 
@@ -126,6 +142,51 @@ __global__ void k_fm_rescale(float* table16, size_t n, float s)
 {
     const size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
     if (i < n) table16[i] *= s;
+}
+
+__global__ void k_fm_fill(float* p, size_t n, float v)
+{
+    const size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
+    if (i < n) p[i] = v;
+}
+
+// Adam / FTRL on the table: the L2 term makes TensorFlow's gradient DENSE, so every live element (row < n_rows, column < K)
+// moves each step: g = G + lambda w, the optimiser, w and both state values written back.  The state is compact [n_rows, K]
+// (s0 / s1 rounded up to a multiple of 4 floats): a thread owns 4 consecutive elements of it -- one 16-byte access per state
+// array -- and the matching 4 table / G elements at their padded-row addresses; padding columns are never touched.
+// G (the batch's per-row gradient sums, padded rows) is read and cleared only where it was written: DENSE_G = false reads a
+// row's G when stamp[row] == step (the rows this step's forward touched); DENSE_G = true reads and clears every element of G.
+template <bool DENSE_G>
+__global__ __launch_bounds__(256) void k_fm_opt_pass(float* __restrict__ table16, float* __restrict__ G, const int* __restrict__ stamp, int step,
+                                                     float* __restrict__ s0, float* __restrict__ s1, size_t nk, int K, float lambda,
+                                                     int opt, float lr, float b1, float b2, float eps)
+{
+    const size_t e0 = ((size_t)blockIdx.x * blockDim.x + threadIdx.x) * 4;
+    if (e0 >= nk) return;
+    size_t row = e0 / K;
+    int c = (int)(e0 - row * K);
+    const float4 m4 = *reinterpret_cast<const float4*>(s0 + e0), v4 = *reinterpret_cast<const float4*>(s1 + e0);
+    float m[4] = {m4.x, m4.y, m4.z, m4.w}, v[4] = {v4.x, v4.y, v4.z, v4.w}, w[4], g[4];
+    size_t off[4];
+    bool live[4], hit[4];
+#pragma unroll
+    for (int j = 0; j < 4; ++j) {                      // every load first, then the arithmetic, then the stores
+        live[j] = e0 + j < nk;
+        off[j] = row * SLOT + c;
+        w[j] = live[j] ? table16[off[j]] : 0.f;
+        hit[j] = live[j] && (DENSE_G || stamp[row] == step);
+        g[j] = hit[j] ? G[off[j]] : 0.f;
+        if (++c == K) { c = 0; ++row; }
+    }
+#pragma unroll
+    for (int j = 0; j < 4; ++j) {
+        if (!live[j]) continue;
+        w[j] = fm_opt_step(opt, w[j], g[j] + lambda * w[j], m[j], v[j], lr, b1, b2, eps);
+        table16[off[j]] = w[j];
+        if (hit[j]) G[off[j]] = 0.f;
+    }
+    *reinterpret_cast<float4*>(s0 + e0) = make_float4(m[0], m[1], m[2], m[3]);
+    *reinterpret_cast<float4*>(s1 + e0) = make_float4(v[0], v[1], v[2], v[3]);
 }
 
 }  // namespace
@@ -137,6 +198,10 @@ struct fm_handle {
     float *gxp = nullptr, *loss_t = nullptr, *gb_part = nullptr, *loss_dev = nullptr; int* err_flag = nullptr;
     int4* rec = nullptr; double* part = nullptr; int4* owners = nullptr; int* owner_cnt = nullptr; void* skeys = nullptr;
     double* cpow1 = nullptr; bool key64 = true;
+    // Adam / FTRL (fm_set_optimizer): compact state s0 / s1 [n_rows, K], the bias's sb [2], gradient store G [n_rows, SLOT],
+    // stamp [n_rows]; t = steps since the state was initialised.  dense_g: FM_OPT_DENSE_G=1, the A/B variant of k_fm_opt_pass.
+    int opt = FM_OPT_SGD; float beta1 = 0.9f, beta2 = 0.999f, eps = 1e-8f; int64_t t = 0; bool dense_g = false;
+    float *s0 = nullptr, *s1 = nullptr, *sb = nullptr, *G = nullptr; int* stamp = nullptr;
 };
 
 #define MHK(h, expr) do { hipError_t e_ = (expr); if (e_ != hipSuccess) { (h)->err = std::string(#expr) + ": " + hipGetErrorString(e_); return FNN_ERR_HIP; } } while (0)
@@ -154,11 +219,44 @@ int fold_scale(fm_handle* h)          // fold the lazy decay back into the rows
     return FNN_OK;
 }
 
+size_t opt_state_len(const fm_handle* h) { return ((size_t)h->n_rows * h->K + 3) & ~(size_t)3; }
+
+// Free and, under Adam / FTRL, allocate and initialise the optimiser state for the current table; resets the step count.
+int init_opt_state(fm_handle* h)
+{
+    for (float** p : {&h->s0, &h->s1, &h->G}) { if (*p) hipFree(*p); *p = nullptr; }
+    if (h->stamp) hipFree(h->stamp);
+    h->stamp = nullptr; h->t = 0;
+    if (h->opt == FM_OPT_SGD) return FNN_OK;
+    const float sb[2] = {h->opt == FM_OPT_FTRL ? 0.1f : 0.f, 0.f};
+    MHK(h, hipMemcpy(h->sb, sb, 8, hipMemcpyHostToDevice));
+    if (!h->table16) return FNN_OK;
+    const size_t n = opt_state_len(h);
+    MHK(h, hipMalloc((void**)&h->s0, n * 4)); MHK(h, hipMalloc((void**)&h->s1, n * 4));
+    MHK(h, hipMalloc((void**)&h->G, (size_t)h->n_rows * SLOT * 4)); MHK(h, hipMalloc((void**)&h->stamp, (size_t)h->n_rows * 4));
+    MHK(h, hipMemsetAsync(h->s1, 0, n * 4, h->st)); MHK(h, hipMemsetAsync(h->G, 0, (size_t)h->n_rows * SLOT * 4, h->st));
+    MHK(h, hipMemsetAsync(h->stamp, 0, (size_t)h->n_rows * 4, h->st));
+    if (h->opt == FM_OPT_FTRL) hipLaunchKernelGGL(k_fm_fill, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, h->st, h->s0, n, 0.1f);
+    else MHK(h, hipMemsetAsync(h->s0, 0, n * 4, h->st));
+    MHK(h, hipGetLastError());
+    MHK(h, hipStreamSynchronize(h->st));
+    return FNN_OK;
+}
+
 int fm_run(fm_handle* h, const int32_t* ids, const float* y, int B, float lr, float lambda, int reduce_mean, float* p_out, bool train)
 {
     const int Ba = rup(B, 16), F = h->F;
+    const bool opt = train && h->opt != FM_OPT_SGD;
+    float lr_step = lr;
+    if (opt) {
+        h->t += 1;
+        if (h->opt == FM_OPT_ADAM)                 // TensorFlow's bias-corrected step size lr_t
+            lr_step = (float)((double)lr * std::sqrt(1.0 - std::pow((double)h->beta2, (double)h->t)) /
+                              (1.0 - std::pow((double)h->beta1, (double)h->t)));
+    }
     FmArgs a{ids, y, B, F, h->K, h->table16, h->n_rows, h->b, (float)h->scale, reduce_mean ? 1.0f / (float)B : 1.0f, train ? 1 : 0,
-             h->gxp, h->K1p, p_out, h->loss_t, h->gb_part, h->err_flag, !(getenv("FM_WT") && atoi(getenv("FM_WT")) == 0)};
+             h->gxp, h->K1p, p_out, h->loss_t, h->gb_part, h->err_flag, !(getenv("FM_WT") && atoi(getenv("FM_WT")) == 0),
+             opt && !h->dense_g ? h->stamp : nullptr, (int)h->t};
     if (!train) {
         hipLaunchKernelGGL(k_fm, dim3(Ba / 16), dim3(256), 0, h->st, a);
         MHK(h, hipGetLastError());
@@ -175,13 +273,29 @@ int fm_run(fm_handle* h, const int32_t* ids, const float* y, int B, float lr, fl
             hipLaunchKernelGGL((k_fm_merge_fwd<unsigned>), dim3(16 * F + Ba / 16), dim3(256), SORT_N * 4, h->st, sb, a);
         }
     }
+    if (opt) {   // Adam / FTRL: the same sorted sums land in the zeroed gradient store: G[row] = 0 * 1 - (-1) * sum
+        ScatArgs sa{h->rec, SORT_N, F, h->K, h->gxp, h->K1p, h->cpow1, -1.0, h->G, h->part, h->owner_cnt, h->owners, SLOT};
+        hipLaunchKernelGGL(k_scat1, dim3(F * SORT_N / 256), dim3(256), 0, h->st, sa);
+        hipLaunchKernelGGL(k_fm_scat2_tail, dim3(1 + 256), dim3(256), 0, h->st, sa, h->b, h->gb_part, Ba / 16, lr, lambda, h->loss_t, Ba,
+                           reduce_mean ? 1.0f / (float)B : 1.0f, h->loss_dev, FmBiasOpt{h->opt, h->sb, lr_step, h->beta1, h->beta2, h->eps});
+        const size_t nk = (size_t)h->n_rows * h->K;
+        const dim3 grid((unsigned)(((nk + 3) / 4 + 255) / 256));
+        if (h->dense_g)
+            hipLaunchKernelGGL(k_fm_opt_pass<true>, grid, dim3(256), 0, h->st, h->table16, h->G, h->stamp, (int)h->t, h->s0, h->s1, nk, h->K,
+                               lambda, h->opt, lr_step, h->beta1, h->beta2, h->eps);
+        else
+            hipLaunchKernelGGL(k_fm_opt_pass<false>, grid, dim3(256), 0, h->st, h->table16, h->G, h->stamp, (int)h->t, h->s0, h->s1, nk, h->K,
+                               lambda, h->opt, lr_step, h->beta1, h->beta2, h->eps);
+        MHK(h, hipGetLastError());
+        return FNN_OK;
+    }
     // dense L2 decay of the whole table = one scalar; touched rows: stored -= lr * g / scale
     h->scale *= 1.0 - (double)lr * (double)lambda;
     ScatArgs sa{h->rec, SORT_N, F, h->K, h->gxp, h->K1p, h->cpow1, (double)lr / h->scale, h->table16, h->part, h->owner_cnt,
                 h->owners, SLOT};
     hipLaunchKernelGGL(k_scat1, dim3(F * SORT_N / 256), dim3(256), 0, h->st, sa);
     hipLaunchKernelGGL(k_fm_scat2_tail, dim3(1 + 256), dim3(256), 0, h->st, sa, h->b, h->gb_part, Ba / 16, lr, lambda, h->loss_t, Ba,
-                       reduce_mean ? 1.0f / (float)B : 1.0f, h->loss_dev);
+                       reduce_mean ? 1.0f / (float)B : 1.0f, h->loss_dev, FmBiasOpt{FM_OPT_SGD, nullptr, 0.f, 0.f, 0.f, 0.f});
     MHK(h, hipGetLastError());
     if (h->scale < 5.96e-8 || h->scale > 1.0) return fold_scale(h);
     return FNN_OK;
@@ -210,7 +324,7 @@ int fm_create(int n_fields, int k, int max_batch, int device, void* stream, fm_h
     auto al = [&](void** p, size_t bytes) { hipError_t e = hipMalloc(p, bytes); if (e == hipSuccess) e = hipMemsetAsync(*p, 0, bytes, h->st); return e; };
     const size_t Ba = rup(h->Bmax, 16);
     FK(al((void**)&h->gxp, Ba * h->K1p * 4)); FK(al((void**)&h->loss_t, Ba * 4)); FK(al((void**)&h->gb_part, (Ba / 16) * 4));
-    FK(al((void**)&h->loss_dev, 4)); FK(al((void**)&h->b, 4)); FK(al((void**)&h->err_flag, 4));
+    FK(al((void**)&h->loss_dev, 4)); FK(al((void**)&h->b, 4)); FK(al((void**)&h->err_flag, 4)); FK(al((void**)&h->sb, 8));
     FK(al((void**)&h->rec, (size_t)h->F * SORT_N * sizeof(int4))); FK(al((void**)&h->part, (size_t)h->F * (SORT_N / 16) * 2 * SLOT * 8));
     FK(al((void**)&h->owners, (size_t)h->F * (SORT_N / 16) * sizeof(int4))); FK(al((void**)&h->owner_cnt, 4));
     FK(al(&h->skeys, (size_t)h->F * SORT_N * 8));
@@ -221,6 +335,7 @@ int fm_create(int n_fields, int k, int max_batch, int device, void* stream, fm_h
     }
     FK(hipStreamSynchronize(h->st));
 #undef FK
+    h->dense_g = getenv("FM_OPT_DENSE_G") && atoi(getenv("FM_OPT_DENSE_G")) == 1;
     *out = h;
     return FNN_OK;
 }
@@ -231,7 +346,7 @@ int fm_destroy(fm_handle* h)
     hipSetDevice(h->dev);
     if (h->st) hipStreamSynchronize(h->st);
     void* ptrs[] = {h->table16, h->b, h->gxp, h->loss_t, h->gb_part, h->loss_dev, h->err_flag, h->rec, h->part, h->owners, h->owner_cnt,
-                    h->skeys, h->cpow1};
+                    h->skeys, h->cpow1, h->s0, h->s1, h->sb, h->G, h->stamp};
     for (void* p : ptrs) if (p) hipFree(p);
     if (h->own_stream && h->st) hipStreamDestroy(h->st);
     delete h;
@@ -264,7 +379,7 @@ int fm_set_table(fm_handle* h, const float* rows, int64_t n_rows)
     hipFree(tmp);
     h->n_rows = n_rows; h->scale = 1.0;
     h->key64 = (unsigned long long)n_rows * SORT_N > 0xFFFFFFFFull;
-    return FNN_OK;
+    return init_opt_state(h);                                     // fresh state for the new rows
 }
 
 static int fm_rows(fm_handle* h, const int64_t* row_ids, int64_t n, float* out)
@@ -314,7 +429,8 @@ int fm_train_step(fm_handle* h, const int32_t* ids, const float* y, int B, float
     if (!h || !ids || !y) return FNN_ERR_ARG;
     if (B < 1 || B > h->Bmax) MFAIL(h, FNN_ERR_ARG, "B must be in [1, max_batch]");
     if (!h->table16) MFAIL(h, FNN_ERR_STATE, "fm_set_table has not been called");
-    if (!(lr * lambda < 1.0f) || lambda < 0.f) MFAIL(h, FNN_ERR_ARG, "need 0 <= lr * lambda < 1");
+    if (h->opt == FM_OPT_SGD && (!(lr * lambda < 1.0f) || lambda < 0.f)) MFAIL(h, FNN_ERR_ARG, "need 0 <= lr * lambda < 1");
+    if (h->opt != FM_OPT_SGD && (!(lambda >= 0.f) || !(lr > 0.f))) MFAIL(h, FNN_ERR_ARG, "Adam / FTRL need lr > 0 and lambda >= 0");
     MHK(h, hipSetDevice(h->dev));
     int rc = fm_run(h, ids, y, B, lr, lambda, reduce_mean, p_out, true);
     if (rc != FNN_OK) return rc;
@@ -332,6 +448,61 @@ int fm_predict(fm_handle* h, const int32_t* ids, int B, float* p_out)
     if (!h->table16) MFAIL(h, FNN_ERR_STATE, "fm_set_table has not been called");
     MHK(h, hipSetDevice(h->dev));
     return fm_run(h, ids, nullptr, B, 0.f, 0.f, 0, p_out, false);
+}
+
+int fm_set_optimizer(fm_handle* h, int optimizer, float beta1, float beta2, float eps)
+{
+    if (!h) return FNN_ERR_ARG;
+    if (optimizer != FM_OPT_SGD && optimizer != FM_OPT_ADAM && optimizer != FM_OPT_FTRL) MFAIL(h, FNN_ERR_ARG, "bad optimizer");
+    if (optimizer == FM_OPT_ADAM && !(beta1 >= 0.f && beta1 < 1.f && beta2 >= 0.f && beta2 < 1.f && eps > 0.f))
+        MFAIL(h, FNN_ERR_ARG, "Adam needs 0 <= beta1, beta2 < 1 and eps > 0");
+    MHK(h, hipSetDevice(h->dev));
+    const int rc = fold_scale(h);                                  // the pending SGD decay goes into the rows first
+    if (rc != FNN_OK) return rc;
+    MHK(h, hipStreamSynchronize(h->st));
+    h->opt = optimizer;
+    if (optimizer == FM_OPT_ADAM) { h->beta1 = beta1; h->beta2 = beta2; h->eps = eps; }
+    return init_opt_state(h);
+}
+
+int fm_get_opt_state(fm_handle* h, float* s0, float* s1, float* sb, int64_t* t)
+{
+    if (!h) return FNN_ERR_ARG;
+    if (h->opt == FM_OPT_SGD) MFAIL(h, FNN_ERR_STATE, "plain SGD keeps no optimiser state");
+    if (!h->table16) MFAIL(h, FNN_ERR_STATE, "fm_set_table has not been called");
+    MHK(h, hipSetDevice(h->dev)); MHK(h, hipStreamSynchronize(h->st));
+    const size_t n = (size_t)h->n_rows * h->K * 4;
+    if (s0) MHK(h, hipMemcpy(s0, h->s0, n, hipMemcpyDeviceToHost));
+    if (s1) MHK(h, hipMemcpy(s1, h->s1, n, hipMemcpyDeviceToHost));
+    if (sb) MHK(h, hipMemcpy(sb, h->sb, 8, hipMemcpyDeviceToHost));
+    if (t) *t = h->t;
+    return FNN_OK;
+}
+
+int fm_eval(fm_handle* h, const int32_t* ids, const int32_t* y, int64_t N, double* auc, double* rmse, double* logloss)
+{
+    if (!h || !ids || !y || N < 1) return FNN_ERR_ARG;
+    if (!h->table16) MFAIL(h, FNN_ERR_STATE, "fm_set_table has not been called");
+    MHK(h, hipSetDevice(h->dev));
+    float* p_d = nullptr;
+    MHK(h, hipMalloc((void**)&p_d, (size_t)N * 4));
+    for (int64_t lo = 0; lo < N; lo += h->Bmax) {
+        const int B = (int)(N - lo < h->Bmax ? N - lo : h->Bmax);
+        const int rc = fm_run(h, ids + lo * h->F, nullptr, B, 0.f, 0.f, 0, p_d + lo, false);
+        if (rc != FNN_OK) { hipFree(p_d); return rc; }
+    }
+    double out[4] = {0, 0, 0, 0};
+    std::string merr;
+    const int mrc = device_metrics(h->st, p_d, y, N, out, merr);
+    hipFree(p_d);
+    if (mrc == -1) MFAIL(h, FNN_ERR_HIP, merr);
+    if (auc) *auc = out[0];
+    if (rmse) *rmse = out[1];
+    if (logloss) *logloss = out[2];
+    const int rc = fm_sync(h);
+    if (rc != FNN_OK) return rc;
+    if (mrc == -2) MFAIL(h, FNN_ERR_RANGE, merr);
+    return FNN_OK;
 }
 
 }  // extern "C"

@@ -18,6 +18,7 @@
 #include "../../include/ipnn_hip.h"
 #include "fnn_step_kernels.hip.h"
 #include "metrics.hip.h"
+#include "optim.hip.h"
 
 using namespace fnn;
 
@@ -901,22 +902,6 @@ static __global__ void k_ip_update(float* __restrict__ W, const float* __restric
     const int r = (int)(i / Dout), c = (int)(i % Dout);
     wf[ft_off<T>(c, r, Din)] = (T)w;
     wb[ft_off<T>(r, c, Dout)] = (T)w;
-}
-__device__ inline float adam_step(float w, float g, float& m, float& v, float lr_t, float b1, float b2, float eps) {
-    m = b1 * m + (1.0f - b1) * g;
-    v = b2 * v + (1.0f - b2) * g * g;
-    return w - lr_t * m / (sqrtf(v) + eps);
-}
-
-// TensorFlow's FtrlOptimizer(learning_rate) as python/tf_util.py:21-24 builds it (learning_rate_power -0.5, initial
-// accumulator 0.1, l1 = l2 = 0; the ApplyFtrl kernel): state = (accum, linear).  A variable with a zero gradient keeps its
-// accumulator and linear term, and is RE-DERIVED from them: w = -linear lr / sqrt(accum) -- with the dense table gradient
-// of this graph, rows no example has touched yet drop to 0 at the first step, as they do in the reference.
-__device__ inline float ftrl_step(float w, float g, float& accum, float& linear, float lr) {
-    const float na = accum + g * g, sa = sqrtf(na);
-    linear += g - g * g / (sa + sqrtf(accum)) / lr * w;         // sqrt(na) - sqrt(accum), written without the cancellation
-    accum = na;
-    return linear != 0.f ? -linear / (sa / lr) : 0.f;
 }
 __device__ inline float opt_step(int opt, float w, float g, float& s0, float& s1, float lr, float b1, float b2, float eps) {
     return opt == IPNN_OPT_FTRL ? ftrl_step(w, g, s0, s1, lr) : adam_step(w, g, s0, s1, lr, b1, b2, eps);

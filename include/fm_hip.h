@@ -15,6 +15,12 @@
  * sparse-row update as the FNN path, and the scale is folded back into the rows before it leaves
  * 2^-24 .. 1.  Same result as the dense update up to f32 rounding.
  *
+ * Adam and FTRL (python/tf_util.py:15-24, fm_set_optimizer): the lazy scale cannot express them -- under Adam every row's
+ * moments decay each step, under FTRL every variable is re-derived from its linear term.  The batch's per-row gradient sums
+ * then go into a zeroed gradient store instead of the table, and one streaming pass over every live element (row < n_rows,
+ * column < k) applies g = G + lambda * w, the optimiser and its state, and clears G.  The state is compact [n_rows, k].
+ * With k = 1 (rank 0) the model is the reference's LR (python/LR.py): yhat = b + sum_i w_i.
+ *
  * Error codes: FNN_ERR_* of fnn_hip.h; fm_last_error() has the message.
  */
 #ifndef FM_HIP_H
@@ -53,6 +59,22 @@ int fm_train_step(fm_handle* h, const int32_t* ids, const float* y, int B, float
                   int reduce_mean, float* p_out, float* loss_out);
 /* p_out [B] = sigmoid(yhat) (`test_preds`, :52). */
 int fm_predict(fm_handle* h, const int32_t* ids, int B, float* p_out);
+
+/* The optimiser of fm_train_step (python/tf_util.py:15-29); lr and lambda of fm_train_step keep their meaning (base
+ * learning rate, L2 weight).  Folds any pending SGD scale into the rows, (re)initialises the state -- Adam: m = v = 0;
+ * FTRL: accum = 0.1, linear = 0, the bias's as well -- and resets the step count.  fm_set_table re-initialises the state.
+ * beta1 / beta2 / eps: Adam only (TensorFlow's defaults 0.9 / 0.999; eps > 0). */
+#define FM_OPT_SGD  0   /* default: the lazy-scale SGD step above */
+#define FM_OPT_ADAM 1   /* tf.train.AdamOptimizer(lr, beta1, beta2, eps) */
+#define FM_OPT_FTRL 2   /* tf.train.FtrlOptimizer(lr): power -0.5, initial accumulator 0.1, l1 = l2 = 0 */
+int fm_set_optimizer(fm_handle* h, int optimizer, float beta1, float beta2, float eps);
+/* HOST pointers, each nullable.  s0 / s1 [n_rows, k]: Adam (m, v), FTRL (accum, linear); sb [2]: the bias's; t: steps
+ * taken since the state was initialised.  FNN_ERR_STATE under SGD. */
+int fm_get_opt_state(fm_handle* h, float* s0, float* s1, float* sb, int64_t* t);
+/* DEVICE pointers ids [N, F], y [N] (0 / non-zero).  Predictions in chunks of max_batch, then exact AUC (ties at 1/2),
+ * RMSE and logloss (p clipped to [2^-52, 1 - 2^-52]) on the device.  Outputs nullable.  FNN_ERR_RANGE when y holds one
+ * class only (auc undefined; rmse and logloss are still written). */
+int fm_eval(fm_handle* h, const int32_t* ids, const int32_t* y, int64_t N, double* auc, double* rmse, double* logloss);
 
 #if defined(__GNUC__)
 #pragma GCC visibility pop

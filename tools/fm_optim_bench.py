@@ -1,0 +1,139 @@
+"""Per-step time of FM / LR pre-training under SGD, Adam and FTRL at the iPinYou shape (937,670 rows, 16 fields, batch 4096),
+and the bytes the Adam / FTRL optimiser pass (k_fm_opt_pass in fm_api.hip) must move.  One JSON line on stdout.
+
+  python tools/fm_optim_bench.py [--steps 300 --warmup 30] [--only NAME,..]
+  python tools/fm_optim_bench.py --from-stats NAME=DIR ..    (kernel times of separate rocprofv3 --kernel-trace --stats runs,
+                                                              one config each: the pass time and its TB/s)
+
+Configurations: fm_sgd / fm_adam / fm_ftrl (rank 10), lr_ftrl (rank 0 = LR); *_dense: the A/B variant of the pass that reads and
+clears the whole gradient store G (FM_OPT_DENSE_G=1) instead of the rows the step's stamp marks."""
+import argparse
+import ctypes as C
+import glob
+import json
+import os
+import sys
+import time
+
+import numpy as np
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+F, SLOT = 16, 16
+# name: (rank, optimizer (FM_OPT_*), lr, lambda, reduce_mean, dense G) -- python/baseline.py's recipes: FM Adam 1e-4 / eps 1e-8 /
+# 'sum' / lambda 1e-3, LR FTRL 1e-3 / lambda 1e-4; SGD as bench.py's pretrain leg
+CONFIGS = {
+    'fm_sgd': (10, 0, 1e-4, 1e-6, 1, False),
+    'fm_adam': (10, 1, 1e-4, 1e-3, 0, False),
+    'fm_adam_dense': (10, 1, 1e-4, 1e-3, 0, True),
+    'fm_ftrl': (10, 2, 1e-3, 1e-3, 1, False),
+    'fm_ftrl_dense': (10, 2, 1e-3, 1e-3, 1, True),
+    'lr_ftrl': (0, 2, 1e-3, 1e-4, 1, False),
+    'lr_ftrl_dense': (0, 2, 1e-3, 1e-4, 1, True),
+}
+
+
+def pass_bytes(n_rows, K, dense):
+    """What the pass must move per step: w, s0 and s1 read and written for every live element; the stamp variant reads one
+    int per row (and G of the touched rows only: <= B * F rows, not counted), the dense variant reads and clears G everywhere."""
+    return n_rows * K * 4 * (8 if dense else 6) + (0 if dense else n_rows * 4)
+
+
+def shape():
+    sys.path.insert(0, ROOT)
+    import deep_ctr_amd  # noqa: F401
+    from deep_ctr_amd import synth
+    sizes = synth.field_sizes_ipinyou()
+    return sizes, sum(sizes)
+
+
+def run(names, steps, warmup, B):
+    import torch
+    sizes, D = shape()
+    from deep_ctr_amd import _capi, synth
+    lib = _capi.load()
+    dev = torch.device('cuda', 0)
+    stream = torch.cuda.Stream(device=dev)
+    NB = 16
+    ids = torch.as_tensor(synth.zipf_ids(NB * B, sizes, 1.1, 99)).to(dev).contiguous()
+    y = torch.as_tensor((np.random.RandomState(3).uniform(size=NB * B) < 0.02).astype(np.float32)).to(dev)
+    out = {}
+    for name in names:
+        rank, opt, lr, lam, mean, dense = CONFIGS[name]
+        K = rank + 1
+        os.environ['FM_OPT_DENSE_G'] = '1' if dense else '0'        # read by fm_create
+        h = C.c_void_p()
+        if lib.fm_create(F, K, B, 0, C.c_void_p(stream.cuda_stream), C.byref(h)) != 0:
+            raise RuntimeError((lib.fm_last_error(None) or b'').decode())
+        rows = synth.fm_table(D, K, 0.01, 77)
+        for rc in (lib.fm_set_optimizer(h, opt, 0.9, 0.999, 1e-8), lib.fm_set_table(h, rows.ctypes.data, D), lib.fm_set_b(h, 0.0)):
+            if rc != 0:
+                raise RuntimeError(lib.fm_last_error(h).decode())
+
+        def steps_(n):
+            for i in range(n):
+                j = i % NB
+                if lib.fm_train_step(h, ids.data_ptr() + j * B * F * 4, y.data_ptr() + j * B * 4, B, lr, lam, mean, None, None) != 0:
+                    raise RuntimeError(lib.fm_last_error(h).decode())
+        steps_(warmup)
+        if lib.fm_sync(h) != 0:
+            raise RuntimeError(lib.fm_last_error(h).decode())
+        t0 = time.perf_counter()
+        steps_(steps)
+        if lib.fm_sync(h) != 0:
+            raise RuntimeError(lib.fm_last_error(h).decode())
+        dt = (time.perf_counter() - t0) / steps
+        lib.fm_destroy(h)
+        r = {'us_per_step': dt * 1e6, 'examples_per_sec': B / dt}
+        if opt:
+            nb = pass_bytes(D, K, dense)
+            r.update({'pass_bytes': nb, 'pass_bytes_tbps_at_step_time': nb / dt / 1e12})
+        out[name] = r
+    return {'tool': 'fm_optim_bench', 'n_rows': D, 'fields': F, 'batch': B, 'steps': steps, 'warmup': warmup,
+            'device': torch.cuda.get_device_name(0), 'configs': out}
+
+
+def from_stats(pairs):
+    """NAME=DIR: the k_fm_opt_pass row of the kernel-stats CSV rocprofv3 wrote under DIR."""
+    import csv
+    _, D = shape()
+    out = {}
+    for pr in pairs:
+        name, d = pr.split('=', 1)
+        rank, opt, _, _, _, dense = CONFIGS[name]
+        files = glob.glob(os.path.join(d, '**', '*kernel_stats.csv'), recursive=True)
+        if not files:
+            raise SystemExit('no kernel_stats.csv under %s' % d)
+        kern = {}
+        for row in csv.DictReader(open(files[0])):
+            kern[row['Name']] = (int(row['Calls']), float(row['AverageNs']) / 1e3)
+        p = [v for k, v in kern.items() if 'k_fm_opt_pass' in k]
+        short = lambda k: k.replace('(anonymous namespace)::', '').replace('void ', '').split('(')[0]     # noqa: E731
+        r = {'kernels_us': {short(k): round(v[1], 2) for k, v in sorted(kern.items(), key=lambda kv: -kv[1][0] * kv[1][1])[:8]}}
+        if p:
+            nb = pass_bytes(D, rank + 1, dense)
+            r.update({'pass_us': p[0][1], 'pass_calls': p[0][0], 'pass_bytes': nb, 'pass_tbps': nb / (p[0][1] * 1e-6) / 1e12,
+                      'share_of_6.29_tbps_copy': nb / (p[0][1] * 1e-6) / 6.29e12})
+        out[name] = r
+    return {'tool': 'fm_optim_bench', 'kernel_stats': out}
+
+
+def main():
+    ap = argparse.ArgumentParser()
+    ap.add_argument('--steps', type=int, default=300)
+    ap.add_argument('--warmup', type=int, default=30)
+    ap.add_argument('--batch', type=int, default=4096)
+    ap.add_argument('--only', default=','.join(CONFIGS))
+    ap.add_argument('--from-stats', nargs='+', default=None)
+    a = ap.parse_args()
+    if a.from_stats:
+        print(json.dumps(from_stats(a.from_stats)))
+        return
+    names = a.only.split(',')
+    for n in names:
+        if n not in CONFIGS:
+            raise SystemExit('unknown config %r (%s)' % (n, ', '.join(CONFIGS)))
+    print(json.dumps(run(names, a.steps, a.warmup, a.batch)))
+
+
+if __name__ == '__main__':
+    main()
