@@ -3,6 +3,8 @@
 // blocks: padded 64-byte rows, the split sort + two-level segmented sparse-row update.  Adam and
 // FTRL (python/tf_util.py:15-24): the same sorted sums into a zeroed gradient store, then one
 // streaming pass over the live elements of the table and its compact state (k_fm_opt_pass).
+// Wide rows (k >= 17, ranks 16..127: the reference's FM50 / FM100): rows of rup(k, 4) floats, the forward of fm_wide_body and
+// the bag table's wide sparse-row update (scatw1_body / scatw2_body); the sort, the tail and the optimiser pass are shared.
 #include <hip/hip_runtime.h>
 
 #include <cmath>
@@ -30,6 +32,7 @@ struct FmArgs {
     float scale, dscale; int train; float* gxp; int K1p; float* p_out; float* loss_t; float* gb_part; int* err;
     bool wt;                   // gx' written through (see store4_wt in fnn_kernels.hip.h)
     int* stamp; int step;      // Adam / FTRL: stamp[row] = step for every row the batch touches (null: not kept)
+    int rw;                    // wide rows (fm_wide_body): the row stride in floats, a multiple of 4; gx' is [t][F][rw]
 };
 
 __device__ __forceinline__ void fm_body(const FmArgs& a, const int blk, float* s_gb)
@@ -93,6 +96,91 @@ __global__ __launch_bounds__(256) void k_fm(const FmArgs a)
     __shared__ float s_gb[16];
     fm_body(a, blockIdx.x, s_gb);
 }
+// Wide rows (k >= 17): L lanes per example (16 while the row's rw / 4 float4 pieces fit, else 32); lane q owns columns 4q..4q+3
+// of every field's row and issues its example's F row loads together, so that S_l = sum_f v_f[l] is a register sum and only
+// the example's scalar b + lin + 1/2 sum_l (S_l^2 - sum_f v_f[l]^2) crosses lanes.  Lane f < F reads, checks and stamps field
+// f's id.  gx'[t][f] = delta * [1 | S - v_f], zero in the padding columns (>= K); absent fields are not written (no record
+// points at them).
+template <int L>
+__device__ __forceinline__ void fm_wide_body(const FmArgs& a, const int blk, float* s_gb /*[256 / L]*/)
+{
+    constexpr int EPB = 256 / L;                          // examples per workgroup
+    const int tid = threadIdx.x, q = tid % L, grp = tid / L, nq = a.rw >> 2;
+    const int t = blk * EPB + grp;
+    int mine = -1;
+    if (t < a.B && q < a.F) {
+        const int64_t id = a.ids[(size_t)t * a.F + q];
+        if (id < -1 || id >= a.n_rows) atomicOr(a.err, 1);
+        else mine = (int)id;
+        if (a.stamp && mine >= 0) a.stamp[mine] = a.step;
+    }
+    int id[16];
+    float4 v[16];
+#pragma unroll
+    for (int f = 0; f < 16; ++f) {
+        id[f] = __shfl(mine, f, L);                       // -1 for f >= F
+        v[f] = (id[f] >= 0 && q < nq) ? *reinterpret_cast<const float4*>(a.table16 + (size_t)id[f] * a.rw + 4 * q)
+                                      : make_float4(0.f, 0.f, 0.f, 0.f);
+    }
+    float lin = 0.f;
+    float4 S = make_float4(0.f, 0.f, 0.f, 0.f), sq = S;
+#pragma unroll
+    for (int f = 0; f < 16; ++f) {
+        v[f].x *= a.scale; v[f].y *= a.scale; v[f].z *= a.scale; v[f].w *= a.scale;
+        if (q == 0) { lin += v[f].x; v[f].x = 0.f; }      // column 0 is w_f
+        S.x += v[f].x; S.y += v[f].y; S.z += v[f].z; S.w += v[f].w;
+        sq.x = fmaf(v[f].x, v[f].x, sq.x); sq.y = fmaf(v[f].y, v[f].y, sq.y);
+        sq.z = fmaf(v[f].z, v[f].z, sq.z); sq.w = fmaf(v[f].w, v[f].w, sq.w);
+    }
+    // yhat = b + sum_f w_f + 1/2 (sum_l S_l^2 - sum_f sum_l v_f[l]^2)                     (:56-63)
+    float part = lin + 0.5f * ((fmaf(S.x, S.x, -sq.x) + fmaf(S.y, S.y, -sq.y)) + (fmaf(S.z, S.z, -sq.z) + fmaf(S.w, S.w, -sq.w)));
+#pragma unroll
+    for (int o = 1; o < L; o <<= 1) part += __shfl_xor(part, o, L);
+    const float z = *a.b + part;
+    const float p = 1.0f / (1.0f + expf(-z));
+    float delta = 0.f;
+    if (t < a.B) {
+        if (a.p_out && q == 0) a.p_out[t] = p;
+        if (a.train) {
+            const float yy = a.y[t];
+            delta = (p - yy) * a.dscale;                         // dscale = 1 (sum) or 1/B (mean)
+            if (q == 0) a.loss_t[t] = fmaxf(z, 0.f) - z * yy + log1pf(expf(-fabsf(z)));
+        }
+    } else if (a.train && q == 0) a.loss_t[t] = 0.f;
+    if (!a.train) return;
+    // d yhat / d w_f = 1 ; d yhat / d v_f[l] = S_l - v_f[l]   (x = 1)
+    if (q < nq) {
+        const int c = 4 * q;
+        float* out = a.gxp + (size_t)t * a.K1p + c;
+#pragma unroll
+        for (int f = 0; f < 16; ++f) {
+            if (id[f] < 0) continue;
+            const float4 g = make_float4(c == 0 ? delta : (c < a.K ? delta * (S.x - v[f].x) : 0.f),
+                                         c + 1 < a.K ? delta * (S.y - v[f].y) : 0.f,
+                                         c + 2 < a.K ? delta * (S.z - v[f].z) : 0.f,
+                                         c + 3 < a.K ? delta * (S.w - v[f].w) : 0.f);
+            store16_sel(a.wt, out + (size_t)f * a.rw, g);
+        }
+    }
+    if (q == 0) s_gb[grp] = delta;
+    __syncthreads();
+    if (tid == 0) { float s = 0.f; for (int i = 0; i < EPB; ++i) s += s_gb[i]; a.gb_part[blk] = s; }
+}
+template <int L>
+__global__ __launch_bounds__(256) void k_fm_wide(const FmArgs a)
+{
+    __shared__ float s_gb[256 / L];
+    fm_wide_body<L>(a, blockIdx.x, s_gb);
+}
+template <typename KT, int L>
+__global__ __launch_bounds__(256) void k_fm_wide_merge_fwd(const SortArgs so, const FmArgs a)
+{
+    extern __shared__ __align__(16) unsigned char smem[];
+    __shared__ float s_gb[256 / L];
+    if ((int)blockIdx.x < so.nblk) { sortB_body<KT>(so, blockIdx.x, smem); return; }
+    fm_wide_body<L>(a, (int)blockIdx.x - so.nblk, s_gb);
+}
+
 // A training step is four launches: run sorts of the batch's (row, t) keys; their rank merge BESIDE the forward + gradients
 // (both need only the ids: the merge takes 16 F workgroups, the examples the rest); level-1 sparse-row update; level-2 update
 // BESIDE the bias / loss tail.  As six launches in a row (sort, sort, forward, scatter, scatter, tail) the step took 49.6 us.
@@ -137,6 +225,15 @@ __global__ __launch_bounds__(256) void k_fm_scat2_tail(const ScatArgs sa, float*
     if (blockIdx.x == 0) { fm_tail_body(b, gb_part, n, lr, lambda, loss_t, Ba, lscale, loss_out, reinterpret_cast<float*>(&s_sum[0][0]), bo); return; }
     scat2_body(sa, (int)blockIdx.x - 1, (int)gridDim.x - 1, s_sum);
 }
+// the same for wide rows: level 1 on its own, level 2 (8 KiB of LDS) beside the tail
+__global__ __launch_bounds__(256) void k_fm_scatw1(const ScatArgs sa) { scatw1_body(sa, blockIdx.x); }
+__global__ __launch_bounds__(256) void k_fm_scatw2_tail(const ScatArgs sa, float* b, const float* gb_part, int n, float lr, float lambda,
+                                                        const float* loss_t, int Ba, float lscale, float* loss_out, const FmBiasOpt bo)
+{
+    __shared__ double s_w[1024];
+    if (blockIdx.x == 0) { fm_tail_body(b, gb_part, n, lr, lambda, loss_t, Ba, lscale, loss_out, reinterpret_cast<float*>(s_w), bo); return; }
+    scatw2_body(sa, (int)blockIdx.x - 1, (int)gridDim.x - 1, s_w);
+}
 
 __global__ void k_fm_rescale(float* table16, size_t n, float s)
 {
@@ -153,12 +250,12 @@ __global__ void k_fm_fill(float* p, size_t n, float v)
 // Adam / FTRL on the table: the L2 term makes TensorFlow's gradient DENSE, so every live element (row < n_rows, column < K)
 // moves each step: g = G + lambda w, the optimiser, w and both state values written back.  The state is compact [n_rows, K]
 // (s0 / s1 rounded up to a multiple of 4 floats): a thread owns 4 consecutive elements of it -- one 16-byte access per state
-// array -- and the matching 4 table / G elements at their padded-row addresses; padding columns are never touched.
+// array -- and the matching 4 table / G elements at their padded-row addresses (row stride rw); padding columns are never touched.
 // G (the batch's per-row gradient sums, padded rows) is read and cleared only where it was written: DENSE_G = false reads a
 // row's G when stamp[row] == step (the rows this step's forward touched); DENSE_G = true reads and clears every element of G.
 template <bool DENSE_G>
 __global__ __launch_bounds__(256) void k_fm_opt_pass(float* __restrict__ table16, float* __restrict__ G, const int* __restrict__ stamp, int step,
-                                                     float* __restrict__ s0, float* __restrict__ s1, size_t nk, int K, float lambda,
+                                                     float* __restrict__ s0, float* __restrict__ s1, size_t nk, int K, int rw, float lambda,
                                                      int opt, float lr, float b1, float b2, float eps)
 {
     const size_t e0 = ((size_t)blockIdx.x * blockDim.x + threadIdx.x) * 4;
@@ -172,7 +269,7 @@ __global__ __launch_bounds__(256) void k_fm_opt_pass(float* __restrict__ table16
 #pragma unroll
     for (int j = 0; j < 4; ++j) {                      // every load first, then the arithmetic, then the stores
         live[j] = e0 + j < nk;
-        off[j] = row * SLOT + c;
+        off[j] = row * rw + c;
         w[j] = live[j] ? table16[off[j]] : 0.f;
         hit[j] = live[j] && (DENSE_G || stamp[row] == step);
         g[j] = hit[j] ? G[off[j]] : 0.f;
@@ -194,11 +291,14 @@ __global__ __launch_bounds__(256) void k_fm_opt_pass(float* __restrict__ table16
 struct fm_handle {
     std::string err; int dev = 0; hipStream_t st = nullptr; bool own_stream = false;
     int F = 0, K = 0, Bmax = 0, K1p = 0;
+    bool wide = false;         // k >= 17: wide rows (fm_wide_body, scatw1_body / scatw2_body)
+    int rw = SLOT;             // row stride in floats: SLOT for k <= 16, rup(k, 4) on the wide path
+    int* noshare = nullptr;    // wide path: [n_rows] zeros, the scatter's tag_shared (every row takes the plain read-modify-write)
     float* table16 = nullptr; int64_t n_rows = 0; float* b = nullptr; double scale = 1.0;
     float *gxp = nullptr, *loss_t = nullptr, *gb_part = nullptr, *loss_dev = nullptr; int* err_flag = nullptr;
     int4* rec = nullptr; double* part = nullptr; int4* owners = nullptr; int* owner_cnt = nullptr; void* skeys = nullptr;
     double* cpow1 = nullptr; bool key64 = true;
-    // Adam / FTRL (fm_set_optimizer): compact state s0 / s1 [n_rows, K], the bias's sb [2], gradient store G [n_rows, SLOT],
+    // Adam / FTRL (fm_set_optimizer): compact state s0 / s1 [n_rows, K], the bias's sb [2], gradient store G [n_rows, rw],
     // stamp [n_rows]; t = steps since the state was initialised.  dense_g: FM_OPT_DENSE_G=1, the A/B variant of k_fm_opt_pass.
     int opt = FM_OPT_SGD; float beta1 = 0.9f, beta2 = 0.999f, eps = 1e-8f; int64_t t = 0; bool dense_g = false;
     float *s0 = nullptr, *s1 = nullptr, *sb = nullptr, *G = nullptr; int* stamp = nullptr;
@@ -212,7 +312,7 @@ namespace {
 int fold_scale(fm_handle* h)          // fold the lazy decay back into the rows
 {
     if (h->scale == 1.0 || !h->table16) return FNN_OK;
-    const size_t n = (size_t)h->n_rows * SLOT;
+    const size_t n = (size_t)h->n_rows * h->rw;
     hipLaunchKernelGGL(k_fm_rescale, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, h->st, h->table16, n, (float)h->scale);
     MHK(h, hipGetLastError());
     h->scale = 1.0;
@@ -233,14 +333,76 @@ int init_opt_state(fm_handle* h)
     if (!h->table16) return FNN_OK;
     const size_t n = opt_state_len(h);
     MHK(h, hipMalloc((void**)&h->s0, n * 4)); MHK(h, hipMalloc((void**)&h->s1, n * 4));
-    MHK(h, hipMalloc((void**)&h->G, (size_t)h->n_rows * SLOT * 4)); MHK(h, hipMalloc((void**)&h->stamp, (size_t)h->n_rows * 4));
-    MHK(h, hipMemsetAsync(h->s1, 0, n * 4, h->st)); MHK(h, hipMemsetAsync(h->G, 0, (size_t)h->n_rows * SLOT * 4, h->st));
+    MHK(h, hipMalloc((void**)&h->G, (size_t)h->n_rows * h->rw * 4)); MHK(h, hipMalloc((void**)&h->stamp, (size_t)h->n_rows * 4));
+    MHK(h, hipMemsetAsync(h->s1, 0, n * 4, h->st)); MHK(h, hipMemsetAsync(h->G, 0, (size_t)h->n_rows * h->rw * 4, h->st));
     MHK(h, hipMemsetAsync(h->stamp, 0, (size_t)h->n_rows * 4, h->st));
     if (h->opt == FM_OPT_FTRL) hipLaunchKernelGGL(k_fm_fill, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, h->st, h->s0, n, 0.1f);
     else MHK(h, hipMemsetAsync(h->s0, 0, n * 4, h->st));
     MHK(h, hipGetLastError());
     MHK(h, hipStreamSynchronize(h->st));
     return FNN_OK;
+}
+
+// The wide path's forward: L = 16 lanes per example while a row's float4 pieces fit (rank <= 63), else 32; 256 / L examples
+// per workgroup.
+int wide_epb(const fm_handle* h) { return h->rw <= 64 ? 16 : 8; }
+template <typename KT>
+void launch_wide_fwd(const fm_handle* h, const SortArgs* sb, const FmArgs& a, int B)
+{
+    const bool l16 = wide_epb(h) == 16;
+    const int nb = rup(B, wide_epb(h)) / wide_epb(h);
+    if (!sb) {
+        if (l16) hipLaunchKernelGGL(k_fm_wide<16>, dim3(nb), dim3(256), 0, h->st, a);
+        else hipLaunchKernelGGL(k_fm_wide<32>, dim3(nb), dim3(256), 0, h->st, a);
+    } else if (l16) {
+        hipLaunchKernelGGL((k_fm_wide_merge_fwd<KT, 16>), dim3(sb->nblk + nb), dim3(256), sort_lds_bytes<KT>(), h->st, *sb, a);
+    } else {
+        hipLaunchKernelGGL((k_fm_wide_merge_fwd<KT, 32>), dim3(sb->nblk + nb), dim3(256), sort_lds_bytes<KT>(), h->st, *sb, a);
+    }
+}
+
+// The wide step (k >= 17): the same sort, forward + gradients beside the rank merge (k_fm_wide_merge_fwd), then the bag table's
+// wide sparse-row update -- level 1, level 2 beside the bias / loss tail -- into the rows (SGD) or the gradient store G.
+int fm_run_wide(fm_handle* h, FmArgs a, int B, float lr, float lambda, int reduce_mean, bool opt, float lr_step)
+{
+    const int F = h->F, ex = wide_epb(h), Ba = rup(B, ex);
+    if (!a.train) {
+        launch_wide_fwd<unsigned>(h, nullptr, a, B);
+        MHK(h, hipGetLastError());
+        return FNN_OK;
+    }
+    SortArgs so{a.ids, B, F, h->n_rows, h->rec, h->owner_cnt, 4 * F, h->skeys};
+    SortArgs sb = so; sb.nblk = 16 * F;
+    if (h->key64) {
+        hipLaunchKernelGGL((k_sortA<unsigned long long>), dim3(4 * F), dim3(256), 0, h->st, so);
+        launch_wide_fwd<unsigned long long>(h, &sb, a, B);
+    } else {
+        hipLaunchKernelGGL((k_sortA<unsigned>), dim3(4 * F), dim3(256), 0, h->st, so);
+        launch_wide_fwd<unsigned>(h, &sb, a, B);
+    }
+    // SGD: the dense decay is the lazy scale, touched rows -= lr * g / scale; Adam / FTRL: G[row] = G[row] - (-1) * sum
+    if (!opt) h->scale *= 1.0 - (double)lr * (double)lambda;
+    ScatArgs sa{h->rec, SORT_N, F, h->K, h->gxp, h->K1p, h->cpow1, opt ? -1.0 : (double)lr / h->scale, opt ? h->G : h->table16,
+                h->part, h->owner_cnt, h->owners, h->rw, h->noshare, 1, h->rw};
+    const int nthr = F * (SORT_N / WCH) * (h->rw / 4);
+    hipLaunchKernelGGL(k_fm_scatw1, dim3((nthr + 255) / 256), dim3(256), 0, h->st, sa);
+    hipLaunchKernelGGL(k_fm_scatw2_tail, dim3(1 + 256), dim3(256), 0, h->st, sa, h->b, h->gb_part, Ba / ex, lr, lambda, h->loss_t, Ba,
+                       reduce_mean ? 1.0f / (float)B : 1.0f, h->loss_dev,
+                       opt ? FmBiasOpt{h->opt, h->sb, lr_step, h->beta1, h->beta2, h->eps} : FmBiasOpt{FM_OPT_SGD, nullptr, 0.f, 0.f, 0.f, 0.f});
+    MHK(h, hipGetLastError());
+    return FNN_OK;
+}
+
+void launch_opt_pass(fm_handle* h, float lambda, float lr_step)
+{
+    const size_t nk = (size_t)h->n_rows * h->K;
+    const dim3 grid((unsigned)(((nk + 3) / 4 + 255) / 256));
+    if (h->dense_g)
+        hipLaunchKernelGGL(k_fm_opt_pass<true>, grid, dim3(256), 0, h->st, h->table16, h->G, h->stamp, (int)h->t, h->s0, h->s1, nk, h->K,
+                           h->rw, lambda, h->opt, lr_step, h->beta1, h->beta2, h->eps);
+    else
+        hipLaunchKernelGGL(k_fm_opt_pass<false>, grid, dim3(256), 0, h->st, h->table16, h->G, h->stamp, (int)h->t, h->s0, h->s1, nk, h->K,
+                           h->rw, lambda, h->opt, lr_step, h->beta1, h->beta2, h->eps);
 }
 
 int fm_run(fm_handle* h, const int32_t* ids, const float* y, int B, float lr, float lambda, int reduce_mean, float* p_out, bool train)
@@ -256,7 +418,14 @@ int fm_run(fm_handle* h, const int32_t* ids, const float* y, int B, float lr, fl
     }
     FmArgs a{ids, y, B, F, h->K, h->table16, h->n_rows, h->b, (float)h->scale, reduce_mean ? 1.0f / (float)B : 1.0f, train ? 1 : 0,
              h->gxp, h->K1p, p_out, h->loss_t, h->gb_part, h->err_flag, !(getenv("FM_WT") && atoi(getenv("FM_WT")) == 0),
-             opt && !h->dense_g ? h->stamp : nullptr, (int)h->t};
+             opt && !h->dense_g ? h->stamp : nullptr, (int)h->t, h->rw};
+    if (h->wide) {
+        const int rc = fm_run_wide(h, a, B, lr, lambda, reduce_mean, opt, lr_step);
+        if (rc != FNN_OK) return rc;
+        if (opt) { launch_opt_pass(h, lambda, lr_step); MHK(h, hipGetLastError()); return FNN_OK; }
+        if (train && (h->scale < 5.96e-8 || h->scale > 1.0)) return fold_scale(h);
+        return FNN_OK;
+    }
     if (!train) {
         hipLaunchKernelGGL(k_fm, dim3(Ba / 16), dim3(256), 0, h->st, a);
         MHK(h, hipGetLastError());
@@ -278,14 +447,7 @@ int fm_run(fm_handle* h, const int32_t* ids, const float* y, int B, float lr, fl
         hipLaunchKernelGGL(k_scat1, dim3(F * SORT_N / 256), dim3(256), 0, h->st, sa);
         hipLaunchKernelGGL(k_fm_scat2_tail, dim3(1 + 256), dim3(256), 0, h->st, sa, h->b, h->gb_part, Ba / 16, lr, lambda, h->loss_t, Ba,
                            reduce_mean ? 1.0f / (float)B : 1.0f, h->loss_dev, FmBiasOpt{h->opt, h->sb, lr_step, h->beta1, h->beta2, h->eps});
-        const size_t nk = (size_t)h->n_rows * h->K;
-        const dim3 grid((unsigned)(((nk + 3) / 4 + 255) / 256));
-        if (h->dense_g)
-            hipLaunchKernelGGL(k_fm_opt_pass<true>, grid, dim3(256), 0, h->st, h->table16, h->G, h->stamp, (int)h->t, h->s0, h->s1, nk, h->K,
-                               lambda, h->opt, lr_step, h->beta1, h->beta2, h->eps);
-        else
-            hipLaunchKernelGGL(k_fm_opt_pass<false>, grid, dim3(256), 0, h->st, h->table16, h->G, h->stamp, (int)h->t, h->s0, h->s1, nk, h->K,
-                               lambda, h->opt, lr_step, h->beta1, h->beta2, h->eps);
+        launch_opt_pass(h, lambda, lr_step);
         MHK(h, hipGetLastError());
         return FNN_OK;
     }
@@ -311,21 +473,25 @@ int fm_create(int n_fields, int k, int max_batch, int device, void* stream, fm_h
 {
     if (!out) { g_fm_err = "null argument"; return FNN_ERR_ARG; }
     *out = nullptr;
-    if (n_fields < 1 || n_fields > 16 || k < 1 || k > 16 || max_batch < 1 || max_batch > SORT_N) {
-        g_fm_err = "need 1 <= n_fields <= 16, 1 <= k <= 16, 1 <= max_batch <= 4096"; return FNN_ERR_ARG; }
+    if (n_fields < 1 || n_fields > 16 || k < 1 || k > 128 || max_batch < 1 || max_batch > SORT_N) {
+        g_fm_err = "need 1 <= n_fields <= 16, 1 <= k <= 128 (rank 0..127), 1 <= max_batch <= 4096"; return FNN_ERR_ARG; }
     int ndev = 0;
     if (hipGetDeviceCount(&ndev) != hipSuccess || ndev <= 0) { g_fm_err = "no HIP device (libfnn_hip.so has no CPU fallback)"; return FNN_ERR_HIP; }
     fm_handle* h = new fm_handle();
-    h->dev = device; h->F = n_fields; h->K = k; h->Bmax = max_batch; h->K1p = 16 * SLOT;
+    h->dev = device; h->F = n_fields; h->K = k; h->Bmax = max_batch;
+    h->wide = k > 16; h->rw = h->wide ? rup(k, 4) : SLOT;
+    h->K1p = h->wide ? n_fields * h->rw : 16 * SLOT;                // gx' of an example: 16 slots, or [F][rw] on the wide path
     auto fail = [&](int code) { g_fm_err = h->err; fm_destroy(h); return code; };
 #define FK(expr) do { hipError_t e2_ = (expr); if (e2_ != hipSuccess) { h->err = std::string(#expr) + ": " + hipGetErrorString(e2_); return fail(FNN_ERR_HIP); } } while (0)
     FK(hipSetDevice(h->dev));
     if (stream) h->st = (hipStream_t)stream; else { FK(hipStreamCreateWithFlags(&h->st, hipStreamNonBlocking)); h->own_stream = true; }
     auto al = [&](void** p, size_t bytes) { hipError_t e = hipMalloc(p, bytes); if (e == hipSuccess) e = hipMemsetAsync(*p, 0, bytes, h->st); return e; };
     const size_t Ba = rup(h->Bmax, 16);
-    FK(al((void**)&h->gxp, Ba * h->K1p * 4)); FK(al((void**)&h->loss_t, Ba * 4)); FK(al((void**)&h->gb_part, (Ba / 16) * 4));
+    FK(al((void**)&h->gxp, Ba * h->K1p * 4)); FK(al((void**)&h->loss_t, Ba * 4)); FK(al((void**)&h->gb_part, (Ba / 8) * 4));
     FK(al((void**)&h->loss_dev, 4)); FK(al((void**)&h->b, 4)); FK(al((void**)&h->err_flag, 4)); FK(al((void**)&h->sb, 8));
-    FK(al((void**)&h->rec, (size_t)h->F * SORT_N * sizeof(int4))); FK(al((void**)&h->part, (size_t)h->F * (SORT_N / 16) * 2 * SLOT * 8));
+    // level-1 partial sums: two per chunk of 16 (narrow) or WCH (wide) sorted entries, a row each
+    const size_t part_rows = h->wide ? (size_t)h->F * (SORT_N / WCH) * 2 : (size_t)h->F * (SORT_N / 16) * 2;
+    FK(al((void**)&h->rec, (size_t)h->F * SORT_N * sizeof(int4))); FK(al((void**)&h->part, part_rows * h->rw * 8));
     FK(al((void**)&h->owners, (size_t)h->F * (SORT_N / 16) * sizeof(int4))); FK(al((void**)&h->owner_cnt, 4));
     FK(al(&h->skeys, (size_t)h->F * SORT_N * 8));
     {
@@ -346,7 +512,7 @@ int fm_destroy(fm_handle* h)
     hipSetDevice(h->dev);
     if (h->st) hipStreamSynchronize(h->st);
     void* ptrs[] = {h->table16, h->b, h->gxp, h->loss_t, h->gb_part, h->loss_dev, h->err_flag, h->rec, h->part, h->owners, h->owner_cnt,
-                    h->skeys, h->cpow1, h->s0, h->s1, h->sb, h->G, h->stamp};
+                    h->skeys, h->cpow1, h->s0, h->s1, h->sb, h->G, h->stamp, h->noshare};
     for (void* p : ptrs) if (p) hipFree(p);
     if (h->own_stream && h->st) hipStreamDestroy(h->st);
     delete h;
@@ -369,12 +535,17 @@ int fm_set_table(fm_handle* h, const float* rows, int64_t n_rows)
     MHK(h, hipSetDevice(h->dev));
     MHK(h, hipStreamSynchronize(h->st));
     if (h->table16) { hipFree(h->table16); h->table16 = nullptr; }
-    MHK(h, hipMalloc((void**)&h->table16, (size_t)n_rows * SLOT * 4));
+    if (h->noshare) { hipFree(h->noshare); h->noshare = nullptr; }
+    MHK(h, hipMalloc((void**)&h->table16, (size_t)n_rows * h->rw * 4));
+    if (h->wide) {
+        MHK(h, hipMalloc((void**)&h->noshare, (size_t)n_rows * 4));
+        MHK(h, hipMemsetAsync(h->noshare, 0, (size_t)n_rows * 4, h->st));
+    }
     float* tmp = nullptr;
     MHK(h, hipMalloc((void**)&tmp, (size_t)n_rows * h->K * 4));
     MHK(h, hipMemcpy(tmp, rows, (size_t)n_rows * h->K * 4, hipMemcpyHostToDevice));
-    const size_t n = (size_t)n_rows * SLOT;
-    hipLaunchKernelGGL(k_pack_table, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, h->st, tmp, n_rows, h->K, SLOT, h->table16);
+    const size_t n = (size_t)n_rows * h->rw;
+    hipLaunchKernelGGL(k_pack_table, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, h->st, tmp, n_rows, h->K, h->rw, h->table16);
     MHK(h, hipStreamSynchronize(h->st));
     hipFree(tmp);
     h->n_rows = n_rows; h->scale = 1.0;
@@ -392,7 +563,7 @@ static int fm_rows(fm_handle* h, const int64_t* row_ids, int64_t n, float* out)
     if (row_ids) { MHK(h, hipMalloc((void**)&di, n * 8)); MHK(h, hipMemcpy(di, row_ids, n * 8, hipMemcpyHostToDevice)); }
     MHK(h, hipMalloc((void**)&dout, (size_t)n * h->K * 4));
     const size_t cnt = (size_t)n * h->K;
-    hipLaunchKernelGGL(k_unpack_rows, dim3((unsigned)((cnt + 255) / 256)), dim3(256), 0, h->st, h->table16, di, n, h->n_rows, h->K, SLOT,
+    hipLaunchKernelGGL(k_unpack_rows, dim3((unsigned)((cnt + 255) / 256)), dim3(256), 0, h->st, h->table16, di, n, h->n_rows, h->K, h->rw,
                        dout, h->err_flag);
     MHK(h, hipMemcpyAsync(out, dout, cnt * 4, hipMemcpyDeviceToHost, h->st));
     rc = fm_sync(h);

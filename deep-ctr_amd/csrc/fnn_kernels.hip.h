@@ -1688,6 +1688,7 @@ struct ScatArgs {
     float* table16; double* part; int* owner_cnt; int4* owners;
     int rw;          // 16: FM rows (decayed update); otherwise the bag-table row width (plain sum)
     const int* tag_shared; int stamp;     // bag mode: tag_shared[row] == stamp <=> the row sits in several columns of this batch (SortArgs)
+    int gxf;         // wide update (scatw*): floats between two fields' gradients of an example (wide FM rows: rw); 0: one per example (bag)
 };
 // bag rows held by several columns of a batch: every column adds its sum with float atomics (a row touched by one column
 // only -- the rule on iPinYou lines -- keeps the plain read-modify-write, one rounding)
@@ -1797,7 +1798,8 @@ static __global__ __launch_bounds__(256) void k_scat2(const ScatArgs sa)
 // Sparse-row update of the bag table (python/SNN_RBM.py:285-291): ww0[f] -= lr * delta_t for
 // every example t that has feature f; no decay, so a row's result is row - lr * (sum of its
 // deltas) in example order.  Same sorted records as the FM path; rows are rw floats wide, so a
-// thread owns one 16-byte quarter-column of a chunk of 8 sorted entries.
+// thread owns one 16-byte quarter-column of a chunk of 8 sorted entries.  The wide FM rows (k >= 17, fm_api.hip) take the
+// same update with one gradient row per (example, field): ScatArgs::gxf.
 // ------------------------------------------------------------------------------------------
 constexpr int WCH = 32;          // sorted entries per chunk on the wide path (4 sub-batches of 8 loads)
 
@@ -1827,7 +1829,7 @@ __device__ __forceinline__ void scatw1_body(const ScatArgs& sa, const int blk)
 #pragma unroll
         for (int j = 0; j < 8; ++j) {
             const bool live = r[j].x >= 0;
-            g[j] = *reinterpret_cast<const float4*>(sa.gxp + (size_t)(live ? r[j].y : 0) * sa.K1p + 4 * q);
+            g[j] = *reinterpret_cast<const float4*>(sa.gxp + (size_t)(live ? r[j].y : 0) * sa.K1p + (size_t)f * sa.gxf + 4 * q);
             // the old row is read only where it is written: at the last entry of a segment that lies inside this chunk
             const int pos = base + sb + j;
             const bool need = live && pos + 1 == r[j].w && r[j].z >= base;

@@ -5,11 +5,16 @@ and the bytes the Adam / FTRL optimiser pass (k_fm_opt_pass in fm_api.hip) must 
   python tools/fm_optim_bench.py --from-stats NAME=DIR ..    (kernel times of separate rocprofv3 --kernel-trace --stats runs,
                                                               one config each: the pass time and its TB/s)
 
+  python tools/fm_optim_bench.py --only fm_sgd --digest        (adds a sha256 of the table, bias and optimiser state after the
+                                                              timed steps: two builds of the library, FNN_HIP_LIB, compared bit for bit)
+
 Configurations: fm_sgd / fm_adam / fm_ftrl (rank 10), lr_ftrl (rank 0 = LR); *_dense: the A/B variant of the pass that reads and
-clears the whole gradient store G (FM_OPT_DENSE_G=1) instead of the rows the step's stamp marks."""
+clears the whole gradient store G (FM_OPT_DENSE_G=1) instead of the rows the step's stamp marks.  The wide path (k >= 17):
+fm50_* / fm100_* (the reference's FM50 / FM100), and fm100_adam_b100 at python/baseline.py's FM batch of 100."""
 import argparse
 import ctypes as C
 import glob
+import hashlib
 import json
 import os
 import sys
@@ -19,8 +24,8 @@ import numpy as np
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 F, SLOT = 16, 16
-# name: (rank, optimizer (FM_OPT_*), lr, lambda, reduce_mean, dense G) -- python/baseline.py's recipes: FM Adam 1e-4 / eps 1e-8 /
-# 'sum' / lambda 1e-3, LR FTRL 1e-3 / lambda 1e-4; SGD as bench.py's pretrain leg
+# name: (rank, optimizer (FM_OPT_*), lr, lambda, reduce_mean, dense G[, batch]) -- python/baseline.py's recipes: FM Adam 1e-4 /
+# eps 1e-8 / 'sum' / lambda 1e-3, LR FTRL 1e-3 / lambda 1e-4; SGD as bench.py's pretrain leg.  No batch: --batch.
 CONFIGS = {
     'fm_sgd': (10, 0, 1e-4, 1e-6, 1, False),
     'fm_adam': (10, 1, 1e-4, 1e-3, 0, False),
@@ -29,7 +34,24 @@ CONFIGS = {
     'fm_ftrl_dense': (10, 2, 1e-3, 1e-3, 1, True),
     'lr_ftrl': (0, 2, 1e-3, 1e-4, 1, False),
     'lr_ftrl_dense': (0, 2, 1e-3, 1e-4, 1, True),
+    'fm50_sgd': (50, 0, 1e-4, 1e-6, 1, False),
+    'fm50_adam': (50, 1, 1e-4, 1e-3, 0, False),
+    'fm50_ftrl': (50, 2, 1e-3, 1e-3, 1, False),
+    'fm100_sgd': (100, 0, 1e-4, 1e-6, 1, False),
+    'fm100_adam': (100, 1, 1e-4, 1e-3, 0, False),
+    'fm100_ftrl': (100, 2, 1e-3, 1e-3, 1, False),
+    'fm100_adam_b100': (100, 1, 1e-4, 1e-3, 0, False, 100),
 }
+
+
+def rup4(k):
+    return (k + 3) // 4 * 4
+
+
+def fwd_bytes(B, K):
+    """What the wide forward (k_fm_wide_merge_fwd's example role) must move: the B * F rows of rup(K, 4) floats read once and
+    the gradients gx' [B, F, rup(K, 4)] written (the level-1 update reads them back).  Ids, labels and outputs: < 0.1 %."""
+    return 2 * B * F * rup4(K) * 4
 
 
 def pass_bytes(n_rows, K, dense):
@@ -46,7 +68,25 @@ def shape():
     return sizes, sum(sizes)
 
 
-def run(names, steps, warmup, B):
+def digest(lib, h, D, K, opt):
+    """sha256 of the table, the bias and (Adam / FTRL) both state tensors and the bias's state, as the library returns them."""
+    hs = hashlib.sha256()
+    rows = np.empty((D, K), np.float32)
+    b = C.c_float()
+    if lib.fm_get_table(h, rows.ctypes.data) != 0 or lib.fm_get_b(h, C.byref(b)) != 0:
+        raise RuntimeError(lib.fm_last_error(h).decode())
+    hs.update(rows.tobytes())
+    hs.update(np.float32(b.value).tobytes())
+    if opt:
+        s0, s1, sb, t = np.empty((D, K), np.float32), np.empty((D, K), np.float32), np.empty(2, np.float32), C.c_int64()
+        if lib.fm_get_opt_state(h, s0.ctypes.data, s1.ctypes.data, sb.ctypes.data, C.byref(t)) != 0:
+            raise RuntimeError(lib.fm_last_error(h).decode())
+        for a in (s0, s1, sb):
+            hs.update(a.tobytes())
+    return hs.hexdigest()
+
+
+def run(names, steps, warmup, B0, want_digest=False):
     import torch
     sizes, D = shape()
     from deep_ctr_amd import _capi, synth
@@ -54,11 +94,12 @@ def run(names, steps, warmup, B):
     dev = torch.device('cuda', 0)
     stream = torch.cuda.Stream(device=dev)
     NB = 16
-    ids = torch.as_tensor(synth.zipf_ids(NB * B, sizes, 1.1, 99)).to(dev).contiguous()
-    y = torch.as_tensor((np.random.RandomState(3).uniform(size=NB * B) < 0.02).astype(np.float32)).to(dev)
     out = {}
     for name in names:
-        rank, opt, lr, lam, mean, dense = CONFIGS[name]
+        rank, opt, lr, lam, mean, dense = CONFIGS[name][:6]
+        B = CONFIGS[name][6] if len(CONFIGS[name]) > 6 else B0
+        ids = torch.as_tensor(synth.zipf_ids(NB * B, sizes, 1.1, 99)).to(dev).contiguous()
+        y = torch.as_tensor((np.random.RandomState(3).uniform(size=NB * B) < 0.02).astype(np.float32)).to(dev)
         K = rank + 1
         os.environ['FM_OPT_DENSE_G'] = '1' if dense else '0'        # read by fm_create
         h = C.c_void_p()
@@ -82,24 +123,28 @@ def run(names, steps, warmup, B):
         if lib.fm_sync(h) != 0:
             raise RuntimeError(lib.fm_last_error(h).decode())
         dt = (time.perf_counter() - t0) / steps
+        r = {'batch': B, 'us_per_step': dt * 1e6, 'examples_per_sec': B / dt}
+        if want_digest:
+            r['sha256'] = digest(lib, h, D, K, opt)
         lib.fm_destroy(h)
-        r = {'us_per_step': dt * 1e6, 'examples_per_sec': B / dt}
         if opt:
             nb = pass_bytes(D, K, dense)
             r.update({'pass_bytes': nb, 'pass_bytes_tbps_at_step_time': nb / dt / 1e12})
         out[name] = r
-    return {'tool': 'fm_optim_bench', 'n_rows': D, 'fields': F, 'batch': B, 'steps': steps, 'warmup': warmup,
+    return {'tool': 'fm_optim_bench', 'n_rows': D, 'fields': F, 'batch': B0, 'steps': steps, 'warmup': warmup,
             'device': torch.cuda.get_device_name(0), 'configs': out}
 
 
 def from_stats(pairs):
-    """NAME=DIR: the k_fm_opt_pass row of the kernel-stats CSV rocprofv3 wrote under DIR."""
+    """NAME=DIR: the k_fm_opt_pass row (and on the wide path the k_fm_wide_merge_fwd row) of the kernel-stats CSV rocprofv3
+    wrote under DIR."""
     import csv
     _, D = shape()
     out = {}
     for pr in pairs:
         name, d = pr.split('=', 1)
-        rank, opt, _, _, _, dense = CONFIGS[name]
+        rank, opt, _, _, _, dense = CONFIGS[name][:6]
+        B = CONFIGS[name][6] if len(CONFIGS[name]) > 6 else 4096
         files = glob.glob(os.path.join(d, '**', '*kernel_stats.csv'), recursive=True)
         if not files:
             raise SystemExit('no kernel_stats.csv under %s' % d)
@@ -113,6 +158,11 @@ def from_stats(pairs):
             nb = pass_bytes(D, rank + 1, dense)
             r.update({'pass_us': p[0][1], 'pass_calls': p[0][0], 'pass_bytes': nb, 'pass_tbps': nb / (p[0][1] * 1e-6) / 1e12,
                       'share_of_6.29_tbps_copy': nb / (p[0][1] * 1e-6) / 6.29e12})
+        w = [v for k, v in kern.items() if 'k_fm_wide_merge_fwd' in k]
+        if w:       # the launch also runs the rank merge (16 F small workgroups): its time bounds the forward's from above
+            nb = fwd_bytes(B, rank + 1)
+            r.update({'wide_fwd_us': w[0][1], 'wide_fwd_bytes': nb, 'wide_fwd_tbps': nb / (w[0][1] * 1e-6) / 1e12,
+                      'wide_fwd_share_of_6.29_tbps_copy': nb / (w[0][1] * 1e-6) / 6.29e12})
         out[name] = r
     return {'tool': 'fm_optim_bench', 'kernel_stats': out}
 
@@ -124,6 +174,7 @@ def main():
     ap.add_argument('--batch', type=int, default=4096)
     ap.add_argument('--only', default=','.join(CONFIGS))
     ap.add_argument('--from-stats', nargs='+', default=None)
+    ap.add_argument('--digest', action='store_true')
     a = ap.parse_args()
     if a.from_stats:
         print(json.dumps(from_stats(a.from_stats)))
@@ -132,7 +183,7 @@ def main():
     for n in names:
         if n not in CONFIGS:
             raise SystemExit('unknown config %r (%s)' % (n, ', '.join(CONFIGS)))
-    print(json.dumps(run(names, a.steps, a.warmup, a.batch)))
+    print(json.dumps(run(names, a.steps, a.warmup, a.batch, a.digest)))
 
 
 if __name__ == '__main__':
