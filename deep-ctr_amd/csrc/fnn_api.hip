@@ -30,6 +30,7 @@ thread_local std::string g_create_err;
 struct ProfSlot { std::vector<std::pair<hipEvent_t, hipEvent_t>> ev; double ms = 0; int64_t n = 0; };
 
 inline int rup(int x, int m) { return (x + m - 1) / m * m; }
+constexpr int WIDE_XW_MAX = 4096;    // wide FM rows: largest n_fields * rup(k, 4) (16 fields x k = 128: 2048; 39 x k = 101: 4056)
 
 }  // namespace
 
@@ -50,6 +51,7 @@ struct fnn_handle {
     int step1_waves = 8;                                               // FNN_STEP1_WAVES=4: four waves per strip (the 2-byte element types at hidden 300 / 100 run eight)
     int wt_stores = 15;                                                // FNN_WT_STORES (MlpArgs::wt; 0: plain stores): how the strip kernel's training outputs leave
     bool bag = false; int rw = SLOT; size_t nbag = 0, off_bag = 0;     // FNN_MODE_BAG: bag rows rw floats wide
+    bool wide = false;          // FNN_MODE_FM with k >= 17: FM rows of rw = rup(k, 4) floats, w_0 / ones columns F*rw and F*rw + 1
     float* bb0 = nullptr; void* dlxT = nullptr; void* onesT = nullptr; float* gx_raw = nullptr;
     bool fused = true;          // one k_mlp launch instead of gather/fwd1/fwd2/head/bwd1/gx
     int role_off = 0;           // diagnostics only (FNN_ROLE_OFF): 1 sort, 2 dense, 4 sparse roles of launches 2/3 skipped
@@ -194,6 +196,7 @@ template <typename T> void launch_update(fnn_handle* h, const float* bucket, flo
 // the strip kernel is instantiated for the padded shapes in use; anything else takes the
 // layer-by-layer kernels
 bool mlp_shape_ok(const fnn_handle* h) {
+    if (h->wide) return false;                               // the strip kernel reads 16-float slots
     const int c1 = h->H1p / 64, c2 = h->H2p / 64, cx = h->K1p / 64;
     if (cx == 5) return h->bag && c1 == 5 && c2 == 2;        // bag rows 256..316 wide: the reference's default hidden0 = 300 (python/SNN_RBM.py:25)
     return cx == 4 && ((c1 == 5 && c2 == 2) || (c1 == 1 && c2 == 1));
@@ -475,7 +478,7 @@ int run_step_fast(fnn_handle* h, const int32_t* ids, const float* y, int B, cons
         if (h->bag) hipLaunchKernelGGL(k_copy_cols, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, h->st, h->gx_raw,
                                        h->K1p, B, h->xdim, gx_out_dev);
         else hipLaunchKernelGGL(k_gx_ref, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, h->st, h->gxp, h->K1p,
-                                B, h->F, h->K, gx_out_dev);
+                                B, h->F, h->K, SLOT, h->K, gx_out_dev);
     }
     h->pend_Ba = Ba; h->pend_have_next = have_next;
     if (update && h->dp) {
@@ -551,9 +554,15 @@ int run_step(fnn_handle* h, const int32_t* ids, const float* y, int B, const uin
     } else {
         {   // A3
             ProfScope ps(h, "gather", h->st);
-            const int nthreads = Ba * F;
-            hipLaunchKernelGGL((k_gather<T>), dim3((nthreads + 255) / 256), dim3(256), 0, h->st, ids, B, Ba,
-                               F, K, h->table16, h->n_rows, h->w0, xp, K1p, xpT, ldT, h->err_flag);
+            if (h->wide) {
+                const int nthreads = Ba / 4 * (K1p / 4);
+                hipLaunchKernelGGL((k_gather_wide<T>), dim3((nthreads + 255) / 256), dim3(256), 0, h->st, ids, B, Ba,
+                                   F, h->rw, h->table16, h->n_rows, h->w0, xp, K1p, xpT, ldT, h->err_flag);
+            } else {
+                const int nthreads = Ba * F;
+                hipLaunchKernelGGL((k_gather<T>), dim3((nthreads + 255) / 256), dim3(256), 0, h->st, ids, B, Ba,
+                                   F, K, h->table16, h->n_rows, h->w0, xp, K1p, xpT, ldT, h->err_flag);
+            }
         }
         {   // A4 layer 1: d1 = act(x' W1p) * r1
             ProfScope ps(h, "fwd1", h->st);
@@ -603,9 +612,23 @@ int run_step(fnn_handle* h, const int32_t* ids, const float* y, int B, const uin
     if (gx_out_dev) {
         const size_t n = (size_t)B * h->xdim;
         hipLaunchKernelGGL(k_gx_ref, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, h->st, h->gxp, K1p,
-                           B, F, K, gx_out_dev);
+                           B, F, K, h->rw, h->wide ? F * h->rw : K, gx_out_dev);
     }
-    const ScatArgs sa = make_scat_args(h, sl, N2);           // A6 part 2
+    ScatArgs sa = make_scat_args(h, sl, N2);                 // A6 part 2
+    if (h->wide) {                                           // rows of rw floats: chunks of WCH entries, a 16-byte piece per thread
+        sa.gxf = h->rw;
+        {
+            ProfScope ps(h, "scatter", h->st);
+            const size_t nthr = (size_t)F * (N2 / WCH) * (h->rw / 4);
+            hipLaunchKernelGGL(k_scatdw1, dim3((unsigned)((nthr + 255) / 256)), dim3(256), 0, h->st, sa);
+        }
+        {
+            ProfScope ps(h, "finalize", h->st);
+            hipLaunchKernelGGL(k_scatdw2, dim3(256), dim3(256), 0, h->st, sa);
+        }
+        HIPCHK(h, hipGetLastError());
+        return FNN_OK;
+    }
     {
         ProfScope ps(h, "scatter", h->st);
         const size_t nthr = (size_t)F * N2;                  // 16 lanes per chunk of 16 entries
@@ -631,9 +654,9 @@ int ensure_global_ws(fnn_handle* h, int B_g)
         for (void* q : {(void*)sl.rec, (void*)sl.part, (void*)sl.owners, (void*)sl.owner_cnt}) if (q) hipFree(q);
         sl = fnn_handle::SortSlot();
         int rc;
-        const size_t nchunk = (size_t)N2 / 16;
+        const size_t nchunk = h->wide ? (size_t)N2 / WCH : (size_t)N2 / 16;
         if ((rc = alloc_dev(h, &sl.rec, (size_t)h->F * N2)) != FNN_OK) return rc;
-        if ((rc = alloc_dev(h, &sl.part, (size_t)h->F * nchunk * 2 * SLOT)) != FNN_OK) return rc;
+        if ((rc = alloc_dev(h, &sl.part, (size_t)h->F * nchunk * 2 * (h->wide ? h->rw : SLOT))) != FNN_OK) return rc;
         if ((rc = alloc_dev(h, &sl.owners, (size_t)h->F * nchunk)) != FNN_OK) return rc;
         if ((rc = alloc_dev(h, &sl.owner_cnt, (size_t)1)) != FNN_OK) return rc;
         h->gN2 = N2;
@@ -751,6 +774,7 @@ int dp_setup(fnn_handle* h, int rank, int world, int sparse_mode)
     if (sparse_mode != FNN_DP_SPARSE_LOCAL && sparse_mode != FNN_DP_SPARSE_EXCHANGE) FAIL(h, FNN_ERR_ARG, "fnn_dp_init: bad sparse_mode");
     if (h->in_step) FAIL(h, FNN_ERR_STATE, "fnn_dp_init inside a step");
     if (sparse_mode == FNN_DP_SPARSE_EXCHANGE) {
+        if (h->wide) FAIL(h, FNN_ERR_ARG, "FNN_DP_SPARSE_EXCHANGE: not supported on wide rows (k >= 17; its exchange carries 16-float slots): use FNN_DP_SPARSE_LOCAL");
         if ((int64_t)world * h->ldT > GLOBAL_BATCH_MAX) FAIL(h, FNN_ERR_ARG, "FNN_DP_SPARSE_EXCHANGE: world * max_batch (rounded up to 256) must be <= 32768");
         if (!(h->fused && mlp_shape_ok(h)) || h->Bmax > SORT_N) FAIL(h, FNN_ERR_ARG, "FNN_DP_SPARSE_EXCHANGE runs on the three-launch path only (max_batch <= 4096, hidden sizes the strip kernel is built for)");
         int rc;
@@ -799,7 +823,10 @@ int fnn_create(const fnn_cfg* cfg, fnn_handle** out)
     if (cfg->mode != FNN_MODE_FM && cfg->mode != FNN_MODE_BAG) { g_create_err = "bad mode"; return FNN_ERR_ARG; }
     if (cfg->mode == FNN_MODE_BAG && (cfg->h0 < 192 || cfg->h0 > 316 || cfg->h0 % 4 != 0)) {
         g_create_err = "FNN_MODE_BAG: h0 must be a multiple of 4 in [192, 316] (the strip kernel is built for bag rows of 256 or 320 padded floats; the reference uses 200 and 300, python/SNN_RBM.py:25,53)"; return FNN_ERR_ARG; }
-    if (cfg->mode == FNN_MODE_FM && (cfg->k < 1 || cfg->k > 15)) { g_create_err = "k = rank+1 must be in [1, 15] (two pad slots of the 16-float row carry w_0 and the bias)"; return FNN_ERR_ARG; }
+    if (cfg->mode == FNN_MODE_FM && (cfg->k < 1 || cfg->k > 128 || cfg->k == 16)) {
+        g_create_err = "k = rank+1 must be in [1, 15] (two pad slots of the 16-float row carry w_0 and the bias) or in [17, 128] (wide rows of rup(k, 4) floats); k = 16 is not supported"; return FNN_ERR_ARG; }
+    if (cfg->mode == FNN_MODE_FM && cfg->k >= 17 && cfg->n_fields * rup(cfg->k, 4) > WIDE_XW_MAX) {
+        g_create_err = "k >= 17: n_fields * rup(k, 4) must be <= 4096 (the layer-one width of the wide-row path)"; return FNN_ERR_ARG; }
     if (cfg->hidden1 < 1 || cfg->hidden1 > 4095 || cfg->hidden2 < 1 || cfg->hidden2 > 255) { g_create_err = "hidden1 must be in [1, 4095], hidden2 in [1, 255]"; return FNN_ERR_ARG; }
     if (cfg->max_batch < 1 || cfg->max_batch > 16384) { g_create_err = "max_batch must be in [1, 16384] (per-field LDS sort)"; return FNN_ERR_ARG; }
     if (cfg->precision != FNN_PREC_F32 && cfg->precision != FNN_PREC_BF16 && cfg->precision != FNN_PREC_BF16X3) { g_create_err = "bad precision"; return FNN_ERR_ARG; }
@@ -826,6 +853,8 @@ int fnn_create(const fnn_cfg* cfg, fnn_handle** out)
     if (const char* e = getenv("FNN_WT_STORES")) h->wt_stores = atoi(e);
     if (const char* e = getenv("FNN_STEP1_WAVES")) h->step1_waves = atoi(e) == 4 ? 4 : 8;
     if (h->bag) { h->rw = cfg->h0; h->K = cfg->h0; h->xdim = cfg->h0; h->K1p = rup(cfg->h0 + 1, 64); }
+    h->wide = !h->bag && h->K >= 17;
+    if (h->wide) { h->rw = rup(h->K, 4); h->K1p = rup(h->F * h->rw + 2, 64); }       // field columns, then w_0 and the ones column
     h->Bmax = cfg->max_batch; h->ldT = rup(h->Bmax, 256);
     h->N2max = SORT_N; while (h->N2max < h->Bmax) h->N2max <<= 1;    // the three-launch path groups SORT_N slots per field whatever max_batch is
     h->n1 = (size_t)h->K1p * h->H1p; h->n2 = (size_t)h->H1p * h->H2p;
@@ -857,7 +886,7 @@ int fnn_create(const fnn_cfg* cfg, fnn_handle** out)
     CK(alloc_dev(h, &h->loss_dev, (size_t)1));
     for (auto& sl : h->slot) {
         CK(alloc_dev(h, &sl.rec, (size_t)h->F * h->N2max));
-        const size_t nchunk = h->bag ? (size_t)h->N2max / WCH : (size_t)h->N2max / 16;
+        const size_t nchunk = (h->bag || h->wide) ? (size_t)h->N2max / WCH : (size_t)h->N2max / 16;
         CK(alloc_dev(h, &sl.part, (size_t)h->F * nchunk * 2 * h->rw));
         CK(alloc_dev(h, &sl.owners, (size_t)h->F * nchunk));
         CK(alloc_dev(h, &sl.owner_cnt, (size_t)1));
@@ -898,9 +927,11 @@ int fnn_create(const fnn_cfg* cfg, fnn_handle** out)
     HK(hipFuncSetAttribute((const void*)k_sort<8>, hipFuncAttributeMaxDynamicSharedMemorySize, 8192 * 8));
     HK(hipFuncSetAttribute((const void*)k_sort<16>, hipFuncAttributeMaxDynamicSharedMemorySize, 16384 * 8));
     if (!h->bag) {
-        const size_t gl = (size_t)GR_EX * (h->xdim + h->F) * sizeof(float);          // 65,600 bytes at F = 64, K = 15
+        // 65,600 bytes at F = 64, K = 15; wide rows: 133,152 at F * K = 4096, F = 64 (8 examples per tile)
+        const size_t gl = (size_t)(h->wide ? GR_EX_WIDE : GR_EX) * (h->xdim + h->F) * sizeof(float);
         if (gl > 160 * 1024) { h->err = "n_fields * k too large for the reference-layout gather tile"; return fail(FNN_ERR_ARG); }
-        HK(hipFuncSetAttribute((const void*)k_gather_ref, hipFuncAttributeMaxDynamicSharedMemorySize, (int)std::max(gl, (size_t)65536)));
+        const void* kf = h->wide ? (const void*)k_gather_ref<GR_EX_WIDE, true> : (const void*)k_gather_ref<GR_EX, false>;
+        HK(hipFuncSetAttribute(kf, hipFuncAttributeMaxDynamicSharedMemorySize, (int)std::max(gl, (size_t)65536)));
     }
     HK(hipStreamSynchronize(h->st));
 #undef CK
@@ -1052,6 +1083,13 @@ int fnn_set_dense(fnn_handle* h, int layer, const float* W, const float* b, int 
         if (h->bag) {                                                    // W [h0][H1]; b1 on the ones column h0
             for (int i = 0; i < h->rw; ++i) memcpy(&p[(size_t)i * H1p], &hw[(size_t)i * H1], H1 * 4);
             memcpy(&p[(size_t)h->rw * H1p], hb.data(), H1 * 4);
+        } else if (h->wide) {                                            // wide rows: field f at rows f*rw.., then w_0, ones
+            const int rw = h->rw;
+            for (int f = 0; f < F; ++f)
+                for (int l = 0; l < K; ++l)
+                    memcpy(&p[(size_t)(f * rw + l) * H1p], &hw[(size_t)(1 + f * K + l) * H1], H1 * 4);
+            memcpy(&p[(size_t)(F * rw) * H1p], &hw[0], H1 * 4);          // w1[0,:] on the w_0 column
+            memcpy(&p[(size_t)(F * rw + 1) * H1p], hb.data(), H1 * 4);   // b1 on the ones column
         } else {
             for (int f = 0; f < F; ++f)
                 for (int l = 0; l < K; ++l)
@@ -1092,6 +1130,13 @@ int fnn_get_dense(fnn_handle* h, int layer, float* W, float* b, int memkind)
         if (h->bag) {
             for (int i = 0; i < h->rw; ++i) memcpy(&hw[(size_t)i * H1], &m[(size_t)i * H1p], H1 * 4);
             memcpy(hb.data(), &m[(size_t)h->rw * H1p], H1 * 4);
+        } else if (h->wide) {
+            const int rw = h->rw;
+            memcpy(&hw[0], &m[(size_t)(F * rw) * H1p], H1 * 4);
+            for (int f = 0; f < F; ++f)
+                for (int l = 0; l < K; ++l)
+                    memcpy(&hw[(size_t)(1 + f * K + l) * H1], &m[(size_t)(f * rw + l) * H1p], H1 * 4);
+            memcpy(hb.data(), &m[(size_t)(F * rw + 1) * H1p], H1 * 4);
         } else {
             memcpy(&hw[0], &m[(size_t)K * H1p], H1 * 4);
             for (int f = 0; f < F; ++f)
@@ -1157,9 +1202,12 @@ int fnn_gather(fnn_handle* h, const int32_t* ids, int B, float* x_out, int memki
             if (h->bag)
                 hipLaunchKernelGGL(k_bag_ref, dim3((unsigned)((n / 4 + 255) / 256)), dim3(256), 0, h->st, ids_dev, nb, h->F,
                                    h->rw, h->table16, h->n_rows, h->bb0, x_dev, h->err_flag, (h->wt_stores & 16) != 0);   // (measured: 1 % slower written through -- off)
+            else if (h->wide)
+                hipLaunchKernelGGL((k_gather_ref<GR_EX_WIDE, true>), dim3((unsigned)((nb + GR_EX_WIDE - 1) / GR_EX_WIDE)), dim3(256), (size_t)GR_EX_WIDE * (h->xdim + h->F) * sizeof(float), h->st,
+                                   ids_dev, nb, h->F, h->K, h->table16, h->n_rows, h->w0, x_dev, h->err_flag, (h->wt_stores & 8) != 0, h->rw);
             else
-                hipLaunchKernelGGL(k_gather_ref, dim3((unsigned)((nb + GR_EX - 1) / GR_EX)), dim3(256), (size_t)GR_EX * (h->xdim + h->F) * sizeof(float), h->st, ids_dev, nb, h->F,
-                                   h->K, h->table16, h->n_rows, h->w0, x_dev, h->err_flag, (h->wt_stores & 8) != 0);
+                hipLaunchKernelGGL((k_gather_ref<GR_EX, false>), dim3((unsigned)((nb + GR_EX - 1) / GR_EX)), dim3(256), (size_t)GR_EX * (h->xdim + h->F) * sizeof(float), h->st, ids_dev, nb, h->F,
+                                   h->K, h->table16, h->n_rows, h->w0, x_dev, h->err_flag, (h->wt_stores & 8) != 0, SLOT);
         }
         if (host) {
             HIPCHK(h, hipMemcpyAsync(x_out + (size_t)lo * h->xdim, x_dev, n * 4, hipMemcpyDeviceToHost, h->st));
@@ -1284,6 +1332,7 @@ int fnn_sparse_grad(fnn_handle* h, float** dev_ptr, int64_t* row_floats)
 {
     if (!h || !dev_ptr || !row_floats) return FNN_ERR_ARG;
     if (h->bag) FAIL(h, FNN_ERR_ARG, "fnn_sparse_grad: FNN_MODE_FM only");
+    if (h->wide) FAIL(h, FNN_ERR_ARG, "fnn_sparse_grad: the 16-float slot layout of the exact data-parallel mode; not supported on wide rows (k >= 17)");
     *dev_ptr = h->gxp; *row_floats = h->K1p;
     return FNN_OK;
 }
@@ -1291,6 +1340,7 @@ int fnn_sparse_grad(fnn_handle* h, float** dev_ptr, int64_t* row_floats)
 int fnn_step_scatter_global(fnn_handle* h, const int32_t* ids_g, const float* gxp_g, int B_g)
 {
     if (!h) return FNN_ERR_ARG;
+    if (h->wide) FAIL(h, FNN_ERR_ARG, "fnn_step_scatter_global: the 16-float slot layout of the exact data-parallel mode; not supported on wide rows (k >= 17)");
     if (!h->in_step) FAIL(h, FNN_ERR_STATE, "fnn_step_scatter_global without fnn_step_begin");
     if (h->bag) FAIL(h, FNN_ERR_ARG, "fnn_step_scatter_global: FNN_MODE_FM only");
     if (!ids_g || !gxp_g || B_g < 1 || B_g > GLOBAL_BATCH_MAX) FAIL(h, FNN_ERR_ARG, "ids_g / gxp_g null or B_g outside [1, 32768]");

@@ -334,22 +334,68 @@ static __global__ __launch_bounds__(256) void k_gather(const int32_t* __restrict
         store4(xpT + ft_off<T>(c0 + j, t0, ldT), v[0][j], v[1][j], v[2][j], v[3][j]);
 }
 
+// Layer-one array of wide FM rows (k >= 17, rows of rw = rup(k, 4) floats): x' [Ba][K1p] and x'^T (fragment-tiled), column
+// f*rw + l = row(ids[t][f])[l], column F*rw = w_0 (the reference's x[0], python/FNN_wnzh.py:93), column F*rw + 1 = 1 (b1 as a
+// row of W1p), zeros in the row pads, the columns after them and the rows t >= B.  One thread = 4 consecutive examples x one
+// 16-byte piece of x': consecutive threads read consecutive pieces of the same rows (16-byte loads, coalesced over a row's
+// rw / 4 pieces) and write consecutive pieces of both layouts.
+template <typename T>
+static __global__ __launch_bounds__(256) void k_gather_wide(const int32_t* __restrict__ ids, int B, int Ba, int F, int rw,
+                                                            const float* __restrict__ table, int64_t n_rows, float w0,
+                                                            T* __restrict__ xp, int K1p, T* __restrict__ xpT, int ldT,
+                                                            int* __restrict__ err)
+{
+    const int nq = K1p >> 2, rq = rw >> 2;
+    const int gid = blockIdx.x * blockDim.x + threadIdx.x;
+    const int q = gid % nq, t0 = (gid / nq) * 4;
+    if (t0 >= Ba) return;
+    const int f = q / rq, c0 = 4 * q;
+    float v[4][4];
+#pragma unroll
+    for (int i = 0; i < 4; ++i) {
+        const int t = t0 + i;
+        float4 r = make_float4(0.f, 0.f, 0.f, 0.f);
+        if (t < B) {
+            if (f < F) {
+                int64_t id = ids[(size_t)t * F + f];
+                if (id < -1 || id >= n_rows) { atomicOr(err, 1); id = -1; }
+                if (id >= 0) r = *reinterpret_cast<const float4*>(table + (size_t)id * rw + (c0 - f * rw));
+            } else if (c0 == F * rw) {
+                r.x = w0;                                  // x[0] = w_0 (:93)
+                r.y = 1.0f;                                // ones column: b1 is a row of W1p
+            }
+        }
+        v[i][0] = r.x; v[i][1] = r.y; v[i][2] = r.z; v[i][3] = r.w;
+    }
+#pragma unroll
+    for (int i = 0; i < 4; ++i)
+        store4(xp + (size_t)(t0 + i) * K1p + c0, v[i][0], v[i][1], v[i][2], v[i][3]);
+#pragma unroll
+    for (int j = 0; j < 4; ++j)
+        store4(xpT + ft_off<T>(c0 + j, t0, ldT), v[0][j], v[1][j], v[2][j], v[3][j]);
+}
+
 // Reference-layout gather for fnn_gather(): x [B][1+F*K] float (python/FNN_wnzh.py:91-96).  A workgroup writes GR_EX
 // examples; a thread owns one column (its field and slot are worked out once, not per element -- the first version spent its time
 // in the two integer divisions of a flat index: 47 us for 100,000 examples) and keeps 8 examples' ids, then rows, in flight.
 // The tile of GR_EX x xdim floats goes through LDS and leaves as 16-byte stores over the workgroup's flat range of x (rows of
 // 177 floats start on a 16-byte boundary only every fourth row, the range of 16 rows always does).
-constexpr int GR_EX = 16;
+// Wide FM rows (k >= 17): rows of `rw` floats instead of SLOT and 8 examples per workgroup (EX), so that the tile of the largest
+// accepted shape (F * rw <= 4096: 8 x (4097 + 64) floats, 133 KB) fits the 160 KB of LDS; EX a multiple of 4 keeps the flat range
+// 16-byte aligned.
+constexpr int GR_EX = 16, GR_EX_WIDE = 8;
+template <int EX, bool WIDE>
 static __global__ __launch_bounds__(256) void k_gather_ref(const int32_t* __restrict__ ids, int B, int F, int K,
                              const float* __restrict__ table16, int64_t n_rows, float w0,
-                             float* __restrict__ x, int* __restrict__ err, const bool wt)
+                             float* __restrict__ x, int* __restrict__ err, const bool wt, const int rw)
 {
     extern __shared__ __align__(16) unsigned char gr_smem[];
-    float* sx = reinterpret_cast<float*>(gr_smem);                  // [GR_EX][xdim]
+    float* sx = reinterpret_cast<float*>(gr_smem);                  // [EX][xdim]
     const int xdim = 1 + F * K;
-    const int t0 = blockIdx.x * GR_EX;
-    int* sids = reinterpret_cast<int*>(sx + GR_EX * xdim);            // [GR_EX][F]: the strip's ids, read once (contiguous)
-    for (int e = threadIdx.x; e < GR_EX * F; e += 256) {
+    const int stride = WIDE ? rw : SLOT;
+    const int t0 = blockIdx.x * EX;
+    int* sids = reinterpret_cast<int*>(sx + EX * xdim);               // [EX][F]: the strip's ids, read once (contiguous)
+    for (int e = threadIdx.x; e < EX * F; e += 256) {
         int id = -1;
         if (t0 + e / F < B) {
             id = ids[(size_t)t0 * F + e];
@@ -361,35 +407,36 @@ static __global__ __launch_bounds__(256) void k_gather_ref(const int32_t* __rest
     for (int c = threadIdx.x; c < xdim; c += 256) {
         const int f = c ? (c - 1) / K : 0, l = c ? (c - 1) % K : 0;
 #pragma unroll
-        for (int e0 = 0; e0 < GR_EX; e0 += 8) {
+        for (int e0 = 0; e0 < EX; e0 += 8) {
             float v[8];
 #pragma unroll
             for (int u = 0; u < 8; ++u) {
                 const int id = c ? sids[(e0 + u) * F + f] : -1;
-                v[u] = id >= 0 ? table16[(size_t)id * SLOT + l] : 0.f;
+                v[u] = id >= 0 ? table16[(size_t)id * stride + l] : 0.f;
             }
 #pragma unroll
             for (int u = 0; u < 8; ++u) sx[(e0 + u) * xdim + c] = c ? v[u] : w0;          // x[0] = w_0 (:93)
         }
     }
     __syncthreads();
-    const int nex = min(GR_EX, B - t0);
-    const size_t base = (size_t)t0 * xdim;                          // multiple of 16 floats: 16-byte aligned
+    const int nex = min(EX, B - t0);
+    const size_t base = (size_t)t0 * xdim;                          // multiple of EX >= 4 floats: 16-byte aligned
     const int nfl = nex * xdim, n4 = nfl >> 2;
     for (int i = threadIdx.x; i < n4; i += 256) store16_sel(wt, reinterpret_cast<float4*>(x + base) + i, reinterpret_cast<const float4*>(sx)[i]);   // (written through: the output is the caller's)
     for (int i = 4 * n4 + threadIdx.x; i < nfl; i += 256) x[base + i] = sx[i];
 }
 
-// gx' [B][K1p] (slot layout) -> gx [B][1+F*K] (what `train` returns, python/FNN_wnzh.py:179).
-static __global__ void k_gx_ref(const float* __restrict__ gxp, int K1p, int B, int F, int K,
+// gx' [B][K1p] (slot layout) -> gx [B][1+F*K] (what `train` returns, python/FNN_wnzh.py:179).  rw: columns per field (SLOT, or
+// rup(K, 4) for wide rows); cw0: the column of w_0 (K, a pad slot of field 0, or F * rw for wide rows).
+static __global__ void k_gx_ref(const float* __restrict__ gxp, int K1p, int B, int F, int K, int rw, int cw0,
                          float* __restrict__ gx)
 {
     const int xdim = 1 + F * K;
     const size_t gid = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
     if (gid >= (size_t)B * xdim) return;
     const int t = (int)(gid / xdim), i = (int)(gid % xdim);
-    int c = K;                                   // d cost / d x[0] lives in the w_0 slot
-    if (i > 0) c = ((i - 1) / K) * SLOT + (i - 1) % K;
+    int c = cw0;                                 // d cost / d x[0] lives in the w_0 column
+    if (i > 0) c = ((i - 1) / K) * rw + (i - 1) % K;
     gx[gid] = gxp[(size_t)t * K1p + c];
 }
 
@@ -1905,6 +1952,131 @@ __device__ __forceinline__ void scatw2_body(const ScatArgs& sa, const int blk, c
         }
         __syncthreads();
     }
+}
+
+// ------------------------------------------------------------------------------------------
+// Decayed sparse-row update of wide FM rows (FNN_MODE_FM, k >= 17: rows of rw = rup(k, 4) floats): the closed form of
+// scat1_body / scat2_body -- a row whose segment is [s, e) of the sorted entries ends at row*c^(e-s) - lr * sum_pos g_pos *
+// c^(e-1-pos) -- with the chunking of scatw1_body / scatw2_body: WCH sorted entries per chunk, one 16-byte quarter-column per
+// thread, the gradient of (example t, field f) at gx'[t][f*gxf + l].  An entry's weight c^(e-1-pos) is absolute inside its
+// segment, so the level-1 partials of a segment cut by chunk borders simply add up in level 2, which applies c^(e-s) once.
+// f64 sums, no float atomics (a row belongs to one field: one group per row), fixed summation order: bit-reproducible.
+// The pad lanes of a row (l >= K) take no gradient and stay zero.
+// ------------------------------------------------------------------------------------------
+__device__ __forceinline__ void scatdw1_body(const ScatArgs& sa, const int blk)
+{
+    const int rw = sa.rw, nq = rw >> 2, N2 = sa.N2, NQ = N2 / WCH;
+    const int gid = blk * 256 + (int)threadIdx.x;
+    const int chunk = gid / nq, q = gid % nq;
+    if (chunk >= sa.F * NQ) return;
+    const int f = chunk / NQ, qc = chunk % NQ, base = qc * WCH;
+    const int lim = sa.K - 4 * q;                           // live lanes of this piece: < 4 only in the last piece of a padded row
+    const double* __restrict__ cpow = sa.cpow; const double lr = sa.lr;
+    double a0 = 0, a1 = 0, a2 = 0, a3 = 0;
+    int4 rn[8];
+#pragma unroll
+    for (int j = 0; j < 8; ++j) rn[j] = sa.rec[(size_t)f * N2 + base + j];
+    for (int sb = 0; sb < WCH; sb += 8) {
+        int4 r[8];
+#pragma unroll
+        for (int j = 0; j < 8; ++j) r[j] = rn[j];
+        if (r[0].x < 0) break;                               // invalid keys sort to the end
+        if (sb + 8 < WCH) {
+#pragma unroll
+            for (int j = 0; j < 8; ++j) rn[j] = sa.rec[(size_t)f * N2 + base + sb + 8 + j];
+        }
+        float4 g[8], wold[8];
+        double wd[8], cs[8];
+#pragma unroll
+        for (int j = 0; j < 8; ++j) {
+            const int pos = base + sb + j;
+            const bool live = r[j].x >= 0;
+            g[j] = *reinterpret_cast<const float4*>(sa.gxp + (size_t)(live ? r[j].y : 0) * sa.K1p + (size_t)f * sa.gxf + 4 * q);
+            // the old row and the segment's decay c^(e-s) only where the row is written: the last entry of a segment inside the chunk
+            const bool need = live && pos + 1 == r[j].w && r[j].z >= base;
+            wold[j] = *reinterpret_cast<const float4*>(sa.table16 + (size_t)(need ? r[j].x : 0) * rw + 4 * q);
+            wd[j] = cpow[live ? r[j].w - 1 - pos : 0];
+            cs[j] = cpow[need ? r[j].w - r[j].z : 0];
+        }
+        if (lim < 4) {
+#pragma unroll
+            for (int j = 0; j < 8; ++j) {
+                if (lim < 2) g[j].y = 0.f;
+                if (lim < 3) g[j].z = 0.f;
+                g[j].w = 0.f;
+            }
+        }
+#pragma unroll
+        for (int j = 0; j < 8; ++j) {
+            if (r[j].x < 0) continue;
+            a0 += (double)g[j].x * wd[j]; a1 += (double)g[j].y * wd[j]; a2 += (double)g[j].z * wd[j]; a3 += (double)g[j].w * wd[j];
+            const int pos = base + sb + j, s = r[j].z, e = r[j].w;
+            if (pos + 1 != e && pos + 1 != base + WCH) continue;       // the run goes on inside this chunk
+            if (s >= base && e <= base + WCH) {                      // the whole segment lies in this chunk
+                *reinterpret_cast<float4*>(sa.table16 + (size_t)r[j].x * rw + 4 * q) =
+                    make_float4((float)((double)wold[j].x * cs[j] - lr * a0), (float)((double)wold[j].y * cs[j] - lr * a1),
+                                (float)((double)wold[j].z * cs[j] - lr * a2), (float)((double)wold[j].w * cs[j] - lr * a3));
+            } else {
+                const int which = (s < base) ? 0 : 1;                // 0: enters from the left; 1: opens here
+                double* pp = sa.part + (((size_t)f * NQ + qc) * 2 + which) * rw + 4 * q;
+                pp[0] = a0; pp[1] = a1; pp[2] = a2; pp[3] = a3;
+                if (which == 1 && q == 0) sa.owners[atomicAdd(sa.owner_cnt, 1)] = make_int4(f, s, e, r[j].x);
+            }
+            a0 = a1 = a2 = a3 = 0;
+        }
+    }
+}
+
+// level 2: one workgroup per registered multi-chunk segment; groups of nq threads add the chunks' partials in a fixed order
+__device__ __forceinline__ void scatdw2_body(const ScatArgs& sa, const int blk, const int nblk, double* s_w /*[1024]*/)
+{
+    const int rw = sa.rw, nq = rw >> 2, NQ = sa.N2 / WCH, ngrp = 256 / nq;
+    const int grp = threadIdx.x / nq, q = threadIdx.x % nq;
+    const int n = *sa.owner_cnt;
+    for (int o = blk; o < n; o += nblk) {
+        const int4 ow = sa.owners[o];                      // {f, s, e, row}
+        const int q0 = ow.y / WCH, q1 = (ow.z - 1) / WCH;
+        double a0 = 0, a1 = 0, a2 = 0, a3 = 0;
+        // the row and its decay factor are requested with the partial sums, not after them (one round trip less)
+        float4* p = reinterpret_cast<float4*>(sa.table16 + (size_t)ow.w * rw + 4 * q);
+        float4 w = make_float4(0.f, 0.f, 0.f, 0.f);
+        double cdec = 0.0;
+        if (grp == 0) { w = *p; cdec = sa.cpow[ow.z - ow.y]; }
+        if (grp < ngrp) {
+            for (int qq0 = q0 + grp; qq0 <= q1; qq0 += 4 * ngrp) {           // four chunks' partials in flight at a time
+                double v[4][4];
+#pragma unroll
+                for (int k = 0; k < 4; ++k) {
+                    const int qq = qq0 + k * ngrp;
+                    const double* pp = sa.part + (((size_t)ow.x * NQ + (qq <= q1 ? qq : q1)) * 2 + (qq == q0 ? 1 : 0)) * rw + 4 * q;
+                    const bool on = qq <= q1;
+                    v[k][0] = on ? pp[0] : 0.0; v[k][1] = on ? pp[1] : 0.0; v[k][2] = on ? pp[2] : 0.0; v[k][3] = on ? pp[3] : 0.0;
+                }
+#pragma unroll
+                for (int k = 0; k < 4; ++k) { a0 += v[k][0]; a1 += v[k][1]; a2 += v[k][2]; a3 += v[k][3]; }
+            }
+            double* d = s_w + ((size_t)grp * nq + q) * 4;
+            d[0] = a0; d[1] = a1; d[2] = a2; d[3] = a3;
+        }
+        __syncthreads();
+        if (grp == 0) {
+            double t0 = 0, t1 = 0, t2 = 0, t3 = 0;
+            for (int gI = 0; gI < ngrp; ++gI) {
+                const double* d = s_w + ((size_t)gI * nq + q) * 4;
+                t0 += d[0]; t1 += d[1]; t2 += d[2]; t3 += d[3];
+            }
+            *p = make_float4((float)((double)w.x * cdec - sa.lr * t0), (float)((double)w.y * cdec - sa.lr * t1),
+                             (float)((double)w.z * cdec - sa.lr * t2), (float)((double)w.w * cdec - sa.lr * t3));
+        }
+        __syncthreads();
+    }
+}
+
+static __global__ __launch_bounds__(256) void k_scatdw1(const ScatArgs sa) { scatdw1_body(sa, blockIdx.x); }
+static __global__ __launch_bounds__(256) void k_scatdw2(const ScatArgs sa)
+{
+    __shared__ double s_w[1024];
+    scatdw2_body(sa, blockIdx.x, gridDim.x, s_w);
 }
 
 // (A workgroup-per-16-examples form with the ids staged through LDS, which took the FM-row gather from 47 to 21 us per 100,000

@@ -363,7 +363,8 @@ class FNNEngine(object):
 
     def sparse_grad(self, B):
         """gx' [B, row_floats] float32 of the begun step (slot layout: column 16 f + l), a view of the
-        library's buffer -- what the exact data-parallel mode all-gathers."""
+        library's buffer -- what the exact data-parallel mode all-gathers.  Handles of k <= 15 only: on wide
+        rows (k >= 17) the library refuses the call and this raises FNNError."""
         ptr, n = C.c_void_p(), C.c_int64()
         self._ck(self.lib.fnn_sparse_grad(self.h, C.byref(ptr), C.byref(n)))
         return _tensor_from_ptr(self._torch, ptr.value, B * n.value, self.device).view(B, n.value)

@@ -28,6 +28,12 @@
  * y float32 [B]; masks uint8 [H1], [H2];
  * x / gx float32 [B, 1 + F*K] in the reference's layer-one layout
  * (x[0] = w_0, x[1 + f*K + l] = row(ids[f])[l],  python/FNN_wnzh.py:87-96).
+ *
+ * FM rows on the device: K <= 15 pads a row to 16 floats and w_0 / the constant 1 that carries b1 ride in pad slots of fields
+ * 0 and 1.  K = 17..128 (ranks 16..127: the reference's FM50 / FM100 models) takes the wide-row path: rows of rup(K, 4) floats,
+ * w_0 and the ones column after the F*rup(K, 4) field columns, n_fields * rup(K, 4) <= 4096, every step on the layer-by-layer
+ * kernels.  K = 16 is refused.  The reference layouts above and every entry point are the same for both, except the 16-float
+ * slot exchange of FNN_DP_SPARSE_EXCHANGE, fnn_sparse_grad and fnn_step_scatter_global, which wide handles refuse.
  */
 #ifndef FNN_HIP_H
 #define FNN_HIP_H
@@ -74,7 +80,8 @@ extern "C" {
 
 typedef struct fnn_cfg {
     int32_t n_fields;     /* F: 16 for iPinYou (python/FNN_wnzh.py:51-53)     */
-    int32_t k;            /* K = rank + 1: row = [w, v_1..v_rank]  (:76)      */
+    int32_t k;            /* K = rank + 1: row = [w, v_1..v_rank]  (:76); FNN_MODE_FM: 1..15, or 17..128 (wide rows,
+                             n_fields * rup(k, 4) <= 4096)                     */
     int32_t hidden1;      /* python/FNN_wnzh.py:21,46                         */
     int32_t hidden2;      /* python/FNN_wnzh.py:22,47                         */
     int32_t max_batch;    /* largest B of any call; sizes the workspaces      */
@@ -245,7 +252,7 @@ int fnn_dense_grad_bucket(fnn_handle* h, float** dev_ptr, int64_t* n_floats);
  * overlaps an all-reduce the caller has started asynchronously; _end runs it if this was not
  * called.  (_begin leaves the bucket complete before the sparse half is enqueued.) */
 int fnn_step_scatter(fnn_handle* h);
-/* Exact data-parallel mode (FNN_MODE_FM): the sparse-row exchange.  After _begin the slot-layout
+/* Exact data-parallel mode (FNN_MODE_FM, k <= 15; wide handles return FNN_ERR_ARG): the sparse-row exchange.  After _begin the slot-layout
  * row gradients of this rank's shard sit in gx' [B, *row_floats] f32 (column 16 f + l = d cost /
  * d row(ids[t][f])[l]); fnn_sparse_grad exposes that buffer so that the caller can all-gather it
  * together with the ids.  fnn_step_scatter_global then applies, INSTEAD of fnn_step_scatter, the
