@@ -12,9 +12,11 @@ slabs, on the library's own stream) between the second and the third.  `python b
 without a torchrun environment starts the N ranks itself (fresh child processes, before this process
 touches the GPU) and fails if it cannot.
 
-The default N = 1 run also times, briefly, the f32 parity mode of the same step and the other BASELINE
-configs (SNN fine-tune and pre-training, FNN_IP_L7, the standalone gathers) and nests them under
-`precision_f32` / `extra_workloads` of the ONE JSON line rank 0 prints.
+A plain run sets up, warms up, times the steps, writes --dump-outputs and prints ONE JSON line (rank 0).  Everything
+else moves behind --full: the per-launch device times and the roofline (profiled steps of their own), the CPU baselines,
+the exact-mode replica check at N > 1 and, at N = 1 on the default workload, brief runs of the parity-grade precisions
+(f32, bf16x3) of the same step and of the other BASELINE configs (SNN fine-tune and pre-training, FNN_IP_L7, the
+standalone gathers), nested under `precision_f32` / `precision_bf16x3` / `extra_workloads` of the same line.
 """
 import argparse
 import ctypes as C
@@ -91,7 +93,7 @@ def main():
     ap.add_argument('--optimizer', default='sgd', choices=['sgd', 'adam', 'ftrl'],
                     help='--workload ipnn only: sgd (BASELINE configs[2]), or the reference family\'s adam / ftrl (dense table pass per step)')
     ap.add_argument('--workload', default='fnn', choices=['fnn', 'snn', 'ipnn', 'gather', 'rbm', 'e2e', 'pretrain'],
-                    help='fnn: BASELINE configs[1] (default; at N = 1 the other workloads ride along as extra_workloads).  '
+                    help='fnn: BASELINE configs[1] (default; with --full at N = 1 the other workloads ride along as extra_workloads).  '
                          'snn: the SNN fine-tune step of configs[4] (H0=200 bag rows).  '
                          'ipnn: FNN_IP_L7 train step of configs[2] (7 hidden layers, MFMA stack).  '
                          'gather: the standalone embedding gathers (A3: FM rows; A8: 200-wide bag rows) against the HBM roofline.  '
@@ -99,8 +101,12 @@ def main():
                          'e2e: one epoch of `python FNN.py` end to end on synthetic TEXT files of the config shape: native parse of '
                          'fm.model.txt and train.fm.txt, the training steps, the evaluation pass (row N1 of SURVEY 8f)')
     ap.add_argument('--e2e-lines', type=int, default=1 << 20, help='--workload e2e: lines of the synthetic train.fm.txt')
-    ap.add_argument('--no-cpu-baseline', action='store_true')
-    ap.add_argument('--no-extras', action='store_true', help='headline workload only (no precision_f32 / extra_workloads legs)')
+    ap.add_argument('--full', action='store_true',
+                    help='also measure what the headline figure does not need: per-launch device times and roofline (kernel_ms, '
+                         'roofline), CPU baselines, the exact-mode replica check at N > 1, and at N = 1 on --workload fnn the '
+                         'precision_f32 / precision_bf16x3 / extra_workloads legs')
+    ap.add_argument('--no-cpu-baseline', action='store_true', help='with --full: no CPU baselines')
+    ap.add_argument('--no-extras', action='store_true', help='with --full: headline workload only (no precision_f32 / extra_workloads legs)')
     ap.add_argument('--scaling', default='weak', choices=['weak', 'strong'],
                     help="weak: --batch examples per GPU (the contract's default); strong: --batch is the GLOBAL batch, split over the ranks "
                          "(SURVEY 8d config 4, '4096 split 8-way')")
@@ -146,7 +152,7 @@ def main():
         out = bench_pretrain(args)
     else:
         out = bench_fnn(args, args.precision, args.workload == 'snn')
-        if out is not None and world == 1 and args.workload == 'fnn' and not args.no_extras:
+        if out is not None and world == 1 and args.workload == 'fnn' and args.full and not args.no_extras:
             import copy
             short = copy.copy(args)
             short.dump_outputs = None                     # the headline leg's outputs only
@@ -411,58 +417,59 @@ def bench_fnn(args, precision, snn):
     ms_per_step = dt / args.steps * 1e3
     value = gB * args.steps / dt
 
-    # ---- per-kernel device time (HIP events on the library's own streams), same step loop
-    roofline = None
-    kern_ms = {}
-    # every rank runs the profiled steps (under data parallelism a step holds a collective: rank 0 alone would wait
-    # for ever); only rank 0 brackets its launches with events and reports
-    eng.prof_enable(rank == 0)
-    if rank == 0:
-        eng.prof_reset()
-    with torch.cuda.stream(eng.stream):
-        for i in range(min(args.steps, 100)):
-            step(i)
-    sync_all()
-    if rank == 0:
-        for name in ('empty', 'step1', 'step2', 'allreduce', 'p2p_update', 'update', 'allgather', 'step3', 'step2_dense', 'step2_sparse', 'step3_dense', 'step3_sparse',
-                     'sort_global', 'scatter_global', 'sort_now', 'mlp', 'gather', 'fwd1', 'fwd2', 'head', 'bwd1', 'gx', 'wgrad', 'reduce', 'update', 'sort',
-                     'scatter', 'finalize'):
-            kern_ms[name] = eng.prof_get(name)[0]
-        eng.prof_enable(False)
-        merged = dict(kern_ms)
-        merged['scatter'] = kern_ms['scatter'] + kern_ms['finalize']
-        cand = {k: v for k, v in merged.items() if k in ALGO and ALGO[k][1] > 0}
-        dom = max(cand, key=cand.get)
-        bound, per_ex = ALGO[dom]
-        if snn:       # bag forward 64 + 16*800 B; update 2*12,800 + 800 B per example
-            bound, per_ex = {'step1': ('hbm', 64 + 16 * 800), 'step2': ('hbm', 2 * 16 * 800 + 800)}.get(dom, (bound, per_ex))
-        t_s = cand[dom] * 1e-3
-        if bound == 'hbm':
-            ach = per_ex * B / t_s / 1e9
-            peak, unit = HBM_PEAK_GBS, 'GB/s'
-        else:
-            ach = per_ex * B / t_s / 1e12
-            peak, unit = MFMA_PEAK_BY_KERNEL.get((precision, dom), MFMA_PEAK_TFLOPS[precision]), 'TFLOP/s'
-        traffic = pmc_traffic(dom, snn) if precision == 'bf16' else None       # the committed PMC passes are of the bf16 mode
-        roofline = {'kernel': dom, 'bound': bound, 'achieved': ach, 'peak': peak, 'unit': unit,
-                    'frac': ach / peak, 'traffic': traffic,
-                    # what the counters say reached HBM per launch, over the same launch time: beside the algorithmic fraction, never
-                    # instead of it (hot rows served by L2 / Infinity Cache make the algorithmic figure exceed what HBM delivered)
-                    'hbm_frac_from_counters': (traffic / t_s / 1e9 / HBM_PEAK_GBS) if traffic else None,
-                    'avg_launch_ms': cand[dom],
-                    # an event-bracketed slot = kernel + the event mechanism (a back-to-back pair alone: 'event_pair_ms');
-                    # the kernel-only average of the committed rocprofv3 summary of this command is quoted beside it
-                    'event_pair_ms': kern_ms.get('empty'),
-                    # a CONSTANT read from the committed rocprofv3 summary of this command (profiles/), not measured in this run
-                    'committed_rocprof_avg_ms': None if snn else rocprof_avg_ms(dom, precision),
-                    'algorithmic_per_example': per_ex,
-                    'step': {'achieved': (39264 if snn else STEP_MIN_BYTES) * B / (ms_per_step * 1e-3) / 1e9,
-                             'frac': (39264 if snn else STEP_MIN_BYTES) * B / (ms_per_step * 1e-3) / 1e9 / HBM_PEAK_GBS,
-                             'unit': 'GB/s'}}
+    # ---- --full: per-kernel device time (HIP events on the library's own streams), profiled steps of the same loop
+    roofline = kern_ms = None
+    if args.full:
+        kern_ms = {}
+        # every rank runs the profiled steps (under data parallelism a step holds a collective: rank 0 alone would wait
+        # for ever); only rank 0 brackets its launches with events and reports
+        eng.prof_enable(rank == 0)
+        if rank == 0:
+            eng.prof_reset()
+        with torch.cuda.stream(eng.stream):
+            for i in range(min(args.steps, 100)):
+                step(i)
+        sync_all()
+        if rank == 0:
+            for name in ('empty', 'step1', 'step2', 'allreduce', 'p2p_update', 'update', 'allgather', 'step3', 'step2_dense', 'step2_sparse', 'step3_dense', 'step3_sparse',
+                         'sort_global', 'scatter_global', 'sort_now', 'mlp', 'gather', 'fwd1', 'fwd2', 'head', 'bwd1', 'gx', 'wgrad', 'reduce', 'update', 'sort',
+                         'scatter', 'finalize'):
+                kern_ms[name] = eng.prof_get(name)[0]
+            eng.prof_enable(False)
+            merged = dict(kern_ms)
+            merged['scatter'] = kern_ms['scatter'] + kern_ms['finalize']
+            cand = {k: v for k, v in merged.items() if k in ALGO and ALGO[k][1] > 0}
+            dom = max(cand, key=cand.get)
+            bound, per_ex = ALGO[dom]
+            if snn:       # bag forward 64 + 16*800 B; update 2*12,800 + 800 B per example
+                bound, per_ex = {'step1': ('hbm', 64 + 16 * 800), 'step2': ('hbm', 2 * 16 * 800 + 800)}.get(dom, (bound, per_ex))
+            t_s = cand[dom] * 1e-3
+            if bound == 'hbm':
+                ach = per_ex * B / t_s / 1e9
+                peak, unit = HBM_PEAK_GBS, 'GB/s'
+            else:
+                ach = per_ex * B / t_s / 1e12
+                peak, unit = MFMA_PEAK_BY_KERNEL.get((precision, dom), MFMA_PEAK_TFLOPS[precision]), 'TFLOP/s'
+            traffic = pmc_traffic(dom, snn) if precision == 'bf16' else None       # the committed PMC passes are of the bf16 mode
+            roofline = {'kernel': dom, 'bound': bound, 'achieved': ach, 'peak': peak, 'unit': unit,
+                        'frac': ach / peak, 'traffic': traffic,
+                        # what the counters say reached HBM per launch, over the same launch time: beside the algorithmic fraction, never
+                        # instead of it (hot rows served by L2 / Infinity Cache make the algorithmic figure exceed what HBM delivered)
+                        'hbm_frac_from_counters': (traffic / t_s / 1e9 / HBM_PEAK_GBS) if traffic else None,
+                        'avg_launch_ms': cand[dom],
+                        # an event-bracketed slot = kernel + the event mechanism (a back-to-back pair alone: 'event_pair_ms');
+                        # the kernel-only average of the committed rocprofv3 summary of this command is quoted beside it
+                        'event_pair_ms': kern_ms.get('empty'),
+                        # a CONSTANT read from the committed rocprofv3 summary of this command (profiles/), not measured in this run
+                        'committed_rocprof_avg_ms': None if snn else rocprof_avg_ms(dom, precision),
+                        'algorithmic_per_example': per_ex,
+                        'step': {'achieved': (39264 if snn else STEP_MIN_BYTES) * B / (ms_per_step * 1e-3) / 1e9,
+                                 'frac': (39264 if snn else STEP_MIN_BYTES) * B / (ms_per_step * 1e-3) / 1e9 / HBM_PEAK_GBS,
+                                 'unit': 'GB/s'}}
 
-    # ---- N > 1: replicas of the exact mode must hold identical tables (a checksum of each rank's table, min == max over ranks)
+    # ---- --full, N > 1: replicas of the exact mode must hold identical tables (a checksum of each rank's table, min == max over ranks)
     dp_check = None
-    if dist is not None and world > 1 and args.dp_sparse == 'exchange' and not split:
+    if args.full and dist is not None and world > 1 and args.dp_sparse == 'exchange' and not split:
         try:
             # the same rows on every rank: every 229th row of the table (the small fields' hot rows among them) -- all ranks'
             # shards have updated them, in global example order if the exchange works
@@ -475,12 +482,13 @@ def bench_fnn(args, precision, snn):
         except Exception as e:
             dp_check = {'error': '%s: %s' % (type(e).__name__, e)}
 
-    # ---- CPU baseline: the C port of the oracle on this host, 1 core, bounded sample
+    # ---- --full: CPU baseline, the C port of the oracle on this host, 1 core, bounded sample
     cpu = cpu_vec = None
-    if rank == 0 and world == 1 and not args.no_cpu_baseline and not snn:
+    cpu_leg = args.full and not args.no_cpu_baseline
+    if rank == 0 and world == 1 and cpu_leg and not snn:
         cpu = cpu_baseline(rows, ids_np, y_np, m1_np, m2_np, p0, B, args.cpu_seconds)
         cpu_vec = cpu_baseline_vectorised(rows, ids_np, y_np, m1_np, m2_np, p0, B, args.cpu_seconds)
-    if rank == 0 and world == 1 and not args.no_cpu_baseline and snn:
+    if rank == 0 and world == 1 and cpu_leg and snn:
         # the float64 restatement of python/SNN_RBM.py:238-291 (oracle.fnn_oracle.snn_train_step: NumPy bag + MLP, the
         # reference's per-example Python loop for the row updates) on the same table / ids, bounded sample
         from oracle import fnn_oracle as orc
@@ -525,13 +533,14 @@ def bench_fnn(args, precision, snn):
         if dist is not None:
             cfg = eng.dp_config() if not split else {'payload': 'bucket', 'collective': 'torch.distributed', 'region': 'none'}
             p2p = cfg['collective'] == 'p2p'
-            ev = kern_ms.get('empty') or 0.0
+            ev = (kern_ms or {}).get('empty') or 0.0
             out['data_parallel'] = {'collective': collective, 'sparse_rows': args.dp_sparse,
                                     'payload': cfg['payload'], 'exchange_region': cfg['region'],
                                     'p2p_max_flag_wait_us': eng.dp_p2p_max_wait_us() if p2p else None,     # longest wait for a peer's flag in any step (rank skew)
                                     # event-bracketed slot of the collective on rank 0, the event pair's own cost taken off; for p2p the
                                     # slot is the update launch that performs the all-reduce (wait for the peers + sum + update)
-                                    'collective_us': max(0.0, ((kern_ms.get('p2p_update') if p2p else kern_ms.get('allreduce')) or 0.0) - ev) * 1e3,
+                                    'collective_us': (max(0.0, ((kern_ms.get('p2p_update') if p2p else kern_ms.get('allreduce')) or 0.0) - ev) * 1e3
+                                                      if kern_ms is not None else None),
                                     'collective_slot': 'p2p_update (all-reduce + dense update in one launch)' if p2p else 'allreduce',
                                     'launches_per_step': ('five + all-reduce of the flat bucket' if split else
                                                           'three + the p2p update launch (sums every rank\'s bucket over peer pointers)' if p2p else
@@ -636,9 +645,9 @@ def bench_e2e(args):
         ev = eng.evaluate(ids_d, y_d2)
         t_eval = time.perf_counter() - t0
         eng.close()
-        # ---- the reference's way, on a bounded sample: per-line Python parsing (oracle/ingest_oracle.fnn_examples = get_fxy per line)
+        # ---- --full: the reference's way, on a bounded sample: per-line Python parsing (oracle/ingest_oracle.fnn_examples = get_fxy per line)
         cpu = None
-        if not args.no_cpu_baseline:
+        if args.full and not args.no_cpu_baseline:
             from oracle import ingest_oracle as ino
             n_s = min(N, 50000)
             spath = os.path.join(tmp, 'sample.fm.txt')
@@ -994,9 +1003,9 @@ def bench_ipnn(args):
     dt = time.perf_counter() - t0
     loss = C.c_float()
     lib.ipnn_train_step(h, ids.data_ptr(), y.data_ptr(), B, marr[0], None, C.byref(loss))
-    # per-segment device time (HIP events on the library's stream)
+    # --full: per-segment device time (HIP events on the library's stream)
     seg = {}
-    if hasattr(lib, 'ipnn_prof_enable'):
+    if args.full and hasattr(lib, 'ipnn_prof_enable'):
         lib.ipnn_prof_enable(h, 1)
         for i in range(min(args.steps, 50)):
             step(i)
@@ -1032,7 +1041,7 @@ def bench_ipnn(args):
                 'frac': ach_step / peak, 'traffic': None, 'algorithmic_per_example': flops_ex}
     roof['step'] = {'achieved': ach_step, 'frac': ach_step / peak, 'unit': 'TFLOP/s', 'flops_per_example': flops_ex}
     cpu = None
-    if not args.no_cpu_baseline and args.optimizer == 'sgd':
+    if args.full and not args.no_cpu_baseline and args.optimizer == 'sgd':
         # the NumPy float64 restatement (oracle/ipnn_oracle.py, BLAS threads of the host) on the same batches, ~10 s
         from oracle import ipnn_oracle as ipo
         params = {'b': 0.0, 'W': [w.astype(np.float64) for w in Ws], 'bias': [np.zeros(d[i + 1]) for i in range(len(d) - 1)]}

@@ -1,6 +1,7 @@
 """Native data parallelism across TWO REAL GPUs (RCCL over xGMI, world 2): runs wherever two devices are visible and is skipped
 on the one-GPU test boxes of this project (round-2 advisor: the RCCL path with world > 1 had no test that could ever run).
-Each case starts `bench.py --gpus 2` (fresh rank processes) and reads its JSON line."""
+Each case starts `bench.py --gpus 2 --full` (fresh rank processes; the replica check and the per-launch collective time are
+measured under --full) and reads its JSON line."""
 import json
 import os
 import subprocess
@@ -19,7 +20,7 @@ def _two_gpus():
 
 def _bench(*extra):
     env = {k: v for k, v in os.environ.items() if k not in ('WORLD_SIZE', 'RANK', 'LOCAL_RANK', 'FNN_BENCH_REHEARSE')}
-    r = subprocess.run([sys.executable, os.path.join(ROOT, 'bench.py'), '--gpus', '2', '--steps', '30', '--warmup', '5', '--no-extras',
+    r = subprocess.run([sys.executable, os.path.join(ROOT, 'bench.py'), '--gpus', '2', '--steps', '30', '--warmup', '5', '--full', '--no-extras',
                         '--no-cpu-baseline'] + list(extra), env=env, capture_output=True, text=True, timeout=900)
     assert r.returncode == 0, r.stderr[-2000:]
     return json.loads([ln for ln in r.stdout.splitlines() if ln.startswith('{')][-1])

@@ -11,7 +11,7 @@ step() {   # name, seconds, command...
 }
 step gpu_tests 1100 python -m pytest tests -m gpu -q --timeout 600
 step smoke 200 python -c "import __graft_entry__ as g; g.smoke()"
-step bench_default 900 python bench.py
+step bench_default 900 python bench.py --full
 rm -rf gpurun_out/prof_fnn
 step prof_fnn 300 rocprofv3 --kernel-trace --stats --output-format csv -d gpurun_out/prof_fnn -o fnn -- python3 bench.py --steps 400 --warmup 20 --no-cpu-baseline --no-extras
 find gpurun_out/prof_fnn -name "*kernel_stats.csv" -exec cp {} gpurun_out/fnn_kernel_stats.csv \;

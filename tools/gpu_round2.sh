@@ -10,7 +10,7 @@ step() {   # name, seconds, command...
   if [ $rc -ge 124 ]; then echo "killed: stopping"; exit $rc; fi
 }
 step gpu_tests 1000 python -m pytest tests -m gpu -q --timeout 600
-step bench_default 400 bash -c "time python bench.py"
+step bench_default 400 bash -c "time python bench.py --full"
 step bench_dp_world1 200 env FNN_BENCH_FORCE_DP=1 python bench.py --no-extras --no-cpu-baseline
 step bench_rehearse2 300 env FNN_BENCH_REHEARSE=1 python bench.py --gpus 2 --no-extras --no-cpu-baseline --steps 100
 step bench_rehearse2x 300 env FNN_BENCH_REHEARSE=1 python bench.py --gpus 2 --no-extras --no-cpu-baseline --steps 50 --dp-sparse exchange
