@@ -237,6 +237,198 @@ static __global__ __launch_bounds__(256) void k_ip_bwd(const IpBwdArgs a, const 
 }
 
 // ------------------------------------------------------------------------------------------
+// Wide rows (k = 17 .. 128, FM50 / FM100 seeds): the same layer on rows of rw = rup(k, 4) floats.  Layer 0 column f rw + l
+// holds e_f[l], then the P pair products, b and the ones column: D0p = rup(F rw + P + 2, 64).  k_ip_fwd's tile (16 examples x
+// (17 F + D0p) floats) does not fit the LDS there -- 220 KB at F = 16, k = 101, ~560 KB at F rw = 4096 -- so a workgroup takes
+// IPW_EX = 8 examples and stages only their embeddings (F (rw + 1) floats each, <= 132 KB).  Each a0 value is computed in
+// registers: a thread owns EPL consecutive columns of the 8 examples, which is one lane slot of every example's F-layout row and
+// whole lane slots of the T layout (bf16: 8 examples = one 16-byte slot, so no slot is shared by two workgroups), so a0 needs no
+// LDS tile at all.
+// ------------------------------------------------------------------------------------------
+constexpr int IPW_EX = 8;       // examples per workgroup of the wide inner-product launches
+struct IpWideArgs {
+    int P; const int32_t* ids; int B, F, K, rw; const float* table; int64_t n_rows; const float* b;
+    const uint8_t* mask; int d0; float inv_keep; int act; int D0p, ldT; int* err;
+    bool wt;                    // outputs written through (IPNN_WT=0: plain stores)
+    unsigned a0_bytes, emb_bytes;   // sizes of a0 / a0T and of emb: the extent of the write-through stores' buffer resources
+};
+// The wide kernels' write-through stores are raw buffer stores with the sc1 policy (aux 16), not the inline-asm store16_wt /
+// store4_wt: hipcc neither counts nor pads an asm store, so the instruction after a `global_store_dwordx4` there may overwrite its
+// data registers before the store has read them -- in k_ip_fwd_w<bf16_t> that happened (a0 differed between identical runs).
+typedef unsigned int ipw_u32x4 __attribute__((ext_vector_type(4)));
+typedef unsigned int ipw_u32x2 __attribute__((ext_vector_type(2)));
+__device__ __forceinline__ __amdgpu_buffer_rsrc_t ipw_rsrc(const void* p, unsigned bytes) {
+    return __builtin_amdgcn_make_buffer_rsrc(const_cast<void*>(p), 0, (int)bytes, 0x00020000);
+}
+template <typename V> __device__ __forceinline__ void ipw_store16(const bool wt, const __amdgpu_buffer_rsrc_t rs, void* base, const size_t off, const V& v) {
+    static_assert(sizeof(V) == 16, "ipw_store16: 16-byte values");
+    ipw_u32x4 w; __builtin_memcpy(&w, &v, 16);
+    if (wt) __builtin_amdgcn_raw_buffer_store_b128(w, rs, (int)off, 0, 16);
+    else *reinterpret_cast<ipw_u32x4*>(static_cast<char*>(base) + off) = w;
+}
+// four consecutive k of a fragment-tiled operand: 16 bytes (f32) or 8 (bf16)
+__device__ __forceinline__ void ipw_store4(const bool wt, const __amdgpu_buffer_rsrc_t rs, float* base, const size_t e, float a, float b, float c, float d) {
+    ipw_store16(wt, rs, base, e * 4, make_float4(a, b, c, d));
+}
+__device__ __forceinline__ void ipw_store4(const bool wt, const __amdgpu_buffer_rsrc_t rs, bf16_t* base, const size_t e, float a, float b, float c, float d) {
+    bf16x4 v = {(bf16_t)a, (bf16_t)b, (bf16_t)c, (bf16_t)d};
+    ipw_u32x2 w; __builtin_memcpy(&w, &v, 8);
+    if (wt) __builtin_amdgcn_raw_buffer_store_b64(w, rs, (int)(e * 2), 0, 16);
+    else *reinterpret_cast<ipw_u32x2*>(base + e) = w;
+}
+inline size_t ipw_fwd_lds(int F, int rw) { return (size_t)IPW_EX * F * (rw + 1) * sizeof(float); }
+inline size_t ipw_bwd_lds(int F, int rw, int P) { return (size_t)IPW_EX * (F * rw + P) * sizeof(float); }
+
+template <typename T>
+static __global__ __launch_bounds__(256) void k_ip_fwd_w(const IpWideArgs a, T* __restrict__ a0, T* __restrict__ a0T, float* __restrict__ emb)
+{
+    typedef typename Traits<T>::frag frag;
+    constexpr int EPL = Traits<T>::EPL;
+    extern __shared__ __align__(16) unsigned char smem[];
+    float* se = reinterpret_cast<float*>(smem);                 // [IPW_EX][F][rw + 1]: the odd stride spreads the pair reads of a wave
+    const int F = a.F, K = a.K, rw = a.rw, SW = rw + 1, nq = rw >> 2, FW = F * rw, CB = FW + a.P, B = a.B;
+    const int t0 = blockIdx.x * IPW_EX;
+    const __amdgpu_buffer_rsrc_t r_emb = ipw_rsrc(emb, a.emb_bytes), r_a0 = ipw_rsrc(a0, a.a0_bytes), r_a0T = ipw_rsrc(a0T, a.a0_bytes);
+    // gather: IPW_EX x F rows of nq 16-byte pieces, four in flight per thread; the raw rows also go to emb (the backward's copy)
+    const int n = IPW_EX * F * nq;
+    for (int e0 = threadIdx.x; e0 < n; e0 += 256 * 4) {
+        int64_t id[4];
+#pragma unroll
+        for (int j = 0; j < 4; ++j) {
+            const int e = e0 + 256 * j, t = t0 + e / (F * nq), f = (e / nq) % F;
+            id[j] = (e < n && t < B) ? (int64_t)a.ids[(size_t)t * F + f] : -1;
+            if (e < n && t < B && (id[j] < 0 || id[j] >= a.n_rows)) { if (a.err) atomicOr(a.err, 1); id[j] = -1; }
+        }
+        float4 v[4];
+#pragma unroll
+        for (int j = 0; j < 4; ++j) {
+            const int e = e0 + 256 * j;
+            v[j] = id[j] >= 0 ? *reinterpret_cast<const float4*>(a.table + (size_t)id[j] * rw + 4 * (e % nq)) : make_float4(0.f, 0.f, 0.f, 0.f);
+        }
+#pragma unroll
+        for (int j = 0; j < 4; ++j) {
+            const int e = e0 + 256 * j;
+            if (e >= n) continue;
+            const int r = e / (F * nq), f = (e / nq) % F, q = e % nq;
+            float* d = se + (r * F + f) * SW + 4 * q;
+            d[0] = v[j].x; d[1] = v[j].y; d[2] = v[j].z; d[3] = v[j].w;
+            if (emb) ipw_store16(a.wt, r_emb, emb, ((size_t)(t0 + r) * FW + f * rw + 4 * q) * 4, v[j]);
+        }
+    }
+    __syncthreads();
+    const float bval = *a.b;
+    for (int g = threadIdx.x; g < a.D0p / EPL; g += 256) {
+        float v[IPW_EX][EPL];
+#pragma unroll
+        for (int x = 0; x < EPL; ++x) {
+            const int c = g * EPL + x;
+            int ref = -1;
+            float z[IPW_EX];
+#pragma unroll
+            for (int r = 0; r < IPW_EX; ++r) z[r] = 0.f;
+            if (c < FW) {
+                const int f = c / rw, l = c - f * rw;
+                if (l < K) {
+                    ref = f * K + l;
+#pragma unroll
+                    for (int r = 0; r < IPW_EX; ++r) z[r] = se[(r * F + f) * SW + l];
+                }
+            } else if (c < CB) {
+                int m = c - FW, i = 0;                          // m-th pair (i, j), i < j, row-major
+                while (m >= F - 1 - i) { m -= F - 1 - i; ++i; }
+                const int j = i + 1 + m;
+                ref = F * K + (c - FW);
+#pragma unroll
+                for (int r = 0; r < IPW_EX; ++r) {
+                    const float* pi = se + (r * F + i) * SW;
+                    const float* pj = se + (r * F + j) * SW;
+                    float s2 = 0.f;
+                    for (int l = 0; l < K; ++l) s2 = fmaf(pi[l], pj[l], s2);
+                    z[r] = s2;
+                }
+            } else if (c == CB) {
+                ref = a.d0 - 1;
+#pragma unroll
+                for (int r = 0; r < IPW_EX; ++r) z[r] = bval;
+            }
+#pragma unroll
+            for (int r = 0; r < IPW_EX; ++r) {
+                const int t = t0 + r;
+                float val = 0.f;
+                if (t < B) {
+                    if (ref >= 0) val = ip_act(z[r], a.act) * (a.mask ? (float)a.mask[(size_t)t * a.d0 + ref] * a.inv_keep : 1.0f);
+                    else if (c == CB + 1) val = 1.0f;
+                }
+                v[r][x] = val;
+            }
+        }
+#pragma unroll
+        for (int r = 0; r < IPW_EX; ++r) {                       // F layout: the EPL columns of an example are one lane slot
+            frag fv;
+#pragma unroll
+            for (int x = 0; x < EPL; ++x) fv[x] = (T)v[r][x];
+            ipw_store16(a.wt, r_a0, a0, ft_off<T>(t0 + r, g * EPL, a.D0p) * sizeof(T), fv);
+        }
+#pragma unroll
+        for (int x = 0; x < EPL; ++x)                           // T layout: a column's examples are consecutive k
+#pragma unroll
+            for (int r = 0; r < IPW_EX; r += 4)
+                ipw_store4(a.wt, r_a0T, a0T, ft_off<T>(g * EPL + x, t0 + r, a.ldT), v[r][x], v[r + 1][x], v[r + 2][x], v[r + 3][x]);
+    }
+}
+
+// Wide backward: gx'[t][f rw + l] = dz[t][f rw + l] + sum_j dz[t][pair(f, j)] e_j[l] (l < k; pad columns 0), and the per-workgroup
+// partial of db.  The embeddings come from emb (the forward's copy); the pair deltas of the 8 examples are staged beside them.
+static __global__ __launch_bounds__(256) void k_ip_bwd_w(const IpWideArgs a, const float* __restrict__ dz, const float* __restrict__ emb,
+                                                          float* __restrict__ gxp, float* __restrict__ gb_part)
+{
+    extern __shared__ __align__(16) unsigned char smem[];
+    const int F = a.F, K = a.K, rw = a.rw, FW = F * rw, P = a.P, CB = FW + P, D0p = a.D0p;
+    float* se = reinterpret_cast<float*>(smem);                 // [IPW_EX][F rw]
+    float* sp = se + IPW_EX * FW;                               // [IPW_EX][P]
+    const int t0 = blockIdx.x * IPW_EX;
+    {
+        const int n4 = IPW_EX * FW / 4;                         // the 8 examples' rows are contiguous in emb
+        const float4* src = reinterpret_cast<const float4*>(emb + (size_t)t0 * FW);
+        for (int e0 = threadIdx.x; e0 < n4; e0 += 256 * 4) {
+            float4 v[4];
+#pragma unroll
+            for (int k = 0; k < 4; ++k) { const int e = e0 + 256 * k; v[k] = e < n4 ? src[e] : make_float4(0.f, 0.f, 0.f, 0.f); }
+#pragma unroll
+            for (int k = 0; k < 4; ++k) { const int e = e0 + 256 * k; if (e < n4) reinterpret_cast<float4*>(se)[e] = v[k]; }
+        }
+        for (int e = threadIdx.x; e < IPW_EX * P; e += 256) sp[e] = dz[(size_t)(t0 + e / P) * D0p + FW + e % P];
+    }
+    __syncthreads();
+    for (int c = threadIdx.x; c < FW; c += 256) {               // a thread owns (field f, lane l) for the 8 examples
+        const int f = c / rw, l = c - f * rw;
+        float g[IPW_EX];
+#pragma unroll
+        for (int r = 0; r < IPW_EX; ++r) g[r] = l < K ? dz[(size_t)(t0 + r) * D0p + c] : 0.f;
+        if (l < K && P) {
+            for (int j = 0; j < F; ++j) {
+                if (j == f) continue;
+                // pair (i, j), i < j, sits at FW + i (2F - i - 1) / 2 + (j - i - 1)
+                const int i0 = f < j ? f : j, j0 = f < j ? j : f, m = i0 * (2 * F - i0 - 1) / 2 + (j0 - i0 - 1);
+#pragma unroll
+                for (int r = 0; r < IPW_EX; ++r) g[r] = fmaf(sp[r * P + m], se[r * FW + j * rw + l], g[r]);
+            }
+        }
+#pragma unroll
+        for (int r = 0; r < IPW_EX; ++r) gxp[(size_t)(t0 + r) * D0p + c] = g[r];
+    }
+    if (threadIdx.x == 0) { float s = 0.f; for (int r = 0; r < IPW_EX; ++r) s += dz[(size_t)(t0 + r) * D0p + CB]; gb_part[blockIdx.x] = s; }
+}
+
+// the bag table's wide sparse-row update (fnn_kernels.hip.h) on wide rows: gradient of (example t, field f) at gx'[t][f rw + l]
+static __global__ __launch_bounds__(256) void k_ip_scatw1(const ScatArgs sa) { scatw1_body(sa, blockIdx.x); }
+static __global__ __launch_bounds__(256) void k_ip_scatw2(const ScatArgs sa)
+{
+    __shared__ double s_w[1024];
+    scatw2_body(sa, blockIdx.x, gridDim.x, s_w);
+}
+
+// ------------------------------------------------------------------------------------------
 // GEMM epilogues of the deep stack.
 // ------------------------------------------------------------------------------------------
 // All activation / delta matrices of the stack are FRAGMENT-TILED (ft_off) in both orientations:
@@ -1048,6 +1240,10 @@ static __global__ __launch_bounds__(256) void k_ip_update_all(const IpUpdArgs u)
 struct ipnn_handle {
     ipnn_cfg cfg{}; std::string err; int dev = 0; hipStream_t st = nullptr; bool own_stream = false;
     int F = 0, K = 0, L = 0, P = 0, CB = 0, Bmax = 0, ldT = 0; bool bf16 = false; int splitk = 8;   // splitk: slab capacity
+    bool wide = false;                           // k >= 17: wide rows (k_ip_fwd_w / k_ip_bwd_w, k_ip_scatw1 / k_ip_scatw2), chosen at create
+    int rw = SLOT;                               // row stride of the table and field stride of layer 0: SLOT, or rup(k, 4) when wide
+    int* noshare = nullptr;                      // wide: [n_rows] zeros, the wide scatter's tag_shared (a row belongs to one field)
+    bool wide_attr = false;                      // the wide launches' dynamic-LDS opt-in is set
     std::vector<int> sk;                         // split-K of each layer's weight-gradient product
     bool adam = false; int64_t adam_t = 0;       // Adam / FTRL: two state tensors beside every variable, dense row-gradient table; step count
     bool ftrl = false;
@@ -1068,7 +1264,7 @@ struct ipnn_handle {
     // side stream (IPNN_SIDE_STREAM=0: everything in line): the id grouping from the start of the step; the inner-product backward,
     // the scalar b and the sparse-row update beside the weight gradients.  ev_fork / ev_bwd: main -> side; ev_join: side -> main at
     // the end of the step (ev_mask only with IPNN_MASK_SIDE=1)
-    float* emb = nullptr;                            // [ldT][F*16] raw embeddings of the step's examples (forward -> backward)
+    float* emb = nullptr;                            // [ldT][F*rw] raw embeddings of the step's examples (forward -> backward)
     float *dz0 = nullptr, *gxp = nullptr, *gb_part = nullptr, *loss_t = nullptr, *loss_dev = nullptr, *slab = nullptr;
     int* ref0 = nullptr; int* err_flag = nullptr;
     int4* rec = nullptr; double* part = nullptr; int4* owners = nullptr; int* owner_cnt = nullptr; void* skeys = nullptr;
@@ -1139,6 +1335,23 @@ static int ip_join(ipnn_handle* h)
     return FNN_OK;
 }
 
+// the wide launches' arguments (k_ip_fwd_w / k_ip_bwd_w) and their dynamic-LDS opt-in: one fixed ceiling for every handle (the
+// attribute belongs to the kernel, not to the handle; the widest shape takes 132 / 147 KB)
+IpWideArgs ip_wide_args(const ipnn_handle* h, const int32_t* ids, int B, const uint8_t* mask0, float inv_keep)
+{
+    return IpWideArgs{h->P, ids, B, h->F, h->K, h->rw, h->table16, h->n_rows, h->b, mask0, h->d[0], inv_keep, h->cfg.act, h->Dp[0],
+                      h->ldT, h->err_flag, h->wt, (unsigned)((size_t)h->ldT * h->Dp[0] * ts(h)), (unsigned)((size_t)h->ldT * h->F * h->rw * 4)};
+}
+int ip_wide_attr(ipnn_handle* h)
+{
+    if (h->wide_attr) return FNN_OK;
+    IHK(h, hipFuncSetAttribute(reinterpret_cast<const void*>(&k_ip_fwd_w<float>), hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024));
+    IHK(h, hipFuncSetAttribute(reinterpret_cast<const void*>(&k_ip_fwd_w<bf16_t>), hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024));
+    IHK(h, hipFuncSetAttribute(reinterpret_cast<const void*>(&k_ip_bwd_w), hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024));
+    h->wide_attr = true;
+    return FNN_OK;
+}
+
 template <typename T>
 int ip_run(ipnn_handle* h, const int32_t* ids, const float* y, int B, const uint8_t* const* masks, float* logits_out,
            float* p_out, bool train)
@@ -1180,7 +1393,14 @@ int ip_run(ipnn_handle* h, const int32_t* ids, const float* y, int B, const uint
             hipLaunchKernelGGL((k_sortB<unsigned>), dim3(16 * F), dim3(256), SORT_N * 4, ss, so);
         }
     }
-    {
+    if (h->wide) {
+        IpProf ps(h, "ip_fwd");
+        const int rc = ip_wide_attr(h);
+        if (rc != FNN_OK) return rc;
+        const IpWideArgs wa = ip_wide_args(h, ids, B, (train && masks) ? masks[0] : nullptr, (train && masks) ? inv_keep : 1.0f);
+        hipLaunchKernelGGL((k_ip_fwd_w<T>), dim3(Ba / IPW_EX), dim3(256), ipw_fwd_lds(F, h->rw), h->st, wa, (T*)h->a[0], (T*)h->aT[0],
+                           train ? h->emb : nullptr);
+    } else {
         IpProf ps(h, "ip_fwd");
         IpFwdArgs fa{h->P, ids, B, F, h->K, h->table16, h->n_rows, h->b, (train && masks) ? masks[0] : nullptr, h->d[0],
                      (train && masks) ? inv_keep : 1.0f, h->cfg.act, h->Dp[0], ldT, h->err_flag, h->fwd_skip, h->wt};
@@ -1409,12 +1629,25 @@ int ip_run(ipnn_handle* h, const int32_t* ids, const float* y, int B, const uint
         }
         {
             IpProf ps(h, "ip_bwd", ss);
-            IpBwdArgs ba{h->P, ids, B, F, h->K, h->table16, h->n_rows, h->Dp[0], h->emb};
-            hipLaunchKernelGGL(k_ip_bwd, dim3(Ba / 16), dim3(256), lds_ip, ss, ba, h->dz0, h->gxp, h->gb_part);
-            hipLaunchKernelGGL(k_ip_b_update, dim3(1), dim3(256), 0, ss, h->b, h->gb_part, Ba / 16, h->adam ? (int)h->cfg.optimizer : 0, h->bmv,
+            const int ngb = h->wide ? Ba / IPW_EX : Ba / 16;
+            if (h->wide) {
+                const IpWideArgs wa = ip_wide_args(h, ids, B, nullptr, 1.0f);
+                hipLaunchKernelGGL(k_ip_bwd_w, dim3(Ba / IPW_EX), dim3(256), ipw_bwd_lds(F, h->rw, h->P), ss, wa, h->dz0, h->emb, h->gxp, h->gb_part);
+            } else {
+                IpBwdArgs ba{h->P, ids, B, F, h->K, h->table16, h->n_rows, h->Dp[0], h->emb};
+                hipLaunchKernelGGL(k_ip_bwd, dim3(Ba / 16), dim3(256), lds_ip, ss, ba, h->dz0, h->gxp, h->gb_part);
+            }
+            hipLaunchKernelGGL(k_ip_b_update, dim3(1), dim3(256), 0, ss, h->b, h->gb_part, ngb, h->adam ? (int)h->cfg.optimizer : 0, h->bmv,
                                lr_step, h->cfg.adam_beta1, h->cfg.adam_beta2, h->cfg.adam_eps, h->err_flag);
         }
-        {   // sparse rows: row -= lr * sum of its gradients (c = 1: the table of powers is all ones)
+        if (h->wide) {   // wide rows: the bag table's wide scatter, gradient stride rw, row pitch Dp0, c = 1; Adam / FTRL: into tG
+            IpProf ps(h, "scatter", ss);
+            ScatArgs sa{h->rec, SORT_N, F, h->K, h->gxp, h->Dp[0], h->cpow1, h->adam ? -1.0 : (double)h->cfg.lr,
+                        h->adam ? h->tG : h->table16, h->part, h->owner_cnt, h->owners, h->rw, h->noshare, 1, h->rw};
+            const int nthr = F * (SORT_N / WCH) * (h->rw / 4);
+            hipLaunchKernelGGL(k_ip_scatw1, dim3((nthr + 255) / 256), dim3(256), 0, ss, sa);
+            hipLaunchKernelGGL(k_ip_scatw2, dim3(256), dim3(256), 0, ss, sa);
+        } else {   // sparse rows: row -= lr * sum of its gradients (c = 1: the table of powers is all ones)
             IpProf ps(h, "scatter", ss);
             // Adam / FTRL: the same sorted sums land in the (zero) gradient table instead: G[row] = 0 * 1 - (-1) * sum
             ScatArgs sa{h->rec, SORT_N, F, h->K, h->gxp, h->Dp[0], h->cpow1, h->adam ? -1.0 : (double)h->cfg.lr,
@@ -1424,7 +1657,7 @@ int ip_run(ipnn_handle* h, const int32_t* ids, const float* y, int B, const uint
         }
         if (h->adam) {
             IpProf ps(h, "adam_table", ss);
-            const size_t n = (size_t)h->n_rows * SLOT;
+            const size_t n = (size_t)h->n_rows * h->rw;
             hipLaunchKernelGGL(k_adam_table, dim3((unsigned)((n / 4 + 255) / 256)), dim3(256), 0, ss, h->table16, h->tm, h->tv, h->tG, n,
                                lr_step, h->cfg.adam_beta1, h->cfg.adam_beta2, h->cfg.adam_eps, (int)h->cfg.optimizer);
         }
@@ -1497,9 +1730,13 @@ int ipnn_create(const ipnn_cfg* cfg, ipnn_handle** out)
 {
     if (!cfg || !out) { g_ip_err = "null argument"; return FNN_ERR_ARG; }
     *out = nullptr;
-    if (cfg->n_fields < 2 || cfg->n_fields > 32 || cfg->k < 1 || cfg->k > 16 || cfg->n_hidden < 1 || cfg->n_hidden > IPNN_MAX_HIDDEN ||
+    if (cfg->n_fields < 2 || cfg->n_fields > 32) {
+        g_ip_err = "bad shape: n_fields = " + std::to_string(cfg->n_fields) + " (2..32 fields: more than 32 is not built)"; return FNN_ERR_ARG; }
+    if (cfg->k < 1 || cfg->k > 128) {
+        g_ip_err = "bad shape: k = " + std::to_string(cfg->k) + " (k = rank+1 must be 1..128)"; return FNN_ERR_ARG; }
+    if (cfg->n_hidden < 1 || cfg->n_hidden > IPNN_MAX_HIDDEN ||
         cfg->max_batch < 1 || cfg->max_batch > 4096 || !(cfg->keep_prob > 0.f && cfg->keep_prob <= 1.f)) {
-        g_ip_err = "bad shape (2..32 fields, k <= 16, 1..8 hidden layers, batch <= 4096, 0 < keep_prob <= 1)"; return FNN_ERR_ARG; }
+        g_ip_err = "bad shape (2..32 fields, k <= 128, 1..8 hidden layers, batch <= 4096, 0 < keep_prob <= 1)"; return FNN_ERR_ARG; }
     if (cfg->act != A_TANH && cfg->act != A_SIG && cfg->act != A_RELU) { g_ip_err = "bad act"; return FNN_ERR_ARG; }
     if (cfg->precision != FNN_PREC_F32 && cfg->precision != FNN_PREC_BF16) { g_ip_err = "bad precision (FNN_PREC_F32 or FNN_PREC_BF16; FNN_PREC_BF16X3 is the FNN / SNN engine's)"; return FNN_ERR_ARG; }
     if (cfg->optimizer != IPNN_OPT_SGD && cfg->optimizer != IPNN_OPT_ADAM && cfg->optimizer != IPNN_OPT_FTRL) { g_ip_err = "bad optimizer"; return FNN_ERR_ARG; }
@@ -1508,7 +1745,8 @@ int ipnn_create(const ipnn_cfg* cfg, ipnn_handle** out)
     if (hipGetDeviceCount(&ndev) != hipSuccess || ndev <= 0) { g_ip_err = "no HIP device (libfnn_hip.so has no CPU fallback)"; return FNN_ERR_HIP; }
     ipnn_handle* h = new ipnn_handle();
     h->cfg = *cfg; h->dev = cfg->device; h->F = cfg->n_fields; h->K = cfg->k; h->L = cfg->n_hidden;
-    h->P = cfg->pairs ? h->F * (h->F - 1) / 2 : 0; h->CB = h->F * SLOT + h->P; h->bf16 = cfg->precision == FNN_PREC_BF16;
+    h->wide = h->K > SLOT; h->rw = h->wide ? rup(h->K, 4) : SLOT;
+    h->P = cfg->pairs ? h->F * (h->F - 1) / 2 : 0; h->CB = h->F * h->rw + h->P; h->bf16 = cfg->precision == FNN_PREC_BF16;
     h->Bmax = cfg->max_batch; h->ldT = rup(h->Bmax, 256);
     if (const char* e = getenv("IPNN_GEMM_LDS")) h->gemm_lds = atoi(e) != 0;
     if (const char* e = getenv("IPNN_STRIP")) h->strip = atoi(e) != 0;
@@ -1583,11 +1821,12 @@ int ipnn_create(const ipnn_cfg* cfg, ipnn_handle** out)
     for (int t = 0; t <= h->L; ++t) IK(al((void**)&h->maskT[t], Ba * h->Dp[t]));
     h->slab_stride = nw;
     IK(al((void**)&h->slab, (size_t)h->splitk * nw * 4));
-    IK(al((void**)&h->emb, Ba * h->F * SLOT * 4));
+    IK(al((void**)&h->emb, Ba * h->F * h->rw * 4));
     IK(al((void**)&h->dz0, Ba * h->Dp[0] * 4)); IK(al((void**)&h->gxp, Ba * h->Dp[0] * 4));
-    IK(al((void**)&h->gb_part, (Ba / 16) * 4)); IK(al((void**)&h->loss_t, Ba * 4)); IK(al((void**)&h->loss_dev, 4));
+    IK(al((void**)&h->gb_part, (Ba / (h->wide ? IPW_EX : 16)) * 4)); IK(al((void**)&h->loss_t, Ba * 4)); IK(al((void**)&h->loss_dev, 4));
     IK(al((void**)&h->b, 4)); IK(al((void**)&h->err_flag, 4));
-    IK(al((void**)&h->rec, (size_t)h->F * SORT_N * sizeof(int4))); IK(al((void**)&h->part, (size_t)h->F * (SORT_N / 16) * 2 * SLOT * 8));
+    IK(al((void**)&h->rec, (size_t)h->F * SORT_N * sizeof(int4))); IK(al((void**)&h->part, h->wide ? (size_t)h->F * (SORT_N / WCH) * 2 * h->rw * 8
+                                                                                                 : (size_t)h->F * (SORT_N / 16) * 2 * SLOT * 8));
     IK(al((void**)&h->owners, (size_t)h->F * (SORT_N / 16) * sizeof(int4))); IK(al((void**)&h->owner_cnt, 4));
     IK(al(&h->skeys, (size_t)h->F * SORT_N * 8));
     {   // c = 1: every power is 1
@@ -1595,8 +1834,8 @@ int ipnn_create(const ipnn_cfg* cfg, ipnn_handle** out)
         IK(hipMalloc((void**)&h->cpow1, ones.size() * 8));
         IK(hipMemcpy(h->cpow1, ones.data(), ones.size() * 8, hipMemcpyHostToDevice));
         std::vector<int> ref(h->Dp[0], -1);                       // slot column -> reference z1 column
-        for (int f = 0; f < h->F; ++f) for (int l = 0; l < h->K; ++l) ref[f * SLOT + l] = f * h->K + l;
-        for (int n = 0; n < h->P; ++n) ref[h->F * SLOT + n] = h->F * h->K + n;
+        for (int f = 0; f < h->F; ++f) for (int l = 0; l < h->K; ++l) ref[f * h->rw + l] = f * h->K + l;
+        for (int n = 0; n < h->P; ++n) ref[h->F * h->rw + n] = h->F * h->K + n;
         ref[h->CB] = h->d[0] - 1;
         IK(hipMalloc((void**)&h->ref0, ref.size() * 4));
         IK(hipMemcpy(h->ref0, ref.data(), ref.size() * 4, hipMemcpyHostToDevice));
@@ -1619,7 +1858,7 @@ int ipnn_destroy(ipnn_handle* h)
     for (float* p : h->Wm) if (p) hipFree(p);
     for (float* p : h->Wv) if (p) hipFree(p);
     for (float* p : {h->tm, h->tv, h->tG, h->bmv}) if (p) hipFree(p);
-    void* ptrs[] = {h->table16, h->b, h->emb, h->dz0, h->gxp, h->gb_part, h->loss_t, h->loss_dev, h->slab, h->ref0, h->err_flag, h->rec,
+    void* ptrs[] = {h->table16, h->noshare, h->b, h->emb, h->dz0, h->gxp, h->gb_part, h->loss_t, h->loss_dev, h->slab, h->ref0, h->err_flag, h->rec,
                     h->part, h->owners, h->owner_cnt, h->skeys, h->cpow1, h->duo_xch, h->duo_flags};
     for (void* p : ptrs) if (p) hipFree(p);
     for (auto& kv : h->prof_ev) for (auto& p : kv.second) { hipEventDestroy(p.first); hipEventDestroy(p.second); }
@@ -1660,12 +1899,18 @@ int ipnn_set_table(ipnn_handle* h, const float* rows, int64_t n_rows)
     { const int jrc = ip_join(h); if (jrc != FNN_OK) return jrc; }
     IHK(h, hipStreamSynchronize(h->st));
     if (h->table16) hipFree(h->table16);
-    IHK(h, hipMalloc((void**)&h->table16, (size_t)n_rows * SLOT * 4));
+    IHK(h, hipMalloc((void**)&h->table16, (size_t)n_rows * h->rw * 4));
+    if (h->wide) {
+        if (h->noshare) hipFree(h->noshare);
+        h->noshare = nullptr;
+        IHK(h, hipMalloc((void**)&h->noshare, (size_t)n_rows * 4));
+        IHK(h, hipMemset(h->noshare, 0, (size_t)n_rows * 4));
+    }
     float* tmp = nullptr;
     IHK(h, hipMalloc((void**)&tmp, (size_t)n_rows * h->K * 4));
     IHK(h, hipMemcpy(tmp, rows, (size_t)n_rows * h->K * 4, hipMemcpyHostToDevice));
-    const size_t n = (size_t)n_rows * SLOT;
-    hipLaunchKernelGGL(k_pack_table, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, h->st, tmp, n_rows, h->K, SLOT, h->table16);
+    const size_t n = (size_t)n_rows * h->rw;
+    hipLaunchKernelGGL(k_pack_table, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, h->st, tmp, n_rows, h->K, h->rw, h->table16);
     IHK(h, hipStreamSynchronize(h->st));
     hipFree(tmp);
     h->n_rows = n_rows;
@@ -1691,7 +1936,7 @@ int ipnn_get_rows(ipnn_handle* h, const int64_t* row_ids, int64_t n, float* out)
     IHK(h, hipMalloc((void**)&di, n * 8)); IHK(h, hipMalloc((void**)&dout, n * h->K * 4));
     IHK(h, hipMemcpy(di, row_ids, n * 8, hipMemcpyHostToDevice));
     const size_t cnt = (size_t)n * h->K;
-    hipLaunchKernelGGL(k_unpack_rows, dim3((unsigned)((cnt + 255) / 256)), dim3(256), 0, h->st, h->table16, di, n, h->n_rows, h->K, SLOT,
+    hipLaunchKernelGGL(k_unpack_rows, dim3((unsigned)((cnt + 255) / 256)), dim3(256), 0, h->st, h->table16, di, n, h->n_rows, h->K, h->rw,
                        dout, h->err_flag);
     IHK(h, hipMemcpyAsync(out, dout, cnt * 4, hipMemcpyDeviceToHost, h->st));
     IHK(h, hipStreamSynchronize(h->st));
@@ -1723,8 +1968,8 @@ static int ip_row_of(const ipnn_handle* h, int layer, int r)
 {
     if (layer > 1) return r;
     const int FK = h->F * h->K;
-    if (r < FK) return (r / h->K) * SLOT + r % h->K;
-    if (r < FK + h->P) return h->F * SLOT + (r - FK);
+    if (r < FK) return (r / h->K) * h->rw + r % h->K;
+    if (r < FK + h->P) return h->F * h->rw + (r - FK);
     return h->CB;
 }
 

@@ -3,7 +3,9 @@
 `IPNNEngine` is the PyTorch-ROCm plumbing; the three class names of the reference are kept as
 constructors with its `_rch_argv` layout (X_dim, X_feas, rank, h1..hN, act_func), its `forward`
 role (`train_step` / `predict`) and its `dump` keys (`W`, `V`, `b`, `h{i}_w`, `h{i}_b`).
-Categorical fields only; optimiser 'sgd', 'adam' or 'ftrl' (python/tf_util.py:15-29)."""
+Categorical fields only; optimiser 'sgd', 'adam' or 'ftrl' (python/tf_util.py:15-29).  rank 0..127
+(k = rank + 1 up to 128, either precision): an FM50 / FM100 pickle from FM.dump seeds FNN_IP_L3_50 / FNN100 through
+_init_argv."""
 import ctypes as C
 import pickle
 

@@ -7,6 +7,11 @@
  * fields only (iPinYou shape: one id per field); optimiser: plain SGD, Adam or FTRL (IPNN_OPT_*).  Dropout keep-masks are INPUTS (uint8, one per element,
  * reference column order), NULL = no dropout (`drop_out=False`).
  *
+ * Wide rows (k = 17..128, any of 2..32 fields, both `pairs`, both precisions, every optimiser): the table keeps rows of
+ * rw = rup(k, 4) floats (pad columns zero; under Adam / FTRL the state and gradient tables are [n_rows, rw] too) and layer 0
+ * holds column f*rw + l = e_f[l], then the pair products, b and the ones column: rup(F*rw + P + 2, 64) padded columns (at most
+ * 4608: 32 fields of 128).  The layout is internal: every entry point below takes and returns the reference's shapes.
+ *
  * Error codes are the FNN_ERR_* of fnn_hip.h; ipnn_last_error() has the message.
  */
 #ifndef IPNN_HIP_H
@@ -40,7 +45,9 @@ extern "C" {
 
 typedef struct ipnn_cfg {
     int32_t n_fields;                  /* X_feas                                             */
-    int32_t k;                         /* rank + 1: embedding row [w | v]  (FNN_IP_L7.py:66) */
+    int32_t k;                         /* rank + 1: embedding row [w | v]  (FNN_IP_L7.py:66); 1..128:
+                                          k <= 16 keeps rows in 16-float slots; k = 17..128 (the FM50 /
+                                          FM100 seeds) is the WIDE layout below                */
     int32_t n_hidden;                  /* 3, 5 or 7 (any 1..8)                               */
     int32_t hidden[IPNN_MAX_HIDDEN];   /* e.g. 1000,800,600,400,200,100,50 (baseline.py:139) */
     int32_t act;                       /* IPNN_ACT_*                                         */
