@@ -531,7 +531,7 @@ int run_step(fnn_handle* h, const int32_t* ids, const float* y, int B, const uin
     }
     fnn_handle::SortSlot& sl = nsh > 0 ? h->gsl : h->slot[h->cur];
     h->sorted_ids = nullptr; h->next_ids = nullptr;            // this path keeps no grouping across steps
-    if (h->bag && !(h->fused && mlp_shape_ok(h))) FAIL(h, FNN_ERR_ARG, "FNN_MODE_BAG needs the strip kernel (hidden sizes 300/100 or <=63/<=63)");
+    if (h->bag && !(h->fused && mlp_shape_ok(h))) FAIL(h, FNN_ERR_ARG, "FNN_MODE_BAG runs on the strip kernel only, which FNN_NO_FUSE=1 turns off (hidden1 256..319 with hidden2 64..127, or <= 63 / <= 63 at h0 <= 252)");
     if (h->bag && train) FAIL(h, FNN_ERR_ARG, "FNN_MODE_BAG trains through the three-launch path only (B <= 4096)");
     if (train && h->step_native_dp && h->dp_sparse == FNN_DP_SPARSE_EXCHANGE)
         FAIL(h, FNN_ERR_ARG, "FNN_DP_SPARSE_EXCHANGE runs on the three-launch path only (B <= 4096, hidden sizes the strip kernel is built for)");
@@ -892,7 +892,7 @@ int fnn_create(const fnn_cfg* cfg, fnn_handle** out)
         CK(alloc_dev(h, &sl.owner_cnt, (size_t)1));
     }
     if (h->bag) {
-        if (!mlp_shape_ok(h)) { h->err = "FNN_MODE_BAG needs hidden sizes the strip kernel is built for (hidden1 257..319 with hidden2 65..127, e.g. 300/100; h0 <= 252 also <=63/<=63)"; return fail(FNN_ERR_ARG); }
+        if (!mlp_shape_ok(h)) { h->err = "FNN_MODE_BAG needs hidden sizes the strip kernel is built for: hidden1 256..319 with hidden2 64..127 (e.g. 300/100) at any h0, or hidden1 <= 63 with hidden2 <= 63 at h0 <= 252"; return fail(FNN_ERR_ARG); }
         CK(alloc_dev(h, &h->bb0, (size_t)h->K1p));
         CK(alloc_dev(h, (char**)&h->dlxT, Ba * h->K1p * ts));
         CK(alloc_dev(h, (char**)&h->onesT, Ba * 64 * ts));

@@ -392,14 +392,15 @@ def snn_bag(ww0, bb0, ids):
     return 1.0 / (1.0 + np.exp(-s))
 
 
-def snn_train_step(p, ww0, bb0, ids, y, r1, r2, lr, lambda1, acti_type='tanh'):
+def snn_train_step(p, ww0, bb0, ids, y, r1, r2, lr, lambda1, acti_type='tanh', vec=False):
     """One pass of python/SNN_RBM.py:281-291: x from the bag (pre-update ww0/bb0), train(x, y)
     with lambda1 on all six dense tensors (:141-143), then per example, in order,
     delta = lr*gx[t]*x[t]*(1-x[t]); bb0 -= delta; ww0[f] -= delta for each active f.
+    `vec`: the update through snn_update_vec (the same sum, other float64 rounding).
     Mutates p, ww0, bb0 (bb0 must be an ndarray)."""
     x = snn_bag(ww0, bb0, ids)
     gx, pre, loss, p_drop, g = train_call(p, x, y, r1, r2, lr, lambda1, acti_type, reg_all=True)
-    snn_update(ww0, bb0, ids, x, gx, lr)
+    (snn_update_vec if vec else snn_update)(ww0, bb0, ids, x, gx, lr)
     return {'x': x, 'gx': gx, 'loss': loss, 'p_drop': p_drop, 'grads': g, 'pre': pre}
 
 
@@ -415,6 +416,26 @@ def snn_update(ww0, bb0, ids, x, gx, lr):
             r = ids[t, f]
             if r >= 0:
                 ww0[r] = ww0[r] - lr * gx[t] * x[t] * (1 - x[t])
+    return ww0, bb0
+
+
+def snn_update_vec(ww0, bb0, ids, x, gx, lr):
+    """snn_update vectorised: the update has no decay, so a row ends at ww0[r] - sum of the deltas of every (t, f) that
+    lists it, and the order changes only float64 rounding (checked against snn_update in tests/test_oracle.py).  Per column a
+    stable argsort groups the live (row, t) pairs and np.add.reduceat sums each row's deltas; the columns apply one after the
+    other, so a row listed in several columns, or twice on one line, takes every delta.  In place (bb0 must be an ndarray)."""
+    d = lr * gx * x * (1 - x)                                   # [B, h0]: the delta of every line
+    bb0 -= d.sum(axis=0)
+    for f in range(ids.shape[1]):
+        col = ids[:, f]
+        live = np.nonzero(col >= 0)[0]
+        if len(live) == 0:
+            continue
+        order = live[np.argsort(col[live], kind='stable')]
+        r = col[order]
+        start = np.nonzero(np.r_[True, r[1:] != r[:-1]])[0]
+        ur = r[start]
+        ww0[ur] -= np.add.reduceat(d[order], start, axis=0)
     return ww0, bb0
 
 

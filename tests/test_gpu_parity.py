@@ -652,28 +652,54 @@ def test_full_shape_properties(built, full_problem, prec):
 
 
 # ----------------------------------------------------------------- SNN fine-tune path (A8)
-def make_snn_problem(B, n_rows=600, h0=200, seed=0, dup_col=None, empty=()):
-    sizes = synth.field_sizes_tiny(n_rows)
+def snn_active_ids(B, n_rows, n_fields, seed):
+    """ids [B, n_fields] as ingest.MODE_SNN_ACTIVE builds them (python/SNN_RBM.py:248-253): each line's active features packed
+    to the left in line order, -1 after them, a random count per line.  Rows are drawn Zipf-like from the whole table, so one
+    row sits in different columns across lines; every fifth line lists one feature twice; beyond two columns the last
+    max(1, n_fields // 8) columns stay empty for the whole batch."""
+    rng = np.random.RandomState(seed)
+    w = np.arange(1, n_rows + 1, dtype=np.float64) ** -1.1
+    cdf = np.cumsum(w) / w.sum()
+    perm = rng.permutation(n_rows)
+    top = n_fields - (max(1, n_fields // 8) if n_fields > 2 else 0)
+    ids = np.full((B, n_fields), -1, np.int32)
+    for t in range(B):
+        c = int(rng.randint(0, top + 1))
+        feats = perm[np.minimum(np.searchsorted(cdf, rng.uniform(size=c)), n_rows - 1)]
+        if t % 5 == 0 and c >= 2:
+            feats[rng.randint(1, c)] = feats[0]
+        ids[t, :c] = feats
+    return ids
+
+
+def make_snn_problem(B, n_rows=600, h0=200, seed=0, dup_col=None, empty=(), n_fields=F, h1=H1, h2=H2, layout='fields'):
+    """layout 'fields': column f draws from field f's own rows (synth.zipf_ids); 'active': snn_active_ids."""
+    sizes = synth.field_sizes_tiny(n_rows, n_fields=n_fields) if layout == 'fields' else [n_rows]
     rng = np.random.RandomState(seed)
     ww0 = (rng.standard_normal((sum(sizes), h0)) * 0.1).astype(np.float32)
     bb0 = (rng.standard_normal(h0) * 0.1).astype(np.float32)
-    ids = synth.zipf_ids(B, sizes, 1.1, seed + 1)
+    if layout == 'fields':
+        ids = synth.zipf_ids(B, sizes, 1.1, seed + 1)
+    else:
+        assert layout == 'active', layout
+        ids = snn_active_ids(B, n_rows, n_fields, seed + 1)
     if dup_col is not None:
         ids[:, dup_col] = ids[0, dup_col]
     for (t, f) in empty:
         ids[t, f] = -1
     y = (rng.uniform(size=B) < 0.3).astype(np.float32)
-    p = {'w1': f32r(rng.uniform(-0.3, 0.3, (h0, H1))), 'b1': f32r(rng.uniform(-0.1, 0.1, H1)),
-         'w2': f32r(rng.uniform(-0.3, 0.3, (H1, H2))), 'b2': f32r(rng.uniform(-0.1, 0.1, H2)),
-         'w3': f32r(rng.uniform(-0.2, 0.2, H2)), 'b3': 0.05}
-    r1 = (rng.uniform(size=H1) < 0.9).astype(np.uint8)
-    r2 = (rng.uniform(size=H2) < 0.9).astype(np.uint8)
+    p = {'w1': f32r(rng.uniform(-0.3, 0.3, (h0, h1))), 'b1': f32r(rng.uniform(-0.1, 0.1, h1)),
+         'w2': f32r(rng.uniform(-0.3, 0.3, (h1, h2))), 'b2': f32r(rng.uniform(-0.1, 0.1, h2)),
+         'w3': f32r(rng.uniform(-0.2, 0.2, h2)), 'b3': 0.05}
+    r1 = (rng.uniform(size=h1) < 0.9).astype(np.uint8)
+    r2 = (rng.uniform(size=h2) < 0.9).astype(np.uint8)
     return ww0, bb0, ids, y, p, r1, r2
 
 
-def make_snn_engine(ww0, bb0, p, prec='f32', lr=0.01, lam1=0.001, h0=200, max_batch=4096):
-    eng = FNNEngine(F, 0, H1, H2, max_batch=max_batch, precision=prec, lr=lr, lambda1=lam1, lambda_fm=0.0,
-                    reg_all=True, mode='bag', hidden0=h0)
+def make_snn_engine(ww0, bb0, p, prec='f32', lr=0.01, lam1=0.001, h0=200, max_batch=4096, n_fields=F, h1=H1, h2=H2,
+                    acti='tanh'):
+    eng = FNNEngine(n_fields, 0, h1, h2, max_batch=max_batch, precision=prec, acti_type=acti, lr=lr, lambda1=lam1,
+                    lambda_fm=0.0, reg_all=True, mode='bag', hidden0=h0)
     eng.set_table(ww0, np.zeros(ww0.shape[0], np.int32), 0.0)
     eng.set_bag_bias(bb0)
     eng.set_dense(p)

@@ -333,6 +333,43 @@ def test_vectorised_cpu_variant_equals_the_sequential_oracle():
         np.testing.assert_allclose(p[k], pa[k], rtol=1e-13, atol=1e-15)
 
 
+@pytest.mark.parametrize("F", [2, 16, 64])
+def test_vectorised_snn_update_equals_the_sequential_oracle(F):
+    """oracle.snn_update_vec (per-column segment sums) against the per-example loop of python/SNN_RBM.py:285-291 (snn_update):
+    a feature listed twice on one line, the same row in several columns across lines, empty slots (a whole empty line and
+    trailing columns empty for the whole batch) -- also through snn_train_step."""
+    rng = np.random.RandomState(40 + F)
+    B, n_rows, h0 = 50, 9, 6
+    ids = rng.randint(0, n_rows, (B, F)).astype(np.int32)
+    ids[rng.uniform(size=(B, F)) < 0.2] = -1
+    ids[3, :] = -1
+    ids[5, -1] = ids[5, 0] = 4                                   # the same feature twice on one line
+    ids[7, 0] = ids[8, F - 1] = 4                                # and in other columns on other lines
+    if F > 2:
+        ids[:, -1] = -1
+    ww0, bb0 = rng.standard_normal((n_rows, h0)) * 0.2, rng.standard_normal(h0) * 0.1
+    x = orc.snn_bag(ww0, bb0, ids)
+    gx = rng.standard_normal((B, h0))
+    wa, ba, wb, bb = ww0.copy(), bb0.copy(), ww0.copy(), bb0.copy()
+    orc.snn_update(wa, ba, ids, x, gx, 0.03)
+    orc.snn_update_vec(wb, bb, ids, x, gx, 0.03)
+    assert not np.allclose(wa, ww0) and not np.allclose(ba, bb0)
+    np.testing.assert_allclose(wb, wa, rtol=1e-13, atol=1e-15)
+    np.testing.assert_allclose(bb, ba, rtol=1e-13, atol=1e-15)
+    H1, H2 = 5, 3
+    p = {'w1': rng.standard_normal((h0, H1)) * 0.3, 'b1': np.zeros(H1), 'w2': rng.standard_normal((H1, H2)) * 0.3,
+         'b2': np.zeros(H2), 'w3': rng.standard_normal(H2) * 0.3, 'b3': 0.1}
+    y = (rng.uniform(size=B) < 0.4).astype(np.float64)
+    r1, r2 = np.ones(H1), np.ones(H2)
+    pa = {k: (v.copy() if isinstance(v, np.ndarray) else v) for k, v in p.items()}
+    wa, ba, wb, bb = ww0.copy(), bb0.copy(), ww0.copy(), bb0.copy()
+    a = orc.snn_train_step(pa, wa, ba, ids, y, r1, r2, 0.05, 0.01)
+    b = orc.snn_train_step(p, wb, bb, ids, y, r1, r2, 0.05, 0.01, vec=True)
+    assert a['loss'] == b['loss']
+    np.testing.assert_allclose(wb, wa, rtol=1e-13, atol=1e-15)
+    np.testing.assert_allclose(bb, ba, rtol=1e-13, atol=1e-15)
+
+
 def test_fm_oracle_gradient_is_the_dense_sgd_of_the_loss():
     """oracle/fm_oracle.py: one sgd_step equals theta - lr * numerical gradient of loss_value (data term
     + lambda * l2_loss over ALL parameters), with a repeated row and an absent field."""
