@@ -31,6 +31,7 @@ def parse_ptmzr(_ptmzr_argv):
 
 class FM(object):
     def __init__(self, batch_size, _rch_argv, _init_argv, _ptmzr_argv, _reg_argv, mode='train', eval_size=0, device=0):
+        """_rch_argv = [X_dim, X_feas, rank]: X_feas fields (1..64, one id per field), rank 0..127 (python/FM.py:7)."""
         import torch
         X_dim, X_feas, rank = _rch_argv                              # python/FM.py:7
         self.optimizer, self.lr, self.eps, self.reduce_mean = parse_ptmzr(_ptmzr_argv)

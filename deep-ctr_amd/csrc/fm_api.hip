@@ -5,6 +5,8 @@
 // streaming pass over the live elements of the table and its compact state (k_fm_opt_pass).
 // Wide rows (k >= 17, ranks 16..127: the reference's FM50 / FM100): rows of rup(k, 4) floats, the forward of fm_wide_body and
 // the bag table's wide sparse-row update (scatw1_body / scatw2_body); the sort, the tail and the optimiser pass are shared.
+// 1..64 fields on both layouts: the forwards take 16 fields at a time (fm_body<NF>, fm_wide_body<L, NC>; one instantiation per
+// 16 fields, the first being the 16-field kernels); the sort and both sparse-row updates are the FNN step's, sized by F.
 #include <hip/hip_runtime.h>
 
 #include <cmath>
@@ -25,8 +27,9 @@ namespace {
 thread_local std::string g_fm_err;
 inline int rup(int x, int m) { return (x + m - 1) / m * m; }
 
-// 16 lanes per example (lane = field): each lane loads its field's 64-byte row, the field sums
-// S_l = sum_f v_f[l] are 4-step shuffle reductions inside the 16-lane group.
+// 16 lanes per example: lane f owns fields f, f + 16, .. (NF = ceil(F / 16) of them; NF = 1 up to 16 fields, lane = field) and
+// loads their 64-byte rows, sums them in registers, and the field sums S_l = sum_f v_f[l] are 4-step shuffle reductions inside
+// the 16-lane group.
 struct FmArgs {
     const int32_t* ids; const float* y; int B, F, K; const float* table16; int64_t n_rows; const float* b;
     float scale, dscale; int train; float* gxp; int K1p; float* p_out; float* loss_t; float* gb_part; int* err;
@@ -35,27 +38,51 @@ struct FmArgs {
     int rw;                    // wide rows (fm_wide_body): the row stride in floats, a multiple of 4; gx' is [t][F][rw]
 };
 
+// store16_sel and the two wait states gfx950 needs before a VALU instruction may overwrite the data VGPRs of a store wider than 8
+// bytes: the compiler provides them after its own stores, not after store16_wt's inline assembly.  With several fields per lane the
+// next field's gradients are computed into the registers the previous store reads (NF = 1 stores last: store16_sel as it was).
+__device__ __forceinline__ void store16_sel_ws(const bool wt, float* p, const float4 v)
+{
+    u32x4 w; __builtin_memcpy(&w, &v, 16);
+    if (wt) asm volatile("global_store_dwordx4 %0, %1, off sc1\n\ts_nop 1" :: "v"(p), "v"(w) : "memory");
+    else *reinterpret_cast<u32x4*>(p) = w;
+}
+template <int NF>
 __device__ __forceinline__ void fm_body(const FmArgs& a, const int blk, float* s_gb)
 {
     const int tid = threadIdx.x, f = tid & 15, grp = tid >> 4;
     const int t = blk * 16 + grp;
-    int64_t id = -1;
-    if (t < a.B && f < a.F) {
-        id = a.ids[(size_t)t * a.F + f];
-        if (id < -1 || id >= a.n_rows) { atomicOr(a.err, 1); id = -1; }
-        if (a.stamp && id >= 0) a.stamp[id] = a.step;
-    }
-    float r[16];
+    int64_t id[NF];
 #pragma unroll
-    for (int q = 0; q < 4; ++q) {
-        float4 v = make_float4(0.f, 0.f, 0.f, 0.f);
-        if (id >= 0) v = *reinterpret_cast<const float4*>(a.table16 + (size_t)id * SLOT + 4 * q);
-        r[4 * q] = v.x * a.scale; r[4 * q + 1] = v.y * a.scale; r[4 * q + 2] = v.z * a.scale; r[4 * q + 3] = v.w * a.scale;
+    for (int n = 0; n < NF; ++n) {                          // every id first: the row loads below do not wait behind a stamp
+        const int fld = f + 16 * n;
+        id[n] = -1;
+        if (t < a.B && fld < a.F) {
+            id[n] = a.ids[(size_t)t * a.F + fld];
+            if (id[n] < -1 || id[n] >= a.n_rows) { atomicOr(a.err, 1); id[n] = -1; }
+            if (a.stamp && id[n] >= 0) a.stamp[id[n]] = a.step;
+        }
+    }
+    float r[NF][16];
+#pragma unroll
+    for (int n = 0; n < NF; ++n) {
+#pragma unroll
+        for (int q = 0; q < 4; ++q) {
+            float4 v = make_float4(0.f, 0.f, 0.f, 0.f);
+            if (id[n] >= 0) v = *reinterpret_cast<const float4*>(a.table16 + (size_t)id[n] * SLOT + 4 * q);
+            r[n][4 * q] = v.x * a.scale; r[n][4 * q + 1] = v.y * a.scale; r[n][4 * q + 2] = v.z * a.scale; r[n][4 * q + 3] = v.w * a.scale;
+        }
     }
     // yhat = b + sum_f w_f + 1/2 (sum_l S_l^2 - sum_f sum_l v_f[l]^2)                     (:56-63)
-    float lin = r[0], sq = 0.f, S[16];
+    float lin = r[0][0], sq = 0.f, S[16];
 #pragma unroll
-    for (int l = 1; l < 16; ++l) { S[l] = r[l]; sq = fmaf(r[l], r[l], sq); }
+    for (int l = 1; l < 16; ++l) { S[l] = r[0][l]; sq = fmaf(r[0][l], r[0][l], sq); }
+#pragma unroll
+    for (int n = 1; n < NF; ++n) {                          // the lane's further fields, in field order
+        lin += r[n][0];
+#pragma unroll
+        for (int l = 1; l < 16; ++l) { S[l] += r[n][l]; sq = fmaf(r[n][l], r[n][l], sq); }
+    }
 #pragma unroll
     for (int o = 1; o < 16; o <<= 1) {
         lin += __shfl_xor(lin, o, 16); sq += __shfl_xor(sq, o, 16);
@@ -78,59 +105,102 @@ __device__ __forceinline__ void fm_body(const FmArgs& a, const int blk, float* s
     } else if (a.train && f == 0) a.loss_t[t] = 0.f;
     if (!a.train) return;
     // d yhat / d w_f = 1 ; d yhat / d v_f[l] = S_l - v_f[l]   (x = 1)
-    float g[16];
-    g[0] = (id >= 0) ? delta : 0.f;
 #pragma unroll
-    for (int l = 1; l < 16; ++l) g[l] = (id >= 0 && l < a.K) ? delta * (S[l] - r[l]) : 0.f;
-    float* out = a.gxp + (size_t)t * a.K1p + f * SLOT;
-    if (f < a.F) {
+    for (int n = 0; n < NF; ++n) {
+        const int fld = f + 16 * n;
+        float g[16];
+        g[0] = (id[n] >= 0) ? delta : 0.f;
 #pragma unroll
-        for (int q = 0; q < 4; ++q) store16_sel(a.wt, out + 4 * q, make_float4(g[4 * q], g[4 * q + 1], g[4 * q + 2], g[4 * q + 3]));   // (written through: FM_WT=0 for plain stores)
+        for (int l = 1; l < 16; ++l) g[l] = (id[n] >= 0 && l < a.K) ? delta * (S[l] - r[n][l]) : 0.f;
+        float* out = a.gxp + (size_t)t * a.K1p + fld * SLOT;    // K1p = rup(F, 16) * SLOT
+        if (fld < a.F) {
+#pragma unroll
+            for (int q = 0; q < 4; ++q) {                   // (written through: FM_WT=0 for plain stores)
+                const float4 g4 = make_float4(g[4 * q], g[4 * q + 1], g[4 * q + 2], g[4 * q + 3]);
+                if (NF == 1) store16_sel(a.wt, out + 4 * q, g4);
+                else store16_sel_ws(a.wt, out + 4 * q, g4);
+            }
+        }
     }
     if (f == 0) s_gb[grp] = delta;
     __syncthreads();
     if (tid == 0) { float s = 0.f; for (int i = 0; i < 16; ++i) s += s_gb[i]; a.gb_part[blk] = s; }
 }
+template <int NF>
 __global__ __launch_bounds__(256) void k_fm(const FmArgs a)
 {
     __shared__ float s_gb[16];
-    fm_body(a, blockIdx.x, s_gb);
+    fm_body<NF>(a, blockIdx.x, s_gb);
 }
 // Wide rows (k >= 17): L lanes per example (16 while the row's rw / 4 float4 pieces fit, else 32); lane q owns columns 4q..4q+3
-// of every field's row and issues its example's F row loads together, so that S_l = sum_f v_f[l] is a register sum and only
-// the example's scalar b + lin + 1/2 sum_l (S_l^2 - sum_f v_f[l]^2) crosses lanes.  Lane f < F reads, checks and stamps field
-// f's id.  gx'[t][f] = delta * [1 | S - v_f], zero in the padding columns (>= K); absent fields are not written (no record
-// points at them).
-template <int L>
-__device__ __forceinline__ void fm_wide_body(const FmArgs& a, const int blk, float* s_gb /*[256 / L]*/)
+// of every field's row and issues its example's row loads 16 fields at a time, so that S_l = sum_f v_f[l] is a register sum and
+// only the example's scalar b + lin + 1/2 sum_l (S_l^2 - sum_f v_f[l]^2) crosses lanes.  Lane q reads, checks and stamps the ids
+// of fields q, q + L, .. (< F).  gx'[t][f] = delta * [1 | S - v_f], zero in the padding columns (>= K); absent fields are not
+// written (no record points at them).  More than 16 fields (NC = ceil(F / 16) chunks of 16): a rolled first pass sums every
+// chunk, the second reloads each chunk's rows and writes its gradients (holding the last chunk across the passes cost 30-40
+// VGPRs and an occupancy step).  NC = 1, up to 16 fields: the gradients from the rows still in registers, nothing reloaded.
+template <int L, int NR>
+__device__ __forceinline__ void fm_wide_chunk(const FmArgs& a, const int (&mine)[NR], const int c, const int q, const int nq,
+                                              int (&id)[16], float4 (&v)[16])
 {
-    constexpr int EPB = 256 / L;                          // examples per workgroup
-    const int tid = threadIdx.x, q = tid % L, grp = tid / L, nq = a.rw >> 2;
-    const int t = blk * EPB + grp;
-    int mine = -1;
-    if (t < a.B && q < a.F) {
-        const int64_t id = a.ids[(size_t)t * a.F + q];
-        if (id < -1 || id >= a.n_rows) atomicOr(a.err, 1);
-        else mine = (int)id;
-        if (a.stamp && mine >= 0) a.stamp[mine] = a.step;
-    }
-    int id[16];
-    float4 v[16];
+    // fields 16 c .. 16 c + 15 lie in one round of ids (L = 16 or 32): round 16 c / L, lanes 16 c % L + f
+    int m = mine[0];
+#pragma unroll
+    for (int r = 1; r < NR; ++r) m = (r == 16 * c / L) ? mine[r] : m;
 #pragma unroll
     for (int f = 0; f < 16; ++f) {
-        id[f] = __shfl(mine, f, L);                       // -1 for f >= F
+        id[f] = __shfl(m, 16 * c % L + f, L);             // -1 for fields >= F
         v[f] = (id[f] >= 0 && q < nq) ? *reinterpret_cast<const float4*>(a.table16 + (size_t)id[f] * a.rw + 4 * q)
                                       : make_float4(0.f, 0.f, 0.f, 0.f);
     }
-    float lin = 0.f;
-    float4 S = make_float4(0.f, 0.f, 0.f, 0.f), sq = S;
+}
+__device__ __forceinline__ void fm_wide_grads(const FmArgs& a, float* out, const int c, const int (&id)[16], const float4 (&v)[16],
+                                              const float4 S, const float delta)
+{
 #pragma unroll
     for (int f = 0; f < 16; ++f) {
-        v[f].x *= a.scale; v[f].y *= a.scale; v[f].z *= a.scale; v[f].w *= a.scale;
-        if (q == 0) { lin += v[f].x; v[f].x = 0.f; }      // column 0 is w_f
-        S.x += v[f].x; S.y += v[f].y; S.z += v[f].z; S.w += v[f].w;
-        sq.x = fmaf(v[f].x, v[f].x, sq.x); sq.y = fmaf(v[f].y, v[f].y, sq.y);
-        sq.z = fmaf(v[f].z, v[f].z, sq.z); sq.w = fmaf(v[f].w, v[f].w, sq.w);
+        if (id[f] < 0) continue;
+        const float4 g = make_float4(c == 0 ? delta : (c < a.K ? delta * (S.x - v[f].x) : 0.f),
+                                     c + 1 < a.K ? delta * (S.y - v[f].y) : 0.f,
+                                     c + 2 < a.K ? delta * (S.z - v[f].z) : 0.f,
+                                     c + 3 < a.K ? delta * (S.w - v[f].w) : 0.f);
+        store16_sel(a.wt, out + (size_t)f * a.rw, g);
+    }
+}
+template <int L, int NC>
+__device__ __forceinline__ void fm_wide_body(const FmArgs& a, const int blk, float* s_gb /*[256 / L]*/)
+{
+    constexpr int EPB = 256 / L;                          // examples per workgroup
+    constexpr int NR = (16 * NC + L - 1) / L;             // id rounds: lane q holds the ids of fields q, q + L, ..
+    const int tid = threadIdx.x, q = tid % L, grp = tid / L, nq = a.rw >> 2;
+    const int t = blk * EPB + grp;
+    int mine[NR];
+#pragma unroll
+    for (int r = 0; r < NR; ++r) {
+        const int fld = q + r * L;
+        mine[r] = -1;
+        if (t < a.B && fld < a.F) {
+            const int64_t id = a.ids[(size_t)t * a.F + fld];
+            if (id < -1 || id >= a.n_rows) atomicOr(a.err, 1);
+            else mine[r] = (int)id;
+            if (a.stamp && mine[r] >= 0) a.stamp[mine[r]] = a.step;
+        }
+    }
+    int id[16];
+    float4 v[16];
+    float lin = 0.f;
+    float4 S = make_float4(0.f, 0.f, 0.f, 0.f), sq = S;
+#pragma unroll 1
+    for (int c = 0; c < NC; ++c) {                        // rolled: one chunk's 16 rows in registers at a time
+        fm_wide_chunk<L, NR>(a, mine, c, q, nq, id, v);
+#pragma unroll
+        for (int f = 0; f < 16; ++f) {
+            v[f].x *= a.scale; v[f].y *= a.scale; v[f].z *= a.scale; v[f].w *= a.scale;
+            if (q == 0) { lin += v[f].x; v[f].x = 0.f; }      // column 0 is w_f
+            S.x += v[f].x; S.y += v[f].y; S.z += v[f].z; S.w += v[f].w;
+            sq.x = fmaf(v[f].x, v[f].x, sq.x); sq.y = fmaf(v[f].y, v[f].y, sq.y);
+            sq.z = fmaf(v[f].z, v[f].z, sq.z); sq.w = fmaf(v[f].w, v[f].w, sq.w);
+        }
     }
     // yhat = b + sum_f w_f + 1/2 (sum_l S_l^2 - sum_f sum_l v_f[l]^2)                     (:56-63)
     float part = lin + 0.5f * ((fmaf(S.x, S.x, -sq.x) + fmaf(S.y, S.y, -sq.y)) + (fmaf(S.z, S.z, -sq.z) + fmaf(S.w, S.w, -sq.w)));
@@ -149,48 +219,47 @@ __device__ __forceinline__ void fm_wide_body(const FmArgs& a, const int blk, flo
     } else if (a.train && q == 0) a.loss_t[t] = 0.f;
     if (!a.train) return;
     // d yhat / d w_f = 1 ; d yhat / d v_f[l] = S_l - v_f[l]   (x = 1)
-    if (q < nq) {
-        const int c = 4 * q;
-        float* out = a.gxp + (size_t)t * a.K1p + c;
+    float* out = a.gxp + (size_t)t * a.K1p + 4 * q;
+    if (NC == 1) {                                        // up to 16 fields: the rows are still in registers
+        if (q < nq) fm_wide_grads(a, out, 4 * q, id, v, S, delta);
+    } else {
+#pragma unroll 1
+        for (int c = 0; c < NC; ++c) {                    // every chunk's rows again (the shuffles with the whole group)
+            fm_wide_chunk<L, NR>(a, mine, c, q, nq, id, v);
 #pragma unroll
-        for (int f = 0; f < 16; ++f) {
-            if (id[f] < 0) continue;
-            const float4 g = make_float4(c == 0 ? delta : (c < a.K ? delta * (S.x - v[f].x) : 0.f),
-                                         c + 1 < a.K ? delta * (S.y - v[f].y) : 0.f,
-                                         c + 2 < a.K ? delta * (S.z - v[f].z) : 0.f,
-                                         c + 3 < a.K ? delta * (S.w - v[f].w) : 0.f);
-            store16_sel(a.wt, out + (size_t)f * a.rw, g);
+            for (int f = 0; f < 16; ++f) { v[f].x *= a.scale; v[f].y *= a.scale; v[f].z *= a.scale; v[f].w *= a.scale; }
+            if (q < nq) fm_wide_grads(a, out + (size_t)(16 * c) * a.rw, 4 * q, id, v, S, delta);
         }
     }
     if (q == 0) s_gb[grp] = delta;
     __syncthreads();
     if (tid == 0) { float s = 0.f; for (int i = 0; i < EPB; ++i) s += s_gb[i]; a.gb_part[blk] = s; }
 }
-template <int L>
+template <int L, int NC>
 __global__ __launch_bounds__(256) void k_fm_wide(const FmArgs a)
 {
     __shared__ float s_gb[256 / L];
-    fm_wide_body<L>(a, blockIdx.x, s_gb);
+    fm_wide_body<L, NC>(a, blockIdx.x, s_gb);
 }
-template <typename KT, int L>
+template <typename KT, int L, int NC>
 __global__ __launch_bounds__(256) void k_fm_wide_merge_fwd(const SortArgs so, const FmArgs a)
 {
     extern __shared__ __align__(16) unsigned char smem[];
     __shared__ float s_gb[256 / L];
     if ((int)blockIdx.x < so.nblk) { sortB_body<KT>(so, blockIdx.x, smem); return; }
-    fm_wide_body<L>(a, (int)blockIdx.x - so.nblk, s_gb);
+    fm_wide_body<L, NC>(a, (int)blockIdx.x - so.nblk, s_gb);
 }
 
 // A training step is four launches: run sorts of the batch's (row, t) keys; their rank merge BESIDE the forward + gradients
 // (both need only the ids: the merge takes 16 F workgroups, the examples the rest); level-1 sparse-row update; level-2 update
 // BESIDE the bias / loss tail.  As six launches in a row (sort, sort, forward, scatter, scatter, tail) the step took 49.6 us.
-template <typename KT>
+template <typename KT, int NF>
 __global__ __launch_bounds__(256) void k_fm_merge_fwd(const SortArgs so, const FmArgs a)
 {
     extern __shared__ __align__(16) unsigned char smem[];
     __shared__ float s_gb[16];
     if ((int)blockIdx.x < so.nblk) { sortB_body<KT>(so, blockIdx.x, smem); return; }
-    fm_body(a, (int)blockIdx.x - so.nblk, s_gb);
+    fm_body<NF>(a, (int)blockIdx.x - so.nblk, s_gb);
 }
 
 // The bias under Adam / FTRL: the state beside it (sb [2]) and this step's learning rate (Adam: lr_t).  opt = 0: SGD.
@@ -343,23 +412,34 @@ int init_opt_state(fm_handle* h)
     return FNN_OK;
 }
 
-// The wide path's forward: L = 16 lanes per example while a row's float4 pieces fit (rank <= 63), else 32; 256 / L examples
-// per workgroup.
-int wide_epb(const fm_handle* h) { return h->rw <= 64 ? 16 : 8; }
-template <typename KT>
-void launch_wide_fwd(const fm_handle* h, const SortArgs* sb, const FmArgs& a, int B)
+// The forwards of both layouts, one instantiation per 16 fields: NF = NC = ceil(F / 16) (1 up to 16 fields).  sb: the rank merge
+// of the batch's sort runs beside the forward (training), null: the forward alone (predictions).  nb: the examples' workgroups.
+template <typename KT, int N>
+void launch_fwd_n(const fm_handle* h, const SortArgs* sb, const FmArgs& a, int nb)
 {
-    const bool l16 = wide_epb(h) == 16;
-    const int nb = rup(B, wide_epb(h)) / wide_epb(h);
-    if (!sb) {
-        if (l16) hipLaunchKernelGGL(k_fm_wide<16>, dim3(nb), dim3(256), 0, h->st, a);
-        else hipLaunchKernelGGL(k_fm_wide<32>, dim3(nb), dim3(256), 0, h->st, a);
-    } else if (l16) {
-        hipLaunchKernelGGL((k_fm_wide_merge_fwd<KT, 16>), dim3(sb->nblk + nb), dim3(256), sort_lds_bytes<KT>(), h->st, *sb, a);
+    if (!h->wide) {
+        if (!sb) hipLaunchKernelGGL(k_fm<N>, dim3(nb), dim3(256), 0, h->st, a);
+        else hipLaunchKernelGGL((k_fm_merge_fwd<KT, N>), dim3(sb->nblk + nb), dim3(256), sort_lds_bytes<KT>(), h->st, *sb, a);
+    } else if (h->rw <= 64) {         // L = 16 lanes per example while a row's float4 pieces fit (rank <= 63), else 32
+        if (!sb) hipLaunchKernelGGL((k_fm_wide<16, N>), dim3(nb), dim3(256), 0, h->st, a);
+        else hipLaunchKernelGGL((k_fm_wide_merge_fwd<KT, 16, N>), dim3(sb->nblk + nb), dim3(256), sort_lds_bytes<KT>(), h->st, *sb, a);
     } else {
-        hipLaunchKernelGGL((k_fm_wide_merge_fwd<KT, 32>), dim3(sb->nblk + nb), dim3(256), sort_lds_bytes<KT>(), h->st, *sb, a);
+        if (!sb) hipLaunchKernelGGL((k_fm_wide<32, N>), dim3(nb), dim3(256), 0, h->st, a);
+        else hipLaunchKernelGGL((k_fm_wide_merge_fwd<KT, 32, N>), dim3(sb->nblk + nb), dim3(256), sort_lds_bytes<KT>(), h->st, *sb, a);
     }
 }
+template <typename KT>
+void launch_fwd(const fm_handle* h, const SortArgs* sb, const FmArgs& a, int nb)
+{
+    switch ((h->F + 15) / 16) {
+    case 1: launch_fwd_n<KT, 1>(h, sb, a, nb); break;
+    case 2: launch_fwd_n<KT, 2>(h, sb, a, nb); break;
+    case 3: launch_fwd_n<KT, 3>(h, sb, a, nb); break;
+    default: launch_fwd_n<KT, 4>(h, sb, a, nb); break;
+    }
+}
+// The wide path's forward: 256 / L examples per workgroup (L = 16 while rank <= 63, else 32).
+int wide_epb(const fm_handle* h) { return h->rw <= 64 ? 16 : 8; }
 
 // The wide step (k >= 17): the same sort, forward + gradients beside the rank merge (k_fm_wide_merge_fwd), then the bag table's
 // wide sparse-row update -- level 1, level 2 beside the bias / loss tail -- into the rows (SGD) or the gradient store G.
@@ -367,7 +447,7 @@ int fm_run_wide(fm_handle* h, FmArgs a, int B, float lr, float lambda, int reduc
 {
     const int F = h->F, ex = wide_epb(h), Ba = rup(B, ex);
     if (!a.train) {
-        launch_wide_fwd<unsigned>(h, nullptr, a, B);
+        launch_fwd<unsigned>(h, nullptr, a, Ba / ex);
         MHK(h, hipGetLastError());
         return FNN_OK;
     }
@@ -375,10 +455,10 @@ int fm_run_wide(fm_handle* h, FmArgs a, int B, float lr, float lambda, int reduc
     SortArgs sb = so; sb.nblk = 16 * F;
     if (h->key64) {
         hipLaunchKernelGGL((k_sortA<unsigned long long>), dim3(4 * F), dim3(256), 0, h->st, so);
-        launch_wide_fwd<unsigned long long>(h, &sb, a, B);
+        launch_fwd<unsigned long long>(h, &sb, a, Ba / ex);
     } else {
         hipLaunchKernelGGL((k_sortA<unsigned>), dim3(4 * F), dim3(256), 0, h->st, so);
-        launch_wide_fwd<unsigned>(h, &sb, a, B);
+        launch_fwd<unsigned>(h, &sb, a, Ba / ex);
     }
     // SGD: the dense decay is the lazy scale, touched rows -= lr * g / scale; Adam / FTRL: G[row] = G[row] - (-1) * sum
     if (!opt) h->scale *= 1.0 - (double)lr * (double)lambda;
@@ -427,7 +507,7 @@ int fm_run(fm_handle* h, const int32_t* ids, const float* y, int B, float lr, fl
         return FNN_OK;
     }
     if (!train) {
-        hipLaunchKernelGGL(k_fm, dim3(Ba / 16), dim3(256), 0, h->st, a);
+        launch_fwd<unsigned>(h, nullptr, a, Ba / 16);
         MHK(h, hipGetLastError());
         return FNN_OK;
     }
@@ -436,10 +516,10 @@ int fm_run(fm_handle* h, const int32_t* ids, const float* y, int B, float lr, fl
         SortArgs sb = so; sb.nblk = 16 * F;
         if (h->key64) {
             hipLaunchKernelGGL((k_sortA<unsigned long long>), dim3(4 * F), dim3(256), 0, h->st, so);
-            hipLaunchKernelGGL((k_fm_merge_fwd<unsigned long long>), dim3(16 * F + Ba / 16), dim3(256), SORT_N * 8, h->st, sb, a);
+            launch_fwd<unsigned long long>(h, &sb, a, Ba / 16);
         } else {
             hipLaunchKernelGGL((k_sortA<unsigned>), dim3(4 * F), dim3(256), 0, h->st, so);
-            hipLaunchKernelGGL((k_fm_merge_fwd<unsigned>), dim3(16 * F + Ba / 16), dim3(256), SORT_N * 4, h->st, sb, a);
+            launch_fwd<unsigned>(h, &sb, a, Ba / 16);
         }
     }
     if (opt) {   // Adam / FTRL: the same sorted sums land in the zeroed gradient store: G[row] = 0 * 1 - (-1) * sum
@@ -473,14 +553,14 @@ int fm_create(int n_fields, int k, int max_batch, int device, void* stream, fm_h
 {
     if (!out) { g_fm_err = "null argument"; return FNN_ERR_ARG; }
     *out = nullptr;
-    if (n_fields < 1 || n_fields > 16 || k < 1 || k > 128 || max_batch < 1 || max_batch > SORT_N) {
-        g_fm_err = "need 1 <= n_fields <= 16, 1 <= k <= 128 (rank 0..127), 1 <= max_batch <= 4096"; return FNN_ERR_ARG; }
+    if (n_fields < 1 || n_fields > 64 || k < 1 || k > 128 || max_batch < 1 || max_batch > SORT_N) {
+        g_fm_err = "need 1 <= n_fields <= 64, 1 <= k <= 128 (rank 0..127), 1 <= max_batch <= 4096"; return FNN_ERR_ARG; }
     int ndev = 0;
     if (hipGetDeviceCount(&ndev) != hipSuccess || ndev <= 0) { g_fm_err = "no HIP device (libfnn_hip.so has no CPU fallback)"; return FNN_ERR_HIP; }
     fm_handle* h = new fm_handle();
     h->dev = device; h->F = n_fields; h->K = k; h->Bmax = max_batch;
     h->wide = k > 16; h->rw = h->wide ? rup(k, 4) : SLOT;
-    h->K1p = h->wide ? n_fields * h->rw : 16 * SLOT;                // gx' of an example: 16 slots, or [F][rw] on the wide path
+    h->K1p = h->wide ? n_fields * h->rw : rup(n_fields, 16) * SLOT;   // gx' of an example: a slot per field of rup(F, 16), or [F][rw]
     auto fail = [&](int code) { g_fm_err = h->err; fm_destroy(h); return code; };
 #define FK(expr) do { hipError_t e2_ = (expr); if (e2_ != hipSuccess) { h->err = std::string(#expr) + ": " + hipGetErrorString(e2_); return fail(FNN_ERR_HIP); } } while (0)
     FK(hipSetDevice(h->dev));

@@ -87,7 +87,7 @@ def load_ipinyou_file(path, max_dim, max_fea):
 
 
 def to_field_ids(X_ind, X_val, field_of_row):
-    """Bridge to the HIP path: padded index lists -> ids int32 [n,16] with slot = field and -1 for
+    """Bridge to the HIP path: padded index lists -> ids int32 [n, n_fields] with slot = field and -1 for
     empty fields (pads have X_val == 0)."""
     n = X_ind.shape[0]
     n_fields = int(field_of_row.max()) + 1

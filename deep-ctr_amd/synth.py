@@ -17,9 +17,17 @@ _IPINYOU_SIZES = [7, 24, 40, None, 35, 370, 5, 100000, 130000, 21, 14, 11, 4, 70
 IPINYOU_DIMS = 937670
 
 
-def field_sizes_ipinyou(total=IPINYOU_DIMS):
+def field_sizes_ipinyou(total=IPINYOU_DIMS, n_fields=16):
+    """The 16 iPinYou-like field sizes summing to `total`.  Another field count cycles those 16 sizes over n_fields fields and
+    rescales them to the same total (every field keeps at least one row; the rounding remainder goes to the largest field)."""
     rest = sum(s for s in _IPINYOU_SIZES if s is not None)
-    return [s if s is not None else total - rest for s in _IPINYOU_SIZES]
+    base = [s if s is not None else total - rest for s in _IPINYOU_SIZES]
+    if n_fields == 16:
+        return base
+    cyc = [base[f % 16] for f in range(n_fields)]
+    out = [max(1, int(round(s * float(total) / sum(cyc)))) for s in cyc]
+    out[int(np.argmax(out))] += total - sum(out)
+    return out
 
 
 def field_sizes_tiny(total=1000, n_fields=16):

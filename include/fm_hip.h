@@ -9,17 +9,18 @@
  * python/ipinyou.py:136-173.  One feature per field with value 1 (iPinYou; `load_ipinyou_data`
  * returns X_val = 1); ids [B, F] int32 with -1 = absent.
  *
- * Ranks 0..127 (k = rank + 1 = 1..128: python/baseline.py's FM10, FM50 and FM100), 1..16 fields, batches up to 4096.
- * Row layout on the device: k <= 16 keeps the FNN path's 64-byte rows (16 floats, one lane per field in the forward);
- * k >= 17 takes the wide path, rows of rup(k, 4) floats (k = 101: 104) so that every row piece is one 16-byte access,
- * a half or quarter wave per example in the forward.  The library picks the layout from k; padding columns are zero and
- * stay zero.  The host sees [n_rows, k] either way.
+ * Ranks 0..127 (k = rank + 1 = 1..128: python/baseline.py's FM10, FM50 and FM100), 1..64 fields (python/baseline.py's
+ * 39-column runs included), batches up to 4096.
+ * Row layout on the device: k <= 16 keeps the FNN path's 64-byte rows (16 floats; in the forward a lane per field up to 16
+ * fields, beyond that lane f takes fields f, f + 16, ..); k >= 17 takes the wide path, rows of rup(k, 4) floats (k = 101: 104)
+ * so that every row piece is one 16-byte access, a half or quarter wave per example in the forward, 16 fields at a time.  The
+ * library picks the layout from k; padding columns are zero and stay zero.  The host sees [n_rows, k] either way.
  *
  * A row id belongs to ONE field (iPinYou: every field owns its own range of ids).  The update groups a batch's entries per
  * field: inside a field, repeated rows sum their gradients in example order; a row that appears under two fields of one
  * batch is updated by two unordered read-modify-writes in one launch, so one field's contribution can be lost (both
- * layouts; not checked).  Predictions and the loss are exact for any ids.  A model of rank > 14 does not feed the FNN step,
- * whose k stays <= 15 (fnn_create refuses it).
+ * layouts; not checked).  Predictions and the loss are exact for any ids.  Of the ranks, only 15 (k = 16) does not feed the FNN
+ * step: fnn_create refuses k = 16 (its other limits: fnn_hip.h).
  *
  * The L2 term makes TensorFlow's gradient DENSE: every step multiplies the whole table by
  * (1 - lr * lambda).  Here the table is kept as `scale * stored` -- the decay is one scalar
@@ -52,7 +53,7 @@ typedef struct fm_handle fm_handle;
 
 const char* fm_last_error(const fm_handle* h);
 /* k = rank + 1 (row = [w | v_1..v_rank]), 1 <= k <= 128 (rank 0..127; k >= 17: the wide row layout above);
- * 1 <= n_fields <= 16; 1 <= max_batch <= 4096.  FNN_ERR_ARG otherwise. */
+ * 1 <= n_fields <= 64; 1 <= max_batch <= 4096.  FNN_ERR_ARG otherwise. */
 int fm_create(int n_fields, int k, int max_batch, int device, void* stream, fm_handle** out);
 int fm_destroy(fm_handle* h);
 int fm_sync(fm_handle* h);

@@ -1,7 +1,7 @@
 """Per-step time of FM / LR pre-training under SGD, Adam and FTRL at the iPinYou shape (937,670 rows, 16 fields, batch 4096),
 and the bytes the Adam / FTRL optimiser pass (k_fm_opt_pass in fm_api.hip) must move.  One JSON line on stdout.
 
-  python tools/fm_optim_bench.py [--steps 300 --warmup 30] [--only NAME,..]
+  python tools/fm_optim_bench.py [--steps 300 --warmup 30] [--only NAME,..] [--fields N]
   python tools/fm_optim_bench.py --from-stats NAME=DIR ..    (kernel times of separate rocprofv3 --kernel-trace --stats runs,
                                                               one config each: the pass time and its TB/s)
 
@@ -10,7 +10,10 @@ and the bytes the Adam / FTRL optimiser pass (k_fm_opt_pass in fm_api.hip) must 
 
 Configurations: fm_sgd / fm_adam / fm_ftrl (rank 10), lr_ftrl (rank 0 = LR); *_dense: the A/B variant of the pass that reads and
 clears the whole gradient store G (FM_OPT_DENSE_G=1) instead of the rows the step's stamp marks.  The wide path (k >= 17):
-fm50_* / fm100_* (the reference's FM50 / FM100), and fm100_adam_b100 at python/baseline.py's FM batch of 100."""
+fm50_* / fm100_* (the reference's FM50 / FM100), and fm100_adam_b100 at python/baseline.py's FM batch of 100.
+
+--fields N (1..64, default 16): the same 937,670 rows spread over N fields -- synth.field_sizes_ipinyou(n_fields=N) cycles the
+16 iPinYou-like field sizes over the N fields and rescales them to the same total.  16 is the shape above, unchanged."""
 import argparse
 import ctypes as C
 import glob
@@ -64,7 +67,7 @@ def shape():
     sys.path.insert(0, ROOT)
     import deep_ctr_amd  # noqa: F401
     from deep_ctr_amd import synth
-    sizes = synth.field_sizes_ipinyou()
+    sizes = synth.field_sizes_ipinyou(n_fields=F)
     return sizes, sum(sizes)
 
 
@@ -175,7 +178,10 @@ def main():
     ap.add_argument('--only', default=','.join(CONFIGS))
     ap.add_argument('--from-stats', nargs='+', default=None)
     ap.add_argument('--digest', action='store_true')
+    ap.add_argument('--fields', type=int, default=16)
     a = ap.parse_args()
+    global F
+    F = a.fields
     if a.from_stats:
         print(json.dumps(from_stats(a.from_stats)))
         return
