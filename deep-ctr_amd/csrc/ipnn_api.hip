@@ -429,6 +429,183 @@ static __global__ __launch_bounds__(256) void k_ip_scatw2(const ScatArgs sa)
 }
 
 // ------------------------------------------------------------------------------------------
+// Many fields (33 .. 64 fields of narrow rows, k <= 16: the reference's own 39 columns): k_ip_fwd's tile of 16 examples x
+// (17 F + D0p) floats passes the LDS above 45 fields with pairs (164,736 B at 46, 266,240 B at 64), and where it still fits it
+// leaves one workgroup per CU.  These two kernels (each chosen on its own: ip_many_choice) stage the embeddings only, as the wide pair does, on the 16-float slots of
+// the narrow table: the forward takes IPM_EX = 8 examples per workgroup (8 x F x 17 floats: 34,816 B at 64 fields, four
+// workgroups per CU) and computes every a0 value in registers -- a thread owns EPL consecutive columns of the 8 examples: one
+// lane slot of each example's F-layout row and whole lane slots of the T layout.  At 64 fields 2016 of the 3042 used columns
+// are pair products, so the column -> (i, j) walk of k_ip_fwd (up to F - 1 trips per column) is a table here (ptab, written at
+// create beside ref0: i | j << 8).  The backward takes IPM_BEX = 4 examples: their embeddings and the pair slice of dz
+// (4 x (16 F + P) floats: 48,640 B at 64 fields, three workgroups per CU).
+// ------------------------------------------------------------------------------------------
+constexpr int IPM_EX = 8;       // examples per workgroup of the many-field forward
+constexpr int IPM_BEX = 4;      // ... and of the backward
+struct IpManyArgs {
+    int P; const int32_t* ids; int B, F, K; const float* table16; int64_t n_rows; const float* b;
+    const uint8_t* mask; int d0; float inv_keep; int act; int D0p, ldT; int* err;
+    const unsigned short* ptab; // [P]: pair n = (i, j), i < j, row-major, as i | j << 8
+    bool wt;                    // outputs written through (IPNN_WT=0: plain stores)
+    unsigned a0_bytes, emb_bytes;   // sizes of a0 / a0T and of emb: the extent of the write-through stores' buffer resources
+};
+inline size_t ipm_fwd_lds(int F) { return (size_t)IPM_EX * F * (SLOT + 1) * sizeof(float); }
+inline size_t ipm_bwd_lds(int F, int P) { return (size_t)IPM_BEX * (F * SLOT + P) * sizeof(float); }
+
+template <typename T>
+static __global__ __launch_bounds__(256) void k_ip_fwd_m(const IpManyArgs a, T* __restrict__ a0, T* __restrict__ a0T, float* __restrict__ emb)
+{
+    typedef typename Traits<T>::frag frag;
+    constexpr int EPL = Traits<T>::EPL, SP = SLOT + 1;
+    extern __shared__ __align__(16) unsigned char smem[];
+    float* se = reinterpret_cast<float*>(smem);                 // [IPM_EX][F][17]: lanes reading slot l of different fields fall on different banks
+    const int F = a.F, K = a.K, FS = F * SLOT, FSP = F * SP, CB = FS + a.P, B = a.B;
+    const int t0 = blockIdx.x * IPM_EX;
+    const __amdgpu_buffer_rsrc_t r_emb = ipw_rsrc(emb, a.emb_bytes), r_a0 = ipw_rsrc(a0, a.a0_bytes), r_a0T = ipw_rsrc(a0T, a.a0_bytes);
+    // gather: IPM_EX x F rows of four 16-byte pieces, four in flight per thread; the raw rows also go to emb (the backward's copy)
+    const int n = IPM_EX * F * 4;
+    for (int e0 = threadIdx.x; e0 < n; e0 += 256 * 4) {
+        int64_t id[4];
+#pragma unroll
+        for (int j = 0; j < 4; ++j) {
+            const int e = e0 + 256 * j, t = t0 + (e >> 2) / F, f = (e >> 2) % F;
+            id[j] = (e < n && t < B) ? (int64_t)a.ids[(size_t)t * F + f] : -1;
+            if (e < n && t < B && (id[j] < 0 || id[j] >= a.n_rows)) { if (a.err) atomicOr(a.err, 1); id[j] = -1; }
+        }
+        float4 v[4];
+#pragma unroll
+        for (int j = 0; j < 4; ++j) {
+            const int e = e0 + 256 * j;
+            v[j] = id[j] >= 0 ? *reinterpret_cast<const float4*>(a.table16 + (size_t)id[j] * SLOT + 4 * (e & 3)) : make_float4(0.f, 0.f, 0.f, 0.f);
+        }
+#pragma unroll
+        for (int j = 0; j < 4; ++j) {
+            const int e = e0 + 256 * j;
+            if (e >= n) continue;
+            const int r = (e >> 2) / F, f = (e >> 2) % F, q = e & 3;
+            float* d = se + r * FSP + f * SP + 4 * q;
+            d[0] = v[j].x; d[1] = v[j].y; d[2] = v[j].z; d[3] = v[j].w;
+            if (emb) ipw_store16(a.wt, r_emb, emb, ((size_t)(t0 + r) * FS + f * SLOT + 4 * q) * 4, v[j]);
+        }
+    }
+    __syncthreads();
+    const float bval = *a.b;
+    for (int g = threadIdx.x; g < a.D0p / EPL; g += 256) {
+        float v[IPM_EX][EPL];
+#pragma unroll
+        for (int x = 0; x < EPL; ++x) {
+            const int c = g * EPL + x;
+            int ref = -1, pi = 0, pj = 0;                       // ref: column in the reference's z1 order
+            if (c < FS) { if ((c & 15) < K) ref = (c >> 4) * K + (c & 15); }
+            else if (c < CB) { const unsigned pr = a.ptab[c - FS]; pi = (int)(pr & 255u); pj = (int)(pr >> 8); ref = F * K + (c - FS); }
+            else if (c == CB) ref = a.d0 - 1;
+            float mk[IPM_EX];                                   // the column's keep-mask bytes: one round trip, under the products
+#pragma unroll
+            for (int r = 0; r < IPM_EX; ++r)
+                mk[r] = (a.mask && ref >= 0 && t0 + r < B) ? (float)a.mask[(size_t)(t0 + r) * a.d0 + ref] * a.inv_keep : 1.0f;
+            float z[IPM_EX];
+#pragma unroll
+            for (int r = 0; r < IPM_EX; ++r) z[r] = 0.f;
+            if (c < FS) {
+#pragma unroll
+                for (int r = 0; r < IPM_EX; ++r) z[r] = se[r * FSP + (c >> 4) * SP + (c & 15)];
+            } else if (c < CB) {
+                const float* qi = se + pi * SP;
+                const float* qj = se + pj * SP;
+                for (int l = 0; l < K; ++l)
+#pragma unroll
+                    for (int r = 0; r < IPM_EX; ++r) z[r] = fmaf(qi[r * FSP + l], qj[r * FSP + l], z[r]);
+            } else if (c == CB) {
+#pragma unroll
+                for (int r = 0; r < IPM_EX; ++r) z[r] = bval;
+            }
+#pragma unroll
+            for (int r = 0; r < IPM_EX; ++r) {
+                float val = 0.f;
+                if (t0 + r < B) {
+                    if (ref >= 0) val = ip_act(z[r], a.act) * mk[r];
+                    else if (c == CB + 1) val = 1.0f;
+                }
+                v[r][x] = val;
+            }
+        }
+#pragma unroll
+        for (int r = 0; r < IPM_EX; ++r) {                       // F layout: the EPL columns of an example are one lane slot
+            frag fv;
+#pragma unroll
+            for (int x = 0; x < EPL; ++x) fv[x] = (T)v[r][x];
+            ipw_store16(a.wt, r_a0, a0, ft_off<T>(t0 + r, g * EPL, a.D0p) * sizeof(T), fv);
+        }
+#pragma unroll
+        for (int x = 0; x < EPL; ++x)                           // T layout: a column's examples are consecutive k
+#pragma unroll
+            for (int r = 0; r < IPM_EX; r += 4)
+                ipw_store4(a.wt, r_a0T, a0T, ft_off<T>(g * EPL + x, t0 + r, a.ldT), v[r][x], v[r + 1][x], v[r + 2][x], v[r + 3][x]);
+    }
+}
+
+// Many-field backward: gx'[t][16 f + l] = dz[t][16 f + l] + sum_{j != f} dz[t][pair(f, j)] e_j[l] (l < k; pad columns 0) and the
+// per-workgroup partial of db (one per IPM_BEX examples).  The embeddings come from emb (the forward's copy).  A wave holds four
+// fields x 16 slots: its read of e_j[l] is 16 addresses broadcast to the four fields, its read of the pair delta four addresses.
+static __global__ __launch_bounds__(256) void k_ip_bwd_m(const IpManyArgs a, const float* __restrict__ dz, const float* __restrict__ emb,
+                                                          float* __restrict__ gxp, float* __restrict__ gb_part)
+{
+    extern __shared__ __align__(16) unsigned char smem[];
+    const int F = a.F, K = a.K, FS = F * SLOT, P = a.P, CB = FS + P, D0p = a.D0p;
+    float* se = reinterpret_cast<float*>(smem);                 // [IPM_BEX][16 F]
+    float* sp = se + IPM_BEX * FS;                              // [IPM_BEX][P]
+    const int t0 = blockIdx.x * IPM_BEX;
+    {
+        const int n4 = IPM_BEX * FS / 4;                        // the examples' rows are contiguous in emb
+        const float4* src = reinterpret_cast<const float4*>(emb + (size_t)t0 * FS);
+        for (int e0 = threadIdx.x; e0 < n4; e0 += 256 * 4) {
+            float4 v[4];
+#pragma unroll
+            for (int k = 0; k < 4; ++k) { const int e = e0 + 256 * k; v[k] = e < n4 ? src[e] : make_float4(0.f, 0.f, 0.f, 0.f); }
+#pragma unroll
+            for (int k = 0; k < 4; ++k) { const int e = e0 + 256 * k; if (e < n4) reinterpret_cast<float4*>(se)[e] = v[k]; }
+        }
+        // the pair slice of each example starts at column 16 F of a row of D0p floats: both multiples of 4, 16-byte pieces up to
+        // the last whole one, the rest one float at a time
+        const int p4 = P >> 2;
+        for (int e = threadIdx.x; e < IPM_BEX * p4; e += 256) {
+            const int r = e / p4, q = e - r * p4;
+            const float4 v = *reinterpret_cast<const float4*>(dz + (size_t)(t0 + r) * D0p + FS + 4 * q);
+            float* d = sp + r * P + 4 * q;
+            d[0] = v.x; d[1] = v.y; d[2] = v.z; d[3] = v.w;
+        }
+        const int rest = P & 3;
+        if ((int)threadIdx.x < IPM_BEX * rest) {
+            const int r = threadIdx.x / rest, q = 4 * p4 + threadIdx.x % rest;
+            sp[r * P + q] = dz[(size_t)(t0 + r) * D0p + FS + q];
+        }
+    }
+    __syncthreads();
+    for (int c = threadIdx.x; c < FS; c += 256) {               // a thread owns (field f, slot l) for the IPM_BEX examples
+        const int f = c >> 4, l = c & 15;
+        float g[IPM_BEX];
+#pragma unroll
+        for (int r = 0; r < IPM_BEX; ++r) g[r] = l < K ? dz[(size_t)(t0 + r) * D0p + c] : 0.f;
+        if (l < K && P) {
+            // pair (i, j), i < j, sits at i (2F - i - 1) / 2 + (j - i - 1): partners below f walk down the column of f, partners
+            // above it along its row
+            for (int j = 0; j < f; ++j) {
+                const int m = j * (2 * F - j - 1) / 2 + (f - j - 1);
+#pragma unroll
+                for (int r = 0; r < IPM_BEX; ++r) g[r] = fmaf(sp[r * P + m], se[r * FS + j * SLOT + l], g[r]);
+            }
+            const int m0 = f * (2 * F - f - 1) / 2 - f - 1;
+            for (int j = f + 1; j < F; ++j) {
+#pragma unroll
+                for (int r = 0; r < IPM_BEX; ++r) g[r] = fmaf(sp[r * P + m0 + j], se[r * FS + j * SLOT + l], g[r]);
+            }
+        }
+#pragma unroll
+        for (int r = 0; r < IPM_BEX; ++r) gxp[(size_t)(t0 + r) * D0p + c] = g[r];
+    }
+    if (threadIdx.x == 0) { float s = 0.f; for (int r = 0; r < IPM_BEX; ++r) s += dz[(size_t)(t0 + r) * D0p + CB]; gb_part[blockIdx.x] = s; }
+}
+
+// ------------------------------------------------------------------------------------------
 // GEMM epilogues of the deep stack.
 // ------------------------------------------------------------------------------------------
 // All activation / delta matrices of the stack are FRAGMENT-TILED (ft_off) in both orientations:
@@ -1244,6 +1421,9 @@ struct ipnn_handle {
     int rw = SLOT;                               // row stride of the table and field stride of layer 0: SLOT, or rup(k, 4) when wide
     int* noshare = nullptr;                      // wide: [n_rows] zeros, the wide scatter's tag_shared (a row belongs to one field)
     bool wide_attr = false;                      // the wide launches' dynamic-LDS opt-in is set
+    bool many_fwd = false, many_bwd = false;     // 33 .. 64 fields of narrow rows: k_ip_fwd_m / k_ip_bwd_m (each chosen at create: ip_many_choice)
+    bool many_attr = false;                      // their dynamic-LDS opt-in is set
+    unsigned short* ptab = nullptr;              // many: [P] pair n -> i | j << 8
     std::vector<int> sk;                         // split-K of each layer's weight-gradient product
     bool adam = false; int64_t adam_t = 0;       // Adam / FTRL: two state tensors beside every variable, dense row-gradient table; step count
     bool ftrl = false;
@@ -1311,6 +1491,8 @@ struct IpProf {                                      // one segment of ip_run on
 namespace {
 
 size_t ts(const ipnn_handle* h) { return h->bf16 ? 2 : 4; }
+// examples per workgroup of the handle's inner-product backward: the grain of gb_part
+int ip_bwd_ex(const ipnn_handle* h) { return h->wide ? IPW_EX : h->many_bwd ? IPM_BEX : 16; }
 
 template <typename T> void ip_refresh(ipnn_handle* h, int t, const float* slab, float lr) {      // t = 1..L+1
     const int Din = h->Dp[t - 1], Dout = h->Dp[t];
@@ -1337,6 +1519,34 @@ static int ip_join(ipnn_handle* h)
 
 // the wide launches' arguments (k_ip_fwd_w / k_ip_bwd_w) and their dynamic-LDS opt-in: one fixed ceiling for every handle (the
 // attribute belongs to the kernel, not to the handle; the widest shape takes 132 / 147 KB)
+// Which inner-product kernels a narrow handle runs.  Up to 32 fields: always the 16-example pair (k_ip_fwd / k_ip_bwd).  Above,
+// each direction has its own crossover, both measured: the 4-example backward wins from 33 fields on
+// (IPM_BWD_MIN_FIELDS; IPNN_MANY_MIN is the A/B knob), the 16-example forward wins wherever its tile fits the 160 KiB of LDS,
+// so the 8-example forward takes over where it does not: 46 fields and more with pairs (IPM_FWD_MIN_FIELDS = 65 means "by LDS
+// only"; IPNN_MANY_FWD_MIN is the A/B knob).  Neither knob goes below 33.
+constexpr int IPM_BWD_MIN_FIELDS = 33, IPM_FWD_MIN_FIELDS = 65;
+inline size_t ip16_lds(int F, int Dp0) { return (size_t)16 * (F * (SLOT + 1) + Dp0) * sizeof(float); }
+inline bool ip_many_choice(int F, int Dp0, int dflt, const char* knob)
+{
+    if (F <= 32) return false;
+    int mn = dflt;
+    if (const char* e = getenv(knob)) mn = std::max(33, atoi(e));
+    return F >= mn || ip16_lds(F, Dp0) > (size_t)160 * 1024;
+}
+IpManyArgs ip_many_args(const ipnn_handle* h, const int32_t* ids, int B, const uint8_t* mask0, float inv_keep)
+{
+    return IpManyArgs{h->P, ids, B, h->F, h->K, h->table16, h->n_rows, h->b, mask0, h->d[0], inv_keep, h->cfg.act, h->Dp[0], h->ldT,
+                      h->err_flag, h->ptab, h->wt, (unsigned)((size_t)h->ldT * h->Dp[0] * ts(h)), (unsigned)((size_t)h->ldT * h->F * SLOT * 4)};
+}
+int ip_many_attr(ipnn_handle* h)
+{
+    if (h->many_attr) return FNN_OK;
+    IHK(h, hipFuncSetAttribute(reinterpret_cast<const void*>(&k_ip_fwd_m<float>), hipFuncAttributeMaxDynamicSharedMemorySize, 64 * 1024));
+    IHK(h, hipFuncSetAttribute(reinterpret_cast<const void*>(&k_ip_fwd_m<bf16_t>), hipFuncAttributeMaxDynamicSharedMemorySize, 64 * 1024));
+    IHK(h, hipFuncSetAttribute(reinterpret_cast<const void*>(&k_ip_bwd_m), hipFuncAttributeMaxDynamicSharedMemorySize, 64 * 1024));
+    h->many_attr = true;
+    return FNN_OK;
+}
 IpWideArgs ip_wide_args(const ipnn_handle* h, const int32_t* ids, int B, const uint8_t* mask0, float inv_keep)
 {
     return IpWideArgs{h->P, ids, B, h->F, h->K, h->rw, h->table16, h->n_rows, h->b, mask0, h->d[0], inv_keep, h->cfg.act, h->Dp[0],
@@ -1358,7 +1568,7 @@ int ip_run(ipnn_handle* h, const int32_t* ids, const float* y, int B, const uint
 {
     const int Ba = rup(B, 256), L = h->L, F = h->F, ldT = h->ldT;
     const float keep = h->cfg.keep_prob, inv_keep = 1.0f / keep;
-    const size_t lds_ip = (size_t)16 * (F * (SLOT + 1) + h->Dp[0]) * sizeof(float);    // k_ip_fwd pads its embedding tile
+    const size_t lds_ip = ip16_lds(F, h->Dp[0]);                 // k_ip_fwd pads its embedding tile
     const bool drop = train && masks;
     if (drop) for (int t = 0; t <= L; ++t) if (!masks[t]) IFAIL(h, FNN_ERR_ARG, "masks: null entry");
     { const int jrc = ip_join_table(h); if (jrc != FNN_OK) return jrc; }      // the previous step's sparse rows / bias (read by the gather)
@@ -1399,6 +1609,13 @@ int ip_run(ipnn_handle* h, const int32_t* ids, const float* y, int B, const uint
         if (rc != FNN_OK) return rc;
         const IpWideArgs wa = ip_wide_args(h, ids, B, (train && masks) ? masks[0] : nullptr, (train && masks) ? inv_keep : 1.0f);
         hipLaunchKernelGGL((k_ip_fwd_w<T>), dim3(Ba / IPW_EX), dim3(256), ipw_fwd_lds(F, h->rw), h->st, wa, (T*)h->a[0], (T*)h->aT[0],
+                           train ? h->emb : nullptr);
+    } else if (h->many_fwd) {
+        IpProf ps(h, "ip_fwd");
+        const int rc = ip_many_attr(h);
+        if (rc != FNN_OK) return rc;
+        const IpManyArgs ma = ip_many_args(h, ids, B, (train && masks) ? masks[0] : nullptr, (train && masks) ? inv_keep : 1.0f);
+        hipLaunchKernelGGL((k_ip_fwd_m<T>), dim3(Ba / IPM_EX), dim3(256), ipm_fwd_lds(F), h->st, ma, (T*)h->a[0], (T*)h->aT[0],
                            train ? h->emb : nullptr);
     } else {
         IpProf ps(h, "ip_fwd");
@@ -1629,10 +1846,13 @@ int ip_run(ipnn_handle* h, const int32_t* ids, const float* y, int B, const uint
         }
         {
             IpProf ps(h, "ip_bwd", ss);
-            const int ngb = h->wide ? Ba / IPW_EX : Ba / 16;
+            const int ngb = Ba / ip_bwd_ex(h);                       // one partial of db per workgroup of the backward
             if (h->wide) {
                 const IpWideArgs wa = ip_wide_args(h, ids, B, nullptr, 1.0f);
                 hipLaunchKernelGGL(k_ip_bwd_w, dim3(Ba / IPW_EX), dim3(256), ipw_bwd_lds(F, h->rw, h->P), ss, wa, h->dz0, h->emb, h->gxp, h->gb_part);
+            } else if (h->many_bwd) {
+                const IpManyArgs ma = ip_many_args(h, ids, B, nullptr, 1.0f);
+                hipLaunchKernelGGL(k_ip_bwd_m, dim3(Ba / IPM_BEX), dim3(256), ipm_bwd_lds(F, h->P), ss, ma, h->dz0, h->emb, h->gxp, h->gb_part);
             } else {
                 IpBwdArgs ba{h->P, ids, B, F, h->K, h->table16, h->n_rows, h->Dp[0], h->emb};
                 hipLaunchKernelGGL(k_ip_bwd, dim3(Ba / 16), dim3(256), lds_ip, ss, ba, h->dz0, h->gxp, h->gb_part);
@@ -1709,7 +1929,7 @@ int ip_run(ipnn_handle* h, const int32_t* ids, const float* y, int B, const uint
         u.n = L + 1; u.off[L + 1] = off; u.slab = h->slab; u.zstride = h->slab_stride; u.lr = lr_step;
         u.adam = h->adam ? (int)h->cfg.optimizer : 0; u.beta1 = h->cfg.adam_beta1; u.beta2 = h->cfg.adam_beta2; u.eps = h->cfg.adam_eps; u.bmv = h->bmv;
         if (h->adam) for (int t = 0; t <= L; ++t) { u.Wm[t] = h->Wm[t]; u.Wv[t] = h->Wv[t]; }
-        u.b = h->b; u.gb_part = h->gb_part; u.ngb = Ba / 16; u.loss_t = h->loss_t; u.Ba = Ba; u.loss_sum = h->loss_dev; u.err = h->err_flag;
+        u.b = h->b; u.gb_part = h->gb_part; u.ngb = Ba / ip_bwd_ex(h); u.loss_t = h->loss_t; u.Ba = Ba; u.loss_sum = h->loss_dev; u.err = h->err_flag;
         hipLaunchKernelGGL((k_ip_update_all<T>), dim3((unsigned)(off / 4096 + 1)), dim3(256), 0, us, u);
     }
     if (side_upd) { IHK(h, hipEventRecord(h->ev_join, h->st2)); h->tab_pending = h->upd_pending = true; }   // joined by the next call (ip_join)
@@ -1730,13 +1950,16 @@ int ipnn_create(const ipnn_cfg* cfg, ipnn_handle** out)
 {
     if (!cfg || !out) { g_ip_err = "null argument"; return FNN_ERR_ARG; }
     *out = nullptr;
-    if (cfg->n_fields < 2 || cfg->n_fields > 32) {
-        g_ip_err = "bad shape: n_fields = " + std::to_string(cfg->n_fields) + " (2..32 fields: more than 32 is not built)"; return FNN_ERR_ARG; }
     if (cfg->k < 1 || cfg->k > 128) {
         g_ip_err = "bad shape: k = " + std::to_string(cfg->k) + " (k = rank+1 must be 1..128)"; return FNN_ERR_ARG; }
+    if (cfg->n_fields < 2 || cfg->n_fields > 64) {
+        g_ip_err = "bad shape: n_fields = " + std::to_string(cfg->n_fields) + " (2..64 fields of k <= 16, 2..32 fields of k = 17..128: more is not built)"; return FNN_ERR_ARG; }
+    if (cfg->k > SLOT && cfg->n_fields > 32) {
+        g_ip_err = "bad shape: n_fields = " + std::to_string(cfg->n_fields) + " with k = " + std::to_string(cfg->k) +
+                   " (wide rows, k = 17..128, take 2..32 fields: more than 32 is not built; k <= 16 takes 2..64)"; return FNN_ERR_ARG; }
     if (cfg->n_hidden < 1 || cfg->n_hidden > IPNN_MAX_HIDDEN ||
         cfg->max_batch < 1 || cfg->max_batch > 4096 || !(cfg->keep_prob > 0.f && cfg->keep_prob <= 1.f)) {
-        g_ip_err = "bad shape (2..32 fields, k <= 128, 1..8 hidden layers, batch <= 4096, 0 < keep_prob <= 1)"; return FNN_ERR_ARG; }
+        g_ip_err = "bad shape (2..64 fields of k <= 16 or 2..32 fields of k = 17..128, 1..8 hidden layers, batch <= 4096, 0 < keep_prob <= 1)"; return FNN_ERR_ARG; }
     if (cfg->act != A_TANH && cfg->act != A_SIG && cfg->act != A_RELU) { g_ip_err = "bad act"; return FNN_ERR_ARG; }
     if (cfg->precision != FNN_PREC_F32 && cfg->precision != FNN_PREC_BF16) { g_ip_err = "bad precision (FNN_PREC_F32 or FNN_PREC_BF16; FNN_PREC_BF16X3 is the FNN / SNN engine's)"; return FNN_ERR_ARG; }
     if (cfg->optimizer != IPNN_OPT_SGD && cfg->optimizer != IPNN_OPT_ADAM && cfg->optimizer != IPNN_OPT_FTRL) { g_ip_err = "bad optimizer"; return FNN_ERR_ARG; }
@@ -1783,6 +2006,8 @@ int ipnn_create(const ipnn_cfg* cfg, ipnn_handle** out)
     h->d[0] = h->F * h->K + h->P + 1; h->Dp[0] = rup(h->CB + 2, 64);
     for (int t = 1; t <= h->L; ++t) { h->d[t] = cfg->hidden[t - 1]; h->Dp[t] = rup(h->d[t] + 1, 64); if (h->d[t] < 1 || h->d[t] > 4095) { h->err = "hidden size out of range"; return fail(FNN_ERR_ARG); } }
     h->d[h->L + 1] = 1; h->Dp[h->L + 1] = 64;
+    h->many_fwd = !h->wide && ip_many_choice(h->F, h->Dp[0], IPM_FWD_MIN_FIELDS, "IPNN_MANY_FWD_MIN");
+    h->many_bwd = !h->wide && ip_many_choice(h->F, h->Dp[0], IPM_BWD_MIN_FIELDS, "IPNN_MANY_MIN");
     h->sk.resize(h->L + 1);
     for (int t = 1; t <= h->L + 1; ++t) {                          // ~256 workgroups of 128 x 128 per product
         const int tiles = ((h->Dp[t - 1] + 127) / 128) * ((h->Dp[t] + 127) / 128);
@@ -1823,7 +2048,7 @@ int ipnn_create(const ipnn_cfg* cfg, ipnn_handle** out)
     IK(al((void**)&h->slab, (size_t)h->splitk * nw * 4));
     IK(al((void**)&h->emb, Ba * h->F * h->rw * 4));
     IK(al((void**)&h->dz0, Ba * h->Dp[0] * 4)); IK(al((void**)&h->gxp, Ba * h->Dp[0] * 4));
-    IK(al((void**)&h->gb_part, (Ba / (h->wide ? IPW_EX : 16)) * 4)); IK(al((void**)&h->loss_t, Ba * 4)); IK(al((void**)&h->loss_dev, 4));
+    IK(al((void**)&h->gb_part, (Ba / ip_bwd_ex(h)) * 4)); IK(al((void**)&h->loss_t, Ba * 4)); IK(al((void**)&h->loss_dev, 4));
     IK(al((void**)&h->b, 4)); IK(al((void**)&h->err_flag, 4));
     IK(al((void**)&h->rec, (size_t)h->F * SORT_N * sizeof(int4))); IK(al((void**)&h->part, h->wide ? (size_t)h->F * (SORT_N / WCH) * 2 * h->rw * 8
                                                                                                  : (size_t)h->F * (SORT_N / 16) * 2 * SLOT * 8));
@@ -1839,6 +2064,13 @@ int ipnn_create(const ipnn_cfg* cfg, ipnn_handle** out)
         ref[h->CB] = h->d[0] - 1;
         IK(hipMalloc((void**)&h->ref0, ref.size() * 4));
         IK(hipMemcpy(h->ref0, ref.data(), ref.size() * 4, hipMemcpyHostToDevice));
+        if (h->many_fwd && h->P) {                                    // pair n -> (i, j), i < j, row-major: the column order of z1's products
+            std::vector<unsigned short> pt;
+            pt.reserve(h->P);
+            for (int i = 0; i < h->F; ++i) for (int j = i + 1; j < h->F; ++j) pt.push_back((unsigned short)(i | (j << 8)));
+            IK(hipMalloc((void**)&h->ptab, pt.size() * 2));
+            IK(hipMemcpy(h->ptab, pt.data(), pt.size() * 2, hipMemcpyHostToDevice));
+        }
     }
     if (getenv("IPNN_STAMPS")) { IK(al((void**)&h->stamps, (size_t)2 * (h->ldT / 16) * 16 * 8)); h->stamp_tail = atoi(getenv("IPNN_STAMPS")) == 2; }
     IK(hipStreamSynchronize(h->st));
@@ -1858,7 +2090,7 @@ int ipnn_destroy(ipnn_handle* h)
     for (float* p : h->Wm) if (p) hipFree(p);
     for (float* p : h->Wv) if (p) hipFree(p);
     for (float* p : {h->tm, h->tv, h->tG, h->bmv}) if (p) hipFree(p);
-    void* ptrs[] = {h->table16, h->noshare, h->b, h->emb, h->dz0, h->gxp, h->gb_part, h->loss_t, h->loss_dev, h->slab, h->ref0, h->err_flag, h->rec,
+    void* ptrs[] = {h->table16, h->noshare, h->b, h->emb, h->dz0, h->gxp, h->gb_part, h->loss_t, h->loss_dev, h->slab, h->ref0, h->ptab, h->err_flag, h->rec,
                     h->part, h->owners, h->owner_cnt, h->skeys, h->cpow1, h->duo_xch, h->duo_flags};
     for (void* p : ptrs) if (p) hipFree(p);
     for (auto& kv : h->prof_ev) for (auto& p : kv.second) { hipEventDestroy(p.first); hipEventDestroy(p.second); }

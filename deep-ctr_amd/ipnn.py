@@ -3,7 +3,8 @@
 `IPNNEngine` is the PyTorch-ROCm plumbing; the three class names of the reference are kept as
 constructors with its `_rch_argv` layout (X_dim, X_feas, rank, h1..hN, act_func), its `forward`
 role (`train_step` / `predict`) and its `dump` keys (`W`, `V`, `b`, `h{i}_w`, `h{i}_b`).
-Categorical fields only; optimiser 'sgd', 'adam' or 'ftrl' (python/tf_util.py:15-29).  rank 0..127
+Categorical fields only (one id per field; X_feas = 2..64 at rank <= 15 -- the reference's own 39 columns included -- and 2..32
+above); optimiser 'sgd', 'adam' or 'ftrl' (python/tf_util.py:15-29).  rank 0..127
 (k = rank + 1 up to 128, either precision): an FM50 / FM100 pickle from FM.dump seeds FNN_IP_L3_50 / FNN100 through
 _init_argv."""
 import ctypes as C
@@ -134,7 +135,8 @@ class _IPFamily(object):
     """Constructor signature of python/FNN_IP_L7.py:5: (cat_sizes, offsets, batch_size, _rch_argv,
     _init_argv, _ptmzr_argv, _reg_argv, mode, eval_size).  _rch_argv = [X_dim, X_feas, rank,
     h1.., act_func]; _init_argv = ['uniform', lo, hi, seeds, path] (python/tf_util.py:41-82: a
-    pickle path seeds any subset of the variables); _ptmzr_argv = ['sgd', lr, ...]."""
+    pickle path seeds any subset of the variables); _ptmzr_argv = ['sgd', lr, ...].  X_feas is whatever ipnn_create takes
+    (2..64 fields of rank <= 15, 2..32 above): an FM.dump of [D, 39, 10] seeds FNN_IP_L3 with X_feas = 39."""
     N_HIDDEN = 0
     PAIRS = True
 

@@ -7,6 +7,12 @@
  * fields only (iPinYou shape: one id per field); optimiser: plain SGD, Adam or FTRL (IPNN_OPT_*).  Dropout keep-masks are INPUTS (uint8, one per element,
  * reference column order), NULL = no dropout (`drop_out=False`).
  *
+ * Field counts: narrow rows (k = 1..16) take 2..64 fields -- the reference's classes are 39-field models (X_feas = 13 +
+ * len(cat_sizes), python/FNN_IP_L3.py) -- with and without `pairs`, in both precisions, under every optimiser; layer 0 then holds
+ * 16 F + F(F-1)/2 + 2 columns padded to a multiple of 64: at most 3072 (64 fields with pairs; 1408 at 39).  Up to 32 fields the
+ * inner-product layer runs 16 examples per workgroup; above, 8 (forward) and 4 (backward) with only the embeddings in LDS.  A
+ * layer 0 wider than 1024 columns sends the deep stack to one GEMM launch per product.  Wide rows stay at 2..32 fields.
+ *
  * Wide rows (k = 17..128, any of 2..32 fields, both `pairs`, both precisions, every optimiser): the table keeps rows of
  * rw = rup(k, 4) floats (pad columns zero; under Adam / FTRL the state and gradient tables are [n_rows, rw] too) and layer 0
  * holds column f*rw + l = e_f[l], then the pair products, b and the ones column: rup(F*rw + P + 2, 64) padded columns (at most
@@ -44,7 +50,7 @@ extern "C" {
                                    re-derived from its (zero) linear term, i.e. drops to 0 at step 1   */
 
 typedef struct ipnn_cfg {
-    int32_t n_fields;                  /* X_feas                                             */
+    int32_t n_fields;                  /* X_feas: 2..64 with k <= 16, 2..32 with k = 17..128 */
     int32_t k;                         /* rank + 1: embedding row [w | v]  (FNN_IP_L7.py:66); 1..128:
                                           k <= 16 keeps rows in 16-float slots; k = 17..128 (the FM50 /
                                           FM100 seeds) is the WIDE layout below                */

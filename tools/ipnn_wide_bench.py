@@ -5,6 +5,8 @@ per-segment device times of ipnn_prof_* and a FLOP / byte model of the step.  On
 
   python tools/ipnn_wide_bench.py [--steps 100 --warmup 10] [--only NAME,..] [--no-prof]
   python tools/ipnn_wide_bench.py --digest --steps 5 --only l7_k11_bf16_sgd,...   (sha256 of table, layers and b after the steps)
+  python tools/ipnn_wide_bench.py --fields 39    (narrow rows on N fields, synth.field_sizes_ipinyou(n_fields=N): the reference's
+                                                  39 columns, up to 64; the default configurations are then the NARROW_MANY ones)
 
 The k11 configurations use only what the parent C ABI already had, so the same script digests a build of the parent tree.
 The timed window and the profiled window are separate runs of the same steps: the profiling events sit between the launches."""
@@ -31,6 +33,13 @@ for _c in ('l7', 'l3'):
     for _p in ('f32', 'bf16'):
         CONFIGS['%s_k11_%s_sgd' % (_c, _p)] = (_c, 11, _p, 'sgd')
 WIDE = [n for n in CONFIGS if '_k11_' not in n]
+# narrow rows at any field count (--fields 39 / 64: wide rows stop at 32 fields)
+NARROW_MANY = []
+for _c in ('l3', 'fnn'):
+    for _p in ('f32', 'bf16'):
+        for _o in ('sgd', 'adam'):
+            CONFIGS['%s_k11_%s_%s' % (_c, _p, _o)] = (_c, 11, _p, _o)
+            NARROW_MANY.append('%s_k11_%s_%s' % (_c, _p, _o))
 SEGMENTS = ('mask_t', 'sort', 'ip_fwd', 'fwd', 'bwd', 'wgrad', 'ip_bwd', 'scatter', 'adam_table', 'update')
 PEAK_TFLOPS = {'f32': 157.3, 'bf16': 2516.6}        # MI355X dense MFMA peaks
 HBM_TBPS = 8.0
@@ -115,7 +124,7 @@ def run(names, steps, warmup, B, prof, dig):
     import torch
     import deep_ctr_amd  # noqa: F401
     from deep_ctr_amd import synth
-    sizes = synth.field_sizes_ipinyou()
+    sizes = synth.field_sizes_ipinyou(n_fields=F)
     D = sum(sizes)
     NB = 8
     ids_h = synth.zipf_ids(NB * B, sizes, 1.1, 99)
@@ -171,11 +180,14 @@ def main():
     ap.add_argument('--steps', type=int, default=100)
     ap.add_argument('--warmup', type=int, default=10)
     ap.add_argument('--batch', type=int, default=4096)
-    ap.add_argument('--only', default=','.join(WIDE))
+    ap.add_argument('--only', default=None)
+    ap.add_argument('--fields', type=int, default=16, help='field count (2..64; more than 32: narrow rows only)')
     ap.add_argument('--no-prof', action='store_true')
     ap.add_argument('--digest', action='store_true', help='sha256 of table, layers and b after --steps steps (no timing)')
     a = ap.parse_args()
-    names = a.only.split(',')
+    global F
+    F = a.fields
+    names = (a.only or ','.join(WIDE if F == 16 else NARROW_MANY)).split(',')
     for n in names:
         if n not in CONFIGS:
             raise SystemExit('unknown config %r (%s)' % (n, ', '.join(CONFIGS)))
