@@ -124,6 +124,9 @@ IPNN_SIGNATURES = {
     "ipnn_set_loss_mean": (_i, [_vp, _i]),
     "ipnn_predict": (_i, [_vp, _vp, _i, _vp]),
     "ipnn_eval": (_i, [_vp, _vp, _vp, _i64, C.POINTER(C.c_double), C.POINTER(C.c_double), C.POINTER(C.c_double)]),
+    "ipnn_train_step_w": (_i, [_vp, _vp, _vp, _vp, _i, _vp, _vp, C.POINTER(_f)]),
+    "ipnn_predict_w": (_i, [_vp, _vp, _vp, _i, _vp]),
+    "ipnn_eval_w": (_i, [_vp, _vp, _vp, _vp, _i64, C.POINTER(C.c_double), C.POINTER(C.c_double), C.POINTER(C.c_double)]),
     "ipnn_prof_enable": (_i, [_vp, _i]),
     "ipnn_prof_get": (_i, [_vp, C.c_char_p, C.POINTER(C.c_double)]),
 }

@@ -65,23 +65,29 @@ struct IpFwdArgs {
     const uint8_t* mask; int d0; float inv_keep; int act; int D0p, ldT; int* err;
     int skip;                   // diagnostics (IPNN_FWD_SKIP bits: 1 gather, 2 embedding store, 4 compute, 8 output stores); 0 in production
     bool wt;                    // outputs written through (IPNN_WT=0: plain stores; see store4_wt in fnn_kernels.hip.h)
+    const float* wts;           // value weights [B][F] (read by the WV variant only; NULL: every weight 1)
 };
 
 // gather of 16 examples' rows into an LDS tile [16][F*16]: all ids of a batch of 4 elements per thread first, then all
 // rows (two dependent round trips per batch instead of two per element)
 // STR: floats per field in the tile -- 16 (vector stores), or 17 for the forward's pair products: lanes that read slot l of
 // DIFFERENT fields then fall on different banks (with 16 all of them share two banks: a 32-way conflict per read)
-template <int STR, int NT = 256>
+// WV: value weights (ipnn_*_w with wts != NULL): the weight of (example t, field f) sits at the id's own index, is loaded in the id's
+// round trip and scales the row's pieces in f32, so that the tile -- and emb, copied from it -- holds e_f = wts[t][f] * row
+template <int STR, int NT = 256, bool WV = false>
 __device__ __forceinline__ void ip_gather16(float* se, const int32_t* __restrict__ ids, const float* __restrict__ table16,
-                                            const int64_t n_rows, const int t0, const int B, const int F, int* err)
+                                            const int64_t n_rows, const int t0, const int B, const int F, int* err,
+                                            const float* __restrict__ wts = nullptr)
 {
     const int n = 16 * F * 4, FS = F * STR;
     for (int e0 = threadIdx.x; e0 < n; e0 += NT * 4) {
         int64_t id[4];
+        float w[4];
 #pragma unroll
         for (int j = 0; j < 4; ++j) {
             const int e = e0 + NT * j, f = (e >> 2) % F, t = t0 + (e >> 2) / F;
             id[j] = (e < n && t < B) ? (int64_t)ids[(size_t)t * F + f] : -1;
+            if (WV) w[j] = (e < n && t < B) ? wts[(size_t)t * F + f] : 0.f;
         }
         float4 v[4];
 #pragma unroll
@@ -89,6 +95,7 @@ __device__ __forceinline__ void ip_gather16(float* se, const int32_t* __restrict
             const int e = e0 + NT * j;
             if (e < n && t0 + (e >> 2) / F < B && (id[j] < 0 || id[j] >= n_rows)) { if (err) atomicOr(err, 1); id[j] = -1; }
             v[j] = id[j] >= 0 ? *reinterpret_cast<const float4*>(table16 + (size_t)id[j] * SLOT + 4 * (e & 3)) : make_float4(0.f, 0.f, 0.f, 0.f);
+            if (WV && id[j] >= 0) { v[j].x *= w[j]; v[j].y *= w[j]; v[j].z *= w[j]; v[j].w *= w[j]; }
         }
 #pragma unroll
         for (int j = 0; j < 4; ++j) {
@@ -103,7 +110,7 @@ __device__ __forceinline__ void ip_gather16(float* se, const int32_t* __restrict
 }
 
 constexpr int IPF_NT = 512;     // 8 waves: the kernel is bound by instruction issue, two waves per SIMD overlap it (IPNN_IPF_NT=1024: four)
-template <typename T, int NT = IPF_NT>
+template <typename T, int NT = IPF_NT, bool WV = false>
 static __global__ __launch_bounds__(NT) void k_ip_fwd(const IpFwdArgs a, T* __restrict__ a0, T* __restrict__ a0T, float* __restrict__ emb)
 {
     typedef typename Traits<T>::frag frag;
@@ -114,9 +121,9 @@ static __global__ __launch_bounds__(NT) void k_ip_fwd(const IpFwdArgs a, T* __re
     float* sa = se + 16 * a.F * SP;                             // [16][D0p]  a0 values
     const int tid = threadIdx.x, t0 = blockIdx.x * 16, F = a.F, K = a.K, B = a.B, FS = F * SLOT, FSP = F * SP;
     const int P = a.P, CB = FS + P;
-    if (!(a.skip & 1)) ip_gather16<SP, NT>(se, a.ids, a.table16, a.n_rows, t0, B, F, a.err);
+    if (!(a.skip & 1)) ip_gather16<SP, NT, WV>(se, a.ids, a.table16, a.n_rows, t0, B, F, a.err, a.wts);
     __syncthreads();
-    if (emb && !(a.skip & 2))                                                    // kept for the backward of the inner products (no second gather)
+    if (emb && !(a.skip & 2))                                                    // kept for the backward of the inner products (no second gather; WV: weighted)
         for (int e = tid; e < 16 * FS / 4; e += NT) {
             const int r = (4 * e) / FS, c = (4 * e) % FS;
             const float* q = se + r * FSP + (c >> 4) * SP + (c & 15);
@@ -190,14 +197,19 @@ static __global__ __launch_bounds__(NT) void k_ip_fwd(const IpFwdArgs a, T* __re
 // Inner-product layer, backward: dz1' [Ba][D0p] f32 (already times mask/keep and act') ->
 // slot-layout embedding gradients gx' [Ba][D0p] (columns 16f + l) for the sparse-row update, and the
 // per-workgroup partial of db = sum_t dz1[b].
-struct IpBwdArgs { int P; const int32_t* ids; int B, F, K; const float* table16; int64_t n_rows; int D0p; const float* emb; };
+// WV (value weights): emb holds the weighted embeddings, so the partner reads are unchanged; the finished gradient of (field f,
+// example t) is the gradient of e_f, and its row's is that times wts[t][f].  The 16 x F weights of the tile are staged in the F
+// floats per example that the launch's LDS size (k_ip_fwd's: a 17-float field stride) leaves behind sd.
+struct IpBwdArgs { int P; const int32_t* ids; int B, F, K; const float* table16; int64_t n_rows; int D0p; const float* emb; const float* wts; };
 
+template <bool WV = false>
 static __global__ __launch_bounds__(256) void k_ip_bwd(const IpBwdArgs a, const float* __restrict__ dz, float* __restrict__ gxp,
                                                         float* __restrict__ gb_part)
 {
     extern __shared__ __align__(16) unsigned char smem[];
     float* se = reinterpret_cast<float*>(smem);                 // [16][F*16]
     float* sd = se + 16 * a.F * SLOT;                           // [16][D0p]
+    float* sw = sd + 16 * a.D0p;                                // [16][F] value weights (WV only)
     const int tid = threadIdx.x, t0 = blockIdx.x * 16, F = a.F, K = a.K, B = a.B, FS = F * SLOT;
     const int P = a.P, CB = FS + P;
     // both tiles are contiguous in memory (16 consecutive rows): 16-byte pieces, eight loads in flight per thread before the
@@ -212,7 +224,8 @@ static __global__ __launch_bounds__(256) void k_ip_bwd(const IpBwdArgs a, const 
         }
     };
     if (a.emb) fill(se, a.emb + (size_t)t0 * FS, 16 * FS / 4);       // the raw embeddings the forward gathered
-    else ip_gather16<SLOT>(se, a.ids, a.table16, a.n_rows, t0, B, F, nullptr);
+    else ip_gather16<SLOT, 256, WV>(se, a.ids, a.table16, a.n_rows, t0, B, F, nullptr, a.wts);
+    if (WV) for (int e = tid; e < 16 * F; e += 256) sw[e] = t0 + e / F < B ? a.wts[(size_t)t0 * F + e] : 1.0f;
     fill(sd, dz + (size_t)t0 * a.D0p, 16 * a.D0p / 4);
     __syncthreads();
     for (int c = tid; c < FS; c += 256) {                        // a thread owns (field f, slot l) for all 16 examples:
@@ -229,6 +242,10 @@ static __global__ __launch_bounds__(256) void k_ip_bwd(const IpBwdArgs a, const 
 #pragma unroll
                 for (int r = 0; r < 16; ++r) g[r] = fmaf(sd[r * a.D0p + FS + n] * on, se[r * FS + j * SLOT + l], g[r]);
             }
+        }
+        if (WV) {
+#pragma unroll
+            for (int r = 0; r < 16; ++r) g[r] *= sw[r * F + f];
         }
 #pragma unroll
         for (int r = 0; r < 16; ++r) gxp[(size_t)(t0 + r) * a.D0p + c] = g[r];
@@ -251,6 +268,7 @@ struct IpWideArgs {
     const uint8_t* mask; int d0; float inv_keep; int act; int D0p, ldT; int* err;
     bool wt;                    // outputs written through (IPNN_WT=0: plain stores)
     unsigned a0_bytes, emb_bytes;   // sizes of a0 / a0T and of emb: the extent of the write-through stores' buffer resources
+    const float* wts;           // value weights [B][F] (read by the WV variants only; NULL: every weight 1)
 };
 // The wide kernels' write-through stores are raw buffer stores with the sc1 policy (aux 16), not the inline-asm store16_wt /
 // store4_wt: hipcc neither counts nor pads an asm store, so the instruction after a `global_store_dwordx4` there may overwrite its
@@ -277,9 +295,11 @@ __device__ __forceinline__ void ipw_store4(const bool wt, const __amdgpu_buffer_
     else *reinterpret_cast<ipw_u32x2*>(base + e) = w;
 }
 inline size_t ipw_fwd_lds(int F, int rw) { return (size_t)IPW_EX * F * (rw + 1) * sizeof(float); }
-inline size_t ipw_bwd_lds(int F, int rw, int P) { return (size_t)IPW_EX * (F * rw + P) * sizeof(float); }
+inline size_t ipw_bwd_lds(int F, int rw, int P, bool wv) { return (size_t)IPW_EX * (F * rw + P + (wv ? F : 0)) * sizeof(float); }
 
-template <typename T>
+// WV (value weights, here and in k_ip_bwd_w / k_ip_fwd_m / k_ip_bwd_m): as in ip_gather16 and k_ip_bwd -- every 16-byte piece of a
+// gathered row is scaled by wts[t][f] before it goes to the tile and to emb; the backward scales its finished gradient once.
+template <typename T, bool WV = false>
 static __global__ __launch_bounds__(256) void k_ip_fwd_w(const IpWideArgs a, T* __restrict__ a0, T* __restrict__ a0T, float* __restrict__ emb)
 {
     typedef typename Traits<T>::frag frag;
@@ -293,10 +313,12 @@ static __global__ __launch_bounds__(256) void k_ip_fwd_w(const IpWideArgs a, T* 
     const int n = IPW_EX * F * nq;
     for (int e0 = threadIdx.x; e0 < n; e0 += 256 * 4) {
         int64_t id[4];
+        float w[4];
 #pragma unroll
         for (int j = 0; j < 4; ++j) {
             const int e = e0 + 256 * j, t = t0 + e / (F * nq), f = (e / nq) % F;
             id[j] = (e < n && t < B) ? (int64_t)a.ids[(size_t)t * F + f] : -1;
+            if (WV) w[j] = (e < n && t < B) ? a.wts[(size_t)t * F + f] : 0.f;
             if (e < n && t < B && (id[j] < 0 || id[j] >= a.n_rows)) { if (a.err) atomicOr(a.err, 1); id[j] = -1; }
         }
         float4 v[4];
@@ -304,6 +326,7 @@ static __global__ __launch_bounds__(256) void k_ip_fwd_w(const IpWideArgs a, T* 
         for (int j = 0; j < 4; ++j) {
             const int e = e0 + 256 * j;
             v[j] = id[j] >= 0 ? *reinterpret_cast<const float4*>(a.table + (size_t)id[j] * rw + 4 * (e % nq)) : make_float4(0.f, 0.f, 0.f, 0.f);
+            if (WV && id[j] >= 0) { v[j].x *= w[j]; v[j].y *= w[j]; v[j].z *= w[j]; v[j].w *= w[j]; }
         }
 #pragma unroll
         for (int j = 0; j < 4; ++j) {
@@ -379,6 +402,7 @@ static __global__ __launch_bounds__(256) void k_ip_fwd_w(const IpWideArgs a, T* 
 
 // Wide backward: gx'[t][f rw + l] = dz[t][f rw + l] + sum_j dz[t][pair(f, j)] e_j[l] (l < k; pad columns 0), and the per-workgroup
 // partial of db.  The embeddings come from emb (the forward's copy); the pair deltas of the 8 examples are staged beside them.
+template <bool WV = false>
 static __global__ __launch_bounds__(256) void k_ip_bwd_w(const IpWideArgs a, const float* __restrict__ dz, const float* __restrict__ emb,
                                                           float* __restrict__ gxp, float* __restrict__ gb_part)
 {
@@ -386,6 +410,7 @@ static __global__ __launch_bounds__(256) void k_ip_bwd_w(const IpWideArgs a, con
     const int F = a.F, K = a.K, rw = a.rw, FW = F * rw, P = a.P, CB = FW + P, D0p = a.D0p;
     float* se = reinterpret_cast<float*>(smem);                 // [IPW_EX][F rw]
     float* sp = se + IPW_EX * FW;                               // [IPW_EX][P]
+    float* sw = sp + IPW_EX * P;                                // [IPW_EX][F] value weights (WV only: ipw_bwd_lds)
     const int t0 = blockIdx.x * IPW_EX;
     {
         const int n4 = IPW_EX * FW / 4;                         // the 8 examples' rows are contiguous in emb
@@ -398,6 +423,7 @@ static __global__ __launch_bounds__(256) void k_ip_bwd_w(const IpWideArgs a, con
             for (int k = 0; k < 4; ++k) { const int e = e0 + 256 * k; if (e < n4) reinterpret_cast<float4*>(se)[e] = v[k]; }
         }
         for (int e = threadIdx.x; e < IPW_EX * P; e += 256) sp[e] = dz[(size_t)(t0 + e / P) * D0p + FW + e % P];
+        if (WV) for (int e = threadIdx.x; e < IPW_EX * F; e += 256) sw[e] = t0 + e / F < a.B ? a.wts[(size_t)t0 * F + e] : 1.0f;
     }
     __syncthreads();
     for (int c = threadIdx.x; c < FW; c += 256) {               // a thread owns (field f, lane l) for the 8 examples
@@ -413,6 +439,10 @@ static __global__ __launch_bounds__(256) void k_ip_bwd_w(const IpWideArgs a, con
 #pragma unroll
                 for (int r = 0; r < IPW_EX; ++r) g[r] = fmaf(sp[r * P + m], se[r * FW + j * rw + l], g[r]);
             }
+        }
+        if (WV) {
+#pragma unroll
+            for (int r = 0; r < IPW_EX; ++r) g[r] *= sw[r * F + f];
         }
 #pragma unroll
         for (int r = 0; r < IPW_EX; ++r) gxp[(size_t)(t0 + r) * D0p + c] = g[r];
@@ -447,11 +477,12 @@ struct IpManyArgs {
     const unsigned short* ptab; // [P]: pair n = (i, j), i < j, row-major, as i | j << 8
     bool wt;                    // outputs written through (IPNN_WT=0: plain stores)
     unsigned a0_bytes, emb_bytes;   // sizes of a0 / a0T and of emb: the extent of the write-through stores' buffer resources
+    const float* wts;           // value weights [B][F] (read by the WV variants only; NULL: every weight 1)
 };
 inline size_t ipm_fwd_lds(int F) { return (size_t)IPM_EX * F * (SLOT + 1) * sizeof(float); }
-inline size_t ipm_bwd_lds(int F, int P) { return (size_t)IPM_BEX * (F * SLOT + P) * sizeof(float); }
+inline size_t ipm_bwd_lds(int F, int P, bool wv) { return (size_t)IPM_BEX * (F * SLOT + P + (wv ? F : 0)) * sizeof(float); }
 
-template <typename T>
+template <typename T, bool WV = false>
 static __global__ __launch_bounds__(256) void k_ip_fwd_m(const IpManyArgs a, T* __restrict__ a0, T* __restrict__ a0T, float* __restrict__ emb)
 {
     typedef typename Traits<T>::frag frag;
@@ -465,10 +496,12 @@ static __global__ __launch_bounds__(256) void k_ip_fwd_m(const IpManyArgs a, T* 
     const int n = IPM_EX * F * 4;
     for (int e0 = threadIdx.x; e0 < n; e0 += 256 * 4) {
         int64_t id[4];
+        float w[4];
 #pragma unroll
         for (int j = 0; j < 4; ++j) {
             const int e = e0 + 256 * j, t = t0 + (e >> 2) / F, f = (e >> 2) % F;
             id[j] = (e < n && t < B) ? (int64_t)a.ids[(size_t)t * F + f] : -1;
+            if (WV) w[j] = (e < n && t < B) ? a.wts[(size_t)t * F + f] : 0.f;
             if (e < n && t < B && (id[j] < 0 || id[j] >= a.n_rows)) { if (a.err) atomicOr(a.err, 1); id[j] = -1; }
         }
         float4 v[4];
@@ -476,6 +509,7 @@ static __global__ __launch_bounds__(256) void k_ip_fwd_m(const IpManyArgs a, T* 
         for (int j = 0; j < 4; ++j) {
             const int e = e0 + 256 * j;
             v[j] = id[j] >= 0 ? *reinterpret_cast<const float4*>(a.table16 + (size_t)id[j] * SLOT + 4 * (e & 3)) : make_float4(0.f, 0.f, 0.f, 0.f);
+            if (WV && id[j] >= 0) { v[j].x *= w[j]; v[j].y *= w[j]; v[j].z *= w[j]; v[j].w *= w[j]; }
         }
 #pragma unroll
         for (int j = 0; j < 4; ++j) {
@@ -546,6 +580,7 @@ static __global__ __launch_bounds__(256) void k_ip_fwd_m(const IpManyArgs a, T* 
 // Many-field backward: gx'[t][16 f + l] = dz[t][16 f + l] + sum_{j != f} dz[t][pair(f, j)] e_j[l] (l < k; pad columns 0) and the
 // per-workgroup partial of db (one per IPM_BEX examples).  The embeddings come from emb (the forward's copy).  A wave holds four
 // fields x 16 slots: its read of e_j[l] is 16 addresses broadcast to the four fields, its read of the pair delta four addresses.
+template <bool WV = false>
 static __global__ __launch_bounds__(256) void k_ip_bwd_m(const IpManyArgs a, const float* __restrict__ dz, const float* __restrict__ emb,
                                                           float* __restrict__ gxp, float* __restrict__ gb_part)
 {
@@ -553,6 +588,7 @@ static __global__ __launch_bounds__(256) void k_ip_bwd_m(const IpManyArgs a, con
     const int F = a.F, K = a.K, FS = F * SLOT, P = a.P, CB = FS + P, D0p = a.D0p;
     float* se = reinterpret_cast<float*>(smem);                 // [IPM_BEX][16 F]
     float* sp = se + IPM_BEX * FS;                              // [IPM_BEX][P]
+    float* sw = sp + IPM_BEX * P;                               // [IPM_BEX][F] value weights (WV only: ipm_bwd_lds)
     const int t0 = blockIdx.x * IPM_BEX;
     {
         const int n4 = IPM_BEX * FS / 4;                        // the examples' rows are contiguous in emb
@@ -578,6 +614,7 @@ static __global__ __launch_bounds__(256) void k_ip_bwd_m(const IpManyArgs a, con
             const int r = threadIdx.x / rest, q = 4 * p4 + threadIdx.x % rest;
             sp[r * P + q] = dz[(size_t)(t0 + r) * D0p + FS + q];
         }
+        if (WV) for (int e = threadIdx.x; e < IPM_BEX * F; e += 256) sw[e] = t0 + e / F < a.B ? a.wts[(size_t)t0 * F + e] : 1.0f;
     }
     __syncthreads();
     for (int c = threadIdx.x; c < FS; c += 256) {               // a thread owns (field f, slot l) for the IPM_BEX examples
@@ -598,6 +635,10 @@ static __global__ __launch_bounds__(256) void k_ip_bwd_m(const IpManyArgs a, con
 #pragma unroll
                 for (int r = 0; r < IPM_BEX; ++r) g[r] = fmaf(sp[r * P + m0 + j], se[r * FS + j * SLOT + l], g[r]);
             }
+        }
+        if (WV) {
+#pragma unroll
+            for (int r = 0; r < IPM_BEX; ++r) g[r] *= sw[r * F + f];
         }
 #pragma unroll
         for (int r = 0; r < IPM_BEX; ++r) gxp[(size_t)(t0 + r) * D0p + c] = g[r];
@@ -1533,37 +1574,46 @@ inline bool ip_many_choice(int F, int Dp0, int dflt, const char* knob)
     if (const char* e = getenv(knob)) mn = std::max(33, atoi(e));
     return F >= mn || ip16_lds(F, Dp0) > (size_t)160 * 1024;
 }
-IpManyArgs ip_many_args(const ipnn_handle* h, const int32_t* ids, int B, const uint8_t* mask0, float inv_keep)
+IpManyArgs ip_many_args(const ipnn_handle* h, const int32_t* ids, const float* wts, int B, const uint8_t* mask0, float inv_keep)
 {
     return IpManyArgs{h->P, ids, B, h->F, h->K, h->table16, h->n_rows, h->b, mask0, h->d[0], inv_keep, h->cfg.act, h->Dp[0], h->ldT,
-                      h->err_flag, h->ptab, h->wt, (unsigned)((size_t)h->ldT * h->Dp[0] * ts(h)), (unsigned)((size_t)h->ldT * h->F * SLOT * 4)};
+                      h->err_flag, h->ptab, h->wt, (unsigned)((size_t)h->ldT * h->Dp[0] * ts(h)), (unsigned)((size_t)h->ldT * h->F * SLOT * 4), wts};
 }
 int ip_many_attr(ipnn_handle* h)
 {
     if (h->many_attr) return FNN_OK;
     IHK(h, hipFuncSetAttribute(reinterpret_cast<const void*>(&k_ip_fwd_m<float>), hipFuncAttributeMaxDynamicSharedMemorySize, 64 * 1024));
     IHK(h, hipFuncSetAttribute(reinterpret_cast<const void*>(&k_ip_fwd_m<bf16_t>), hipFuncAttributeMaxDynamicSharedMemorySize, 64 * 1024));
-    IHK(h, hipFuncSetAttribute(reinterpret_cast<const void*>(&k_ip_bwd_m), hipFuncAttributeMaxDynamicSharedMemorySize, 64 * 1024));
+    IHK(h, hipFuncSetAttribute(reinterpret_cast<const void*>(&k_ip_bwd_m<false>), hipFuncAttributeMaxDynamicSharedMemorySize, 64 * 1024));
+    IHK(h, hipFuncSetAttribute(reinterpret_cast<const void*>(&k_ip_fwd_m<float, true>), hipFuncAttributeMaxDynamicSharedMemorySize, 64 * 1024));
+    IHK(h, hipFuncSetAttribute(reinterpret_cast<const void*>(&k_ip_fwd_m<bf16_t, true>), hipFuncAttributeMaxDynamicSharedMemorySize, 64 * 1024));
+    IHK(h, hipFuncSetAttribute(reinterpret_cast<const void*>(&k_ip_bwd_m<true>), hipFuncAttributeMaxDynamicSharedMemorySize, 64 * 1024));
     h->many_attr = true;
     return FNN_OK;
 }
-IpWideArgs ip_wide_args(const ipnn_handle* h, const int32_t* ids, int B, const uint8_t* mask0, float inv_keep)
+IpWideArgs ip_wide_args(const ipnn_handle* h, const int32_t* ids, const float* wts, int B, const uint8_t* mask0, float inv_keep)
 {
     return IpWideArgs{h->P, ids, B, h->F, h->K, h->rw, h->table16, h->n_rows, h->b, mask0, h->d[0], inv_keep, h->cfg.act, h->Dp[0],
-                      h->ldT, h->err_flag, h->wt, (unsigned)((size_t)h->ldT * h->Dp[0] * ts(h)), (unsigned)((size_t)h->ldT * h->F * h->rw * 4)};
+                      h->ldT, h->err_flag, h->wt, (unsigned)((size_t)h->ldT * h->Dp[0] * ts(h)), (unsigned)((size_t)h->ldT * h->F * h->rw * 4), wts};
 }
 int ip_wide_attr(ipnn_handle* h)
 {
     if (h->wide_attr) return FNN_OK;
     IHK(h, hipFuncSetAttribute(reinterpret_cast<const void*>(&k_ip_fwd_w<float>), hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024));
     IHK(h, hipFuncSetAttribute(reinterpret_cast<const void*>(&k_ip_fwd_w<bf16_t>), hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024));
-    IHK(h, hipFuncSetAttribute(reinterpret_cast<const void*>(&k_ip_bwd_w), hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024));
+    IHK(h, hipFuncSetAttribute(reinterpret_cast<const void*>(&k_ip_bwd_w<false>), hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024));
+    IHK(h, hipFuncSetAttribute(reinterpret_cast<const void*>(&k_ip_fwd_w<float, true>), hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024));
+    IHK(h, hipFuncSetAttribute(reinterpret_cast<const void*>(&k_ip_fwd_w<bf16_t, true>), hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024));
+    IHK(h, hipFuncSetAttribute(reinterpret_cast<const void*>(&k_ip_bwd_w<true>), hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024));
     h->wide_attr = true;
     return FNN_OK;
 }
 
+// wts: value weights [B][F] (device) or NULL.  NULL launches the kernels as they were before the weights existed (WV = false);
+// a pointer launches their WV instantiations -- a compile-time variant, so that the unweighted path carries neither the loads
+// nor a branch.
 template <typename T>
-int ip_run(ipnn_handle* h, const int32_t* ids, const float* y, int B, const uint8_t* const* masks, float* logits_out,
+int ip_run(ipnn_handle* h, const int32_t* ids, const float* wts, const float* y, int B, const uint8_t* const* masks, float* logits_out,
            float* p_out, bool train)
 {
     const int Ba = rup(B, 256), L = h->L, F = h->F, ldT = h->ldT;
@@ -1607,21 +1657,27 @@ int ip_run(ipnn_handle* h, const int32_t* ids, const float* y, int B, const uint
         IpProf ps(h, "ip_fwd");
         const int rc = ip_wide_attr(h);
         if (rc != FNN_OK) return rc;
-        const IpWideArgs wa = ip_wide_args(h, ids, B, (train && masks) ? masks[0] : nullptr, (train && masks) ? inv_keep : 1.0f);
-        hipLaunchKernelGGL((k_ip_fwd_w<T>), dim3(Ba / IPW_EX), dim3(256), ipw_fwd_lds(F, h->rw), h->st, wa, (T*)h->a[0], (T*)h->aT[0],
-                           train ? h->emb : nullptr);
+        const IpWideArgs wa = ip_wide_args(h, ids, wts, B, (train && masks) ? masks[0] : nullptr, (train && masks) ? inv_keep : 1.0f);
+        if (wts) hipLaunchKernelGGL((k_ip_fwd_w<T, true>), dim3(Ba / IPW_EX), dim3(256), ipw_fwd_lds(F, h->rw), h->st, wa, (T*)h->a[0], (T*)h->aT[0],
+                                    train ? h->emb : nullptr);
+        else hipLaunchKernelGGL((k_ip_fwd_w<T>), dim3(Ba / IPW_EX), dim3(256), ipw_fwd_lds(F, h->rw), h->st, wa, (T*)h->a[0], (T*)h->aT[0],
+                                train ? h->emb : nullptr);
     } else if (h->many_fwd) {
         IpProf ps(h, "ip_fwd");
         const int rc = ip_many_attr(h);
         if (rc != FNN_OK) return rc;
-        const IpManyArgs ma = ip_many_args(h, ids, B, (train && masks) ? masks[0] : nullptr, (train && masks) ? inv_keep : 1.0f);
-        hipLaunchKernelGGL((k_ip_fwd_m<T>), dim3(Ba / IPM_EX), dim3(256), ipm_fwd_lds(F), h->st, ma, (T*)h->a[0], (T*)h->aT[0],
-                           train ? h->emb : nullptr);
+        const IpManyArgs ma = ip_many_args(h, ids, wts, B, (train && masks) ? masks[0] : nullptr, (train && masks) ? inv_keep : 1.0f);
+        if (wts) hipLaunchKernelGGL((k_ip_fwd_m<T, true>), dim3(Ba / IPM_EX), dim3(256), ipm_fwd_lds(F), h->st, ma, (T*)h->a[0], (T*)h->aT[0],
+                                    train ? h->emb : nullptr);
+        else hipLaunchKernelGGL((k_ip_fwd_m<T>), dim3(Ba / IPM_EX), dim3(256), ipm_fwd_lds(F), h->st, ma, (T*)h->a[0], (T*)h->aT[0],
+                                train ? h->emb : nullptr);
     } else {
         IpProf ps(h, "ip_fwd");
         IpFwdArgs fa{h->P, ids, B, F, h->K, h->table16, h->n_rows, h->b, (train && masks) ? masks[0] : nullptr, h->d[0],
-                     (train && masks) ? inv_keep : 1.0f, h->cfg.act, h->Dp[0], ldT, h->err_flag, h->fwd_skip, h->wt};
-        if (h->ipf_nt == 1024) hipLaunchKernelGGL((k_ip_fwd<T, 1024>), dim3(Ba / 16), dim3(1024), lds_ip, h->st, fa, (T*)h->a[0], (T*)h->aT[0], train ? h->emb : nullptr);
+                     (train && masks) ? inv_keep : 1.0f, h->cfg.act, h->Dp[0], ldT, h->err_flag, h->fwd_skip, h->wt, wts};
+        if (wts && h->ipf_nt == 1024) hipLaunchKernelGGL((k_ip_fwd<T, 1024, true>), dim3(Ba / 16), dim3(1024), lds_ip, h->st, fa, (T*)h->a[0], (T*)h->aT[0], train ? h->emb : nullptr);
+        else if (wts) hipLaunchKernelGGL((k_ip_fwd<T, IPF_NT, true>), dim3(Ba / 16), dim3(IPF_NT), lds_ip, h->st, fa, (T*)h->a[0], (T*)h->aT[0], train ? h->emb : nullptr);
+        else if (h->ipf_nt == 1024) hipLaunchKernelGGL((k_ip_fwd<T, 1024>), dim3(Ba / 16), dim3(1024), lds_ip, h->st, fa, (T*)h->a[0], (T*)h->aT[0], train ? h->emb : nullptr);
         else hipLaunchKernelGGL((k_ip_fwd<T>), dim3(Ba / 16), dim3(IPF_NT), lds_ip, h->st, fa, (T*)h->a[0], (T*)h->aT[0], train ? h->emb : nullptr);
     }
     // one product: C [M][N] = A . B^T on fragment-tiled operands; narrow problems take smaller wave tiles
@@ -1848,14 +1904,17 @@ int ip_run(ipnn_handle* h, const int32_t* ids, const float* y, int B, const uint
             IpProf ps(h, "ip_bwd", ss);
             const int ngb = Ba / ip_bwd_ex(h);                       // one partial of db per workgroup of the backward
             if (h->wide) {
-                const IpWideArgs wa = ip_wide_args(h, ids, B, nullptr, 1.0f);
-                hipLaunchKernelGGL(k_ip_bwd_w, dim3(Ba / IPW_EX), dim3(256), ipw_bwd_lds(F, h->rw, h->P), ss, wa, h->dz0, h->emb, h->gxp, h->gb_part);
+                const IpWideArgs wa = ip_wide_args(h, ids, wts, B, nullptr, 1.0f);
+                if (wts) hipLaunchKernelGGL(k_ip_bwd_w<true>, dim3(Ba / IPW_EX), dim3(256), ipw_bwd_lds(F, h->rw, h->P, true), ss, wa, h->dz0, h->emb, h->gxp, h->gb_part);
+                else hipLaunchKernelGGL(k_ip_bwd_w<false>, dim3(Ba / IPW_EX), dim3(256), ipw_bwd_lds(F, h->rw, h->P, false), ss, wa, h->dz0, h->emb, h->gxp, h->gb_part);
             } else if (h->many_bwd) {
-                const IpManyArgs ma = ip_many_args(h, ids, B, nullptr, 1.0f);
-                hipLaunchKernelGGL(k_ip_bwd_m, dim3(Ba / IPM_BEX), dim3(256), ipm_bwd_lds(F, h->P), ss, ma, h->dz0, h->emb, h->gxp, h->gb_part);
+                const IpManyArgs ma = ip_many_args(h, ids, wts, B, nullptr, 1.0f);
+                if (wts) hipLaunchKernelGGL(k_ip_bwd_m<true>, dim3(Ba / IPM_BEX), dim3(256), ipm_bwd_lds(F, h->P, true), ss, ma, h->dz0, h->emb, h->gxp, h->gb_part);
+                else hipLaunchKernelGGL(k_ip_bwd_m<false>, dim3(Ba / IPM_BEX), dim3(256), ipm_bwd_lds(F, h->P, false), ss, ma, h->dz0, h->emb, h->gxp, h->gb_part);
             } else {
-                IpBwdArgs ba{h->P, ids, B, F, h->K, h->table16, h->n_rows, h->Dp[0], h->emb};
-                hipLaunchKernelGGL(k_ip_bwd, dim3(Ba / 16), dim3(256), lds_ip, ss, ba, h->dz0, h->gxp, h->gb_part);
+                IpBwdArgs ba{h->P, ids, B, F, h->K, h->table16, h->n_rows, h->Dp[0], h->emb, wts};
+                if (wts) hipLaunchKernelGGL(k_ip_bwd<true>, dim3(Ba / 16), dim3(256), lds_ip, ss, ba, h->dz0, h->gxp, h->gb_part);
+                else hipLaunchKernelGGL(k_ip_bwd<false>, dim3(Ba / 16), dim3(256), lds_ip, ss, ba, h->dz0, h->gxp, h->gb_part);
             }
             hipLaunchKernelGGL(k_ip_b_update, dim3(1), dim3(256), 0, ss, h->b, h->gb_part, ngb, h->adam ? (int)h->cfg.optimizer : 0, h->bmv,
                                lr_step, h->cfg.adam_beta1, h->cfg.adam_beta2, h->cfg.adam_eps, h->err_flag);
@@ -2240,13 +2299,19 @@ int ipnn_get_layer(ipnn_handle* h, int layer, float* W, float* bias)
 int ipnn_train_step(ipnn_handle* h, const int32_t* ids, const float* y, int B, const uint8_t* const* masks,
                     float* logits_out, float* loss_sum_out)
 {
+    return ipnn_train_step_w(h, ids, nullptr, y, B, masks, logits_out, loss_sum_out);
+}
+
+int ipnn_train_step_w(ipnn_handle* h, const int32_t* ids, const float* wts, const float* y, int B, const uint8_t* const* masks,
+                      float* logits_out, float* loss_sum_out)
+{
     if (!h || !ids || !y) return FNN_ERR_ARG;
     if (B < 1 || B > h->Bmax) IFAIL(h, FNN_ERR_ARG, "B must be in [1, max_batch]");
     if (!h->table16) IFAIL(h, FNN_ERR_STATE, "ipnn_set_table has not been called");
     if (h->duo_failed) IFAIL(h, FNN_ERR_STATE, "an earlier step failed (StripDuo swap timed out): re-create the handle");
     IHK(h, hipSetDevice(h->dev));
-    int rc = h->bf16 ? ip_run<bf16_t>(h, ids, y, B, masks, logits_out, nullptr, true)
-                     : ip_run<float>(h, ids, y, B, masks, logits_out, nullptr, true);
+    int rc = h->bf16 ? ip_run<bf16_t>(h, ids, wts, y, B, masks, logits_out, nullptr, true)
+                     : ip_run<float>(h, ids, wts, y, B, masks, logits_out, nullptr, true);
     if (rc != FNN_OK) return rc;
     if (loss_sum_out) {                                      // (the loss is summed in the update launch: join it)
         { const int jrc = ip_join(h); if (jrc != FNN_OK) return jrc; }
@@ -2263,17 +2328,24 @@ int ipnn_set_loss_mean(ipnn_handle* h, int mean)
     return FNN_OK;
 }
 
-int ipnn_predict(ipnn_handle* h, const int32_t* ids, int B, float* p_out)
+int ipnn_predict(ipnn_handle* h, const int32_t* ids, int B, float* p_out) { return ipnn_predict_w(h, ids, nullptr, B, p_out); }
+
+int ipnn_predict_w(ipnn_handle* h, const int32_t* ids, const float* wts, int B, float* p_out)
 {
     if (!h || !ids || !p_out) return FNN_ERR_ARG;
     if (B < 1 || B > h->Bmax) IFAIL(h, FNN_ERR_ARG, "B must be in [1, max_batch]");
     if (!h->table16) IFAIL(h, FNN_ERR_STATE, "ipnn_set_table has not been called");
     IHK(h, hipSetDevice(h->dev));
-    return h->bf16 ? ip_run<bf16_t>(h, ids, nullptr, B, nullptr, nullptr, p_out, false)
-                   : ip_run<float>(h, ids, nullptr, B, nullptr, nullptr, p_out, false);
+    return h->bf16 ? ip_run<bf16_t>(h, ids, wts, nullptr, B, nullptr, nullptr, p_out, false)
+                   : ip_run<float>(h, ids, wts, nullptr, B, nullptr, nullptr, p_out, false);
 }
 
 int ipnn_eval(ipnn_handle* h, const int32_t* ids, const int32_t* y, int64_t N, double* auc, double* rmse, double* logloss)
+{
+    return ipnn_eval_w(h, ids, nullptr, y, N, auc, rmse, logloss);
+}
+
+int ipnn_eval_w(ipnn_handle* h, const int32_t* ids, const float* wts, const int32_t* y, int64_t N, double* auc, double* rmse, double* logloss)
 {
     if (!h || !ids || !y || N < 1) return FNN_ERR_ARG;
     if (!h->table16) IFAIL(h, FNN_ERR_STATE, "ipnn_set_table has not been called");
@@ -2282,8 +2354,9 @@ int ipnn_eval(ipnn_handle* h, const int32_t* ids, const int32_t* y, int64_t N, d
     IHK(h, hipMalloc((void**)&p_d, (size_t)N * 4));
     for (int64_t lo = 0; lo < N; lo += h->Bmax) {
         const int B = (int)(N - lo < h->Bmax ? N - lo : h->Bmax);
-        const int rc = h->bf16 ? ip_run<bf16_t>(h, ids + lo * h->F, nullptr, B, nullptr, nullptr, p_d + lo, false)
-                               : ip_run<float>(h, ids + lo * h->F, nullptr, B, nullptr, nullptr, p_d + lo, false);
+        const float* w = wts ? wts + lo * h->F : nullptr;        // the chunk's weights travel with its ids
+        const int rc = h->bf16 ? ip_run<bf16_t>(h, ids + lo * h->F, w, nullptr, B, nullptr, nullptr, p_d + lo, false)
+                               : ip_run<float>(h, ids + lo * h->F, w, nullptr, B, nullptr, nullptr, p_d + lo, false);
         if (rc != FNN_OK) { hipFree(p_d); return rc; }
     }
     double out[4] = {0, 0, 0, 0};

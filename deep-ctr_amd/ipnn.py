@@ -3,8 +3,9 @@
 `IPNNEngine` is the PyTorch-ROCm plumbing; the three class names of the reference are kept as
 constructors with its `_rch_argv` layout (X_dim, X_feas, rank, h1..hN, act_func), its `forward`
 role (`train_step` / `predict`) and its `dump` keys (`W`, `V`, `b`, `h{i}_w`, `h{i}_b`).
-Categorical fields only (one id per field; X_feas = 2..64 at rank <= 15 -- the reference's own 39 columns included -- and 2..32
-above); optimiser 'sgd', 'adam' or 'ftrl' (python/tf_util.py:15-29).  rank 0..127
+One id per field and, optionally, one value weight per (example, field) -- `wts`, e_f = wts * row: the reference's Criteo
+feed of 13 numeric and 26 weighted categorical fields, see `criteo_feed` -- at X_feas = 2..64 for rank <= 15 (the reference's own
+39 columns included) and 2..32 above; optimiser 'sgd', 'adam' or 'ftrl' (python/tf_util.py:15-29).  rank 0..127
 (k = rank + 1 up to 128, either precision): an FM50 / FM100 pickle from FM.dump seeds FNN_IP_L3_50 / FNN100 through
 _init_argv."""
 import ctypes as C
@@ -14,6 +15,21 @@ import numpy as np
 
 from . import _capi
 from .engine import FNNError
+
+
+def criteo_feed(v_wts, c_ids, c_wts, offsets):
+    """The reference's three feeds (python/baseline.py:347-349: `_vals[:, :13]`, `_cols[:, 13:] - offsets`, `_vals[:, 13:]`) as
+    one (ids int32 [B, n_v + n_c], wts float32 [B, n_v + n_c]) pair: numeric field i is row i of the table weighted by its value
+    (python/FNN_IP_L7.py:103), categorical field j is row c_ids[:, j] + offsets[j] weighted by c_wts[:, j].  Pure NumPy."""
+    v_wts, c_ids, c_wts = np.asarray(v_wts), np.asarray(c_ids), np.asarray(c_wts)
+    B, n_v = v_wts.shape
+    if c_ids.shape != c_wts.shape or c_ids.shape[0] != B:
+        raise ValueError("criteo_feed: v_wts %r, c_ids %r, c_wts %r" % (v_wts.shape, c_ids.shape, c_wts.shape))
+    off = np.broadcast_to(np.asarray(offsets, dtype=np.int64), (c_ids.shape[1],))
+    ids = np.empty((B, n_v + c_ids.shape[1]), dtype=np.int32)
+    ids[:, :n_v] = np.arange(n_v, dtype=np.int32)
+    ids[:, n_v:] = c_ids.astype(np.int64) + off
+    return ids, np.concatenate([v_wts, c_wts], axis=1).astype(np.float32)
 
 
 class IPNNEngine(object):
@@ -87,10 +103,20 @@ class IPNNEngine(object):
             return a.to(device=self.device, dtype=dtype).contiguous()
         return torch.as_tensor(np.ascontiguousarray(a)).to(device=self.device, dtype=dtype).contiguous()
 
-    def train_step(self, ids, y, masks=None, want_logits=False, want_loss=True):
-        """masks: list of len(hidden)+1 uint8 arrays [B, d_t] (keep-masks for z1 and every hidden layer)."""
+    def _wts(self, wts, ids_t):
+        """Value weights on the device (f32, the shape of ids), or None: every weight 1, the call without weights."""
+        if wts is None:
+            return None
+        if tuple(wts.shape) != tuple(ids_t.shape):
+            raise ValueError("wts has shape %r, ids %r" % (tuple(wts.shape), tuple(ids_t.shape)))
+        return self._dev(wts, self._torch.float32)
+
+    def train_step(self, ids, y, masks=None, want_logits=False, want_loss=True, wts=None):
+        """masks: list of len(hidden)+1 uint8 arrays [B, d_t] (keep-masks for z1 and every hidden layer).
+        wts: value weights [B, F] (e_f = wts * row), None = all ones."""
         torch = self._torch
         ids_t, y_t = self._dev(ids, torch.int32), self._dev(y, torch.float32)
+        wts_t = self._wts(wts, ids_t)
         B = ids_t.shape[0]
         mts, marr = None, None
         if masks is not None:
@@ -100,31 +126,44 @@ class IPNNEngine(object):
         logits = torch.empty(B, dtype=torch.float32, device=self.device) if want_logits else None
         loss = C.c_float()
         self.stream.wait_stream(torch.cuda.current_stream(self.device))
-        self._ck(self.lib.ipnn_train_step(self.h, ids_t.data_ptr(), y_t.data_ptr(), B, marr,
-                                          logits.data_ptr() if want_logits else None, C.byref(loss) if want_loss else None))
+        if wts_t is None:
+            self._ck(self.lib.ipnn_train_step(self.h, ids_t.data_ptr(), y_t.data_ptr(), B, marr,
+                                              logits.data_ptr() if want_logits else None, C.byref(loss) if want_loss else None))
+        else:
+            self._ck(self.lib.ipnn_train_step_w(self.h, ids_t.data_ptr(), wts_t.data_ptr(), y_t.data_ptr(), B, marr,
+                                                logits.data_ptr() if want_logits else None, C.byref(loss) if want_loss else None))
         torch.cuda.current_stream(self.device).wait_stream(self.stream)
-        self._keep = (ids_t, y_t, mts)
+        self._keep = (ids_t, y_t, mts, wts_t)
         scale = 1.0 if self.reduce == 'sum' else 1.0 / B     # the library returns the sum of the per-example losses
         return {'loss': float(loss.value) * scale if want_loss else None, 'logits': logits}
 
-    def predict(self, ids):
+    def predict(self, ids, wts=None):
         torch = self._torch
         ids_t = self._dev(ids, torch.int32)
+        wts_t = self._wts(wts, ids_t)
         out = torch.empty(ids_t.shape[0], dtype=torch.float32, device=self.device)
         self.stream.wait_stream(torch.cuda.current_stream(self.device))
         for lo in range(0, ids_t.shape[0], self.max_batch):          # ipnn_predict takes at most max_batch examples a call
             hi = min(ids_t.shape[0], lo + self.max_batch)
-            self._ck(self.lib.ipnn_predict(self.h, ids_t[lo:hi].data_ptr(), hi - lo, out[lo:hi].data_ptr()))
+            if wts_t is None:
+                self._ck(self.lib.ipnn_predict(self.h, ids_t[lo:hi].data_ptr(), hi - lo, out[lo:hi].data_ptr()))
+            else:
+                self._ck(self.lib.ipnn_predict_w(self.h, ids_t[lo:hi].data_ptr(), wts_t[lo:hi].data_ptr(), hi - lo, out[lo:hi].data_ptr()))
         torch.cuda.current_stream(self.device).wait_stream(self.stream)
         return out
 
-    def evaluate(self, ids, y):
-        """python/baseline.py:382-437: predictions + AUC / RMSE / logloss on the device (ipnn_eval)."""
+    def evaluate(self, ids, y, wts=None):
+        """python/baseline.py:382-437: predictions + AUC / RMSE / logloss on the device (ipnn_eval / ipnn_eval_w)."""
         torch = self._torch
         ids_t, y_t = self._dev(ids, torch.int32), self._dev(y, torch.int32)
+        wts_t = self._wts(wts, ids_t)
         auc, rmse, ll = C.c_double(), C.c_double(), C.c_double()
         self.stream.wait_stream(torch.cuda.current_stream(self.device))
-        self._ck(self.lib.ipnn_eval(self.h, ids_t.data_ptr(), y_t.data_ptr(), ids_t.shape[0], C.byref(auc), C.byref(rmse), C.byref(ll)))
+        if wts_t is None:
+            self._ck(self.lib.ipnn_eval(self.h, ids_t.data_ptr(), y_t.data_ptr(), ids_t.shape[0], C.byref(auc), C.byref(rmse), C.byref(ll)))
+        else:
+            self._ck(self.lib.ipnn_eval_w(self.h, ids_t.data_ptr(), wts_t.data_ptr(), y_t.data_ptr(), ids_t.shape[0],
+                                          C.byref(auc), C.byref(rmse), C.byref(ll)))
         return {'auc': auc.value, 'rmse': rmse.value, 'logloss': ll.value}
 
     def sync(self):
@@ -172,16 +211,18 @@ class _IPFamily(object):
         self.eng.set_params(np.concatenate([W, V], axis=1), b, Ws, bs)
         self.rank, self.X_dim = rank, X_dim
 
-    def train_step(self, ids, y, masks=None):
-        return self.eng.train_step(ids, y, masks)
+    def train_step(self, ids, y, masks=None, wts=None):
+        return self.eng.train_step(ids, y, masks, wts=wts)
 
-    def forward(self, ids, v_wts=None):
-        """Predictions for categorical ids [N, X_feas].  The reference's `forward(N, M, v_wts, c_ids, c_wts, ...)`
-        (python/FNN_IP_L7.py:102-106) also takes Criteo's 13 numeric fields, each a value times a row (:103): not built --
-        the path here is the iPinYou shape, one categorical id per field, every weight 1."""
+    def forward(self, ids, v_wts=None, wts=None):
+        """Predictions for ids [N, X_feas] (global row ids) and, optionally, value weights wts [N, X_feas].  The reference's
+        `forward(N, M, v_wts, c_ids, c_wts, ...)` (python/FNN_IP_L7.py:102-106) takes its 13 numeric and 26 categorical fields
+        apart; here they are one (ids, wts) pair -- `criteo_feed(v_wts, c_ids, c_wts, offsets)` builds it -- so the reference's
+        own `v_wts` keyword alone is refused."""
         if v_wts is not None:
-            raise NotImplementedError("numeric value-weighted fields (python/FNN_IP_L7.py:103) are not built: categorical ids only")
-        return self.eng.predict(ids)
+            raise NotImplementedError("v_wts alone does not say which rows it weighs: pass wts= [N, X_feas] beside ids "
+                                      "(ipnn.criteo_feed(v_wts, c_ids, c_wts, offsets) returns both)")
+        return self.eng.predict(ids, wts=wts)
 
     def dump(self, model_path):
         """python/FNN_IP_L7.py:135-143: var_map pickle (touched rows only are current on the host:
@@ -210,6 +251,6 @@ class FNN_IP_L7(_IPFamily):
 class FNN(_IPFamily):
     """The reference's plain TensorFlow `FNN` class (python/FNN.py:5-101): z1 = [e_0 .. e_{F-1} | b], two
     hidden layers, activation and inverted dropout before every matmul; var_map keys W, V, b, h1_w .. h3_b.
-    (Its Criteo numeric fields -- a value times a row, :78 -- are not built: categorical fields only.)"""
+    (Its Criteo numeric fields -- a value times a row, :78 -- go through `wts`, as in the inner-product classes.)"""
     N_HIDDEN = 2
     PAIRS = False

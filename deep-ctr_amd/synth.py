@@ -61,6 +61,24 @@ def zipf_ids(n, field_sizes, s=1.1, seed=1234):
     return ids
 
 
+def criteo_like(B, n_numeric, cat_sizes, seed=1234, s=1.1, p_zero=0.05):
+    """(ids int32 [B, n_numeric + len(cat_sizes)], wts float32 of the same shape) in the layout of the reference's Criteo feed
+    (python/baseline.py:347-349) after ipnn.criteo_feed: numeric field i is the constant row i with a value in [0, 2) -- about
+    p_zero of them exact zeros, as a missing count is -- and the categorical fields are zipf ids behind the n_numeric rows,
+    weight 1."""
+    rng = np.random.RandomState(seed)
+    F = n_numeric + len(cat_sizes)
+    ids = np.empty((B, F), dtype=np.int32)
+    wts = np.ones((B, F), dtype=np.float32)
+    ids[:, :n_numeric] = np.arange(n_numeric, dtype=np.int32)
+    v = rng.uniform(0.0, 2.0, size=(B, n_numeric))
+    v[rng.uniform(size=(B, n_numeric)) < p_zero] = 0.0
+    wts[:, :n_numeric] = v
+    if len(cat_sizes):
+        ids[:, n_numeric:] = zipf_ids(B, list(cat_sizes), s, seed + 1) + n_numeric
+    return ids, wts
+
+
 def field_of_row(field_sizes):
     return np.repeat(np.arange(len(field_sizes), dtype=np.int32), field_sizes)
 

@@ -3,8 +3,10 @@
  * Replaces the TensorFlow graph of Atomu2014/deep-ctr's python/FNN_IP_L7.py (and _L3 / _L5, same
  * pattern): `forward` :102-133 (embeddings, pair-wise inner products, z1 = [e | p | b], then
  * l_{t+1} = dropout(act(l_t)) W_t + b_t with activation and inverted dropout BEFORE every matmul),
- * the loss sum(sigmoid_cross_entropy_with_logits) :82-88 and the gradient step.  Categorical
- * fields only (iPinYou shape: one id per field); optimiser: plain SGD, Adam or FTRL (IPNN_OPT_*).  Dropout keep-masks are INPUTS (uint8, one per element,
+ * the loss sum(sigmoid_cross_entropy_with_logits) :82-88 and the gradient step.  One id per field, and -- through the
+ * `_w` entry points -- one value weight per (example, field): e_f = wts[t][f] * table[ids[t][f]], which is both the iPinYou
+ * shape (every weight 1) and the reference's Criteo feed (13 numeric fields `v_wt * fm_wv[i]`, :103, and 26 weighted categorical
+ * ones).  Optimiser: plain SGD, Adam or FTRL (IPNN_OPT_*).  Dropout keep-masks are INPUTS (uint8, one per element,
  * reference column order), NULL = no dropout (`drop_out=False`).
  *
  * Field counts: narrow rows (k = 1..16) take 2..64 fields -- the reference's classes are 39-field models (X_feas = 13 +
@@ -101,10 +103,23 @@ int ipnn_set_loss_mean(ipnn_handle* h, int mean);
 /* p_out [B] = sigmoid(logits) without dropout (`test_preds`, FNN_IP_L3.py:81-84). */
 int ipnn_predict(ipnn_handle* h, const int32_t* ids, int B, float* p_out);
 
+/* Value weights: the same three calls with wts f32 [B, F] (DEVICE pointer, row-major like ids): the embedding of field f of
+ * example t is e_f = wts[t][f] * table[ids[t][f]] (python/FNN_IP_L7.py:103 for the numeric fields, the c_wts of
+ * embedding_lookup_sparse for the categorical ones); pairs, z1, the stack and the loss follow from e, and the gradient of a row
+ * is wts[t][f] * dL/de_f.  wts == NULL means every weight 1 and IS the call without `_w` (which forwards here with NULL): the
+ * same kernels, bit-identical results.  Weights are data: they are not range-checked, zero and negative values are legal (a
+ * zero weight leaves its row's gradient exactly 0), NaN and Inf propagate into the outputs and the touched rows.
+ * ipnn_eval_w advances wts with ids, max_batch examples a chunk. */
+int ipnn_train_step_w(ipnn_handle* h, const int32_t* ids, const float* wts, const float* y, int B,
+                      const uint8_t* const* masks, float* logits_out, float* loss_sum_out);
+int ipnn_predict_w(ipnn_handle* h, const int32_t* ids, const float* wts, int B, float* p_out);
+
 /* Evaluation pass (python/baseline.py:382-437 `test`): predict all N examples (DEVICE ids [N, F]
  * int32, y [N] int32; chunks of max_batch), then AUC / RMSE / logloss on the device.  Metrics are
  * HOST doubles.  One class only: FNN_ERR_RANGE. */
 int ipnn_eval(ipnn_handle* h, const int32_t* ids, const int32_t* y, int64_t N, double* auc, double* rmse, double* logloss);
+int ipnn_eval_w(ipnn_handle* h, const int32_t* ids, const float* wts, const int32_t* y, int64_t N,
+                double* auc, double* rmse, double* logloss);
 
 /* Measurement hook (bench.py): HIP events on the handle's stream around the segments of a train
  * step -- "sort", "ip_fwd", "fwd", "bwd", "wgrad", "ip_bwd", "scatter", "update".  enable(1) clears

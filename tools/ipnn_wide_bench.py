@@ -7,6 +7,11 @@ per-segment device times of ipnn_prof_* and a FLOP / byte model of the step.  On
   python tools/ipnn_wide_bench.py --digest --steps 5 --only l7_k11_bf16_sgd,...   (sha256 of table, layers and b after the steps)
   python tools/ipnn_wide_bench.py --fields 39    (narrow rows on N fields, synth.field_sizes_ipinyou(n_fields=N): the reference's
                                                   39 columns, up to 64; the default configurations are then the NARROW_MANY ones)
+  python tools/ipnn_wide_bench.py --weights criteo|random   (value weights through ipnn_train_step_w: `criteo` is
+                                                  synth.criteo_like -- the first 13 fields (a third of fewer than 39) are numeric,
+                                                  one constant row each for the whole batch, weighted by a value in [0, 2), the
+                                                  others categorical with weight 1; `random` keeps the ids and draws every weight
+                                                  from [0, 2); `none`, the default, is the call without weights)
 
 The k11 configurations use only what the parent C ABI already had, so the same script digests a build of the parent tree.
 The timed window and the profiled window are separate runs of the same steps: the profiling events sit between the launches."""
@@ -80,12 +85,11 @@ def model(B, K, cls, prec, opt, n_rows):
             'bytes_step': sum(by.values()), 'bytes_adam_table': adam_pass}
 
 
-def setup(name, B, NB, sizes, ids_h, y_h):
+def setup(name, B, NB, D, ids_h, y_h, w_h=None):
     import torch
     from deep_ctr_amd.ipnn import IPNNEngine
     cls, K, prec, opt = CONFIGS[name]
     hid = HIDDEN[cls]
-    D = sum(sizes)
     eng = IPNNEngine(F, K, hid, 'relu', max_batch=B, precision=prec, lr=1e-4 if opt == 'adam' else 1e-3, keep_prob=0.5,
                      pairs=cls != 'fnn', optimizer=opt, adam_eps=1e-8)
     rng = np.random.RandomState(77)
@@ -96,6 +100,7 @@ def setup(name, B, NB, sizes, ids_h, y_h):
     eng.set_params(table, 0.1, Ws, bs)
     ids = torch.as_tensor(ids_h).to(eng.device)
     y = torch.as_tensor(y_h).to(eng.device)
+    w = None if w_h is None else torch.as_tensor(w_h).to(eng.device)
     mk = [torch.as_tensor((np.random.RandomState(40 + t).uniform(size=(B, d[t])) < 0.5).astype(np.uint8)).to(eng.device)
           for t in range(len(hid) + 1)]
     marr = (C.c_void_p * len(mk))(*[m.data_ptr() for m in mk])
@@ -105,8 +110,12 @@ def setup(name, B, NB, sizes, ids_h, y_h):
     def steps_(n):
         for i in range(n):
             j = i % NB
-            eng._ck(lib.ipnn_train_step(h, ids.data_ptr() + j * B * F * 4, y.data_ptr() + j * B * 4, B, marr, None, None))
-    return eng, steps_, (ids, y, mk)
+            if w is None:
+                eng._ck(lib.ipnn_train_step(h, ids.data_ptr() + j * B * F * 4, y.data_ptr() + j * B * 4, B, marr, None, None))
+            else:
+                eng._ck(lib.ipnn_train_step_w(h, ids.data_ptr() + j * B * F * 4, w.data_ptr() + j * B * F * 4, y.data_ptr() + j * B * 4,
+                                              B, marr, None, None))
+    return eng, steps_, (ids, y, mk, w)
 
 
 def digest(eng, D):
@@ -119,7 +128,7 @@ def digest(eng, D):
     return h.hexdigest()
 
 
-def run(names, steps, warmup, B, prof, dig):
+def run(names, steps, warmup, B, prof, dig, weights='none'):
     sys.path.insert(0, ROOT)
     import torch
     import deep_ctr_amd  # noqa: F401
@@ -127,12 +136,18 @@ def run(names, steps, warmup, B, prof, dig):
     sizes = synth.field_sizes_ipinyou(n_fields=F)
     D = sum(sizes)
     NB = 8
-    ids_h = synth.zipf_ids(NB * B, sizes, 1.1, 99)
+    ids_h, w_h, n_num = synth.zipf_ids(NB * B, sizes, 1.1, 99), None, 0
+    if weights == 'criteo':
+        n_num = 13 if F >= 39 else F // 3
+        D = n_num + sum(sizes[n_num:])
+        ids_h, w_h = synth.criteo_like(NB * B, n_num, sizes[n_num:], seed=99)
+    elif weights == 'random':
+        w_h = np.random.RandomState(98).uniform(0.0, 2.0, size=ids_h.shape).astype(np.float32)
     y_h = (np.random.RandomState(3).uniform(size=NB * B) < 0.02).astype(np.float32)
     out = {}
     for name in names:
         cls, K, prec, opt = CONFIGS[name]
-        eng, steps_, keep = setup(name, B, NB, sizes, ids_h, y_h)
+        eng, steps_, keep = setup(name, B, NB, D, ids_h, y_h, w_h)
         lib, h = eng.lib, eng.h
         if dig:
             steps_(steps)
@@ -172,6 +187,7 @@ def run(names, steps, warmup, B, prof, dig):
                           share_of_roofline=max(t_mfma, t_hbm) / dt, achieved_tflops=md['flop'] / dt / 1e12)
         out[name] = r
     return {'tool': 'ipnn_wide_bench', 'mode': 'digest' if dig else 'time', 'n_rows': D, 'fields': F, 'batch': B, 'steps': steps,
+            'weights': weights, 'numeric_fields': n_num,
             'warmup': warmup, 'device': torch.cuda.get_device_name(0), 'configs': out}
 
 
@@ -182,6 +198,8 @@ def main():
     ap.add_argument('--batch', type=int, default=4096)
     ap.add_argument('--only', default=None)
     ap.add_argument('--fields', type=int, default=16, help='field count (2..64; more than 32: narrow rows only)')
+    ap.add_argument('--weights', choices=('none', 'criteo', 'random'), default='none',
+                    help='value weights of the steps (ipnn_train_step_w); none = the call without weights')
     ap.add_argument('--no-prof', action='store_true')
     ap.add_argument('--digest', action='store_true', help='sha256 of table, layers and b after --steps steps (no timing)')
     a = ap.parse_args()
@@ -191,7 +209,7 @@ def main():
     for n in names:
         if n not in CONFIGS:
             raise SystemExit('unknown config %r (%s)' % (n, ', '.join(CONFIGS)))
-    print(json.dumps(run(names, a.steps, a.warmup, a.batch, not a.no_prof, a.digest)))
+    print(json.dumps(run(names, a.steps, a.warmup, a.batch, not a.no_prof, a.digest, a.weights)))
 
 
 if __name__ == '__main__':
