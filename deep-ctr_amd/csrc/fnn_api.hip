@@ -44,8 +44,9 @@ struct fnn_handle {
     int F = 0, K = 0, H1 = 0, H2 = 0, xdim = 0, K1p = 0, H1p = 0, H2p = 0;
     int Bmax = 0, ldT = 0, N2max = 0;
     size_t n1 = 0, n2 = 0, nw12 = 0, nw = 0;
-    int splitk = 4;             // split-K of the weight-gradient products (measured: 4 -> 40.8 us per step, 8 -> 42.9, 2 -> 51.1)
+    int splitk = 4;             // split-K of the weight-gradient products (measured beside scat1_body: 4 -> 40.8 us per step, 8 -> 42.9, 2 -> 51.1; fnn_create: 8 beside scat1q_body)
     int scat2_wgs = 256;        // workgroups walking the multi-chunk segments in launch 3
+    int scat_slot = 0;          // FNN_SCAT1_FORM=slot: level 1 of the sparse-row update runs scat1_body (default: scat1q_body, quarter-columns)
     bool bf16 = false;          // FNN_PREC_BF16: 2-byte elements
     bool split = false;         // FNN_PREC_BF16X3: 4-byte elements (bs16_t), the f32 mode's layouts
     int step1_waves = 8;                                               // FNN_STEP1_WAVES=4: four waves per strip (the 2-byte element types at hidden 300 / 100 run eight)
@@ -311,7 +312,7 @@ void launch_step2(fnn_handle* h, bool dense, bool sparse, const float* gxp_src =
     const WgradArgs wa = make_wgrad_args<T>(h, Ba);
     const int nwx = dense ? wgrad_blocks(wa) : 0;
     const int nsc = !sparse ? 0 : (h->bag ? (int)(((size_t)h->F * (SORT_N / WCH) * (h->rw / 4) + 255) / 256)
-                                          : h->F * SORT_N / 256);
+                                          : scat1_blocks(sa, h->scat_slot));
     SortArgs so{h->next_ids, h->next_B, h->F, h->n_rows, h->slot[nxt].rec, h->slot[nxt].owner_cnt,
                 have_next ? 4 * h->F : 0, h->skeys, nullptr, nullptr, 0};
     const dim3 grid(so.nblk + nwx * h->splitk + nsc);
@@ -631,8 +632,8 @@ int run_step(fnn_handle* h, const int32_t* ids, const float* y, int B, const uin
     }
     {
         ProfScope ps(h, "scatter", h->st);
-        const size_t nthr = (size_t)F * N2;                  // 16 lanes per chunk of 16 entries
-        hipLaunchKernelGGL(k_scat1, dim3((unsigned)((nthr + 255) / 256)), dim3(256), 0, h->st, sa);
+        const int nblk = scat1_blocks(sa, h->scat_slot);     // a thread per live quarter-column of a chunk of 16 entries (or 16 lanes per chunk)
+        hipLaunchKernelGGL(k_scat1, dim3(nblk), dim3(256), 0, h->st, sa);
     }
     {
         ProfScope ps(h, "finalize", h->st);
@@ -701,7 +702,8 @@ int scatter_global_impl(fnn_handle* h, const int32_t* ids_g, const float* gxp_g,
         ProfScope ps(h, "scatter_global", h->st);
         ScatArgs sa = make_scat_args(h, sl, N2);
         sa.gxp = gxp_g;
-        hipLaunchKernelGGL(k_scat1, dim3((unsigned)(((size_t)F * N2 + 255) / 256)), dim3(256), 0, h->st, sa);
+        const int nblk = scat1_blocks(sa, h->scat_slot);     // after sa.gxp changed: the caller's buffer may not be 16-byte aligned
+        hipLaunchKernelGGL(k_scat1, dim3(nblk), dim3(256), 0, h->st, sa);
         hipLaunchKernelGGL(k_scat2, dim3(N2 > 4096 ? 256 : 64), dim3(256), 0, h->st, sa);
     }
     HIPCHK(h, hipGetLastError());
@@ -862,6 +864,12 @@ int fnn_create(const fnn_cfg* cfg, fnn_handle** out)
     h->bf16 = cfg->precision == FNN_PREC_BF16; h->split = cfg->precision == FNN_PREC_BF16X3;
     if (const char* ev = getenv("FNN_NO_FUSE")) h->fused = !(ev[0] == '1');
     if (const char* ev = getenv("FNN_ROLE_OFF")) h->role_off = atoi(ev);
+    h->scat_slot = scat1_form_env();
+    // the quarter-column scatter role leaves launch 2 the residency for eight K slices of the weight gradients (bf16 37.4 us per
+    // step against 38.4 with four, f32 57.1 against 61.4; the bf16 pairs 46.9 against 45.1 and stay at four; beside the
+    // slot-per-lane role eight are slower: 39.8 against 39.1) -- profiles/scat1_forms_ab.json
+    // (handles whose every step of up to 4096 examples takes the three launches; the layer-by-layer kernels keep four)
+    if (h->fused && mlp_shape_ok(h) && !h->bag && !h->scat_slot && !h->split && h->Bmax <= SORT_N) h->splitk = 8;
     if (const char* ev = getenv("FNN_SPLITK")) { const int v = atoi(ev); if (v == 2 || v == 4 || v == 8 || v == 16) h->splitk = v; }   // tuning knob
     if (const char* ev = getenv("FNN_SCAT2_WGS")) { const int v = atoi(ev); if (v >= 16 && v <= 1024) h->scat2_wgs = v; }
     const size_t ts = tsize(h), Ba = h->ldT;

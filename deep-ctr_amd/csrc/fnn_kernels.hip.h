@@ -20,6 +20,8 @@
 #pragma once
 #include <hip/hip_runtime.h>
 #include <stdint.h>
+#include <stdlib.h>
+#include <string.h>
 #include <type_traits>
 
 namespace fnn {
@@ -1615,11 +1617,16 @@ static __global__ void k_check_shadowed(const int32_t* __restrict__ tfr, int n, 
 //             cross waves -- then every sorted entry learns its segment [s, e) by binary search
 //             -> rec {row, t, s, e}.  Independent of the gradients: runs on a side stream under
 //             the MLP.
-//   k_scat1   a 16-lane group (lane = slot of the row) owns 16 consecutive sorted entries and adds
-//             g * c^(e-1-pos) in f64 per run of equal rows.  The weight is absolute inside the
-//             segment, so partial sums of a segment cut by chunk borders simply add up.  Runs
-//             that lie inside the chunk are written back at once; the others leave a partial and
-//             the run that opens a multi-chunk segment registers its owner.
+//   k_scat1   a chunk of 16 consecutive sorted entries is folded per slot of the row: g * c^(e-1-pos)
+//             added in f64 per run of equal rows, in entry order.  A thread owns one 16-byte
+//             quarter-column of the chunk (scat1q_body: only the quarters with live slots, 3 of 4
+//             at K = 11) and has a sub-batch of 8 entries' gradients, old rows and decay factors
+//             in flight at once; FNN_SCAT1_FORM=slot runs the earlier form, a 16-lane group per
+//             chunk with a lane per slot (scat1_body), bit for bit the same result.  The weight
+//             is absolute inside the segment, so partial sums of a segment cut by chunk borders
+//             simply add up.  Runs that lie inside the chunk are written back at once; the
+//             others leave a partial and the run that opens a multi-chunk segment registers its
+//             owner.
 //   k_scat2   one workgroup per registered owner adds the partials of its segment in a fixed
 //             order and writes the row.  No float atomics anywhere: the result is bitwise
 //             reproducible.
@@ -1736,6 +1743,7 @@ struct ScatArgs {
     int rw;          // 16: FM rows (decayed update); otherwise the bag-table row width (plain sum)
     const int* tag_shared; int stamp;     // bag mode: tag_shared[row] == stamp <=> the row sits in several columns of this batch (SortArgs)
     int gxf;         // wide update (scatw*): floats between two fields' gradients of an example (wide FM rows: rw); 0: one per example (bag)
+    int slot_form;   // level 1 of the 16-float rows: 0 = scat1q_body (a thread per quarter-column), 1 = scat1_body (a lane per slot); set by scat1_blocks
 };
 // bag rows held by several columns of a batch: every column adds its sum with float atomics (a row touched by one column
 // only -- the rule on iPinYou lines -- keeps the plain read-modify-write, one rounding)
@@ -1756,9 +1764,11 @@ __device__ __forceinline__ void scat1_body(const ScatArgs& sa, const int blk)
     const int4 mine = rec[(size_t)f * N2 + base + l];
     // both decay factors of an entry depend on its record only: its own weight c^(e-1-pos) and its
     // segment's c^(e-s) -- fetched together with the gradients and the old rows, not after them.
-    // (The conditional loads below compile to a branch and a wait per entry.  Making all 34 of them unconditional puts them
-    // in flight together and was measured SLOWER inside the launch, 16.4 -> 18.2 us, A/B on one box with tools/gpu_ab.sh:
-    // the role shares its CUs' 64 B/clk texture path with the weight-gradient role, which the burst of dword loads starves.)
+    // (The conditional loads below compile to a branch and a wait per entry: 18 dependent round trips per chunk.  Making all
+    // 34 dword loads unconditional was measured SLOWER inside the launch, 16.4 -> 18.2 us.  What did shorten the chain is
+    // scat1q_body below -- four times fewer, four times wider loads, 8 entries in flight: the role alone 14.5 -> 12.8 us on the
+    // events' clock, launch 2 14.35 -> 13.7 us at split-K 4 and 13.1 us with the eight K slices it then has room for.  This form
+    // stays as FNN_SCAT1_FORM=slot.)
     const double wmine = (mine.x >= 0) ? cpow[mine.w - 1 - (base + l)] : 0.0;
     const double cmine = (mine.x >= 0) ? cpow[mine.w - mine.z] : 0.0;
     int row[16], sg[16], eg[16];
@@ -1795,7 +1805,105 @@ __device__ __forceinline__ void scat1_body(const ScatArgs& sa, const int blk)
     }
 }
 
-static __global__ __launch_bounds__(256) void k_scat1(const ScatArgs sa) { scat1_body(sa, blockIdx.x); }
+// The quarter-column form of scat1_body (the narrow-row sibling of scatdw1_body below): a thread owns one 16-byte quarter of a
+// chunk of 16 sorted entries, only the (K + 3) / 4 quarters that hold live slots get a thread.  Two sub-batches of 8 entries;
+// the records of the second are requested before the data of the first, and a sub-batch's gradients (one float4 per entry), old
+// rows and both decay factors go out together: rec -> {gx', rows, cpow} -> stores, twice, instead of a wait per entry.
+// Chunks, partials and owners are those of scat1_body (scat2_body reads either), and every slot folds its entries in the same
+// order with the same f64 operations, so the two forms give the same bits (tests/test_gpu_scat1_forms.py).
+// Needs gxp and table16 16-byte aligned and K1p % 4 == 0 (scat1_blocks checks).
+__device__ __forceinline__ void scat1q_body(const ScatArgs& sa, const int blk)
+{
+    const int N2 = sa.N2, NQ = N2 >> 4, nq = (sa.K + 3) >> 2;
+    const int gid = blk * 256 + (int)threadIdx.x;
+    const int chunk = gid / nq, q = gid % nq;
+    if (chunk >= sa.F * NQ) return;
+    const int f = chunk / NQ, qc = chunk % NQ, base = qc * 16;
+    const int lim = sa.K - 4 * q;                           // live lanes of this quarter: < 4 only in the last one of a padded row
+    const double* __restrict__ cpow = sa.cpow; const double lr = sa.lr;
+    double a0 = 0, a1 = 0, a2 = 0, a3 = 0;
+    int4 rn[8];
+#pragma unroll
+    for (int j = 0; j < 8; ++j) rn[j] = sa.rec[(size_t)f * N2 + base + j];
+    for (int sb = 0; sb < 16; sb += 8) {
+        int4 r[8];
+#pragma unroll
+        for (int j = 0; j < 8; ++j) r[j] = rn[j];
+        if (r[0].x < 0) break;                               // invalid keys sort to the end
+        if (sb == 0) {
+#pragma unroll
+            for (int j = 0; j < 8; ++j) rn[j] = sa.rec[(size_t)f * N2 + base + 8 + j];
+        }
+        float4 g[8], wold[8];
+        double wd[8], cs[8];
+#pragma unroll
+        for (int j = 0; j < 8; ++j) {
+            const int pos = base + sb + j;
+            const bool live = r[j].x >= 0;
+            // (dead entries and entries that write no row read example 0 / row 0 / cpow[0]: in bounds, and they stay in cache)
+            g[j] = *reinterpret_cast<const float4*>(sa.gxp + (size_t)(live ? r[j].y : 0) * sa.K1p + f * SLOT + 4 * q);
+            // the old row and the segment's decay c^(e-s) only where the row is written: the last entry of a segment inside the chunk
+            const bool need = live && pos + 1 == r[j].w && r[j].z >= base;
+            wold[j] = *reinterpret_cast<const float4*>(sa.table16 + (size_t)(need ? r[j].x : 0) * SLOT + 4 * q);
+            wd[j] = cpow[live ? r[j].w - 1 - pos : 0];
+            cs[j] = cpow[need ? r[j].w - r[j].z : 0];
+        }
+        if (lim < 4) {                                       // pad lanes take no gradient
+#pragma unroll
+            for (int j = 0; j < 8; ++j) {
+                if (lim < 2) g[j].y = 0.f;
+                if (lim < 3) g[j].z = 0.f;
+                g[j].w = 0.f;
+            }
+        }
+#pragma unroll
+        for (int j = 0; j < 8; ++j) {
+            if (r[j].x < 0) continue;
+            a0 += (double)g[j].x * wd[j]; a1 += (double)g[j].y * wd[j]; a2 += (double)g[j].z * wd[j]; a3 += (double)g[j].w * wd[j];
+            const int pos = base + sb + j, s = r[j].z, e = r[j].w;
+            if (pos + 1 != e && pos + 1 != base + 16) continue;        // the run goes on inside this chunk
+            if (s >= base && e <= base + 16) {                       // the whole segment lies in this chunk
+                float4 o = make_float4((float)((double)wold[j].x * cs[j] - lr * a0), (float)((double)wold[j].y * cs[j] - lr * a1),
+                                       (float)((double)wold[j].z * cs[j] - lr * a2), (float)((double)wold[j].w * cs[j] - lr * a3));
+                if (lim < 4) {                                       // pad lanes of the row keep what they hold (scat1_body never writes them)
+                    if (lim < 2) o.y = wold[j].y;
+                    if (lim < 3) o.z = wold[j].z;
+                    o.w = wold[j].w;
+                }
+                *reinterpret_cast<float4*>(sa.table16 + (size_t)r[j].x * SLOT + 4 * q) = o;
+            } else {
+                const int which = (s < base) ? 0 : 1;                // 0: enters from the left; 1: opens here
+                double* pp = sa.part + (((size_t)f * NQ + qc) * 2 + which) * SLOT + 4 * q;
+                pp[0] = a0; pp[1] = a1; pp[2] = a2; pp[3] = a3;
+                if (which == 1 && q == 0) sa.owners[atomicAdd(sa.owner_cnt, 1)] = make_int4(f, s, e, r[j].x);
+            }
+            a0 = a1 = a2 = a3 = 0;
+        }
+    }
+}
+
+static __global__ __launch_bounds__(256) void k_scat1(const ScatArgs sa)
+{
+    if (sa.slot_form) scat1_body(sa, blockIdx.x);
+    else scat1q_body(sa, blockIdx.x);
+}
+
+// Workgroups of level 1 on 16-float rows -- k_scat1's grid and the scatter role's share of k_step2's -- and the form they run:
+// `slot_form` is the handle's choice (FNN_SCAT1_FORM, scat1_form_env), overruled where the float4 loads of the quarter-column
+// form would be misaligned.  Every launch site takes its count from here, after the last change to sa.
+inline int scat1_blocks(ScatArgs& sa, const int slot_form)
+{
+    const bool vec_ok = ((uintptr_t)sa.gxp | (uintptr_t)sa.table16) % 16 == 0 && sa.K1p % 4 == 0;
+    sa.slot_form = (slot_form || !vec_ok) ? 1 : 0;
+    const size_t nthr = sa.slot_form ? (size_t)sa.F * sa.N2 : (size_t)sa.F * (sa.N2 / 16) * ((sa.K + 3) / 4);
+    return (int)((nthr + 255) / 256);
+}
+// FNN_SCAT1_FORM=slot|quarter (default quarter), read where a handle is created
+inline int scat1_form_env()
+{
+    const char* e = getenv("FNN_SCAT1_FORM");
+    return e && !strcmp(e, "slot") ? 1 : 0;
+}
 
 __device__ __forceinline__ void scat2_body(const ScatArgs& sa, const int blk, const int nblk, double (*s_sum)[16])
 {
