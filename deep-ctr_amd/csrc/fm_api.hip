@@ -371,6 +371,7 @@ struct fm_handle {
     // stamp [n_rows]; t = steps since the state was initialised.  dense_g: FM_OPT_DENSE_G=1, the A/B variant of k_fm_opt_pass.
     int opt = FM_OPT_SGD; float beta1 = 0.9f, beta2 = 0.999f, eps = 1e-8f; int64_t t = 0; bool dense_g = false;
     int scat_slot = 0;         // FNN_SCAT1_FORM=slot (scat1_blocks)
+    int sort_merge4 = 0;       // FNN_SORT_RUNS=4|16 (sortA_body; default 16: the run sort is a launch of its own here)
     float *s0 = nullptr, *s1 = nullptr, *sb = nullptr, *G = nullptr; int* stamp = nullptr;
 };
 
@@ -453,12 +454,13 @@ int fm_run_wide(fm_handle* h, FmArgs a, int B, float lr, float lambda, int reduc
         return FNN_OK;
     }
     SortArgs so{a.ids, B, F, h->n_rows, h->rec, h->owner_cnt, 4 * F, h->skeys};
+    so.merge4 = h->sort_merge4;
     SortArgs sb = so; sb.nblk = 16 * F;
     if (h->key64) {
-        hipLaunchKernelGGL((k_sortA<unsigned long long>), dim3(4 * F), dim3(256), 0, h->st, so);
+        hipLaunchKernelGGL((k_sortA<unsigned long long>), dim3(4 * F), dim3(256), sortA_lds_bytes<unsigned long long>(so.merge4), h->st, so);
         launch_fwd<unsigned long long>(h, &sb, a, Ba / ex);
     } else {
-        hipLaunchKernelGGL((k_sortA<unsigned>), dim3(4 * F), dim3(256), 0, h->st, so);
+        hipLaunchKernelGGL((k_sortA<unsigned>), dim3(4 * F), dim3(256), sortA_lds_bytes<unsigned>(so.merge4), h->st, so);
         launch_fwd<unsigned>(h, &sb, a, Ba / ex);
     }
     // SGD: the dense decay is the lazy scale, touched rows -= lr * g / scale; Adam / FTRL: G[row] = G[row] - (-1) * sum
@@ -514,12 +516,13 @@ int fm_run(fm_handle* h, const int32_t* ids, const float* y, int B, float lr, fl
     }
     {
         SortArgs so{ids, B, F, h->n_rows, h->rec, h->owner_cnt, 4 * F, h->skeys};
+        so.merge4 = h->sort_merge4;
         SortArgs sb = so; sb.nblk = 16 * F;
         if (h->key64) {
-            hipLaunchKernelGGL((k_sortA<unsigned long long>), dim3(4 * F), dim3(256), 0, h->st, so);
+            hipLaunchKernelGGL((k_sortA<unsigned long long>), dim3(4 * F), dim3(256), sortA_lds_bytes<unsigned long long>(so.merge4), h->st, so);
             launch_fwd<unsigned long long>(h, &sb, a, Ba / 16);
         } else {
-            hipLaunchKernelGGL((k_sortA<unsigned>), dim3(4 * F), dim3(256), 0, h->st, so);
+            hipLaunchKernelGGL((k_sortA<unsigned>), dim3(4 * F), dim3(256), sortA_lds_bytes<unsigned>(so.merge4), h->st, so);
             launch_fwd<unsigned>(h, &sb, a, Ba / 16);
         }
     }
@@ -586,6 +589,7 @@ int fm_create(int n_fields, int k, int max_batch, int device, void* stream, fm_h
 #undef FK
     h->dense_g = getenv("FM_OPT_DENSE_G") && atoi(getenv("FM_OPT_DENSE_G")) == 1;
     h->scat_slot = scat1_form_env();
+    h->sort_merge4 = sort_merge4_env(0);
     *out = h;
     return FNN_OK;
 }

@@ -46,11 +46,13 @@ struct fnn_handle {
     size_t n1 = 0, n2 = 0, nw12 = 0, nw = 0;
     int splitk = 4;             // split-K of the weight-gradient products (measured beside scat1_body: 4 -> 40.8 us per step, 8 -> 42.9, 2 -> 51.1; fnn_create: 8 beside scat1q_body)
     int scat2_wgs = 256;        // workgroups walking the multi-chunk segments in launch 3
+    int sort_merge4 = 1;        // FNN_SORT_RUNS=4 (the default on FM rows): the run sort leaves 4 runs of 1024 keys per field for the rank merge; 16 (bag mode's default): 16 runs of 256
     int scat_slot = 0;          // FNN_SCAT1_FORM=slot: level 1 of the sparse-row update runs scat1_body (default: scat1q_body, quarter-columns)
     bool bf16 = false;          // FNN_PREC_BF16: 2-byte elements
     bool split = false;         // FNN_PREC_BF16X3: 4-byte elements (bs16_t), the f32 mode's layouts
     int step1_waves = 8;                                               // FNN_STEP1_WAVES=4: four waves per strip (the 2-byte element types at hidden 300 / 100 run eight)
-    int wt_stores = 15;                                                // FNN_WT_STORES (MlpArgs::wt; 0: plain stores): how the strip kernel's training outputs leave
+    int wt_stores = 47;                                                // FNN_WT_STORES (MlpArgs::wt; 0: plain stores): how the strip kernel's training outputs leave
+                                                                       // (bit 32: bf16 on FM rows, the transposed activations 16 bytes per lane, written through or plain as bit 1 says)
     bool bag = false; int rw = SLOT; size_t nbag = 0, off_bag = 0;     // FNN_MODE_BAG: bag rows rw floats wide
     bool wide = false;          // FNN_MODE_FM with k >= 17: FM rows of rw = rup(k, 4) floats, w_0 / ones columns F*rw and F*rw + 1
     float* bb0 = nullptr; void* dlxT = nullptr; void* onesT = nullptr; float* gx_raw = nullptr;
@@ -284,13 +286,14 @@ template <typename T> void launch_step1(fnn_handle* h, int nmlp, const MlpArgs<T
         else hipLaunchKernelGGL((k_step1<T, 1, 1, 4, false>), g, b, lds, h->st, a);
     }
 }
-void launch_sort16(fnn_handle* h, const SortArgs& so) {      // split sort: 256-key runs, then the rank merge
+void launch_sort16(fnn_handle* h, SortArgs so) {             // split sort: the runs, then the rank merge
     const int F = so.nblk;
+    so.merge4 = h->sort_merge4;
     if (h->key64) {
-        hipLaunchKernelGGL((k_sortA<unsigned long long>), dim3(4 * F), dim3(256), 0, h->st, so);
+        hipLaunchKernelGGL((k_sortA<unsigned long long>), dim3(4 * F), dim3(256), sortA_lds_bytes<unsigned long long>(so.merge4), h->st, so);
         hipLaunchKernelGGL((k_sortB<unsigned long long>), dim3(16 * F), dim3(256), SORT_N * 8, h->st, so);
     } else {
-        hipLaunchKernelGGL((k_sortA<unsigned>), dim3(4 * F), dim3(256), 0, h->st, so);
+        hipLaunchKernelGGL((k_sortA<unsigned>), dim3(4 * F), dim3(256), sortA_lds_bytes<unsigned>(so.merge4), h->st, so);
         hipLaunchKernelGGL((k_sortB<unsigned>), dim3(16 * F), dim3(256), SORT_N * 4, h->st, so);
     }
 }
@@ -314,14 +317,30 @@ void launch_step2(fnn_handle* h, bool dense, bool sparse, const float* gxp_src =
     const int nsc = !sparse ? 0 : (h->bag ? (int)(((size_t)h->F * (SORT_N / WCH) * (h->rw / 4) + 255) / 256)
                                           : scat1_blocks(sa, h->scat_slot));
     SortArgs so{h->next_ids, h->next_B, h->F, h->n_rows, h->slot[nxt].rec, h->slot[nxt].owner_cnt,
-                have_next ? 4 * h->F : 0, h->skeys, nullptr, nullptr, 0};
+                have_next ? 4 * h->F : 0, h->skeys, nullptr, nullptr, 0, h->sort_merge4};
     const dim3 grid(so.nblk + nwx * h->splitk + nsc);
     if (grid.x == 0) return;
-    if (h->key64)
-        hipLaunchKernelGGL((k_step2<T, unsigned long long>), grid, dim3(256), 0, h->st, so, wa, nwx,
-                           h->splitk, sa);
-    else
-        hipLaunchKernelGGL((k_step2<T, unsigned>), grid, dim3(256), 0, h->st, so, wa, nwx, h->splitk, sa);
+    if (h->key64) {
+        const size_t lds = sortA_lds_bytes<unsigned long long>(so.merge4);
+        if (so.merge4) hipLaunchKernelGGL((k_step2<T, unsigned long long, true>), grid, dim3(256), lds, h->st, so, wa, nwx, h->splitk, sa);
+        else hipLaunchKernelGGL((k_step2<T, unsigned long long, false>), grid, dim3(256), lds, h->st, so, wa, nwx, h->splitk, sa);
+    } else {
+        const size_t lds = sortA_lds_bytes<unsigned>(so.merge4);
+        if (so.merge4) hipLaunchKernelGGL((k_step2<T, unsigned, true>), grid, dim3(256), lds, h->st, so, wa, nwx, h->splitk, sa);
+        else hipLaunchKernelGGL((k_step2<T, unsigned, false>), grid, dim3(256), lds, h->st, so, wa, nwx, h->splitk, sa);
+    }
+}
+
+template <typename T, bool M4>
+void launch_step3_form(fnn_handle* h, bool update, const dim3 grid, const size_t lds, const SortArgs& so, const TailArgs& ta, const ScatArgs& sa)
+{
+    if (h->key64) {
+        if (update) hipLaunchKernelGGL((k_step3<T, true, unsigned long long, M4>), grid, dim3(256), lds, h->st, so, ta, sa);
+        else hipLaunchKernelGGL((k_step3<T, false, unsigned long long, M4>), grid, dim3(256), lds, h->st, so, ta, sa);
+    } else {
+        if (update) hipLaunchKernelGGL((k_step3<T, true, unsigned, M4>), grid, dim3(256), lds, h->st, so, ta, sa);
+        else hipLaunchKernelGGL((k_step3<T, false, unsigned, M4>), grid, dim3(256), lds, h->st, so, ta, sa);
+    }
 }
 
 template <typename T>
@@ -341,17 +360,12 @@ void launch_step3(fnn_handle* h, bool dense, bool sparse, bool update, float* bu
                     h->w1, h->w1t, h->w2, h->w2t, nred, h->bb0, h->nbag, h->off_bag};
         const int stamp = have_next ? next_stamp(h, h->slot[nxt]) : 0;      // the rank merge of the NEXT batch marks its shared rows
         SortArgs so{h->next_ids, h->next_B, h->F, h->n_rows, h->slot[nxt].rec, h->slot[nxt].owner_cnt,
-                    have_next ? 16 * h->F : 0, h->skeys, h->tag_first, h->slot[nxt].tag_shared, stamp};
+                    have_next ? 16 * h->F : 0, h->skeys, h->tag_first, h->slot[nxt].tag_shared, stamp, h->sort_merge4};
         const dim3 grid(so.nblk + nred + (sparse ? h->scat2_wgs : 0));    // these workgroups walk the multi-chunk segments
         const size_t lds = h->key64 ? sort_lds_bytes<unsigned long long>() : sort_lds_bytes<unsigned>();
         if (grid.x > 0) {
-            if (h->key64) {
-                if (update) hipLaunchKernelGGL((k_step3<T, true, unsigned long long>), grid, dim3(256), lds, h->st, so, ta, sa);
-                else hipLaunchKernelGGL((k_step3<T, false, unsigned long long>), grid, dim3(256), lds, h->st, so, ta, sa);
-            } else {
-                if (update) hipLaunchKernelGGL((k_step3<T, true, unsigned>), grid, dim3(256), lds, h->st, so, ta, sa);
-                else hipLaunchKernelGGL((k_step3<T, false, unsigned>), grid, dim3(256), lds, h->st, so, ta, sa);
-            }
+            if (so.merge4) launch_step3_form<T, true>(h, update, grid, lds, so, ta, sa);
+            else launch_step3_form<T, false>(h, update, grid, lds, so, ta, sa);
         }
     }
     if (sparse) {
@@ -865,6 +879,7 @@ int fnn_create(const fnn_cfg* cfg, fnn_handle** out)
     if (const char* ev = getenv("FNN_NO_FUSE")) h->fused = !(ev[0] == '1');
     if (const char* ev = getenv("FNN_ROLE_OFF")) h->role_off = atoi(ev);
     h->scat_slot = scat1_form_env();
+    h->sort_merge4 = sort_merge4_env(h->bag ? 0 : 1);
     // the quarter-column scatter role leaves launch 2 the residency for eight K slices of the weight gradients (bf16 37.4 us per
     // step against 38.4 with four, f32 57.1 against 61.4; the bf16 pairs 46.9 against 45.1 and stay at four; beside the
     // slot-per-lane role eight are slower: 39.8 against 39.1) -- profiles/scat1_forms_ab.json

@@ -225,6 +225,50 @@ template <typename P> __device__ inline void store4_sel(const bool wt, P* p, flo
     if (wt) store4_wt(p, a, b, c, d); else store4(p, a, b, c, d);
 }
 __device__ inline void store1_wt(float* p, float a) { asm volatile("global_store_dword %0, %1, off sc1" :: "v"(p), "v"(a) : "memory"); }
+
+// ---- bf16 transposed activations in 16-byte stores (MlpArgs::wt bit 32).  ft_off<bf16_t> keeps examples 8 j .. 8 j + 7 of a column
+// in one 16-byte slot, but a lane of an MFMA epilogue owns 4 examples of its column (8 bytes: store4_wt is a dwordx2, priced at
+// 2.7 x the dwordx4 time per byte when written through); the lane 16 further on owns the other half of the slot.
+// v_permlane16_swap (vdst = tile i, src = tile i + 1) trades the odd 16-lane rows of tile i for the even rows of tile i + 1:
+// afterwards even rows hold {own, upper row's} 8 bytes of tile i and odd rows {lower row's, own} of tile i + 1 -- all 64 lanes
+// issue ONE 16-byte store per pair of tiles.  The stores are plain C++ or raw buffer stores (sc1 = aux 16), never inline
+// assembly: they sit behind wave-uniform branches the compiler cannot prove uniform, and it has to see their data registers.
+typedef unsigned int u32x2 __attribute__((ext_vector_type(2)));
+__device__ __forceinline__ u32x2 pack4_bf16(float a, float b, float c, float d) {
+    const bf16x4 v = {(bf16_t)a, (bf16_t)b, (bf16_t)c, (bf16_t)d};
+    u32x2 w; __builtin_memcpy(&w, &v, 8);
+    return w;
+}
+struct T16Dst { bf16_t* base; __amdgpu_buffer_rsrc_t rs; bool wt; };
+// `cols` x ldT elements: the extent of the operand, beyond which a buffer store is dropped
+__device__ __forceinline__ T16Dst t16_dst(bf16_t* base, const int cols, const int ldT, const bool wt) {
+    return T16Dst{base, __builtin_amdgcn_make_buffer_rsrc(base, 0, cols * ldT * 2, 0x00020000), wt};
+}
+__device__ __forceinline__ void t16_store(const T16Dst& d, const size_t elem, const u32x4 w) {
+    if (d.wt) __builtin_amdgcn_raw_buffer_store_b128(w, d.rs, (int)(elem * 2), 0, 16);
+    else *reinterpret_cast<u32x4*>(d.base + elem) = w;
+}
+// pk[i]: a lane's 4 examples t0 + 4 lq .. + 3 of column lr of tile tile0 + i, for the wave's run of C tiles clipped at NF
+// (tile0, NF: wave-uniform).  A run's unpaired last tile is stored by the even rows only.
+template <int C>
+__device__ __forceinline__ void t16_store_run(const T16Dst& d, const u32x2 (&pk)[C], const int tile0, const int NF, const int t0,
+                                              const int ldT, const int lr, const int lq) {
+    const int n = NF - tile0;
+#pragma unroll
+    for (int i = 0; i < C; i += 2) {
+        if (i >= n) break;
+        const int j = i + 1 < C ? i + 1 : i;
+        if (j > i && j < n) {
+            const auto s0 = __builtin_amdgcn_permlane16_swap(pk[i][0], pk[j][0], false, false);
+            const auto s1 = __builtin_amdgcn_permlane16_swap(pk[i][1], pk[j][1], false, false);
+            t16_store(d, ft_off<bf16_t>((tile0 + i + (lq & 1)) * 16 + lr, t0 + 4 * (lq & 2), ldT), u32x4{s0[0], s1[0], s0[1], s1[1]});
+        } else {
+            const auto s0 = __builtin_amdgcn_permlane16_swap(pk[i][0], pk[i][0], false, false);
+            const auto s1 = __builtin_amdgcn_permlane16_swap(pk[i][1], pk[i][1], false, false);
+            if (!(lq & 1)) t16_store(d, ft_off<bf16_t>((tile0 + i) * 16 + lr, t0 + 4 * lq, ldT), u32x4{pk[i][0], pk[i][1], s0[1], s1[1]});
+        }
+    }
+}
 // Workgroup barrier that orders LDS traffic only.  `__syncthreads()` also drains every global
 // load and store in flight (s_waitcnt vmcnt(0)), which would serialise the strip kernel's
 // weight prefetch and its activation stores behind each phase barrier; the waves of a strip
@@ -959,7 +1003,8 @@ template <typename T> struct MlpArgs {
     float *gxp, *p_out, *loss_t; int* err;
     // embedding-bag input layer (SNN fine-tune, python/SNN_RBM.py:238-291); unused in FM mode
     const float* bb0; int rw; T* dlxT; float* gx_raw;
-    int wt;                         // bits: 1 the transposed activations by write-through stores (store4_wt), 2 gx' too, 4 gx' regrouped into whole lines
+    int wt;                         // bits: 1 the transposed activations by write-through stores (store4_wt), 2 gx' too, 4 gx' regrouped into whole lines,
+                                    // 32 (bf16, FM mode) the transposed activations in 16-byte stores (t16_store_run)
                                     // (bit 8 of FNN_WT_STORES: the reference-shaped outputs of fnn_gather, k_gather_ref / k_bag_ref)
 #ifdef FNN_STAMPS
     long long* dbg;                 // diagnostic build only: per-workgroup phase time stamps
@@ -1055,6 +1100,11 @@ __device__ __forceinline__ void mlp_body(const MlpArgs<T>& a, const int blk, uns
     const int t0 = blk * 16;
     const int F = a.F, K = a.K, B = a.B, ldT = a.ldT;
     const bool wt = (a.wt & 1) != 0, wtg = (a.wt & 2) != 0;
+    // (FM mode only.  Bag mode keeps the 8-byte stores: the SNN step was level with them and 0.3 us slower with the code in place,
+    // and the instance for bag rows 256 .. 316 wide, which sits at 256 VGPRs, spilled the packed tiles)
+    constexpr bool B16 = std::is_same<T, bf16_t>::value && !BAG;
+    bool st16 = false;                                        // bf16, training: the transposed activations leave 16 bytes per lane
+    if constexpr (B16) st16 = (a.wt & 32) != 0 && a.train;
 #define ST4(p, x0, x1, x2, x3) do { if (wt) store4_wt(p, x0, x1, x2, x3); else store4(p, x0, x1, x2, x3); } while (0)
     FNN_STAMP_RT(14);
     FNN_STAMP(0);
@@ -1153,8 +1203,16 @@ __device__ __forceinline__ void mlp_body(const MlpArgs<T>& a, const int blk, uns
     } else {
     // ---- P0: gather 16 examples x F rows (64 B each) into the x' tile and x'^T (:87-96).
     // All ids first, then all rows: two dependent round trips for the whole strip.
-    for (int e = tid; e < 16 * F; e += NT) {
-        const int q = e & 3, f = (e >> 2) % F, tq = (e >> 2) / F;
+    // st16: a piece (f, q, 8 examples) sits on two lanes 16 apart, each with 4 of its examples, so that one swap per dword gives
+    // every lane a whole 16-byte slot of x'^T (pieces in groups of 16: lanes l and l + 16 are both live or both idle)
+    const int ne = st16 ? ((8 * F + 15) >> 4) * 32 : 16 * F;
+    for (int e = tid; e < ne; e += NT) {
+        int q = e & 3, f = (e >> 2) % F, tq = (e >> 2) / F;
+        if (st16) {
+            const int pc = (e >> 5) * 16 + (e & 15);
+            if (pc >= 8 * F) continue;
+            q = pc & 3; f = (pc >> 2) % F; tq = 2 * ((pc >> 2) / F) + ((e >> 4) & 1);
+        }
         int64_t id[4];
 #pragma unroll
         for (int i = 0; i < 4; ++i) {
@@ -1186,7 +1244,19 @@ __device__ __forceinline__ void mlp_body(const MlpArgs<T>& a, const int blk, uns
         const int c0 = f * SLOT + 4 * q;
 #pragma unroll
         for (int i = 0; i < 4; ++i) store4(sx + (4 * tq + i) * LX + c0, v[i][0], v[i][1], v[i][2], v[i][3]);
-        if (a.train) {
+        if constexpr (B16) {
+            if (st16) {
+                const T16Dst dx = t16_dst(a.xpT, K1p, ldT, wt);
+#pragma unroll
+                for (int j = 0; j < 4; j += 2) {
+                    const u32x2 x = pack4_bf16(v[0][j], v[1][j], v[2][j], v[3][j]), y = pack4_bf16(v[0][j + 1], v[1][j + 1], v[2][j + 1], v[3][j + 1]);
+                    const auto s0 = __builtin_amdgcn_permlane16_swap(x[0], y[0], false, false);
+                    const auto s1 = __builtin_amdgcn_permlane16_swap(x[1], y[1], false, false);
+                    t16_store(dx, ft_off<T>(c0 + j + (tq & 1), t0 + 8 * (tq >> 1), ldT), u32x4{s0[0], s1[0], s0[1], s1[1]});
+                }
+            }
+        }
+        if (a.train && !st16) {
 #pragma unroll
             for (int j = 0; j < 4; ++j)
                 ST4(a.xpT + ft_off<T>(c0 + j, t0 + 4 * tq, ldT), v[0][j], v[1][j], v[2][j], v[3][j]);
@@ -1239,7 +1309,15 @@ __device__ __forceinline__ void mlp_body(const MlpArgs<T>& a, const int blk, uns
                 if (ok) sd1[(4 * lq + r) * L1 + col] = (T)v;
             }
         }
-        if (a.train) {
+        if constexpr (B16) {
+            if (st16) {
+                u32x2 pk[C1];
+#pragma unroll
+                for (int i = 0; i < C1; ++i) pk[i] = pack4_bf16(d1v[i][0], d1v[i][1], d1v[i][2], d1v[i][3]);
+                t16_store_run<C1>(t16_dst(a.d1T, H1p, ldT, wt), pk, wave * C1, NF1, t0, ldT, lr, lq);
+            }
+        }
+        if (a.train && !st16) {
 #pragma unroll
             for (int i = 0; i < C1; ++i)
                 if (wave * C1 + i < NF1) ST4(a.d1T + ft_off<T>((wave * C1 + i) * 16 + lr, t0 + 4 * lq, ldT), d1v[i][0], d1v[i][1], d1v[i][2], d1v[i][3]);
@@ -1287,7 +1365,15 @@ __device__ __forceinline__ void mlp_body(const MlpArgs<T>& a, const int blk, uns
                 zp[r] = fmaf(v, w3, zp[r]);
             }
         }
-        if (a.train) {
+        if constexpr (B16) {
+            if (st16) {
+                u32x2 pk[C2];
+#pragma unroll
+                for (int i = 0; i < C2; ++i) pk[i] = pack4_bf16(d2v[i][0], d2v[i][1], d2v[i][2], d2v[i][3]);
+                t16_store_run<C2>(t16_dst(a.d2T, H2p, ldT, wt), pk, wave * C2, NF2, t0, ldT, lr, lq);
+            }
+        }
+        if (a.train && !st16) {
 #pragma unroll
             for (int i = 0; i < C2; ++i)
                 if (wave * C2 + i < NF2) ST4(a.d2T + ft_off<T>((wave * C2 + i) * 16 + lr, t0 + 4 * lq, ldT), d2v[i][0], d2v[i][1], d2v[i][2], d2v[i][3]);
@@ -1325,6 +1411,7 @@ __device__ __forceinline__ void mlp_body(const MlpArgs<T>& a, const int blk, uns
         store4(a.loss_t + t0 + 4 * lq, ls[0], ls[1], ls[2], ls[3]);
     }
     // delta2 = delta3 * w3 * r2 * (1 - d2^2)   (layer 2 is tanh on the dropout path, :165)
+    u32x2 pk2[B16 ? C2 : 1];                                  // st16: the run's packed tiles, stored behind the loop
 #pragma unroll
     for (int i = 0; i < C2; ++i) {
         const int col = (wave * C2 + i) * 16 + lr;
@@ -1336,8 +1423,10 @@ __device__ __forceinline__ void mlp_body(const MlpArgs<T>& a, const int blk, uns
             v[r] = d3[r] * w3m * (1.0f - d2v[i][r] * d2v[i][r]);
             sdl2[(4 * lq + r) * L2 + col] = (T)v[r];
         }
-        ST4(a.dl2T + ft_off<T>(col, t0 + 4 * lq, ldT), v[0], v[1], v[2], v[3]);
+        if constexpr (B16) pk2[i] = pack4_bf16(v[0], v[1], v[2], v[3]);
+        if (!st16) ST4(a.dl2T + ft_off<T>(col, t0 + 4 * lq, ldT), v[0], v[1], v[2], v[3]);
     }
+    if constexpr (B16) { if (st16) t16_store_run<C2>(t16_dst(a.dl2T, H2p, ldT, wt), pk2, wave * C2, NF2, t0, ldT, lr, lq); }
     lds_barrier();
     FNN_STAMP(6);
 
@@ -1367,6 +1456,7 @@ __device__ __forceinline__ void mlp_body(const MlpArgs<T>& a, const int blk, uns
         } else wring_product<T, NKH2, C1, DR3>(acc, r3, ap, a.w2, wave * C1, lane, NF1 - 1);
         FNN_STAMP(7);
         const ActCoef ac1 = act_coef(a.act1);
+        u32x2 pk1[B16 ? C1 : 1];
 #pragma unroll
         for (int i = 0; i < C1; ++i) {
             const int col = (wave * C1 + i) * 16 + lr;
@@ -1378,8 +1468,10 @@ __device__ __forceinline__ void mlp_body(const MlpArgs<T>& a, const int blk, uns
                 v[r] = acc[i][r] * m * dact_apply(ac1, d1v[i][r]) * rv[r];
                 sdl1[(4 * lq + r) * L1 + col] = (T)v[r];
             }
-            ST4(a.dl1T + ft_off<T>(col, t0 + 4 * lq, ldT), v[0], v[1], v[2], v[3]);
+            if constexpr (B16) pk1[i] = pack4_bf16(v[0], v[1], v[2], v[3]);
+            if (!st16) ST4(a.dl1T + ft_off<T>(col, t0 + 4 * lq, ldT), v[0], v[1], v[2], v[3]);
         }
+        if constexpr (B16) { if (st16) t16_store_run<C1>(t16_dst(a.dl1T, H1p, ldT, wt), pk1, wave * C1, NF1, t0, ldT, lr, lq); }
     }
     lds_barrier();
     FNN_STAMP(8);

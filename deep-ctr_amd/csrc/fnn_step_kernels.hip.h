@@ -17,9 +17,10 @@ namespace fnn {
 
 // ------------------------------------------------------------------------------------------
 // Grouping role: a field's 4096 (row, t) keys sorted in two independent phases -- 16 runs of 256
-// keys, each bitonic-sorted inside ONE wave's registers (phase A), then a merge by rank in which
-// every key finds its final place and its segment [s, e) with binary searches over the runs
-// (phase B).  32-bit keys (row << 12 | t) when n_rows * 4096 fits, else 64-bit.  Measured against
+// keys, each bitonic-sorted inside ONE wave's registers, and (SortArgs::merge4) a workgroup's four runs
+// merged into one of 1024 (phase A), then a merge by rank in which every key finds its final place
+// and its segment [s, e) with binary searches over the 16 or 4 runs (phase B).  32-bit keys
+// (row << 12 | t) when n_rows * 4096 fits, else 64-bit.  Measured against
 // the single-kernel bitonic network it replaced: 34 us -> 2 x ~4 us of role time.
 // ------------------------------------------------------------------------------------------
 template <typename KT> struct KeyTraits;
@@ -35,11 +36,24 @@ struct SortArgs {
     // under another column marks tag_shared[row] = stamp, and the update launches (at least one kernel boundary later) add
     // into such rows with float atomics instead (scatw1_body / scatw2_body).  Stamps grow with every grouping: no reset pass.
     int* tag_first; int* tag_shared; int stamp;
+    int merge4;      // 1: phase A leaves 4 runs of 1024 keys per field and phase B merges those (FNN_SORT_RUNS=4, the default); 0: 16 runs of 256
 };
 
 constexpr int SORT_N = 4096;     // keys per field handled by the union-kernel path (B <= 4096)
 
 template <typename KT> __host__ __device__ constexpr size_t sort_lds_bytes() { return (size_t)SORT_N * sizeof(KT); }
+// dynamic LDS of phase A (sortA_body): a workgroup's four wave runs, merged in place into one run of 1024 keys; none for the 16-run form
+template <typename KT> inline size_t sortA_lds_bytes(const int merge4) { return merge4 ? (size_t)1024 * sizeof(KT) : 0; }
+// FNN_SORT_RUNS=16|4, read where a handle is created: the runs per field that phase A leaves for the rank merge.  `dflt` (1: four
+// runs) is the handle's own choice: four where phase A rides beside longer roles (the FNN step on FM rows: 35.6 -> 33.6 us per
+// step) and in the inner-product step (level), sixteen where the longer phase A is a launch of its own in front of the merge
+// (FM pre-training: 29.3 -> 30.8 us with four) and in bag mode (the SNN step: 47.5 -> 48.1) -- profiles/step_stores16_sort4_ab.json
+inline int sort_merge4_env(const int dflt)
+{
+    const char* e = getenv("FNN_SORT_RUNS");
+    const int v = e ? atoi(e) : 0;
+    return v == 16 ? 0 : (v == 4 ? 1 : dflt);
+}
 
 // Invalid entries (t >= B, id outside the table) carry the all-ones row, so that every key of a
 // field is distinct (the rank merges below need a strict total order) and they sort to the end.
@@ -57,8 +71,12 @@ __device__ __forceinline__ int lower_bound_pow2(const KT* q, const KT v) {
 // Phase A of the split sort: every wave bitonic-sorts a run of 256 keys in registers (4 per lane:
 // strides below 4 inside the lane, the rest wave shuffles -- no LDS, no barriers) and stores it.
 // One workgroup = 4 runs = a quarter of a field; so.nblk = 4 F.
-template <typename KT>
-__device__ __forceinline__ void sortA_body(const SortArgs& so, const int blk, unsigned char*)
+// so.merge4: the workgroup then merges its four wave runs by rank into ONE run of 1024 keys (LDS, one barrier: a key's place is
+// its index in its own run plus the keys below it in the three others, 27 reads each) -- the rank merge of phase B, the longest
+// role of its launch, then searches 4 runs of 1024 instead of 16 of 256: 11 searches per key instead of 48.
+// M4 = so.merge4 as a template parameter: the union launches are instantiated per form (see sortB_form).
+template <typename KT, bool M4>
+__device__ __forceinline__ void sortA_form(const SortArgs& so, const int blk, unsigned char* smem)
 {
     constexpr int SH = KeyTraits<KT>::SH;
     const int tid = threadIdx.x, wave = tid >> 6, lane = tid & 63, F = so.F, B = so.B;
@@ -102,9 +120,45 @@ __device__ __forceinline__ void sortA_body(const SortArgs& so, const int blk, un
             }
         }
     }
+    if constexpr (M4) {
+        KT* s_run = reinterpret_cast<KT*>(smem);              // [4][256] the workgroup's wave runs
+#pragma unroll
+        for (int a = 0; a < 4; ++a) s_run[wave * 256 + i0 + a] = key[a];
+        __syncthreads();
+        int place[4];
+#pragma unroll
+        for (int a = 0; a < 4; ++a) place[a] = i0 + a;
+        // 12 searches (3 other runs x 4 keys) in lockstep: every step issues 12 independent LDS reads.  Keys are distinct, so
+        // "keys below" is the same strict order from both sides of a pair of runs.
+        int bq[3][4];
+#pragma unroll
+        for (int o = 0; o < 3; ++o)
+#pragma unroll
+            for (int a = 0; a < 4; ++a) bq[o][a] = ((wave + 1 + o) & 3) * 256;
+#pragma unroll
+        for (int st = 128; st >= 1; st >>= 1)
+#pragma unroll
+            for (int o = 0; o < 3; ++o)
+#pragma unroll
+                for (int a = 0; a < 4; ++a) bq[o][a] += s_run[bq[o][a] + st - 1] < key[a] ? st : 0;
+#pragma unroll
+        for (int o = 0; o < 3; ++o)
+#pragma unroll
+            for (int a = 0; a < 4; ++a)
+                place[a] += bq[o][a] - ((wave + 1 + o) & 3) * 256 + (s_run[bq[o][a]] < key[a] ? 1 : 0);
+        KT* out = static_cast<KT*>(so.skeys) + (size_t)f * SORT_N + (blk & 3) * 1024;
+#pragma unroll
+        for (int a = 0; a < 4; ++a) out[place[a]] = key[a];
+        return;
+    }
     KT* out = static_cast<KT*>(so.skeys) + (size_t)f * SORT_N + base + i0;
 #pragma unroll
     for (int a = 0; a < 4; ++a) out[a] = key[a];
+}
+template <typename KT>
+__device__ __forceinline__ void sortA_body(const SortArgs& so, const int blk, unsigned char* smem)
+{
+    if (so.merge4) sortA_form<KT, true>(so, blk, smem); else sortA_form<KT, false>(so, blk, smem);
 }
 
 // Phase B of the split sort: merge by RANK.  A key's place in the field's final order is its index
@@ -112,8 +166,11 @@ __device__ __forceinline__ void sortA_body(const SortArgs& so, const int blk, un
 // search in LDS); its segment [s, e) comes the same way: s = keys below (row, 0), e = keys below
 // (row + 1, 0).  Every key is independent -- one thread per key, 16 workgroups per field
 // (so.nblk = 16 F), one barrier -- instead of a 15 us chain of dependent merge stages.
-template <typename KT>
-__device__ __forceinline__ void sortB_body(const SortArgs& so, const int blk, unsigned char* smem)
+// M4: the runs are 4 of 1024 keys (so.merge4); a template parameter, because launch 3 carrying both forms behind a run-time
+// branch took 107 VGPRs against the 16-run form's 94 (gfx950, hipcc 7.2) -- the union launches are instantiated per form, so
+// that a handle on sixteen runs launches the code it launched before there were two.
+template <typename KT, bool M4>
+__device__ __forceinline__ void sortB_form(const SortArgs& so, const int blk, unsigned char* smem)
 {
     constexpr int SH = KeyTraits<KT>::SH;
     KT* s_key = reinterpret_cast<KT*>(smem);                 // [4096] the 16 sorted runs
@@ -125,26 +182,55 @@ __device__ __forceinline__ void sortB_body(const SortArgs& so, const int blk, un
     __syncthreads();
     const KT key = s_key[run * 256 + tid];
     const KT row = key >> SH, lo_key = row << SH, hi_key = (row + 1) << SH;    // row + 1 wraps only for invalid entries
-    // 48 binary searches (16 runs x {key, lo_key, hi_key}) advance in lockstep, so that every step
-    // issues 48 independent LDS reads instead of one dependent read at a time.  The search of the
-    // key in its own run returns its own index, so no run is special.
-    int bp[16], bs[16], be[16];
+    int pos = 0, s = 0, e = 0;
+    if constexpr (M4) {
+        // 4 runs of 1024 keys: the key's index in its own run plus its rank in the 3 others, and the ranks of lo_key / hi_key in
+        // all 4 -- 11 searches of 10 steps in lockstep (about 120 LDS reads against the 16-run form's 480)
+        const int own = run >> 2;
+        int bp[3], bs[4], be[4];
 #pragma unroll
-    for (int r = 0; r < 16; ++r) bp[r] = bs[r] = be[r] = r * 256;
+        for (int o = 0; o < 3; ++o) bp[o] = ((own + 1 + o) & 3) * 1024;
 #pragma unroll
-    for (int st = 128; st >= 1; st >>= 1) {
+        for (int r = 0; r < 4; ++r) bs[r] = be[r] = r * 1024;
+#pragma unroll
+        for (int st = 512; st >= 1; st >>= 1) {
+#pragma unroll
+            for (int o = 0; o < 3; ++o) bp[o] += s_key[bp[o] + st - 1] < key ? st : 0;
+#pragma unroll
+            for (int r = 0; r < 4; ++r) {
+                const KT vs = s_key[bs[r] + st - 1], ve = s_key[be[r] + st - 1];
+                bs[r] += vs < lo_key ? st : 0; be[r] += ve < hi_key ? st : 0;
+            }
+        }
+        pos = (run & 3) * 256 + tid;
+#pragma unroll
+        for (int o = 0; o < 3; ++o) pos += bp[o] - ((own + 1 + o) & 3) * 1024 + (s_key[bp[o]] < key ? 1 : 0);
+#pragma unroll
+        for (int r = 0; r < 4; ++r) {
+            s += bs[r] - r * 1024 + (s_key[bs[r]] < lo_key ? 1 : 0);
+            e += be[r] - r * 1024 + (s_key[be[r]] < hi_key ? 1 : 0);
+        }
+    } else {
+        // 48 binary searches (16 runs x {key, lo_key, hi_key}) advance in lockstep, so that every step
+        // issues 48 independent LDS reads instead of one dependent read at a time.  The search of the
+        // key in its own run returns its own index, so no run is special.
+        int bp[16], bs[16], be[16];
+#pragma unroll
+        for (int r = 0; r < 16; ++r) bp[r] = bs[r] = be[r] = r * 256;
+#pragma unroll
+        for (int st = 128; st >= 1; st >>= 1) {
+#pragma unroll
+            for (int r = 0; r < 16; ++r) {
+                const KT vp = s_key[bp[r] + st - 1], vs = s_key[bs[r] + st - 1], ve = s_key[be[r] + st - 1];
+                bp[r] += vp < key ? st : 0; bs[r] += vs < lo_key ? st : 0; be[r] += ve < hi_key ? st : 0;
+            }
+        }
 #pragma unroll
         for (int r = 0; r < 16; ++r) {
-            const KT vp = s_key[bp[r] + st - 1], vs = s_key[bs[r] + st - 1], ve = s_key[be[r] + st - 1];
-            bp[r] += vp < key ? st : 0; bs[r] += vs < lo_key ? st : 0; be[r] += ve < hi_key ? st : 0;
+            pos += bp[r] - r * 256 + (s_key[bp[r]] < key ? 1 : 0);
+            s += bs[r] - r * 256 + (s_key[bs[r]] < lo_key ? 1 : 0);
+            e += be[r] - r * 256 + (s_key[be[r]] < hi_key ? 1 : 0);
         }
-    }
-    int pos = 0, s = 0, e = 0;
-#pragma unroll
-    for (int r = 0; r < 16; ++r) {
-        pos += bp[r] - r * 256 + (s_key[bp[r]] < key ? 1 : 0);
-        s += bs[r] - r * 256 + (s_key[bs[r]] < lo_key ? 1 : 0);
-        e += be[r] - r * 256 + (s_key[be[r]] < hi_key ? 1 : 0);
     }
     int4 rr = make_int4(-1, 0, 0, 0);
     if (row != inv_row<KT>()) {
@@ -156,6 +242,11 @@ __device__ __forceinline__ void sortB_body(const SortArgs& so, const int blk, un
         }
     }
     so.rec[(size_t)f * SORT_N + pos] = rr;
+}
+template <typename KT>
+__device__ __forceinline__ void sortB_body(const SortArgs& so, const int blk, unsigned char* smem)
+{
+    if (so.merge4) sortB_form<KT, true>(so, blk, smem); else sortB_form<KT, false>(so, blk, smem);
 }
 
 // The split sort as two plain launches, for a batch nobody announced (fnn_prefetch_ids) and for
@@ -188,13 +279,13 @@ static __global__ __launch_bounds__(64 * NW) void k_step1(const MlpArgs<T> a)
 // ------------------------------------------------------------------------------------------
 // step 2: run-sorts of the NEXT batch's keys  U  weight gradients  U  sparse-row SGD level 1
 // ------------------------------------------------------------------------------------------
-template <typename T, typename KT>
+template <typename T, typename KT, bool M4>
 static __global__ __launch_bounds__(256) void k_step2(const SortArgs so, const WgradArgs wa, const int nwx,
                                                const int splitk, const ScatArgs sa)
 {
     extern __shared__ __align__(16) unsigned char smem[];
     const int b = blockIdx.x, nw = nwx * splitk;
-    if (b < so.nblk) sortA_body<KT>(so, b, smem);                              // so.nblk = 4 * F or 0
+    if (b < so.nblk) sortA_form<KT, M4>(so, b, smem);                          // so.nblk = 4 * F or 0
     else if (b < so.nblk + nw) {
         // XCD-aware order: hardware block ids that differ by a multiple of 8 share an XCD (and its L2); deal the role's blocks so
         // that each of the 8 classes owns a contiguous run of (tile, K slice) pairs -- one or two K slices of the operands per XCD
@@ -225,12 +316,12 @@ struct TailArgs {
     float* bb0; size_t nbag, off_bag;      // bag mode: bias vector, its length (K1p) and slab offset
 };
 
-template <typename T, bool UPDATE, typename KT>
+template <typename T, bool UPDATE, typename KT, bool M4>
 static __global__ __launch_bounds__(256) void k_step3(const SortArgs so, const TailArgs ta, const ScatArgs sa)
 {
     extern __shared__ __align__(16) unsigned char smem[];
     __shared__ double s_sum[16][16];
-    if ((int)blockIdx.x < so.nblk) { sortB_body<KT>(so, blockIdx.x, smem); return; }          // rank merge: 16 F or 0 WGs
+    if ((int)blockIdx.x < so.nblk) { sortB_form<KT, M4>(so, blockIdx.x, smem); return; }      // rank merge: 16 F or 0 WGs
     const int b = (int)blockIdx.x - so.nblk;
     if (b >= ta.nblk_red) {
         const int nb = (int)gridDim.x - so.nblk - ta.nblk_red;

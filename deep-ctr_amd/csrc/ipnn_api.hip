@@ -1500,6 +1500,7 @@ struct ipnn_handle {
     int strip_rot = 1, fwd_skip = 0;                 // IPNN_STRIP_ROT (0: every workgroup walks the blocks in the same order), IPNN_FWD_SKIP (diagnostics)
     int wide_nf = 2, wide_nw = 8;                    // IPNN_WIDE=nf:nw -- items (16-column fragments) and waves of the wide (pair) launches: 2:8 (default), 4:8, 2:12
     int scat_slot = 0;                               // FNN_SCAT1_FORM=slot (scat1_blocks)
+    int sort_merge4 = 1;                             // FNN_SORT_RUNS=4|16 (sortA_body; default 4)
     bool wt = true;                                  // IPNN_WT=0: plain stores where the launches write through by default
     int tail_fuse = 1;                               // IPNN_TAIL_FUSE: training steps run the forward and the backward tail in one launch
     int tail_nf = 1;                                 // IPNN_TAIL_NF: 16-column fragments per item in the 16-example strips of the narrow tail (1 / 2 / 4)
@@ -1646,11 +1647,12 @@ int ip_run(ipnn_handle* h, const int32_t* ids, const float* wts, const float* y,
             if (h->st2 && h->mask_side) IHK(h, hipEventRecord(h->ev_mask, h->st2));
         }
         SortArgs so{ids, B, F, h->n_rows, h->rec, h->owner_cnt, F, h->skeys};
+        so.merge4 = h->sort_merge4;
         if (h->key64) {
-            hipLaunchKernelGGL((k_sortA<unsigned long long>), dim3(4 * F), dim3(256), 0, ss, so);
+            hipLaunchKernelGGL((k_sortA<unsigned long long>), dim3(4 * F), dim3(256), sortA_lds_bytes<unsigned long long>(so.merge4), ss, so);
             hipLaunchKernelGGL((k_sortB<unsigned long long>), dim3(16 * F), dim3(256), SORT_N * 8, ss, so);
         } else {
-            hipLaunchKernelGGL((k_sortA<unsigned>), dim3(4 * F), dim3(256), 0, ss, so);
+            hipLaunchKernelGGL((k_sortA<unsigned>), dim3(4 * F), dim3(256), sortA_lds_bytes<unsigned>(so.merge4), ss, so);
             hipLaunchKernelGGL((k_sortB<unsigned>), dim3(16 * F), dim3(256), SORT_N * 4, ss, so);
         }
     }
@@ -2045,6 +2047,7 @@ int ipnn_create(const ipnn_cfg* cfg, ipnn_handle** out)
     if (const char* e = getenv("IPNN_TAIL_FUSE")) h->tail_fuse = atoi(e) != 0;
     if (const char* e = getenv("IPNN_WT")) h->wt = atoi(e) != 0;
     h->scat_slot = scat1_form_env();
+    h->sort_merge4 = sort_merge4_env(1);
     if (const char* e = getenv("IPNN_WIDE")) { int nf = 4, nw = 8; if (sscanf(e, "%d:%d", &nf, &nw) == 2 && ((nf == 2 && (nw == 8 || nw == 12)) || (nf == 4 && nw == 8))) { h->wide_nf = nf; h->wide_nw = nw; } }
     if (const char* e = getenv("IPNN_TAIL_NW")) h->tail_nw = atoi(e) == 16 ? 16 : 8;
     if (const char* e = getenv("IPNN_TAIL_NF")) { const int v = atoi(e); if (v == 1 || v == 2 || v == 4) h->tail_nf = v; }
