@@ -141,7 +141,7 @@ __global__ __launch_bounds__(1024) void k_dae_dense_g(const DenseGArgs<S> a)
     S* s_part = reinterpret_cast<S*>(dae_smem);                  // [G][CP] <= 1024
     S* s_y = s_part + 1024; S* s_dy = s_y + CP;                  // [CP] each
     S* s_x = s_dy + CP; S* s_xn = s_x + row; S* s_d = s_xn + row; S* s_bv = s_d + row;    // [row] each
-    double* s_cost = reinterpret_cast<double*>(s_bv + row + (row & 1));     // [16]
+    double* s_cost = reinterpret_cast<double*>(s_bv + row);                // [16]; 1024 + 2 CP + 4 row elements precede it: 8-byte aligned for float too
     S bh = (tid < col) ? a.bhid[tid] : (S)0;
     for (int i = tid; i < row; i += 1024) { s_x[i] = a.X[i]; s_bv[i] = a.bvis[i]; }
     double cost = 0.0;

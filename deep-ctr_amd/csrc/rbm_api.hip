@@ -1012,7 +1012,8 @@ int rbm_dense_cd1(rbm_handle* h, const float* X, int n, const float* unif, float
 int rbm_bag_sum(const float* W0, const float* b0, int H, int64_t n_rows, const int32_t* ids, int n, int F,
                 float* out, void* stream)
 {
-    if (!W0 || !b0 || !ids || !out || n < 1) RFAIL(FNN_ERR_ARG, "bad argument");
+    if (!W0 || !b0 || !ids || !out) RFAIL(FNN_ERR_ARG, "null pointer");
+    if (H < 1 || n < 1 || F < 1 || n_rows < 0) RFAIL(FNN_ERR_ARG, "need H >= 1, n >= 1, F >= 1, n_rows >= 0");
     const size_t nt = (size_t)n * H;
     hipLaunchKernelGGL(k_bag_sum, dim3((unsigned)((nt + 255) / 256)), dim3(256), 0, (hipStream_t)stream, W0, b0, H, n_rows,
                        ids, n, F, out);
@@ -1022,7 +1023,8 @@ int rbm_bag_sum(const float* W0, const float* b0, int H, int64_t n_rows, const i
 
 int rbm_affine(const float* in, const float* W, const float* bias, int n, int a, int b, float* out, void* stream)
 {
-    if (!in || !W || !bias || !out || n < 1) RFAIL(FNN_ERR_ARG, "bad argument");
+    if (!in || !W || !bias || !out) RFAIL(FNN_ERR_ARG, "null pointer");
+    if (n < 1 || a < 1 || b < 1) RFAIL(FNN_ERR_ARG, "need n >= 1, a >= 1, b >= 1");
     const size_t nt = (size_t)n * b;
     hipLaunchKernelGGL(k_affine, dim3((unsigned)((nt + 255) / 256)), dim3(256), 0, (hipStream_t)stream, in, W, bias, n, a,
                        b, out);
@@ -1032,7 +1034,8 @@ int rbm_affine(const float* in, const float* W, const float* bias, int n, int a,
 
 int rbm_sigmoid(float* x, int64_t count, void* stream)
 {
-    if (!x || count < 1) RFAIL(FNN_ERR_ARG, "bad argument");
+    if (!x) RFAIL(FNN_ERR_ARG, "null pointer");
+    if (count < 1) RFAIL(FNN_ERR_ARG, "need count >= 1");
     hipLaunchKernelGGL(k_sigmoid, dim3((unsigned)((count + 255) / 256)), dim3(256), 0, (hipStream_t)stream, x, count);
     RCK(hipGetLastError());
     return FNN_OK;

@@ -87,7 +87,9 @@ int rbm_dense_cd1(rbm_handle* h, const float* X, int n, const float* unif, float
 
 /* Lower-layer propagation (:198-218).  out [n, H] = sum of the rows W0[id] of the ACTIVE ids of
  * each example (ids [n, F] int32, -1 = none) + b0;  out [n, b] = in [n, a] . W [a, b] + bias [b]
- * (no nonlinearity between stacked layers);  x = 1 / (1 + exp(-x)) in place. */
+ * (no nonlinearity between stacked layers);  x = 1 / (1 + exp(-x)) in place.
+ * rbm_bag_sum SKIPS an id >= n_rows like a -1 (there is no FNN_ERR_RANGE here, unlike dae_bag_cumsum_sigmoid); any H >= 1,
+ * F >= 1.  Empty shapes (n, H, F, a, b or count < 1) are FNN_ERR_ARG. */
 int rbm_bag_sum(const float* W0, const float* b0, int H, int64_t n_rows, const int32_t* ids, int n, int F,
                 float* out, void* stream);
 int rbm_affine(const float* in, const float* W, const float* bias, int n, int a, int b, float* out,
