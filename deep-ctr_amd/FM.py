@@ -4,6 +4,10 @@
 `forward` = test_preds).  `write_fm_model` closes the loop the reference leaves open: it writes the
 `fm.model.txt` text format that python/FNN_wnzh.py:62-84 parses, so that FM -> FNN runs end to end.
 Optimisers: plain SGD, Adam and FTRL as python/tf_util.py:15-29 builds them (`parse_ptmzr`).
+Value weights (the class's `sp_wt_hldr`, python/FM.py:24-29): `wts=` of train_step / forward / evaluate, one f32 value per
+(example, field) beside its id; `model.train_step(_cols, _labels, wts=_vals)` is python/baseline.py:345's feed, and the
+`(ids, wts)` pair that `ipnn.criteo_feed` makes for the inner-product family feeds FM / LR unchanged.  Without `wts` every
+value is 1 (iPinYou).
 Random init uses NumPy RandomState(seed) streams (TensorFlow's cannot be reproduced here)."""
 import ctypes as C
 import pickle
@@ -92,40 +96,58 @@ class FM(object):
             return a.to(device=self.device, dtype=dtype).contiguous()
         return torch.as_tensor(np.ascontiguousarray(a)).to(device=self.device, dtype=dtype).contiguous()
 
-    def train_step(self, ids, y, want_p=False, want_loss=True):
-        """ids [B, X_feas] int32 (-1 = absent), y [B].  Returns {'loss', 'p'} (python/ipinyou.py:171)."""
+    def _wts(self, wts, ids_t):
+        """wts [B, X_feas] f32 on the device, or None (every value 1); ValueError unless its shape is ids'."""
+        if wts is None:
+            return None
+        shape = tuple(wts.shape) if hasattr(wts, 'shape') else np.shape(wts)
+        if shape != tuple(ids_t.shape):
+            raise ValueError("wts has shape %s, ids %s: one weight per (example, field)" % (shape, tuple(ids_t.shape)))
+        return self._dev(wts, self._torch.float32)
+
+    def train_step(self, ids, y, want_p=False, want_loss=True, wts=None):
+        """ids [B, X_feas] int32 (-1 = absent), y [B], wts [B, X_feas] f32 or None (every value 1): e_f = wts[t, f] * row(ids[t, f])
+        (python/FM.py:55-64).  `model.train_step(_cols, _labels, wts=_vals)` is python/baseline.py:345's feed; the (ids, wts) pair
+        of ipnn.criteo_feed feeds this unchanged.  Returns {'loss', 'p'} (python/ipinyou.py:171)."""
         torch = self._torch
         ids_t, y_t = self._dev(ids, torch.int32), self._dev(y, torch.float32)
+        w_t = self._wts(wts, ids_t)
         B = ids_t.shape[0]
         p = torch.empty(B, dtype=torch.float32, device=self.device) if want_p else None
         loss = C.c_float()
         if B > 4096:                # one call = ONE optimiser step (python/ipinyou.py:171); splitting it would change the update
             raise FNNError(_capi.FNN_ERR_ARG, "FM.train_step: batch %d > 4096 (fm_create's largest step)" % B)
         self.stream.wait_stream(torch.cuda.current_stream(self.device))
-        self._ck(self.lib.fm_train_step(self.h, ids_t.data_ptr(), y_t.data_ptr(), B, self.lr, self.lam, self.reduce_mean,
-                                        p.data_ptr() if want_p else None, C.byref(loss) if want_loss else None))
+        self._ck(self.lib.fm_train_step_w(self.h, ids_t.data_ptr(), None if w_t is None else w_t.data_ptr(), y_t.data_ptr(), B,
+                                          self.lr, self.lam, self.reduce_mean, p.data_ptr() if want_p else None,
+                                          C.byref(loss) if want_loss else None))
         torch.cuda.current_stream(self.device).wait_stream(self.stream)
-        self._keep = (ids_t, y_t)
+        self._keep = (ids_t, y_t, w_t)
         return {'loss': float(loss.value) if want_loss else None, 'p': p}
 
-    def forward(self, ids):
+    def forward(self, ids, wts=None):
+        """sigmoid(yhat) [N] (`test_preds`), max_batch examples a call; wts as in train_step."""
         torch = self._torch
         ids_t = self._dev(ids, torch.int32)
+        w_t = self._wts(wts, ids_t)
         out = torch.empty(ids_t.shape[0], dtype=torch.float32, device=self.device)
         self.stream.wait_stream(torch.cuda.current_stream(self.device))
         for lo in range(0, ids_t.shape[0], self.max_batch):
             hi = min(ids_t.shape[0], lo + self.max_batch)
-            self._ck(self.lib.fm_predict(self.h, ids_t[lo:hi].data_ptr(), hi - lo, out[lo:hi].data_ptr()))
+            self._ck(self.lib.fm_predict_w(self.h, ids_t[lo:hi].data_ptr(), None if w_t is None else w_t[lo:hi].data_ptr(), hi - lo,
+                                           out[lo:hi].data_ptr()))
         self._ck(self.lib.fm_sync(self.h))
         return out
 
-    def evaluate(self, ids, y):
-        """Predictions and (auc, rmse, logloss) on the device (fm_eval): exact AUC, ties at 1/2."""
+    def evaluate(self, ids, y, wts=None):
+        """Predictions and (auc, rmse, logloss) on the device (fm_eval_w): exact AUC, ties at 1/2; wts as in train_step."""
         torch = self._torch
         ids_t, y_t = self._dev(ids, torch.int32), self._dev(y, torch.int32)
+        w_t = self._wts(wts, ids_t)
         auc, rmse, ll = C.c_double(), C.c_double(), C.c_double()
         self.stream.wait_stream(torch.cuda.current_stream(self.device))
-        self._ck(self.lib.fm_eval(self.h, ids_t.data_ptr(), y_t.data_ptr(), ids_t.shape[0], C.byref(auc), C.byref(rmse), C.byref(ll)))
+        self._ck(self.lib.fm_eval_w(self.h, ids_t.data_ptr(), None if w_t is None else w_t.data_ptr(), y_t.data_ptr(), ids_t.shape[0],
+                                    C.byref(auc), C.byref(rmse), C.byref(ll)))
         return auc.value, rmse.value, ll.value
 
     def get_opt_state(self):

@@ -2,7 +2,9 @@
 signature, `dump` keys (`W`, `b`) and graph outputs (`train_step` = ptmzr + loss + train_preds, `forward` =
 test_preds, `evaluate` = eval_preds + metrics).  It runs on the factorisation machine of include/fm_hip.h at
 rank 0 (rows [w]): yhat = b + sum_i w_i and the loss xent + lambda * (l2_loss(W) + l2_loss(b)) are exactly
-python/LR.py:38-44 and :57-59.  SGD, Adam and FTRL as python/tf_util.py:15-29 builds them."""
+python/LR.py:38-44 and :57-59.  SGD, Adam and FTRL as python/tf_util.py:15-29 builds them.  Value weights (the class's
+`sp_wt_hldr`, python/LR.py:23-27 and :53-55: yhat = b + sum_i x_i w_i) are FM's `wts=`: `model.train_step(_cols, _labels,
+wts=_vals)` is python/baseline.py:345's feed, and the (ids, wts) pair of ipnn.criteo_feed feeds it unchanged."""
 import pickle
 
 import numpy as np

@@ -159,6 +159,9 @@ FM_SIGNATURES = {
     "fm_set_optimizer": (_i, [_vp, _i, _f, _f, _f]),
     "fm_get_opt_state": (_i, [_vp, _vp, _vp, _vp, C.POINTER(_i64)]),
     "fm_eval": (_i, [_vp, _vp, _vp, _i64, C.POINTER(C.c_double), C.POINTER(C.c_double), C.POINTER(C.c_double)]),
+    "fm_train_step_w": (_i, [_vp, _vp, _vp, _vp, _i, _f, _f, _i, _vp, C.POINTER(_f)]),
+    "fm_predict_w": (_i, [_vp, _vp, _vp, _i, _vp]),
+    "fm_eval_w": (_i, [_vp, _vp, _vp, _vp, _i64, C.POINTER(C.c_double), C.POINTER(C.c_double), C.POINTER(C.c_double)]),
 }
 
 _i64p = C.POINTER(_i64)

@@ -36,31 +36,40 @@ struct FmArgs {
     bool wt;                   // gx' written through (see store4_wt in fnn_kernels.hip.h)
     int* stamp; int step;      // Adam / FTRL: stamp[row] = step for every row the batch touches (null: not kept)
     int rw;                    // wide rows (fm_wide_body): the row stride in floats, a multiple of 4; gx' is [t][F][rw]
+    const float* wts;          // value weights [B, F] beside ids (the WV = true kernels), or null: every value is 1
 };
 
 // store16_sel and the two wait states gfx950 needs before a VALU instruction may overwrite the data VGPRs of a store wider than 8
 // bytes: the compiler provides them after its own stores, not after store16_wt's inline assembly.  With several fields per lane the
-// next field's gradients are computed into the registers the previous store reads (NF = 1 stores last: store16_sel as it was).
+// next field's gradients are computed into the registers the previous store reads (NF = 1 stores last: store16_sel as it was;
+// every weighted kernel, WV = true, stores through this one).
 __device__ __forceinline__ void store16_sel_ws(const bool wt, float* p, const float4 v)
 {
     u32x4 w; __builtin_memcpy(&w, &v, 16);
     if (wt) asm volatile("global_store_dwordx4 %0, %1, off sc1\n\ts_nop 1" :: "v"(p), "v"(w) : "memory");
     else *reinterpret_cast<u32x4*>(p) = w;
 }
-template <int NF>
+// WV: value weights (python/FM.py:24-29's sp_wt_hldr).  x = wts[t][fld] is loaded beside the id, the row enters as e = x * row, and
+// lin, S and sq follow from e as they did from the row; d yhat / d w_f = x, d yhat / d v_f[l] = x (S_l - e_f[l]).  The weight of
+// an absent field or of a padding example is replaced by 0 (its row by zeros), so that no value there, NaN included, reaches e.
+template <int NF, bool WV>
 __device__ __forceinline__ void fm_body(const FmArgs& a, const int blk, float* s_gb)
 {
     const int tid = threadIdx.x, f = tid & 15, grp = tid >> 4;
     const int t = blk * 16 + grp;
     int64_t id[NF];
+    float x[NF];
 #pragma unroll
     for (int n = 0; n < NF; ++n) {                          // every id first: the row loads below do not wait behind a stamp
         const int fld = f + 16 * n;
         id[n] = -1;
+        x[n] = 0.f;
         if (t < a.B && fld < a.F) {
             id[n] = a.ids[(size_t)t * a.F + fld];
+            if (WV) x[n] = a.wts[(size_t)t * a.F + fld];    // in the id's round trip
             if (id[n] < -1 || id[n] >= a.n_rows) { atomicOr(a.err, 1); id[n] = -1; }
             if (a.stamp && id[n] >= 0) a.stamp[id[n]] = a.step;
+            if (WV && id[n] < 0) x[n] = 0.f;
         }
     }
     float r[NF][16];
@@ -71,6 +80,7 @@ __device__ __forceinline__ void fm_body(const FmArgs& a, const int blk, float* s
             float4 v = make_float4(0.f, 0.f, 0.f, 0.f);
             if (id[n] >= 0) v = *reinterpret_cast<const float4*>(a.table16 + (size_t)id[n] * SLOT + 4 * q);
             r[n][4 * q] = v.x * a.scale; r[n][4 * q + 1] = v.y * a.scale; r[n][4 * q + 2] = v.z * a.scale; r[n][4 * q + 3] = v.w * a.scale;
+            if (WV) { r[n][4 * q] *= x[n]; r[n][4 * q + 1] *= x[n]; r[n][4 * q + 2] *= x[n]; r[n][4 * q + 3] *= x[n]; }
         }
     }
     // yhat = b + sum_f w_f + 1/2 (sum_l S_l^2 - sum_f sum_l v_f[l]^2)                     (:56-63)
@@ -104,20 +114,21 @@ __device__ __forceinline__ void fm_body(const FmArgs& a, const int blk, float* s
         }
     } else if (a.train && f == 0) a.loss_t[t] = 0.f;
     if (!a.train) return;
-    // d yhat / d w_f = 1 ; d yhat / d v_f[l] = S_l - v_f[l]   (x = 1)
+    // d yhat / d w_f = x_f ; d yhat / d v_f[l] = x_f (S_l - e_f[l])   (WV = false: x = 1)
 #pragma unroll
     for (int n = 0; n < NF; ++n) {
         const int fld = f + 16 * n;
+        const float dx = WV ? delta * x[n] : delta;
         float g[16];
-        g[0] = (id[n] >= 0) ? delta : 0.f;
+        g[0] = (id[n] >= 0) ? dx : 0.f;
 #pragma unroll
-        for (int l = 1; l < 16; ++l) g[l] = (id[n] >= 0 && l < a.K) ? delta * (S[l] - r[n][l]) : 0.f;
+        for (int l = 1; l < 16; ++l) g[l] = (id[n] >= 0 && l < a.K) ? dx * (S[l] - r[n][l]) : 0.f;
         float* out = a.gxp + (size_t)t * a.K1p + fld * SLOT;    // K1p = rup(F, 16) * SLOT
         if (fld < a.F) {
 #pragma unroll
             for (int q = 0; q < 4; ++q) {                   // (written through: FM_WT=0 for plain stores)
                 const float4 g4 = make_float4(g[4 * q], g[4 * q + 1], g[4 * q + 2], g[4 * q + 3]);
-                if (NF == 1) store16_sel(a.wt, out + 4 * q, g4);
+                if (NF == 1 && !WV) store16_sel(a.wt, out + 4 * q, g4);
                 else store16_sel_ws(a.wt, out + 4 * q, g4);
             }
         }
@@ -126,11 +137,11 @@ __device__ __forceinline__ void fm_body(const FmArgs& a, const int blk, float* s
     __syncthreads();
     if (tid == 0) { float s = 0.f; for (int i = 0; i < 16; ++i) s += s_gb[i]; a.gb_part[blk] = s; }
 }
-template <int NF>
+template <int NF, bool WV>
 __global__ __launch_bounds__(256) void k_fm(const FmArgs a)
 {
     __shared__ float s_gb[16];
-    fm_body<NF>(a, blockIdx.x, s_gb);
+    fm_body<NF, WV>(a, blockIdx.x, s_gb);
 }
 // Wide rows (k >= 17): L lanes per example (16 while the row's rw / 4 float4 pieces fit, else 32); lane q owns columns 4q..4q+3
 // of every field's row and issues its example's row loads 16 fields at a time, so that S_l = sum_f v_f[l] is a register sum and
@@ -139,35 +150,43 @@ __global__ __launch_bounds__(256) void k_fm(const FmArgs a)
 // written (no record points at them).  More than 16 fields (NC = ceil(F / 16) chunks of 16): a rolled first pass sums every
 // chunk, the second reloads each chunk's rows and writes its gradients (holding the last chunk across the passes cost 30-40
 // VGPRs and an occupancy step).  NC = 1, up to 16 fields: the gradients from the rows still in registers, nothing reloaded.
-template <int L, int NR>
-__device__ __forceinline__ void fm_wide_chunk(const FmArgs& a, const int (&mine)[NR], const int c, const int q, const int nq,
-                                              int (&id)[16], float4 (&v)[16])
+// WV (value weights, as in fm_body): lane q keeps the weights of its fields beside their ids (0 where the id is absent), a chunk's
+// weights x[16] are shuffled out with its ids, and the rows enter as e = (scale x) row in BOTH passes -- the second pass has to
+// reproduce the first pass's e bit for bit; x[] lives across one chunk only.
+template <int L, int NR, bool WV>
+__device__ __forceinline__ void fm_wide_chunk(const FmArgs& a, const int (&mine)[NR], const float (&minex)[NR], const int c, const int q,
+                                              const int nq, int (&id)[16], float (&x)[16], float4 (&v)[16])
 {
     // fields 16 c .. 16 c + 15 lie in one round of ids (L = 16 or 32): round 16 c / L, lanes 16 c % L + f
     int m = mine[0];
+    float mx = minex[0];
 #pragma unroll
-    for (int r = 1; r < NR; ++r) m = (r == 16 * c / L) ? mine[r] : m;
+    for (int r = 1; r < NR; ++r) { m = (r == 16 * c / L) ? mine[r] : m; if (WV) mx = (r == 16 * c / L) ? minex[r] : mx; }
 #pragma unroll
     for (int f = 0; f < 16; ++f) {
         id[f] = __shfl(m, 16 * c % L + f, L);             // -1 for fields >= F
+        if (WV) x[f] = __shfl(mx, 16 * c % L + f, L);     // 0 where the id is -1
         v[f] = (id[f] >= 0 && q < nq) ? *reinterpret_cast<const float4*>(a.table16 + (size_t)id[f] * a.rw + 4 * q)
                                       : make_float4(0.f, 0.f, 0.f, 0.f);
     }
 }
-__device__ __forceinline__ void fm_wide_grads(const FmArgs& a, float* out, const int c, const int (&id)[16], const float4 (&v)[16],
-                                              const float4 S, const float delta)
+template <bool WV>
+__device__ __forceinline__ void fm_wide_grads(const FmArgs& a, float* out, const int c, const int (&id)[16], const float (&x)[16],
+                                              const float4 (&v)[16], const float4 S, const float delta)
 {
 #pragma unroll
     for (int f = 0; f < 16; ++f) {
         if (id[f] < 0) continue;
-        const float4 g = make_float4(c == 0 ? delta : (c < a.K ? delta * (S.x - v[f].x) : 0.f),
-                                     c + 1 < a.K ? delta * (S.y - v[f].y) : 0.f,
-                                     c + 2 < a.K ? delta * (S.z - v[f].z) : 0.f,
-                                     c + 3 < a.K ? delta * (S.w - v[f].w) : 0.f);
-        store16_sel(a.wt, out + (size_t)f * a.rw, g);
+        const float dx = WV ? delta * x[f] : delta;
+        const float4 g = make_float4(c == 0 ? dx : (c < a.K ? dx * (S.x - v[f].x) : 0.f),
+                                     c + 1 < a.K ? dx * (S.y - v[f].y) : 0.f,
+                                     c + 2 < a.K ? dx * (S.z - v[f].z) : 0.f,
+                                     c + 3 < a.K ? dx * (S.w - v[f].w) : 0.f);
+        if (WV) store16_sel_ws(a.wt, out + (size_t)f * a.rw, g);
+        else store16_sel(a.wt, out + (size_t)f * a.rw, g);
     }
 }
-template <int L, int NC>
+template <int L, int NC, bool WV>
 __device__ __forceinline__ void fm_wide_body(const FmArgs& a, const int blk, float* s_gb /*[256 / L]*/)
 {
     constexpr int EPB = 256 / L;                          // examples per workgroup
@@ -175,27 +194,34 @@ __device__ __forceinline__ void fm_wide_body(const FmArgs& a, const int blk, flo
     const int tid = threadIdx.x, q = tid % L, grp = tid / L, nq = a.rw >> 2;
     const int t = blk * EPB + grp;
     int mine[NR];
+    float minex[NR];
 #pragma unroll
     for (int r = 0; r < NR; ++r) {
         const int fld = q + r * L;
         mine[r] = -1;
+        minex[r] = 0.f;
         if (t < a.B && fld < a.F) {
             const int64_t id = a.ids[(size_t)t * a.F + fld];
+            float w = 0.f;
+            if (WV) w = a.wts[(size_t)t * a.F + fld];       // in the id's round trip
             if (id < -1 || id >= a.n_rows) atomicOr(a.err, 1);
             else mine[r] = (int)id;
             if (a.stamp && mine[r] >= 0) a.stamp[mine[r]] = a.step;
+            if (WV && mine[r] >= 0) minex[r] = w;
         }
     }
     int id[16];
+    float x[16];
     float4 v[16];
     float lin = 0.f;
     float4 S = make_float4(0.f, 0.f, 0.f, 0.f), sq = S;
 #pragma unroll 1
     for (int c = 0; c < NC; ++c) {                        // rolled: one chunk's 16 rows in registers at a time
-        fm_wide_chunk<L, NR>(a, mine, c, q, nq, id, v);
+        fm_wide_chunk<L, NR, WV>(a, mine, minex, c, q, nq, id, x, v);
 #pragma unroll
         for (int f = 0; f < 16; ++f) {
-            v[f].x *= a.scale; v[f].y *= a.scale; v[f].z *= a.scale; v[f].w *= a.scale;
+            const float s = WV ? a.scale * x[f] : a.scale;    // e = (scale x) row
+            v[f].x *= s; v[f].y *= s; v[f].z *= s; v[f].w *= s;
             if (q == 0) { lin += v[f].x; v[f].x = 0.f; }      // column 0 is w_f
             S.x += v[f].x; S.y += v[f].y; S.z += v[f].z; S.w += v[f].w;
             sq.x = fmaf(v[f].x, v[f].x, sq.x); sq.y = fmaf(v[f].y, v[f].y, sq.y);
@@ -218,48 +244,51 @@ __device__ __forceinline__ void fm_wide_body(const FmArgs& a, const int blk, flo
         }
     } else if (a.train && q == 0) a.loss_t[t] = 0.f;
     if (!a.train) return;
-    // d yhat / d w_f = 1 ; d yhat / d v_f[l] = S_l - v_f[l]   (x = 1)
+    // d yhat / d w_f = x_f ; d yhat / d v_f[l] = x_f (S_l - e_f[l])   (WV = false: x = 1)
     float* out = a.gxp + (size_t)t * a.K1p + 4 * q;
     if (NC == 1) {                                        // up to 16 fields: the rows are still in registers
-        if (q < nq) fm_wide_grads(a, out, 4 * q, id, v, S, delta);
+        if (q < nq) fm_wide_grads<WV>(a, out, 4 * q, id, x, v, S, delta);
     } else {
 #pragma unroll 1
         for (int c = 0; c < NC; ++c) {                    // every chunk's rows again (the shuffles with the whole group)
-            fm_wide_chunk<L, NR>(a, mine, c, q, nq, id, v);
+            fm_wide_chunk<L, NR, WV>(a, mine, minex, c, q, nq, id, x, v);
 #pragma unroll
-            for (int f = 0; f < 16; ++f) { v[f].x *= a.scale; v[f].y *= a.scale; v[f].z *= a.scale; v[f].w *= a.scale; }
-            if (q < nq) fm_wide_grads(a, out + (size_t)(16 * c) * a.rw, 4 * q, id, v, S, delta);
+            for (int f = 0; f < 16; ++f) {
+                const float s = WV ? a.scale * x[f] : a.scale;
+                v[f].x *= s; v[f].y *= s; v[f].z *= s; v[f].w *= s;
+            }
+            if (q < nq) fm_wide_grads<WV>(a, out + (size_t)(16 * c) * a.rw, 4 * q, id, x, v, S, delta);
         }
     }
     if (q == 0) s_gb[grp] = delta;
     __syncthreads();
     if (tid == 0) { float s = 0.f; for (int i = 0; i < EPB; ++i) s += s_gb[i]; a.gb_part[blk] = s; }
 }
-template <int L, int NC>
+template <int L, int NC, bool WV>
 __global__ __launch_bounds__(256) void k_fm_wide(const FmArgs a)
 {
     __shared__ float s_gb[256 / L];
-    fm_wide_body<L, NC>(a, blockIdx.x, s_gb);
+    fm_wide_body<L, NC, WV>(a, blockIdx.x, s_gb);
 }
-template <typename KT, int L, int NC>
+template <typename KT, int L, int NC, bool WV>
 __global__ __launch_bounds__(256) void k_fm_wide_merge_fwd(const SortArgs so, const FmArgs a)
 {
     extern __shared__ __align__(16) unsigned char smem[];
     __shared__ float s_gb[256 / L];
     if ((int)blockIdx.x < so.nblk) { sortB_body<KT>(so, blockIdx.x, smem); return; }
-    fm_wide_body<L, NC>(a, (int)blockIdx.x - so.nblk, s_gb);
+    fm_wide_body<L, NC, WV>(a, (int)blockIdx.x - so.nblk, s_gb);
 }
 
 // A training step is four launches: run sorts of the batch's (row, t) keys; their rank merge BESIDE the forward + gradients
 // (both need only the ids: the merge takes 16 F workgroups, the examples the rest); level-1 sparse-row update; level-2 update
 // BESIDE the bias / loss tail.  As six launches in a row (sort, sort, forward, scatter, scatter, tail) the step took 49.6 us.
-template <typename KT, int NF>
+template <typename KT, int NF, bool WV>
 __global__ __launch_bounds__(256) void k_fm_merge_fwd(const SortArgs so, const FmArgs a)
 {
     extern __shared__ __align__(16) unsigned char smem[];
     __shared__ float s_gb[16];
     if ((int)blockIdx.x < so.nblk) { sortB_body<KT>(so, blockIdx.x, smem); return; }
-    fm_body<NF>(a, (int)blockIdx.x - so.nblk, s_gb);
+    fm_body<NF, WV>(a, (int)blockIdx.x - so.nblk, s_gb);
 }
 
 // The bias under Adam / FTRL: the state beside it (sb [2]) and this step's learning rate (Adam: lr_t).  opt = 0: SGD.
@@ -416,19 +445,26 @@ int init_opt_state(fm_handle* h)
 
 // The forwards of both layouts, one instantiation per 16 fields: NF = NC = ceil(F / 16) (1 up to 16 fields).  sb: the rank merge
 // of the batch's sort runs beside the forward (training), null: the forward alone (predictions).  nb: the examples' workgroups.
+// WV = (a.wts != nullptr): without weights the kernels are the ones that never read a weight.
+template <typename KT, int N, bool WV>
+void launch_fwd_nw(const fm_handle* h, const SortArgs* sb, const FmArgs& a, int nb)
+{
+    if (!h->wide) {
+        if (!sb) hipLaunchKernelGGL((k_fm<N, WV>), dim3(nb), dim3(256), 0, h->st, a);
+        else hipLaunchKernelGGL((k_fm_merge_fwd<KT, N, WV>), dim3(sb->nblk + nb), dim3(256), sort_lds_bytes<KT>(), h->st, *sb, a);
+    } else if (h->rw <= 64) {         // L = 16 lanes per example while a row's float4 pieces fit (rank <= 63), else 32
+        if (!sb) hipLaunchKernelGGL((k_fm_wide<16, N, WV>), dim3(nb), dim3(256), 0, h->st, a);
+        else hipLaunchKernelGGL((k_fm_wide_merge_fwd<KT, 16, N, WV>), dim3(sb->nblk + nb), dim3(256), sort_lds_bytes<KT>(), h->st, *sb, a);
+    } else {
+        if (!sb) hipLaunchKernelGGL((k_fm_wide<32, N, WV>), dim3(nb), dim3(256), 0, h->st, a);
+        else hipLaunchKernelGGL((k_fm_wide_merge_fwd<KT, 32, N, WV>), dim3(sb->nblk + nb), dim3(256), sort_lds_bytes<KT>(), h->st, *sb, a);
+    }
+}
 template <typename KT, int N>
 void launch_fwd_n(const fm_handle* h, const SortArgs* sb, const FmArgs& a, int nb)
 {
-    if (!h->wide) {
-        if (!sb) hipLaunchKernelGGL(k_fm<N>, dim3(nb), dim3(256), 0, h->st, a);
-        else hipLaunchKernelGGL((k_fm_merge_fwd<KT, N>), dim3(sb->nblk + nb), dim3(256), sort_lds_bytes<KT>(), h->st, *sb, a);
-    } else if (h->rw <= 64) {         // L = 16 lanes per example while a row's float4 pieces fit (rank <= 63), else 32
-        if (!sb) hipLaunchKernelGGL((k_fm_wide<16, N>), dim3(nb), dim3(256), 0, h->st, a);
-        else hipLaunchKernelGGL((k_fm_wide_merge_fwd<KT, 16, N>), dim3(sb->nblk + nb), dim3(256), sort_lds_bytes<KT>(), h->st, *sb, a);
-    } else {
-        if (!sb) hipLaunchKernelGGL((k_fm_wide<32, N>), dim3(nb), dim3(256), 0, h->st, a);
-        else hipLaunchKernelGGL((k_fm_wide_merge_fwd<KT, 32, N>), dim3(sb->nblk + nb), dim3(256), sort_lds_bytes<KT>(), h->st, *sb, a);
-    }
+    if (a.wts) launch_fwd_nw<KT, N, true>(h, sb, a, nb);
+    else launch_fwd_nw<KT, N, false>(h, sb, a, nb);
 }
 template <typename KT>
 void launch_fwd(const fm_handle* h, const SortArgs* sb, const FmArgs& a, int nb)
@@ -488,7 +524,8 @@ void launch_opt_pass(fm_handle* h, float lambda, float lr_step)
                            h->rw, lambda, h->opt, lr_step, h->beta1, h->beta2, h->eps);
 }
 
-int fm_run(fm_handle* h, const int32_t* ids, const float* y, int B, float lr, float lambda, int reduce_mean, float* p_out, bool train)
+int fm_run(fm_handle* h, const int32_t* ids, const float* wts, const float* y, int B, float lr, float lambda, int reduce_mean, float* p_out,
+           bool train)
 {
     const int Ba = rup(B, 16), F = h->F;
     const bool opt = train && h->opt != FM_OPT_SGD;
@@ -501,7 +538,7 @@ int fm_run(fm_handle* h, const int32_t* ids, const float* y, int B, float lr, fl
     }
     FmArgs a{ids, y, B, F, h->K, h->table16, h->n_rows, h->b, (float)h->scale, reduce_mean ? 1.0f / (float)B : 1.0f, train ? 1 : 0,
              h->gxp, h->K1p, p_out, h->loss_t, h->gb_part, h->err_flag, !(getenv("FM_WT") && atoi(getenv("FM_WT")) == 0),
-             opt && !h->dense_g ? h->stamp : nullptr, (int)h->t, h->rw};
+             opt && !h->dense_g ? h->stamp : nullptr, (int)h->t, h->rw, wts};
     if (h->wide) {
         const int rc = fm_run_wide(h, a, B, lr, lambda, reduce_mean, opt, lr_step);
         if (rc != FNN_OK) return rc;
@@ -685,13 +722,19 @@ int fm_get_b(fm_handle* h, float* b)
 int fm_train_step(fm_handle* h, const int32_t* ids, const float* y, int B, float lr, float lambda, int reduce_mean, float* p_out,
                   float* loss_out)
 {
+    return fm_train_step_w(h, ids, nullptr, y, B, lr, lambda, reduce_mean, p_out, loss_out);
+}
+
+int fm_train_step_w(fm_handle* h, const int32_t* ids, const float* wts, const float* y, int B, float lr, float lambda, int reduce_mean,
+                    float* p_out, float* loss_out)
+{
     if (!h || !ids || !y) return FNN_ERR_ARG;
     if (B < 1 || B > h->Bmax) MFAIL(h, FNN_ERR_ARG, "B must be in [1, max_batch]");
     if (!h->table16) MFAIL(h, FNN_ERR_STATE, "fm_set_table has not been called");
     if (h->opt == FM_OPT_SGD && (!(lr * lambda < 1.0f) || lambda < 0.f)) MFAIL(h, FNN_ERR_ARG, "need 0 <= lr * lambda < 1");
     if (h->opt != FM_OPT_SGD && (!(lambda >= 0.f) || !(lr > 0.f))) MFAIL(h, FNN_ERR_ARG, "Adam / FTRL need lr > 0 and lambda >= 0");
     MHK(h, hipSetDevice(h->dev));
-    int rc = fm_run(h, ids, y, B, lr, lambda, reduce_mean, p_out, true);
+    int rc = fm_run(h, ids, wts, y, B, lr, lambda, reduce_mean, p_out, true);
     if (rc != FNN_OK) return rc;
     if (loss_out) {
         MHK(h, hipMemcpyAsync(loss_out, h->loss_dev, 4, hipMemcpyDeviceToHost, h->st));
@@ -700,13 +743,15 @@ int fm_train_step(fm_handle* h, const int32_t* ids, const float* y, int B, float
     return FNN_OK;
 }
 
-int fm_predict(fm_handle* h, const int32_t* ids, int B, float* p_out)
+int fm_predict(fm_handle* h, const int32_t* ids, int B, float* p_out) { return fm_predict_w(h, ids, nullptr, B, p_out); }
+
+int fm_predict_w(fm_handle* h, const int32_t* ids, const float* wts, int B, float* p_out)
 {
     if (!h || !ids || !p_out) return FNN_ERR_ARG;
     if (B < 1 || B > h->Bmax) MFAIL(h, FNN_ERR_ARG, "B must be in [1, max_batch]");
     if (!h->table16) MFAIL(h, FNN_ERR_STATE, "fm_set_table has not been called");
     MHK(h, hipSetDevice(h->dev));
-    return fm_run(h, ids, nullptr, B, 0.f, 0.f, 0, p_out, false);
+    return fm_run(h, ids, wts, nullptr, B, 0.f, 0.f, 0, p_out, false);
 }
 
 int fm_set_optimizer(fm_handle* h, int optimizer, float beta1, float beta2, float eps)
@@ -740,6 +785,11 @@ int fm_get_opt_state(fm_handle* h, float* s0, float* s1, float* sb, int64_t* t)
 
 int fm_eval(fm_handle* h, const int32_t* ids, const int32_t* y, int64_t N, double* auc, double* rmse, double* logloss)
 {
+    return fm_eval_w(h, ids, nullptr, y, N, auc, rmse, logloss);
+}
+
+int fm_eval_w(fm_handle* h, const int32_t* ids, const float* wts, const int32_t* y, int64_t N, double* auc, double* rmse, double* logloss)
+{
     if (!h || !ids || !y || N < 1) return FNN_ERR_ARG;
     if (!h->table16) MFAIL(h, FNN_ERR_STATE, "fm_set_table has not been called");
     MHK(h, hipSetDevice(h->dev));
@@ -747,7 +797,7 @@ int fm_eval(fm_handle* h, const int32_t* ids, const int32_t* y, int64_t N, doubl
     MHK(h, hipMalloc((void**)&p_d, (size_t)N * 4));
     for (int64_t lo = 0; lo < N; lo += h->Bmax) {
         const int B = (int)(N - lo < h->Bmax ? N - lo : h->Bmax);
-        const int rc = fm_run(h, ids + lo * h->F, nullptr, B, 0.f, 0.f, 0, p_d + lo, false);
+        const int rc = fm_run(h, ids + lo * h->F, wts ? wts + lo * h->F : nullptr, nullptr, B, 0.f, 0.f, 0, p_d + lo, false);
         if (rc != FNN_OK) { hipFree(p_d); return rc; }
     }
     double out[4] = {0, 0, 0, 0};

@@ -6,8 +6,15 @@
  *      yhat = b + sum_i w_i x_i + 1/2 (|sum_i v_i x_i|^2 - sum_i |v_i|^2 x_i^2),
  * loss :36-41 (sigmoid cross-entropy, reduce_sum or reduce_mean, + lambda * (l2_loss(W) + l2_loss(V)
  * + l2_loss(b)) with tf.nn.l2_loss = sum(t^2)/2), plain SGD (python/tf_util.py:26-29), as driven by
- * python/ipinyou.py:136-173.  One feature per field with value 1 (iPinYou; `load_ipinyou_data`
- * returns X_val = 1); ids [B, F] int32 with -1 = absent.
+ * python/ipinyou.py:136-173.  One feature per field: ids [B, F] int32 with -1 = absent.  Its value x is 1 (iPinYou;
+ * `load_ipinyou_data` returns X_val = 1) through fm_train_step / fm_predict / fm_eval, or wts[t][f] through the *_w entry points
+ * (the reference's `sp_wt_hldr`, python/FM.py:24-29 and python/LR.py:23-27; python/baseline.py:345 feeds the values of Criteo's 13
+ * numeric fields and the weights of its 26 categorical ones).  With e_f = x_f * row(ids[t][f]):
+ *      yhat = b + sum_f e_f[0] + 1/2 (sum_l (sum_f e_f[l])^2 - sum_f sum_l e_f[l]^2),
+ *      d yhat / d w_f = x_f,   d yhat / d v_f[l] = x_f (S_l - e_f[l]),   S_l = sum_f e_f[l];
+ * (x v)^2 is the reference's v^2 x^2 up to f32 rounding.  Weights are data and are not range-checked: zero and negative ones are
+ * legal, a zero weight adds exactly 0 to its row's gradient (the row is still stamped for Adam / FTRL), NaN / Inf at a present
+ * field propagate, and the weight of an absent field (id = -1) has no effect whatever its value.
  *
  * Ranks 0..127 (k = rank + 1 = 1..128: python/baseline.py's FM10, FM50 and FM100), 1..64 fields (python/baseline.py's
  * 39-column runs included), batches up to 4096.
@@ -73,6 +80,12 @@ int fm_train_step(fm_handle* h, const int32_t* ids, const float* y, int B, float
                   int reduce_mean, float* p_out, float* loss_out);
 /* p_out [B] = sigmoid(yhat) (`test_preds`, :52). */
 int fm_predict(fm_handle* h, const int32_t* ids, int B, float* p_out);
+/* The same with value weights: wts [B, F] f32, a DEVICE pointer, row-major like ids.  wts == NULL IS the call above: the three
+ * entry points without weights forward here with NULL, run the same kernels and give bit-identical results.  fm_eval_w advances
+ * wts with ids, max_batch examples a chunk. */
+int fm_train_step_w(fm_handle* h, const int32_t* ids, const float* wts, const float* y, int B, float lr, float lambda,
+                    int reduce_mean, float* p_out, float* loss_out);
+int fm_predict_w(fm_handle* h, const int32_t* ids, const float* wts, int B, float* p_out);
 
 /* The optimiser of fm_train_step (python/tf_util.py:15-29); lr and lambda of fm_train_step keep their meaning (base
  * learning rate, L2 weight).  Folds any pending SGD scale into the rows, (re)initialises the state -- Adam: m = v = 0;
@@ -89,6 +102,8 @@ int fm_get_opt_state(fm_handle* h, float* s0, float* s1, float* sb, int64_t* t);
  * RMSE and logloss (p clipped to [2^-52, 1 - 2^-52]) on the device.  Outputs nullable.  FNN_ERR_RANGE when y holds one
  * class only (auc undefined; rmse and logloss are still written). */
 int fm_eval(fm_handle* h, const int32_t* ids, const int32_t* y, int64_t N, double* auc, double* rmse, double* logloss);
+int fm_eval_w(fm_handle* h, const int32_t* ids, const float* wts, const int32_t* y, int64_t N,
+              double* auc, double* rmse, double* logloss);
 
 #if defined(__GNUC__)
 #pragma GCC visibility pop

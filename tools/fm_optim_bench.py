@@ -12,6 +12,11 @@ Configurations: fm_sgd / fm_adam / fm_ftrl (rank 10), lr_ftrl (rank 0 = LR); *_d
 clears the whole gradient store G (FM_OPT_DENSE_G=1) instead of the rows the step's stamp marks.  The wide path (k >= 17):
 fm50_* / fm100_* (the reference's FM50 / FM100), and fm100_adam_b100 at python/baseline.py's FM batch of 100.
 
+--weights none|uniform|criteo: value weights through fm_train_step_w.  `none`, the default, is the call without weights
+(fm_train_step).  `uniform`: the same ids with a weight from [0, 2) per (example, field) -- its step time against `none` of the
+same build is what the weights cost.  `criteo`: synth.criteo_like -- the first 13 fields (a third of fewer than 39) are numeric,
+ONE row each with a real weight, the rest are categorical with weight 1 (as tools/ipnn_wide_bench.py --weights criteo).
+
 --fields N (1..64, default 16): the same 937,670 rows spread over N fields -- synth.field_sizes_ipinyou(n_fields=N) cycles the
 16 iPinYou-like field sizes over the N fields and rescales them to the same total.  16 is the shape above, unchanged."""
 import argparse
@@ -89,10 +94,19 @@ def digest(lib, h, D, K, opt):
     return hs.hexdigest()
 
 
-def run(names, steps, warmup, B0, want_digest=False):
+def weight_bytes(B):
+    """What the weights add to the forward's traffic: B * F floats read once (fwd_bytes moves 2 * B * F * row bytes)."""
+    return B * F * 4
+
+
+def run(names, steps, warmup, B0, want_digest=False, weights='none'):
     import torch
     sizes, D = shape()
     from deep_ctr_amd import _capi, synth
+    n_num = 0
+    if weights == 'criteo':
+        n_num = 13 if F >= 39 else F // 3
+        D = n_num + sum(sizes[n_num:])
     lib = _capi.load()
     dev = torch.device('cuda', 0)
     stream = torch.cuda.Stream(device=dev)
@@ -101,7 +115,13 @@ def run(names, steps, warmup, B0, want_digest=False):
     for name in names:
         rank, opt, lr, lam, mean, dense = CONFIGS[name][:6]
         B = CONFIGS[name][6] if len(CONFIGS[name]) > 6 else B0
-        ids = torch.as_tensor(synth.zipf_ids(NB * B, sizes, 1.1, 99)).to(dev).contiguous()
+        ids_h, w_h = synth.zipf_ids(NB * B, sizes, 1.1, 99), None
+        if weights == 'criteo':
+            ids_h, w_h = synth.criteo_like(NB * B, n_num, sizes[n_num:], seed=99)
+        elif weights == 'uniform':
+            w_h = np.random.RandomState(98).uniform(0.0, 2.0, size=ids_h.shape).astype(np.float32)
+        ids = torch.as_tensor(ids_h).to(dev).contiguous()
+        wts = None if w_h is None else torch.as_tensor(w_h).to(dev).contiguous()
         y = torch.as_tensor((np.random.RandomState(3).uniform(size=NB * B) < 0.02).astype(np.float32)).to(dev)
         K = rank + 1
         os.environ['FM_OPT_DENSE_G'] = '1' if dense else '0'        # read by fm_create
@@ -116,7 +136,12 @@ def run(names, steps, warmup, B0, want_digest=False):
         def steps_(n):
             for i in range(n):
                 j = i % NB
-                if lib.fm_train_step(h, ids.data_ptr() + j * B * F * 4, y.data_ptr() + j * B * 4, B, lr, lam, mean, None, None) != 0:
+                if wts is None:
+                    rc = lib.fm_train_step(h, ids.data_ptr() + j * B * F * 4, y.data_ptr() + j * B * 4, B, lr, lam, mean, None, None)
+                else:
+                    rc = lib.fm_train_step_w(h, ids.data_ptr() + j * B * F * 4, wts.data_ptr() + j * B * F * 4, y.data_ptr() + j * B * 4,
+                                             B, lr, lam, mean, None, None)
+                if rc != 0:
                     raise RuntimeError(lib.fm_last_error(h).decode())
         steps_(warmup)
         if lib.fm_sync(h) != 0:
@@ -127,6 +152,9 @@ def run(names, steps, warmup, B0, want_digest=False):
             raise RuntimeError(lib.fm_last_error(h).decode())
         dt = (time.perf_counter() - t0) / steps
         r = {'batch': B, 'us_per_step': dt * 1e6, 'examples_per_sec': B / dt}
+        if wts is not None:
+            rw = SLOT if K <= 16 else rup4(K)
+            r.update({'weight_bytes': weight_bytes(B), 'weight_share_of_forward_bytes': weight_bytes(B) / float(2 * B * F * rw * 4)})
         if want_digest:
             r['sha256'] = digest(lib, h, D, K, opt)
         lib.fm_destroy(h)
@@ -134,8 +162,11 @@ def run(names, steps, warmup, B0, want_digest=False):
             nb = pass_bytes(D, K, dense)
             r.update({'pass_bytes': nb, 'pass_bytes_tbps_at_step_time': nb / dt / 1e12})
         out[name] = r
-    return {'tool': 'fm_optim_bench', 'n_rows': D, 'fields': F, 'batch': B0, 'steps': steps, 'warmup': warmup,
-            'device': torch.cuda.get_device_name(0), 'configs': out}
+    res = {'tool': 'fm_optim_bench', 'n_rows': D, 'fields': F, 'batch': B0, 'steps': steps, 'warmup': warmup,
+           'device': torch.cuda.get_device_name(0), 'configs': out}
+    if weights != 'none':
+        res.update({'weights': weights, 'numeric_fields': n_num})
+    return res
 
 
 def from_stats(pairs):
@@ -179,6 +210,8 @@ def main():
     ap.add_argument('--from-stats', nargs='+', default=None)
     ap.add_argument('--digest', action='store_true')
     ap.add_argument('--fields', type=int, default=16)
+    ap.add_argument('--weights', choices=('none', 'uniform', 'criteo'), default='none',
+                    help='value weights of the steps (fm_train_step_w); none = the call without weights')
     a = ap.parse_args()
     global F
     F = a.fields
@@ -189,7 +222,7 @@ def main():
     for n in names:
         if n not in CONFIGS:
             raise SystemExit('unknown config %r (%s)' % (n, ', '.join(CONFIGS)))
-    print(json.dumps(run(names, a.steps, a.warmup, a.batch, a.digest)))
+    print(json.dumps(run(names, a.steps, a.warmup, a.batch, a.digest, a.weights)))
 
 
 if __name__ == '__main__':
