@@ -1296,6 +1296,81 @@ static __global__ __launch_bounds__(256) void k_mask_T(const MaskTArgs a)
     }
 }
 
+// Drawn keep-masks (ipnn_train_step_drawn / ipnn_draw_masks): the generator that stands where k_mask_T stands.  The mask of
+// (layer t, example ex, reference column c) is one 32-bit word of Philox4x32-10 (Salmon et al., SC'11) against a threshold:
+//   key = (lo32(seed), hi32(seed)), counter = (c, t << 16 | ex >> 2, lo32(step), hi32(step)), word j <-> example 4 (ex >> 2) + j
+// (include/ipnn_hip.h; deep-ctr_amd/dropout.py restates it in NumPy and the tests hold the two equal byte for byte).
+__device__ __forceinline__ void philox4x32_10(unsigned c0, unsigned c1, unsigned c2, unsigned c3, unsigned k0, unsigned k1, unsigned w[4])
+{
+#pragma unroll
+    for (int r = 0; r < 10; ++r) {
+        const unsigned long long p0 = (unsigned long long)0xD2511F53u * c0, p1 = (unsigned long long)0xCD9E8D57u * c2;
+        const unsigned n0 = (unsigned)(p1 >> 32) ^ c1 ^ k0, n2 = (unsigned)(p0 >> 32) ^ c3 ^ k1;
+        c1 = (unsigned)p1; c3 = (unsigned)p0; c0 = n0; c2 = n2;
+        k0 += 0x9E3779B9u; k1 += 0xBB67AE85u;
+    }
+    w[0] = c0; w[1] = c1; w[2] = c2; w[3] = c3;
+}
+// One launch for every layer, tiled like k_mask_T (64 columns x 64 examples a workgroup).  A thread owns one column and 16
+// consecutive examples: four Philox calls, one 16-byte slot of the transposed layout dstT[t] ([Dp][ldT], mask_off; pad columns
+// and the examples from B on are zero, layer 0 in slot order with the draw taken at the slot's reference column) -- written
+// exactly as k_mask_T writes it, but with nothing read.  dstR[t], where set, takes the same bytes row-major in the ABI's layout
+// ([B][d_t], reference column order) through an LDS transposition: layer 0 of a training step (the inner-product forward reads
+// it through its `mask` argument), every layer for ipnn_draw_masks.  The stores are plain C++ or raw buffer stores with the sc1
+// policy (see ipw_store16), never inline assembly.
+struct MaskDrawArgs {
+    uint8_t* dstT[IPNN_MAX_HIDDEN + 1]; uint8_t* dstR[IPNN_MAX_HIDDEN + 1]; int d[IPNN_MAX_HIDDEN + 1], Dp[IPNN_MAX_HIDDEN + 1];
+    unsigned bytesT[IPNN_MAX_HIDDEN + 1];       // extent of dstT[t]: the write-through stores' buffer resource
+    int tile0[IPNN_MAX_HIDDEN + 2]; int n; const int* ref0; int B, Ba, ldT; bool wt;
+    unsigned key0, key1, step0, step1, thr; bool all;      // all: keep_prob >= 1, every element is kept
+};
+static __global__ __launch_bounds__(256) void k_mask_draw(const MaskDrawArgs a)
+{
+    __shared__ __align__(16) uint8_t s[64][68];         // [column][example], 17 dwords per row (k_mask_T's tile)
+    int t = 0;
+#pragma unroll
+    for (int q = 1; q <= IPNN_MAX_HIDDEN; ++q) t += (q < a.n && (int)blockIdx.x >= a.tile0[q]) ? 1 : 0;
+    uint8_t* const dT = a.dstT[t];
+    uint8_t* const dR = a.dstR[t];
+    if (!dT && !dR) return;
+    const int local = (int)blockIdx.x - a.tile0[t], ntx = a.Ba / 64;
+    const int t0 = (local % ntx) * 64, c0 = (local / ntx) * 64, d = a.d[t];
+    {
+        const int cc = threadIdx.x >> 2, q = threadIdx.x & 3, c = c0 + cc, ex0 = t0 + 16 * q;
+        int sc = t == 0 ? a.ref0[c] : (c < d ? c : -1);             // c < Dp[t]: the tiles cover exactly the padded columns
+        ipw_u32x4 v = {0u, 0u, 0u, 0u};
+        if (sc >= 0) {
+#pragma unroll
+            for (int j = 0; j < 4; ++j) {
+                const int ex = ex0 + 4 * j;
+                if (ex >= a.B) continue;
+                unsigned w[4] = {0u, 0u, 0u, 0u};
+                if (!a.all) philox4x32_10((unsigned)sc, ((unsigned)t << 16) | (unsigned)(ex >> 2), a.step0, a.step1, a.key0, a.key1, w);
+                unsigned pk = 0;
+#pragma unroll
+                for (int i = 0; i < 4; ++i) pk |= ((ex + i < a.B && (a.all || w[i] < a.thr)) ? 1u : 0u) << (8 * i);
+                v[j] = pk;
+            }
+        }
+        if (dT) ipw_store16(a.wt, ipw_rsrc(dT, a.bytesT[t]), dT, mask_off(c, ex0, a.ldT), v);
+        if (dR) {                                                    // 68 cc + 16 q is a multiple of 4 only: four dword stores
+            unsigned* sw = reinterpret_cast<unsigned*>(&s[cc][16 * q]);
+#pragma unroll
+            for (int j = 0; j < 4; ++j) sw[j] = v[j];
+        }
+    }
+    if (!dR) return;
+    __syncthreads();
+    const int cx = threadIdx.x & 63, c = c0 + cx;
+    const int sc = t == 0 ? a.ref0[c] : (c < d ? c : -1);
+    if (sc < 0) return;
+#pragma unroll
+    for (int k = 0; k < 16; ++k) {                                   // a wave writes 64 columns of one example: one run per field
+        const int r = (threadIdx.x >> 6) + 4 * k, ex = t0 + r;
+        if (ex < a.B) dR[(size_t)ex * d + sc] = s[cx][r];
+    }
+}
+
 // W_t <- W_t - lr * sum of slabs; refresh both tiled shadows.  Layer 1 rows are in slot layout.
 template <typename T>
 static __global__ void k_ip_update(float* __restrict__ W, const float* __restrict__ slab, int splitk, size_t zstride,
@@ -1475,6 +1550,7 @@ struct ipnn_handle {
     std::vector<float*> W; std::vector<void*> wf, wb;           // W[t], t = 1..L+1 (index t-1)
     std::vector<void*> a, aT, dl, dlT;                           // a[t] t=0..L ; dl[t] t=1..L+1 (index t-1)
     std::vector<uint8_t*> maskT;                                 // keep-masks of a step, transposed [Dp_t][ldT], t = 0..L
+    uint8_t* mask0 = nullptr;                                    // drawn steps: layer 0's mask row-major [max_batch][d_0] (k_mask_draw -> IpArgs::mask); made by the first one
     hipStream_t st2 = nullptr; hipEvent_t ev_fork = nullptr, ev_join = nullptr, ev_mask = nullptr, ev_bwd = nullptr;
     // IPNN_UPDATE_SIDE=1 (default 0, measured slower -- DESIGN.md section 4): the dense update runs at the END of the side chain (behind ev_wg: the weight gradients) and the main
     // stream does NOT wait for it at the end of the step: the next call's mask transposition and gather -- which read neither the dense
@@ -1614,22 +1690,54 @@ int ip_wide_attr(ipnn_handle* h)
 // wts: value weights [B][F] (device) or NULL.  NULL launches the kernels as they were before the weights existed (WV = false);
 // a pointer launches their WV instantiations -- a compile-time variant, so that the unweighted path carries neither the loads
 // nor a branch.
+// the launch arguments of k_mask_draw for one (seed, step): the tiles of every layer (k_mask_T's grid), the key, the counter's
+// step words and the threshold of the handle's keep_prob; the targets (dstT / dstR) are the caller's to fill in
+struct IpDraw { uint64_t seed, step; };
+MaskDrawArgs ip_draw_args(const ipnn_handle* h, const IpDraw& dr, int B, int* tiles_out)
+{
+    MaskDrawArgs a{};
+    const int Ba = rup(B, 256);
+    int tiles = 0;
+    for (int t = 0; t <= h->L; ++t) {
+        a.d[t] = h->d[t]; a.Dp[t] = h->Dp[t]; a.bytesT[t] = (unsigned)((size_t)h->ldT * h->Dp[t]); a.tile0[t] = tiles;
+        tiles += (Ba / 64) * (h->Dp[t] / 64);
+    }
+    a.tile0[h->L + 1] = tiles; a.n = h->L + 1; a.ref0 = h->ref0; a.B = B; a.Ba = Ba; a.ldT = h->ldT; a.wt = h->wt;
+    a.key0 = (unsigned)dr.seed; a.key1 = (unsigned)(dr.seed >> 32); a.step0 = (unsigned)dr.step; a.step1 = (unsigned)(dr.step >> 32);
+    const double thr = std::floor((double)h->cfg.keep_prob * 4294967296.0);
+    a.all = h->cfg.keep_prob >= 1.0f;
+    a.thr = thr >= 4294967295.0 ? 0xffffffffu : (unsigned)thr;
+    *tiles_out = tiles;
+    return a;
+}
+
+// masks: the caller's keep-masks (ipnn_train_step_w), or draw: the (seed, step) the library draws them from (ipnn_train_step_drawn);
+// neither: no dropout.
 template <typename T>
 int ip_run(ipnn_handle* h, const int32_t* ids, const float* wts, const float* y, int B, const uint8_t* const* masks, float* logits_out,
-           float* p_out, bool train)
+           float* p_out, bool train, const IpDraw* draw = nullptr)
 {
     const int Ba = rup(B, 256), L = h->L, F = h->F, ldT = h->ldT;
     const float keep = h->cfg.keep_prob, inv_keep = 1.0f / keep;
     const size_t lds_ip = ip16_lds(F, h->Dp[0]);                 // k_ip_fwd pads its embedding tile
-    const bool drop = train && masks;
-    if (drop) for (int t = 0; t <= L; ++t) if (!masks[t]) IFAIL(h, FNN_ERR_ARG, "masks: null entry");
+    const bool drop = train && (masks || draw);
+    if (drop && !draw) for (int t = 0; t <= L; ++t) if (!masks[t]) IFAIL(h, FNN_ERR_ARG, "masks: null entry");
+    const uint8_t* const mask0 = !drop ? nullptr : draw ? h->mask0 : masks[0];      // layer 0's mask, row-major (the inner-product forward)
     { const int jrc = ip_join_table(h); if (jrc != FNN_OK) return jrc; }      // the previous step's sparse rows / bias (read by the gather)
     if (train) {
         // beside the stack, on the side stream: the grouping of the batch's ids for the sparse-row update (needed by the scatter);
         // the transposed keep-masks (needed from the first product on) go first on the main stream
         hipStream_t ss = h->st2 ? h->st2 : h->st;
         if (h->st2) { IHK(h, hipEventRecord(h->ev_fork, h->st)); IHK(h, hipStreamWaitEvent(h->st2, h->ev_fork, 0)); }
-        if (drop) {   // keep-masks of all layers -> transposed, tiled, zero padded, slot-ordered for layer 0
+        if (draw) {   // the library's own draw: the same transposed masks, and layer 0's row-major, written by one launch that reads nothing
+            int tiles = 0;
+            MaskDrawArgs da = ip_draw_args(h, *draw, B, &tiles);
+            for (int t = 0; t <= L; ++t) da.dstT[t] = h->maskT[t];
+            da.dstR[0] = h->mask0;
+            IpProf pm(h, "mask_t", h->mask_side ? ss : h->st);
+            hipLaunchKernelGGL(k_mask_draw, dim3(tiles), dim3(256), 0, h->mask_side ? ss : h->st, da);
+            if (h->st2 && h->mask_side) IHK(h, hipEventRecord(h->ev_mask, h->st2));
+        } else if (drop) {   // keep-masks of all layers -> transposed, tiled, zero padded, slot-ordered for layer 0
             MaskTArgs ma{};
             int tiles = 0;
             for (int t = 0; t <= L; ++t) {
@@ -1656,11 +1764,12 @@ int ip_run(ipnn_handle* h, const int32_t* ids, const float* wts, const float* y,
             hipLaunchKernelGGL((k_sortB<unsigned>), dim3(16 * F), dim3(256), SORT_N * 4, ss, so);
         }
     }
+    if (draw && h->st2 && h->mask_side) IHK(h, hipStreamWaitEvent(h->st, h->ev_mask, 0));     // the inner-product forward reads the drawn mask0
     if (h->wide) {
         IpProf ps(h, "ip_fwd");
         const int rc = ip_wide_attr(h);
         if (rc != FNN_OK) return rc;
-        const IpWideArgs wa = ip_wide_args(h, ids, wts, B, (train && masks) ? masks[0] : nullptr, (train && masks) ? inv_keep : 1.0f);
+        const IpWideArgs wa = ip_wide_args(h, ids, wts, B, mask0, drop ? inv_keep : 1.0f);
         if (wts) hipLaunchKernelGGL((k_ip_fwd_w<T, true>), dim3(Ba / IPW_EX), dim3(256), ipw_fwd_lds(F, h->rw), h->st, wa, (T*)h->a[0], (T*)h->aT[0],
                                     train ? h->emb : nullptr);
         else hipLaunchKernelGGL((k_ip_fwd_w<T>), dim3(Ba / IPW_EX), dim3(256), ipw_fwd_lds(F, h->rw), h->st, wa, (T*)h->a[0], (T*)h->aT[0],
@@ -1669,15 +1778,15 @@ int ip_run(ipnn_handle* h, const int32_t* ids, const float* wts, const float* y,
         IpProf ps(h, "ip_fwd");
         const int rc = ip_many_attr(h);
         if (rc != FNN_OK) return rc;
-        const IpManyArgs ma = ip_many_args(h, ids, wts, B, (train && masks) ? masks[0] : nullptr, (train && masks) ? inv_keep : 1.0f);
+        const IpManyArgs ma = ip_many_args(h, ids, wts, B, mask0, drop ? inv_keep : 1.0f);
         if (wts) hipLaunchKernelGGL((k_ip_fwd_m<T, true>), dim3(Ba / IPM_EX), dim3(256), ipm_fwd_lds(F), h->st, ma, (T*)h->a[0], (T*)h->aT[0],
                                     train ? h->emb : nullptr);
         else hipLaunchKernelGGL((k_ip_fwd_m<T>), dim3(Ba / IPM_EX), dim3(256), ipm_fwd_lds(F), h->st, ma, (T*)h->a[0], (T*)h->aT[0],
                                 train ? h->emb : nullptr);
     } else {
         IpProf ps(h, "ip_fwd");
-        IpFwdArgs fa{h->P, ids, B, F, h->K, h->table16, h->n_rows, h->b, (train && masks) ? masks[0] : nullptr, h->d[0],
-                     (train && masks) ? inv_keep : 1.0f, h->cfg.act, h->Dp[0], ldT, h->err_flag, h->fwd_skip, h->wt, wts};
+        IpFwdArgs fa{h->P, ids, B, F, h->K, h->table16, h->n_rows, h->b, mask0, h->d[0],
+                     drop ? inv_keep : 1.0f, h->cfg.act, h->Dp[0], ldT, h->err_flag, h->fwd_skip, h->wt, wts};
         if (wts && h->ipf_nt == 1024) hipLaunchKernelGGL((k_ip_fwd<T, 1024, true>), dim3(Ba / 16), dim3(1024), lds_ip, h->st, fa, (T*)h->a[0], (T*)h->aT[0], train ? h->emb : nullptr);
         else if (wts) hipLaunchKernelGGL((k_ip_fwd<T, IPF_NT, true>), dim3(Ba / 16), dim3(IPF_NT), lds_ip, h->st, fa, (T*)h->a[0], (T*)h->aT[0], train ? h->emb : nullptr);
         else if (h->ipf_nt == 1024) hipLaunchKernelGGL((k_ip_fwd<T, 1024>), dim3(Ba / 16), dim3(1024), lds_ip, h->st, fa, (T*)h->a[0], (T*)h->aT[0], train ? h->emb : nullptr);
@@ -1705,7 +1814,7 @@ int ip_run(ipnn_handle* h, const int32_t* ids, const float* wts, const float* y,
             hipLaunchKernelGGL((k_gemm_ft<T, 2, 2, E>), dim3((M + 63) / 64, (N + 63) / 64, splitk), dim3(256), lds2, h->st, A, Bm,
                                mt16, nt16, nkt_all, nkt, epi);
     };
-    if (drop && h->st2 && h->mask_side) IHK(h, hipStreamWaitEvent(h->st, h->ev_mask, 0));     // the strips / GEMMs read the transposed masks
+    if (drop && !draw && h->st2 && h->mask_side) IHK(h, hipStreamWaitEvent(h->st, h->ev_mask, 0));     // the strips / GEMMs read the transposed masks
     { const int jrc = ip_join(h); if (jrc != FNN_OK) return jrc; }            // the previous step's dense update (read from here on)
     constexpr int KS = Traits<T>::KS;
     int maxD = 0;
@@ -2155,7 +2264,7 @@ int ipnn_destroy(ipnn_handle* h)
     for (float* p : h->Wm) if (p) hipFree(p);
     for (float* p : h->Wv) if (p) hipFree(p);
     for (float* p : {h->tm, h->tv, h->tG, h->bmv}) if (p) hipFree(p);
-    void* ptrs[] = {h->table16, h->noshare, h->b, h->emb, h->dz0, h->gxp, h->gb_part, h->loss_t, h->loss_dev, h->slab, h->ref0, h->ptab, h->err_flag, h->rec,
+    void* ptrs[] = {h->mask0, h->table16, h->noshare, h->b, h->emb, h->dz0, h->gxp, h->gb_part, h->loss_t, h->loss_dev, h->slab, h->ref0, h->ptab, h->err_flag, h->rec,
                     h->part, h->owners, h->owner_cnt, h->skeys, h->cpow1, h->duo_xch, h->duo_flags};
     for (void* p : ptrs) if (p) hipFree(p);
     for (auto& kv : h->prof_ev) for (auto& p : kv.second) { hipEventDestroy(p.first); hipEventDestroy(p.second); }
@@ -2308,22 +2417,50 @@ int ipnn_train_step(ipnn_handle* h, const int32_t* ids, const float* y, int B, c
     return ipnn_train_step_w(h, ids, nullptr, y, B, masks, logits_out, loss_sum_out);
 }
 
-int ipnn_train_step_w(ipnn_handle* h, const int32_t* ids, const float* wts, const float* y, int B, const uint8_t* const* masks,
-                      float* logits_out, float* loss_sum_out)
+// one training step: the caller's masks, the library's draw, or neither
+static int ip_train_step(ipnn_handle* h, const int32_t* ids, const float* wts, const float* y, int B, const uint8_t* const* masks,
+                         const IpDraw* draw, float* logits_out, float* loss_sum_out)
 {
     if (!h || !ids || !y) return FNN_ERR_ARG;
     if (B < 1 || B > h->Bmax) IFAIL(h, FNN_ERR_ARG, "B must be in [1, max_batch]");
     if (!h->table16) IFAIL(h, FNN_ERR_STATE, "ipnn_set_table has not been called");
     if (h->duo_failed) IFAIL(h, FNN_ERR_STATE, "an earlier step failed (StripDuo swap timed out): re-create the handle");
     IHK(h, hipSetDevice(h->dev));
-    int rc = h->bf16 ? ip_run<bf16_t>(h, ids, wts, y, B, masks, logits_out, nullptr, true)
-                     : ip_run<float>(h, ids, wts, y, B, masks, logits_out, nullptr, true);
+    if (draw && !h->mask0) IHK(h, hipMalloc((void**)&h->mask0, (size_t)h->Bmax * h->d[0]));      // every byte a step reads is drawn by that step
+    int rc = h->bf16 ? ip_run<bf16_t>(h, ids, wts, y, B, masks, logits_out, nullptr, true, draw)
+                     : ip_run<float>(h, ids, wts, y, B, masks, logits_out, nullptr, true, draw);
     if (rc != FNN_OK) return rc;
     if (loss_sum_out) {                                      // (the loss is summed in the update launch: join it)
         { const int jrc = ip_join(h); if (jrc != FNN_OK) return jrc; }
         IHK(h, hipMemcpyAsync(loss_sum_out, h->loss_dev, 4, hipMemcpyDeviceToHost, h->st));
         return ipnn_sync(h);
     }
+    return FNN_OK;
+}
+
+int ipnn_train_step_w(ipnn_handle* h, const int32_t* ids, const float* wts, const float* y, int B, const uint8_t* const* masks,
+                      float* logits_out, float* loss_sum_out)
+{
+    return ip_train_step(h, ids, wts, y, B, masks, nullptr, logits_out, loss_sum_out);
+}
+
+int ipnn_train_step_drawn(ipnn_handle* h, const int32_t* ids, const float* wts, const float* y, int B, uint64_t seed, uint64_t step,
+                          float* logits_out, float* loss_sum_out)
+{
+    const IpDraw dr{seed, step};
+    return ip_train_step(h, ids, wts, y, B, nullptr, &dr, logits_out, loss_sum_out);
+}
+
+int ipnn_draw_masks(ipnn_handle* h, uint64_t seed, uint64_t step, int B, uint8_t* const* masks_out)
+{
+    if (!h || !masks_out) return FNN_ERR_ARG;
+    if (B < 1 || B > h->Bmax) IFAIL(h, FNN_ERR_ARG, "B must be in [1, max_batch]");
+    IHK(h, hipSetDevice(h->dev));
+    int tiles = 0;
+    MaskDrawArgs da = ip_draw_args(h, IpDraw{seed, step}, B, &tiles);
+    for (int t = 0; t <= h->L; ++t) da.dstR[t] = masks_out[t];               // row-major targets only (a NULL entry: that layer's tiles return)
+    hipLaunchKernelGGL(k_mask_draw, dim3(tiles), dim3(256), 0, h->st, da);
+    IHK(h, hipGetLastError());
     return FNN_OK;
 }
 

@@ -14,7 +14,30 @@ import pickle
 import numpy as np
 
 from . import _capi
+from .dropout import _u64
 from .engine import FNNError
+
+
+class Drawn(object):
+    """`masks=Drawn(seed, step)`: the library draws the step's keep-masks itself (ipnn_train_step_drawn; dropout.drawn_masks
+    restates the draw).  seed and step are integers in uint64; the pair names the masks of one step."""
+    __slots__ = ('seed', 'step')
+
+    def __init__(self, seed, step):
+        object.__setattr__(self, 'seed', _u64('seed', seed))
+        object.__setattr__(self, 'step', _u64('step', step))
+
+    def __setattr__(self, name, value):
+        raise AttributeError("Drawn is a value: make another one")
+
+    def __eq__(self, other):
+        return isinstance(other, Drawn) and (self.seed, self.step) == (other.seed, other.step)
+
+    def __hash__(self):
+        return hash((self.seed, self.step))
+
+    def __repr__(self):
+        return "Drawn(seed=%d, step=%d)" % (self.seed, self.step)
 
 
 def criteo_feed(v_wts, c_ids, c_wts, offsets):
@@ -112,21 +135,27 @@ class IPNNEngine(object):
         return self._dev(wts, self._torch.float32)
 
     def train_step(self, ids, y, masks=None, want_logits=False, want_loss=True, wts=None):
-        """masks: list of len(hidden)+1 uint8 arrays [B, d_t] (keep-masks for z1 and every hidden layer).
+        """masks: list of len(hidden)+1 uint8 arrays [B, d_t] (keep-masks for z1 and every hidden layer), or Drawn(seed, step):
+        the library draws them on the device (ipnn_train_step_drawn), or None: no dropout.
         wts: value weights [B, F] (e_f = wts * row), None = all ones."""
         torch = self._torch
         ids_t, y_t = self._dev(ids, torch.int32), self._dev(y, torch.float32)
         wts_t = self._wts(wts, ids_t)
         B = ids_t.shape[0]
         mts, marr = None, None
-        if masks is not None:
+        drawn = masks if isinstance(masks, Drawn) else None
+        if masks is not None and drawn is None:
             mts = [self._dev(m, torch.uint8) for m in masks]
             assert len(mts) == len(self.hidden) + 1 and all(m.shape == (B, self.d[t]) for t, m in enumerate(mts))
             marr = (C.c_void_p * len(mts))(*[m.data_ptr() for m in mts])
         logits = torch.empty(B, dtype=torch.float32, device=self.device) if want_logits else None
         loss = C.c_float()
         self.stream.wait_stream(torch.cuda.current_stream(self.device))
-        if wts_t is None:
+        if drawn is not None:
+            self._ck(self.lib.ipnn_train_step_drawn(self.h, ids_t.data_ptr(), wts_t.data_ptr() if wts_t is not None else None, y_t.data_ptr(), B,
+                                                    drawn.seed, drawn.step, logits.data_ptr() if want_logits else None,
+                                                    C.byref(loss) if want_loss else None))
+        elif wts_t is None:
             self._ck(self.lib.ipnn_train_step(self.h, ids_t.data_ptr(), y_t.data_ptr(), B, marr,
                                               logits.data_ptr() if want_logits else None, C.byref(loss) if want_loss else None))
         else:
@@ -136,6 +165,18 @@ class IPNNEngine(object):
         self._keep = (ids_t, y_t, mts, wts_t)
         scale = 1.0 if self.reduce == 'sum' else 1.0 / B     # the library returns the sum of the per-example losses
         return {'loss': float(loss.value) * scale if want_loss else None, 'logits': logits}
+
+    def draw_masks(self, seed, step, B):
+        """The keep-masks ipnn_train_step_drawn(seed, step) draws for a batch of B: a list of len(hidden)+1 device tensors uint8
+        [B, d_t], what `masks=` takes (ipnn_draw_masks)."""
+        torch = self._torch
+        dr = Drawn(seed, step)
+        out = [torch.empty((B, self.d[t]), dtype=torch.uint8, device=self.device) for t in range(len(self.hidden) + 1)]
+        marr = (C.c_void_p * len(out))(*[m.data_ptr() for m in out])
+        self.stream.wait_stream(torch.cuda.current_stream(self.device))
+        self._ck(self.lib.ipnn_draw_masks(self.h, dr.seed, dr.step, B, marr))
+        torch.cuda.current_stream(self.device).wait_stream(self.stream)
+        return out
 
     def predict(self, ids, wts=None):
         torch = self._torch

@@ -12,6 +12,12 @@ per-segment device times of ipnn_prof_* and a FLOP / byte model of the step.  On
                                                   one constant row each for the whole batch, weighted by a value in [0, 2), the
                                                   others categorical with weight 1; `random` keeps the ids and draws every weight
                                                   from [0, 2); `none`, the default, is the call without weights)
+  python tools/ipnn_wide_bench.py --dropout none|input|drawn   (who makes the keep-masks of the timed steps: `none`, the default,
+                                                  changes nothing -- the resident masks built once at set-up, as always; `input`
+                                                  is a training loop's caller: fresh masks every step, torch.rand(...) < keep ->
+                                                  uint8 per layer on the device, then passed in; `drawn` is ipnn_train_step_drawn:
+                                                  the library draws the masks of (seed 1234, step i) itself.  With --mask-cost the
+                                                  device time of making one step's `input` masks is measured on its own.)
 
 The k11 configurations use only what the parent C ABI already had, so the same script digests a build of the parent tree.
 The timed window and the profiled window are separate runs of the same steps: the profiling events sit between the launches."""
@@ -85,7 +91,7 @@ def model(B, K, cls, prec, opt, n_rows):
             'bytes_step': sum(by.values()), 'bytes_adam_table': adam_pass}
 
 
-def setup(name, B, NB, D, ids_h, y_h, w_h=None):
+def setup(name, B, NB, D, ids_h, y_h, w_h=None, dropout='none'):
     import torch
     from deep_ctr_amd.ipnn import IPNNEngine
     cls, K, prec, opt = CONFIGS[name]
@@ -107,7 +113,27 @@ def setup(name, B, NB, D, ids_h, y_h, w_h=None):
     torch.cuda.synchronize()
     lib, h = eng.lib, eng.h
 
+    keep = 0.5
+    wp = (lambda j: None) if w is None else (lambda j: w.data_ptr() + j * B * F * 4)
+
+    def fresh_masks():
+        """One step's masks as a caller of the mask-input entry point makes them on the device (three launches a layer)."""
+        return [(torch.rand((B, d[t]), device=eng.device) < keep).to(torch.uint8) for t in range(len(hid) + 1)]
+
     def steps_(n):
+        if dropout == 'drawn':
+            for i in range(n):
+                j = i % NB
+                eng._ck(lib.ipnn_train_step_drawn(h, ids.data_ptr() + j * B * F * 4, wp(j), y.data_ptr() + j * B * 4, B, 1234, i, None, None))
+            return
+        if dropout == 'input':
+            for i in range(n):
+                j = i % NB
+                with torch.cuda.stream(eng.stream):          # the handle's stream: the step follows the masks in order
+                    fm = fresh_masks()
+                fa = (C.c_void_p * len(fm))(*[m.data_ptr() for m in fm])
+                eng._ck(lib.ipnn_train_step_w(h, ids.data_ptr() + j * B * F * 4, wp(j), y.data_ptr() + j * B * 4, B, fa, None, None))
+            return
         for i in range(n):
             j = i % NB
             if w is None:
@@ -115,6 +141,7 @@ def setup(name, B, NB, D, ids_h, y_h, w_h=None):
             else:
                 eng._ck(lib.ipnn_train_step_w(h, ids.data_ptr() + j * B * F * 4, w.data_ptr() + j * B * F * 4, y.data_ptr() + j * B * 4,
                                               B, marr, None, None))
+    steps_.fresh_masks = fresh_masks
     return eng, steps_, (ids, y, mk, w)
 
 
@@ -128,7 +155,22 @@ def digest(eng, D):
     return h.hexdigest()
 
 
-def run(names, steps, warmup, B, prof, dig, weights='none'):
+def mask_cost_us(eng, fresh_masks, steps):
+    """Device time of making one step's masks the caller's way: HIP events around `steps` makings on the handle's stream."""
+    import torch
+    with torch.cuda.stream(eng.stream):
+        for _ in range(3):
+            fresh_masks()
+        e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+        e0.record()
+        for _ in range(steps):
+            fresh_masks()
+        e1.record()
+    e1.synchronize()
+    return e0.elapsed_time(e1) * 1e3 / steps
+
+
+def run(names, steps, warmup, B, prof, dig, weights='none', dropout='none', mask_cost=False):
     sys.path.insert(0, ROOT)
     import torch
     import deep_ctr_amd  # noqa: F401
@@ -147,7 +189,7 @@ def run(names, steps, warmup, B, prof, dig, weights='none'):
     out = {}
     for name in names:
         cls, K, prec, opt = CONFIGS[name]
-        eng, steps_, keep = setup(name, B, NB, D, ids_h, y_h, w_h)
+        eng, steps_, keep = setup(name, B, NB, D, ids_h, y_h, w_h, dropout)
         lib, h = eng.lib, eng.h
         if dig:
             steps_(steps)
@@ -162,6 +204,8 @@ def run(names, steps, warmup, B, prof, dig, weights='none'):
         eng.sync()
         dt = (time.perf_counter() - t0) / steps
         r = {'class': cls, 'k': K, 'precision': prec, 'optimizer': opt, 'us_per_step': dt * 1e6, 'examples_per_sec': B / dt}
+        if mask_cost:
+            r['caller_mask_making_us'] = mask_cost_us(eng, steps_.fresh_masks, steps)
         md = model(B, K, cls, prec, opt, D)
         if prof:
             eng._ck(lib.ipnn_prof_enable(h, 1))
@@ -187,7 +231,7 @@ def run(names, steps, warmup, B, prof, dig, weights='none'):
                           share_of_roofline=max(t_mfma, t_hbm) / dt, achieved_tflops=md['flop'] / dt / 1e12)
         out[name] = r
     return {'tool': 'ipnn_wide_bench', 'mode': 'digest' if dig else 'time', 'n_rows': D, 'fields': F, 'batch': B, 'steps': steps,
-            'weights': weights, 'numeric_fields': n_num,
+            'weights': weights, 'numeric_fields': n_num, 'dropout': dropout,
             'warmup': warmup, 'device': torch.cuda.get_device_name(0), 'configs': out}
 
 
@@ -200,6 +244,10 @@ def main():
     ap.add_argument('--fields', type=int, default=16, help='field count (2..64; more than 32: narrow rows only)')
     ap.add_argument('--weights', choices=('none', 'criteo', 'random'), default='none',
                     help='value weights of the steps (ipnn_train_step_w); none = the call without weights')
+    ap.add_argument('--dropout', choices=('none', 'input', 'drawn'), default='none',
+                    help='keep-masks of the steps: none = the resident masks of set-up (unchanged), input = the caller makes fresh '
+                         'ones every step with torch.rand, drawn = the library draws them (ipnn_train_step_drawn)')
+    ap.add_argument('--mask-cost', action='store_true', help='also time the making of one step\'s masks with torch.rand on its own')
     ap.add_argument('--no-prof', action='store_true')
     ap.add_argument('--digest', action='store_true', help='sha256 of table, layers and b after --steps steps (no timing)')
     a = ap.parse_args()
@@ -209,7 +257,7 @@ def main():
     for n in names:
         if n not in CONFIGS:
             raise SystemExit('unknown config %r (%s)' % (n, ', '.join(CONFIGS)))
-    print(json.dumps(run(names, a.steps, a.warmup, a.batch, not a.no_prof, a.digest, a.weights)))
+    print(json.dumps(run(names, a.steps, a.warmup, a.batch, not a.no_prof, a.digest, a.weights, a.dropout, a.mask_cost)))
 
 
 if __name__ == '__main__':
