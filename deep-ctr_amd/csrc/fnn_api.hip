@@ -47,6 +47,7 @@ struct fnn_handle {
     int splitk = 4;             // split-K of the weight-gradient products (measured beside scat1_body: 4 -> 40.8 us per step, 8 -> 42.9, 2 -> 51.1; fnn_create: 8 beside scat1q_body)
     int scat2_wgs = 256;        // workgroups walking the multi-chunk segments in launch 3
     int sort_merge4 = 1;        // FNN_SORT_RUNS=4 (the default on FM rows): the run sort leaves 4 runs of 1024 keys per field for the rank merge; 16 (bag mode's default): 16 runs of 256
+    int wgrad_lds = 0;          // FNN_WGRAD_FORM=lds: the bf16 weight-gradient products stage their operands through LDS (wgrad_tile; f32 and the bf16 pairs keep their register ring)
     int scat_slot = 0;          // FNN_SCAT1_FORM=slot: level 1 of the sparse-row update runs scat1_body (default: scat1q_body, quarter-columns)
     bool bf16 = false;          // FNN_PREC_BF16: 2-byte elements
     bool split = false;         // FNN_PREC_BF16X3: 4-byte elements (bs16_t), the f32 mode's layouts
@@ -320,15 +321,19 @@ void launch_step2(fnn_handle* h, bool dense, bool sparse, const float* gxp_src =
                 have_next ? 4 * h->F : 0, h->skeys, nullptr, nullptr, 0, h->sort_merge4};
     const dim3 grid(so.nblk + nwx * h->splitk + nsc);
     if (grid.x == 0) return;
-    if (h->key64) {
-        const size_t lds = sortA_lds_bytes<unsigned long long>(so.merge4);
-        if (so.merge4) hipLaunchKernelGGL((k_step2<T, unsigned long long, true>), grid, dim3(256), lds, h->st, so, wa, nwx, h->splitk, sa);
-        else hipLaunchKernelGGL((k_step2<T, unsigned long long, false>), grid, dim3(256), lds, h->st, so, wa, nwx, h->splitk, sa);
-    } else {
-        const size_t lds = sortA_lds_bytes<unsigned>(so.merge4);
-        if (so.merge4) hipLaunchKernelGGL((k_step2<T, unsigned, true>), grid, dim3(256), lds, h->st, so, wa, nwx, h->splitk, sa);
-        else hipLaunchKernelGGL((k_step2<T, unsigned, false>), grid, dim3(256), lds, h->st, so, wa, nwx, h->splitk, sa);
+    // the LDS form of the weight gradients sizes the launch's dynamic LDS for every role's workgroups
+    const bool wl = nwx > 0 && h->wgrad_lds && sizeof(T) == 2;
+    const size_t lds = std::max(h->key64 ? sortA_lds_bytes<unsigned long long>(so.merge4) : sortA_lds_bytes<unsigned>(so.merge4),
+                                wl ? WGRAD_LDS_BYTES : (size_t)0);
+#define STEP2(KT, M4, WF) hipLaunchKernelGGL((k_step2<T, KT, M4, WF>), grid, dim3(256), lds, h->st, so, wa, nwx, h->splitk, sa)
+#define STEP2_KEYS(WF) do { if (h->key64) { if (so.merge4) STEP2(unsigned long long, true, WF); else STEP2(unsigned long long, false, WF); } \
+                            else { if (so.merge4) STEP2(unsigned, true, WF); else STEP2(unsigned, false, WF); } } while (0)
+    if constexpr (sizeof(T) == 2) {
+        if (wl) { STEP2_KEYS(WGRAD_LDS); return; }
     }
+    STEP2_KEYS(WGRAD_DIRECT);
+#undef STEP2_KEYS
+#undef STEP2
 }
 
 template <typename T, bool M4>
@@ -610,7 +615,14 @@ int run_step(fnn_handle* h, const int32_t* ids, const float* y, int B, const uin
     {   // A5: dense gradients, contraction over the examples, split-K slabs
         ProfScope ps(h, "wgrad", h->st);
         const WgradArgs wa = make_wgrad_args<T>(h, Ba);
-        hipLaunchKernelGGL((k_wgrad<T>), dim3(wgrad_blocks(wa), h->splitk), dim3(256), 0, h->st, wa);
+        bool lds_form = false;
+        if constexpr (sizeof(T) == 2) {
+            if (h->wgrad_lds) {
+                hipLaunchKernelGGL((k_wgrad<T, WGRAD_LDS>), dim3(wgrad_blocks(wa), h->splitk), dim3(256), WGRAD_LDS_BYTES, h->st, wa);
+                lds_form = true;
+            }
+        }
+        if (!lds_form) hipLaunchKernelGGL((k_wgrad<T>), dim3(wgrad_blocks(wa), h->splitk), dim3(256), 0, h->st, wa);
     }
     if (train && h->step_native_dp && !dp_bucket_mode(h)) {
         // native data parallelism, slabs payload: the SAME collective as the three-launch path issues, so that a rank whose shard
@@ -847,6 +859,8 @@ int fnn_create(const fnn_cfg* cfg, fnn_handle** out)
     if (cfg->max_batch < 1 || cfg->max_batch > 16384) { g_create_err = "max_batch must be in [1, 16384] (per-field LDS sort)"; return FNN_ERR_ARG; }
     if (cfg->precision != FNN_PREC_F32 && cfg->precision != FNN_PREC_BF16 && cfg->precision != FNN_PREC_BF16X3) { g_create_err = "bad precision"; return FNN_ERR_ARG; }
     if (cfg->act < 0 || cfg->act > 2) { g_create_err = "bad act"; return FNN_ERR_ARG; }
+    const int wgrad_form = wgrad_form_env();
+    if (wgrad_form == -2) { g_create_err = "FNN_WGRAD_FORM must be direct or lds"; return FNN_ERR_ARG; }
     int ndev = 0;
     hipError_t e = hipGetDeviceCount(&ndev);
     if (e != hipSuccess || ndev <= 0) {
@@ -884,7 +898,19 @@ int fnn_create(const fnn_cfg* cfg, fnn_handle** out)
     // step against 38.4 with four, f32 57.1 against 61.4; the bf16 pairs 46.9 against 45.1 and stay at four; beside the
     // slot-per-lane role eight are slower: 39.8 against 39.1) -- profiles/scat1_forms_ab.json
     // (handles whose every step of up to 4096 examples takes the three launches; the layer-by-layer kernels keep four)
-    if (h->fused && mlp_shape_ok(h) && !h->bag && !h->scat_slot && !h->split && h->Bmax <= SORT_N) h->splitk = 8;
+    const bool steps3 = h->fused && mlp_shape_ok(h) && !h->bag && !h->scat_slot && !h->split && h->Bmax <= SORT_N;
+    if (steps3) h->splitk = 8;
+    // FNN_WGRAD_FORM: the bf16 weight gradients through LDS (wgrad_tile) are 2.8 us shorter alone (role time 11.8 -> 9.0 us) but
+    // leave launch 2 beside the scatter role where it was (33.8 us per step either way); what they buy is split-K 4 again, which
+    // the direct form cannot afford (its role alone is as long as the launch): half the role's workgroups beside the scatter
+    // chain and half the slabs in launch 3 -- 33.6 -> 32.3 us per step, k_step2 12.7 -> 11.0 us (profiles/wgrad_lds_ab.json).
+    // The default on the same handles as above in bf16, where a slice of the handle's largest batch at split-K 4 holds a whole
+    // stage (max_batch > 256; smaller handles keep the direct form at split-K 8: the bit-equality test of the two scatter forms
+    // pins that split there, though batch 256 measured 25.4 -> 24.4 us).  Bag mode keeps the direct form (the SNN step:
+    // 47.7 against 48.3 us with lds).  An explicit FNN_WGRAD_FORM=lds takes the form anywhere in bf16 and moves no split-K.
+    const bool lds_dflt = steps3 && h->bf16 && h->ldT / 4 / Traits<bf16_t>::KS >= WGRAD_LDS_S;
+    h->wgrad_lds = wgrad_form == WGRAD_LDS || (wgrad_form == -1 && lds_dflt) ? 1 : 0;
+    if (wgrad_form == -1 && lds_dflt) h->splitk = 4;
     if (const char* ev = getenv("FNN_SPLITK")) { const int v = atoi(ev); if (v == 2 || v == 4 || v == 8 || v == 16) h->splitk = v; }   // tuning knob
     if (const char* ev = getenv("FNN_SCAT2_WGS")) { const int v = atoi(ev); if (v >= 16 && v <= 1024) h->scat2_wgs = v; }
     const size_t ts = tsize(h), Ba = h->ldT;

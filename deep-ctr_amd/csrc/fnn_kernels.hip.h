@@ -880,9 +880,26 @@ static __global__ __launch_bounds__(256) void k_gemm_lds(const T* __restrict__ A
 struct WgradProb { const void* A; const void* B; float* out; int mt, nt, ldo; };   // mt, nt: 64-blocks
 struct WgradArgs { WgradProb p[4]; int ldT, klen; size_t zstride; };      // p[3]: bag-bias gradient (mt = 0 if unused)
 
-template <typename T>
+// FORM (FNN_WGRAD_FORM=direct|lds, read where a handle is created): WGRAD_DIRECT -- every wave loads its A fragment and the
+// block's four B fragments from global memory into registers; WGRAD_LDS (the 2-byte element type only; the 4-byte types keep
+// their register ring whatever FORM says) -- the workgroup stages the slice through LDS: per k-step its four A and four B
+// fragments, 8 KiB, each fragment copied once by global_load_lds_dwordx4 (wave w: A fragment w, B fragment w) and lane-linear
+// in LDS as in global memory, so that a wave's read-back is one conflict-free ds_read_b128 per fragment (a 16-lane group
+// covers one 256-byte bank row).  A stage is WGRAD_LDS_S k-steps; the 64 KiB hold WGRAD_LDS_NB stages, all requested before
+// the first wait, and a stage is requested again as soon as every wave has read it (raw barriers: the loads in flight stay
+// in flight).  k-steps past the end of a slice re-read its last one into slots nobody multiplies, which keeps the counted
+// waits constant.  The products are the direct form's, in its order, into its accumulators: the slabs are bit-identical.
+constexpr int WGRAD_DIRECT = 0, WGRAD_LDS = 1;
+#ifndef FNN_WGRAD_LDS_S
+#define FNN_WGRAD_LDS_S 4
+#endif
+constexpr int WGRAD_LDS_S = FNN_WGRAD_LDS_S, WGRAD_LDS_NB = 8 / WGRAD_LDS_S;
+static_assert(WGRAD_LDS_S == 4 || WGRAD_LDS_S == 8, "a stage is 4 k-steps (two buffers) or 8 (one)");
+constexpr size_t WGRAD_LDS_BYTES = (size_t)WGRAD_LDS_S * WGRAD_LDS_NB * 8192;      // two workgroups of launch 2 share a CU's 160 KiB
+
+template <typename T, int FORM = WGRAD_DIRECT>
 __device__ __forceinline__ void wgrad_tile(const WgradProb& pr, const int b, const int by, const int ldT,
-                                           const int klen, const size_t zstride)
+                                           const int klen, const size_t zstride, unsigned char* smem)
 {
     typedef typename Traits<T>::frag frag;
     constexpr int KS = Traits<T>::KS;
@@ -949,6 +966,61 @@ __device__ __forceinline__ void wgrad_tile(const WgradProb& pr, const int b, con
             }
         }
         }
+    } else if constexpr (FORM == WGRAD_LDS) {
+        constexpr int S = WGRAD_LDS_S, NB = WGRAD_LDS_NB, EPL = Traits<T>::EPL;
+        const int nst = (nkt + S - 1) / S;
+        const T* srcA = ft_frag<T>(A, rt, kt0, nkt_all, lane);
+        const T* srcB = ft_frag<T>(B, ct0 + wave, kt0, nkt_all, lane);
+        auto stage = [&](const int s) {                        // stage s -> buffer s % NB; this wave's two fragments of each k-step
+            unsigned char* buf = smem + (size_t)(s % NB) * (S * 8192) + (size_t)wave * 1024;
+#pragma unroll
+            for (int j = 0; j < S; ++j) {
+                const size_t k = (size_t)min(s * S + j, nkt - 1) * 64 * EPL;
+                __builtin_amdgcn_global_load_lds((const __attribute__((address_space(1))) void*)(srcA + k),
+                                                 (__attribute__((address_space(3))) void*)(buf + j * 8192), 16, 0, 0);
+                __builtin_amdgcn_global_load_lds((const __attribute__((address_space(1))) void*)(srcB + k),
+                                                 (__attribute__((address_space(3))) void*)(buf + j * 8192 + 4096), 16, 0, 0);
+            }
+        };
+        for (int s = 0; s < min(NB, nst); ++s) stage(s);
+        for (int s = 0; s < nst; ++s) {
+            // outstanding: stage s and, with two buffers, stage s + 1 behind it (2 S loads of this wave)
+            if (NB > 1 && s + 1 < nst) wait_vmcnt<2 * S>(); else wait_vmcnt<0>();
+            __builtin_amdgcn_s_barrier();                                       // every wave's part of stage s has landed
+            asm volatile("" ::: "memory");
+            const unsigned char* buf = smem + (size_t)(s % NB) * (S * 8192) + lane * 16;
+            auto kstep = [&](const int j) {
+                const frag af = *reinterpret_cast<const frag*>(buf + j * 8192 + wave * 1024);
+#pragma unroll
+                for (int n = 0; n < 4; ++n) {
+                    const frag bf = *reinterpret_cast<const frag*>(buf + j * 8192 + 4096 + n * 1024);
+                    mma(acc[n], af, bf);
+                }
+            };
+            const int ns = min(S, nkt - s * S);
+            if (ns == S) {
+                // a whole stage, four k-steps at a time: all 20 reads issued, then the products behind counted waits (left to
+                // itself the compiler, at this launch's register budget, waits for every second read: 8 LDS round trips per stage)
+#pragma unroll
+                for (int j0 = 0; j0 < S; j0 += 4) {
+                    frag fa[4], fb[4][4];
+#pragma unroll
+                    for (int j = 0; j < 4; ++j) {
+                        fa[j] = *reinterpret_cast<const frag*>(buf + (j0 + j) * 8192 + wave * 1024);
+#pragma unroll
+                        for (int n = 0; n < 4; ++n) fb[j][n] = *reinterpret_cast<const frag*>(buf + (j0 + j) * 8192 + 4096 + n * 1024);
+                    }
+                    __builtin_amdgcn_sched_barrier(0);
+#pragma unroll
+                    for (int j = 0; j < 4; ++j)
+#pragma unroll
+                        for (int n = 0; n < 4; ++n) mma(acc[n], fa[j], fb[j][n]);
+                }
+            } else {
+                for (int j = 0; j < ns; ++j) kstep(j);
+            }
+            if (s + NB < nst) { lds_barrier(); stage(s + NB); }                 // every wave has read the buffer: request it again
+        }
     } else {
 #pragma unroll 4
     for (int kt = 0; kt < nkt; ++kt) {
@@ -971,18 +1043,32 @@ __device__ __forceinline__ void wgrad_tile(const WgradProb& pr, const int b, con
 }
 
 // the product is picked with constant indices into the argument struct (a runtime index spills it)
-template <typename T>
-__device__ __forceinline__ void wgrad_body(const WgradArgs& a, const int bx, const int by)
+template <typename T, int FORM = WGRAD_DIRECT>
+__device__ __forceinline__ void wgrad_body(const WgradArgs& a, const int bx, const int by, unsigned char* smem)
 {
+    constexpr int WF = sizeof(T) == 2 ? FORM : WGRAD_DIRECT;
     const int n0 = a.p[0].mt * a.p[0].nt, n1 = a.p[1].mt * a.p[1].nt, n2 = a.p[2].mt * a.p[2].nt;
-    if (bx < n0) wgrad_tile<T>(a.p[0], bx, by, a.ldT, a.klen, a.zstride);
-    else if (bx < n0 + n1) wgrad_tile<T>(a.p[1], bx - n0, by, a.ldT, a.klen, a.zstride);
-    else if (bx < n0 + n1 + n2) wgrad_tile<T>(a.p[2], bx - n0 - n1, by, a.ldT, a.klen, a.zstride);
-    else wgrad_tile<T>(a.p[3], bx - n0 - n1 - n2, by, a.ldT, a.klen, a.zstride);
+    if (bx < n0) wgrad_tile<T, WF>(a.p[0], bx, by, a.ldT, a.klen, a.zstride, smem);
+    else if (bx < n0 + n1) wgrad_tile<T, WF>(a.p[1], bx - n0, by, a.ldT, a.klen, a.zstride, smem);
+    else if (bx < n0 + n1 + n2) wgrad_tile<T, WF>(a.p[2], bx - n0 - n1, by, a.ldT, a.klen, a.zstride, smem);
+    else wgrad_tile<T, WF>(a.p[3], bx - n0 - n1 - n2, by, a.ldT, a.klen, a.zstride, smem);
 }
 
-template <typename T>
-static __global__ __launch_bounds__(256) void k_wgrad(const WgradArgs a) { wgrad_body<T>(a, blockIdx.x, blockIdx.y); }
+// dynamic LDS: WGRAD_LDS_BYTES for the LDS form, none for the direct one
+template <typename T, int FORM = WGRAD_DIRECT>
+static __global__ __launch_bounds__(256) void k_wgrad(const WgradArgs a)
+{
+    extern __shared__ __align__(16) unsigned char smem[];
+    wgrad_body<T, FORM>(a, blockIdx.x, blockIdx.y, smem);
+}
+
+// FNN_WGRAD_FORM=direct|lds, read where a handle is created.  -1: unset (the handle's own default), -2: any other value
+inline int wgrad_form_env()
+{
+    const char* e = getenv("FNN_WGRAD_FORM");
+    if (!e) return -1;
+    return !strcmp(e, "direct") ? WGRAD_DIRECT : (!strcmp(e, "lds") ? WGRAD_LDS : -2);
+}
 
 // ------------------------------------------------------------------------------------------
 // Fused MLP strip kernel: A3 gather -> A4 forward -> loss -> A5 backward-data for 16 examples per

@@ -279,7 +279,8 @@ static __global__ __launch_bounds__(64 * NW) void k_step1(const MlpArgs<T> a)
 // ------------------------------------------------------------------------------------------
 // step 2: run-sorts of the NEXT batch's keys  U  weight gradients  U  sparse-row SGD level 1
 // ------------------------------------------------------------------------------------------
-template <typename T, typename KT, bool M4>
+// WF: the form of the weight-gradient role (WGRAD_LDS: WGRAD_LDS_BYTES of dynamic LDS for the whole launch; bf16 only)
+template <typename T, typename KT, bool M4, int WF = WGRAD_DIRECT>
 static __global__ __launch_bounds__(256) void k_step2(const SortArgs so, const WgradArgs wa, const int nwx,
                                                const int splitk, const ScatArgs sa)
 {
@@ -295,7 +296,7 @@ static __global__ __launch_bounds__(256) void k_step2(const SortArgs so, const W
             const int cls = w & 7, k = w >> 3, qd = nw >> 3, rm = nw & 7;
             w = (cls < rm ? cls * (qd + 1) : rm * (qd + 1) + (cls - rm) * qd) + k;
         }
-        wgrad_body<T>(wa, w % nwx, w / nwx);
+        wgrad_body<T, WF>(wa, w % nwx, w / nwx, smem);
     }
     // (the scatter role's blocks dealt BEFORE the weight gradients', so that their chain starts while those are still being
     // placed, measured level: 39.06 / 38.53 / 39.01 us per step against 38.45 / 39.17 / 39.03 behind them -- they stay behind)
