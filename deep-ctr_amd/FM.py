@@ -140,7 +140,8 @@ class FM(object):
         return out
 
     def evaluate(self, ids, y, wts=None):
-        """Predictions and (auc, rmse, logloss) on the device (fm_eval_w): exact AUC, ties at 1/2; wts as in train_step."""
+        """Predictions and (auc, rmse, logloss) on the device (fm_eval_w): exact AUC, ties at 1/2; wts as in train_step.
+        y: 0 / non-zero.  FNNError(FNN_ERR_RANGE) for one class only and for any prediction NaN or outside [0, 1]."""
         torch = self._torch
         ids_t, y_t = self._dev(ids, torch.int32), self._dev(y, torch.int32)
         w_t = self._wts(wts, ids_t)

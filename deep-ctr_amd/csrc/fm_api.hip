@@ -810,7 +810,7 @@ int fm_eval_w(fm_handle* h, const int32_t* ids, const float* wts, const int32_t*
     if (logloss) *logloss = out[2];
     const int rc = fm_sync(h);
     if (rc != FNN_OK) return rc;
-    if (mrc == -2) MFAIL(h, FNN_ERR_RANGE, merr);
+    if (mrc == -2 || mrc == -3) MFAIL(h, FNN_ERR_RANGE, merr);
     return FNN_OK;
 }
 

@@ -1659,7 +1659,7 @@ int fnn_eval(fnn_handle* h, const int32_t* ids, const int32_t* y, int64_t N, int
     if (logloss) *logloss = out[2];
     rc = check_async(h);
     if (rc != FNN_OK) return rc;
-    if (mrc == -2) FAIL(h, FNN_ERR_RANGE, merr);
+    if (mrc == -2 || mrc == -3) FAIL(h, FNN_ERR_RANGE, merr);
     return FNN_OK;
 }
 

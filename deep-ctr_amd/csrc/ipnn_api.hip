@@ -2512,7 +2512,7 @@ int ipnn_eval_w(ipnn_handle* h, const int32_t* ids, const float* wts, const int3
     if (logloss) *logloss = out[2];
     const int rc = ipnn_sync(h);
     if (rc != FNN_OK) return rc;
-    if (mrc == -2) IFAIL(h, FNN_ERR_RANGE, merr);
+    if (mrc == -2 || mrc == -3) IFAIL(h, FNN_ERR_RANGE, merr);
     return FNN_OK;
 }
 

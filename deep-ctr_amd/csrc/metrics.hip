@@ -8,6 +8,8 @@
 // statistic with ties counted 1/2, which is what the trapezoid rule over distinct thresholds gives.
 // The sums are 64-bit integer atomics: order-independent, bitwise reproducible.  RMSE and logloss
 // accumulate in f64 with a fixed-shape tree per block and a fixed-order sum of the block partials.
+// A prediction outside [0, 1] (NaN included) has no key -- the key drops the sign, a NaN's bits sort above every finite p -- and
+// fmax(NaN, eps) = eps would give it a finite logloss term: such predictions are counted, and device_metrics reports them (-3).
 // The key sort of the METRIC pass is rocPRIM's device radix sort (a library sort for the metric pass; no hot-path
 // kernel goes through a library).  The groupings of the update paths use this file's own radix sort.
 #include "metrics.hip.h"
@@ -26,10 +28,10 @@ constexpr int ITEMS = 8;         // examples per thread
 
 __global__ __launch_bounds__(MB) void k_metric_keys(const float* __restrict__ p, const int32_t* __restrict__ y, int64_t n,
                                                     uint32_t* __restrict__ keys, double* __restrict__ part /*[nblk][2]*/,
-                                                    unsigned long long* __restrict__ n_pos)
+                                                    unsigned long long* __restrict__ cnt /*[0] n_pos, [1] n_bad*/)
 {
     __shared__ double s_se[MB], s_ll[MB];
-    __shared__ unsigned s_np;
+    __shared__ unsigned s_np;                               // positives | predictions outside [0, 1] << 16 (a block holds 2,048 examples)
     if (threadIdx.x == 0) s_np = 0;
     __syncthreads();
     const double eps = 2.220446049250313e-16;
@@ -46,7 +48,7 @@ __global__ __launch_bounds__(MB) void k_metric_keys(const float* __restrict__ p,
             se += (yd - pd) * (yd - pd);
             const double pc = fmin(fmax(pd, eps), 1.0 - eps);
             ll -= pos ? log(pc) : log(1.0 - pc);
-            np_ += pos ? 1u : 0u;
+            np_ += (pos ? 1u : 0u) + (!(pf >= 0.f && pf <= 1.f) ? 1u << 16 : 0u);
         }
     }
     s_se[threadIdx.x] = se; s_ll[threadIdx.x] = ll;
@@ -58,7 +60,8 @@ __global__ __launch_bounds__(MB) void k_metric_keys(const float* __restrict__ p,
     }
     if (threadIdx.x == 0) {
         part[2 * (size_t)blockIdx.x] = s_se[0]; part[2 * (size_t)blockIdx.x + 1] = s_ll[0];
-        if (s_np) atomicAdd(n_pos, (unsigned long long)s_np);
+        if (s_np & 0xFFFFu) atomicAdd(cnt, (unsigned long long)(s_np & 0xFFFFu));
+        if (s_np >> 16) atomicAdd(cnt + 1, (unsigned long long)(s_np >> 16));
     }
 }
 
@@ -288,30 +291,36 @@ int device_metrics(hipStream_t st, const float* p, const int32_t* y, int64_t n, 
     size_t tmp_bytes = 0;
     const int64_t nblk = (n + (int64_t)MB * ITEMS - 1) / ((int64_t)MB * ITEMS);
     std::vector<double> hp((size_t)nblk * 2);
-    unsigned long long hc[2] = {0, 0};
+    unsigned long long hc[3] = {0, 0, 0};                       // n_pos, predictions outside [0, 1], the AUC's integer sum
     if (n < 1 || n > (int64_t)1 << 31) { err = "n outside [1, 2^31]"; return -1; }
     MK(hipMalloc((void**)&keys, (size_t)n * 4)); MK(hipMalloc((void**)&sorted, (size_t)n * 4));
-    MK(hipMalloc((void**)&part, (size_t)nblk * 16)); MK(hipMalloc((void**)&cnt, 16));
-    MK(hipMemsetAsync(cnt, 0, 16, st));
+    MK(hipMalloc((void**)&part, (size_t)nblk * 16)); MK(hipMalloc((void**)&cnt, 24));
+    MK(hipMemsetAsync(cnt, 0, 24, st));
     hipLaunchKernelGGL(k_metric_keys, dim3((unsigned)nblk), dim3(MB), 0, st, p, y, n, keys, part, cnt);
     MK(rocprim::radix_sort_keys(nullptr, tmp_bytes, keys, sorted, (size_t)n, 0, 32, st));
     MK(hipMalloc(&tmp, tmp_bytes ? tmp_bytes : 16));
     MK(rocprim::radix_sort_keys(tmp, tmp_bytes, keys, sorted, (size_t)n, 0, 32, st));
-    MK(hipMemcpyAsync(hc, cnt, 8, hipMemcpyDeviceToHost, st));
+    MK(hipMemcpyAsync(hc, cnt, 16, hipMemcpyDeviceToHost, st));
     MK(hipStreamSynchronize(st));
     {
         const int64_t n_pos = (int64_t)hc[0], n_neg = n - n_pos;
+        if (hc[1]) {
+            out[0] = out[1] = out[2] = std::nan(""); out[3] = (double)n_pos;
+            err = std::to_string(hc[1]) + " of " + std::to_string(n) + " predictions are NaN or outside [0, 1] (roc_auc_score / log_loss raise ValueError)";
+            rc = -3;
+            goto done;
+        }
         if (n_pos > 0 && n_neg > 0) {
             const int64_t want = (n_pos + MB - 1) / MB;
-            hipLaunchKernelGGL(k_metric_auc, dim3((unsigned)(want < 2048 ? want : 2048)), dim3(MB), 0, st, sorted, n, n_neg, cnt + 1);
+            hipLaunchKernelGGL(k_metric_auc, dim3((unsigned)(want < 2048 ? want : 2048)), dim3(MB), 0, st, sorted, n, n_neg, cnt + 2);
         }
-        MK(hipMemcpyAsync(hc + 1, cnt + 1, 8, hipMemcpyDeviceToHost, st));
+        MK(hipMemcpyAsync(hc + 2, cnt + 2, 8, hipMemcpyDeviceToHost, st));
         MK(hipMemcpyAsync(hp.data(), part, (size_t)nblk * 16, hipMemcpyDeviceToHost, st));
         MK(hipStreamSynchronize(st));
         double se = 0.0, ll = 0.0;
         for (int64_t b = 0; b < nblk; ++b) { se += hp[2 * b]; ll += hp[2 * b + 1]; }
         out[1] = std::sqrt(se / (double)n); out[2] = ll / (double)n; out[3] = (double)n_pos;
-        if (n_pos > 0 && n_neg > 0) { out[0] = (double)hc[1] / (2.0 * (double)n_pos * (double)n_neg); rc = 0; }
+        if (n_pos > 0 && n_neg > 0) { out[0] = (double)hc[2] / (2.0 * (double)n_pos * (double)n_neg); rc = 0; }
         else { out[0] = std::nan(""); err = "only one class present in y (roc_auc_score raises ValueError)"; rc = -2; }
     }
 done:

@@ -9,7 +9,9 @@ namespace fnn {
 // (sklearn.metrics.log_loss: p clipped to [eps, 1 - eps], eps = 2^-52) of p [n] against labels
 // y [n] (0 / non-zero), both DEVICE pointers.  out = {auc, rmse, logloss, n_pos}.  Synchronises `st`.
 // Returns 0, -1 on a HIP error (err set), -2 when only one class is present (auc undefined; the
-// other two are still written).
+// other two are still written), -3 when any prediction is NaN or outside [0, 1] (err set to a message with
+// their number; all three metrics are NaN, as roc_auc_score and log_loss raise ValueError on such input;
+// this outranks -2).  y: 0 is the negative class, EVERY other int32 the positive one.
 int device_metrics(hipStream_t st, const float* p, const int32_t* y, int64_t n, double out[4], std::string& err);
 
 // Grouping of a GLOBAL batch for the exact data-parallel mode (fnn_step_scatter_global beyond the 16,384 keys the one-workgroup

@@ -405,8 +405,8 @@ class FNNEngine(object):
 
     def evaluate(self, ids, y, want_p=False):
         """A10 (python/FNN_wnzh.py:193-221): predict every example and compute AUC / RMSE / logloss
-        on the device (fnn_eval).  Returns {'auc', 'rmse', 'logloss'[, 'p']}.  One class only ->
-        FNNError(FNN_ERR_RANGE), as roc_auc_score raises."""
+        on the device (fnn_eval).  Returns {'auc', 'rmse', 'logloss'[, 'p']}.  y: 0 / non-zero.  One class only, or any
+        prediction NaN or outside [0, 1] (a diverged model) -> FNNError(FNN_ERR_RANGE), as roc_auc_score / log_loss raise."""
         torch = self._torch
         ids_t, y_t = self._dev(ids, torch.int32), self._dev(y, torch.int32)
         n = ids_t.shape[0]

@@ -194,7 +194,8 @@ class IPNNEngine(object):
         return out
 
     def evaluate(self, ids, y, wts=None):
-        """python/baseline.py:382-437: predictions + AUC / RMSE / logloss on the device (ipnn_eval / ipnn_eval_w)."""
+        """python/baseline.py:382-437: predictions + AUC / RMSE / logloss on the device (ipnn_eval / ipnn_eval_w).
+        y: 0 / non-zero.  FNNError(FNN_ERR_RANGE) for one class only and for any prediction NaN or outside [0, 1]."""
         torch = self._torch
         ids_t, y_t = self._dev(ids, torch.int32), self._dev(y, torch.int32)
         wts_t = self._wts(wts, ids_t)

@@ -100,7 +100,8 @@ int fm_set_optimizer(fm_handle* h, int optimizer, float beta1, float beta2, floa
 int fm_get_opt_state(fm_handle* h, float* s0, float* s1, float* sb, int64_t* t);
 /* DEVICE pointers ids [N, F], y [N] (0 / non-zero).  Predictions in chunks of max_batch, then exact AUC (ties at 1/2),
  * RMSE and logloss (p clipped to [2^-52, 1 - 2^-52]) on the device.  Outputs nullable.  FNN_ERR_RANGE when y holds one
- * class only (auc undefined; rmse and logloss are still written). */
+ * class only (auc undefined; rmse and logloss are still written), and when any prediction is NaN or outside [0, 1] (a diverged
+ * model; all three outputs are then NaN and fm_last_error gives their number). */
 int fm_eval(fm_handle* h, const int32_t* ids, const int32_t* y, int64_t N, double* auc, double* rmse, double* logloss);
 int fm_eval_w(fm_handle* h, const int32_t* ids, const float* wts, const int32_t* y, int64_t N,
               double* auc, double* rmse, double* logloss);

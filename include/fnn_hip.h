@@ -273,7 +273,9 @@ int fnn_predict(fnn_handle* h, const int32_t* ids, int B, float* p_out, int memk
  * roc_auc_score, sqrt(mean_squared_error) and log_loss (python/baseline.py:427-429) on the device.
  * ids [N, F] int32, y [N] int32 labels; p_out [N] float32 or NULL; metrics are HOST doubles.
  * Only one class in y: FNN_ERR_RANGE (the reference's roc_auc_score raises ValueError); rmse and
- * logloss are still written. */
+ * logloss are still written.  Any prediction NaN or outside [0, 1] (a diverged model): FNN_ERR_RANGE too
+ * (roc_auc_score and log_loss raise ValueError), all three metrics NaN, their number in fnn_last_error;
+ * p_out is still written.  y: 0 is the negative class, every other value the positive one. */
 int fnn_eval(fnn_handle* h, const int32_t* ids, const int32_t* y, int64_t N, int memkind,
              double* auc, double* rmse, double* logloss, float* p_out);
 

@@ -133,7 +133,8 @@ int ipnn_draw_masks(ipnn_handle* h, uint64_t seed, uint64_t step, int B, uint8_t
 
 /* Evaluation pass (python/baseline.py:382-437 `test`): predict all N examples (DEVICE ids [N, F]
  * int32, y [N] int32; chunks of max_batch), then AUC / RMSE / logloss on the device.  Metrics are
- * HOST doubles.  One class only: FNN_ERR_RANGE. */
+ * HOST doubles.  y: 0 / non-zero.  One class only: FNN_ERR_RANGE (rmse and logloss are still written).  Any prediction NaN or
+ * outside [0, 1] (a diverged model): FNN_ERR_RANGE, all three metrics NaN, their number in ipnn_last_error. */
 int ipnn_eval(ipnn_handle* h, const int32_t* ids, const int32_t* y, int64_t N, double* auc, double* rmse, double* logloss);
 int ipnn_eval_w(ipnn_handle* h, const int32_t* ids, const float* wts, const int32_t* y, int64_t N,
                 double* auc, double* rmse, double* logloss);
