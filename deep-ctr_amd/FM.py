@@ -81,6 +81,7 @@ class FM(object):
     def set_params(self, rows, b):
         t = np.ascontiguousarray(rows, dtype=np.float32)
         self._ck(self.lib.fm_set_table(self.h, t.ctypes.data, t.shape[0]))
+        self.X_dim = t.shape[0]                  # get_params / get_opt_state size their buffers by it: fm_get_table writes n_rows rows
         self._ck(self.lib.fm_set_b(self.h, float(b)))
 
     def get_params(self):

@@ -2327,7 +2327,16 @@ int ipnn_set_table(ipnn_handle* h, const float* rows, int64_t n_rows)
             IHK(h, hipMalloc((void**)p, n * 4));
             IHK(h, hipMemset(*p, 0, n * 4));
         }
-        if (h->ftrl) { hipLaunchKernelGGL(k_fill_f32, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, h->st, h->tm, n, 0.1f); IHK(h, hipStreamSynchronize(h->st)); }
+        if (h->ftrl) hipLaunchKernelGGL(k_fill_f32, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, h->st, h->tm, n, 0.1f);
+        // the optimiser restarts as a whole (as fm_set_table does): every dense layer's and b's state as ipnn_create left them
+        for (int t = 1; t <= h->L + 1; ++t) {
+            const size_t nd = (size_t)h->Dp[t - 1] * h->Dp[t];
+            IHK(h, hipMemsetAsync(h->Wm[t - 1], 0, nd * 4, h->st)); IHK(h, hipMemsetAsync(h->Wv[t - 1], 0, nd * 4, h->st));
+            if (h->ftrl) hipLaunchKernelGGL(k_fill_f32, dim3((unsigned)((nd + 255) / 256)), dim3(256), 0, h->st, h->Wm[t - 1], nd, 0.1f);
+        }
+        IHK(h, hipMemsetAsync(h->bmv, 0, 8, h->st));
+        if (h->ftrl) hipLaunchKernelGGL(k_fill_f32, dim3(1), dim3(64), 0, h->st, h->bmv, (size_t)1, 0.1f);
+        IHK(h, hipStreamSynchronize(h->st));
         h->adam_t = 0;
     }
     return FNN_OK;

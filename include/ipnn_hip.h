@@ -82,7 +82,10 @@ int ipnn_create(const ipnn_cfg* cfg, ipnn_handle** out);
 int ipnn_destroy(ipnn_handle* h);
 int ipnn_sync(ipnn_handle* h);
 
-/* HOST pointers.  table rows [n_rows, K] = concat(W, V) (fm_wv, :66); b: the scalar `fm_b`. */
+/* HOST pointers.  table rows [n_rows, K] = concat(W, V) (fm_wv, :66); b: the scalar `fm_b`.
+ * Under Adam / FTRL, ipnn_set_table restarts the optimiser as fm_set_table does: the state of the table, of every dense layer
+ * and of b goes back to what ipnn_create left (Adam: m = v = 0; FTRL: accum = 0.1, linear = 0) and the step count to 0; n_rows
+ * may differ from the last call's.  ipnn_set_layer and ipnn_set_b replace values only and leave the optimiser's state alone. */
 int ipnn_set_table(ipnn_handle* h, const float* rows, int64_t n_rows);
 int ipnn_get_rows(ipnn_handle* h, const int64_t* row_ids, int64_t n, float* out);
 int ipnn_set_b(ipnn_handle* h, float b);
