@@ -48,7 +48,7 @@ struct fnn_handle {
     int scat2_wgs = 256;        // workgroups walking the multi-chunk segments in launch 3
     int sort_merge4 = 1;        // FNN_SORT_RUNS=4 (the default on FM rows): the run sort leaves 4 runs of 1024 keys per field for the rank merge; 16 (bag mode's default): 16 runs of 256
     int wgrad_lds = 0;          // FNN_WGRAD_FORM=lds: the bf16 weight-gradient products stage their operands through LDS (wgrad_tile; f32 and the bf16 pairs keep their register ring)
-    int scat_slot = 0;          // FNN_SCAT1_FORM=slot: level 1 of the sparse-row update runs scat1_body (default: scat1q_body, quarter-columns)
+    int scat_form = SCAT1_HALF;      // FNN_SCAT1_FORM: the body of level 1 of the sparse-row update (scat1h_body; quarter: scat1q_body, slot: scat1_body)
     bool bf16 = false;          // FNN_PREC_BF16: 2-byte elements
     bool split = false;         // FNN_PREC_BF16X3: 4-byte elements (bs16_t), the f32 mode's layouts
     int step1_waves = 8;                                               // FNN_STEP1_WAVES=4: four waves per strip (the 2-byte element types at hidden 300 / 100 run eight)
@@ -316,7 +316,7 @@ void launch_step2(fnn_handle* h, bool dense, bool sparse, const float* gxp_src =
     const WgradArgs wa = make_wgrad_args<T>(h, Ba);
     const int nwx = dense ? wgrad_blocks(wa) : 0;
     const int nsc = !sparse ? 0 : (h->bag ? (int)(((size_t)h->F * (SORT_N / WCH) * (h->rw / 4) + 255) / 256)
-                                          : scat1_blocks(sa, h->scat_slot));
+                                          : scat1_blocks(sa, h->scat_form));
     SortArgs so{h->next_ids, h->next_B, h->F, h->n_rows, h->slot[nxt].rec, h->slot[nxt].owner_cnt,
                 have_next ? 4 * h->F : 0, h->skeys, nullptr, nullptr, 0, h->sort_merge4};
     const dim3 grid(so.nblk + nwx * h->splitk + nsc);
@@ -658,7 +658,7 @@ int run_step(fnn_handle* h, const int32_t* ids, const float* y, int B, const uin
     }
     {
         ProfScope ps(h, "scatter", h->st);
-        const int nblk = scat1_blocks(sa, h->scat_slot);     // a thread per live quarter-column of a chunk of 16 entries (or 16 lanes per chunk)
+        const int nblk = scat1_blocks(sa, h->scat_form);     // a thread per live quarter-column of a chunk of 16 entries (or 16 lanes per chunk)
         hipLaunchKernelGGL(k_scat1, dim3(nblk), dim3(256), 0, h->st, sa);
     }
     {
@@ -728,7 +728,7 @@ int scatter_global_impl(fnn_handle* h, const int32_t* ids_g, const float* gxp_g,
         ProfScope ps(h, "scatter_global", h->st);
         ScatArgs sa = make_scat_args(h, sl, N2);
         sa.gxp = gxp_g;
-        const int nblk = scat1_blocks(sa, h->scat_slot);     // after sa.gxp changed: the caller's buffer may not be 16-byte aligned
+        const int nblk = scat1_blocks(sa, h->scat_form);     // after sa.gxp changed: the caller's buffer may not be 16-byte aligned
         hipLaunchKernelGGL(k_scat1, dim3(nblk), dim3(256), 0, h->st, sa);
         hipLaunchKernelGGL(k_scat2, dim3(N2 > 4096 ? 256 : 64), dim3(256), 0, h->st, sa);
     }
@@ -843,6 +843,12 @@ uint64_t fnn_cfg_size(void) { return (uint64_t)sizeof(fnn_cfg); }
 
 const char* fnn_last_error(const fnn_handle* h) { return h ? h->err.c_str() : g_create_err.c_str(); }
 
+const char* fnn_scat1_form(void)
+{
+    const int f = scat1_form_env(-1);
+    return f == SCAT1_SLOT ? "slot" : f == SCAT1_QUARTER ? "quarter" : f == SCAT1_HALF ? "half" : "default";
+}
+
 int fnn_create(const fnn_cfg* cfg, fnn_handle** out)
 {
     if (!cfg || !out) { g_create_err = "null argument"; return FNN_ERR_ARG; }
@@ -892,13 +898,15 @@ int fnn_create(const fnn_cfg* cfg, fnn_handle** out)
     h->bf16 = cfg->precision == FNN_PREC_BF16; h->split = cfg->precision == FNN_PREC_BF16X3;
     if (const char* ev = getenv("FNN_NO_FUSE")) h->fused = !(ev[0] == '1');
     if (const char* ev = getenv("FNN_ROLE_OFF")) h->role_off = atoi(ev);
-    h->scat_slot = scat1_form_env();
+    h->scat_form = scat1_form_env();
     h->sort_merge4 = sort_merge4_env(h->bag ? 0 : 1);
     // the quarter-column scatter role leaves launch 2 the residency for eight K slices of the weight gradients (bf16 37.4 us per
     // step against 38.4 with four, f32 57.1 against 61.4; the bf16 pairs 46.9 against 45.1 and stay at four; beside the
     // slot-per-lane role eight are slower: 39.8 against 39.1) -- profiles/scat1_forms_ab.json
     // (handles whose every step of up to 4096 examples takes the three launches; the layer-by-layer kernels keep four)
-    const bool steps3 = h->fused && mlp_shape_ok(h) && !h->bag && !h->scat_slot && !h->split && h->Bmax <= SORT_N;
+    // (beside the half-chunk role, scat1h_body, the splits stay as they are: bf16 with the LDS form 31.3 us per step at eight
+    // slices against 29.8 at four -- profiles/scat1_half_ab.json)
+    const bool steps3 = h->fused && mlp_shape_ok(h) && !h->bag && h->scat_form != SCAT1_SLOT && !h->split && h->Bmax <= SORT_N;
     if (steps3) h->splitk = 8;
     // FNN_WGRAD_FORM: the bf16 weight gradients through LDS (wgrad_tile) are 2.8 us shorter alone (role time 11.8 -> 9.0 us) but
     // leave launch 2 beside the scatter role where it was (33.8 us per step either way); what they buy is split-K 4 again, which

@@ -1799,8 +1799,10 @@ static __global__ void k_check_shadowed(const int32_t* __restrict__ tfr, int n, 
 //             added in f64 per run of equal rows, in entry order.  A thread owns one 16-byte
 //             quarter-column of the chunk (scat1q_body: only the quarters with live slots, 3 of 4
 //             at K = 11) and has a sub-batch of 8 entries' gradients, old rows and decay factors
-//             in flight at once; FNN_SCAT1_FORM=slot runs the earlier form, a 16-lane group per
-//             chunk with a lane per slot (scat1_body), bit for bit the same result.  The weight
+//             in flight at once; scat1h_body, the default, gives each sub-batch a thread of its
+//             own, so that both are in flight at once; FNN_SCAT1_FORM=slot runs the earliest form,
+//             a 16-lane group per chunk with a lane per slot (scat1_body); all three give the same
+//             bits.  The weight
 //             is absolute inside the segment, so partial sums of a segment cut by chunk borders
 //             simply add up.  Runs that lie inside the chunk are written back at once; the
 //             others leave a partial and the run that opens a multi-chunk segment registers its
@@ -1921,8 +1923,9 @@ struct ScatArgs {
     int rw;          // 16: FM rows (decayed update); otherwise the bag-table row width (plain sum)
     const int* tag_shared; int stamp;     // bag mode: tag_shared[row] == stamp <=> the row sits in several columns of this batch (SortArgs)
     int gxf;         // wide update (scatw*): floats between two fields' gradients of an example (wide FM rows: rw); 0: one per example (bag)
-    int slot_form;   // level 1 of the 16-float rows: 0 = scat1q_body (a thread per quarter-column), 1 = scat1_body (a lane per slot); set by scat1_blocks
+    int form;        // level 1 of the 16-float rows: SCAT1_QUARTER (scat1q_body), SCAT1_SLOT (scat1_body) or SCAT1_HALF (scat1h_body); set by scat1_blocks
 };
+enum { SCAT1_QUARTER = 0, SCAT1_SLOT = 1, SCAT1_HALF = 2 };   // a thread per quarter-column of a chunk / a lane per slot / a thread per quarter-column of half a chunk
 // bag rows held by several columns of a batch: every column adds its sum with float atomics (a row touched by one column
 // only -- the rule on iPinYou lines -- keeps the plain read-modify-write, one rounding)
 __device__ __forceinline__ void atomic_add4(float* p, float a, float b, float c, float d) {
@@ -2060,27 +2063,117 @@ __device__ __forceinline__ void scat1q_body(const ScatArgs& sa, const int blk)
     }
 }
 
+// An odd lane takes its even neighbour's value (DPP quad_perm [0, 0, 2, 2]: registers only, no LDS); even lanes keep their own.
+__device__ __forceinline__ double lane_below(const double v)
+{
+    const int lo = __builtin_amdgcn_update_dpp(0, __double2loint(v), 0xA0, 0xf, 0xf, false);
+    const int hi = __builtin_amdgcn_update_dpp(0, __double2hiint(v), 0xA0, 0xf, 0xf, false);
+    return __hiloint2double(hi, lo);
+}
+
+// The half-chunk form of scat1q_body: a thread owns one 16-byte quarter-column of ONE of the chunk's two sub-batches of 8 entries
+// (half = gid & 1: the two halves of a quarter-column sit on adjacent lanes of a wave and leave or stay together).  Both halves'
+// gradients, old rows and decay factors are therefore requested at once, and no load waits behind a store to the table:
+// rec -> {gx', rows, cpow} -> stores, once.  The f64 fold stays sequential over the chunk: every thread first folds its own eight
+// entries to find what its half leaves open at its end (the accumulator restarts where a segment ends), the upper half takes the
+// lower half's open sums -- four doubles -- from the lane below as its starting value, and then every thread folds again with
+// the stores.  Same expressions in the same entry order as scat1q_body, so the same bits (tests/test_gpu_scat1_half.py);
+// chunks, partials, `which` and owners follow the chunk's base as there.  The hand-off sits where both lanes of a pair always
+// arrive: a dead upper half is not left early, its entries load example 0 / row 0 like any dead entry.
+// Needs what scat1q_body needs (scat1_blocks checks).
+__device__ __forceinline__ void scat1h_body(const ScatArgs& sa, const int blk)
+{
+    const int N2 = sa.N2, NQ = N2 >> 4, nq = (sa.K + 3) >> 2;
+    const int gid = blk * 256 + (int)threadIdx.x;
+    const int half = gid & 1, cq = gid >> 1;
+    const int chunk = cq / nq, q = cq % nq;
+    if (chunk >= sa.F * NQ) return;                         // both lanes of a pair
+    const int f = chunk / NQ, qc = chunk % NQ, base = qc * 16, hb = base + 8 * half;
+    const int lim = sa.K - 4 * q;                           // live lanes of this quarter: < 4 only in the last one of a padded row
+    const double* __restrict__ cpow = sa.cpow; const double lr = sa.lr;
+    int4 r[8];
+#pragma unroll
+    for (int j = 0; j < 8; ++j) r[j] = sa.rec[(size_t)f * N2 + hb + j];
+    float4 g[8], wold[8];
+    double wd[8], cs[8];
+#pragma unroll
+    for (int j = 0; j < 8; ++j) {
+        const int pos = hb + j;
+        const bool live = r[j].x >= 0;
+        // (dead entries and entries that write no row read example 0 / row 0 / cpow[0]: in bounds, and they stay in cache)
+        g[j] = *reinterpret_cast<const float4*>(sa.gxp + (size_t)(live ? r[j].y : 0) * sa.K1p + f * SLOT + 4 * q);
+        const bool need = live && pos + 1 == r[j].w && r[j].z >= base;
+        wold[j] = *reinterpret_cast<const float4*>(sa.table16 + (size_t)(need ? r[j].x : 0) * SLOT + 4 * q);
+        wd[j] = cpow[live ? r[j].w - 1 - pos : 0];
+        cs[j] = cpow[need ? r[j].w - r[j].z : 0];
+    }
+    if (lim < 4) {                                           // pad lanes take no gradient
+#pragma unroll
+        for (int j = 0; j < 8; ++j) {
+            if (lim < 2) g[j].y = 0.f;
+            if (lim < 3) g[j].z = 0.f;
+            g[j].w = 0.f;
+        }
+    }
+    double a0 = 0, a1 = 0, a2 = 0, a3 = 0;
+#pragma unroll
+    for (int j = 0; j < 8; ++j) {                            // what this half leaves open at its end
+        if (r[j].x < 0) continue;
+        a0 += (double)g[j].x * wd[j]; a1 += (double)g[j].y * wd[j]; a2 += (double)g[j].z * wd[j]; a3 += (double)g[j].w * wd[j];
+        if (hb + j + 1 == r[j].w) a0 = a1 = a2 = a3 = 0;
+    }
+    a0 = lane_below(a0); a1 = lane_below(a1); a2 = lane_below(a2); a3 = lane_below(a3);
+    if (!half) a0 = a1 = a2 = a3 = 0;
+#pragma unroll
+    for (int j = 0; j < 8; ++j) {
+        if (r[j].x < 0) continue;
+        a0 += (double)g[j].x * wd[j]; a1 += (double)g[j].y * wd[j]; a2 += (double)g[j].z * wd[j]; a3 += (double)g[j].w * wd[j];
+        const int pos = hb + j, s = r[j].z, e = r[j].w;
+        if (pos + 1 != e && pos + 1 != base + 16) continue;        // the run goes on inside this chunk
+        if (s >= base && e <= base + 16) {                       // the whole segment lies in this chunk
+            float4 o = make_float4((float)((double)wold[j].x * cs[j] - lr * a0), (float)((double)wold[j].y * cs[j] - lr * a1),
+                                   (float)((double)wold[j].z * cs[j] - lr * a2), (float)((double)wold[j].w * cs[j] - lr * a3));
+            if (lim < 4) {                                       // pad lanes of the row keep what they hold
+                if (lim < 2) o.y = wold[j].y;
+                if (lim < 3) o.z = wold[j].z;
+                o.w = wold[j].w;
+            }
+            *reinterpret_cast<float4*>(sa.table16 + (size_t)r[j].x * SLOT + 4 * q) = o;
+        } else {
+            const int which = (s < base) ? 0 : 1;                // 0: enters from the left; 1: opens here
+            double* pp = sa.part + (((size_t)f * NQ + qc) * 2 + which) * SLOT + 4 * q;
+            pp[0] = a0; pp[1] = a1; pp[2] = a2; pp[3] = a3;
+            if (which == 1 && q == 0) sa.owners[atomicAdd(sa.owner_cnt, 1)] = make_int4(f, s, e, r[j].x);
+        }
+        a0 = a1 = a2 = a3 = 0;
+    }
+}
+
 static __global__ __launch_bounds__(256) void k_scat1(const ScatArgs sa)
 {
-    if (sa.slot_form) scat1_body(sa, blockIdx.x);
+    if (sa.form == SCAT1_SLOT) scat1_body(sa, blockIdx.x);
+    else if (sa.form == SCAT1_HALF) scat1h_body(sa, blockIdx.x);
     else scat1q_body(sa, blockIdx.x);
 }
 
 // Workgroups of level 1 on 16-float rows -- k_scat1's grid and the scatter role's share of k_step2's -- and the form they run:
-// `slot_form` is the handle's choice (FNN_SCAT1_FORM, scat1_form_env), overruled where the float4 loads of the quarter-column
-// form would be misaligned.  Every launch site takes its count from here, after the last change to sa.
-inline int scat1_blocks(ScatArgs& sa, const int slot_form)
+// `form` is the handle's choice (FNN_SCAT1_FORM, scat1_form_env), overruled by the slot form where the float4 loads of the
+// quarter-column and half-chunk forms would be misaligned.  Every launch site takes its count from here, after the last change to sa.
+inline int scat1_blocks(ScatArgs& sa, const int form)
 {
     const bool vec_ok = ((uintptr_t)sa.gxp | (uintptr_t)sa.table16) % 16 == 0 && sa.K1p % 4 == 0;
-    sa.slot_form = (slot_form || !vec_ok) ? 1 : 0;
-    const size_t nthr = sa.slot_form ? (size_t)sa.F * sa.N2 : (size_t)sa.F * (sa.N2 / 16) * ((sa.K + 3) / 4);
+    sa.form = vec_ok ? form : SCAT1_SLOT;
+    const size_t nquarters = (size_t)sa.F * (sa.N2 / 16) * ((sa.K + 3) / 4);
+    const size_t nthr = sa.form == SCAT1_SLOT ? (size_t)sa.F * sa.N2 : sa.form == SCAT1_HALF ? 2 * nquarters : nquarters;
     return (int)((nthr + 255) / 256);
 }
-// FNN_SCAT1_FORM=slot|quarter (default quarter), read where a handle is created
-inline int scat1_form_env()
+// FNN_SCAT1_FORM=slot|quarter|half, read where a handle is created; unset or unknown: `dflt` -- half, which was measured a gain or
+// level for every user of the body (profiles/scat1_half_ab.json)
+inline int scat1_form_env(const int dflt = SCAT1_HALF)
 {
     const char* e = getenv("FNN_SCAT1_FORM");
-    return e && !strcmp(e, "slot") ? 1 : 0;
+    if (!e) return dflt;
+    return !strcmp(e, "slot") ? SCAT1_SLOT : !strcmp(e, "quarter") ? SCAT1_QUARTER : !strcmp(e, "half") ? SCAT1_HALF : dflt;
 }
 
 __device__ __forceinline__ void scat2_body(const ScatArgs& sa, const int blk, const int nblk, double (*s_sum)[16])

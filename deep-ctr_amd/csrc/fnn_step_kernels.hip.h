@@ -299,9 +299,11 @@ static __global__ __launch_bounds__(256) void k_step2(const SortArgs so, const W
         wgrad_body<T, WF>(wa, w % nwx, w / nwx, smem);
     }
     // (the scatter role's blocks dealt BEFORE the weight gradients', so that their chain starts while those are still being
-    // placed, measured level: 39.06 / 38.53 / 39.01 us per step against 38.45 / 39.17 / 39.03 behind them -- they stay behind)
+    // placed, measured level: 39.06 / 38.53 / 39.01 us per step against 38.45 / 39.17 / 39.03 behind them; with the 96 blocks
+    // of the half-chunk form slower, 30.8 against 29.8 -- they stay behind)
     else if (sa.rw != SLOT) scatw1_body(sa, b - so.nblk - nw);
-    else if (sa.slot_form) scat1_body(sa, b - so.nblk - nw);       // FNN_SCAT1_FORM=slot
+    else if (sa.form == SCAT1_SLOT) scat1_body(sa, b - so.nblk - nw);       // FNN_SCAT1_FORM=slot
+    else if (sa.form == SCAT1_HALF) scat1h_body(sa, b - so.nblk - nw);      // FNN_SCAT1_FORM=half
     else scat1q_body(sa, b - so.nblk - nw);
 }
 

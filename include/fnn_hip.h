@@ -110,6 +110,10 @@ uint64_t fnn_cfg_size(void);
 /* Message of the last failing call on `h` (or of the last failing fnn_create
  * when h == NULL).  Valid until the next call on that handle. */
 const char* fnn_last_error(const fnn_handle* h);
+/* What $FNN_SCAT1_FORM selects for handles created from now on (fnn_create, fm_create, ipnn_create): "slot", "quarter" or
+ * "half" -- the body of level 1 of the sparse-row update on 16-float rows, all three bit for bit the same result -- or
+ * "default" when it is unset or names none of them: every handle then takes its own default.  Needs no device. */
+const char* fnn_scat1_form(void);
 
 int fnn_create(const fnn_cfg* cfg, fnn_handle** out);
 int fnn_destroy(fnn_handle* h);
