@@ -43,6 +43,7 @@ SIGNATURES = {
     "fnn_cfg_size": (C.c_uint64, []),
     "fnn_last_error": (C.c_char_p, [_vp]),
     "fnn_scat1_form": (C.c_char_p, []),
+    "fnn_scat2_form": (C.c_char_p, []),
     "fnn_create": (_i, [C.POINTER(fnn_cfg), C.POINTER(_vp)]),
     "fnn_destroy": (_i, [_vp]),
     "fnn_set_hparams": (_i, [_vp, _f, _f, _f]),

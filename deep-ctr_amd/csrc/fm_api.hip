@@ -321,7 +321,8 @@ __global__ __launch_bounds__(256) void k_fm_scat2_tail(const ScatArgs sa, float*
 {
     __shared__ double s_sum[16][16];
     if (blockIdx.x == 0) { fm_tail_body(b, gb_part, n, lr, lambda, loss_t, Ba, lscale, loss_out, reinterpret_cast<float*>(&s_sum[0][0]), bo); return; }
-    scat2_body(sa, (int)blockIdx.x - 1, (int)gridDim.x - 1, s_sum);
+    if (sa.form2 == SCAT2_WAVE) scat2w_body(sa, (int)blockIdx.x - 1, (int)gridDim.x - 1);
+    else scat2_body(sa, (int)blockIdx.x - 1, (int)gridDim.x - 1, s_sum);
 }
 // the same for wide rows: level 1 on its own, level 2 (8 KiB of LDS) beside the tail
 __global__ __launch_bounds__(256) void k_fm_scatw1(const ScatArgs sa) { scatw1_body(sa, blockIdx.x); }
@@ -400,6 +401,7 @@ struct fm_handle {
     // stamp [n_rows]; t = steps since the state was initialised.  dense_g: FM_OPT_DENSE_G=1, the A/B variant of k_fm_opt_pass.
     int opt = FM_OPT_SGD; float beta1 = 0.9f, beta2 = 0.999f, eps = 1e-8f; int64_t t = 0; bool dense_g = false;
     int scat_form = SCAT1_HALF;      // FNN_SCAT1_FORM (scat1_blocks)
+    int scat2_form = SCAT2_WAVE;     // FNN_SCAT2_FORM: level 2 of the narrow rows (scat2w_body; block: scat2_body)
     int sort_merge4 = 0;       // FNN_SORT_RUNS=4|16 (sortA_body; default 16: the run sort is a launch of its own here)
     float *s0 = nullptr, *s1 = nullptr, *sb = nullptr, *G = nullptr; int* stamp = nullptr;
 };
@@ -566,6 +568,7 @@ int fm_run(fm_handle* h, const int32_t* ids, const float* wts, const float* y, i
     if (opt) {   // Adam / FTRL: the same sorted sums land in the zeroed gradient store: G[row] = 0 * 1 - (-1) * sum
         ScatArgs sa{h->rec, SORT_N, F, h->K, h->gxp, h->K1p, h->cpow1, -1.0, h->G, h->part, h->owner_cnt, h->owners, SLOT};
         const int nsc1 = scat1_blocks(sa, h->scat_form);      // also chooses sa.form
+        sa.form2 = h->scat2_form;
         hipLaunchKernelGGL(k_scat1, dim3(nsc1), dim3(256), 0, h->st, sa);
         hipLaunchKernelGGL(k_fm_scat2_tail, dim3(1 + 256), dim3(256), 0, h->st, sa, h->b, h->gb_part, Ba / 16, lr, lambda, h->loss_t, Ba,
                            reduce_mean ? 1.0f / (float)B : 1.0f, h->loss_dev, FmBiasOpt{h->opt, h->sb, lr_step, h->beta1, h->beta2, h->eps});
@@ -578,6 +581,7 @@ int fm_run(fm_handle* h, const int32_t* ids, const float* wts, const float* y, i
     ScatArgs sa{h->rec, SORT_N, F, h->K, h->gxp, h->K1p, h->cpow1, (double)lr / h->scale, h->table16, h->part, h->owner_cnt,
                 h->owners, SLOT};
     const int nsc1 = scat1_blocks(sa, h->scat_form);      // also chooses sa.form
+    sa.form2 = h->scat2_form;
     hipLaunchKernelGGL(k_scat1, dim3(nsc1), dim3(256), 0, h->st, sa);
     hipLaunchKernelGGL(k_fm_scat2_tail, dim3(1 + 256), dim3(256), 0, h->st, sa, h->b, h->gb_part, Ba / 16, lr, lambda, h->loss_t, Ba,
                        reduce_mean ? 1.0f / (float)B : 1.0f, h->loss_dev, FmBiasOpt{FM_OPT_SGD, nullptr, 0.f, 0.f, 0.f, 0.f});
@@ -626,6 +630,7 @@ int fm_create(int n_fields, int k, int max_batch, int device, void* stream, fm_h
 #undef FK
     h->dense_g = getenv("FM_OPT_DENSE_G") && atoi(getenv("FM_OPT_DENSE_G")) == 1;
     h->scat_form = scat1_form_env();
+    h->scat2_form = scat2_form_env();
     h->sort_merge4 = sort_merge4_env(0);
     *out = h;
     return FNN_OK;

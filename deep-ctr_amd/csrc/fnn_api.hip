@@ -48,6 +48,7 @@ struct fnn_handle {
     int scat2_wgs = 256;        // workgroups walking the multi-chunk segments in launch 3
     int sort_merge4 = 1;        // FNN_SORT_RUNS=4 (the default on FM rows): the run sort leaves 4 runs of 1024 keys per field for the rank merge; 16 (bag mode's default): 16 runs of 256
     int wgrad_lds = 0;          // FNN_WGRAD_FORM=lds: the bf16 weight-gradient products stage their operands through LDS (wgrad_tile; f32 and the bf16 pairs keep their register ring)
+    int scat2_form = SCAT2_WAVE;     // FNN_SCAT2_FORM: the body of level 2 of the 16-float rows (scat2w_body, a wave per multi-chunk segment; block: scat2_body)
     int scat_form = SCAT1_HALF;      // FNN_SCAT1_FORM: the body of level 1 of the sparse-row update (scat1h_body; quarter: scat1q_body, slot: scat1_body)
     bool bf16 = false;          // FNN_PREC_BF16: 2-byte elements
     bool split = false;         // FNN_PREC_BF16X3: 4-byte elements (bs16_t), the f32 mode's layouts
@@ -233,7 +234,7 @@ int wgrad_blocks(const WgradArgs& wa) {
 }
 ScatArgs make_scat_args(fnn_handle* h, const fnn_handle::SortSlot& sl, int N2) {
     return ScatArgs{sl.rec, N2, h->F, h->K, h->gxp, h->K1p, h->cpow_dev, (double)h->cfg.lr, h->table16,
-                    sl.part, sl.owner_cnt, sl.owners, h->rw, sl.tag_shared, sl.stamp};
+                    sl.part, sl.owner_cnt, sl.owners, h->rw, sl.tag_shared, sl.stamp, 0, 0, h->scat2_form};
 }
 template <typename T> MlpArgs<T> make_mlp_args(fnn_handle* h, const int32_t* ids, const float* y, int B,
                                                 const uint8_t* m1, const uint8_t* m2, bool train, float* p_out) {
@@ -843,6 +844,12 @@ uint64_t fnn_cfg_size(void) { return (uint64_t)sizeof(fnn_cfg); }
 
 const char* fnn_last_error(const fnn_handle* h) { return h ? h->err.c_str() : g_create_err.c_str(); }
 
+const char* fnn_scat2_form(void)
+{
+    const int f = scat2_form_env(-1);
+    return f == SCAT2_BLOCK ? "block" : f == SCAT2_WAVE ? "wave" : "default";
+}
+
 const char* fnn_scat1_form(void)
 {
     const int f = scat1_form_env(-1);
@@ -899,6 +906,7 @@ int fnn_create(const fnn_cfg* cfg, fnn_handle** out)
     if (const char* ev = getenv("FNN_NO_FUSE")) h->fused = !(ev[0] == '1');
     if (const char* ev = getenv("FNN_ROLE_OFF")) h->role_off = atoi(ev);
     h->scat_form = scat1_form_env();
+    h->scat2_form = scat2_form_env();
     h->sort_merge4 = sort_merge4_env(h->bag ? 0 : 1);
     // the quarter-column scatter role leaves launch 2 the residency for eight K slices of the weight gradients (bf16 37.4 us per
     // step against 38.4 with four, f32 57.1 against 61.4; the bf16 pairs 46.9 against 45.1 and stay at four; beside the

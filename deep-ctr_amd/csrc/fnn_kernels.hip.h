@@ -1807,7 +1807,8 @@ static __global__ void k_check_shadowed(const int32_t* __restrict__ tfr, int n, 
 //             simply add up.  Runs that lie inside the chunk are written back at once; the
 //             others leave a partial and the run that opens a multi-chunk segment registers its
 //             owner.
-//   k_scat2   one workgroup per registered owner adds the partials of its segment in a fixed
+//   k_scat2   one wave per registered owner (scat2w_body; FNN_SCAT2_FORM=block: one workgroup,
+//             scat2_body -- the same bits) adds the partials of its segment in a fixed
 //             order and writes the row.  No float atomics anywhere: the result is bitwise
 //             reproducible.
 // ------------------------------------------------------------------------------------------
@@ -1924,6 +1925,7 @@ struct ScatArgs {
     const int* tag_shared; int stamp;     // bag mode: tag_shared[row] == stamp <=> the row sits in several columns of this batch (SortArgs)
     int gxf;         // wide update (scatw*): floats between two fields' gradients of an example (wide FM rows: rw); 0: one per example (bag)
     int form;        // level 1 of the 16-float rows: SCAT1_QUARTER (scat1q_body), SCAT1_SLOT (scat1_body) or SCAT1_HALF (scat1h_body); set by scat1_blocks
+    int form2;       // level 2 of the 16-float rows: SCAT2_BLOCK (scat2_body; what an initialiser that does not name it gets) or SCAT2_WAVE (scat2w_body)
 };
 enum { SCAT1_QUARTER = 0, SCAT1_SLOT = 1, SCAT1_HALF = 2 };   // a thread per quarter-column of a chunk / a lane per slot / a thread per quarter-column of half a chunk
 // bag rows held by several columns of a batch: every column adds its sum with float atomics (a row touched by one column
@@ -2214,10 +2216,86 @@ __device__ __forceinline__ void scat2_body(const ScatArgs& sa, const int blk, co
     }
 }
 
+// Every lane takes the value lane `src` holds (both halves of the double through the wave's permute: registers only).
+__device__ __forceinline__ double lane_from(const double v, const int src)
+{
+    const int lo = __shfl(__double2loint(v), src, 64), hi = __shfl(__double2hiint(v), src, 64);
+    return __hiloint2double(hi, lo);
+}
+
+// 64 chunks of a segment, from chunk qb on: lane (j, l) requests slot l of the chunks qb + j + 4 m + 16 k (m, k = 0..3; NK = 1:
+// k = 0 only, for a segment of up to 16 chunks) -- all of them before the first is used -- and adds them to its four sums
+// S[m] = S_{j + 4 m} in ascending k.  A chunk past the segment's last one reads that last chunk's partial instead (in bounds,
+// the same cache line for every such lane) and enters as +0.0, as in scat2_body.
+template <int NK>
+__device__ __forceinline__ void scat2w_batch(const double* __restrict__ part, const size_t fq, const int q0, const int q1,
+                                             const int qb, const int j, const int l, double (&S)[4])
+{
+    double v[4][NK];
+#pragma unroll
+    for (int m = 0; m < 4; ++m) {
+#pragma unroll
+        for (int k = 0; k < NK; ++k) {
+            const int q = qb + j + 4 * m + 16 * k, qc = min(q, q1);
+            const double t = part[((fq + qc) * 2 + (qc == q0 ? 1 : 0)) * SLOT + l];
+            v[m][k] = q <= q1 ? t : 0.0;
+        }
+    }
+#pragma unroll
+    for (int m = 0; m < 4; ++m) {
+#pragma unroll
+        for (int k = 0; k < 4; ++k) S[m] += k < NK ? v[m][k] : 0.0;
+    }
+}
+
+// The wave form of scat2_body (FNN_SCAT2_FORM=wave): one 64-lane wave per registered owner instead of a 256-thread workgroup,
+// no LDS and no workgroup barrier.  A wave's first owner record is requested together with the owner count -- speculatively:
+// owners[] holds at least F * N2 / 16 records at every allocation site, and the record is used only once o < n is known --
+// and the old row and the segment's decay factor go out with the partial sums: count and record, then the data, then the
+// store.  With 256 workgroups the benchmark's ~540 owners all sit in a first iteration; scat2_body walks up to three owners per
+// workgroup, each a chain of its own behind two barriers.  Lane (j = lane >> 4, l = lane & 15): l is the row's slot, quarter j
+// adds the sums S_g with g = j (mod 4) in scat2_body's order, S_g = (((0 + P_g) + P_{g+16}) + P_{g+32}) + ..., and then every
+// lane folds tot = ((0 + S_0) + S_1) + ... + S_15, taking the twelve sums of the other quarters from their lanes: the same f64
+// expressions, the same bits (tests/test_gpu_scat2_forms.py).  Control flow is wave-uniform; lanes of quarter 0 with l < K store.
+__device__ __forceinline__ void scat2w_body(const ScatArgs& sa, const int blk, const int nblk)
+{
+    const double* __restrict__ part = sa.part; const double* __restrict__ cpow = sa.cpow; const double lr = sa.lr;
+    const int lane = threadIdx.x & 63, j = lane >> 4, l = lane & 15;
+    const int gw = __builtin_amdgcn_readfirstlane(blk * 4 + ((int)threadIdx.x >> 6));
+    const int NQ = sa.N2 >> 4, cap = sa.F * NQ;
+    int4 ow = sa.owners[min(gw, cap - 1)];                   // {f, s, e, row}; stale or never written where gw >= n
+    const int n = *sa.owner_cnt;
+    for (int o = gw; o < n; o += 4 * nblk) {
+        if (o != gw) ow = sa.owners[o];
+        const int q0 = ow.y >> 4, q1 = (ow.z - 1) >> 4;
+        const size_t fq = (size_t)ow.x * NQ;
+        float* p = sa.table16 + (size_t)ow.w * SLOT + l;
+        const float wold = *p;                               // every lane: all 16 floats of the row exist, no branch around the loads
+        const double cdec = cpow[ow.z - ow.y];
+        double S[4] = {0.0, 0.0, 0.0, 0.0};
+        if (q1 - q0 < 16) scat2w_batch<1>(part, fq, q0, q1, q0, j, l, S);
+        else for (int qb = q0; qb <= q1; qb += 64) scat2w_batch<4>(part, fq, q0, q1, qb, j, l, S);
+        double tot = 0.0;
+#pragma unroll
+        for (int g = 0; g < 16; ++g) tot += (g & 3) ? lane_from(S[g >> 2], (g & 3) * 16 + l) : S[g >> 2];   // quarter 0 holds S_0, S_4, ...
+        if (j == 0 && l < sa.K) *p = (float)((double)wold * cdec - lr * tot);
+    }
+}
+enum { SCAT2_BLOCK = 0, SCAT2_WAVE = 1 };                    // ScatArgs::form2: scat2_body / scat2w_body
+// FNN_SCAT2_FORM=block|wave, read where a handle is created; unset or unknown: `dflt` -- wave, which was measured a gain or
+// level for every user of the body (profiles/scat2_wave_ab.json)
+inline int scat2_form_env(const int dflt = SCAT2_WAVE)
+{
+    const char* e = getenv("FNN_SCAT2_FORM");
+    if (!e) return dflt;
+    return !strcmp(e, "block") ? SCAT2_BLOCK : !strcmp(e, "wave") ? SCAT2_WAVE : dflt;
+}
+
 static __global__ __launch_bounds__(256) void k_scat2(const ScatArgs sa)
 {
     __shared__ double s_sum[16][16];
-    scat2_body(sa, blockIdx.x, gridDim.x, s_sum);
+    if (sa.form2 == SCAT2_WAVE) scat2w_body(sa, blockIdx.x, gridDim.x);
+    else scat2_body(sa, blockIdx.x, gridDim.x, s_sum);
 }
 
 // ------------------------------------------------------------------------------------------

@@ -328,7 +328,10 @@ static __global__ __launch_bounds__(256) void k_step3(const SortArgs so, const T
     const int b = (int)blockIdx.x - so.nblk;
     if (b >= ta.nblk_red) {
         const int nb = (int)gridDim.x - so.nblk - ta.nblk_red;
-        if (sa.rw == SLOT) scat2_body(sa, b - ta.nblk_red, nb, s_sum);
+        if (sa.rw == SLOT) {
+            if (sa.form2 == SCAT2_WAVE) scat2w_body(sa, b - ta.nblk_red, nb);      // FNN_SCAT2_FORM=wave
+            else scat2_body(sa, b - ta.nblk_red, nb, s_sum);
+        }
         else scatw2_body(sa, b - ta.nblk_red, nb, reinterpret_cast<double*>(smem));
         return;
     }

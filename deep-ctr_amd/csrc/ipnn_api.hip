@@ -1576,6 +1576,7 @@ struct ipnn_handle {
     int strip_rot = 1, fwd_skip = 0;                 // IPNN_STRIP_ROT (0: every workgroup walks the blocks in the same order), IPNN_FWD_SKIP (diagnostics)
     int wide_nf = 2, wide_nw = 8;                    // IPNN_WIDE=nf:nw -- items (16-column fragments) and waves of the wide (pair) launches: 2:8 (default), 4:8, 2:12
     int scat_form = SCAT1_HALF;                      // FNN_SCAT1_FORM (scat1_blocks)
+    int scat2_form = SCAT2_WAVE;                     // FNN_SCAT2_FORM: level 2 of the narrow rows (scat2w_body; block: scat2_body)
     int sort_merge4 = 1;                             // FNN_SORT_RUNS=4|16 (sortA_body; default 4)
     bool wt = true;                                  // IPNN_WT=0: plain stores where the launches write through by default
     int tail_fuse = 1;                               // IPNN_TAIL_FUSE: training steps run the forward and the backward tail in one launch
@@ -2044,6 +2045,7 @@ int ip_run(ipnn_handle* h, const int32_t* ids, const float* wts, const float* y,
             ScatArgs sa{h->rec, SORT_N, F, h->K, h->gxp, h->Dp[0], h->cpow1, h->adam ? -1.0 : (double)h->cfg.lr,
                         h->adam ? h->tG : h->table16, h->part, h->owner_cnt, h->owners, SLOT};
             const int nsc1 = scat1_blocks(sa, h->scat_form);      // also chooses sa.form
+            sa.form2 = h->scat2_form;
             hipLaunchKernelGGL(k_scat1, dim3(nsc1), dim3(256), 0, ss, sa);
             hipLaunchKernelGGL(k_scat2, dim3(256), dim3(256), 0, ss, sa);
         }
@@ -2156,6 +2158,7 @@ int ipnn_create(const ipnn_cfg* cfg, ipnn_handle** out)
     if (const char* e = getenv("IPNN_TAIL_FUSE")) h->tail_fuse = atoi(e) != 0;
     if (const char* e = getenv("IPNN_WT")) h->wt = atoi(e) != 0;
     h->scat_form = scat1_form_env();
+    h->scat2_form = scat2_form_env();
     h->sort_merge4 = sort_merge4_env(1);
     if (const char* e = getenv("IPNN_WIDE")) { int nf = 4, nw = 8; if (sscanf(e, "%d:%d", &nf, &nw) == 2 && ((nf == 2 && (nw == 8 || nw == 12)) || (nf == 4 && nw == 8))) { h->wide_nf = nf; h->wide_nw = nw; } }
     if (const char* e = getenv("IPNN_TAIL_NW")) h->tail_nw = atoi(e) == 16 ? 16 : 8;

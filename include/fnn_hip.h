@@ -114,6 +114,9 @@ const char* fnn_last_error(const fnn_handle* h);
  * "half" -- the body of level 1 of the sparse-row update on 16-float rows, all three bit for bit the same result -- or
  * "default" when it is unset or names none of them: every handle then takes its own default.  Needs no device. */
 const char* fnn_scat1_form(void);
+/* The same for $FNN_SCAT2_FORM: "block" (a workgroup per multi-chunk segment) or "wave" (a wave per segment) -- the body of
+ * level 2 of that update, both bit for bit the same result -- or "default".  Needs no device. */
+const char* fnn_scat2_form(void);
 
 int fnn_create(const fnn_cfg* cfg, fnn_handle** out);
 int fnn_destroy(fnn_handle* h);
