@@ -8,6 +8,8 @@ Value weights (the class's `sp_wt_hldr`, python/FM.py:24-29): `wts=` of train_st
 (example, field) beside its id; `model.train_step(_cols, _labels, wts=_vals)` is python/baseline.py:345's feed, and the
 `(ids, wts)` pair that `ipnn.criteo_feed` makes for the inner-product family feeds FM / LR unchanged.  Without `wts` every
 value is 1 (iPinYou).
+Rows shared between columns (`shared_rows=True`, fm_set_shared_rows): the columns of `ids` are then positions, not fields, as
+python/ipinyou.py:42-65 feeds the reference -- `ipinyou.to_column_ids` makes such ids and `ipinyou.run` is the driver.
 Random init uses NumPy RandomState(seed) streams (TensorFlow's cannot be reproduced here)."""
 import ctypes as C
 import pickle
@@ -34,8 +36,10 @@ def parse_ptmzr(_ptmzr_argv):
 
 
 class FM(object):
-    def __init__(self, batch_size, _rch_argv, _init_argv, _ptmzr_argv, _reg_argv, mode='train', eval_size=0, device=0):
-        """_rch_argv = [X_dim, X_feas, rank]: X_feas fields (1..64, one id per field), rank 0..127 (python/FM.py:7)."""
+    def __init__(self, batch_size, _rch_argv, _init_argv, _ptmzr_argv, _reg_argv, mode='train', eval_size=0, device=0,
+                 shared_rows=False):
+        """_rch_argv = [X_dim, X_feas, rank]: X_feas fields (1..64, one id per field), rank 0..127 (python/FM.py:7).
+        shared_rows: a row may sit under several columns of a batch (set_shared_rows)."""
         import torch
         X_dim, X_feas, rank = _rch_argv                              # python/FM.py:7
         self.optimizer, self.lr, self.eps, self.reduce_mean = parse_ptmzr(_ptmzr_argv)
@@ -54,8 +58,11 @@ class FM(object):
         if rc != 0:
             raise FNNError(rc, (self.lib.fm_last_error(None) or b'').decode())
         self.h = h
+        self.shared_rows = False
         if self.optimizer:                                          # tf.train.AdamOptimizer's beta1 / beta2 defaults
             self._ck(self.lib.fm_set_optimizer(h, self.optimizer, 0.9, 0.999, self.eps))
+        if shared_rows:
+            self.set_shared_rows(True)
         lo, hi, seeds, path = _init_argv[1], _init_argv[2], _init_argv[3], _init_argv[-1]
         var_map = pickle.load(open(path, 'rb')) if path else {}     # python/tf_util.py:41-82
         W = var_map['W'] if 'W' in var_map else np.random.RandomState(seeds[0]).uniform(lo, hi, (X_dim, 1))
@@ -77,6 +84,19 @@ class FM(object):
             self.close()
         except Exception:
             pass
+
+    def set_shared_rows(self, on):
+        """fm_set_shared_rows: on, a training step is right for any ids in [-1, X_dim) -- a row under several columns of a batch
+        receives every column's contribution (float atomics; rows under one column keep their single rounded store)."""
+        self._ck(self.lib.fm_set_shared_rows(self.h, 1 if on else 0))
+        self.shared_rows = bool(on)
+
+    def count_shared_rows(self):
+        """Rows the last train_step found under more than one column (fm_count_shared_rows); FNNError(FNN_ERR_STATE) while the
+        mode is off or before a step."""
+        n = C.c_int64()
+        self._ck(self.lib.fm_count_shared_rows(self.h, C.byref(n)))
+        return int(n.value)
 
     def set_params(self, rows, b):
         t = np.ascontiguousarray(rows, dtype=np.float32)

@@ -13,11 +13,12 @@ from .FM import FM
 
 
 class LR(FM):
-    def __init__(self, batch_size, _rch_argv, _init_argv, _ptmzr_argv, _reg_argv, mode='train', eval_size=0, device=0):
-        """_rch_argv = [X_dim, X_feas]: X_feas fields (1..64, one id per field)."""
+    def __init__(self, batch_size, _rch_argv, _init_argv, _ptmzr_argv, _reg_argv, mode='train', eval_size=0, device=0,
+                 shared_rows=False):
+        """_rch_argv = [X_dim, X_feas]: X_feas fields (1..64, one id per field); shared_rows: FM's (columns are positions)."""
         X_dim, X_feas = _rch_argv                                    # python/LR.py:7
         # init_var_map (python/LR.py:15-16): W 'random' from the pickle or _init_argv's distribution, b 'zero'
-        FM.__init__(self, batch_size, [X_dim, X_feas, 0], _init_argv, _ptmzr_argv, _reg_argv, mode, eval_size, device)
+        FM.__init__(self, batch_size, [X_dim, X_feas, 0], _init_argv, _ptmzr_argv, _reg_argv, mode, eval_size, device, shared_rows)
         self.log = 'input dim: %d, features: %d, ' % (X_dim, X_feas)
 
     def dump(self, model_path):                                      # python/LR.py:61-64

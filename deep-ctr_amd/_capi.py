@@ -166,6 +166,8 @@ FM_SIGNATURES = {
     "fm_train_step_w": (_i, [_vp, _vp, _vp, _vp, _i, _f, _f, _i, _vp, C.POINTER(_f)]),
     "fm_predict_w": (_i, [_vp, _vp, _vp, _i, _vp]),
     "fm_eval_w": (_i, [_vp, _vp, _vp, _vp, _i64, C.POINTER(C.c_double), C.POINTER(C.c_double), C.POINTER(C.c_double)]),
+    "fm_set_shared_rows": (_i, [_vp, _i]),
+    "fm_count_shared_rows": (_i, [_vp, C.POINTER(_i64)]),
 }
 
 _i64p = C.POINTER(_i64)

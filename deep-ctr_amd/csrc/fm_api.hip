@@ -324,6 +324,27 @@ __global__ __launch_bounds__(256) void k_fm_scat2_tail(const ScatArgs sa, float*
     if (sa.form2 == SCAT2_WAVE) scat2w_body(sa, (int)blockIdx.x - 1, (int)gridDim.x - 1);
     else scat2_body(sa, (int)blockIdx.x - 1, (int)gridDim.x - 1, s_sum);
 }
+// Shared rows (fm_set_shared_rows): the half-chunk level 1 and the wave-per-segment level 2 in their SHARED forms, whatever
+// FNN_SCAT1_FORM / FNN_SCAT2_FORM say -- rows the rank merge marked (SortArgs::tag_shared) take float atomics, the others the
+// stores of k_scat1 / k_fm_scat2_tail.  FM only: the FNN step's and the inner-product family's columns are fields.
+__global__ __launch_bounds__(256) void k_fm_scat1s(const ScatArgs sa) { scat1h_form<true>(sa, blockIdx.x); }
+__global__ __launch_bounds__(256) void k_fm_scat2s_tail(const ScatArgs sa, float* b, const float* gb_part, int n, float lr, float lambda,
+                                                        const float* loss_t, int Ba, float lscale, float* loss_out, const FmBiasOpt bo)
+{
+    __shared__ float s_l[256];
+    if (blockIdx.x == 0) { fm_tail_body(b, gb_part, n, lr, lambda, loss_t, Ba, lscale, loss_out, s_l, bo); return; }
+    scat2w_form<true>(sa, (int)blockIdx.x - 1, (int)gridDim.x - 1);
+}
+// fm_count_shared_rows: the rows the last step's rank merge marked
+__global__ __launch_bounds__(256) void k_fm_count_marks(const int* __restrict__ tag_shared, int64_t n_rows, int stamp, unsigned long long* out)
+{
+    __shared__ int s_c[256];
+    int c = 0;
+    for (int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x; i < n_rows; i += (int64_t)gridDim.x * 256) c += tag_shared[i] == stamp;
+    s_c[threadIdx.x] = c; __syncthreads();
+    for (int o = 128; o > 0; o >>= 1) { if ((int)threadIdx.x < o) s_c[threadIdx.x] += s_c[threadIdx.x + o]; __syncthreads(); }
+    if (threadIdx.x == 0 && s_c[0]) atomicAdd(out, (unsigned long long)s_c[0]);
+}
 // the same for wide rows: level 1 on its own, level 2 (8 KiB of LDS) beside the tail
 __global__ __launch_bounds__(256) void k_fm_scatw1(const ScatArgs sa) { scatw1_body(sa, blockIdx.x); }
 __global__ __launch_bounds__(256) void k_fm_scatw2_tail(const ScatArgs sa, float* b, const float* gb_part, int n, float lr, float lambda,
@@ -404,6 +425,11 @@ struct fm_handle {
     int scat2_form = SCAT2_WAVE;     // FNN_SCAT2_FORM: level 2 of the narrow rows (scat2w_body; block: scat2_body)
     int sort_merge4 = 0;       // FNN_SORT_RUNS=4|16 (sortA_body; default 16: the run sort is a launch of its own here)
     float *s0 = nullptr, *s1 = nullptr, *sb = nullptr, *G = nullptr; int* stamp = nullptr;
+    // fm_set_shared_rows: tag_first / tag_shared [n_rows] of SortArgs, allocated with the table while the mode is on (kept when it
+    // goes off); tag_stamp: the last grouping's stamp (25 bits, then both arrays start over); step_stamp: the stamp of the last
+    // training step under the mode, 0 = none yet -- what fm_count_shared_rows scans for.
+    bool shared = false; int* tag_first = nullptr; int* tag_shared = nullptr; int tag_stamp = 0, step_stamp = 0;
+    unsigned long long* mark_cnt = nullptr;
 };
 
 #define MHK(h, expr) do { hipError_t e_ = (expr); if (e_ != hipSuccess) { (h)->err = std::string(#expr) + ": " + hipGetErrorString(e_); return FNN_ERR_HIP; } } while (0)
@@ -419,6 +445,37 @@ int fold_scale(fm_handle* h)          // fold the lazy decay back into the rows
     MHK(h, hipGetLastError());
     h->scale = 1.0;
     return FNN_OK;
+}
+
+// (Re)allocate and zero the shared-row tags for the current table; the stamps start over.
+int alloc_tags(fm_handle* h)
+{
+    for (int** p : {&h->tag_first, &h->tag_shared}) { if (*p) hipFree(*p); *p = nullptr; }
+    h->tag_stamp = h->step_stamp = 0;
+    if (!h->shared || !h->table16) return FNN_OK;
+    for (int** p : {&h->tag_first, &h->tag_shared}) {
+        MHK(h, hipMalloc((void**)p, (size_t)h->n_rows * sizeof(int)));
+        MHK(h, hipMemsetAsync(*p, 0, (size_t)h->n_rows * sizeof(int), h->st));
+    }
+    MHK(h, hipStreamSynchronize(h->st));
+    return FNN_OK;
+}
+// a fresh stamp for the grouping of the step about to run (next_stamp of fnn_api.hip): 2^25 groupings, then the tags start over
+int fm_next_stamp(fm_handle* h)
+{
+    if (h->tag_stamp >= (1 << 25) - 1) {
+        hipMemsetAsync(h->tag_first, 0, (size_t)h->n_rows * sizeof(int), h->st);
+        hipMemsetAsync(h->tag_shared, 0, (size_t)h->n_rows * sizeof(int), h->st);
+        h->tag_stamp = 0;
+    }
+    h->step_stamp = ++h->tag_stamp;
+    return h->step_stamp;
+}
+// the claim of the rank merge (sortB_body): on only while the mode is
+void set_claim(fm_handle* h, SortArgs& so)
+{
+    if (!h->shared) return;
+    so.tag_first = h->tag_first; so.tag_shared = h->tag_shared; so.stamp = fm_next_stamp(h);
 }
 
 size_t opt_state_len(const fm_handle* h) { return ((size_t)h->n_rows * h->K + 3) & ~(size_t)3; }
@@ -494,6 +551,7 @@ int fm_run_wide(fm_handle* h, FmArgs a, int B, float lr, float lambda, int reduc
     SortArgs so{a.ids, B, F, h->n_rows, h->rec, h->owner_cnt, 4 * F, h->skeys};
     so.merge4 = h->sort_merge4;
     SortArgs sb = so; sb.nblk = 16 * F;
+    set_claim(h, sb);
     if (h->key64) {
         hipLaunchKernelGGL((k_sortA<unsigned long long>), dim3(4 * F), dim3(256), sortA_lds_bytes<unsigned long long>(so.merge4), h->st, so);
         launch_fwd<unsigned long long>(h, &sb, a, Ba / ex);
@@ -504,7 +562,7 @@ int fm_run_wide(fm_handle* h, FmArgs a, int B, float lr, float lambda, int reduc
     // SGD: the dense decay is the lazy scale, touched rows -= lr * g / scale; Adam / FTRL: G[row] = G[row] - (-1) * sum
     if (!opt) h->scale *= 1.0 - (double)lr * (double)lambda;
     ScatArgs sa{h->rec, SORT_N, F, h->K, h->gxp, h->K1p, h->cpow1, opt ? -1.0 : (double)lr / h->scale, opt ? h->G : h->table16,
-                h->part, h->owner_cnt, h->owners, h->rw, h->noshare, 1, h->rw};
+                h->part, h->owner_cnt, h->owners, h->rw, h->shared ? h->tag_shared : h->noshare, h->shared ? sb.stamp : 1, h->rw};
     const int nthr = F * (SORT_N / WCH) * (h->rw / 4);
     hipLaunchKernelGGL(k_fm_scatw1, dim3((nthr + 255) / 256), dim3(256), 0, h->st, sa);
     hipLaunchKernelGGL(k_fm_scatw2_tail, dim3(1 + 256), dim3(256), 0, h->st, sa, h->b, h->gb_part, Ba / ex, lr, lambda, h->loss_t, Ba,
@@ -524,6 +582,27 @@ void launch_opt_pass(fm_handle* h, float lambda, float lr_step)
     else
         hipLaunchKernelGGL(k_fm_opt_pass<false>, grid, dim3(256), 0, h->st, h->table16, h->G, h->stamp, (int)h->t, h->s0, h->s1, nk, h->K,
                            h->rw, lambda, h->opt, lr_step, h->beta1, h->beta2, h->eps);
+}
+
+// Both levels of the narrow-row update (k <= 16): level 1, then level 2 beside the bias / loss tail.  Under fm_set_shared_rows the
+// SHARED forms with the marks of this step's rank merge (h->step_stamp); otherwise the forms the handle chose.
+void launch_scat(fm_handle* h, ScatArgs& sa, int Ba, int B, float lr, float lambda, int reduce_mean, const FmBiasOpt bo)
+{
+    const float lscale = reduce_mean ? 1.0f / (float)B : 1.0f;
+    if (h->shared) {
+        sa.tag_shared = h->tag_shared; sa.stamp = h->step_stamp;
+        const int nsc1 = scat1_blocks(sa, SCAT1_HALF);
+        sa.form2 = SCAT2_WAVE;
+        hipLaunchKernelGGL(k_fm_scat1s, dim3(nsc1), dim3(256), 0, h->st, sa);
+        hipLaunchKernelGGL(k_fm_scat2s_tail, dim3(1 + 256), dim3(256), 0, h->st, sa, h->b, h->gb_part, Ba / 16, lr, lambda, h->loss_t, Ba,
+                           lscale, h->loss_dev, bo);
+        return;
+    }
+    const int nsc1 = scat1_blocks(sa, h->scat_form);      // also chooses sa.form
+    sa.form2 = h->scat2_form;
+    hipLaunchKernelGGL(k_scat1, dim3(nsc1), dim3(256), 0, h->st, sa);
+    hipLaunchKernelGGL(k_fm_scat2_tail, dim3(1 + 256), dim3(256), 0, h->st, sa, h->b, h->gb_part, Ba / 16, lr, lambda, h->loss_t, Ba,
+                       lscale, h->loss_dev, bo);
 }
 
 int fm_run(fm_handle* h, const int32_t* ids, const float* wts, const float* y, int B, float lr, float lambda, int reduce_mean, float* p_out,
@@ -557,6 +636,7 @@ int fm_run(fm_handle* h, const int32_t* ids, const float* wts, const float* y, i
         SortArgs so{ids, B, F, h->n_rows, h->rec, h->owner_cnt, 4 * F, h->skeys};
         so.merge4 = h->sort_merge4;
         SortArgs sb = so; sb.nblk = 16 * F;
+        set_claim(h, sb);
         if (h->key64) {
             hipLaunchKernelGGL((k_sortA<unsigned long long>), dim3(4 * F), dim3(256), sortA_lds_bytes<unsigned long long>(so.merge4), h->st, so);
             launch_fwd<unsigned long long>(h, &sb, a, Ba / 16);
@@ -567,11 +647,7 @@ int fm_run(fm_handle* h, const int32_t* ids, const float* wts, const float* y, i
     }
     if (opt) {   // Adam / FTRL: the same sorted sums land in the zeroed gradient store: G[row] = 0 * 1 - (-1) * sum
         ScatArgs sa{h->rec, SORT_N, F, h->K, h->gxp, h->K1p, h->cpow1, -1.0, h->G, h->part, h->owner_cnt, h->owners, SLOT};
-        const int nsc1 = scat1_blocks(sa, h->scat_form);      // also chooses sa.form
-        sa.form2 = h->scat2_form;
-        hipLaunchKernelGGL(k_scat1, dim3(nsc1), dim3(256), 0, h->st, sa);
-        hipLaunchKernelGGL(k_fm_scat2_tail, dim3(1 + 256), dim3(256), 0, h->st, sa, h->b, h->gb_part, Ba / 16, lr, lambda, h->loss_t, Ba,
-                           reduce_mean ? 1.0f / (float)B : 1.0f, h->loss_dev, FmBiasOpt{h->opt, h->sb, lr_step, h->beta1, h->beta2, h->eps});
+        launch_scat(h, sa, Ba, B, lr, lambda, reduce_mean, FmBiasOpt{h->opt, h->sb, lr_step, h->beta1, h->beta2, h->eps});
         launch_opt_pass(h, lambda, lr_step);
         MHK(h, hipGetLastError());
         return FNN_OK;
@@ -580,11 +656,7 @@ int fm_run(fm_handle* h, const int32_t* ids, const float* wts, const float* y, i
     h->scale *= 1.0 - (double)lr * (double)lambda;
     ScatArgs sa{h->rec, SORT_N, F, h->K, h->gxp, h->K1p, h->cpow1, (double)lr / h->scale, h->table16, h->part, h->owner_cnt,
                 h->owners, SLOT};
-    const int nsc1 = scat1_blocks(sa, h->scat_form);      // also chooses sa.form
-    sa.form2 = h->scat2_form;
-    hipLaunchKernelGGL(k_scat1, dim3(nsc1), dim3(256), 0, h->st, sa);
-    hipLaunchKernelGGL(k_fm_scat2_tail, dim3(1 + 256), dim3(256), 0, h->st, sa, h->b, h->gb_part, Ba / 16, lr, lambda, h->loss_t, Ba,
-                       reduce_mean ? 1.0f / (float)B : 1.0f, h->loss_dev, FmBiasOpt{FM_OPT_SGD, nullptr, 0.f, 0.f, 0.f, 0.f});
+    launch_scat(h, sa, Ba, B, lr, lambda, reduce_mean, FmBiasOpt{FM_OPT_SGD, nullptr, 0.f, 0.f, 0.f, 0.f});
     MHK(h, hipGetLastError());
     if (h->scale < 5.96e-8 || h->scale > 1.0) return fold_scale(h);
     return FNN_OK;
@@ -616,6 +688,7 @@ int fm_create(int n_fields, int k, int max_batch, int device, void* stream, fm_h
     const size_t Ba = rup(h->Bmax, 16);
     FK(al((void**)&h->gxp, Ba * h->K1p * 4)); FK(al((void**)&h->loss_t, Ba * 4)); FK(al((void**)&h->gb_part, (Ba / 8) * 4));
     FK(al((void**)&h->loss_dev, 4)); FK(al((void**)&h->b, 4)); FK(al((void**)&h->err_flag, 4)); FK(al((void**)&h->sb, 8));
+    FK(al((void**)&h->mark_cnt, 8));
     // level-1 partial sums: two per chunk of 16 (narrow) or WCH (wide) sorted entries, a row each
     const size_t part_rows = h->wide ? (size_t)h->F * (SORT_N / WCH) * 2 : (size_t)h->F * (SORT_N / 16) * 2;
     FK(al((void**)&h->rec, (size_t)h->F * SORT_N * sizeof(int4))); FK(al((void**)&h->part, part_rows * h->rw * 8));
@@ -642,7 +715,7 @@ int fm_destroy(fm_handle* h)
     hipSetDevice(h->dev);
     if (h->st) hipStreamSynchronize(h->st);
     void* ptrs[] = {h->table16, h->b, h->gxp, h->loss_t, h->gb_part, h->loss_dev, h->err_flag, h->rec, h->part, h->owners, h->owner_cnt,
-                    h->skeys, h->cpow1, h->s0, h->s1, h->sb, h->G, h->stamp, h->noshare};
+                    h->skeys, h->cpow1, h->s0, h->s1, h->sb, h->G, h->stamp, h->noshare, h->tag_first, h->tag_shared, h->mark_cnt};
     for (void* p : ptrs) if (p) hipFree(p);
     if (h->own_stream && h->st) hipStreamDestroy(h->st);
     delete h;
@@ -680,6 +753,8 @@ int fm_set_table(fm_handle* h, const float* rows, int64_t n_rows)
     hipFree(tmp);
     h->n_rows = n_rows; h->scale = 1.0;
     h->key64 = (unsigned long long)n_rows * SORT_N > 0xFFFFFFFFull;
+    const int rct = alloc_tags(h);                                // the tags are sized by the table
+    if (rct != FNN_OK) return rct;
     return init_opt_state(h);                                     // fresh state for the new rows
 }
 
@@ -785,6 +860,37 @@ int fm_get_opt_state(fm_handle* h, float* s0, float* s1, float* sb, int64_t* t)
     if (s1) MHK(h, hipMemcpy(s1, h->s1, n, hipMemcpyDeviceToHost));
     if (sb) MHK(h, hipMemcpy(sb, h->sb, 8, hipMemcpyDeviceToHost));
     if (t) *t = h->t;
+    return FNN_OK;
+}
+
+int fm_set_shared_rows(fm_handle* h, int on)
+{
+    if (!h) return FNN_ERR_ARG;
+    MHK(h, hipSetDevice(h->dev));
+    const bool want = on != 0;
+    if (want == h->shared) return FNN_OK;
+    MHK(h, hipStreamSynchronize(h->st));
+    h->shared = want;
+    h->step_stamp = 0;                                            // no step has run under this setting
+    if (want && h->table16 && !h->tag_first) return alloc_tags(h);
+    return FNN_OK;
+}
+
+int fm_count_shared_rows(fm_handle* h, int64_t* n_out)
+{
+    if (!h || !n_out) return FNN_ERR_ARG;
+    if (!h->shared) MFAIL(h, FNN_ERR_STATE, "fm_set_shared_rows is off");
+    if (!h->step_stamp) MFAIL(h, FNN_ERR_STATE, "no training step has run since fm_set_shared_rows / fm_set_table");
+    MHK(h, hipSetDevice(h->dev));
+    MHK(h, hipMemsetAsync(h->mark_cnt, 0, 8, h->st));
+    const int64_t nb = (h->n_rows + 255) / 256;
+    hipLaunchKernelGGL(k_fm_count_marks, dim3((unsigned)(nb < 1024 ? nb : 1024)), dim3(256), 0, h->st, h->tag_shared, h->n_rows, h->step_stamp,
+                       h->mark_cnt);
+    MHK(h, hipGetLastError());
+    unsigned long long c = 0;
+    MHK(h, hipMemcpyAsync(&c, h->mark_cnt, 8, hipMemcpyDeviceToHost, h->st));
+    MHK(h, hipStreamSynchronize(h->st));
+    *n_out = (int64_t)c;
     return FNN_OK;
 }
 

@@ -2083,7 +2083,13 @@ __device__ __forceinline__ double lane_below(const double v)
 // chunks, partials, `which` and owners follow the chunk's base as there.  The hand-off sits where both lanes of a pair always
 // arrive: a dead upper half is not left early, its entries load example 0 / row 0 like any dead entry.
 // Needs what scat1q_body needs (scat1_blocks checks).
-__device__ __forceinline__ void scat1h_body(const ScatArgs& sa, const int blk)
+// SHARED (FM / LR pre-training with fm_set_shared_rows, fm_api.hip): a row may sit under several columns of the batch, each a
+// segment of its own.  The row's mark tag_shared[row] (SortArgs) is requested beside its old value -- the same round trip, row 0
+// for entries that write nothing -- and a marked row takes -lr * sum as float atomics, one add per (column, segment), instead of
+// the rounded store; FM's update has no per-row decay (cpow == 1), which is what makes the adds legal.  Unmarked rows run the
+// expression and the store of SHARED = false, which is the body as it was.
+template <bool SHARED>
+__device__ __forceinline__ void scat1h_form(const ScatArgs& sa, const int blk)
 {
     const int N2 = sa.N2, NQ = N2 >> 4, nq = (sa.K + 3) >> 2;
     const int gid = blk * 256 + (int)threadIdx.x;
@@ -2098,6 +2104,7 @@ __device__ __forceinline__ void scat1h_body(const ScatArgs& sa, const int blk)
     for (int j = 0; j < 8; ++j) r[j] = sa.rec[(size_t)f * N2 + hb + j];
     float4 g[8], wold[8];
     double wd[8], cs[8];
+    int mk[8];
 #pragma unroll
     for (int j = 0; j < 8; ++j) {
         const int pos = hb + j;
@@ -2108,6 +2115,7 @@ __device__ __forceinline__ void scat1h_body(const ScatArgs& sa, const int blk)
         wold[j] = *reinterpret_cast<const float4*>(sa.table16 + (size_t)(need ? r[j].x : 0) * SLOT + 4 * q);
         wd[j] = cpow[live ? r[j].w - 1 - pos : 0];
         cs[j] = cpow[need ? r[j].w - r[j].z : 0];
+        if (SHARED) mk[j] = sa.tag_shared[need ? r[j].x : 0];
     }
     if (lim < 4) {                                           // pad lanes take no gradient
 #pragma unroll
@@ -2132,7 +2140,9 @@ __device__ __forceinline__ void scat1h_body(const ScatArgs& sa, const int blk)
         a0 += (double)g[j].x * wd[j]; a1 += (double)g[j].y * wd[j]; a2 += (double)g[j].z * wd[j]; a3 += (double)g[j].w * wd[j];
         const int pos = hb + j, s = r[j].z, e = r[j].w;
         if (pos + 1 != e && pos + 1 != base + 16) continue;        // the run goes on inside this chunk
-        if (s >= base && e <= base + 16) {                       // the whole segment lies in this chunk
+        if (SHARED && s >= base && e <= base + 16 && mk[j] == sa.stamp) {   // a marked row: this column's sum is added (pad lanes: +0)
+            atomic_add4(sa.table16 + (size_t)r[j].x * SLOT + 4 * q, (float)(-lr * a0), (float)(-lr * a1), (float)(-lr * a2), (float)(-lr * a3));
+        } else if (s >= base && e <= base + 16) {                // the whole segment lies in this chunk
             float4 o = make_float4((float)((double)wold[j].x * cs[j] - lr * a0), (float)((double)wold[j].y * cs[j] - lr * a1),
                                    (float)((double)wold[j].z * cs[j] - lr * a2), (float)((double)wold[j].w * cs[j] - lr * a3));
             if (lim < 4) {                                       // pad lanes of the row keep what they hold
@@ -2150,6 +2160,7 @@ __device__ __forceinline__ void scat1h_body(const ScatArgs& sa, const int blk)
         a0 = a1 = a2 = a3 = 0;
     }
 }
+__device__ __forceinline__ void scat1h_body(const ScatArgs& sa, const int blk) { scat1h_form<false>(sa, blk); }
 
 static __global__ __launch_bounds__(256) void k_scat1(const ScatArgs sa)
 {
@@ -2257,7 +2268,10 @@ __device__ __forceinline__ void scat2w_batch(const double* __restrict__ part, co
 // adds the sums S_g with g = j (mod 4) in scat2_body's order, S_g = (((0 + P_g) + P_{g+16}) + P_{g+32}) + ..., and then every
 // lane folds tot = ((0 + S_0) + S_1) + ... + S_15, taking the twelve sums of the other quarters from their lanes: the same f64
 // expressions, the same bits (tests/test_gpu_scat2_forms.py).  Control flow is wave-uniform; lanes of quarter 0 with l < K store.
-__device__ __forceinline__ void scat2w_body(const ScatArgs& sa, const int blk, const int nblk)
+// SHARED: as in scat1h_form -- the owner row's mark goes out with its old value and the partial sums, and a marked row takes
+// -lr * tot as one float atomic per live slot.
+template <bool SHARED>
+__device__ __forceinline__ void scat2w_form(const ScatArgs& sa, const int blk, const int nblk)
 {
     const double* __restrict__ part = sa.part; const double* __restrict__ cpow = sa.cpow; const double lr = sa.lr;
     const int lane = threadIdx.x & 63, j = lane >> 4, l = lane & 15;
@@ -2272,15 +2286,19 @@ __device__ __forceinline__ void scat2w_body(const ScatArgs& sa, const int blk, c
         float* p = sa.table16 + (size_t)ow.w * SLOT + l;
         const float wold = *p;                               // every lane: all 16 floats of the row exist, no branch around the loads
         const double cdec = cpow[ow.z - ow.y];
+        int mk = 0;
+        if (SHARED) mk = sa.tag_shared[ow.w];
         double S[4] = {0.0, 0.0, 0.0, 0.0};
         if (q1 - q0 < 16) scat2w_batch<1>(part, fq, q0, q1, q0, j, l, S);
         else for (int qb = q0; qb <= q1; qb += 64) scat2w_batch<4>(part, fq, q0, q1, qb, j, l, S);
         double tot = 0.0;
 #pragma unroll
         for (int g = 0; g < 16; ++g) tot += (g & 3) ? lane_from(S[g >> 2], (g & 3) * 16 + l) : S[g >> 2];   // quarter 0 holds S_0, S_4, ...
-        if (j == 0 && l < sa.K) *p = (float)((double)wold * cdec - lr * tot);
+        if (SHARED && mk == sa.stamp) { if (j == 0 && l < sa.K) atomicAdd(p, (float)(-lr * tot)); }
+        else if (j == 0 && l < sa.K) *p = (float)((double)wold * cdec - lr * tot);
     }
 }
+__device__ __forceinline__ void scat2w_body(const ScatArgs& sa, const int blk, const int nblk) { scat2w_form<false>(sa, blk, nblk); }
 enum { SCAT2_BLOCK = 0, SCAT2_WAVE = 1 };                    // ScatArgs::form2: scat2_body / scat2w_body
 // FNN_SCAT2_FORM=block|wave, read where a handle is created; unset or unknown: `dflt` -- wave, which was measured a gain or
 // level for every user of the body (profiles/scat2_wave_ab.json)

@@ -1,8 +1,13 @@
 """Loader interface #2: the iPinYou "yzx" readers of the reference's python/ipinyou.py
 (`collect`, `stat`, `load_ipinyou_data`, `feed_zero`), same names, arguments and return values.
-Line format: `y z idx:val idx:val ...` (token 1, `z`, is skipped).  Host logic only; the TF FM/LR
-driver under `__main__` in the reference is out of scope.
+Line format: `y z idx:val idx:val ...` (token 1, `z`, is skipped).  The loaders are host logic; `run` is the
+reference's FM / LR driver (python/ipinyou.py:113-199) on the device: `to_column_ids` turns the loaders' positional
+arrays into the ids of FM / LR with `shared_rows=True`, where a column is a position of the line and not a field.
 """
+import os
+import sys
+import time
+
 import numpy as np
 
 
@@ -97,3 +102,128 @@ def to_field_ids(X_ind, X_val, field_of_row):
         rows = X_ind[present, j]
         ids[np.nonzero(present)[0], field_of_row[rows]] = rows
     return ids
+
+
+def to_column_ids(X_ind, X_val):
+    """Bridge to FM / LR with shared_rows=True: the output of load_ipinyou_data / feed_zero / load_ipinyou_file unchanged ->
+    (ids int32 [n, max_fea], wts).  Column j is position j of the line (python/ipinyou.py:42-65), X_val == 0 (the pads) becomes
+    id -1; wts is None when every present value is 1, else X_val as float32.  Nothing is dropped: a row may sit under any
+    number of columns of a batch, which is what shared_rows is for."""
+    X_ind, X_val = np.asarray(X_ind), np.asarray(X_val)
+    present = X_val != 0
+    ids = np.where(present, X_ind, -1).astype(np.int32)
+    wts = None if (X_val[present] == 1).all() else np.ascontiguousarray(X_val, dtype=np.float32)
+    return np.ascontiguousarray(ids), wts
+
+
+def exact_auc(labels, preds):
+    """roc_auc_score (ties at 1/2) of a buffer's training predictions for the log line; -1 with one class only, as
+    python/ipinyou.py:100-103 logs it."""
+    labels, preds = np.asarray(labels) != 0, np.asarray(preds, dtype=np.float64)
+    n1 = int(labels.sum())
+    n0 = len(labels) - n1
+    if n0 == 0 or n1 == 0:
+        return -1
+    _, inv, cnt = np.unique(preds, return_inverse=True, return_counts=True)
+    rank = (np.cumsum(cnt) - (cnt - 1) / 2.0)[inv]           # mean rank of a tie group, 1-based
+    return (rank[labels].sum() - n1 * (n1 + 1) / 2.0) / (n0 * float(n1))
+
+
+def run(train_path, test_path, algo='FM', batch_size=4096, buffer=10000, eval_size=100000, epochs=1, log_file=None, device=0,
+        echo=True):
+    """python/ipinyou.py:113-199, the FM / LR driver, on the device.  `stat` both files, X_dim = max + 2, X_feas = the longest
+    line; LR (:133) or FM rank 10 (:139-140) with the reference's init, optimiser and L2 weight and shared_rows=True; per pass
+    over the training file, buffers of `buffer` shuffled lines (load_ipinyou_data) in mini-batches of `batch_size`, each one
+    train_step; after every buffer the test file is evaluated on the device (fm_eval) in chunks of eval_size lines, at most
+    10 * eval_size of them (:196), and watch_train's line `step\tbatch_auc\teval_auc\tloss\t` is written to log_file.
+    Differences from the reference: batch_size is a parameter (its 1 is allowed; a buffer's tail shorter than batch_size is one
+    shorter step), `epochs` passes instead of an endless loop, every buffer is evaluated (the reference skips a short last
+    one) and a last test chunk shorter than eval_size counts.  Lines longer than fm_create's 64 columns raise ValueError.
+    Returns {'model', 'log': [(step, batch_auc, eval_auc, loss)], 'X_dim', 'X_feas'}."""
+    from .FM import FM
+    from .LR import LR
+    X_dim_train, X_feas_train = stat(train_path)
+    X_dim_test, X_feas_test = stat(test_path)
+    X_dim = max(X_dim_train, X_dim_test) + 2
+    X_feas = max(X_feas_train, X_feas_test)
+    if X_feas > 64:
+        raise ValueError("the longest line has %d features: FM / LR take at most 64 columns (fm_create)" % X_feas)
+    if batch_size < 1 or batch_size > 4096:
+        raise ValueError("batch_size %d: one step takes 1..4096 examples" % batch_size)
+    max_eval = min(eval_size, 4096)
+    if 'LR' in algo:
+        model = LR(batch_size, [X_dim, X_feas], ['uniform', -0.001, 0.001, [0x89AB], None], ['sgd', 1e-3], [1e-3],
+                   'train', max_eval, device, shared_rows=True)
+    elif 'FM' in algo:
+        model = FM(batch_size, [X_dim, X_feas, 10], ['uniform', -0.001, 0.001, [0x3210, 0x7654], None], ['sgd', 1e-3],
+                   [1e-2], 'train', max_eval, device, shared_rows=True)
+    else:
+        raise ValueError("algo %r: 'LR' or 'FM'" % (algo,))
+
+    def write_log(line):
+        if log_file:
+            with open(log_file, 'a') as f:
+                f.write(line + '\n')
+        if echo:
+            print(line)
+
+    write_log(model.log)
+    history = []
+    for it in range(epochs):
+        step = 0
+        start_time = time.time()
+        with open(train_path) as train_data_set:
+            while True:
+                X_ind, X_val, labels = load_ipinyou_data(train_data_set, buffer, X_dim - 1, X_feas)
+                if X_ind is None:
+                    break
+                ids, wts = to_column_ids(X_ind, X_val)
+                preds, loss = [], float('nan')
+                for lo in range(0, len(labels), batch_size):
+                    out = model.train_step(ids[lo:lo + batch_size], labels[lo:lo + batch_size], want_p=True,
+                                           wts=None if wts is None else wts[lo:lo + batch_size])
+                    preds.append(out['p'].cpu().numpy())
+                    loss = out['loss']
+                step += len(labels)
+                if echo:
+                    print('step: %d\ttime: %d\tloss: %g' % (step, time.time() - start_time, loss))
+                e_ids, e_wts, e_y = [], [], []
+                with open(test_path) as test_data_set:
+                    while sum(len(v) for v in e_y) < 10 * eval_size:
+                        t_ind, t_val, t_y = load_ipinyou_data(test_data_set, eval_size, X_dim - 1, X_feas)
+                        if t_ind is None:
+                            break
+                        e_ids.append(t_ind), e_wts.append(t_val), e_y.append(t_y)
+                eval_auc = -1
+                if e_y:
+                    t_ids, t_wts = to_column_ids(np.concatenate(e_ids), np.concatenate(e_wts))
+                    try:
+                        eval_auc = model.evaluate(t_ids, np.concatenate(e_y), wts=t_wts)[0]
+                    except RuntimeError as e:                          # one class only: -1, as watch_train logs it
+                        if getattr(e, 'code', None) != -4 or 'one class' not in str(e):
+                            raise
+                batch_auc = exact_auc(labels, np.concatenate(preds))
+                history.append((step, batch_auc, eval_auc, loss))
+                write_log('%d\t%g\t%g\t%g\t' % (step, batch_auc, eval_auc, loss))
+                start_time = time.time()
+    return {'model': model, 'log': history, 'X_dim': X_dim, 'X_feas': X_feas}
+
+
+if __name__ == '__main__':
+    # python/ipinyou.py:113-127: the campaign's yzx files under DEEPCTR_DATA_DIR (default ../data, as FNN.py), the log under
+    # DEEPCTR_LOG_DIR (default ../log/); `python ipinyou.py [FM|LR] [batch_size]`
+    sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
+    from deep_ctr_amd import ipinyou as _drv
+    cam = 'all'
+    data_dir = os.environ.get('DEEPCTR_DATA_DIR', '../data')
+    algo = sys.argv[1] if len(sys.argv) > 1 else 'FM'
+    tag = (str(cam) + ' ' + time.strftime('%c') + ' ' + algo).replace(' ', '_')
+    log_dir = os.environ.get('DEEPCTR_LOG_DIR', '../log/')
+    if not os.path.exists(log_dir):
+        os.makedirs(log_dir)
+    print(os.path.join(log_dir, tag))
+    _drv.run(os.path.join(data_dir, 'ipinyou-data/%s/train.yzx.txt.shuf' % cam),
+             os.path.join(data_dir, 'ipinyou-data/%s/test.yzx.txt.shuf' % cam), algo,
+             batch_size=int(sys.argv[2]) if len(sys.argv) > 2 else 4096,
+             buffer=100000 if 'LR' in algo else 10000, epochs=int(os.environ.get('DEEPCTR_EPOCHS', 1)),
+             log_file=os.path.join(log_dir, tag))

@@ -23,11 +23,24 @@
  * so that every row piece is one 16-byte access, a half or quarter wave per example in the forward, 16 fields at a time.  The
  * library picks the layout from k; padding columns are zero and stay zero.  The host sees [n_rows, k] either way.
  *
- * A row id belongs to ONE field (iPinYou: every field owns its own range of ids).  The update groups a batch's entries per
- * field: inside a field, repeated rows sum their gradients in example order; a row that appears under two fields of one
- * batch is updated by two unordered read-modify-writes in one launch, so one field's contribution can be lost (both
- * layouts; not checked).  Predictions and the loss are exact for any ids.  Of the ranks, only 15 (k = 16) does not feed the FNN
- * step: fnn_create refuses k = 16 (its other limits: fnn_hip.h).
+ * Columns and rows.  The update groups a batch's entries per column ("field"): inside a column, repeated rows sum their
+ * gradients in example order (f64) and the row takes one rounded store.  By default a row id must belong to ONE column of a
+ * batch (iPinYou with a field per column: every field owns its own range of ids); a row under two columns would be updated by two
+ * unordered read-modify-writes in one launch and could lose one of them (not checked).  fm_set_shared_rows(h, 1) lifts this:
+ * columns are then mere positions, as in the reference, whose classes have no fields (python/FM.py:23-29 takes batch_size *
+ * X_feas (id, weight) pairs and embedding_lookup_sparse sums whatever it is given; python/ipinyou.py:42-65 lists a line's
+ * features in line order, so a missing field shifts the rest one column left and a multi-valued field takes several).  With the
+ * mode on, a training step is correct for ANY ids in [-1, n_rows), all optimisers, both layouts, with or without weights:
+ *   - a row under several columns of a batch receives every column's contribution; a row twice on one line is two columns;
+ *   - a row held by one column of the batch takes the same single rounded store as with the mode off, and a batch in which no
+ *     row is shared leaves table, bias and optimiser state bit-identical to the mode being off;
+ *   - a shared row receives one f32 atomic add per (column, segment) of that segment's f64 sum (SGD: into the row, under the
+ *     lazy scale; Adam / FTRL: into the zeroed gradient store), in no fixed order: such rows are reproducible to f32 rounding,
+ *     not bit for bit (a bit-reproducible form would need a second grouping across columns);
+ *   - the narrow rows (k <= 16) run the half-chunk level 1 and the wave-per-segment level 2 of the sparse-row update in their
+ *     shared-row forms whatever FNN_SCAT1_FORM / FNN_SCAT2_FORM say.
+ * With the mode off nothing changes.  Predictions, the loss, fm_predict* and fm_eval* are exact for any ids in either mode.
+ * Of the ranks, only 15 (k = 16) does not feed the FNN step: fnn_create refuses k = 16 (its other limits: fnn_hip.h).
  *
  * The L2 term makes TensorFlow's gradient DENSE: every step multiplies the whole table by
  * (1 - lr * lambda).  Here the table is kept as `scale * stored` -- the decay is one scalar
@@ -98,6 +111,15 @@ int fm_set_optimizer(fm_handle* h, int optimizer, float beta1, float beta2, floa
 /* HOST pointers, each nullable.  s0 / s1 [n_rows, k]: Adam (m, v), FTRL (accum, linear); sb [2]: the bias's; t: steps
  * taken since the state was initialised.  FNN_ERR_STATE under SGD. */
 int fm_get_opt_state(fm_handle* h, float* s0, float* s1, float* sb, int64_t* t);
+/* Rows shared between columns of a batch (see "Columns and rows" above).  on != 0: the rank merge of every training step marks
+ * the rows that sit under more than one column, and the update adds into those with float atomics.  Off by default; legal at any
+ * time between steps.  On allocates -- now, or at the next fm_set_table -- and zeroes two int arrays [n_rows] (8 bytes per row);
+ * off keeps them for a later on and returns the handle to the launches it ran before. */
+int fm_set_shared_rows(fm_handle* h, int on);
+/* n_out (HOST): the number of rows the LAST training step found under more than one column -- how ragged the feed is.  A scan
+ * of the marks, run on demand and not part of the step; synchronises.  FNN_ERR_STATE while the mode is off, and before the first
+ * training step after fm_set_shared_rows turned it on or fm_set_table replaced the table. */
+int fm_count_shared_rows(fm_handle* h, int64_t* n_out);
 /* DEVICE pointers ids [N, F], y [N] (0 / non-zero).  Predictions in chunks of max_batch, then exact AUC (ties at 1/2),
  * RMSE and logloss (p clipped to [2^-52, 1 - 2^-52]) on the device.  Outputs nullable.  FNN_ERR_RANGE when y holds one
  * class only (auc undefined; rmse and logloss are still written), and when any prediction is NaN or outside [0, 1] (a diverged

@@ -18,7 +18,13 @@ same build is what the weights cost.  `criteo`: synth.criteo_like -- the first 1
 ONE row each with a real weight, the rest are categorical with weight 1 (as tools/ipnn_wide_bench.py --weights criteo).
 
 --fields N (1..64, default 16): the same 937,670 rows spread over N fields -- synth.field_sizes_ipinyou(n_fields=N) cycles the
-16 iPinYou-like field sizes over the N fields and rescales them to the same total.  16 is the shape above, unchanged."""
+16 iPinYou-like field sizes over the N fields and rescales them to the same total.  16 is the shape above, unchanged.
+
+--shared-rows: fm_set_shared_rows(h, 1) before the steps -- the rank merge claims rows, the update loads their marks.  On the
+default ids no row is shared: the step time against a run without the switch is the price of the claims and the mark loads, and
+the digest is the same.  --shift FRAC: that fraction of the lines loses its first feature and moves one column left (the last
+column becomes -1), as a yzx line with a missing field does: rows then sit under two columns of a batch and take the float
+atomics (needs --shared-rows to be right; `shared_rows_last_step` reports how many rows the last step found shared)."""
 import argparse
 import ctypes as C
 import glob
@@ -99,7 +105,16 @@ def weight_bytes(B):
     return B * F * 4
 
 
-def run(names, steps, warmup, B0, want_digest=False, weights='none'):
+def shift_left(ids, frac, seed=97):
+    """A fraction of the lines moves one column left: column j takes column j + 1's id, the last column is empty."""
+    ids = ids.copy()
+    pick = np.random.RandomState(seed).uniform(size=len(ids)) < frac
+    ids[pick, :-1] = ids[pick, 1:]
+    ids[pick, -1] = -1
+    return ids
+
+
+def run(names, steps, warmup, B0, want_digest=False, weights='none', shared_rows=False, shift=0.0):
     import torch
     sizes, D = shape()
     from deep_ctr_amd import _capi, synth
@@ -120,6 +135,8 @@ def run(names, steps, warmup, B0, want_digest=False, weights='none'):
             ids_h, w_h = synth.criteo_like(NB * B, n_num, sizes[n_num:], seed=99)
         elif weights == 'uniform':
             w_h = np.random.RandomState(98).uniform(0.0, 2.0, size=ids_h.shape).astype(np.float32)
+        if shift > 0:
+            ids_h = shift_left(ids_h, shift)
         ids = torch.as_tensor(ids_h).to(dev).contiguous()
         wts = None if w_h is None else torch.as_tensor(w_h).to(dev).contiguous()
         y = torch.as_tensor((np.random.RandomState(3).uniform(size=NB * B) < 0.02).astype(np.float32)).to(dev)
@@ -132,6 +149,8 @@ def run(names, steps, warmup, B0, want_digest=False, weights='none'):
         for rc in (lib.fm_set_optimizer(h, opt, 0.9, 0.999, 1e-8), lib.fm_set_table(h, rows.ctypes.data, D), lib.fm_set_b(h, 0.0)):
             if rc != 0:
                 raise RuntimeError(lib.fm_last_error(h).decode())
+        if shared_rows and lib.fm_set_shared_rows(h, 1) != 0:
+            raise RuntimeError(lib.fm_last_error(h).decode())
 
         def steps_(n):
             for i in range(n):
@@ -155,6 +174,11 @@ def run(names, steps, warmup, B0, want_digest=False, weights='none'):
         if wts is not None:
             rw = SLOT if K <= 16 else rup4(K)
             r.update({'weight_bytes': weight_bytes(B), 'weight_share_of_forward_bytes': weight_bytes(B) / float(2 * B * F * rw * 4)})
+        if shared_rows:
+            n_sh = C.c_int64()
+            if lib.fm_count_shared_rows(h, C.byref(n_sh)) != 0:
+                raise RuntimeError(lib.fm_last_error(h).decode())
+            r['shared_rows_last_step'] = int(n_sh.value)
         if want_digest:
             r['sha256'] = digest(lib, h, D, K, opt)
         lib.fm_destroy(h)
@@ -166,6 +190,8 @@ def run(names, steps, warmup, B0, want_digest=False, weights='none'):
            'device': torch.cuda.get_device_name(0), 'configs': out}
     if weights != 'none':
         res.update({'weights': weights, 'numeric_fields': n_num})
+    if shared_rows or shift > 0:
+        res.update({'shared_rows': bool(shared_rows), 'shift': shift})
     return res
 
 
@@ -212,6 +238,8 @@ def main():
     ap.add_argument('--fields', type=int, default=16)
     ap.add_argument('--weights', choices=('none', 'uniform', 'criteo'), default='none',
                     help='value weights of the steps (fm_train_step_w); none = the call without weights')
+    ap.add_argument('--shared-rows', action='store_true', help='fm_set_shared_rows(h, 1): rows may sit under several columns')
+    ap.add_argument('--shift', type=float, default=0.0, help='fraction of the lines moved one column left (shared rows)')
     a = ap.parse_args()
     global F
     F = a.fields
@@ -222,7 +250,7 @@ def main():
     for n in names:
         if n not in CONFIGS:
             raise SystemExit('unknown config %r (%s)' % (n, ', '.join(CONFIGS)))
-    print(json.dumps(run(names, a.steps, a.warmup, a.batch, a.digest, a.weights)))
+    print(json.dumps(run(names, a.steps, a.warmup, a.batch, a.digest, a.weights, a.shared_rows, a.shift)))
 
 
 if __name__ == '__main__':
