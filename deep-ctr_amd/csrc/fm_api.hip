@@ -16,7 +16,7 @@
 
 #include "../../include/fm_hip.h"
 #include "../../include/fnn_hip.h"
-#include "fnn_step_kernels.hip.h"
+#include "sparse_rows.hip.h"
 #include "metrics.hip.h"
 #include "optim.hip.h"
 
@@ -416,7 +416,7 @@ struct fm_handle {
     int* noshare = nullptr;    // wide path: [n_rows] zeros, the scatter's tag_shared (every row takes the plain read-modify-write)
     float* table16 = nullptr; int64_t n_rows = 0; float* b = nullptr; double scale = 1.0;
     float *gxp = nullptr, *loss_t = nullptr, *gb_part = nullptr, *loss_dev = nullptr; int* err_flag = nullptr;
-    int4* rec = nullptr; double* part = nullptr; int4* owners = nullptr; int* owner_cnt = nullptr; void* skeys = nullptr;
+    RowGroupBufs rg; void* skeys = nullptr;     // the batch's grouping (sparse_rows.hip.h); skeys: phase-A output of the split sort
     double* cpow1 = nullptr; bool key64 = true;
     // Adam / FTRL (fm_set_optimizer): compact state s0 / s1 [n_rows, K], the bias's sb [2], gradient store G [n_rows, rw],
     // stamp [n_rows]; t = steps since the state was initialised.  dense_g: FM_OPT_DENSE_G=1, the A/B variant of k_fm_opt_pass.
@@ -548,21 +548,17 @@ int fm_run_wide(fm_handle* h, FmArgs a, int B, float lr, float lambda, int reduc
         MHK(h, hipGetLastError());
         return FNN_OK;
     }
-    SortArgs so{a.ids, B, F, h->n_rows, h->rec, h->owner_cnt, 4 * F, h->skeys};
+    SortArgs so{a.ids, B, F, h->n_rows, h->rg.rec, h->rg.owner_cnt, 4 * F, h->skeys};
     so.merge4 = h->sort_merge4;
     SortArgs sb = so; sb.nblk = 16 * F;
     set_claim(h, sb);
-    if (h->key64) {
-        hipLaunchKernelGGL((k_sortA<unsigned long long>), dim3(4 * F), dim3(256), sortA_lds_bytes<unsigned long long>(so.merge4), h->st, so);
-        launch_fwd<unsigned long long>(h, &sb, a, Ba / ex);
-    } else {
-        hipLaunchKernelGGL((k_sortA<unsigned>), dim3(4 * F), dim3(256), sortA_lds_bytes<unsigned>(so.merge4), h->st, so);
-        launch_fwd<unsigned>(h, &sb, a, Ba / ex);
-    }
+    launch_sort_runs(h->st, h->key64, so);
+    if (h->key64) launch_fwd<unsigned long long>(h, &sb, a, Ba / ex);
+    else launch_fwd<unsigned>(h, &sb, a, Ba / ex);
     // SGD: the dense decay is the lazy scale, touched rows -= lr * g / scale; Adam / FTRL: G[row] = G[row] - (-1) * sum
     if (!opt) h->scale *= 1.0 - (double)lr * (double)lambda;
-    ScatArgs sa{h->rec, SORT_N, F, h->K, h->gxp, h->K1p, h->cpow1, opt ? -1.0 : (double)lr / h->scale, opt ? h->G : h->table16,
-                h->part, h->owner_cnt, h->owners, h->rw, h->shared ? h->tag_shared : h->noshare, h->shared ? sb.stamp : 1, h->rw};
+    ScatArgs sa = scat_args(h->rg, SORT_N, F, h->K, h->gxp, h->K1p, h->cpow1, opt ? -1.0 : (double)lr / h->scale, opt ? h->G : h->table16, h->rw);
+    sa.tag_shared = h->shared ? h->tag_shared : h->noshare; sa.stamp = h->shared ? sb.stamp : 1; sa.gxf = h->rw;
     const int nthr = F * (SORT_N / WCH) * (h->rw / 4);
     hipLaunchKernelGGL(k_fm_scatw1, dim3((nthr + 255) / 256), dim3(256), 0, h->st, sa);
     hipLaunchKernelGGL(k_fm_scatw2_tail, dim3(1 + 256), dim3(256), 0, h->st, sa, h->b, h->gb_part, Ba / ex, lr, lambda, h->loss_t, Ba,
@@ -633,20 +629,16 @@ int fm_run(fm_handle* h, const int32_t* ids, const float* wts, const float* y, i
         return FNN_OK;
     }
     {
-        SortArgs so{ids, B, F, h->n_rows, h->rec, h->owner_cnt, 4 * F, h->skeys};
+        SortArgs so{ids, B, F, h->n_rows, h->rg.rec, h->rg.owner_cnt, 4 * F, h->skeys};
         so.merge4 = h->sort_merge4;
         SortArgs sb = so; sb.nblk = 16 * F;
         set_claim(h, sb);
-        if (h->key64) {
-            hipLaunchKernelGGL((k_sortA<unsigned long long>), dim3(4 * F), dim3(256), sortA_lds_bytes<unsigned long long>(so.merge4), h->st, so);
-            launch_fwd<unsigned long long>(h, &sb, a, Ba / 16);
-        } else {
-            hipLaunchKernelGGL((k_sortA<unsigned>), dim3(4 * F), dim3(256), sortA_lds_bytes<unsigned>(so.merge4), h->st, so);
-            launch_fwd<unsigned>(h, &sb, a, Ba / 16);
-        }
+        launch_sort_runs(h->st, h->key64, so);
+        if (h->key64) launch_fwd<unsigned long long>(h, &sb, a, Ba / 16);
+        else launch_fwd<unsigned>(h, &sb, a, Ba / 16);
     }
     if (opt) {   // Adam / FTRL: the same sorted sums land in the zeroed gradient store: G[row] = 0 * 1 - (-1) * sum
-        ScatArgs sa{h->rec, SORT_N, F, h->K, h->gxp, h->K1p, h->cpow1, -1.0, h->G, h->part, h->owner_cnt, h->owners, SLOT};
+        ScatArgs sa = scat_args(h->rg, SORT_N, F, h->K, h->gxp, h->K1p, h->cpow1, -1.0, h->G, SLOT);
         launch_scat(h, sa, Ba, B, lr, lambda, reduce_mean, FmBiasOpt{h->opt, h->sb, lr_step, h->beta1, h->beta2, h->eps});
         launch_opt_pass(h, lambda, lr_step);
         MHK(h, hipGetLastError());
@@ -654,8 +646,7 @@ int fm_run(fm_handle* h, const int32_t* ids, const float* wts, const float* y, i
     }
     // dense L2 decay of the whole table = one scalar; touched rows: stored -= lr * g / scale
     h->scale *= 1.0 - (double)lr * (double)lambda;
-    ScatArgs sa{h->rec, SORT_N, F, h->K, h->gxp, h->K1p, h->cpow1, (double)lr / h->scale, h->table16, h->part, h->owner_cnt,
-                h->owners, SLOT};
+    ScatArgs sa = scat_args(h->rg, SORT_N, F, h->K, h->gxp, h->K1p, h->cpow1, (double)lr / h->scale, h->table16, SLOT);
     launch_scat(h, sa, Ba, B, lr, lambda, reduce_mean, FmBiasOpt{FM_OPT_SGD, nullptr, 0.f, 0.f, 0.f, 0.f});
     MHK(h, hipGetLastError());
     if (h->scale < 5.96e-8 || h->scale > 1.0) return fold_scale(h);
@@ -689,10 +680,7 @@ int fm_create(int n_fields, int k, int max_batch, int device, void* stream, fm_h
     FK(al((void**)&h->gxp, Ba * h->K1p * 4)); FK(al((void**)&h->loss_t, Ba * 4)); FK(al((void**)&h->gb_part, (Ba / 8) * 4));
     FK(al((void**)&h->loss_dev, 4)); FK(al((void**)&h->b, 4)); FK(al((void**)&h->err_flag, 4)); FK(al((void**)&h->sb, 8));
     FK(al((void**)&h->mark_cnt, 8));
-    // level-1 partial sums: two per chunk of 16 (narrow) or WCH (wide) sorted entries, a row each
-    const size_t part_rows = h->wide ? (size_t)h->F * (SORT_N / WCH) * 2 : (size_t)h->F * (SORT_N / 16) * 2;
-    FK(al((void**)&h->rec, (size_t)h->F * SORT_N * sizeof(int4))); FK(al((void**)&h->part, part_rows * h->rw * 8));
-    FK(al((void**)&h->owners, (size_t)h->F * (SORT_N / 16) * sizeof(int4))); FK(al((void**)&h->owner_cnt, 4));
+    FK(row_group_alloc(h->rg, h->F, SORT_N, h->wide, h->rw, h->st, /*owners16*/ true));
     FK(al(&h->skeys, (size_t)h->F * SORT_N * 8));
     {
         std::vector<double> ones(SORT_N + 1, 1.0);                   // no per-touch decay: every power is 1
@@ -714,9 +702,10 @@ int fm_destroy(fm_handle* h)
     if (!h) return FNN_ERR_ARG;
     hipSetDevice(h->dev);
     if (h->st) hipStreamSynchronize(h->st);
-    void* ptrs[] = {h->table16, h->b, h->gxp, h->loss_t, h->gb_part, h->loss_dev, h->err_flag, h->rec, h->part, h->owners, h->owner_cnt,
-                    h->skeys, h->cpow1, h->s0, h->s1, h->sb, h->G, h->stamp, h->noshare, h->tag_first, h->tag_shared, h->mark_cnt};
+    void* ptrs[] = {h->table16, h->b, h->gxp, h->loss_t, h->gb_part, h->loss_dev, h->err_flag, h->skeys, h->cpow1, h->s0, h->s1,
+                    h->sb, h->G, h->stamp, h->noshare, h->tag_first, h->tag_shared, h->mark_cnt};
     for (void* p : ptrs) if (p) hipFree(p);
+    row_group_free(h->rg);
     if (h->own_stream && h->st) hipStreamDestroy(h->st);
     delete h;
     return FNN_OK;

@@ -77,8 +77,7 @@ struct fnn_handle {
     // the batch being trained and the slot the NEXT batch is grouped into during this step.
     // tag_shared / stamp: bag mode, the rows several columns of the slot's batch hold (SortArgs).  One array per slot: the rank
     // merge of batch n + 1 writes its marks in the same launch in which the update of batch n still reads its own.
-    struct SortSlot { int4* rec = nullptr; double* part = nullptr; int4* owners = nullptr; int* owner_cnt = nullptr;
-                      int* tag_shared = nullptr; int stamp = 0; };
+    struct SortSlot : RowGroupBufs { int* tag_shared = nullptr; int stamp = 0; };
     int* tag_first = nullptr; int tag_stamp = 0;
     SortSlot slot[2]; int cur = 0;
     const int32_t* sorted_ids = nullptr; int sorted_B = 0;      // what slot[cur] holds (nullptr: nothing)
@@ -233,8 +232,9 @@ int wgrad_blocks(const WgradArgs& wa) {
     return wa.p[0].mt * wa.p[0].nt + wa.p[1].mt * wa.p[1].nt + wa.p[2].mt * wa.p[2].nt + wa.p[3].mt * wa.p[3].nt;
 }
 ScatArgs make_scat_args(fnn_handle* h, const fnn_handle::SortSlot& sl, int N2) {
-    return ScatArgs{sl.rec, N2, h->F, h->K, h->gxp, h->K1p, h->cpow_dev, (double)h->cfg.lr, h->table16,
-                    sl.part, sl.owner_cnt, sl.owners, h->rw, sl.tag_shared, sl.stamp, 0, 0, h->scat2_form};
+    ScatArgs sa = scat_args(sl, N2, h->F, h->K, h->gxp, h->K1p, h->cpow_dev, (double)h->cfg.lr, h->table16, h->rw);
+    sa.tag_shared = sl.tag_shared; sa.stamp = sl.stamp; sa.form2 = h->scat2_form;
+    return sa;
 }
 template <typename T> MlpArgs<T> make_mlp_args(fnn_handle* h, const int32_t* ids, const float* y, int B,
                                                 const uint8_t* m1, const uint8_t* m2, bool train, float* p_out) {
@@ -289,15 +289,8 @@ template <typename T> void launch_step1(fnn_handle* h, int nmlp, const MlpArgs<T
     }
 }
 void launch_sort16(fnn_handle* h, SortArgs so) {             // split sort: the runs, then the rank merge
-    const int F = so.nblk;
     so.merge4 = h->sort_merge4;
-    if (h->key64) {
-        hipLaunchKernelGGL((k_sortA<unsigned long long>), dim3(4 * F), dim3(256), sortA_lds_bytes<unsigned long long>(so.merge4), h->st, so);
-        hipLaunchKernelGGL((k_sortB<unsigned long long>), dim3(16 * F), dim3(256), SORT_N * 8, h->st, so);
-    } else {
-        hipLaunchKernelGGL((k_sortA<unsigned>), dim3(4 * F), dim3(256), sortA_lds_bytes<unsigned>(so.merge4), h->st, so);
-        hipLaunchKernelGGL((k_sortB<unsigned>), dim3(16 * F), dim3(256), SORT_N * 4, h->st, so);
-    }
+    launch_sort(h->st, h->key64, so);
 }
 
 // Launches 2 and 3 of a step.  `dense`: weight gradients / slab reduce (+ update); `sparse`: the
@@ -559,14 +552,7 @@ int run_step(fnn_handle* h, const int32_t* ids, const float* y, int B, const uin
 
     if (train) {   // A6 part 1: group the (row, t) pairs
         ProfScope ps(h, "sort", h->st);
-        const int kpt = N2 <= 4096 ? 4 : (N2 == 8192 ? 8 : 16);
-        const dim3 blk(N2 / kpt);
-        if (kpt == 4)
-            hipLaunchKernelGGL(k_sort<4>, dim3(F), blk, (size_t)N2 * 8, h->st, ids, B, F, h->n_rows, N2, sl.rec, sl.owner_cnt, h->shadow_dev, h->n_shadow, h->err_flag);
-        else if (kpt == 8)
-            hipLaunchKernelGGL(k_sort<8>, dim3(F), blk, (size_t)N2 * 8, h->st, ids, B, F, h->n_rows, N2, sl.rec, sl.owner_cnt, h->shadow_dev, h->n_shadow, h->err_flag);
-        else
-            hipLaunchKernelGGL(k_sort<16>, dim3(F), blk, (size_t)N2 * 8, h->st, ids, B, F, h->n_rows, N2, sl.rec, sl.owner_cnt, h->shadow_dev, h->n_shadow, h->err_flag);
+        launch_k_sort(h->st, N2, ids, B, F, h->n_rows, sl, h->shadow_dev, h->n_shadow, h->err_flag);
     }
     if (h->fused && mlp_shape_ok(h)) {
         ProfScope ps(h, "mlp", h->st);
@@ -679,14 +665,8 @@ int ensure_global_ws(fnn_handle* h, int B_g)
     HIPCHK(h, hipStreamSynchronize(h->st));
     if (N2 > h->gN2) {
         fnn_handle::SortSlot& sl = h->gsl;
-        for (void* q : {(void*)sl.rec, (void*)sl.part, (void*)sl.owners, (void*)sl.owner_cnt}) if (q) hipFree(q);
-        sl = fnn_handle::SortSlot();
-        int rc;
-        const size_t nchunk = h->wide ? (size_t)N2 / WCH : (size_t)N2 / 16;
-        if ((rc = alloc_dev(h, &sl.rec, (size_t)h->F * N2)) != FNN_OK) return rc;
-        if ((rc = alloc_dev(h, &sl.part, (size_t)h->F * nchunk * 2 * (h->wide ? h->rw : SLOT))) != FNN_OK) return rc;
-        if ((rc = alloc_dev(h, &sl.owners, (size_t)h->F * nchunk)) != FNN_OK) return rc;
-        if ((rc = alloc_dev(h, &sl.owner_cnt, (size_t)1)) != FNN_OK) return rc;
+        row_group_free(sl);
+        HIPCHK(h, row_group_alloc(sl, h->F, N2, h->wide, h->wide ? h->rw : SLOT, h->st));
         h->gN2 = N2;
     }
     if (h->cpow_cap < N2 + 1) {             // a row can be hit by every example of the global batch
@@ -717,21 +697,13 @@ int scatter_global_impl(fnn_handle* h, const int32_t* ids_g, const float* gxp_g,
             std::string err;
             if (group_global(h->st, ids_g, B_g, F, h->n_rows, N2, sl.rec, sl.owner_cnt, &h->gws, &h->gws_bytes, err) != 0)
                 FAIL(h, FNN_ERR_HIP, err);
-        } else {
-            const int kpt = N2 <= 4096 ? 4 : (N2 == 8192 ? 8 : 16);
-            const dim3 blk(N2 / kpt);
-            if (kpt == 4) hipLaunchKernelGGL(k_sort<4>, dim3(F), blk, (size_t)N2 * 8, h->st, ids_g, B_g, F, h->n_rows, N2, sl.rec, sl.owner_cnt, nullptr, 0, h->err_flag);
-            else if (kpt == 8) hipLaunchKernelGGL(k_sort<8>, dim3(F), blk, (size_t)N2 * 8, h->st, ids_g, B_g, F, h->n_rows, N2, sl.rec, sl.owner_cnt, nullptr, 0, h->err_flag);
-            else hipLaunchKernelGGL(k_sort<16>, dim3(F), blk, (size_t)N2 * 8, h->st, ids_g, B_g, F, h->n_rows, N2, sl.rec, sl.owner_cnt, nullptr, 0, h->err_flag);
-        }
+        } else launch_k_sort(h->st, N2, ids_g, B_g, F, h->n_rows, sl, nullptr, 0, h->err_flag);
     }
     {
         ProfScope ps(h, "scatter_global", h->st);
         ScatArgs sa = make_scat_args(h, sl, N2);
         sa.gxp = gxp_g;
-        const int nblk = scat1_blocks(sa, h->scat_form);     // after sa.gxp changed: the caller's buffer may not be 16-byte aligned
-        hipLaunchKernelGGL(k_scat1, dim3(nblk), dim3(256), 0, h->st, sa);
-        hipLaunchKernelGGL(k_scat2, dim3(N2 > 4096 ? 256 : 64), dim3(256), 0, h->st, sa);
+        launch_scat_narrow(h->st, sa, h->scat_form, N2 > 4096 ? 256 : 64);      // after sa.gxp changed: the caller's buffer may not be 16-byte aligned
     }
     HIPCHK(h, hipGetLastError());
     h->next_ids = nullptr; h->next_B = 0;       // no grouping of a later batch rides on this step
@@ -949,13 +921,7 @@ int fnn_create(const fnn_cfg* cfg, fnn_handle** out)
     CK(alloc_dev(h, (char**)&h->dl3T, Ba * 64 * ts));
     CK(alloc_dev(h, &h->loss_t, Ba));
     CK(alloc_dev(h, &h->loss_dev, (size_t)1));
-    for (auto& sl : h->slot) {
-        CK(alloc_dev(h, &sl.rec, (size_t)h->F * h->N2max));
-        const size_t nchunk = (h->bag || h->wide) ? (size_t)h->N2max / WCH : (size_t)h->N2max / 16;
-        CK(alloc_dev(h, &sl.part, (size_t)h->F * nchunk * 2 * h->rw));
-        CK(alloc_dev(h, &sl.owners, (size_t)h->F * nchunk));
-        CK(alloc_dev(h, &sl.owner_cnt, (size_t)1));
-    }
+    for (auto& sl : h->slot) HK(row_group_alloc(sl, h->F, h->N2max, h->bag || h->wide, h->rw, h->st));
     if (h->bag) {
         if (!mlp_shape_ok(h)) { h->err = "FNN_MODE_BAG needs hidden sizes the strip kernel is built for: hidden1 256..319 with hidden2 64..127 (e.g. 300/100) at any h0, or hidden1 <= 63 with hidden2 <= 63 at h0 <= 252"; return fail(FNN_ERR_ARG); }
         CK(alloc_dev(h, &h->bb0, (size_t)h->K1p));
@@ -1012,17 +978,14 @@ int fnn_destroy(fnn_handle* h)
     if (h->st) hipStreamSynchronize(h->st);
     if (h->comm && h->dp_own_comm && g_rccl.CommDestroy) g_rccl.CommDestroy(h->comm);
     p2p_release(h);
-    for (void* q : {(void*)h->tag_first, (void*)h->slot[0].tag_shared, (void*)h->slot[1].tag_shared, (void*)h->shadow_dev, (void*)h->xg_ids_send, (void*)h->xg_ids, (void*)h->xg_gxp, (void*)h->gsl.rec, (void*)h->gsl.part, (void*)h->gsl.owners,
-                    (void*)h->gsl.owner_cnt, h->gws}) if (q) hipFree(q);
+    for (void* q : {(void*)h->tag_first, (void*)h->slot[0].tag_shared, (void*)h->slot[1].tag_shared, (void*)h->shadow_dev, (void*)h->xg_ids_send, (void*)h->xg_ids, (void*)h->xg_gxp, h->gws}) if (q) hipFree(q);
     for (auto& kv : h->prof_slots) for (auto& p : kv.second.ev) { hipEventDestroy(p.first); hipEventDestroy(p.second); }
     void* ptrs[] = {h->table16, h->field_of_row, h->master, h->bucket, h->slab, h->w1, h->w1t, h->w2, h->w2t,
                     h->xp, h->xpT, h->d1, h->d1T, h->d2, h->dl2, h->dl2T, h->dl1, h->dl1T, h->gxp, h->p_buf,
                     h->loss_t, h->d2T, h->dl3T, h->loss_dev, h->cpow_dev, h->err_flag, h->ones_u8, h->skeys, h->bb0, h->dlxT, h->onesT, h->gx_raw,
                     h->st_ids, h->st_y, h->st_m1, h->st_m2, h->st_p, h->st_x};
     for (void* p : ptrs) if (p) hipFree(p);
-    for (auto& sl : h->slot) {
-        for (void* p : {(void*)sl.rec, (void*)sl.part, (void*)sl.owners, (void*)sl.owner_cnt}) if (p) hipFree(p);
-    }
+    for (fnn_handle::SortSlot* sl : {&h->slot[0], &h->slot[1], &h->gsl}) row_group_free(*sl);
     if (h->own_stream && h->st) hipStreamDestroy(h->st);
     delete h;
     return FNN_OK;

@@ -12,258 +12,9 @@
 // a 7-node hipGraph replay costs 46 us on this runtime, seven plain launches 18.5 us).
 #pragma once
 #include "fnn_kernels.hip.h"
+#include "sparse_rows.hip.h"      // the grouping and row-update roles of launches 2 and 3
 
 namespace fnn {
-
-// ------------------------------------------------------------------------------------------
-// Grouping role: a field's 4096 (row, t) keys sorted in two independent phases -- 16 runs of 256
-// keys, each bitonic-sorted inside ONE wave's registers, and (SortArgs::merge4) a workgroup's four runs
-// merged into one of 1024 (phase A), then a merge by rank in which every key finds its final place
-// and its segment [s, e) with binary searches over the 16 or 4 runs (phase B).  32-bit keys
-// (row << 12 | t) when n_rows * 4096 fits, else 64-bit.  Measured against
-// the single-kernel bitonic network it replaced: 34 us -> 2 x ~4 us of role time.
-// ------------------------------------------------------------------------------------------
-template <typename KT> struct KeyTraits;
-template <> struct KeyTraits<unsigned> { static constexpr int SH = 12; };
-template <> struct KeyTraits<unsigned long long> { static constexpr int SH = 32; };
-
-struct SortArgs {
-    const int32_t* ids; int B, F; int64_t n_rows; int4* rec; int* owner_cnt; int nblk; void* skeys;
-    // bag mode only (null otherwise): which rows of this batch sit in MORE THAN ONE column.  The grouping is per column, and a
-    // row's update is one read-modify-write per column segment -- two columns holding the same row (python/SNN_RBM.py:248-253
-    // lists a line's active features in line order, so a feature's column depends on the line) would race.  Every segment head
-    // claims its row with atomicMax(tag_first[row], stamp << 6 | column); a head that finds this batch's stamp already there
-    // under another column marks tag_shared[row] = stamp, and the update launches (at least one kernel boundary later) add
-    // into such rows with float atomics instead (scatw1_body / scatw2_body).  Stamps grow with every grouping: no reset pass.
-    int* tag_first; int* tag_shared; int stamp;
-    int merge4;      // 1: phase A leaves 4 runs of 1024 keys per field and phase B merges those (FNN_SORT_RUNS=4, the default); 0: 16 runs of 256
-};
-
-constexpr int SORT_N = 4096;     // keys per field handled by the union-kernel path (B <= 4096)
-
-template <typename KT> __host__ __device__ constexpr size_t sort_lds_bytes() { return (size_t)SORT_N * sizeof(KT); }
-// dynamic LDS of phase A (sortA_body): a workgroup's four wave runs, merged in place into one run of 1024 keys; none for the 16-run form
-template <typename KT> inline size_t sortA_lds_bytes(const int merge4) { return merge4 ? (size_t)1024 * sizeof(KT) : 0; }
-// FNN_SORT_RUNS=16|4, read where a handle is created: the runs per field that phase A leaves for the rank merge.  `dflt` (1: four
-// runs) is the handle's own choice: four where phase A rides beside longer roles (the FNN step on FM rows: 35.6 -> 33.6 us per
-// step) and in the inner-product step (level), sixteen where the longer phase A is a launch of its own in front of the merge
-// (FM pre-training: 29.3 -> 30.8 us with four) and in bag mode (the SNN step: 47.5 -> 48.1) -- profiles/step_stores16_sort4_ab.json
-inline int sort_merge4_env(const int dflt)
-{
-    const char* e = getenv("FNN_SORT_RUNS");
-    const int v = e ? atoi(e) : 0;
-    return v == 16 ? 0 : (v == 4 ? 1 : dflt);
-}
-
-// Invalid entries (t >= B, id outside the table) carry the all-ones row, so that every key of a
-// field is distinct (the rank merges below need a strict total order) and they sort to the end.
-template <typename KT> __device__ __forceinline__ KT inv_row() { return (~(KT)0) >> KeyTraits<KT>::SH; }
-
-// first index in the ascending run q[0 .. 1 << LOG) whose key is >= v (branch-free; q in LDS)
-template <typename KT, int LOG>
-__device__ __forceinline__ int lower_bound_pow2(const KT* q, const KT v) {
-    int base = 0;
-#pragma unroll
-    for (int s = 1 << (LOG - 1); s >= 1; s >>= 1) base += (q[base + s - 1] < v) ? s : 0;
-    return base + ((q[base] < v) ? 1 : 0);
-}
-
-// Phase A of the split sort: every wave bitonic-sorts a run of 256 keys in registers (4 per lane:
-// strides below 4 inside the lane, the rest wave shuffles -- no LDS, no barriers) and stores it.
-// One workgroup = 4 runs = a quarter of a field; so.nblk = 4 F.
-// so.merge4: the workgroup then merges its four wave runs by rank into ONE run of 1024 keys (LDS, one barrier: a key's place is
-// its index in its own run plus the keys below it in the three others, 27 reads each) -- the rank merge of phase B, the longest
-// role of its launch, then searches 4 runs of 1024 instead of 16 of 256: 11 searches per key instead of 48.
-// M4 = so.merge4 as a template parameter: the union launches are instantiated per form (see sortB_form).
-template <typename KT, bool M4>
-__device__ __forceinline__ void sortA_form(const SortArgs& so, const int blk, unsigned char* smem)
-{
-    constexpr int SH = KeyTraits<KT>::SH;
-    const int tid = threadIdx.x, wave = tid >> 6, lane = tid & 63, F = so.F, B = so.B;
-    const int f = blk >> 2, base = (blk & 3) * 1024 + wave * 256;
-    KT key[4];
-#pragma unroll
-    for (int a = 0; a < 4; ++a) {                             // initial order inside a run is free
-        const int t = base + a * 64 + lane;
-        KT row = inv_row<KT>();
-        if (t < B) {
-            const int64_t id = so.ids[(size_t)t * F + f];
-            if (id >= 0 && id < so.n_rows) row = (KT)id;
-        }
-        key[a] = (row << SH) | (KT)t;
-    }
-    const int i0 = lane * 4;                                  // position of key[0] in the run
-#pragma unroll
-    for (int k = 2; k <= 256; k <<= 1) {
-#pragma unroll
-        for (int j = k >> 1; j > 0; j >>= 1) {
-            if (j < 4) {
-#pragma unroll
-                for (int a = 0; a < 4; ++a) {
-                    const int b = a ^ j;
-                    if (b > a) {
-                        const bool up = ((i0 + a) & k) == 0;
-                        const KT x = key[a], y = key[b];
-                        const KT mn = x < y ? x : y, mx = x < y ? y : x;
-                        key[a] = up ? mn : mx; key[b] = up ? mx : mn;
-                    }
-                }
-            } else {
-                const bool keepmin = ((i0 & j) == 0) == ((i0 & k) == 0);
-#pragma unroll
-                for (int a = 0; a < 4; ++a) {
-                    const KT other = __shfl_xor(key[a], j >> 2);
-                    const KT mine = key[a];
-                    const KT mn = mine < other ? mine : other, mx = mine < other ? other : mine;
-                    key[a] = keepmin ? mn : mx;
-                }
-            }
-        }
-    }
-    if constexpr (M4) {
-        KT* s_run = reinterpret_cast<KT*>(smem);              // [4][256] the workgroup's wave runs
-#pragma unroll
-        for (int a = 0; a < 4; ++a) s_run[wave * 256 + i0 + a] = key[a];
-        __syncthreads();
-        int place[4];
-#pragma unroll
-        for (int a = 0; a < 4; ++a) place[a] = i0 + a;
-        // 12 searches (3 other runs x 4 keys) in lockstep: every step issues 12 independent LDS reads.  Keys are distinct, so
-        // "keys below" is the same strict order from both sides of a pair of runs.
-        int bq[3][4];
-#pragma unroll
-        for (int o = 0; o < 3; ++o)
-#pragma unroll
-            for (int a = 0; a < 4; ++a) bq[o][a] = ((wave + 1 + o) & 3) * 256;
-#pragma unroll
-        for (int st = 128; st >= 1; st >>= 1)
-#pragma unroll
-            for (int o = 0; o < 3; ++o)
-#pragma unroll
-                for (int a = 0; a < 4; ++a) bq[o][a] += s_run[bq[o][a] + st - 1] < key[a] ? st : 0;
-#pragma unroll
-        for (int o = 0; o < 3; ++o)
-#pragma unroll
-            for (int a = 0; a < 4; ++a)
-                place[a] += bq[o][a] - ((wave + 1 + o) & 3) * 256 + (s_run[bq[o][a]] < key[a] ? 1 : 0);
-        KT* out = static_cast<KT*>(so.skeys) + (size_t)f * SORT_N + (blk & 3) * 1024;
-#pragma unroll
-        for (int a = 0; a < 4; ++a) out[place[a]] = key[a];
-        return;
-    }
-    KT* out = static_cast<KT*>(so.skeys) + (size_t)f * SORT_N + base + i0;
-#pragma unroll
-    for (int a = 0; a < 4; ++a) out[a] = key[a];
-}
-template <typename KT>
-__device__ __forceinline__ void sortA_body(const SortArgs& so, const int blk, unsigned char* smem)
-{
-    if (so.merge4) sortA_form<KT, true>(so, blk, smem); else sortA_form<KT, false>(so, blk, smem);
-}
-
-// Phase B of the split sort: merge by RANK.  A key's place in the field's final order is its index
-// in its own run plus, for each of the 15 other runs, the number of keys below it (a 9-step binary
-// search in LDS); its segment [s, e) comes the same way: s = keys below (row, 0), e = keys below
-// (row + 1, 0).  Every key is independent -- one thread per key, 16 workgroups per field
-// (so.nblk = 16 F), one barrier -- instead of a 15 us chain of dependent merge stages.
-// M4: the runs are 4 of 1024 keys (so.merge4); a template parameter, because launch 3 carrying both forms behind a run-time
-// branch took 107 VGPRs against the 16-run form's 94 (gfx950, hipcc 7.2) -- the union launches are instantiated per form, so
-// that a handle on sixteen runs launches the code it launched before there were two.
-template <typename KT, bool M4>
-__device__ __forceinline__ void sortB_form(const SortArgs& so, const int blk, unsigned char* smem)
-{
-    constexpr int SH = KeyTraits<KT>::SH;
-    KT* s_key = reinterpret_cast<KT*>(smem);                 // [4096] the 16 sorted runs
-    const int tid = threadIdx.x, f = blk >> 4, run = blk & 15;
-    if (blk == 0 && tid == 0) *so.owner_cnt = 0;
-    const KT* in = static_cast<const KT*>(so.skeys) + (size_t)f * SORT_N;
-#pragma unroll
-    for (int a = 0; a < 16; ++a) s_key[a * 256 + tid] = in[a * 256 + tid];
-    __syncthreads();
-    const KT key = s_key[run * 256 + tid];
-    const KT row = key >> SH, lo_key = row << SH, hi_key = (row + 1) << SH;    // row + 1 wraps only for invalid entries
-    int pos = 0, s = 0, e = 0;
-    if constexpr (M4) {
-        // 4 runs of 1024 keys: the key's index in its own run plus its rank in the 3 others, and the ranks of lo_key / hi_key in
-        // all 4 -- 11 searches of 10 steps in lockstep (about 120 LDS reads against the 16-run form's 480)
-        const int own = run >> 2;
-        int bp[3], bs[4], be[4];
-#pragma unroll
-        for (int o = 0; o < 3; ++o) bp[o] = ((own + 1 + o) & 3) * 1024;
-#pragma unroll
-        for (int r = 0; r < 4; ++r) bs[r] = be[r] = r * 1024;
-#pragma unroll
-        for (int st = 512; st >= 1; st >>= 1) {
-#pragma unroll
-            for (int o = 0; o < 3; ++o) bp[o] += s_key[bp[o] + st - 1] < key ? st : 0;
-#pragma unroll
-            for (int r = 0; r < 4; ++r) {
-                const KT vs = s_key[bs[r] + st - 1], ve = s_key[be[r] + st - 1];
-                bs[r] += vs < lo_key ? st : 0; be[r] += ve < hi_key ? st : 0;
-            }
-        }
-        pos = (run & 3) * 256 + tid;
-#pragma unroll
-        for (int o = 0; o < 3; ++o) pos += bp[o] - ((own + 1 + o) & 3) * 1024 + (s_key[bp[o]] < key ? 1 : 0);
-#pragma unroll
-        for (int r = 0; r < 4; ++r) {
-            s += bs[r] - r * 1024 + (s_key[bs[r]] < lo_key ? 1 : 0);
-            e += be[r] - r * 1024 + (s_key[be[r]] < hi_key ? 1 : 0);
-        }
-    } else {
-        // 48 binary searches (16 runs x {key, lo_key, hi_key}) advance in lockstep, so that every step
-        // issues 48 independent LDS reads instead of one dependent read at a time.  The search of the
-        // key in its own run returns its own index, so no run is special.
-        int bp[16], bs[16], be[16];
-#pragma unroll
-        for (int r = 0; r < 16; ++r) bp[r] = bs[r] = be[r] = r * 256;
-#pragma unroll
-        for (int st = 128; st >= 1; st >>= 1) {
-#pragma unroll
-            for (int r = 0; r < 16; ++r) {
-                const KT vp = s_key[bp[r] + st - 1], vs = s_key[bs[r] + st - 1], ve = s_key[be[r] + st - 1];
-                bp[r] += vp < key ? st : 0; bs[r] += vs < lo_key ? st : 0; be[r] += ve < hi_key ? st : 0;
-            }
-        }
-#pragma unroll
-        for (int r = 0; r < 16; ++r) {
-            pos += bp[r] - r * 256 + (s_key[bp[r]] < key ? 1 : 0);
-            s += bs[r] - r * 256 + (s_key[bs[r]] < lo_key ? 1 : 0);
-            e += be[r] - r * 256 + (s_key[be[r]] < hi_key ? 1 : 0);
-        }
-    }
-    int4 rr = make_int4(-1, 0, 0, 0);
-    if (row != inv_row<KT>()) {
-        rr = make_int4((int)row, (int)(key & (((KT)1 << SH) - 1)), s, e);
-        if (so.tag_first && pos == s) {                            // head of its segment: one claim per (row, column)
-            const int mine = (so.stamp << 6) | f;
-            const int old = atomicMax(&so.tag_first[(size_t)row], mine);
-            if ((old >> 6) == so.stamp && old != mine) so.tag_shared[(size_t)row] = so.stamp;
-        }
-    }
-    so.rec[(size_t)f * SORT_N + pos] = rr;
-}
-template <typename KT>
-__device__ __forceinline__ void sortB_body(const SortArgs& so, const int blk, unsigned char* smem)
-{
-    if (so.merge4) sortB_form<KT, true>(so, blk, smem); else sortB_form<KT, false>(so, blk, smem);
-}
-
-// The split sort as two plain launches, for a batch nobody announced (fnn_prefetch_ids) and for
-// the inner-product family: 4 F then 16 F workgroups, ~7 us each instead of the 34 us single-kernel
-// bitonic network.
-template <typename KT>
-static __global__ __launch_bounds__(256) void k_sortA(const SortArgs so)
-{
-    extern __shared__ __align__(16) unsigned char smem[];
-    sortA_body<KT>(so, blockIdx.x, smem);
-}
-template <typename KT>
-static __global__ __launch_bounds__(256) void k_sortB(const SortArgs so)
-{
-    extern __shared__ __align__(16) unsigned char smem[];
-    sortB_body<KT>(so, blockIdx.x, smem);
-}
 
 // ------------------------------------------------------------------------------------------
 // step 1: MLP strips of this batch.  (At 256 VGPRs a strip workgroup fills its CU, so the sort

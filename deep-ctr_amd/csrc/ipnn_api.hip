@@ -16,7 +16,8 @@
 
 #include "../../include/fnn_hip.h"
 #include "../../include/ipnn_hip.h"
-#include "fnn_step_kernels.hip.h"
+#include "fnn_kernels.hip.h"
+#include "sparse_rows.hip.h"
 #include "metrics.hip.h"
 #include "optim.hip.h"
 
@@ -450,7 +451,7 @@ static __global__ __launch_bounds__(256) void k_ip_bwd_w(const IpWideArgs a, con
     if (threadIdx.x == 0) { float s = 0.f; for (int r = 0; r < IPW_EX; ++r) s += dz[(size_t)(t0 + r) * D0p + CB]; gb_part[blockIdx.x] = s; }
 }
 
-// the bag table's wide sparse-row update (fnn_kernels.hip.h) on wide rows: gradient of (example t, field f) at gx'[t][f rw + l]
+// the bag table's wide sparse-row update (sparse_rows.hip.h) on wide rows: gradient of (example t, field f) at gx'[t][f rw + l]
 static __global__ __launch_bounds__(256) void k_ip_scatw1(const ScatArgs sa) { scatw1_body(sa, blockIdx.x); }
 static __global__ __launch_bounds__(256) void k_ip_scatw2(const ScatArgs sa)
 {
@@ -1564,7 +1565,7 @@ struct ipnn_handle {
     float* emb = nullptr;                            // [ldT][F*rw] raw embeddings of the step's examples (forward -> backward)
     float *dz0 = nullptr, *gxp = nullptr, *gb_part = nullptr, *loss_t = nullptr, *loss_dev = nullptr, *slab = nullptr;
     int* ref0 = nullptr; int* err_flag = nullptr;
-    int4* rec = nullptr; double* part = nullptr; int4* owners = nullptr; int* owner_cnt = nullptr; void* skeys = nullptr;
+    RowGroupBufs rg; void* skeys = nullptr;          // the batch's grouping (sparse_rows.hip.h); skeys: phase-A output of the split sort
     double* cpow1 = nullptr; bool key64 = true;
     size_t slab_stride = 0;
     bool prof = false;                               // HIP-event timing of the step's segments
@@ -1755,15 +1756,9 @@ int ip_run(ipnn_handle* h, const int32_t* ids, const float* wts, const float* y,
             hipLaunchKernelGGL(k_mask_T, dim3(tiles), dim3(256), 0, h->mask_side ? ss : h->st, ma);
             if (h->st2 && h->mask_side) IHK(h, hipEventRecord(h->ev_mask, h->st2));
         }
-        SortArgs so{ids, B, F, h->n_rows, h->rec, h->owner_cnt, F, h->skeys};
+        SortArgs so{ids, B, F, h->n_rows, h->rg.rec, h->rg.owner_cnt, F, h->skeys};
         so.merge4 = h->sort_merge4;
-        if (h->key64) {
-            hipLaunchKernelGGL((k_sortA<unsigned long long>), dim3(4 * F), dim3(256), sortA_lds_bytes<unsigned long long>(so.merge4), ss, so);
-            hipLaunchKernelGGL((k_sortB<unsigned long long>), dim3(16 * F), dim3(256), SORT_N * 8, ss, so);
-        } else {
-            hipLaunchKernelGGL((k_sortA<unsigned>), dim3(4 * F), dim3(256), sortA_lds_bytes<unsigned>(so.merge4), ss, so);
-            hipLaunchKernelGGL((k_sortB<unsigned>), dim3(16 * F), dim3(256), SORT_N * 4, ss, so);
-        }
+        launch_sort(ss, h->key64, so);
     }
     if (draw && h->st2 && h->mask_side) IHK(h, hipStreamWaitEvent(h->st, h->ev_mask, 0));     // the inner-product forward reads the drawn mask0
     if (h->wide) {
@@ -2034,20 +2029,19 @@ int ip_run(ipnn_handle* h, const int32_t* ids, const float* wts, const float* y,
         }
         if (h->wide) {   // wide rows: the bag table's wide scatter, gradient stride rw, row pitch Dp0, c = 1; Adam / FTRL: into tG
             IpProf ps(h, "scatter", ss);
-            ScatArgs sa{h->rec, SORT_N, F, h->K, h->gxp, h->Dp[0], h->cpow1, h->adam ? -1.0 : (double)h->cfg.lr,
-                        h->adam ? h->tG : h->table16, h->part, h->owner_cnt, h->owners, h->rw, h->noshare, 1, h->rw};
+            ScatArgs sa = scat_args(h->rg, SORT_N, F, h->K, h->gxp, h->Dp[0], h->cpow1, h->adam ? -1.0 : (double)h->cfg.lr,
+                                    h->adam ? h->tG : h->table16, h->rw);
+            sa.tag_shared = h->noshare; sa.stamp = 1; sa.gxf = h->rw;
             const int nthr = F * (SORT_N / WCH) * (h->rw / 4);
             hipLaunchKernelGGL(k_ip_scatw1, dim3((nthr + 255) / 256), dim3(256), 0, ss, sa);
             hipLaunchKernelGGL(k_ip_scatw2, dim3(256), dim3(256), 0, ss, sa);
         } else {   // sparse rows: row -= lr * sum of its gradients (c = 1: the table of powers is all ones)
             IpProf ps(h, "scatter", ss);
             // Adam / FTRL: the same sorted sums land in the (zero) gradient table instead: G[row] = 0 * 1 - (-1) * sum
-            ScatArgs sa{h->rec, SORT_N, F, h->K, h->gxp, h->Dp[0], h->cpow1, h->adam ? -1.0 : (double)h->cfg.lr,
-                        h->adam ? h->tG : h->table16, h->part, h->owner_cnt, h->owners, SLOT};
-            const int nsc1 = scat1_blocks(sa, h->scat_form);      // also chooses sa.form
+            ScatArgs sa = scat_args(h->rg, SORT_N, F, h->K, h->gxp, h->Dp[0], h->cpow1, h->adam ? -1.0 : (double)h->cfg.lr,
+                                    h->adam ? h->tG : h->table16, SLOT);
             sa.form2 = h->scat2_form;
-            hipLaunchKernelGGL(k_scat1, dim3(nsc1), dim3(256), 0, ss, sa);
-            hipLaunchKernelGGL(k_scat2, dim3(256), dim3(256), 0, ss, sa);
+            launch_scat_narrow(ss, sa, h->scat_form, 256);
         }
         if (h->adam) {
             IpProf ps(h, "adam_table", ss);
@@ -2227,9 +2221,7 @@ int ipnn_create(const ipnn_cfg* cfg, ipnn_handle** out)
     IK(al((void**)&h->dz0, Ba * h->Dp[0] * 4)); IK(al((void**)&h->gxp, Ba * h->Dp[0] * 4));
     IK(al((void**)&h->gb_part, (Ba / ip_bwd_ex(h)) * 4)); IK(al((void**)&h->loss_t, Ba * 4)); IK(al((void**)&h->loss_dev, 4));
     IK(al((void**)&h->b, 4)); IK(al((void**)&h->err_flag, 4));
-    IK(al((void**)&h->rec, (size_t)h->F * SORT_N * sizeof(int4))); IK(al((void**)&h->part, h->wide ? (size_t)h->F * (SORT_N / WCH) * 2 * h->rw * 8
-                                                                                                 : (size_t)h->F * (SORT_N / 16) * 2 * SLOT * 8));
-    IK(al((void**)&h->owners, (size_t)h->F * (SORT_N / 16) * sizeof(int4))); IK(al((void**)&h->owner_cnt, 4));
+    IK(row_group_alloc(h->rg, h->F, SORT_N, h->wide, h->wide ? h->rw : SLOT, h->st, /*owners16*/ true));
     IK(al(&h->skeys, (size_t)h->F * SORT_N * 8));
     {   // c = 1: every power is 1
         std::vector<double> ones(SORT_N + 1, 1.0);
@@ -2267,9 +2259,10 @@ int ipnn_destroy(ipnn_handle* h)
     for (float* p : h->Wm) if (p) hipFree(p);
     for (float* p : h->Wv) if (p) hipFree(p);
     for (float* p : {h->tm, h->tv, h->tG, h->bmv}) if (p) hipFree(p);
-    void* ptrs[] = {h->mask0, h->table16, h->noshare, h->b, h->emb, h->dz0, h->gxp, h->gb_part, h->loss_t, h->loss_dev, h->slab, h->ref0, h->ptab, h->err_flag, h->rec,
-                    h->part, h->owners, h->owner_cnt, h->skeys, h->cpow1, h->duo_xch, h->duo_flags};
+    void* ptrs[] = {h->mask0, h->table16, h->noshare, h->b, h->emb, h->dz0, h->gxp, h->gb_part, h->loss_t, h->loss_dev, h->slab, h->ref0, h->ptab, h->err_flag,
+                    h->skeys, h->cpow1, h->duo_xch, h->duo_flags};
     for (void* p : ptrs) if (p) hipFree(p);
+    row_group_free(h->rg);
     for (auto& kv : h->prof_ev) for (auto& p : kv.second) { hipEventDestroy(p.first); hipEventDestroy(p.second); }
     if (h->st2) { hipStreamSynchronize(h->st2); hipStreamDestroy(h->st2); }
     if (h->ev_fork) hipEventDestroy(h->ev_fork);

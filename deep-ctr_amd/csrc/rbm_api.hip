@@ -12,6 +12,7 @@
 #include "../../include/fnn_hip.h"
 #include "../../include/rbm_hip.h"
 #include "fnn_kernels.hip.h"
+#include "sparse_rows.hip.h"      // the sorted-record update whose shape k_rbm_scat1 / k_rbm_scat2 follow (scatw1_body)
 #include "metrics.hip.h"
 
 using namespace fnn;

@@ -36,7 +36,7 @@ int main() {
     float* gxp = (float*)dev((size_t)B * K1p * 4); float* p_out = (float*)dev(B * 4); float* loss_t = (float*)dev(B * 4); int* err = (int*)dev(4);
     long long* dbg = (long long*)dev(256 * 16 * 8);
     MlpArgs<bf16_t> a{d_ids, d_y, B, F, K, d_tab, D, -3.f, w1, w1t, w2, w2t, w3p, m, m, 0, 0, H1, H2, 1,
-                      xpT, d1T, d2T, dl1T, dl2T, dl3T, ldT, gxp, p_out, loss_t, err, nullptr, 16, nullptr, nullptr, dbg};
+                      xpT, d1T, d2T, dl1T, dl2T, dl3T, ldT, gxp, p_out, loss_t, err, nullptr, 16, nullptr, nullptr, /*wt*/ 0, dbg};
     const size_t lds = 16 * (328 + 328 + 136) * 2 + 256;
     hipEvent_t e0, e1; hipEventCreate(&e0); hipEventCreate(&e1);
     for (int it = 0; it < 20; ++it) hipLaunchKernelGGL((k_step1<bf16_t, 5, 2, 4, false>), dim3(256), dim3(256), lds, 0, a);

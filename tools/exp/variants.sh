@@ -4,7 +4,7 @@ set -e
 SRC=deep-ctr_amd/csrc
 run_variant() {   # name, sed script
   d=/tmp/fnnv_$1; rm -rf $d; mkdir -p $d/deep-ctr_amd/csrc $d/tools/exp
-  cp $SRC/fnn_kernels.hip.h $SRC/fnn_step_kernels.hip.h $d/deep-ctr_amd/csrc/
+  cp $SRC/fnn_kernels.hip.h $SRC/sparse_rows.hip.h $SRC/fnn_step_kernels.hip.h $d/deep-ctr_amd/csrc/
   cp tools/exp/mlp_stamps.hip $d/tools/exp/
   if [ -n "$2" ]; then sed -i -E "$2" $d/deep-ctr_amd/csrc/fnn_kernels.hip.h; fi
   hipcc --offload-arch=gfx950 -O3 -std=c++17 -o $d/ms $d/tools/exp/mlp_stamps.hip 2>&1 | grep -E " error" || true
