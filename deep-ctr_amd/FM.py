@@ -8,6 +8,8 @@ Value weights (the class's `sp_wt_hldr`, python/FM.py:24-29): `wts=` of train_st
 (example, field) beside its id; `model.train_step(_cols, _labels, wts=_vals)` is python/baseline.py:345's feed, and the
 `(ids, wts)` pair that `ipnn.criteo_feed` makes for the inner-product family feeds FM / LR unchanged.  Without `wts` every
 value is 1 (iPinYou).
+The reference's own schedule -- batch_size = 1, a step per line (python/ipinyou.py:129-140, :167-173) -- is `train_online`: a
+buffer of lines per call, one persistent workgroup walking them in order (fm_train_online); `ipinyou.run(..., online=True)`.
 Rows shared between columns (`shared_rows=True`, fm_set_shared_rows): the columns of `ids` are then positions, not fields, as
 python/ipinyou.py:42-65 feeds the reference -- `ipinyou.to_column_ids` makes such ids and `ipinyou.run` is the driver.
 Random init uses NumPy RandomState(seed) streams (TensorFlow's cannot be reproduced here)."""
@@ -145,6 +147,32 @@ class FM(object):
         torch.cuda.current_stream(self.device).wait_stream(self.stream)
         self._keep = (ids_t, y_t, w_t)
         return {'loss': float(loss.value) if want_loss else None, 'p': p}
+
+    def train_online(self, ids, y, wts=None, want_p=False, want_loss=True):
+        """fm_train_online: the N lines of ids [N, X_feas] as N batch-1 SGD steps in line order (python/ipinyou.py:129-140 builds FM
+        and LR with batch_size = 1, :167-173 runs a step per line), example n on the parameters examples 0..n-1 left; N is not
+        bounded by max_batch.  Plain SGD only: FNNError(FNN_ERR_STATE) under Adam / FTRL.  Returns {'loss': the sum of the N
+        data losses, 'loss_last': the last line's (the `l` python/ipinyou.py:177 prints), 'p': sigmoid(yhat_n) before line n's
+        update, or None}; both losses are None without want_loss (no synchronisation then)."""
+        torch = self._torch
+        ids_t, y_t = self._dev(ids, torch.int32), self._dev(y, torch.float32)
+        if ids_t.dim() != 2 or ids_t.shape[1] != self.X_feas or y_t.shape != (ids_t.shape[0],):
+            raise ValueError("ids %s, y %s: need [N, %d] and [N]" % (tuple(ids_t.shape), tuple(y_t.shape), self.X_feas))
+        w_t = self._wts(wts, ids_t)
+        N = ids_t.shape[0]
+        p = torch.empty(N, dtype=torch.float32, device=self.device) if want_p else None
+        loss, last = C.c_double(), C.c_float()
+        self.stream.wait_stream(torch.cuda.current_stream(self.device))
+        self._ck(self.lib.fm_train_online(self.h, ids_t.data_ptr(), None if w_t is None else w_t.data_ptr(), y_t.data_ptr(), N,
+                                          self.lr, self.lam, p.data_ptr() if want_p and N else None,
+                                          C.byref(loss) if want_loss else None, C.byref(last) if want_loss else None))
+        torch.cuda.current_stream(self.device).wait_stream(self.stream)
+        self._keep = (ids_t, y_t, w_t)
+        return {'loss': float(loss.value) if want_loss else None, 'loss_last': float(last.value) if want_loss else None, 'p': p}
+
+    def online_form(self):
+        """fm_online_form: the form of the online kernel this handle runs."""
+        return self.lib.fm_online_form(self.h).decode()
 
     def forward(self, ids, wts=None):
         """sigmoid(yhat) [N] (`test_preds`), max_batch examples a call; wts as in train_step."""

@@ -19,6 +19,7 @@
 #include "sparse_rows.hip.h"
 #include "metrics.hip.h"
 #include "optim.hip.h"
+#include "fm_online.hip.h"
 
 using namespace fnn;
 
@@ -430,6 +431,8 @@ struct fm_handle {
     // training step under the mode, 0 = none yet -- what fm_count_shared_rows scans for.
     bool shared = false; int* tag_first = nullptr; int* tag_shared = nullptr; int tag_stamp = 0, step_stamp = 0;
     unsigned long long* mark_cnt = nullptr;
+    // fm_train_online: the examples one launch may take (FM_ONLINE_CHUNK, read at fm_create) and the call's loss accumulators
+    int64_t online_chunk = 65536; fm_online::Out* online_out = nullptr;
 };
 
 #define MHK(h, expr) do { hipError_t e_ = (expr); if (e_ != hipSuccess) { (h)->err = std::string(#expr) + ": " + hipGetErrorString(e_); return FNN_ERR_HIP; } } while (0)
@@ -679,7 +682,7 @@ int fm_create(int n_fields, int k, int max_batch, int device, void* stream, fm_h
     const size_t Ba = rup(h->Bmax, 16);
     FK(al((void**)&h->gxp, Ba * h->K1p * 4)); FK(al((void**)&h->loss_t, Ba * 4)); FK(al((void**)&h->gb_part, (Ba / 8) * 4));
     FK(al((void**)&h->loss_dev, 4)); FK(al((void**)&h->b, 4)); FK(al((void**)&h->err_flag, 4)); FK(al((void**)&h->sb, 8));
-    FK(al((void**)&h->mark_cnt, 8));
+    FK(al((void**)&h->mark_cnt, 8)); FK(al((void**)&h->online_out, sizeof(fm_online::Out)));
     FK(row_group_alloc(h->rg, h->F, SORT_N, h->wide, h->rw, h->st, /*owners16*/ true));
     FK(al(&h->skeys, (size_t)h->F * SORT_N * 8));
     {
@@ -693,6 +696,7 @@ int fm_create(int n_fields, int k, int max_batch, int device, void* stream, fm_h
     h->scat_form = scat1_form_env();
     h->scat2_form = scat2_form_env();
     h->sort_merge4 = sort_merge4_env(0);
+    if (const char* e = getenv("FM_ONLINE_CHUNK")) { const long long c = atoll(e); if (c >= 1) h->online_chunk = c; }
     *out = h;
     return FNN_OK;
 }
@@ -703,7 +707,7 @@ int fm_destroy(fm_handle* h)
     hipSetDevice(h->dev);
     if (h->st) hipStreamSynchronize(h->st);
     void* ptrs[] = {h->table16, h->b, h->gxp, h->loss_t, h->gb_part, h->loss_dev, h->err_flag, h->skeys, h->cpow1, h->s0, h->s1,
-                    h->sb, h->G, h->stamp, h->noshare, h->tag_first, h->tag_shared, h->mark_cnt};
+                    h->sb, h->G, h->stamp, h->noshare, h->tag_first, h->tag_shared, h->mark_cnt, h->online_out};
     for (void* p : ptrs) if (p) hipFree(p);
     row_group_free(h->rg);
     if (h->own_stream && h->st) hipStreamDestroy(h->st);
@@ -811,6 +815,49 @@ int fm_train_step_w(fm_handle* h, const int32_t* ids, const float* wts, const fl
     }
     return FNN_OK;
 }
+
+// The online schedule (fm_online.hip.h): one launch per run of examples, cut at FM_ONLINE_CHUNK and after the example whose decay
+// takes the lazy scale out of [2^-24, 1] (fm_run's rule, so that online calls and batch steps fold at the same places).  A cut at
+// the cap hands b (f32), the scale and the loss sum (f64) to the next launch unchanged: where it falls changes no bit.
+int fm_train_online(fm_handle* h, const int32_t* ids, const float* wts, const float* y, int64_t N, float lr, float lambda, float* p_out,
+                    double* loss_sum_out, float* loss_last_out)
+{
+    if (!h) return FNN_ERR_ARG;
+    if (N < 0 || (N > 0 && (!ids || !y))) MFAIL(h, FNN_ERR_ARG, "need N >= 0, ids and y");
+    if (h->opt != FM_OPT_SGD) MFAIL(h, FNN_ERR_STATE, "fm_train_online is plain SGD only (Adam / FTRL pass over the whole table per step)");
+    if (!h->table16) MFAIL(h, FNN_ERR_STATE, "fm_set_table has not been called");
+    if (!(lr * lambda < 1.0f) || lambda < 0.f) MFAIL(h, FNN_ERR_ARG, "need 0 <= lr * lambda < 1");
+    if (loss_sum_out) *loss_sum_out = 0.0;
+    if (loss_last_out) *loss_last_out = 0.f;
+    if (N == 0) return FNN_OK;
+    MHK(h, hipSetDevice(h->dev));
+    MHK(h, hipMemsetAsync(h->online_out, 0, sizeof(fm_online::Out), h->st));
+    const double dec = 1.0 - (double)lr * (double)lambda;
+    for (int64_t n0 = 0; n0 < N;) {
+        int64_t cnt = 0;
+        double s = h->scale;
+        bool fold = false;
+        while (n0 + cnt < N && cnt < h->online_chunk && !fold) { s *= dec; ++cnt; fold = s < 5.96e-8 || s > 1.0; }
+        const fm_online::Args a{ids + n0 * h->F, wts ? wts + n0 * h->F : nullptr, y + n0, cnt, h->F, h->K, h->rw, h->table16, h->n_rows, h->b,
+                                h->scale, dec, lr, lambda, p_out ? p_out + n0 : nullptr, h->err_flag, h->online_out};
+        hipLaunchKernelGGL(fm_online::k_fm_online, dim3(1), dim3(256), 0, h->st, a);
+        MHK(h, hipGetLastError());
+        h->scale = s;
+        if (fold) { const int rc = fold_scale(h); if (rc != FNN_OK) return rc; }
+        n0 += cnt;
+    }
+    if (loss_sum_out || loss_last_out) {
+        fm_online::Out o{0.0, 0.f, 0.f};
+        MHK(h, hipMemcpyAsync(&o, h->online_out, sizeof(o), hipMemcpyDeviceToHost, h->st));
+        const int rc = fm_sync(h);
+        if (loss_sum_out) *loss_sum_out = o.loss_sum;
+        if (loss_last_out) *loss_last_out = o.loss_last;
+        return rc;
+    }
+    return FNN_OK;
+}
+
+const char* fm_online_form(const fm_handle*) { return "plain"; }
 
 int fm_predict(fm_handle* h, const int32_t* ids, int B, float* p_out) { return fm_predict_w(h, ids, nullptr, B, p_out); }
 

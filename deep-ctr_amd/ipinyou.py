@@ -130,15 +130,18 @@ def exact_auc(labels, preds):
 
 
 def run(train_path, test_path, algo='FM', batch_size=4096, buffer=10000, eval_size=100000, epochs=1, log_file=None, device=0,
-        echo=True):
+        echo=True, online=False):
     """python/ipinyou.py:113-199, the FM / LR driver, on the device.  `stat` both files, X_dim = max + 2, X_feas = the longest
     line; LR (:133) or FM rank 10 (:139-140) with the reference's init, optimiser and L2 weight and shared_rows=True; per pass
     over the training file, buffers of `buffer` shuffled lines (load_ipinyou_data) in mini-batches of `batch_size`, each one
     train_step; after every buffer the test file is evaluated on the device (fm_eval) in chunks of eval_size lines, at most
     10 * eval_size of them (:196), and watch_train's line `step\tbatch_auc\teval_auc\tloss\t` is written to log_file.
-    Differences from the reference: batch_size is a parameter (its 1 is allowed; a buffer's tail shorter than batch_size is one
-    shorter step), `epochs` passes instead of an endless loop, every buffer is evaluated (the reference skips a short last
-    one) and a last test chunk shorter than eval_size counts.  Lines longer than fm_create's 64 columns raise ValueError.
+    online=True is the reference's schedule end to end: batch_size is ignored, every buffer is ONE train_online call -- a batch-1
+    SGD step per line, in the buffer's shuffled order (python/ipinyou.py:129-140, :167-173) -- and the logged loss is the last
+    line's, as :177 has it; give buffer=100000 for LR (:131), the 10000 default is FM's (:137).
+    Differences from the reference: without `online`, batch_size is a parameter (its 1 is allowed but costs a whole step's launches
+    per line; a buffer's tail shorter than batch_size is one shorter step); `epochs` passes instead of an endless loop, every
+    buffer is evaluated (the reference skips a short last one) and a last test chunk shorter than eval_size counts.  Lines longer than fm_create's 64 columns raise ValueError.
     Returns {'model', 'log': [(step, batch_auc, eval_auc, loss)], 'X_dim', 'X_feas'}."""
     from .FM import FM
     from .LR import LR
@@ -148,6 +151,8 @@ def run(train_path, test_path, algo='FM', batch_size=4096, buffer=10000, eval_si
     X_feas = max(X_feas_train, X_feas_test)
     if X_feas > 64:
         raise ValueError("the longest line has %d features: FM / LR take at most 64 columns (fm_create)" % X_feas)
+    if online:
+        batch_size = 1                                             # the models are built as the reference builds them
     if batch_size < 1 or batch_size > 4096:
         raise ValueError("batch_size %d: one step takes 1..4096 examples" % batch_size)
     max_eval = min(eval_size, 4096)
@@ -179,7 +184,11 @@ def run(train_path, test_path, algo='FM', batch_size=4096, buffer=10000, eval_si
                     break
                 ids, wts = to_column_ids(X_ind, X_val)
                 preds, loss = [], float('nan')
-                for lo in range(0, len(labels), batch_size):
+                if online:
+                    out = model.train_online(ids, labels, wts=wts, want_p=True)
+                    preds.append(out['p'].cpu().numpy())
+                    loss = out['loss_last']
+                for lo in range(0, 0 if online else len(labels), batch_size):
                     out = model.train_step(ids[lo:lo + batch_size], labels[lo:lo + batch_size], want_p=True,
                                            wts=None if wts is None else wts[lo:lo + batch_size])
                     preds.append(out['p'].cpu().numpy())
@@ -211,7 +220,7 @@ def run(train_path, test_path, algo='FM', batch_size=4096, buffer=10000, eval_si
 
 if __name__ == '__main__':
     # python/ipinyou.py:113-127: the campaign's yzx files under DEEPCTR_DATA_DIR (default ../data, as FNN.py), the log under
-    # DEEPCTR_LOG_DIR (default ../log/); `python ipinyou.py [FM|LR] [batch_size]`
+    # DEEPCTR_LOG_DIR (default ../log/); `python ipinyou.py [FM|LR] [batch_size | online]`
     sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
     from deep_ctr_amd import ipinyou as _drv
     cam = 'all'
@@ -224,6 +233,6 @@ if __name__ == '__main__':
     print(os.path.join(log_dir, tag))
     _drv.run(os.path.join(data_dir, 'ipinyou-data/%s/train.yzx.txt.shuf' % cam),
              os.path.join(data_dir, 'ipinyou-data/%s/test.yzx.txt.shuf' % cam), algo,
-             batch_size=int(sys.argv[2]) if len(sys.argv) > 2 else 4096,
+             batch_size=int(sys.argv[2]) if len(sys.argv) > 2 and sys.argv[2] != 'online' else 4096,
              buffer=100000 if 'LR' in algo else 10000, epochs=int(os.environ.get('DEEPCTR_EPOCHS', 1)),
-             log_file=os.path.join(log_dir, tag))
+             log_file=os.path.join(log_dir, tag), online=len(sys.argv) > 2 and sys.argv[2] == 'online')

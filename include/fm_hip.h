@@ -100,6 +100,30 @@ int fm_train_step_w(fm_handle* h, const int32_t* ids, const float* wts, const fl
                     int reduce_mean, float* p_out, float* loss_out);
 int fm_predict_w(fm_handle* h, const int32_t* ids, const float* wts, int B, float* p_out);
 
+/* The reference's own pre-training schedule (python/ipinyou.py:129-140 and :167-173: batch_size = 1, one step per line).
+ * N batch-1 SGD steps in line order, on the handle's stream: example n is trained on the parameters examples 0..n-1 left.
+ * DEVICE pointers: ids [N, F] int32 (-1 = absent), wts [N, F] f32 (nullable: every value 1), y [N] f32,
+ * p_out [N] (nullable): sigmoid(yhat_n) BEFORE example n's update (`train_preds`).
+ * HOST, nullable, either one synchronises: loss_sum_out = sum of the N data losses (accumulated in f64),
+ * loss_last_out = example N-1's (the `l` python/ipinyou.py:177 prints).
+ * One step is fm_train_step_w at B = 1 (mean and sum coincide): every row of the table takes theta <- theta (1 - lr lambda) - lr g
+ * with g at the pre-step values (the dense decay is the lazy scale, advanced once per example), b <- b - lr (delta + lambda b).
+ * Right for any ids in [-1, n_rows) whether fm_set_shared_rows is on or off: a row under several columns of one line receives
+ * the sum of those columns' contributions in one store, and the result is reproducible bit for bit.  The shared-row marks are
+ * not touched: fm_count_shared_rows keeps referring to the last batch step.  An id outside [-1, n_rows) is treated as absent,
+ * never dereferenced, and reported by fm_sync as FNN_ERR_RANGE, as fm_train_step does.
+ * Every shape fm_create accepts, any N >= 0 (0: nothing happens, FNN_OK), not bounded by max_batch; online calls and batch
+ * steps may be interleaved freely.  One persistent workgroup runs the examples of a launch (the work is a dependence chain);
+ * a launch takes at most FM_ONLINE_CHUNK examples (environment, read at fm_create; default 65536), and where the call is cut
+ * into launches does not change a bit of the result.
+ * FNN_ERR_STATE under Adam or FTRL, nothing written: their update is a pass over the whole table per step, per example that is
+ * the table's size in traffic, which is not a schedule anybody can run.  FNN_ERR_ARG (before any launch): a null handle, ids or
+ * y, N < 0, or lr * lambda outside [0, 1). */
+int fm_train_online(fm_handle* h, const int32_t* ids, const float* wts, const float* y, int64_t N,
+                    float lr, float lambda, float* p_out, double* loss_sum_out, float* loss_last_out);
+/* which form the handle runs, as fnn_scat1_form() does for its knob: "plain" (the only one built) */
+const char* fm_online_form(const fm_handle* h);
+
 /* The optimiser of fm_train_step (python/tf_util.py:15-29); lr and lambda of fm_train_step keep their meaning (base
  * learning rate, L2 weight).  Folds any pending SGD scale into the rows, (re)initialises the state -- Adam: m = v = 0;
  * FTRL: accum = 0.1, linear = 0, the bias's as well -- and resets the step count.  fm_set_table re-initialises the state.
