@@ -33,10 +33,11 @@ def load_active_ids(path, n_fields=16):
     return ids, y
 
 
-def run(argv, kind='rbm'):
+def run(argv, kind='rbm', pretrain_kw=None):
     """kind = 'rbm': python/SNN_RBM.py.  kind = 'dae': python/SNN_DAE.py -- the same script with the
     denoising-autoencoder pre-trainer, its own 2997 hyper-parameters (:42-50), no train-file suffix
-    flag and the cache file dropda_<adv>_.p (:82-86)."""
+    flag and the cache file dropda_<adv>_.p (:82-86).  pretrain_kw: further keyword arguments of
+    `get_da_weights` (SNN_DAE.py passes its mini-batch size and corruption level)."""
     srng = ut.RandomStreams(seed=234)                          # :18
     ut.seed_global(1234)                                       # :19-21 (and the two imports before it)
     batch_size = 1000                                          # :22-29
@@ -106,7 +107,7 @@ def run(argv, kind='rbm'):
         with open(train_file) as fi:                           # num_feats, python/SNN_DAE.py:75-81
             numf = len(fi.readline().strip().split(':')) - 1
         ww0, bb0, ww1, bb1, ww2, bb2 = da.get_da_weights(train_file, arr, num_feats=numf, ncases=train_size,
-                                                         batch_size=100000)
+                                                         batch_size=100000, **(pretrain_kw or {}))
         pickle.dump((ww0, bb0, ww1, bb1, ww2, bb2), open(wfile, "wb"))
     else:
         ww0, bb0, ww1, bb1, ww2, bb2 = gbrbm.get_rbm_weights(train_file, arr, ncases=train_size, batch_size=100000,

@@ -353,6 +353,280 @@ __global__ __launch_bounds__(1024) void k_dae_dense_split(const DenseSArgs<S> a)
     }
 }
 
+// ------------------------------------------------------------------------------------------
+// The MINI-BATCH dense trainer (dae_dense_batch / _f64): da() of the reference as it is written (:97-113, batch_size = M,
+// cost = T.mean(L), an optional keep mask on the encoder's input), on the layout of k_dae_dense_split above: eight workgroups
+// 8 block ids apart, workgroup c keeps ITS columns [c cw, (c + 1) cw) of W in registers for the whole call (wave w: rows w, w + 16,
+// ...; lane: column).  A mini-batch of m examples is three phases over sub-blocks of EB examples (LDS holds EB examples, never m):
+//   A   Xt = keep * X staged in LDS; Y = sigmoid(Xt W + bhid) for the owned columns (a wave's rows, then 16 partials per column,
+//       wave e adds them for example e) -> this workgroup's private y scratch; its partial row sums sum_{j owned} Y[e][j] W[i][j]
+//       (f32: a butterfly per row; f64: wave_sum_rows, 8 rows per pass over the lanes) -> exchange buffer [parity][workgroup][e][rowp], write-through stores.
+//   --  ONE hand-off per mini-batch: drain the stores, barrier, flag = batch number + 1 (only grows); one lane per peer flag polls
+//       (bounded), barrier.  A peer that never arrives: error bit, every workgroup leaves.
+//   C1  every workgroup re-derives Z from the eight partials (sc1 loads, added to bvis in workgroup order 0..7: the same Z, D and bvis
+//       everywhere), D = (Z - X) / m -> private d scratch; dY = (D W) * Y (1 - Y) for the owned columns -> private dy scratch;
+//       gbhid / gbvis accumulate in example order; workgroup 0 adds the cross-entropy terms against the UNcorrupted X in f64.
+//       W is not touched before C1 has finished: every product of the mini-batch reads W as it was at its start.
+//   C2  (skipped for the call's last mini-batch under skip_last_update) the rank-1 terms lr (Xt[e] (x) dY[e] + D[e] (x) Y[e]) are taken
+//       off the W registers example by example in example order -- a second accumulator set would not fit beside W at 32 rows
+//       per wave in f64 --, then bhid -= lr gbhid, bvis -= lr gbvis.
+// Every sum has a fixed order (documented in dae_hip.h), so two calls give the same bits.  The y / dy / d scratch is private to the
+// workgroup that wrote it (plain accesses behind workgroup barriers); only the exchange buffer crosses workgroups, in exactly the
+// forms of k_dae_dense_split (MI355X_MICROARCH.md "Valid forms": every handed-off byte stored sc1 and drained before the flag, one
+// lane per flag polls, every load of handed-off bytes an sc1 load to registers).
+// Two parities, restated for the mini-batch payload: a workgroup writes the [m][rowp] partials of mini-batch b into parity b & 1 in
+// phase A and every workgroup reads all eight of them in C1 of b.  It writes that parity again in phase A of b + 2, which it enters
+// only after the hand-off of b + 1, i.e. after it has seen every peer's flag at b + 2; a peer raises that flag after its phase A of
+// b + 1, which in program order follows its C1 of b, whose loads have all been consumed (into LDS, behind barriers) by then.
+// ------------------------------------------------------------------------------------------
+// Sums over the 64 lanes of a wave of P values per lane (P a power of two <= 16; row_sums, the f64 path, takes 8) in P - 1 + log2(64 / P) exchanges instead of 6 P:
+// at every step a lane keeps one half of its values, hands the other half to the lane `bit` away and adds what it receives to what
+// it kept (bit = 32, 16, ..: the lane with the bit clear keeps the lower half), until one value per lane is left; the remaining bits
+// are a plain butterfly.  Lane l ends with the sum of value l / (64 / P).  A fixed tree: the same bits on every call.
+template <typename S, int P>
+__device__ __forceinline__ S wave_sum_rows(S (&a)[P], int l)
+{
+    constexpr int STEPS = P >= 16 ? 4 : P >= 8 ? 3 : P >= 4 ? 2 : P >= 2 ? 1 : 0;
+#pragma unroll
+    for (int s = 0; s < STEPS; ++s) {
+        const int h = P >> (s + 1), bit = 32 >> s;
+        const bool hi = (l & bit) != 0;
+#pragma unroll
+        for (int k = 0; k < h; ++k) {
+            const S keep = hi ? a[k + h] : a[k], send = hi ? a[k] : a[k + h];
+            a[k] = keep + __shfl_xor(send, bit);
+        }
+    }
+    S v = a[0];
+#pragma unroll
+    for (int s = STEPS; s < 6; ++s) v += __shfl_xor(v, 32 >> s);
+    return v;
+}
+// dst[w + 16 r] = sum over the wave's lanes of yl * Wr[r], r = R0 .. RPW - 1, in chunks of up to 8 rows in f64 (16 in f32, which does not take this path)
+template <typename S, int RPW, int R0>
+__device__ __forceinline__ void row_sums(const S (&Wr)[RPW], S yl, int w, int l, S* dst)
+{
+    if constexpr (R0 < RPW) {
+        constexpr int REM = RPW - R0, PMAX = 64 / (int)sizeof(S), Q = REM > 8 ? 16 : REM > 4 ? 8 : REM > 2 ? 4 : REM > 1 ? 2 : 1, P = Q < PMAX ? Q : PMAX;
+        constexpr int LPR = 64 / P;                               // lanes per row at the end
+        S a[P];
+#pragma unroll
+        for (int k = 0; k < P; ++k) { if (R0 + k < RPW) a[k] = yl * Wr[R0 + k < RPW ? R0 + k : 0]; else a[k] = (S)0; }
+        const S v = wave_sum_rows<S, P>(a, l);
+        const int k = l / LPR;
+        if (l % LPR == 0 && R0 + k < RPW) dst[w + 16 * (R0 + k)] = v;
+        row_sums<S, RPW, R0 + P>(Wr, yl, w, l, dst);
+    }
+}
+
+template <typename S> struct DenseBArgs {
+    S *W, *bhid, *bvis; const S* X; const uint8_t* keep; int64_t N; int M, row, col, cw; S lr; int skip_last; double* cost;
+    S* xch;                        // [2][DSP_NS][Mc][rowp] partial row sums (Mc = min(M, N))
+    S* dbuf;                       // [DSP_NS][Mc][rowp] D, private per workgroup
+    S* ybuf;                       // [DSP_NS][2][Mc][64] Y and dY of the owned columns, private per workgroup
+    unsigned long long* flags;     // [DSP_NS] on 64-byte lines (stride 8)
+    int rowp, Mc; int* err;
+};
+
+template <typename S, int RPW>
+__global__ __launch_bounds__(1024) void k_dae_dense_batch(const DenseBArgs<S> a)
+{
+    constexpr int RP = 16 * RPW, EB = 32 / (int)sizeof(S);       // examples per sub-block: 4 in f64, 8 in f32
+    __shared__ S s_a[EB][RP];                                     // Xt (A, C2) or D (C1) of the sub-block
+    __shared__ S s_part[EB * 1024];                               // [EB][16][64] column partials; [EB][RP] row sums (A) / D (C2) alias it
+    __shared__ S s_bv[RP];
+    __shared__ S s_y[EB][64], s_dy[EB][64];
+    __shared__ double s_cost[16];
+    __shared__ int s_bad;
+    if (blockIdx.x & 7) return;                                   // the eight working blocks are 8 apart: one XCD under round-robin placement
+    const int wg = blockIdx.x >> 3, tid = threadIdx.x, w = tid >> 6, l = tid & 63, row = a.row, col = a.col, rowp = a.rowp;
+    const int j = wg * a.cw + l;
+    const bool cact = l < a.cw && j < col;
+    S (*s_b)[RP] = reinterpret_cast<S (*)[RP]>(s_part);
+    S Wr[RPW];
+#pragma unroll
+    for (int r = 0; r < RPW; ++r) { const int i = w + 16 * r; Wr[r] = (cact && i < row) ? a.W[(size_t)i * col + j] : (S)0; }
+    S bh = cact ? a.bhid[j] : (S)0;                               // every wave keeps the same copy
+    for (int i = tid; i < RP; i += 1024) s_bv[i] = i < row ? a.bvis[i] : (S)0;
+    if (tid == 0) s_bad = 0;
+    double cost = 0.0;
+    const size_t wgs = (size_t)a.Mc * rowp;
+    S* ymine = a.ybuf + (size_t)wg * 2 * a.Mc * 64;
+    S* dymine = ymine + (size_t)a.Mc * 64;
+    S* dmine = a.dbuf + (size_t)wg * wgs;
+    const int64_t nb = (a.N + a.M - 1) / a.M;
+    __syncthreads();
+    for (int64_t b = 0; b < nb; ++b) {
+        const int64_t n0 = b * a.M;
+        const int m = (int)((a.N - n0 < (int64_t)a.M) ? (a.N - n0) : (int64_t)a.M);
+        const S* Xb = a.X + (size_t)n0 * row;
+        const uint8_t* Kb = a.keep ? a.keep + (size_t)n0 * row : nullptr;
+        S* mine = a.xch + ((size_t)(b & 1) * DSP_NS + wg) * wgs;
+        // ---- A: Y and this workgroup's partial row sums
+        for (int e0 = 0; e0 < m; e0 += EB) {
+            const int cnt = (m - e0 < EB) ? (m - e0) : EB;
+#pragma unroll 1
+            for (int k = tid; k < cnt * RP; k += 1024) {
+                const int e = k / RP, i = k - e * RP;
+                S v = (S)0;
+                if (i < row) {
+                    const size_t o = (size_t)(e0 + e) * row + i;
+                    v = Xb[o];
+                    if (Kb && Kb[o] == 0) v = (S)0;
+                }
+                s_a[e][i] = v;
+            }
+            __syncthreads();
+#pragma unroll 1
+            for (int e = 0; e < cnt; ++e) {
+                S p = (S)0;
+#pragma unroll
+                for (int r = 0; r < RPW; ++r) p = fma(s_a[e][w + 16 * r], Wr[r], p);
+                s_part[(e * 16 + w) * 64 + l] = p;
+            }
+            __syncthreads();
+            if (w < cnt) {                                        // wave e finishes example e: bhid + the 16 partials in wave order
+                S t = bh;
+#pragma unroll
+                for (int q = 0; q < 16; ++q) t += s_part[(w * 16 + q) * 64 + l];
+                const S y = cact ? sigm(t) : (S)0;
+                s_y[w][l] = y;
+                ymine[(size_t)(e0 + w) * 64 + l] = y;
+            }
+            __syncthreads();
+#pragma unroll 1
+            for (int e = 0; e < cnt; ++e) {                       // row sums over the owned columns (wave reductions)
+                const S yl = s_y[e][l];
+                if constexpr (sizeof(S) == 8) row_sums<S, RPW, 0>(Wr, yl, w, l, s_b[e]);      // measured: 14.9 -> 9.9 us per example at 300 x 100, M = 20
+                else {                                                                     // f32 butterflies are cheap; row_sums measured slower (7.8 -> 9.3 us)
+#pragma unroll
+                    for (int r = 0; r < RPW; ++r) {
+                        const S v = wave_sum(yl * Wr[r]);
+                        if (l == 0) s_b[e][w + 16 * r] = v;
+                    }
+                }
+            }
+            __syncthreads();
+#pragma unroll 1
+            for (int k = tid; k < cnt * RP; k += 1024) {
+                const int e = k / RP, i = k - e * RP;
+                if (i < row) __hip_atomic_store(mine + (size_t)(e0 + e) * rowp + i, s_b[e][i], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);   // sc1: write-through
+            }
+            // the next sub-block writes s_a (last read two barriers ago) and, behind its first barrier, s_part
+        }
+        {   // ---- the hand-off: signal, wait
+            asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
+            __syncthreads();
+            if (tid == 0) __hip_atomic_store(a.flags + wg * 8, (unsigned long long)(b + 1), __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+            if (tid < DSP_NS) {
+                int tries = 0;
+                while (__hip_atomic_load(a.flags + tid * 8, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) < (unsigned long long)(b + 1)) {
+                    if (++tries > (1 << 22)) { s_bad = 1; break; }
+                    __builtin_amdgcn_s_sleep(1);
+                }
+            }
+            __syncthreads();
+            if (s_bad) break;
+        }
+        // ---- C1: Z, D, dY of the whole mini-batch against W as it stands
+        const S* all = a.xch + (size_t)(b & 1) * DSP_NS * wgs;
+        double cb = 0.0;
+        S gbh = (S)0, gbv = (S)0;
+        for (int e0 = 0; e0 < m; e0 += EB) {
+            const int cnt = (m - e0 < EB) ? (m - e0) : EB;
+#pragma unroll 1
+            for (int k = tid; k < cnt * RP; k += 1024) {
+                const int e = k / RP, i = k - e * RP;
+                S d = (S)0;
+                if (i < row) {
+                    const size_t o = (size_t)(e0 + e) * rowp + i;
+                    S zs = s_bv[i];
+#pragma unroll
+                    for (int c = 0; c < DSP_NS; ++c) zs += __hip_atomic_load(all + (size_t)c * wgs + o, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);   // sc1 loads
+                    const S zi = sigm(zs), xi = Xb[(size_t)(e0 + e) * row + i];
+                    d = (zi - xi) / (S)m;
+                    dmine[o] = d;
+                    if (wg == 0) cb += (double)xent(xi, zi);
+                }
+                s_a[e][i] = d;
+            }
+            __syncthreads();
+#pragma unroll 1
+            for (int e = 0; e < cnt; ++e) {
+                S p = (S)0;
+#pragma unroll
+                for (int r = 0; r < RPW; ++r) p = fma(s_a[e][w + 16 * r], Wr[r], p);
+                s_part[(e * 16 + w) * 64 + l] = p;
+            }
+            __syncthreads();
+            if (w < cnt) {
+                S t = (S)0;
+#pragma unroll
+                for (int q = 0; q < 16; ++q) t += s_part[(w * 16 + q) * 64 + l];
+                const S y = ymine[(size_t)(e0 + w) * 64 + l];
+                const S dy = t * y * ((S)1 - y);
+                s_dy[w][l] = dy;
+                dymine[(size_t)(e0 + w) * 64 + l] = dy;
+            }
+            __syncthreads();
+            for (int e = 0; e < cnt; ++e) {                       // the bias gradients: example order
+                gbh += s_dy[e][l];
+                if (tid < RP) gbv += s_a[e][tid];
+            }
+            __syncthreads();
+        }
+        if (wg == 0) cost += cb / (double)m;
+        // ---- C2: the update, example by example
+        if (!(a.skip_last && b + 1 == nb)) {
+            for (int e0 = 0; e0 < m; e0 += EB) {
+                const int cnt = (m - e0 < EB) ? (m - e0) : EB;
+    #pragma unroll 1
+            for (int k = tid; k < cnt * RP; k += 1024) {
+                    const int e = k / RP, i = k - e * RP;
+                    S v = (S)0, d = (S)0;
+                    if (i < row) {
+                        const size_t o = (size_t)(e0 + e) * row + i;
+                        v = Xb[o];
+                        if (Kb && Kb[o] == 0) v = (S)0;
+                        d = dmine[(size_t)(e0 + e) * rowp + i];
+                    }
+                    s_a[e][i] = v;
+                    s_b[e][i] = d;
+                }
+                if (tid < cnt * 64) {
+                    s_y[w][l] = ymine[(size_t)(e0 + w) * 64 + l];
+                    s_dy[w][l] = dymine[(size_t)(e0 + w) * 64 + l];
+                }
+                __syncthreads();
+#pragma unroll 1
+                for (int e = 0; e < cnt; ++e) {
+                    const S dyl = s_dy[e][l], yl = s_y[e][l];
+#pragma unroll
+                    for (int r = 0; r < RPW; ++r) {
+                        const int i = w + 16 * r;
+                        Wr[r] -= a.lr * fma(s_a[e][i], dyl, s_b[e][i] * yl);      // 0 stays 0 in idle lanes (y = dy = 0) and pad rows (xt = d = 0)
+                    }
+                }
+                __syncthreads();
+            }
+            bh -= a.lr * gbh;
+            if (tid < RP) s_bv[tid] -= a.lr * gbv;
+            __syncthreads();
+        }
+    }
+    if (s_bad) { if (tid == 0) atomicOr(a.err, 4); return; }
+#pragma unroll
+    for (int r = 0; r < RPW; ++r) { const int i = w + 16 * r; if (cact && i < row) a.W[(size_t)i * col + j] = Wr[r]; }
+    if (w == 0 && cact) a.bhid[j] = bh;
+    if (wg == 0) {
+        for (int i = tid; i < row; i += 1024) a.bvis[i] = s_bv[i];
+        const double cwv = wave_sum(cost);
+        if (l == 0) s_cost[w] = cwv;
+        __syncthreads();
+        if (tid == 0 && a.cost) { double t = 0.0; for (int q = 0; q < 16; ++q) t += s_cost[q]; *a.cost = t; }
+    }
+}
+
 struct DenseArgs { float *W, *bhid, *bvis; const float* X; int64_t N; int row, col; float lr; int skip_last; double* cost; };
 
 template <int RPW, int CPL>
@@ -603,6 +877,40 @@ int dense_g_epoch_t(S* W, S* bhid, S* bvis, const S* X, int64_t N, int row, int 
     return FNN_OK;
 }
 
+// dae_dense_batch / _f64: one persistent launch of k_dae_dense_batch per call; one scratch allocation (exchange buffer, the private
+// d / y / dy buffers, flags, error word, cost: at most 25 MB at M = 256, row = 512 in f64), freed on every path
+template <typename S>
+int dense_batch_t(const char* name, S* W, S* bhid, S* bvis, const S* X, const uint8_t* keep, int64_t N, int M, int row, int col, S lr,
+                  int skip_last, double* cost_sum_out, void* stream)
+{
+    if (!W || !bhid || !bvis || !X || N < 1 || M < 1 || M > 256 || row < 1 || row > 16 * 32 || col < 1 || col > 64 * DSP_NS)
+        DFAIL(FNN_ERR_ARG, std::string(name) + ": need non-null W, bhid, bvis, X, N >= 1, a mini-batch size M in 1..256, row in 1..512 and col in 1..512");
+    hipStream_t st = (hipStream_t)stream;
+    const int rowp = (row + 15) / 16 * 16, cw = (col + DSP_NS - 1) / DSP_NS, Mc = (int)((N < (int64_t)M) ? N : (int64_t)M);
+    struct Scratch { char* p = nullptr; ~Scratch() { if (p) hipFree(p); } } sc;
+    const size_t xb = (size_t)2 * DSP_NS * Mc * rowp * sizeof(S), db = (size_t)DSP_NS * Mc * rowp * sizeof(S),
+                 yb = (size_t)DSP_NS * 2 * Mc * 64 * sizeof(S), fb = (size_t)DSP_NS * 64, tail = fb + 64;     // flags, then error word and cost
+    DHK(hipMalloc((void**)&sc.p, xb + db + yb + tail));
+    char* t = sc.p + xb + db + yb;
+    DHK(hipMemsetAsync(t, 0, tail, st));
+    DenseBArgs<S> ba{W, bhid, bvis, X, keep, N, M, row, col, cw, lr, skip_last, reinterpret_cast<double*>(t + fb + 8),
+                     reinterpret_cast<S*>(sc.p), reinterpret_cast<S*>(sc.p + xb), reinterpret_cast<S*>(sc.p + xb + db),
+                     reinterpret_cast<unsigned long long*>(t), rowp, Mc, reinterpret_cast<int*>(t + fb)};
+    const int rpw = (row + 15) / 16;
+    if (rpw <= 8) hipLaunchKernelGGL((k_dae_dense_batch<S, 8>), dim3(8 * DSP_NS), dim3(1024), 0, st, ba);
+    else if (rpw <= 13) hipLaunchKernelGGL((k_dae_dense_batch<S, 13>), dim3(8 * DSP_NS), dim3(1024), 0, st, ba);
+    else if (rpw <= 19) hipLaunchKernelGGL((k_dae_dense_batch<S, 19>), dim3(8 * DSP_NS), dim3(1024), 0, st, ba);
+    else hipLaunchKernelGGL((k_dae_dense_batch<S, 32>), dim3(8 * DSP_NS), dim3(1024), 0, st, ba);
+    DHK(hipGetLastError());
+    double c = 0.0; int bad = 0;
+    DHK(hipMemcpyAsync(&c, ba.cost, 8, hipMemcpyDeviceToHost, st));
+    DHK(hipMemcpyAsync(&bad, ba.err, 4, hipMemcpyDeviceToHost, st));
+    DHK(hipStreamSynchronize(st));
+    if (bad) DFAIL(FNN_ERR_HIP, std::string(name) + ": a workgroup of the split trainer gave up waiting for its peers; the parameters of this pass are invalid");
+    if (cost_sum_out) *cost_sum_out = c;
+    return FNN_OK;
+}
+
 template <typename S>
 int bag_cumsum_t(const S* W0, const S* b0, int H, int64_t n_rows, const int32_t* ids, int n, int F, S* out, void* stream)
 {
@@ -664,6 +972,17 @@ int dae_dense_epoch_f64(double* W, double* bhid, double* bvis, const double* X, 
                         int skip_last_update, double* cost_sum_out, void* stream)
 {
     return dense_g_epoch_t<double>(W, bhid, bvis, X, N, row, col, lr, skip_last_update, cost_sum_out, stream);
+}
+
+int dae_dense_batch(float* W, float* bhid, float* bvis, const float* X, const uint8_t* keep, int64_t N, int M, int row, int col, float lr,
+                    int skip_last_update, double* cost_sum_out, void* stream)
+{
+    return dense_batch_t<float>("dae_dense_batch", W, bhid, bvis, X, keep, N, M, row, col, lr, skip_last_update, cost_sum_out, stream);
+}
+int dae_dense_batch_f64(double* W, double* bhid, double* bvis, const double* X, const uint8_t* keep, int64_t N, int M, int row, int col,
+                        double lr, int skip_last_update, double* cost_sum_out, void* stream)
+{
+    return dense_batch_t<double>("dae_dense_batch_f64", W, bhid, bvis, X, keep, N, M, row, col, lr, skip_last_update, cost_sum_out, stream);
 }
 
 int dae_bag_cumsum_sigmoid(const float* W0, const float* b0, int H, int64_t n_rows, const int32_t* ids, int n, int F, float* out,

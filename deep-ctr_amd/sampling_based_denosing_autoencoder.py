@@ -3,6 +3,9 @@
 the sparse first layer (`sparse_da`, :234-345), the dense upper layers (`da`, :116-232) and the
 lower-layer propagation inside `da` (:163-187).  Same name, arguments and return value; the file
 name keeps the reference's spelling.
+`da` itself is here too, as the reference writes it: a mini-batch trainer with input corruption
+(batch_size, corruption_level), on dae_dense_batch[_f64]; `get_da_weights` reaches it through
+`da_batch_size` / `corruption_level` and by default makes the reference's online calls.
 
 What the reference's code does is kept, including what it probably did not intend (each is a
 tested behaviour of oracle/dae_oracle.py, Q1-Q5 there): the sparse layer's W comes back un-trained
@@ -67,12 +70,96 @@ def sampled_visibles(rs, lines, row, k=2):
     return idx, x
 
 
-def get_da_weights(file, arr, ncases, num_feats=16, batch_size=100000, epochs=3, learning_rate=0.1, device=0, precision='f64'):
+def _train_dense_batch(lib, sfx, W, bh, bv, X, N, row, col, learning_rate, epochs, batch_size, corruption_level, seed, dev, st):
+    """`epochs` passes of dae_dense_batch[_f64] over X [N, row] (device tensors, updated in place); skip_last_update on the
+    last pass only (Q2: the reference returns the state before its last train_da call).  corruption_level > 0: the keep
+    masks come from dl_utils.RandomStreams(seed).binomial(size=(N, row), n=1, p=1 - corruption_level), one [N, row] draw per
+    pass -- the legacy RandomState.binomial consumes its stream element by element, so that equals the per-call draws
+    of get_corrupted_input (:86-89).  That this stand-in IS Theano's stream is unpinned: Theano cannot run here."""
+    import torch
+    from . import dl_utils
+    dense_batch = getattr(lib, 'dae_dense_batch' + sfx)
+    op = dl_utils.RandomStreams(seed).binomial(size=(N, row), n=1, p=1 - corruption_level) if corruption_level > 0 else None
+    n_batches = (N + batch_size - 1) // batch_size
+    cost = C.c_double()
+    for ep in range(epochs):
+        keep = torch.as_tensor(np.ascontiguousarray(op.draw(), dtype=np.uint8)).to(dev).contiguous() if op is not None else None
+        _check(lib, dense_batch(W.data_ptr(), bh.data_ptr(), bv.data_ptr(), X.data_ptr(), keep.data_ptr() if keep is not None else None,
+                                N, batch_size, row, col, learning_rate, 1 if ep == epochs - 1 else 0, C.byref(cost), st))
+        print('Training epoch %d, cost ' % ep, cost.value / n_batches)
+
+
+def da(row, col, file, results, learning_rate=0.1, training_epochs=15, batch_size=20, corruption_level=0, device=0, precision='f64'):
+    """:116-232 with the reference's name, argument order and return value (w, b): a dense denoising autoencoder
+    [row -> col] trained by mini-batch SGD on the lines of `file` propagated through the lower layers `results` =
+    [W0, b0, W1, b1, ...] (:163-187: Q3 running sum at layer 0, Q4 a sigmoid after every layer; with no lower layer the
+    lines' values are the input).  Initialisation replays :119-127: RandomState(123), the randint(2**30) that seeds
+    theano_rng, then W.  training_epochs passes of dae_dense_batch[_f64] (include/dae_hip.h), a short last batch with
+    its own mean; (w, b) are the parameters before the last mini-batch's update (Q2), float64 arrays.
+    corruption_level > 0: keep masks from dl_utils.RandomStreams seeded with the value drawn above, our stand-in for
+    Theano's stream -- unpinned, since Theano cannot run here; the arithmetic on a given mask is pinned
+    (tests/dae_batch_ref.py).  batch_size 1..256, row and col 1..512 (the C ABI refuses anything else)."""
+    import torch
+    lib = _capi.load()
+    dev = torch.device('cuda', device)
+    st = torch.cuda.current_stream(dev).cuda_stream
+    f64 = precision == 'f64'
+    npdt, tdt = (np.float64, torch.float64) if f64 else (np.float32, torch.float32)
+    sfx = '_f64' if f64 else ''
+    lines = parse_lines(file)
+    N = len(lines)
+
+    def t32(a):
+        return torch.as_tensor(np.ascontiguousarray(a, dtype=npdt)).to(dev).contiguous()
+
+    if len(results) == 0:
+        X = t32(np.array([l[1] for l in lines], dtype=np.float32))
+    else:
+        n_fields = max(len(l[0]) for l in lines)
+        act = np.full((N, n_fields), -1, np.int32)                         # ALL ids of the line (:173-176)
+        for n, (ids, _) in enumerate(lines):
+            act[n, :len(ids)] = ids
+        W0, b0, act_d = t32(results[0]), t32(results[1]), torch.as_tensor(act).to(dev)
+        X = torch.empty((N, W0.shape[1]), dtype=tdt, device=dev)
+        _check(lib, getattr(lib, 'dae_bag_cumsum_sigmoid' + sfx)(W0.data_ptr(), b0.data_ptr(), W0.shape[1], W0.shape[0], act_d.data_ptr(),
+                                                                 N, n_fields, X.data_ptr(), st))
+        for i in range(2, len(results), 2):
+            Wl, bl = t32(results[i]), t32(results[i + 1])
+            X = _affine_sigmoid(lib, f64, X, Wl, bl, N, Wl.shape[0], Wl.shape[1], st)
+    if X.shape[1] != row:
+        raise ValueError("the propagated input has %d columns, the autoencoder %d visibles" % (X.shape[1], row))
+    rs = np.random.RandomState(123)                                        # :119
+    seed = int(rs.randint(2 ** 30))                                        # :120, the theano_rng seed
+    W = t32(rs.uniform(low=-_bound(col, row), high=_bound(col, row), size=(row, col)))
+    bh = torch.zeros(col, dtype=tdt, device=dev)
+    bv = torch.zeros(row, dtype=tdt, device=dev)
+    _train_dense_batch(lib, sfx, W, bh, bv, X, N, row, col, learning_rate, training_epochs, batch_size, corruption_level, seed, dev, st)
+    torch.cuda.synchronize(dev)
+    return W.cpu().numpy().astype(np.float64), bh.cpu().numpy().astype(np.float64)
+
+
+def _affine_sigmoid(lib, f64, X, W, bh, N, row, col, st):
+    """sigmoid(X W + b): the propagation between dense layers (:183-187)."""
+    import torch
+    Xn = torch.empty((N, col), dtype=X.dtype, device=X.device)
+    if f64:
+        _check(lib, lib.dae_affine_sigmoid_f64(X.data_ptr(), W.data_ptr(), bh.data_ptr(), N, row, col, Xn.data_ptr(), st))
+    else:
+        _check_rbm(lib, lib.rbm_affine(X.data_ptr(), W.data_ptr(), bh.data_ptr(), N, row, col, Xn.data_ptr(), st))
+        _check_rbm(lib, lib.rbm_sigmoid(Xn.data_ptr(), Xn.numel(), st))
+    return Xn
+
+
+def get_da_weights(file, arr, ncases, num_feats=16, batch_size=100000, epochs=3, learning_rate=0.1, device=0, precision='f64',
+                   da_batch_size=1, corruption_level=0.0):
     """:347-371.  arr = [x_dim, H0, H1, H2]; returns [W0, b0, W1, b1, W2, b2] (float64 arrays, as
     python/SNN_DAE.py:83-86 pickles them).  precision 'f64' (default) is the reference's own
     (theano.config.floatX): its online lr = 0.1 dynamics are sensitive enough that only an f64 run
     tracks them over a whole pre-training; 'f32' keeps W of the dense layers in registers (faster,
-    step-level parity 1e-7, trajectories drift apart after a few thousand steps)."""
+    step-level parity 1e-7, trajectories drift apart after a few thousand steps).
+    da_batch_size = 1 and corruption_level = 0 (the defaults, what the reference's get_da_weights passes) run the
+    online trainers; anything else trains the dense layers through dae_dense_batch[_f64] as `da` does (the sparse
+    first layer has no mini-batch form: Q1).  `batch_size` is the reference's argument and stays unused."""
     import torch
     lib = _capi.load()
     dev = torch.device('cuda', device)
@@ -94,7 +181,7 @@ def get_da_weights(file, arr, ncases, num_feats=16, batch_size=100000, epochs=3,
     for index in range(2, len(arr) + 1):
         row, col = int(arr[index - 2]), int(arr[index - 1])
         rs = np.random.RandomState(123)                                    # :119 / :238
-        rs.randint(2 ** 30)                                                # the theano_rng seed
+        seed = int(rs.randint(2 ** 30))                                    # the theano_rng seed
         cost = C.c_double()
         if index == 2:
             sparse_len, row = row, num_feats * k
@@ -125,10 +212,13 @@ def get_da_weights(file, arr, ncases, num_feats=16, batch_size=100000, epochs=3,
             W = t32(rs.uniform(low=-_bound(col, row), high=_bound(col, row), size=(row, col)))
             bh = torch.zeros(col, dtype=tdt, device=dev)
             bv = torch.zeros(row, dtype=tdt, device=dev)
-            for ep in range(epochs):
-                _check(lib, dense_epoch(W.data_ptr(), bh.data_ptr(), bv.data_ptr(), X.data_ptr(), N, row, col,
-                                                learning_rate, 1 if ep == epochs - 1 else 0, C.byref(cost), st))
-                print('Training epoch %d, cost ' % ep, cost.value / N)
+            if da_batch_size != 1 or corruption_level > 0:
+                _train_dense_batch(lib, sfx, W, bh, bv, X, N, row, col, learning_rate, epochs, da_batch_size, corruption_level, seed, dev, st)
+            else:
+                for ep in range(epochs):
+                    _check(lib, dense_epoch(W.data_ptr(), bh.data_ptr(), bv.data_ptr(), X.data_ptr(), N, row, col,
+                                            learning_rate, 1 if ep == epochs - 1 else 0, C.byref(cost), st))
+                    print('Training epoch %d, cost ' % ep, cost.value / N)
             results += [W.cpu().numpy().astype(np.float64), bh.cpu().numpy().astype(np.float64)]
             if index < len(arr):                                           # input of the next layer: sigmoid(X W + b)
                 Xn = torch.empty((N, col), dtype=tdt, device=dev)
