@@ -10,6 +10,8 @@ Value weights (the class's `sp_wt_hldr`, python/FM.py:24-29): `wts=` of train_st
 value is 1 (iPinYou).
 The reference's own schedule -- batch_size = 1, a step per line (python/ipinyou.py:129-140, :167-173) -- is `train_online`: a
 buffer of lines per call, one persistent workgroup walking them in order (fm_train_online); `ipinyou.run(..., online=True)`.
+`train_online_many(models, ids, y)` runs that schedule for several models in one pass, a workgroup per model
+(fm_train_online_multi), each ending bit for bit as its own `train_online` would; `ipinyou.run_many` is its driver.
 Rows shared between columns (`shared_rows=True`, fm_set_shared_rows): the columns of `ids` are then positions, not fields, as
 python/ipinyou.py:42-65 feeds the reference -- `ipinyou.to_column_ids` makes such ids and `ipinyou.run` is the driver.
 Random init uses NumPy RandomState(seed) streams (TensorFlow's cannot be reproduced here)."""
@@ -223,3 +225,41 @@ class FM(object):
             for i in range(len(rows)):
                 f.write('%d %s %s:%d\n' % (feat_ids[i], ' '.join(repr(float(v)) for v in rows[i]),
                                            field_names[int(field_of_row[i])], feat_ids[i]))
+
+
+def train_online_many(models, ids, y, wts=None, want_p=False, want_loss=True):
+    """fm_train_online_multi: the online schedule of `train_online` for every model of `models` (FM / LR objects, ranks, table
+    sizes, lr and lam their own) in ONE pass over the lines, a workgroup per model.  Every model ends bit for bit as its own
+    `train_online(ids, y, wts, ...)` would have left it.  Returns the list of the dicts `train_online` returns, in the order
+    of `models`.  ValueError for an empty list or models that differ in X_feas; FNNError for what the library refuses (a
+    model twice, Adam / FTRL, different devices, ...: nothing is trained then)."""
+    models = list(models)
+    if not models:
+        raise ValueError("train_online_many: no models")
+    first = models[0]
+    if any(m.X_feas != first.X_feas for m in models):
+        raise ValueError("train_online_many: the models differ in X_feas %s: one feed, one width" % ([m.X_feas for m in models],))
+    torch, lib, M = first._torch, first.lib, len(models)
+    ids_t, y_t = first._dev(ids, torch.int32), first._dev(y, torch.float32)
+    if ids_t.dim() != 2 or ids_t.shape[1] != first.X_feas or y_t.shape != (ids_t.shape[0],):
+        raise ValueError("ids %s, y %s: need [N, %d] and [N]" % (tuple(ids_t.shape), tuple(y_t.shape), first.X_feas))
+    w_t = first._wts(wts, ids_t)
+    N = ids_t.shape[0]
+    ps = [torch.empty(N, dtype=torch.float32, device=first.device) if want_p else None for _ in models]
+    hs = (C.c_void_p * M)(*[m.h.value if m.h else None for m in models])
+    lrs, lams = (C.c_float * M)(*[m.lr for m in models]), (C.c_float * M)(*[m.lam for m in models])
+    p_arr = (C.c_void_p * M)(*[p.data_ptr() if want_p and N else None for p in ps])
+    loss, last = (C.c_double * M)(), (C.c_float * M)()
+    cur = torch.cuda.current_stream(first.device)
+    for m in models:
+        m.stream.wait_stream(cur)
+    rc = lib.fm_train_online_multi(hs, M, ids_t.data_ptr(), None if w_t is None else w_t.data_ptr(), y_t.data_ptr(), N, lrs, lams,
+                                   p_arr if want_p else None, loss if want_loss else None, last if want_loss else None)
+    if rc != 0:
+        # the message is with hs[0], or with the library when hs[0] is no handle (a closed model)
+        raise FNNError(rc, (lib.fm_last_error(first.h if first.h else None) or b'').decode())
+    for m in models:
+        cur.wait_stream(m.stream)
+        m._keep = (ids_t, y_t, w_t)
+    return [{'loss': float(loss[i]) if want_loss else None, 'loss_last': float(last[i]) if want_loss else None, 'p': ps[i]}
+            for i in range(M)]

@@ -171,6 +171,8 @@ FM_SIGNATURES = {
     "fm_set_shared_rows": (_i, [_vp, _i]),
     "fm_count_shared_rows": (_i, [_vp, C.POINTER(_i64)]),
     "fm_train_online": (_i, [_vp, _vp, _vp, _vp, _i64, _f, _f, _vp, C.POINTER(C.c_double), C.POINTER(_f)]),
+    "fm_train_online_multi": (_i, [_vp, _i, _vp, _vp, _vp, _i64, C.POINTER(_f), C.POINTER(_f), _vp, C.POINTER(C.c_double),
+                                   C.POINTER(_f)]),
     "fm_online_form": (C.c_char_p, [_vp]),
 }
 

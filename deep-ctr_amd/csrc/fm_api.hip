@@ -9,6 +9,7 @@
 // 16 fields, the first being the 16-field kernels); the sort and both sparse-row updates are the FNN step's, sized by F.
 #include <hip/hip_runtime.h>
 
+#include <algorithm>
 #include <cmath>
 #include <cstring>
 #include <string>
@@ -433,6 +434,10 @@ struct fm_handle {
     unsigned long long* mark_cnt = nullptr;
     // fm_train_online: the examples one launch may take (FM_ONLINE_CHUNK, read at fm_create) and the call's loss accumulators
     int64_t online_chunk = 65536; fm_online::Out* online_out = nullptr;
+    // fm_train_online_multi, used when this handle is hs[0]: a pinned host ring and its device image for the launches' argument
+    // arrays (slot s of one is copied to slot s of the other on st), and the event recorded after the latest such copy
+    fm_online::Args* multi_host = nullptr; fm_online::Args* multi_dev = nullptr; size_t multi_cur = 0;
+    hipEvent_t multi_copied = nullptr, multi_join = nullptr;
 };
 
 #define MHK(h, expr) do { hipError_t e_ = (expr); if (e_ != hipSuccess) { (h)->err = std::string(#expr) + ": " + hipGetErrorString(e_); return FNN_ERR_HIP; } } while (0)
@@ -707,8 +712,10 @@ int fm_destroy(fm_handle* h)
     hipSetDevice(h->dev);
     if (h->st) hipStreamSynchronize(h->st);
     void* ptrs[] = {h->table16, h->b, h->gxp, h->loss_t, h->gb_part, h->loss_dev, h->err_flag, h->skeys, h->cpow1, h->s0, h->s1,
-                    h->sb, h->G, h->stamp, h->noshare, h->tag_first, h->tag_shared, h->mark_cnt, h->online_out};
+                    h->sb, h->G, h->stamp, h->noshare, h->tag_first, h->tag_shared, h->mark_cnt, h->online_out, h->multi_dev};
     for (void* p : ptrs) if (p) hipFree(p);
+    if (h->multi_host) hipHostFree(h->multi_host);
+    for (hipEvent_t e : {h->multi_copied, h->multi_join}) if (e) hipEventDestroy(e);
     row_group_free(h->rg);
     if (h->own_stream && h->st) hipStreamDestroy(h->st);
     delete h;
@@ -854,6 +861,153 @@ int fm_train_online(fm_handle* h, const int32_t* ids, const float* wts, const fl
         if (loss_last_out) *loss_last_out = o.loss_last;
         return rc;
     }
+    return FNN_OK;
+}
+
+// Several models, one feed (fm_online::k_fm_online_multi).  Everything runs on hs[0]'s stream, `st`: the other handles' streams
+// are joined into it by events before the first launch and wait for it after the last, and fold_scale() -- which works on its
+// handle's stream -- is given st for the time of its launch.
+//
+// The argument array of a launch is written into the next free slot of hs[0]'s pinned ring and copied from there to the same slot
+// of the device image.  The copy is asynchronous, so a slot is the copy's to read until the copy has run: slots are handed out
+// in order and never rewritten before the ring wraps, and a wrap first waits for the event recorded after the latest copy (all
+// copies are on st, in order, so that covers every one of them).  The ring persists from call to call for the same reason.
+namespace {
+
+constexpr size_t MULTI_RING = 8 * FM_ONLINE_MAX_MODELS;      // Args per ring (1 MiB): eight launches of the largest group
+
+int multi_ring(fm_handle* h0, size_t n_models, size_t* slot)
+{
+    if (!h0->multi_host) {                                           // first group call with this handle in front
+        MHK(h0, hipEventCreateWithFlags(&h0->multi_copied, hipEventDisableTiming));
+        MHK(h0, hipEventCreateWithFlags(&h0->multi_join, hipEventDisableTiming));
+        MHK(h0, hipMalloc((void**)&h0->multi_dev, MULTI_RING * sizeof(fm_online::Args)));
+        MHK(h0, hipHostMalloc((void**)&h0->multi_host, MULTI_RING * sizeof(fm_online::Args), hipHostMallocDefault));
+    }
+    if (h0->multi_cur + n_models > MULTI_RING) {
+        MHK(h0, hipEventSynchronize(h0->multi_copied));
+        h0->multi_cur = 0;
+    }
+    *slot = h0->multi_cur;
+    h0->multi_cur += n_models;
+    return FNN_OK;
+}
+
+}  // namespace
+
+int fm_train_online_multi(fm_handle* const* hs, int n_models, const int32_t* ids, const float* wts, const float* y, int64_t N,
+                          const float* lr, const float* lambda, float* const* p_out, double* loss_sum_out, float* loss_last_out)
+{
+    fm_handle* h0 = hs && n_models >= 1 && n_models <= FM_ONLINE_MAX_MODELS ? hs[0] : nullptr;
+    auto refuse = [&](int code, const std::string& msg) { (h0 ? h0->err : g_fm_err) = msg; return code; };
+    auto at = [](const char* what, int m) { return std::string("fm_train_online_multi: model ") + std::to_string(m) + ": " + what; };
+    if (!hs || !lr || !lambda) return refuse(FNN_ERR_ARG, "fm_train_online_multi: null hs, lr or lambda");
+    if (n_models < 1 || n_models > FM_ONLINE_MAX_MODELS) return refuse(FNN_ERR_ARG, "fm_train_online_multi: n_models must be in [1, 1024]");
+    for (int m = 0; m < n_models; ++m) if (!hs[m]) return refuse(FNN_ERR_ARG, at("null handle", m));
+    {
+        std::vector<const fm_handle*> seen(hs, hs + n_models);
+        std::sort(seen.begin(), seen.end());
+        const auto dup = std::adjacent_find(seen.begin(), seen.end());
+        if (dup != seen.end()) {
+            int m = n_models - 1;
+            while (hs[m] != *dup) --m;                                // the later of the two places
+            return refuse(FNN_ERR_ARG, at("the same handle twice in one call (two workgroups would race on one table)", m));
+        }
+    }
+    for (int m = 1; m < n_models; ++m)
+        if (hs[m]->F != h0->F || hs[m]->dev != h0->dev) return refuse(FNN_ERR_ARG, at("n_fields or device differs from model 0's", m));
+    if (N < 0 || (N > 0 && (!ids || !y))) return refuse(FNN_ERR_ARG, "fm_train_online_multi: need N >= 0, ids and y");
+    for (int m = 0; m < n_models; ++m) {
+        const float ll = lr[m] * lambda[m];
+        if (!(ll >= 0.f && ll < 1.0f) || lambda[m] < 0.f) return refuse(FNN_ERR_ARG, at("need 0 <= lr * lambda < 1", m));
+    }
+    for (int m = 0; m < n_models; ++m) {
+        if (hs[m]->opt != FM_OPT_SGD) return refuse(FNN_ERR_STATE, at("plain SGD only (Adam / FTRL pass over the whole table per step)", m));
+        if (!hs[m]->table16) return refuse(FNN_ERR_STATE, at("fm_set_table has not been called", m));
+    }
+    for (int m = 0; m < n_models; ++m) {
+        if (loss_sum_out) loss_sum_out[m] = 0.0;
+        if (loss_last_out) loss_last_out[m] = 0.f;
+    }
+    if (N == 0) return FNN_OK;
+    MHK(h0, hipSetDevice(h0->dev));
+    const hipStream_t st = h0->st;
+    // the streams that are not st, each once
+    std::vector<hipStream_t> others;
+    for (int m = 1; m < n_models; ++m) if (hs[m]->st != st) others.push_back(hs[m]->st);
+    std::sort(others.begin(), others.end());
+    others.erase(std::unique(others.begin(), others.end()), others.end());
+    size_t slot = 0;
+    int rc = multi_ring(h0, (size_t)n_models, &slot);                 // also creates the events
+    if (rc != FNN_OK) return rc;
+    for (hipStream_t o : others) {                                    // st after everything enqueued on the others so far
+        MHK(h0, hipEventRecord(h0->multi_join, o));
+        MHK(h0, hipStreamWaitEvent(st, h0->multi_join, 0));
+    }
+    int64_t chunk = h0->online_chunk;
+    std::vector<double> dec(n_models);
+    for (int m = 0; m < n_models; ++m) {
+        MHK(h0, hipMemsetAsync(hs[m]->online_out, 0, sizeof(fm_online::Out), st));
+        dec[m] = 1.0 - (double)lr[m] * (double)lambda[m];
+        if (hs[m]->online_chunk < chunk) chunk = hs[m]->online_chunk;
+    }
+    // an error from here on leaves the loop, and the other streams still get their join: they stay ordered behind what was launched
+    auto enqueue = [&]() -> int {
+    for (int64_t n0 = 0; n0 < N;) {
+        if (n0) { const int rr = multi_ring(h0, (size_t)n_models, &slot); if (rr != FNN_OK) return rr; }
+        // the launch ends after the first example whose decay takes ANY model's scale out of [2^-24, 1]
+        int64_t cnt = 0;
+        bool fold = false;
+        std::vector<double> s(n_models);
+        for (int m = 0; m < n_models; ++m) s[m] = hs[m]->scale;
+        while (n0 + cnt < N && cnt < chunk && !fold) {
+            for (int m = 0; m < n_models; ++m) { s[m] *= dec[m]; fold = fold || s[m] < 5.96e-8 || s[m] > 1.0; }
+            ++cnt;
+        }
+        fm_online::Args* a = h0->multi_host + slot;
+        for (int m = 0; m < n_models; ++m) {
+            fm_handle* h = hs[m];
+            a[m] = fm_online::Args{ids + n0 * h->F, wts ? wts + n0 * h->F : nullptr, y + n0, cnt, h->F, h->K, h->rw, h->table16, h->n_rows, h->b,
+                                   h->scale, dec[m], lr[m], lambda[m], p_out && p_out[m] ? p_out[m] + n0 : nullptr, h->err_flag,
+                                   h->online_out};
+        }
+        MHK(h0, hipMemcpyAsync(h0->multi_dev + slot, a, (size_t)n_models * sizeof(fm_online::Args), hipMemcpyHostToDevice, st));
+        MHK(h0, hipEventRecord(h0->multi_copied, st));
+        hipLaunchKernelGGL(fm_online::k_fm_online_multi, dim3((unsigned)n_models), dim3(256), 0, st, h0->multi_dev + slot);
+        MHK(h0, hipGetLastError());
+        for (int m = 0; m < n_models; ++m) {
+            fm_handle* h = hs[m];
+            h->scale = s[m];
+            if (s[m] < 5.96e-8 || s[m] > 1.0) {
+                const hipStream_t own = h->st;
+                h->st = st;                                           // fold_scale launches on h->st: this one belongs on st
+                const int rf = fold_scale(h);
+                h->st = own;
+                if (rf != FNN_OK) { if (h != h0) h0->err = at(h->err.c_str(), m); return rf; }
+            }
+        }
+        n0 += cnt;
+    }
+    return FNN_OK;
+    };
+    rc = enqueue();
+    if (!others.empty()) {                                            // whatever the other streams get from here on comes after the call
+        MHK(h0, hipEventRecord(h0->multi_join, st));
+        for (hipStream_t o : others) MHK(h0, hipStreamWaitEvent(o, h0->multi_join, 0));
+    }
+    if (rc != FNN_OK || (!loss_sum_out && !loss_last_out)) return rc;
+    std::string bad;
+    for (int m = 0; m < n_models; ++m) {
+        fm_handle* h = hs[m];
+        fm_online::Out o{0.0, 0.f, 0.f};
+        MHK(h0, hipMemcpyAsync(&o, h->online_out, sizeof(o), hipMemcpyDeviceToHost, h->st));
+        const int rm = fm_sync(h);
+        if (rm == FNN_ERR_RANGE) bad += (bad.empty() ? "" : ", ") + std::to_string(m);
+        else if (rm != FNN_OK) { if (h != h0) h0->err = at(h->err.c_str(), m); return rm; }
+        if (loss_sum_out) loss_sum_out[m] = o.loss_sum;
+        if (loss_last_out) loss_last_out[m] = o.loss_last;
+    }
+    if (!bad.empty()) MFAIL(h0, FNN_ERR_RANGE, "fm_train_online_multi: feature id outside [-1, n_rows) in model(s) " + bad);
     return FNN_OK;
 }
 

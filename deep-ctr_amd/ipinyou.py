@@ -129,6 +129,53 @@ def exact_auc(labels, preds):
     return (rank[labels].sum() - n1 * (n1 + 1) / 2.0) / (n0 * float(n1))
 
 
+def _dims(train_path, test_path):
+    """(X_dim, X_feas) as python/ipinyou.py:117-121 takes them: `stat` of both files, X_dim = max + 2, X_feas = the longest line."""
+    X_dim_train, X_feas_train = stat(train_path)
+    X_dim_test, X_feas_test = stat(test_path)
+    X_feas = max(X_feas_train, X_feas_test)
+    if X_feas > 64:
+        raise ValueError("the longest line has %d features: FM / LR take at most 64 columns (fm_create)" % X_feas)
+    return max(X_dim_train, X_dim_test) + 2, X_feas
+
+
+def _load_eval(test_path, eval_size, X_dim, X_feas):
+    """The test lines one evaluation of `run` sees: chunks of eval_size lines, at most 10 * eval_size of them
+    (python/ipinyou.py:196), each shuffled as load_ipinyou_data shuffles.  (ids, wts, y), or None for an empty file."""
+    e_ids, e_wts, e_y = [], [], []
+    with open(test_path) as test_data_set:
+        while sum(len(v) for v in e_y) < 10 * eval_size:
+            t_ind, t_val, t_y = load_ipinyou_data(test_data_set, eval_size, X_dim - 1, X_feas)
+            if t_ind is None:
+                break
+            e_ids.append(t_ind), e_wts.append(t_val), e_y.append(t_y)
+    if not e_y:
+        return None
+    return to_column_ids(np.concatenate(e_ids), np.concatenate(e_wts)) + (np.concatenate(e_y),)
+
+
+def _eval_auc(model, test):
+    """The model's AUC on _load_eval's lines; -1 without lines or with one class only, as watch_train logs it."""
+    if test is None:
+        return -1
+    try:
+        return model.evaluate(test[0], test[2], wts=test[1])[0]
+    except RuntimeError as e:
+        if getattr(e, 'code', None) != -4 or 'one class' not in str(e):
+            raise
+    return -1
+
+
+def _appender(log_file, echo):
+    def write_log(line):
+        if log_file:
+            with open(log_file, 'a') as f:
+                f.write(line + '\n')
+        if echo:
+            print(line)
+    return write_log
+
+
 def run(train_path, test_path, algo='FM', batch_size=4096, buffer=10000, eval_size=100000, epochs=1, log_file=None, device=0,
         echo=True, online=False):
     """python/ipinyou.py:113-199, the FM / LR driver, on the device.  `stat` both files, X_dim = max + 2, X_feas = the longest
@@ -145,12 +192,7 @@ def run(train_path, test_path, algo='FM', batch_size=4096, buffer=10000, eval_si
     Returns {'model', 'log': [(step, batch_auc, eval_auc, loss)], 'X_dim', 'X_feas'}."""
     from .FM import FM
     from .LR import LR
-    X_dim_train, X_feas_train = stat(train_path)
-    X_dim_test, X_feas_test = stat(test_path)
-    X_dim = max(X_dim_train, X_dim_test) + 2
-    X_feas = max(X_feas_train, X_feas_test)
-    if X_feas > 64:
-        raise ValueError("the longest line has %d features: FM / LR take at most 64 columns (fm_create)" % X_feas)
+    X_dim, X_feas = _dims(train_path, test_path)
     if online:
         batch_size = 1                                             # the models are built as the reference builds them
     if batch_size < 1 or batch_size > 4096:
@@ -165,13 +207,7 @@ def run(train_path, test_path, algo='FM', batch_size=4096, buffer=10000, eval_si
     else:
         raise ValueError("algo %r: 'LR' or 'FM'" % (algo,))
 
-    def write_log(line):
-        if log_file:
-            with open(log_file, 'a') as f:
-                f.write(line + '\n')
-        if echo:
-            print(line)
-
+    write_log = _appender(log_file, echo)
     write_log(model.log)
     history = []
     for it in range(epochs):
@@ -196,21 +232,7 @@ def run(train_path, test_path, algo='FM', batch_size=4096, buffer=10000, eval_si
                 step += len(labels)
                 if echo:
                     print('step: %d\ttime: %d\tloss: %g' % (step, time.time() - start_time, loss))
-                e_ids, e_wts, e_y = [], [], []
-                with open(test_path) as test_data_set:
-                    while sum(len(v) for v in e_y) < 10 * eval_size:
-                        t_ind, t_val, t_y = load_ipinyou_data(test_data_set, eval_size, X_dim - 1, X_feas)
-                        if t_ind is None:
-                            break
-                        e_ids.append(t_ind), e_wts.append(t_val), e_y.append(t_y)
-                eval_auc = -1
-                if e_y:
-                    t_ids, t_wts = to_column_ids(np.concatenate(e_ids), np.concatenate(e_wts))
-                    try:
-                        eval_auc = model.evaluate(t_ids, np.concatenate(e_y), wts=t_wts)[0]
-                    except RuntimeError as e:                          # one class only: -1, as watch_train logs it
-                        if getattr(e, 'code', None) != -4 or 'one class' not in str(e):
-                            raise
+                eval_auc = _eval_auc(model, _load_eval(test_path, eval_size, X_dim, X_feas))
                 batch_auc = exact_auc(labels, np.concatenate(preds))
                 history.append((step, batch_auc, eval_auc, loss))
                 write_log('%d\t%g\t%g\t%g\t' % (step, batch_auc, eval_auc, loss))
@@ -218,9 +240,64 @@ def run(train_path, test_path, algo='FM', batch_size=4096, buffer=10000, eval_si
     return {'model': model, 'log': history, 'X_dim': X_dim, 'X_feas': X_feas}
 
 
+def run_many(train_path, test_path, specs, buffer=10000, eval_size=100000, epochs=1, log_file=None, device=0, echo=True):
+    """`run(..., online=True)` for several models in ONE pass over the training file: the reference's driver trains LR and FM on
+    the same file (python/ipinyou.py:133, :139), its notebook FM10 / FM50 / FM100, each with a learning-rate and L2 search.
+    specs: a list of (algo, rank, lr, lam), algo 'LR' | 'FM' (rank is ignored for LR); the models are built as `run` builds
+    them (its init and seeds, plain SGD, shared_rows=True, batch_size 1).  Every buffer is one FM.train_online_many call -- a
+    workgroup per model walks the buffer's lines, so every model sees the schedule `run(..., online=True)` gives it, bit for
+    bit -- followed by each model's `evaluate` on the same test lines.  One log line per model per buffer, `run`'s line behind
+    the spec's index and a tab.  Returns a list of what `run` returns, one per spec."""
+    from .FM import FM, train_online_many
+    from .LR import LR
+    specs = [tuple(s) for s in specs]
+    if not specs:
+        raise ValueError("run_many: no specs")
+    for algo, rank, lr, lam in specs:
+        if algo not in ('LR', 'FM'):
+            raise ValueError("algo %r: 'LR' or 'FM'" % (algo,))
+    X_dim, X_feas = _dims(train_path, test_path)
+    max_eval = min(eval_size, 4096)
+    models = []
+    for algo, rank, lr, lam in specs:
+        if algo == 'LR':
+            models.append(LR(1, [X_dim, X_feas], ['uniform', -0.001, 0.001, [0x89AB], None], ['sgd', lr], [lam],
+                             'train', max_eval, device, shared_rows=True))
+        else:
+            models.append(FM(1, [X_dim, X_feas, int(rank)], ['uniform', -0.001, 0.001, [0x3210, 0x7654], None], ['sgd', lr],
+                             [lam], 'train', max_eval, device, shared_rows=True))
+    write_log = _appender(log_file, echo)
+    for i, model in enumerate(models):
+        write_log('%d\t%s' % (i, model.log))
+    history = [[] for _ in models]
+    for it in range(epochs):
+        step = 0
+        with open(train_path) as train_data_set:
+            while True:
+                X_ind, X_val, labels = load_ipinyou_data(train_data_set, buffer, X_dim - 1, X_feas)
+                if X_ind is None:
+                    break
+                ids, wts = to_column_ids(X_ind, X_val)
+                outs = train_online_many(models, ids, labels, wts=wts, want_p=True)
+                step += len(labels)
+                test = _load_eval(test_path, eval_size, X_dim, X_feas)
+                for i, (model, out) in enumerate(zip(models, outs)):
+                    rec = (step, exact_auc(labels, out['p'].cpu().numpy()), _eval_auc(model, test), out['loss_last'])
+                    history[i].append(rec)
+                    write_log('%d\t' % i + '%d\t%g\t%g\t%g\t' % rec)
+    return [{'model': m, 'log': h, 'X_dim': X_dim, 'X_feas': X_feas} for m, h in zip(models, history)]
+
+
+def parse_spec(text):
+    """'FM:10:1e-3:1e-2' -> ('FM', 10, 1e-3, 1e-2): algo:rank:lr:lambda of run_many."""
+    algo, rank, lr, lam = text.split(':')
+    return algo, int(rank), float(lr), float(lam)
+
+
 if __name__ == '__main__':
     # python/ipinyou.py:113-127: the campaign's yzx files under DEEPCTR_DATA_DIR (default ../data, as FNN.py), the log under
-    # DEEPCTR_LOG_DIR (default ../log/); `python ipinyou.py [FM|LR] [batch_size | online]`
+    # DEEPCTR_LOG_DIR (default ../log/); `python ipinyou.py [FM|LR] [batch_size | online]`, or
+    # `python ipinyou.py many FM:10:1e-3:1e-2 LR:0:1e-3:1e-3 ...` (algo:rank:lr:lambda, run_many)
     sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
     from deep_ctr_amd import ipinyou as _drv
     cam = 'all'
@@ -231,6 +308,11 @@ if __name__ == '__main__':
     if not os.path.exists(log_dir):
         os.makedirs(log_dir)
     print(os.path.join(log_dir, tag))
+    if algo == 'many':
+        _drv.run_many(os.path.join(data_dir, 'ipinyou-data/%s/train.yzx.txt.shuf' % cam),
+                      os.path.join(data_dir, 'ipinyou-data/%s/test.yzx.txt.shuf' % cam), [_drv.parse_spec(a) for a in sys.argv[2:]],
+                      epochs=int(os.environ.get('DEEPCTR_EPOCHS', 1)), log_file=os.path.join(log_dir, tag))
+        sys.exit(0)
     _drv.run(os.path.join(data_dir, 'ipinyou-data/%s/train.yzx.txt.shuf' % cam),
              os.path.join(data_dir, 'ipinyou-data/%s/test.yzx.txt.shuf' % cam), algo,
              batch_size=int(sys.argv[2]) if len(sys.argv) > 2 and sys.argv[2] != 'online' else 4096,

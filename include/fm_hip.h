@@ -121,6 +121,34 @@ int fm_predict_w(fm_handle* h, const int32_t* ids, const float* wts, int B, floa
  * y, N < 0, or lr * lambda outside [0, 1). */
 int fm_train_online(fm_handle* h, const int32_t* ids, const float* wts, const float* y, int64_t N,
                     float lr, float lambda, float* p_out, double* loss_sum_out, float* loss_last_out);
+/* fm_train_online for several models at once: the reference's driver trains LR and FM on one file (python/ipinyou.py:133, :139),
+ * its notebook FM10, FM50 and FM100, each under a learning-rate and L2 search.  Their chains are independent -- one feed, a table
+ * each -- so one launch runs them side by side, a workgroup per model, instead of one pass after another on one CU of 256.
+ * Model m ends exactly as fm_train_online(hs[m], ids, wts, y, N, lr[m], lambda[m], p_out[m], ..) alone would have left it, bit
+ * for bit: table, b, the lazy scale and where it folds, p_out[m], both losses and the range flag (both kernels are the same
+ * per-example body).  The models may differ in k (narrow and wide rows mixed), n_rows, lr, lambda, fm_set_shared_rows and the
+ * state they start from; they share n_fields and the device.
+ * HOST arrays of n_models entries: hs, lr, lambda; p_out (the array or any entry nullable) holds DEVICE pointers [N];
+ * loss_sum_out / loss_last_out (nullable; either one synchronises) take every model's losses.  ids, wts (nullable), y: the one
+ * DEVICE feed, as in fm_train_online.
+ * A launch takes the examples up to the nearest of FM_ONLINE_CHUNK (the smallest among the handles) and the first example whose
+ * decay takes ANY model's scale out of [2^-24, 1]; the models that left it are folded before the next launch.  Where the cuts
+ * fall changes no bit.  More models than CUs: the surplus workgroups queue; nothing waits on another workgroup.
+ * Streams: every launch, fold and copy of the call runs on hs[0]'s stream.  That stream first waits (events) for everything
+ * enqueued so far on every other handle's stream, and every other handle's stream then waits for the call's last launch, so
+ * the call is ordered after earlier work and before later work on ALL the handles, as if each had run its own fm_train_online.
+ * Refused before any launch, nothing written on any model and the loss arrays untouched, the message (with the index of the
+ * offending model) in fm_last_error(hs[0]), or fm_last_error(NULL) without a usable hs[0] --
+ *   FNN_ERR_ARG: null hs, lr or lambda; a null entry of hs; n_models outside 1..FM_ONLINE_MAX_MODELS; one handle twice (two
+ *   workgroups would race on one table); n_fields or device differing from hs[0]'s; N < 0; N > 0 with null ids or y; any
+ *   lr[m] * lambda[m] outside [0, 1);
+ *   FNN_ERR_STATE: any handle under Adam or FTRL, or without a table.
+ * N == 0: FNN_OK, nothing happens.  An id outside [-1, n_rows) is per model (n_rows may differ), absent for that model: a call
+ * that synchronises returns FNN_ERR_RANGE and lists the models' indices (their flags are then cleared); otherwise each handle's
+ * fm_sync reports its own flag, as after fm_train_online. */
+#define FM_ONLINE_MAX_MODELS 1024
+int fm_train_online_multi(fm_handle* const* hs, int n_models, const int32_t* ids, const float* wts, const float* y, int64_t N,
+                          const float* lr, const float* lambda, float* const* p_out, double* loss_sum_out, float* loss_last_out);
 /* which form the handle runs, as fnn_scat1_form() does for its knob: "plain" (the only one built) */
 const char* fm_online_form(const fm_handle* h);
 
