@@ -12,6 +12,8 @@ The reference's own schedule -- batch_size = 1, a step per line (python/ipinyou.
 buffer of lines per call, one persistent workgroup walking them in order (fm_train_online); `ipinyou.run(..., online=True)`.
 `train_online_many(models, ids, y)` runs that schedule for several models in one pass, a workgroup per model
 (fm_train_online_multi), each ending bit for bit as its own `train_online` would; `ipinyou.run_many` is its driver.
+`predict_many(models, ids)` / `evaluate_many(models, ids, y)` are the other half of such a search: every model's predictions and
+metrics on one test feed in one call (fm_predict_multi / fm_eval_multi), each bit for bit its own `forward` / `evaluate`.
 Rows shared between columns (`shared_rows=True`, fm_set_shared_rows): the columns of `ids` are then positions, not fields, as
 python/ipinyou.py:42-65 feeds the reference -- `ipinyou.to_column_ids` makes such ids and `ipinyou.run` is the driver.
 Random init uses NumPy RandomState(seed) streams (TensorFlow's cannot be reproduced here)."""
@@ -263,3 +265,83 @@ def train_online_many(models, ids, y, wts=None, want_p=False, want_loss=True):
         m._keep = (ids_t, y_t, w_t)
     return [{'loss': float(loss[i]) if want_loss else None, 'loss_last': float(last[i]) if want_loss else None, 'p': ps[i]}
             for i in range(M)]
+
+
+def _many_feed(what, models, ids, wts):
+    """The checks and the one device feed of predict_many / evaluate_many: (models, ids_t, w_t, handle array)."""
+    models = list(models)
+    if not models:
+        raise ValueError("%s: no models" % what)
+    first = models[0]
+    if any(m.X_feas != first.X_feas for m in models):
+        raise ValueError("%s: the models differ in X_feas %s: one feed, one width" % (what, [m.X_feas for m in models]))
+    ids_t = first._dev(ids, first._torch.int32)
+    if ids_t.dim() != 2 or ids_t.shape[1] != first.X_feas:
+        raise ValueError("ids %s: need [N, %d]" % (tuple(ids_t.shape), first.X_feas))
+    hs = (C.c_void_p * len(models))(*[m.h.value if m.h else None for m in models])
+    return models, ids_t, first._wts(wts, ids_t), hs
+
+
+def _many_error(first, rc):
+    # the message is with hs[0], or with the library when hs[0] is no handle (a closed model)
+    return FNNError(rc, (first.lib.fm_last_error(first.h if first.h else None) or b'').decode())
+
+
+def predict_many(models, ids, wts=None):
+    """fm_predict_multi: sigmoid(yhat) [N] of every model of `models` (FM / LR objects; ranks, table sizes and optimisers their own)
+    on the one feed `ids` [N, X_feas] (a device tensor is used as it is), in one call instead of N / max_batch calls per model.
+    Returns the list of device tensors, each bit for bit what the model's `forward(ids, wts)` returns.  ValueError for an empty
+    list or models that differ in X_feas; FNNError for what the library refuses and, as `forward`, for an id outside
+    [-1, X_dim) of some model (the models' indices in the message; such an id is absent for that model)."""
+    models, ids_t, w_t, hs = _many_feed("predict_many", models, ids, wts)
+    first, M, N = models[0], len(models), ids_t.shape[0]
+    torch = first._torch
+    ps = [torch.empty(N, dtype=torch.float32, device=first.device) for _ in models]
+    p_arr = (C.c_void_p * M)(*[p.data_ptr() for p in ps])
+    cur = torch.cuda.current_stream(first.device)
+    for m in models:
+        m.stream.wait_stream(cur)
+    rc = first.lib.fm_predict_multi(hs, M, ids_t.data_ptr(), None if w_t is None else w_t.data_ptr(), N, p_arr)
+    if rc != 0:
+        raise _many_error(first, rc)
+    bad = []
+    for i, m in enumerate(models):
+        cur.wait_stream(m.stream)
+        m._keep = (ids_t, None, w_t)
+        rs = m.lib.fm_sync(m.h)
+        if rs == _capi.FNN_ERR_RANGE:
+            bad.append(i)
+        elif rs != 0:
+            m._ck(rs)
+    if bad:
+        raise FNNError(_capi.FNN_ERR_RANGE, "predict_many: feature id outside [-1, n_rows) in model(s) " + ', '.join(map(str, bad)))
+    return ps
+
+
+def evaluate_many(models, ids, y, wts=None):
+    """fm_eval_multi: what `evaluate(ids, y, wts)` gives for every model of `models`, on ONE upload of the feed, with one scratch
+    allocation, one launch per stage for all the models and one synchronisation (per group of models that fit the scratch cap).
+    ids / y / wts may be device tensors already.  Returns a list of {'auc', 'rmse', 'logloss', 'status'}, the three numbers bit for
+    bit `evaluate`'s.  Nothing is raised for what `evaluate` reports about the numbers themselves: 'status' is FNN_ERR_RANGE (-4)
+    and the three are NaN for a model with a prediction NaN or outside [0, 1] -- a search wants the other models' results -- and
+    with one class only in y every 'auc' is NaN.  Every other error raises: ValueError for an empty list or models that differ
+    in X_feas, FNNError for what the library refuses and for an id outside [-1, X_dim) of some model."""
+    models, ids_t, w_t, hs = _many_feed("evaluate_many", models, ids, wts)
+    first, M, N = models[0], len(models), ids_t.shape[0]
+    torch = first._torch
+    y_t = first._dev(y, torch.int32)
+    if y_t.shape != (N,):
+        raise ValueError("ids %s, y %s: need [N, %d] and [N]" % (tuple(ids_t.shape), tuple(y_t.shape), first.X_feas))
+    auc, rmse, ll, status = (C.c_double * M)(), (C.c_double * M)(), (C.c_double * M)(), (C.c_int * M)()
+    cur = torch.cuda.current_stream(first.device)
+    for m in models:
+        m.stream.wait_stream(cur)
+    rc = first.lib.fm_eval_multi(hs, M, ids_t.data_ptr(), None if w_t is None else w_t.data_ptr(), y_t.data_ptr(), N,
+                                 auc, rmse, ll, status)
+    if rc != 0:
+        err = _many_error(first, rc)
+        if rc != _capi.FNN_ERR_RANGE or 'feature id' in str(err):
+            raise err
+    for m in models:
+        cur.wait_stream(m.stream)
+    return [{'auc': auc[i], 'rmse': rmse[i], 'logloss': ll[i], 'status': status[i]} for i in range(M)]

@@ -174,6 +174,9 @@ FM_SIGNATURES = {
     "fm_train_online_multi": (_i, [_vp, _i, _vp, _vp, _vp, _i64, C.POINTER(_f), C.POINTER(_f), _vp, C.POINTER(C.c_double),
                                    C.POINTER(_f)]),
     "fm_online_form": (C.c_char_p, [_vp]),
+    "fm_predict_multi": (_i, [_vp, _i, _vp, _vp, _i64, _vp]),
+    "fm_eval_multi": (_i, [_vp, _i, _vp, _vp, _vp, _i64, C.POINTER(C.c_double), C.POINTER(C.c_double), C.POINTER(C.c_double),
+                           C.POINTER(_i)]),
 }
 
 _i64p = C.POINTER(_i64)

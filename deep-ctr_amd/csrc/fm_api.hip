@@ -7,6 +7,8 @@
 // the bag table's wide sparse-row update (scatw1_body / scatw2_body); the sort, the tail and the optimiser pass are shared.
 // 1..64 fields on both layouts: the forwards take 16 fields at a time (fm_body<NF>, fm_wide_body<L, NC>; one instantiation per
 // 16 fields, the first being the 16-field kernels); the sort and both sparse-row updates are the FNN step's, sized by F.
+// Several models on one test feed (fm_predict_multi, fm_eval_multi): the same forward bodies, the arguments of each model read from
+// a device array (k_fm_multi, k_fm_wide_multi), and the metric pass of metrics.hip with a model dimension (metrics_multi).
 #include <hip/hip_runtime.h>
 
 #include <algorithm>
@@ -281,6 +283,53 @@ __global__ __launch_bounds__(256) void k_fm_wide_merge_fwd(const SortArgs so, co
     fm_wide_body<L, NC, WV>(a, (int)blockIdx.x - so.nblk, s_gb);
 }
 
+// Predictions of several models on one feed (fm_predict_multi, fm_eval_multi): the forward bodies above with train = 0, the
+// arguments of model m read from a device array instead of the kernel's own (k_fm_online_multi's way), so p is bit for bit what
+// k_fm / k_fm_wide write for that model: an example's p depends on its own lines and rows only, not on the batch around it.
+// One launch per layout class present in a call (narrow; wide at 16 lanes an example; wide at 32), so that the narrow models do
+// not run at the wide bodies' register count: cls[0 .. nm) lists the class's models as indices into args.  The grid is the
+// (model, example tile) pairs flattened over x and y; model_fast: neighbouring workgroups take the same tile of different
+// models (the feed's lines are shared, the tables are not), else a model's tiles are neighbours (one table at a time).
+struct EvalArg { FmArgs a; int cls; };
+__device__ __forceinline__ bool eval_pick(const EvalArg* __restrict__ args, const int first, const int nm, const int64_t tiles,
+                                          const int model_fast, int& m, int& tile)
+{
+    const int64_t lin = (int64_t)blockIdx.y * gridDim.x + blockIdx.x;
+    if (lin >= tiles * nm) return false;
+    const int64_t j = model_fast ? lin % nm : lin / tiles;
+    tile = (int)(model_fast ? lin / nm : lin % tiles);
+    m = args[first + j].cls;
+    return true;
+}
+template <int NF, bool WV>
+__global__ __launch_bounds__(256) void k_fm_multi(const EvalArg* __restrict__ args, const int first, const int nm, const int64_t tiles,
+                                                  const int model_fast)
+{
+    __shared__ float s_gb[16];
+    int m, tile;
+    if (!eval_pick(args, first, nm, tiles, model_fast, m, tile)) return;
+    const FmArgs a = args[m].a;
+    fm_body<NF, WV>(a, tile, s_gb);
+}
+template <int L, int NC, bool WV>
+__global__ __launch_bounds__(256) void k_fm_wide_multi(const EvalArg* __restrict__ args, const int first, const int nm, const int64_t tiles,
+                                                       const int model_fast)
+{
+    __shared__ float s_gb[256 / L];
+    int m, tile;
+    if (!eval_pick(args, first, nm, tiles, model_fast, m, tile)) return;
+    const FmArgs a = args[m].a;
+    fm_wide_body<L, NC, WV>(a, tile, s_gb);
+}
+// fm_eval_multi: the range flags of a group's models, read and then cleared where set (fm_sync's rule); one workgroup, so that a
+// handle listed twice shows its flag in both places before either clears it.
+__global__ __launch_bounds__(256) void k_fm_eval_flags(const EvalArg* __restrict__ args, const int n, int* __restrict__ flags)
+{
+    for (int i = threadIdx.x; i < n; i += 256) flags[i] = *static_cast<volatile int*>(args[i].a.err);
+    __syncthreads();
+    for (int i = threadIdx.x; i < n; i += 256) if (flags[i]) *args[i].a.err = 0;
+}
+
 // A training step is four launches: run sorts of the batch's (row, t) keys; their rank merge BESIDE the forward + gradients
 // (both need only the ids: the merge takes 16 F workgroups, the examples the rest); level-1 sparse-row update; level-2 update
 // BESIDE the bias / loss tail.  As six launches in a row (sort, sort, forward, scatter, scatter, tail) the step took 49.6 us.
@@ -438,6 +487,9 @@ struct fm_handle {
     // arrays (slot s of one is copied to slot s of the other on st), and the event recorded after the latest such copy
     fm_online::Args* multi_host = nullptr; fm_online::Args* multi_dev = nullptr; size_t multi_cur = 0;
     hipEvent_t multi_copied = nullptr, multi_join = nullptr;
+    // fm_predict_multi / fm_eval_multi, used when this handle is hs[0]: the same kind of ring for their argument arrays
+    void* eval_host = nullptr; void* eval_dev = nullptr; size_t eval_cur = 0;
+    hipEvent_t eval_copied = nullptr, eval_join = nullptr;
 };
 
 #define MHK(h, expr) do { hipError_t e_ = (expr); if (e_ != hipSuccess) { (h)->err = std::string(#expr) + ": " + hipGetErrorString(e_); return FNN_ERR_HIP; } } while (0)
@@ -543,6 +595,21 @@ void launch_fwd(const fm_handle* h, const SortArgs* sb, const FmArgs& a, int nb)
     default: launch_fwd_n<KT, 4>(h, sb, a, nb); break;
     }
 }
+// The forwards of a group of models (eval_forward): cls 0 narrow rows, 1 wide at 16 lanes an example, 2 wide at 32.
+template <int N, bool WV>
+void launch_multi_nw(hipStream_t st, int cls, dim3 grid, const EvalArg* args, int first, int nm, int64_t tiles, int model_fast)
+{
+    if (cls == 0) hipLaunchKernelGGL((k_fm_multi<N, WV>), grid, dim3(256), 0, st, args, first, nm, tiles, model_fast);
+    else if (cls == 1) hipLaunchKernelGGL((k_fm_wide_multi<16, N, WV>), grid, dim3(256), 0, st, args, first, nm, tiles, model_fast);
+    else hipLaunchKernelGGL((k_fm_wide_multi<32, N, WV>), grid, dim3(256), 0, st, args, first, nm, tiles, model_fast);
+}
+template <int N>
+void launch_multi_n(bool wv, hipStream_t st, int cls, dim3 grid, const EvalArg* args, int first, int nm, int64_t tiles, int model_fast)
+{
+    if (wv) launch_multi_nw<N, true>(st, cls, grid, args, first, nm, tiles, model_fast);
+    else launch_multi_nw<N, false>(st, cls, grid, args, first, nm, tiles, model_fast);
+}
+
 // The wide path's forward: 256 / L examples per workgroup (L = 16 while rank <= 63, else 32).
 int wide_epb(const fm_handle* h) { return h->rw <= 64 ? 16 : 8; }
 
@@ -712,10 +779,11 @@ int fm_destroy(fm_handle* h)
     hipSetDevice(h->dev);
     if (h->st) hipStreamSynchronize(h->st);
     void* ptrs[] = {h->table16, h->b, h->gxp, h->loss_t, h->gb_part, h->loss_dev, h->err_flag, h->skeys, h->cpow1, h->s0, h->s1,
-                    h->sb, h->G, h->stamp, h->noshare, h->tag_first, h->tag_shared, h->mark_cnt, h->online_out, h->multi_dev};
+                    h->sb, h->G, h->stamp, h->noshare, h->tag_first, h->tag_shared, h->mark_cnt, h->online_out, h->multi_dev, h->eval_dev};
     for (void* p : ptrs) if (p) hipFree(p);
     if (h->multi_host) hipHostFree(h->multi_host);
-    for (hipEvent_t e : {h->multi_copied, h->multi_join}) if (e) hipEventDestroy(e);
+    if (h->eval_host) hipHostFree(h->eval_host);
+    for (hipEvent_t e : {h->multi_copied, h->multi_join, h->eval_copied, h->eval_join}) if (e) hipEventDestroy(e);
     row_group_free(h->rg);
     if (h->own_stream && h->st) hipStreamDestroy(h->st);
     delete h;
@@ -1112,6 +1180,227 @@ int fm_eval_w(fm_handle* h, const int32_t* ids, const float* wts, const int32_t*
     const int rc = fm_sync(h);
     if (rc != FNN_OK) return rc;
     if (mrc == -2 || mrc == -3) MFAIL(h, FNN_ERR_RANGE, merr);
+    return FNN_OK;
+}
+
+// Several models, one test feed (fm_predict_multi, fm_eval_multi).  Everything runs on hs[0]'s stream under fm_train_online_multi's
+// rule (the other handles' streams joined in by events before the first launch, and waiting for the last one after it).  The
+// argument array of a group goes through a pinned ring of hs[0]'s and its device image, as that call's does: a slot is the copy's
+// to read until the copy has run, so slots are handed out in order and a wrap waits for the event behind the latest copy.
+namespace {
+
+constexpr size_t EVAL_RING = 4 * FM_EVAL_MAX_MODELS;             // EvalArgs per ring: four groups of the largest size
+
+int eval_ring(fm_handle* h0, size_t n, size_t* slot)
+{
+    if (!h0->eval_host) {                                            // first such call with this handle in front
+        if (!h0->eval_copied) MHK(h0, hipEventCreateWithFlags(&h0->eval_copied, hipEventDisableTiming));
+        if (!h0->eval_join) MHK(h0, hipEventCreateWithFlags(&h0->eval_join, hipEventDisableTiming));
+        if (!h0->eval_dev) MHK(h0, hipMalloc(&h0->eval_dev, EVAL_RING * sizeof(EvalArg)));
+        MHK(h0, hipHostMalloc(&h0->eval_host, EVAL_RING * sizeof(EvalArg), hipHostMallocDefault));
+    }
+    if (h0->eval_cur + n > EVAL_RING) {
+        MHK(h0, hipEventSynchronize(h0->eval_copied));
+        h0->eval_cur = 0;
+    }
+    *slot = h0->eval_cur;
+    h0->eval_cur += n;
+    return FNN_OK;
+}
+
+// What both calls refuse before any launch.  The message goes to hs[0], or to the library without a usable hs[0].
+int eval_check(const char* fn, fm_handle* const* hs, int n_models, const int32_t* ids, bool need_y, const int32_t* y, int64_t N)
+{
+    const std::string name(fn);
+    fm_handle* h0 = hs && n_models >= 1 && n_models <= FM_EVAL_MAX_MODELS ? hs[0] : nullptr;
+    auto refuse = [&](int code, const std::string& msg) { (h0 ? h0->err : g_fm_err) = name + ": " + msg; return code; };
+    auto at = [](const char* what, int m) { return "model " + std::to_string(m) + ": " + what; };
+    if (!hs) return refuse(FNN_ERR_ARG, "null hs");
+    if (n_models < 1 || n_models > FM_EVAL_MAX_MODELS) return refuse(FNN_ERR_ARG, "n_models must be in [1, 1024]");
+    for (int m = 0; m < n_models; ++m) if (!hs[m]) return refuse(FNN_ERR_ARG, at("null handle", m));
+    if (!ids || (need_y && !y)) return refuse(FNN_ERR_ARG, need_y ? "null ids or y" : "null ids");
+    if (N < 1 || N > ((int64_t)1 << 30)) return refuse(FNN_ERR_ARG, "N must be in [1, 2^30]");
+    for (int m = 1; m < n_models; ++m)
+        if (hs[m]->F != h0->F || hs[m]->dev != h0->dev) return refuse(FNN_ERR_ARG, at("n_fields or device differs from model 0's", m));
+    for (int m = 0; m < n_models; ++m) if (!hs[m]->table16) return refuse(FNN_ERR_STATE, at("fm_set_table has not been called", m));
+    return FNN_OK;
+}
+
+void eval_other_streams(fm_handle* const* hs, int n_models, std::vector<hipStream_t>& others)      // the streams that are not hs[0]'s, each once
+{
+    for (int m = 1; m < n_models; ++m) if (hs[m]->st != hs[0]->st) others.push_back(hs[m]->st);
+    std::sort(others.begin(), others.end());
+    others.erase(std::unique(others.begin(), others.end()), others.end());
+}
+
+// The predictions of g models on the N lines, p[m] (nullable) each: the argument array into the ring, then one launch per layout
+// class present.  *dev_args: where the group's arguments are on the device (k_fm_eval_flags reads them again).
+int eval_forward(fm_handle* h0, fm_handle* const* hs, int g, const int32_t* ids, const float* wts, int64_t N, float* const* p,
+                 const EvalArg** dev_args)
+{
+    size_t slot = 0;
+    const int rc = eval_ring(h0, (size_t)g, &slot);
+    if (rc != FNN_OK) return rc;
+    EvalArg* a = static_cast<EvalArg*>(h0->eval_host) + slot;
+    const EvalArg* d = static_cast<const EvalArg*>(h0->eval_dev) + slot;
+    auto cls_of = [](const fm_handle* h) { return !h->wide ? 0 : h->rw <= 64 ? 1 : 2; };   // launch_fwd_nw's choice of kernel
+    int cnt[3] = {0, 0, 0}, first[3], pos[3];
+    for (int m = 0; m < g; ++m) ++cnt[cls_of(hs[m])];
+    first[0] = 0; first[1] = cnt[0]; first[2] = cnt[0] + cnt[1];
+    for (int c = 0; c < 3; ++c) pos[c] = first[c];
+    const bool wt = !(getenv("FM_WT") && atoi(getenv("FM_WT")) == 0);
+    for (int m = 0; m < g; ++m) {
+        const fm_handle* h = hs[m];                               // fm_run's arguments of a prediction, with B = N
+        a[m].a = FmArgs{ids, nullptr, (int)N, h->F, h->K, h->table16, h->n_rows, h->b, (float)h->scale, 1.0f, 0, h->gxp, h->K1p, p[m],
+                        h->loss_t, h->gb_part, h->err_flag, wt, nullptr, (int)h->t, h->rw, wts};
+        a[pos[cls_of(h)]++].cls = m;
+    }
+    const hipStream_t st = h0->st;
+    MHK(h0, hipMemcpyAsync(const_cast<EvalArg*>(d), a, (size_t)g * sizeof(EvalArg), hipMemcpyHostToDevice, st));
+    MHK(h0, hipEventRecord(h0->eval_copied, st));
+    const char* order = getenv("FM_EVAL_ORDER");                  // "model": the model is the fast index of the grid; default: the tile
+    const int model_fast = order && !strcmp(order, "model");
+    for (int c = 0; c < 3; ++c) {
+        if (!cnt[c]) continue;
+        const int epb = c == 2 ? 8 : 16;                          // examples per workgroup: 256 / L, 16 on the narrow path
+        const int64_t tiles = (N + epb - 1) / epb, total = tiles * cnt[c];
+        const int64_t gx = total < (1 << 22) ? total : (1 << 22);
+        const dim3 grid((unsigned)gx, (unsigned)((total + gx - 1) / gx));
+        switch ((h0->F + 15) / 16) {
+        case 1: launch_multi_n<1>(wts != nullptr, st, c, grid, d, first[c], cnt[c], tiles, model_fast); break;
+        case 2: launch_multi_n<2>(wts != nullptr, st, c, grid, d, first[c], cnt[c], tiles, model_fast); break;
+        case 3: launch_multi_n<3>(wts != nullptr, st, c, grid, d, first[c], cnt[c], tiles, model_fast); break;
+        default: launch_multi_n<4>(wts != nullptr, st, c, grid, d, first[c], cnt[c], tiles, model_fast); break;
+        }
+        MHK(h0, hipGetLastError());
+    }
+    *dev_args = d;
+    return FNN_OK;
+}
+
+int eval_join_in(fm_handle* h0, const std::vector<hipStream_t>& others)
+{
+    for (hipStream_t o : others) {                                    // st after everything enqueued on the others so far
+        MHK(h0, hipEventRecord(h0->eval_join, o));
+        MHK(h0, hipStreamWaitEvent(h0->st, h0->eval_join, 0));
+    }
+    return FNN_OK;
+}
+int eval_join_out(fm_handle* h0, const std::vector<hipStream_t>& others)
+{
+    if (others.empty()) return FNN_OK;                                // whatever the other streams get from here on comes after the call
+    MHK(h0, hipEventRecord(h0->eval_join, h0->st));
+    for (hipStream_t o : others) MHK(h0, hipStreamWaitEvent(o, h0->eval_join, 0));
+    return FNN_OK;
+}
+
+inline size_t up256(size_t b) { return (b + 255) / 256 * 256; }
+// scratch of a group of g models: p [g][N], the metric pass's, out [g], flags [g], n_pos
+size_t eval_scratch_bytes(int g, int64_t N)
+{
+    return up256((size_t)g * (size_t)N * 4) + up256(metrics_multi_bytes(g, N)) + up256((size_t)g * sizeof(MetricOut)) + up256((size_t)g * 4) + 256;
+}
+
+}  // namespace
+
+int fm_predict_multi(fm_handle* const* hs, int n_models, const int32_t* ids, const float* wts, int64_t N, float* const* p_out)
+{
+    int rc = eval_check("fm_predict_multi", hs, n_models, ids, false, nullptr, N);
+    if (rc != FNN_OK) return rc;
+    fm_handle* h0 = hs[0];
+    if (!p_out) MFAIL(h0, FNN_ERR_ARG, "fm_predict_multi: null p_out");
+    MHK(h0, hipSetDevice(h0->dev));
+    std::vector<hipStream_t> others;
+    eval_other_streams(hs, n_models, others);
+    size_t slot = 0;
+    if (!h0->eval_host) { rc = eval_ring(h0, 0, &slot); if (rc != FNN_OK) return rc; }     // the events
+    rc = eval_join_in(h0, others);
+    if (rc != FNN_OK) return rc;
+    const EvalArg* d = nullptr;
+    rc = eval_forward(h0, hs, n_models, ids, wts, N, p_out, &d);
+    const int rj = eval_join_out(h0, others);                         // also after an error: the others stay ordered behind what ran
+    return rc != FNN_OK ? rc : rj;
+}
+
+int fm_eval_multi(fm_handle* const* hs, int n_models, const int32_t* ids, const float* wts, const int32_t* y, int64_t N,
+                  double* auc, double* rmse, double* logloss, int* status)
+{
+    int rc = eval_check("fm_eval_multi", hs, n_models, ids, true, y, N);
+    if (rc != FNN_OK) return rc;
+    fm_handle* h0 = hs[0];
+    MHK(h0, hipSetDevice(h0->dev));
+    const hipStream_t st = h0->st;
+    // the models of a group share one scratch allocation: as many as fit under the cap, one at the least
+    size_t cap = (size_t)1 << 30;
+    if (const char* e = getenv("FM_EVAL_SCRATCH_BYTES")) { const long long c = atoll(e); if (c >= 1) cap = (size_t)c; }
+    int G = n_models;
+    {
+        const size_t one = eval_scratch_bytes(1, N);
+        if ((size_t)G > cap / one) G = (int)(cap / one);
+        if (G < 1) G = 1;
+        while (G > 1 && eval_scratch_bytes(G, N) > cap) --G;
+    }
+    std::vector<hipStream_t> others;
+    eval_other_streams(hs, n_models, others);
+    size_t slot = 0;
+    if (!h0->eval_host) { rc = eval_ring(h0, 0, &slot); if (rc != FNN_OK) return rc; }     // the events
+    char* scratch = nullptr;
+    MHK(h0, hipMalloc((void**)&scratch, eval_scratch_bytes(G, N)));
+    float* p_d = reinterpret_cast<float*>(scratch);
+    char* ms = scratch + up256((size_t)G * (size_t)N * 4);
+    MetricOut* out_d = reinterpret_cast<MetricOut*>(ms + up256(metrics_multi_bytes(G, N)));
+    int* flags_d = reinterpret_cast<int*>(reinterpret_cast<char*>(out_d) + up256((size_t)G * sizeof(MetricOut)));
+    unsigned long long* npos_d = reinterpret_cast<unsigned long long*>(reinterpret_cast<char*>(flags_d) + up256((size_t)G * 4));
+    std::vector<MetricOut> ho(G);
+    std::vector<int> hf(G);
+    std::vector<float*> pp(G);
+    unsigned long long n_pos = 0;
+    std::string bad, range;
+    rc = eval_join_in(h0, others);
+    auto groups = [&]() -> int {
+        for (int g0 = 0; g0 < n_models; g0 += G) {
+            const int g = n_models - g0 < G ? n_models - g0 : G;
+            for (int m = 0; m < g; ++m) pp[m] = p_d + (size_t)m * (size_t)N;
+            const EvalArg* d = nullptr;
+            const int rf = eval_forward(h0, hs + g0, g, ids, wts, N, pp.data(), &d);
+            if (rf != FNN_OK) return rf;
+            MHK(h0, metrics_multi(st, p_d, y, N, g, ms, g0 == 0, npos_d, out_d));
+            hipLaunchKernelGGL(k_fm_eval_flags, dim3(1), dim3(256), 0, st, d, g, flags_d);
+            MHK(h0, hipGetLastError());
+            MHK(h0, hipMemcpyAsync(ho.data(), out_d, (size_t)g * sizeof(MetricOut), hipMemcpyDeviceToHost, st));
+            MHK(h0, hipMemcpyAsync(hf.data(), flags_d, (size_t)g * 4, hipMemcpyDeviceToHost, st));
+            if (g0 == 0) MHK(h0, hipMemcpyAsync(&n_pos, npos_d, 8, hipMemcpyDeviceToHost, st));
+            MHK(h0, hipStreamSynchronize(st));                        // the group's one synchronisation
+            const double np_ = (double)n_pos, nn = (double)(N - (int64_t)n_pos);
+            const bool two = n_pos > 0 && (int64_t)n_pos < N;
+            for (int m = 0; m < g; ++m) {
+                const MetricOut& o = ho[m];
+                const int i = g0 + m;
+                double v[3] = {std::nan(""), std::nan(""), std::nan("")};
+                if (!o.n_bad) {
+                    if (two) v[0] = (double)o.auc_sum / (2.0 * np_ * nn);
+                    v[1] = std::sqrt(o.se / (double)N); v[2] = o.ll / (double)N;
+                } else bad += (bad.empty() ? "" : ", ") + std::to_string(i);
+                if (hf[m]) range += (range.empty() ? "" : ", ") + std::to_string(i);
+                if (auc) auc[i] = v[0];
+                if (rmse) rmse[i] = v[1];
+                if (logloss) logloss[i] = v[2];
+                if (status) status[i] = o.n_bad ? FNN_ERR_RANGE : FNN_OK;
+            }
+        }
+        return FNN_OK;
+    };
+    if (rc == FNN_OK) rc = groups();
+    const int rj = eval_join_out(h0, others);                         // also after an error: the others stay ordered behind what ran
+    if (rc != FNN_OK) hipStreamSynchronize(st);                       // nothing may still be using the scratch
+    hipFree(scratch);
+    if (rc != FNN_OK) return rc;
+    if (rj != FNN_OK) return rj;
+    std::string msg;
+    if (!bad.empty()) msg += "predictions NaN or outside [0, 1] in model(s) " + bad;
+    if (!range.empty()) msg += std::string(msg.empty() ? "" : "; ") + "feature id outside [-1, n_rows) in model(s) " + range;
+    if (n_pos == 0 || (int64_t)n_pos == N) msg += std::string(msg.empty() ? "" : "; ") + "only one class present in y (roc_auc_score raises ValueError)";
+    if (!msg.empty()) MFAIL(h0, FNN_ERR_RANGE, "fm_eval_multi: " + msg);
     return FNN_OK;
 }
 

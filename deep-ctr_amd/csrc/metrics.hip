@@ -12,6 +12,8 @@
 // fmax(NaN, eps) = eps would give it a finite logloss term: such predictions are counted, and device_metrics reports them (-3).
 // The key sort of the METRIC pass is rocPRIM's device radix sort (a library sort for the metric pass; no hot-path
 // kernel goes through a library).  The groupings of the update paths use this file's own radix sort.
+// metrics_multi (several models on one feed: fm_eval_multi) runs the same key, AUC and sum kernels with a model dimension and
+// sorts with this file's own radix sort on 32-bit keys, a segment per model: no library in that path.
 #include "metrics.hip.h"
 
 #include <cstring>
@@ -26,9 +28,11 @@ namespace {
 constexpr int MB = 256;          // threads per block
 constexpr int ITEMS = 8;         // examples per thread
 
-__global__ __launch_bounds__(MB) void k_metric_keys(const float* __restrict__ p, const int32_t* __restrict__ y, int64_t n,
-                                                    uint32_t* __restrict__ keys, double* __restrict__ part /*[nblk][2]*/,
-                                                    unsigned long long* __restrict__ cnt /*[0] n_pos, [1] n_bad*/)
+// One block of 2,048 examples: their keys, the block's partial sums of the squared error and the logloss (a fixed-shape tree), and
+// the counts of positives (cnt_pos, nullable: not counted) and of predictions outside [0, 1] (cnt_bad).
+__device__ __forceinline__ void metric_keys_body(const float* __restrict__ p, const int32_t* __restrict__ y, int64_t n,
+                                                 uint32_t* __restrict__ keys, double* __restrict__ part /*[nblk][2]*/,
+                                                 unsigned long long* __restrict__ cnt_pos, unsigned long long* __restrict__ cnt_bad)
 {
     __shared__ double s_se[MB], s_ll[MB];
     __shared__ unsigned s_np;                               // positives | predictions outside [0, 1] << 16 (a block holds 2,048 examples)
@@ -60,13 +64,29 @@ __global__ __launch_bounds__(MB) void k_metric_keys(const float* __restrict__ p,
     }
     if (threadIdx.x == 0) {
         part[2 * (size_t)blockIdx.x] = s_se[0]; part[2 * (size_t)blockIdx.x + 1] = s_ll[0];
-        if (s_np & 0xFFFFu) atomicAdd(cnt, (unsigned long long)(s_np & 0xFFFFu));
-        if (s_np >> 16) atomicAdd(cnt + 1, (unsigned long long)(s_np >> 16));
+        if (cnt_pos && (s_np & 0xFFFFu)) atomicAdd(cnt_pos, (unsigned long long)(s_np & 0xFFFFu));
+        if (s_np >> 16) atomicAdd(cnt_bad, (unsigned long long)(s_np >> 16));
     }
 }
+__global__ __launch_bounds__(MB) void k_metric_keys(const float* __restrict__ p, const int32_t* __restrict__ y, int64_t n,
+                                                    uint32_t* __restrict__ keys, double* __restrict__ part /*[nblk][2]*/,
+                                                    unsigned long long* __restrict__ cnt /*[0] n_pos, [1] n_bad*/)
+{
+    metric_keys_body(p, y, n, keys, part, cnt, cnt + 1);
+}
+// The same for the predictions of several models on one feed (metrics_multi): blockIdx.y = the model; p, keys [model][n], part
+// [model][nblk][2].  y is shared, so the positives are counted once per call, by model 0 of its first group (count_pos).
+__global__ __launch_bounds__(MB) void k_metric_keys_multi(const float* __restrict__ p, const int32_t* __restrict__ y, int64_t n,
+                                                          uint32_t* __restrict__ keys, double* __restrict__ part, int count_pos,
+                                                          unsigned long long* __restrict__ n_pos, MetricOut* __restrict__ out)
+{
+    const size_t m = blockIdx.y;
+    metric_keys_body(p + m * (size_t)n, y, n, keys + m * (size_t)n, part + m * 2 * (size_t)gridDim.x,
+                     count_pos && m == 0 ? n_pos : nullptr, &out[m].n_bad);
+}
 
-__global__ __launch_bounds__(MB) void k_metric_auc(const uint32_t* __restrict__ sorted, int64_t n, int64_t n_neg,
-                                                   unsigned long long* __restrict__ acc)
+__device__ __forceinline__ void metric_auc_body(const uint32_t* __restrict__ sorted, int64_t n, int64_t n_neg,
+                                                unsigned long long* __restrict__ acc)
 {
     __shared__ unsigned long long s_a[MB];
     unsigned long long a = 0;
@@ -84,6 +104,37 @@ __global__ __launch_bounds__(MB) void k_metric_auc(const uint32_t* __restrict__ 
     for (int o = MB / 2; o > 0; o >>= 1) { if ((int)threadIdx.x < o) s_a[threadIdx.x] += s_a[threadIdx.x + o]; __syncthreads(); }
     if (threadIdx.x == 0 && s_a[0]) atomicAdd(acc, s_a[0]);
 }
+__global__ __launch_bounds__(MB) void k_metric_auc(const uint32_t* __restrict__ sorted, int64_t n, int64_t n_neg,
+                                                   unsigned long long* __restrict__ acc)
+{
+    metric_auc_body(sorted, n, n_neg, acc);
+}
+// blockIdx.y = the model; n_neg from the device's count of positives, so that the host need not wait for it.  One class only:
+// nothing to do (the AUC is undefined).
+__global__ __launch_bounds__(MB) void k_metric_auc_multi(const uint32_t* __restrict__ sorted, int64_t n,
+                                                         const unsigned long long* __restrict__ n_pos, MetricOut* __restrict__ out)
+{
+    const int64_t n_neg = n - (int64_t)*n_pos;
+    if (n_neg <= 0 || n_neg >= n) return;
+    metric_auc_body(sorted + (size_t)blockIdx.y * (size_t)n, n, n_neg, &out[blockIdx.y].auc_sum);
+}
+// The block partials of a model added in block order in f64, as device_metrics adds them on the host: a thread per model, eight
+// loads in flight, the additions in order.
+__global__ __launch_bounds__(64) void k_metric_sum_multi(const double* __restrict__ part, int64_t nblk, int nseg, MetricOut* __restrict__ out)
+{
+    const int m = blockIdx.x * 64 + threadIdx.x;
+    if (m >= nseg) return;
+    const double2* q = reinterpret_cast<const double2*>(part) + (size_t)m * nblk;
+    double se = 0.0, ll = 0.0;
+    for (int64_t b0 = 0; b0 < nblk; b0 += 8) {
+        double2 v[8];
+#pragma unroll
+        for (int k = 0; k < 8; ++k) v[k] = b0 + k < nblk ? q[b0 + k] : make_double2(0.0, 0.0);
+#pragma unroll
+        for (int k = 0; k < 8; ++k) if (b0 + k < nblk) { se += v[k].x; ll += v[k].y; }
+    }
+    out[m].se = se; out[m].ll = ll;
+}
 
 // ------------------------------------------------------------------------------------------
 // Stable LSD radix sort of independent SEGMENTS of 64-bit keys, 8 bits per pass (metrics.hip.h: radix_sort_segments).  The
@@ -98,12 +149,13 @@ __global__ __launch_bounds__(MB) void k_metric_auc(const uint32_t* __restrict__ 
 // ------------------------------------------------------------------------------------------
 constexpr int RS_TILE = 2048, RS_ITEMS = 8;
 
-__global__ __launch_bounds__(256) void k_rs_hist(const unsigned long long* __restrict__ keys, int n, int shift, int nblk, unsigned* __restrict__ hist)
+template <typename KT>
+__global__ __launch_bounds__(256) void k_rs_hist(const KT* __restrict__ keys, int n, int shift, int nblk, unsigned* __restrict__ hist)
 {
     __shared__ unsigned s_h[256];
     s_h[threadIdx.x] = 0;
     __syncthreads();
-    const unsigned long long* seg = keys + (size_t)blockIdx.y * n;
+    const KT* seg = keys + (size_t)blockIdx.y * n;
     const int base = blockIdx.x * RS_TILE;
 #pragma unroll
     for (int k = 0; k < RS_ITEMS; ++k) {
@@ -147,23 +199,24 @@ __global__ __launch_bounds__(256) void k_rs_scan(unsigned* __restrict__ hist, in
     }
 }
 
-__global__ __launch_bounds__(256) void k_rs_scatter(const unsigned long long* __restrict__ keys_in, unsigned long long* __restrict__ keys_out,
+template <typename KT>
+__global__ __launch_bounds__(256) void k_rs_scatter(const KT* __restrict__ keys_in, KT* __restrict__ keys_out,
                                                     int n, int shift, int nblk, const unsigned* __restrict__ hist)
 {
     __shared__ unsigned s_cnt[4][256];                         // per wave: keys of each digit seen so far (then: in all)
     __shared__ unsigned s_base[256];                           // where this tile's keys of a digit start in the segment
     const int tid = threadIdx.x, wave = tid >> 6, lane = tid & 63;
-    const unsigned long long* seg = keys_in + (size_t)blockIdx.y * n;
-    unsigned long long* out = keys_out + (size_t)blockIdx.y * n;
+    const KT* seg = keys_in + (size_t)blockIdx.y * n;
+    KT* out = keys_out + (size_t)blockIdx.y * n;
 #pragma unroll
     for (int w = 0; w < 4; ++w) s_cnt[w][tid] = 0;
     s_base[tid] = hist[((size_t)blockIdx.y * nblk + blockIdx.x) * 256 + tid];
     __syncthreads();
     const int base = blockIdx.x * RS_TILE + wave * (RS_TILE / 4);
     const unsigned long long lt = (1ull << lane) - 1ull;
-    unsigned long long key[RS_ITEMS]; unsigned pre[RS_ITEMS];
+    KT key[RS_ITEMS]; unsigned pre[RS_ITEMS];
 #pragma unroll
-    for (int k = 0; k < RS_ITEMS; ++k) { const int i = base + k * 64 + lane; key[k] = i < n ? seg[i] : 0ull; }
+    for (int k = 0; k < RS_ITEMS; ++k) { const int i = base + k * 64 + lane; key[k] = i < n ? seg[i] : (KT)0; }
 #pragma unroll
     for (int k = 0; k < RS_ITEMS; ++k) {
         const bool valid = base + k * 64 + lane < n;
@@ -239,18 +292,29 @@ void group_records(hipStream_t st, const unsigned long long* sorted, int nseg, i
     hipLaunchKernelGGL(k_group_rec, dim3((unsigned)((tot + 255) / 256)), dim3(256), 0, st, sorted, nseg, n, rec);
 }
 
-unsigned long long* radix_sort_segments(hipStream_t st, unsigned long long* keys, unsigned long long* tmp, unsigned* hist, int nseg, int n,
-                                        int lo_bit, int hi_bit)
+namespace {
+template <typename KT>
+KT* radix_sort_segments_t(hipStream_t st, KT* keys, KT* tmp, unsigned* hist, int nseg, int n, int lo_bit, int hi_bit)
 {
     const int nblk = (n + RS_TILE - 1) / RS_TILE;
-    unsigned long long *in = keys, *out = tmp;
+    KT *in = keys, *out = tmp;
     for (int shift = lo_bit; shift < hi_bit; shift += 8) {
-        hipLaunchKernelGGL(k_rs_hist, dim3(nblk, nseg), dim3(256), 0, st, in, n, shift, nblk, hist);
+        hipLaunchKernelGGL(k_rs_hist<KT>, dim3(nblk, nseg), dim3(256), 0, st, in, n, shift, nblk, hist);
         hipLaunchKernelGGL(k_rs_scan, dim3(nseg), dim3(256), 0, st, hist, nblk);
-        hipLaunchKernelGGL(k_rs_scatter, dim3(nblk, nseg), dim3(256), 0, st, in, out, n, shift, nblk, hist);
+        hipLaunchKernelGGL(k_rs_scatter<KT>, dim3(nblk, nseg), dim3(256), 0, st, in, out, n, shift, nblk, hist);
         std::swap(in, out);
     }
     return in;
+}
+}  // namespace
+unsigned long long* radix_sort_segments(hipStream_t st, unsigned long long* keys, unsigned long long* tmp, unsigned* hist, int nseg, int n,
+                                        int lo_bit, int hi_bit)
+{
+    return radix_sort_segments_t<unsigned long long>(st, keys, tmp, hist, nseg, n, lo_bit, hi_bit);
+}
+uint32_t* radix_sort_segments32(hipStream_t st, uint32_t* keys, uint32_t* tmp, unsigned* hist, int nseg, int n, int lo_bit, int hi_bit)
+{
+    return radix_sort_segments_t<uint32_t>(st, keys, tmp, hist, nseg, n, lo_bit, hi_bit);
 }
 size_t radix_sort_hist_bytes(int nseg, int n) { return (size_t)nseg * 256 * ((n + RS_TILE - 1) / RS_TILE) * sizeof(unsigned); }
 
@@ -327,6 +391,37 @@ done:
     for (void* q : {(void*)keys, (void*)sorted, (void*)part, (void*)cnt, tmp}) if (q) hipFree(q);
     return rc;
 #undef MK
+}
+
+// ---- the metrics of several models on one feed (metrics.hip.h: metrics_multi)
+namespace {
+inline size_t up256(size_t b) { return (b + 255) / 256 * 256; }
+inline int64_t metric_blocks(int64_t n) { return (n + (int64_t)MB * ITEMS - 1) / ((int64_t)MB * ITEMS); }
+}  // namespace
+
+size_t metrics_multi_bytes(int nseg, int64_t n)
+{
+    return 2 * up256((size_t)nseg * (size_t)n * 4) + up256(radix_sort_hist_bytes(nseg, (int)n)) + up256((size_t)nseg * (size_t)metric_blocks(n) * 16);
+}
+
+hipError_t metrics_multi(hipStream_t st, const float* p, const int32_t* y, int64_t n, int nseg, void* scratch, int count_pos,
+                         unsigned long long* n_pos, MetricOut* out)
+{
+    const int64_t nblk = metric_blocks(n);
+    const size_t kb = up256((size_t)nseg * (size_t)n * 4);
+    uint32_t* keys = static_cast<uint32_t*>(scratch);
+    uint32_t* tmp = reinterpret_cast<uint32_t*>(static_cast<char*>(scratch) + kb);
+    unsigned* hist = reinterpret_cast<unsigned*>(static_cast<char*>(scratch) + 2 * kb);
+    double* part = reinterpret_cast<double*>(static_cast<char*>(scratch) + 2 * kb + up256(radix_sort_hist_bytes(nseg, (int)n)));
+    hipError_t e = hipMemsetAsync(out, 0, (size_t)nseg * sizeof(MetricOut), st);
+    if (e == hipSuccess && count_pos) e = hipMemsetAsync(n_pos, 0, 8, st);
+    if (e != hipSuccess) return e;
+    hipLaunchKernelGGL(k_metric_keys_multi, dim3((unsigned)nblk, (unsigned)nseg), dim3(MB), 0, st, p, y, n, keys, part, count_pos, n_pos, out);
+    const uint32_t* sorted = radix_sort_segments32(st, keys, tmp, hist, nseg, (int)n, 0, 32);
+    const int64_t want = (n + MB - 1) / MB;                     // n_pos is not known here; blocks beyond the positives leave at once
+    hipLaunchKernelGGL(k_metric_auc_multi, dim3((unsigned)(want < 1024 ? want : 1024), (unsigned)nseg), dim3(MB), 0, st, sorted, n, n_pos, out);
+    hipLaunchKernelGGL(k_metric_sum_multi, dim3((unsigned)((nseg + 63) / 64)), dim3(64), 0, st, part, nblk, nseg, out);
+    return hipGetLastError();
 }
 
 }  // namespace fnn

@@ -30,6 +30,22 @@ int group_global(hipStream_t st, const int32_t* ids, int B, int F, int64_t n_row
 unsigned long long* radix_sort_segments(hipStream_t st, unsigned long long* keys, unsigned long long* tmp, unsigned* hist, int nseg, int n,
                                         int lo_bit, int hi_bit);
 size_t radix_sort_hist_bytes(int nseg, int n);
+// The same sort over 32-bit keys (the metric keys `label << 31 | bits of p`: half the traffic of the 64-bit form).
+uint32_t* radix_sort_segments32(hipStream_t st, uint32_t* keys, uint32_t* tmp, unsigned* hist, int nseg, int n, int lo_bit, int hi_bit);
+
+// device_metrics for the predictions of `nseg` models on ONE feed, p [nseg][n] against the one y [n], without rocPRIM, without an
+// allocation and without a synchronisation: everything is enqueued on `st` and out[m] (DEVICE, [nseg]) receives what model m's
+// metrics are made of.  The partition of the sums is device_metrics' -- 2,048 examples a block, its tree, the block partials added
+// in block order in f64 -- and the AUC's sum is an integer, so
+//     auc = auc_sum / (2 n_pos n_neg),  rmse = sqrt(se / n),  logloss = ll / n
+// are bit for bit what device_metrics returns for p[m].  n_bad != 0: model m has predictions NaN or outside [0, 1] (-3 there).
+// n_pos (DEVICE, one count): written when count_pos != 0 -- y is shared, so the first call over a feed counts and the later
+// ones (further groups of models) read it; the AUC pass takes n_neg from it on the device.  One class only: auc_sum stays 0.
+// scratch: metrics_multi_bytes(nseg, n) bytes, about 8.5 n per model; 1 <= n <= 2^30.
+struct MetricOut { double se, ll; unsigned long long auc_sum, n_bad; };
+size_t metrics_multi_bytes(int nseg, int64_t n);
+hipError_t metrics_multi(hipStream_t st, const float* p, const int32_t* y, int64_t n, int nseg, void* scratch, int count_pos,
+                         unsigned long long* n_pos, MetricOut* out);
 // Sorted keys `row << 20 | index` (row = 2^31 - 1: invalid, sorted last) of `nseg` segments of `n` -> rec[g * n + pos] =
 // {row, index, s, e}, [s, e) = the positions of the row's run inside its segment; {-1, 0, 0, 0} for invalid entries.
 constexpr int GROUP_INDEX_BITS = 20;

@@ -166,6 +166,20 @@ def _eval_auc(model, test):
     return -1
 
 
+def _eval_aucs(models, test):
+    """_eval_auc for every model of run_many in one FM.evaluate_many call: the test lines are converted and uploaded once, not
+    once per model.  A model whose predictions left [0, 1] raises, as its own `evaluate` would."""
+    from .FM import evaluate_many
+    from .engine import FNNError
+    if test is None:
+        return [-1] * len(models)
+    out = evaluate_many(models, test[0], test[2], wts=test[1])
+    for i, r in enumerate(out):
+        if r['status'] != 0:
+            raise FNNError(r['status'], "run_many: model %d has predictions NaN or outside [0, 1]" % i)
+    return [-1 if r['auc'] != r['auc'] else r['auc'] for r in out]         # NaN: one class only
+
+
 def _appender(log_file, echo):
     def write_log(line):
         if log_file:
@@ -246,7 +260,8 @@ def run_many(train_path, test_path, specs, buffer=10000, eval_size=100000, epoch
     specs: a list of (algo, rank, lr, lam), algo 'LR' | 'FM' (rank is ignored for LR); the models are built as `run` builds
     them (its init and seeds, plain SGD, shared_rows=True, batch_size 1).  Every buffer is one FM.train_online_many call -- a
     workgroup per model walks the buffer's lines, so every model sees the schedule `run(..., online=True)` gives it, bit for
-    bit -- followed by each model's `evaluate` on the same test lines.  One log line per model per buffer, `run`'s line behind
+    bit -- followed by ONE FM.evaluate_many call for all of them on the same test lines (fm_eval_multi: each model's numbers are
+    its own `evaluate`'s, bit for bit).  One log line per model per buffer, `run`'s line behind
     the spec's index and a tab.  Returns a list of what `run` returns, one per spec."""
     from .FM import FM, train_online_many
     from .LR import LR
@@ -280,9 +295,9 @@ def run_many(train_path, test_path, specs, buffer=10000, eval_size=100000, epoch
                 ids, wts = to_column_ids(X_ind, X_val)
                 outs = train_online_many(models, ids, labels, wts=wts, want_p=True)
                 step += len(labels)
-                test = _load_eval(test_path, eval_size, X_dim, X_feas)
-                for i, (model, out) in enumerate(zip(models, outs)):
-                    rec = (step, exact_auc(labels, out['p'].cpu().numpy()), _eval_auc(model, test), out['loss_last'])
+                eval_aucs = _eval_aucs(models, _load_eval(test_path, eval_size, X_dim, X_feas))
+                for i, out in enumerate(outs):
+                    rec = (step, exact_auc(labels, out['p'].cpu().numpy()), eval_aucs[i], out['loss_last'])
                     history[i].append(rec)
                     write_log('%d\t' % i + '%d\t%g\t%g\t%g\t' % rec)
     return [{'model': m, 'log': h, 'X_dim': X_dim, 'X_feas': X_feas} for m, h in zip(models, history)]

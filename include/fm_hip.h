@@ -180,6 +180,36 @@ int fm_eval(fm_handle* h, const int32_t* ids, const int32_t* y, int64_t N, doubl
 int fm_eval_w(fm_handle* h, const int32_t* ids, const float* wts, const int32_t* y, int64_t N,
               double* auc, double* rmse, double* logloss);
 
+/* Predictions and metrics of several models on ONE test feed in one call: what follows fm_train_online_multi in a learning-rate /
+ * L2 / rank search, where every model is evaluated on the same lines after every buffer.  One pass of the arguments, one or a few
+ * launches per stage for all the models, the library's own radix sort (32-bit keys, a segment per model), one scratch allocation.
+ * hs and the outputs auc, rmse, logloss, status: HOST arrays of n_models entries, each output array nullable.  ids [N, F], wts
+ * [N, F] (nullable: every value 1), y [N] (0 / non-zero): the one DEVICE feed.  1 <= N <= 2^30, NOT bounded by max_batch.
+ * The models may differ in k (narrow and wide rows mixed), n_rows, optimiser (SGD, Adam and FTRL handles all predict) and the
+ * shared-rows mode; they share n_fields and the device.  A handle may appear twice: the calls only read it.
+ * The contract: p_out[m] (DEVICE, [N]; the entry nullable) is bit for bit what the single-model prediction call writes for
+ * hs[m] over the same lines in chunks of max_batch, and auc[m], rmse[m], logloss[m] are bit for bit what the single-model
+ * evaluation returns -- the same forward bodies, the same 2,048-example blocks and block-order f64 sums, an integer AUC sum.  A
+ * pending lazy SGD scale is applied as those calls apply it; it is not folded and no bit of any model changes.
+ * status[m]: FNN_OK, or FNN_ERR_RANGE when model m has a prediction NaN or outside [0, 1] (its three metrics are then NaN).
+ * y with one class only: every auc[m] is NaN, rmse and logloss are still written.  An id outside [-1, n_rows) is per model
+ * (n_rows may differ) and absent for that model; the evaluation call clears the flags it reports, the prediction call leaves
+ * them to each handle's fm_sync.  Any of the three: FNN_ERR_RANGE, the models' indices in fm_last_error(hs[0]).
+ * Scratch (evaluation): about 12.5 N bytes per model, in groups of as many models as fit under FM_EVAL_SCRATCH_BYTES
+ * (environment, read per call; default 2^30), one model at the least; one allocation per call, and where the groups are cut
+ * changes no bit.  The evaluation call synchronises once per group; the prediction call does not synchronise.
+ * FM_EVAL_ORDER (environment, read per call): "tile" (default) or "model", the fast index of the prediction grid; same bits.
+ * Streams: everything runs on hs[0]'s stream, which first waits (events) for what is queued on every other handle's stream;
+ * every other handle's stream then waits for the call's last launch.
+ * Refused before any launch, nothing written, the message in fm_last_error(hs[0]) or fm_last_error(NULL) without a usable hs[0] --
+ *   FNN_ERR_ARG: null hs or a null entry; n_models outside 1..FM_EVAL_MAX_MODELS; null ids (evaluation: or y; prediction: or
+ *   p_out); N outside its range; n_fields or device differing from hs[0]'s;   FNN_ERR_STATE: a handle without a table. */
+#define FM_EVAL_MAX_MODELS 1024
+int fm_predict_multi(fm_handle* const* hs, int n_models, const int32_t* ids, const float* wts, int64_t N,
+                     float* const* p_out);
+int fm_eval_multi(fm_handle* const* hs, int n_models, const int32_t* ids, const float* wts, const int32_t* y,
+                  int64_t N, double* auc, double* rmse, double* logloss, int* status);
+
 #if defined(__GNUC__)
 #pragma GCC visibility pop
 #endif
