@@ -53,7 +53,8 @@ struct fnn_handle {
     bool bf16 = false;          // FNN_PREC_BF16: 2-byte elements
     bool split = false;         // FNN_PREC_BF16X3: 4-byte elements (bs16_t), the f32 mode's layouts
     int step1_waves = 8;                                               // FNN_STEP1_WAVES=4: four waves per strip (the 2-byte element types at hidden 300 / 100 run eight)
-    int wt_stores = 47;                                                // FNN_WT_STORES (MlpArgs::wt; 0: plain stores): how the strip kernel's training outputs leave
+    bool step1_fixed = true;                                           // FNN_STEP1_FORM=generic: never the fixed training instance of the strip kernel (launch_step1)
+    int wt_stores = 47;                                              // FNN_WT_STORES (MlpArgs::wt; 0: plain stores): how the strip kernel's training outputs leave
                                                                        // (bit 32: bf16 on FM rows, the transposed activations 16 bytes per lane, written through or plain as bit 1 says)
     bool bag = false; int rw = SLOT; size_t nbag = 0, off_bag = 0;     // FNN_MODE_BAG: bag rows rw floats wide
     bool wide = false;          // FNN_MODE_FM with k >= 17: FM rows of rw = rup(k, 4) floats, w_0 / ones columns F*rw and F*rw + 1
@@ -245,14 +246,6 @@ template <typename T> MlpArgs<T> make_mlp_args(fnn_handle* h, const int32_t* ids
                       (T*)h->xpT, (T*)h->d1T, (T*)h->d2T, (T*)h->dl1T, (T*)h->dl2T, (T*)h->dl3T, h->ldT,
                       h->gxp, p_out, h->loss_t, h->err_flag, h->bb0, h->rw, (T*)h->dlxT, nullptr, h->wt_stores};
 }
-template <typename T, int C1, int C2, int CX> size_t mlp_lds_bytes(bool bag, int F, int nw = 4) {
-    constexpr int PAD = 16 / (int)sizeof(T);
-    constexpr int LX = 64 * CX + PAD, L1 = 64 * C1 + PAD, L2 = 64 * C2 + PAD, LXM = LX > L1 ? LX : L1;
-    size_t n = (size_t)16 * (LXM + L1 + L2) * sizeof(T) + (size_t)16 * nw * sizeof(float);
-    if (bag) n += (size_t)16 * 64 * CX * sizeof(float) + (size_t)16 * F * sizeof(int);
-    else n += (size_t)nw * 16 * 36 * sizeof(float);           // the waves' blocks for regrouping gx' into whole lines (mlp_body, P4)
-    return n;
-}
 template <typename T> void launch_step1(fnn_handle* h, int nmlp, const MlpArgs<T>& a) {
     const bool big = h->H1p / 64 == 5;
     const dim3 g(nmlp), b(256);
@@ -269,6 +262,15 @@ template <typename T> void launch_step1(fnn_handle* h, int nmlp, const MlpArgs<T
                 hipLaunchKernelGGL((k_step1<T, 5, 2, 4, true, 8>), g, b8, lds, h->st, a);
             } else {
                 const size_t lds = mlp_lds_bytes<T, 5, 2, 4>(false, h->F, 8);
+                // the fixed training form (mlp_body, WTF): a training step of the default store policy in bf16, whose gather is
+                // one trip of the workgroup (8-example pieces in groups of 16, two lanes each: F <= 32); FNN_STEP1_FORM=generic
+                // and everything else -- prediction, any other FNN_WT_STORES -- run the instance that reads its flags
+                if constexpr (std::is_same<T, bf16_t>::value) {
+                    if (h->step1_fixed && a.train == 1 && a.wt == 47 && ((8 * h->F + 15) >> 4) * 32 <= 512) {
+                        hipLaunchKernelGGL((k_step1<T, 5, 2, 4, false, 8, 47>), g, b8, lds, h->st, a);
+                        return;
+                    }
+                }
                 hipLaunchKernelGGL((k_step1<T, 5, 2, 4, false, 8>), g, b8, lds, h->st, a);
             }
             return;
@@ -867,6 +869,7 @@ int fnn_create(const fnn_cfg* cfg, fnn_handle** out)
     h->bag = cfg->mode == FNN_MODE_BAG;
     if (const char* e = getenv("FNN_WT_STORES")) h->wt_stores = atoi(e);
     if (const char* e = getenv("FNN_STEP1_WAVES")) h->step1_waves = atoi(e) == 4 ? 4 : 8;
+    if (const char* e = getenv("FNN_STEP1_FORM")) h->step1_fixed = strcmp(e, "generic") != 0;      // fixed | generic; anything else: the default, fixed
     if (h->bag) { h->rw = cfg->h0; h->K = cfg->h0; h->xdim = cfg->h0; h->K1p = rup(cfg->h0 + 1, 64); }
     h->wide = !h->bag && h->K >= 17;
     if (h->wide) { h->rw = rup(h->K, 4); h->K1p = rup(h->F * h->rw + 2, 64); }       // field columns, then w_0 and the ones column

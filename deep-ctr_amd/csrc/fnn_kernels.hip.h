@@ -1164,7 +1164,18 @@ __device__ __forceinline__ void wring_product(f32x4 (&acc)[C], WRing<T, C, D>& r
 //              delta = gx * x * (1 - x) (:288-290) instead of gx.
 // D1, D2, DX: 64-column blocks of H1p, H2p, K1p.  NW waves share a layer's 16-column fragments in contiguous runs of
 // C = ceil(fragments / NW) per wave (NW = 4: the blocks' own quarters, C = D; NW = 8: the last waves' runs are clipped -- `ok`).
-template <typename T, int D1, int D2, int DX, bool BAG = false, int NW = 4>
+// WTF >= 0: the FIXED training form -- a.train = 1 and a.wt = WTF are compile-time constants (launch_step1 picks the instance for
+// handles that run exactly that), so every test of them below folds away: no branch stands around a weight prefetch or a store,
+// and the wait counts the compiler derives are those of the one path there is.  The form also requests the strip's ids ahead of
+// the layer-1 weights (P0) and relies on one trip of the gather loop (ne <= NT).  WTF = -1: the flags are read at run time
+// (A_TRAIN, A_WT below are a.train, a.wt themselves there: those instances compile to what they were without the parameter).
+#ifndef FNN_FIXED_FLAGS
+#define FNN_FIXED_FLAGS 1             // 0 (diagnostic builds): the fixed form reads its flags at run time -- the ids-first order alone
+#endif
+#ifndef FNN_FIXED_IDS_FIRST
+#define FNN_FIXED_IDS_FIRST 1         // 0 (diagnostic builds): the fixed form keeps the generic order of P0 -- the constant flags alone
+#endif
+template <typename T, int D1, int D2, int DX, bool BAG = false, int NW = 4, int WTF = -1>
 __device__ __forceinline__ void mlp_body(const MlpArgs<T>& a, const int blk, unsigned char* smem)
 {
     constexpr int NF1 = 4 * D1, NF2 = 4 * D2, NFX = 4 * DX, NT = 64 * NW;
@@ -1185,12 +1196,15 @@ __device__ __forceinline__ void mlp_body(const MlpArgs<T>& a, const int blk, uns
     const int tid = threadIdx.x, wave = tid >> 6, lane = tid & 63, lr = lane & 15, lq = lane >> 4;
     const int t0 = blk * 16;
     const int F = a.F, K = a.K, B = a.B, ldT = a.ldT;
-    const bool wt = (a.wt & 1) != 0, wtg = (a.wt & 2) != 0;
+    constexpr bool FXF = WTF >= 0 && FNN_FIXED_FLAGS != 0, IDS1 = WTF >= 0 && !BAG && FNN_FIXED_IDS_FIRST != 0;
+#define A_TRAIN (FXF ? 1 : a.train)
+#define A_WT (FXF ? WTF : a.wt)
+    const bool wt = (A_WT & 1) != 0, wtg = (A_WT & 2) != 0;
     // (FM mode only.  Bag mode keeps the 8-byte stores: the SNN step was level with them and 0.3 us slower with the code in place,
     // and the instance for bag rows 256 .. 316 wide, which sits at 256 VGPRs, spilled the packed tiles)
     constexpr bool B16 = std::is_same<T, bf16_t>::value && !BAG;
     bool st16 = false;                                        // bf16, training: the transposed activations leave 16 bytes per lane
-    if constexpr (B16) st16 = (a.wt & 32) != 0 && a.train;
+    if constexpr (B16) st16 = (A_WT & 32) != 0 && A_TRAIN;
 #define ST4(p, x0, x1, x2, x3) do { if (wt) store4_wt(p, x0, x1, x2, x3); else store4(p, x0, x1, x2, x3); } while (0)
     FNN_STAMP_RT(14);
     FNN_STAMP(0);
@@ -1217,6 +1231,22 @@ __device__ __forceinline__ void mlp_body(const MlpArgs<T>& a, const int blk, uns
     float yv[4];                                   // labels of this lane's 4 rows (y is never null)
 #pragma unroll
     for (int r = 0; r < 4; ++r) { const int t = t0 + 4 * lq + r; yv[r] = a.y[t < B ? t : B - 1]; }
+
+    // the fixed form: this thread's ids of the strip (its piece of P0's one trip, below) are requested HERE, ahead of the layer-1
+    // weights -- nothing makes them depend on those, and behind them they returned only after the whole weight stream.  The wait
+    // on them leaves b1 in flight, and the rows are requested as soon as they are back
+    [[maybe_unused]] int64_t id0[4] = {-1, -1, -1, -1};
+    if constexpr (IDS1) {
+        const int pc = (tid >> 5) * 16 + (tid & 15);          // st16 is set: 8-example pieces, two lanes each
+        if (tid < ((8 * F + 15) >> 4) * 32 && pc < 8 * F) {
+            const int f = (pc >> 2) % F, tq = 2 * ((pc >> 2) / F) + ((tid >> 4) & 1);
+#pragma unroll
+            for (int i = 0; i < 4; ++i) {
+                const int t = t0 + 4 * tq + i;
+                id0[i] = a.ids[(size_t)(t < B ? t : B - 1) * F + f];
+            }
+        }
+    }
 
     // bf16 mode: the weight fragments of a whole phase are fetched into registers one phase AHEAD
     // (they do not depend on the activations), so the L2 latency of the weight stream hides under
@@ -1279,7 +1309,7 @@ __device__ __forceinline__ void mlp_body(const MlpArgs<T>& a, const int blk, uns
             sx[r * LX + c] = (T)v; sxf[r * K1p + c] = 0.0f;
         }
         lds_barrier();
-        if (a.train) {
+        if (A_TRAIN) {
             for (int e = tid; e < K1p * 4; e += NT) {
                 const int c = e >> 2, tq = e & 3;
                 ST4(a.xpT + ft_off<T>(c, t0 + 4 * tq, ldT), (float)sx[(4 * tq) * LX + c], (float)sx[(4 * tq + 1) * LX + c],
@@ -1303,7 +1333,7 @@ __device__ __forceinline__ void mlp_body(const MlpArgs<T>& a, const int blk, uns
 #pragma unroll
         for (int i = 0; i < 4; ++i) {
             const int t = t0 + 4 * tq + i;
-            id[i] = a.ids[(size_t)(t < B ? t : B - 1) * F + f];
+            id[i] = IDS1 ? id0[i] : a.ids[(size_t)(t < B ? t : B - 1) * F + f];
         }
         bool bad = false;
         float4 r[4];
@@ -1342,11 +1372,12 @@ __device__ __forceinline__ void mlp_body(const MlpArgs<T>& a, const int blk, uns
                 }
             }
         }
-        if (a.train && !st16) {
+        if (A_TRAIN && !st16) {
 #pragma unroll
             for (int j = 0; j < 4; ++j)
                 ST4(a.xpT + ft_off<T>(c0 + j, t0 + 4 * tq, ldT), v[0][j], v[1][j], v[2][j], v[3][j]);
         }
+        if constexpr (IDS1) break;                              // one trip: ne <= NT (launch_step1)
     }
     for (int e = tid; e < 16 * (K1p - F * SLOT); e += NT) {       // pad columns of the tile
         const int r = e / (K1p - F * SLOT), c = F * SLOT + e % (K1p - F * SLOT);
@@ -1403,7 +1434,7 @@ __device__ __forceinline__ void mlp_body(const MlpArgs<T>& a, const int blk, uns
                 t16_store_run<C1>(t16_dst(a.d1T, H1p, ldT, wt), pk, wave * C1, NF1, t0, ldT, lr, lq);
             }
         }
-        if (a.train && !st16) {
+        if (A_TRAIN && !st16) {
 #pragma unroll
             for (int i = 0; i < C1; ++i)
                 if (wave * C1 + i < NF1) ST4(a.d1T + ft_off<T>((wave * C1 + i) * 16 + lr, t0 + 4 * lq, ldT), d1v[i][0], d1v[i][1], d1v[i][2], d1v[i][3]);
@@ -1417,14 +1448,14 @@ __device__ __forceinline__ void mlp_body(const MlpArgs<T>& a, const int blk, uns
     frag b3[PF ? NKH2 : 1][PF ? C1 : 1];
     WRing<T, C1, PF ? 1 : DR3> r3;
     if constexpr (PF) {
-        if (a.train) {
+        if (A_TRAIN) {
 #pragma unroll
             for (int kk = 0; kk < NKH2; ++kk)
 #pragma unroll
                 for (int i = 0; i < C1; ++i)
                     b3[kk][i] = *reinterpret_cast<const frag*>(ft_frag<T>(a.w2, min(wave * C1 + i, NF1 - 1), kk, NKH2, lane));
         }
-    } else { if (a.train) wring_head<T, NKH2, C1, DR3>(r3, a.w2, wave * C1, lane, NF1 - 1); }
+    } else { if (A_TRAIN) wring_head<T, NKH2, C1, DR3>(r3, a.w2, wave * C1, lane, NF1 - 1); }
     {
         f32x4 acc[C2];
 #pragma unroll
@@ -1459,7 +1490,7 @@ __device__ __forceinline__ void mlp_body(const MlpArgs<T>& a, const int blk, uns
                 t16_store_run<C2>(t16_dst(a.d2T, H2p, ldT, wt), pk, wave * C2, NF2, t0, ldT, lr, lq);
             }
         }
-        if (a.train && !st16) {
+        if (A_TRAIN && !st16) {
 #pragma unroll
             for (int i = 0; i < C2; ++i)
                 if (wave * C2 + i < NF2) ST4(a.d2T + ft_off<T>((wave * C2 + i) * 16 + lr, t0 + 4 * lq, ldT), d2v[i][0], d2v[i][1], d2v[i][2], d2v[i][3]);
@@ -1481,11 +1512,11 @@ __device__ __forceinline__ void mlp_body(const MlpArgs<T>& a, const int blk, uns
         for (int w = 0; w < NW; ++w) zs += sz[16 * w + row];
         zr[r] = zs;
         const float p = sigmoid_fast(zr[r]);
-        d3[r] = (a.train && t < B) ? p - yv[r] : 0.f;
+        d3[r] = (A_TRAIN && t < B) ? p - yv[r] : 0.f;
         if (a.p_out && wave == 0 && lr == 0 && t < B) a.p_out[t] = p;
     }
     FNN_STAMP(5);
-    if (!a.train) return;
+    if (!A_TRAIN) return;
     if (wave == 0 && lr == 0) {          // one lane per 4 rows writes delta3 and the per-example loss
         float ls[4];
 #pragma unroll
@@ -1578,7 +1609,7 @@ __device__ __forceinline__ void mlp_body(const MlpArgs<T>& a, const int blk, uns
         } else wring_product<T, NKH1, CX, DR4>(acc, r4, ap, a.w1, wave * CX, lane, NFX - 1);
         FNN_STAMP(9);
         if constexpr (!BAG && CX % 2 == 0) {
-            if (a.wt & 4) {
+            if (A_WT & 4) {
                 // gx' [example][K1p] f32 in whole 128-byte lines: two fragments (32 columns) at a time through a wave-private LDS
                 // block -- the MFMA layout has a lane on 4 ROWS of one column (sixteen 4-byte stores per lane,
                 // 64-byte pieces per instruction); regrouped, a lane holds 4 columns of one row (four 16-byte stores per lane)
@@ -1627,6 +1658,17 @@ __device__ __forceinline__ void mlp_body(const MlpArgs<T>& a, const int blk, uns
     FNN_STAMP(10);
     FNN_STAMP_RT(15);
 #undef ST4
+#undef A_TRAIN
+#undef A_WT
+}
+// dynamic LDS of a strip workgroup (mlp_body's tiles; host side of every launch of it)
+template <typename T, int C1, int C2, int CX> size_t mlp_lds_bytes(bool bag, int F, int nw = 4) {
+    constexpr int PAD = 16 / (int)sizeof(T);
+    constexpr int LX = 64 * CX + PAD, L1 = 64 * C1 + PAD, L2 = 64 * C2 + PAD, LXM = LX > L1 ? LX : L1;
+    size_t n = (size_t)16 * (LXM + L1 + L2) * sizeof(T) + (size_t)16 * nw * sizeof(float);
+    if (bag) n += (size_t)16 * 64 * CX * sizeof(float) + (size_t)16 * F * sizeof(int);
+    else n += (size_t)nw * 16 * 36 * sizeof(float);           // the waves' blocks for regrouping gx' into whole lines (mlp_body, P4)
+    return n;
 }
 
 template <typename T, int C1, int C2, int CX>

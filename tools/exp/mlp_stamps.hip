@@ -4,17 +4,24 @@
 #include "../../deep-ctr_amd/csrc/fnn_step_kernels.hip.h"
 #include <algorithm>
 #include <cstdio>
+#include <cstdlib>
+#include <cstring>
+#include <string>
 #include <vector>
 #include <random>
 using namespace fnn;
 #define CK(x) do { hipError_t e = (x); if (e != hipSuccess) { printf("ERR %s line %d: %s\n", #x, __LINE__, hipGetErrorString(e)); return 1; } } while (0)
-int main() {
+// usage: mlp_stamps [generic|fixed]   (the strip kernel's instance of the bf16 training step; -> $OUT/step1_phases[_fixed].json,
+// $OUT as the tools/ scripts have it: tool_out unless set)
+int main(int argc, char** argv) {
+    const bool fixed = argc > 1 && !strcmp(argv[1], "fixed");
     const int B = 4096, F = 16, K = 11, H1 = 300, H2 = 100, K1p = 256, H1p = 320, H2p = 128, ldT = 4096;
     const int64_t D = 937670;
     std::mt19937 rng(1);
     std::vector<int32_t> ids(B * F); for (auto& v : ids) v = rng() % D;
     const char* ids_kind = "uniform over the table";
-    if (FILE* f = fopen("gpurun_out/zipf_ids.bin", "rb")) {          // the bench's Zipf(1.1) ids of one batch (tools/step1_phases.sh writes them)
+    const std::string out = getenv("OUT") ? getenv("OUT") : "tool_out";
+    if (FILE* f = fopen((out + "/zipf_ids.bin").c_str(), "rb")) {          // the bench's Zipf(1.1) ids of one batch (tools/step1_phases.sh writes them)
         if (fread(ids.data(), 4, ids.size(), f) == ids.size()) ids_kind = "Zipf(1.1) per field (synth.zipf_ids, the bench's batch 0)";
         fclose(f);
     }
@@ -36,14 +43,20 @@ int main() {
     float* gxp = (float*)dev((size_t)B * K1p * 4); float* p_out = (float*)dev(B * 4); float* loss_t = (float*)dev(B * 4); int* err = (int*)dev(4);
     long long* dbg = (long long*)dev(256 * 16 * 8);
     MlpArgs<bf16_t> a{d_ids, d_y, B, F, K, d_tab, D, -3.f, w1, w1t, w2, w2t, w3p, m, m, 0, 0, H1, H2, 1,
-                      xpT, d1T, d2T, dl1T, dl2T, dl3T, ldT, gxp, p_out, loss_t, err, nullptr, 16, nullptr, nullptr, /*wt*/ 0, dbg};
-    const size_t lds = 16 * (328 + 328 + 136) * 2 + 256;
+                      xpT, d1T, d2T, dl1T, dl2T, dl3T, ldT, gxp, p_out, loss_t, err, nullptr, 16, nullptr, nullptr, /*wt*/ 47, dbg};
+    // the product's launch (launch_step1): eight waves per strip, training, FNN_WT_STORES = 47
+    const size_t lds = mlp_lds_bytes<bf16_t, 5, 2, 4>(false, F, 8);
+    auto launch = [&]() {
+        if (fixed) hipLaunchKernelGGL((k_step1<bf16_t, 5, 2, 4, false, 8, 47>), dim3(256), dim3(512), lds, 0, a);
+        else hipLaunchKernelGGL((k_step1<bf16_t, 5, 2, 4, false, 8>), dim3(256), dim3(512), lds, 0, a);
+    };
     hipEvent_t e0, e1; hipEventCreate(&e0); hipEventCreate(&e1);
-    for (int it = 0; it < 20; ++it) hipLaunchKernelGGL((k_step1<bf16_t, 5, 2, 4, false>), dim3(256), dim3(256), lds, 0, a);
+    for (int it = 0; it < 20; ++it) launch();
     hipEventRecord(e0, 0);
-    for (int it = 0; it < 50; ++it) hipLaunchKernelGGL((k_step1<bf16_t, 5, 2, 4, false>), dim3(256), dim3(256), lds, 0, a);
+    for (int it = 0; it < 50; ++it) launch();
     hipEventRecord(e1, 0); CK(hipEventSynchronize(e1));
-    float ms; hipEventElapsedTime(&ms, e0, e1); printf("k_step1 (mlp only, with stamps) %.2f us/launch\n", ms * 1000 / 50);
+    CK(hipGetLastError());
+    float ms; hipEventElapsedTime(&ms, e0, e1); printf("k_step1 (%s instance, mlp only, with stamps) %.2f us/launch\n", fixed ? "fixed" : "generic", ms * 1000 / 50);
     std::vector<long long> hd(256 * 16); CK(hipMemcpy(hd.data(), dbg, hd.size() * 8, hipMemcpyDeviceToHost));
     const char* names[10] = {"init loads+P0 gather+barrier", "P1 mfma loop", "P1 epilogue+barrier", "P2 mfma loop", "P2 epi+head (2 barriers)",
                              "delta2+barrier", "P3 mfma loop", "P3 epilogue+barrier", "P4 mfma loop", "P4 stores"};
@@ -61,8 +74,8 @@ int main() {
     std::vector<double> tpu; for (int b = 0; b < 256; ++b) { const long long rt = hd[b * 16 + 15] - hd[b * 16 + 14]; if (rt > 0) tpu.push_back((double)(hd[b * 16 + 10] - hd[b * 16]) / ((double)rt / 100.0)); }
     std::sort(tpu.begin(), tpu.end());
     const double ticks_per_us = tpu.empty() ? 2400.0 : tpu[tpu.size() / 2];
-    if (FILE* f = fopen("gpurun_out/step1_phases.json", "w")) {
-        fprintf(f, "{\"kernel\": \"k_step1<bf16, 5, 2, 4> (mlp_body), diagnostic build with s_memtime stamps (tools/exp/mlp_stamps.hip); the product kernel executes no stamp\", ");
+    if (FILE* f = fopen((out + (fixed ? "/step1_phases_fixed.json" : "/step1_phases.json")).c_str(), "w")) {
+        fprintf(f, "{\"kernel\": \"k_step1<bf16, 5, 2, 4, false, 8%s> (mlp_body, 512 threads, train = 1, wt = 47), diagnostic build with s_memtime stamps (tools/exp/mlp_stamps.hip); the product kernel executes no stamp\", ", fixed ? ", 47" : "");
         fprintf(f, "\"batch\": %d, \"workgroups\": 256, \"ids\": \"%s\", \"ticks_per_us\": %.1f, \"launch_us_with_stamps\": %.2f, ", B, ids_kind, ticks_per_us, ms * 1000 / 50);
         fprintf(f, "\"phases_us_median\": {");
         for (int i = 0; i < 10; ++i) {
