@@ -1097,8 +1097,10 @@ template <typename T> struct MlpArgs {
 #endif
 };
 #ifdef FNN_STAMPS
-#define FNN_STAMP(i) do { if (threadIdx.x == 0) a.dbg[(size_t)blk * 16 + (i)] = (long long)__builtin_amdgcn_s_memtime(); } while (0)
-#define FNN_STAMP_RT(i) do { if (threadIdx.x == 0) a.dbg[(size_t)blk * 16 + (i)] = (long long)__builtin_amdgcn_s_memrealtime(); } while (0)   // 100 MHz
+// (FNN_STAMP_SLOTS stamps per workgroup: 0 .. 10 the phases, 14 / 15 the real-time pair, 16 .. 19 the head's finer ones)
+#define FNN_STAMP_SLOTS 24
+#define FNN_STAMP(i) do { if (threadIdx.x == 0) a.dbg[(size_t)blk * FNN_STAMP_SLOTS + (i)] = (long long)__builtin_amdgcn_s_memtime(); } while (0)
+#define FNN_STAMP_RT(i) do { if (threadIdx.x == 0) a.dbg[(size_t)blk * FNN_STAMP_SLOTS + (i)] = (long long)__builtin_amdgcn_s_memrealtime(); } while (0)   // 100 MHz
 #else
 #define FNN_STAMP(i) do { } while (0)
 #define FNN_STAMP_RT(i) do { } while (0)
@@ -1175,6 +1177,22 @@ __device__ __forceinline__ void wring_product(f32x4 (&acc)[C], WRing<T, C, D>& r
 #ifndef FNN_FIXED_IDS_FIRST
 #define FNN_FIXED_IDS_FIRST 1         // 0 (diagnostic builds): the fixed form keeps the generic order of P0 -- the constant flags alone
 #endif
+// The head of the fixed form (z3's row sums, the sigmoids, the loss; between P2's last MFMA and P3's first).  Same expressions,
+// same summation order, same stored layout as the generic form -- each switch only says HOW the same values travel; 0 (diagnostic
+// builds) keeps the generic form's code for that part
+#ifndef FNN_HEAD_DPP
+#define FNN_HEAD_DPP 1                // z3's 16-lane row sums by four DPP steps per row, the four rows side by side, one 16-byte LDS store
+#endif
+#ifndef FNN_HEAD_ONE_TRIP
+#define FNN_HEAD_ONE_TRIP 1           // the waves' partial sums read as NW 16-byte LDS loads issued together, the four sigmoids together
+#endif
+// v + (v of the lane that the DPP control names).  Every control used below names a lane of the same row of 16, all of them
+// active, so neither `old` nor bound_ctrl can reach the result; bound_ctrl is set because with it the compiler needs no register
+// initialised for `old` (off: one v_mov_b32 per DPP move).  hipcc pairs the four rows' adds into v_pk_add_f32 fed by
+// v_mov_b32_dpp instead of folding each move into a v_add_f32 -- the same IEEE sums either way
+template <int CTRL> __device__ __forceinline__ float dpp_add(const float v) {
+    return v + __int_as_float(__builtin_amdgcn_update_dpp(0, __float_as_int(v), CTRL, 0xf, 0xf, true));
+}
 template <typename T, int D1, int D2, int DX, bool BAG = false, int NW = 4, int WTF = -1>
 __device__ __forceinline__ void mlp_body(const MlpArgs<T>& a, const int blk, unsigned char* smem)
 {
@@ -1197,6 +1215,7 @@ __device__ __forceinline__ void mlp_body(const MlpArgs<T>& a, const int blk, uns
     const int t0 = blk * 16;
     const int F = a.F, K = a.K, B = a.B, ldT = a.ldT;
     constexpr bool FXF = WTF >= 0 && FNN_FIXED_FLAGS != 0, IDS1 = WTF >= 0 && !BAG && FNN_FIXED_IDS_FIRST != 0;
+    constexpr bool HDPP = WTF >= 0 && FNN_HEAD_DPP != 0, H1T = WTF >= 0 && FNN_HEAD_ONE_TRIP != 0;
 #define A_TRAIN (FXF ? 1 : a.train)
 #define A_WT (FXF ? WTF : a.wt)
     const bool wt = (A_WT & 1) != 0, wtg = (A_WT & 2) != 0;
@@ -1496,14 +1515,52 @@ __device__ __forceinline__ void mlp_body(const MlpArgs<T>& a, const int blk, uns
                 if (wave * C2 + i < NF2) ST4(a.d2T + ft_off<T>((wave * C2 + i) * 16 + lr, t0 + 4 * lq, ldT), d2v[i][0], d2v[i][1], d2v[i][2], d2v[i][3]);
         }
     }
+    FNN_STAMP(16);
+    if constexpr (HDPP) {
+        // the butterfly over a row of 16 lanes as DPP adds.  After the xor-1 and xor-2 steps the four lanes of a quad hold the same
+        // bits, so the half-mirror partner (lane 7 - l of the half row) holds what the xor-4 partner holds, and after that step
+        // the mirror partner (15 - l) what the xor-8 partner holds: the same sums in the same order, f32 addition commutes.
+        // Step by step over the four rows, so that their chains run side by side; no LDS crossbar trip
+#pragma unroll
+        for (int r = 0; r < 4; ++r) zp[r] = dpp_add<0xB1>(zp[r]);           // quad_perm [1, 0, 3, 2]
+#pragma unroll
+        for (int r = 0; r < 4; ++r) zp[r] = dpp_add<0x4E>(zp[r]);           // quad_perm [2, 3, 0, 1]
+#pragma unroll
+        for (int r = 0; r < 4; ++r) zp[r] = dpp_add<0x141>(zp[r]);          // row_half_mirror
+#pragma unroll
+        for (int r = 0; r < 4; ++r) zp[r] = dpp_add<0x140>(zp[r]);          // row_mirror
+        if (lr == 0) *reinterpret_cast<float4*>(sz + wave * 16 + 4 * lq) = make_float4(zp[0], zp[1], zp[2], zp[3]);
+    } else {
 #pragma unroll
     for (int r = 0; r < 4; ++r) {
         zp[r] += __shfl_xor(zp[r], 1); zp[r] += __shfl_xor(zp[r], 2);
         zp[r] += __shfl_xor(zp[r], 4); zp[r] += __shfl_xor(zp[r], 8);
         if (lr == 0) sz[wave * 16 + 4 * lq + r] = zp[r];
     }
+    }
+    FNN_STAMP(17);
     lds_barrier();
+    FNN_STAMP(18);
     float d3[4], zr[4];
+    if constexpr (H1T) {
+        // a lane's four rows are contiguous in every wave's block of sz: NW 16-byte reads, all requested before the first sum
+        float4 zw[NW];
+#pragma unroll
+        for (int w = 0; w < NW; ++w) zw[w] = *reinterpret_cast<const float4*>(sz + 16 * w + 4 * lq);
+#pragma unroll
+        for (int r = 0; r < 4; ++r) zr[r] = 0.f;
+#pragma unroll
+        for (int w = 0; w < NW; ++w) { zr[0] += zw[w].x; zr[1] += zw[w].y; zr[2] += zw[w].z; zr[3] += zw[w].w; }
+        float p[4];
+#pragma unroll
+        for (int r = 0; r < 4; ++r) p[r] = sigmoid_fast(zr[r]);
+#pragma unroll
+        for (int r = 0; r < 4; ++r) d3[r] = (A_TRAIN && t0 + 4 * lq + r < B) ? p[r] - yv[r] : 0.f;
+        if (a.p_out && wave == 0 && lr == 0) {
+#pragma unroll
+            for (int r = 0; r < 4; ++r) if (t0 + 4 * lq + r < B) a.p_out[t0 + 4 * lq + r] = p[r];
+        }
+    } else {
 #pragma unroll
     for (int r = 0; r < 4; ++r) {
         const int row = 4 * lq + r, t = t0 + row;
@@ -1514,6 +1571,7 @@ __device__ __forceinline__ void mlp_body(const MlpArgs<T>& a, const int blk, uns
         const float p = sigmoid_fast(zr[r]);
         d3[r] = (A_TRAIN && t < B) ? p - yv[r] : 0.f;
         if (a.p_out && wave == 0 && lr == 0 && t < B) a.p_out[t] = p;
+    }
     }
     FNN_STAMP(5);
     if (!A_TRAIN) return;
@@ -1527,6 +1585,7 @@ __device__ __forceinline__ void mlp_body(const MlpArgs<T>& a, const int blk, uns
         store4(a.dl3T + ft_off<T>(0, t0 + 4 * lq, ldT), d3[0], d3[1], d3[2], d3[3]);
         store4(a.loss_t + t0 + 4 * lq, ls[0], ls[1], ls[2], ls[3]);
     }
+    FNN_STAMP(19);
     // delta2 = delta3 * w3 * r2 * (1 - d2^2)   (layer 2 is tanh on the dropout path, :165)
     u32x2 pk2[B16 ? C2 : 1];                                  // st16: the run's packed tiles, stored behind the loop
 #pragma unroll

@@ -2,6 +2,8 @@
 # per-phase s_memtime stamps of the strip kernel (k_step1) on the bench's ids, the generic and the fixed training instance of the
 # bf16 step one after the other -> $OUT/step1_phases.json, $OUT/step1_phases_fixed.json
 # (copy to profiles/rNN_step1_phases.json: bench.py quotes the in-step gather figure from the newest).  Diagnostic build.
+# "head_us_median": the stretch from P2's last MFMA to P3's first in finer intervals.  The fixed instance with the generic
+# form's head: build tools/exp/mlp_stamps.hip with -DFNN_HEAD_DPP=0 -DFNN_HEAD_ONE_TRIP=0 (either alone: that part alone).
 set -e
 export OUT=${OUT:-tool_out}
 mkdir -p $OUT
