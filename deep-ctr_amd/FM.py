@@ -14,6 +14,8 @@ buffer of lines per call, one persistent workgroup walking them in order (fm_tra
 (fm_train_online_multi), each ending bit for bit as its own `train_online` would; `ipinyou.run_many` is its driver.
 `predict_many(models, ids)` / `evaluate_many(models, ids, y)` are the other half of such a search: every model's predictions and
 metrics on one test feed in one call (fm_predict_multi / fm_eval_multi), each bit for bit its own `forward` / `evaluate`.
+`train_step_many(models, ids, y)` is the mini-batch step of such a search: one `train_step` of every model on one batch in one
+call (fm_train_step_multi), the batch's grouping shared; `ipinyou.run_many_batches` is its driver.
 Rows shared between columns (`shared_rows=True`, fm_set_shared_rows): the columns of `ids` are then positions, not fields, as
 python/ipinyou.py:42-65 feeds the reference -- `ipinyou.to_column_ids` makes such ids and `ipinyou.run` is the driver.
 Random init uses NumPy RandomState(seed) streams (TensorFlow's cannot be reproduced here)."""
@@ -265,6 +267,47 @@ def train_online_many(models, ids, y, wts=None, want_p=False, want_loss=True):
         m._keep = (ids_t, y_t, w_t)
     return [{'loss': float(loss[i]) if want_loss else None, 'loss_last': float(last[i]) if want_loss else None, 'p': ps[i]}
             for i in range(M)]
+
+
+def train_step_many(models, ids, y, wts=None, want_p=False, want_loss=True):
+    """fm_train_step_multi: ONE optimiser step of `train_step` for every model of `models` (FM / LR objects; ranks, table sizes,
+    optimisers, lr, lam and shared_rows their own) on the one mini-batch ids [B, X_feas], y [B], in one call: the models that agree
+    in table size and shared_rows share the batch's grouping, and every other stage is one launch for all of them.  Every model
+    ends bit for bit as its own `train_step(ids, y, wts=wts, ...)` would have left it (rows really shared between columns: to
+    rounding, as there).  Returns the list of the {'loss', 'p'} dicts `train_step` returns, in the order of `models`.
+    ValueError for an empty list, models that differ in X_feas or a bad wts shape; FNNError for what the library refuses (a model
+    twice, B above a model's max_batch, ...: nothing is trained then) and for an id outside [-1, X_dim) of some model."""
+    models = list(models)
+    if not models:
+        raise ValueError("train_step_many: no models")
+    first = models[0]
+    if any(m.X_feas != first.X_feas for m in models):
+        raise ValueError("train_step_many: the models differ in X_feas %s: one feed, one width" % ([m.X_feas for m in models],))
+    torch, lib, M = first._torch, first.lib, len(models)
+    ids_t, y_t = first._dev(ids, torch.int32), first._dev(y, torch.float32)
+    if ids_t.dim() != 2 or ids_t.shape[1] != first.X_feas or y_t.shape != (ids_t.shape[0],):
+        raise ValueError("ids %s, y %s: need [B, %d] and [B]" % (tuple(ids_t.shape), tuple(y_t.shape), first.X_feas))
+    w_t = first._wts(wts, ids_t)
+    B = ids_t.shape[0]
+    if B > 4096:                    # one call = ONE optimiser step per model, as in train_step
+        raise FNNError(_capi.FNN_ERR_ARG, "train_step_many: batch %d > 4096 (fm_create's largest step)" % B)
+    ps = [torch.empty(B, dtype=torch.float32, device=first.device) if want_p else None for _ in models]
+    hs = (C.c_void_p * M)(*[m.h.value if m.h else None for m in models])
+    lrs, lams = (C.c_float * M)(*[m.lr for m in models]), (C.c_float * M)(*[m.lam for m in models])
+    means = (C.c_int * M)(*[m.reduce_mean for m in models])
+    p_arr = (C.c_void_p * M)(*[p.data_ptr() if want_p else None for p in ps])
+    loss = (C.c_float * M)()
+    cur = torch.cuda.current_stream(first.device)
+    for m in models:
+        m.stream.wait_stream(cur)
+    rc = lib.fm_train_step_multi(hs, M, ids_t.data_ptr(), None if w_t is None else w_t.data_ptr(), y_t.data_ptr(), B, lrs, lams,
+                                 means, p_arr if want_p else None, loss if want_loss else None)
+    if rc != 0:
+        raise _many_error(first, rc)
+    for m in models:
+        cur.wait_stream(m.stream)
+        m._keep = (ids_t, y_t, w_t)
+    return [{'loss': float(loss[i]) if want_loss else None, 'p': ps[i]} for i in range(M)]
 
 
 def _many_feed(what, models, ids, wts):

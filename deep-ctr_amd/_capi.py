@@ -173,6 +173,7 @@ FM_SIGNATURES = {
     "fm_train_online": (_i, [_vp, _vp, _vp, _vp, _i64, _f, _f, _vp, C.POINTER(C.c_double), C.POINTER(_f)]),
     "fm_train_online_multi": (_i, [_vp, _i, _vp, _vp, _vp, _i64, C.POINTER(_f), C.POINTER(_f), _vp, C.POINTER(C.c_double),
                                    C.POINTER(_f)]),
+    "fm_train_step_multi": (_i, [_vp, _i, _vp, _vp, _vp, _i, C.POINTER(_f), C.POINTER(_f), C.POINTER(_i), _vp, C.POINTER(_f)]),
     "fm_online_form": (C.c_char_p, [_vp]),
     "fm_predict_multi": (_i, [_vp, _i, _vp, _vp, _i64, _vp]),
     "fm_eval_multi": (_i, [_vp, _i, _vp, _vp, _vp, _i64, C.POINTER(C.c_double), C.POINTER(C.c_double), C.POINTER(C.c_double),

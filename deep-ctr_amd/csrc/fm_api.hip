@@ -9,6 +9,8 @@
 // 16 fields, the first being the 16-field kernels); the sort and both sparse-row updates are the FNN step's, sized by F.
 // Several models on one test feed (fm_predict_multi, fm_eval_multi): the same forward bodies, the arguments of each model read from
 // a device array (k_fm_multi, k_fm_wide_multi), and the metric pass of metrics.hip with a model dimension (metrics_multi).
+// Several models, one mini-batch step (fm_train_step_multi): the models that agree in n_rows and the shared-rows mode share the
+// batch's run sort and rank merge, and the step's bodies run once per layout present with the model as a grid dimension (k_fm_step_*).
 #include <hip/hip_runtime.h>
 
 #include <algorithm>
@@ -406,6 +408,123 @@ __global__ __launch_bounds__(256) void k_fm_scatw2_tail(const ScatArgs sa, float
     scatw2_body(sa, (int)blockIdx.x - 1, (int)gridDim.x - 1, s_w);
 }
 
+// One mini-batch step of several models on one feed (fm_train_step_multi): the bodies above, the arguments of model m read from a
+// device array (k_fm_multi's way), the model a grid dimension.  The grouping -- run sort and rank merge -- depends on the ids,
+// n_rows and the shared-rows mode only, so the models that agree in those (a grouping CLASS) share one: every model's update reads
+// the class's rec (and shared-row marks) with its own part / owners / owner_cnt, gx', table and scale.
+//   launch 1  the run sort of a class (k_sortA), as the solo step's
+//   launch 2  k_fm_step_fwd / k_fm_step_fwd_wide, one per layout present: the classes' rank merges (16 F workgroups each, in the
+//             first such launch) beside the forward + gradients of every (model, example tile) of the layout
+//   launch 3  k_fm_step_scat1 / k_fm_step_scatw1: level 1, grid (workgroups of the largest model, models)
+//   launch 4  k_fm_step_scat2_tail / k_fm_step_scatw2_tail: per model the bias / loss tail and 256 level-2 workgroups
+// The narrow rows take the half-chunk level 1 and the wave level 2 whatever FNN_SCAT1_FORM / FNN_SCAT2_FORM say: every form
+// gives the same bits (tests/test_gpu_scat1_half.py, test_gpu_scat2_forms.py).
+struct StepTail { float* b; const float* gb_part; int n; float lr, lambda; const float* loss_t; int Ba; float lscale; float* loss_out; FmBiasOpt bo; };
+struct StepPack { float loss; int flag; };
+struct StepArg {
+    FmArgs a; ScatArgs sa; StepTail t;
+    // a shared-rows model that is not its class's first: the class's marks (sa.tag_shared, sa.stamp) are copied into its own
+    // array under its own stamp (null: nothing to copy) -- what fm_count_shared_rows scans for this handle
+    int* own_marks; int own_stamp;
+    StepPack* pack;            // the call's loss and range flag of this model, for one copy to the host (null: not asked)
+    int nb1;                   // level-1 workgroups of this model
+    int fcls, scls;            // entry j: the j-th model in forward-layout order / in update-form order (indices into the array)
+    SortArgs so;               // entry c: the rank merge of the call's c-th grouping class
+};
+// launch 2.  Workgroups [0, ncls * mblk): class b / mblk's rank merge (mblk = 16 F); then the (model, tile) pairs, a model's tiles
+// neighbours as in the solo step.  A model's tile 0 clears its owner count (sortB_body clears the class's: the first model's).
+__device__ __forceinline__ void step_pick(const StepArg* __restrict__ args, const int ncls, const int mblk, const int first, const int tiles,
+                                          int& m, int& tile)
+{
+    const int lin = (int)blockIdx.x - ncls * mblk;
+    m = args[first + lin / tiles].fcls;
+    tile = lin % tiles;
+    if (tile == 0 && threadIdx.x == 0) *args[m].sa.owner_cnt = 0;
+}
+template <typename KT, int NF, bool WV>
+__global__ __launch_bounds__(256) void k_fm_step_fwd(const StepArg* __restrict__ args, const int ncls, const int mblk, const int first,
+                                                     const int tiles)
+{
+    extern __shared__ __align__(16) unsigned char smem[];
+    __shared__ float s_gb[16];
+    if ((int)blockIdx.x < ncls * mblk) { const SortArgs so = args[(int)blockIdx.x / mblk].so; sortB_body<KT>(so, (int)blockIdx.x % mblk, smem); return; }
+    int m, tile;
+    step_pick(args, ncls, mblk, first, tiles, m, tile);
+    const FmArgs a = args[m].a;
+    fm_body<NF, WV>(a, tile, s_gb);
+}
+template <typename KT, int L, int NC, bool WV>
+__global__ __launch_bounds__(256) void k_fm_step_fwd_wide(const StepArg* __restrict__ args, const int ncls, const int mblk, const int first,
+                                                          const int tiles)
+{
+    extern __shared__ __align__(16) unsigned char smem[];
+    __shared__ float s_gb[256 / L];
+    if ((int)blockIdx.x < ncls * mblk) { const SortArgs so = args[(int)blockIdx.x / mblk].so; sortB_body<KT>(so, (int)blockIdx.x % mblk, smem); return; }
+    int m, tile;
+    step_pick(args, ncls, mblk, first, tiles, m, tile);
+    const FmArgs a = args[m].a;
+    fm_wide_body<L, NC, WV>(a, tile, s_gb);
+}
+// the class's marks into the model's own array: a segment head whose row the rank merge (a launch earlier) marked
+__device__ __forceinline__ void step_copy_marks(const StepArg& g, const ScatArgs& sa, const int blk, const int nblk)
+{
+    if (!g.own_marks) return;
+    const int n = sa.F * sa.N2;
+    for (int i = blk * 256 + (int)threadIdx.x; i < n; i += nblk * 256) {
+        const int4 r = sa.rec[i];
+        if (r.x >= 0 && (i % sa.N2) == r.z && sa.tag_shared[r.x] == sa.stamp) g.own_marks[r.x] = g.own_stamp;
+    }
+}
+// launch 3: grid (nb1 of the largest model, models of the form)
+template <bool SHARED>
+__global__ __launch_bounds__(256) void k_fm_step_scat1(const StepArg* __restrict__ args, const int first)
+{
+    const int m = args[first + blockIdx.y].scls;
+    const int nb1 = args[m].nb1;
+    if ((int)blockIdx.x >= nb1) return;
+    const ScatArgs sa = args[m].sa;
+    if (SHARED) step_copy_marks(args[m], sa, blockIdx.x, nb1);
+    scat1h_form<SHARED>(sa, blockIdx.x);
+}
+__global__ __launch_bounds__(256) void k_fm_step_scatw1(const StepArg* __restrict__ args, const int first)
+{
+    const int m = args[first + blockIdx.y].scls;
+    const int nb1 = args[m].nb1;
+    if ((int)blockIdx.x >= nb1) return;
+    const ScatArgs sa = args[m].sa;
+    step_copy_marks(args[m], sa, blockIdx.x, nb1);
+    scatw1_body(sa, blockIdx.x);
+}
+// launch 4: grid (1 + 256, models of the form).  The tail's workgroup also hands the model's loss and range flag to the call's
+// packed array (the forwards that raise the flag ran two launches earlier) and clears a raised flag, as fm_sync does.
+__device__ __forceinline__ void step_tail(const StepArg& g, float* sl)
+{
+    const StepTail t = g.t;
+    fm_tail_body(t.b, t.gb_part, t.n, t.lr, t.lambda, t.loss_t, t.Ba, t.lscale, t.loss_out, sl, t.bo);
+    if (threadIdx.x == 0 && g.pack) {
+        const int flag = *static_cast<volatile int*>(g.a.err);
+        g.pack->loss = *t.loss_out; g.pack->flag = flag;
+        if (flag) *g.a.err = 0;
+    }
+}
+template <bool SHARED>
+__global__ __launch_bounds__(256) void k_fm_step_scat2_tail(const StepArg* __restrict__ args, const int first)
+{
+    __shared__ float s_l[256];
+    const int m = args[first + blockIdx.y].scls;
+    if (blockIdx.x == 0) { step_tail(args[m], s_l); return; }
+    const ScatArgs sa = args[m].sa;
+    scat2w_form<SHARED>(sa, (int)blockIdx.x - 1, (int)gridDim.x - 1);
+}
+__global__ __launch_bounds__(256) void k_fm_step_scatw2_tail(const StepArg* __restrict__ args, const int first)
+{
+    __shared__ double s_w[1024];
+    const int m = args[first + blockIdx.y].scls;
+    if (blockIdx.x == 0) { step_tail(args[m], reinterpret_cast<float*>(s_w)); return; }
+    const ScatArgs sa = args[m].sa;
+    scatw2_body(sa, (int)blockIdx.x - 1, (int)gridDim.x - 1, s_w);
+}
+
 __global__ void k_fm_rescale(float* table16, size_t n, float s)
 {
     const size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
@@ -490,6 +609,10 @@ struct fm_handle {
     // fm_predict_multi / fm_eval_multi, used when this handle is hs[0]: the same kind of ring for their argument arrays
     void* eval_host = nullptr; void* eval_dev = nullptr; size_t eval_cur = 0;
     hipEvent_t eval_copied = nullptr, eval_join = nullptr;
+    // fm_train_step_multi, used when this handle is hs[0]: the same kind of ring for its argument arrays, and the packed
+    // {loss, range flag} of a call that asks for the losses
+    void* step_host = nullptr; void* step_dev = nullptr; size_t step_cur = 0; void* step_pack = nullptr;
+    hipEvent_t step_copied = nullptr, step_join = nullptr;
 };
 
 #define MHK(h, expr) do { hipError_t e_ = (expr); if (e_ != hipSuccess) { (h)->err = std::string(#expr) + ": " + hipGetErrorString(e_); return FNN_ERR_HIP; } } while (0)
@@ -676,6 +799,41 @@ void launch_scat(fm_handle* h, ScatArgs& sa, int Ba, int B, float lr, float lamb
                        lscale, h->loss_dev, bo);
 }
 
+// fm_train_step_multi: launch 2 of a layout: lay 0 narrow rows, 1 wide at 16 lanes an example, 2 wide at 32; ncls > 0: the classes' rank merges in front
+template <typename KT, int N, bool WV>
+void launch_step_fwd_nw(hipStream_t st, int lay, const StepArg* d, int ncls, int mblk, int first, int nm, int tiles)
+{
+    const dim3 grid((unsigned)(ncls * mblk + nm * tiles));
+    const size_t lds = ncls ? sort_lds_bytes<KT>() : 0;
+    if (lay == 0) hipLaunchKernelGGL((k_fm_step_fwd<KT, N, WV>), grid, dim3(256), lds, st, d, ncls, mblk, first, tiles);
+    else if (lay == 1) hipLaunchKernelGGL((k_fm_step_fwd_wide<KT, 16, N, WV>), grid, dim3(256), lds, st, d, ncls, mblk, first, tiles);
+    else hipLaunchKernelGGL((k_fm_step_fwd_wide<KT, 32, N, WV>), grid, dim3(256), lds, st, d, ncls, mblk, first, tiles);
+}
+template <typename KT>
+void launch_step_fwd(hipStream_t st, int F, bool wv, int lay, const StepArg* d, int ncls, int mblk, int first, int nm, int tiles)
+{
+#define FM_STEP_FWD(N) do { if (wv) launch_step_fwd_nw<KT, N, true>(st, lay, d, ncls, mblk, first, nm, tiles); \
+                            else launch_step_fwd_nw<KT, N, false>(st, lay, d, ncls, mblk, first, nm, tiles); } while (0)
+    switch ((F + 15) / 16) {
+    case 1: FM_STEP_FWD(1); break;
+    case 2: FM_STEP_FWD(2); break;
+    case 3: FM_STEP_FWD(3); break;
+    default: FM_STEP_FWD(4); break;
+    }
+#undef FM_STEP_FWD
+}
+
+// runs `fn` with h's launches going to `st` (fold_scale, fm_next_stamp and launch_opt_pass work on their handle's stream)
+template <typename Fn>
+auto on_stream(fm_handle* h, hipStream_t st, Fn fn)
+{
+    const hipStream_t own = h->st;
+    h->st = st;
+    auto r = fn();
+    h->st = own;
+    return r;
+}
+
 int fm_run(fm_handle* h, const int32_t* ids, const float* wts, const float* y, int B, float lr, float lambda, int reduce_mean, float* p_out,
            bool train)
 {
@@ -779,11 +937,13 @@ int fm_destroy(fm_handle* h)
     hipSetDevice(h->dev);
     if (h->st) hipStreamSynchronize(h->st);
     void* ptrs[] = {h->table16, h->b, h->gxp, h->loss_t, h->gb_part, h->loss_dev, h->err_flag, h->skeys, h->cpow1, h->s0, h->s1,
-                    h->sb, h->G, h->stamp, h->noshare, h->tag_first, h->tag_shared, h->mark_cnt, h->online_out, h->multi_dev, h->eval_dev};
+                    h->sb, h->G, h->stamp, h->noshare, h->tag_first, h->tag_shared, h->mark_cnt, h->online_out, h->multi_dev, h->eval_dev, h->step_dev,
+                    h->step_pack};
     for (void* p : ptrs) if (p) hipFree(p);
     if (h->multi_host) hipHostFree(h->multi_host);
     if (h->eval_host) hipHostFree(h->eval_host);
-    for (hipEvent_t e : {h->multi_copied, h->multi_join, h->eval_copied, h->eval_join}) if (e) hipEventDestroy(e);
+    if (h->step_host) hipHostFree(h->step_host);
+    for (hipEvent_t e : {h->multi_copied, h->multi_join, h->eval_copied, h->eval_join, h->step_copied, h->step_join}) if (e) hipEventDestroy(e);
     row_group_free(h->rg);
     if (h->own_stream && h->st) hipStreamDestroy(h->st);
     delete h;
@@ -1076,6 +1236,223 @@ int fm_train_online_multi(fm_handle* const* hs, int n_models, const int32_t* ids
         if (loss_last_out) loss_last_out[m] = o.loss_last;
     }
     if (!bad.empty()) MFAIL(h0, FNN_ERR_RANGE, "fm_train_online_multi: feature id outside [-1, n_rows) in model(s) " + bad);
+    return FNN_OK;
+}
+
+// One mini-batch step of several models on one feed (the kernels: k_fm_step_*).  Streams and the pinned ring as in
+// fm_train_online_multi: everything on hs[0]'s stream, the argument array of a call in the next free slots of the ring.
+namespace {
+
+constexpr size_t STEP_RING = 4 * FM_STEP_MAX_MODELS;             // StepArgs per ring: four calls of the largest group
+
+int step_ring(fm_handle* h0, size_t n, size_t* slot)
+{
+    if (!h0->step_host) {                                            // first such call with this handle in front
+        if (!h0->step_copied) MHK(h0, hipEventCreateWithFlags(&h0->step_copied, hipEventDisableTiming));
+        if (!h0->step_join) MHK(h0, hipEventCreateWithFlags(&h0->step_join, hipEventDisableTiming));
+        if (!h0->step_dev) MHK(h0, hipMalloc(&h0->step_dev, STEP_RING * sizeof(StepArg)));
+        if (!h0->step_pack) MHK(h0, hipMalloc(&h0->step_pack, FM_STEP_MAX_MODELS * sizeof(StepPack)));
+        MHK(h0, hipHostMalloc(&h0->step_host, STEP_RING * sizeof(StepArg), hipHostMallocDefault));
+    }
+    if (h0->step_cur + n > STEP_RING) {
+        MHK(h0, hipEventSynchronize(h0->step_copied));
+        h0->step_cur = 0;
+    }
+    *slot = h0->step_cur;
+    h0->step_cur += n;
+    return FNN_OK;
+}
+
+}  // namespace
+
+int fm_train_step_multi(fm_handle* const* hs, int n_models, const int32_t* ids, const float* wts, const float* y, int B,
+                        const float* lr, const float* lambda, const int* reduce_mean, float* const* p_out, float* loss_out)
+{
+    fm_handle* h0 = hs && n_models >= 1 && n_models <= FM_STEP_MAX_MODELS ? hs[0] : nullptr;
+    auto refuse = [&](int code, const std::string& msg) { (h0 ? h0->err : g_fm_err) = "fm_train_step_multi: " + msg; return code; };
+    auto at = [](const char* what, int m) { return "model " + std::to_string(m) + ": " + what; };
+    if (!hs || !lr || !lambda) return refuse(FNN_ERR_ARG, "null hs, lr or lambda");
+    if (n_models < 1 || n_models > FM_STEP_MAX_MODELS) return refuse(FNN_ERR_ARG, "n_models must be in [1, 1024]");
+    for (int m = 0; m < n_models; ++m) if (!hs[m]) return refuse(FNN_ERR_ARG, at("null handle", m));
+    {
+        std::vector<const fm_handle*> seen(hs, hs + n_models);
+        std::sort(seen.begin(), seen.end());
+        const auto dup = std::adjacent_find(seen.begin(), seen.end());
+        if (dup != seen.end()) {
+            int m = n_models - 1;
+            while (hs[m] != *dup) --m;                                // the later of the two places
+            return refuse(FNN_ERR_ARG, at("the same handle twice in one call (two updates would race on one table)", m));
+        }
+    }
+    for (int m = 1; m < n_models; ++m)
+        if (hs[m]->F != h0->F || hs[m]->dev != h0->dev) return refuse(FNN_ERR_ARG, at("n_fields or device differs from model 0's", m));
+    if (!ids || !y) return refuse(FNN_ERR_ARG, "null ids or y");
+    if (B < 1) return refuse(FNN_ERR_ARG, "B must be in [1, max_batch]");
+    for (int m = 0; m < n_models; ++m) if (B > hs[m]->Bmax) return refuse(FNN_ERR_ARG, at("B must be in [1, max_batch]", m));
+    for (int m = 0; m < n_models; ++m) {                              // fm_train_step_w's own expressions
+        const fm_handle* h = hs[m];
+        if (h->opt == FM_OPT_SGD && (!(lr[m] * lambda[m] < 1.0f) || lambda[m] < 0.f)) return refuse(FNN_ERR_ARG, at("need 0 <= lr * lambda < 1", m));
+        if (h->opt != FM_OPT_SGD && (!(lambda[m] >= 0.f) || !(lr[m] > 0.f))) return refuse(FNN_ERR_ARG, at("Adam / FTRL need lr > 0 and lambda >= 0", m));
+    }
+    for (int m = 0; m < n_models; ++m) if (!hs[m]->table16) return refuse(FNN_ERR_STATE, at("fm_set_table has not been called", m));
+
+    if (n_models == 1) {       // nothing to share: the solo step itself, without the argument copy (15 us in front of a 27 us step)
+        const int rs = fm_train_step_w(h0, ids, wts, y, B, lr[0], lambda[0], reduce_mean ? reduce_mean[0] : 0, p_out ? p_out[0] : nullptr, loss_out);
+        if (rs == FNN_ERR_RANGE) h0->err = "fm_train_step_multi: feature id outside [-1, n_rows) in model(s) 0";
+        return rs;
+    }
+    MHK(h0, hipSetDevice(h0->dev));
+    const hipStream_t st = h0->st;
+    const int F = h0->F, M = n_models;
+    std::vector<hipStream_t> others;                                  // the streams that are not st, each once
+    for (int m = 1; m < M; ++m) if (hs[m]->st != st) others.push_back(hs[m]->st);
+    std::sort(others.begin(), others.end());
+    others.erase(std::unique(others.begin(), others.end()), others.end());
+    size_t slot = 0;
+    int rc = step_ring(h0, (size_t)M, &slot);                         // also creates the events
+    if (rc != FNN_OK) return rc;
+    for (hipStream_t o : others) {                                    // st after everything enqueued on the others so far
+        MHK(h0, hipEventRecord(h0->step_join, o));
+        MHK(h0, hipStreamWaitEvent(st, h0->step_join, 0));
+    }
+    StepArg* a = static_cast<StepArg*>(h0->step_host) + slot;
+    const StepArg* d = static_cast<const StepArg*>(h0->step_dev) + slot;
+    StepPack* pack = loss_out ? static_cast<StepPack*>(h0->step_pack) : nullptr;
+
+    // grouping classes: equal n_rows and equal shared-rows mode; the class's first model lends rec, skeys and the marks
+    struct Cls { fm_handle* lead; int stamp; };
+    std::vector<Cls> cls;
+    std::vector<int> cls_of(M);
+    for (int m = 0; m < M; ++m) {
+        int c = 0;
+        while (c < (int)cls.size() && (cls[c].lead->n_rows != hs[m]->n_rows || cls[c].lead->shared != hs[m]->shared)) ++c;
+        if (c == (int)cls.size()) cls.push_back(Cls{hs[m], 0});
+        cls_of[m] = c;
+    }
+    // the classes with the first one's key width have their rank merge in launch 2; the others a launch of their own
+    std::vector<int> order;                                           // classes, the riders first
+    for (int c = 0; c < (int)cls.size(); ++c) if (cls[c].lead->key64 == cls[0].lead->key64) order.push_back(c);
+    const int nride = (int)order.size();
+    for (int c = 0; c < (int)cls.size(); ++c) if (cls[c].lead->key64 != cls[0].lead->key64) order.push_back(c);
+    std::vector<SortArgs> sorts(cls.size());
+    for (int i = 0; i < (int)order.size(); ++i) {
+        Cls& k = cls[order[i]];
+        fm_handle* h = k.lead;
+        SortArgs so{ids, B, F, h->n_rows, h->rg.rec, h->rg.owner_cnt, 4 * F, h->skeys};
+        so.merge4 = h->sort_merge4;
+        launch_sort_runs(st, h->key64, so);                           // launch 1
+        so.nblk = 16 * F;
+        if (h->shared) {
+            so.tag_first = h->tag_first; so.tag_shared = h->tag_shared;
+            so.stamp = k.stamp = on_stream(h, st, [&] { return fm_next_stamp(h); });
+        }
+        sorts[i] = so;
+        a[i].so = so;
+    }
+    MHK(h0, hipGetLastError());
+
+    const bool wt = !(getenv("FM_WT") && atoi(getenv("FM_WT")) == 0);
+    auto lay_of = [](const fm_handle* h) { return !h->wide ? 0 : h->rw <= 64 ? 1 : 2; };          // launch_fwd_nw's choice of kernel
+    auto form_of = [](const fm_handle* h) { return h->wide ? 2 : h->shared ? 1 : 0; };              // level 1 / 2: narrow, narrow shared, wide
+    int fcnt[3] = {0, 0, 0}, scnt[3] = {0, 0, 0}, ffirst[3], sfirst[3], fpos[3], spos[3], nb1max[3] = {0, 0, 0};
+    for (int m = 0; m < M; ++m) { ++fcnt[lay_of(hs[m])]; ++scnt[form_of(hs[m])]; }
+    ffirst[0] = sfirst[0] = 0;
+    for (int c = 1; c < 3; ++c) { ffirst[c] = ffirst[c - 1] + fcnt[c - 1]; sfirst[c] = sfirst[c - 1] + scnt[c - 1]; }
+    for (int c = 0; c < 3; ++c) { fpos[c] = ffirst[c]; spos[c] = sfirst[c]; }
+    std::vector<float> lr_step(M);
+    for (int m = 0; m < M; ++m) {                                     // fm_run's arguments of a training step, model by model
+        fm_handle* h = hs[m];
+        const Cls& k = cls[cls_of[m]];
+        const bool opt = h->opt != FM_OPT_SGD;
+        const int rm = reduce_mean ? reduce_mean[m] : 0;
+        lr_step[m] = lr[m];
+        if (opt) {
+            h->t += 1;
+            if (h->opt == FM_OPT_ADAM)                 // TensorFlow's bias-corrected step size lr_t
+                lr_step[m] = (float)((double)lr[m] * std::sqrt(1.0 - std::pow((double)h->beta2, (double)h->t)) /
+                                     (1.0 - std::pow((double)h->beta1, (double)h->t)));
+        }
+        const int ex = h->wide ? wide_epb(h) : 16, Ba = rup(B, ex);
+        a[m].a = FmArgs{ids, y, B, F, h->K, h->table16, h->n_rows, h->b, (float)h->scale, rm ? 1.0f / (float)B : 1.0f, 1,
+                        h->gxp, h->K1p, p_out ? p_out[m] : nullptr, h->loss_t, h->gb_part, h->err_flag, wt,
+                        opt && !h->dense_g ? h->stamp : nullptr, (int)h->t, h->rw, wts};
+        if (!opt) h->scale *= 1.0 - (double)lr[m] * (double)lambda[m];
+        RowGroupBufs rg = h->rg;
+        rg.rec = k.lead->rg.rec;
+        ScatArgs sa = scat_args(rg, SORT_N, F, h->K, h->gxp, h->K1p, h->cpow1, opt ? -1.0 : (double)lr[m] / h->scale,
+                                opt ? h->G : h->table16, h->wide ? h->rw : SLOT);
+        a[m].own_marks = nullptr; a[m].own_stamp = 0;
+        if (h->shared) {
+            sa.tag_shared = k.lead->tag_shared; sa.stamp = k.stamp;
+            if (h != k.lead) { a[m].own_marks = h->tag_shared; a[m].own_stamp = on_stream(h, st, [&] { return fm_next_stamp(h); }); }
+        } else if (h->wide) { sa.tag_shared = h->noshare; sa.stamp = 1; }
+        if (h->wide) {
+            sa.gxf = h->rw;
+            a[m].nb1 = (F * (SORT_N / WCH) * (h->rw / 4) + 255) / 256;
+        } else {
+            a[m].nb1 = scat1_blocks(sa, SCAT1_HALF);
+            sa.form2 = SCAT2_WAVE;
+        }
+        a[m].sa = sa;
+        a[m].t = StepTail{h->b, h->gb_part, Ba / ex, lr[m], lambda[m], h->loss_t, Ba, rm ? 1.0f / (float)B : 1.0f, h->loss_dev,
+                          opt ? FmBiasOpt{h->opt, h->sb, lr_step[m], h->beta1, h->beta2, h->eps} : FmBiasOpt{FM_OPT_SGD, nullptr, 0.f, 0.f, 0.f, 0.f}};
+        a[m].pack = pack ? pack + m : nullptr;
+        a[fpos[lay_of(h)]++].fcls = m;
+        a[spos[form_of(h)]++].scls = m;
+        nb1max[form_of(h)] = std::max(nb1max[form_of(h)], a[m].nb1);
+    }
+    // an error from here on leaves the lambda, and the other streams still get their join: they stay ordered behind what was launched
+    auto enqueue = [&]() -> int {
+        MHK(h0, hipMemcpyAsync(const_cast<StepArg*>(d), a, (size_t)M * sizeof(StepArg), hipMemcpyHostToDevice, st));
+        MHK(h0, hipEventRecord(h0->step_copied, st));
+        for (int i = nride; i < (int)order.size(); ++i) {             // the other key width: the plain rank merge
+            const SortArgs& so = sorts[i];
+            if (cls[order[i]].lead->key64) hipLaunchKernelGGL((k_sortB<unsigned long long>), dim3(so.nblk), dim3(256), sort_lds_bytes<unsigned long long>(), st, so);
+            else hipLaunchKernelGGL((k_sortB<unsigned>), dim3(so.nblk), dim3(256), sort_lds_bytes<unsigned>(), st, so);
+        }
+        int ride = nride;                                             // launch 2: the merges ride in the first layout present
+        for (int c = 0; c < 3; ++c) {
+            if (!fcnt[c]) continue;
+            const int tiles = (B + (c == 2 ? 8 : 16) - 1) / (c == 2 ? 8 : 16);
+            if (cls[0].lead->key64) launch_step_fwd<unsigned long long>(st, F, wts != nullptr, c, d, ride, 16 * F, ffirst[c], fcnt[c], tiles);
+            else launch_step_fwd<unsigned>(st, F, wts != nullptr, c, d, ride, 16 * F, ffirst[c], fcnt[c], tiles);
+            ride = 0;
+        }
+        MHK(h0, hipGetLastError());
+        if (scnt[0]) hipLaunchKernelGGL(k_fm_step_scat1<false>, dim3(nb1max[0], scnt[0]), dim3(256), 0, st, d, sfirst[0]);      // launch 3
+        if (scnt[1]) hipLaunchKernelGGL(k_fm_step_scat1<true>, dim3(nb1max[1], scnt[1]), dim3(256), 0, st, d, sfirst[1]);
+        if (scnt[2]) hipLaunchKernelGGL(k_fm_step_scatw1, dim3(nb1max[2], scnt[2]), dim3(256), 0, st, d, sfirst[2]);
+        if (scnt[0]) hipLaunchKernelGGL(k_fm_step_scat2_tail<false>, dim3(1 + 256, scnt[0]), dim3(256), 0, st, d, sfirst[0]);   // launch 4
+        if (scnt[1]) hipLaunchKernelGGL(k_fm_step_scat2_tail<true>, dim3(1 + 256, scnt[1]), dim3(256), 0, st, d, sfirst[1]);
+        if (scnt[2]) hipLaunchKernelGGL(k_fm_step_scatw2_tail, dim3(1 + 256, scnt[2]), dim3(256), 0, st, d, sfirst[2]);
+        MHK(h0, hipGetLastError());
+        for (int m = 0; m < M; ++m) {                                 // Adam / FTRL: the dense pass; SGD: the fold where it is due
+            fm_handle* h = hs[m];
+            if (h->opt != FM_OPT_SGD) {
+                on_stream(h, st, [&] { launch_opt_pass(h, lambda[m], lr_step[m]); return 0; });
+                MHK(h0, hipGetLastError());
+            } else if (h->scale < 5.96e-8 || h->scale > 1.0) {
+                const int rf = on_stream(h, st, [&] { return fold_scale(h); });
+                if (rf != FNN_OK) { if (h != h0) h0->err = "fm_train_step_multi: " + at(h->err.c_str(), m); return rf; }
+            }
+        }
+        return FNN_OK;
+    };
+    rc = enqueue();
+    if (!others.empty()) {                                            // whatever the other streams get from here on comes after the call
+        MHK(h0, hipEventRecord(h0->step_join, st));
+        for (hipStream_t o : others) MHK(h0, hipStreamWaitEvent(o, h0->step_join, 0));
+    }
+    if (rc != FNN_OK || !loss_out) return rc;
+    std::vector<StepPack> hp(M);
+    MHK(h0, hipMemcpyAsync(hp.data(), pack, (size_t)M * sizeof(StepPack), hipMemcpyDeviceToHost, st));
+    MHK(h0, hipStreamSynchronize(st));
+    std::string bad;
+    for (int m = 0; m < M; ++m) {
+        loss_out[m] = hp[m].loss;
+        if (hp[m].flag) bad += (bad.empty() ? "" : ", ") + std::to_string(m);
+    }
+    if (!bad.empty()) MFAIL(h0, FNN_ERR_RANGE, "fm_train_step_multi: feature id outside [-1, n_rows) in model(s) " + bad);
     return FNN_OK;
 }
 

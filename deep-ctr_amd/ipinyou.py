@@ -303,6 +303,62 @@ def run_many(train_path, test_path, specs, buffer=10000, eval_size=100000, epoch
     return [{'model': m, 'log': h, 'X_dim': X_dim, 'X_feas': X_feas} for m, h in zip(models, history)]
 
 
+def run_many_batches(train_path, test_path, specs, batch_size=4096, buffer=10000, eval_size=100000, epochs=1, log_file=None,
+                     device=0, echo=True):
+    """`run`'s mini-batch schedule for several models in ONE pass over the training file: specs as in run_many, the models built
+    as `run` builds them (its init and seeds, plain SGD, shared_rows=True, batch_size as given).  Every mini-batch of a buffer is
+    one FM.train_step_many call (fm_train_step_multi: the models share the batch's grouping, and each ends as its own
+    `train_step` would have left it), a buffer's tail shorter than batch_size one shorter step as in `run`; every buffer is
+    followed by ONE FM.evaluate_many call on the test lines.  run_many's log format and return value; the logged loss is the
+    last mini-batch's, as in `run`."""
+    from .FM import FM, train_step_many
+    from .LR import LR
+    specs = [tuple(s) for s in specs]
+    if not specs:
+        raise ValueError("run_many_batches: no specs")
+    for algo, rank, lr, lam in specs:
+        if algo not in ('LR', 'FM'):
+            raise ValueError("algo %r: 'LR' or 'FM'" % (algo,))
+    if batch_size < 1 or batch_size > 4096:
+        raise ValueError("batch_size %d: one step takes 1..4096 examples" % batch_size)
+    X_dim, X_feas = _dims(train_path, test_path)
+    max_eval = min(eval_size, 4096)
+    models = []
+    for algo, rank, lr, lam in specs:
+        if algo == 'LR':
+            models.append(LR(batch_size, [X_dim, X_feas], ['uniform', -0.001, 0.001, [0x89AB], None], ['sgd', lr], [lam],
+                             'train', max_eval, device, shared_rows=True))
+        else:
+            models.append(FM(batch_size, [X_dim, X_feas, int(rank)], ['uniform', -0.001, 0.001, [0x3210, 0x7654], None],
+                             ['sgd', lr], [lam], 'train', max_eval, device, shared_rows=True))
+    write_log = _appender(log_file, echo)
+    for i, model in enumerate(models):
+        write_log('%d\t%s' % (i, model.log))
+    history = [[] for _ in models]
+    for it in range(epochs):
+        step = 0
+        with open(train_path) as train_data_set:
+            while True:
+                X_ind, X_val, labels = load_ipinyou_data(train_data_set, buffer, X_dim - 1, X_feas)
+                if X_ind is None:
+                    break
+                ids, wts = to_column_ids(X_ind, X_val)
+                preds, loss = [[] for _ in models], [float('nan')] * len(models)
+                for lo in range(0, len(labels), batch_size):
+                    outs = train_step_many(models, ids[lo:lo + batch_size], labels[lo:lo + batch_size], want_p=True,
+                                           wts=None if wts is None else wts[lo:lo + batch_size])
+                    for i, out in enumerate(outs):
+                        preds[i].append(out['p'].cpu().numpy())
+                        loss[i] = out['loss']
+                step += len(labels)
+                eval_aucs = _eval_aucs(models, _load_eval(test_path, eval_size, X_dim, X_feas))
+                for i in range(len(models)):
+                    rec = (step, exact_auc(labels, np.concatenate(preds[i])), eval_aucs[i], loss[i])
+                    history[i].append(rec)
+                    write_log('%d\t' % i + '%d\t%g\t%g\t%g\t' % rec)
+    return [{'model': m, 'log': h, 'X_dim': X_dim, 'X_feas': X_feas} for m, h in zip(models, history)]
+
+
 def parse_spec(text):
     """'FM:10:1e-3:1e-2' -> ('FM', 10, 1e-3, 1e-2): algo:rank:lr:lambda of run_many."""
     algo, rank, lr, lam = text.split(':')
@@ -312,7 +368,8 @@ def parse_spec(text):
 if __name__ == '__main__':
     # python/ipinyou.py:113-127: the campaign's yzx files under DEEPCTR_DATA_DIR (default ../data, as FNN.py), the log under
     # DEEPCTR_LOG_DIR (default ../log/); `python ipinyou.py [FM|LR] [batch_size | online]`, or
-    # `python ipinyou.py many FM:10:1e-3:1e-2 LR:0:1e-3:1e-3 ...` (algo:rank:lr:lambda, run_many)
+    # `python ipinyou.py many FM:10:1e-3:1e-2 LR:0:1e-3:1e-3 ...` (algo:rank:lr:lambda, run_many), or
+    # `python ipinyou.py many-batch 4096 FM:10:1e-3:1e-2 LR:0:1e-3:1e-3 ...` (run_many_batches: mini-batches of 4096)
     sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
     from deep_ctr_amd import ipinyou as _drv
     cam = 'all'
@@ -327,6 +384,12 @@ if __name__ == '__main__':
         _drv.run_many(os.path.join(data_dir, 'ipinyou-data/%s/train.yzx.txt.shuf' % cam),
                       os.path.join(data_dir, 'ipinyou-data/%s/test.yzx.txt.shuf' % cam), [_drv.parse_spec(a) for a in sys.argv[2:]],
                       epochs=int(os.environ.get('DEEPCTR_EPOCHS', 1)), log_file=os.path.join(log_dir, tag))
+        sys.exit(0)
+    if algo == 'many-batch':
+        _drv.run_many_batches(os.path.join(data_dir, 'ipinyou-data/%s/train.yzx.txt.shuf' % cam),
+                              os.path.join(data_dir, 'ipinyou-data/%s/test.yzx.txt.shuf' % cam),
+                              [_drv.parse_spec(a) for a in sys.argv[3:]], batch_size=int(sys.argv[2]),
+                              epochs=int(os.environ.get('DEEPCTR_EPOCHS', 1)), log_file=os.path.join(log_dir, tag))
         sys.exit(0)
     _drv.run(os.path.join(data_dir, 'ipinyou-data/%s/train.yzx.txt.shuf' % cam),
              os.path.join(data_dir, 'ipinyou-data/%s/test.yzx.txt.shuf' % cam), algo,

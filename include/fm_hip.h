@@ -149,6 +149,40 @@ int fm_train_online(fm_handle* h, const int32_t* ids, const float* wts, const fl
 #define FM_ONLINE_MAX_MODELS 1024
 int fm_train_online_multi(fm_handle* const* hs, int n_models, const int32_t* ids, const float* wts, const float* y, int64_t N,
                           const float* lr, const float* lambda, float* const* p_out, double* loss_sum_out, float* loss_last_out);
+/* fm_train_step_w for several models at once: ONE optimiser step of each of n_models handles on ONE device feed -- the mini-batch
+ * schedule of a learning-rate / L2 / rank search, where every model of the search steps on the same lines.  A solo step is four
+ * dependent launches and latency-bound, and its first two -- the run sort and the rank merge of the batch's (row, t) keys --
+ * depend on the ids only: here the models that agree in n_rows and in the shared-rows mode (a grouping class) share ONE run sort
+ * and ONE rank merge, and every other stage is launched once per row layout present (narrow; wide at 16 lanes an example; wide
+ * at 32; plain and shared-row forms) with the model as a grid dimension.  One class and one layout under SGD: four launches
+ * however many models, plus a fold launch for a model whose lazy scale leaves [2^-24, 1]; Adam / FTRL handles are accepted and
+ * keep their dense pass, one launch per model.  n_models == 1 runs the solo step itself (there is nothing to share, and the copy
+ * of the argument array would stand in front of it).
+ * DEVICE pointers: ids [B, F] int32, wts [B, F] f32 (nullable: every value 1), y [B] f32.  HOST arrays of n_models entries: hs,
+ * lr, lambda, reduce_mean (NULL: 0 for every model), p_out (DEVICE pointers [B]; the array or any entry nullable), loss_out
+ * (nullable; non-null synchronises).
+ * The models may differ in k (1..128, narrow and wide rows mixed), n_rows, optimiser (SGD, Adam, FTRL), the shared-rows mode and
+ * the state they start from; they share n_fields and the device.
+ * The contract: model m ends exactly as fm_train_step_w(hs[m], ids, wts, y, B, lr[m], lambda[m], reduce_mean[m], p_out[m], &loss)
+ * alone would have left it, bit for bit -- the table, b, the lazy SGD scale and the steps at which it folds, the Adam / FTRL
+ * state and step count, p_out[m] and loss_out[m], the range flag, and what fm_count_shared_rows(hs[m]) then answers (the same
+ * bodies run on the same records).  The one exception is the solo step's own: rows that really sit under several columns of the
+ * batch on a shared-rows handle take f32 atomics and are reproducible to rounding only.  Multi steps, solo steps and online
+ * calls may be interleaved on the same handles in any order.
+ * Streams: everything runs on hs[0]'s stream, which first waits (events) for what is queued on every other handle's stream;
+ * every other handle's stream then waits for the call's last launch.
+ * Refused before any launch, nothing written on any model and loss_out untouched, the message (with the index of the offending
+ * model) in fm_last_error(hs[0]), or fm_last_error(NULL) without a usable hs[0] --
+ *   FNN_ERR_ARG: null hs, lr or lambda; a null entry of hs; n_models outside 1..FM_STEP_MAX_MODELS; one handle twice;
+ *   n_fields or device differing from hs[0]'s; null ids or y; B < 1 or B above ANY handle's max_batch; any model's lr / lambda
+ *   outside what fm_train_step_w accepts for its optimiser (SGD: 0 <= lr * lambda < 1; Adam / FTRL: lr > 0, lambda >= 0);
+ *   FNN_ERR_STATE: a handle without a table.
+ * An id outside [-1, n_rows) is judged per model (n_rows may differ): absent for that model and never dereferenced.  A call with
+ * loss_out returns FNN_ERR_RANGE, lists the models' indices and clears their flags (the losses are still written); without
+ * loss_out each handle's fm_sync reports its own flag. */
+#define FM_STEP_MAX_MODELS 1024
+int fm_train_step_multi(fm_handle* const* hs, int n_models, const int32_t* ids, const float* wts, const float* y, int B,
+                        const float* lr, const float* lambda, const int* reduce_mean, float* const* p_out, float* loss_out);
 /* which form the handle runs, as fnn_scat1_form() does for its knob: "plain" (the only one built) */
 const char* fm_online_form(const fm_handle* h);
 
