@@ -576,6 +576,19 @@ __global__ __launch_bounds__(256) void k_fm_opt_pass(float* __restrict__ table16
     *reinterpret_cast<float4*>(s1 + e0) = make_float4(v[0], v[1], v[2], v[3]);
 }
 
+// The argument arrays of the group calls (fm_train_online_multi, fm_train_step_multi, fm_predict_multi / fm_eval_multi) reach the
+// device through a pinned host ring and its device image, both of the handle in front (hs[0]): a launch's array is written into the
+// next free slots of the one and copied to the same slots of the other on hs[0]'s stream.  The copy is asynchronous, so a slot is
+// the copy's to read until the copy has run: slots are handed out in order and never rewritten before the ring wraps, and a wrap
+// first waits for the event recorded after the latest copy (all copies are on one stream, in order, so that covers every one of
+// them).  The ring persists from call to call for the same reason.  (ring_take, ring_send, ring_release below.)
+struct ArgRing {
+    size_t elem, cap;          // bytes per element, elements per ring
+    void* host = nullptr; void* dev = nullptr; size_t cur = 0; hipEvent_t copied = nullptr;
+    template <typename T> T* at_host(size_t slot) const { return static_cast<T*>(host) + slot; }
+    template <typename T> const T* at_dev(size_t slot) const { return static_cast<const T*>(dev) + slot; }
+};
+
 }  // namespace
 
 struct fm_handle {
@@ -602,17 +615,14 @@ struct fm_handle {
     unsigned long long* mark_cnt = nullptr;
     // fm_train_online: the examples one launch may take (FM_ONLINE_CHUNK, read at fm_create) and the call's loss accumulators
     int64_t online_chunk = 65536; fm_online::Out* online_out = nullptr;
-    // fm_train_online_multi, used when this handle is hs[0]: a pinned host ring and its device image for the launches' argument
-    // arrays (slot s of one is copied to slot s of the other on st), and the event recorded after the latest such copy
-    fm_online::Args* multi_host = nullptr; fm_online::Args* multi_dev = nullptr; size_t multi_cur = 0;
-    hipEvent_t multi_copied = nullptr, multi_join = nullptr;
-    // fm_predict_multi / fm_eval_multi, used when this handle is hs[0]: the same kind of ring for their argument arrays
-    void* eval_host = nullptr; void* eval_dev = nullptr; size_t eval_cur = 0;
-    hipEvent_t eval_copied = nullptr, eval_join = nullptr;
-    // fm_train_step_multi, used when this handle is hs[0]: the same kind of ring for its argument arrays, and the packed
-    // {loss, range flag} of a call that asks for the losses
-    void* step_host = nullptr; void* step_dev = nullptr; size_t step_cur = 0; void* step_pack = nullptr;
-    hipEvent_t step_copied = nullptr, step_join = nullptr;
+    // The group calls, used when this handle is hs[0]: the argument rings of fm_train_online_multi (eight launches of the largest
+    // group, 1 MiB), fm_train_step_multi and fm_predict_multi / fm_eval_multi (four calls of the largest group each); the event
+    // that joins the other members' streams to this one's and back (GroupCall); the packed {loss, range flag} of an
+    // fm_train_step_multi call that asks for the losses
+    ArgRing online_ring{sizeof(fm_online::Args), 8 * FM_ONLINE_MAX_MODELS};
+    ArgRing step_ring{sizeof(StepArg), 4 * FM_STEP_MAX_MODELS};
+    ArgRing eval_ring{sizeof(EvalArg), 4 * FM_EVAL_MAX_MODELS};
+    hipEvent_t join = nullptr; StepPack* step_pack = nullptr;
 };
 
 #define MHK(h, expr) do { hipError_t e_ = (expr); if (e_ != hipSuccess) { (h)->err = std::string(#expr) + ": " + hipGetErrorString(e_); return FNN_ERR_HIP; } } while (0)
@@ -736,68 +746,9 @@ void launch_multi_n(bool wv, hipStream_t st, int cls, dim3 grid, const EvalArg* 
 // The wide path's forward: 256 / L examples per workgroup (L = 16 while rank <= 63, else 32).
 int wide_epb(const fm_handle* h) { return h->rw <= 64 ? 16 : 8; }
 
-// The wide step (k >= 17): the same sort, forward + gradients beside the rank merge (k_fm_wide_merge_fwd), then the bag table's
-// wide sparse-row update -- level 1, level 2 beside the bias / loss tail -- into the rows (SGD) or the gradient store G.
-int fm_run_wide(fm_handle* h, FmArgs a, int B, float lr, float lambda, int reduce_mean, bool opt, float lr_step)
-{
-    const int F = h->F, ex = wide_epb(h), Ba = rup(B, ex);
-    if (!a.train) {
-        launch_fwd<unsigned>(h, nullptr, a, Ba / ex);
-        MHK(h, hipGetLastError());
-        return FNN_OK;
-    }
-    SortArgs so{a.ids, B, F, h->n_rows, h->rg.rec, h->rg.owner_cnt, 4 * F, h->skeys};
-    so.merge4 = h->sort_merge4;
-    SortArgs sb = so; sb.nblk = 16 * F;
-    set_claim(h, sb);
-    launch_sort_runs(h->st, h->key64, so);
-    if (h->key64) launch_fwd<unsigned long long>(h, &sb, a, Ba / ex);
-    else launch_fwd<unsigned>(h, &sb, a, Ba / ex);
-    // SGD: the dense decay is the lazy scale, touched rows -= lr * g / scale; Adam / FTRL: G[row] = G[row] - (-1) * sum
-    if (!opt) h->scale *= 1.0 - (double)lr * (double)lambda;
-    ScatArgs sa = scat_args(h->rg, SORT_N, F, h->K, h->gxp, h->K1p, h->cpow1, opt ? -1.0 : (double)lr / h->scale, opt ? h->G : h->table16, h->rw);
-    sa.tag_shared = h->shared ? h->tag_shared : h->noshare; sa.stamp = h->shared ? sb.stamp : 1; sa.gxf = h->rw;
-    const int nthr = F * (SORT_N / WCH) * (h->rw / 4);
-    hipLaunchKernelGGL(k_fm_scatw1, dim3((nthr + 255) / 256), dim3(256), 0, h->st, sa);
-    hipLaunchKernelGGL(k_fm_scatw2_tail, dim3(1 + 256), dim3(256), 0, h->st, sa, h->b, h->gb_part, Ba / ex, lr, lambda, h->loss_t, Ba,
-                       reduce_mean ? 1.0f / (float)B : 1.0f, h->loss_dev,
-                       opt ? FmBiasOpt{h->opt, h->sb, lr_step, h->beta1, h->beta2, h->eps} : FmBiasOpt{FM_OPT_SGD, nullptr, 0.f, 0.f, 0.f, 0.f});
-    MHK(h, hipGetLastError());
-    return FNN_OK;
-}
-
-void launch_opt_pass(fm_handle* h, float lambda, float lr_step)
-{
-    const size_t nk = (size_t)h->n_rows * h->K;
-    const dim3 grid((unsigned)(((nk + 3) / 4 + 255) / 256));
-    if (h->dense_g)
-        hipLaunchKernelGGL(k_fm_opt_pass<true>, grid, dim3(256), 0, h->st, h->table16, h->G, h->stamp, (int)h->t, h->s0, h->s1, nk, h->K,
-                           h->rw, lambda, h->opt, lr_step, h->beta1, h->beta2, h->eps);
-    else
-        hipLaunchKernelGGL(k_fm_opt_pass<false>, grid, dim3(256), 0, h->st, h->table16, h->G, h->stamp, (int)h->t, h->s0, h->s1, nk, h->K,
-                           h->rw, lambda, h->opt, lr_step, h->beta1, h->beta2, h->eps);
-}
-
-// Both levels of the narrow-row update (k <= 16): level 1, then level 2 beside the bias / loss tail.  Under fm_set_shared_rows the
-// SHARED forms with the marks of this step's rank merge (h->step_stamp); otherwise the forms the handle chose.
-void launch_scat(fm_handle* h, ScatArgs& sa, int Ba, int B, float lr, float lambda, int reduce_mean, const FmBiasOpt bo)
-{
-    const float lscale = reduce_mean ? 1.0f / (float)B : 1.0f;
-    if (h->shared) {
-        sa.tag_shared = h->tag_shared; sa.stamp = h->step_stamp;
-        const int nsc1 = scat1_blocks(sa, SCAT1_HALF);
-        sa.form2 = SCAT2_WAVE;
-        hipLaunchKernelGGL(k_fm_scat1s, dim3(nsc1), dim3(256), 0, h->st, sa);
-        hipLaunchKernelGGL(k_fm_scat2s_tail, dim3(1 + 256), dim3(256), 0, h->st, sa, h->b, h->gb_part, Ba / 16, lr, lambda, h->loss_t, Ba,
-                           lscale, h->loss_dev, bo);
-        return;
-    }
-    const int nsc1 = scat1_blocks(sa, h->scat_form);      // also chooses sa.form
-    sa.form2 = h->scat2_form;
-    hipLaunchKernelGGL(k_scat1, dim3(nsc1), dim3(256), 0, h->st, sa);
-    hipLaunchKernelGGL(k_fm_scat2_tail, dim3(1 + 256), dim3(256), 0, h->st, sa, h->b, h->gb_part, Ba / 16, lr, lambda, h->loss_t, Ba,
-                       lscale, h->loss_dev, bo);
-}
+// Adam's / FTRL's pass over the table (k_fm_opt_pass).  Defined below fm_step: the kernel templates are instantiated in the order
+// of their first use, and that order is the order of the functions in the device code.
+void launch_opt_pass(fm_handle* h, float lambda, float lr_step);
 
 // fm_train_step_multi: launch 2 of a layout: lay 0 narrow rows, 1 wide at 16 lanes an example, 2 wide at 32; ncls > 0: the classes' rank merges in front
 template <typename KT, int N, bool WV>
@@ -834,57 +785,205 @@ auto on_stream(fm_handle* h, hipStream_t st, Fn fn)
     return r;
 }
 
-int fm_run(fm_handle* h, const int32_t* ids, const float* wts, const float* y, int B, float lr, float lambda, int reduce_mean, float* p_out,
-           bool train)
+bool fm_wt_env() { return !(getenv("FM_WT") && atoi(getenv("FM_WT")) == 0); }     // gx' written through unless FM_WT=0
+
+// The forward's arguments of a prediction (fm_predict_w, fm_eval_w; B = N: a member of fm_predict_multi / fm_eval_multi)
+FmArgs predict_args(const fm_handle* h, const int32_t* ids, const float* wts, int B, float* p_out, bool wt)
 {
-    const int Ba = rup(B, 16), F = h->F;
-    const bool opt = train && h->opt != FM_OPT_SGD;
-    float lr_step = lr;
+    return FmArgs{ids, nullptr, B, h->F, h->K, h->table16, h->n_rows, h->b, (float)h->scale, 1.0f, 0, h->gxp, h->K1p, p_out,
+                  h->loss_t, h->gb_part, h->err_flag, wt, nullptr, (int)h->t, h->rw, wts};
+}
+
+int fm_forward(fm_handle* h, const int32_t* ids, const float* wts, int B, float* p_out)
+{
+    const int ex = h->wide ? wide_epb(h) : 16;
+    launch_fwd<unsigned>(h, nullptr, predict_args(h, ids, wts, B, p_out, fm_wt_env()), rup(B, ex) / ex);
+    MHK(h, hipGetLastError());
+    return FNN_OK;
+}
+
+// One optimiser step of one handle, as arguments: the forward + gradients (a; p.t.n workgroups of examples), both levels of the
+// sparse-row update (sa; nb1 workgroups at level 1) and the bias / loss tail (t); lr_step: Adam's bias-corrected step size, else
+// lr.  The solo step (fm_step) launches its kernels with these; fm_train_step_multi stores them in the model's StepArg.
+//   lead, stamp  the handle whose grouping (rec, shared-row marks) the update reads, and that grouping's stamp: h itself and the
+//                stamp it just claimed in a solo step, the grouping class's first model in a group
+//   form1, form2 levels 1 / 2 of the narrow rows: the handle's own choice in a solo step without shared rows, else SCAT1_HALF /
+//                SCAT2_WAVE (shared rows have no other form; every form gives the same bits)
+// The step's changes to the handle happen here, in this order: the step count (Adam / FTRL), a.scale, then SGD's dense L2
+// decay as the lazy scale, then the update's lr / scale: touched rows get stored -= lr * g / scale.  Adam / FTRL: the same
+// sorted sums land in the zeroed gradient store, G[row] = G[row] - (-1) * sum.
+struct StepPlan { FmArgs a; ScatArgs sa; StepTail t; int nb1; float lr_step; };
+StepPlan plan_step(fm_handle* h, const int32_t* ids, const float* wts, const float* y, int B, float lr, float lambda, int reduce_mean,
+                   float* p_out, bool wt, const fm_handle* lead, int stamp, int form1, int form2)
+{
+    StepPlan p;
+    const int F = h->F, ex = h->wide ? wide_epb(h) : 16, Ba = rup(B, ex);
+    const bool opt = h->opt != FM_OPT_SGD;
+    const float dscale = reduce_mean ? 1.0f / (float)B : 1.0f;
+    p.lr_step = lr;
     if (opt) {
         h->t += 1;
         if (h->opt == FM_OPT_ADAM)                 // TensorFlow's bias-corrected step size lr_t
-            lr_step = (float)((double)lr * std::sqrt(1.0 - std::pow((double)h->beta2, (double)h->t)) /
-                              (1.0 - std::pow((double)h->beta1, (double)h->t)));
+            p.lr_step = (float)((double)lr * std::sqrt(1.0 - std::pow((double)h->beta2, (double)h->t)) /
+                                (1.0 - std::pow((double)h->beta1, (double)h->t)));
     }
-    FmArgs a{ids, y, B, F, h->K, h->table16, h->n_rows, h->b, (float)h->scale, reduce_mean ? 1.0f / (float)B : 1.0f, train ? 1 : 0,
-             h->gxp, h->K1p, p_out, h->loss_t, h->gb_part, h->err_flag, !(getenv("FM_WT") && atoi(getenv("FM_WT")) == 0),
-             opt && !h->dense_g ? h->stamp : nullptr, (int)h->t, h->rw, wts};
+    p.a = FmArgs{ids, y, B, F, h->K, h->table16, h->n_rows, h->b, (float)h->scale, dscale, 1, h->gxp, h->K1p, p_out, h->loss_t,
+                 h->gb_part, h->err_flag, wt, opt && !h->dense_g ? h->stamp : nullptr, (int)h->t, h->rw, wts};
+    if (!opt) h->scale *= 1.0 - (double)lr * (double)lambda;
+    RowGroupBufs rg = h->rg;
+    rg.rec = lead->rg.rec;
+    p.sa = scat_args(rg, SORT_N, F, h->K, h->gxp, h->K1p, h->cpow1, opt ? -1.0 : (double)lr / h->scale, opt ? h->G : h->table16, h->rw);
+    if (h->shared) { p.sa.tag_shared = lead->tag_shared; p.sa.stamp = stamp; }
+    else if (h->wide) { p.sa.tag_shared = h->noshare; p.sa.stamp = 1; }
     if (h->wide) {
-        const int rc = fm_run_wide(h, a, B, lr, lambda, reduce_mean, opt, lr_step);
-        if (rc != FNN_OK) return rc;
-        if (opt) { launch_opt_pass(h, lambda, lr_step); MHK(h, hipGetLastError()); return FNN_OK; }
-        if (train && (h->scale < 5.96e-8 || h->scale > 1.0)) return fold_scale(h);
-        return FNN_OK;
+        p.sa.gxf = h->rw;
+        p.nb1 = (F * (SORT_N / WCH) * (h->rw / 4) + 255) / 256;
+    } else {
+        p.nb1 = scat1_blocks(p.sa, form1);         // also chooses sa.form
+        p.sa.form2 = form2;
     }
-    if (!train) {
-        launch_fwd<unsigned>(h, nullptr, a, Ba / 16);
-        MHK(h, hipGetLastError());
-        return FNN_OK;
-    }
-    {
-        SortArgs so{ids, B, F, h->n_rows, h->rg.rec, h->rg.owner_cnt, 4 * F, h->skeys};
-        so.merge4 = h->sort_merge4;
-        SortArgs sb = so; sb.nblk = 16 * F;
-        set_claim(h, sb);
-        launch_sort_runs(h->st, h->key64, so);
-        if (h->key64) launch_fwd<unsigned long long>(h, &sb, a, Ba / 16);
-        else launch_fwd<unsigned>(h, &sb, a, Ba / 16);
-    }
-    if (opt) {   // Adam / FTRL: the same sorted sums land in the zeroed gradient store: G[row] = 0 * 1 - (-1) * sum
-        ScatArgs sa = scat_args(h->rg, SORT_N, F, h->K, h->gxp, h->K1p, h->cpow1, -1.0, h->G, SLOT);
-        launch_scat(h, sa, Ba, B, lr, lambda, reduce_mean, FmBiasOpt{h->opt, h->sb, lr_step, h->beta1, h->beta2, h->eps});
-        launch_opt_pass(h, lambda, lr_step);
-        MHK(h, hipGetLastError());
-        return FNN_OK;
-    }
-    // dense L2 decay of the whole table = one scalar; touched rows: stored -= lr * g / scale
-    h->scale *= 1.0 - (double)lr * (double)lambda;
-    ScatArgs sa = scat_args(h->rg, SORT_N, F, h->K, h->gxp, h->K1p, h->cpow1, (double)lr / h->scale, h->table16, SLOT);
-    launch_scat(h, sa, Ba, B, lr, lambda, reduce_mean, FmBiasOpt{FM_OPT_SGD, nullptr, 0.f, 0.f, 0.f, 0.f});
+    p.t = StepTail{h->b, h->gb_part, Ba / ex, lr, lambda, h->loss_t, Ba, dscale, h->loss_dev,
+                   opt ? FmBiasOpt{h->opt, h->sb, p.lr_step, h->beta1, h->beta2, h->eps} : FmBiasOpt{FM_OPT_SGD, nullptr, 0.f, 0.f, 0.f, 0.f}};
+    return p;
+}
+
+// The solo step, narrow and wide rows: the run sort; the forward + gradients beside the rank merge; level 1 of the sparse-row
+// update; level 2 beside the bias / loss tail; then Adam's / FTRL's pass over the table, or the fold of SGD's lazy scale where due.
+int fm_step(fm_handle* h, const int32_t* ids, const float* wts, const float* y, int B, float lr, float lambda, int reduce_mean, float* p_out)
+{
+    const int F = h->F;
+    SortArgs so{ids, B, F, h->n_rows, h->rg.rec, h->rg.owner_cnt, 4 * F, h->skeys};
+    so.merge4 = h->sort_merge4;
+    SortArgs sb = so; sb.nblk = 16 * F;
+    set_claim(h, sb);
+    const bool own_forms = !h->wide && !h->shared;
+    const StepPlan p = plan_step(h, ids, wts, y, B, lr, lambda, reduce_mean, p_out, fm_wt_env(), h, sb.stamp,
+                                 own_forms ? h->scat_form : SCAT1_HALF, own_forms ? h->scat2_form : SCAT2_WAVE);
+    const StepTail& t = p.t;
+    launch_sort_runs(h->st, h->key64, so);
+    if (h->key64) launch_fwd<unsigned long long>(h, &sb, p.a, t.n);
+    else launch_fwd<unsigned>(h, &sb, p.a, t.n);
+#define FM_SCAT(k1, k2_tail) do { \
+        hipLaunchKernelGGL(k1, dim3(p.nb1), dim3(256), 0, h->st, p.sa); \
+        hipLaunchKernelGGL(k2_tail, dim3(1 + 256), dim3(256), 0, h->st, p.sa, t.b, t.gb_part, t.n, t.lr, t.lambda, t.loss_t, t.Ba, t.lscale, \
+                           t.loss_out, t.bo); } while (0)
+    if (h->wide) FM_SCAT(k_fm_scatw1, k_fm_scatw2_tail);
+    else if (h->shared) FM_SCAT(k_fm_scat1s, k_fm_scat2s_tail);          // the SHARED forms, with the marks of this step's rank merge
+    else FM_SCAT(k_scat1, k_fm_scat2_tail);
+#undef FM_SCAT
     MHK(h, hipGetLastError());
+    if (h->opt != FM_OPT_SGD) { launch_opt_pass(h, lambda, p.lr_step); MHK(h, hipGetLastError()); return FNN_OK; }
     if (h->scale < 5.96e-8 || h->scale > 1.0) return fold_scale(h);
     return FNN_OK;
 }
+
+void launch_opt_pass(fm_handle* h, float lambda, float lr_step)
+{
+    const size_t nk = (size_t)h->n_rows * h->K;
+    const dim3 grid((unsigned)(((nk + 3) / 4 + 255) / 256));
+    if (h->dense_g)
+        hipLaunchKernelGGL(k_fm_opt_pass<true>, grid, dim3(256), 0, h->st, h->table16, h->G, h->stamp, (int)h->t, h->s0, h->s1, nk, h->K,
+                           h->rw, lambda, h->opt, lr_step, h->beta1, h->beta2, h->eps);
+    else
+        hipLaunchKernelGGL(k_fm_opt_pass<false>, grid, dim3(256), 0, h->st, h->table16, h->G, h->stamp, (int)h->t, h->s0, h->s1, nk, h->K,
+                           h->rw, lambda, h->opt, lr_step, h->beta1, h->beta2, h->eps);
+}
+
+// ArgRing: n elements of the ring, *slot the first of them.  Allocates on first use, every piece guarded, so that a call that
+// failed half way can be made again; a wrap waits for the latest copy.
+int ring_take(fm_handle* h0, ArgRing& r, size_t n, size_t* slot)
+{
+    if (!r.copied) MHK(h0, hipEventCreateWithFlags(&r.copied, hipEventDisableTiming));
+    if (!r.dev) MHK(h0, hipMalloc(&r.dev, r.cap * r.elem));
+    if (!r.host) MHK(h0, hipHostMalloc(&r.host, r.cap * r.elem, hipHostMallocDefault));
+    if (r.cur + n > r.cap) {
+        MHK(h0, hipEventSynchronize(r.copied));
+        r.cur = 0;
+    }
+    *slot = r.cur;
+    r.cur += n;
+    return FNN_OK;
+}
+// the n elements written at `slot` of the host ring, to the device image on h0's stream
+int ring_send(fm_handle* h0, ArgRing& r, size_t slot, size_t n)
+{
+    MHK(h0, hipMemcpyAsync(static_cast<char*>(r.dev) + slot * r.elem, static_cast<const char*>(r.host) + slot * r.elem, n * r.elem,
+                           hipMemcpyHostToDevice, h0->st));
+    MHK(h0, hipEventRecord(r.copied, h0->st));
+    return FNN_OK;
+}
+void ring_release(ArgRing& r)
+{
+    if (r.dev) hipFree(r.dev);
+    if (r.host) hipHostFree(r.host);
+    if (r.copied) hipEventDestroy(r.copied);
+    r.dev = r.host = nullptr; r.copied = nullptr; r.cur = 0;
+}
+
+// A call on a list of handles: what every such call refuses before any launch, and the streams.  A refusal's message goes to
+// hs[0], or to the library without a usable hs[0].  Everything a group call launches runs on hs[0]'s stream: enter() has that
+// stream wait for what the other members' streams hold so far, leave() -- at the latest the end of the scope, so on every error
+// path too -- has those streams wait for it, so that they stay ordered behind what was launched.  fold_scale(), fm_next_stamp()
+// and launch_opt_pass() work on their handle's stream: on_stream() gives them hs[0]'s.
+struct GroupCall {
+    const char* fn; fm_handle* const* hs; int n, max; fm_handle* h0;
+    std::vector<hipStream_t> others;               // the streams that are not hs[0]'s, each once
+    bool entered = false;
+    GroupCall(const char* fn_, fm_handle* const* hs_, int n_, int max_)
+        : fn(fn_), hs(hs_), n(n_), max(max_), h0(hs_ && n_ >= 1 && n_ <= max_ ? hs_[0] : nullptr) {}
+    ~GroupCall() { leave(); }
+    int refuse(int code, const std::string& msg) const { (h0 ? h0->err : g_fm_err) = std::string(fn) + ": " + msg; return code; }
+    static std::string at(const std::string& what, int m) { return "model " + std::to_string(m) + ": " + what; }
+    int member_failed(int code, const fm_handle* h, int m) const { if (h != h0) refuse(code, at(h->err, m)); return code; }
+    // the list itself; twice: why the same handle twice is refused (null: it is not -- reading is not a race)
+    int check_handles(const char* twice) const
+    {
+        if (!hs) return refuse(FNN_ERR_ARG, "null hs");
+        if (n < 1 || n > max) return refuse(FNN_ERR_ARG, "n_models must be in [1, " + std::to_string(max) + "]");
+        for (int m = 0; m < n; ++m) if (!hs[m]) return refuse(FNN_ERR_ARG, at("null handle", m));
+        if (twice) {
+            std::vector<const fm_handle*> seen(hs, hs + n);
+            std::sort(seen.begin(), seen.end());
+            const auto dup = std::adjacent_find(seen.begin(), seen.end());
+            if (dup != seen.end()) {
+                int m = n - 1;
+                while (hs[m] != *dup) --m;                            // the later of the two places
+                return refuse(FNN_ERR_ARG, at(std::string("the same handle twice in one call (") + twice + ")", m));
+            }
+        }
+        for (int m = 1; m < n; ++m)
+            if (hs[m]->F != h0->F || hs[m]->dev != h0->dev) return refuse(FNN_ERR_ARG, at("n_fields or device differs from model 0's", m));
+        return FNN_OK;
+    }
+    int check_tables() const
+    {
+        for (int m = 0; m < n; ++m) if (!hs[m]->table16) return refuse(FNN_ERR_STATE, at("fm_set_table has not been called", m));
+        return FNN_OK;
+    }
+    int enter()
+    {
+        MHK(h0, hipSetDevice(h0->dev));
+        for (int m = 1; m < n; ++m) if (hs[m]->st != h0->st) others.push_back(hs[m]->st);
+        std::sort(others.begin(), others.end());
+        others.erase(std::unique(others.begin(), others.end()), others.end());
+        if (!others.empty() && !h0->join) MHK(h0, hipEventCreateWithFlags(&h0->join, hipEventDisableTiming));
+        entered = true;
+        for (hipStream_t o : others) {                                // hs[0]'s stream after everything enqueued on the others so far
+            MHK(h0, hipEventRecord(h0->join, o));
+            MHK(h0, hipStreamWaitEvent(h0->st, h0->join, 0));
+        }
+        return FNN_OK;
+    }
+    int leave()
+    {
+        if (!entered) return FNN_OK;
+        entered = false;
+        if (others.empty()) return FNN_OK;                            // whatever the other streams get from here on comes after the call
+        MHK(h0, hipEventRecord(h0->join, h0->st));
+        for (hipStream_t o : others) MHK(h0, hipStreamWaitEvent(o, h0->join, 0));
+        return FNN_OK;
+    }
+};
 
 }  // namespace
 
@@ -937,13 +1036,10 @@ int fm_destroy(fm_handle* h)
     hipSetDevice(h->dev);
     if (h->st) hipStreamSynchronize(h->st);
     void* ptrs[] = {h->table16, h->b, h->gxp, h->loss_t, h->gb_part, h->loss_dev, h->err_flag, h->skeys, h->cpow1, h->s0, h->s1,
-                    h->sb, h->G, h->stamp, h->noshare, h->tag_first, h->tag_shared, h->mark_cnt, h->online_out, h->multi_dev, h->eval_dev, h->step_dev,
-                    h->step_pack};
+                    h->sb, h->G, h->stamp, h->noshare, h->tag_first, h->tag_shared, h->mark_cnt, h->online_out, h->step_pack};
     for (void* p : ptrs) if (p) hipFree(p);
-    if (h->multi_host) hipHostFree(h->multi_host);
-    if (h->eval_host) hipHostFree(h->eval_host);
-    if (h->step_host) hipHostFree(h->step_host);
-    for (hipEvent_t e : {h->multi_copied, h->multi_join, h->eval_copied, h->eval_join, h->step_copied, h->step_join}) if (e) hipEventDestroy(e);
+    for (ArgRing* r : {&h->online_ring, &h->step_ring, &h->eval_ring}) ring_release(*r);
+    if (h->join) hipEventDestroy(h->join);
     row_group_free(h->rg);
     if (h->own_stream && h->st) hipStreamDestroy(h->st);
     delete h;
@@ -1042,7 +1138,7 @@ int fm_train_step_w(fm_handle* h, const int32_t* ids, const float* wts, const fl
     if (h->opt == FM_OPT_SGD && (!(lr * lambda < 1.0f) || lambda < 0.f)) MFAIL(h, FNN_ERR_ARG, "need 0 <= lr * lambda < 1");
     if (h->opt != FM_OPT_SGD && (!(lambda >= 0.f) || !(lr > 0.f))) MFAIL(h, FNN_ERR_ARG, "Adam / FTRL need lr > 0 and lambda >= 0");
     MHK(h, hipSetDevice(h->dev));
-    int rc = fm_run(h, ids, wts, y, B, lr, lambda, reduce_mean, p_out, true);
+    int rc = fm_step(h, ids, wts, y, B, lr, lambda, reduce_mean, p_out);
     if (rc != FNN_OK) return rc;
     if (loss_out) {
         MHK(h, hipMemcpyAsync(loss_out, h->loss_dev, 4, hipMemcpyDeviceToHost, h->st));
@@ -1052,7 +1148,7 @@ int fm_train_step_w(fm_handle* h, const int32_t* ids, const float* wts, const fl
 }
 
 // The online schedule (fm_online.hip.h): one launch per run of examples, cut at FM_ONLINE_CHUNK and after the example whose decay
-// takes the lazy scale out of [2^-24, 1] (fm_run's rule, so that online calls and batch steps fold at the same places).  A cut at
+// takes the lazy scale out of [2^-24, 1] (fm_step's rule, so that online calls and batch steps fold at the same places).  A cut at
 // the cap hands b (f32), the scale and the loss sum (f64) to the next launch unchanged: where it falls changes no bit.
 int fm_train_online(fm_handle* h, const int32_t* ids, const float* wts, const float* y, int64_t N, float lr, float lambda, float* p_out,
                     double* loss_sum_out, float* loss_last_out)
@@ -1092,137 +1188,74 @@ int fm_train_online(fm_handle* h, const int32_t* ids, const float* wts, const fl
     return FNN_OK;
 }
 
-// Several models, one feed (fm_online::k_fm_online_multi).  Everything runs on hs[0]'s stream, `st`: the other handles' streams
-// are joined into it by events before the first launch and wait for it after the last, and fold_scale() -- which works on its
-// handle's stream -- is given st for the time of its launch.
-//
-// The argument array of a launch is written into the next free slot of hs[0]'s pinned ring and copied from there to the same slot
-// of the device image.  The copy is asynchronous, so a slot is the copy's to read until the copy has run: slots are handed out
-// in order and never rewritten before the ring wraps, and a wrap first waits for the event recorded after the latest copy (all
-// copies are on st, in order, so that covers every one of them).  The ring persists from call to call for the same reason.
-namespace {
-
-constexpr size_t MULTI_RING = 8 * FM_ONLINE_MAX_MODELS;      // Args per ring (1 MiB): eight launches of the largest group
-
-int multi_ring(fm_handle* h0, size_t n_models, size_t* slot)
-{
-    if (!h0->multi_host) {                                           // first group call with this handle in front
-        MHK(h0, hipEventCreateWithFlags(&h0->multi_copied, hipEventDisableTiming));
-        MHK(h0, hipEventCreateWithFlags(&h0->multi_join, hipEventDisableTiming));
-        MHK(h0, hipMalloc((void**)&h0->multi_dev, MULTI_RING * sizeof(fm_online::Args)));
-        MHK(h0, hipHostMalloc((void**)&h0->multi_host, MULTI_RING * sizeof(fm_online::Args), hipHostMallocDefault));
-    }
-    if (h0->multi_cur + n_models > MULTI_RING) {
-        MHK(h0, hipEventSynchronize(h0->multi_copied));
-        h0->multi_cur = 0;
-    }
-    *slot = h0->multi_cur;
-    h0->multi_cur += n_models;
-    return FNN_OK;
-}
-
-}  // namespace
-
+// Several models, one feed (fm_online::k_fm_online_multi), as a GroupCall: every launch on hs[0]'s stream, the argument array
+// of each launch through hs[0]'s online_ring.
 int fm_train_online_multi(fm_handle* const* hs, int n_models, const int32_t* ids, const float* wts, const float* y, int64_t N,
                           const float* lr, const float* lambda, float* const* p_out, double* loss_sum_out, float* loss_last_out)
 {
-    fm_handle* h0 = hs && n_models >= 1 && n_models <= FM_ONLINE_MAX_MODELS ? hs[0] : nullptr;
-    auto refuse = [&](int code, const std::string& msg) { (h0 ? h0->err : g_fm_err) = msg; return code; };
-    auto at = [](const char* what, int m) { return std::string("fm_train_online_multi: model ") + std::to_string(m) + ": " + what; };
-    if (!hs || !lr || !lambda) return refuse(FNN_ERR_ARG, "fm_train_online_multi: null hs, lr or lambda");
-    if (n_models < 1 || n_models > FM_ONLINE_MAX_MODELS) return refuse(FNN_ERR_ARG, "fm_train_online_multi: n_models must be in [1, 1024]");
-    for (int m = 0; m < n_models; ++m) if (!hs[m]) return refuse(FNN_ERR_ARG, at("null handle", m));
-    {
-        std::vector<const fm_handle*> seen(hs, hs + n_models);
-        std::sort(seen.begin(), seen.end());
-        const auto dup = std::adjacent_find(seen.begin(), seen.end());
-        if (dup != seen.end()) {
-            int m = n_models - 1;
-            while (hs[m] != *dup) --m;                                // the later of the two places
-            return refuse(FNN_ERR_ARG, at("the same handle twice in one call (two workgroups would race on one table)", m));
-        }
-    }
-    for (int m = 1; m < n_models; ++m)
-        if (hs[m]->F != h0->F || hs[m]->dev != h0->dev) return refuse(FNN_ERR_ARG, at("n_fields or device differs from model 0's", m));
-    if (N < 0 || (N > 0 && (!ids || !y))) return refuse(FNN_ERR_ARG, "fm_train_online_multi: need N >= 0, ids and y");
+    GroupCall g("fm_train_online_multi", hs, n_models, FM_ONLINE_MAX_MODELS);
+    if (!hs || !lr || !lambda) return g.refuse(FNN_ERR_ARG, "null hs, lr or lambda");
+    int rc = g.check_handles("two workgroups would race on one table");
+    if (rc != FNN_OK) return rc;
+    if (N < 0 || (N > 0 && (!ids || !y))) return g.refuse(FNN_ERR_ARG, "need N >= 0, ids and y");
     for (int m = 0; m < n_models; ++m) {
         const float ll = lr[m] * lambda[m];
-        if (!(ll >= 0.f && ll < 1.0f) || lambda[m] < 0.f) return refuse(FNN_ERR_ARG, at("need 0 <= lr * lambda < 1", m));
+        if (!(ll >= 0.f && ll < 1.0f) || lambda[m] < 0.f) return g.refuse(FNN_ERR_ARG, g.at("need 0 <= lr * lambda < 1", m));
     }
-    for (int m = 0; m < n_models; ++m) {
-        if (hs[m]->opt != FM_OPT_SGD) return refuse(FNN_ERR_STATE, at("plain SGD only (Adam / FTRL pass over the whole table per step)", m));
-        if (!hs[m]->table16) return refuse(FNN_ERR_STATE, at("fm_set_table has not been called", m));
-    }
+    for (int m = 0; m < n_models; ++m)
+        if (hs[m]->opt != FM_OPT_SGD) return g.refuse(FNN_ERR_STATE, g.at("plain SGD only (Adam / FTRL pass over the whole table per step)", m));
+    rc = g.check_tables();
+    if (rc != FNN_OK) return rc;
     for (int m = 0; m < n_models; ++m) {
         if (loss_sum_out) loss_sum_out[m] = 0.0;
         if (loss_last_out) loss_last_out[m] = 0.f;
     }
     if (N == 0) return FNN_OK;
-    MHK(h0, hipSetDevice(h0->dev));
-    const hipStream_t st = h0->st;
-    // the streams that are not st, each once
-    std::vector<hipStream_t> others;
-    for (int m = 1; m < n_models; ++m) if (hs[m]->st != st) others.push_back(hs[m]->st);
-    std::sort(others.begin(), others.end());
-    others.erase(std::unique(others.begin(), others.end()), others.end());
-    size_t slot = 0;
-    int rc = multi_ring(h0, (size_t)n_models, &slot);                 // also creates the events
+    fm_handle* h0 = g.h0;
+    rc = g.enter();
     if (rc != FNN_OK) return rc;
-    for (hipStream_t o : others) {                                    // st after everything enqueued on the others so far
-        MHK(h0, hipEventRecord(h0->multi_join, o));
-        MHK(h0, hipStreamWaitEvent(st, h0->multi_join, 0));
-    }
+    const hipStream_t st = h0->st;
     int64_t chunk = h0->online_chunk;
-    std::vector<double> dec(n_models);
+    std::vector<double> dec(n_models), s(n_models);
     for (int m = 0; m < n_models; ++m) {
         MHK(h0, hipMemsetAsync(hs[m]->online_out, 0, sizeof(fm_online::Out), st));
         dec[m] = 1.0 - (double)lr[m] * (double)lambda[m];
         if (hs[m]->online_chunk < chunk) chunk = hs[m]->online_chunk;
     }
-    // an error from here on leaves the loop, and the other streams still get their join: they stay ordered behind what was launched
-    auto enqueue = [&]() -> int {
     for (int64_t n0 = 0; n0 < N;) {
-        if (n0) { const int rr = multi_ring(h0, (size_t)n_models, &slot); if (rr != FNN_OK) return rr; }
+        size_t slot = 0;
+        rc = ring_take(h0, h0->online_ring, (size_t)n_models, &slot);
+        if (rc != FNN_OK) return rc;
         // the launch ends after the first example whose decay takes ANY model's scale out of [2^-24, 1]
         int64_t cnt = 0;
         bool fold = false;
-        std::vector<double> s(n_models);
         for (int m = 0; m < n_models; ++m) s[m] = hs[m]->scale;
         while (n0 + cnt < N && cnt < chunk && !fold) {
             for (int m = 0; m < n_models; ++m) { s[m] *= dec[m]; fold = fold || s[m] < 5.96e-8 || s[m] > 1.0; }
             ++cnt;
         }
-        fm_online::Args* a = h0->multi_host + slot;
+        fm_online::Args* a = h0->online_ring.at_host<fm_online::Args>(slot);
         for (int m = 0; m < n_models; ++m) {
             fm_handle* h = hs[m];
             a[m] = fm_online::Args{ids + n0 * h->F, wts ? wts + n0 * h->F : nullptr, y + n0, cnt, h->F, h->K, h->rw, h->table16, h->n_rows, h->b,
                                    h->scale, dec[m], lr[m], lambda[m], p_out && p_out[m] ? p_out[m] + n0 : nullptr, h->err_flag,
                                    h->online_out};
         }
-        MHK(h0, hipMemcpyAsync(h0->multi_dev + slot, a, (size_t)n_models * sizeof(fm_online::Args), hipMemcpyHostToDevice, st));
-        MHK(h0, hipEventRecord(h0->multi_copied, st));
-        hipLaunchKernelGGL(fm_online::k_fm_online_multi, dim3((unsigned)n_models), dim3(256), 0, st, h0->multi_dev + slot);
+        rc = ring_send(h0, h0->online_ring, slot, (size_t)n_models);
+        if (rc != FNN_OK) return rc;
+        hipLaunchKernelGGL(fm_online::k_fm_online_multi, dim3((unsigned)n_models), dim3(256), 0, st, h0->online_ring.at_dev<fm_online::Args>(slot));
         MHK(h0, hipGetLastError());
         for (int m = 0; m < n_models; ++m) {
             fm_handle* h = hs[m];
             h->scale = s[m];
             if (s[m] < 5.96e-8 || s[m] > 1.0) {
-                const hipStream_t own = h->st;
-                h->st = st;                                           // fold_scale launches on h->st: this one belongs on st
-                const int rf = fold_scale(h);
-                h->st = own;
-                if (rf != FNN_OK) { if (h != h0) h0->err = at(h->err.c_str(), m); return rf; }
+                const int rf = on_stream(h, st, [&] { return fold_scale(h); });
+                if (rf != FNN_OK) return g.member_failed(rf, h, m);
             }
         }
         n0 += cnt;
     }
-    return FNN_OK;
-    };
-    rc = enqueue();
-    if (!others.empty()) {                                            // whatever the other streams get from here on comes after the call
-        MHK(h0, hipEventRecord(h0->multi_join, st));
-        for (hipStream_t o : others) MHK(h0, hipStreamWaitEvent(o, h0->multi_join, 0));
-    }
+    rc = g.leave();
     if (rc != FNN_OK || (!loss_sum_out && !loss_last_out)) return rc;
     std::string bad;
     for (int m = 0; m < n_models; ++m) {
@@ -1231,93 +1264,50 @@ int fm_train_online_multi(fm_handle* const* hs, int n_models, const int32_t* ids
         MHK(h0, hipMemcpyAsync(&o, h->online_out, sizeof(o), hipMemcpyDeviceToHost, h->st));
         const int rm = fm_sync(h);
         if (rm == FNN_ERR_RANGE) bad += (bad.empty() ? "" : ", ") + std::to_string(m);
-        else if (rm != FNN_OK) { if (h != h0) h0->err = at(h->err.c_str(), m); return rm; }
+        else if (rm != FNN_OK) return g.member_failed(rm, h, m);
         if (loss_sum_out) loss_sum_out[m] = o.loss_sum;
         if (loss_last_out) loss_last_out[m] = o.loss_last;
     }
-    if (!bad.empty()) MFAIL(h0, FNN_ERR_RANGE, "fm_train_online_multi: feature id outside [-1, n_rows) in model(s) " + bad);
+    if (!bad.empty()) return g.refuse(FNN_ERR_RANGE, "feature id outside [-1, n_rows) in model(s) " + bad);
     return FNN_OK;
 }
 
-// One mini-batch step of several models on one feed (the kernels: k_fm_step_*).  Streams and the pinned ring as in
-// fm_train_online_multi: everything on hs[0]'s stream, the argument array of a call in the next free slots of the ring.
-namespace {
-
-constexpr size_t STEP_RING = 4 * FM_STEP_MAX_MODELS;             // StepArgs per ring: four calls of the largest group
-
-int step_ring(fm_handle* h0, size_t n, size_t* slot)
-{
-    if (!h0->step_host) {                                            // first such call with this handle in front
-        if (!h0->step_copied) MHK(h0, hipEventCreateWithFlags(&h0->step_copied, hipEventDisableTiming));
-        if (!h0->step_join) MHK(h0, hipEventCreateWithFlags(&h0->step_join, hipEventDisableTiming));
-        if (!h0->step_dev) MHK(h0, hipMalloc(&h0->step_dev, STEP_RING * sizeof(StepArg)));
-        if (!h0->step_pack) MHK(h0, hipMalloc(&h0->step_pack, FM_STEP_MAX_MODELS * sizeof(StepPack)));
-        MHK(h0, hipHostMalloc(&h0->step_host, STEP_RING * sizeof(StepArg), hipHostMallocDefault));
-    }
-    if (h0->step_cur + n > STEP_RING) {
-        MHK(h0, hipEventSynchronize(h0->step_copied));
-        h0->step_cur = 0;
-    }
-    *slot = h0->step_cur;
-    h0->step_cur += n;
-    return FNN_OK;
-}
-
-}  // namespace
-
+// One mini-batch step of several models on one feed (the kernels: k_fm_step_*), as a GroupCall: every launch on hs[0]'s stream,
+// the call's argument array through hs[0]'s step_ring.  Each member's entry is its plan_step(), the plan the solo step launches.
 int fm_train_step_multi(fm_handle* const* hs, int n_models, const int32_t* ids, const float* wts, const float* y, int B,
                         const float* lr, const float* lambda, const int* reduce_mean, float* const* p_out, float* loss_out)
 {
-    fm_handle* h0 = hs && n_models >= 1 && n_models <= FM_STEP_MAX_MODELS ? hs[0] : nullptr;
-    auto refuse = [&](int code, const std::string& msg) { (h0 ? h0->err : g_fm_err) = "fm_train_step_multi: " + msg; return code; };
-    auto at = [](const char* what, int m) { return "model " + std::to_string(m) + ": " + what; };
-    if (!hs || !lr || !lambda) return refuse(FNN_ERR_ARG, "null hs, lr or lambda");
-    if (n_models < 1 || n_models > FM_STEP_MAX_MODELS) return refuse(FNN_ERR_ARG, "n_models must be in [1, 1024]");
-    for (int m = 0; m < n_models; ++m) if (!hs[m]) return refuse(FNN_ERR_ARG, at("null handle", m));
-    {
-        std::vector<const fm_handle*> seen(hs, hs + n_models);
-        std::sort(seen.begin(), seen.end());
-        const auto dup = std::adjacent_find(seen.begin(), seen.end());
-        if (dup != seen.end()) {
-            int m = n_models - 1;
-            while (hs[m] != *dup) --m;                                // the later of the two places
-            return refuse(FNN_ERR_ARG, at("the same handle twice in one call (two updates would race on one table)", m));
-        }
-    }
-    for (int m = 1; m < n_models; ++m)
-        if (hs[m]->F != h0->F || hs[m]->dev != h0->dev) return refuse(FNN_ERR_ARG, at("n_fields or device differs from model 0's", m));
-    if (!ids || !y) return refuse(FNN_ERR_ARG, "null ids or y");
-    if (B < 1) return refuse(FNN_ERR_ARG, "B must be in [1, max_batch]");
-    for (int m = 0; m < n_models; ++m) if (B > hs[m]->Bmax) return refuse(FNN_ERR_ARG, at("B must be in [1, max_batch]", m));
+    GroupCall g("fm_train_step_multi", hs, n_models, FM_STEP_MAX_MODELS);
+    if (!hs || !lr || !lambda) return g.refuse(FNN_ERR_ARG, "null hs, lr or lambda");
+    int rc = g.check_handles("two updates would race on one table");
+    if (rc != FNN_OK) return rc;
+    if (!ids || !y) return g.refuse(FNN_ERR_ARG, "null ids or y");
+    if (B < 1) return g.refuse(FNN_ERR_ARG, "B must be in [1, max_batch]");
+    for (int m = 0; m < n_models; ++m) if (B > hs[m]->Bmax) return g.refuse(FNN_ERR_ARG, g.at("B must be in [1, max_batch]", m));
     for (int m = 0; m < n_models; ++m) {                              // fm_train_step_w's own expressions
         const fm_handle* h = hs[m];
-        if (h->opt == FM_OPT_SGD && (!(lr[m] * lambda[m] < 1.0f) || lambda[m] < 0.f)) return refuse(FNN_ERR_ARG, at("need 0 <= lr * lambda < 1", m));
-        if (h->opt != FM_OPT_SGD && (!(lambda[m] >= 0.f) || !(lr[m] > 0.f))) return refuse(FNN_ERR_ARG, at("Adam / FTRL need lr > 0 and lambda >= 0", m));
+        if (h->opt == FM_OPT_SGD && (!(lr[m] * lambda[m] < 1.0f) || lambda[m] < 0.f)) return g.refuse(FNN_ERR_ARG, g.at("need 0 <= lr * lambda < 1", m));
+        if (h->opt != FM_OPT_SGD && (!(lambda[m] >= 0.f) || !(lr[m] > 0.f))) return g.refuse(FNN_ERR_ARG, g.at("Adam / FTRL need lr > 0 and lambda >= 0", m));
     }
-    for (int m = 0; m < n_models; ++m) if (!hs[m]->table16) return refuse(FNN_ERR_STATE, at("fm_set_table has not been called", m));
-
+    rc = g.check_tables();
+    if (rc != FNN_OK) return rc;
+    fm_handle* h0 = g.h0;
     if (n_models == 1) {       // nothing to share: the solo step itself, without the argument copy (15 us in front of a 27 us step)
         const int rs = fm_train_step_w(h0, ids, wts, y, B, lr[0], lambda[0], reduce_mean ? reduce_mean[0] : 0, p_out ? p_out[0] : nullptr, loss_out);
-        if (rs == FNN_ERR_RANGE) h0->err = "fm_train_step_multi: feature id outside [-1, n_rows) in model(s) 0";
+        if (rs == FNN_ERR_RANGE) g.refuse(rs, "feature id outside [-1, n_rows) in model(s) 0");
         return rs;
     }
-    MHK(h0, hipSetDevice(h0->dev));
+    rc = g.enter();
+    if (rc != FNN_OK) return rc;
     const hipStream_t st = h0->st;
     const int F = h0->F, M = n_models;
-    std::vector<hipStream_t> others;                                  // the streams that are not st, each once
-    for (int m = 1; m < M; ++m) if (hs[m]->st != st) others.push_back(hs[m]->st);
-    std::sort(others.begin(), others.end());
-    others.erase(std::unique(others.begin(), others.end()), others.end());
+    if (!h0->step_pack) MHK(h0, hipMalloc((void**)&h0->step_pack, FM_STEP_MAX_MODELS * sizeof(StepPack)));
     size_t slot = 0;
-    int rc = step_ring(h0, (size_t)M, &slot);                         // also creates the events
+    rc = ring_take(h0, h0->step_ring, (size_t)M, &slot);
     if (rc != FNN_OK) return rc;
-    for (hipStream_t o : others) {                                    // st after everything enqueued on the others so far
-        MHK(h0, hipEventRecord(h0->step_join, o));
-        MHK(h0, hipStreamWaitEvent(st, h0->step_join, 0));
-    }
-    StepArg* a = static_cast<StepArg*>(h0->step_host) + slot;
-    const StepArg* d = static_cast<const StepArg*>(h0->step_dev) + slot;
-    StepPack* pack = loss_out ? static_cast<StepPack*>(h0->step_pack) : nullptr;
+    StepArg* a = h0->step_ring.at_host<StepArg>(slot);
+    const StepArg* d = h0->step_ring.at_dev<StepArg>(slot);
+    StepPack* pack = loss_out ? h0->step_pack : nullptr;
 
     // grouping classes: equal n_rows and equal shared-rows mode; the class's first model lends rec, skeys and the marks
     struct Cls { fm_handle* lead; int stamp; };
@@ -1351,7 +1341,7 @@ int fm_train_step_multi(fm_handle* const* hs, int n_models, const int32_t* ids, 
     }
     MHK(h0, hipGetLastError());
 
-    const bool wt = !(getenv("FM_WT") && atoi(getenv("FM_WT")) == 0);
+    const bool wt = fm_wt_env();
     auto lay_of = [](const fm_handle* h) { return !h->wide ? 0 : h->rw <= 64 ? 1 : 2; };          // launch_fwd_nw's choice of kernel
     auto form_of = [](const fm_handle* h) { return h->wide ? 2 : h->shared ? 1 : 0; };              // level 1 / 2: narrow, narrow shared, wide
     int fcnt[3] = {0, 0, 0}, scnt[3] = {0, 0, 0}, ffirst[3], sfirst[3], fpos[3], spos[3], nb1max[3] = {0, 0, 0};
@@ -1360,89 +1350,54 @@ int fm_train_step_multi(fm_handle* const* hs, int n_models, const int32_t* ids, 
     for (int c = 1; c < 3; ++c) { ffirst[c] = ffirst[c - 1] + fcnt[c - 1]; sfirst[c] = sfirst[c - 1] + scnt[c - 1]; }
     for (int c = 0; c < 3; ++c) { fpos[c] = ffirst[c]; spos[c] = sfirst[c]; }
     std::vector<float> lr_step(M);
-    for (int m = 0; m < M; ++m) {                                     // fm_run's arguments of a training step, model by model
+    for (int m = 0; m < M; ++m) {                                     // plan, store into a[m], bucket by layout / form
         fm_handle* h = hs[m];
         const Cls& k = cls[cls_of[m]];
-        const bool opt = h->opt != FM_OPT_SGD;
-        const int rm = reduce_mean ? reduce_mean[m] : 0;
-        lr_step[m] = lr[m];
-        if (opt) {
-            h->t += 1;
-            if (h->opt == FM_OPT_ADAM)                 // TensorFlow's bias-corrected step size lr_t
-                lr_step[m] = (float)((double)lr[m] * std::sqrt(1.0 - std::pow((double)h->beta2, (double)h->t)) /
-                                     (1.0 - std::pow((double)h->beta1, (double)h->t)));
-        }
-        const int ex = h->wide ? wide_epb(h) : 16, Ba = rup(B, ex);
-        a[m].a = FmArgs{ids, y, B, F, h->K, h->table16, h->n_rows, h->b, (float)h->scale, rm ? 1.0f / (float)B : 1.0f, 1,
-                        h->gxp, h->K1p, p_out ? p_out[m] : nullptr, h->loss_t, h->gb_part, h->err_flag, wt,
-                        opt && !h->dense_g ? h->stamp : nullptr, (int)h->t, h->rw, wts};
-        if (!opt) h->scale *= 1.0 - (double)lr[m] * (double)lambda[m];
-        RowGroupBufs rg = h->rg;
-        rg.rec = k.lead->rg.rec;
-        ScatArgs sa = scat_args(rg, SORT_N, F, h->K, h->gxp, h->K1p, h->cpow1, opt ? -1.0 : (double)lr[m] / h->scale,
-                                opt ? h->G : h->table16, h->wide ? h->rw : SLOT);
+        const StepPlan p = plan_step(h, ids, wts, y, B, lr[m], lambda[m], reduce_mean ? reduce_mean[m] : 0, p_out ? p_out[m] : nullptr, wt,
+                                     k.lead, k.stamp, SCAT1_HALF, SCAT2_WAVE);
+        a[m].a = p.a; a[m].sa = p.sa; a[m].t = p.t; a[m].nb1 = p.nb1;
+        lr_step[m] = p.lr_step;
         a[m].own_marks = nullptr; a[m].own_stamp = 0;
-        if (h->shared) {
-            sa.tag_shared = k.lead->tag_shared; sa.stamp = k.stamp;
-            if (h != k.lead) { a[m].own_marks = h->tag_shared; a[m].own_stamp = on_stream(h, st, [&] { return fm_next_stamp(h); }); }
-        } else if (h->wide) { sa.tag_shared = h->noshare; sa.stamp = 1; }
-        if (h->wide) {
-            sa.gxf = h->rw;
-            a[m].nb1 = (F * (SORT_N / WCH) * (h->rw / 4) + 255) / 256;
-        } else {
-            a[m].nb1 = scat1_blocks(sa, SCAT1_HALF);
-            sa.form2 = SCAT2_WAVE;
-        }
-        a[m].sa = sa;
-        a[m].t = StepTail{h->b, h->gb_part, Ba / ex, lr[m], lambda[m], h->loss_t, Ba, rm ? 1.0f / (float)B : 1.0f, h->loss_dev,
-                          opt ? FmBiasOpt{h->opt, h->sb, lr_step[m], h->beta1, h->beta2, h->eps} : FmBiasOpt{FM_OPT_SGD, nullptr, 0.f, 0.f, 0.f, 0.f}};
+        if (h->shared && h != k.lead) { a[m].own_marks = h->tag_shared; a[m].own_stamp = on_stream(h, st, [&] { return fm_next_stamp(h); }); }
         a[m].pack = pack ? pack + m : nullptr;
         a[fpos[lay_of(h)]++].fcls = m;
         a[spos[form_of(h)]++].scls = m;
-        nb1max[form_of(h)] = std::max(nb1max[form_of(h)], a[m].nb1);
+        nb1max[form_of(h)] = std::max(nb1max[form_of(h)], p.nb1);
     }
-    // an error from here on leaves the lambda, and the other streams still get their join: they stay ordered behind what was launched
-    auto enqueue = [&]() -> int {
-        MHK(h0, hipMemcpyAsync(const_cast<StepArg*>(d), a, (size_t)M * sizeof(StepArg), hipMemcpyHostToDevice, st));
-        MHK(h0, hipEventRecord(h0->step_copied, st));
-        for (int i = nride; i < (int)order.size(); ++i) {             // the other key width: the plain rank merge
-            const SortArgs& so = sorts[i];
-            if (cls[order[i]].lead->key64) hipLaunchKernelGGL((k_sortB<unsigned long long>), dim3(so.nblk), dim3(256), sort_lds_bytes<unsigned long long>(), st, so);
-            else hipLaunchKernelGGL((k_sortB<unsigned>), dim3(so.nblk), dim3(256), sort_lds_bytes<unsigned>(), st, so);
-        }
-        int ride = nride;                                             // launch 2: the merges ride in the first layout present
-        for (int c = 0; c < 3; ++c) {
-            if (!fcnt[c]) continue;
-            const int tiles = (B + (c == 2 ? 8 : 16) - 1) / (c == 2 ? 8 : 16);
-            if (cls[0].lead->key64) launch_step_fwd<unsigned long long>(st, F, wts != nullptr, c, d, ride, 16 * F, ffirst[c], fcnt[c], tiles);
-            else launch_step_fwd<unsigned>(st, F, wts != nullptr, c, d, ride, 16 * F, ffirst[c], fcnt[c], tiles);
-            ride = 0;
-        }
-        MHK(h0, hipGetLastError());
-        if (scnt[0]) hipLaunchKernelGGL(k_fm_step_scat1<false>, dim3(nb1max[0], scnt[0]), dim3(256), 0, st, d, sfirst[0]);      // launch 3
-        if (scnt[1]) hipLaunchKernelGGL(k_fm_step_scat1<true>, dim3(nb1max[1], scnt[1]), dim3(256), 0, st, d, sfirst[1]);
-        if (scnt[2]) hipLaunchKernelGGL(k_fm_step_scatw1, dim3(nb1max[2], scnt[2]), dim3(256), 0, st, d, sfirst[2]);
-        if (scnt[0]) hipLaunchKernelGGL(k_fm_step_scat2_tail<false>, dim3(1 + 256, scnt[0]), dim3(256), 0, st, d, sfirst[0]);   // launch 4
-        if (scnt[1]) hipLaunchKernelGGL(k_fm_step_scat2_tail<true>, dim3(1 + 256, scnt[1]), dim3(256), 0, st, d, sfirst[1]);
-        if (scnt[2]) hipLaunchKernelGGL(k_fm_step_scatw2_tail, dim3(1 + 256, scnt[2]), dim3(256), 0, st, d, sfirst[2]);
-        MHK(h0, hipGetLastError());
-        for (int m = 0; m < M; ++m) {                                 // Adam / FTRL: the dense pass; SGD: the fold where it is due
-            fm_handle* h = hs[m];
-            if (h->opt != FM_OPT_SGD) {
-                on_stream(h, st, [&] { launch_opt_pass(h, lambda[m], lr_step[m]); return 0; });
-                MHK(h0, hipGetLastError());
-            } else if (h->scale < 5.96e-8 || h->scale > 1.0) {
-                const int rf = on_stream(h, st, [&] { return fold_scale(h); });
-                if (rf != FNN_OK) { if (h != h0) h0->err = "fm_train_step_multi: " + at(h->err.c_str(), m); return rf; }
-            }
-        }
-        return FNN_OK;
-    };
-    rc = enqueue();
-    if (!others.empty()) {                                            // whatever the other streams get from here on comes after the call
-        MHK(h0, hipEventRecord(h0->step_join, st));
-        for (hipStream_t o : others) MHK(h0, hipStreamWaitEvent(o, h0->step_join, 0));
+    rc = ring_send(h0, h0->step_ring, slot, (size_t)M);
+    if (rc != FNN_OK) return rc;
+    for (int i = nride; i < (int)order.size(); ++i) {                 // the other key width: the plain rank merge
+        const SortArgs& so = sorts[i];
+        if (cls[order[i]].lead->key64) hipLaunchKernelGGL((k_sortB<unsigned long long>), dim3(so.nblk), dim3(256), sort_lds_bytes<unsigned long long>(), st, so);
+        else hipLaunchKernelGGL((k_sortB<unsigned>), dim3(so.nblk), dim3(256), sort_lds_bytes<unsigned>(), st, so);
     }
+    int ride = nride;                                                 // launch 2: the merges ride in the first layout present
+    for (int c = 0; c < 3; ++c) {
+        if (!fcnt[c]) continue;
+        const int tiles = (B + (c == 2 ? 8 : 16) - 1) / (c == 2 ? 8 : 16);
+        if (cls[0].lead->key64) launch_step_fwd<unsigned long long>(st, F, wts != nullptr, c, d, ride, 16 * F, ffirst[c], fcnt[c], tiles);
+        else launch_step_fwd<unsigned>(st, F, wts != nullptr, c, d, ride, 16 * F, ffirst[c], fcnt[c], tiles);
+        ride = 0;
+    }
+    MHK(h0, hipGetLastError());
+    if (scnt[0]) hipLaunchKernelGGL(k_fm_step_scat1<false>, dim3(nb1max[0], scnt[0]), dim3(256), 0, st, d, sfirst[0]);      // launch 3
+    if (scnt[1]) hipLaunchKernelGGL(k_fm_step_scat1<true>, dim3(nb1max[1], scnt[1]), dim3(256), 0, st, d, sfirst[1]);
+    if (scnt[2]) hipLaunchKernelGGL(k_fm_step_scatw1, dim3(nb1max[2], scnt[2]), dim3(256), 0, st, d, sfirst[2]);
+    if (scnt[0]) hipLaunchKernelGGL(k_fm_step_scat2_tail<false>, dim3(1 + 256, scnt[0]), dim3(256), 0, st, d, sfirst[0]);   // launch 4
+    if (scnt[1]) hipLaunchKernelGGL(k_fm_step_scat2_tail<true>, dim3(1 + 256, scnt[1]), dim3(256), 0, st, d, sfirst[1]);
+    if (scnt[2]) hipLaunchKernelGGL(k_fm_step_scatw2_tail, dim3(1 + 256, scnt[2]), dim3(256), 0, st, d, sfirst[2]);
+    MHK(h0, hipGetLastError());
+    for (int m = 0; m < M; ++m) {                                     // Adam / FTRL: the dense pass; SGD: the fold where it is due
+        fm_handle* h = hs[m];
+        if (h->opt != FM_OPT_SGD) {
+            on_stream(h, st, [&] { launch_opt_pass(h, lambda[m], lr_step[m]); return 0; });
+            MHK(h0, hipGetLastError());
+        } else if (h->scale < 5.96e-8 || h->scale > 1.0) {
+            const int rf = on_stream(h, st, [&] { return fold_scale(h); });
+            if (rf != FNN_OK) return g.member_failed(rf, h, m);
+        }
+    }
+    rc = g.leave();
     if (rc != FNN_OK || !loss_out) return rc;
     std::vector<StepPack> hp(M);
     MHK(h0, hipMemcpyAsync(hp.data(), pack, (size_t)M * sizeof(StepPack), hipMemcpyDeviceToHost, st));
@@ -1452,7 +1407,7 @@ int fm_train_step_multi(fm_handle* const* hs, int n_models, const int32_t* ids, 
         loss_out[m] = hp[m].loss;
         if (hp[m].flag) bad += (bad.empty() ? "" : ", ") + std::to_string(m);
     }
-    if (!bad.empty()) MFAIL(h0, FNN_ERR_RANGE, "fm_train_step_multi: feature id outside [-1, n_rows) in model(s) " + bad);
+    if (!bad.empty()) return g.refuse(FNN_ERR_RANGE, "feature id outside [-1, n_rows) in model(s) " + bad);
     return FNN_OK;
 }
 
@@ -1466,7 +1421,7 @@ int fm_predict_w(fm_handle* h, const int32_t* ids, const float* wts, int B, floa
     if (B < 1 || B > h->Bmax) MFAIL(h, FNN_ERR_ARG, "B must be in [1, max_batch]");
     if (!h->table16) MFAIL(h, FNN_ERR_STATE, "fm_set_table has not been called");
     MHK(h, hipSetDevice(h->dev));
-    return fm_run(h, ids, wts, nullptr, B, 0.f, 0.f, 0, p_out, false);
+    return fm_forward(h, ids, wts, B, p_out);
 }
 
 int fm_set_optimizer(fm_handle* h, int optimizer, float beta1, float beta2, float eps)
@@ -1543,7 +1498,7 @@ int fm_eval_w(fm_handle* h, const int32_t* ids, const float* wts, const int32_t*
     MHK(h, hipMalloc((void**)&p_d, (size_t)N * 4));
     for (int64_t lo = 0; lo < N; lo += h->Bmax) {
         const int B = (int)(N - lo < h->Bmax ? N - lo : h->Bmax);
-        const int rc = fm_run(h, ids + lo * h->F, wts ? wts + lo * h->F : nullptr, nullptr, B, 0.f, 0.f, 0, p_d + lo, false);
+        const int rc = fm_forward(h, ids + lo * h->F, wts ? wts + lo * h->F : nullptr, B, p_d + lo);
         if (rc != FNN_OK) { hipFree(p_d); return rc; }
     }
     double out[4] = {0, 0, 0, 0};
@@ -1560,54 +1515,16 @@ int fm_eval_w(fm_handle* h, const int32_t* ids, const float* wts, const int32_t*
     return FNN_OK;
 }
 
-// Several models, one test feed (fm_predict_multi, fm_eval_multi).  Everything runs on hs[0]'s stream under fm_train_online_multi's
-// rule (the other handles' streams joined in by events before the first launch, and waiting for the last one after it).  The
-// argument array of a group goes through a pinned ring of hs[0]'s and its device image, as that call's does: a slot is the copy's
-// to read until the copy has run, so slots are handed out in order and a wrap waits for the event behind the latest copy.
+// Several models, one test feed (fm_predict_multi, fm_eval_multi), as GroupCalls: every launch on hs[0]'s stream, the argument
+// array of a group through hs[0]'s eval_ring.  A handle may be listed twice: reading is not a race.
 namespace {
 
-constexpr size_t EVAL_RING = 4 * FM_EVAL_MAX_MODELS;             // EvalArgs per ring: four groups of the largest size
-
-int eval_ring(fm_handle* h0, size_t n, size_t* slot)
+// what both calls refuse after the list itself
+int eval_check(const GroupCall& g, const int32_t* ids, bool need_y, const int32_t* y, int64_t N)
 {
-    if (!h0->eval_host) {                                            // first such call with this handle in front
-        if (!h0->eval_copied) MHK(h0, hipEventCreateWithFlags(&h0->eval_copied, hipEventDisableTiming));
-        if (!h0->eval_join) MHK(h0, hipEventCreateWithFlags(&h0->eval_join, hipEventDisableTiming));
-        if (!h0->eval_dev) MHK(h0, hipMalloc(&h0->eval_dev, EVAL_RING * sizeof(EvalArg)));
-        MHK(h0, hipHostMalloc(&h0->eval_host, EVAL_RING * sizeof(EvalArg), hipHostMallocDefault));
-    }
-    if (h0->eval_cur + n > EVAL_RING) {
-        MHK(h0, hipEventSynchronize(h0->eval_copied));
-        h0->eval_cur = 0;
-    }
-    *slot = h0->eval_cur;
-    h0->eval_cur += n;
-    return FNN_OK;
-}
-
-// What both calls refuse before any launch.  The message goes to hs[0], or to the library without a usable hs[0].
-int eval_check(const char* fn, fm_handle* const* hs, int n_models, const int32_t* ids, bool need_y, const int32_t* y, int64_t N)
-{
-    const std::string name(fn);
-    fm_handle* h0 = hs && n_models >= 1 && n_models <= FM_EVAL_MAX_MODELS ? hs[0] : nullptr;
-    auto refuse = [&](int code, const std::string& msg) { (h0 ? h0->err : g_fm_err) = name + ": " + msg; return code; };
-    auto at = [](const char* what, int m) { return "model " + std::to_string(m) + ": " + what; };
-    if (!hs) return refuse(FNN_ERR_ARG, "null hs");
-    if (n_models < 1 || n_models > FM_EVAL_MAX_MODELS) return refuse(FNN_ERR_ARG, "n_models must be in [1, 1024]");
-    for (int m = 0; m < n_models; ++m) if (!hs[m]) return refuse(FNN_ERR_ARG, at("null handle", m));
-    if (!ids || (need_y && !y)) return refuse(FNN_ERR_ARG, need_y ? "null ids or y" : "null ids");
-    if (N < 1 || N > ((int64_t)1 << 30)) return refuse(FNN_ERR_ARG, "N must be in [1, 2^30]");
-    for (int m = 1; m < n_models; ++m)
-        if (hs[m]->F != h0->F || hs[m]->dev != h0->dev) return refuse(FNN_ERR_ARG, at("n_fields or device differs from model 0's", m));
-    for (int m = 0; m < n_models; ++m) if (!hs[m]->table16) return refuse(FNN_ERR_STATE, at("fm_set_table has not been called", m));
-    return FNN_OK;
-}
-
-void eval_other_streams(fm_handle* const* hs, int n_models, std::vector<hipStream_t>& others)      // the streams that are not hs[0]'s, each once
-{
-    for (int m = 1; m < n_models; ++m) if (hs[m]->st != hs[0]->st) others.push_back(hs[m]->st);
-    std::sort(others.begin(), others.end());
-    others.erase(std::unique(others.begin(), others.end()), others.end());
+    if (!ids || (need_y && !y)) return g.refuse(FNN_ERR_ARG, need_y ? "null ids or y" : "null ids");
+    if (N < 1 || N > ((int64_t)1 << 30)) return g.refuse(FNN_ERR_ARG, "N must be in [1, 2^30]");
+    return g.check_tables();
 }
 
 // The predictions of g models on the N lines, p[m] (nullable) each: the argument array into the ring, then one launch per layout
@@ -1616,25 +1533,23 @@ int eval_forward(fm_handle* h0, fm_handle* const* hs, int g, const int32_t* ids,
                  const EvalArg** dev_args)
 {
     size_t slot = 0;
-    const int rc = eval_ring(h0, (size_t)g, &slot);
+    int rc = ring_take(h0, h0->eval_ring, (size_t)g, &slot);
     if (rc != FNN_OK) return rc;
-    EvalArg* a = static_cast<EvalArg*>(h0->eval_host) + slot;
-    const EvalArg* d = static_cast<const EvalArg*>(h0->eval_dev) + slot;
+    EvalArg* a = h0->eval_ring.at_host<EvalArg>(slot);
+    const EvalArg* d = h0->eval_ring.at_dev<EvalArg>(slot);
     auto cls_of = [](const fm_handle* h) { return !h->wide ? 0 : h->rw <= 64 ? 1 : 2; };   // launch_fwd_nw's choice of kernel
     int cnt[3] = {0, 0, 0}, first[3], pos[3];
     for (int m = 0; m < g; ++m) ++cnt[cls_of(hs[m])];
     first[0] = 0; first[1] = cnt[0]; first[2] = cnt[0] + cnt[1];
     for (int c = 0; c < 3; ++c) pos[c] = first[c];
-    const bool wt = !(getenv("FM_WT") && atoi(getenv("FM_WT")) == 0);
+    const bool wt = fm_wt_env();
     for (int m = 0; m < g; ++m) {
-        const fm_handle* h = hs[m];                               // fm_run's arguments of a prediction, with B = N
-        a[m].a = FmArgs{ids, nullptr, (int)N, h->F, h->K, h->table16, h->n_rows, h->b, (float)h->scale, 1.0f, 0, h->gxp, h->K1p, p[m],
-                        h->loss_t, h->gb_part, h->err_flag, wt, nullptr, (int)h->t, h->rw, wts};
-        a[pos[cls_of(h)]++].cls = m;
+        a[m].a = predict_args(hs[m], ids, wts, (int)N, p[m], wt);
+        a[pos[cls_of(hs[m])]++].cls = m;
     }
     const hipStream_t st = h0->st;
-    MHK(h0, hipMemcpyAsync(const_cast<EvalArg*>(d), a, (size_t)g * sizeof(EvalArg), hipMemcpyHostToDevice, st));
-    MHK(h0, hipEventRecord(h0->eval_copied, st));
+    rc = ring_send(h0, h0->eval_ring, slot, (size_t)g);
+    if (rc != FNN_OK) return rc;
     const char* order = getenv("FM_EVAL_ORDER");                  // "model": the model is the fast index of the grid; default: the tile
     const int model_fast = order && !strcmp(order, "model");
     for (int c = 0; c < 3; ++c) {
@@ -1655,22 +1570,6 @@ int eval_forward(fm_handle* h0, fm_handle* const* hs, int g, const int32_t* ids,
     return FNN_OK;
 }
 
-int eval_join_in(fm_handle* h0, const std::vector<hipStream_t>& others)
-{
-    for (hipStream_t o : others) {                                    // st after everything enqueued on the others so far
-        MHK(h0, hipEventRecord(h0->eval_join, o));
-        MHK(h0, hipStreamWaitEvent(h0->st, h0->eval_join, 0));
-    }
-    return FNN_OK;
-}
-int eval_join_out(fm_handle* h0, const std::vector<hipStream_t>& others)
-{
-    if (others.empty()) return FNN_OK;                                // whatever the other streams get from here on comes after the call
-    MHK(h0, hipEventRecord(h0->eval_join, h0->st));
-    for (hipStream_t o : others) MHK(h0, hipStreamWaitEvent(o, h0->eval_join, 0));
-    return FNN_OK;
-}
-
 inline size_t up256(size_t b) { return (b + 255) / 256 * 256; }
 // scratch of a group of g models: p [g][N], the metric pass's, out [g], flags [g], n_pos
 size_t eval_scratch_bytes(int g, int64_t N)
@@ -1682,31 +1581,27 @@ size_t eval_scratch_bytes(int g, int64_t N)
 
 int fm_predict_multi(fm_handle* const* hs, int n_models, const int32_t* ids, const float* wts, int64_t N, float* const* p_out)
 {
-    int rc = eval_check("fm_predict_multi", hs, n_models, ids, false, nullptr, N);
+    GroupCall g("fm_predict_multi", hs, n_models, FM_EVAL_MAX_MODELS);
+    int rc = g.check_handles(nullptr);
+    if (rc == FNN_OK) rc = eval_check(g, ids, false, nullptr, N);
     if (rc != FNN_OK) return rc;
-    fm_handle* h0 = hs[0];
-    if (!p_out) MFAIL(h0, FNN_ERR_ARG, "fm_predict_multi: null p_out");
-    MHK(h0, hipSetDevice(h0->dev));
-    std::vector<hipStream_t> others;
-    eval_other_streams(hs, n_models, others);
-    size_t slot = 0;
-    if (!h0->eval_host) { rc = eval_ring(h0, 0, &slot); if (rc != FNN_OK) return rc; }     // the events
-    rc = eval_join_in(h0, others);
+    if (!p_out) return g.refuse(FNN_ERR_ARG, "null p_out");
+    rc = g.enter();
     if (rc != FNN_OK) return rc;
     const EvalArg* d = nullptr;
-    rc = eval_forward(h0, hs, n_models, ids, wts, N, p_out, &d);
-    const int rj = eval_join_out(h0, others);                         // also after an error: the others stay ordered behind what ran
+    rc = eval_forward(g.h0, hs, n_models, ids, wts, N, p_out, &d);
+    const int rj = g.leave();
     return rc != FNN_OK ? rc : rj;
 }
 
 int fm_eval_multi(fm_handle* const* hs, int n_models, const int32_t* ids, const float* wts, const int32_t* y, int64_t N,
                   double* auc, double* rmse, double* logloss, int* status)
 {
-    int rc = eval_check("fm_eval_multi", hs, n_models, ids, true, y, N);
+    GroupCall g("fm_eval_multi", hs, n_models, FM_EVAL_MAX_MODELS);
+    int rc = g.check_handles(nullptr);
+    if (rc == FNN_OK) rc = eval_check(g, ids, true, y, N);
     if (rc != FNN_OK) return rc;
-    fm_handle* h0 = hs[0];
-    MHK(h0, hipSetDevice(h0->dev));
-    const hipStream_t st = h0->st;
+    fm_handle* h0 = g.h0;
     // the models of a group share one scratch allocation: as many as fit under the cap, one at the least
     size_t cap = (size_t)1 << 30;
     if (const char* e = getenv("FM_EVAL_SCRATCH_BYTES")) { const long long c = atoll(e); if (c >= 1) cap = (size_t)c; }
@@ -1717,10 +1612,9 @@ int fm_eval_multi(fm_handle* const* hs, int n_models, const int32_t* ids, const 
         if (G < 1) G = 1;
         while (G > 1 && eval_scratch_bytes(G, N) > cap) --G;
     }
-    std::vector<hipStream_t> others;
-    eval_other_streams(hs, n_models, others);
-    size_t slot = 0;
-    if (!h0->eval_host) { rc = eval_ring(h0, 0, &slot); if (rc != FNN_OK) return rc; }     // the events
+    rc = g.enter();
+    if (rc != FNN_OK) return rc;
+    const hipStream_t st = h0->st;
     char* scratch = nullptr;
     MHK(h0, hipMalloc((void**)&scratch, eval_scratch_bytes(G, N)));
     float* p_d = reinterpret_cast<float*>(scratch);
@@ -1733,8 +1627,7 @@ int fm_eval_multi(fm_handle* const* hs, int n_models, const int32_t* ids, const 
     std::vector<float*> pp(G);
     unsigned long long n_pos = 0;
     std::string bad, range;
-    rc = eval_join_in(h0, others);
-    auto groups = [&]() -> int {
+    auto groups = [&]() -> int {                                      // an error leaves the lambda: the scratch is still freed
         for (int g0 = 0; g0 < n_models; g0 += G) {
             const int g = n_models - g0 < G ? n_models - g0 : G;
             for (int m = 0; m < g; ++m) pp[m] = p_d + (size_t)m * (size_t)N;
@@ -1767,8 +1660,8 @@ int fm_eval_multi(fm_handle* const* hs, int n_models, const int32_t* ids, const 
         }
         return FNN_OK;
     };
-    if (rc == FNN_OK) rc = groups();
-    const int rj = eval_join_out(h0, others);                         // also after an error: the others stay ordered behind what ran
+    rc = groups();
+    const int rj = g.leave();
     if (rc != FNN_OK) hipStreamSynchronize(st);                       // nothing may still be using the scratch
     hipFree(scratch);
     if (rc != FNN_OK) return rc;
@@ -1777,7 +1670,7 @@ int fm_eval_multi(fm_handle* const* hs, int n_models, const int32_t* ids, const 
     if (!bad.empty()) msg += "predictions NaN or outside [0, 1] in model(s) " + bad;
     if (!range.empty()) msg += std::string(msg.empty() ? "" : "; ") + "feature id outside [-1, n_rows) in model(s) " + range;
     if (n_pos == 0 || (int64_t)n_pos == N) msg += std::string(msg.empty() ? "" : "; ") + "only one class present in y (roc_auc_score raises ValueError)";
-    if (!msg.empty()) MFAIL(h0, FNN_ERR_RANGE, "fm_eval_multi: " + msg);
+    if (!msg.empty()) return g.refuse(FNN_ERR_RANGE, msg);
     return FNN_OK;
 }
 

@@ -54,6 +54,21 @@ def test_library_exports_them_and_refuses_no_models(built):
         assert b'fm_predict_multi' in lib.fm_last_error(None)
 
 
+def test_each_refusal_keeps_its_text_and_a_second_try_is_refused_alike(built):
+    """Every refusal that needs no device, twice in a row: the same code and the same whole message, nothing half-made between."""
+    lib = _capi.load()
+    two = (C.c_void_p * 2)(None, None)
+    cases = [(None, 1, b'null hs'), (two, 0, b'n_models must be in [1, 1024]'), (two, 1025, b'n_models must be in [1, 1024]'),
+             (two, 2, b'model 0: null handle')]
+    for hs, n, text in cases:
+        for _ in range(2):
+            assert lib.fm_create(0, 0, 0, 0, None, C.byref(C.c_void_p())) == _capi.FNN_ERR_ARG      # some other message first
+            assert lib.fm_eval_multi(hs, n, None, None, None, 5, None, None, None, None) == _capi.FNN_ERR_ARG
+            assert lib.fm_last_error(None) == b'fm_eval_multi: ' + text
+            assert lib.fm_predict_multi(hs, n, None, None, 5, None) == _capi.FNN_ERR_ARG
+            assert lib.fm_last_error(None) == b'fm_predict_multi: ' + text
+
+
 def test_python_signatures():
     p = inspect.signature(fm_module.predict_many).parameters
     assert list(p) == ['models', 'ids', 'wts'] and p['wts'].default is None

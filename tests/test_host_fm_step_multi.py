@@ -56,6 +56,24 @@ def test_library_exports_it_and_refuses_no_models(built):
     assert b'null hs, lr or lambda' in refused(hs, 2, None, None, None, 64, None, lam, None, None, loss)
 
 
+def test_each_refusal_keeps_its_text_and_a_second_try_is_refused_alike(built):
+    """Every refusal that needs no device, twice in a row: the same code and the same whole message, nothing half-made between."""
+    lib = _capi.load()
+    lr, lam = (C.c_float * 2)(0.05, 0.05), (C.c_float * 2)(0.0, 0.0)
+    hs = (C.c_void_p * 2)(None, None)
+    cases = [((None, 2, None, None, None, 64, lr, lam, None, None, None), b'fm_train_step_multi: null hs, lr or lambda'),
+             ((hs, 2, None, None, None, 64, None, lam, None, None, None), b'fm_train_step_multi: null hs, lr or lambda'),
+             ((hs, 2, None, None, None, 64, lr, None, None, None, None), b'fm_train_step_multi: null hs, lr or lambda'),
+             ((hs, 0, None, None, None, 64, lr, lam, None, None, None), b'fm_train_step_multi: n_models must be in [1, 1024]'),
+             ((hs, 1025, None, None, None, 64, lr, lam, None, None, None), b'fm_train_step_multi: n_models must be in [1, 1024]'),
+             ((hs, 2, None, None, None, 64, lr, lam, None, None, None), b'fm_train_step_multi: model 0: null handle')]
+    for args, text in cases:
+        for _ in range(2):
+            assert lib.fm_create(0, 0, 0, 0, None, C.byref(C.c_void_p())) == _capi.FNN_ERR_ARG      # some other message first
+            assert lib.fm_train_step_multi(*args) == _capi.FNN_ERR_ARG
+            assert lib.fm_last_error(None) == text
+
+
 def test_python_signatures():
     p = inspect.signature(fm_module.train_step_many).parameters
     assert list(p) == ['models', 'ids', 'y', 'wts', 'want_p', 'want_loss']
