@@ -1531,15 +1531,60 @@ static __global__ __launch_bounds__(256) void k_ip_update_all(const IpUpdArgs u)
 
 }  // namespace
 
+namespace {
+
+// The A/B knobs of a handle, read from the environment ONCE, by ip_read_knobs in ipnn_create: a variable changed while a handle
+// lives does nothing to it.  The forms measured slower stay: the tests hold the forms against each other through these knobs.
+struct IpKnobs {
+    int side_stream = 1;                             // IPNN_SIDE_STREAM=0: everything in line on the handle's stream
+    int upd_side = 0;                                // IPNN_UPDATE_SIDE=1: the dense update at the end of the side chain (ip_run; measured slower)
+    int mask_side = 0;                               // IPNN_MASK_SIDE=1: the mask transposition on the side stream
+    int strip = 1;                                   // IPNN_STRIP=0: one GEMM launch per product instead of the strip kernels
+    int gemm_lds = 0;                                // IPNN_GEMM_LDS=1: LDS-staged k_gemm_lds for the wide products (measured equal to k_gemm_ft: both L2-bound)
+    int duo = 1, duo_min = DUO_MIN_BLOCKS;           // IPNN_STRIP_DUO=0: one workgroup per strip (StripDuo); IPNN_DUO_MIN: narrowest product a pair splits
+    int tail_split = 1;                              // IPNN_TAIL_SPLIT=0: the whole stack in one strip launch per direction (round 2's form)
+    int tail_fuse = 1;                               // IPNN_TAIL_FUSE: training steps run the forward and the backward tail in one launch
+    int tail_nf = 1, tail_nw = 16;                   // IPNN_TAIL_NF (1 / 2 / 4), IPNN_TAIL_NW (8 / 16): fragments per item and waves of the 16-example tail strips
+    int tail_w_lds = 0;                              // IPNN_TAIL_LDS=1: the tail's small weights in LDS behind the tiles (ip_tail_weights; measured slower)
+    int wide_nf = 2, wide_nw = 8;                    // IPNN_WIDE=nf:nw -- items (16-column fragments) and waves of the wide (pair) launches: 2:8, 4:8, 2:12
+    int strip_rot = 1, fwd_skip = 0;                 // IPNN_STRIP_ROT (0: every workgroup walks the blocks in the same order), IPNN_FWD_SKIP (diagnostics)
+    int strip_warm = 1;                              // IPNN_STRIP_WARM: the strip kernels touch their argument lines at the start (strip_warm_args)
+    int ipf_nt = 1024;                               // IPNN_IPF_NT: threads per workgroup of the gather + inner-product launch (512 / 1024)
+    bool wt = true;                                  // IPNN_WT=0: plain stores where the launches write through by default
+    int group_wgrad = 1, group_xcd = 1;              // IPNN_GROUP_WGRAD=0: one launch per weight-gradient product; IPNN_GROUP_XCD=0: tiles in launch order
+    int wgrad_want = 0;                              // IPNN_WGRAD_WANT: workgroups a weight-gradient product's split-K aims at (tuning knob)
+    int scat_form = SCAT1_HALF, scat2_form = SCAT2_WAVE, sort_merge4 = 1;       // FNN_SCAT1_FORM, FNN_SCAT2_FORM, FNN_SORT_RUNS (sparse_rows.hip.h)
+    int stamps = 0, stamp_sel = -1;                  // IPNN_STAMPS=1 / 2: time stamps of the wide / the tail strip launches; IPNN_STAMP_SEL=p: product p's last block
+};
+
+// main -> side: fork (start of the step), bwd (dz1 is there), wg (the weight gradients are).  side -> main: join (end of the side
+// chain), tab (its table / bias half), mask (the masks).  wg and tab: IPNN_UPDATE_SIDE=1 only; mask: IPNN_MASK_SIDE=1 only.  See IpSide.
+struct IpEvents { hipEvent_t fork = nullptr, bwd = nullptr, wg = nullptr, join = nullptr, tab = nullptr, mask = nullptr; };
+
+// What the handle's shape and knobs decide of a step: made once, at the end of ipnn_create (ip_make_plan).  What the batch length
+// adds is IpCall's (ip_form).  The cut between wide products and narrow tail: DESIGN.md section 4, round 3.
+struct IpPlan {
+    int maxD = 0; size_t strip_lds = 0;              // widest padded layer: the strips' tile width; two tiles of a strip
+    bool strip = false;                              // the strip kernels run the stack: IPNN_STRIP, and strip_lds <= 128 KiB
+    bool pairs = false;                              // ... on strips of 32 examples (bf16) with IPNN_STRIP_DUO: a batch whose pairs fit the chip takes them
+    int cut = 0, maxD2 = 0; size_t tail_lds = 0;     // products 1 .. cut are wide enough for pairs; widest layer from `cut` on, and the tail's two tiles
+    size_t off[IPNN_MAX_HIDDEN + 2] = {};            // element offset of product t's gradient in a slab (index t - 1); off[L + 1]: a slab's elements
+    int wg_order[IPNN_MAX_HIDDEN + 1] = {};          // the products by size, widest first: the order of the grouped weight-gradient launch
+    GemmGroupArgs group{};                           // that launch's arguments, all but nkt (the batch's k-steps)
+    IpUpdArgs upd{};                                 // k_ip_update_all's, all but lr, ngb and Ba
+    int mask_cols64[IPNN_MAX_HIDDEN + 1] = {};       // tiles of layer t's keep-mask per 64 examples (ip_mask_layout)
+};
+
+}  // namespace
+
 struct ipnn_handle {
     ipnn_cfg cfg{}; std::string err; int dev = 0; hipStream_t st = nullptr; bool own_stream = false;
     int F = 0, K = 0, L = 0, P = 0, CB = 0, Bmax = 0, ldT = 0; bool bf16 = false; int splitk = 8;   // splitk: slab capacity
+    IpKnobs kn; IpPlan plan;
     bool wide = false;                           // k >= 17: wide rows (k_ip_fwd_w / k_ip_bwd_w, k_ip_scatw1 / k_ip_scatw2), chosen at create
     int rw = SLOT;                               // row stride of the table and field stride of layer 0: SLOT, or rup(k, 4) when wide
     int* noshare = nullptr;                      // wide: [n_rows] zeros, the wide scatter's tag_shared (a row belongs to one field)
-    bool wide_attr = false;                      // the wide launches' dynamic-LDS opt-in is set
     bool many_fwd = false, many_bwd = false;     // 33 .. 64 fields of narrow rows: k_ip_fwd_m / k_ip_bwd_m (each chosen at create: ip_many_choice)
-    bool many_attr = false;                      // their dynamic-LDS opt-in is set
     unsigned short* ptab = nullptr;              // many: [P] pair n -> i | j << 8
     std::vector<int> sk;                         // split-K of each layer's weight-gradient product
     bool adam = false; int64_t adam_t = 0;       // Adam / FTRL: two state tensors beside every variable, dense row-gradient table; step count
@@ -1552,16 +1597,11 @@ struct ipnn_handle {
     std::vector<void*> a, aT, dl, dlT;                           // a[t] t=0..L ; dl[t] t=1..L+1 (index t-1)
     std::vector<uint8_t*> maskT;                                 // keep-masks of a step, transposed [Dp_t][ldT], t = 0..L
     uint8_t* mask0 = nullptr;                                    // drawn steps: layer 0's mask row-major [max_batch][d_0] (k_mask_draw -> IpArgs::mask); made by the first one
-    hipStream_t st2 = nullptr; hipEvent_t ev_fork = nullptr, ev_join = nullptr, ev_mask = nullptr, ev_bwd = nullptr;
-    // IPNN_UPDATE_SIDE=1 (default 0, measured slower -- DESIGN.md section 4): the dense update runs at the END of the side chain (behind ev_wg: the weight gradients) and the main
-    // stream does NOT wait for it at the end of the step: the next call's mask transposition and gather -- which read neither the dense
-    // weights nor the slabs -- run beside it, and the wait (ev_join) sits in front of the first product.  ev_tab: the side chain's table /
-    // bias half is done (in front of the next gather).  Every other entry point joins first (ip_join).
-    hipEvent_t ev_tab = nullptr, ev_wg = nullptr;
-    bool upd_side = false, tab_pending = false, upd_pending = false;
-    // side stream (IPNN_SIDE_STREAM=0: everything in line): the id grouping from the start of the step; the inner-product backward,
-    // the scalar b and the sparse-row update beside the weight gradients.  ev_fork / ev_bwd: main -> side; ev_join: side -> main at
-    // the end of the step (ev_mask only with IPNN_MASK_SIDE=1)
+    // side stream (IPNN_SIDE_STREAM=0: none, everything in line): the id grouping from the start of the step; the inner-product
+    // backward, the scalar b and the sparse-row update beside the weight gradients (IpSide).  With IPNN_UPDATE_SIDE=1 a step leaves
+    // its dense update running there: tab_pending / upd_pending say what the main stream has not waited for yet (ip_join)
+    hipStream_t st2 = nullptr; IpEvents ev;
+    bool tab_pending = false, upd_pending = false;
     float* emb = nullptr;                            // [ldT][F*rw] raw embeddings of the step's examples (forward -> backward)
     float *dz0 = nullptr, *gxp = nullptr, *gb_part = nullptr, *loss_t = nullptr, *loss_dev = nullptr, *slab = nullptr;
     int* ref0 = nullptr; int* err_flag = nullptr;
@@ -1569,29 +1609,9 @@ struct ipnn_handle {
     double* cpow1 = nullptr; bool key64 = true;
     size_t slab_stride = 0;
     bool prof = false;                               // HIP-event timing of the step's segments
-    long long* stamps = nullptr;                     // IPNN_STAMPS=1: [2][Ba/16][16] time stamps of the strip kernels
-    bool group_wgrad = true;                         // IPNN_GROUP_WGRAD=0: one launch per weight-gradient product
-    bool strip_attr = false;
-    int mask_side = 0;                               // IPNN_MASK_SIDE=1: the mask transposition on the side stream
-    int group_xcd = 1;                               // IPNN_GROUP_XCD=0: tiles in launch order
-    int strip_rot = 1, fwd_skip = 0;                 // IPNN_STRIP_ROT (0: every workgroup walks the blocks in the same order), IPNN_FWD_SKIP (diagnostics)
-    int wide_nf = 2, wide_nw = 8;                    // IPNN_WIDE=nf:nw -- items (16-column fragments) and waves of the wide (pair) launches: 2:8 (default), 4:8, 2:12
-    int scat_form = SCAT1_HALF;                      // FNN_SCAT1_FORM (scat1_blocks)
-    int scat2_form = SCAT2_WAVE;                     // FNN_SCAT2_FORM: level 2 of the narrow rows (scat2w_body; block: scat2_body)
-    int sort_merge4 = 1;                             // FNN_SORT_RUNS=4|16 (sortA_body; default 4)
-    bool wt = true;                                  // IPNN_WT=0: plain stores where the launches write through by default
-    int tail_fuse = 1;                               // IPNN_TAIL_FUSE: training steps run the forward and the backward tail in one launch
-    int tail_nf = 1;                                 // IPNN_TAIL_NF: 16-column fragments per item in the 16-example strips of the narrow tail (1 / 2 / 4)
-    int tail_nw = 16;                                // IPNN_TAIL_NW: waves per workgroup there (16 with IPNN_TAIL_NF=1 only: 128 registers per lane)
-    int ipf_nt = 1024;                               // IPNN_IPF_NT: threads per workgroup of the gather + inner-product launch (512 / 1024)
-    int strip_warm = 1;                              // IPNN_STRIP_WARM: the strip kernels touch their argument lines at the start (strip_warm_args)
-    bool strip = true;                               // IPNN_STRIP=0: one GEMM launch per product instead of the strip kernels
-    int duo = 1, duo_min = DUO_MIN_BLOCKS;           // IPNN_STRIP_DUO=0: one workgroup per strip (StripDuo); IPNN_DUO_MIN: narrowest product a pair splits
+    long long* stamps = nullptr;                     // IPNN_STAMPS: [2][Ba/16][16] time stamps of the strip kernels
     unsigned long long* duo_xch = nullptr; int* duo_flags = nullptr; int duo_epoch = 0; size_t duo_xch_wg = 0; int n_cu = 256;
-    bool stamp_tail = false;                         // IPNN_STAMPS=2: the stamps of the 16-example-strip launches instead of the wide ones
-    int tail_split = 1;                              // IPNN_TAIL_SPLIT=0: the whole stack in one strip launch per direction (round 2's form)
     bool duo_failed = false;                         // a pair gave up once: every later train step is refused until the handle is re-created
-    bool gemm_lds = false;                           // IPNN_GEMM_LDS=1: LDS-staged k_gemm_lds for the wide products (measured equal to k_gemm_ft: both L2-bound)
     std::map<std::string, std::vector<std::pair<hipEvent_t, hipEvent_t>>> prof_ev;
 };
 
@@ -1608,12 +1628,11 @@ struct IpProf {                                      // one segment of ip_run on
 
 #define IHK(h, expr) do { hipError_t e_ = (expr); if (e_ != hipSuccess) { (h)->err = std::string(#expr) + ": " + hipGetErrorString(e_); return FNN_ERR_HIP; } } while (0)
 #define IFAIL(h, code, msg) do { (h)->err = (msg); return (code); } while (0)
+#define IRC(expr) do { const int rc_ = (expr); if (rc_ != FNN_OK) return rc_; } while (0)
 
 namespace {
 
 size_t ts(const ipnn_handle* h) { return h->bf16 ? 2 : 4; }
-// examples per workgroup of the handle's inner-product backward: the grain of gb_part
-int ip_bwd_ex(const ipnn_handle* h) { return h->wide ? IPW_EX : h->many_bwd ? IPM_BEX : 16; }
 
 template <typename T> void ip_refresh(ipnn_handle* h, int t, const float* slab, float lr) {      // t = 1..L+1
     const int Din = h->Dp[t - 1], Dout = h->Dp[t];
@@ -1622,486 +1641,670 @@ template <typename T> void ip_refresh(ipnn_handle* h, int t, const float* slab, 
                        h->slab_stride, lr, Din, Dout, (T*)h->wf[t - 1], (T*)h->wb[t - 1]);
 }
 
-inline int maxD2x(const int* Dp, int n) { int m = 0; for (int t = 0; t <= n; ++t) m = std::max(m, Dp[t]); return m; }
+inline int env_int(const char* name, int dflt) { const char* e = getenv(name); return e ? atoi(e) : dflt; }
 
-// the main stream waits for what the previous step left running on the side stream (see upd_side)
-static int ip_join_table(ipnn_handle* h)
+IpKnobs ip_read_knobs()
 {
-    if (h->tab_pending) { IHK(h, hipStreamWaitEvent(h->st, h->ev_tab, 0)); h->tab_pending = false; }
+    IpKnobs k;
+    const struct { const char* name; int* v; bool flag; } plain[] = {     // flag: 0 / 1, whatever number is given
+        {"IPNN_SIDE_STREAM", &k.side_stream, true}, {"IPNN_UPDATE_SIDE", &k.upd_side, true}, {"IPNN_MASK_SIDE", &k.mask_side, false},
+        {"IPNN_STRIP", &k.strip, true}, {"IPNN_GEMM_LDS", &k.gemm_lds, true}, {"IPNN_STRIP_DUO", &k.duo, false}, {"IPNN_DUO_MIN", &k.duo_min, false},
+        {"IPNN_TAIL_SPLIT", &k.tail_split, false}, {"IPNN_TAIL_FUSE", &k.tail_fuse, true}, {"IPNN_TAIL_LDS", &k.tail_w_lds, false},
+        {"IPNN_STRIP_ROT", &k.strip_rot, false}, {"IPNN_FWD_SKIP", &k.fwd_skip, false}, {"IPNN_STRIP_WARM", &k.strip_warm, false},
+        {"IPNN_GROUP_WGRAD", &k.group_wgrad, true}, {"IPNN_GROUP_XCD", &k.group_xcd, false}, {"IPNN_STAMP_SEL", &k.stamp_sel, false}};
+    for (const auto& e : plain) { *e.v = env_int(e.name, *e.v); if (e.flag) *e.v = *e.v != 0; }
+    k.wt = env_int("IPNN_WT", 1) != 0;
+    k.duo_min = std::max(2, k.duo_min);
+    { const int v = env_int("IPNN_TAIL_NF", 1); if (v == 1 || v == 2 || v == 4) k.tail_nf = v; }
+    k.tail_nw = env_int("IPNN_TAIL_NW", 16) == 16 ? 16 : 8;
+    k.ipf_nt = env_int("IPNN_IPF_NT", 1024) == 1024 ? 1024 : 512;
+    int nf = 4, nw = 8;
+    if (getenv("IPNN_WIDE") && sscanf(getenv("IPNN_WIDE"), "%d:%d", &nf, &nw) == 2 && ((nf == 2 && (nw == 8 || nw == 12)) || (nf == 4 && nw == 8))) { k.wide_nf = nf; k.wide_nw = nw; }
+    // one launch per product wants ~256 workgroups each; the grouped launch runs all products side by side and is
+    // served best by half of that (measured: 0.353 -> 0.345 ms/step; a quarter: 0.355)
+    k.wgrad_want = getenv("IPNN_WGRAD_WANT") ? std::max(16, env_int("IPNN_WGRAD_WANT", 0)) : k.group_wgrad ? 144 : 288;
+    k.scat_form = scat1_form_env(); k.scat2_form = scat2_form_env(); k.sort_merge4 = sort_merge4_env(1);
+    if (getenv("IPNN_STAMPS")) k.stamps = env_int("IPNN_STAMPS", 0) == 2 ? 2 : 1;
+    return k;
+}
+
+// The main stream waits for what the previous step left running on the side stream (IPNN_UPDATE_SIDE=1): its sparse rows and bias
+// (read by the gather) ...
+int ip_join_table(ipnn_handle* h)
+{
+    if (h->tab_pending) { IHK(h, hipStreamWaitEvent(h->st, h->ev.tab, 0)); h->tab_pending = false; }
     return FNN_OK;
 }
-static int ip_join(ipnn_handle* h)
+// ... and its dense update (read by the first product, and by every other entry point)
+int ip_join(ipnn_handle* h)
 {
-    const int rc = ip_join_table(h);
-    if (rc != FNN_OK) return rc;
-    if (h->upd_pending) { IHK(h, hipStreamWaitEvent(h->st, h->ev_join, 0)); h->upd_pending = false; }
+    IRC(ip_join_table(h));
+    if (h->upd_pending) { IHK(h, hipStreamWaitEvent(h->st, h->ev.join, 0)); h->upd_pending = false; }
     return FNN_OK;
 }
 
-// the wide launches' arguments (k_ip_fwd_w / k_ip_bwd_w) and their dynamic-LDS opt-in: one fixed ceiling for every handle (the
-// attribute belongs to the kernel, not to the handle; the widest shape takes 132 / 147 KB)
+// The side stream of one step, as a scope.  fork: the side stream waits for what the main stream holds so far; signal: an event
+// at the side stream's end; wait: the main stream waits for it.  Without a side stream (IPNN_SIDE_STREAM=0) `s` is the main stream
+// and all three do nothing.  A step that ends well calls settle(): its last wait is enqueued, or tab_pending / upd_pending hand it
+// to the next call.  Any other exit after the first fork -- every error return of ip_run -- joins here: the main stream waits for
+// whatever the step put on the side stream, so that no later call on the handle's stream races with it.
+struct IpSide {
+    ipnn_handle* const h; hipStream_t const s; bool open = false;
+    explicit IpSide(ipnn_handle* h_) : h(h_), s(h_->st2 ? h_->st2 : h_->st) {}
+    IpSide(const IpSide&) = delete;
+    bool on() const { return h->st2 != nullptr; }
+    int fork(hipEvent_t ev)
+    {
+        if (!on()) return FNN_OK;
+        IHK(h, hipEventRecord(ev, h->st));
+        open = true;
+        IHK(h, hipStreamWaitEvent(h->st2, ev, 0));
+        return FNN_OK;
+    }
+    int signal(hipEvent_t ev) { if (on()) IHK(h, hipEventRecord(ev, h->st2)); return FNN_OK; }
+    int wait(hipEvent_t ev) { if (on()) IHK(h, hipStreamWaitEvent(h->st, ev, 0)); return FNN_OK; }
+    void settle() { open = false; }
+    ~IpSide() { if (open && hipEventRecord(h->ev.join, h->st2) == hipSuccess) hipStreamWaitEvent(h->st, h->ev.join, 0); }
+};
+
+// ---------------------------------------------------------------------------------------------------------------- kernel selectors
+// A launchable kernel: what a selector returns.  The selectors below are the only places that name an instantiation of the strip
+// and gather kernels; the launch sites call them, and so does the dynamic-LDS opt-in (ip_opt_in), over every form the knobs can
+// select: what can be launched has its attribute.
+struct IpKernel { const void* fn; int threads; };
+#define IP_K(threads, ...) IpKernel{reinterpret_cast<const void*>(&__VA_ARGS__), (threads)}
+
+// args: the kernel's parameters, in order and of exactly its parameter types
+template <typename... A> hipError_t ip_launch(const IpKernel& k, int grid, size_t lds, hipStream_t s, const A&... args)
+{
+    void* p[] = {const_cast<void*>(static_cast<const void*>(&args))...};
+    return hipLaunchKernel(k.fn, dim3((unsigned)grid), dim3((unsigned)k.threads), p, lds, s);
+}
+
+// The strip kernels of one direction by (rt: rows of 16 examples per strip, nf: 16-column fragments per item, nw: waves).  Built:
+// 32-example strips (bf16) as 4:8 -- the whole stack in one launch, and IPNN_WIDE=4:8 --, 2:8 and 2:12 (half-block items; measured:
+// forward 59.8 -> 56.4 us at 2:8); 16-example strips (every f32 launch, every tail) as 4:8, 2:8, 1:8 and 1:16.  What is not built
+// takes nf:nw = 4:8, and f32 has no 32-example strips (it ignores IPNN_WIDE).
+template <typename T> IpKernel ip_strip_sel(bool bwd, int rt, int nf, int nw)
+{
+#define IP_STRIP(RT_, NF, NW) (bwd ? IP_K(64 * NW, k_ip_strip_bwd<T, RT_, NF, NW>) : IP_K(64 * NW, k_ip_strip_fwd<T, RT_, NF, NW>))
+    if constexpr (sizeof(T) == 2) if (rt == 2) {
+        if (nf == 2 && nw == 12) return IP_STRIP(2, 2, 12);
+        if (nf == 2 && nw == 8) return IP_STRIP(2, 2, 8);
+        return IP_STRIP(2, 4, STRIP_NW);
+    }
+    if (nf == 1 && nw == 16) return IP_STRIP(1, 1, 16);
+    if (nf == 1) return IP_STRIP(1, 1, STRIP_NW);
+    if (nf == 2) return IP_STRIP(1, 2, STRIP_NW);
+    return IP_STRIP(1, 4, STRIP_NW);
+#undef IP_STRIP
+}
+// both passes' tails in one launch: the fused form's only instantiation (1 fragment per item on 16 waves)
+template <typename T> IpKernel ip_strip_tail_sel() { return IP_K(64 * 16, k_ip_strip_tail<T, 1, 16>); }
+
+// Which inner-product (gather) kernels a handle runs, per direction: wide rows (k >= 17), many fields (ip_many_choice), or the
+// 16-example pair k_ip_fwd / k_ip_bwd
+enum IpRows { IP_NARROW, IP_WIDE, IP_MANY };
+IpRows ip_fwd_rows(const ipnn_handle* h) { return h->wide ? IP_WIDE : h->many_fwd ? IP_MANY : IP_NARROW; }
+IpRows ip_bwd_rows(const ipnn_handle* h) { return h->wide ? IP_WIDE : h->many_bwd ? IP_MANY : IP_NARROW; }
+// examples per workgroup of the handle's inner-product backward: the grain of gb_part
+int ip_bwd_ex(const ipnn_handle* h) { return h->wide ? IPW_EX : h->many_bwd ? IPM_BEX : 16; }
+// ceiling of their dynamic LDS: one per kernel family, for every handle (the attribute belongs to the kernel, not to the handle; the
+// widest wide shape takes 132 / 147 KB, the 16-example tile up to 160 KiB: ip_many_choice)
+int ip_rows_lds_kib(IpRows r) { return r == IP_MANY ? 64 : 160; }
+
+// wv: value weights are given.  A compile-time variant, so that the unweighted path carries neither the loads nor a branch.
+template <typename T> IpKernel ip_gather_fwd_sel(IpRows rows, bool wv, int nt)
+{
+    if (rows == IP_WIDE) return wv ? IP_K(256, k_ip_fwd_w<T, true>) : IP_K(256, k_ip_fwd_w<T>);
+    if (rows == IP_MANY) return wv ? IP_K(256, k_ip_fwd_m<T, true>) : IP_K(256, k_ip_fwd_m<T>);
+    if (nt == 1024) return wv ? IP_K(1024, k_ip_fwd<T, 1024, true>) : IP_K(1024, k_ip_fwd<T, 1024>);
+    return wv ? IP_K(IPF_NT, k_ip_fwd<T, IPF_NT, true>) : IP_K(IPF_NT, k_ip_fwd<T>);
+}
+IpKernel ip_gather_bwd_sel(IpRows rows, bool wv)
+{
+    if (rows == IP_WIDE) return wv ? IP_K(256, k_ip_bwd_w<true>) : IP_K(256, k_ip_bwd_w<false>);
+    if (rows == IP_MANY) return wv ? IP_K(256, k_ip_bwd_m<true>) : IP_K(256, k_ip_bwd_m<false>);
+    return wv ? IP_K(256, k_ip_bwd<true>) : IP_K(256, k_ip_bwd<false>);
+}
+
+// > 64 KiB of dynamic LDS needs the opt-in, once per device: every kernel a selector can return for a form the knobs can name gets
+// its family's ceiling -- 128 KiB for the 32-example strips, 160 KiB for the 16-example ones and the fused tail, ip_rows_lds_kib for
+// the gathers.  (A form named twice is set twice: the same value.)
+template <typename T> int ip_opt_in(ipnn_handle* h)
+{
+    constexpr int RT = sizeof(T) == 2 ? 2 : 1;
+    auto set = [](const IpKernel& k, int kib) { return hipFuncSetAttribute(k.fn, hipFuncAttributeMaxDynamicSharedMemorySize, kib * 1024); };
+    for (int bwd = 0; bwd < 2; ++bwd)
+        for (int rt : {RT, 1}) for (int nf : {1, 2, 4}) for (int nw : {8, 12, 16})
+            IHK(h, set(ip_strip_sel<T>(bwd != 0, rt, nf, nw), rt == 2 ? 128 : 160));
+    IHK(h, set(ip_strip_tail_sel<T>(), 160));
+    for (IpRows r : {IP_NARROW, IP_WIDE, IP_MANY}) for (int wv = 0; wv < 2; ++wv) {
+        for (int nt : {512, 1024}) IHK(h, set(ip_gather_fwd_sel<T>(r, wv != 0, nt), ip_rows_lds_kib(r)));
+        IHK(h, set(ip_gather_bwd_sel(r, wv != 0), ip_rows_lds_kib(r)));
+    }
+    return FNN_OK;
+}
+
+// ------------------------------------------------------------------------------------------------------------------ the step plan
 // Which inner-product kernels a narrow handle runs.  Up to 32 fields: always the 16-example pair (k_ip_fwd / k_ip_bwd).  Above,
 // each direction has its own crossover, both measured: the 4-example backward wins from 33 fields on
 // (IPM_BWD_MIN_FIELDS; IPNN_MANY_MIN is the A/B knob), the 16-example forward wins wherever its tile fits the 160 KiB of LDS,
 // so the 8-example forward takes over where it does not: 46 fields and more with pairs (IPM_FWD_MIN_FIELDS = 65 means "by LDS
 // only"; IPNN_MANY_FWD_MIN is the A/B knob).  Neither knob goes below 33.
 constexpr int IPM_BWD_MIN_FIELDS = 33, IPM_FWD_MIN_FIELDS = 65;
-inline size_t ip16_lds(int F, int Dp0) { return (size_t)16 * (F * (SLOT + 1) + Dp0) * sizeof(float); }
+inline size_t ip16_lds(int F, int Dp0) { return (size_t)16 * (F * (SLOT + 1) + Dp0) * sizeof(float); }      // k_ip_fwd pads its embedding tile
 inline bool ip_many_choice(int F, int Dp0, int dflt, const char* knob)
 {
     if (F <= 32) return false;
-    int mn = dflt;
-    if (const char* e = getenv(knob)) mn = std::max(33, atoi(e));
+    const int mn = getenv(knob) ? std::max(33, env_int(knob, 0)) : dflt;
     return F >= mn || ip16_lds(F, Dp0) > (size_t)160 * 1024;
 }
-IpManyArgs ip_many_args(const ipnn_handle* h, const int32_t* ids, const float* wts, int B, const uint8_t* mask0, float inv_keep)
+
+template <typename T> void ip_make_plan(ipnn_handle* h)
 {
-    return IpManyArgs{h->P, ids, B, h->F, h->K, h->table16, h->n_rows, h->b, mask0, h->d[0], inv_keep, h->cfg.act, h->Dp[0], h->ldT,
-                      h->err_flag, h->ptab, h->wt, (unsigned)((size_t)h->ldT * h->Dp[0] * ts(h)), (unsigned)((size_t)h->ldT * h->F * SLOT * 4), wts};
+    IpPlan& p = h->plan;
+    const IpKnobs& kn = h->kn;
+    const int L = h->L;
+    constexpr int KS = Traits<T>::KS;
+    constexpr int RT = sizeof(T) == 2 ? 2 : 1;                   // strip = 32 (bf16) / 16 (f32) examples: two LDS tiles of 64 KiB at 1024 units
+    for (int t = 0; t <= L + 1; ++t) p.maxD = std::max(p.maxD, h->Dp[t]);
+    p.strip_lds = (size_t)2 * RT * 16 * p.maxD * sizeof(T);
+    p.strip = kn.strip && p.strip_lds <= 128 * 1024;
+    p.pairs = p.strip && kn.duo && RT == 2;
+    p.cut = L;
+    while (p.cut >= 1 && h->Dp[p.cut] / 64 < kn.duo_min) --p.cut;
+    for (int t = p.cut; t <= L + 1; ++t) p.maxD2 = std::max(p.maxD2, h->Dp[t]);
+    p.tail_lds = (size_t)2 * 16 * p.maxD2 * sizeof(T);
+    for (int t = 0; t <= L; ++t) p.mask_cols64[t] = h->Dp[t] / 64;
+    for (int t = 1; t <= L + 1; ++t) { p.off[t] = p.off[t - 1] + (size_t)h->Dp[t - 1] * h->Dp[t]; p.wg_order[t - 1] = t; }
+    std::sort(p.wg_order, p.wg_order + L + 1, [&](int x, int y) { return (size_t)h->Dp[x - 1] * h->Dp[x] > (size_t)h->Dp[y - 1] * h->Dp[y]; });
+    if (L + 1 <= GEMM_GROUP_MAX) {   // ONE launch for the whole stack: 128 x 128 tiles of every product, widest first
+        GemmGroupArgs& g = p.group;
+        int wg = 0;
+        for (int i = 0; i <= L; ++i) {
+            const int t = p.wg_order[i], M = h->Dp[t - 1], N = h->Dp[t];
+            GemmGroupProb& pr = g.p[i];
+            pr.A = h->aT[t - 1]; pr.B = h->dlT[t - 1]; pr.out = h->slab + p.off[t - 1]; pr.mt16 = M / 16; pr.nt16 = N / 16;
+            pr.nkt_all = h->ldT / KS; pr.nkt = 0; pr.ldo = N; pr.gx = (M + 127) / 128; pr.gy = (N + 127) / 128;
+            g.wg0[i] = wg; wg += pr.gx * pr.gy * h->sk[t - 1];
+        }
+        g.wg0[L + 1] = wg; g.n = L + 1; g.zstride = h->slab_stride; g.xcd = kn.group_xcd; g.wt = kn.wt;
+    }
+    IpUpdArgs& u = p.upd;
+    u.wt = kn.wt;
+    for (int t = 1; t <= L + 1; ++t) {
+        u.W[t - 1] = h->W[t - 1]; u.wf[t - 1] = h->wf[t - 1]; u.wb[t - 1] = h->wb[t - 1]; u.off[t - 1] = p.off[t - 1];
+        u.Din[t - 1] = h->Dp[t - 1]; u.Dout[t - 1] = h->Dp[t]; u.sk[t - 1] = h->sk[t - 1];
+    }
+    u.n = L + 1; u.off[L + 1] = p.off[L + 1]; u.slab = h->slab; u.zstride = h->slab_stride;
+    u.adam = h->adam ? (int)h->cfg.optimizer : 0; u.beta1 = h->cfg.adam_beta1; u.beta2 = h->cfg.adam_beta2; u.eps = h->cfg.adam_eps; u.bmv = h->bmv;
+    if (h->adam) for (int t = 0; t <= L; ++t) { u.Wm[t] = h->Wm[t]; u.Wv[t] = h->Wv[t]; }
+    u.b = h->b; u.gb_part = h->gb_part; u.loss_t = h->loss_t; u.loss_sum = h->loss_dev; u.err = h->err_flag;
 }
-int ip_many_attr(ipnn_handle* h)
+
+// Adam / FTRL start over: zero moments beside every dense layer and b, FTRL's accumulators at 0.1 (initial_accumulator_value), step
+// count 0.  (The table's state is ipnn_set_table's: it is sized by the table.)
+int ip_reset_dense_state(ipnn_handle* h)
 {
-    if (h->many_attr) return FNN_OK;
-    IHK(h, hipFuncSetAttribute(reinterpret_cast<const void*>(&k_ip_fwd_m<float>), hipFuncAttributeMaxDynamicSharedMemorySize, 64 * 1024));
-    IHK(h, hipFuncSetAttribute(reinterpret_cast<const void*>(&k_ip_fwd_m<bf16_t>), hipFuncAttributeMaxDynamicSharedMemorySize, 64 * 1024));
-    IHK(h, hipFuncSetAttribute(reinterpret_cast<const void*>(&k_ip_bwd_m<false>), hipFuncAttributeMaxDynamicSharedMemorySize, 64 * 1024));
-    IHK(h, hipFuncSetAttribute(reinterpret_cast<const void*>(&k_ip_fwd_m<float, true>), hipFuncAttributeMaxDynamicSharedMemorySize, 64 * 1024));
-    IHK(h, hipFuncSetAttribute(reinterpret_cast<const void*>(&k_ip_fwd_m<bf16_t, true>), hipFuncAttributeMaxDynamicSharedMemorySize, 64 * 1024));
-    IHK(h, hipFuncSetAttribute(reinterpret_cast<const void*>(&k_ip_bwd_m<true>), hipFuncAttributeMaxDynamicSharedMemorySize, 64 * 1024));
-    h->many_attr = true;
-    return FNN_OK;
-}
-IpWideArgs ip_wide_args(const ipnn_handle* h, const int32_t* ids, const float* wts, int B, const uint8_t* mask0, float inv_keep)
-{
-    return IpWideArgs{h->P, ids, B, h->F, h->K, h->rw, h->table16, h->n_rows, h->b, mask0, h->d[0], inv_keep, h->cfg.act, h->Dp[0],
-                      h->ldT, h->err_flag, h->wt, (unsigned)((size_t)h->ldT * h->Dp[0] * ts(h)), (unsigned)((size_t)h->ldT * h->F * h->rw * 4), wts};
-}
-int ip_wide_attr(ipnn_handle* h)
-{
-    if (h->wide_attr) return FNN_OK;
-    IHK(h, hipFuncSetAttribute(reinterpret_cast<const void*>(&k_ip_fwd_w<float>), hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024));
-    IHK(h, hipFuncSetAttribute(reinterpret_cast<const void*>(&k_ip_fwd_w<bf16_t>), hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024));
-    IHK(h, hipFuncSetAttribute(reinterpret_cast<const void*>(&k_ip_bwd_w<false>), hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024));
-    IHK(h, hipFuncSetAttribute(reinterpret_cast<const void*>(&k_ip_fwd_w<float, true>), hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024));
-    IHK(h, hipFuncSetAttribute(reinterpret_cast<const void*>(&k_ip_fwd_w<bf16_t, true>), hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024));
-    IHK(h, hipFuncSetAttribute(reinterpret_cast<const void*>(&k_ip_bwd_w<true>), hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024));
-    h->wide_attr = true;
+    if (!h->adam) return FNN_OK;
+    for (int t = 1; t <= h->L + 1; ++t) {
+        const size_t n = (size_t)h->Dp[t - 1] * h->Dp[t];
+        IHK(h, hipMemsetAsync(h->Wm[t - 1], 0, n * 4, h->st)); IHK(h, hipMemsetAsync(h->Wv[t - 1], 0, n * 4, h->st));
+        if (h->ftrl) hipLaunchKernelGGL(k_fill_f32, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, h->st, h->Wm[t - 1], n, 0.1f);
+    }
+    IHK(h, hipMemsetAsync(h->bmv, 0, 8, h->st));
+    if (h->ftrl) hipLaunchKernelGGL(k_fill_f32, dim3(1), dim3(64), 0, h->st, h->bmv, (size_t)1, 0.1f);
+    h->adam_t = 0;
     return FNN_OK;
 }
 
-// wts: value weights [B][F] (device) or NULL.  NULL launches the kernels as they were before the weights existed (WV = false);
-// a pointer launches their WV instantiations -- a compile-time variant, so that the unweighted path carries neither the loads
-// nor a branch.
-// the launch arguments of k_mask_draw for one (seed, step): the tiles of every layer (k_mask_T's grid), the key, the counter's
-// step words and the threshold of the handle's keep_prob; the targets (dstT / dstR) are the caller's to fill in
+// ------------------------------------------------------------------------------------------------------------------- one call
+// masks: the caller's keep-masks (ipnn_train_step_w), or draw: the (seed, step) the library draws them from (ipnn_train_step_drawn);
+// neither: no dropout.  wts: value weights [B][F] (device) or NULL: the kernels as they were before the weights existed.
 struct IpDraw { uint64_t seed, step; };
+struct IpCall {
+    const int32_t* ids; const float* wts; const float* y; int B; const uint8_t* const* masks; const IpDraw* draw;
+    float* logits_out; float* p_out; bool train;
+    // what the batch length makes of the plan (ip_form)
+    int Ba = 0, nstrips = 0; bool duo = false, tsplit = false, fuse_tail = false;
+    bool drop = false; const uint8_t* mask0 = nullptr;      // dropout at all; layer 0's mask, row-major (the inner-product forward)
+};
+
+void ip_form(const ipnn_handle* h, IpCall& c)
+{
+    const IpPlan& p = h->plan;
+    const IpKnobs& kn = h->kn;
+    c.Ba = rup(c.B, 256);
+    c.nstrips = c.Ba / (16 * (h->bf16 ? 2 : 1));
+    // two workgroups per strip (StripDuo) where the pairs fit the chip at one workgroup per CU: both halves of a pair must be
+    // resident to swap (bf16 strips of 32 examples: 256 workgroups at batch 4096)
+    c.duo = p.pairs && 2 * c.nstrips <= h->n_cu;
+    c.tsplit = p.strip && c.duo && kn.tail_split && p.cut >= 1 && p.cut < h->L;
+    // training steps: the forward tail rides in the backward tail's launch (k_ip_strip_tail; IPNN_TAIL_FUSE=0: two launches)
+    c.fuse_tail = c.tsplit && c.train && kn.tail_fuse && kn.tail_nf == 1 && kn.tail_nw == 16 && !kn.tail_w_lds;
+    c.drop = c.train && (c.masks || c.draw);
+    c.mask0 = !c.drop ? nullptr : c.draw ? h->mask0 : c.masks[0];
+}
+
+// The tiles of every layer's keep-mask, 64 examples x 64 columns each, layer after layer: the grid of k_mask_T and k_mask_draw and
+// the fields their argument structs share.  Returns the number of tiles.
+template <typename A> int ip_mask_layout(const ipnn_handle* h, int B, A& a)
+{
+    const int Ba = rup(B, 256);
+    int tiles = 0;
+    for (int t = 0; t <= h->L; ++t) { a.d[t] = h->d[t]; a.Dp[t] = h->Dp[t]; a.tile0[t] = tiles; tiles += (Ba / 64) * h->plan.mask_cols64[t]; }
+    a.tile0[h->L + 1] = tiles; a.n = h->L + 1; a.ref0 = h->ref0; a.B = B; a.Ba = Ba; a.ldT = h->ldT; a.wt = h->kn.wt;
+    return tiles;
+}
+// the launch arguments of k_mask_draw for one (seed, step): the layout, the key, the counter's step words and the threshold of the
+// handle's keep_prob; the targets (dstT / dstR) are the caller's to fill in
 MaskDrawArgs ip_draw_args(const ipnn_handle* h, const IpDraw& dr, int B, int* tiles_out)
 {
     MaskDrawArgs a{};
-    const int Ba = rup(B, 256);
-    int tiles = 0;
-    for (int t = 0; t <= h->L; ++t) {
-        a.d[t] = h->d[t]; a.Dp[t] = h->Dp[t]; a.bytesT[t] = (unsigned)((size_t)h->ldT * h->Dp[t]); a.tile0[t] = tiles;
-        tiles += (Ba / 64) * (h->Dp[t] / 64);
-    }
-    a.tile0[h->L + 1] = tiles; a.n = h->L + 1; a.ref0 = h->ref0; a.B = B; a.Ba = Ba; a.ldT = h->ldT; a.wt = h->wt;
+    *tiles_out = ip_mask_layout(h, B, a);
+    for (int t = 0; t <= h->L; ++t) a.bytesT[t] = (unsigned)((size_t)h->ldT * h->Dp[t]);
     a.key0 = (unsigned)dr.seed; a.key1 = (unsigned)(dr.seed >> 32); a.step0 = (unsigned)dr.step; a.step1 = (unsigned)(dr.step >> 32);
     const double thr = std::floor((double)h->cfg.keep_prob * 4294967296.0);
     a.all = h->cfg.keep_prob >= 1.0f;
     a.thr = thr >= 4294967295.0 ? 0xffffffffu : (unsigned)thr;
-    *tiles_out = tiles;
     return a;
 }
 
-// masks: the caller's keep-masks (ipnn_train_step_w), or draw: the (seed, step) the library draws them from (ipnn_train_step_drawn);
-// neither: no dropout.
-template <typename T>
-int ip_run(ipnn_handle* h, const int32_t* ids, const float* wts, const float* y, int B, const uint8_t* const* masks, float* logits_out,
-           float* p_out, bool train, const IpDraw* draw = nullptr)
+// The step's keep-masks where the launches read them: the library's own draw (transposed, and layer 0's row-major, written by one
+// launch that reads nothing), or the caller's, transposed, tiled, zero padded and slot-ordered for layer 0.
+// On the MAIN stream by default: a cross-stream event on the way into the first strip kernel costs more (10-20 us of wait
+// resolution, measured on the kernel trace) than the 10 us the transposition takes in line (IPNN_MASK_SIDE=1; DESIGN.md section 4
+// also tells of transposing the NEXT step's masks ahead: not kept).
+int ip_masks(ipnn_handle* h, const IpCall& c, IpSide& side)
 {
-    const int Ba = rup(B, 256), L = h->L, F = h->F, ldT = h->ldT;
-    const float keep = h->cfg.keep_prob, inv_keep = 1.0f / keep;
-    const size_t lds_ip = ip16_lds(F, h->Dp[0]);                 // k_ip_fwd pads its embedding tile
-    const bool drop = train && (masks || draw);
-    if (drop && !draw) for (int t = 0; t <= L; ++t) if (!masks[t]) IFAIL(h, FNN_ERR_ARG, "masks: null entry");
-    const uint8_t* const mask0 = !drop ? nullptr : draw ? h->mask0 : masks[0];      // layer 0's mask, row-major (the inner-product forward)
-    { const int jrc = ip_join_table(h); if (jrc != FNN_OK) return jrc; }      // the previous step's sparse rows / bias (read by the gather)
-    if (train) {
-        // beside the stack, on the side stream: the grouping of the batch's ids for the sparse-row update (needed by the scatter);
-        // the transposed keep-masks (needed from the first product on) go first on the main stream
-        hipStream_t ss = h->st2 ? h->st2 : h->st;
-        if (h->st2) { IHK(h, hipEventRecord(h->ev_fork, h->st)); IHK(h, hipStreamWaitEvent(h->st2, h->ev_fork, 0)); }
-        if (draw) {   // the library's own draw: the same transposed masks, and layer 0's row-major, written by one launch that reads nothing
-            int tiles = 0;
-            MaskDrawArgs da = ip_draw_args(h, *draw, B, &tiles);
-            for (int t = 0; t <= L; ++t) da.dstT[t] = h->maskT[t];
-            da.dstR[0] = h->mask0;
-            IpProf pm(h, "mask_t", h->mask_side ? ss : h->st);
-            hipLaunchKernelGGL(k_mask_draw, dim3(tiles), dim3(256), 0, h->mask_side ? ss : h->st, da);
-            if (h->st2 && h->mask_side) IHK(h, hipEventRecord(h->ev_mask, h->st2));
-        } else if (drop) {   // keep-masks of all layers -> transposed, tiled, zero padded, slot-ordered for layer 0
-            MaskTArgs ma{};
-            int tiles = 0;
-            for (int t = 0; t <= L; ++t) {
-                ma.src[t] = masks[t]; ma.dst[t] = h->maskT[t]; ma.d[t] = h->d[t]; ma.Dp[t] = h->Dp[t]; ma.tile0[t] = tiles;
-                tiles += (Ba / 64) * (h->Dp[t] / 64);
-            }
-            ma.tile0[L + 1] = tiles; ma.n = L + 1; ma.ref0 = h->ref0; ma.B = B; ma.Ba = Ba; ma.ldT = ldT; ma.wt = h->wt;
-            // on the MAIN stream by default: a cross-stream event on the way into the first strip kernel costs more (10-20 us of
-            // wait resolution, measured on the kernel trace) than the 10 us the transposition takes in line.  (Round 3 also tried
-            // transposing the NEXT step's masks ahead, on the side stream -- beside the strips: 0.265 -> 0.270 ms per step, at the end
-            // of the side chain beside the weight gradients: 0.286 -> 0.302 on a slower box: every kernel of this step is bound by
-            // the CUs' ports or the L2, and a co-running launch takes what it saves.  Not kept.)
-            IpProf pm(h, "mask_t", h->mask_side ? ss : h->st);
-            hipLaunchKernelGGL(k_mask_T, dim3(tiles), dim3(256), 0, h->mask_side ? ss : h->st, ma);
-            if (h->st2 && h->mask_side) IHK(h, hipEventRecord(h->ev_mask, h->st2));
-        }
-        SortArgs so{ids, B, F, h->n_rows, h->rg.rec, h->rg.owner_cnt, F, h->skeys};
-        so.merge4 = h->sort_merge4;
-        launch_sort(ss, h->key64, so);
-    }
-    if (draw && h->st2 && h->mask_side) IHK(h, hipStreamWaitEvent(h->st, h->ev_mask, 0));     // the inner-product forward reads the drawn mask0
-    if (h->wide) {
-        IpProf ps(h, "ip_fwd");
-        const int rc = ip_wide_attr(h);
-        if (rc != FNN_OK) return rc;
-        const IpWideArgs wa = ip_wide_args(h, ids, wts, B, mask0, drop ? inv_keep : 1.0f);
-        if (wts) hipLaunchKernelGGL((k_ip_fwd_w<T, true>), dim3(Ba / IPW_EX), dim3(256), ipw_fwd_lds(F, h->rw), h->st, wa, (T*)h->a[0], (T*)h->aT[0],
-                                    train ? h->emb : nullptr);
-        else hipLaunchKernelGGL((k_ip_fwd_w<T>), dim3(Ba / IPW_EX), dim3(256), ipw_fwd_lds(F, h->rw), h->st, wa, (T*)h->a[0], (T*)h->aT[0],
-                                train ? h->emb : nullptr);
-    } else if (h->many_fwd) {
-        IpProf ps(h, "ip_fwd");
-        const int rc = ip_many_attr(h);
-        if (rc != FNN_OK) return rc;
-        const IpManyArgs ma = ip_many_args(h, ids, wts, B, mask0, drop ? inv_keep : 1.0f);
-        if (wts) hipLaunchKernelGGL((k_ip_fwd_m<T, true>), dim3(Ba / IPM_EX), dim3(256), ipm_fwd_lds(F), h->st, ma, (T*)h->a[0], (T*)h->aT[0],
-                                    train ? h->emb : nullptr);
-        else hipLaunchKernelGGL((k_ip_fwd_m<T>), dim3(Ba / IPM_EX), dim3(256), ipm_fwd_lds(F), h->st, ma, (T*)h->a[0], (T*)h->aT[0],
-                                train ? h->emb : nullptr);
+    if (!c.drop) return FNN_OK;
+    hipStream_t ms = h->kn.mask_side ? side.s : h->st;
+    IpProf pm(h, "mask_t", ms);
+    if (c.draw) {
+        int tiles = 0;
+        MaskDrawArgs da = ip_draw_args(h, *c.draw, c.B, &tiles);
+        for (int t = 0; t <= h->L; ++t) da.dstT[t] = h->maskT[t];
+        da.dstR[0] = h->mask0;
+        hipLaunchKernelGGL(k_mask_draw, dim3(tiles), dim3(256), 0, ms, da);
     } else {
-        IpProf ps(h, "ip_fwd");
-        IpFwdArgs fa{h->P, ids, B, F, h->K, h->table16, h->n_rows, h->b, mask0, h->d[0],
-                     drop ? inv_keep : 1.0f, h->cfg.act, h->Dp[0], ldT, h->err_flag, h->fwd_skip, h->wt, wts};
-        if (wts && h->ipf_nt == 1024) hipLaunchKernelGGL((k_ip_fwd<T, 1024, true>), dim3(Ba / 16), dim3(1024), lds_ip, h->st, fa, (T*)h->a[0], (T*)h->aT[0], train ? h->emb : nullptr);
-        else if (wts) hipLaunchKernelGGL((k_ip_fwd<T, IPF_NT, true>), dim3(Ba / 16), dim3(IPF_NT), lds_ip, h->st, fa, (T*)h->a[0], (T*)h->aT[0], train ? h->emb : nullptr);
-        else if (h->ipf_nt == 1024) hipLaunchKernelGGL((k_ip_fwd<T, 1024>), dim3(Ba / 16), dim3(1024), lds_ip, h->st, fa, (T*)h->a[0], (T*)h->aT[0], train ? h->emb : nullptr);
-        else hipLaunchKernelGGL((k_ip_fwd<T>), dim3(Ba / 16), dim3(IPF_NT), lds_ip, h->st, fa, (T*)h->a[0], (T*)h->aT[0], train ? h->emb : nullptr);
+        MaskTArgs ma{};
+        const int tiles = ip_mask_layout(h, c.B, ma);
+        for (int t = 0; t <= h->L; ++t) { ma.src[t] = c.masks[t]; ma.dst[t] = h->maskT[t]; }
+        hipLaunchKernelGGL(k_mask_T, dim3(tiles), dim3(256), 0, ms, ma);
     }
-    // one product: C [M][N] = A . B^T on fragment-tiled operands; narrow problems take smaller wave tiles
-    auto gemm = [&](const T* A, const T* Bm, int M, int N, int nkt_all, int nkt, int splitk, auto epi) {
-        typedef decltype(epi) E;
-        const int mt16 = M / 16, nt16 = N / 16;
-        const long wg44 = (long)((M + 127) / 128) * ((N + 127) / 128) * splitk;
-        const size_t lds4 = E::TILE ? gemm_ft_lds<T, 4>() : 0, lds2 = E::TILE ? gemm_ft_lds<T, 2>() : 0;
-        if (wg44 >= 160 && h->gemm_lds) {
-            constexpr size_t ldsb = gemm_lds_bytes<T, E::TILE>();
-            // > 64 KiB of dynamic LDS needs the opt-in (opt-in path: set on every launch, a host-side call)
-            hipFuncSetAttribute(reinterpret_cast<const void*>(&k_gemm_lds<T, E>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)ldsb);
-            hipLaunchKernelGGL((k_gemm_lds<T, E>), dim3((M + 127) / 128, (N + 127) / 128, splitk), dim3(256), ldsb, h->st, A, Bm,
-                               mt16, nt16, nkt_all, nkt, epi);
-        } else if (wg44 >= 160)
-            hipLaunchKernelGGL((k_gemm_ft<T, 4, 4, E>), dim3((M + 127) / 128, (N + 127) / 128, splitk), dim3(256), lds4, h->st, A, Bm,
-                               mt16, nt16, nkt_all, nkt, epi);
-        else if (N > 64)
-            hipLaunchKernelGGL((k_gemm_ft<T, 2, 4, E>), dim3((M + 63) / 64, (N + 127) / 128, splitk), dim3(256), lds4, h->st, A, Bm,
-                               mt16, nt16, nkt_all, nkt, epi);
-        else
-            hipLaunchKernelGGL((k_gemm_ft<T, 2, 2, E>), dim3((M + 63) / 64, (N + 63) / 64, splitk), dim3(256), lds2, h->st, A, Bm,
-                               mt16, nt16, nkt_all, nkt, epi);
-    };
-    if (drop && !draw && h->st2 && h->mask_side) IHK(h, hipStreamWaitEvent(h->st, h->ev_mask, 0));     // the strips / GEMMs read the transposed masks
-    { const int jrc = ip_join(h); if (jrc != FNN_OK) return jrc; }            // the previous step's dense update (read from here on)
-    constexpr int KS = Traits<T>::KS;
-    int maxD = 0;
-    for (int t = 0; t <= L + 1; ++t) maxD = std::max(maxD, h->Dp[t]);
-    constexpr int RT = sizeof(T) == 2 ? 2 : 1;                   // strip = 32 (bf16) / 16 (f32) examples: two LDS tiles of 64 KiB at 1024 units
-    const size_t strip_lds = (size_t)2 * RT * 16 * maxD * sizeof(T);
-    const bool strip = h->strip && strip_lds <= 128 * 1024;
-    // two workgroups per strip (StripDuo) where the pairs fit the chip at one workgroup per CU: both halves of a pair must be
-    // resident to swap (bf16 strips of 32 examples: 256 workgroups at batch 4096)
-    const int nstrips = Ba / (16 * RT);
-    const bool duo = strip && h->duo && RT == 2 && 2 * nstrips <= h->n_cu;
-    if (duo && !h->duo_xch) {
-        h->duo_xch_wg = (size_t)2 * ((maxD / 64 + 1) / 2) * RT * 256;       // 8-byte words: [2 parities][own blocks][RT][256]
-        IHK(h, hipMalloc((void**)&h->duo_xch, (size_t)(h->ldT / (16 * RT)) * 2 * h->duo_xch_wg * 8));
-        IHK(h, hipMalloc((void**)&h->duo_flags, (size_t)(h->ldT / (16 * RT)) * 2 * sizeof(int)));
-        IHK(h, hipMemsetAsync(h->duo_flags, 0, (size_t)(h->ldT / (16 * RT)) * 2 * sizeof(int), h->st));
+    if (h->kn.mask_side) IRC(side.signal(h->ev.mask));
+    return FNN_OK;
+}
+
+// the grouping of the batch's ids for the sparse-row update (needed by the scatter): beside the stack, on the side stream
+void ip_sort_ids(ipnn_handle* h, const IpCall& c, hipStream_t ss)
+{
+    SortArgs so{c.ids, c.B, h->F, h->n_rows, h->rg.rec, h->rg.owner_cnt, h->F, h->skeys};
+    so.merge4 = h->kn.sort_merge4;
+    launch_sort(ss, h->key64, so);
+}
+
+IpManyArgs ip_many_args(const ipnn_handle* h, const IpCall& c, const uint8_t* mask0, float inv_keep)
+{
+    return IpManyArgs{h->P, c.ids, c.B, h->F, h->K, h->table16, h->n_rows, h->b, mask0, h->d[0], inv_keep, h->cfg.act, h->Dp[0], h->ldT,
+                      h->err_flag, h->ptab, h->kn.wt, (unsigned)((size_t)h->ldT * h->Dp[0] * ts(h)), (unsigned)((size_t)h->ldT * h->F * SLOT * 4), c.wts};
+}
+IpWideArgs ip_wide_args(const ipnn_handle* h, const IpCall& c, const uint8_t* mask0, float inv_keep)
+{
+    return IpWideArgs{h->P, c.ids, c.B, h->F, h->K, h->rw, h->table16, h->n_rows, h->b, mask0, h->d[0], inv_keep, h->cfg.act, h->Dp[0],
+                      h->ldT, h->err_flag, h->kn.wt, (unsigned)((size_t)h->ldT * h->Dp[0] * ts(h)), (unsigned)((size_t)h->ldT * h->F * h->rw * 4), c.wts};
+}
+
+// layer 0: the gather of the batch's rows and their inner products -> a[0], aT[0]; training steps keep the raw embeddings (emb)
+template <typename T> int ip_gather_fwd(ipnn_handle* h, const IpCall& c)
+{
+    IpProf ps(h, "ip_fwd");
+    const IpRows rows = ip_fwd_rows(h);
+    const IpKernel k = ip_gather_fwd_sel<T>(rows, c.wts != nullptr, h->kn.ipf_nt);
+    const float inv_keep = c.drop ? 1.0f / h->cfg.keep_prob : 1.0f;
+    T *a0 = (T*)h->a[0], *a0T = (T*)h->aT[0];
+    float* emb = c.train ? h->emb : nullptr;
+    if (rows == IP_WIDE) {
+        const IpWideArgs wa = ip_wide_args(h, c, c.mask0, inv_keep);
+        IHK(h, ip_launch(k, c.Ba / IPW_EX, ipw_fwd_lds(h->F, h->rw), h->st, wa, a0, a0T, emb));
+    } else if (rows == IP_MANY) {
+        const IpManyArgs ma = ip_many_args(h, c, c.mask0, inv_keep);
+        IHK(h, ip_launch(k, c.Ba / IPM_EX, ipm_fwd_lds(h->F), h->st, ma, a0, a0T, emb));
+    } else {
+        const IpFwdArgs fa{h->P, c.ids, c.B, h->F, h->K, h->table16, h->n_rows, h->b, c.mask0, h->d[0],
+                           inv_keep, h->cfg.act, h->Dp[0], h->ldT, h->err_flag, h->kn.fwd_skip, h->kn.wt, c.wts};
+        IHK(h, ip_launch(k, c.Ba / 16, ip16_lds(h->F, h->Dp[0]), h->st, fa, a0, a0T, emb));
     }
-    if (duo && h->duo_epoch >= (1 << 26)) {
+    return FNN_OK;
+}
+
+// ------------------------------------------------------------------------------------------------------------------- the stack
+// The epilogues of the stack's products, for the strip kernels (the tile stays in LDS) and for the GEMM launches (row_major: the
+// result also goes to HBM row-major, for the next launch).
+template <typename T> EpiIpFwd<T> ip_epi_fwd(const ipnn_handle* h, const IpCall& c, int t, bool row_major)         // a_t, t = 1..L
+{
+    return EpiIpFwd<T>{row_major ? (T*)h->a[t] : nullptr, h->Dp[t], (T*)h->aT[t], h->ldT, c.drop ? h->maskT[t] : nullptr,
+                       c.drop ? 1.0f / h->cfg.keep_prob : 1.0f, h->cfg.act, h->d[t], c.B};
+}
+template <typename T> EpiIpOut<T> ip_epi_out(const ipnn_handle* h, const IpCall& c)
+{
+    const int L = h->L;
+    return EpiIpOut<T>{c.train ? (T*)h->dl[L] : nullptr, h->Dp[L + 1], c.train ? (T*)h->dlT[L] : nullptr, h->ldT, c.train ? c.y : nullptr,
+                       c.logits_out, h->loss_t, c.p_out, c.B, h->loss_mean ? 1.0f / (float)c.B : 1.0f};
+}
+template <typename T> EpiIpBwd<T> ip_epi_bwd(const ipnn_handle* h, const IpCall& c, int t, bool row_major)         // product t -> delta l_{t-1}
+{
+    const bool first = (t == 1);
+    const float keep = h->cfg.keep_prob;
+    return EpiIpBwd<T>{row_major && !first ? (T*)h->dl[t - 2] : nullptr, h->Dp[t - 1], first ? nullptr : (T*)h->dlT[t - 2], h->ldT,
+                       first ? h->dz0 : nullptr, h->Dp[0], (const T*)h->aT[t - 1], c.drop ? h->maskT[t - 1] : nullptr, 1.0f / keep, keep,
+                       h->cfg.act, h->d[t - 1], c.B, first ? h->ref0 : nullptr};
+}
+
+// The pair state of one strip launch.  A launch of whole strips (the whole stack, or its wide products) takes the next epoch, pairs
+// or not: the flags hold epoch * 16 + swap index, so every launch that could swap needs a number of its own, in launch order.  The
+// 16-example tail never swaps and takes none.
+StripDuo ip_strip_duo(ipnn_handle* h, bool tail, bool on)
+{
+    if (tail) return StripDuo{0, nullptr, nullptr, 0, h->err_flag, 0, h->kn.duo_min};
+    return StripDuo{on ? 1 : 0, h->duo_xch, h->duo_flags, ++h->duo_epoch, h->err_flag, h->duo_xch_wg, h->kn.duo_min};
+}
+
+// the pairs' exchange buffers (made by the first call that runs pairs) and the epoch's wrap
+template <typename T> int ip_duo_ready(ipnn_handle* h)
+{
+    constexpr int RT = sizeof(T) == 2 ? 2 : 1;
+    const size_t nflags = (size_t)(h->ldT / (16 * RT)) * 2;
+    if (!h->duo_xch) {
+        h->duo_xch_wg = (size_t)2 * ((h->plan.maxD / 64 + 1) / 2) * RT * 256;       // 8-byte words: [2 parities][own blocks][RT][256]
+        IHK(h, hipMalloc((void**)&h->duo_xch, nflags * h->duo_xch_wg * 8));
+        IHK(h, hipMalloc((void**)&h->duo_flags, nflags * sizeof(int)));
+        IHK(h, hipMemsetAsync(h->duo_flags, 0, nflags * sizeof(int), h->st));
+    }
+    if (h->duo_epoch >= (1 << 26)) {
         // flags hold epoch * 16 + swap index in 32 bits: long before that wraps (2^27 launches), drain the stream and start over at 0
         IHK(h, hipStreamSynchronize(h->st));
-        IHK(h, hipMemsetAsync(h->duo_flags, 0, (size_t)(h->ldT / (16 * RT)) * 2 * sizeof(int), h->st));
+        IHK(h, hipMemsetAsync(h->duo_flags, 0, nflags * sizeof(int), h->st));
         h->duo_epoch = 0;
     }
-    if (strip) {
-        if (!h->strip_attr) {                               // > 64 KiB of dynamic LDS needs the opt-in (once per handle = per device)
-            IHK(h, hipFuncSetAttribute(reinterpret_cast<const void*>(&k_ip_strip_fwd<T, RT>), hipFuncAttributeMaxDynamicSharedMemorySize, 128 * 1024));
-            if constexpr (RT == 2) {
-                IHK(h, hipFuncSetAttribute(reinterpret_cast<const void*>(&k_ip_strip_fwd<T, RT, 2, 12>), hipFuncAttributeMaxDynamicSharedMemorySize, 128 * 1024));
-                IHK(h, hipFuncSetAttribute(reinterpret_cast<const void*>(&k_ip_strip_bwd<T, RT, 2, 12>), hipFuncAttributeMaxDynamicSharedMemorySize, 128 * 1024));
-                IHK(h, hipFuncSetAttribute(reinterpret_cast<const void*>(&k_ip_strip_fwd<T, RT, 2, 8>), hipFuncAttributeMaxDynamicSharedMemorySize, 128 * 1024));
-                IHK(h, hipFuncSetAttribute(reinterpret_cast<const void*>(&k_ip_strip_bwd<T, RT, 2, 8>), hipFuncAttributeMaxDynamicSharedMemorySize, 128 * 1024));
-            }
-            IHK(h, hipFuncSetAttribute(reinterpret_cast<const void*>(&k_ip_strip_bwd<T, RT>), hipFuncAttributeMaxDynamicSharedMemorySize, 128 * 1024));
-            IHK(h, hipFuncSetAttribute(reinterpret_cast<const void*>(&k_ip_strip_fwd<T, 1>), hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024));
-            IHK(h, hipFuncSetAttribute(reinterpret_cast<const void*>(&k_ip_strip_bwd<T, 1>), hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024));
-            IHK(h, hipFuncSetAttribute(reinterpret_cast<const void*>(&k_ip_strip_fwd<T, 1, 2>), hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024));
-            IHK(h, hipFuncSetAttribute(reinterpret_cast<const void*>(&k_ip_strip_bwd<T, 1, 2>), hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024));
-            IHK(h, hipFuncSetAttribute(reinterpret_cast<const void*>(&k_ip_strip_fwd<T, 1, 1>), hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024));
-            IHK(h, hipFuncSetAttribute(reinterpret_cast<const void*>(&k_ip_strip_bwd<T, 1, 1>), hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024));
-            IHK(h, hipFuncSetAttribute(reinterpret_cast<const void*>(&k_ip_strip_fwd<T, 1, 1, 16>), hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024));
-            IHK(h, hipFuncSetAttribute(reinterpret_cast<const void*>(&k_ip_strip_bwd<T, 1, 1, 16>), hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024));
-            IHK(h, hipFuncSetAttribute(reinterpret_cast<const void*>(&k_ip_strip_tail<T, 1, 16>), hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024));
-            h->strip_attr = true;
-        }
+    return FNN_OK;
+}
+
+// IPNN_TAIL_LDS=1: small products of a 16-example-strip launch whose weights go to LDS behind the tiles: each up to 64 KB, all of them
+// within what is left of 152 KB.  Returns the bytes they take, fills the element offsets (-1: from memory).  OFF by default: measured
+// (profiles/r03d_ipnn_tail_lds_ab.json) the 88 KB copy costs more than the k-steps it shortens.
+template <typename T> size_t ip_tail_weights(const ipnn_handle* h, const int* Dp, int n, int* wlds)
+{
+    int maxd = 0;
+    for (int t = 0; t <= n; ++t) maxd = std::max(maxd, Dp[t]);
+    const size_t tiles = (size_t)2 * 16 * maxd * sizeof(T), budget = (size_t)152 * 1024 > tiles ? (size_t)152 * 1024 - tiles : 0;
+    size_t used = 0;
+    for (int p = 0; p < n; ++p) {
+        const size_t b = (size_t)Dp[p] * Dp[p + 1] * sizeof(T);
+        if (h->kn.tail_w_lds && b <= 64 * 1024 && used + b <= budget) { wlds[p] = (int)(used / sizeof(T)); used += b; }
+        else wlds[p] = -1;
     }
-    // Round 3: the narrow tail of the stack in launches of its own.  The products a pair does not split (fewer than duo_min column
-    // blocks: 448 -> 256 -> 128 -> 64 -> 1 of FNN_IP_L7) are a chain of short k-loops, each a barrier, an epilogue and a cold weight
-    // fetch long -- stamped at 4.5-7 us per product, 23 us forward and 29 us backward for 4 % of the FLOPs, on HALF the CUs forward
-    // (the second workgroup of a pair has nothing to do there).  They run as 16-example strips instead: 256 workgroups, one per CU, no
-    // pairs; the wide products keep the pairs of 32-example strips.  The hand-over is the tile of layer `cut` in the F layout (a[cut]
-    // forward, dl[cut - 1] backward), written block by block by the waves that computed it.
-    // small products of a 16-example-strip launch whose weights go to LDS behind the tiles: each up to 64 KB, all of them within what is
-    // left of 152 KB (IPNN_TAIL_LDS=0: none); returns the bytes they take, fills the element offsets
-    // Measured (profiles/r03d_ipnn_tail_lds_ab.json, A/B on one box): with the 88 KB copy 0.2700 / 0.2704 ms per step against 0.2629 /
-    // 0.2667 without -- the copy costs more than the k-steps it shortens (the tails are not bound by their weight fetches): OFF by default
-    const int tail_w_lds = getenv("IPNN_TAIL_LDS") ? atoi(getenv("IPNN_TAIL_LDS")) : 0;
-    auto lds_weights = [&](const int* Dp, int n, int* wlds) -> size_t {
-        size_t used = 0;
-        const size_t budget = (size_t)152 * 1024 > (size_t)2 * 16 * maxD2x(Dp, n) * sizeof(T) ? (size_t)152 * 1024 - (size_t)2 * 16 * maxD2x(Dp, n) * sizeof(T) : 0;
-        for (int p = 0; p < n; ++p) {
-            const size_t b = (size_t)Dp[p] * Dp[p + 1] * sizeof(T);
-            if (tail_w_lds && b <= 64 * 1024 && used + b <= budget) { wlds[p] = (int)(used / sizeof(T)); used += b; }
-            else wlds[p] = -1;
-        }
-        return used;
-    };
-    int cut = L;
-    while (cut >= 1 && h->Dp[cut] / 64 < h->duo_min) --cut;
-    const bool tsplit = strip && duo && h->tail_split && cut >= 1 && cut < L;
-    int maxD2 = 0;
-    for (int t = cut; t <= L + 1; ++t) maxD2 = std::max(maxD2, h->Dp[t]);
-    const size_t tail_lds = (size_t)2 * 16 * maxD2 * sizeof(T);
-    // training steps: the forward tail rides in the backward tail's launch (k_ip_strip_tail; IPNN_TAIL_FUSE=0: two launches)
-    const bool fuse_tail = tsplit && train && h->tail_fuse && h->tail_nf == 1 && h->tail_nw == 16 && !tail_w_lds;
-    StripFwdArgs<T> s2_fused{};
-    if (strip) {
-        IpProf ps(h, "fwd");
-        StripFwdArgs<T> sa{};
-        sa.a0 = (const T*)h->a[0]; sa.n = L + 1;
-        for (int t = 0; t <= L + 1; ++t) sa.Dp[t] = h->Dp[t];
-        for (int t = 1; t <= L + 1; ++t) sa.W[t - 1] = (const T*)h->wf[t - 1];
-        for (int t = 1; t <= L; ++t)
-            sa.ef[t - 1] = EpiIpFwd<T>{nullptr, h->Dp[t], (T*)h->aT[t], ldT, drop ? h->maskT[t] : nullptr, drop ? inv_keep : 1.0f, h->cfg.act,
-                                       h->d[t], B};
-        sa.eo = EpiIpOut<T>{train ? (T*)h->dl[L] : nullptr, h->Dp[L + 1], train ? (T*)h->dlT[L] : nullptr, ldT, train ? y : nullptr,
-                            logits_out, h->loss_t, p_out, B, h->loss_mean ? 1.0f / (float)B : 1.0f};
-        sa.dbg = h->stamps; sa.rot = h->strip_rot; sa.sel = getenv("IPNN_STAMP_SEL") ? atoi(getenv("IPNN_STAMP_SEL")) : -1;
-        sa.has_out = 1; sa.finalF = nullptr; sa.warm = h->strip_warm;
-        for (int t = 0; t < STRIP_MAXP; ++t) sa.wlds[t] = -1;
-        if (!tsplit) {
-            sa.duo = StripDuo{duo ? 1 : 0, h->duo_xch, h->duo_flags, ++h->duo_epoch, h->err_flag, h->duo_xch_wg, h->duo_min};
-            hipLaunchKernelGGL((k_ip_strip_fwd<T, RT>), dim3(nstrips * (duo ? 2 : 1)), dim3(64 * STRIP_NW), strip_lds, h->st, sa, maxD);
-        } else {
-            StripFwdArgs<T> s1 = sa;                                  // products 1 .. cut: pairs of 32-example strips; a[cut] -> HBM
-            s1.n = cut; s1.has_out = 0; s1.finalF = (T*)h->a[cut];
-            s1.duo = StripDuo{1, h->duo_xch, h->duo_flags, ++h->duo_epoch, h->err_flag, h->duo_xch_wg, h->duo_min};
-            StripFwdArgs<T> s2{};                                     // products cut + 1 .. L + 1: 16-example strips, every CU
-            s2.a0 = (const T*)h->a[cut]; s2.n = L + 1 - cut;
-            for (int t = cut; t <= L + 1; ++t) s2.Dp[t - cut] = h->Dp[t];
-            for (int t = cut + 1; t <= L + 1; ++t) s2.W[t - cut - 1] = sa.W[t - 1];
-            for (int t = cut + 1; t <= L; ++t) s2.ef[t - cut - 1] = sa.ef[t - 1];
-            s2.eo = sa.eo; s2.dbg = h->stamp_tail ? h->stamps : nullptr; s2.rot = h->strip_rot; s2.sel = -1; s2.has_out = 1; s2.finalF = nullptr; s2.warm = sa.warm;
-            if (h->stamp_tail) s1.dbg = nullptr;
-            s2.duo = StripDuo{0, nullptr, nullptr, 0, h->err_flag, 0, h->duo_min};
-            bool wide_done = false;
-            if constexpr (RT == 2) {                              // half-block items in the wide launch (IPNN_WIDE=nf:nw; measured: forward 59.8 -> 56.4 us at 2:8)
-                if (h->wide_nf == 2 && h->wide_nw == 12) { hipLaunchKernelGGL((k_ip_strip_fwd<T, RT, 2, 12>), dim3(nstrips * 2), dim3(64 * 12), strip_lds, h->st, s1, maxD); wide_done = true; }
-                else if (h->wide_nf == 2 && h->wide_nw == 8) { hipLaunchKernelGGL((k_ip_strip_fwd<T, RT, 2, 8>), dim3(nstrips * 2), dim3(64 * 8), strip_lds, h->st, s1, maxD); wide_done = true; }
-            }
-            if (!wide_done)
-            hipLaunchKernelGGL((k_ip_strip_fwd<T, RT>), dim3(nstrips * 2), dim3(64 * STRIP_NW), strip_lds, h->st, s1, maxD);
-            const size_t wl2 = lds_weights(s2.Dp, s2.n, s2.wlds);
-            if (fuse_tail) s2_fused = s2;
-            else if (h->tail_nf == 1 && h->tail_nw == 16) hipLaunchKernelGGL((k_ip_strip_fwd<T, 1, 1, 16>), dim3(Ba / 16), dim3(64 * 16), tail_lds + wl2, h->st, s2, maxD2);
-            else if (h->tail_nf == 1) hipLaunchKernelGGL((k_ip_strip_fwd<T, 1, 1>), dim3(Ba / 16), dim3(64 * STRIP_NW), tail_lds + wl2, h->st, s2, maxD2);
-            else if (h->tail_nf == 2) hipLaunchKernelGGL((k_ip_strip_fwd<T, 1, 2>), dim3(Ba / 16), dim3(64 * STRIP_NW), tail_lds + wl2, h->st, s2, maxD2);
-            else hipLaunchKernelGGL((k_ip_strip_fwd<T, 1>), dim3(Ba / 16), dim3(64 * STRIP_NW), tail_lds + wl2, h->st, s2, maxD2);
-        }
-    } else {
+    return used;
+}
+
+// Forward through the stack by the strip kernels: one launch, or (c.tsplit) the wide products 1 .. cut as pairs of 32-example
+// strips, a[cut] through HBM, and the tail cut + 1 .. L + 1 as 16-example strips on every CU.  A fused tail is not launched here:
+// its arguments go to the backward (*fused_tail).
+template <typename T> int ip_strips_fwd(ipnn_handle* h, const IpCall& c, StripFwdArgs<T>* fused_tail)
+{
     IpProf ps(h, "fwd");
-    for (int t = 1; t <= L; ++t) {       // l_t = a_{t-1} W_t ; a_t = drop(act(l_t))
-        EpiIpFwd<T> e{(T*)h->a[t], h->Dp[t], (T*)h->aT[t], ldT, drop ? h->maskT[t] : nullptr, drop ? inv_keep : 1.0f, h->cfg.act,
-                      h->d[t], B};
-        gemm((const T*)h->a[t - 1], (const T*)h->wf[t - 1], Ba, h->Dp[t], h->Dp[t - 1] / KS, h->Dp[t - 1] / KS, 1, e);
+    const IpPlan& p = h->plan;
+    const IpKnobs& kn = h->kn;
+    const int L = h->L, cut = p.cut;
+    constexpr int RT = sizeof(T) == 2 ? 2 : 1;
+    StripFwdArgs<T> sa{};
+    sa.a0 = (const T*)h->a[0]; sa.n = L + 1;
+    for (int t = 0; t <= L + 1; ++t) sa.Dp[t] = h->Dp[t];
+    for (int t = 1; t <= L + 1; ++t) sa.W[t - 1] = (const T*)h->wf[t - 1];
+    for (int t = 1; t <= L; ++t) sa.ef[t - 1] = ip_epi_fwd<T>(h, c, t, false);
+    sa.eo = ip_epi_out<T>(h, c);
+    sa.dbg = h->stamps; sa.rot = kn.strip_rot; sa.sel = kn.stamp_sel;
+    sa.has_out = 1; sa.finalF = nullptr; sa.warm = kn.strip_warm;
+    for (int t = 0; t < STRIP_MAXP; ++t) sa.wlds[t] = -1;
+    if (!c.tsplit) {
+        sa.duo = ip_strip_duo(h, false, c.duo);
+        IHK(h, ip_launch(ip_strip_sel<T>(false, RT, 4, STRIP_NW), c.nstrips * (c.duo ? 2 : 1), p.strip_lds, h->st, sa, p.maxD));
+        return FNN_OK;
     }
-    {
-        EpiIpOut<T> e{train ? (T*)h->dl[L] : nullptr, h->Dp[L + 1], train ? (T*)h->dlT[L] : nullptr, ldT, train ? y : nullptr,
-                      logits_out, h->loss_t, p_out, B, h->loss_mean ? 1.0f / (float)B : 1.0f};
-        gemm((const T*)h->a[L], (const T*)h->wf[L], Ba, h->Dp[L + 1], h->Dp[L] / KS, h->Dp[L] / KS, 1, e);
-    }
-    }
-    if (!train) { IHK(h, hipGetLastError()); return FNN_OK; }
-    if (strip) {
-        IpProf ps(h, "bwd");
-        StripBwdArgs<T> sb{};
-        sb.dlast = (const T*)h->dl[L]; sb.n = L + 1;
-        for (int t = 0; t <= L + 1; ++t) sb.Dp[t] = h->Dp[t];
-        for (int t = 1; t <= L + 1; ++t) {
-            const bool first = (t == 1);
-            sb.W[t - 1] = (const T*)h->wb[t - 1];
-            sb.eb[t - 1] = EpiIpBwd<T>{nullptr, h->Dp[t - 1], first ? nullptr : (T*)h->dlT[t - 2], ldT, first ? h->dz0 : nullptr, h->Dp[0],
-                                       (const T*)h->aT[t - 1], drop ? h->maskT[t - 1] : nullptr, inv_keep, keep, h->cfg.act, h->d[t - 1], B,
-                                       first ? h->ref0 : nullptr};
-        }
-        sb.dbg = h->stamps ? h->stamps + (size_t)(h->ldT / 16) * 16 : nullptr; sb.rot = h->strip_rot;
-        sb.bottom = 1; sb.finalF = nullptr; sb.warm = h->strip_warm;
-        for (int t = 0; t < STRIP_MAXP; ++t) sb.wlds[t] = -1;
-        if (!tsplit) {
-            sb.duo = StripDuo{duo ? 1 : 0, h->duo_xch, h->duo_flags, ++h->duo_epoch, h->err_flag, h->duo_xch_wg, h->duo_min};
-            hipLaunchKernelGGL((k_ip_strip_bwd<T, RT>), dim3(nstrips * (duo ? 2 : 1)), dim3(64 * STRIP_NW), strip_lds, h->st, sb, maxD);
-        } else {
-            StripBwdArgs<T> sA{};                                     // products L + 1 .. cut + 1 (the narrow ones come first): 16-example strips
-            sA.dlast = (const T*)h->dl[L]; sA.n = L + 1 - cut;
-            for (int t = cut; t <= L + 1; ++t) sA.Dp[t - cut] = h->Dp[t];
-            for (int t = cut + 1; t <= L + 1; ++t) { sA.W[t - cut - 1] = sb.W[t - 1]; sA.eb[t - cut - 1] = sb.eb[t - 1]; }
-            sA.dbg = h->stamp_tail ? sb.dbg : nullptr; sA.rot = h->strip_rot; sA.bottom = 0; sA.finalF = (T*)h->dl[cut - 1]; sA.warm = sb.warm;
-            sA.duo = StripDuo{0, nullptr, nullptr, 0, h->err_flag, 0, h->duo_min};
-            const size_t wlA = lds_weights(sA.Dp, sA.n, sA.wlds);
-            if (fuse_tail) hipLaunchKernelGGL((k_ip_strip_tail<T, 1, 16>), dim3(Ba / 16), dim3(64 * 16), tail_lds, h->st, s2_fused, sA, maxD2);
-            else if (h->tail_nf == 1 && h->tail_nw == 16) hipLaunchKernelGGL((k_ip_strip_bwd<T, 1, 1, 16>), dim3(Ba / 16), dim3(64 * 16), tail_lds + wlA, h->st, sA, maxD2);
-            else if (h->tail_nf == 1) hipLaunchKernelGGL((k_ip_strip_bwd<T, 1, 1>), dim3(Ba / 16), dim3(64 * STRIP_NW), tail_lds + wlA, h->st, sA, maxD2);
-            else if (h->tail_nf == 2) hipLaunchKernelGGL((k_ip_strip_bwd<T, 1, 2>), dim3(Ba / 16), dim3(64 * STRIP_NW), tail_lds + wlA, h->st, sA, maxD2);
-            else hipLaunchKernelGGL((k_ip_strip_bwd<T, 1>), dim3(Ba / 16), dim3(64 * STRIP_NW), tail_lds + wlA, h->st, sA, maxD2);
-            StripBwdArgs<T> sB = sb;                                  // products cut .. 1: pairs of 32-example strips, from delta l_cut in HBM
-            sB.dlast = (const T*)h->dl[cut - 1]; sB.n = cut;
-            if (h->stamp_tail) sB.dbg = nullptr;
-            sB.duo = StripDuo{1, h->duo_xch, h->duo_flags, ++h->duo_epoch, h->err_flag, h->duo_xch_wg, h->duo_min};
-            bool wide_done = false;
-            if constexpr (RT == 2) {
-                if (h->wide_nf == 2 && h->wide_nw == 12) { hipLaunchKernelGGL((k_ip_strip_bwd<T, RT, 2, 12>), dim3(nstrips * 2), dim3(64 * 12), strip_lds, h->st, sB, maxD); wide_done = true; }
-                else if (h->wide_nf == 2 && h->wide_nw == 8) { hipLaunchKernelGGL((k_ip_strip_bwd<T, RT, 2, 8>), dim3(nstrips * 2), dim3(64 * 8), strip_lds, h->st, sB, maxD); wide_done = true; }
-            }
-            if (!wide_done)
-            hipLaunchKernelGGL((k_ip_strip_bwd<T, RT>), dim3(nstrips * 2), dim3(64 * STRIP_NW), strip_lds, h->st, sB, maxD);
-        }
-    } else {
+    StripFwdArgs<T> s1 = sa;                                  // products 1 .. cut: pairs of 32-example strips; a[cut] -> HBM
+    s1.n = cut; s1.has_out = 0; s1.finalF = (T*)h->a[cut];
+    s1.duo = ip_strip_duo(h, false, true);
+    if (kn.stamps == 2) s1.dbg = nullptr;
+    IHK(h, ip_launch(ip_strip_sel<T>(false, RT, kn.wide_nf, kn.wide_nw), c.nstrips * 2, p.strip_lds, h->st, s1, p.maxD));
+    StripFwdArgs<T> s2{};                                     // products cut + 1 .. L + 1: 16-example strips, every CU
+    s2.a0 = (const T*)h->a[cut]; s2.n = L + 1 - cut;
+    for (int t = cut; t <= L + 1; ++t) s2.Dp[t - cut] = h->Dp[t];
+    for (int t = cut + 1; t <= L + 1; ++t) s2.W[t - cut - 1] = sa.W[t - 1];
+    for (int t = cut + 1; t <= L; ++t) s2.ef[t - cut - 1] = sa.ef[t - 1];
+    s2.eo = sa.eo; s2.dbg = kn.stamps == 2 ? h->stamps : nullptr; s2.rot = kn.strip_rot; s2.sel = -1; s2.has_out = 1; s2.finalF = nullptr; s2.warm = sa.warm;
+    s2.duo = ip_strip_duo(h, true, false);
+    const size_t wl2 = ip_tail_weights<T>(h, s2.Dp, s2.n, s2.wlds);
+    if (c.fuse_tail) *fused_tail = s2;
+    else IHK(h, ip_launch(ip_strip_sel<T>(false, 1, kn.tail_nf, kn.tail_nw), c.Ba / 16, p.tail_lds + wl2, h->st, s2, p.maxD2));
+    return FNN_OK;
+}
+
+// Backward through the stack, the mirror image: the tail L + 1 .. cut + 1 first (with the forward tail in the same launch when
+// fused), delta l_cut through HBM, then the wide products cut .. 1 as pairs.
+template <typename T> int ip_strips_bwd(ipnn_handle* h, const IpCall& c, const StripFwdArgs<T>& fused_tail)
+{
     IpProf ps(h, "bwd");
-    for (int t = L + 1; t >= 1; --t) {   // delta l_{t-1} from delta l_t ; then gW_t = a_{t-1}^T delta l_t
-        const bool first = (t == 1);
-        EpiIpBwd<T> e{first ? nullptr : (T*)h->dl[t - 2], h->Dp[t - 1], first ? nullptr : (T*)h->dlT[t - 2], ldT,
-                      first ? h->dz0 : nullptr, h->Dp[0], (const T*)h->aT[t - 1], drop ? h->maskT[t - 1] : nullptr, inv_keep, keep,
-                      h->cfg.act, h->d[t - 1], B, first ? h->ref0 : nullptr};
-        gemm((const T*)h->dl[t - 1], (const T*)h->wb[t - 1], Ba, h->Dp[t - 1], h->Dp[t] / KS, h->Dp[t] / KS, 1, e);
+    const IpPlan& p = h->plan;
+    const IpKnobs& kn = h->kn;
+    const int L = h->L, cut = p.cut;
+    constexpr int RT = sizeof(T) == 2 ? 2 : 1;
+    StripBwdArgs<T> sb{};
+    sb.dlast = (const T*)h->dl[L]; sb.n = L + 1;
+    for (int t = 0; t <= L + 1; ++t) sb.Dp[t] = h->Dp[t];
+    for (int t = 1; t <= L + 1; ++t) { sb.W[t - 1] = (const T*)h->wb[t - 1]; sb.eb[t - 1] = ip_epi_bwd<T>(h, c, t, false); }
+    sb.dbg = h->stamps ? h->stamps + (size_t)(h->ldT / 16) * 16 : nullptr; sb.rot = kn.strip_rot;
+    sb.bottom = 1; sb.finalF = nullptr; sb.warm = kn.strip_warm;
+    for (int t = 0; t < STRIP_MAXP; ++t) sb.wlds[t] = -1;
+    if (!c.tsplit) {
+        sb.duo = ip_strip_duo(h, false, c.duo);
+        IHK(h, ip_launch(ip_strip_sel<T>(true, RT, 4, STRIP_NW), c.nstrips * (c.duo ? 2 : 1), p.strip_lds, h->st, sb, p.maxD));
+        return FNN_OK;
     }
+    StripBwdArgs<T> sA{};                                     // products L + 1 .. cut + 1 (the narrow ones come first): 16-example strips
+    sA.dlast = (const T*)h->dl[L]; sA.n = L + 1 - cut;
+    for (int t = cut; t <= L + 1; ++t) sA.Dp[t - cut] = h->Dp[t];
+    for (int t = cut + 1; t <= L + 1; ++t) { sA.W[t - cut - 1] = sb.W[t - 1]; sA.eb[t - cut - 1] = sb.eb[t - 1]; }
+    sA.dbg = kn.stamps == 2 ? sb.dbg : nullptr; sA.rot = kn.strip_rot; sA.bottom = 0; sA.finalF = (T*)h->dl[cut - 1]; sA.warm = sb.warm;
+    sA.duo = ip_strip_duo(h, true, false);
+    const size_t wlA = ip_tail_weights<T>(h, sA.Dp, sA.n, sA.wlds);
+    if (c.fuse_tail) IHK(h, ip_launch(ip_strip_tail_sel<T>(), c.Ba / 16, p.tail_lds, h->st, fused_tail, sA, p.maxD2));
+    else IHK(h, ip_launch(ip_strip_sel<T>(true, 1, kn.tail_nf, kn.tail_nw), c.Ba / 16, p.tail_lds + wlA, h->st, sA, p.maxD2));
+    StripBwdArgs<T> sB = sb;                                  // products cut .. 1: pairs of 32-example strips, from delta l_cut in HBM
+    sB.dlast = (const T*)h->dl[cut - 1]; sB.n = cut;
+    if (kn.stamps == 2) sB.dbg = nullptr;
+    sB.duo = ip_strip_duo(h, false, true);
+    IHK(h, ip_launch(ip_strip_sel<T>(true, RT, kn.wide_nf, kn.wide_nw), c.nstrips * 2, p.strip_lds, h->st, sB, p.maxD));
+    return FNN_OK;
+}
+
+// IPNN_STRIP=0, or a layer too wide for the strips' tiles: one product per launch, C [M][N] = A . B^T on fragment-tiled operands;
+// narrow problems take smaller wave tiles
+template <typename T, typename E>
+void ip_gemm(ipnn_handle* h, const T* A, const T* Bm, int M, int N, int nkt_all, int nkt, int splitk, E epi)
+{
+    const int mt16 = M / 16, nt16 = N / 16;
+    const long wg44 = (long)((M + 127) / 128) * ((N + 127) / 128) * splitk;
+    const size_t lds4 = E::TILE ? gemm_ft_lds<T, 4>() : 0, lds2 = E::TILE ? gemm_ft_lds<T, 2>() : 0;
+    if (wg44 >= 160 && h->kn.gemm_lds) {
+        constexpr size_t ldsb = gemm_lds_bytes<T, E::TILE>();
+        // > 64 KiB of dynamic LDS needs the opt-in (opt-in path: set on every launch, a host-side call)
+        hipFuncSetAttribute(reinterpret_cast<const void*>(&k_gemm_lds<T, E>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)ldsb);
+        hipLaunchKernelGGL((k_gemm_lds<T, E>), dim3((M + 127) / 128, (N + 127) / 128, splitk), dim3(256), ldsb, h->st, A, Bm,
+                           mt16, nt16, nkt_all, nkt, epi);
+    } else if (wg44 >= 160)
+        hipLaunchKernelGGL((k_gemm_ft<T, 4, 4, E>), dim3((M + 127) / 128, (N + 127) / 128, splitk), dim3(256), lds4, h->st, A, Bm,
+                           mt16, nt16, nkt_all, nkt, epi);
+    else if (N > 64)
+        hipLaunchKernelGGL((k_gemm_ft<T, 2, 4, E>), dim3((M + 63) / 64, (N + 127) / 128, splitk), dim3(256), lds4, h->st, A, Bm,
+                           mt16, nt16, nkt_all, nkt, epi);
+    else
+        hipLaunchKernelGGL((k_gemm_ft<T, 2, 2, E>), dim3((M + 63) / 64, (N + 63) / 64, splitk), dim3(256), lds2, h->st, A, Bm,
+                           mt16, nt16, nkt_all, nkt, epi);
+}
+template <typename T> void ip_gemms_fwd(ipnn_handle* h, const IpCall& c)       // l_t = a_{t-1} W_t ; a_t = drop(act(l_t)); then the output unit
+{
+    IpProf ps(h, "fwd");
+    constexpr int KS = Traits<T>::KS;
+    for (int t = 1; t <= h->L + 1; ++t) {
+        const T *A = (const T*)h->a[t - 1], *W = (const T*)h->wf[t - 1];
+        const int nkt = h->Dp[t - 1] / KS;
+        if (t <= h->L) ip_gemm(h, A, W, c.Ba, h->Dp[t], nkt, nkt, 1, ip_epi_fwd<T>(h, c, t, true));
+        else ip_gemm(h, A, W, c.Ba, h->Dp[t], nkt, nkt, 1, ip_epi_out<T>(h, c));
     }
-    // Beside the weight gradients, on the side stream (after the id grouping, in stream order): the backward of the inner
-    // products and the sparse-row update -- they need dz1 only, the weight gradients need the transposed operands only.
-    float lr_step = h->cfg.lr;
+}
+template <typename T> void ip_gemms_bwd(ipnn_handle* h, const IpCall& c)       // delta l_{t-1} from delta l_t
+{
+    IpProf ps(h, "bwd");
+    constexpr int KS = Traits<T>::KS;
+    for (int t = h->L + 1; t >= 1; --t)
+        ip_gemm(h, (const T*)h->dl[t - 1], (const T*)h->wb[t - 1], c.Ba, h->Dp[t - 1], h->Dp[t] / KS, h->Dp[t] / KS, 1, ip_epi_bwd<T>(h, c, t, true));
+}
+
+// ------------------------------------------------------------------------------------------------------- after the backward pass
+// The side chain: the backward of the inner products, b, the sparse-row update and (Adam / FTRL) the table pass.  They need dz1
+// only; the weight gradients, beside them on the main stream, need the transposed operands only.
+int ip_side_chain(ipnn_handle* h, const IpCall& c, hipStream_t ss, float lr_step)
+{
+    const int F = h->F;
     {
-        hipStream_t ss = h->st2 ? h->st2 : h->st;
-        if (h->st2) { IHK(h, hipEventRecord(h->ev_bwd, h->st)); IHK(h, hipStreamWaitEvent(h->st2, h->ev_bwd, 0)); }
-        if (h->adam) {
-            h->adam_t += 1;
-            if (!h->ftrl)
-                lr_step = (float)((double)h->cfg.lr * std::sqrt(1.0 - std::pow((double)h->cfg.adam_beta2, (double)h->adam_t)) /
-                                  (1.0 - std::pow((double)h->cfg.adam_beta1, (double)h->adam_t)));
+        IpProf ps(h, "ip_bwd", ss);
+        const IpRows rows = ip_bwd_rows(h);
+        const bool wv = c.wts != nullptr;
+        const IpKernel k = ip_gather_bwd_sel(rows, wv);
+        const float *dz0 = h->dz0, *emb = h->emb;
+        if (rows == IP_WIDE) {
+            const IpWideArgs wa = ip_wide_args(h, c, nullptr, 1.0f);
+            IHK(h, ip_launch(k, c.Ba / IPW_EX, ipw_bwd_lds(F, h->rw, h->P, wv), ss, wa, dz0, emb, h->gxp, h->gb_part));
+        } else if (rows == IP_MANY) {
+            const IpManyArgs ma = ip_many_args(h, c, nullptr, 1.0f);
+            IHK(h, ip_launch(k, c.Ba / IPM_BEX, ipm_bwd_lds(F, h->P, wv), ss, ma, dz0, emb, h->gxp, h->gb_part));
+        } else {
+            const IpBwdArgs ba{h->P, c.ids, c.B, F, h->K, h->table16, h->n_rows, h->Dp[0], h->emb, c.wts};
+            IHK(h, ip_launch(k, c.Ba / 16, ip16_lds(F, h->Dp[0]), ss, ba, dz0, h->gxp, h->gb_part));
         }
-        {
-            IpProf ps(h, "ip_bwd", ss);
-            const int ngb = Ba / ip_bwd_ex(h);                       // one partial of db per workgroup of the backward
-            if (h->wide) {
-                const IpWideArgs wa = ip_wide_args(h, ids, wts, B, nullptr, 1.0f);
-                if (wts) hipLaunchKernelGGL(k_ip_bwd_w<true>, dim3(Ba / IPW_EX), dim3(256), ipw_bwd_lds(F, h->rw, h->P, true), ss, wa, h->dz0, h->emb, h->gxp, h->gb_part);
-                else hipLaunchKernelGGL(k_ip_bwd_w<false>, dim3(Ba / IPW_EX), dim3(256), ipw_bwd_lds(F, h->rw, h->P, false), ss, wa, h->dz0, h->emb, h->gxp, h->gb_part);
-            } else if (h->many_bwd) {
-                const IpManyArgs ma = ip_many_args(h, ids, wts, B, nullptr, 1.0f);
-                if (wts) hipLaunchKernelGGL(k_ip_bwd_m<true>, dim3(Ba / IPM_BEX), dim3(256), ipm_bwd_lds(F, h->P, true), ss, ma, h->dz0, h->emb, h->gxp, h->gb_part);
-                else hipLaunchKernelGGL(k_ip_bwd_m<false>, dim3(Ba / IPM_BEX), dim3(256), ipm_bwd_lds(F, h->P, false), ss, ma, h->dz0, h->emb, h->gxp, h->gb_part);
-            } else {
-                IpBwdArgs ba{h->P, ids, B, F, h->K, h->table16, h->n_rows, h->Dp[0], h->emb, wts};
-                if (wts) hipLaunchKernelGGL(k_ip_bwd<true>, dim3(Ba / 16), dim3(256), lds_ip, ss, ba, h->dz0, h->gxp, h->gb_part);
-                else hipLaunchKernelGGL(k_ip_bwd<false>, dim3(Ba / 16), dim3(256), lds_ip, ss, ba, h->dz0, h->gxp, h->gb_part);
-            }
-            hipLaunchKernelGGL(k_ip_b_update, dim3(1), dim3(256), 0, ss, h->b, h->gb_part, ngb, h->adam ? (int)h->cfg.optimizer : 0, h->bmv,
-                               lr_step, h->cfg.adam_beta1, h->cfg.adam_beta2, h->cfg.adam_eps, h->err_flag);
-        }
-        if (h->wide) {   // wide rows: the bag table's wide scatter, gradient stride rw, row pitch Dp0, c = 1; Adam / FTRL: into tG
-            IpProf ps(h, "scatter", ss);
-            ScatArgs sa = scat_args(h->rg, SORT_N, F, h->K, h->gxp, h->Dp[0], h->cpow1, h->adam ? -1.0 : (double)h->cfg.lr,
-                                    h->adam ? h->tG : h->table16, h->rw);
+        const int ngb = c.Ba / ip_bwd_ex(h);                       // one partial of db per workgroup of the backward
+        hipLaunchKernelGGL(k_ip_b_update, dim3(1), dim3(256), 0, ss, h->b, h->gb_part, ngb, h->adam ? (int)h->cfg.optimizer : 0, h->bmv,
+                           lr_step, h->cfg.adam_beta1, h->cfg.adam_beta2, h->cfg.adam_eps, h->err_flag);
+    }
+    {   // sparse rows: row -= lr * sum of its gradients (c = 1: the table of powers is all ones).  Adam / FTRL: the same sorted sums
+        // land in the (zero) gradient table instead: G[row] = 0 * 1 - (-1) * sum
+        IpProf ps(h, "scatter", ss);
+        ScatArgs sa = scat_args(h->rg, SORT_N, F, h->K, h->gxp, h->Dp[0], h->cpow1, h->adam ? -1.0 : (double)h->cfg.lr,
+                                h->adam ? h->tG : h->table16, h->wide ? h->rw : SLOT);
+        if (h->wide) {   // the bag table's wide scatter, gradient stride rw, row pitch Dp0
             sa.tag_shared = h->noshare; sa.stamp = 1; sa.gxf = h->rw;
             const int nthr = F * (SORT_N / WCH) * (h->rw / 4);
             hipLaunchKernelGGL(k_ip_scatw1, dim3((nthr + 255) / 256), dim3(256), 0, ss, sa);
             hipLaunchKernelGGL(k_ip_scatw2, dim3(256), dim3(256), 0, ss, sa);
-        } else {   // sparse rows: row -= lr * sum of its gradients (c = 1: the table of powers is all ones)
-            IpProf ps(h, "scatter", ss);
-            // Adam / FTRL: the same sorted sums land in the (zero) gradient table instead: G[row] = 0 * 1 - (-1) * sum
-            ScatArgs sa = scat_args(h->rg, SORT_N, F, h->K, h->gxp, h->Dp[0], h->cpow1, h->adam ? -1.0 : (double)h->cfg.lr,
-                                    h->adam ? h->tG : h->table16, SLOT);
-            sa.form2 = h->scat2_form;
-            launch_scat_narrow(ss, sa, h->scat_form, 256);
-        }
-        if (h->adam) {
-            IpProf ps(h, "adam_table", ss);
-            const size_t n = (size_t)h->n_rows * h->rw;
-            hipLaunchKernelGGL(k_adam_table, dim3((unsigned)((n / 4 + 255) / 256)), dim3(256), 0, ss, h->table16, h->tm, h->tv, h->tG, n,
-                               lr_step, h->cfg.adam_beta1, h->cfg.adam_beta2, h->cfg.adam_eps, (int)h->cfg.optimizer);
-        }
-        if (h->st2) IHK(h, hipEventRecord(h->st2 && h->upd_side ? h->ev_tab : h->ev_join, h->st2));
-    }
-    {   // all weight gradients: gW_t [Dp_{t-1}][Dp_t] = a_{t-1}^T . delta l_t, contraction over the examples,
-        // split-K slabs (the split chosen per layer so that every product fills the chip)
-        IpProf ps(h, "wgrad");
-        if (h->group_wgrad && L + 1 <= GEMM_GROUP_MAX) {   // ONE launch for the whole stack: 128 x 128 tiles of every product, widest first
-            GemmGroupArgs g{};
-            std::vector<size_t> offs(L + 2, 0);
-            for (int t = 1; t <= L + 1; ++t) offs[t] = offs[t - 1] + (size_t)h->Dp[t - 1] * h->Dp[t];
-            std::vector<int> order(L + 1);
-            for (int t = 1; t <= L + 1; ++t) order[t - 1] = t;
-            std::sort(order.begin(), order.end(), [&](int x, int y) { return (size_t)h->Dp[x - 1] * h->Dp[x] > (size_t)h->Dp[y - 1] * h->Dp[y]; });
-            int wg = 0;
-            for (int i = 0; i <= L; ++i) {
-                const int t = order[i], sk = h->sk[t - 1], M = h->Dp[t - 1], N = h->Dp[t];
-                GemmGroupProb& pr = g.p[i];
-                pr.A = h->aT[t - 1]; pr.B = h->dlT[t - 1]; pr.out = h->slab + offs[t - 1]; pr.mt16 = M / 16; pr.nt16 = N / 16;
-                pr.nkt_all = ldT / KS; pr.nkt = Ba / KS / sk; pr.ldo = N; pr.gx = (M + 127) / 128; pr.gy = (N + 127) / 128;
-                g.wg0[i] = wg; wg += pr.gx * pr.gy * sk;
-            }
-            g.wg0[L + 1] = wg; g.n = L + 1; g.zstride = h->slab_stride; g.xcd = h->group_xcd; g.wt = h->wt;
-            hipLaunchKernelGGL((k_gemm_group<T, 4, 4>), dim3(wg), dim3(256), gemm_f32w_lds(), h->st, g);
         } else {
-        size_t off = 0;
-        for (int t = 1; t <= L + 1; ++t) {
-            const int sk = h->sk[t - 1];
-            EpiF32 e{h->slab + off, h->Dp[t], h->slab_stride};
-            gemm((const T*)h->aT[t - 1], (const T*)h->dlT[t - 1], h->Dp[t - 1], h->Dp[t], ldT / KS, Ba / KS / sk, sk, e);
-            off += (size_t)h->Dp[t - 1] * h->Dp[t];
-        }
+            sa.form2 = h->kn.scat2_form;
+            launch_scat_narrow(ss, sa, h->kn.scat_form, 256);
         }
     }
-    const bool side_upd = h->st2 && h->upd_side;
-    if (side_upd) { IHK(h, hipEventRecord(h->ev_wg, h->st)); IHK(h, hipStreamWaitEvent(h->st2, h->ev_wg, 0)); }
-    {
-        hipStream_t us = side_upd ? h->st2 : h->st;
-        IpProf ps(h, "update", us);
-        size_t off = 0;
-        IpUpdArgs u{};
-        u.wt = h->wt;
-        for (int t = 1; t <= L + 1; ++t) {
-            u.W[t - 1] = h->W[t - 1]; u.wf[t - 1] = h->wf[t - 1]; u.wb[t - 1] = h->wb[t - 1]; u.off[t - 1] = off;
-            u.Din[t - 1] = h->Dp[t - 1]; u.Dout[t - 1] = h->Dp[t]; u.sk[t - 1] = h->sk[t - 1];
-            off += (size_t)h->Dp[t - 1] * h->Dp[t];
-        }
-        u.n = L + 1; u.off[L + 1] = off; u.slab = h->slab; u.zstride = h->slab_stride; u.lr = lr_step;
-        u.adam = h->adam ? (int)h->cfg.optimizer : 0; u.beta1 = h->cfg.adam_beta1; u.beta2 = h->cfg.adam_beta2; u.eps = h->cfg.adam_eps; u.bmv = h->bmv;
-        if (h->adam) for (int t = 0; t <= L; ++t) { u.Wm[t] = h->Wm[t]; u.Wv[t] = h->Wv[t]; }
-        u.b = h->b; u.gb_part = h->gb_part; u.ngb = Ba / ip_bwd_ex(h); u.loss_t = h->loss_t; u.Ba = Ba; u.loss_sum = h->loss_dev; u.err = h->err_flag;
-        hipLaunchKernelGGL((k_ip_update_all<T>), dim3((unsigned)(off / 4096 + 1)), dim3(256), 0, us, u);
+    if (h->adam) {
+        IpProf ps(h, "adam_table", ss);
+        const size_t n = (size_t)h->n_rows * h->rw;
+        hipLaunchKernelGGL(k_adam_table, dim3((unsigned)((n / 4 + 255) / 256)), dim3(256), 0, ss, h->table16, h->tm, h->tv, h->tG, n,
+                           lr_step, h->cfg.adam_beta1, h->cfg.adam_beta2, h->cfg.adam_eps, (int)h->cfg.optimizer);
     }
-    if (side_upd) { IHK(h, hipEventRecord(h->ev_join, h->st2)); h->tab_pending = h->upd_pending = true; }   // joined by the next call (ip_join)
-    else if (h->st2) IHK(h, hipStreamWaitEvent(h->st, h->ev_join, 0));      // the step ends when the side chain has
+    return FNN_OK;
+}
+
+// All weight gradients: gW_t [Dp_{t-1}][Dp_t] = a_{t-1}^T . delta l_t, contraction over the examples, into split-K slabs (the
+// split chosen per layer so that every product fills the chip): one grouped launch, or one launch per product
+template <typename T> void ip_wgrad(ipnn_handle* h, const IpCall& c)
+{
+    IpProf ps(h, "wgrad");
+    const IpPlan& p = h->plan;
+    const int L = h->L;
+    constexpr int KS = Traits<T>::KS;
+    if (h->kn.group_wgrad && L + 1 <= GEMM_GROUP_MAX) {
+        GemmGroupArgs g = p.group;
+        for (int i = 0; i <= L; ++i) g.p[i].nkt = c.Ba / KS / h->sk[p.wg_order[i] - 1];
+        hipLaunchKernelGGL((k_gemm_group<T, 4, 4>), dim3(g.wg0[L + 1]), dim3(256), gemm_f32w_lds(), h->st, g);
+        return;
+    }
+    for (int t = 1; t <= L + 1; ++t) {
+        const int sk = h->sk[t - 1];
+        ip_gemm(h, (const T*)h->aT[t - 1], (const T*)h->dlT[t - 1], h->Dp[t - 1], h->Dp[t], h->ldT / KS, c.Ba / KS / sk, sk,
+                EpiF32{h->slab + p.off[t - 1], h->Dp[t], h->slab_stride});
+    }
+}
+
+// every dense layer's update from its slabs, b's, and the step's loss sum, in one launch
+template <typename T> void ip_dense_update(ipnn_handle* h, const IpCall& c, hipStream_t us, float lr_step)
+{
+    IpProf ps(h, "update", us);
+    IpUpdArgs u = h->plan.upd;
+    u.lr = lr_step; u.ngb = c.Ba / ip_bwd_ex(h); u.Ba = c.Ba;
+    hipLaunchKernelGGL((k_ip_update_all<T>), dim3((unsigned)(u.off[h->L + 1] / 4096 + 1)), dim3(256), 0, us, u);
+}
+
+// One forward pass (predict, eval) or one training step.  Everything that can refuse the call stands in front of the first enqueue.
+template <typename T>
+int ip_run(ipnn_handle* h, IpCall c)
+{
+    const IpPlan& p = h->plan;
+    const IpKnobs& kn = h->kn;
+    if (c.train && c.masks && !c.draw) for (int t = 0; t <= h->L; ++t) if (!c.masks[t]) IFAIL(h, FNN_ERR_ARG, "masks: null entry");
+    ip_form(h, c);
+    IpSide side(h);
+    IRC(ip_join_table(h));                                      // the previous step's sparse rows / bias (read by the gather)
+    if (c.train) {
+        // beside the stack, on the side stream: the grouping of the batch's ids; the keep-masks (needed from the first product on)
+        // go first, on the main stream
+        IRC(side.fork(h->ev.fork));
+        IRC(ip_masks(h, c, side));
+        ip_sort_ids(h, c, side.s);
+    }
+    const bool mask_wait = c.drop && kn.mask_side;             // IPNN_MASK_SIDE=1: the masks come from the side stream
+    if (mask_wait && c.draw) IRC(side.wait(h->ev.mask));        // the inner-product forward reads the drawn mask0
+    IRC(ip_gather_fwd<T>(h, c));
+    if (mask_wait && !c.draw) IRC(side.wait(h->ev.mask));       // the strips / GEMMs read the transposed masks
+    IRC(ip_join(h));                                            // the previous step's dense update (read from here on)
+    if (c.duo) IRC(ip_duo_ready<T>(h));
+    StripFwdArgs<T> fused_tail{};
+    if (p.strip) IRC(ip_strips_fwd<T>(h, c, &fused_tail)); else ip_gemms_fwd<T>(h, c);
+    if (!c.train) { IHK(h, hipGetLastError()); return FNN_OK; }
+    if (p.strip) IRC(ip_strips_bwd<T>(h, c, fused_tail)); else ip_gemms_bwd<T>(h, c);
+    float lr_step = h->cfg.lr;
+    if (h->adam) {
+        h->adam_t += 1;
+        if (!h->ftrl)
+            lr_step = (float)((double)h->cfg.lr * std::sqrt(1.0 - std::pow((double)h->cfg.adam_beta2, (double)h->adam_t)) /
+                              (1.0 - std::pow((double)h->cfg.adam_beta1, (double)h->adam_t)));
+    }
+    // Beside the weight gradients, on the side stream (after the id grouping, in stream order): the side chain
+    const bool side_upd = side.on() && kn.upd_side;
+    IRC(side.fork(h->ev.bwd));
+    IRC(ip_side_chain(h, c, side.s, lr_step));
+    IRC(side.signal(side_upd ? h->ev.tab : h->ev.join));
+    ip_wgrad<T>(h, c);
+    if (side_upd) {
+        // IPNN_UPDATE_SIDE=1: the dense update runs at the END of the side chain, behind the weight gradients, and the main stream
+        // does NOT wait for it at the end of the step: the next call's mask transposition and gather -- which read neither the dense
+        // weights nor the slabs -- run beside it, and the wait sits in front of the first product (ip_join; ip_join_table in front
+        // of the gather).  Every other entry point joins first.
+        IRC(side.fork(h->ev.wg));
+        ip_dense_update<T>(h, c, side.s, lr_step);
+        IRC(side.signal(h->ev.join));
+        h->tab_pending = h->upd_pending = true;
+    } else {
+        ip_dense_update<T>(h, c, h->st, lr_step);
+        IRC(side.wait(h->ev.join));                             // the step ends when the side chain has
+    }
+    side.settle();
     IHK(h, hipGetLastError());
     return FNN_OK;
 }
@@ -2139,39 +2342,15 @@ int ipnn_create(const ipnn_cfg* cfg, ipnn_handle** out)
     h->wide = h->K > SLOT; h->rw = h->wide ? rup(h->K, 4) : SLOT;
     h->P = cfg->pairs ? h->F * (h->F - 1) / 2 : 0; h->CB = h->F * h->rw + h->P; h->bf16 = cfg->precision == FNN_PREC_BF16;
     h->Bmax = cfg->max_batch; h->ldT = rup(h->Bmax, 256);
-    if (const char* e = getenv("IPNN_GEMM_LDS")) h->gemm_lds = atoi(e) != 0;
-    if (const char* e = getenv("IPNN_STRIP")) h->strip = atoi(e) != 0;
-    if (const char* e = getenv("IPNN_STRIP_DUO")) h->duo = atoi(e);
-    if (const char* e = getenv("IPNN_DUO_MIN")) h->duo_min = std::max(2, atoi(e));
-    if (const char* e = getenv("IPNN_TAIL_SPLIT")) h->tail_split = atoi(e);
+    h->kn = ip_read_knobs();
     { int ncu = 0; if (hipDeviceGetAttribute(&ncu, hipDeviceAttributeMultiprocessorCount, cfg->device) == hipSuccess && ncu > 0) h->n_cu = ncu; }
-    if (const char* e = getenv("IPNN_STRIP_ROT")) h->strip_rot = atoi(e);
-    if (const char* e = getenv("IPNN_STRIP_WARM")) h->strip_warm = atoi(e);
-    if (const char* e = getenv("IPNN_UPDATE_SIDE")) h->upd_side = atoi(e) != 0;
-    if (const char* e = getenv("IPNN_IPF_NT")) h->ipf_nt = atoi(e) == 1024 ? 1024 : 512;
-    if (const char* e = getenv("IPNN_TAIL_FUSE")) h->tail_fuse = atoi(e) != 0;
-    if (const char* e = getenv("IPNN_WT")) h->wt = atoi(e) != 0;
-    h->scat_form = scat1_form_env();
-    h->scat2_form = scat2_form_env();
-    h->sort_merge4 = sort_merge4_env(1);
-    if (const char* e = getenv("IPNN_WIDE")) { int nf = 4, nw = 8; if (sscanf(e, "%d:%d", &nf, &nw) == 2 && ((nf == 2 && (nw == 8 || nw == 12)) || (nf == 4 && nw == 8))) { h->wide_nf = nf; h->wide_nw = nw; } }
-    if (const char* e = getenv("IPNN_TAIL_NW")) h->tail_nw = atoi(e) == 16 ? 16 : 8;
-    if (const char* e = getenv("IPNN_TAIL_NF")) { const int v = atoi(e); if (v == 1 || v == 2 || v == 4) h->tail_nf = v; }
-    if (const char* e = getenv("IPNN_GROUP_XCD")) h->group_xcd = atoi(e);
-    if (const char* e = getenv("IPNN_MASK_SIDE")) h->mask_side = atoi(e);
-    if (const char* e = getenv("IPNN_FWD_SKIP")) h->fwd_skip = atoi(e);
-    const char* side = getenv("IPNN_SIDE_STREAM");
-    if (const char* e = getenv("IPNN_GROUP_WGRAD")) h->group_wgrad = atoi(e) != 0;
     auto fail = [&](int code) { g_ip_err = h->err; ipnn_destroy(h); return code; };
 #define IK(expr) do { hipError_t e2_ = (expr); if (e2_ != hipSuccess) { h->err = std::string(#expr) + ": " + hipGetErrorString(e2_); return fail(FNN_ERR_HIP); } } while (0)
     IK(hipSetDevice(h->dev));
     if (cfg->stream) h->st = (hipStream_t)cfg->stream; else { IK(hipStreamCreateWithFlags(&h->st, hipStreamNonBlocking)); h->own_stream = true; }
-    if (!side || atoi(side) != 0) {
+    if (h->kn.side_stream) {
         IK(hipStreamCreateWithFlags(&h->st2, hipStreamNonBlocking));
-        IK(hipEventCreateWithFlags(&h->ev_fork, hipEventDisableTiming)); IK(hipEventCreateWithFlags(&h->ev_join, hipEventDisableTiming));
-        IK(hipEventCreateWithFlags(&h->ev_mask, hipEventDisableTiming));
-        IK(hipEventCreateWithFlags(&h->ev_bwd, hipEventDisableTiming));
-        IK(hipEventCreateWithFlags(&h->ev_tab, hipEventDisableTiming)); IK(hipEventCreateWithFlags(&h->ev_wg, hipEventDisableTiming));
+        for (hipEvent_t* e : {&h->ev.fork, &h->ev.bwd, &h->ev.wg, &h->ev.join, &h->ev.tab, &h->ev.mask}) IK(hipEventCreateWithFlags(e, hipEventDisableTiming));
     }
     h->d.resize(h->L + 2); h->Dp.resize(h->L + 2);
     h->d[0] = h->F * h->K + h->P + 1; h->Dp[0] = rup(h->CB + 2, 64);
@@ -2183,11 +2362,7 @@ int ipnn_create(const ipnn_cfg* cfg, ipnn_handle** out)
     for (int t = 1; t <= h->L + 1; ++t) {                          // ~256 workgroups of 128 x 128 per product
         const int tiles = ((h->Dp[t - 1] + 127) / 128) * ((h->Dp[t] + 127) / 128);
         int sk = 1;
-        // one launch per product wants ~256 workgroups each; the grouped launch runs all products side by side and is
-        // served best by half of that (measured: 0.353 -> 0.345 ms/step; a quarter: 0.355)
-        int want = h->group_wgrad ? 144 : 288;
-        if (const char* e = getenv("IPNN_WGRAD_WANT")) want = std::max(16, atoi(e));       // tuning knob
-        while (sk < h->splitk && tiles * sk * 2 <= want) sk *= 2;
+        while (sk < h->splitk && tiles * sk * 2 <= h->kn.wgrad_want) sk *= 2;
         h->sk[t - 1] = sk;
     }
     auto al = [&](void** p, size_t bytes) { hipError_t e = hipMalloc(p, bytes); if (e == hipSuccess) e = hipMemsetAsync(*p, 0, bytes, h->st); return e; };
@@ -2208,10 +2383,9 @@ int ipnn_create(const ipnn_cfg* cfg, ipnn_handle** out)
         for (int t = 1; t <= h->L + 1; ++t) {
             const size_t n = (size_t)h->Dp[t - 1] * h->Dp[t];
             IK(al((void**)&h->Wm[t - 1], n * 4)); IK(al((void**)&h->Wv[t - 1], n * 4));
-            if (h->ftrl) hipLaunchKernelGGL(k_fill_f32, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, h->st, h->Wm[t - 1], n, 0.1f);   // initial_accumulator_value
         }
         IK(al((void**)&h->bmv, 8));
-        if (h->ftrl) hipLaunchKernelGGL(k_fill_f32, dim3(1), dim3(64), 0, h->st, h->bmv, (size_t)1, 0.1f);
+        if (ip_reset_dense_state(h) != FNN_OK) return fail(FNN_ERR_HIP);
     }
     h->maskT.assign(h->L + 1, nullptr);
     for (int t = 0; t <= h->L; ++t) IK(al((void**)&h->maskT[t], Ba * h->Dp[t]));
@@ -2241,7 +2415,9 @@ int ipnn_create(const ipnn_cfg* cfg, ipnn_handle** out)
             IK(hipMemcpy(h->ptab, pt.data(), pt.size() * 2, hipMemcpyHostToDevice));
         }
     }
-    if (getenv("IPNN_STAMPS")) { IK(al((void**)&h->stamps, (size_t)2 * (h->ldT / 16) * 16 * 8)); h->stamp_tail = atoi(getenv("IPNN_STAMPS")) == 2; }
+    if (h->kn.stamps) IK(al((void**)&h->stamps, (size_t)2 * (h->ldT / 16) * 16 * 8));
+    if (h->bf16) ip_make_plan<bf16_t>(h); else ip_make_plan<float>(h);
+    if ((h->bf16 ? ip_opt_in<bf16_t>(h) : ip_opt_in<float>(h)) != FNN_OK) return fail(FNN_ERR_HIP);
     IK(hipStreamSynchronize(h->st));
 #undef IK
     *out = h;
@@ -2265,12 +2441,7 @@ int ipnn_destroy(ipnn_handle* h)
     row_group_free(h->rg);
     for (auto& kv : h->prof_ev) for (auto& p : kv.second) { hipEventDestroy(p.first); hipEventDestroy(p.second); }
     if (h->st2) { hipStreamSynchronize(h->st2); hipStreamDestroy(h->st2); }
-    if (h->ev_fork) hipEventDestroy(h->ev_fork);
-    if (h->ev_join) hipEventDestroy(h->ev_join);
-    if (h->ev_mask) hipEventDestroy(h->ev_mask);
-    if (h->ev_bwd) hipEventDestroy(h->ev_bwd);
-    if (h->ev_tab) hipEventDestroy(h->ev_tab);
-    if (h->ev_wg) hipEventDestroy(h->ev_wg);
+    for (hipEvent_t e : {h->ev.fork, h->ev.bwd, h->ev.wg, h->ev.join, h->ev.tab, h->ev.mask}) if (e) hipEventDestroy(e);
     if (h->own_stream && h->st) hipStreamDestroy(h->st);
     delete h;
     return FNN_OK;
@@ -2280,7 +2451,7 @@ int ipnn_sync(ipnn_handle* h)
 {
     if (!h) return FNN_ERR_ARG;
     int flag = 0;
-    { const int jrc = ip_join(h); if (jrc != FNN_OK) return jrc; }
+    IRC(ip_join(h));
     IHK(h, hipMemcpyAsync(&flag, h->err_flag, 4, hipMemcpyDeviceToHost, h->st));
     IHK(h, hipStreamSynchronize(h->st));
     if (flag) {
@@ -2298,7 +2469,7 @@ int ipnn_set_table(ipnn_handle* h, const float* rows, int64_t n_rows)
 {
     if (!h || !rows || n_rows < 1) return FNN_ERR_ARG;
     IHK(h, hipSetDevice(h->dev));
-    { const int jrc = ip_join(h); if (jrc != FNN_OK) return jrc; }
+    IRC(ip_join(h));
     IHK(h, hipStreamSynchronize(h->st));
     if (h->table16) hipFree(h->table16);
     IHK(h, hipMalloc((void**)&h->table16, (size_t)n_rows * h->rw * 4));
@@ -2325,15 +2496,8 @@ int ipnn_set_table(ipnn_handle* h, const float* rows, int64_t n_rows)
         }
         if (h->ftrl) hipLaunchKernelGGL(k_fill_f32, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, h->st, h->tm, n, 0.1f);
         // the optimiser restarts as a whole (as fm_set_table does): every dense layer's and b's state as ipnn_create left them
-        for (int t = 1; t <= h->L + 1; ++t) {
-            const size_t nd = (size_t)h->Dp[t - 1] * h->Dp[t];
-            IHK(h, hipMemsetAsync(h->Wm[t - 1], 0, nd * 4, h->st)); IHK(h, hipMemsetAsync(h->Wv[t - 1], 0, nd * 4, h->st));
-            if (h->ftrl) hipLaunchKernelGGL(k_fill_f32, dim3((unsigned)((nd + 255) / 256)), dim3(256), 0, h->st, h->Wm[t - 1], nd, 0.1f);
-        }
-        IHK(h, hipMemsetAsync(h->bmv, 0, 8, h->st));
-        if (h->ftrl) hipLaunchKernelGGL(k_fill_f32, dim3(1), dim3(64), 0, h->st, h->bmv, (size_t)1, 0.1f);
+        IRC(ip_reset_dense_state(h));
         IHK(h, hipStreamSynchronize(h->st));
-        h->adam_t = 0;
     }
     return FNN_OK;
 }
@@ -2342,7 +2506,7 @@ int ipnn_get_rows(ipnn_handle* h, const int64_t* row_ids, int64_t n, float* out)
 {
     if (!h || !row_ids || !out || n < 1 || !h->table16) return FNN_ERR_ARG;
     IHK(h, hipSetDevice(h->dev));
-    { const int jrc = ip_join(h); if (jrc != FNN_OK) return jrc; }
+    IRC(ip_join(h));
     int64_t* di = nullptr; float* dout = nullptr;
     IHK(h, hipMalloc((void**)&di, n * 8)); IHK(h, hipMalloc((void**)&dout, n * h->K * 4));
     IHK(h, hipMemcpy(di, row_ids, n * 8, hipMemcpyHostToDevice));
@@ -2359,7 +2523,7 @@ int ipnn_set_b(ipnn_handle* h, float b)
 {
     if (!h) return FNN_ERR_ARG;
     IHK(h, hipSetDevice(h->dev));
-    { const int jrc = ip_join(h); if (jrc != FNN_OK) return jrc; }
+    IRC(ip_join(h));
     IHK(h, hipStreamSynchronize(h->st));
     IHK(h, hipMemcpy(h->b, &b, 4, hipMemcpyHostToDevice));
     return FNN_OK;
@@ -2368,7 +2532,7 @@ int ipnn_get_b(ipnn_handle* h, float* b)
 {
     if (!h || !b) return FNN_ERR_ARG;
     IHK(h, hipSetDevice(h->dev));
-    { const int jrc = ip_join(h); if (jrc != FNN_OK) return jrc; }
+    IRC(ip_join(h));
     IHK(h, hipStreamSynchronize(h->st));
     IHK(h, hipMemcpy(b, h->b, 4, hipMemcpyDeviceToHost));
     return FNN_OK;
@@ -2393,7 +2557,7 @@ int ipnn_set_layer(ipnn_handle* h, int layer, const float* W, const float* bias)
     for (int r = 0; r < din; ++r) memcpy(&p[(size_t)ip_row_of(h, layer, r) * Dout], &W[(size_t)r * dout], (size_t)dout * 4);
     const int ones_row = layer == 1 ? h->CB + 1 : din;
     memcpy(&p[(size_t)ones_row * Dout], bias, (size_t)dout * 4);
-    { const int jrc = ip_join(h); if (jrc != FNN_OK) return jrc; }
+    IRC(ip_join(h));
     IHK(h, hipStreamSynchronize(h->st));
     IHK(h, hipMemcpy(h->W[layer - 1], p.data(), p.size() * 4, hipMemcpyHostToDevice));
     if (h->bf16) ip_refresh<bf16_t>(h, layer, nullptr, 0.f); else ip_refresh<float>(h, layer, nullptr, 0.f);
@@ -2407,7 +2571,7 @@ int ipnn_get_layer(ipnn_handle* h, int layer, float* W, float* bias)
     IHK(h, hipSetDevice(h->dev));
     const int din = h->d[layer - 1], dout = h->d[layer], Din = h->Dp[layer - 1], Dout = h->Dp[layer];
     std::vector<float> p((size_t)Din * Dout);
-    { const int jrc = ip_join(h); if (jrc != FNN_OK) return jrc; }
+    IRC(ip_join(h));
     IHK(h, hipStreamSynchronize(h->st));
     IHK(h, hipMemcpy(p.data(), h->W[layer - 1], p.size() * 4, hipMemcpyDeviceToHost));
     for (int r = 0; r < din; ++r) memcpy(&W[(size_t)r * dout], &p[(size_t)ip_row_of(h, layer, r) * Dout], (size_t)dout * 4);
@@ -2432,11 +2596,10 @@ static int ip_train_step(ipnn_handle* h, const int32_t* ids, const float* wts, c
     if (h->duo_failed) IFAIL(h, FNN_ERR_STATE, "an earlier step failed (StripDuo swap timed out): re-create the handle");
     IHK(h, hipSetDevice(h->dev));
     if (draw && !h->mask0) IHK(h, hipMalloc((void**)&h->mask0, (size_t)h->Bmax * h->d[0]));      // every byte a step reads is drawn by that step
-    int rc = h->bf16 ? ip_run<bf16_t>(h, ids, wts, y, B, masks, logits_out, nullptr, true, draw)
-                     : ip_run<float>(h, ids, wts, y, B, masks, logits_out, nullptr, true, draw);
-    if (rc != FNN_OK) return rc;
+    const IpCall c{ids, wts, y, B, masks, draw, logits_out, nullptr, true};
+    IRC(h->bf16 ? ip_run<bf16_t>(h, c) : ip_run<float>(h, c));
     if (loss_sum_out) {                                      // (the loss is summed in the update launch: join it)
-        { const int jrc = ip_join(h); if (jrc != FNN_OK) return jrc; }
+        IRC(ip_join(h));
         IHK(h, hipMemcpyAsync(loss_sum_out, h->loss_dev, 4, hipMemcpyDeviceToHost, h->st));
         return ipnn_sync(h);
     }
@@ -2484,8 +2647,8 @@ int ipnn_predict_w(ipnn_handle* h, const int32_t* ids, const float* wts, int B, 
     if (B < 1 || B > h->Bmax) IFAIL(h, FNN_ERR_ARG, "B must be in [1, max_batch]");
     if (!h->table16) IFAIL(h, FNN_ERR_STATE, "ipnn_set_table has not been called");
     IHK(h, hipSetDevice(h->dev));
-    return h->bf16 ? ip_run<bf16_t>(h, ids, wts, nullptr, B, nullptr, nullptr, p_out, false)
-                   : ip_run<float>(h, ids, wts, nullptr, B, nullptr, nullptr, p_out, false);
+    const IpCall c{ids, wts, nullptr, B, nullptr, nullptr, nullptr, p_out, false};
+    return h->bf16 ? ip_run<bf16_t>(h, c) : ip_run<float>(h, c);
 }
 
 int ipnn_eval(ipnn_handle* h, const int32_t* ids, const int32_t* y, int64_t N, double* auc, double* rmse, double* logloss)
@@ -2503,8 +2666,8 @@ int ipnn_eval_w(ipnn_handle* h, const int32_t* ids, const float* wts, const int3
     for (int64_t lo = 0; lo < N; lo += h->Bmax) {
         const int B = (int)(N - lo < h->Bmax ? N - lo : h->Bmax);
         const float* w = wts ? wts + lo * h->F : nullptr;        // the chunk's weights travel with its ids
-        const int rc = h->bf16 ? ip_run<bf16_t>(h, ids + lo * h->F, w, nullptr, B, nullptr, nullptr, p_d + lo, false)
-                               : ip_run<float>(h, ids + lo * h->F, w, nullptr, B, nullptr, nullptr, p_d + lo, false);
+        const IpCall c{ids + lo * h->F, w, nullptr, B, nullptr, nullptr, nullptr, p_d + lo, false};
+        const int rc = h->bf16 ? ip_run<bf16_t>(h, c) : ip_run<float>(h, c);
         if (rc != FNN_OK) { hipFree(p_d); return rc; }
     }
     double out[4] = {0, 0, 0, 0};
@@ -2524,52 +2687,57 @@ int ipnn_eval_w(ipnn_handle* h, const int32_t* ids, const float* wts, const int3
 int ipnn_prof_enable(ipnn_handle* h, int on)
 {
     if (!h) return FNN_ERR_ARG;
-    { const int jrc = ip_join(h); if (jrc != FNN_OK) return jrc; }
+    IRC(ip_join(h));
     IHK(h, hipStreamSynchronize(h->st));
     if (on) { for (auto& kv : h->prof_ev) for (auto& p : kv.second) { hipEventDestroy(p.first); hipEventDestroy(p.second); } h->prof_ev.clear(); }
     h->prof = on != 0;
     return FNN_OK;
 }
 
+// IPNN_STAMPS: the last step's per-layer time stamps of the strip launches of one direction ("fwd" / "bwd"), to stderr
+static int ip_print_stamps(ipnn_handle* h, const char* which)
+{
+    const bool fwd = !strcmp(which, "fwd"), tail = h->kn.stamps == 2;
+    const bool duo = h->duo_xch != nullptr && !tail;           // pairs: even workgroups run the whole stack, odd ones the wide products only
+    const int nwg = tail ? h->ldT / 16 : h->ldT / (h->bf16 ? 32 : 16) * (duo ? 2 : 1), np = h->L + 3, step = duo ? 2 : 1;
+    std::vector<long long> st((size_t)nwg * 16);
+    IHK(h, hipMemcpy(st.data(), h->stamps + (fwd ? 0 : (size_t)(h->ldT / 16) * 16), st.size() * 8, hipMemcpyDeviceToHost));
+    auto at = [&](int w, int i) { return st[(size_t)w * 16 + i]; };
+    for (int par = 0; par < step; ++par) {
+        long long t0 = at(par, 0), t1 = 0; int cnt = 0;
+        for (int w = par; w < nwg; w += step) {
+            t0 = std::min(t0, at(w, 0)); ++cnt;
+            for (int i = 0; i < np; ++i) t1 = std::max(t1, at(w, i));
+        }
+        fprintf(stderr, "[ipnn stamps %s%s] %d workgroups, first start -> last stamp %lld ticks; avg ticks per phase (load, then products):", which,
+                duo ? (par ? " odd" : " even") : "", cnt, t1 - t0);
+        for (int i = 1; i < np; ++i) {
+            double s2 = 0; int c2 = 0;
+            for (int w = par; w < nwg; w += step) if (at(w, i) > at(w, i - 1)) { s2 += (double)(at(w, i) - at(w, i - 1)); ++c2; }
+            fprintf(stderr, " %.0f", c2 ? s2 / c2 : 0.0);
+        }
+        double sk = 0, d3[3] = {0, 0, 0};
+        for (int w = par; w < nwg; w += step) sk += (double)(at(w, 0) - t0);
+        fprintf(stderr, " | avg start skew %.0f", sk / cnt);
+        if (h->kn.stamp_sel >= 0 && fwd) {
+            for (int w = par; w < nwg; w += step) for (int i = 0; i < 3; ++i) d3[i] += (double)(at(w, 11 + i) - at(w, 10 + i));
+            fprintf(stderr, " | product %d, wave 0, last block: aux+product %.0f, next+prefetch %.0f, epilogue %.0f", h->kn.stamp_sel, d3[0] / cnt, d3[1] / cnt, d3[2] / cnt);
+        } else if (duo) {
+            for (int w = par; w < nwg; w += 2) for (int i = 0; i < 3; ++i) d3[i] += (double)at(w, 11 + i);
+            fprintf(stderr, " | swaps in all: drain+barrier %.0f, flag wait %.0f, pull %.0f", d3[0] / cnt, d3[1] / cnt, d3[2] / cnt);
+        }
+        fprintf(stderr, "\n");
+    }
+    return FNN_OK;
+}
+
 int ipnn_prof_get(ipnn_handle* h, const char* which, double* avg_ms)
 {
     if (!h || !which || !avg_ms) return FNN_ERR_ARG;
-    { const int jrc = ip_join(h); if (jrc != FNN_OK) return jrc; }
+    IRC(ip_join(h));
     IHK(h, hipStreamSynchronize(h->st));
     *avg_ms = 0.0;
-    if (h->stamps && (!strcmp(which, "fwd") || !strcmp(which, "bwd"))) {      // IPNN_STAMPS=1: the last step's per-layer stamps
-        const bool duo = h->duo_xch != nullptr && !h->stamp_tail;  // pairs: even workgroups run the whole stack, odd ones the wide products only
-        const int nwg = h->stamp_tail ? h->ldT / 16 : h->ldT / (h->bf16 ? 32 : 16) * (duo ? 2 : 1), np = h->L + 3;
-        std::vector<long long> st((size_t)nwg * 16);
-        IHK(h, hipMemcpy(st.data(), h->stamps + (strcmp(which, "bwd") ? 0 : (size_t)(h->ldT / 16) * 16), st.size() * 8, hipMemcpyDeviceToHost));
-        for (int par = 0; par < (duo ? 2 : 1); ++par) {
-            long long t0 = st[(size_t)par * 16], t1 = 0; int cnt = 0;
-            for (int w = par; w < nwg; w += duo ? 2 : 1) {
-                t0 = std::min(t0, st[(size_t)w * 16]); ++cnt;
-                for (int i = 0; i < np; ++i) t1 = std::max(t1, st[(size_t)w * 16 + i]);
-            }
-            fprintf(stderr, "[ipnn stamps %s%s] %d workgroups, first start -> last stamp %lld ticks; avg ticks per phase (load, then products):", which,
-                    duo ? (par ? " odd" : " even") : "", cnt, t1 - t0);
-            for (int i = 1; i < np; ++i) {
-                double s2 = 0; int c2 = 0;
-                for (int w = par; w < nwg; w += duo ? 2 : 1)
-                    if (st[(size_t)w * 16 + i] > st[(size_t)w * 16 + i - 1]) { s2 += (double)(st[(size_t)w * 16 + i] - st[(size_t)w * 16 + i - 1]); ++c2; }
-                fprintf(stderr, " %.0f", c2 ? s2 / c2 : 0.0);
-            }
-            double sk = 0; for (int w = par; w < nwg; w += duo ? 2 : 1) sk += (double)(st[(size_t)w * 16] - t0);
-            fprintf(stderr, " | avg start skew %.0f", sk / cnt);
-            if (getenv("IPNN_STAMP_SEL") && !strcmp(which, "fwd")) {
-                double dd[3] = {0, 0, 0};
-                for (int w = par; w < nwg; w += duo ? 2 : 1) for (int i = 0; i < 3; ++i) dd[i] += (double)(st[(size_t)w * 16 + 11 + i] - st[(size_t)w * 16 + 10 + i]);
-                fprintf(stderr, " | product %s, wave 0, last block: aux+product %.0f, next+prefetch %.0f, epilogue %.0f", getenv("IPNN_STAMP_SEL"), dd[0] / cnt, dd[1] / cnt, dd[2] / cnt);
-            } else if (duo) {
-                double acc3[3] = {0, 0, 0};
-                for (int w = par; w < nwg; w += 2) for (int i = 0; i < 3; ++i) acc3[i] += (double)st[(size_t)w * 16 + 11 + i];
-                fprintf(stderr, " | swaps in all: drain+barrier %.0f, flag wait %.0f, pull %.0f", acc3[0] / cnt, acc3[1] / cnt, acc3[2] / cnt);
-            }
-            fprintf(stderr, "\n");
-        }
-    }
+    if (h->stamps && (!strcmp(which, "fwd") || !strcmp(which, "bwd"))) IRC(ip_print_stamps(h, which));
     auto it = h->prof_ev.find(which);
     if (it == h->prof_ev.end() || it->second.empty()) return FNN_OK;
     double tot = 0.0;
