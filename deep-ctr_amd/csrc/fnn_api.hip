@@ -32,35 +32,66 @@ struct ProfSlot { std::vector<std::pair<hipEvent_t, hipEvent_t>> ev; double ms =
 inline int rup(int x, int m) { return (x + m - 1) / m * m; }
 constexpr int WIDE_XW_MAX = 4096;    // wide FM rows: largest n_fields * rup(k, 4) (16 fields x k = 128: 2048; 39 x k = 101: 4056)
 
+// The A/B knobs of a handle, read from the environment ONCE, by read_knobs at the top of fnn_create: a variable changed while a
+// handle lives does nothing to it.  (Read later, where they always were: FNN_DP_PAYLOAD in dp_setup, FNN_P2P_REGION and
+// FNN_P2P_TIMEOUT_MS in fnn_dp_p2p_export.)
+struct FnnKnobs {
+    int wt_stores = 47;         // FNN_WT_STORES (MlpArgs::wt; 0: plain stores): how the strip kernel's training outputs leave
+                                // (bit 32: bf16 on FM rows, the transposed activations 16 bytes per lane, written through or plain as bit 1 says)
+    int step1_waves = 8;        // FNN_STEP1_WAVES=4: four waves per strip (the 2-byte element types at hidden 300 / 100 run eight)
+    bool step1_fixed = true;    // FNN_STEP1_FORM=generic: never the fixed training instance of the strip kernel (step1_sel)
+    bool fused = true;          // FNN_NO_FUSE=1: the layer-by-layer kernels instead of the strip kernel
+    int role_off = 0;           // FNN_ROLE_OFF, diagnostics only: 1 sort, 2 dense, 4 sparse roles of launches 2 / 3 skipped (make_roles)
+    int splitk = 0;             // FNN_SPLITK=2|4|8|16: split-K of the weight-gradient products (0: the plan's choice)
+    int scat2_wgs = 256;        // FNN_SCAT2_WGS=16..1024: workgroups walking the multi-chunk segments in launch 3
+    int wgrad_form = -1;        // FNN_WGRAD_FORM=direct|lds (-1: the plan's choice, -2: neither word)
+    int scat_form = SCAT1_HALF;      // FNN_SCAT1_FORM: the body of level 1 of the sparse-row update (scat1h_body; quarter: scat1q_body, slot: scat1_body)
+    int scat2_form = SCAT2_WAVE;     // FNN_SCAT2_FORM: the body of level 2 of the 16-float rows (scat2w_body, a wave per multi-chunk segment; block: scat2_body)
+    int sort_merge4 = 1;        // FNN_SORT_RUNS=4 (the default on FM rows): the run sort leaves 4 runs of 1024 keys per field for the rank merge; 16 (bag mode's default): 16 runs of 256
+};
+
+// A launchable kernel: what a selector (step1_sel / step2_sel / step3_sel) returns
+template <typename... A> struct FnnKernel { void (*fn)(A...) = nullptr; int threads = 0; size_t lds = 0; };
+template <typename T> using Step1Kernel = FnnKernel<MlpArgs<T>>;
+using Step2Kernel = FnnKernel<SortArgs, WgradArgs, int, int, ScatArgs>;
+using Step3Kernel = FnnKernel<SortArgs, TailArgs, ScatArgs>;
+
+// What the configuration and the knobs decide of every call on a handle: made once, by make_plan and plan_step1 in fnn_create.  The
+// half that hangs on the width of the sort keys is plan_keys', which fnn_set_table calls again.  What a call adds is its batch
+// length and the shadowed features (step_impl).  DESIGN.md section 4, "The step's host side".
+struct FnnPlan {
+    // shapes
+    int F = 0, K = 0, H1 = 0, H2 = 0, xdim = 0, K1p = 0, H1p = 0, H2p = 0;
+    int Bmax = 0, ldT = 0, N2max = 0;
+    size_t n1 = 0, n2 = 0, nw12 = 0, nw = 0, nslab = 0;
+    bool bf16 = false;          // FNN_PREC_BF16: 2-byte elements
+    bool split = false;         // FNN_PREC_BF16X3: 4-byte elements (bs16_t), the f32 mode's layouts
+    bool bag = false; int rw = SLOT; size_t nbag = 0, off_bag = 0;     // FNN_MODE_BAG: bag rows rw floats wide
+    bool wide = false;          // FNN_MODE_FM with k >= 17: FM rows of rw = rup(k, 4) floats, w_0 / ones columns F*rw and F*rw + 1
+    // paths
+    bool strip_shape = false;   // the strip kernel is built for these padded shapes (strip_shape_ok)
+    bool strip_ok = false;      // ... and FNN_NO_FUSE does not turn it off: k_step1 instead of gather / fwd1 / fwd2 / head / bwd1 / gx
+    int three_launch_max_B = 0; // the longest batch that trains in the three launches: SORT_N where strip_ok, else none does
+    int splitk = 4;             // split-K of the weight-gradient products
+    int wgrad_lds = 0;          // the bf16 weight-gradient products stage their operands through LDS (wgrad_tile; f32 and the bf16 pairs keep their register ring)
+    // kernels
+    FnnKernel<> step1[2];       // [train]: a Step1Kernel<T> of the handle's element type (launch_step1 casts it back)
+    bool key64 = false;         // 64-bit sort keys (row << 12 | t does not fit 32 bits)
+    Step2Kernel step2[2];       // [the launch carries LDS-form weight gradients]; lds: the sort role's share
+    Step3Kernel step3[2];       // [update]
+};
+
 }  // namespace
 
-struct fnn_handle {
+struct fnn_handle : FnnPlan {
     fnn_cfg cfg{};
     std::string err;
     int dev = 0;
     hipStream_t st = nullptr;
     bool own_stream = false;
-    // shapes
-    int F = 0, K = 0, H1 = 0, H2 = 0, xdim = 0, K1p = 0, H1p = 0, H2p = 0;
-    int Bmax = 0, ldT = 0, N2max = 0;
-    size_t n1 = 0, n2 = 0, nw12 = 0, nw = 0;
-    int splitk = 4;             // split-K of the weight-gradient products (measured beside scat1_body: 4 -> 40.8 us per step, 8 -> 42.9, 2 -> 51.1; fnn_create: 8 beside scat1q_body)
-    int scat2_wgs = 256;        // workgroups walking the multi-chunk segments in launch 3
-    int sort_merge4 = 1;        // FNN_SORT_RUNS=4 (the default on FM rows): the run sort leaves 4 runs of 1024 keys per field for the rank merge; 16 (bag mode's default): 16 runs of 256
-    int wgrad_lds = 0;          // FNN_WGRAD_FORM=lds: the bf16 weight-gradient products stage their operands through LDS (wgrad_tile; f32 and the bf16 pairs keep their register ring)
-    int scat2_form = SCAT2_WAVE;     // FNN_SCAT2_FORM: the body of level 2 of the 16-float rows (scat2w_body, a wave per multi-chunk segment; block: scat2_body)
-    int scat_form = SCAT1_HALF;      // FNN_SCAT1_FORM: the body of level 1 of the sparse-row update (scat1h_body; quarter: scat1q_body, slot: scat1_body)
-    bool bf16 = false;          // FNN_PREC_BF16: 2-byte elements
-    bool split = false;         // FNN_PREC_BF16X3: 4-byte elements (bs16_t), the f32 mode's layouts
-    int step1_waves = 8;                                               // FNN_STEP1_WAVES=4: four waves per strip (the 2-byte element types at hidden 300 / 100 run eight)
-    bool step1_fixed = true;                                           // FNN_STEP1_FORM=generic: never the fixed training instance of the strip kernel (launch_step1)
-    int wt_stores = 47;                                              // FNN_WT_STORES (MlpArgs::wt; 0: plain stores): how the strip kernel's training outputs leave
-                                                                       // (bit 32: bf16 on FM rows, the transposed activations 16 bytes per lane, written through or plain as bit 1 says)
-    bool bag = false; int rw = SLOT; size_t nbag = 0, off_bag = 0;     // FNN_MODE_BAG: bag rows rw floats wide
-    bool wide = false;          // FNN_MODE_FM with k >= 17: FM rows of rw = rup(k, 4) floats, w_0 / ones columns F*rw and F*rw + 1
-    float* bb0 = nullptr; void* dlxT = nullptr; void* onesT = nullptr; float* gx_raw = nullptr;
-    bool fused = true;          // one k_mlp launch instead of gather/fwd1/fwd2/head/bwd1/gx
-    int role_off = 0;           // diagnostics only (FNN_ROLE_OFF): 1 sort, 2 dense, 4 sparse roles of launches 2/3 skipped
+    FnnKnobs kn;
+    std::vector<void*> owned;   // device buffers that live as long as the handle (alloc_owned): fnn_destroy frees them from this record
+    float* bb0 = nullptr; void* dlxT = nullptr; void* onesT = nullptr; float* gx_raw = nullptr;     // bag mode
     // FM table
     float* table16 = nullptr; int32_t* field_of_row = nullptr; int64_t n_rows = 0; float w0 = 0.f;
     // dense
@@ -70,9 +101,8 @@ struct fnn_handle {
     // activations (T) and f32 work buffers
     void *xp = nullptr, *xpT = nullptr, *d1 = nullptr, *d1T = nullptr, *d2 = nullptr, *dl2 = nullptr,
          *dl2T = nullptr, *dl1 = nullptr, *dl1T = nullptr;
-    float *gxp = nullptr, *p_buf = nullptr, *loss_t = nullptr, *loss_dev = nullptr;
+    float *gxp = nullptr, *loss_t = nullptr, *loss_dev = nullptr;
     void *d2T = nullptr, *dl3T = nullptr;
-    size_t nslab = 0;
     // scatter
     // Grouping results (sorted (row, t) records + level-2 work lists), double-buffered: the slot of
     // the batch being trained and the slot the NEXT batch is grouped into during this step.
@@ -83,7 +113,6 @@ struct fnn_handle {
     SortSlot slot[2]; int cur = 0;
     const int32_t* sorted_ids = nullptr; int sorted_B = 0;      // what slot[cur] holds (nullptr: nothing)
     const int32_t* next_ids = nullptr; int next_B = 0;          // pending fnn_prefetch_ids request
-    bool key64 = false;
     void* skeys = nullptr;              // phase-A output of the split sort
     double* cpow_dev = nullptr;
     std::vector<double> cpow_host; double cpow_c = -1.0; int cpow_n = 0;
@@ -120,15 +149,11 @@ struct fnn_handle {
     std::map<std::string, ProfSlot> prof_slots;
 };
 
-#define HIPCHK(h, expr)                                                                         \
-    do {                                                                                        \
-        hipError_t e_ = (expr);                                                                 \
-        if (e_ != hipSuccess) {                                                                 \
-            (h)->err = std::string(#expr) + ": " + hipGetErrorString(e_);                       \
-            return FNN_ERR_HIP;                                                                 \
-        }                                                                                       \
-    } while (0)
-#define FAIL(h, code, msg) do { (h)->err = (msg); return (code); } while (0)
+// The early returns of every entry point; what follows the named arguments is a cleanup statement run before the return.
+// HIPCHK: a failing HIP call leaves "<its text>: <the error's string>"; FAIL: a refusal with its message; RCCHK: a callee's code (and message) passed on.
+#define HIPCHK(h, expr, ...) do { hipError_t e_ = (expr); if (e_ != hipSuccess) { (h)->err = std::string(#expr) + ": " + hipGetErrorString(e_); __VA_ARGS__; return FNN_ERR_HIP; } } while (0)
+#define FAIL(h, code, msg, ...) do { (h)->err = (msg); __VA_ARGS__; return (code); } while (0)
+#define RCCHK(expr, ...) do { const int rc_ = (expr); if (rc_ != FNN_OK) { __VA_ARGS__; return rc_; } } while (0)
 
 namespace {
 
@@ -150,6 +175,30 @@ template <typename T> int alloc_dev(fnn_handle* h, T** p, size_t n, bool zero = 
     if (zero) HIPCHK(h, hipMemsetAsync(*p, 0, n * sizeof(T), h->st));
     return FNN_OK;
 }
+// a buffer that fnn_create allocates and nothing regrows: recorded as it is allocated, freed by fnn_destroy from the record
+template <typename T> int alloc_owned(fnn_handle* h, T** p, size_t n, bool zero = true) {
+    const int rc = alloc_dev(h, p, n, zero);
+    if (*p) h->owned.push_back(*p);
+    return rc;
+}
+
+// Host pointers (FNN_MEM_HOST) of a call go through the handle's staging buffers; device pointers pass untouched.  in(): copy an
+// input up and point at the copy; out(): point a result at its staging buffer; copy_back(): enqueue the results' way home (the
+// caller synchronises).
+struct Staged {
+    fnn_handle* h; bool host; struct { void* dst; const void* src; size_t bytes; } back[2] = {}; int nback = 0;
+    template <typename T> int in(const T*& p, T* buf, size_t n) {
+        if (!host) return FNN_OK;
+        HIPCHK(h, hipMemcpyAsync(buf, p, n * sizeof(T), hipMemcpyHostToDevice, h->st));
+        p = buf;
+        return FNN_OK;
+    }
+    template <typename T> void out(T*& p, T* buf, size_t n) { if (host && p) { back[nback++] = {p, buf, n * sizeof(T)}; p = buf; } }
+    int copy_back() {
+        for (int i = 0; i < nback; ++i) HIPCHK(h, hipMemcpyAsync(back[i].dst, back[i].src, back[i].bytes, hipMemcpyDeviceToHost, h->st));
+        return FNN_OK;
+    }
+};
 
 size_t tsize(const fnn_handle* h) { return h->bf16 ? 2 : 4; }
 // the element type of the handle's precision: FN<T> ARGS
@@ -200,10 +249,10 @@ template <typename T> void launch_update(fnn_handle* h, const float* bucket, flo
 
 // the strip kernel is instantiated for the padded shapes in use; anything else takes the
 // layer-by-layer kernels
-bool mlp_shape_ok(const fnn_handle* h) {
-    if (h->wide) return false;                               // the strip kernel reads 16-float slots
-    const int c1 = h->H1p / 64, c2 = h->H2p / 64, cx = h->K1p / 64;
-    if (cx == 5) return h->bag && c1 == 5 && c2 == 2;        // bag rows 256..316 wide: the reference's default hidden0 = 300 (python/SNN_RBM.py:25)
+bool strip_shape_ok(const FnnPlan& p) {
+    if (p.wide) return false;                                // the strip kernel reads 16-float slots
+    const int c1 = p.H1p / 64, c2 = p.H2p / 64, cx = p.K1p / 64;
+    if (cx == 5) return p.bag && c1 == 5 && c2 == 2;         // bag rows 256..316 wide: the reference's default hidden0 = 300 (python/SNN_RBM.py:25)
     return cx == 4 && ((c1 == 5 && c2 == 2) || (c1 == 1 && c2 == 1));
 }
 // a fresh stamp for a grouping about to be written into `sl` (bag mode; see SortArgs).  2^25 groupings, then the tags start over.
@@ -234,7 +283,7 @@ int wgrad_blocks(const WgradArgs& wa) {
 }
 ScatArgs make_scat_args(fnn_handle* h, const fnn_handle::SortSlot& sl, int N2) {
     ScatArgs sa = scat_args(sl, N2, h->F, h->K, h->gxp, h->K1p, h->cpow_dev, (double)h->cfg.lr, h->table16, h->rw);
-    sa.tag_shared = sl.tag_shared; sa.stamp = sl.stamp; sa.form2 = h->scat2_form;
+    sa.tag_shared = sl.tag_shared; sa.stamp = sl.stamp; sa.form2 = h->kn.scat2_form;
     return sa;
 }
 template <typename T> MlpArgs<T> make_mlp_args(fnn_handle* h, const int32_t* ids, const float* y, int B,
@@ -244,145 +293,139 @@ template <typename T> MlpArgs<T> make_mlp_args(fnn_handle* h, const int32_t* ids
                       m1 ? m1 : h->ones_u8, m2 ? m2 : h->ones_u8, h->cfg.act, train ? ACT_TANH : h->cfg.act,
                       h->H1, h->H2, train ? 1 : 0,
                       (T*)h->xpT, (T*)h->d1T, (T*)h->d2T, (T*)h->dl1T, (T*)h->dl2T, (T*)h->dl3T, h->ldT,
-                      h->gxp, p_out, h->loss_t, h->err_flag, h->bb0, h->rw, (T*)h->dlxT, nullptr, h->wt_stores};
+                      h->gxp, p_out, h->loss_t, h->err_flag, h->bb0, h->rw, (T*)h->dlxT, nullptr, h->kn.wt_stores};
 }
+// ---- kernel selectors: the only places that name an instantiation of k_step1, k_step2 or k_step3
+// The strip kernel by padded shape (strip_shape_ok), waves per strip and form.  Hidden 300 / 100 runs EIGHT waves per strip (two
+// per SIMD), a layer's 16-column fragments in runs of ceil(n / 8) per wave -- the strip is a chain of phases, each as long as its
+// busiest wave's run (FNN_STEP1_WAVES=4: four waves).  The fixed training form (mlp_body, WTF): a training step of the default
+// store policy in bf16 on FM rows, whose gather is one trip of the workgroup (8-example pieces in groups of 16, two lanes each:
+// F <= 32); FNN_STEP1_FORM=generic and everything else -- prediction, any other FNN_WT_STORES -- run the instance that reads its flags.
+template <typename T> Step1Kernel<T> step1_sel(const FnnPlan& p, const FnnKnobs& kn, bool train)
+{
+#define STEP1(C1, C2, CX, BAG, NW, ...) Step1Kernel<T>{k_step1<T, C1, C2, CX, BAG, NW, ##__VA_ARGS__>, 64 * NW, mlp_lds_bytes<T, C1, C2, CX>(BAG, p.F, NW)}
+    const bool big = p.H1p / 64 == 5, x5 = p.K1p / 64 == 5;             // x5: bag mode only (strip_shape_ok)
+    if (big && kn.step1_waves == 8) {
+        if (x5) return STEP1(5, 2, 5, true, 8);
+        if (p.bag) return STEP1(5, 2, 4, true, 8);
+        if constexpr (std::is_same<T, bf16_t>::value)
+            if (kn.step1_fixed && train && kn.wt_stores == 47 && ((8 * p.F + 15) >> 4) * 32 <= 512) return STEP1(5, 2, 4, false, 8, 47);
+        return STEP1(5, 2, 4, false, 8);
+    }
+    if (x5) return STEP1(5, 2, 5, true, 4);
+    if (p.bag) return big ? STEP1(5, 2, 4, true, 4) : STEP1(1, 1, 4, true, 4);
+    return big ? STEP1(5, 2, 4, false, 4) : STEP1(1, 1, 4, false, 4);
+#undef STEP1
+}
+// launch 2 by key width x merge form x weight-gradient form (the LDS form: 2-byte elements only); lds: the run sort's share
+template <typename T> Step2Kernel step2_sel(bool key64, bool m4, bool wgrad_lds)
+{
+#define STEP2(WF) (key64 ? (m4 ? Step2Kernel{k_step2<T, unsigned long long, true, WF>, 256, lds} : Step2Kernel{k_step2<T, unsigned long long, false, WF>, 256, lds}) \
+                         : (m4 ? Step2Kernel{k_step2<T, unsigned, true, WF>, 256, lds} : Step2Kernel{k_step2<T, unsigned, false, WF>, 256, lds}))
+    const size_t lds = key64 ? sortA_lds_bytes<unsigned long long>(m4) : sortA_lds_bytes<unsigned>(m4);
+    if constexpr (sizeof(T) == 2) if (wgrad_lds) return STEP2(WGRAD_LDS);
+    return STEP2(WGRAD_DIRECT);
+#undef STEP2
+}
+// launch 3 by key width x merge form x update; lds: the rank merge's
+template <typename T> Step3Kernel step3_sel(bool key64, bool m4, bool update)
+{
+#define STEP3(KT, LDS) (m4 ? (update ? Step3Kernel{k_step3<T, true, KT, true>, 256, LDS} : Step3Kernel{k_step3<T, false, KT, true>, 256, LDS}) \
+                           : (update ? Step3Kernel{k_step3<T, true, KT, false>, 256, LDS} : Step3Kernel{k_step3<T, false, KT, false>, 256, LDS}))
+    return key64 ? STEP3(unsigned long long, sort_lds_bytes<unsigned long long>()) : STEP3(unsigned, sort_lds_bytes<unsigned>());
+#undef STEP3
+}
+// the plan's kernels: launch 1 for prediction and training, made at create ...
+template <typename T> void plan_step1(fnn_handle* h)
+{
+    for (int train = 0; train < 2; ++train) {
+        const Step1Kernel<T> k = step1_sel<T>(*h, h->kn, train != 0);
+        h->step1[train] = {reinterpret_cast<void (*)()>(k.fn), k.threads, k.lds};
+    }
+}
+// ... and launches 2 and 3, which change with the width of the sort keys: at create and whenever a table is set
+template <typename T> void plan_keys(fnn_handle* h, bool key64)
+{
+    h->key64 = key64;
+    for (int i = 0; i < 2; ++i) {
+        h->step2[i] = step2_sel<T>(key64, h->kn.sort_merge4 != 0, i && h->wgrad_lds);
+        h->step3[i] = step3_sel<T>(key64, h->kn.sort_merge4 != 0, i != 0);
+    }
+}
+
 template <typename T> void launch_step1(fnn_handle* h, int nmlp, const MlpArgs<T>& a) {
-    const bool big = h->H1p / 64 == 5;
-    const dim3 g(nmlp), b(256);
-    {
-        // hidden 300 / 100: EIGHT waves per strip (two per SIMD), a layer's 16-column fragments in runs of
-        // ceil(n / 8) per wave -- the strip is a chain of phases, each as long as its busiest wave's run (FNN_STEP1_WAVES=4: four waves)
-        if (big && h->step1_waves == 8) {
-            const dim3 b8(512);
-            if (h->K1p / 64 == 5) {
-                const size_t lds = mlp_lds_bytes<T, 5, 2, 5>(true, h->F, 8);
-                hipLaunchKernelGGL((k_step1<T, 5, 2, 5, true, 8>), g, b8, lds, h->st, a);
-            } else if (h->bag) {
-                const size_t lds = mlp_lds_bytes<T, 5, 2, 4>(true, h->F, 8);
-                hipLaunchKernelGGL((k_step1<T, 5, 2, 4, true, 8>), g, b8, lds, h->st, a);
-            } else {
-                const size_t lds = mlp_lds_bytes<T, 5, 2, 4>(false, h->F, 8);
-                // the fixed training form (mlp_body, WTF): a training step of the default store policy in bf16, whose gather is
-                // one trip of the workgroup (8-example pieces in groups of 16, two lanes each: F <= 32); FNN_STEP1_FORM=generic
-                // and everything else -- prediction, any other FNN_WT_STORES -- run the instance that reads its flags
-                if constexpr (std::is_same<T, bf16_t>::value) {
-                    if (h->step1_fixed && a.train == 1 && a.wt == 47 && ((8 * h->F + 15) >> 4) * 32 <= 512) {
-                        hipLaunchKernelGGL((k_step1<T, 5, 2, 4, false, 8, 47>), g, b8, lds, h->st, a);
-                        return;
-                    }
-                }
-                hipLaunchKernelGGL((k_step1<T, 5, 2, 4, false, 8>), g, b8, lds, h->st, a);
-            }
-            return;
-        }
-    }
-    if (h->K1p / 64 == 5) {                                      // bag mode only (mlp_shape_ok)
-        const size_t lds5 = mlp_lds_bytes<T, 5, 2, 5>(true, h->F);
-        hipLaunchKernelGGL((k_step1<T, 5, 2, 5, true>), g, b, lds5, h->st, a);
-        return;
-    }
-    const size_t lds = big ? mlp_lds_bytes<T, 5, 2, 4>(h->bag, h->F) : mlp_lds_bytes<T, 1, 1, 4>(h->bag, h->F);
-    if (h->bag) {
-        if (big) hipLaunchKernelGGL((k_step1<T, 5, 2, 4, true>), g, b, lds, h->st, a);
-        else hipLaunchKernelGGL((k_step1<T, 1, 1, 4, true>), g, b, lds, h->st, a);
-    } else {
-        if (big) hipLaunchKernelGGL((k_step1<T, 5, 2, 4, false>), g, b, lds, h->st, a);
-        else hipLaunchKernelGGL((k_step1<T, 1, 1, 4, false>), g, b, lds, h->st, a);
-    }
+    const FnnKernel<>& k = h->step1[a.train];
+    hipLaunchKernelGGL(reinterpret_cast<void (*)(MlpArgs<T>)>(k.fn), dim3(nmlp), dim3(k.threads), k.lds, h->st, a);
 }
 void launch_sort16(fnn_handle* h, SortArgs so) {             // split sort: the runs, then the rank merge
-    so.merge4 = h->sort_merge4;
+    so.merge4 = h->kn.sort_merge4;
     launch_sort(h->st, h->key64, so);
 }
 
-// Launches 2 and 3 of a step.  `dense`: weight gradients / slab reduce (+ update); `sparse`: the
-// sparse-row SGD of this batch and the grouping of the next one.  Single-GPU and native data-parallel
-// steps run both halves in the same two launches (the data-parallel one with its all-reduce of the slabs
-// between them); the portable split API (fnn_step_begin / _scatter / _end) runs the halves separately.
-template <typename T>
-void launch_step2(fnn_handle* h, bool dense, bool sparse, const float* gxp_src = nullptr)
+// Launches 2 and 3 of a step, always issued as a pair, and what the pair does.  `dense`: weight gradients / slab reduce (+ `update`,
+// into `bucket_dst` if given, else the handle's bucket); `sparse`: the sparse-row SGD of this batch (reading `gxp_src` if given: another
+// shard's gathered gradients, bag EXCHANGE) with `group_next`, the grouping of the next one.  Single-GPU and native data-parallel steps
+// run both halves in the same two launches (the data-parallel one with its collective between or behind them); the portable split API
+// (fnn_step_begin / _scatter / _end) runs the halves separately.
+struct StepRoles { bool dense, sparse, group_next, update; const float* gxp_src; float* bucket_dst; };
+StepRoles make_roles(const fnn_handle* h, bool dense, bool sparse, bool update, const float* gxp_src = nullptr, float* bucket_dst = nullptr)
 {
-    const int Ba = h->pend_Ba, nxt = h->cur ^ 1;
-    const bool have_next = sparse && h->pend_have_next && !(h->role_off & 1);
-    if (h->role_off & 2) dense = false;                     // timing experiments: results are wrong by construction
-    if (h->role_off & 4) sparse = false;
-    ScatArgs sa = make_scat_args(h, h->slot[h->cur], SORT_N);
-    if (gxp_src) sa.gxp = gxp_src;                          // the sparse role reads another shard's gathered gradients (bag EXCHANGE)
-    ProfScope ps(h, dense && sparse ? "step2" : (dense ? "step2_dense" : "step2_sparse"), h->st);
-    const WgradArgs wa = make_wgrad_args<T>(h, Ba);
-    const int nwx = dense ? wgrad_blocks(wa) : 0;
-    const int nsc = !sparse ? 0 : (h->bag ? (int)(((size_t)h->F * (SORT_N / WCH) * (h->rw / 4) + 255) / 256)
-                                          : scat1_blocks(sa, h->scat_form));
-    SortArgs so{h->next_ids, h->next_B, h->F, h->n_rows, h->slot[nxt].rec, h->slot[nxt].owner_cnt,
-                have_next ? 4 * h->F : 0, h->skeys, nullptr, nullptr, 0, h->sort_merge4};
-    const dim3 grid(so.nblk + nwx * h->splitk + nsc);
+    const int off = h->kn.role_off;                          // timing experiments: results are wrong by construction
+    return {dense && !(off & 2), sparse && !(off & 4), sparse && !(off & 1), update, gxp_src, bucket_dst};
+}
+// What both launches take: the row update's arguments on the current slot, and the grouping of the next batch into the other one.
+// The launches differ in so.nblk (2: four run sorts per field, 3: sixteen rank merges) and in the tag fields, which only the rank
+// merge of launch 3 writes (it draws the next slot's stamp, once).
+struct Step23Args { bool have_next; ScatArgs sa; SortArgs so; };
+Step23Args make_step23_args(fnn_handle* h, const StepRoles& r, bool merge)
+{
+    const bool have_next = r.group_next && h->pend_have_next;
+    fnn_handle::SortSlot& nx = h->slot[h->cur ^ 1];
+    Step23Args a{have_next, make_scat_args(h, h->slot[h->cur], SORT_N), {}};
+    if (r.gxp_src) a.sa.gxp = r.gxp_src;
+    a.so = SortArgs{h->next_ids, h->next_B, h->F, h->n_rows, nx.rec, nx.owner_cnt, have_next ? (merge ? 16 : 4) * h->F : 0, h->skeys,
+                    merge ? h->tag_first : nullptr, merge ? nx.tag_shared : nullptr, merge && have_next ? next_stamp(h, nx) : 0, h->kn.sort_merge4};
+    return a;
+}
+const char* role_name(const StepRoles& r, const char* both, const char* dense, const char* sparse) { return r.dense && r.sparse ? both : (r.dense ? dense : sparse); }
+
+template <typename T> void launch_step2(fnn_handle* h, const StepRoles& r)
+{
+    Step23Args a = make_step23_args(h, r, false);
+    ProfScope ps(h, role_name(r, "step2", "step2_dense", "step2_sparse"), h->st);
+    const WgradArgs wa = make_wgrad_args<T>(h, h->pend_Ba);
+    const int nwx = r.dense ? wgrad_blocks(wa) : 0;
+    const int nsc = !r.sparse ? 0 : (h->bag ? (int)(((size_t)h->F * (SORT_N / WCH) * (h->rw / 4) + 255) / 256)
+                                            : scat1_blocks(a.sa, h->kn.scat_form));
+    const dim3 grid(a.so.nblk + nwx * h->splitk + nsc);
     if (grid.x == 0) return;
     // the LDS form of the weight gradients sizes the launch's dynamic LDS for every role's workgroups
     const bool wl = nwx > 0 && h->wgrad_lds && sizeof(T) == 2;
-    const size_t lds = std::max(h->key64 ? sortA_lds_bytes<unsigned long long>(so.merge4) : sortA_lds_bytes<unsigned>(so.merge4),
-                                wl ? WGRAD_LDS_BYTES : (size_t)0);
-#define STEP2(KT, M4, WF) hipLaunchKernelGGL((k_step2<T, KT, M4, WF>), grid, dim3(256), lds, h->st, so, wa, nwx, h->splitk, sa)
-#define STEP2_KEYS(WF) do { if (h->key64) { if (so.merge4) STEP2(unsigned long long, true, WF); else STEP2(unsigned long long, false, WF); } \
-                            else { if (so.merge4) STEP2(unsigned, true, WF); else STEP2(unsigned, false, WF); } } while (0)
-    if constexpr (sizeof(T) == 2) {
-        if (wl) { STEP2_KEYS(WGRAD_LDS); return; }
-    }
-    STEP2_KEYS(WGRAD_DIRECT);
-#undef STEP2_KEYS
-#undef STEP2
+    const Step2Kernel& k = h->step2[wl];
+    hipLaunchKernelGGL(k.fn, grid, dim3(k.threads), std::max(k.lds, wl ? WGRAD_LDS_BYTES : (size_t)0), h->st, a.so, wa, nwx, h->splitk, a.sa);
 }
 
-template <typename T, bool M4>
-void launch_step3_form(fnn_handle* h, bool update, const dim3 grid, const size_t lds, const SortArgs& so, const TailArgs& ta, const ScatArgs& sa)
+template <typename T> void launch_step3(fnn_handle* h, const StepRoles& r)
 {
-    if (h->key64) {
-        if (update) hipLaunchKernelGGL((k_step3<T, true, unsigned long long, M4>), grid, dim3(256), lds, h->st, so, ta, sa);
-        else hipLaunchKernelGGL((k_step3<T, false, unsigned long long, M4>), grid, dim3(256), lds, h->st, so, ta, sa);
-    } else {
-        if (update) hipLaunchKernelGGL((k_step3<T, true, unsigned, M4>), grid, dim3(256), lds, h->st, so, ta, sa);
-        else hipLaunchKernelGGL((k_step3<T, false, unsigned, M4>), grid, dim3(256), lds, h->st, so, ta, sa);
-    }
-}
-
-template <typename T>
-void launch_step3(fnn_handle* h, bool dense, bool sparse, bool update, float* bucket_dst = nullptr, const float* gxp_src = nullptr)
-{
-    const int Ba = h->pend_Ba, nxt = h->cur ^ 1;
-    const bool have_next = sparse && h->pend_have_next && !(h->role_off & 1);
-    if (h->role_off & 2) dense = false;
-    if (h->role_off & 4) sparse = false;
-    ScatArgs sa = make_scat_args(h, h->slot[h->cur], SORT_N);
-    if (gxp_src) sa.gxp = gxp_src;
+    const Step23Args a = make_step23_args(h, r, true);
     {
-        ProfScope ps(h, dense && sparse ? "step3" : (dense ? "step3_dense" : "step3_sparse"), h->st);
-        const int nred = dense ? (int)((h->nw12 / 4 + 255) / 256) + (int)((h->nw - h->nw12 + h->nbag + 255) / 256) + 1 : 0;
+        ProfScope ps(h, role_name(r, "step3", "step3_dense", "step3_sparse"), h->st);
+        const int nred = r.dense ? (int)((h->nw12 / 4 + 255) / 256) + (int)((h->nw - h->nw12 + h->nbag + 255) / 256) + 1 : 0;
         TailArgs ta{h->slab, h->splitk, h->nw, h->nw12, h->nslab, h->master, h->cfg.lambda1, h->cfg.reg_all,
-                    h->loss_t, Ba, bucket_dst ? bucket_dst : h->bucket, h->loss_dev, h->cfg.lr, h->K1p, h->H1p, h->H2p,
+                    h->loss_t, h->pend_Ba, r.bucket_dst ? r.bucket_dst : h->bucket, h->loss_dev, h->cfg.lr, h->K1p, h->H1p, h->H2p,
                     h->w1, h->w1t, h->w2, h->w2t, nred, h->bb0, h->nbag, h->off_bag};
-        const int stamp = have_next ? next_stamp(h, h->slot[nxt]) : 0;      // the rank merge of the NEXT batch marks its shared rows
-        SortArgs so{h->next_ids, h->next_B, h->F, h->n_rows, h->slot[nxt].rec, h->slot[nxt].owner_cnt,
-                    have_next ? 16 * h->F : 0, h->skeys, h->tag_first, h->slot[nxt].tag_shared, stamp, h->sort_merge4};
-        const dim3 grid(so.nblk + nred + (sparse ? h->scat2_wgs : 0));    // these workgroups walk the multi-chunk segments
-        const size_t lds = h->key64 ? sort_lds_bytes<unsigned long long>() : sort_lds_bytes<unsigned>();
-        if (grid.x > 0) {
-            if (so.merge4) launch_step3_form<T, true>(h, update, grid, lds, so, ta, sa);
-            else launch_step3_form<T, false>(h, update, grid, lds, so, ta, sa);
-        }
+        const dim3 grid(a.so.nblk + nred + (r.sparse ? h->kn.scat2_wgs : 0));    // these workgroups walk the multi-chunk segments
+        const Step3Kernel& k = h->step3[r.update];
+        if (grid.x > 0) hipLaunchKernelGGL(k.fn, grid, dim3(k.threads), k.lds, h->st, a.so, ta, a.sa);
     }
-    if (sparse) {
-        if (have_next) { h->cur = nxt; h->sorted_ids = h->next_ids; h->sorted_B = h->next_B; }
+    if (r.sparse) {                                          // the sparse role's bookkeeping: the slots flip, nothing is left to scatter
+        if (a.have_next) { h->cur ^= 1; h->sorted_ids = h->next_ids; h->sorted_B = h->next_B; }
         else { h->sorted_ids = nullptr; h->sorted_B = 0; }
         h->next_ids = nullptr; h->next_B = 0;
         h->scatter_pending = false;
     }
 }
-
-template <typename T>
-void launch_steps23(fnn_handle* h, bool dense, bool sparse, bool update)
-{
-    launch_step2<T>(h, dense, sparse);
-    launch_step3<T>(h, dense, sparse, update);
-}
+template <typename T> void launch_steps23(fnn_handle* h, const StepRoles& r) { launch_step2<T>(h, r); launch_step3<T>(h, r); }
 
 // ---- collectives of the native data-parallel step, enqueued on the handle's stream
 int dp_allreduce(fnn_handle* h, float* buf, size_t n, const char* what)
@@ -416,8 +459,7 @@ template <typename T> int dp_finish_bucket(fnn_handle* h, bool in_region)
         h->dp_step_no++;
         return FNN_OK;
     }
-    int rc = dp_allreduce(h, h->bucket, h->nw + h->nbag, "dense-gradient bucket");
-    if (rc != FNN_OK) return rc;
+    RCCHK(dp_allreduce(h, h->bucket, h->nw + h->nbag, "dense-gradient bucket"));
     ProfScope ps(h, "update", h->st);
     launch_update<T>(h, h->bucket, h->cfg.lr);
     return FNN_OK;
@@ -456,12 +498,19 @@ int dp_exchange_sparse(fnn_handle* h, const int32_t* ids, int B)
             SortArgs so{ids_r, rows, F, h->n_rows, sl.rec, sl.owner_cnt, F, h->skeys, h->tag_first, sl.tag_shared, next_stamp(h, sl)};
             launch_sort16(h, so);
         }
-        const float* gx_r = h->xg_gxp + (size_t)r * rows * h->K1p;
-        launch_step2<T>(h, false, true, gx_r);
-        launch_step3<T>(h, false, true, false, nullptr, gx_r);
+        launch_steps23<T>(h, make_roles(h, false, true, false, h->xg_gxp + (size_t)r * rows * h->K1p));
     }
     HIPCHK(h, hipGetLastError());
     return FNN_OK;
+}
+
+// gx in the reference's layout, for a caller that asked for it
+void copy_gx_out(fnn_handle* h, int B, float* gx_out_dev)
+{
+    const size_t n = (size_t)B * h->xdim;
+    if (h->bag) hipLaunchKernelGGL(k_copy_cols, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, h->st, h->gx_raw, h->K1p, B, h->xdim, gx_out_dev);
+    else hipLaunchKernelGGL(k_gx_ref, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, h->st, h->gxp, h->K1p, B, h->F, h->K, h->rw,
+                            h->wide ? h->F * h->rw : h->K, gx_out_dev);
 }
 
 // The fast path: three role-split launches on the main stream (fnn_step_kernels.hip.h).
@@ -469,191 +518,170 @@ template <typename T>
 int run_step_fast(fnn_handle* h, const int32_t* ids, const float* y, int B, const uint8_t* m1,
                   const uint8_t* m2, float* p_out, float* gx_out_dev, bool update)
 {
-    const int Ba = rup(B, 256);
-    const bool exchange = update && h->dp && h->dp_sparse == FNN_DP_SPARSE_EXCHANGE;   // the rows are grouped over the GLOBAL batch later
+    const bool native = update && h->dp;                                     // the step runs its own collective
+    const bool local = !native || h->dp_sparse == FNN_DP_SPARSE_LOCAL;      // else EXCHANGE: the rows are grouped over the GLOBAL batch later
     // grouping of THIS batch: done by the previous step (fnn_prefetch_ids) or right now
-    if (exchange) { h->next_ids = nullptr; h->next_B = 0; }
+    if (!local) { h->next_ids = nullptr; h->next_B = 0; }
     else if (!(h->sorted_ids == ids && h->sorted_B == B)) {
         h->prefetch_misses++;
         ProfScope ps(h, "sort_now", h->st);
-        SortArgs so{ids, B, h->F, h->n_rows, h->slot[h->cur].rec, h->slot[h->cur].owner_cnt, h->F, h->skeys,
-                    h->tag_first, h->slot[h->cur].tag_shared, next_stamp(h, h->slot[h->cur])};
-        launch_sort16(h, so);
+        fnn_handle::SortSlot& sl = h->slot[h->cur];
+        launch_sort16(h, SortArgs{ids, B, h->F, h->n_rows, sl.rec, sl.owner_cnt, h->F, h->skeys, h->tag_first, sl.tag_shared, next_stamp(h, sl)});
     } else h->prefetch_hits++;
-    const bool have_next = h->next_ids != nullptr && !(h->next_ids == ids && h->next_B == B);
-    const int nxt = h->cur ^ 1;
+    h->pend_Ba = rup(B, 256);
+    h->pend_have_next = h->next_ids != nullptr && !(h->next_ids == ids && h->next_B == B);
     { ProfScope pe(h, "empty", h->st); }         // a back-to-back event pair: what the event mechanism itself adds to every slot
     {
         ProfScope ps(h, "step1", h->st);
         MlpArgs<T> ma = make_mlp_args<T>(h, ids, y, B, m1, m2, true, p_out);
         if (h->bag && gx_out_dev) ma.gx_raw = h->gx_raw;
-        launch_step1<T>(h, Ba / 16, ma);
+        launch_step1<T>(h, h->pend_Ba / 16, ma);
     }
-    if (gx_out_dev) {
-        const size_t n = (size_t)B * h->xdim;
-        if (h->bag) hipLaunchKernelGGL(k_copy_cols, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, h->st, h->gx_raw,
-                                       h->K1p, B, h->xdim, gx_out_dev);
-        else hipLaunchKernelGGL(k_gx_ref, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, h->st, h->gxp, h->K1p,
-                                B, h->F, h->K, SLOT, h->K, gx_out_dev);
+    if (gx_out_dev) copy_gx_out(h, B, gx_out_dev);
+    if (!native) {
+        // single: dense and sparse roles share the launches; split API (no update): the sparse half is deferred to fnn_step_scatter
+        launch_steps23<T>(h, make_roles(h, true, update, update));
+        if (!update) h->scatter_pending = true;
+    } else if (!dp_bucket_mode(h)) {
+        // slabs collective: the same launches with ONE collective between the second and the third -- the split-K slabs of the
+        // weight gradients are all-reduced in place, the third launch then sums GLOBAL slabs
+        const StepRoles r = make_roles(h, true, local, true);
+        launch_step2<T>(h, r);
+        RCCHK(dp_allreduce(h, h->slab, (size_t)h->splitk * h->nslab, "weight-gradient slabs"));
+        launch_step3<T>(h, r);
+    } else {
+        // bucket collective: launch 3 sums this rank's slabs (no update), the collective carries a quarter of the bytes, a fourth
+        // launch applies the update -- with the p2p collective that launch IS the all-reduce
+        const bool p2p = h->dp_collective == FNN_DP_COLLECTIVE_P2P;
+        launch_steps23<T>(h, make_roles(h, true, local, false, nullptr, p2p ? p2p_bucket(h) : nullptr));
+        RCCHK(dp_finish_bucket<T>(h, p2p));
     }
-    h->pend_Ba = Ba; h->pend_have_next = have_next;
-    if (update && h->dp) {
-        // native data-parallel step: the same launches with ONE collective between the second and the third -- the split-K
-        // slabs of the weight gradients are all-reduced in place, the third launch then sums GLOBAL slabs
-        const bool local = h->dp_sparse == FNN_DP_SPARSE_LOCAL;
-        launch_step2<T>(h, true, local);
-        int rc;
-        if (!dp_bucket_mode(h)) {
-            rc = dp_allreduce(h, h->slab, (size_t)h->splitk * h->nslab, "weight-gradient slabs");
-            if (rc != FNN_OK) return rc;
-            launch_step3<T>(h, true, local, true);
-        } else {
-            // bucket payload: launch 3 sums this rank's slabs (no update), the collective carries a quarter of the bytes, a fourth
-            // launch applies the update -- with the p2p collective that launch IS the all-reduce
-            const bool p2p = h->dp_collective == FNN_DP_COLLECTIVE_P2P;
-            launch_step3<T>(h, true, local, false, p2p ? p2p_bucket(h) : nullptr);
-            rc = dp_finish_bucket<T>(h, p2p);
-            if (rc != FNN_OK) return rc;
-        }
-        if (!local) {
-            h->pend_have_next = false;
-            rc = dp_exchange_sparse<T>(h, ids, B);
-            if (rc != FNN_OK) return rc;
-        }
+    if (!local) {
+        h->pend_have_next = false;
+        RCCHK(dp_exchange_sparse<T>(h, ids, B));
     }
-    else if (update) launch_steps23<T>(h, true, true, true);     // dense and sparse roles share the launches
-    else { launch_steps23<T>(h, true, false, false); h->scatter_pending = true; }   // split API: sparse half deferred
     HIPCHK(h, hipGetLastError());
     return FNN_OK;
 }
 
-// The generic path: one kernel per layer / stage, any padded shape, B up to 16384.
+// ---- the generic path, one kernel per layer / stage, any padded shape, B up to 16384: its stages, then run_step
+// A3, A4 and the head: gather, d1 = act(x' W1p) * r1, d2 = tanh(d1 W2p) * r2 (predict: acti_type, no mask), output unit, loss, delta2
+template <typename T>
+void layers_forward(fnn_handle* h, const int32_t* ids, const float* y, int B, int Ba, const uint8_t* m1, const uint8_t* m2, bool train, float* p_out)
+{
+    const int K1p = h->K1p, H1p = h->H1p, H2p = h->H2p, ldT = h->ldT;
+    T *xp = (T*)h->xp, *d1 = (T*)h->d1, *d2 = (T*)h->d2;
+    {
+        ProfScope ps(h, "gather", h->st);
+        if (h->wide) {
+            const int nthreads = Ba / 4 * (K1p / 4);
+            hipLaunchKernelGGL((k_gather_wide<T>), dim3((nthreads + 255) / 256), dim3(256), 0, h->st, ids, B, Ba,
+                               h->F, h->rw, h->table16, h->n_rows, h->w0, xp, K1p, (T*)h->xpT, ldT, h->err_flag);
+        } else {
+            const int nthreads = Ba * h->F;
+            hipLaunchKernelGGL((k_gather<T>), dim3((nthreads + 255) / 256), dim3(256), 0, h->st, ids, B, Ba,
+                               h->F, h->K, h->table16, h->n_rows, h->w0, xp, K1p, (T*)h->xpT, ldT, h->err_flag);
+        }
+    }
+    {
+        ProfScope ps(h, "fwd1", h->st);
+        EpiFwd<T> e{d1, H1p, train ? (T*)h->d1T : nullptr, ldT, m1, h->cfg.act, h->H1, B};
+        launch_gemm<T, 4>(h->st, xp, K1p, (const T*)h->w1t, Ba, H1p, K1p, e);
+    }
+    {
+        ProfScope ps(h, "fwd2", h->st);
+        EpiFwd<T> e{d2, H2p, train ? (T*)h->d2T : nullptr, ldT, m2, train ? ACT_TANH : h->cfg.act, h->H2, B};
+        launch_gemm<T, 4>(h->st, d1, H1p, (const T*)h->w2t, Ba, H2p, H1p, e);
+    }
+    ProfScope ps(h, "head", h->st);
+    hipLaunchKernelGGL((k_head<T>), dim3(Ba / 64), dim3(256), 0, h->st, d2, H2p, h->H2, h->master + h->nw12, m2, y, B, train ? 1 : 0,
+                       p_out, (T*)h->dl2, (T*)h->dl2T, ldT, (T*)h->dl3T, h->loss_t);
+}
+// A5, backward data: delta1 = (delta2 W2p^T) * r1 * act'(d1), then gx' = delta1 W1p^T
+template <typename T> void layers_backward(fnn_handle* h, int B, int Ba, const uint8_t* m1)
+{
+    const int K1p = h->K1p, H1p = h->H1p, H2p = h->H2p;
+    {
+        ProfScope ps(h, "bwd1", h->st);
+        EpiBwd<T> e{(T*)h->dl1, H1p, (T*)h->dl1T, h->ldT, (T*)h->d1, m1, h->cfg.act, h->H1, B};
+        launch_gemm<T, 4>(h->st, (T*)h->dl2, H2p, (const T*)h->w2, Ba, H1p, H2p, e);
+    }
+    ProfScope ps(h, "gx", h->st);
+    EpiF32 e{h->gxp, K1p, 0};
+    launch_gemm<T, 4>(h->st, (T*)h->dl1, H1p, (const T*)h->w1, Ba, K1p, H1p, e);
+}
+// A5, dense gradients: contraction over the examples into split-K slabs, then their sum (+ L2 term) into the bucket
+template <typename T> int layers_wgrad_reduce(fnn_handle* h, int Ba)
+{
+    {
+        ProfScope ps(h, "wgrad", h->st);
+        const WgradArgs wa = make_wgrad_args<T>(h, Ba);
+        const dim3 grid(wgrad_blocks(wa), h->splitk);
+        bool lds_form = false;
+        if constexpr (sizeof(T) == 2) {
+            if (h->wgrad_lds) {
+                hipLaunchKernelGGL((k_wgrad<T, WGRAD_LDS>), grid, dim3(256), WGRAD_LDS_BYTES, h->st, wa);
+                lds_form = true;
+            }
+        }
+        if (!lds_form) hipLaunchKernelGGL((k_wgrad<T>), grid, dim3(256), 0, h->st, wa);
+    }
+    // native data parallelism, slabs payload: the SAME collective as the three-launch path issues, so that a rank whose shard
+    // takes these kernels (shadowed features, B > 4096) pairs with peers that do not
+    if (h->step_native_dp && !dp_bucket_mode(h)) RCCHK(dp_allreduce(h, h->slab, (size_t)h->splitk * h->nslab, "weight-gradient slabs"));
+    ProfScope ps(h, "reduce", h->st);
+    hipLaunchKernelGGL(k_reduce, dim3((unsigned)((h->nw + 255) / 256 + 1)), dim3(256), 0, h->st, h->slab, h->splitk, h->nw, h->nw12,
+                       h->nslab, h->master, h->cfg.lambda1, h->cfg.reg_all, h->loss_t, Ba, h->bucket, h->loss_dev);
+    return FNN_OK;
+}
+// A6 part 2: the two-level row update on the grouping in `sl`
+void layers_row_update(fnn_handle* h, const fnn_handle::SortSlot& sl, int N2)
+{
+    ScatArgs sa = make_scat_args(h, sl, N2);
+    if (h->wide) sa.gxf = h->rw;                             // rows of rw floats: chunks of WCH entries, a 16-byte piece per thread
+    {
+        ProfScope ps(h, "scatter", h->st);
+        // narrow rows: a thread per live quarter-column of a chunk of 16 entries (or 16 lanes per chunk); scat1_blocks settles sa.form
+        const int nblk = h->wide ? (int)(((size_t)h->F * (N2 / WCH) * (h->rw / 4) + 255) / 256) : scat1_blocks(sa, h->kn.scat_form);
+        if (h->wide) hipLaunchKernelGGL(k_scatdw1, dim3(nblk), dim3(256), 0, h->st, sa);
+        else hipLaunchKernelGGL(k_scat1, dim3(nblk), dim3(256), 0, h->st, sa);
+    }
+    ProfScope ps(h, "finalize", h->st);
+    if (h->wide) hipLaunchKernelGGL(k_scatdw2, dim3(256), dim3(256), 0, h->st, sa);
+    else hipLaunchKernelGGL(k_scat2, dim3(64), dim3(256), 0, h->st, sa);
+}
+
 template <typename T>
 int run_step(fnn_handle* h, const int32_t* ids, const float* y, int B, const uint8_t* m1,
              const uint8_t* m2, bool train, float* p_out, float* gx_out_dev)
 {
     const int Ba = rup(B, 256);
-    const int F = h->F, K = h->K, K1p = h->K1p, H1p = h->H1p, H2p = h->H2p, ldT = h->ldT;
-    T *xp = (T*)h->xp, *xpT = (T*)h->xpT, *d1 = (T*)h->d1, *d1T = (T*)h->d1T, *d2 = (T*)h->d2,
-      *dl2 = (T*)h->dl2, *dl2T = (T*)h->dl2T, *dl1 = (T*)h->dl1, *dl1T = (T*)h->dl1T;
     // shadowed features join their field's keys behind the B regular ones: room for all of them in any one field
     const int nsh = train ? h->n_shadow : 0;
     const int N2 = sort_n2(B + nsh);
-    T *d2T = (T*)h->d2T, *dl3T = (T*)h->dl3T;
     if (nsh > 0) {
         if (B + nsh > 16384) FAIL(h, FNN_ERR_ARG, "batch plus shadowed features exceed 16384 keys per field");
-        int rc = ensure_global_ws(h, B + nsh);                 // the per-batch slots hold max_batch keys per field
-        if (rc != FNN_OK) return rc;
+        RCCHK(ensure_global_ws(h, B + nsh));                   // the per-batch slots hold max_batch keys per field
     }
     fnn_handle::SortSlot& sl = nsh > 0 ? h->gsl : h->slot[h->cur];
     h->sorted_ids = nullptr; h->next_ids = nullptr;            // this path keeps no grouping across steps
-    if (h->bag && !(h->fused && mlp_shape_ok(h))) FAIL(h, FNN_ERR_ARG, "FNN_MODE_BAG runs on the strip kernel only, which FNN_NO_FUSE=1 turns off (hidden1 256..319 with hidden2 64..127, or <= 63 / <= 63 at h0 <= 252)");
+    if (h->bag && !h->strip_ok) FAIL(h, FNN_ERR_ARG, "FNN_MODE_BAG runs on the strip kernel only, which FNN_NO_FUSE=1 turns off (hidden1 256..319 with hidden2 64..127, or <= 63 / <= 63 at h0 <= 252)");
     if (h->bag && train) FAIL(h, FNN_ERR_ARG, "FNN_MODE_BAG trains through the three-launch path only (B <= 4096)");
     if (train && h->step_native_dp && h->dp_sparse == FNN_DP_SPARSE_EXCHANGE)
         FAIL(h, FNN_ERR_ARG, "FNN_DP_SPARSE_EXCHANGE runs on the three-launch path only (B <= 4096, hidden sizes the strip kernel is built for)");
-
     if (train) {   // A6 part 1: group the (row, t) pairs
         ProfScope ps(h, "sort", h->st);
-        launch_k_sort(h->st, N2, ids, B, F, h->n_rows, sl, h->shadow_dev, h->n_shadow, h->err_flag);
+        launch_k_sort(h->st, N2, ids, B, h->F, h->n_rows, sl, h->shadow_dev, h->n_shadow, h->err_flag);
     }
-    if (h->fused && mlp_shape_ok(h)) {
+    if (h->strip_ok) {
         ProfScope ps(h, "mlp", h->st);
         launch_step1<T>(h, Ba / 16, make_mlp_args<T>(h, ids, y, B, m1, m2, train, p_out));
-        if (!train) return FNN_OK;
-    } else {
-        {   // A3
-            ProfScope ps(h, "gather", h->st);
-            if (h->wide) {
-                const int nthreads = Ba / 4 * (K1p / 4);
-                hipLaunchKernelGGL((k_gather_wide<T>), dim3((nthreads + 255) / 256), dim3(256), 0, h->st, ids, B, Ba,
-                                   F, h->rw, h->table16, h->n_rows, h->w0, xp, K1p, xpT, ldT, h->err_flag);
-            } else {
-                const int nthreads = Ba * F;
-                hipLaunchKernelGGL((k_gather<T>), dim3((nthreads + 255) / 256), dim3(256), 0, h->st, ids, B, Ba,
-                                   F, K, h->table16, h->n_rows, h->w0, xp, K1p, xpT, ldT, h->err_flag);
-            }
-        }
-        {   // A4 layer 1: d1 = act(x' W1p) * r1
-            ProfScope ps(h, "fwd1", h->st);
-            EpiFwd<T> e{d1, H1p, train ? d1T : nullptr, ldT, m1, h->cfg.act, h->H1, B};
-            launch_gemm<T, 4>(h->st, xp, K1p, (const T*)h->w1t, Ba, H1p, K1p, e);
-        }
-        {   // A4 layer 2: d2 = tanh(d1 W2p) * r2   (predict: acti_type, no mask)
-            ProfScope ps(h, "fwd2", h->st);
-            EpiFwd<T> e{d2, H2p, train ? d2T : nullptr, ldT, m2, train ? ACT_TANH : h->cfg.act, h->H2, B};
-            launch_gemm<T, 4>(h->st, d1, H1p, (const T*)h->w2t, Ba, H2p, H1p, e);
-        }
-        {   // output unit, loss, delta2
-            ProfScope ps(h, "head", h->st);
-            hipLaunchKernelGGL((k_head<T>), dim3(Ba / 64), dim3(256), 0, h->st, d2, H2p, h->H2,
-                               h->master + h->nw12, m2, y, B, train ? 1 : 0, p_out, dl2, dl2T, ldT, dl3T,
-                               h->loss_t);
-        }
-        if (!train) return FNN_OK;
-        {   // A5: delta1 = (delta2 W2p^T) * r1 * act'(d1)
-            ProfScope ps(h, "bwd1", h->st);
-            EpiBwd<T> e{dl1, H1p, dl1T, ldT, d1, m1, h->cfg.act, h->H1, B};
-            launch_gemm<T, 4>(h->st, dl2, H2p, (const T*)h->w2, Ba, H1p, H2p, e);
-        }
-        {   // A5: gx' = delta1 W1p^T
-            ProfScope ps(h, "gx", h->st);
-            EpiF32 e{h->gxp, K1p, 0};
-            launch_gemm<T, 4>(h->st, dl1, H1p, (const T*)h->w1, Ba, K1p, H1p, e);
-        }
-    }
-    {   // A5: dense gradients, contraction over the examples, split-K slabs
-        ProfScope ps(h, "wgrad", h->st);
-        const WgradArgs wa = make_wgrad_args<T>(h, Ba);
-        bool lds_form = false;
-        if constexpr (sizeof(T) == 2) {
-            if (h->wgrad_lds) {
-                hipLaunchKernelGGL((k_wgrad<T, WGRAD_LDS>), dim3(wgrad_blocks(wa), h->splitk), dim3(256), WGRAD_LDS_BYTES, h->st, wa);
-                lds_form = true;
-            }
-        }
-        if (!lds_form) hipLaunchKernelGGL((k_wgrad<T>), dim3(wgrad_blocks(wa), h->splitk), dim3(256), 0, h->st, wa);
-    }
-    if (train && h->step_native_dp && !dp_bucket_mode(h)) {
-        // native data parallelism, slabs payload: the SAME collective as the three-launch path issues, so that a rank whose shard
-        // takes these kernels (shadowed features, B > 4096) pairs with peers that do not (round-2 advisor: mismatched counts)
-        int rc = dp_allreduce(h, h->slab, (size_t)h->splitk * h->nslab, "weight-gradient slabs");
-        if (rc != FNN_OK) return rc;
-    }
-    {
-        ProfScope ps(h, "reduce", h->st);
-        hipLaunchKernelGGL(k_reduce, dim3((unsigned)((h->nw + 255) / 256 + 1)), dim3(256), 0, h->st, h->slab,
-                           h->splitk, h->nw, h->nw12, h->nslab, h->master, h->cfg.lambda1, h->cfg.reg_all,
-                           h->loss_t, Ba, h->bucket, h->loss_dev);
-    }
-    if (gx_out_dev) {
-        const size_t n = (size_t)B * h->xdim;
-        hipLaunchKernelGGL(k_gx_ref, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, h->st, h->gxp, K1p,
-                           B, F, K, h->rw, h->wide ? F * h->rw : K, gx_out_dev);
-    }
-    ScatArgs sa = make_scat_args(h, sl, N2);                 // A6 part 2
-    if (h->wide) {                                           // rows of rw floats: chunks of WCH entries, a 16-byte piece per thread
-        sa.gxf = h->rw;
-        {
-            ProfScope ps(h, "scatter", h->st);
-            const size_t nthr = (size_t)F * (N2 / WCH) * (h->rw / 4);
-            hipLaunchKernelGGL(k_scatdw1, dim3((unsigned)((nthr + 255) / 256)), dim3(256), 0, h->st, sa);
-        }
-        {
-            ProfScope ps(h, "finalize", h->st);
-            hipLaunchKernelGGL(k_scatdw2, dim3(256), dim3(256), 0, h->st, sa);
-        }
-        HIPCHK(h, hipGetLastError());
-        return FNN_OK;
-    }
-    {
-        ProfScope ps(h, "scatter", h->st);
-        const int nblk = scat1_blocks(sa, h->scat_form);     // a thread per live quarter-column of a chunk of 16 entries (or 16 lanes per chunk)
-        hipLaunchKernelGGL(k_scat1, dim3(nblk), dim3(256), 0, h->st, sa);
-    }
-    {
-        ProfScope ps(h, "finalize", h->st);
-        hipLaunchKernelGGL(k_scat2, dim3(64), dim3(256), 0, h->st, sa);
-    }
+    } else layers_forward<T>(h, ids, y, B, Ba, m1, m2, train, p_out);
+    if (!train) return FNN_OK;
+    if (!h->strip_ok) layers_backward<T>(h, B, Ba, m1);
+    RCCHK(layers_wgrad_reduce<T>(h, Ba));
+    if (gx_out_dev) copy_gx_out(h, B, gx_out_dev);
+    layers_row_update(h, sl, N2);
     HIPCHK(h, hipGetLastError());
     return FNN_OK;
 }
@@ -674,10 +702,9 @@ int ensure_global_ws(fnn_handle* h, int B_g)
     if (h->cpow_cap < N2 + 1) {             // a row can be hit by every example of the global batch
         hipFree(h->cpow_dev); h->cpow_dev = nullptr;
         h->cpow_cap = N2 + 1;
-        int rc = alloc_dev(h, &h->cpow_dev, (size_t)h->cpow_cap);
-        if (rc != FNN_OK) return rc;
+        RCCHK(alloc_dev(h, &h->cpow_dev, (size_t)h->cpow_cap));
         h->cpow_c = -1.0; h->cpow_n = 0;
-        if (h->step_bsize > 0 && (rc = update_cpow(h, h->step_bsize, B_g)) != FNN_OK) return rc;
+        if (h->step_bsize > 0) RCCHK(update_cpow(h, h->step_bsize, B_g));
     }
     HIPCHK(h, hipStreamSynchronize(h->st));
     return FNN_OK;                              // (the LDS attributes of k_sort<8> / <16> are set at fnn_create)
@@ -688,8 +715,7 @@ int ensure_global_ws(fnn_handle* h, int B_g)
 // two-level segmented update reading the gathered gradients
 int scatter_global_impl(fnn_handle* h, const int32_t* ids_g, const float* gxp_g, int B_g)
 {
-    int rc = ensure_global_ws(h, B_g);
-    if (rc != FNN_OK) return rc;
+    RCCHK(ensure_global_ws(h, B_g));
     if (h->cpow_n < B_g + 1) FAIL(h, FNN_ERR_STATE, "decay table shorter than the global batch");
     fnn_handle::SortSlot& sl = h->gsl;
     const int N2 = sort_n2(B_g), F = h->F;
@@ -705,7 +731,7 @@ int scatter_global_impl(fnn_handle* h, const int32_t* ids_g, const float* gxp_g,
         ProfScope ps(h, "scatter_global", h->st);
         ScatArgs sa = make_scat_args(h, sl, N2);
         sa.gxp = gxp_g;
-        launch_scat_narrow(h->st, sa, h->scat_form, N2 > 4096 ? 256 : 64);      // after sa.gxp changed: the caller's buffer may not be 16-byte aligned
+        launch_scat_narrow(h->st, sa, h->kn.scat_form, N2 > 4096 ? 256 : 64);      // after sa.gxp changed: the caller's buffer may not be 16-byte aligned
     }
     HIPCHK(h, hipGetLastError());
     h->next_ids = nullptr; h->next_B = 0;       // no grouping of a later batch rides on this step
@@ -779,15 +805,14 @@ int dp_setup(fnn_handle* h, int rank, int world, int sparse_mode)
     if (sparse_mode == FNN_DP_SPARSE_EXCHANGE) {
         if (h->wide) FAIL(h, FNN_ERR_ARG, "FNN_DP_SPARSE_EXCHANGE: not supported on wide rows (k >= 17; its exchange carries 16-float slots): use FNN_DP_SPARSE_LOCAL");
         if ((int64_t)world * h->ldT > GLOBAL_BATCH_MAX) FAIL(h, FNN_ERR_ARG, "FNN_DP_SPARSE_EXCHANGE: world * max_batch (rounded up to 256) must be <= 32768");
-        if (!(h->fused && mlp_shape_ok(h)) || h->Bmax > SORT_N) FAIL(h, FNN_ERR_ARG, "FNN_DP_SPARSE_EXCHANGE runs on the three-launch path only (max_batch <= 4096, hidden sizes the strip kernel is built for)");
-        int rc;
+        if (h->Bmax > h->three_launch_max_B) FAIL(h, FNN_ERR_ARG, "FNN_DP_SPARSE_EXCHANGE runs on the three-launch path only (max_batch <= 4096, hidden sizes the strip kernel is built for)");
         const size_t rows = (size_t)h->ldT;
-        if (!h->xg_ids_send && (rc = alloc_dev(h, &h->xg_ids_send, rows * h->F)) != FNN_OK) return rc;
+        if (!h->xg_ids_send) RCCHK(alloc_dev(h, &h->xg_ids_send, rows * h->F));
         if (h->xg_ids) { hipFree(h->xg_ids); h->xg_ids = nullptr; }
         if (h->xg_gxp) { hipFree(h->xg_gxp); h->xg_gxp = nullptr; }
-        if ((rc = alloc_dev(h, &h->xg_ids, rows * world * h->F)) != FNN_OK) return rc;
-        if ((rc = alloc_dev(h, &h->xg_gxp, rows * world * h->K1p)) != FNN_OK) return rc;
-        if (!h->bag && (rc = ensure_global_ws(h, (int)rows * world)) != FNN_OK) return rc;
+        RCCHK(alloc_dev(h, &h->xg_ids, rows * world * h->F));
+        RCCHK(alloc_dev(h, &h->xg_gxp, rows * world * h->K1p));
+        if (!h->bag) RCCHK(ensure_global_ws(h, (int)rows * world));
     }
     h->dp_rank = rank; h->dp_world = world; h->dp_sparse = sparse_mode;
     h->sorted_ids = nullptr; h->next_ids = nullptr;
@@ -806,6 +831,57 @@ int check_ready(fnn_handle* h, int B) {
     if (!(h->dense_set[0] && h->dense_set[1] && h->dense_set[2]))
         FAIL(h, FNN_ERR_STATE, "fnn_set_dense has not been called for all three layers");
     return FNN_OK;
+}
+
+// every knob fnn_create takes from the environment, each with the values it accepts; anything else leaves the default
+FnnKnobs read_knobs(bool bag)
+{
+    FnnKnobs k;
+    if (const char* e = getenv("FNN_WT_STORES")) k.wt_stores = atoi(e);
+    if (const char* e = getenv("FNN_STEP1_WAVES")) k.step1_waves = atoi(e) == 4 ? 4 : 8;
+    if (const char* e = getenv("FNN_STEP1_FORM")) k.step1_fixed = strcmp(e, "generic") != 0;      // fixed | generic; anything else: the default, fixed
+    if (const char* e = getenv("FNN_NO_FUSE")) k.fused = !(e[0] == '1');
+    if (const char* e = getenv("FNN_ROLE_OFF")) k.role_off = atoi(e);
+    if (const char* e = getenv("FNN_SPLITK")) { const int v = atoi(e); if (v == 2 || v == 4 || v == 8 || v == 16) k.splitk = v; }   // tuning knob
+    if (const char* e = getenv("FNN_SCAT2_WGS")) { const int v = atoi(e); if (v >= 16 && v <= 1024) k.scat2_wgs = v; }
+    k.wgrad_form = wgrad_form_env(); k.scat_form = scat1_form_env(); k.scat2_form = scat2_form_env();
+    k.sort_merge4 = sort_merge4_env(bag ? 0 : 1);
+    return k;
+}
+
+// the shapes and the paths of a handle, from a configuration fnn_create has checked (plan_step1 / plan_keys add the kernels)
+FnnPlan make_plan(const fnn_cfg& c, const FnnKnobs& kn)
+{
+    FnnPlan p;
+    p.F = c.n_fields; p.K = c.k; p.H1 = c.hidden1; p.H2 = c.hidden2;
+    p.xdim = 1 + p.F * p.K;
+    p.K1p = rup(p.F * SLOT, 64); p.H1p = rup(p.H1 + 1, 64); p.H2p = rup(p.H2 + 1, 64);
+    p.bag = c.mode == FNN_MODE_BAG;
+    if (p.bag) { p.rw = c.h0; p.K = c.h0; p.xdim = c.h0; p.K1p = rup(c.h0 + 1, 64); }
+    p.wide = !p.bag && p.K >= 17;
+    if (p.wide) { p.rw = rup(p.K, 4); p.K1p = rup(p.F * p.rw + 2, 64); }       // field columns, then w_0 and the ones column
+    p.Bmax = c.max_batch; p.ldT = rup(p.Bmax, 256);
+    p.N2max = SORT_N; while (p.N2max < p.Bmax) p.N2max <<= 1;    // the three-launch path groups SORT_N slots per field whatever max_batch is
+    p.n1 = (size_t)p.K1p * p.H1p; p.n2 = (size_t)p.H1p * p.H2p;
+    p.nw12 = p.n1 + p.n2; p.nw = p.nw12 + p.H2p;
+    p.off_bag = p.nw12 + (size_t)p.H2p * 64;
+    p.nbag = p.bag ? (size_t)p.K1p : 0;
+    p.nslab = p.off_bag + p.nbag * 64;
+    p.bf16 = c.precision == FNN_PREC_BF16; p.split = c.precision == FNN_PREC_BF16X3;
+    p.strip_shape = strip_shape_ok(p);
+    p.strip_ok = kn.fused && p.strip_shape;
+    p.three_launch_max_B = p.strip_ok ? SORT_N : 0;
+    // Split-K and the form of the weight-gradient products (the measurements: DESIGN.md section 4, "The step's host side").
+    // eight: handles whose every step takes the three launches with the quarter-column or half-chunk scatter role beside the
+    // products in launch 2 (FM rows, f32 and bf16, max_batch <= 4096); everything else four -- the layer-by-layer kernels, bag mode,
+    // the bf16 pairs, the slot-per-lane role.  lds_dflt: the same handles in bf16, where a slice of the handle's largest batch at
+    // split-K 4 holds a whole stage (max_batch > 256), stage the products' operands through LDS, which buys split-K 4 again.  An
+    // explicit FNN_WGRAD_FORM=lds takes the form anywhere in bf16 and moves no split-K; FNN_SPLITK overrules the split.
+    const bool eight = p.strip_ok && !p.bag && kn.scat_form != SCAT1_SLOT && !p.split && p.Bmax <= SORT_N;
+    const bool lds_dflt = kn.wgrad_form == -1 && eight && p.bf16 && p.ldT / 4 / Traits<bf16_t>::KS >= WGRAD_LDS_S;
+    p.wgrad_lds = kn.wgrad_form == WGRAD_LDS || lds_dflt ? 1 : 0;
+    p.splitk = kn.splitk ? kn.splitk : (eight && !lds_dflt ? 8 : 4);
+    return p;
 }
 
 }  // namespace
@@ -846,8 +922,8 @@ int fnn_create(const fnn_cfg* cfg, fnn_handle** out)
     if (cfg->max_batch < 1 || cfg->max_batch > 16384) { g_create_err = "max_batch must be in [1, 16384] (per-field LDS sort)"; return FNN_ERR_ARG; }
     if (cfg->precision != FNN_PREC_F32 && cfg->precision != FNN_PREC_BF16 && cfg->precision != FNN_PREC_BF16X3) { g_create_err = "bad precision"; return FNN_ERR_ARG; }
     if (cfg->act < 0 || cfg->act > 2) { g_create_err = "bad act"; return FNN_ERR_ARG; }
-    const int wgrad_form = wgrad_form_env();
-    if (wgrad_form == -2) { g_create_err = "FNN_WGRAD_FORM must be direct or lds"; return FNN_ERR_ARG; }
+    const FnnKnobs kn = read_knobs(cfg->mode == FNN_MODE_BAG);
+    if (kn.wgrad_form == -2) { g_create_err = "FNN_WGRAD_FORM must be direct or lds"; return FNN_ERR_ARG; }
     int ndev = 0;
     hipError_t e = hipGetDeviceCount(&ndev);
     if (e != hipSuccess || ndev <= 0) {
@@ -856,81 +932,36 @@ int fnn_create(const fnn_cfg* cfg, fnn_handle** out)
     }
     if (cfg->device < 0 || cfg->device >= ndev) { g_create_err = "device ordinal out of range"; return FNN_ERR_ARG; }
     fnn_handle* h = new fnn_handle();
-    h->cfg = *cfg; h->dev = cfg->device;
-    auto fail = [&](int code) { g_create_err = h->err; fnn_destroy(h); return code; };
-#define CK(expr) do { int rc_ = (expr); if (rc_ != FNN_OK) return fail(rc_); } while (0)
-#define HK(expr) do { hipError_t e2_ = (expr); if (e2_ != hipSuccess) { h->err = std::string(#expr) + ": " + hipGetErrorString(e2_); return fail(FNN_ERR_HIP); } } while (0)
-    HK(hipSetDevice(h->dev));
+    static_cast<FnnPlan&>(*h) = make_plan(*cfg, kn);
+    h->cfg = *cfg; h->dev = cfg->device; h->kn = kn;
+    auto fail = [&] { g_create_err = h->err; fnn_destroy(h); };        // the cleanup of every early return below
+#define OWN(p, n, ...) RCCHK(alloc_owned(h, p, n, ##__VA_ARGS__), fail())
+    HIPCHK(h, hipSetDevice(h->dev), fail());
     if (cfg->stream) { h->st = (hipStream_t)cfg->stream; h->own_stream = false; }
-    else { HK(hipStreamCreateWithFlags(&h->st, hipStreamNonBlocking)); h->own_stream = true; }
-    h->F = cfg->n_fields; h->K = cfg->k; h->H1 = cfg->hidden1; h->H2 = cfg->hidden2;
-    h->xdim = 1 + h->F * h->K;
-    h->K1p = rup(h->F * SLOT, 64); h->H1p = rup(h->H1 + 1, 64); h->H2p = rup(h->H2 + 1, 64);
-    h->bag = cfg->mode == FNN_MODE_BAG;
-    if (const char* e = getenv("FNN_WT_STORES")) h->wt_stores = atoi(e);
-    if (const char* e = getenv("FNN_STEP1_WAVES")) h->step1_waves = atoi(e) == 4 ? 4 : 8;
-    if (const char* e = getenv("FNN_STEP1_FORM")) h->step1_fixed = strcmp(e, "generic") != 0;      // fixed | generic; anything else: the default, fixed
-    if (h->bag) { h->rw = cfg->h0; h->K = cfg->h0; h->xdim = cfg->h0; h->K1p = rup(cfg->h0 + 1, 64); }
-    h->wide = !h->bag && h->K >= 17;
-    if (h->wide) { h->rw = rup(h->K, 4); h->K1p = rup(h->F * h->rw + 2, 64); }       // field columns, then w_0 and the ones column
-    h->Bmax = cfg->max_batch; h->ldT = rup(h->Bmax, 256);
-    h->N2max = SORT_N; while (h->N2max < h->Bmax) h->N2max <<= 1;    // the three-launch path groups SORT_N slots per field whatever max_batch is
-    h->n1 = (size_t)h->K1p * h->H1p; h->n2 = (size_t)h->H1p * h->H2p;
-    h->nw12 = h->n1 + h->n2; h->nw = h->nw12 + h->H2p;
-    h->bf16 = cfg->precision == FNN_PREC_BF16; h->split = cfg->precision == FNN_PREC_BF16X3;
-    if (const char* ev = getenv("FNN_NO_FUSE")) h->fused = !(ev[0] == '1');
-    if (const char* ev = getenv("FNN_ROLE_OFF")) h->role_off = atoi(ev);
-    h->scat_form = scat1_form_env();
-    h->scat2_form = scat2_form_env();
-    h->sort_merge4 = sort_merge4_env(h->bag ? 0 : 1);
-    // the quarter-column scatter role leaves launch 2 the residency for eight K slices of the weight gradients (bf16 37.4 us per
-    // step against 38.4 with four, f32 57.1 against 61.4; the bf16 pairs 46.9 against 45.1 and stay at four; beside the
-    // slot-per-lane role eight are slower: 39.8 against 39.1) -- profiles/scat1_forms_ab.json
-    // (handles whose every step of up to 4096 examples takes the three launches; the layer-by-layer kernels keep four)
-    // (beside the half-chunk role, scat1h_body, the splits stay as they are: bf16 with the LDS form 31.3 us per step at eight
-    // slices against 29.8 at four -- profiles/scat1_half_ab.json)
-    const bool steps3 = h->fused && mlp_shape_ok(h) && !h->bag && h->scat_form != SCAT1_SLOT && !h->split && h->Bmax <= SORT_N;
-    if (steps3) h->splitk = 8;
-    // FNN_WGRAD_FORM: the bf16 weight gradients through LDS (wgrad_tile) are 2.8 us shorter alone (role time 11.8 -> 9.0 us) but
-    // leave launch 2 beside the scatter role where it was (33.8 us per step either way); what they buy is split-K 4 again, which
-    // the direct form cannot afford (its role alone is as long as the launch): half the role's workgroups beside the scatter
-    // chain and half the slabs in launch 3 -- 33.6 -> 32.3 us per step, k_step2 12.7 -> 11.0 us (profiles/wgrad_lds_ab.json).
-    // The default on the same handles as above in bf16, where a slice of the handle's largest batch at split-K 4 holds a whole
-    // stage (max_batch > 256; smaller handles keep the direct form at split-K 8: the bit-equality test of the two scatter forms
-    // pins that split there, though batch 256 measured 25.4 -> 24.4 us).  Bag mode keeps the direct form (the SNN step:
-    // 47.7 against 48.3 us with lds).  An explicit FNN_WGRAD_FORM=lds takes the form anywhere in bf16 and moves no split-K.
-    const bool lds_dflt = steps3 && h->bf16 && h->ldT / 4 / Traits<bf16_t>::KS >= WGRAD_LDS_S;
-    h->wgrad_lds = wgrad_form == WGRAD_LDS || (wgrad_form == -1 && lds_dflt) ? 1 : 0;
-    if (wgrad_form == -1 && lds_dflt) h->splitk = 4;
-    if (const char* ev = getenv("FNN_SPLITK")) { const int v = atoi(ev); if (v == 2 || v == 4 || v == 8 || v == 16) h->splitk = v; }   // tuning knob
-    if (const char* ev = getenv("FNN_SCAT2_WGS")) { const int v = atoi(ev); if (v >= 16 && v <= 1024) h->scat2_wgs = v; }
+    else { HIPCHK(h, hipStreamCreateWithFlags(&h->st, hipStreamNonBlocking), fail()); h->own_stream = true; }
     const size_t ts = tsize(h), Ba = h->ldT;
-    CK(alloc_dev(h, &h->master, h->nw));
-    h->off_bag = h->nw12 + (size_t)h->H2p * 64;
-    h->nbag = h->bag ? (size_t)h->K1p : 0;
-    CK(alloc_dev(h, &h->bucket, h->nw + h->nbag));
-    h->nslab = h->off_bag + h->nbag * 64;
-    CK(alloc_dev(h, &h->slab, (size_t)h->splitk * h->nslab));
-    CK(alloc_dev(h, (char**)&h->w1, h->n1 * ts));   CK(alloc_dev(h, (char**)&h->w1t, h->n1 * ts));
-    CK(alloc_dev(h, (char**)&h->w2, h->n2 * ts));   CK(alloc_dev(h, (char**)&h->w2t, h->n2 * ts));
-    CK(alloc_dev(h, (char**)&h->xp, Ba * h->K1p * ts));  CK(alloc_dev(h, (char**)&h->xpT, Ba * h->K1p * ts));
-    CK(alloc_dev(h, (char**)&h->d1, Ba * h->H1p * ts));  CK(alloc_dev(h, (char**)&h->d1T, Ba * h->H1p * ts));
-    CK(alloc_dev(h, (char**)&h->dl1, Ba * h->H1p * ts)); CK(alloc_dev(h, (char**)&h->dl1T, Ba * h->H1p * ts));
-    CK(alloc_dev(h, (char**)&h->d2, Ba * h->H2p * ts));
-    CK(alloc_dev(h, (char**)&h->dl2, Ba * h->H2p * ts)); CK(alloc_dev(h, (char**)&h->dl2T, Ba * h->H2p * ts));
-    CK(alloc_dev(h, &h->gxp, Ba * h->K1p));
-    CK(alloc_dev(h, &h->p_buf, Ba));
-    CK(alloc_dev(h, (char**)&h->d2T, Ba * h->H2p * ts));
-    CK(alloc_dev(h, (char**)&h->dl3T, Ba * 64 * ts));
-    CK(alloc_dev(h, &h->loss_t, Ba));
-    CK(alloc_dev(h, &h->loss_dev, (size_t)1));
-    for (auto& sl : h->slot) HK(row_group_alloc(sl, h->F, h->N2max, h->bag || h->wide, h->rw, h->st));
+    OWN(&h->master, h->nw);
+    OWN(&h->bucket, h->nw + h->nbag);
+    OWN(&h->slab, (size_t)h->splitk * h->nslab);
+    OWN((char**)&h->w1, h->n1 * ts);   OWN((char**)&h->w1t, h->n1 * ts);
+    OWN((char**)&h->w2, h->n2 * ts);   OWN((char**)&h->w2t, h->n2 * ts);
+    OWN((char**)&h->xp, Ba * h->K1p * ts);  OWN((char**)&h->xpT, Ba * h->K1p * ts);
+    OWN((char**)&h->d1, Ba * h->H1p * ts);  OWN((char**)&h->d1T, Ba * h->H1p * ts);
+    OWN((char**)&h->dl1, Ba * h->H1p * ts); OWN((char**)&h->dl1T, Ba * h->H1p * ts);
+    OWN((char**)&h->d2, Ba * h->H2p * ts);
+    OWN((char**)&h->dl2, Ba * h->H2p * ts); OWN((char**)&h->dl2T, Ba * h->H2p * ts);
+    OWN(&h->gxp, Ba * h->K1p);
+    OWN((char**)&h->d2T, Ba * h->H2p * ts);
+    OWN((char**)&h->dl3T, Ba * 64 * ts);
+    OWN(&h->loss_t, Ba);
+    OWN(&h->loss_dev, (size_t)1);
+    for (auto& sl : h->slot) HIPCHK(h, row_group_alloc(sl, h->F, h->N2max, h->bag || h->wide, h->rw, h->st), fail());
     if (h->bag) {
-        if (!mlp_shape_ok(h)) { h->err = "FNN_MODE_BAG needs hidden sizes the strip kernel is built for: hidden1 256..319 with hidden2 64..127 (e.g. 300/100) at any h0, or hidden1 <= 63 with hidden2 <= 63 at h0 <= 252"; return fail(FNN_ERR_ARG); }
-        CK(alloc_dev(h, &h->bb0, (size_t)h->K1p));
-        CK(alloc_dev(h, (char**)&h->dlxT, Ba * h->K1p * ts));
-        CK(alloc_dev(h, (char**)&h->onesT, Ba * 64 * ts));
-        CK(alloc_dev(h, &h->gx_raw, Ba * h->K1p));
+        if (!h->strip_shape) FAIL(h, FNN_ERR_ARG, "FNN_MODE_BAG needs hidden sizes the strip kernel is built for: hidden1 256..319 with hidden2 64..127 (e.g. 300/100) at any h0, or hidden1 <= 63 with hidden2 <= 63 at h0 <= 252", fail());
+        OWN(&h->bb0, (size_t)h->K1p);
+        OWN((char**)&h->dlxT, Ba * h->K1p * ts);
+        OWN((char**)&h->onesT, Ba * 64 * ts);
+        OWN(&h->gx_raw, Ba * h->K1p);
         // onesT: fragment-tiled [64][ldT] matrix whose row 0 is all ones (column sums via MFMA)
         std::vector<unsigned char> ones(Ba * 64 * ts, 0);
         for (size_t t = 0; t < Ba; ++t) {
@@ -940,36 +971,36 @@ int fnn_create(const fnn_cfg* cfg, fnn_handle** out)
         }
         // alloc_dev zeroes with hipMemsetAsync on the handle's (non-blocking) stream, which a null-stream hipMemcpy does not
         // wait for: without this sync the zeroing could land AFTER the copy (seen as a bag bias that never moved, one run in a few)
-        HK(hipStreamSynchronize(h->st));
-        HK(hipMemcpy(h->onesT, ones.data(), ones.size(), hipMemcpyHostToDevice));
+        HIPCHK(h, hipStreamSynchronize(h->st), fail());
+        HIPCHK(h, hipMemcpy(h->onesT, ones.data(), ones.size(), hipMemcpyHostToDevice), fail());
     }
-    h->key64 = true;                                                  // refined when the table is set
-    CK(alloc_dev(h, (char**)&h->skeys, (size_t)h->F * SORT_N * 8));
+    BY_PREC(h, plan_step1, (h));
+    BY_PREC(h, plan_keys, (h, true));                                 // 64-bit keys until the table is set
+    OWN((char**)&h->skeys, (size_t)h->F * SORT_N * 8);
     h->cpow_cap = h->N2max + 1;
-    CK(alloc_dev(h, &h->cpow_dev, (size_t)h->cpow_cap));
-    CK(alloc_dev(h, &h->err_flag, (size_t)1));
-    CK(alloc_dev(h, &h->ones_u8, (size_t)(h->H1p + h->H2p), false));
-    HK(hipMemsetAsync(h->ones_u8, 1, (size_t)(h->H1p + h->H2p), h->st));
-    CK(alloc_dev(h, &h->st_ids, (size_t)h->Bmax * h->F));
-    CK(alloc_dev(h, &h->st_y, (size_t)h->Bmax));
-    CK(alloc_dev(h, &h->st_m1, (size_t)h->H1p)); CK(alloc_dev(h, &h->st_m2, (size_t)h->H2p));
-    CK(alloc_dev(h, &h->st_p, (size_t)h->Bmax));
-    CK(alloc_dev(h, &h->st_x, (size_t)h->Bmax * h->xdim));
-    // dynamic LDS beyond the 64 KB default, set once and for every size a later call can ask for (round-2 advisor: the workspace
-    // of a global batch grows monotonically, so a smaller batch after a larger one used to launch k_sort<8> without its attribute;
+    RCCHK(alloc_dev(h, &h->cpow_dev, (size_t)h->cpow_cap), fail());   // (regrown by ensure_global_ws: freed by name)
+    OWN(&h->err_flag, (size_t)1);
+    OWN(&h->ones_u8, (size_t)(h->H1p + h->H2p), false);
+    HIPCHK(h, hipMemsetAsync(h->ones_u8, 1, (size_t)(h->H1p + h->H2p), h->st), fail());
+    OWN(&h->st_ids, (size_t)h->Bmax * h->F);
+    OWN(&h->st_y, (size_t)h->Bmax);
+    OWN(&h->st_m1, (size_t)h->H1p); OWN(&h->st_m2, (size_t)h->H2p);
+    OWN(&h->st_p, (size_t)h->Bmax);
+    OWN(&h->st_x, (size_t)h->Bmax * h->xdim);
+#undef OWN
+    // dynamic LDS beyond the 64 KB default, set once and for every size a later call can ask for (the workspace of a global batch
+    // grows monotonically, so a smaller batch after a larger one used to launch k_sort<8> without its attribute;
     // with the kernel's static counter k_sort<8> at 8192 keys is 65,540 bytes)
-    HK(hipFuncSetAttribute((const void*)k_sort<8>, hipFuncAttributeMaxDynamicSharedMemorySize, 8192 * 8));
-    HK(hipFuncSetAttribute((const void*)k_sort<16>, hipFuncAttributeMaxDynamicSharedMemorySize, 16384 * 8));
+    HIPCHK(h, hipFuncSetAttribute((const void*)k_sort<8>, hipFuncAttributeMaxDynamicSharedMemorySize, 8192 * 8), fail());
+    HIPCHK(h, hipFuncSetAttribute((const void*)k_sort<16>, hipFuncAttributeMaxDynamicSharedMemorySize, 16384 * 8), fail());
     if (!h->bag) {
         // 65,600 bytes at F = 64, K = 15; wide rows: 133,152 at F * K = 4096, F = 64 (8 examples per tile)
         const size_t gl = (size_t)(h->wide ? GR_EX_WIDE : GR_EX) * (h->xdim + h->F) * sizeof(float);
-        if (gl > 160 * 1024) { h->err = "n_fields * k too large for the reference-layout gather tile"; return fail(FNN_ERR_ARG); }
+        if (gl > 160 * 1024) FAIL(h, FNN_ERR_ARG, "n_fields * k too large for the reference-layout gather tile", fail());
         const void* kf = h->wide ? (const void*)k_gather_ref<GR_EX_WIDE, true> : (const void*)k_gather_ref<GR_EX, false>;
-        HK(hipFuncSetAttribute(kf, hipFuncAttributeMaxDynamicSharedMemorySize, (int)std::max(gl, (size_t)65536)));
+        HIPCHK(h, hipFuncSetAttribute(kf, hipFuncAttributeMaxDynamicSharedMemorySize, (int)std::max(gl, (size_t)65536)), fail());
     }
-    HK(hipStreamSynchronize(h->st));
-#undef CK
-#undef HK
+    HIPCHK(h, hipStreamSynchronize(h->st), fail());
     *out = h;
     return FNN_OK;
 }
@@ -981,13 +1012,11 @@ int fnn_destroy(fnn_handle* h)
     if (h->st) hipStreamSynchronize(h->st);
     if (h->comm && h->dp_own_comm && g_rccl.CommDestroy) g_rccl.CommDestroy(h->comm);
     p2p_release(h);
-    for (void* q : {(void*)h->tag_first, (void*)h->slot[0].tag_shared, (void*)h->slot[1].tag_shared, (void*)h->shadow_dev, (void*)h->xg_ids_send, (void*)h->xg_ids, (void*)h->xg_gxp, h->gws}) if (q) hipFree(q);
     for (auto& kv : h->prof_slots) for (auto& p : kv.second.ev) { hipEventDestroy(p.first); hipEventDestroy(p.second); }
-    void* ptrs[] = {h->table16, h->field_of_row, h->master, h->bucket, h->slab, h->w1, h->w1t, h->w2, h->w2t,
-                    h->xp, h->xpT, h->d1, h->d1T, h->d2, h->dl2, h->dl2T, h->dl1, h->dl1T, h->gxp, h->p_buf,
-                    h->loss_t, h->d2T, h->dl3T, h->loss_dev, h->cpow_dev, h->err_flag, h->ones_u8, h->skeys, h->bb0, h->dlxT, h->onesT, h->gx_raw,
-                    h->st_ids, h->st_y, h->st_m1, h->st_m2, h->st_p, h->st_x};
-    for (void* p : ptrs) if (p) hipFree(p);
+    // what is regrown while the handle lives, by name; then the record of what fnn_create allocated for good
+    for (void* q : {(void*)h->table16, (void*)h->field_of_row, (void*)h->tag_first, (void*)h->slot[0].tag_shared, (void*)h->slot[1].tag_shared, (void*)h->cpow_dev,
+                    (void*)h->shadow_dev, (void*)h->xg_ids_send, (void*)h->xg_ids, (void*)h->xg_gxp, h->gws}) if (q) hipFree(q);
+    for (void* q : h->owned) hipFree(q);
     for (fnn_handle::SortSlot* sl : {&h->slot[0], &h->slot[1], &h->gsl}) row_group_free(*sl);
     if (h->own_stream && h->st) hipStreamDestroy(h->st);
     delete h;
@@ -1046,7 +1075,7 @@ int fnn_set_table(fnn_handle* h, const float* rows, int64_t n_rows, const int32_
         h->tag_stamp = 0;
     }
     h->n_rows = n_rows; h->w0 = w0;
-    h->key64 = (unsigned long long)n_rows * SORT_N > 0xFFFFFFFFull;     // else 32-bit (row << 12 | t) keys
+    BY_PREC(h, plan_keys, (h, (unsigned long long)n_rows * SORT_N > 0xFFFFFFFFull));     // else 32-bit (row << 12 | t) keys
     h->sorted_ids = nullptr; h->next_ids = nullptr;
     return FNN_OK;
 }
@@ -1223,28 +1252,24 @@ int fnn_gather(fnn_handle* h, const int32_t* ids, int B, float* x_out, int memki
     for (int lo = 0; lo < B; lo += host ? h->Bmax : B) {
         const int nb = host ? std::min(h->Bmax, B - lo) : B;
         const int32_t* ids_dev = ids + (size_t)lo * h->F; float* x_dev = x_out + (size_t)lo * h->xdim;
-        if (host) {
-            HIPCHK(h, hipMemcpyAsync(h->st_ids, ids + (size_t)lo * h->F, (size_t)nb * h->F * 4, hipMemcpyHostToDevice, h->st));
-            ids_dev = h->st_ids; x_dev = h->st_x;
-        }
         const size_t n = (size_t)nb * h->xdim;
+        Staged sg{h, host};
+        RCCHK(sg.in(ids_dev, h->st_ids, (size_t)nb * h->F));
+        sg.out(x_dev, h->st_x, n);
         {
             ProfScope ps(h, "gather_ref", h->st);
             if (h->bag)
                 hipLaunchKernelGGL(k_bag_ref, dim3((unsigned)((n / 4 + 255) / 256)), dim3(256), 0, h->st, ids_dev, nb, h->F,
-                                   h->rw, h->table16, h->n_rows, h->bb0, x_dev, h->err_flag, (h->wt_stores & 16) != 0);   // (measured: 1 % slower written through -- off)
+                                   h->rw, h->table16, h->n_rows, h->bb0, x_dev, h->err_flag, (h->kn.wt_stores & 16) != 0);   // (measured: 1 % slower written through -- off)
             else if (h->wide)
                 hipLaunchKernelGGL((k_gather_ref<GR_EX_WIDE, true>), dim3((unsigned)((nb + GR_EX_WIDE - 1) / GR_EX_WIDE)), dim3(256), (size_t)GR_EX_WIDE * (h->xdim + h->F) * sizeof(float), h->st,
-                                   ids_dev, nb, h->F, h->K, h->table16, h->n_rows, h->w0, x_dev, h->err_flag, (h->wt_stores & 8) != 0, h->rw);
+                                   ids_dev, nb, h->F, h->K, h->table16, h->n_rows, h->w0, x_dev, h->err_flag, (h->kn.wt_stores & 8) != 0, h->rw);
             else
                 hipLaunchKernelGGL((k_gather_ref<GR_EX, false>), dim3((unsigned)((nb + GR_EX - 1) / GR_EX)), dim3(256), (size_t)GR_EX * (h->xdim + h->F) * sizeof(float), h->st, ids_dev, nb, h->F,
-                                   h->K, h->table16, h->n_rows, h->w0, x_dev, h->err_flag, (h->wt_stores & 8) != 0, SLOT);
+                                   h->K, h->table16, h->n_rows, h->w0, x_dev, h->err_flag, (h->kn.wt_stores & 8) != 0, SLOT);
         }
-        if (host) {
-            HIPCHK(h, hipMemcpyAsync(x_out + (size_t)lo * h->xdim, x_dev, n * 4, hipMemcpyDeviceToHost, h->st));
-            const int rc = check_async(h);              // (synchronises: the staging buffers are free for the next chunk)
-            if (rc != FNN_OK) return rc;
-        }
+        RCCHK(sg.copy_back());
+        if (host) RCCHK(check_async(h));                // (synchronises: the staging buffers are free for the next chunk)
     }
     return FNN_OK;
 }
@@ -1253,45 +1278,34 @@ static int step_impl(fnn_handle* h, const int32_t* ids, const float* y, int B, c
                      const uint8_t* mask2, int b_size, float* p_out, float* gx_out, int memkind,
                      bool inline_update)
 {
-    int rc = check_ready(h, B);
-    if (rc != FNN_OK) return rc;
+    RCCHK(check_ready(h, B));
     if (!ids || !y || !mask1 || !mask2) FAIL(h, FNN_ERR_ARG, "ids, y, mask1, mask2 must be non-null");
     if (h->in_step) FAIL(h, FNN_ERR_STATE, "fnn_step_begin called twice without fnn_step_end");
     HIPCHK(h, hipSetDevice(h->dev));
     if (b_size <= 0) b_size = B;
-    rc = update_cpow(h, b_size, B);
-    if (rc != FNN_OK) return rc;
-    const int32_t* ids_d = ids; const float* y_d = y; const uint8_t *m1 = mask1, *m2 = mask2;
-    float* p_d = p_out; float* gx_d = gx_out;
-    if (memkind == FNN_MEM_HOST) {
-        HIPCHK(h, hipMemcpyAsync(h->st_ids, ids, (size_t)B * h->F * 4, hipMemcpyHostToDevice, h->st));
-        HIPCHK(h, hipMemcpyAsync(h->st_y, y, (size_t)B * 4, hipMemcpyHostToDevice, h->st));
-        HIPCHK(h, hipMemcpyAsync(h->st_m1, mask1, (size_t)h->H1, hipMemcpyHostToDevice, h->st));
-        HIPCHK(h, hipMemcpyAsync(h->st_m2, mask2, (size_t)h->H2, hipMemcpyHostToDevice, h->st));
-        ids_d = h->st_ids; y_d = h->st_y; m1 = h->st_m1; m2 = h->st_m2;
-        if (p_out) p_d = h->st_p;
-        if (gx_out) gx_d = h->st_x;
-        h->sorted_ids = nullptr; h->next_ids = nullptr;     // staging buffers are reused: no carried grouping
-    }
+    RCCHK(update_cpow(h, b_size, B));
+    Staged sg{h, memkind == FNN_MEM_HOST};
+    RCCHK(sg.in(ids, h->st_ids, (size_t)B * h->F));
+    RCCHK(sg.in(y, h->st_y, (size_t)B));
+    RCCHK(sg.in(mask1, h->st_m1, (size_t)h->H1));
+    RCCHK(sg.in(mask2, h->st_m2, (size_t)h->H2));
+    sg.out(p_out, h->st_p, (size_t)B);
+    sg.out(gx_out, h->st_x, (size_t)B * h->xdim);
+    if (sg.host) { h->sorted_ids = nullptr; h->next_ids = nullptr; }     // staging buffers are reused: no carried grouping
     if (h->n_shadow > 0 && h->bag) FAIL(h, FNN_ERR_ARG, "fnn_set_shadowed: FNN_MODE_FM only");
     if (h->n_shadow > 0 && h->dp && inline_update && h->dp_sparse == FNN_DP_SPARSE_EXCHANGE)
         FAIL(h, FNN_ERR_ARG, "shadowed features are not carried through FNN_DP_SPARSE_EXCHANGE");
     // shadowed features: the layer-by-layer path, whose per-field sort has room for the extra keys
-    const bool fast = h->fused && mlp_shape_ok(h) && B <= SORT_N && h->n_shadow == 0;
+    const bool fast = B <= h->three_launch_max_B && h->n_shadow == 0;
     h->update_pending = !(fast && inline_update);
     h->step_native_dp = inline_update && h->dp;
     h->step_bsize = b_size;
-    if (fast)
-        rc = BY_PREC_RC(h, run_step_fast, (h, ids_d, y_d, B, m1, m2, p_d, gx_d, inline_update));
-    else
-        rc = BY_PREC_RC(h, run_step, (h, ids_d, y_d, B, m1, m2, true, p_d, gx_d));
+    const int rc = fast ? BY_PREC_RC(h, run_step_fast, (h, ids, y, B, mask1, mask2, p_out, gx_out, inline_update))
+                        : BY_PREC_RC(h, run_step, (h, ids, y, B, mask1, mask2, true, p_out, gx_out));
     h->n_shadow = 0;                                            // consumed (also by a failing step)
     if (rc != FNN_OK) return rc;
-    if (memkind == FNN_MEM_HOST) {
-        if (p_out) HIPCHK(h, hipMemcpyAsync(p_out, p_d, (size_t)B * 4, hipMemcpyDeviceToHost, h->st));
-        if (gx_out) HIPCHK(h, hipMemcpyAsync(gx_out, gx_d, (size_t)B * h->xdim * 4, hipMemcpyDeviceToHost, h->st));
-        if (p_out || gx_out) HIPCHK(h, hipStreamSynchronize(h->st));
-    }
+    RCCHK(sg.copy_back());
+    if (sg.nback > 0) HIPCHK(h, hipStreamSynchronize(h->st));
     h->in_step = true; h->step_B = B;
     return FNN_OK;
 }
@@ -1340,8 +1354,7 @@ int fnn_set_shadowed(fnn_handle* h, const int32_t* tfr, int n, int memkind)
 
 int fnn_prefetch_ids(fnn_handle* h, const int32_t* ids, int B)
 {
-    int rc = check_ready(h, B);
-    if (rc != FNN_OK) return rc;
+    RCCHK(check_ready(h, B));
     if (!ids) FAIL(h, FNN_ERR_ARG, "ids null");
     h->next_ids = ids; h->next_B = B;       // grouped by the next step's first launch
     return FNN_OK;
@@ -1353,7 +1366,7 @@ int fnn_step_scatter(fnn_handle* h)
     if (!h->in_step) FAIL(h, FNN_ERR_STATE, "fnn_step_scatter without fnn_step_begin");
     HIPCHK(h, hipSetDevice(h->dev));
     if (h->scatter_pending) {
-        BY_PREC(h, launch_steps23, (h, false, true, false));
+        BY_PREC(h, launch_steps23, (h, make_roles(h, false, true, false)));
         HIPCHK(h, hipGetLastError());
     }
     return FNN_OK;
@@ -1382,8 +1395,7 @@ int fnn_step_scatter_global(fnn_handle* h, const int32_t* ids_g, const float* gx
 int fnn_dp_unique_id(void* id128_out)
 {
     if (!id128_out) { g_create_err = "fnn_dp_unique_id: null pointer"; return FNN_ERR_ARG; }
-    int rc = rccl_load(g_create_err);
-    if (rc != FNN_OK) return rc;
+    RCCHK(rccl_load(g_create_err));
     static_assert(sizeof(ncclUniqueId) == 128, "ncclUniqueId is 128 bytes");
     ncclUniqueId id;
     const ncclResult_t r = g_rccl.GetUniqueId(&id);
@@ -1509,12 +1521,10 @@ int fnn_dp_init(fnn_handle* h, int rank, int world, const void* id128, int spars
 {
     if (!h) return FNN_ERR_ARG;
     if (!id128) FAIL(h, FNN_ERR_ARG, "fnn_dp_init: null unique id");
-    if (h->dp) { int rc = fnn_dp_shutdown(h); if (rc != FNN_OK) return rc; }
+    if (h->dp) RCCHK(fnn_dp_shutdown(h));
     HIPCHK(h, hipSetDevice(h->dev));
-    int rc = rccl_load(h->err);
-    if (rc != FNN_OK) return rc;
-    rc = dp_setup(h, rank, world, sparse_mode);
-    if (rc != FNN_OK) return rc;
+    RCCHK(rccl_load(h->err));
+    RCCHK(dp_setup(h, rank, world, sparse_mode));
     ncclUniqueId id;
     memcpy(&id, id128, sizeof(id));
     HIPCHK(h, hipStreamSynchronize(h->st));
@@ -1531,10 +1541,9 @@ int fnn_dp_init_custom(fnn_handle* h, int rank, int world, fnn_allreduce_fn allr
 {
     if (!h) return FNN_ERR_ARG;
     if (!allreduce || (sparse_mode == FNN_DP_SPARSE_EXCHANGE && !allgather)) FAIL(h, FNN_ERR_ARG, "fnn_dp_init_custom: null callback");
-    if (h->dp) { int rc = fnn_dp_shutdown(h); if (rc != FNN_OK) return rc; }
+    if (h->dp) RCCHK(fnn_dp_shutdown(h));
     HIPCHK(h, hipSetDevice(h->dev));
-    int rc = dp_setup(h, rank, world, sparse_mode);
-    if (rc != FNN_OK) return rc;
+    RCCHK(dp_setup(h, rank, world, sparse_mode));
     h->dp_allreduce = allreduce; h->dp_allgather = allgather; h->dp_ctx = ctx;
     h->dp = true;
     return FNN_OK;
@@ -1552,11 +1561,10 @@ int fnn_step_end(fnn_handle* h, float* loss_sum_out)
     if (!h) return FNN_ERR_ARG;
     if (!h->in_step) FAIL(h, FNN_ERR_STATE, "fnn_step_end without fnn_step_begin");
     HIPCHK(h, hipSetDevice(h->dev));
-    if (h->scatter_pending) { int rc = fnn_step_scatter(h); if (rc != FNN_OK) return rc; }
+    if (h->scatter_pending) RCCHK(fnn_step_scatter(h));
     if (h->update_pending) {
         if (h->step_native_dp && dp_bucket_mode(h)) {     // layer-by-layer path under native data parallelism, bucket payload
-            int rc = BY_PREC_RC(h, dp_finish_bucket, (h, false));
-            if (rc != FNN_OK) { h->in_step = false; return rc; }
+            RCCHK(BY_PREC_RC(h, dp_finish_bucket, (h, false)), h->in_step = false);
         } else {                                           // (slabs payload: k_reduce already summed GLOBAL slabs)
             ProfScope ps(h, "update", h->st);
             BY_PREC(h, launch_update, (h, h->bucket, h->cfg.lr));
@@ -1580,67 +1588,54 @@ int fnn_train_step(fnn_handle* h, const int32_t* ids, const float* y, int B, con
                    const uint8_t* mask2, int b_size, float* p_out, float* gx_out, int memkind,
                    float* loss_sum_out)
 {
-    int rc = step_impl(h, ids, y, B, mask1, mask2, b_size, p_out, gx_out, memkind, true);
-    if (rc != FNN_OK) return rc;
+    RCCHK(step_impl(h, ids, y, B, mask1, mask2, b_size, p_out, gx_out, memkind, true));
     return fnn_step_end(h, loss_sum_out);
 }
 
 int fnn_predict(fnn_handle* h, const int32_t* ids, int B, float* p_out, int memkind)
 {
-    int rc = check_ready(h, B);
-    if (rc != FNN_OK) return rc;
+    RCCHK(check_ready(h, B));
     if (!ids || !p_out) FAIL(h, FNN_ERR_ARG, "null pointer");
     HIPCHK(h, hipSetDevice(h->dev));
-    const int32_t* ids_d = ids; float* p_d = p_out;
-    if (memkind == FNN_MEM_HOST) {
-        HIPCHK(h, hipMemcpyAsync(h->st_ids, ids, (size_t)B * h->F * 4, hipMemcpyHostToDevice, h->st));
-        ids_d = h->st_ids; p_d = h->st_p;
-    }
-    rc = BY_PREC_RC(h, run_step, (h, ids_d, nullptr, B, nullptr, nullptr, false, p_d, nullptr));
-    if (rc != FNN_OK) return rc;
+    Staged sg{h, memkind == FNN_MEM_HOST};
+    RCCHK(sg.in(ids, h->st_ids, (size_t)B * h->F));
+    sg.out(p_out, h->st_p, (size_t)B);
+    RCCHK(BY_PREC_RC(h, run_step, (h, ids, nullptr, B, nullptr, nullptr, false, p_out, nullptr)));
     HIPCHK(h, hipGetLastError());
-    if (memkind == FNN_MEM_HOST) {
-        HIPCHK(h, hipMemcpyAsync(p_out, p_d, (size_t)B * 4, hipMemcpyDeviceToHost, h->st));
-        return check_async(h);
-    }
-    return FNN_OK;
+    RCCHK(sg.copy_back());
+    return sg.host ? check_async(h) : FNN_OK;
 }
 
 int fnn_eval(fnn_handle* h, const int32_t* ids, const int32_t* y, int64_t N, int memkind, double* auc, double* rmse,
              double* logloss, float* p_out)
 {
-    int rc = check_ready(h, 1);
-    if (rc != FNN_OK) return rc;
+    RCCHK(check_ready(h, 1));
     if (!ids || !y || N < 1) FAIL(h, FNN_ERR_ARG, "ids / y null or N < 1");
     HIPCHK(h, hipSetDevice(h->dev));
     const bool host = memkind == FNN_MEM_HOST;
     int32_t *ids_d = nullptr, *y_d = nullptr; float* p_d = nullptr;
     auto cleanup = [&]() { if (host) { if (ids_d) hipFree(ids_d); if (y_d) hipFree(y_d); } if (p_d && p_d != p_out) hipFree(p_d); };
-#define EK(expr) do { hipError_t e_ = (expr); if (e_ != hipSuccess) { h->err = std::string(#expr) + ": " + hipGetErrorString(e_); cleanup(); return FNN_ERR_HIP; } } while (0)
     if (host) {
-        EK(hipMalloc((void**)&ids_d, (size_t)N * h->F * 4)); EK(hipMalloc((void**)&y_d, (size_t)N * 4));
-        EK(hipMemcpyAsync(ids_d, ids, (size_t)N * h->F * 4, hipMemcpyHostToDevice, h->st));
-        EK(hipMemcpyAsync(y_d, y, (size_t)N * 4, hipMemcpyHostToDevice, h->st));
+        HIPCHK(h, hipMalloc((void**)&ids_d, (size_t)N * h->F * 4), cleanup()); HIPCHK(h, hipMalloc((void**)&y_d, (size_t)N * 4), cleanup());
+        HIPCHK(h, hipMemcpyAsync(ids_d, ids, (size_t)N * h->F * 4, hipMemcpyHostToDevice, h->st), cleanup());
+        HIPCHK(h, hipMemcpyAsync(y_d, y, (size_t)N * 4, hipMemcpyHostToDevice, h->st), cleanup());
     } else { ids_d = const_cast<int32_t*>(ids); y_d = const_cast<int32_t*>(y); }
-    if (p_out && !host) p_d = p_out; else EK(hipMalloc((void**)&p_d, (size_t)N * 4));
+    if (p_out && !host) p_d = p_out; else HIPCHK(h, hipMalloc((void**)&p_d, (size_t)N * 4), cleanup());
     for (int64_t lo = 0; lo < N; lo += h->Bmax) {
         const int B = (int)std::min<int64_t>(h->Bmax, N - lo);
-        rc = BY_PREC_RC(h, run_step, (h, ids_d + lo * h->F, nullptr, B, nullptr, nullptr, false, p_d + lo, nullptr));
-        if (rc != FNN_OK) { cleanup(); return rc; }
+        RCCHK(BY_PREC_RC(h, run_step, (h, ids_d + lo * h->F, nullptr, B, nullptr, nullptr, false, p_d + lo, nullptr)), cleanup());
     }
-    EK(hipGetLastError());
+    HIPCHK(h, hipGetLastError(), cleanup());
     double out[4] = {0, 0, 0, 0};
     std::string merr;
     const int mrc = device_metrics(h->st, p_d, y_d, N, out, merr);
-    if (mrc == -1) { h->err = merr; cleanup(); return FNN_ERR_HIP; }
-    if (p_out && host) EK(hipMemcpy(p_out, p_d, (size_t)N * 4, hipMemcpyDeviceToHost));
-#undef EK
+    if (mrc == -1) FAIL(h, FNN_ERR_HIP, merr, cleanup());
+    if (p_out && host) HIPCHK(h, hipMemcpy(p_out, p_d, (size_t)N * 4, hipMemcpyDeviceToHost), cleanup());
     cleanup();
     if (auc) *auc = out[0];
     if (rmse) *rmse = out[1];
     if (logloss) *logloss = out[2];
-    rc = check_async(h);
-    if (rc != FNN_OK) return rc;
+    RCCHK(check_async(h));
     if (mrc == -2 || mrc == -3) FAIL(h, FNN_ERR_RANGE, merr);
     return FNN_OK;
 }
@@ -1672,8 +1667,7 @@ int fnn_prof_reset(fnn_handle* h)
 int fnn_prof_get(fnn_handle* h, const char* which, double* avg_ms, int64_t* launches)
 {
     if (!h || !which || !avg_ms) return FNN_ERR_ARG;
-    int rc = prof_collect(h);
-    if (rc != FNN_OK) return rc;
+    RCCHK(prof_collect(h));
     auto it = h->prof_slots.find(which);
     if (it == h->prof_slots.end() || it->second.n == 0) { *avg_ms = 0.0; if (launches) *launches = 0; return FNN_OK; }
     *avg_ms = it->second.ms / (double)it->second.n;

@@ -1,7 +1,7 @@
 """The FNN step at the shapes fnn_create accepts beyond the default layout (16 fields, k = 11, hidden 300 / 100): field counts
 2..64, k = rank + 1 in 1..15, hidden sizes 1..4095 / 1..255, all three precisions, against the float64 oracle.
 
-Both code paths depend on the shape.  Every case id starts with the path the restatement of mlp_shape_ok (fnn_api.hip) below
+Both code paths depend on the shape.  Every case id starts with the path the restatement of strip_shape_ok (fnn_api.hip) below
 predicts:
   strip  the fused strip kernel: K1p = rup(16 F, 64) = 256 (F = 13..16) and hidden sizes padding to 320 / 128 (256..319 /
          64..127) or to 64 / 64 (<= 63 / <= 63).  Its gather writes w_0 into slot k of field 0 and 1.0 into slot k of field 1
@@ -36,7 +36,7 @@ def rup(a, m):
 
 
 def path_of(F, H1, H2):
-    """mlp_shape_ok of fnn_api.hip for FM mode (K1p = rup(16 F, 64), H1p = rup(H1 + 1, 64), H2p = rup(H2 + 1, 64))."""
+    """strip_shape_ok of fnn_api.hip for FM mode (K1p = rup(16 F, 64), H1p = rup(H1 + 1, 64), H2p = rup(H2 + 1, 64))."""
     cx, c1, c2 = rup(16 * F, 64) // 64, rup(H1 + 1, 64) // 64, rup(H2 + 1, 64) // 64
     return 'strip' if cx == 4 and ((c1 == 5 and c2 == 2) or (c1 == 1 and c2 == 1)) else 'layer'
 

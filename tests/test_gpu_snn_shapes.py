@@ -3,8 +3,8 @@ other bag-mode test uses (16 columns, hidden 300 / 100, tanh): 2..64 columns, h0
 kernel is built for, all three activations and precisions, max_batch above 4096 for predict and eval, and a table large
 enough for 64-bit sort keys -- against the float64 oracle.
 
-Bag mode runs on the strip kernel only.  Every case id starts with the instance the restatement of mlp_shape_ok and
-launch_step1 (fnn_api.hip) below predicts:
+Bag mode runs on the strip kernel only.  Every case id starts with the instance the restatement of strip_shape_ok and
+step1_sel (fnn_api.hip) below predicts:
   cx4-c5x2-nw8  k_step1<T, 5, 2, 4, true, 8>   h0 <= 252 (K1p = rup(h0 + 1, 64) = 256), hidden 256..319 / 64..127
   cx5-c5x2-nw8  k_step1<T, 5, 2, 5, true, 8>   h0 >= 256 (K1p = 320), the same hidden pairs
   cx4-c1x1      k_step1<T, 1, 1, 4, true>      h0 <= 252, hidden <= 63 / <= 63 (four waves)
@@ -41,7 +41,7 @@ def rup(a, m):
 
 
 def instance_of(h0, H1, H2, waves=8):
-    """The bag branch of mlp_shape_ok and launch_step1's choice of k_step1 instance; None: fnn_create refuses the pair."""
+    """The bag branch of strip_shape_ok and step1_sel's choice of k_step1 instance; None: fnn_create refuses the pair."""
     cx, c1, c2 = rup(h0 + 1, 64) // 64, rup(H1 + 1, 64) // 64, rup(H2 + 1, 64) // 64
     if c1 == 5 and c2 == 2 and cx in (4, 5):
         return 'cx%d-c5x2-nw%d' % (cx, waves)
@@ -432,7 +432,7 @@ ACCEPTED = [(200, 256, 64), (200, 319, 127), (316, 256, 64), (256, 319, 127)]
 @pytest.mark.parametrize("h0,H1,H2", REFUSED, ids=['h%d-H%dx%d' % c for c in REFUSED])
 def test_hidden_pairs_outside_the_strip_kernel_are_refused(built, h0, H1, H2):
     """fnn_create refuses a bag handle whose hidden pair the strip kernel is not built for, and its message states the ranges
-    mlp_shape_ok accepts: hidden1 256..319 with hidden2 64..127, or both <= 63 at h0 <= 252."""
+    strip_shape_ok accepts: hidden1 256..319 with hidden2 64..127, or both <= 63 at h0 <= 252."""
     assert instance_of(h0, H1, H2) is None
     with pytest.raises(FNNError) as ei:
         FNNEngine(17, 0, H1, H2, max_batch=256, precision='f32', mode='bag', hidden0=h0, reg_all=True, lambda_fm=0.0)
