@@ -155,5 +155,134 @@ def run(argv, out=None):
     return hist
 
 
+def parse_spec(s):
+    """'LR:DROPOUT:LAMBDA1:LAMBDA_FM' -> (lr, dropout, lambda1, lambda_fm); a tuple of the four passes through."""
+    if isinstance(s, str):
+        s = s.split(':')
+    lr, dropout, lambda1, lambda_fm = (float(v) for v in s)
+    return lr, dropout, lambda1, lambda_fm
+
+
+def run_many(argv, specs, out=None):
+    """run()'s schedule for every (lr, dropout, lambda1, lambda_fm) of `specs` in ONE pass over the data: the files are loaded
+    once and the ids are resident once; every model has its own engine, its initial weights from the same seeded draws as run()'s,
+    its own RandomStreams(234) dropout stream, early-stop bookkeeping and best-weights snapshot.  The models still training
+    step together (engine.train_epoch_many: one fnn_train_step_multi per batch); a model that stops leaves the group.
+    Returns the list of histories; the prediction pickles are mlp3fm_{train,test}_<advertiser>_m<i>.p.  `out` (a dict)
+    receives the engines under 'engines', each loaded with its model's best weights."""
+    from deep_ctr_amd.engine import train_epoch_many
+    specs = [parse_spec(s) for s in specs]
+    assert len(specs) >= 1
+    batch_size = 100
+    hidden1, hidden2 = 300, 100
+    acti_type = 'tanh'
+    epoch = int(os.environ.get('DEEPCTR_EPOCHS', 100))
+    advertiser = argv[1] if len(argv) > 1 else '2997'
+    data_dir = os.environ.get('DEEPCTR_DATA_DIR', '../data')
+    train_file = os.path.join(data_dir, 'train.fm.txt')
+    test_file = os.path.join(data_dir, 'test.fm.txt')
+    fm_model_file = os.path.join(data_dir, 'fm.model.txt')
+    if len(argv) > 2 and advertiser == 'all':
+        train_file = train_file + '.5.txt'
+    elif len(argv) > 2:
+        train_file = train_file + '.10.txt'
+    print(train_file)
+    train_size = ut.file_len(train_file)
+    n_batch = train_size // batch_size
+
+    def log_p(m, msg):
+        ut.logfile(msg, "fm" + str(advertiser) + "_m" + str(m))
+
+    data = DataFM(fm_model_file)
+    k, xdim = data.k, data.xdim
+    rows, field_of_row, w_0 = data.table()
+    precision = os.environ.get('DEEPCTR_PRECISION', 'f32')
+
+    class Model(object):
+        pass
+
+    models = []
+    for m, (lr, dropout, lambda1, lambda_fm) in enumerate(specs):
+        mo = Model()
+        log_p(m, 'ad:' + str(advertiser))
+        log_p(m, 'batch_size:' + str(batch_size))
+        log_p(m, 'drop_mlp3fm.py|ad:' + advertiser + '|drop:' + str(dropout) + '|b_size:' + str(batch_size) +
+              ' | X:' + str(xdim) + ' | Hidden 1:' + str(hidden1) + ' | Hidden 2:' + str(hidden2) +
+              ' | L_r:' + str(lr) + ' | activation1:' + str(acti_type) + ' | lambda:' + str(lambda1))
+        srng = ut.RandomStreams(seed=234)
+        ut.seed_global(1234)
+        weights = ut.init_fnn_weights(xdim, hidden1, hidden2, acti_type)
+        srng.binomial(size=(1, xdim), n=1, p=dropout)              # r0: dead, but takes a seed
+        mo.r1 = srng.binomial(size=(1, hidden1), n=1, p=dropout)
+        mo.r2 = srng.binomial(size=(1, hidden2), n=1, p=dropout)
+        mo.eng = FNNEngine(n_fields=len(data.name_field), k=k, hidden1=hidden1, hidden2=hidden2,
+                           max_batch=max(batch_size, 4096), precision=precision, acti_type=acti_type,
+                           lr=lr, lambda1=lambda1, lambda_fm=lambda_fm)
+        mo.eng.set_table(rows, field_of_row, w_0)
+        mo.eng.set_dense(weights)
+        mo.best = mo.eng.get_dense()
+        mo.min_err, mo.min_err_epoch, mo.times_reduce, mo.hist, mo.live = 0, 0, 0, [], True
+        models.append(mo)
+    eng0 = models[0].eng
+    data.engine = eng0
+
+    train_ids, train_y, train_sh = data.load_ids(train_file, want_shadowed=True)
+    test_ids, test_y = data.load_ids(test_file)
+    train_ids_d, train_y_d = eng0.to_device(train_ids, train_y)
+    test_ids_d, test_y_d = eng0.to_device(test_ids, test_y)
+    train_yf_d = train_y_d.float()
+
+    print("Training models:")
+    n_run = n_batch if (n_batch - 1) * batch_size + 1 <= train_size else (train_size + batch_size - 1) // batch_size
+    for i in range(epoch):
+        live = [m for m, mo in enumerate(models) if mo.live]
+        if not live:
+            break
+        start_time = time.time()
+        engs = [models[m].eng for m in live]
+        m1 = [models[m].r1.draw_rows(n_run) for m in live]
+        m2 = [models[m].r2.draw_rows(n_run) for m in live]
+        pre = [models[m].best for m in live]
+        if n_run > 1:
+            train_epoch_many(engs, train_ids_d, train_yf_d, batch_size, m1, m2, 0, n_run - 1, train_sh)
+        if n_run > 0:
+            if n_run == n_batch:
+                pre = [e.get_dense() for e in engs]
+            train_epoch_many(engs, train_ids_d, train_yf_d, batch_size, m1, m2, n_run - 1, 1, train_sh)
+        for e in engs:
+            e.sync()
+        print('training: %d models, %.1fs' % (len(live), time.time() - start_time))
+        for j, m in enumerate(live):
+            mo = models[m]
+            tr = mo.eng.evaluate(train_ids_d, train_y_d)
+            log_p(m, '\t\tTraining Err: \t' + str(i) + '\t' + str(tr['auc']) + '\t' + str(tr['rmse']))
+            te = mo.eng.evaluate(test_ids_d, test_y_d)
+            auc, rmse, ll = te['auc'], te['rmse'], te['logloss']
+            log_p(m, 'Test Err:' + str(i) + '\t' + str(auc) + '\t' + str(rmse))
+            log_p(m, 'Test logloss:' + str(i) + '\t' + str(ll))
+            mo.hist.append({'epoch': i, 'test_auc': auc, 'test_rmse': rmse, 'test_logloss': ll})
+            if auc > mo.min_err:
+                mo.best = pre[j]
+                mo.min_err = auc
+                mo.min_err_epoch = i
+                if mo.times_reduce < 3:
+                    mo.times_reduce += 1
+            else:
+                mo.times_reduce -= 1
+            if mo.times_reduce < 0:
+                mo.live = False
+    for m, mo in enumerate(models):
+        log_p(m, 'Minimal test error is ' + str(mo.min_err) + ' , at EPOCH ' + str(mo.min_err_epoch))
+        mo.eng.set_dense(mo.best)
+        ut.save_weights("mlp3fm_train_" + advertiser + "_m" + str(m) + ".p", mo.eng.predict(train_ids).cpu().numpy())
+        ut.save_weights("mlp3fm_test_" + advertiser + "_m" + str(m) + ".p", mo.eng.predict(test_ids).cpu().numpy())
+    if out is not None:
+        out['engines'] = [mo.eng for mo in models]
+    return [mo.hist for mo in models]
+
+
 if __name__ == '__main__':
-    run(sys.argv)
+    if len(sys.argv) > 1 and sys.argv[1] == 'many':           # python FNN.py many <advertiser> LR:DROPOUT:LAMBDA1:LAMBDA_FM ...
+        run_many([sys.argv[0]] + sys.argv[2:3], sys.argv[3:])
+    else:
+        run(sys.argv)

@@ -25,6 +25,7 @@
 #include "metrics.hip.h"
 #include "optim.hip.h"
 #include "fm_online.hip.h"
+#include "arg_ring.h"
 
 using namespace fnn;
 
@@ -576,18 +577,7 @@ __global__ __launch_bounds__(256) void k_fm_opt_pass(float* __restrict__ table16
     *reinterpret_cast<float4*>(s1 + e0) = make_float4(v[0], v[1], v[2], v[3]);
 }
 
-// The argument arrays of the group calls (fm_train_online_multi, fm_train_step_multi, fm_predict_multi / fm_eval_multi) reach the
-// device through a pinned host ring and its device image, both of the handle in front (hs[0]): a launch's array is written into the
-// next free slots of the one and copied to the same slots of the other on hs[0]'s stream.  The copy is asynchronous, so a slot is
-// the copy's to read until the copy has run: slots are handed out in order and never rewritten before the ring wraps, and a wrap
-// first waits for the event recorded after the latest copy (all copies are on one stream, in order, so that covers every one of
-// them).  The ring persists from call to call for the same reason.  (ring_take, ring_send, ring_release below.)
-struct ArgRing {
-    size_t elem, cap;          // bytes per element, elements per ring
-    void* host = nullptr; void* dev = nullptr; size_t cur = 0; hipEvent_t copied = nullptr;
-    template <typename T> T* at_host(size_t slot) const { return static_cast<T*>(host) + slot; }
-    template <typename T> const T* at_dev(size_t slot) const { return static_cast<const T*>(dev) + slot; }
-};
+// (the argument arrays of the group calls reach the device through an ArgRing of the handle in front: arg_ring.h)
 
 }  // namespace
 
@@ -889,35 +879,16 @@ void launch_opt_pass(fm_handle* h, float lambda, float lr_step)
                            h->rw, lambda, h->opt, lr_step, h->beta1, h->beta2, h->eps);
 }
 
-// ArgRing: n elements of the ring, *slot the first of them.  Allocates on first use, every piece guarded, so that a call that
-// failed half way can be made again; a wrap waits for the latest copy.
+// ArgRing (arg_ring.h) with the failure's text left on the handle in front
 int ring_take(fm_handle* h0, ArgRing& r, size_t n, size_t* slot)
 {
-    if (!r.copied) MHK(h0, hipEventCreateWithFlags(&r.copied, hipEventDisableTiming));
-    if (!r.dev) MHK(h0, hipMalloc(&r.dev, r.cap * r.elem));
-    if (!r.host) MHK(h0, hipHostMalloc(&r.host, r.cap * r.elem, hipHostMallocDefault));
-    if (r.cur + n > r.cap) {
-        MHK(h0, hipEventSynchronize(r.copied));
-        r.cur = 0;
-    }
-    *slot = r.cur;
-    r.cur += n;
+    MHK(h0, fnn::ring_take(r, n, slot));
     return FNN_OK;
 }
-// the n elements written at `slot` of the host ring, to the device image on h0's stream
 int ring_send(fm_handle* h0, ArgRing& r, size_t slot, size_t n)
 {
-    MHK(h0, hipMemcpyAsync(static_cast<char*>(r.dev) + slot * r.elem, static_cast<const char*>(r.host) + slot * r.elem, n * r.elem,
-                           hipMemcpyHostToDevice, h0->st));
-    MHK(h0, hipEventRecord(r.copied, h0->st));
+    MHK(h0, fnn::ring_send(r, slot, n, h0->st));
     return FNN_OK;
-}
-void ring_release(ArgRing& r)
-{
-    if (r.dev) hipFree(r.dev);
-    if (r.host) hipHostFree(r.host);
-    if (r.copied) hipEventDestroy(r.copied);
-    r.dev = r.host = nullptr; r.copied = nullptr; r.cur = 0;
 }
 
 // A call on a list of handles: what every such call refuses before any launch, and the streams.  A refusal's message goes to

@@ -20,6 +20,7 @@
 #include "../../include/fnn_hip.h"
 #include "fnn_step_kernels.hip.h"
 #include "metrics.hip.h"
+#include "arg_ring.h"
 
 using namespace fnn;
 
@@ -55,6 +56,8 @@ template <typename... A> struct FnnKernel { void (*fn)(A...) = nullptr; int thre
 template <typename T> using Step1Kernel = FnnKernel<MlpArgs<T>>;
 using Step2Kernel = FnnKernel<SortArgs, WgradArgs, int, int, ScatArgs>;
 using Step3Kernel = FnnKernel<SortArgs, TailArgs, ScatArgs>;
+template <typename T> using GroupKernel = FnnKernel<const GroupArg<T>*>;      // the launches of fnn_train_step_multi
+static_assert(sizeof(GroupArg<float>) == sizeof(GroupArg<bf16_t>) && sizeof(GroupArg<float>) == sizeof(GroupArg<bs16_t>), "one argument ring serves every element type");
 
 // What the configuration and the knobs decide of every call on a handle: made once, by make_plan and plan_step1 in fnn_create.  The
 // half that hangs on the width of the sort keys is plan_keys', which fnn_set_table calls again.  What a call adds is its batch
@@ -144,6 +147,10 @@ struct fnn_handle : FnnPlan {
     unsigned long long p2p_timeout_ticks = 3000000000ull;      // 30 s of the 100 MHz clock ($FNN_P2P_TIMEOUT_MS)
     unsigned long long* p2p_wait_max = nullptr;                // device word: the longest flag wait so far (diagnostic)
     int step_bsize = 0;                 // its b_size (the decay table is rebuilt with it when a global batch outgrows the table)
+    // fnn_train_step_multi, used when this handle is hs[0]: the argument ring (four calls of the largest group), the event that
+    // joins the other members' streams to this one's and back, the packed {loss, range flag} of a call that asks for the losses
+    ArgRing step_ring{sizeof(GroupArg<float>), 4 * FNN_STEP_MAX_MODELS};
+    hipEvent_t join = nullptr; GroupPack* step_pack = nullptr;
     // profiling
     bool prof = false;
     std::map<std::string, ProfSlot> prof_slots;
@@ -335,6 +342,35 @@ template <typename T> Step3Kernel step3_sel(bool key64, bool m4, bool update)
     return key64 ? STEP3(unsigned long long, sort_lds_bytes<unsigned long long>()) : STEP3(unsigned, sort_lds_bytes<unsigned>());
 #undef STEP3
 }
+// ---- the group kernels of fnn_train_step_multi: the training forms on FM rows that step1_sel(train = true), step2_sel and
+// step3_sel(update = true) can return, chosen by the same conditions; the only places that name an instantiation of k_gstep*
+template <typename T> GroupKernel<T> gstep1_sel(const FnnPlan& p, const FnnKnobs& kn)
+{
+#define GSTEP1(C1, C2, NW, WTF) GroupKernel<T>{k_gstep1<T, C1, C2, 4, NW, WTF>, 64 * NW, mlp_lds_bytes<T, C1, C2, 4>(false, p.F, NW)}
+    const bool big = p.H1p / 64 == 5;
+    if (big && kn.step1_waves == 8) {
+        if constexpr (std::is_same<T, bf16_t>::value)
+            if (kn.step1_fixed && kn.wt_stores == 47 && ((8 * p.F + 15) >> 4) * 32 <= 512) return GSTEP1(5, 2, 8, 47);
+        return GSTEP1(5, 2, 8, -1);
+    }
+    return big ? GSTEP1(5, 2, 4, -1) : GSTEP1(1, 1, 4, -1);
+#undef GSTEP1
+}
+template <typename T> GroupKernel<T> gstep2_sel(bool key64, bool m4, bool wgrad_lds)
+{
+#define GSTEP2(WF) (key64 ? (m4 ? GroupKernel<T>{k_gstep2<T, unsigned long long, true, WF>, 256, lds} : GroupKernel<T>{k_gstep2<T, unsigned long long, false, WF>, 256, lds}) \
+                          : (m4 ? GroupKernel<T>{k_gstep2<T, unsigned, true, WF>, 256, lds} : GroupKernel<T>{k_gstep2<T, unsigned, false, WF>, 256, lds}))
+    const size_t lds = key64 ? sortA_lds_bytes<unsigned long long>(m4) : sortA_lds_bytes<unsigned>(m4);
+    if constexpr (sizeof(T) == 2) if (wgrad_lds) return GSTEP2(WGRAD_LDS);
+    return GSTEP2(WGRAD_DIRECT);
+#undef GSTEP2
+}
+template <typename T> GroupKernel<T> gstep3_sel(bool key64, bool m4)
+{
+#define GSTEP3(KT) (m4 ? GroupKernel<T>{k_gstep3<T, KT, true>, 256, sort_lds_bytes<KT>()} : GroupKernel<T>{k_gstep3<T, KT, false>, 256, sort_lds_bytes<KT>()})
+    return key64 ? GSTEP3(unsigned long long) : GSTEP3(unsigned);
+#undef GSTEP3
+}
 // the plan's kernels: launch 1 for prediction and training, made at create ...
 template <typename T> void plan_step1(fnn_handle* h)
 {
@@ -405,25 +441,35 @@ template <typename T> void launch_step2(fnn_handle* h, const StepRoles& r)
     hipLaunchKernelGGL(k.fn, grid, dim3(k.threads), std::max(k.lds, wl ? WGRAD_LDS_BYTES : (size_t)0), h->st, a.so, wa, nwx, h->splitk, a.sa);
 }
 
+// the dense role of launch 3: its arguments and (nblk_red) its workgroups
+TailArgs make_tail_args(const fnn_handle* h, const StepRoles& r)
+{
+    const int nred = r.dense ? (int)((h->nw12 / 4 + 255) / 256) + (int)((h->nw - h->nw12 + h->nbag + 255) / 256) + 1 : 0;
+    return TailArgs{h->slab, h->splitk, h->nw, h->nw12, h->nslab, h->master, h->cfg.lambda1, h->cfg.reg_all,
+                    h->loss_t, h->pend_Ba, r.bucket_dst ? r.bucket_dst : h->bucket, h->loss_dev, h->cfg.lr, h->K1p, h->H1p, h->H2p,
+                    h->w1, h->w1t, h->w2, h->w2t, nred, h->bb0, h->nbag, h->off_bag};
+}
+// the sparse role's bookkeeping behind launch 3: the slots flip, nothing is left to scatter
+void sparse_role_done(fnn_handle* h, bool have_next)
+{
+    if (have_next) { h->cur ^= 1; h->sorted_ids = h->next_ids; h->sorted_B = h->next_B; }
+    else { h->sorted_ids = nullptr; h->sorted_B = 0; }
+    h->next_ids = nullptr; h->next_B = 0;
+    h->scatter_pending = false;
+}
+
 template <typename T> void launch_step3(fnn_handle* h, const StepRoles& r)
 {
     const Step23Args a = make_step23_args(h, r, true);
     {
         ProfScope ps(h, role_name(r, "step3", "step3_dense", "step3_sparse"), h->st);
-        const int nred = r.dense ? (int)((h->nw12 / 4 + 255) / 256) + (int)((h->nw - h->nw12 + h->nbag + 255) / 256) + 1 : 0;
-        TailArgs ta{h->slab, h->splitk, h->nw, h->nw12, h->nslab, h->master, h->cfg.lambda1, h->cfg.reg_all,
-                    h->loss_t, h->pend_Ba, r.bucket_dst ? r.bucket_dst : h->bucket, h->loss_dev, h->cfg.lr, h->K1p, h->H1p, h->H2p,
-                    h->w1, h->w1t, h->w2, h->w2t, nred, h->bb0, h->nbag, h->off_bag};
+        const TailArgs ta = make_tail_args(h, r);
+        const int nred = ta.nblk_red;
         const dim3 grid(a.so.nblk + nred + (r.sparse ? h->kn.scat2_wgs : 0));    // these workgroups walk the multi-chunk segments
         const Step3Kernel& k = h->step3[r.update];
         if (grid.x > 0) hipLaunchKernelGGL(k.fn, grid, dim3(k.threads), k.lds, h->st, a.so, ta, a.sa);
     }
-    if (r.sparse) {                                          // the sparse role's bookkeeping: the slots flip, nothing is left to scatter
-        if (a.have_next) { h->cur ^= 1; h->sorted_ids = h->next_ids; h->sorted_B = h->next_B; }
-        else { h->sorted_ids = nullptr; h->sorted_B = 0; }
-        h->next_ids = nullptr; h->next_B = 0;
-        h->scatter_pending = false;
-    }
+    if (r.sparse) sparse_role_done(h, a.have_next);
 }
 template <typename T> void launch_steps23(fnn_handle* h, const StepRoles& r) { launch_step2<T>(h, r); launch_step3<T>(h, r); }
 
@@ -884,6 +930,115 @@ FnnPlan make_plan(const fnn_cfg& c, const FnnKnobs& kn)
     return p;
 }
 
+// ---- fnn_train_step_multi: one step of several handles on one feed (the kernels: k_gstep1 / k_gstep2 / k_gstep3)
+// A call on a list of handles: its refusals and the streams.  A refusal's message goes to hs[0], or to the library without a
+// usable hs[0].  Everything the call launches runs on hs[0]'s stream: enter() has that stream wait for what the other members'
+// streams hold so far, leave() -- at the latest the end of the scope, so on every error path too -- has those streams wait for it.
+struct StepGroup {
+    fnn_handle* const* hs; int n; fnn_handle* h0;
+    std::vector<hipStream_t> others;               // the streams that are not hs[0]'s, each once
+    bool entered = false;
+    StepGroup(fnn_handle* const* hs_, int n_) : hs(hs_), n(n_), h0(hs_ && n_ >= 1 && n_ <= FNN_STEP_MAX_MODELS ? hs_[0] : nullptr) {}
+    ~StepGroup() { leave(); }
+    int refuse(int code, const std::string& msg) const { (h0 ? h0->err : g_create_err) = "fnn_train_step_multi: " + msg; return code; }
+    static std::string at(const std::string& what, int m) { return "model " + std::to_string(m) + ": " + what; }
+    int enter()
+    {
+        HIPCHK(h0, hipSetDevice(h0->dev));
+        for (int m = 1; m < n; ++m) if (hs[m]->st != h0->st) others.push_back(hs[m]->st);
+        std::sort(others.begin(), others.end());
+        others.erase(std::unique(others.begin(), others.end()), others.end());
+        if (!others.empty() && !h0->join) HIPCHK(h0, hipEventCreateWithFlags(&h0->join, hipEventDisableTiming));
+        entered = true;
+        for (hipStream_t o : others) {                                // hs[0]'s stream after everything enqueued on the others so far
+            HIPCHK(h0, hipEventRecord(h0->join, o));
+            HIPCHK(h0, hipStreamWaitEvent(h0->st, h0->join, 0));
+        }
+        return FNN_OK;
+    }
+    int leave()
+    {
+        if (!entered) return FNN_OK;
+        entered = false;
+        if (others.empty()) return FNN_OK;                            // whatever the other streams get from here on comes after the call
+        HIPCHK(h0, hipEventRecord(h0->join, h0->st));
+        for (hipStream_t o : others) HIPCHK(h0, hipStreamWaitEvent(o, h0->join, 0));
+        return FNN_OK;
+    }
+};
+// work of member h that enqueues on "the handle's stream", on the group's stream instead
+template <typename Fn> auto on_stream(fnn_handle* h, hipStream_t st, Fn fn)
+{
+    const hipStream_t own = h->st;
+    h->st = st;
+    auto r = fn();
+    h->st = own;
+    return r;
+}
+
+// What decides which handles one set of group launches serves: the three kernels with their block and LDS sizes, and what
+// shapes the grid -- a LAUNCH CLASS (include/fnn_hip.h).  The kernels follow from element type, padded shapes, key width, sort
+// runs, weight-gradient form and the strip kernel's knobs (gstep*_sel).
+struct LaunchClass {
+    FnnKernel<> k[3]; int prec, F, K, K1p, H1p, H2p, splitk, wl, scat_form, scat2_form, scat2_wgs, wt_stores, role_off;
+    std::vector<int> members;                      // indices into hs, in the call's order
+    bool same(const LaunchClass& o) const
+    {
+        for (int i = 0; i < 3; ++i) if (k[i].fn != o.k[i].fn || k[i].threads != o.k[i].threads || k[i].lds != o.k[i].lds) return false;
+        return prec == o.prec && F == o.F && K == o.K && K1p == o.K1p && H1p == o.H1p && H2p == o.H2p && splitk == o.splitk && wl == o.wl &&
+               scat_form == o.scat_form && scat2_form == o.scat2_form && scat2_wgs == o.scat2_wgs && wt_stores == o.wt_stores && role_off == o.role_off;
+    }
+};
+template <typename T> LaunchClass launch_class_of(const fnn_handle* h)
+{
+    const bool m4 = h->kn.sort_merge4 != 0;
+    const bool wl = !(h->kn.role_off & 2) && h->wgrad_lds && sizeof(T) == 2;       // launch_step2's choice
+    const GroupKernel<T> k1 = gstep1_sel<T>(*h, h->kn), k2 = gstep2_sel<T>(h->key64, m4, wl), k3 = gstep3_sel<T>(h->key64, m4);
+    LaunchClass c{};
+    c.k[0] = {reinterpret_cast<void (*)()>(k1.fn), k1.threads, k1.lds};
+    c.k[1] = {reinterpret_cast<void (*)()>(k2.fn), k2.threads, std::max(k2.lds, wl ? WGRAD_LDS_BYTES : (size_t)0)};
+    c.k[2] = {reinterpret_cast<void (*)()>(k3.fn), k3.threads, k3.lds};
+    c.prec = h->cfg.precision; c.F = h->F; c.K = h->K; c.K1p = h->K1p; c.H1p = h->H1p; c.H2p = h->H2p; c.splitk = h->splitk; c.wl = wl;
+    c.scat_form = h->kn.scat_form; c.scat2_form = h->kn.scat2_form; c.scat2_wgs = h->kn.scat2_wgs; c.wt_stores = h->kn.wt_stores;
+    c.role_off = h->kn.role_off;
+    return c;
+}
+// Member h's entry of the argument array: what launch_step1 / launch_step2 / launch_step3 would pass for it, with the grouping
+// class's records (`rec`: of the slot in which the class's first member holds the batch's grouping).  x2 / x3: the workgroups it needs in
+// launches 2 / 3.
+template <typename T>
+bool fill_group_arg(fnn_handle* h, const int4* rec, const int32_t* ids, const float* y, int B, const uint8_t* m1, const uint8_t* m2,
+                    float* p_out, GroupPack* pack, void* dst, int* x2, int* x3)
+{
+    GroupArg<T>& g = *static_cast<GroupArg<T>*>(dst);
+    const StepRoles r = make_roles(h, true, true, true);
+    g.ma = make_mlp_args<T>(h, ids, y, B, m1, m2, true, p_out);
+    g.nmlp = h->pend_Ba / 16;
+    Step23Args a = make_step23_args(h, r, false);
+    a.sa.rec = rec;
+    g.wa = make_wgrad_args<T>(h, h->pend_Ba);
+    g.nwx = r.dense ? wgrad_blocks(g.wa) : 0; g.splitk = h->splitk;
+    g.nsc1 = r.sparse ? scat1_blocks(a.sa, h->kn.scat_form) : 0;
+    g.so2 = a.so; g.sa = a.sa;
+    g.so3 = make_step23_args(h, r, true).so;
+    g.ta = make_tail_args(h, r);
+    g.nsc2 = r.sparse ? h->kn.scat2_wgs : 0;
+    g.pack = pack;
+    *x2 = g.so2.nblk + g.nwx * g.splitk + g.nsc1;
+    *x3 = g.so3.nblk + g.ta.nblk_red + g.nsc2;
+    return a.have_next;
+}
+template <typename T> void launch_group(const LaunchClass& c, hipStream_t st, const void* dev_args, int nmlp, int x2, int x3)
+{
+    const GroupArg<T>* d = static_cast<const GroupArg<T>*>(dev_args);
+    const unsigned M = (unsigned)c.members.size();
+    using Fn = void (*)(const GroupArg<T>*);
+    hipLaunchKernelGGL(reinterpret_cast<Fn>(c.k[0].fn), dim3(nmlp, M), dim3(c.k[0].threads), c.k[0].lds, st, d);
+    // (x a multiple of 8: every model's blocks start on the XCD a solo launch's start on, which keeps the weight-gradient deal XCD-aware)
+    if (x2 > 0) hipLaunchKernelGGL(reinterpret_cast<Fn>(c.k[1].fn), dim3(rup(x2, 8), M), dim3(c.k[1].threads), c.k[1].lds, st, d);
+    if (x3 > 0) hipLaunchKernelGGL(reinterpret_cast<Fn>(c.k[2].fn), dim3(x3, M), dim3(c.k[2].threads), c.k[2].lds, st, d);
+}
+
 }  // namespace
 
 extern "C" {
@@ -1017,6 +1172,9 @@ int fnn_destroy(fnn_handle* h)
     for (void* q : {(void*)h->table16, (void*)h->field_of_row, (void*)h->tag_first, (void*)h->slot[0].tag_shared, (void*)h->slot[1].tag_shared, (void*)h->cpow_dev,
                     (void*)h->shadow_dev, (void*)h->xg_ids_send, (void*)h->xg_ids, (void*)h->xg_gxp, h->gws}) if (q) hipFree(q);
     for (void* q : h->owned) hipFree(q);
+    ring_release(h->step_ring);
+    if (h->join) hipEventDestroy(h->join);
+    if (h->step_pack) hipFree(h->step_pack);
     for (fnn_handle::SortSlot* sl : {&h->slot[0], &h->slot[1], &h->gsl}) row_group_free(*sl);
     if (h->own_stream && h->st) hipStreamDestroy(h->st);
     delete h;
@@ -1590,6 +1748,153 @@ int fnn_train_step(fnn_handle* h, const int32_t* ids, const float* y, int B, con
 {
     RCCHK(step_impl(h, ids, y, B, mask1, mask2, b_size, p_out, gx_out, memkind, true));
     return fnn_step_end(h, loss_sum_out);
+}
+
+// One step of several handles on one feed: per launch class the three launches of run_step_fast with the model as a grid
+// dimension ("The FNN step for many models").
+int fnn_train_step_multi(fnn_handle* const* hs, int n_models, const int32_t* ids, const float* y, int B,
+                         const uint8_t* const* mask1, const uint8_t* const* mask2, int b_size,
+                         const int32_t* next_ids, int next_B, float* const* p_out, float* loss_sum_out)
+{
+    StepGroup g(hs, n_models);
+    const int M = n_models;
+    // ---- refusals: all of them before anything is launched or written
+    if (!hs) return g.refuse(FNN_ERR_ARG, "null hs");
+    if (M < 1 || M > FNN_STEP_MAX_MODELS) return g.refuse(FNN_ERR_ARG, "n_models must be in [1, " + std::to_string(FNN_STEP_MAX_MODELS) + "]");
+    for (int m = 0; m < M; ++m) if (!hs[m]) return g.refuse(FNN_ERR_ARG, g.at("null handle", m));
+    {
+        std::vector<const fnn_handle*> seen(hs, hs + M);
+        std::sort(seen.begin(), seen.end());
+        const auto dup = std::adjacent_find(seen.begin(), seen.end());
+        if (dup != seen.end()) {
+            int m = M - 1;
+            while (hs[m] != *dup) --m;                                // the later of the two places
+            return g.refuse(FNN_ERR_ARG, g.at("the same handle twice in one call (two updates would race on one model)", m));
+        }
+    }
+    fnn_handle* h0 = g.h0;
+    for (int m = 1; m < M; ++m)
+        if (hs[m]->F != h0->F || hs[m]->dev != h0->dev) return g.refuse(FNN_ERR_ARG, g.at("n_fields or device differs from model 0's", m));
+    if (!ids || !y || !mask1 || !mask2) return g.refuse(FNN_ERR_ARG, "null ids, y, mask1 or mask2");
+    for (int m = 0; m < M; ++m) if (!mask1[m] || !mask2[m]) return g.refuse(FNN_ERR_ARG, g.at("null mask1 or mask2", m));
+    if (B < 1 || B > SORT_N) return g.refuse(FNN_ERR_ARG, "B must be in [1, 4096]");
+    for (int m = 0; m < M; ++m) if (B > hs[m]->Bmax) return g.refuse(FNN_ERR_ARG, g.at("B must be in [1, max_batch]", m));
+    if (next_ids && (next_B < 1 || next_B > SORT_N)) return g.refuse(FNN_ERR_ARG, "next_B must be in [1, 4096]");
+    for (int m = 0; m < M; ++m) {
+        const fnn_handle* h = hs[m];
+        if (next_ids && next_B > h->Bmax) return g.refuse(FNN_ERR_ARG, g.at("next_B must be in [1, max_batch]", m));
+        if (h->bag) return g.refuse(FNN_ERR_ARG, g.at("FNN_MODE_BAG handles take fnn_train_step, one at a time", m));
+        if (h->wide) return g.refuse(FNN_ERR_ARG, g.at("wide rows (k >= 17) take fnn_train_step, one at a time", m));
+        if (!h->strip_ok) return g.refuse(FNN_ERR_ARG, g.at("the handle does not run the strip kernel (hidden sizes it is not built for, or FNN_NO_FUSE=1)", m));
+        if (h->n_shadow > 0) return g.refuse(FNN_ERR_ARG, g.at("shadowed features pending (fnn_set_shadowed): such a batch takes fnn_train_step", m));
+        if (h->dp) return g.refuse(FNN_ERR_ARG, g.at("a data-parallel handle (fnn_dp_init) takes fnn_train_step", m));
+    }
+    for (int m = 0; m < M; ++m) {
+        const fnn_handle* h = hs[m];
+        if (!h->table16) return g.refuse(FNN_ERR_STATE, g.at("fnn_set_table has not been called", m));
+        if (!(h->dense_set[0] && h->dense_set[1] && h->dense_set[2])) return g.refuse(FNN_ERR_STATE, g.at("fnn_set_dense has not been called for all three layers", m));
+        if (h->in_step) return g.refuse(FNN_ERR_STATE, g.at("inside fnn_step_begin / fnn_step_end", m));
+    }
+    if (b_size <= 0) b_size = B;
+    if (M == 1) {              // nothing to share: the solo step itself, without the argument copy
+        if (next_ids) RCCHK(fnn_prefetch_ids(h0, next_ids, next_B));
+        const int rs = fnn_train_step(h0, ids, y, B, mask1[0], mask2[0], b_size, p_out ? p_out[0] : nullptr, nullptr, FNN_MEM_DEVICE, loss_sum_out);
+        if (rs == FNN_ERR_RANGE) g.refuse(rs, "feature id outside [-1, n_rows) in model(s) 0");
+        return rs;
+    }
+
+    RCCHK(g.enter());
+    const hipStream_t st = h0->st;
+    // per-model preparation that copies to the device, inside the scope: the decay table when lr, lambda_fm or b_size changed
+    for (int m = 0; m < M; ++m) {
+        fnn_handle* h = hs[m];
+        const int rc = on_stream(h, st, [&] { return update_cpow(h, b_size, B); });
+        if (rc != FNN_OK) { if (h != h0) g.refuse(rc, g.at(h->err, m)); return rc; }
+    }
+    // launch classes, in the order of their first members
+    std::vector<LaunchClass> cls;
+    for (int m = 0; m < M; ++m) {
+        LaunchClass c = BY_PREC_RC(hs[m], launch_class_of, (hs[m]));
+        size_t i = 0;
+        while (i < cls.size() && !cls[i].same(c)) ++i;
+        if (i == cls.size()) cls.push_back(c);
+        cls[i].members.push_back(m);
+    }
+    size_t slot = 0;
+    HIPCHK(h0, ring_take(h0->step_ring, (size_t)M, &slot));
+    char* a = static_cast<char*>(h0->step_ring.host) + slot * h0->step_ring.elem;
+    const char* d = static_cast<const char*>(h0->step_ring.dev) + slot * h0->step_ring.elem;
+    if (loss_sum_out && !h0->step_pack) HIPCHK(h0, hipMalloc((void**)&h0->step_pack, FNN_STEP_MAX_MODELS * sizeof(GroupPack)));
+    GroupPack* pack = loss_sum_out ? h0->step_pack : nullptr;
+
+    struct Launch { const void* dev; int nmlp, x2, x3; };
+    std::vector<Launch> launches;
+    std::vector<char> have_next(M, 0);                                // per member: the next batch's grouping rides in its sort roles
+    size_t pos = 0;
+    for (LaunchClass& c : cls) {
+        // grouping classes: the members of equal n_rows share the grouping of the first of them
+        std::vector<fnn_handle*> lead(c.members.size());
+        std::vector<const int4*> rec(c.members.size());
+        for (size_t i = 0; i < c.members.size(); ++i) {
+            size_t j = 0;
+            while (hs[c.members[j]]->n_rows != hs[c.members[i]]->n_rows) ++j;
+            lead[i] = hs[c.members[j]];
+            rec[i] = lead[i]->slot[lead[i]->cur].rec;
+        }
+        Launch L{d + pos * h0->step_ring.elem, 0, 0, 0};
+        for (size_t i = 0; i < c.members.size(); ++i) {
+            const int m = c.members[i];
+            fnn_handle* h = hs[m];
+            h->pend_Ba = rup(B, 256);
+            h->update_pending = false; h->step_native_dp = false; h->step_bsize = b_size; h->step_B = B;
+            if (h == lead[i]) {
+                // grouping of THIS batch: done by the previous call (next_ids) or right now, as in run_step_fast
+                if (!(h->sorted_ids == ids && h->sorted_B == B)) {
+                    h->prefetch_misses++;
+                    fnn_handle::SortSlot& sl = h->slot[h->cur];
+                    on_stream(h, st, [&] { launch_sort16(h, SortArgs{ids, B, h->F, h->n_rows, sl.rec, sl.owner_cnt, h->F, h->skeys, h->tag_first, sl.tag_shared, 0}); return 0; });
+                    h->sorted_ids = ids; h->sorted_B = B;             // what the slot holds from here on, whatever becomes of the call
+                } else h->prefetch_hits++;
+                if (next_ids) { h->next_ids = next_ids; h->next_B = next_B; }
+                h->pend_have_next = h->next_ids != nullptr && !(h->next_ids == ids && h->next_B == B);
+            } else {
+                h->next_ids = nullptr; h->next_B = 0; h->pend_have_next = false;
+            }
+            int x2 = 0, x3 = 0;
+            have_next[m] = BY_PREC_RC(h, fill_group_arg, (h, rec[i], ids, y, B, mask1[m], mask2[m], p_out ? p_out[m] : nullptr,
+                                                                 pack ? pack + m : nullptr, a + (pos + i) * h0->step_ring.elem, &x2, &x3));
+            L.nmlp = h->pend_Ba / 16; L.x2 = std::max(L.x2, x2); L.x3 = std::max(L.x3, x3);
+        }
+        launches.push_back(L);
+        pos += c.members.size();
+    }
+    HIPCHK(h0, hipGetLastError());
+    HIPCHK(h0, ring_send(h0->step_ring, slot, (size_t)M, st));
+    for (size_t i = 0; i < cls.size(); ++i) {
+        const Launch& L = launches[i];
+        BY_PREC(hs[cls[i].members[0]], launch_group, (cls[i], st, L.dev, L.nmlp, L.x2, L.x3));
+    }
+    HIPCHK(h0, hipGetLastError());
+    // the step is enqueued: only now the members' bookkeeping says so (the first members' slots flip, the others keep no grouping)
+    for (int m = 0; m < M; ++m) sparse_role_done(hs[m], have_next[m] != 0);
+    RCCHK(g.leave());
+    if (!loss_sum_out) return FNN_OK;
+    std::vector<GroupPack> hp(M);
+    HIPCHK(h0, hipMemcpyAsync(hp.data(), pack, (size_t)M * sizeof(GroupPack), hipMemcpyDeviceToHost, st));
+    HIPCHK(h0, hipStreamSynchronize(st));
+    std::string bad;
+    for (int m = 0; m < M; ++m) {
+        loss_sum_out[m] = hp[m].loss;
+        if (hp[m].flag) {
+            bad += (bad.empty() ? "" : ", ") + std::to_string(m);
+            HIPCHK(h0, hipMemsetAsync(hs[m]->err_flag, 0, sizeof(int), st));
+        }
+    }
+    if (!bad.empty()) {
+        HIPCHK(h0, hipStreamSynchronize(st));
+        return g.refuse(FNN_ERR_RANGE, "feature id outside [-1, n_rows) in model(s) " + bad);
+    }
+    return FNN_OK;
 }
 
 int fnn_predict(fnn_handle* h, const int32_t* ids, int B, float* p_out, int memkind)

@@ -31,6 +31,30 @@ static __global__ __launch_bounds__(64 * NW) void k_step1(const MlpArgs<T> a)
 // ------------------------------------------------------------------------------------------
 // step 2: run-sorts of the NEXT batch's keys  U  weight gradients  U  sparse-row SGD level 1
 // ------------------------------------------------------------------------------------------
+// The weight-gradient role of launch 2: block w of the role's nw = nwx * splitk workgroups -> its (tile, K slice).
+// XCD-aware order: hardware block ids that differ by a multiple of 8 share an XCD (and its L2); deal the role's blocks so
+// that each of the 8 classes owns a contiguous run of (tile, K slice) pairs -- one or two K slices of the operands per XCD
+// instead of a little of every slice.  `aligned`: the role starts at a hardware block id that is a multiple of 8 (placement
+// only: any deal computes the same slabs).
+template <typename T, int WF>
+__device__ __forceinline__ void wgrad_role(const WgradArgs& wa, const int nwx, int w, const int nw, const bool aligned, unsigned char* smem)
+{
+    if (aligned) {
+        const int cls = w & 7, k = w >> 3, qd = nw >> 3, rm = nw & 7;
+        w = (cls < rm ? cls * (qd + 1) : rm * (qd + 1) + (cls - rm) * qd) + k;
+    }
+    wgrad_body<T, WF>(wa, w % nwx, w / nwx, smem);
+}
+// level 1 of the sparse-row update in the form the arguments name (scat1_blocks; wide and bag rows: scatw1_body).  The group
+// kernel's; k_step2 keeps the same chain written out, which keeps its code what it was to the byte (as k_step3 does for level 2).
+__device__ __forceinline__ void scat1_role(const ScatArgs& sa, const int blk)
+{
+    if (sa.rw != SLOT) scatw1_body(sa, blk);
+    else if (sa.form == SCAT1_SLOT) scat1_body(sa, blk);       // FNN_SCAT1_FORM=slot
+    else if (sa.form == SCAT1_HALF) scat1h_body(sa, blk);      // FNN_SCAT1_FORM=half
+    else scat1q_body(sa, blk);
+}
+
 // WF: the form of the weight-gradient role (WGRAD_LDS: WGRAD_LDS_BYTES of dynamic LDS for the whole launch; bf16 only)
 template <typename T, typename KT, bool M4, int WF = WGRAD_DIRECT>
 static __global__ __launch_bounds__(256) void k_step2(const SortArgs so, const WgradArgs wa, const int nwx,
@@ -40,15 +64,8 @@ static __global__ __launch_bounds__(256) void k_step2(const SortArgs so, const W
     const int b = blockIdx.x, nw = nwx * splitk;
     if (b < so.nblk) sortA_form<KT, M4>(so, b, smem);                          // so.nblk = 4 * F or 0
     else if (b < so.nblk + nw) {
-        // XCD-aware order: hardware block ids that differ by a multiple of 8 share an XCD (and its L2); deal the role's blocks so
-        // that each of the 8 classes owns a contiguous run of (tile, K slice) pairs -- one or two K slices of the operands per XCD
-        // instead of a little of every slice
-        int w = b - so.nblk;
-        if (((b ^ w) & 7) == 0) {                              // the role starts at a multiple of 8
-            const int cls = w & 7, k = w >> 3, qd = nw >> 3, rm = nw & 7;
-            w = (cls < rm ? cls * (qd + 1) : rm * (qd + 1) + (cls - rm) * qd) + k;
-        }
-        wgrad_body<T, WF>(wa, w % nwx, w / nwx, smem);
+        const int w = b - so.nblk;
+        wgrad_role<T, WF>(wa, nwx, w, nw, ((b ^ w) & 7) == 0, smem);
     }
     // (the scatter role's blocks dealt BEFORE the weight gradients', so that their chain starts while those are still being
     // placed, measured level: 39.06 / 38.53 / 39.01 us per step against 38.45 / 39.17 / 39.03 behind them; with the 96 blocks
@@ -71,22 +88,11 @@ struct TailArgs {
     float* bb0; size_t nbag, off_bag;      // bag mode: bias vector, its length (K1p) and slab offset
 };
 
-template <typename T, bool UPDATE, typename KT, bool M4>
-static __global__ __launch_bounds__(256) void k_step3(const SortArgs so, const TailArgs ta, const ScatArgs sa)
+// The dense role of launch 3: block b of the role's ta.nblk_red workgroups.  The last one sums the loss (fixed-shape tree); the
+// others reduce the split-K slabs into the bucket and, UPDATE, apply the step with the L2 term and refresh the shadows.
+template <typename T, bool UPDATE>
+__device__ __forceinline__ void dense_body(const TailArgs& ta, const int b, double (&s_sum)[16][16])
 {
-    extern __shared__ __align__(16) unsigned char smem[];
-    __shared__ double s_sum[16][16];
-    if ((int)blockIdx.x < so.nblk) { sortB_form<KT, M4>(so, blockIdx.x, smem); return; }      // rank merge: 16 F or 0 WGs
-    const int b = (int)blockIdx.x - so.nblk;
-    if (b >= ta.nblk_red) {
-        const int nb = (int)gridDim.x - so.nblk - ta.nblk_red;
-        if (sa.rw == SLOT) {
-            if (sa.form2 == SCAT2_WAVE) scat2w_body(sa, b - ta.nblk_red, nb);      // FNN_SCAT2_FORM=wave
-            else scat2_body(sa, b - ta.nblk_red, nb, s_sum);
-        }
-        else scatw2_body(sa, b - ta.nblk_red, nb, reinterpret_cast<double*>(smem));
-        return;
-    }
     if (b == ta.nblk_red - 1) {                                // loss: fixed-shape tree
         float* s_l = reinterpret_cast<float*>(&s_sum[0][0]);
         float v = 0.f;
@@ -155,6 +161,102 @@ static __global__ __launch_bounds__(256) void k_step3(const SortArgs so, const T
         g += 2.0f * ta.lambda1 * w;                              // w3, b3 are always regularised (:173)
         ta.master[i] = w - ta.lr * g;
     }
+}
+// level 2 of the sparse-row update: block `blk` of the role's nb workgroups
+__device__ __forceinline__ void scat2_role(const ScatArgs& sa, const int blk, const int nb, double (*s_sum)[16], unsigned char* smem)
+{
+    if (sa.rw == SLOT) {
+        if (sa.form2 == SCAT2_WAVE) scat2w_body(sa, blk, nb);      // FNN_SCAT2_FORM=wave
+        else scat2_body(sa, blk, nb, s_sum);
+    }
+    else scatw2_body(sa, blk, nb, reinterpret_cast<double*>(smem));
+}
+
+template <typename T, bool UPDATE, typename KT, bool M4>
+static __global__ __launch_bounds__(256) void k_step3(const SortArgs so, const TailArgs ta, const ScatArgs sa)
+{
+    extern __shared__ __align__(16) unsigned char smem[];
+    __shared__ double s_sum[16][16];
+    if ((int)blockIdx.x < so.nblk) { sortB_form<KT, M4>(so, blockIdx.x, smem); return; }      // rank merge: 16 F or 0 WGs
+    const int b = (int)blockIdx.x - so.nblk;
+    if (b >= ta.nblk_red) {
+        const int nb = (int)gridDim.x - so.nblk - ta.nblk_red;
+        if (sa.rw == SLOT) {
+            if (sa.form2 == SCAT2_WAVE) scat2w_body(sa, b - ta.nblk_red, nb);      // FNN_SCAT2_FORM=wave
+            else scat2_body(sa, b - ta.nblk_red, nb, s_sum);
+        }
+        else scatw2_body(sa, b - ta.nblk_red, nb, reinterpret_cast<double*>(smem));
+        return;
+    }
+    dense_body<T, UPDATE>(ta, b, s_sum);
+}
+
+// ------------------------------------------------------------------------------------------
+// One step of several models on one feed (fnn_train_step_multi): the three launches with the model as blockIdx.y, the
+// arguments of model y read from a device array, the SAME bodies on them as the solo kernels run.  The models of one launch
+// agree in the kernel and its launch shape (a launch class); a model whose role counts are smaller than the grid's returns.
+// Only the first member of a grouping class carries sort-role blocks (so2 / so3: nblk = 0 on the others), every member's
+// ScatArgs reads that member's rec.
+// ------------------------------------------------------------------------------------------
+struct GroupPack { float loss; int flag; };
+template <typename T> struct GroupArg {
+    MlpArgs<T> ma; int nmlp;                   // launch 1: the strips
+    SortArgs so2, so3;                         // launches 2 / 3: run sorts and rank merges of the NEXT batch (first member only)
+    WgradArgs wa; int nwx, splitk, nsc1;       // launch 2: tiles, K slices, level-1 workgroups
+    ScatArgs sa;
+    TailArgs ta; int nsc2;                     // launch 3: the dense role (ta.nblk_red workgroups), level-2 workgroups
+    GroupPack* pack;                           // the call's loss and range flag of this model for one copy to the host (null: not asked)
+};
+
+// (a member's owner count is cleared here, before level 1 counts into it: the rank merge clears only the slot it fills)
+template <typename T, int C1, int C2, int CX, int NW, int WTF>
+static __global__ __launch_bounds__(64 * NW) void k_gstep1(const GroupArg<T>* __restrict__ args)
+{
+    extern __shared__ __align__(16) unsigned char smem[];
+    const GroupArg<T>& g = args[blockIdx.y];
+    const MlpArgs<T> a = g.ma;
+    const int nmlp = g.nmlp;
+    int* const owner_cnt = g.sa.owner_cnt;
+    if ((int)blockIdx.x >= nmlp) return;
+    if (blockIdx.x == 0 && threadIdx.x == 0) *owner_cnt = 0;
+    mlp_body<T, C1, C2, CX, false, NW, WTF>(a, blockIdx.x, smem);
+}
+
+// (the grid's x extent is a multiple of 8, so that a model's blocks start on the XCD the solo launch's start on and the
+// weight-gradient deal stays XCD-aware)
+template <typename T, typename KT, bool M4, int WF>
+static __global__ __launch_bounds__(256) void k_gstep2(const GroupArg<T>* __restrict__ args)
+{
+    extern __shared__ __align__(16) unsigned char smem[];
+    const GroupArg<T>& g = args[blockIdx.y];
+    const int b = blockIdx.x, nsort = g.so2.nblk, nwx = g.nwx, nw = nwx * g.splitk, nsc = g.nsc1;
+    if (b < nsort) { const SortArgs so = g.so2; sortA_form<KT, M4>(so, b, smem); }
+    else if (b < nsort + nw) {
+        const WgradArgs wa = g.wa;
+        const int w = b - nsort;
+        wgrad_role<T, WF>(wa, nwx, w, nw, ((b ^ w) & 7) == 0, smem);
+    }
+    else if (b < nsort + nw + nsc) { const ScatArgs sa = g.sa; scat1_role(sa, b - nsort - nw); }
+}
+
+template <typename T, typename KT, bool M4>
+static __global__ __launch_bounds__(256) void k_gstep3(const GroupArg<T>* __restrict__ args)
+{
+    extern __shared__ __align__(16) unsigned char smem[];
+    __shared__ double s_sum[16][16];
+    const GroupArg<T>& g = args[blockIdx.y];
+    const int nsort = g.so3.nblk, nred = g.ta.nblk_red, nsc = g.nsc2;
+    if ((int)blockIdx.x < nsort) { const SortArgs so = g.so3; sortB_form<KT, M4>(so, blockIdx.x, smem); return; }
+    const int b = (int)blockIdx.x - nsort;
+    if (b >= nred) {
+        if (b - nred < nsc) { const ScatArgs sa = g.sa; scat2_role(sa, b - nred, nsc, s_sum, smem); }
+        return;
+    }
+    const TailArgs ta = g.ta;
+    GroupPack* const pack = g.pack;
+    int* const err = g.ma.err;
+    dense_body<T, true>(ta, b, s_sum);
+    if (pack && b == nred - 1 && threadIdx.x == 0) { pack->loss = *ta.loss_sum; pack->flag = *err; }
 }
 
 // ------------------------------------------------------------------------------------------

@@ -30,7 +30,7 @@ class FNNEngine(object):
 
     def __init__(self, n_fields=16, k=11, hidden1=300, hidden2=100, max_batch=4096, precision='bf16',
                  acti_type='tanh', lr=0.001, lambda1=0.0, lambda_fm=0.1, reg_all=False, device=0,
-                 mode='fm', hidden0=0):
+                 mode='fm', hidden0=0, stream=None):
         import torch
         if not torch.cuda.is_available():
             raise FNNError(_capi.FNN_ERR_HIP, "no HIP device visible to PyTorch-ROCm; the FNN hot path has "
@@ -38,7 +38,7 @@ class FNNEngine(object):
         self._torch = torch
         self.lib = _capi.load()
         self.device = torch.device('cuda', device)
-        self.stream = torch.cuda.Stream(device=self.device)
+        self.stream = stream if stream is not None else torch.cuda.Stream(device=self.device)     # stream: a torch stream to share
         self.F, self.K, self.H1, self.H2 = n_fields, k, hidden1, hidden2
         self.xdim = 1 + n_fields * k
         self.bag = mode == 'bag'               # SNN fine-tune input layer (python/SNN_RBM.py:238-291)
@@ -432,6 +432,105 @@ class FNNEngine(object):
         ms, n = C.c_double(), C.c_int64()
         self._ck(self.lib.fnn_prof_get(self.h, which.encode(), C.byref(ms), C.byref(n)))
         return ms.value, n.value
+
+
+def _group_call(engines, *args):
+    """fnn_train_step_multi on the engines' handles: every engine's stream joins the caller's, the refusal is engines[0]'s."""
+    lib = engines[0].lib
+    hs = (C.c_void_p * len(engines))(*[e.h.value for e in engines])
+    rc = lib.fnn_train_step_multi(hs, len(engines), *args)
+    if rc != 0:
+        raise FNNError(rc, (lib.fnn_last_error(engines[0].h) or b'').decode())
+
+
+def train_step_many(engines, ids, y, masks1, masks2, b_size=0, next_ids=None, want_p=False, want_loss=True):
+    """One train_step of every engine of a list on ONE feed, in one call (fnn_train_step_multi): engine m ends bit for bit as
+    engines[m].train_step(ids, y, masks1[m], masks2[m], b_size) alone would have left it.  next_ids: the device int32 tensor
+    of the NEXT call's ids (grouped during this one; a scheduling hint).  Returns a list of dicts shaped like train_step's:
+    'loss' (float), 'p' [B]."""
+    e0 = engines[0]
+    torch = e0._torch
+    M = len(engines)
+    assert len(masks1) == M and len(masks2) == M
+    ids_t, y_t = e0._dev(ids, torch.int32), e0._dev(y, torch.float32)
+    B = ids_t.shape[0]
+    m1 = [e._dev(m, torch.uint8) for e, m in zip(engines, masks1)]
+    m2 = [e._dev(m, torch.uint8) for e, m in zip(engines, masks2)]
+    assert y_t.numel() == B and all(a.numel() == e.H1 and b.numel() == e.H2 for e, a, b in zip(engines, m1, m2))
+    ps = [torch.empty(B, dtype=torch.float32, device=e0.device) for _ in engines] if want_p else None
+    nxt, nB = None, 0
+    if next_ids is not None:
+        assert next_ids.is_cuda and next_ids.dtype == torch.int32 and next_ids.is_contiguous()
+        nxt, nB = next_ids.data_ptr(), next_ids.shape[0]
+    loss = (C.c_float * M)()
+    for e in engines:
+        e._enter()
+    _group_call(engines, ids_t.data_ptr(), y_t.data_ptr(), B, (C.c_void_p * M)(*[t.data_ptr() for t in m1]),
+                (C.c_void_p * M)(*[t.data_ptr() for t in m2]), int(b_size), nxt, nB,
+                (C.c_void_p * M)(*[t.data_ptr() for t in ps]) if want_p else None, loss if want_loss else None)
+    for e in engines:
+        e._leave()
+    e0._keep_many = (ids_t, y_t, m1, m2, next_ids)
+    outs = []
+    for m in range(M):
+        o = {}
+        if want_loss:
+            o['loss'] = float(loss[m])
+        if want_p:
+            o['p'] = ps[m]
+        outs.append(o)
+    return outs
+
+
+def train_epoch_many(engines, ids_d, yf_d, batch_size, masks1, masks2, first=0, n_steps=None, shadowed=None):
+    """FNNEngine.train_epoch's loop for a list of engines on one resident feed: masks1[m] [n, H1 of m] / masks2[m] [n, H2 of m]
+    are engine m's dropout rows, every batch is ONE fnn_train_step_multi call with the next batch announced through next_ids.
+    A batch with shadowed features (or longer than 4096) runs as solo steps of every engine, fnn_set_shadowed + fnn_train_step,
+    which the group call refuses: every engine's trajectory is that of its own train_epoch."""
+    e0 = engines[0]
+    torch = e0._torch
+    M = len(engines)
+    assert ids_d.is_cuda and ids_d.dtype == torch.int32 and ids_d.is_contiguous() and yf_d.is_cuda and yf_d.dtype == torch.float32
+    N = ids_d.shape[0]
+    n_all = (N + batch_size - 1) // batch_size
+    n_steps = n_all - first if n_steps is None else n_steps
+    m1 = [e._dev(m, torch.uint8) for e, m in zip(engines, masks1)]
+    m2 = [e._dev(m, torch.uint8) for e, m in zip(engines, masks2)]
+    for e, a, b in zip(engines, m1, m2):
+        assert a.shape == (a.shape[0], e.H1) and b.shape == (b.shape[0], e.H2) and min(a.shape[0], b.shape[0]) >= first + n_steps
+    lib, F = e0.lib, e0.F
+    ip, yp = ids_d.data_ptr(), yf_d.data_ptr()
+    p1, p2 = [t.data_ptr() for t in m1], [t.data_ptr() for t in m2]
+    sh = None if shadowed is None or len(shadowed) == 0 else np.ascontiguousarray(shadowed, dtype=np.int32)
+    a1, a2 = (C.c_void_p * M)(), (C.c_void_p * M)()
+    for e in engines:
+        e._enter()
+    for j in range(first, first + n_steps):
+        lo = j * batch_size
+        B = min(batch_size, N - lo)
+        if B <= 0:
+            break
+        nlo = lo + batch_size
+        nB = min(batch_size, N - nlo) if j + 1 < first + n_steps and nlo < N and B <= 4096 else 0
+        part = None
+        if sh is not None:
+            a, b = np.searchsorted(sh[:, 0], [lo, lo + B])
+            if b > a:
+                part = sh[a:b].copy()
+                part[:, 0] -= lo
+        if part is not None or B > 4096:
+            for m, e in enumerate(engines):
+                if part is not None:
+                    e._ck(lib.fnn_set_shadowed(e.h, part.ctypes.data, len(part), _capi.FNN_MEM_HOST))
+                e._ck(lib.fnn_train_step(e.h, ip + lo * F * 4, yp + lo * 4, B, p1[m] + j * e.H1, p2[m] + j * e.H2, B, None, None,
+                                         _capi.FNN_MEM_DEVICE, None))
+            continue
+        for m, e in enumerate(engines):
+            a1[m], a2[m] = p1[m] + j * e.H1, p2[m] + j * e.H2
+        _group_call(engines, ip + lo * F * 4, yp + lo * 4, B, a1, a2, B, (ip + nlo * F * 4) if nB else None, nB, None, None)
+    for e in engines:
+        e._leave()
+    e0._keep_many = (ids_d, yf_d, m1, m2)
 
 
 def _tensor_from_ptr(torch, ptr, n, device, kind='f4'):

@@ -175,6 +175,47 @@ int fnn_set_shadowed(fnn_handle* h, const int32_t* tfr, int n, int memkind);
  * this call and the step that consumes them. */
 int fnn_prefetch_ids(fnn_handle* h, const int32_t* ids, int B);
 
+/* One fnn_train_step of each of n_models handles on ONE device feed (a hyper-parameter search, one model per setting).
+ * ids [B, F], y [B] and next_ids [next_B, F] are DEVICE pointers; hs, mask1, mask2 and p_out are HOST arrays of n_models
+ * entries: mask1[m] uint8 [H1 of model m] and mask2[m] uint8 [H2 of model m] on the device, p_out[m] [B] on the device (the
+ * array or any entry may be NULL).  loss_sum_out: HOST array [n_models] or NULL; non-NULL synchronises once for the whole call.
+ * Device pointers only (no memkind), no gx_out.
+ *
+ * Model m ends BIT FOR BIT as fnn_train_step(hs[m], ids, y, B, mask1[m], mask2[m], b_size, p_out[m], NULL, FNN_MEM_DEVICE, &loss)
+ * alone would have left it: table, the six dense tensors and their shadows, p_out[m], the loss, the range flag.  The same device
+ * bodies run on the same records, and FM-mode steps use no float atomics.  Group steps, solo steps, fnn_predict and fnn_eval may
+ * be interleaved on the same handles in any order.  The models may differ in hyper-parameters, masks, state, precision, hidden
+ * sizes, act, reg_all, max_batch and n_rows; they share n_fields and the device.
+ *
+ * Accepted: handles whose step is the plain three-launch step -- FNN_MODE_FM, k <= 15, hidden sizes the strip kernel is built
+ * for, B <= 4096.  The handles that the same three kernels and launch shape serve (element type, padded shapes, split-K,
+ * weight-gradient form, key width, sort runs, scatter forms, store policy) form a LAUNCH CLASS: each of the three launches is
+ * issued once per class, the model a grid dimension, its arguments read from a device array.  Inside a launch class the handles
+ * of equal n_rows share ONE grouping of the batch (run sort and rank merge), kept by the first of them with its usual
+ * bookkeeping; on the others a pending fnn_prefetch_ids request and any carried grouping are cleared.
+ *
+ * next_ids / next_B (NULL / 0: none): the group's fnn_prefetch_ids -- the grouping of the NEXT batch rides in launches 2 and 3,
+ * and the next call (same ids pointer, same B, same first members) issues three launches per launch class.  Otherwise the call
+ * sorts first.  A scheduling hint only.  n_models == 1 forwards to fnn_train_step (after fnn_prefetch_ids when next_ids is given).
+ *
+ * Streams: everything runs on hs[0]'s stream, which first waits for what is queued on every other member's stream; every other
+ * member's stream then waits for the call's last launch.
+ *
+ * A refused call launches nothing and writes nothing, loss_sum_out included; its message starts with "fnn_train_step_multi:",
+ * names the offending model's index and is left with fnn_last_error(hs[0]) (fnn_last_error(NULL) without a usable hs[0]).
+ * FNN_ERR_ARG: null hs / ids / y / mask1 / mask2 or a null entry of hs / mask1 / mask2; n_models outside 1..FNN_STEP_MAX_MODELS;
+ * one handle twice; n_fields or device differing from hs[0]'s; B < 1, above ANY member's max_batch or above 4096; next_ids with
+ * next_B outside 1..4096 or above ANY member's max_batch (the call that trains that batch would be refused); a bag-mode handle; a wide-row handle (k >= 17); a handle off the strip kernel (shape or FNN_NO_FUSE);
+ * shadowed features pending (fnn_set_shadowed); a handle after fnn_dp_init*.  FNN_ERR_STATE: a handle without table or dense
+ * tensors; a handle between fnn_step_begin and fnn_step_end.
+ * An id outside [-1, n_rows) is judged per model (n_rows may differ): absent for that model, never dereferenced.  With
+ * loss_sum_out the call returns FNN_ERR_RANGE, lists the models' indices and clears their flags (the losses are written);
+ * without it each handle's fnn_sync reports its own flag, as after a solo step. */
+#define FNN_STEP_MAX_MODELS 256
+int fnn_train_step_multi(fnn_handle* const* hs, int n_models, const int32_t* ids, const float* y, int B,
+                         const uint8_t* const* mask1, const uint8_t* const* mask2, int b_size,
+                         const int32_t* next_ids, int next_B, float* const* p_out, float* loss_sum_out);
+
 /* ---- Data parallelism (new: the reference has no distributed code).  One process per GPU; the global batch is cut into
  * contiguous shards; the loss is a batch SUM (python/FNN_wnzh.py:173), so the dense gradients of the shards add up exactly and
  * ONE collective per step is the whole exchange.  Tables are replicated.
