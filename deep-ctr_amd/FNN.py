@@ -167,10 +167,16 @@ def run_many(argv, specs, out=None):
     """run()'s schedule for every (lr, dropout, lambda1, lambda_fm) of `specs` in ONE pass over the data: the files are loaded
     once and the ids are resident once; every model has its own engine, its initial weights from the same seeded draws as run()'s,
     its own RandomStreams(234) dropout stream, early-stop bookkeeping and best-weights snapshot.  The models still training
-    step together (engine.train_epoch_many: one fnn_train_step_multi per batch); a model that stops leaves the group.
+    step together (engine.train_epoch_many: one fnn_train_step_multi per batch) and are evaluated together
+    (engine.evaluate_many: one fnn_eval_multi per feed and epoch); a model that stops leaves the group.
     Returns the list of histories; the prediction pickles are mlp3fm_{train,test}_<advertiser>_m<i>.p.  `out` (a dict)
     receives the engines under 'engines', each loaded with its model's best weights."""
-    from deep_ctr_amd.engine import train_epoch_many
+    from deep_ctr_amd.engine import FNNError, evaluate_many, predict_many, train_epoch_many
+
+    def _raise_status(r):
+        if 'status' in r:
+            raise FNNError(r['status'], r['error'])
+        return r
     specs = [parse_spec(s) for s in specs]
     assert len(specs) >= 1
     batch_size = 100
@@ -252,11 +258,15 @@ def run_many(argv, specs, out=None):
         for e in engs:
             e.sync()
         print('training: %d models, %.1fs' % (len(live), time.time() - start_time))
+        # both passes of every live model in one call each (fnn_eval_multi); a model whose own evaluate would have raised
+        # raises here, where its turn comes
+        trs = evaluate_many(engs, train_ids_d, train_y_d)
+        tes = evaluate_many(engs, test_ids_d, test_y_d)
         for j, m in enumerate(live):
             mo = models[m]
-            tr = mo.eng.evaluate(train_ids_d, train_y_d)
+            tr = _raise_status(trs[j])
             log_p(m, '\t\tTraining Err: \t' + str(i) + '\t' + str(tr['auc']) + '\t' + str(tr['rmse']))
-            te = mo.eng.evaluate(test_ids_d, test_y_d)
+            te = _raise_status(tes[j])
             auc, rmse, ll = te['auc'], te['rmse'], te['logloss']
             log_p(m, 'Test Err:' + str(i) + '\t' + str(auc) + '\t' + str(rmse))
             log_p(m, 'Test logloss:' + str(i) + '\t' + str(ll))
@@ -274,8 +284,11 @@ def run_many(argv, specs, out=None):
     for m, mo in enumerate(models):
         log_p(m, 'Minimal test error is ' + str(mo.min_err) + ' , at EPOCH ' + str(mo.min_err_epoch))
         mo.eng.set_dense(mo.best)
-        ut.save_weights("mlp3fm_train_" + advertiser + "_m" + str(m) + ".p", mo.eng.predict(train_ids).cpu().numpy())
-        ut.save_weights("mlp3fm_test_" + advertiser + "_m" + str(m) + ".p", mo.eng.predict(test_ids).cpu().numpy())
+    engs = [mo.eng for mo in models]
+    p_train, p_test = predict_many(engs, train_ids_d), predict_many(engs, test_ids_d)     # fnn_predict_multi
+    for m in range(len(models)):
+        ut.save_weights("mlp3fm_train_" + advertiser + "_m" + str(m) + ".p", p_train[m].cpu().numpy())
+        ut.save_weights("mlp3fm_test_" + advertiser + "_m" + str(m) + ".p", p_test[m].cpu().numpy())
     if out is not None:
         out['engines'] = [mo.eng for mo in models]
     return [mo.hist for mo in models]

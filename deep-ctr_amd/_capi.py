@@ -81,6 +81,10 @@ SIGNATURES = {
     "fnn_last_loss": (_i, [_vp, C.POINTER(_f)]),
     "fnn_predict": (_i, [_vp, _vp, _i, _vp, _i]),
     "fnn_eval": (_i, [_vp, _vp, _vp, _i64, _i, C.POINTER(C.c_double), C.POINTER(C.c_double), C.POINTER(C.c_double), _vp]),
+    # hs, p_out: host arrays of n_models pointers; auc, rmse, logloss, status: host arrays [n_models]
+    "fnn_predict_multi": (_i, [_vp, _i, _vp, _i64, _vp]),
+    "fnn_eval_multi": (_i, [_vp, _i, _vp, _vp, _i64, C.POINTER(C.c_double), C.POINTER(C.c_double), C.POINTER(C.c_double),
+                            C.POINTER(_i), _vp]),
     "fnn_prof_enable": (_i, [_vp, _i]),
     "fnn_prof_reset": (_i, [_vp]),
     "fnn_prof_get": (_i, [_vp, C.c_char_p, C.POINTER(C.c_double), C.POINTER(_i64)]),

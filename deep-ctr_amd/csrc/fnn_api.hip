@@ -58,6 +58,8 @@ using Step2Kernel = FnnKernel<SortArgs, WgradArgs, int, int, ScatArgs>;
 using Step3Kernel = FnnKernel<SortArgs, TailArgs, ScatArgs>;
 template <typename T> using GroupKernel = FnnKernel<const GroupArg<T>*>;      // the launches of fnn_train_step_multi
 static_assert(sizeof(GroupArg<float>) == sizeof(GroupArg<bf16_t>) && sizeof(GroupArg<float>) == sizeof(GroupArg<bs16_t>), "one argument ring serves every element type");
+template <typename T> using GroupPredKernel = FnnKernel<const GroupPredArg<T>*, int, int64_t, int, int64_t, int64_t, int>;      // the launch of fnn_predict_multi / fnn_eval_multi
+static_assert(sizeof(GroupPredArg<float>) == sizeof(GroupPredArg<bf16_t>) && sizeof(GroupPredArg<float>) == sizeof(GroupPredArg<bs16_t>), "one argument ring serves every element type");
 
 // What the configuration and the knobs decide of every call on a handle: made once, by make_plan and plan_step1 in fnn_create.  The
 // half that hangs on the width of the sort keys is plan_keys', which fnn_set_table calls again.  What a call adds is its batch
@@ -151,6 +153,10 @@ struct fnn_handle : FnnPlan {
     // joins the other members' streams to this one's and back, the packed {loss, range flag} of a call that asks for the losses
     ArgRing step_ring{sizeof(GroupArg<float>), 4 * FNN_STEP_MAX_MODELS};
     hipEvent_t join = nullptr; GroupPack* step_pack = nullptr;
+    // fnn_predict_multi / fnn_eval_multi, used when this handle is hs[0]: their argument ring and the zeroed labels of one feed
+    // batch that the strip kernel reads (and does not use) while it predicts
+    ArgRing eval_ring{sizeof(GroupPredArg<float>), 4 * FNN_EVAL_MAX_MODELS};
+    float* eval_y = nullptr;
     // profiling
     bool prof = false;
     std::map<std::string, ProfSlot> prof_slots;
@@ -355,6 +361,16 @@ template <typename T> GroupKernel<T> gstep1_sel(const FnnPlan& p, const FnnKnobs
     }
     return big ? GSTEP1(5, 2, 4, -1) : GSTEP1(1, 1, 4, -1);
 #undef GSTEP1
+}
+// ---- the group kernel of fnn_predict_multi / fnn_eval_multi: the generic instance on FM rows that step1_sel(train = false)
+// returns, by the same conditions; the only place that names an instantiation of k_gpredict
+template <typename T> GroupPredKernel<T> gpredict_sel(const FnnPlan& p, const FnnKnobs& kn)
+{
+#define GPREDICT(C1, C2, NW) GroupPredKernel<T>{k_gpredict<T, C1, C2, 4, NW>, 64 * NW, mlp_lds_bytes<T, C1, C2, 4>(false, p.F, NW)}
+    const bool big = p.H1p / 64 == 5;
+    if (big && kn.step1_waves == 8) return GPREDICT(5, 2, 8);
+    return big ? GPREDICT(5, 2, 4) : GPREDICT(1, 1, 4);
+#undef GPREDICT
 }
 template <typename T> GroupKernel<T> gstep2_sel(bool key64, bool m4, bool wgrad_lds)
 {
@@ -938,9 +954,11 @@ struct StepGroup {
     fnn_handle* const* hs; int n; fnn_handle* h0;
     std::vector<hipStream_t> others;               // the streams that are not hs[0]'s, each once
     bool entered = false;
-    StepGroup(fnn_handle* const* hs_, int n_) : hs(hs_), n(n_), h0(hs_ && n_ >= 1 && n_ <= FNN_STEP_MAX_MODELS ? hs_[0] : nullptr) {}
+    const char* name;                              // the entry point, in front of every refusal
+    StepGroup(fnn_handle* const* hs_, int n_, const char* name_ = "fnn_train_step_multi", int max_models = FNN_STEP_MAX_MODELS)
+        : hs(hs_), n(n_), h0(hs_ && n_ >= 1 && n_ <= max_models ? hs_[0] : nullptr), name(name_) {}
     ~StepGroup() { leave(); }
-    int refuse(int code, const std::string& msg) const { (h0 ? h0->err : g_create_err) = "fnn_train_step_multi: " + msg; return code; }
+    int refuse(int code, const std::string& msg) const { (h0 ? h0->err : g_create_err) = std::string(name) + ": " + msg; return code; }
     static std::string at(const std::string& what, int m) { return "model " + std::to_string(m) + ": " + what; }
     int enter()
     {
@@ -1037,6 +1055,157 @@ template <typename T> void launch_group(const LaunchClass& c, hipStream_t st, co
     // (x a multiple of 8: every model's blocks start on the XCD a solo launch's start on, which keeps the weight-gradient deal XCD-aware)
     if (x2 > 0) hipLaunchKernelGGL(reinterpret_cast<Fn>(c.k[1].fn), dim3(rup(x2, 8), M), dim3(c.k[1].threads), c.k[1].lds, st, d);
     if (x3 > 0) hipLaunchKernelGGL(reinterpret_cast<Fn>(c.k[2].fn), dim3(x3, M), dim3(c.k[2].threads), c.k[2].lds, st, d);
+}
+
+// ---- fnn_predict_multi / fnn_eval_multi: the predictions (and metrics) of several handles on one feed (the kernel: k_gpredict)
+// What the two calls read from the environment, per call: none of it changes a bit of any result.
+struct EvalKnobs {
+    int fb_len = 4096;          // FNN_EVAL_FEED_BATCH=256..65536, a multiple of 256: lines per feed batch (k_gpredict)
+    bool model_fast = false;    // FNN_EVAL_ORDER=model: the model is the fast index of the grid (default: tile, the strips of one model adjacent)
+    bool per_batch = false;     // FNN_EVAL_LAUNCH=batch: one launch per feed batch (default: span, one launch over all feed batches)
+    size_t cap = (size_t)1 << 30;      // FNN_EVAL_SCRATCH_BYTES: the scratch of one group of models (fnn_eval_multi)
+};
+constexpr int EVAL_FEED_BATCH_MAX = 65536;
+EvalKnobs read_eval_knobs()
+{
+    EvalKnobs k;
+    if (const char* e = getenv("FNN_EVAL_FEED_BATCH")) { const int v = atoi(e); if (v >= 256 && v <= EVAL_FEED_BATCH_MAX && v % 256 == 0) k.fb_len = v; }
+    if (const char* e = getenv("FNN_EVAL_ORDER")) k.model_fast = !strcmp(e, "model");
+    if (const char* e = getenv("FNN_EVAL_LAUNCH")) k.per_batch = !strcmp(e, "batch");
+    if (const char* e = getenv("FNN_EVAL_SCRATCH_BYTES")) { const long long c = atoll(e); if (c >= 1) k.cap = (size_t)c; }
+    return k;
+}
+// A member whose prediction is the strip kernel on FM rows rides in a group launch; every other one (bag mode, wide rows, shapes
+// off the strip kernel, FNN_NO_FUSE) runs its own prediction launches inside the call.
+inline bool pred_in_group(const fnn_handle* h) { return h->strip_ok && !h->bag; }
+// The members that one k_gpredict launch serves: a launch class of the prediction -- element type, padded shapes and waves per
+// strip, which is what gpredict_sel (as step1_sel(train = false)) looks at.  members: positions in the group, in its order.
+struct PredClass { FnnKernel<> k; int prec; std::vector<int> members; };
+template <typename T> PredClass pred_class_of(const fnn_handle* h)
+{
+    const GroupPredKernel<T> k = gpredict_sel<T>(*h, h->kn);
+    return PredClass{{reinterpret_cast<void (*)()>(k.fn), k.threads, k.lds}, h->cfg.precision, {}};
+}
+// (y: the zeroed labels of one feed batch.  The strip kernel reads a.y[t] for every t < a.B while it predicts too and uses none
+// of the values when train = 0 -- the solo path points it at the handle's loss_t for the same reason, which is only max_batch long)
+template <typename T> void fill_pred_arg(fnn_handle* h, int m, const int32_t* ids, const float* y, int fb_len, float* p, void* dst)
+{
+    GroupPredArg<T>& g = *static_cast<GroupPredArg<T>*>(dst);
+    g.ma = make_mlp_args<T>(h, ids, y, fb_len, nullptr, nullptr, false, p);
+    g.m = m;
+}
+// One class's launches: the whole feed in one (up to 2^22 strips, 2^26 lines, a launch: the runtime counts a grid's threads in 32 bits), or one per feed batch.
+template <typename T> void launch_gpredict(const PredClass& c, hipStream_t st, const void* dev_args, int64_t N, const EvalKnobs& ek)
+{
+    using Fn = void (*)(const GroupPredArg<T>*, int, int64_t, int, int64_t, int64_t, int);
+    const GroupPredArg<T>* d = static_cast<const GroupPredArg<T>*>(dev_args);
+    const int M = (int)c.members.size();
+    const int64_t strips = (N + 15) / 16, span = ek.per_batch ? ek.fb_len / 16 : (int64_t)1 << 22;
+    for (int64_t s0 = 0; s0 < strips; s0 += span) {
+        const int64_t ns = std::min(span, strips - s0);
+        dim3 grid((unsigned)ns, (unsigned)M);
+        if (ek.model_fast) {
+            const int64_t total = ns * M, gx = std::min<int64_t>(total, (int64_t)1 << 22);
+            grid = dim3((unsigned)gx, (unsigned)((total + gx - 1) / gx));
+        }
+        hipLaunchKernelGGL(reinterpret_cast<Fn>(c.k.fn), grid, dim3(c.k.threads), c.k.lds, st, d, M, N, ek.fb_len, s0, ns, ek.model_fast ? 1 : 0);
+    }
+}
+// The range flags of the n members behind `args`, bit 1 of each handle's error word, into flags[their position]; then the bit is
+// cleared (after every read: a handle may be listed twice).  One workgroup.
+static __global__ __launch_bounds__(256) void k_gpred_flags(const GroupPredArg<float>* __restrict__ args, const int n, int* __restrict__ flags)
+{
+    for (int i = threadIdx.x; i < n; i += 256) flags[args[i].m] = *args[i].ma.err & 1;
+    __syncthreads();
+    for (int i = threadIdx.x; i < n; i += 256) if (flags[args[i].m]) atomicAnd(args[i].ma.err, ~1);
+}
+// What both calls refuse, all of it before anything is launched or written.
+int pred_check(const StepGroup& g, const int32_t* ids, bool need_y, const int32_t* y, int64_t N, bool need_p, float* const* p_out)
+{
+    fnn_handle* const* hs = g.hs;
+    const int M = g.n;
+    if (!hs) return g.refuse(FNN_ERR_ARG, "null hs");
+    if (M < 1 || M > FNN_EVAL_MAX_MODELS) return g.refuse(FNN_ERR_ARG, "n_models must be in [1, " + std::to_string(FNN_EVAL_MAX_MODELS) + "]");
+    for (int m = 0; m < M; ++m) if (!hs[m]) return g.refuse(FNN_ERR_ARG, g.at("null handle", m));
+    fnn_handle* h0 = g.h0;
+    for (int m = 1; m < M; ++m)
+        if (hs[m]->F != h0->F || hs[m]->dev != h0->dev) return g.refuse(FNN_ERR_ARG, g.at("n_fields or device differs from model 0's", m));
+    if (!ids || (need_y && !y)) return g.refuse(FNN_ERR_ARG, need_y ? "null ids or y" : "null ids");
+    if (need_p && !p_out) return g.refuse(FNN_ERR_ARG, "null p_out");
+    if (need_p) for (int m = 0; m < M; ++m) if (!p_out[m]) return g.refuse(FNN_ERR_ARG, g.at("null p_out", m));
+    if (N < 1 || N > ((int64_t)1 << 30)) return g.refuse(FNN_ERR_ARG, "N must be in [1, 2^30]");
+    for (int m = 0; m < M; ++m)
+        if (hs[m]->bag && !hs[m]->strip_ok) return g.refuse(FNN_ERR_ARG, g.at("FNN_MODE_BAG runs on the strip kernel only, which FNN_NO_FUSE=1 turns off (or a shape it is not built for)", m));
+    for (int m = 0; m < M; ++m) {
+        const fnn_handle* h = hs[m];
+        if (!h->table16) return g.refuse(FNN_ERR_STATE, g.at("fnn_set_table has not been called", m));
+        if (!(h->dense_set[0] && h->dense_set[1] && h->dense_set[2])) return g.refuse(FNN_ERR_STATE, g.at("fnn_set_dense has not been called for all three layers", m));
+        if (h->in_step) return g.refuse(FNN_ERR_STATE, g.at("inside fnn_step_begin / fnn_step_end", m));
+    }
+    return FNN_OK;
+}
+// The predictions of the n members hs[0 .. n) of group `g` on the N lines, p[m] each: the argument array into hs[0]'s ring, one
+// set of launches per prediction launch class, then the members off the strip kernel one after the other, each in chunks of its
+// own max_batch with its stream swapped for the group's.  *dev_args: the members' arguments on the device (k_gpred_flags).
+int pred_forward(const StepGroup& g, fnn_handle* const* hs, int n, int base, const int32_t* ids, int64_t N, float* const* p, const EvalKnobs& ek,
+                 const GroupPredArg<float>** dev_args)
+{
+    fnn_handle* h0 = g.h0;
+    const hipStream_t st = h0->st;
+    std::vector<PredClass> cls;
+    std::vector<int> own;
+    for (int m = 0; m < n; ++m) {
+        if (!pred_in_group(hs[m])) { own.push_back(m); continue; }
+        PredClass c = BY_PREC_RC(hs[m], pred_class_of, (hs[m]));
+        size_t i = 0;
+        while (i < cls.size() && !(cls[i].k.fn == c.k.fn && cls[i].k.threads == c.k.threads && cls[i].k.lds == c.k.lds && cls[i].prec == c.prec)) ++i;
+        if (i == cls.size()) cls.push_back(c);
+        cls[i].members.push_back(m);
+    }
+    size_t slot = 0;
+    HIPCHK(h0, ring_take(h0->eval_ring, (size_t)n, &slot));
+    const size_t elem = h0->eval_ring.elem;
+    char* a = static_cast<char*>(h0->eval_ring.host) + slot * elem;
+    const char* d = static_cast<const char*>(h0->eval_ring.dev) + slot * elem;
+    size_t pos = 0;
+    auto fill = [&](int m) { BY_PREC(hs[m], fill_pred_arg, (hs[m], m, ids, h0->eval_y, ek.fb_len, p[m], a + pos * elem)); ++pos; };
+    for (const PredClass& c : cls) for (int m : c.members) fill(m);
+    for (int m : own) fill(m);                                        // not launched from: their range flags are read through them
+    HIPCHK(h0, ring_send(h0->eval_ring, slot, (size_t)n, st));
+    pos = 0;
+    for (const PredClass& c : cls) {
+        BY_PREC(hs[c.members[0]], launch_gpredict, (c, st, d + pos * elem, N, ek));
+        pos += c.members.size();
+    }
+    HIPCHK(h0, hipGetLastError());
+    for (int m : own) {
+        fnn_handle* h = hs[m];
+        const int rc = on_stream(h, st, [&]() -> int {
+            for (int64_t lo = 0; lo < N; lo += h->Bmax) {
+                const int B = (int)std::min<int64_t>(h->Bmax, N - lo);
+                RCCHK(BY_PREC_RC(h, run_step, (h, ids + lo * h->F, nullptr, B, nullptr, nullptr, false, p[m] + lo, nullptr)));
+            }
+            HIPCHK(h, hipGetLastError());
+            return FNN_OK;
+        });
+        if (rc != FNN_OK) { if (h != h0) g.refuse(rc, g.at(h->err, base + m)); return rc; }
+    }
+    *dev_args = reinterpret_cast<const GroupPredArg<float>*>(d);
+    return FNN_OK;
+}
+// the zeroed labels of the longest feed batch, hs[0]'s from its first group call on
+int ensure_eval_y(fnn_handle* h0)
+{
+    if (h0->eval_y) return FNN_OK;
+    HIPCHK(h0, hipMalloc((void**)&h0->eval_y, EVAL_FEED_BATCH_MAX * sizeof(float)));
+    HIPCHK(h0, hipMemsetAsync(h0->eval_y, 0, EVAL_FEED_BATCH_MAX * sizeof(float), h0->st));
+    return FNN_OK;
+}
+inline size_t up256(size_t b) { return (b + 255) / 256 * 256; }
+// scratch of a group of g models: p [g][N], the metric pass's, out [g], flags [g], n_pos
+size_t eval_scratch_bytes(int g, int64_t N)
+{
+    return up256((size_t)g * (size_t)N * 4) + up256(metrics_multi_bytes(g, N)) + up256((size_t)g * sizeof(MetricOut)) + up256((size_t)g * 4) + 256;
 }
 
 }  // namespace
@@ -1173,6 +1342,8 @@ int fnn_destroy(fnn_handle* h)
                     (void*)h->shadow_dev, (void*)h->xg_ids_send, (void*)h->xg_ids, (void*)h->xg_gxp, h->gws}) if (q) hipFree(q);
     for (void* q : h->owned) hipFree(q);
     ring_release(h->step_ring);
+    ring_release(h->eval_ring);
+    if (h->eval_y) hipFree(h->eval_y);
     if (h->join) hipEventDestroy(h->join);
     if (h->step_pack) hipFree(h->step_pack);
     for (fnn_handle::SortSlot* sl : {&h->slot[0], &h->slot[1], &h->gsl}) row_group_free(*sl);
@@ -1942,6 +2113,99 @@ int fnn_eval(fnn_handle* h, const int32_t* ids, const int32_t* y, int64_t N, int
     if (logloss) *logloss = out[2];
     RCCHK(check_async(h));
     if (mrc == -2 || mrc == -3) FAIL(h, FNN_ERR_RANGE, merr);
+    return FNN_OK;
+}
+
+// The predictions of several handles on one feed: per prediction launch class ONE launch with the model as a grid dimension
+// ("Evaluating many FNN models").  Nothing is allocated after hs[0]'s first group call, nothing synchronises.
+int fnn_predict_multi(fnn_handle* const* hs, int n_models, const int32_t* ids, int64_t N, float* const* p_out)
+{
+    StepGroup g(hs, n_models, "fnn_predict_multi", FNN_EVAL_MAX_MODELS);
+    RCCHK(pred_check(g, ids, false, nullptr, N, true, p_out));
+    const EvalKnobs ek = read_eval_knobs();
+    RCCHK(g.enter());
+    RCCHK(ensure_eval_y(g.h0));
+    const GroupPredArg<float>* d = nullptr;
+    RCCHK(pred_forward(g, hs, n_models, 0, ids, N, p_out, ek, &d));
+    return g.leave();
+}
+
+// ... and their metrics: the models in groups of as many as fit the scratch cap, per group the predictions, metrics_multi on
+// them, the range flags, one copy home and one synchronisation.
+int fnn_eval_multi(fnn_handle* const* hs, int n_models, const int32_t* ids, const int32_t* y, int64_t N,
+                   double* auc, double* rmse, double* logloss, int* status, float* const* p_out)
+{
+    StepGroup g(hs, n_models, "fnn_eval_multi", FNN_EVAL_MAX_MODELS);
+    RCCHK(pred_check(g, ids, true, y, N, false, nullptr));
+    fnn_handle* h0 = g.h0;
+    const EvalKnobs ek = read_eval_knobs();
+    int G = n_models;
+    {
+        const size_t one = eval_scratch_bytes(1, N);
+        if ((size_t)G > ek.cap / one) G = (int)(ek.cap / one);
+        if (G < 1) G = 1;
+        while (G > 1 && eval_scratch_bytes(G, N) > ek.cap) --G;
+    }
+    RCCHK(g.enter());
+    RCCHK(ensure_eval_y(h0));
+    const hipStream_t st = h0->st;
+    char* scratch = nullptr;
+    HIPCHK(h0, hipMalloc((void**)&scratch, eval_scratch_bytes(G, N)));
+    float* p_d = reinterpret_cast<float*>(scratch);
+    char* ms = scratch + up256((size_t)G * (size_t)N * 4);
+    MetricOut* out_d = reinterpret_cast<MetricOut*>(ms + up256(metrics_multi_bytes(G, N)));
+    int* flags_d = reinterpret_cast<int*>(reinterpret_cast<char*>(out_d) + up256((size_t)G * sizeof(MetricOut)));
+    unsigned long long* npos_d = reinterpret_cast<unsigned long long*>(reinterpret_cast<char*>(flags_d) + up256((size_t)G * 4));
+    std::vector<MetricOut> ho(G);
+    std::vector<int> hf(G);
+    std::vector<float*> pp(G);
+    unsigned long long n_pos = 0;
+    std::string bad, range;
+    auto groups = [&]() -> int {                                      // an error leaves the lambda: the scratch is still freed
+        for (int g0 = 0; g0 < n_models; g0 += G) {
+            const int n = std::min(G, n_models - g0);
+            for (int m = 0; m < n; ++m) pp[m] = p_d + (size_t)m * (size_t)N;
+            const GroupPredArg<float>* d = nullptr;
+            RCCHK(pred_forward(g, hs + g0, n, g0, ids, N, pp.data(), ek, &d));
+            HIPCHK(h0, metrics_multi(st, p_d, y, N, n, ms, g0 == 0, npos_d, out_d));
+            hipLaunchKernelGGL(k_gpred_flags, dim3(1), dim3(256), 0, st, d, n, flags_d);
+            HIPCHK(h0, hipGetLastError());
+            if (p_out) for (int m = 0; m < n; ++m)
+                if (p_out[g0 + m]) HIPCHK(h0, hipMemcpyAsync(p_out[g0 + m], pp[m], (size_t)N * 4, hipMemcpyDeviceToDevice, st));
+            HIPCHK(h0, hipMemcpyAsync(ho.data(), out_d, (size_t)n * sizeof(MetricOut), hipMemcpyDeviceToHost, st));
+            HIPCHK(h0, hipMemcpyAsync(hf.data(), flags_d, (size_t)n * 4, hipMemcpyDeviceToHost, st));
+            if (g0 == 0) HIPCHK(h0, hipMemcpyAsync(&n_pos, npos_d, 8, hipMemcpyDeviceToHost, st));
+            HIPCHK(h0, hipStreamSynchronize(st));                     // the group's one synchronisation
+            const double np_ = (double)n_pos, nn = (double)(N - (int64_t)n_pos);
+            const bool two = n_pos > 0 && (int64_t)n_pos < N;
+            for (int m = 0; m < n; ++m) {
+                const MetricOut& o = ho[m];
+                const int i = g0 + m;
+                double v[3] = {std::nan(""), std::nan(""), std::nan("")};
+                if (!o.n_bad) {
+                    if (two) v[0] = (double)o.auc_sum / (2.0 * np_ * nn);
+                    v[1] = std::sqrt(o.se / (double)N); v[2] = o.ll / (double)N;
+                } else bad += (bad.empty() ? "" : ", ") + std::to_string(i);
+                if (hf[m]) range += (range.empty() ? "" : ", ") + std::to_string(i);
+                if (auc) auc[i] = v[0];
+                if (rmse) rmse[i] = v[1];
+                if (logloss) logloss[i] = v[2];
+                if (status) status[i] = o.n_bad ? FNN_ERR_RANGE : FNN_OK;
+            }
+        }
+        return FNN_OK;
+    };
+    const int rc = groups();
+    const int rj = g.leave();
+    if (rc != FNN_OK) hipStreamSynchronize(st);                       // nothing may still be using the scratch
+    hipFree(scratch);
+    if (rc != FNN_OK) return rc;
+    if (rj != FNN_OK) return rj;
+    std::string msg;
+    if (!bad.empty()) msg += "predictions NaN or outside [0, 1] in model(s) " + bad;
+    if (!range.empty()) msg += std::string(msg.empty() ? "" : "; ") + "feature id outside [-1, n_rows) in model(s) " + range;
+    if (n_pos == 0 || (int64_t)n_pos == N) msg += std::string(msg.empty() ? "" : "; ") + "only one class present in y (roc_auc_score raises ValueError)";
+    if (!msg.empty()) return g.refuse(FNN_ERR_RANGE, msg);
     return FNN_OK;
 }
 

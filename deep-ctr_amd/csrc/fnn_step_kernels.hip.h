@@ -260,6 +260,37 @@ static __global__ __launch_bounds__(256) void k_gstep3(const GroupArg<T>* __rest
 }
 
 // ------------------------------------------------------------------------------------------
+// The predictions of several models on one feed (fnn_predict_multi / fnn_eval_multi): the strip kernel's generic prediction
+// instance -- what step1_sel(train = false) returns for each member of the launch -- with the model as a grid dimension and
+// the feed of N lines cut into FEED BATCHES of `fb_len` lines (a multiple of 256; the last one shorter), whatever the members'
+// max_batch.  Strip s of the feed is strip s % (fb_len / 16) of feed batch s / (fb_len / 16): the body runs on a register copy
+// of the member's arguments with ids, p_out and B moved to that feed batch, so that every index it forms (the labels' among
+// them: a.y is fb_len floats long) stays below fb_len.  A line's prediction depends on that line's ids alone, so how the feed
+// is cut changes no bit.  model_fast = 0: grid (strips, models), the strips of one model adjacent (they share W1 / W2 in L2);
+// 1: a linear grid with the model the fast index (the models of one strip share its ids and table rows).
+// ------------------------------------------------------------------------------------------
+template <typename T> struct GroupPredArg { MlpArgs<T> ma; int m; };        // m: the member's place in the call's group (its range flag's)
+template <typename T, int C1, int C2, int CX, int NW>
+static __global__ __launch_bounds__(64 * NW) void k_gpredict(const GroupPredArg<T>* __restrict__ args, const int n_models, const int64_t N,
+                                                             const int fb_len, const int64_t strip0, const int64_t n_strips, const int model_fast)
+{
+    extern __shared__ __align__(16) unsigned char smem[];
+    int64_t s = blockIdx.x; int m = blockIdx.y;
+    if (model_fast) {
+        const int64_t l = (int64_t)blockIdx.y * gridDim.x + blockIdx.x;
+        s = l / n_models; m = (int)(l % n_models);
+    }
+    if (s >= n_strips) return;
+    s += strip0;
+    MlpArgs<T> a = args[m].ma;                                        // the whole block before anything is stored: scalar loads
+    const int per = fb_len >> 4;
+    const int64_t lo = s / per * fb_len;
+    a.ids += lo * a.F; a.p_out += lo;
+    a.B = (int)(N - lo < fb_len ? N - lo : fb_len);
+    mlp_body<T, C1, C2, CX, false, NW, -1>(a, (int)(s % per), smem);
+}
+
+// ------------------------------------------------------------------------------------------
 // Data parallelism, FNN_DP_COLLECTIVE_P2P: the update launch that IS the all-reduce.  Every rank's exchange region
 // ([2 parities][nbp floats] buckets, then 8 flags on 64-byte lines of their own) is mapped by every peer (hipIpc*).
 //   1. block 0, lane p: release at system scope (this rank's bucket of the step -- written by the launch before this one -- is

@@ -533,6 +533,67 @@ def train_epoch_many(engines, ids_d, yf_d, batch_size, masks1, masks2, first=0, 
     e0._keep_many = (ids_d, yf_d, m1, m2)
 
 
+def predict_many(engines, ids):
+    """predict of every engine of a list on ONE feed, in one call (fnn_predict_multi): a list of device tensors [N] float32,
+    entry m bit for bit engines[m].predict(ids).  N is not bounded by any engine's max_batch.  Nothing synchronises: an id
+    outside an engine's table shows at that engine's sync(), as after predict."""
+    e0 = engines[0]
+    torch = e0._torch
+    M = len(engines)
+    ids_t = e0._dev(ids, torch.int32)
+    n = ids_t.shape[0]
+    ps = [torch.empty(n, dtype=torch.float32, device=e0.device) for _ in engines]
+    hs = (C.c_void_p * M)(*[e.h.value for e in engines])
+    for e in engines:
+        e._enter()
+    rc = e0.lib.fnn_predict_multi(hs, M, ids_t.data_ptr(), n, (C.c_void_p * M)(*[t.data_ptr() for t in ps]))
+    for e in engines:
+        e._leave()
+    if rc != 0:
+        raise FNNError(rc, (e0.lib.fnn_last_error(e0.h) or b'').decode())
+    e0._keep_eval = ids_t
+    return ps
+
+
+def evaluate_many(engines, ids, y, want_p=False):
+    """evaluate of every engine of a list on ONE feed, in one call (fnn_eval_multi).  Returns a list: entry m is what
+    engines[m].evaluate(ids, y, want_p) returns, {'auc', 'rmse', 'logloss'[, 'p']}, bit for bit.  Where that call would raise
+    FNNError(FNN_ERR_RANGE) the entry says so instead, so that one diverged model does not cost the others their results: it
+    then carries the further keys 'status' (FNN_ERR_RANGE) and 'error' (the call's message) --
+      a model with a prediction NaN or outside [0, 1]: 'auc', 'rmse' and 'logloss' are NaN ('p' is still the predictions);
+      only one class in y: every entry, 'auc' NaN, 'rmse' and 'logloss' as computed.
+    An id outside [-1, n_rows) of some engine's table is a fault of the feed and raises FNNError(FNN_ERR_RANGE) naming the
+    models, as every other refusal of the call does."""
+    e0 = engines[0]
+    torch = e0._torch
+    M = len(engines)
+    ids_t, y_t = e0._dev(ids, torch.int32), e0._dev(y, torch.int32)
+    n = ids_t.shape[0]
+    ps = [torch.empty(n, dtype=torch.float32, device=e0.device) for _ in engines] if want_p else None
+    auc, rmse, ll, status = (C.c_double * M)(), (C.c_double * M)(), (C.c_double * M)(), (C.c_int * M)()
+    hs = (C.c_void_p * M)(*[e.h.value for e in engines])
+    for e in engines:
+        e._enter()
+    rc = e0.lib.fnn_eval_multi(hs, M, ids_t.data_ptr(), y_t.data_ptr(), n, auc, rmse, ll, status,
+                               (C.c_void_p * M)(*[t.data_ptr() for t in ps]) if want_p else None)
+    for e in engines:
+        e._leave()
+    msg = '' if rc == 0 else (e0.lib.fnn_last_error(e0.h) or b'').decode()
+    if rc != 0 and (rc != _capi.FNN_ERR_RANGE or 'feature id outside' in msg):
+        raise FNNError(rc, msg)
+    one_class = 'only one class' in msg
+    outs = []
+    for m in range(M):
+        o = {'auc': auc[m], 'rmse': rmse[m], 'logloss': ll[m]}
+        if want_p:
+            o['p'] = ps[m]
+        if status[m] != 0 or one_class:
+            o['status'] = _capi.FNN_ERR_RANGE
+            o['error'] = msg
+        outs.append(o)
+    return outs
+
+
 def _tensor_from_ptr(torch, ptr, n, device, kind='f4'):
     """Zero-copy view of `n` elements (float32, or 'u1' bytes) of device memory owned by the library."""
 

@@ -327,6 +327,53 @@ int fnn_predict(fnn_handle* h, const int32_t* ids, int B, float* p_out, int memk
 int fnn_eval(fnn_handle* h, const int32_t* ids, const int32_t* y, int64_t N, int memkind,
              double* auc, double* rmse, double* logloss, float* p_out);
 
+/* fnn_predict / fnn_eval of SEVERAL handles on ONE feed in one call (the evaluation passes of a hyper-parameter search:
+ * python/FNN_wnzh.py:193-221 once per model and epoch).  ids [N, F] int32 and y [N] int32 are the one DEVICE feed, 1 <= N <= 2^30;
+ * N is not bounded by any member's max_batch.  hs, auc, rmse, logloss, status and p_out are HOST arrays of n_models entries, each
+ * output array may be NULL; p_out[m] is a DEVICE pointer [N], an entry may be NULL in fnn_eval_multi and is required in
+ * fnn_predict_multi.  Device pointers only (no memkind).
+ *
+ * p_out[m] is BIT FOR BIT what fnn_eval(hs[m], ..., p_out) -- or fnn_predict in chunks of max_batch -- writes, and auc[m], rmse[m],
+ * logloss[m] are bit for bit what fnn_eval(hs[m]) returns.  status[m]: FNN_OK, or FNN_ERR_RANGE for a model with a prediction NaN
+ * or outside [0, 1] (a diverged model): its three metrics are NaN, the other models' results stand.  Only one class in y: every
+ * auc[m] is NaN, rmse and logloss are written.  An id outside [-1, n_rows) is judged per model (n_rows may differ), as in
+ * fnn_train_step_multi: fnn_eval_multi reports those models and clears their flags, fnn_predict_multi leaves them to each
+ * handle's fnn_sync.  Any of the three makes the call return FNN_ERR_RANGE with the models' indices in fnn_last_error(hs[0]);
+ * every other result is still written.
+ *
+ * The calls only READ the models: no bit of table, dense tensors or shadows changes, a handle may be listed twice, and group
+ * steps, solo steps, fnn_predict, fnn_eval and these calls may be interleaved in any order.  A grouping carried for the next step
+ * (fnn_prefetch_ids) survives on the members the group launch serves; a member that runs its own launches drops it, as fnn_predict does.
+ *
+ * Accepted: everything fnn_eval accepts, data-parallel handles included, of hs[0]'s n_fields and device.  The members whose
+ * prediction is the strip kernel on FM rows (FNN_MODE_FM, k <= 15, hidden sizes the strip kernel is built for, no FNN_NO_FUSE)
+ * form prediction LAUNCH CLASSES by element type, padded shapes and waves per strip; the feed is cut into feed batches of 4096
+ * lines whatever the members' max_batch ($FNN_EVAL_FEED_BATCH, a multiple of 256 up to 65536), and each class takes ONE launch over all feed batches
+ * with the model a grid dimension, its arguments read from a device array.  Every other member (bag mode, wide rows, other
+ * hidden sizes, FNN_NO_FUSE) runs its own prediction launches inside the call, in chunks of its max_batch, on the group's stream.
+ *
+ * fnn_eval_multi computes the metrics of all models of a group in one pass over their predictions, without a per-model
+ * allocation or synchronisation.  Scratch: N * 4 bytes of predictions plus about 8.5 N bytes of metric scratch per model, taken in
+ * groups of as many models as fit under $FNN_EVAL_SCRATCH_BYTES (read per call, default 2^30; one model at the least): one
+ * allocation per call, one synchronisation per group; where the groups are cut changes no bit.  A non-NULL p_out[m] receives a
+ * device copy of the model's predictions.  fnn_predict_multi writes straight into p_out[m], allocates nothing (after hs[0]'s first
+ * group call) and does not synchronise.  $FNN_EVAL_ORDER=tile|model (which of strip and model is the grid's fast index) and
+ * $FNN_EVAL_LAUNCH=span|batch (one launch per class, or one per feed batch) are read per call and change no bit.
+ *
+ * Streams: everything runs on hs[0]'s stream, which first waits for what is queued on every other member's stream; every other
+ * member's stream then waits for the call's last launch.
+ *
+ * A refused call launches nothing and writes nothing; its message starts with the function's name, names the offending model's
+ * index and is left with fnn_last_error(hs[0]) (fnn_last_error(NULL) without a usable hs[0]).  FNN_ERR_ARG: null hs or a null
+ * entry; n_models outside 1..FNN_EVAL_MAX_MODELS; null ids, null y (fnn_eval_multi), null p_out or a null entry of it
+ * (fnn_predict_multi); N outside [1, 2^30]; n_fields or device differing from hs[0]'s; a bag-mode handle off the strip kernel
+ * (fnn_eval refuses it too).  FNN_ERR_STATE: a handle without table or dense tensors; a handle between fnn_step_begin and
+ * fnn_step_end.  n_models == 1 takes the same path. */
+#define FNN_EVAL_MAX_MODELS 1024
+int fnn_predict_multi(fnn_handle* const* hs, int n_models, const int32_t* ids, int64_t N, float* const* p_out);
+int fnn_eval_multi(fnn_handle* const* hs, int n_models, const int32_t* ids, const int32_t* y, int64_t N,
+                   double* auc, double* rmse, double* logloss, int* status, float* const* p_out);
+
 /* Timing hook for bench.py: average device time (ms) of the kernel named
  * `which` ("gather", "fwd1", "fwd2", "head", "bwd1", "gx", "wgrad", "reduce",
  * "update", "sort", "scatter", "finalize") over the steps since the last
