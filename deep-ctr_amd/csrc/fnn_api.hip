@@ -535,9 +535,10 @@ int scatter_global_impl(fnn_handle* h, const int32_t* ids_g, const float* gxp_g,
 // global batch in global example order on this rank.
 // Bag mode (python/SNN_RBM.py:285-291: ww0[f] -= delta_t, no decay -- a plain sum over the examples): the gathered shards are
 // applied ONE AFTER THE OTHER in rank order with the step's own sparse role (grouping of the shard's ids, then the two levels of
-// the segmented row update reading that shard's gathered deltas): every rank performs the same operations in the same order, so
-// the replicas stay bit-identical to each other, and equal to the single-process step of the global batch up to the rounding of
-// `world` partial sums per row instead of one.
+// the segmented row update reading that shard's gathered deltas): every rank launches the same operations in the same order, so
+// the replicas equal the single-process step of the global batch up to the rounding of `world` partial sums per row instead of
+// one, and stay bit-identical to each other while no row sits in two columns of a shard; rows that do take the float atomics of
+// the row update, whose order no launch fixes (include/fnn_hip.h).
 template <typename T>
 int dp_exchange_sparse(fnn_handle* h, const int32_t* ids, int B)
 {

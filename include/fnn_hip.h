@@ -231,8 +231,12 @@ int fnn_train_step_multi(fnn_handle* const* hs, int n_models, const int32_t* ids
  *                           applies the whole global batch's row updates: replicas stay identical (the parity mode; world *
  *                           max_batch <= 32768).  FNN_MODE_FM: in global example order, equal to a single-process run of the
  *                           global batch.  FNN_MODE_BAG (no decay, the update is a sum: python/SNN_RBM.py:285-291): the shards
- *                           one after the other in rank order -- replicas bit-identical to each other, equal to the
- *                           single-process run up to the rounding of `world` partial sums per row
+ *                           one after the other in rank order -- equal to the single-process run up to the rounding of
+ *                           `world` partial sums per row, and replicas bit-identical to each other as long as no row
+ *                           sits in two columns of a shard (one feature per field).  A row that several columns hold
+ *                           -- the rule on the reference's own feed, which packs a line's active features to the left
+ *                           -- is updated with float atomics, whose order is not fixed: there the replicas agree up
+ *                           to rounding, like two single-process runs of such a batch
  * The collectives are RCCL's: librccl.so.1 is opened at fnn_dp_init (no link-time dependency), the handle owns its communicator. */
 #define FNN_DP_SPARSE_LOCAL    0
 #define FNN_DP_SPARSE_EXCHANGE 1
