@@ -43,7 +43,7 @@ struct FnnKnobs {
     bool step1_fixed = true;    // FNN_STEP1_FORM=generic: never the fixed training instance of the strip kernel (step1_sel)
     bool fused = true;          // FNN_NO_FUSE=1: the layer-by-layer kernels instead of the strip kernel
     int role_off = 0;           // FNN_ROLE_OFF, diagnostics only: 1 sort, 2 dense, 4 sparse roles of launches 2 / 3 skipped (make_roles)
-    int splitk = 0;             // FNN_SPLITK=2|4|8|16: split-K of the weight-gradient products (0: the plan's choice)
+    int splitk = 0;             // FNN_SPLITK=2|4|8|16: split-K of the weight-gradient products (0: the plan's choice; bf16 takes 16 as 8: make_plan)
     int scat2_wgs = 256;        // FNN_SCAT2_WGS=16..1024: workgroups walking the multi-chunk segments in launch 3
     int wgrad_form = -1;        // FNN_WGRAD_FORM=direct|lds (-1: the plan's choice, -2: neither word)
     int scat_form = SCAT1_HALF;      // FNN_SCAT1_FORM: the body of level 1 of the sparse-row update (scat1h_body; quarter: scat1q_body, slot: scat1_body)
@@ -944,6 +944,9 @@ FnnPlan make_plan(const fnn_cfg& c, const FnnKnobs& kn)
     const bool lds_dflt = kn.wgrad_form == -1 && eight && p.bf16 && p.ldT / 4 / Traits<bf16_t>::KS >= WGRAD_LDS_S;
     p.wgrad_lds = kn.wgrad_form == WGRAD_LDS || lds_dflt ? 1 : 0;
     p.splitk = kn.splitk ? kn.splitk : (eight && !lds_dflt ? 8 : 4);
+    // a slice of the shortest padded batch (256 lines) must hold a k-step of the element type, or the products of a batch of up to
+    // 256 lines walk no step and the dense tensors do not move: FNN_SPLITK=16 means 8 in bf16 (32 lines a step)
+    if (p.bf16) p.splitk = std::min(p.splitk, 256 / Traits<bf16_t>::KS);
     return p;
 }
 

@@ -19,7 +19,7 @@ import deep_ctr_amd  # noqa: F401
 from deep_ctr_amd import _capi, engine, synth
 from deep_ctr_amd.engine import FNNEngine, FNNError
 
-from test_gpu_shapes import make_engine, make_problem
+from test_gpu_shapes import edge_empties, make_engine, make_problem
 
 pytestmark = pytest.mark.gpu
 
@@ -33,15 +33,18 @@ SENT = -7.0
 
 
 class Feed(object):
-    """N lines on the device: ids for the NROWS-row table, int32 labels of both classes; its first 2 * TB lines train."""
+    """N lines on the device: ids for the NROWS-row table, int32 labels of both classes; its first 2 * TB lines train.  F / K / n:
+    the layout and the number of lines (the default: the module's); empties: edge_empties(n, F) as well."""
 
-    def __init__(self, seed=5):
+    def __init__(self, seed=5, F=F_, K=K, n=N, empties=False):
         import torch
         self.dev = torch.device('cuda', 0)
-        self.rows, self.fo, ids, y, _, _, _ = make_problem(F_, K, 300, 100, N, n_rows=NROWS, seed=seed)
+        self.F, self.K, self.seed, self.n = F, K, seed, n
+        self.rows, self.fo, ids, y, _, _, _ = make_problem(F, K, 300, 100, n, n_rows=NROWS, seed=seed,
+                                                           empty=edge_empties(n, F) if empties else ())
         ids[1, 2] = -1                                                   # an empty field
         self.ids, self.y = ids, y.astype(np.int32)
-        assert 0 < self.y.sum() < N
+        assert 0 < self.y.sum() < n
         self.ids_d, self.y_d, self.yf_d = self.put(ids), self.put(self.y), self.put(y.astype(np.float32))
 
     def put(self, a):
@@ -50,9 +53,10 @@ class Feed(object):
         torch.cuda.synchronize()
         return t
 
-    def table(self, n_rows, k=K):
+    def table(self, n_rows, k=None):
         """The feed's table continued to n_rows rows (rows beyond NROWS are in no line of the feed); another k: its own rows."""
-        rows = self.rows if k == K else make_problem(F_, k, 300, 100, 4, n_rows=NROWS, seed=5)[0]
+        k = self.K if k is None else k
+        rows = self.rows if k == self.K else make_problem(self.F, k, 300, 100, 4, n_rows=NROWS, seed=self.seed)[0]
         if n_rows <= NROWS:
             return rows[:n_rows].copy(), self.fo[:n_rows].copy()
         extra = synth.fm_table(n_rows - NROWS, k, 0.05, 77)
@@ -63,11 +67,12 @@ class Spec(object):
     """One model of a group: what make_engine takes and the seed of its initial dense tensors and masks; bag: an FNN_MODE_BAG
     handle of the smallest shape the strip kernel takes bag rows at (h0 = 192, hidden below 64)."""
 
-    def __init__(self, m, prec='bf16', H1=300, H2=100, n_rows=NROWS, max_batch=512, k=K, bag=False):
+    def __init__(self, m, prec='bf16', H1=300, H2=100, n_rows=NROWS, max_batch=512, k=K, bag=False, F=F_):
         self.m, self.prec, self.H1, self.H2, self.n_rows, self.max_batch, self.k, self.bag = m, prec, H1, H2, n_rows, max_batch, k, bag
+        self.F = F
         self.lr = (0.01, 0.004, 0.02, 0.007, 0.013)[m % 5]
         self.acti = ACTS[m % 3]
-        self.p = make_problem(F_, k, H1, H2, 4, n_rows=64, seed=40 + m)[4]
+        self.p = make_problem(F, k, H1, H2, 4, n_rows=64 if F <= 16 else NROWS, seed=40 + m)[4]     # (the dense tensors do not depend on n_rows)
 
     def masks(self, s):
         rng = np.random.RandomState(1000 * self.m + s)
@@ -78,19 +83,19 @@ class Spec(object):
     def fresh(self, feed):
         if self.bag:
             from test_gpu_parity import make_snn_engine, make_snn_problem
-            ww0, bb0, _, _, p, _, _ = make_snn_problem(8, n_rows=NROWS, h0=192, seed=40 + self.m, n_fields=F_, h1=self.H1, h2=self.H2)
-            return make_snn_engine(ww0, bb0, p, prec=self.prec, lr=self.lr, h0=192, max_batch=self.max_batch, n_fields=F_, h1=self.H1,
+            ww0, bb0, _, _, p, _, _ = make_snn_problem(8, n_rows=NROWS, h0=192, seed=40 + self.m, n_fields=self.F, h1=self.H1, h2=self.H2)
+            return make_snn_engine(ww0, bb0, p, prec=self.prec, lr=self.lr, h0=192, max_batch=self.max_batch, n_fields=self.F, h1=self.H1,
                                    h2=self.H2, acti=self.acti)
         rows, fo = feed.table(self.n_rows, self.k)
-        return make_engine(F_, self.k, self.H1, self.H2, rows, fo, self.p, prec=self.prec, acti=self.acti, max_batch=self.max_batch,
+        return make_engine(self.F, self.k, self.H1, self.H2, rows, fo, self.p, prec=self.prec, acti=self.acti, max_batch=self.max_batch,
                            lr=self.lr, lam1=(0.02, 0.0, 0.05)[self.m % 3], lamfm=(0.1, 0.3, 0.0, 0.05)[self.m % 4])
 
-    def engine(self, feed, steps=2):
-        """A handle that has taken `steps` training steps on the head of the feed."""
+    def engine(self, feed, steps=2, tb=TB):
+        """A handle that has taken `steps` training steps of tb lines on the head of the feed."""
         eng = self.fresh(feed)
         for s in range(steps):
             r1, r2 = self.masks(s)
-            eng.train_step(feed.ids_d[s * TB:(s + 1) * TB], feed.yf_d[s * TB:(s + 1) * TB], r1, r2, want_loss=False)
+            eng.train_step(feed.ids_d[s * tb:(s + 1) * tb], feed.yf_d[s * tb:(s + 1) * tb], r1, r2, want_loss=False)
         eng.sync()
         return eng
 
@@ -107,14 +112,15 @@ def _arr(ptrs):
     return (C.c_void_p * len(ptrs))(*ptrs)
 
 
-def eval_multi(engs, ids_t, y_t, want=None, n=None):
+def eval_multi(engs, ids_t, y_t, want=None, n=None, tail=0):
     """One raw fnn_eval_multi.  want: per model, whether p_out[m] is given (None: all; 'null': a null p_out).  Returns
-    (code, auc, rmse, logloss, status, p per model as numpy or None); every output starts at a sentinel."""
+    (code, auc, rmse, logloss, status, p per model as numpy or None); every output starts at a sentinel.  tail: that many more
+    floats behind each p_out, returned with it."""
     import torch
     M = len(engs)
     n = ids_t.shape[0] if n is None else n
     want = [True] * M if want is None else want
-    ps = None if want == 'null' else [torch.full((max(n, 1),), SENT, dtype=torch.float32, device=ids_t.device) if w else None for w in want]
+    ps = None if want == 'null' else [torch.full((max(n, 1) + tail,), SENT, dtype=torch.float32, device=ids_t.device) if w else None for w in want]
     torch.cuda.synchronize()
     auc, rmse, ll = ((C.c_double * M)(*([SENT] * M)) for _ in range(3))
     st = (C.c_int * M)(*([77] * M))
@@ -124,20 +130,20 @@ def eval_multi(engs, ids_t, y_t, want=None, n=None):
     return rc, list(auc), list(rmse), list(ll), list(st), [None] * M if ps is None else [None if p is None else p.cpu().numpy() for p in ps]
 
 
-def predict_multi(engs, ids_t, n=None):
+def predict_multi(engs, ids_t, n=None, tail=0):
     import torch
     n = ids_t.shape[0] if n is None else n
-    ps = [torch.full((max(n, 1),), SENT, dtype=torch.float32, device=ids_t.device) for _ in engs]
+    ps = [torch.full((max(n, 1) + tail,), SENT, dtype=torch.float32, device=ids_t.device) for _ in engs]
     torch.cuda.synchronize()
     rc = engs[0].lib.fnn_predict_multi(_arr([e.h.value for e in engs]), len(engs), ids_t.data_ptr(), n, _arr([p.data_ptr() for p in ps]))
     torch.cuda.synchronize()
     return rc, [p.cpu().numpy() for p in ps]
 
 
-def solo_eval(eng, ids_t, y_t):
+def solo_eval(eng, ids_t, y_t, tail=0):
     """The twin's fnn_eval: (code, auc, rmse, logloss, p)."""
     import torch
-    p = torch.full((ids_t.shape[0],), SENT, dtype=torch.float32, device=ids_t.device)
+    p = torch.full((ids_t.shape[0] + tail,), SENT, dtype=torch.float32, device=ids_t.device)
     torch.cuda.synchronize()
     auc, rmse, ll = C.c_double(SENT), C.c_double(SENT), C.c_double(SENT)
     rc = eng.lib.fnn_eval(eng.h, ids_t.data_ptr(), y_t.data_ptr(), ids_t.shape[0], DEV, C.byref(auc), C.byref(rmse), C.byref(ll), p.data_ptr())
@@ -156,7 +162,7 @@ def assert_equals_twin(got, m, ref, what, with_p=True):
     assert auc[m] == ref[1] and rmse[m] == ref[2] and ll[m] == ref[3], '%s: metrics %r against %r' % (what, (auc[m], rmse[m], ll[m]), ref[1:4])
     assert st[m] == 0, what
     if with_p:
-        assert np.array_equal(bits(ps[m]), bits(ref[4])), '%s: p, %d of %d differ' % (what, (bits(ps[m]) != bits(ref[4])).sum(), N)
+        assert np.array_equal(bits(ps[m]), bits(ref[4])), '%s: p, %d of %d differ' % (what, (bits(ps[m]) != bits(ref[4])).sum(), ref[4].size)
 
 
 def dense_state(e):

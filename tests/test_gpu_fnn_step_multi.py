@@ -20,7 +20,7 @@ import deep_ctr_amd  # noqa: F401
 from deep_ctr_amd import _capi, engine, synth
 from deep_ctr_amd.engine import FNNError
 
-from test_gpu_shapes import make_engine, make_problem
+from test_gpu_shapes import edge_empties, make_engine, make_problem
 
 pytestmark = pytest.mark.gpu
 
@@ -34,13 +34,21 @@ ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 
 
 class Feed(object):
-    """Batches of the given lengths on the device: ids for the NROWS-row table, labels."""
+    """Batches of the given lengths on the device: ids for the NROWS-row table, labels.  F / K: the layout (the default: the
+    module's); empties: edge_empties in every batch; dup: every batch's last column names one row almost everywhere."""
 
-    def __init__(self, lens, seed=5):
+    def __init__(self, lens, seed=5, F=F_, K=K, empties=False, dup=False):
         import torch
-        self.rows, self.fo, ids, y, _, _, _ = make_problem(F_, K, 300, 100, sum(lens), n_rows=NROWS, seed=seed)
+        self.F, self.K, self.seed, self.long = F, K, seed, {}
+        self.rows, self.fo, ids, y, _, _, _ = make_problem(F, K, 300, 100, sum(lens), n_rows=NROWS, seed=seed)
         ids[1, 2] = -1                                                   # an empty field
         cut = np.cumsum([0] + list(lens))
+        for a, b in zip(cut[:-1], cut[1:]):
+            if dup:
+                ids[a:b, F - 1] = ids[a, F - 1]
+            if empties:
+                for t, f in edge_empties(b - a, F):
+                    ids[a + t, f] = -1
         self.ids = [np.ascontiguousarray(ids[a:b]) for a, b in zip(cut[:-1], cut[1:])]
         self.y = [np.ascontiguousarray(y[a:b]) for a, b in zip(cut[:-1], cut[1:])]
         self.dev = torch.device('cuda', 0)
@@ -52,36 +60,46 @@ class Feed(object):
         torch.cuda.synchronize()
         return t
 
-    def table(self, n_rows):
-        """The feed's table cut to, or continued to, n_rows rows (rows beyond NROWS are in no batch)."""
+    def table(self, n_rows, k=None):
+        """The feed's table cut to, or continued to, n_rows rows (rows beyond NROWS are in no batch); another k: its own rows
+        over the same row ids."""
+        k = self.K if k is None else k
+        rows = self.rows if k == self.K else make_problem(self.F, k, 300, 100, 4, n_rows=NROWS, seed=self.seed)[0]
         if n_rows <= NROWS:
-            return self.rows[:n_rows].copy(), self.fo[:n_rows].copy()
-        extra = synth.fm_table(n_rows - NROWS, K, 0.05, 77)
-        return np.concatenate([self.rows, extra]), np.concatenate([self.fo, np.zeros(n_rows - NROWS, np.int32)])
+            return rows[:n_rows].copy(), self.fo[:n_rows].copy()
+        if (n_rows, k) not in self.long:                                 # made once: a 2^20-row table is 46 MB
+            extra = synth.fm_table(n_rows - NROWS, k, 0.05, 77)
+            self.long[(n_rows, k)] = np.concatenate([rows, extra]), np.concatenate([self.fo, np.zeros(n_rows - NROWS, np.int32)])
+        return self.long[(n_rows, k)]
 
 
 class Spec(object):
     """One model of a group: what make_engine takes, the seed of its initial dense tensors and of its masks."""
 
-    def __init__(self, m, prec='bf16', H1=300, H2=100, n_rows=NROWS, max_batch=BMAX, lr=None):
+    def __init__(self, m, prec='bf16', H1=300, H2=100, n_rows=NROWS, max_batch=BMAX, lr=None, F=F_, K=K, reg_all=False, lam1=None):
         self.m, self.prec, self.H1, self.H2, self.n_rows, self.max_batch = m, prec, H1, H2, n_rows, max_batch
+        self.F, self.K, self.reg_all = F, K, reg_all
         self.lr = (0.01, 0.004, 0.02, 0.007, 0.013)[m % 5] if lr is None else lr
-        self.lam1 = (0.02, 0.0, 0.05)[m % 3]
+        self.lam1 = (0.02, 0.0, 0.05)[m % 3] if lam1 is None else lam1
         self.lamfm = (0.1, 0.3, 0.0, 0.05)[m % 4]
         self.acti = ACTS[m % 3]
-        self.p = make_problem(F_, K, H1, H2, 4, n_rows=64, seed=40 + m)[4]
+        self.p = make_problem(F, K, H1, H2, 4, n_rows=64, seed=40 + m)[4]
 
     def engine(self, feed):
-        rows, fo = feed.table(self.n_rows)
-        return make_engine(F_, K, self.H1, self.H2, rows, fo, self.p, prec=self.prec, acti=self.acti, max_batch=self.max_batch,
-                           lr=self.lr, lam1=self.lam1, lamfm=self.lamfm)
+        rows, fo = feed.table(self.n_rows, self.K)
+        return make_engine(self.F, self.K, self.H1, self.H2, rows, fo, self.p, prec=self.prec, acti=self.acti, max_batch=self.max_batch,
+                           lr=self.lr, lam1=self.lam1, lamfm=self.lamfm, reg_all=self.reg_all)
 
     def masks(self, feed, s):
         """The dropout rows of step s, on the device."""
+        r1, r2 = self.host_masks(s)
+        return feed.put(r1), feed.put(r2)
+
+    def host_masks(self, s):
         rng = np.random.RandomState(1000 * self.m + s)
         r1, r2 = (rng.uniform(size=self.H1) < 0.5).astype(np.uint8), (rng.uniform(size=self.H2) < 0.5).astype(np.uint8)
         r1[0] = r2[0] = 1
-        return feed.put(r1), feed.put(r2)
+        return r1, r2
 
 
 def group_step(engs, ids_t, y_t, masks, nxt=None, want_loss=True, b_size=0):

@@ -81,8 +81,10 @@ def make_problem(F, K, H1, H2, B, n_rows=1000, seed=0, dup_col=None, empty=()):
     return rows, fo, ids, y, p, r1, r2
 
 
-def make_engine(F, K, H1, H2, rows, fo, p, prec='f32', acti='tanh', max_batch=4096, lr=0.01, lam1=0.02, lamfm=0.1, w0=-3.0):
-    eng = FNNEngine(F, K, H1, H2, max_batch=max_batch, precision=prec, acti_type=acti, lr=lr, lambda1=lam1, lambda_fm=lamfm)
+def make_engine(F, K, H1, H2, rows, fo, p, prec='f32', acti='tanh', max_batch=4096, lr=0.01, lam1=0.02, lamfm=0.1, w0=-3.0,
+                reg_all=False):
+    eng = FNNEngine(F, K, H1, H2, max_batch=max_batch, precision=prec, acti_type=acti, lr=lr, lambda1=lam1, lambda_fm=lamfm,
+                    reg_all=reg_all)
     eng.set_table(rows, fo, w0)
     eng.set_dense(p)
     return eng
@@ -95,11 +97,11 @@ def lr_for(B):
     return 0.001 if B >= 4096 else 0.01
 
 
-def oracle_step(rows64, p64, ids, y, r1, r2, lr, lam1, lamfm, acti='tanh', w0=-3.0, b_size=None):
+def oracle_step(rows64, p64, ids, y, r1, r2, lr, lam1, lamfm, acti='tanh', w0=-3.0, b_size=None, reg_all=False):
     """One step of the float64 oracle, in place on rows64 / p64: (gx, loss, p_drop, grads)."""
     x = orc.gather_vec(rows64, ids, w0)
     gx, _, loss, p_drop, g = orc.train_call(p64, x, y.astype(np.float64), r1.astype(np.float64), r2.astype(np.float64),
-                                            lr, lam1, acti)
+                                            lr, lam1, acti, reg_all)
     orc.scatter_sgd_vec(rows64, ids, gx, lr, lamfm, b_size)
     return gx, loss, p_drop, g
 
@@ -121,6 +123,30 @@ class Bounds(object):
         print("\n[shapes] %s: worst error %.3f of the bound (%s)" % (label, self.worst, self.where))
 
 
+def compare_step(bd, prec, rows, lr, got_p, got_loss, tab, d, oracle, got_gx=None):
+    """What check_step asserts about one step's outputs, on the Bounds `bd`.  rows: the table before the step; tab / d: the table
+    and fnn_get_dense after it; oracle: (rows64, p64, gx, loss, p_drop, g), the oracle's state after its step and what oracle_step
+    returned.  got_gx None (a call that returns no gx) leaves the gx bound out; every other bound is check_step's."""
+    rows64, p64, gx, loss, p_drop, g = oracle
+    gscale = np.abs(gx).max()
+    if prec == 'bf16':
+        bd.close('p_drop', got_p, p_drop, 0.0, 2e-2)
+        if got_gx is not None:
+            bd.close('gx', got_gx, gx, 0.0, 5e-2 * gscale)
+        bd.close('loss', got_loss, loss, 0.0, 2e-2 * loss)
+        bd.close('table', tab, rows64, 0.0, 5e-2 * np.abs(rows64 - rows).max() + 1e-6)
+    else:
+        tol, tt = (8.0, 40.0) if prec == 'bf16x3' else (1.0, 1.0)
+        bd.close('p_drop', got_p, p_drop, 1e-4 * tol, 1e-6 * tol)
+        if got_gx is not None:
+            bd.close('gx', got_gx, gx, 2e-3 * tol, 2e-5 * gscale * tol + 1e-9)
+        bd.close('loss', got_loss, loss, 0.0, 2e-5 * tol * max(1.0, abs(loss)))
+        bd.close('table', tab, rows64, 1e-5 * tt, 2e-7 * tt)
+        for k in DENSE:
+            bd.close(k, d[k], p64[k], 1e-5 * tol, 1e-3 * lr * np.abs(g[k]).max() * tol + 1e-7)
+        bd.close('b3', d['b3'], p64['b3'], 0.0, 1e-5 * tol)
+
+
 def check_step(eng, prob, lr, lam1, lamfm, prec='f32', acti='tanh', b_size=0, label=''):
     """test_gpu_parity._check_step for any shape, at its bounds (f32: tol 1; bf16x3: tol 8, table 40; bf16: the bounds of
     test_train_step_bf16_vs_oracle): p_drop, gx, the loss, the whole table and every dense tensor."""
@@ -130,22 +156,8 @@ def check_step(eng, prob, lr, lam1, lamfm, prec='f32', acti='tanh', b_size=0, la
     out = eng.train_step(ids, y, r1, r2, b_size=b_size, want_p=True, want_gx=True)
     gx, loss, p_drop, g = oracle_step(rows64, p64, ids, y, r1, r2, lr, lam1, lamfm, acti, b_size=b_size if b_size > 0 else None)
     bd = Bounds()
-    got_p, got_gx, tab, d = out['p'].cpu().numpy(), out['gx'].cpu().numpy(), eng.get_table(), eng.get_dense()
-    gscale = np.abs(gx).max()
-    if prec == 'bf16':
-        bd.close('p_drop', got_p, p_drop, 0.0, 2e-2)
-        bd.close('gx', got_gx, gx, 0.0, 5e-2 * gscale)
-        bd.close('loss', out['loss'], loss, 0.0, 2e-2 * loss)
-        bd.close('table', tab, rows64, 0.0, 5e-2 * np.abs(rows64 - rows).max() + 1e-6)
-    else:
-        tol, tt = (8.0, 40.0) if prec == 'bf16x3' else (1.0, 1.0)
-        bd.close('p_drop', got_p, p_drop, 1e-4 * tol, 1e-6 * tol)
-        bd.close('gx', got_gx, gx, 2e-3 * tol, 2e-5 * gscale * tol + 1e-9)
-        bd.close('loss', out['loss'], loss, 0.0, 2e-5 * tol * max(1.0, abs(loss)))
-        bd.close('table', tab, rows64, 1e-5 * tt, 2e-7 * tt)
-        for k in DENSE:
-            bd.close(k, d[k], p64[k], 1e-5 * tol, 1e-3 * lr * np.abs(g[k]).max() * tol + 1e-7)
-        bd.close('b3', d['b3'], p64['b3'], 0.0, 1e-5 * tol)
+    compare_step(bd, prec, rows, lr, out['p'].cpu().numpy(), out['loss'], eng.get_table(), eng.get_dense(),
+                 (rows64, p64, gx, loss, p_drop, g), got_gx=out['gx'].cpu().numpy())
     bd.report(label)
     return rows64, p64
 
