@@ -66,6 +66,22 @@ def test_wide_step_vs_oracle(built, F, K, H1, H2, B, prec):
         eng.close()
 
 
+# (F, K, H1, H2, B, precision, max_batch): above 4096 keys per field -- N2 = 8192 (k_sort<8>, 256 chunks of the row update per
+# field) and 16384 (k_sort<16>, 512 chunks), and the generic GEMMs on a wide K1p with more than 4096 rows
+STEP_ABOVE_4096 = [(16, 51, 300, 100, 5000, 'f32', 8192), (3, 128, 64, 63, 9000, 'bf16x3', 16384)]
+
+
+@pytest.mark.parametrize("F,K,H1,H2,B,prec,max_batch", STEP_ABOVE_4096, ids=[cid(*c[:6]) + '-of-%d' % c[6] for c in STEP_ABOVE_4096])
+def test_wide_step_above_4096_keys_vs_oracle(built, F, K, H1, H2, B, prec, max_batch):
+    """test_wide_step_vs_oracle's check (check_step at its bounds for the precision) on 5000 and 9000 examples."""
+    prob = make_problem(F, K, H1, H2, B, seed=3 * F + K + B, empty=edge_empties(B, F))
+    eng = make_engine(F, K, H1, H2, prob[0], prob[1], prob[4], prec=prec, max_batch=max_batch, lr=lr_for(B))
+    try:
+        check_step(eng, prob, lr_for(B), 0.02, 0.1, prec=prec, label=cid(F, K, H1, H2, B, prec))
+    finally:
+        eng.close()
+
+
 def test_wide_decay_of_a_row_hit_many_times(built):
     """lambda_fm > 0 with c = 1 - 2 lambda_fm lr / b_size = 0.975: column 3 holds one row in all 200 examples (a segment over
     seven chunks of the row update, c^200 = 0.006), the Zipf columns hold runs of every length.  The table equals the
