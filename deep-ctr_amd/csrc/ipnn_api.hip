@@ -16,6 +16,7 @@
 
 #include "../../include/fnn_hip.h"
 #include "../../include/ipnn_hip.h"
+#include "arg_ring.h"
 #include "fnn_kernels.hip.h"
 #include "sparse_rows.hip.h"
 #include "metrics.hip.h"
@@ -111,8 +112,9 @@ __device__ __forceinline__ void ip_gather16(float* se, const int32_t* __restrict
 }
 
 constexpr int IPF_NT = 512;     // 8 waves: the kernel is bound by instruction issue, two waves per SIMD overlap it (IPNN_IPF_NT=1024: four)
-template <typename T, int NT = IPF_NT, bool WV = false>
-static __global__ __launch_bounds__(NT) void k_ip_fwd(const IpFwdArgs a, T* __restrict__ a0, T* __restrict__ a0T, float* __restrict__ emb)
+// (the body of k_ip_fwd and of its group form k_ip_fwd_g; TL = false: the T layout a0T is not written -- a prediction reads a0 only)
+template <typename T, int NT, bool WV, bool TL = true>
+__device__ __forceinline__ void ip_fwd_body(const IpFwdArgs& a, T* __restrict__ a0, T* __restrict__ a0T, float* __restrict__ emb)
 {
     typedef typename Traits<T>::frag frag;
     constexpr int EPL = Traits<T>::EPL;
@@ -188,11 +190,17 @@ static __global__ __launch_bounds__(NT) void k_ip_fwd(const IpFwdArgs a, T* __re
         for (int x = 0; x < EPL; ++x) fv[x] = (T)sa[r * a.D0p + g * EPL + x];
         store16_sel(a.wt, a0 + ft_off<T>(t0 + r, g * EPL, a.D0p), fv);
     }
+    if (!TL) return;
     for (int e = tid; e < a.D0p * 4; e += NT) {
         const int c = e >> 2, tq = e & 3;
         store4_sel(a.wt, a0T + ft_off<T>(c, t0 + 4 * tq, a.ldT), sa[(4 * tq) * a.D0p + c], sa[(4 * tq + 1) * a.D0p + c],
                   sa[(4 * tq + 2) * a.D0p + c], sa[(4 * tq + 3) * a.D0p + c]);
     }
+}
+template <typename T, int NT = IPF_NT, bool WV = false>
+static __global__ __launch_bounds__(NT) void k_ip_fwd(const IpFwdArgs a, T* __restrict__ a0, T* __restrict__ a0T, float* __restrict__ emb)
+{
+    ip_fwd_body<T, NT, WV>(a, a0, a0T, emb);
 }
 
 // Inner-product layer, backward: dz1' [Ba][D0p] f32 (already times mask/keep and act') ->
@@ -300,8 +308,8 @@ inline size_t ipw_bwd_lds(int F, int rw, int P, bool wv) { return (size_t)IPW_EX
 
 // WV (value weights, here and in k_ip_bwd_w / k_ip_fwd_m / k_ip_bwd_m): as in ip_gather16 and k_ip_bwd -- every 16-byte piece of a
 // gathered row is scaled by wts[t][f] before it goes to the tile and to emb; the backward scales its finished gradient once.
-template <typename T, bool WV = false>
-static __global__ __launch_bounds__(256) void k_ip_fwd_w(const IpWideArgs a, T* __restrict__ a0, T* __restrict__ a0T, float* __restrict__ emb)
+template <typename T, bool WV, bool TL = true>
+__device__ __forceinline__ void ip_fwd_w_body(const IpWideArgs& a, T* __restrict__ a0, T* __restrict__ a0T, float* __restrict__ emb)
 {
     typedef typename Traits<T>::frag frag;
     constexpr int EPL = Traits<T>::EPL;
@@ -397,8 +405,13 @@ static __global__ __launch_bounds__(256) void k_ip_fwd_w(const IpWideArgs a, T* 
         for (int x = 0; x < EPL; ++x)                           // T layout: a column's examples are consecutive k
 #pragma unroll
             for (int r = 0; r < IPW_EX; r += 4)
-                ipw_store4(a.wt, r_a0T, a0T, ft_off<T>(g * EPL + x, t0 + r, a.ldT), v[r][x], v[r + 1][x], v[r + 2][x], v[r + 3][x]);
+                if (TL) ipw_store4(a.wt, r_a0T, a0T, ft_off<T>(g * EPL + x, t0 + r, a.ldT), v[r][x], v[r + 1][x], v[r + 2][x], v[r + 3][x]);
     }
+}
+template <typename T, bool WV = false>
+static __global__ __launch_bounds__(256) void k_ip_fwd_w(const IpWideArgs a, T* __restrict__ a0, T* __restrict__ a0T, float* __restrict__ emb)
+{
+    ip_fwd_w_body<T, WV>(a, a0, a0T, emb);
 }
 
 // Wide backward: gx'[t][f rw + l] = dz[t][f rw + l] + sum_j dz[t][pair(f, j)] e_j[l] (l < k; pad columns 0), and the per-workgroup
@@ -483,8 +496,8 @@ struct IpManyArgs {
 inline size_t ipm_fwd_lds(int F) { return (size_t)IPM_EX * F * (SLOT + 1) * sizeof(float); }
 inline size_t ipm_bwd_lds(int F, int P, bool wv) { return (size_t)IPM_BEX * (F * SLOT + P + (wv ? F : 0)) * sizeof(float); }
 
-template <typename T, bool WV = false>
-static __global__ __launch_bounds__(256) void k_ip_fwd_m(const IpManyArgs a, T* __restrict__ a0, T* __restrict__ a0T, float* __restrict__ emb)
+template <typename T, bool WV, bool TL = true>
+__device__ __forceinline__ void ip_fwd_m_body(const IpManyArgs& a, T* __restrict__ a0, T* __restrict__ a0T, float* __restrict__ emb)
 {
     typedef typename Traits<T>::frag frag;
     constexpr int EPL = Traits<T>::EPL, SP = SLOT + 1;
@@ -574,8 +587,13 @@ static __global__ __launch_bounds__(256) void k_ip_fwd_m(const IpManyArgs a, T* 
         for (int x = 0; x < EPL; ++x)                           // T layout: a column's examples are consecutive k
 #pragma unroll
             for (int r = 0; r < IPM_EX; r += 4)
-                ipw_store4(a.wt, r_a0T, a0T, ft_off<T>(g * EPL + x, t0 + r, a.ldT), v[r][x], v[r + 1][x], v[r + 2][x], v[r + 3][x]);
+                if (TL) ipw_store4(a.wt, r_a0T, a0T, ft_off<T>(g * EPL + x, t0 + r, a.ldT), v[r][x], v[r + 1][x], v[r + 2][x], v[r + 3][x]);
     }
+}
+template <typename T, bool WV = false>
+static __global__ __launch_bounds__(256) void k_ip_fwd_m(const IpManyArgs a, T* __restrict__ a0, T* __restrict__ a0T, float* __restrict__ emb)
+{
+    ip_fwd_m_body<T, WV>(a, a0, a0T, emb);
 }
 
 // Many-field backward: gx'[t][16 f + l] = dz[t][16 f + l] + sum_{j != f} dz[t][pair(f, j)] e_j[l] (l < k; pad columns 0) and the
@@ -1258,6 +1276,55 @@ static __global__ __launch_bounds__(64 * NW) void k_ip_strip_tail(const StripFwd
     strip_bwd_body<T, 1, NF, NW>(ba, maxD);
 }
 
+// ------------------------------------------------------------------------------------------
+// Group forms (ipnn_predict_multi / ipnn_eval_multi): the prediction of several handles on one feed batch in two launches with
+// the MODEL as blockIdx.y.  A workgroup reads its member's arguments from a device array (IpGroupArg, sent through hs[0]'s
+// ArgRing) and runs the solo kernels' bodies on them: blockIdx.x stays the example tile / the strip, so the bodies are the solo
+// kernels' own.  The gather writes the F layout of the member's a[0] only (TL = false); the strip launch is the
+// one-workgroup-per-strip form over the whole stack (duo.on = 0: a grid of strips x models exceeds the chip, so no workgroup
+// may wait for another -- no swap, no flag).  warm = 0: the arguments are not in the kernel argument segment here.
+// ------------------------------------------------------------------------------------------
+template <typename T> struct IpGroupArg {
+    int* err; int model;                                         // the member's error word and its position in the call (k_ip_gflags)
+    IpFwdArgs f; IpManyArgs m; IpWideArgs w;                     // the one its row kind takes
+    T* a0;                                                       // the member's a[0]: the hand-off between the two launches
+    StripFwdArgs<T> s;
+};
+template <typename T, int NT, bool WV>
+static __global__ __launch_bounds__(NT) void k_ip_fwd_g(const IpGroupArg<T>* __restrict__ g)
+{
+    const IpFwdArgs a = g[blockIdx.y].f;
+    ip_fwd_body<T, NT, WV, false>(a, g[blockIdx.y].a0, nullptr, nullptr);
+}
+template <typename T, bool WV>
+static __global__ __launch_bounds__(256) void k_ip_fwd_m_g(const IpGroupArg<T>* __restrict__ g)
+{
+    const IpManyArgs a = g[blockIdx.y].m;
+    ip_fwd_m_body<T, WV, false>(a, g[blockIdx.y].a0, nullptr, nullptr);
+}
+template <typename T, bool WV>
+static __global__ __launch_bounds__(256) void k_ip_fwd_w_g(const IpGroupArg<T>* __restrict__ g)
+{
+    const IpWideArgs a = g[blockIdx.y].w;
+    ip_fwd_w_body<T, WV, false>(a, g[blockIdx.y].a0, nullptr, nullptr);
+}
+template <typename T, int RT>
+static __global__ __launch_bounds__(64 * STRIP_NW) void k_ip_strip_fwd_g(const IpGroupArg<T>* __restrict__ g, const int maxD)
+{
+    strip_fwd_body<T, RT, 4, STRIP_NW>(g[blockIdx.y].s, maxD);
+}
+// The range bits (bit 1 of each member's error word) of the n members behind `args` (element stride `elem` bytes: both element
+// types share the header) into flags[their position], then cleared.  One workgroup; no handle is listed twice.
+static __global__ __launch_bounds__(256) void k_ip_gflags(const char* __restrict__ args, const size_t elem, const int n, int* __restrict__ flags)
+{
+    for (int i = threadIdx.x; i < n; i += 256) {
+        const IpGroupArg<float>* g = reinterpret_cast<const IpGroupArg<float>*>(args + (size_t)i * elem);
+        const int f = *g->err & 1;
+        flags[g->model] = f;
+        if (f) atomicAnd(g->err, ~1);
+    }
+}
+
 // Keep-masks [B][d] uint8 (the ABI's layout, reference column order) -> [Dp][ldT] uint8, zero padded,
 // for every layer in one launch; layer 0's columns are mapped to the slot layout on the way.
 struct MaskTArgs {
@@ -1612,6 +1679,10 @@ struct ipnn_handle {
     long long* stamps = nullptr;                     // IPNN_STAMPS: [2][Ba/16][16] time stamps of the strip kernels
     unsigned long long* duo_xch = nullptr; int* duo_flags = nullptr; int duo_epoch = 0; size_t duo_xch_wg = 0; int n_cu = 256;
     bool duo_failed = false;                         // a pair gave up once: every later train step is refused until the handle is re-created
+    // ipnn_predict_multi / ipnn_eval_multi, used when this handle is hs[0]: the argument ring, the event that joins the members'
+    // streams, and the scratch of one group of models (predictions, metric pass, results), kept while it is large enough
+    ArgRing eval_ring{sizeof(IpGroupArg<float>), 4 * IPNN_EVAL_MAX_MODELS};
+    hipEvent_t gjoin = nullptr; char* ev_scratch = nullptr; size_t ev_scratch_bytes = 0;
     std::map<std::string, std::vector<std::pair<hipEvent_t, hipEvent_t>>> prof_ev;
 };
 
@@ -1761,6 +1832,15 @@ template <typename T> IpKernel ip_gather_fwd_sel(IpRows rows, bool wv, int nt)
     if (nt == 1024) return wv ? IP_K(1024, k_ip_fwd<T, 1024, true>) : IP_K(1024, k_ip_fwd<T, 1024>);
     return wv ? IP_K(IPF_NT, k_ip_fwd<T, IPF_NT, true>) : IP_K(IPF_NT, k_ip_fwd<T>);
 }
+// the group forms (ipnn_predict_multi / ipnn_eval_multi): the gather of a row kind, and the whole stack on single strips
+template <typename T> IpKernel ip_gather_fwd_g_sel(IpRows rows, bool wv, int nt)
+{
+    if (rows == IP_WIDE) return wv ? IP_K(256, k_ip_fwd_w_g<T, true>) : IP_K(256, k_ip_fwd_w_g<T, false>);
+    if (rows == IP_MANY) return wv ? IP_K(256, k_ip_fwd_m_g<T, true>) : IP_K(256, k_ip_fwd_m_g<T, false>);
+    if (nt == 1024) return wv ? IP_K(1024, k_ip_fwd_g<T, 1024, true>) : IP_K(1024, k_ip_fwd_g<T, 1024, false>);
+    return wv ? IP_K(IPF_NT, k_ip_fwd_g<T, IPF_NT, true>) : IP_K(IPF_NT, k_ip_fwd_g<T, IPF_NT, false>);
+}
+template <typename T> IpKernel ip_strip_g_sel() { return IP_K(64 * STRIP_NW, k_ip_strip_fwd_g<T, sizeof(T) == 2 ? 2 : 1>); }
 IpKernel ip_gather_bwd_sel(IpRows rows, bool wv)
 {
     if (rows == IP_WIDE) return wv ? IP_K(256, k_ip_bwd_w<true>) : IP_K(256, k_ip_bwd_w<false>);
@@ -1781,8 +1861,10 @@ template <typename T> int ip_opt_in(ipnn_handle* h)
     IHK(h, set(ip_strip_tail_sel<T>(), 160));
     for (IpRows r : {IP_NARROW, IP_WIDE, IP_MANY}) for (int wv = 0; wv < 2; ++wv) {
         for (int nt : {512, 1024}) IHK(h, set(ip_gather_fwd_sel<T>(r, wv != 0, nt), ip_rows_lds_kib(r)));
+        for (int nt : {512, 1024}) IHK(h, set(ip_gather_fwd_g_sel<T>(r, wv != 0, nt), ip_rows_lds_kib(r)));
         IHK(h, set(ip_gather_bwd_sel(r, wv != 0), ip_rows_lds_kib(r)));
     }
+    IHK(h, set(ip_strip_g_sel<T>(), RT == 2 ? 128 : 160));
     return FNN_OK;
 }
 
@@ -2309,6 +2391,212 @@ int ip_run(ipnn_handle* h, IpCall c)
     return FNN_OK;
 }
 
+// --------------------------------------------------------------------------------------------- many models on one feed
+// ipnn_predict_multi / ipnn_eval_multi ("Evaluating many inner-product models").  The group of one call:
+// its refusals (the entry point's name in front, left with hs[0], or with ipnn_last_error(NULL) without a usable hs[0]) and
+// its streams -- everything runs on hs[0]'s, which first waits for every other member's; they wait for the call's last launch.
+struct IpGroup {
+    ipnn_handle* const* hs; int n; ipnn_handle* h0; const char* name;
+    std::vector<hipStream_t> others;                 // the streams that are not hs[0]'s, each once
+    bool entered = false;
+    IpGroup(ipnn_handle* const* hs_, int n_, const char* name_)
+        : hs(hs_), n(n_), h0(hs_ && n_ >= 1 && n_ <= IPNN_EVAL_MAX_MODELS ? hs_[0] : nullptr), name(name_) {}
+    ~IpGroup() { leave(); }
+    int refuse(int code, const std::string& msg) const { (h0 ? h0->err : g_ip_err) = std::string(name) + ": " + msg; return code; }
+    static std::string at(const std::string& what, int m) { return "model " + std::to_string(m) + ": " + what; }
+    int enter()
+    {
+        IHK(h0, hipSetDevice(h0->dev));
+        // a member's deferred dense update and sparse-row chain (IPNN_UPDATE_SIDE=1) join its own stream first
+        for (int m = 0; m < n; ++m) {
+            const int rc = ip_join(hs[m]);
+            if (rc != FNN_OK) { if (hs[m] != h0) refuse(rc, at(hs[m]->err, m)); return rc; }
+        }
+        for (int m = 1; m < n; ++m) if (hs[m]->st != h0->st) others.push_back(hs[m]->st);
+        std::sort(others.begin(), others.end());
+        others.erase(std::unique(others.begin(), others.end()), others.end());
+        if (!others.empty() && !h0->gjoin) IHK(h0, hipEventCreateWithFlags(&h0->gjoin, hipEventDisableTiming));
+        entered = true;
+        for (hipStream_t o : others) {
+            IHK(h0, hipEventRecord(h0->gjoin, o));
+            IHK(h0, hipStreamWaitEvent(h0->st, h0->gjoin, 0));
+        }
+        return FNN_OK;
+    }
+    int leave()
+    {
+        if (!entered) return FNN_OK;
+        entered = false;
+        if (others.empty()) return FNN_OK;
+        IHK(h0, hipEventRecord(h0->gjoin, h0->st));
+        for (hipStream_t o : others) IHK(h0, hipStreamWaitEvent(o, h0->gjoin, 0));
+        return FNN_OK;
+    }
+};
+
+// What both calls refuse, all of it before anything is launched or written.
+int ip_group_check(const IpGroup& g, const int32_t* ids, bool need_y, const int32_t* y, int64_t N, bool need_p, float* const* p_out)
+{
+    ipnn_handle* const* hs = g.hs;
+    const int M = g.n;
+    if (!hs) return g.refuse(FNN_ERR_ARG, "null hs");
+    if (M < 1 || M > IPNN_EVAL_MAX_MODELS) return g.refuse(FNN_ERR_ARG, "n_models must be in [1, " + std::to_string(IPNN_EVAL_MAX_MODELS) + "]");
+    for (int m = 0; m < M; ++m) if (!hs[m]) return g.refuse(FNN_ERR_ARG, g.at("null handle", m));
+    const ipnn_handle* h0 = g.h0;
+    for (int m = 1; m < M; ++m)
+        if (hs[m]->F != h0->F || hs[m]->dev != h0->dev) return g.refuse(FNN_ERR_ARG, g.at("n_fields or device differs from model 0's", m));
+    if (!ids) return g.refuse(FNN_ERR_ARG, "null ids");
+    if (need_y && !y) return g.refuse(FNN_ERR_ARG, "null y");
+    if (need_p && !p_out) return g.refuse(FNN_ERR_ARG, "null p_out");
+    if (need_p) for (int m = 0; m < M; ++m) if (!p_out[m]) return g.refuse(FNN_ERR_ARG, g.at("null p_out", m));
+    if (N < 1 || N > ((int64_t)1 << 30)) return g.refuse(FNN_ERR_ARG, "N must be in [1, 2^30]");
+    {   // a member's a[0] is the scratch of the group launch: no handle twice
+        std::vector<std::pair<const ipnn_handle*, int>> v;
+        for (int m = 0; m < M; ++m) v.emplace_back(hs[m], m);
+        std::sort(v.begin(), v.end());
+        int bi = -1, bj = -1;                                    // the pair with the smallest second index
+        for (int i = 0; i + 1 < M; ++i)
+            if (v[i].first == v[i + 1].first && (bj < 0 || v[i + 1].second < bj)) { bi = v[i].second; bj = v[i + 1].second; }
+        if (bj >= 0) return g.refuse(FNN_ERR_ARG, g.at("the same handle as model " + std::to_string(bi) + " (a handle's own buffers are the group launch's scratch: list it once)", bj));
+    }
+    for (int m = 0; m < M; ++m) if (!hs[m]->table16) return g.refuse(FNN_ERR_STATE, g.at("ipnn_set_table has not been called", m));
+    return FNN_OK;
+}
+
+// The members that one pair of group launches serves: a prediction LAUNCH CLASS -- element type, depth, padded widths, the
+// gather's row kind (with its block size, and the row width of wide rows: they size its LDS), pairs, weights given or not.
+// Activation, k, table size and every parameter value may differ inside a class.  members: positions in the list, in its order.
+struct IpPredClass {
+    bool bf16; int L; int Dp[STRIP_MAXP + 1]; IpRows rows; int nt, rw, P; bool wv;
+    std::vector<int> members;
+    bool same(const IpPredClass& o) const
+    {
+        if (bf16 != o.bf16 || L != o.L || rows != o.rows || nt != o.nt || rw != o.rw || P != o.P || wv != o.wv) return false;
+        for (int t = 0; t <= L + 1; ++t) if (Dp[t] != o.Dp[t]) return false;
+        return true;
+    }
+};
+IpPredClass ip_pred_class_of(const ipnn_handle* h, bool wv)
+{
+    IpPredClass c{};
+    c.bf16 = h->bf16; c.L = h->L; c.rows = ip_fwd_rows(h); c.nt = c.rows == IP_NARROW ? h->kn.ipf_nt : 256; c.rw = h->rw; c.P = h->P; c.wv = wv;
+    for (int t = 0; t <= h->L + 1; ++t) c.Dp[t] = h->Dp[t];
+    return c;
+}
+// a member's arguments of both group launches for one feed batch (c: the batch as a prediction call, formed)
+template <typename T> void ip_fill_group_arg(const ipnn_handle* h, int model, const IpCall& c, void* dst)
+{
+    static_assert(sizeof(IpGroupArg<T>) == sizeof(IpGroupArg<float>), "one ring element for both element types");
+    IpGroupArg<T> g{};
+    g.err = h->err_flag; g.model = model; g.a0 = (T*)h->a[0];
+    const IpRows rows = ip_fwd_rows(h);
+    if (rows == IP_WIDE) g.w = ip_wide_args(h, c, nullptr, 1.0f);
+    else if (rows == IP_MANY) g.m = ip_many_args(h, c, nullptr, 1.0f);
+    else g.f = IpFwdArgs{h->P, c.ids, c.B, h->F, h->K, h->table16, h->n_rows, h->b, nullptr, h->d[0],
+                         1.0f, h->cfg.act, h->Dp[0], h->ldT, h->err_flag, h->kn.fwd_skip, h->kn.wt, c.wts};
+    StripFwdArgs<T>& sa = g.s;
+    const int L = h->L;
+    sa.a0 = (const T*)h->a[0]; sa.n = L + 1;
+    for (int t = 0; t <= L + 1; ++t) sa.Dp[t] = h->Dp[t];
+    for (int t = 1; t <= L + 1; ++t) sa.W[t - 1] = (const T*)h->wf[t - 1];
+    for (int t = 1; t <= L; ++t) { sa.ef[t - 1] = ip_epi_fwd<T>(h, c, t, false); sa.ef[t - 1].outT = nullptr; }   // nobody reads a prediction's transposed activations
+    sa.eo = ip_epi_out<T>(h, c);
+    sa.dbg = nullptr; sa.rot = h->kn.strip_rot; sa.sel = -1; sa.has_out = 1; sa.finalF = nullptr; sa.warm = 0;
+    for (int t = 0; t < STRIP_MAXP; ++t) sa.wlds[t] = -1;
+    sa.duo = StripDuo{0, nullptr, nullptr, 0, h->err_flag, 0, h->kn.duo_min};
+    memcpy(dst, &g, sizeof(g));
+}
+template <typename... A> hipError_t ip_launch2(const IpKernel& k, dim3 grid, size_t lds, hipStream_t s, const A&... args)
+{
+    void* p[] = {const_cast<void*>(static_cast<const void*>(&args))...};
+    return hipLaunchKernel(k.fn, grid, dim3((unsigned)k.threads), p, lds, s);
+}
+// one class's two launches for a feed batch of Ba padded lines: the gather with its inner products, then the whole stack
+template <typename T> hipError_t ip_launch_class(const ipnn_handle* h, const IpPredClass& c, const void* dev_args, int Ba, hipStream_t st)
+{
+    constexpr int RT = sizeof(T) == 2 ? 2 : 1;
+    const IpGroupArg<T>* d = static_cast<const IpGroupArg<T>*>(dev_args);
+    const unsigned M = (unsigned)c.members.size();
+    const int ex = c.rows == IP_WIDE ? IPW_EX : c.rows == IP_MANY ? IPM_EX : 16;
+    const size_t lds = c.rows == IP_WIDE ? ipw_fwd_lds(h->F, h->rw) : c.rows == IP_MANY ? ipm_fwd_lds(h->F) : ip16_lds(h->F, h->Dp[0]);
+    hipError_t e = ip_launch2(ip_gather_fwd_g_sel<T>(c.rows, c.wv, c.nt), dim3((unsigned)(Ba / ex), M), lds, st, d);
+    if (e != hipSuccess) return e;
+    const int maxD = h->plan.maxD;
+    return ip_launch2(ip_strip_g_sel<T>(), dim3((unsigned)(Ba / (16 * RT)), M), h->plan.strip_lds, st, d, maxD);
+}
+
+// The predictions of the n members hs[0 .. n) of group `g` (positions base .. in the call) on the N lines, p[m] each.  Members on
+// the strip kernels: per feed batch -- as many lines as the smallest member's buffers hold, at most 4096, a multiple of 256 --
+// their arguments through hs[0]'s ring and two launches per launch class.  Then the members off the strips (a layer too wide for
+// the tiles, IPNN_STRIP=0), one after the other in chunks of their own max_batch, their stream swapped for the group's.
+// (all_own: every member runs its own launches -- a single model, whose solo forms fill the chip better than one model's strips)
+int ip_group_forward(const IpGroup& g, ipnn_handle* const* hs, int n, int base, const int32_t* ids, const float* wts, int64_t N, float* const* p,
+                     bool all_own = false)
+{
+    ipnn_handle* h0 = g.h0;
+    const hipStream_t st = h0->st;
+    const int F = h0->F;
+    std::vector<IpPredClass> cls;
+    std::vector<int> own;
+    int fb = 4096, ng = 0;
+    for (int m = 0; m < n; ++m) {
+        if (all_own || !hs[m]->plan.strip) { own.push_back(m); continue; }
+        const IpPredClass c = ip_pred_class_of(hs[m], wts != nullptr);
+        size_t i = 0;
+        while (i < cls.size() && !cls[i].same(c)) ++i;
+        if (i == cls.size()) cls.push_back(c);
+        cls[i].members.push_back(m);
+        fb = std::min(fb, hs[m]->ldT); ++ng;
+    }
+    const size_t elem = h0->eval_ring.elem;
+    for (int64_t lo = 0; ng && lo < N; lo += fb) {
+        const int B = (int)std::min<int64_t>(fb, N - lo);
+        size_t slot = 0;
+        IHK(h0, ring_take(h0->eval_ring, (size_t)ng, &slot));
+        char* a = static_cast<char*>(h0->eval_ring.host) + slot * elem;
+        const char* d = static_cast<const char*>(h0->eval_ring.dev) + slot * elem;
+        size_t pos = 0;
+        int Ba = 0;
+        for (const IpPredClass& c : cls) for (int m : c.members) {
+            ipnn_handle* h = hs[m];
+            IpCall call{ids + lo * F, wts ? wts + lo * F : nullptr, nullptr, B, nullptr, nullptr, nullptr, p[m] + lo, false};
+            ip_form(h, call);
+            Ba = call.Ba;
+            if (h->bf16) ip_fill_group_arg<bf16_t>(h, base + m, call, a + pos * elem); else ip_fill_group_arg<float>(h, base + m, call, a + pos * elem);
+            ++pos;
+        }
+        IHK(h0, ring_send(h0->eval_ring, slot, (size_t)ng, st));
+        pos = 0;
+        for (const IpPredClass& c : cls) {
+            const ipnn_handle* h = hs[c.members[0]];
+            IHK(h0, c.bf16 ? ip_launch_class<bf16_t>(h, c, d + pos * elem, Ba, st) : ip_launch_class<float>(h, c, d + pos * elem, Ba, st));
+            pos += c.members.size();
+        }
+    }
+    IHK(h0, hipGetLastError());
+    for (int m : own) {
+        ipnn_handle* h = hs[m];
+        const hipStream_t mine = h->st;
+        h->st = st;
+        int rc = FNN_OK;
+        for (int64_t lo = 0; rc == FNN_OK && lo < N; lo += h->Bmax) {
+            const int B = (int)std::min<int64_t>(h->Bmax, N - lo);
+            const IpCall call{ids + lo * F, wts ? wts + lo * F : nullptr, nullptr, B, nullptr, nullptr, nullptr, p[m] + lo, false};
+            rc = h->bf16 ? ip_run<bf16_t>(h, call) : ip_run<float>(h, call);
+        }
+        h->st = mine;
+        if (rc != FNN_OK) { if (h != h0) g.refuse(rc, g.at(h->err, base + m)); return rc; }
+    }
+    return FNN_OK;
+}
+
+inline size_t up256(size_t b) { return (b + 255) / 256 * 256; }
+// scratch of a group of g models: p [g][N], the metric pass's, out [g], flags [g], n_pos
+size_t ip_eval_scratch_bytes(int g, int64_t N)
+{
+    return up256((size_t)g * (size_t)N * 4) + up256(metrics_multi_bytes(g, N)) + up256((size_t)g * sizeof(MetricOut)) + up256((size_t)g * 4) + 256;
+}
+
 }  // namespace
 
 extern "C" {
@@ -2438,6 +2726,9 @@ int ipnn_destroy(ipnn_handle* h)
     void* ptrs[] = {h->mask0, h->table16, h->noshare, h->b, h->emb, h->dz0, h->gxp, h->gb_part, h->loss_t, h->loss_dev, h->slab, h->ref0, h->ptab, h->err_flag,
                     h->skeys, h->cpow1, h->duo_xch, h->duo_flags};
     for (void* p : ptrs) if (p) hipFree(p);
+    if (h->ev_scratch) hipFree(h->ev_scratch);
+    ring_release(h->eval_ring);
+    if (h->gjoin) hipEventDestroy(h->gjoin);
     row_group_free(h->rg);
     for (auto& kv : h->prof_ev) for (auto& p : kv.second) { hipEventDestroy(p.first); hipEventDestroy(p.second); }
     if (h->st2) { hipStreamSynchronize(h->st2); hipStreamDestroy(h->st2); }
@@ -2656,31 +2947,166 @@ int ipnn_eval(ipnn_handle* h, const int32_t* ids, const int32_t* y, int64_t N, d
     return ipnn_eval_w(h, ids, nullptr, y, N, auc, rmse, logloss);
 }
 
-int ipnn_eval_w(ipnn_handle* h, const int32_t* ids, const float* wts, const int32_t* y, int64_t N, double* auc, double* rmse, double* logloss)
+// One handle's evaluation pass up to its metrics: the predictions in chunks of max_batch -- into p_keep (DEVICE, [N]) when given,
+// else into a buffer of the call's own -- and device_metrics on them (*mrc: its verdict, -2 / -3 with *merr; -1 is returned here)
+static int ip_eval_solo(ipnn_handle* h, const int32_t* ids, const float* wts, const int32_t* y, int64_t N, float* p_keep, double out[4],
+                        int* mrc, std::string* merr)
 {
-    if (!h || !ids || !y || N < 1) return FNN_ERR_ARG;
-    if (!h->table16) IFAIL(h, FNN_ERR_STATE, "ipnn_set_table has not been called");
     IHK(h, hipSetDevice(h->dev));
-    float* p_d = nullptr;
-    IHK(h, hipMalloc((void**)&p_d, (size_t)N * 4));
+    float* p_d = p_keep;
+    if (!p_d) IHK(h, hipMalloc((void**)&p_d, (size_t)N * 4));
     for (int64_t lo = 0; lo < N; lo += h->Bmax) {
         const int B = (int)(N - lo < h->Bmax ? N - lo : h->Bmax);
         const float* w = wts ? wts + lo * h->F : nullptr;        // the chunk's weights travel with its ids
         const IpCall c{ids + lo * h->F, w, nullptr, B, nullptr, nullptr, nullptr, p_d + lo, false};
         const int rc = h->bf16 ? ip_run<bf16_t>(h, c) : ip_run<float>(h, c);
-        if (rc != FNN_OK) { hipFree(p_d); return rc; }
+        if (rc != FNN_OK) { if (!p_keep) hipFree(p_d); return rc; }
     }
+    *mrc = device_metrics(h->st, p_d, y, N, out, *merr);
+    if (!p_keep) hipFree(p_d);
+    if (*mrc == -1) IFAIL(h, FNN_ERR_HIP, *merr);
+    return FNN_OK;
+}
+
+int ipnn_eval_w(ipnn_handle* h, const int32_t* ids, const float* wts, const int32_t* y, int64_t N, double* auc, double* rmse, double* logloss)
+{
+    if (!h || !ids || !y || N < 1) return FNN_ERR_ARG;
+    if (!h->table16) IFAIL(h, FNN_ERR_STATE, "ipnn_set_table has not been called");
     double out[4] = {0, 0, 0, 0};
     std::string merr;
-    const int mrc = device_metrics(h->st, p_d, y, N, out, merr);
-    hipFree(p_d);
-    if (mrc == -1) IFAIL(h, FNN_ERR_HIP, merr);
+    int mrc = 0;
+    IRC(ip_eval_solo(h, ids, wts, y, N, nullptr, out, &mrc, &merr));
     if (auc) *auc = out[0];
     if (rmse) *rmse = out[1];
     if (logloss) *logloss = out[2];
     const int rc = ipnn_sync(h);
     if (rc != FNN_OK) return rc;
     if (mrc == -2 || mrc == -3) IFAIL(h, FNN_ERR_RANGE, merr);
+    return FNN_OK;
+}
+
+// The predictions of several handles on one feed: per feed batch and prediction launch class two launches with the model as a
+// grid dimension.  Nothing is allocated after hs[0]'s first group call, nothing synchronises; an id outside a member's table shows
+// at that member's ipnn_sync.
+int ipnn_predict_multi(ipnn_handle* const* hs, int n_models, const int32_t* ids, const float* wts, int64_t N, float* const* p_out)
+{
+    IpGroup g(hs, n_models, "ipnn_predict_multi");
+    IRC(ip_group_check(g, ids, false, nullptr, N, true, p_out));
+    IRC(g.enter());
+    IRC(ip_group_forward(g, hs, n_models, 0, ids, wts, N, p_out, n_models == 1));
+    return g.leave();
+}
+
+// ... and their metrics: the models in groups of as many as fit $IPNN_EVAL_SCRATCH_BYTES (read per call; default 2^30, one model
+// at the least); per group the predictions, one metrics_multi pass over them, the range flags, one copy home, one synchronisation.
+int ipnn_eval_multi(ipnn_handle* const* hs, int n_models, const int32_t* ids, const float* wts, const int32_t* y, int64_t N,
+                    double* auc, double* rmse, double* logloss, int* status, float* const* p_out)
+{
+    IpGroup g(hs, n_models, "ipnn_eval_multi");
+    IRC(ip_group_check(g, ids, true, y, N, false, nullptr));
+    ipnn_handle* h0 = g.h0;
+    if (n_models == 1) {
+        // one model: the solo evaluation (measured: the group path is not faster there -- profiles/ipnn_eval_multi_bench.json --
+        // and the solo strip forms fill the chip better), reported as the group path reports
+        double out[4] = {0, 0, 0, 0};
+        std::string merr, msg;
+        int mrc = 0;
+        IRC(ip_eval_solo(h0, ids, wts, y, N, p_out ? p_out[0] : nullptr, out, &mrc, &merr));
+        const double nan = std::nan("");
+        if (auc) auc[0] = (mrc == -2 || mrc == -3) ? nan : out[0];
+        if (rmse) rmse[0] = mrc == -3 ? nan : out[1];
+        if (logloss) logloss[0] = mrc == -3 ? nan : out[2];
+        if (status) status[0] = mrc == -3 ? FNN_ERR_RANGE : FNN_OK;
+        const int rc = ipnn_sync(h0);
+        if (rc != FNN_OK && rc != FNN_ERR_RANGE) return rc;
+        if (mrc == -3) msg += "predictions NaN or outside [0, 1] in model(s) 0";
+        if (rc == FNN_ERR_RANGE) msg += std::string(msg.empty() ? "" : "; ") + "feature id outside [0, n_rows) in model(s) 0";
+        if (mrc == -2) msg += std::string(msg.empty() ? "" : "; ") + "only one class present in y (roc_auc_score raises ValueError)";
+        if (!msg.empty()) return g.refuse(FNN_ERR_RANGE, msg);
+        return FNN_OK;
+    }
+    size_t cap = (size_t)1 << 30;
+    if (const char* e = getenv("IPNN_EVAL_SCRATCH_BYTES")) { const long long c = atoll(e); if (c >= 1) cap = (size_t)c; }
+    int G = n_models;
+    {
+        const size_t one = ip_eval_scratch_bytes(1, N);
+        if ((size_t)G > cap / one) G = (int)(cap / one);
+        if (G < 1) G = 1;
+        while (G > 1 && ip_eval_scratch_bytes(G, N) > cap) --G;
+    }
+    IRC(g.enter());
+    const hipStream_t st = h0->st;
+    const size_t need = ip_eval_scratch_bytes(G, N);
+    if (h0->ev_scratch_bytes < need) {                                // (the last user of the old one, an earlier call, has synchronised)
+        if (h0->ev_scratch) { hipFree(h0->ev_scratch); h0->ev_scratch = nullptr; h0->ev_scratch_bytes = 0; }
+        IHK(h0, hipMalloc((void**)&h0->ev_scratch, need));
+        h0->ev_scratch_bytes = need;
+    }
+    char* scratch = h0->ev_scratch;
+    float* p_d = reinterpret_cast<float*>(scratch);
+    char* ms = scratch + up256((size_t)G * (size_t)N * 4);
+    MetricOut* out_d = reinterpret_cast<MetricOut*>(ms + up256(metrics_multi_bytes(G, N)));
+    int* flags_d = reinterpret_cast<int*>(reinterpret_cast<char*>(out_d) + up256((size_t)G * sizeof(MetricOut)));
+    unsigned long long* npos_d = reinterpret_cast<unsigned long long*>(reinterpret_cast<char*>(flags_d) + up256((size_t)G * 4));
+    std::vector<MetricOut> ho(G);
+    std::vector<int> hf(G);
+    std::vector<float*> pp(G);
+    unsigned long long n_pos = 0;
+    std::string bad, range;
+    const size_t elem = h0->eval_ring.elem;
+    auto groups = [&]() -> int {
+        for (int g0 = 0; g0 < n_models; g0 += G) {
+            const int n = std::min(G, n_models - g0);
+            for (int m = 0; m < n; ++m) pp[m] = p_d + (size_t)m * (size_t)N;
+            IRC(ip_group_forward(g, hs + g0, n, g0, ids, wts, N, pp.data()));
+            IHK(h0, metrics_multi(st, p_d, y, N, n, ms, g0 == 0, npos_d, out_d));
+            {   // the members' range bits, read and cleared on the device
+                size_t slot = 0;
+                IHK(h0, ring_take(h0->eval_ring, (size_t)n, &slot));
+                char* a = static_cast<char*>(h0->eval_ring.host) + slot * elem;
+                for (int m = 0; m < n; ++m) {
+                    IpGroupArg<float> fa{};
+                    fa.err = hs[g0 + m]->err_flag; fa.model = m;
+                    memcpy(a + (size_t)m * elem, &fa, sizeof(fa));
+                }
+                IHK(h0, ring_send(h0->eval_ring, slot, (size_t)n, st));
+                hipLaunchKernelGGL(k_ip_gflags, dim3(1), dim3(256), 0, st, static_cast<const char*>(h0->eval_ring.dev) + slot * elem, elem, n, flags_d);
+                IHK(h0, hipGetLastError());
+            }
+            if (p_out) for (int m = 0; m < n; ++m)
+                if (p_out[g0 + m]) IHK(h0, hipMemcpyAsync(p_out[g0 + m], pp[m], (size_t)N * 4, hipMemcpyDeviceToDevice, st));
+            IHK(h0, hipMemcpyAsync(ho.data(), out_d, (size_t)n * sizeof(MetricOut), hipMemcpyDeviceToHost, st));
+            IHK(h0, hipMemcpyAsync(hf.data(), flags_d, (size_t)n * 4, hipMemcpyDeviceToHost, st));
+            if (g0 == 0) IHK(h0, hipMemcpyAsync(&n_pos, npos_d, 8, hipMemcpyDeviceToHost, st));
+            IHK(h0, hipStreamSynchronize(st));                        // the group's one synchronisation
+            const double np_ = (double)n_pos, nn = (double)(N - (int64_t)n_pos);
+            const bool two = n_pos > 0 && (int64_t)n_pos < N;
+            for (int m = 0; m < n; ++m) {
+                const MetricOut& o = ho[m];
+                const int i = g0 + m;
+                double v[3] = {std::nan(""), std::nan(""), std::nan("")};
+                if (!o.n_bad) {
+                    if (two) v[0] = (double)o.auc_sum / (2.0 * np_ * nn);
+                    v[1] = std::sqrt(o.se / (double)N); v[2] = o.ll / (double)N;
+                } else bad += (bad.empty() ? "" : ", ") + std::to_string(i);
+                if (hf[m]) range += (range.empty() ? "" : ", ") + std::to_string(i);
+                if (auc) auc[i] = v[0];
+                if (rmse) rmse[i] = v[1];
+                if (logloss) logloss[i] = v[2];
+                if (status) status[i] = o.n_bad ? FNN_ERR_RANGE : FNN_OK;
+            }
+        }
+        return FNN_OK;
+    };
+    const int rc = groups();
+    const int rj = g.leave();
+    if (rc != FNN_OK) { hipStreamSynchronize(st); return rc; }       // nothing may still be using the scratch
+    if (rj != FNN_OK) return rj;
+    std::string msg;
+    if (!bad.empty()) msg += "predictions NaN or outside [0, 1] in model(s) " + bad;
+    if (!range.empty()) msg += std::string(msg.empty() ? "" : "; ") + "feature id outside [0, n_rows) in model(s) " + range;
+    if (n_pos == 0 || (int64_t)n_pos == N) msg += std::string(msg.empty() ? "" : "; ") + "only one class present in y (roc_auc_score raises ValueError)";
+    if (!msg.empty()) return g.refuse(FNN_ERR_RANGE, msg);
     return FNN_OK;
 }
 

@@ -212,6 +212,79 @@ class IPNNEngine(object):
         self._ck(self.lib.ipnn_sync(self.h))
 
 
+def _many_feed(engines, ids, wts, y=None):
+    """The one feed of a group call on engines[0]'s device, and every engine's stream behind the caller's."""
+    e0 = engines[0]
+    torch = e0._torch
+    ids_t = e0._dev(ids, torch.int32)
+    wts_t = e0._wts(wts, ids_t)
+    y_t = e0._dev(y, torch.int32) if y is not None else None
+    cur = torch.cuda.current_stream(e0.device)
+    for e in engines:
+        e.stream.wait_stream(cur)
+    return ids_t, wts_t, y_t
+
+
+def predict_many(engines, ids, wts=None):
+    """predict of every engine of a list on ONE feed, in one call (ipnn_predict_multi): a list of device tensors [N] float32,
+    entry m bit for bit engines[m].predict(ids, wts).  N is not bounded by any engine's max_batch.  Nothing synchronises: an id
+    outside an engine's table shows at that engine's sync(), as after predict.  Every refusal raises FNNError."""
+    e0 = engines[0]
+    torch = e0._torch
+    M = len(engines)
+    ids_t, wts_t, _ = _many_feed(engines, ids, wts)
+    n = ids_t.shape[0]
+    ps = [torch.empty(n, dtype=torch.float32, device=e0.device) for _ in engines]
+    hs = (C.c_void_p * M)(*[e.h.value for e in engines])
+    rc = e0.lib.ipnn_predict_multi(hs, M, ids_t.data_ptr(), wts_t.data_ptr() if wts_t is not None else None, n,
+                                   (C.c_void_p * M)(*[t.data_ptr() for t in ps]))
+    if rc != 0:
+        raise FNNError(rc, (e0.lib.ipnn_last_error(e0.h) or b'').decode())
+    cur = torch.cuda.current_stream(e0.device)
+    for e in engines:
+        cur.wait_stream(e.stream)
+    e0._keep_many = (ids_t, wts_t)
+    return ps
+
+
+def evaluate_many(engines, ids, y, wts=None, want_p=False):
+    """evaluate of every engine of a list on ONE feed, in one call (ipnn_eval_multi).  Returns a list: entry m is
+    {'auc', 'rmse', 'logloss'[, 'p']}, the three metrics bit for bit what engines[m].evaluate(ids, y, wts) returns.  Where that
+    call would raise FNNError(FNN_ERR_RANGE) for that model alone the entry says so instead, so that one diverged model does not
+    cost the others their results: it then carries the further keys 'status' (FNN_ERR_RANGE) and 'error' (the call's message) --
+      a model with a prediction NaN or outside [0, 1]: 'auc', 'rmse' and 'logloss' are NaN ('p' is still the predictions);
+      only one class in y: every entry, 'auc' NaN, 'rmse' and 'logloss' as computed.
+    An id outside [0, n_rows) of some engine's table is a fault of the feed and raises FNNError(FNN_ERR_RANGE) naming the
+    models, as every other refusal of the call does."""
+    e0 = engines[0]
+    torch = e0._torch
+    M = len(engines)
+    ids_t, wts_t, y_t = _many_feed(engines, ids, wts, y)
+    n = ids_t.shape[0]
+    ps = [torch.empty(n, dtype=torch.float32, device=e0.device) for _ in engines] if want_p else None
+    auc, rmse, ll, status = (C.c_double * M)(), (C.c_double * M)(), (C.c_double * M)(), (C.c_int * M)()
+    hs = (C.c_void_p * M)(*[e.h.value for e in engines])
+    rc = e0.lib.ipnn_eval_multi(hs, M, ids_t.data_ptr(), wts_t.data_ptr() if wts_t is not None else None, y_t.data_ptr(), n,
+                                auc, rmse, ll, status, (C.c_void_p * M)(*[t.data_ptr() for t in ps]) if want_p else None)
+    msg = '' if rc == 0 else (e0.lib.ipnn_last_error(e0.h) or b'').decode()
+    if rc != 0 and (rc != _capi.FNN_ERR_RANGE or 'feature id outside' in msg):
+        raise FNNError(rc, msg)
+    cur = torch.cuda.current_stream(e0.device)
+    for e in engines:
+        cur.wait_stream(e.stream)
+    one_class = 'only one class' in msg
+    outs = []
+    for m in range(M):
+        o = {'auc': auc[m], 'rmse': rmse[m], 'logloss': ll[m]}
+        if want_p:
+            o['p'] = ps[m]
+        if status[m] != 0 or one_class:
+            o['status'] = _capi.FNN_ERR_RANGE
+            o['error'] = msg
+        outs.append(o)
+    return outs
+
+
 class _IPFamily(object):
     """Constructor signature of python/FNN_IP_L7.py:5: (cat_sizes, offsets, batch_size, _rch_argv,
     _init_argv, _ptmzr_argv, _reg_argv, mode, eval_size).  _rch_argv = [X_dim, X_feas, rank,

@@ -142,6 +142,42 @@ int ipnn_eval(ipnn_handle* h, const int32_t* ids, const int32_t* y, int64_t N, d
 int ipnn_eval_w(ipnn_handle* h, const int32_t* ids, const float* wts, const int32_t* y, int64_t N,
                 double* auc, double* rmse, double* logloss);
 
+/* Many models on ONE feed in one call (a hyper-parameter search scoring its candidates; DESIGN.md section 4, "Evaluating many
+ * inner-product models").  hs, auc, rmse, logloss, status and p_out are HOST arrays of n_models entries (each output array may be
+ * NULL); ids [N, F] int32, wts [N, F] f32 (nullable: every weight 1, as in ipnn_predict_w), y [N] int32 and every p_out[m] [N] are
+ * DEVICE pointers; 1 <= N <= 2^30, not bounded by any member's max_batch.  p_out[m] is required in ipnn_predict_multi; in
+ * ipnn_eval_multi an entry may be NULL.
+ *   Results: p_out[m] is bit for bit what ipnn_predict_w(hs[m], ..) writes when called in chunks of that handle's max_batch;
+ * auc[m], rmse[m], logloss[m] are bit for bit what ipnn_eval_w(hs[m], ..) returns.  status[m] is FNN_OK, or FNN_ERR_RANGE for a
+ * model with a prediction NaN or outside [0, 1]: its three metrics are NaN, every other model's results stand.  Only one class in
+ * y: every auc[m] is NaN, rmse and logloss are written.  An id outside [0, n_rows) is judged per model (table sizes may differ):
+ * ipnn_eval_multi reports those models and clears their flags, ipnn_predict_multi leaves them to each handle's ipnn_sync.  Any of
+ * the three makes the call return FNN_ERR_RANGE with the models' indices in ipnn_last_error(hs[0]); every other result is written.
+ *   The calls only read the models, and may be interleaved with every other call on the members.  Each member's pending work
+ * (the deferred dense update and sparse-row chain of IPNN_UPDATE_SIDE=1) is joined first; everything then runs on hs[0]'s stream,
+ * which first waits for every other member's streams, and they wait for the call's last launch.  Members whose prediction runs
+ * on the strip kernels share launches: per feed batch (as many lines as the smallest member's buffers hold: at most 4096, a
+ * multiple of 256) and LAUNCH CLASS -- element type, n_hidden, the padded widths, the gather's row kind, pairs, weights given
+ * or not; activation, k, table size and values may differ -- one inner-product launch and one launch over the whole stack,
+ * both with the model as a grid dimension, one workgroup per strip (no workgroup of a group launch waits for another).  The
+ * other members (a layer too wide for the strips, IPNN_STRIP=0) run their own launches inside the call.  ipnn_eval_multi takes
+ * the models in groups of as many as fit $IPNN_EVAL_SCRATCH_BYTES (read per call, default 2^30, one model at the least; N * 4
+ * bytes of predictions plus the metric pass's ~8.5 N per model) in one allocation hs[0] keeps while it is large enough; each
+ * group costs one metric pass and one synchronisation.  Neither where the feed nor where the groups are cut changes a bit.
+ * ipnn_predict_multi allocates nothing after hs[0]'s first group call and does not synchronise.
+ *   Refusals (nothing launched, nothing written; the message starts with the function's name, names the offending model and is
+ * left with ipnn_last_error(hs[0]), or ipnn_last_error(NULL) without a usable hs[0]): FNN_ERR_ARG for null hs, a null entry,
+ * n_models outside 1..IPNN_EVAL_MAX_MODELS, null ids / y / p_out (or a null entry of it, predict), N out of range, n_fields or
+ * device differing from hs[0]'s, a handle listed twice (its own a[0] buffer is the group launch's scratch); FNN_ERR_STATE for a
+ * handle without a table.  n_models == 1 is accepted: the group path was measured not faster there (profiles/
+ * ipnn_eval_multi_bench.json), so it runs the solo launches of ipnn_predict_w / ipnn_eval_w and reports as the group path does. */
+#define IPNN_EVAL_MAX_MODELS 1024
+int ipnn_predict_multi(ipnn_handle* const* hs, int n_models, const int32_t* ids, const float* wts,
+                       int64_t N, float* const* p_out);
+int ipnn_eval_multi(ipnn_handle* const* hs, int n_models, const int32_t* ids, const float* wts,
+                    const int32_t* y, int64_t N, double* auc, double* rmse, double* logloss,
+                    int* status, float* const* p_out);
+
 /* Measurement hook (bench.py): HIP events on the handle's stream around the segments of a train
  * step -- "mask_t" (the keep-masks: transposed, or drawn), "sort", "ip_fwd", "fwd", "bwd", "wgrad", "ip_bwd", "scatter", "update".  enable(1) clears
  * earlier samples; get returns the average device time of one segment in ms (0 if none). */
