@@ -1,7 +1,8 @@
-// arg_ring.h -- how the argument arrays of the group calls reach the device (fm_api.hip, fnn_api.hip).
+// arg_ring.h -- how the argument arrays of the group calls reach the device (fm_api.hip, fnn_api.hip, ipnn_api.hip).
 //
-// The per-model argument array of a group call (fm_train_online_multi, fm_train_step_multi, fm_predict_multi / fm_eval_multi,
-// fnn_train_step_multi) goes through a pinned host ring and its device image, both of the handle in front (hs[0]): a launch's
+// The per-model argument array of a group call (fm_train_online_multi, fm_train_step_multi, fnn_train_step_multi, and the
+// evaluation calls fm_ / fnn_ / ipnn_predict_multi and fm_ / fnn_ / ipnn_eval_multi, the range flags' kernel of the last
+// included) goes through a pinned host ring and its device image, both of the handle in front (hs[0]): a launch's
 // array is written into the next free slots of the one and copied to the same slots of the other on hs[0]'s stream.  The copy is
 // asynchronous, so a slot is the copy's to read until the copy has run: slots are handed out in order and never rewritten before
 // the ring wraps, and a wrap first waits for the event recorded after the latest copy (all copies are on one stream, in order,

@@ -26,6 +26,7 @@
 #include "optim.hip.h"
 #include "fm_online.hip.h"
 #include "arg_ring.h"
+#include "group_call.h"
 
 using namespace fnn;
 
@@ -764,17 +765,6 @@ void launch_step_fwd(hipStream_t st, int F, bool wv, int lay, const StepArg* d, 
 #undef FM_STEP_FWD
 }
 
-// runs `fn` with h's launches going to `st` (fold_scale, fm_next_stamp and launch_opt_pass work on their handle's stream)
-template <typename Fn>
-auto on_stream(fm_handle* h, hipStream_t st, Fn fn)
-{
-    const hipStream_t own = h->st;
-    h->st = st;
-    auto r = fn();
-    h->st = own;
-    return r;
-}
-
 bool fm_wt_env() { return !(getenv("FM_WT") && atoi(getenv("FM_WT")) == 0); }     // gx' written through unless FM_WT=0
 
 // The forward's arguments of a prediction (fm_predict_w, fm_eval_w; B = N: a member of fm_predict_multi / fm_eval_multi)
@@ -891,70 +881,14 @@ int ring_send(fm_handle* h0, ArgRing& r, size_t slot, size_t n)
     return FNN_OK;
 }
 
-// A call on a list of handles: what every such call refuses before any launch, and the streams.  A refusal's message goes to
-// hs[0], or to the library without a usable hs[0].  Everything a group call launches runs on hs[0]'s stream: enter() has that
-// stream wait for what the other members' streams hold so far, leave() -- at the latest the end of the scope, so on every error
-// path too -- has those streams wait for it, so that they stay ordered behind what was launched.  fold_scale(), fm_next_stamp()
-// and launch_opt_pass() work on their handle's stream: on_stream() gives them hs[0]'s.
-struct GroupCall {
-    const char* fn; fm_handle* const* hs; int n, max; fm_handle* h0;
-    std::vector<hipStream_t> others;               // the streams that are not hs[0]'s, each once
-    bool entered = false;
-    GroupCall(const char* fn_, fm_handle* const* hs_, int n_, int max_)
-        : fn(fn_), hs(hs_), n(n_), max(max_), h0(hs_ && n_ >= 1 && n_ <= max_ ? hs_[0] : nullptr) {}
-    ~GroupCall() { leave(); }
-    int refuse(int code, const std::string& msg) const { (h0 ? h0->err : g_fm_err) = std::string(fn) + ": " + msg; return code; }
-    static std::string at(const std::string& what, int m) { return "model " + std::to_string(m) + ": " + what; }
-    int member_failed(int code, const fm_handle* h, int m) const { if (h != h0) refuse(code, at(h->err, m)); return code; }
-    // the list itself; twice: why the same handle twice is refused (null: it is not -- reading is not a race)
-    int check_handles(const char* twice) const
-    {
-        if (!hs) return refuse(FNN_ERR_ARG, "null hs");
-        if (n < 1 || n > max) return refuse(FNN_ERR_ARG, "n_models must be in [1, " + std::to_string(max) + "]");
-        for (int m = 0; m < n; ++m) if (!hs[m]) return refuse(FNN_ERR_ARG, at("null handle", m));
-        if (twice) {
-            std::vector<const fm_handle*> seen(hs, hs + n);
-            std::sort(seen.begin(), seen.end());
-            const auto dup = std::adjacent_find(seen.begin(), seen.end());
-            if (dup != seen.end()) {
-                int m = n - 1;
-                while (hs[m] != *dup) --m;                            // the later of the two places
-                return refuse(FNN_ERR_ARG, at(std::string("the same handle twice in one call (") + twice + ")", m));
-            }
-        }
-        for (int m = 1; m < n; ++m)
-            if (hs[m]->F != h0->F || hs[m]->dev != h0->dev) return refuse(FNN_ERR_ARG, at("n_fields or device differs from model 0's", m));
-        return FNN_OK;
-    }
-    int check_tables() const
-    {
-        for (int m = 0; m < n; ++m) if (!hs[m]->table16) return refuse(FNN_ERR_STATE, at("fm_set_table has not been called", m));
-        return FNN_OK;
-    }
-    int enter()
-    {
-        MHK(h0, hipSetDevice(h0->dev));
-        for (int m = 1; m < n; ++m) if (hs[m]->st != h0->st) others.push_back(hs[m]->st);
-        std::sort(others.begin(), others.end());
-        others.erase(std::unique(others.begin(), others.end()), others.end());
-        if (!others.empty() && !h0->join) MHK(h0, hipEventCreateWithFlags(&h0->join, hipEventDisableTiming));
-        entered = true;
-        for (hipStream_t o : others) {                                // hs[0]'s stream after everything enqueued on the others so far
-            MHK(h0, hipEventRecord(h0->join, o));
-            MHK(h0, hipStreamWaitEvent(h0->st, h0->join, 0));
-        }
-        return FNN_OK;
-    }
-    int leave()
-    {
-        if (!entered) return FNN_OK;
-        entered = false;
-        if (others.empty()) return FNN_OK;                            // whatever the other streams get from here on comes after the call
-        MHK(h0, hipEventRecord(h0->join, h0->st));
-        for (hipStream_t o : others) MHK(h0, hipStreamWaitEvent(o, h0->join, 0));
-        return FNN_OK;
-    }
-};
+// A call on a list of fm handles: GroupCall (group_call.h), refusals without a usable hs[0] left with fm_last_error(NULL).
+// fold_scale(), fm_next_stamp() and launch_opt_pass() work on their handle's stream: on_stream() gives them hs[0]'s.
+using FmGroup = GroupCall<fm_handle>;
+int check_tables(const FmGroup& g)
+{
+    for (int m = 0; m < g.n; ++m) if (!g.hs[m]->table16) return g.refuse(FNN_ERR_STATE, g.at("fm_set_table has not been called", m));
+    return FNN_OK;
+}
 
 }  // namespace
 
@@ -1164,9 +1098,9 @@ int fm_train_online(fm_handle* h, const int32_t* ids, const float* wts, const fl
 int fm_train_online_multi(fm_handle* const* hs, int n_models, const int32_t* ids, const float* wts, const float* y, int64_t N,
                           const float* lr, const float* lambda, float* const* p_out, double* loss_sum_out, float* loss_last_out)
 {
-    GroupCall g("fm_train_online_multi", hs, n_models, FM_ONLINE_MAX_MODELS);
+    FmGroup g("fm_train_online_multi", hs, n_models, FM_ONLINE_MAX_MODELS, g_fm_err);
     if (!hs || !lr || !lambda) return g.refuse(FNN_ERR_ARG, "null hs, lr or lambda");
-    int rc = g.check_handles("two workgroups would race on one table");
+    int rc = g.check_list("two workgroups would race on one table");
     if (rc != FNN_OK) return rc;
     if (N < 0 || (N > 0 && (!ids || !y))) return g.refuse(FNN_ERR_ARG, "need N >= 0, ids and y");
     for (int m = 0; m < n_models; ++m) {
@@ -1175,7 +1109,7 @@ int fm_train_online_multi(fm_handle* const* hs, int n_models, const int32_t* ids
     }
     for (int m = 0; m < n_models; ++m)
         if (hs[m]->opt != FM_OPT_SGD) return g.refuse(FNN_ERR_STATE, g.at("plain SGD only (Adam / FTRL pass over the whole table per step)", m));
-    rc = g.check_tables();
+    rc = check_tables(g);
     if (rc != FNN_OK) return rc;
     for (int m = 0; m < n_models; ++m) {
         if (loss_sum_out) loss_sum_out[m] = 0.0;
@@ -1248,9 +1182,9 @@ int fm_train_online_multi(fm_handle* const* hs, int n_models, const int32_t* ids
 int fm_train_step_multi(fm_handle* const* hs, int n_models, const int32_t* ids, const float* wts, const float* y, int B,
                         const float* lr, const float* lambda, const int* reduce_mean, float* const* p_out, float* loss_out)
 {
-    GroupCall g("fm_train_step_multi", hs, n_models, FM_STEP_MAX_MODELS);
+    FmGroup g("fm_train_step_multi", hs, n_models, FM_STEP_MAX_MODELS, g_fm_err);
     if (!hs || !lr || !lambda) return g.refuse(FNN_ERR_ARG, "null hs, lr or lambda");
-    int rc = g.check_handles("two updates would race on one table");
+    int rc = g.check_list("two updates would race on one table");
     if (rc != FNN_OK) return rc;
     if (!ids || !y) return g.refuse(FNN_ERR_ARG, "null ids or y");
     if (B < 1) return g.refuse(FNN_ERR_ARG, "B must be in [1, max_batch]");
@@ -1260,7 +1194,7 @@ int fm_train_step_multi(fm_handle* const* hs, int n_models, const int32_t* ids, 
         if (h->opt == FM_OPT_SGD && (!(lr[m] * lambda[m] < 1.0f) || lambda[m] < 0.f)) return g.refuse(FNN_ERR_ARG, g.at("need 0 <= lr * lambda < 1", m));
         if (h->opt != FM_OPT_SGD && (!(lambda[m] >= 0.f) || !(lr[m] > 0.f))) return g.refuse(FNN_ERR_ARG, g.at("Adam / FTRL need lr > 0 and lambda >= 0", m));
     }
-    rc = g.check_tables();
+    rc = check_tables(g);
     if (rc != FNN_OK) return rc;
     fm_handle* h0 = g.h0;
     if (n_models == 1) {       // nothing to share: the solo step itself, without the argument copy (15 us in front of a 27 us step)
@@ -1491,11 +1425,11 @@ int fm_eval_w(fm_handle* h, const int32_t* ids, const float* wts, const int32_t*
 namespace {
 
 // what both calls refuse after the list itself
-int eval_check(const GroupCall& g, const int32_t* ids, bool need_y, const int32_t* y, int64_t N)
+int eval_check(const FmGroup& g, const int32_t* ids, bool need_y, const int32_t* y, int64_t N)
 {
     if (!ids || (need_y && !y)) return g.refuse(FNN_ERR_ARG, need_y ? "null ids or y" : "null ids");
     if (N < 1 || N > ((int64_t)1 << 30)) return g.refuse(FNN_ERR_ARG, "N must be in [1, 2^30]");
-    return g.check_tables();
+    return check_tables(g);
 }
 
 // The predictions of g models on the N lines, p[m] (nullable) each: the argument array into the ring, then one launch per layout
@@ -1541,19 +1475,12 @@ int eval_forward(fm_handle* h0, fm_handle* const* hs, int g, const int32_t* ids,
     return FNN_OK;
 }
 
-inline size_t up256(size_t b) { return (b + 255) / 256 * 256; }
-// scratch of a group of g models: p [g][N], the metric pass's, out [g], flags [g], n_pos
-size_t eval_scratch_bytes(int g, int64_t N)
-{
-    return up256((size_t)g * (size_t)N * 4) + up256(metrics_multi_bytes(g, N)) + up256((size_t)g * sizeof(MetricOut)) + up256((size_t)g * 4) + 256;
-}
-
 }  // namespace
 
 int fm_predict_multi(fm_handle* const* hs, int n_models, const int32_t* ids, const float* wts, int64_t N, float* const* p_out)
 {
-    GroupCall g("fm_predict_multi", hs, n_models, FM_EVAL_MAX_MODELS);
-    int rc = g.check_handles(nullptr);
+    FmGroup g("fm_predict_multi", hs, n_models, FM_EVAL_MAX_MODELS, g_fm_err);
+    int rc = g.check_list(nullptr);
     if (rc == FNN_OK) rc = eval_check(g, ids, false, nullptr, N);
     if (rc != FNN_OK) return rc;
     if (!p_out) return g.refuse(FNN_ERR_ARG, "null p_out");
@@ -1568,81 +1495,33 @@ int fm_predict_multi(fm_handle* const* hs, int n_models, const int32_t* ids, con
 int fm_eval_multi(fm_handle* const* hs, int n_models, const int32_t* ids, const float* wts, const int32_t* y, int64_t N,
                   double* auc, double* rmse, double* logloss, int* status)
 {
-    GroupCall g("fm_eval_multi", hs, n_models, FM_EVAL_MAX_MODELS);
-    int rc = g.check_handles(nullptr);
+    FmGroup g("fm_eval_multi", hs, n_models, FM_EVAL_MAX_MODELS, g_fm_err);
+    int rc = g.check_list(nullptr);
     if (rc == FNN_OK) rc = eval_check(g, ids, true, y, N);
     if (rc != FNN_OK) return rc;
     fm_handle* h0 = g.h0;
-    // the models of a group share one scratch allocation: as many as fit under the cap, one at the least
-    size_t cap = (size_t)1 << 30;
-    if (const char* e = getenv("FM_EVAL_SCRATCH_BYTES")) { const long long c = atoll(e); if (c >= 1) cap = (size_t)c; }
-    int G = n_models;
-    {
-        const size_t one = eval_scratch_bytes(1, N);
-        if ((size_t)G > cap / one) G = (int)(cap / one);
-        if (G < 1) G = 1;
-        while (G > 1 && eval_scratch_bytes(G, N) > cap) --G;
-    }
+    // the models of a group share one scratch allocation, the call's own: as many as fit under the cap, one at the least
+    const int G = eval_group_size(n_models, N, "FM_EVAL_SCRATCH_BYTES");
     rc = g.enter();
     if (rc != FNN_OK) return rc;
     const hipStream_t st = h0->st;
     char* scratch = nullptr;
-    MHK(h0, hipMalloc((void**)&scratch, eval_scratch_bytes(G, N)));
-    float* p_d = reinterpret_cast<float*>(scratch);
-    char* ms = scratch + up256((size_t)G * (size_t)N * 4);
-    MetricOut* out_d = reinterpret_cast<MetricOut*>(ms + up256(metrics_multi_bytes(G, N)));
-    int* flags_d = reinterpret_cast<int*>(reinterpret_cast<char*>(out_d) + up256((size_t)G * sizeof(MetricOut)));
-    unsigned long long* npos_d = reinterpret_cast<unsigned long long*>(reinterpret_cast<char*>(flags_d) + up256((size_t)G * 4));
-    std::vector<MetricOut> ho(G);
-    std::vector<int> hf(G);
-    std::vector<float*> pp(G);
-    unsigned long long n_pos = 0;
-    std::string bad, range;
-    auto groups = [&]() -> int {                                      // an error leaves the lambda: the scratch is still freed
-        for (int g0 = 0; g0 < n_models; g0 += G) {
-            const int g = n_models - g0 < G ? n_models - g0 : G;
-            for (int m = 0; m < g; ++m) pp[m] = p_d + (size_t)m * (size_t)N;
-            const EvalArg* d = nullptr;
-            const int rf = eval_forward(h0, hs + g0, g, ids, wts, N, pp.data(), &d);
-            if (rf != FNN_OK) return rf;
-            MHK(h0, metrics_multi(st, p_d, y, N, g, ms, g0 == 0, npos_d, out_d));
-            hipLaunchKernelGGL(k_fm_eval_flags, dim3(1), dim3(256), 0, st, d, g, flags_d);
-            MHK(h0, hipGetLastError());
-            MHK(h0, hipMemcpyAsync(ho.data(), out_d, (size_t)g * sizeof(MetricOut), hipMemcpyDeviceToHost, st));
-            MHK(h0, hipMemcpyAsync(hf.data(), flags_d, (size_t)g * 4, hipMemcpyDeviceToHost, st));
-            if (g0 == 0) MHK(h0, hipMemcpyAsync(&n_pos, npos_d, 8, hipMemcpyDeviceToHost, st));
-            MHK(h0, hipStreamSynchronize(st));                        // the group's one synchronisation
-            const double np_ = (double)n_pos, nn = (double)(N - (int64_t)n_pos);
-            const bool two = n_pos > 0 && (int64_t)n_pos < N;
-            for (int m = 0; m < g; ++m) {
-                const MetricOut& o = ho[m];
-                const int i = g0 + m;
-                double v[3] = {std::nan(""), std::nan(""), std::nan("")};
-                if (!o.n_bad) {
-                    if (two) v[0] = (double)o.auc_sum / (2.0 * np_ * nn);
-                    v[1] = std::sqrt(o.se / (double)N); v[2] = o.ll / (double)N;
-                } else bad += (bad.empty() ? "" : ", ") + std::to_string(i);
-                if (hf[m]) range += (range.empty() ? "" : ", ") + std::to_string(i);
-                if (auc) auc[i] = v[0];
-                if (rmse) rmse[i] = v[1];
-                if (logloss) logloss[i] = v[2];
-                if (status) status[i] = o.n_bad ? FNN_ERR_RANGE : FNN_OK;
-            }
-        }
+    MHK(h0, hipMalloc((void**)&scratch, EvalScratch::bytes(G, N)));
+    const EvalArg* d = nullptr;                                       // the group's arguments on the device, from its forward to its flags
+    const EvalForward forward = [&](int g0, int n, float* const* p) { return eval_forward(h0, hs + g0, n, ids, wts, N, p, &d); };
+    const EvalFlags flags = [&](int, int n, int* flags_d) {
+        hipLaunchKernelGGL(k_fm_eval_flags, dim3(1), dim3(256), 0, st, d, n, flags_d);
+        MHK(h0, hipGetLastError());
         return FNN_OK;
     };
-    rc = groups();
+    EvalFound found;
+    rc = eval_groups(st, n_models, G, y, N, scratch, forward, flags, EvalOut{auc, rmse, logloss, status, nullptr}, found, h0->err);
     const int rj = g.leave();
-    if (rc != FNN_OK) hipStreamSynchronize(st);                       // nothing may still be using the scratch
-    hipFree(scratch);
+    hipFree(scratch);                                                 // (after an error eval_groups has drained the stream)
     if (rc != FNN_OK) return rc;
     if (rj != FNN_OK) return rj;
-    std::string msg;
-    if (!bad.empty()) msg += "predictions NaN or outside [0, 1] in model(s) " + bad;
-    if (!range.empty()) msg += std::string(msg.empty() ? "" : "; ") + "feature id outside [-1, n_rows) in model(s) " + range;
-    if (n_pos == 0 || (int64_t)n_pos == N) msg += std::string(msg.empty() ? "" : "; ") + "only one class present in y (roc_auc_score raises ValueError)";
-    if (!msg.empty()) return g.refuse(FNN_ERR_RANGE, msg);
-    return FNN_OK;
+    const std::string msg = eval_verdict(found.bad, found.range, found.n_pos, N, "[-1, n_rows)");
+    return msg.empty() ? FNN_OK : g.refuse(FNN_ERR_RANGE, msg);
 }
 
 }  // extern "C"

@@ -21,6 +21,7 @@
 #include "fnn_step_kernels.hip.h"
 #include "metrics.hip.h"
 #include "arg_ring.h"
+#include "group_call.h"
 
 using namespace fnn;
 
@@ -951,52 +952,8 @@ FnnPlan make_plan(const fnn_cfg& c, const FnnKnobs& kn)
 }
 
 // ---- fnn_train_step_multi: one step of several handles on one feed (the kernels: k_gstep1 / k_gstep2 / k_gstep3)
-// A call on a list of handles: its refusals and the streams.  A refusal's message goes to hs[0], or to the library without a
-// usable hs[0].  Everything the call launches runs on hs[0]'s stream: enter() has that stream wait for what the other members'
-// streams hold so far, leave() -- at the latest the end of the scope, so on every error path too -- has those streams wait for it.
-struct StepGroup {
-    fnn_handle* const* hs; int n; fnn_handle* h0;
-    std::vector<hipStream_t> others;               // the streams that are not hs[0]'s, each once
-    bool entered = false;
-    const char* name;                              // the entry point, in front of every refusal
-    StepGroup(fnn_handle* const* hs_, int n_, const char* name_ = "fnn_train_step_multi", int max_models = FNN_STEP_MAX_MODELS)
-        : hs(hs_), n(n_), h0(hs_ && n_ >= 1 && n_ <= max_models ? hs_[0] : nullptr), name(name_) {}
-    ~StepGroup() { leave(); }
-    int refuse(int code, const std::string& msg) const { (h0 ? h0->err : g_create_err) = std::string(name) + ": " + msg; return code; }
-    static std::string at(const std::string& what, int m) { return "model " + std::to_string(m) + ": " + what; }
-    int enter()
-    {
-        HIPCHK(h0, hipSetDevice(h0->dev));
-        for (int m = 1; m < n; ++m) if (hs[m]->st != h0->st) others.push_back(hs[m]->st);
-        std::sort(others.begin(), others.end());
-        others.erase(std::unique(others.begin(), others.end()), others.end());
-        if (!others.empty() && !h0->join) HIPCHK(h0, hipEventCreateWithFlags(&h0->join, hipEventDisableTiming));
-        entered = true;
-        for (hipStream_t o : others) {                                // hs[0]'s stream after everything enqueued on the others so far
-            HIPCHK(h0, hipEventRecord(h0->join, o));
-            HIPCHK(h0, hipStreamWaitEvent(h0->st, h0->join, 0));
-        }
-        return FNN_OK;
-    }
-    int leave()
-    {
-        if (!entered) return FNN_OK;
-        entered = false;
-        if (others.empty()) return FNN_OK;                            // whatever the other streams get from here on comes after the call
-        HIPCHK(h0, hipEventRecord(h0->join, h0->st));
-        for (hipStream_t o : others) HIPCHK(h0, hipStreamWaitEvent(o, h0->join, 0));
-        return FNN_OK;
-    }
-};
-// work of member h that enqueues on "the handle's stream", on the group's stream instead
-template <typename Fn> auto on_stream(fnn_handle* h, hipStream_t st, Fn fn)
-{
-    const hipStream_t own = h->st;
-    h->st = st;
-    auto r = fn();
-    h->st = own;
-    return r;
-}
+// A call on a list of handles: GroupCall (group_call.h), refusals without a usable hs[0] left with fnn_last_error(NULL).
+using FnnGroup = GroupCall<fnn_handle>;
 
 // What decides which handles one set of group launches serves: the three kernels with their block and LDS sizes, and what
 // shapes the grid -- a LAUNCH CLASS (include/fnn_hip.h).  The kernels follow from element type, padded shapes, key width, sort
@@ -1067,7 +1024,6 @@ struct EvalKnobs {
     int fb_len = 4096;          // FNN_EVAL_FEED_BATCH=256..65536, a multiple of 256: lines per feed batch (k_gpredict)
     bool model_fast = false;    // FNN_EVAL_ORDER=model: the model is the fast index of the grid (default: tile, the strips of one model adjacent)
     bool per_batch = false;     // FNN_EVAL_LAUNCH=batch: one launch per feed batch (default: span, one launch over all feed batches)
-    size_t cap = (size_t)1 << 30;      // FNN_EVAL_SCRATCH_BYTES: the scratch of one group of models (fnn_eval_multi)
 };
 constexpr int EVAL_FEED_BATCH_MAX = 65536;
 EvalKnobs read_eval_knobs()
@@ -1076,7 +1032,6 @@ EvalKnobs read_eval_knobs()
     if (const char* e = getenv("FNN_EVAL_FEED_BATCH")) { const int v = atoi(e); if (v >= 256 && v <= EVAL_FEED_BATCH_MAX && v % 256 == 0) k.fb_len = v; }
     if (const char* e = getenv("FNN_EVAL_ORDER")) k.model_fast = !strcmp(e, "model");
     if (const char* e = getenv("FNN_EVAL_LAUNCH")) k.per_batch = !strcmp(e, "batch");
-    if (const char* e = getenv("FNN_EVAL_SCRATCH_BYTES")) { const long long c = atoll(e); if (c >= 1) k.cap = (size_t)c; }
     return k;
 }
 // A member whose prediction is the strip kernel on FM rows rides in a group launch; every other one (bag mode, wide rows, shapes
@@ -1124,16 +1079,11 @@ static __global__ __launch_bounds__(256) void k_gpred_flags(const GroupPredArg<f
     for (int i = threadIdx.x; i < n; i += 256) if (flags[args[i].m]) atomicAnd(args[i].ma.err, ~1);
 }
 // What both calls refuse, all of it before anything is launched or written.
-int pred_check(const StepGroup& g, const int32_t* ids, bool need_y, const int32_t* y, int64_t N, bool need_p, float* const* p_out)
+int pred_check(const FnnGroup& g, const int32_t* ids, bool need_y, const int32_t* y, int64_t N, bool need_p, float* const* p_out)
 {
+    RCCHK(g.check_list(nullptr));                                 // a handle may be listed twice: reading is not a race
     fnn_handle* const* hs = g.hs;
     const int M = g.n;
-    if (!hs) return g.refuse(FNN_ERR_ARG, "null hs");
-    if (M < 1 || M > FNN_EVAL_MAX_MODELS) return g.refuse(FNN_ERR_ARG, "n_models must be in [1, " + std::to_string(FNN_EVAL_MAX_MODELS) + "]");
-    for (int m = 0; m < M; ++m) if (!hs[m]) return g.refuse(FNN_ERR_ARG, g.at("null handle", m));
-    fnn_handle* h0 = g.h0;
-    for (int m = 1; m < M; ++m)
-        if (hs[m]->F != h0->F || hs[m]->dev != h0->dev) return g.refuse(FNN_ERR_ARG, g.at("n_fields or device differs from model 0's", m));
     if (!ids || (need_y && !y)) return g.refuse(FNN_ERR_ARG, need_y ? "null ids or y" : "null ids");
     if (need_p && !p_out) return g.refuse(FNN_ERR_ARG, "null p_out");
     if (need_p) for (int m = 0; m < M; ++m) if (!p_out[m]) return g.refuse(FNN_ERR_ARG, g.at("null p_out", m));
@@ -1151,7 +1101,7 @@ int pred_check(const StepGroup& g, const int32_t* ids, bool need_y, const int32_
 // The predictions of the n members hs[0 .. n) of group `g` on the N lines, p[m] each: the argument array into hs[0]'s ring, one
 // set of launches per prediction launch class, then the members off the strip kernel one after the other, each in chunks of its
 // own max_batch with its stream swapped for the group's.  *dev_args: the members' arguments on the device (k_gpred_flags).
-int pred_forward(const StepGroup& g, fnn_handle* const* hs, int n, int base, const int32_t* ids, int64_t N, float* const* p, const EvalKnobs& ek,
+int pred_forward(const FnnGroup& g, fnn_handle* const* hs, int n, int base, const int32_t* ids, int64_t N, float* const* p, const EvalKnobs& ek,
                  const GroupPredArg<float>** dev_args)
 {
     fnn_handle* h0 = g.h0;
@@ -1192,7 +1142,7 @@ int pred_forward(const StepGroup& g, fnn_handle* const* hs, int n, int base, con
             HIPCHK(h, hipGetLastError());
             return FNN_OK;
         });
-        if (rc != FNN_OK) { if (h != h0) g.refuse(rc, g.at(h->err, base + m)); return rc; }
+        if (rc != FNN_OK) return g.member_failed(rc, h, base + m);
     }
     *dev_args = reinterpret_cast<const GroupPredArg<float>*>(d);
     return FNN_OK;
@@ -1204,12 +1154,6 @@ int ensure_eval_y(fnn_handle* h0)
     HIPCHK(h0, hipMalloc((void**)&h0->eval_y, EVAL_FEED_BATCH_MAX * sizeof(float)));
     HIPCHK(h0, hipMemsetAsync(h0->eval_y, 0, EVAL_FEED_BATCH_MAX * sizeof(float), h0->st));
     return FNN_OK;
-}
-inline size_t up256(size_t b) { return (b + 255) / 256 * 256; }
-// scratch of a group of g models: p [g][N], the metric pass's, out [g], flags [g], n_pos
-size_t eval_scratch_bytes(int g, int64_t N)
-{
-    return up256((size_t)g * (size_t)N * 4) + up256(metrics_multi_bytes(g, N)) + up256((size_t)g * sizeof(MetricOut)) + up256((size_t)g * 4) + 256;
 }
 
 }  // namespace
@@ -1931,25 +1875,11 @@ int fnn_train_step_multi(fnn_handle* const* hs, int n_models, const int32_t* ids
                          const uint8_t* const* mask1, const uint8_t* const* mask2, int b_size,
                          const int32_t* next_ids, int next_B, float* const* p_out, float* loss_sum_out)
 {
-    StepGroup g(hs, n_models);
+    FnnGroup g("fnn_train_step_multi", hs, n_models, FNN_STEP_MAX_MODELS, g_create_err);
     const int M = n_models;
     // ---- refusals: all of them before anything is launched or written
-    if (!hs) return g.refuse(FNN_ERR_ARG, "null hs");
-    if (M < 1 || M > FNN_STEP_MAX_MODELS) return g.refuse(FNN_ERR_ARG, "n_models must be in [1, " + std::to_string(FNN_STEP_MAX_MODELS) + "]");
-    for (int m = 0; m < M; ++m) if (!hs[m]) return g.refuse(FNN_ERR_ARG, g.at("null handle", m));
-    {
-        std::vector<const fnn_handle*> seen(hs, hs + M);
-        std::sort(seen.begin(), seen.end());
-        const auto dup = std::adjacent_find(seen.begin(), seen.end());
-        if (dup != seen.end()) {
-            int m = M - 1;
-            while (hs[m] != *dup) --m;                                // the later of the two places
-            return g.refuse(FNN_ERR_ARG, g.at("the same handle twice in one call (two updates would race on one model)", m));
-        }
-    }
+    RCCHK(g.check_list("two updates would race on one model"));
     fnn_handle* h0 = g.h0;
-    for (int m = 1; m < M; ++m)
-        if (hs[m]->F != h0->F || hs[m]->dev != h0->dev) return g.refuse(FNN_ERR_ARG, g.at("n_fields or device differs from model 0's", m));
     if (!ids || !y || !mask1 || !mask2) return g.refuse(FNN_ERR_ARG, "null ids, y, mask1 or mask2");
     for (int m = 0; m < M; ++m) if (!mask1[m] || !mask2[m]) return g.refuse(FNN_ERR_ARG, g.at("null mask1 or mask2", m));
     if (B < 1 || B > SORT_N) return g.refuse(FNN_ERR_ARG, "B must be in [1, 4096]");
@@ -1984,7 +1914,7 @@ int fnn_train_step_multi(fnn_handle* const* hs, int n_models, const int32_t* ids
     for (int m = 0; m < M; ++m) {
         fnn_handle* h = hs[m];
         const int rc = on_stream(h, st, [&] { return update_cpow(h, b_size, B); });
-        if (rc != FNN_OK) { if (h != h0) g.refuse(rc, g.at(h->err, m)); return rc; }
+        if (rc != FNN_OK) return g.member_failed(rc, h, m);
     }
     // launch classes, in the order of their first members
     std::vector<LaunchClass> cls;
@@ -2124,7 +2054,7 @@ int fnn_eval(fnn_handle* h, const int32_t* ids, const int32_t* y, int64_t N, int
 // ("Evaluating many FNN models").  Nothing is allocated after hs[0]'s first group call, nothing synchronises.
 int fnn_predict_multi(fnn_handle* const* hs, int n_models, const int32_t* ids, int64_t N, float* const* p_out)
 {
-    StepGroup g(hs, n_models, "fnn_predict_multi", FNN_EVAL_MAX_MODELS);
+    FnnGroup g("fnn_predict_multi", hs, n_models, FNN_EVAL_MAX_MODELS, g_create_err);
     RCCHK(pred_check(g, ids, false, nullptr, N, true, p_out));
     const EvalKnobs ek = read_eval_knobs();
     RCCHK(g.enter());
@@ -2139,78 +2069,31 @@ int fnn_predict_multi(fnn_handle* const* hs, int n_models, const int32_t* ids, i
 int fnn_eval_multi(fnn_handle* const* hs, int n_models, const int32_t* ids, const int32_t* y, int64_t N,
                    double* auc, double* rmse, double* logloss, int* status, float* const* p_out)
 {
-    StepGroup g(hs, n_models, "fnn_eval_multi", FNN_EVAL_MAX_MODELS);
+    FnnGroup g("fnn_eval_multi", hs, n_models, FNN_EVAL_MAX_MODELS, g_create_err);
     RCCHK(pred_check(g, ids, true, y, N, false, nullptr));
     fnn_handle* h0 = g.h0;
     const EvalKnobs ek = read_eval_knobs();
-    int G = n_models;
-    {
-        const size_t one = eval_scratch_bytes(1, N);
-        if ((size_t)G > ek.cap / one) G = (int)(ek.cap / one);
-        if (G < 1) G = 1;
-        while (G > 1 && eval_scratch_bytes(G, N) > ek.cap) --G;
-    }
+    const int G = eval_group_size(n_models, N, "FNN_EVAL_SCRATCH_BYTES");
     RCCHK(g.enter());
     RCCHK(ensure_eval_y(h0));
     const hipStream_t st = h0->st;
-    char* scratch = nullptr;
-    HIPCHK(h0, hipMalloc((void**)&scratch, eval_scratch_bytes(G, N)));
-    float* p_d = reinterpret_cast<float*>(scratch);
-    char* ms = scratch + up256((size_t)G * (size_t)N * 4);
-    MetricOut* out_d = reinterpret_cast<MetricOut*>(ms + up256(metrics_multi_bytes(G, N)));
-    int* flags_d = reinterpret_cast<int*>(reinterpret_cast<char*>(out_d) + up256((size_t)G * sizeof(MetricOut)));
-    unsigned long long* npos_d = reinterpret_cast<unsigned long long*>(reinterpret_cast<char*>(flags_d) + up256((size_t)G * 4));
-    std::vector<MetricOut> ho(G);
-    std::vector<int> hf(G);
-    std::vector<float*> pp(G);
-    unsigned long long n_pos = 0;
-    std::string bad, range;
-    auto groups = [&]() -> int {                                      // an error leaves the lambda: the scratch is still freed
-        for (int g0 = 0; g0 < n_models; g0 += G) {
-            const int n = std::min(G, n_models - g0);
-            for (int m = 0; m < n; ++m) pp[m] = p_d + (size_t)m * (size_t)N;
-            const GroupPredArg<float>* d = nullptr;
-            RCCHK(pred_forward(g, hs + g0, n, g0, ids, N, pp.data(), ek, &d));
-            HIPCHK(h0, metrics_multi(st, p_d, y, N, n, ms, g0 == 0, npos_d, out_d));
-            hipLaunchKernelGGL(k_gpred_flags, dim3(1), dim3(256), 0, st, d, n, flags_d);
-            HIPCHK(h0, hipGetLastError());
-            if (p_out) for (int m = 0; m < n; ++m)
-                if (p_out[g0 + m]) HIPCHK(h0, hipMemcpyAsync(p_out[g0 + m], pp[m], (size_t)N * 4, hipMemcpyDeviceToDevice, st));
-            HIPCHK(h0, hipMemcpyAsync(ho.data(), out_d, (size_t)n * sizeof(MetricOut), hipMemcpyDeviceToHost, st));
-            HIPCHK(h0, hipMemcpyAsync(hf.data(), flags_d, (size_t)n * 4, hipMemcpyDeviceToHost, st));
-            if (g0 == 0) HIPCHK(h0, hipMemcpyAsync(&n_pos, npos_d, 8, hipMemcpyDeviceToHost, st));
-            HIPCHK(h0, hipStreamSynchronize(st));                     // the group's one synchronisation
-            const double np_ = (double)n_pos, nn = (double)(N - (int64_t)n_pos);
-            const bool two = n_pos > 0 && (int64_t)n_pos < N;
-            for (int m = 0; m < n; ++m) {
-                const MetricOut& o = ho[m];
-                const int i = g0 + m;
-                double v[3] = {std::nan(""), std::nan(""), std::nan("")};
-                if (!o.n_bad) {
-                    if (two) v[0] = (double)o.auc_sum / (2.0 * np_ * nn);
-                    v[1] = std::sqrt(o.se / (double)N); v[2] = o.ll / (double)N;
-                } else bad += (bad.empty() ? "" : ", ") + std::to_string(i);
-                if (hf[m]) range += (range.empty() ? "" : ", ") + std::to_string(i);
-                if (auc) auc[i] = v[0];
-                if (rmse) rmse[i] = v[1];
-                if (logloss) logloss[i] = v[2];
-                if (status) status[i] = o.n_bad ? FNN_ERR_RANGE : FNN_OK;
-            }
-        }
+    char* scratch = nullptr;                                          // the call's own
+    HIPCHK(h0, hipMalloc((void**)&scratch, EvalScratch::bytes(G, N)));
+    const GroupPredArg<float>* d = nullptr;                           // the group's arguments on the device, from its forward to its flags
+    const EvalForward forward = [&](int g0, int n, float* const* p) { return pred_forward(g, hs + g0, n, g0, ids, N, p, ek, &d); };
+    const EvalFlags flags = [&](int, int n, int* flags_d) {
+        hipLaunchKernelGGL(k_gpred_flags, dim3(1), dim3(256), 0, st, d, n, flags_d);
+        HIPCHK(h0, hipGetLastError());
         return FNN_OK;
     };
-    const int rc = groups();
+    EvalFound found;
+    const int rc = eval_groups(st, n_models, G, y, N, scratch, forward, flags, EvalOut{auc, rmse, logloss, status, p_out}, found, h0->err);
     const int rj = g.leave();
-    if (rc != FNN_OK) hipStreamSynchronize(st);                       // nothing may still be using the scratch
-    hipFree(scratch);
+    hipFree(scratch);                                                 // (after an error eval_groups has drained the stream)
     if (rc != FNN_OK) return rc;
     if (rj != FNN_OK) return rj;
-    std::string msg;
-    if (!bad.empty()) msg += "predictions NaN or outside [0, 1] in model(s) " + bad;
-    if (!range.empty()) msg += std::string(msg.empty() ? "" : "; ") + "feature id outside [-1, n_rows) in model(s) " + range;
-    if (n_pos == 0 || (int64_t)n_pos == N) msg += std::string(msg.empty() ? "" : "; ") + "only one class present in y (roc_auc_score raises ValueError)";
-    if (!msg.empty()) return g.refuse(FNN_ERR_RANGE, msg);
-    return FNN_OK;
+    const std::string msg = eval_verdict(found.bad, found.range, found.n_pos, N, "[-1, n_rows)");
+    return msg.empty() ? FNN_OK : g.refuse(FNN_ERR_RANGE, msg);
 }
 
 int fnn_prof_enable(fnn_handle* h, int on) { if (!h) return FNN_ERR_ARG; h->prof = on != 0; return FNN_OK; }

@@ -17,6 +17,7 @@
 #include "../../include/fnn_hip.h"
 #include "../../include/ipnn_hip.h"
 #include "arg_ring.h"
+#include "group_call.h"
 #include "fnn_kernels.hip.h"
 #include "sparse_rows.hip.h"
 #include "metrics.hip.h"
@@ -1682,7 +1683,7 @@ struct ipnn_handle {
     // ipnn_predict_multi / ipnn_eval_multi, used when this handle is hs[0]: the argument ring, the event that joins the members'
     // streams, and the scratch of one group of models (predictions, metric pass, results), kept while it is large enough
     ArgRing eval_ring{sizeof(IpGroupArg<float>), 4 * IPNN_EVAL_MAX_MODELS};
-    hipEvent_t gjoin = nullptr; char* ev_scratch = nullptr; size_t ev_scratch_bytes = 0;
+    hipEvent_t join = nullptr; char* ev_scratch = nullptr; size_t ev_scratch_bytes = 0;
     std::map<std::string, std::vector<std::pair<hipEvent_t, hipEvent_t>>> prof_ev;
 };
 
@@ -2392,65 +2393,26 @@ int ip_run(ipnn_handle* h, IpCall c)
 }
 
 // --------------------------------------------------------------------------------------------- many models on one feed
-// ipnn_predict_multi / ipnn_eval_multi ("Evaluating many inner-product models").  The group of one call:
-// its refusals (the entry point's name in front, left with hs[0], or with ipnn_last_error(NULL) without a usable hs[0]) and
-// its streams -- everything runs on hs[0]'s, which first waits for every other member's; they wait for the call's last launch.
-struct IpGroup {
-    ipnn_handle* const* hs; int n; ipnn_handle* h0; const char* name;
-    std::vector<hipStream_t> others;                 // the streams that are not hs[0]'s, each once
-    bool entered = false;
-    IpGroup(ipnn_handle* const* hs_, int n_, const char* name_)
-        : hs(hs_), n(n_), h0(hs_ && n_ >= 1 && n_ <= IPNN_EVAL_MAX_MODELS ? hs_[0] : nullptr), name(name_) {}
-    ~IpGroup() { leave(); }
-    int refuse(int code, const std::string& msg) const { (h0 ? h0->err : g_ip_err) = std::string(name) + ": " + msg; return code; }
-    static std::string at(const std::string& what, int m) { return "model " + std::to_string(m) + ": " + what; }
-    int enter()
-    {
-        IHK(h0, hipSetDevice(h0->dev));
-        // a member's deferred dense update and sparse-row chain (IPNN_UPDATE_SIDE=1) join its own stream first
-        for (int m = 0; m < n; ++m) {
-            const int rc = ip_join(hs[m]);
-            if (rc != FNN_OK) { if (hs[m] != h0) refuse(rc, at(hs[m]->err, m)); return rc; }
-        }
-        for (int m = 1; m < n; ++m) if (hs[m]->st != h0->st) others.push_back(hs[m]->st);
-        std::sort(others.begin(), others.end());
-        others.erase(std::unique(others.begin(), others.end()), others.end());
-        if (!others.empty() && !h0->gjoin) IHK(h0, hipEventCreateWithFlags(&h0->gjoin, hipEventDisableTiming));
-        entered = true;
-        for (hipStream_t o : others) {
-            IHK(h0, hipEventRecord(h0->gjoin, o));
-            IHK(h0, hipStreamWaitEvent(h0->st, h0->gjoin, 0));
-        }
-        return FNN_OK;
-    }
-    int leave()
-    {
-        if (!entered) return FNN_OK;
-        entered = false;
-        if (others.empty()) return FNN_OK;
-        IHK(h0, hipEventRecord(h0->gjoin, h0->st));
-        for (hipStream_t o : others) IHK(h0, hipStreamWaitEvent(o, h0->gjoin, 0));
-        return FNN_OK;
-    }
+// ipnn_predict_multi / ipnn_eval_multi ("Evaluating many inner-product models").  The group of one call is
+// a GroupCall (group_call.h), refusals without a usable hs[0] left with ipnn_last_error(NULL).  In front of the stream join
+// every member's deferred dense update and sparse-row chain (IPNN_UPDATE_SIDE=1) join its own stream: ip_join.
+struct IpGroup : GroupCall<ipnn_handle> {
+    IpGroup(ipnn_handle* const* hs_, int n_, const char* name_) : GroupCall(name_, hs_, n_, IPNN_EVAL_MAX_MODELS, g_ip_err, ip_join) {}
 };
 
 // What both calls refuse, all of it before anything is launched or written.
 int ip_group_check(const IpGroup& g, const int32_t* ids, bool need_y, const int32_t* y, int64_t N, bool need_p, float* const* p_out)
 {
+    IRC(g.check_list(nullptr));                                 // (the same handle twice: this family's own rule, below)
     ipnn_handle* const* hs = g.hs;
     const int M = g.n;
-    if (!hs) return g.refuse(FNN_ERR_ARG, "null hs");
-    if (M < 1 || M > IPNN_EVAL_MAX_MODELS) return g.refuse(FNN_ERR_ARG, "n_models must be in [1, " + std::to_string(IPNN_EVAL_MAX_MODELS) + "]");
-    for (int m = 0; m < M; ++m) if (!hs[m]) return g.refuse(FNN_ERR_ARG, g.at("null handle", m));
-    const ipnn_handle* h0 = g.h0;
-    for (int m = 1; m < M; ++m)
-        if (hs[m]->F != h0->F || hs[m]->dev != h0->dev) return g.refuse(FNN_ERR_ARG, g.at("n_fields or device differs from model 0's", m));
     if (!ids) return g.refuse(FNN_ERR_ARG, "null ids");
     if (need_y && !y) return g.refuse(FNN_ERR_ARG, "null y");
     if (need_p && !p_out) return g.refuse(FNN_ERR_ARG, "null p_out");
     if (need_p) for (int m = 0; m < M; ++m) if (!p_out[m]) return g.refuse(FNN_ERR_ARG, g.at("null p_out", m));
     if (N < 1 || N > ((int64_t)1 << 30)) return g.refuse(FNN_ERR_ARG, "N must be in [1, 2^30]");
-    {   // a member's a[0] is the scratch of the group launch: no handle twice
+    {   // A member's a[0] is the scratch of the group launch: no handle twice.  Not GroupCall::check_list's rule: this one comes
+        // after the arguments' checks, names both places and reports the pair with the smallest second index.
         std::vector<std::pair<const ipnn_handle*, int>> v;
         for (int m = 0; m < M; ++m) v.emplace_back(hs[m], m);
         std::sort(v.begin(), v.end());
@@ -2576,25 +2538,18 @@ int ip_group_forward(const IpGroup& g, ipnn_handle* const* hs, int n, int base, 
     IHK(h0, hipGetLastError());
     for (int m : own) {
         ipnn_handle* h = hs[m];
-        const hipStream_t mine = h->st;
-        h->st = st;
-        int rc = FNN_OK;
-        for (int64_t lo = 0; rc == FNN_OK && lo < N; lo += h->Bmax) {
-            const int B = (int)std::min<int64_t>(h->Bmax, N - lo);
-            const IpCall call{ids + lo * F, wts ? wts + lo * F : nullptr, nullptr, B, nullptr, nullptr, nullptr, p[m] + lo, false};
-            rc = h->bf16 ? ip_run<bf16_t>(h, call) : ip_run<float>(h, call);
-        }
-        h->st = mine;
-        if (rc != FNN_OK) { if (h != h0) g.refuse(rc, g.at(h->err, base + m)); return rc; }
+        const int rc = on_stream(h, st, [&] {
+            int r = FNN_OK;
+            for (int64_t lo = 0; r == FNN_OK && lo < N; lo += h->Bmax) {
+                const int B = (int)std::min<int64_t>(h->Bmax, N - lo);
+                const IpCall call{ids + lo * F, wts ? wts + lo * F : nullptr, nullptr, B, nullptr, nullptr, nullptr, p[m] + lo, false};
+                r = h->bf16 ? ip_run<bf16_t>(h, call) : ip_run<float>(h, call);
+            }
+            return r;
+        });
+        if (rc != FNN_OK) return g.member_failed(rc, h, base + m);
     }
     return FNN_OK;
-}
-
-inline size_t up256(size_t b) { return (b + 255) / 256 * 256; }
-// scratch of a group of g models: p [g][N], the metric pass's, out [g], flags [g], n_pos
-size_t ip_eval_scratch_bytes(int g, int64_t N)
-{
-    return up256((size_t)g * (size_t)N * 4) + up256(metrics_multi_bytes(g, N)) + up256((size_t)g * sizeof(MetricOut)) + up256((size_t)g * 4) + 256;
 }
 
 }  // namespace
@@ -2728,7 +2683,7 @@ int ipnn_destroy(ipnn_handle* h)
     for (void* p : ptrs) if (p) hipFree(p);
     if (h->ev_scratch) hipFree(h->ev_scratch);
     ring_release(h->eval_ring);
-    if (h->gjoin) hipEventDestroy(h->gjoin);
+    if (h->join) hipEventDestroy(h->join);
     row_group_free(h->rg);
     for (auto& kv : h->prof_ev) for (auto& p : kv.second) { hipEventDestroy(p.first); hipEventDestroy(p.second); }
     if (h->st2) { hipStreamSynchronize(h->st2); hipStreamDestroy(h->st2); }
@@ -3009,7 +2964,7 @@ int ipnn_eval_multi(ipnn_handle* const* hs, int n_models, const int32_t* ids, co
         // one model: the solo evaluation (measured: the group path is not faster there -- profiles/ipnn_eval_multi_bench.json --
         // and the solo strip forms fill the chip better), reported as the group path reports
         double out[4] = {0, 0, 0, 0};
-        std::string merr, msg;
+        std::string merr;
         int mrc = 0;
         IRC(ip_eval_solo(h0, ids, wts, y, N, p_out ? p_out[0] : nullptr, out, &mrc, &merr));
         const double nan = std::nan("");
@@ -3019,95 +2974,41 @@ int ipnn_eval_multi(ipnn_handle* const* hs, int n_models, const int32_t* ids, co
         if (status) status[0] = mrc == -3 ? FNN_ERR_RANGE : FNN_OK;
         const int rc = ipnn_sync(h0);
         if (rc != FNN_OK && rc != FNN_ERR_RANGE) return rc;
-        if (mrc == -3) msg += "predictions NaN or outside [0, 1] in model(s) 0";
-        if (rc == FNN_ERR_RANGE) msg += std::string(msg.empty() ? "" : "; ") + "feature id outside [0, n_rows) in model(s) 0";
-        if (mrc == -2) msg += std::string(msg.empty() ? "" : "; ") + "only one class present in y (roc_auc_score raises ValueError)";
-        if (!msg.empty()) return g.refuse(FNN_ERR_RANGE, msg);
-        return FNN_OK;
+        const std::string msg = eval_verdict(mrc == -3 ? "0" : "", rc == FNN_ERR_RANGE ? "0" : "", mrc == -2, "[0, n_rows)");
+        return msg.empty() ? FNN_OK : g.refuse(FNN_ERR_RANGE, msg);
     }
-    size_t cap = (size_t)1 << 30;
-    if (const char* e = getenv("IPNN_EVAL_SCRATCH_BYTES")) { const long long c = atoll(e); if (c >= 1) cap = (size_t)c; }
-    int G = n_models;
-    {
-        const size_t one = ip_eval_scratch_bytes(1, N);
-        if ((size_t)G > cap / one) G = (int)(cap / one);
-        if (G < 1) G = 1;
-        while (G > 1 && ip_eval_scratch_bytes(G, N) > cap) --G;
-    }
+    const int G = eval_group_size(n_models, N, "IPNN_EVAL_SCRATCH_BYTES");
     IRC(g.enter());
     const hipStream_t st = h0->st;
-    const size_t need = ip_eval_scratch_bytes(G, N);
+    const size_t need = EvalScratch::bytes(G, N);                     // hs[0]'s buffer, grown to the largest call so far
     if (h0->ev_scratch_bytes < need) {                                // (the last user of the old one, an earlier call, has synchronised)
         if (h0->ev_scratch) { hipFree(h0->ev_scratch); h0->ev_scratch = nullptr; h0->ev_scratch_bytes = 0; }
         IHK(h0, hipMalloc((void**)&h0->ev_scratch, need));
         h0->ev_scratch_bytes = need;
     }
-    char* scratch = h0->ev_scratch;
-    float* p_d = reinterpret_cast<float*>(scratch);
-    char* ms = scratch + up256((size_t)G * (size_t)N * 4);
-    MetricOut* out_d = reinterpret_cast<MetricOut*>(ms + up256(metrics_multi_bytes(G, N)));
-    int* flags_d = reinterpret_cast<int*>(reinterpret_cast<char*>(out_d) + up256((size_t)G * sizeof(MetricOut)));
-    unsigned long long* npos_d = reinterpret_cast<unsigned long long*>(reinterpret_cast<char*>(flags_d) + up256((size_t)G * 4));
-    std::vector<MetricOut> ho(G);
-    std::vector<int> hf(G);
-    std::vector<float*> pp(G);
-    unsigned long long n_pos = 0;
-    std::string bad, range;
     const size_t elem = h0->eval_ring.elem;
-    auto groups = [&]() -> int {
-        for (int g0 = 0; g0 < n_models; g0 += G) {
-            const int n = std::min(G, n_models - g0);
-            for (int m = 0; m < n; ++m) pp[m] = p_d + (size_t)m * (size_t)N;
-            IRC(ip_group_forward(g, hs + g0, n, g0, ids, wts, N, pp.data()));
-            IHK(h0, metrics_multi(st, p_d, y, N, n, ms, g0 == 0, npos_d, out_d));
-            {   // the members' range bits, read and cleared on the device
-                size_t slot = 0;
-                IHK(h0, ring_take(h0->eval_ring, (size_t)n, &slot));
-                char* a = static_cast<char*>(h0->eval_ring.host) + slot * elem;
-                for (int m = 0; m < n; ++m) {
-                    IpGroupArg<float> fa{};
-                    fa.err = hs[g0 + m]->err_flag; fa.model = m;
-                    memcpy(a + (size_t)m * elem, &fa, sizeof(fa));
-                }
-                IHK(h0, ring_send(h0->eval_ring, slot, (size_t)n, st));
-                hipLaunchKernelGGL(k_ip_gflags, dim3(1), dim3(256), 0, st, static_cast<const char*>(h0->eval_ring.dev) + slot * elem, elem, n, flags_d);
-                IHK(h0, hipGetLastError());
-            }
-            if (p_out) for (int m = 0; m < n; ++m)
-                if (p_out[g0 + m]) IHK(h0, hipMemcpyAsync(p_out[g0 + m], pp[m], (size_t)N * 4, hipMemcpyDeviceToDevice, st));
-            IHK(h0, hipMemcpyAsync(ho.data(), out_d, (size_t)n * sizeof(MetricOut), hipMemcpyDeviceToHost, st));
-            IHK(h0, hipMemcpyAsync(hf.data(), flags_d, (size_t)n * 4, hipMemcpyDeviceToHost, st));
-            if (g0 == 0) IHK(h0, hipMemcpyAsync(&n_pos, npos_d, 8, hipMemcpyDeviceToHost, st));
-            IHK(h0, hipStreamSynchronize(st));                        // the group's one synchronisation
-            const double np_ = (double)n_pos, nn = (double)(N - (int64_t)n_pos);
-            const bool two = n_pos > 0 && (int64_t)n_pos < N;
-            for (int m = 0; m < n; ++m) {
-                const MetricOut& o = ho[m];
-                const int i = g0 + m;
-                double v[3] = {std::nan(""), std::nan(""), std::nan("")};
-                if (!o.n_bad) {
-                    if (two) v[0] = (double)o.auc_sum / (2.0 * np_ * nn);
-                    v[1] = std::sqrt(o.se / (double)N); v[2] = o.ll / (double)N;
-                } else bad += (bad.empty() ? "" : ", ") + std::to_string(i);
-                if (hf[m]) range += (range.empty() ? "" : ", ") + std::to_string(i);
-                if (auc) auc[i] = v[0];
-                if (rmse) rmse[i] = v[1];
-                if (logloss) logloss[i] = v[2];
-                if (status) status[i] = o.n_bad ? FNN_ERR_RANGE : FNN_OK;
-            }
+    const EvalForward forward = [&](int g0, int n, float* const* p) { return ip_group_forward(g, hs + g0, n, g0, ids, wts, N, p); };
+    const EvalFlags flags = [&](int g0, int n, int* flags_d) {        // the members' range bits, read and cleared on the device
+        size_t slot = 0;
+        IHK(h0, ring_take(h0->eval_ring, (size_t)n, &slot));
+        char* a = static_cast<char*>(h0->eval_ring.host) + slot * elem;
+        for (int m = 0; m < n; ++m) {
+            IpGroupArg<float> fa{};
+            fa.err = hs[g0 + m]->err_flag; fa.model = m;
+            memcpy(a + (size_t)m * elem, &fa, sizeof(fa));
         }
+        IHK(h0, ring_send(h0->eval_ring, slot, (size_t)n, st));
+        hipLaunchKernelGGL(k_ip_gflags, dim3(1), dim3(256), 0, st, static_cast<const char*>(h0->eval_ring.dev) + slot * elem, elem, n, flags_d);
+        IHK(h0, hipGetLastError());
         return FNN_OK;
     };
-    const int rc = groups();
+    EvalFound found;
+    const int rc = eval_groups(st, n_models, G, y, N, h0->ev_scratch, forward, flags, EvalOut{auc, rmse, logloss, status, p_out}, found, h0->err);
     const int rj = g.leave();
-    if (rc != FNN_OK) { hipStreamSynchronize(st); return rc; }       // nothing may still be using the scratch
+    if (rc != FNN_OK) return rc;                                      // (eval_groups has drained the stream: the buffer is free for the next call)
     if (rj != FNN_OK) return rj;
-    std::string msg;
-    if (!bad.empty()) msg += "predictions NaN or outside [0, 1] in model(s) " + bad;
-    if (!range.empty()) msg += std::string(msg.empty() ? "" : "; ") + "feature id outside [0, n_rows) in model(s) " + range;
-    if (n_pos == 0 || (int64_t)n_pos == N) msg += std::string(msg.empty() ? "" : "; ") + "only one class present in y (roc_auc_score raises ValueError)";
-    if (!msg.empty()) return g.refuse(FNN_ERR_RANGE, msg);
-    return FNN_OK;
+    const std::string msg = eval_verdict(found.bad, found.range, found.n_pos, N, "[0, n_rows)");
+    return msg.empty() ? FNN_OK : g.refuse(FNN_ERR_RANGE, msg);
 }
 
 int ipnn_prof_enable(ipnn_handle* h, int on)

@@ -395,7 +395,6 @@ done:
 
 // ---- the metrics of several models on one feed (metrics.hip.h: metrics_multi)
 namespace {
-inline size_t up256(size_t b) { return (b + 255) / 256 * 256; }
 inline int64_t metric_blocks(int64_t n) { return (n + (int64_t)MB * ITEMS - 1) / ((int64_t)MB * ITEMS); }
 }  // namespace
 
@@ -422,6 +421,78 @@ hipError_t metrics_multi(hipStream_t st, const float* p, const int32_t* y, int64
     hipLaunchKernelGGL(k_metric_auc_multi, dim3((unsigned)(want < 1024 ? want : 1024), (unsigned)nseg), dim3(MB), 0, st, sorted, n, n_pos, out);
     hipLaunchKernelGGL(k_metric_sum_multi, dim3((unsigned)((nseg + 63) / 64)), dim3(64), 0, st, part, nblk, nseg, out);
     return hipGetLastError();
+}
+
+// ---- the loop of the calls that evaluate many models on one feed (metrics.hip.h: eval_groups)
+namespace {
+// where the five pieces of a group's scratch start, and where the last one ends
+struct EvalLayout { size_t off[6]; };
+EvalLayout eval_layout(int G, int64_t N)
+{
+    const size_t piece[5] = {(size_t)G * (size_t)N * 4, metrics_multi_bytes(G, N), (size_t)G * sizeof(MetricOut), (size_t)G * 4, 8};
+    EvalLayout l{{0}};
+    for (int i = 0; i < 5; ++i) l.off[i + 1] = l.off[i] + up256(piece[i]);
+    return l;
+}
+}  // namespace
+
+EvalScratch::EvalScratch(int G, int64_t N, char* base)
+{
+    const EvalLayout l = eval_layout(G, N);
+    p = reinterpret_cast<float*>(base + l.off[0]);
+    metric = base + l.off[1];
+    out = reinterpret_cast<MetricOut*>(base + l.off[2]);
+    flags = reinterpret_cast<int*>(base + l.off[3]);
+    n_pos = reinterpret_cast<unsigned long long*>(base + l.off[4]);
+}
+size_t EvalScratch::bytes(int G, int64_t N) { return eval_layout(G, N).off[5]; }
+
+int eval_group_size(int n_models, int64_t N, const char* cap_env)
+{
+    return eval_group_size(n_models, eval_scratch_cap(cap_env), [N](int g) { return EvalScratch::bytes(g, N); });
+}
+
+int eval_groups(hipStream_t st, int n_models, int G, const int32_t* y, int64_t N, char* scratch, const EvalForward& forward,
+                const EvalFlags& flags, const EvalOut& out, EvalFound& found, std::string& err)
+{
+    const EvalScratch s(G, N, scratch);
+    std::vector<MetricOut> ho(G);
+    std::vector<int> hf(G);
+    std::vector<float*> pp(G);
+    for (int m = 0; m < G; ++m) pp[m] = s.p + (size_t)m * (size_t)N;
+    // an error leaves the lambda, and the stream is drained behind it
+    auto groups = [&]() -> int {
+#define EK(expr) do { hipError_t e_ = (expr); if (e_ != hipSuccess) { err = std::string(#expr) + ": " + hipGetErrorString(e_); return FNN_ERR_HIP; } } while (0)
+        for (int g0 = 0; g0 < n_models; g0 += G) {
+            const int n = n_models - g0 < G ? n_models - g0 : G;
+            int rc = forward(g0, n, pp.data());
+            if (rc != FNN_OK) return rc;
+            EK(metrics_multi(st, s.p, y, N, n, s.metric, g0 == 0, s.n_pos, s.out));
+            rc = flags(g0, n, s.flags);
+            if (rc != FNN_OK) return rc;
+            if (out.p_out) for (int m = 0; m < n; ++m)
+                if (out.p_out[g0 + m]) EK(hipMemcpyAsync(out.p_out[g0 + m], pp[m], (size_t)N * 4, hipMemcpyDeviceToDevice, st));
+            EK(hipMemcpyAsync(ho.data(), s.out, (size_t)n * sizeof(MetricOut), hipMemcpyDeviceToHost, st));
+            EK(hipMemcpyAsync(hf.data(), s.flags, (size_t)n * 4, hipMemcpyDeviceToHost, st));
+            if (g0 == 0) EK(hipMemcpyAsync(&found.n_pos, s.n_pos, 8, hipMemcpyDeviceToHost, st));
+            EK(hipStreamSynchronize(st));                             // the group's one synchronisation
+            for (int m = 0; m < n; ++m) {
+                const int i = g0 + m;
+                const EvalValues v = eval_values(ho[m], found.n_pos, N);
+                if (ho[m].n_bad) eval_list_add(found.bad, i);
+                if (hf[m]) eval_list_add(found.range, i);
+                if (out.auc) out.auc[i] = v.auc;
+                if (out.rmse) out.rmse[i] = v.rmse;
+                if (out.logloss) out.logloss[i] = v.logloss;
+                if (out.status) out.status[i] = v.status;
+            }
+        }
+        return FNN_OK;
+#undef EK
+    };
+    const int rc = groups();
+    if (rc != FNN_OK) hipStreamSynchronize(st);                       // nothing may still be using the scratch
+    return rc;
 }
 
 }  // namespace fnn

@@ -2,7 +2,10 @@
 #pragma once
 #include <hip/hip_runtime.h>
 #include <stdint.h>
+#include <functional>
 #include <string>
+
+#include "eval_group.h"
 
 namespace fnn {
 // AUC (ties at 1/2, the trapezoid of sklearn.metrics.roc_auc_score), RMSE and logloss
@@ -42,10 +45,38 @@ uint32_t* radix_sort_segments32(hipStream_t st, uint32_t* keys, uint32_t* tmp, u
 // n_pos (DEVICE, one count): written when count_pos != 0 -- y is shared, so the first call over a feed counts and the later
 // ones (further groups of models) read it; the AUC pass takes n_neg from it on the device.  One class only: auc_sum stays 0.
 // scratch: metrics_multi_bytes(nseg, n) bytes, about 8.5 n per model; 1 <= n <= 2^30.
-struct MetricOut { double se, ll; unsigned long long auc_sum, n_bad; };
+// (struct MetricOut { double se, ll; unsigned long long auc_sum, n_bad; }: eval_group.h)
 size_t metrics_multi_bytes(int nseg, int64_t n);
 hipError_t metrics_multi(hipStream_t st, const float* p, const int32_t* y, int64_t n, int nseg, void* scratch, int count_pos,
                          unsigned long long* n_pos, MetricOut* out);
+
+// ---- evaluating many models on one feed: what fm_eval_multi, fnn_eval_multi and ipnn_eval_multi share (DESIGN.md section 4,
+// "The group calls' shared host side").  The models go in groups of G, each group through one scratch allocation.
+// The scratch of a group of G models on N lines, carved from `base` in pieces of up256(): the predictions p [G][N], the metric
+// pass's own scratch, out [G], the range flags [G] and the feed's count of positives.
+struct EvalScratch {
+    float* p; void* metric; MetricOut* out; int* flags; unsigned long long* n_pos;
+    EvalScratch(int G, int64_t N, char* base);
+    static size_t bytes(int G, int64_t N);
+};
+// The group size of a call on n_models: as many as fit EvalScratch::bytes under $cap_env (default 2^30), one at the least.
+int eval_group_size(int n_models, int64_t N, const char* cap_env);
+// Where the metrics go ([n_models] each, any of them null) and, where given, the predictions (p_out null, or DEVICE [N] / null each).
+struct EvalOut { double *auc, *rmse, *logloss; int* status; float* const* p_out; };
+// What the verdict (eval_verdict) is made of: the models with bad predictions, those with ids out of range, the feed's positives.
+struct EvalFound { std::string bad, range; unsigned long long n_pos = 0; };
+// The loop over the groups of G on stream `st`, `scratch` (DEVICE, EvalScratch::bytes(G, N)) the caller's.  Per group of members
+// g0 .. g0 + n:  forward(g0, n, p) launches their predictions into p[0 .. n) and flags(g0, n, flags_d) the family's kernel that
+// reads (and clears) their range flags into flags_d[0 .. n) -- both return FNN_OK or the failure's code, its text left where the
+// family leaves it; then metrics_multi (which counts the positives in the first group only), the copies to out.p_out, the copies
+// home and the group's ONE synchronisation, after which out and `found` take the group's results.  A HIP error of the loop's own
+// returns FNN_ERR_HIP with its text in `err`.  On every error return the stream has been synchronised: nothing still uses the
+// scratch, which the caller may free or reuse at once.
+using EvalForward = std::function<int(int g0, int n, float* const* p)>;
+using EvalFlags = std::function<int(int g0, int n, int* flags_d)>;
+int eval_groups(hipStream_t st, int n_models, int G, const int32_t* y, int64_t N, char* scratch, const EvalForward& forward,
+                const EvalFlags& flags, const EvalOut& out, EvalFound& found, std::string& err);
+
 // Sorted keys `row << 20 | index` (row = 2^31 - 1: invalid, sorted last) of `nseg` segments of `n` -> rec[g * n + pos] =
 // {row, index, s, e}, [s, e) = the positions of the row's run inside its segment; {-1, 0, 0, 0} for invalid entries.
 constexpr int GROUP_INDEX_BITS = 20;
