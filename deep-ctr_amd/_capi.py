@@ -140,6 +140,7 @@ IPNN_SIGNATURES = {
     "ipnn_predict_multi": (_i, [_vp, _i, _vp, _vp, _i64, _vp]),
     "ipnn_eval_multi": (_i, [_vp, _i, _vp, _vp, _vp, _i64, C.POINTER(C.c_double), C.POINTER(C.c_double), C.POINTER(C.c_double),
                              C.POINTER(C.c_int), _vp]),
+    "ipnn_train_step_multi": (_i, [_vp, _i, _vp, _vp, _vp, _i, _vp, C.POINTER(C.c_uint64), C.POINTER(C.c_uint64), _vp, C.POINTER(_f)]),
     "ipnn_prof_enable": (_i, [_vp, _i]),
     "ipnn_prof_get": (_i, [_vp, C.c_char_p, C.POINTER(C.c_double)]),
 }

@@ -716,14 +716,16 @@ constexpr int GEMM_GROUP_MAX = 9;
 struct GemmGroupProb { const void* A; const void* B; float* out; int mt16, nt16, nkt_all, nkt, ldo, gx, gy; };
 struct GemmGroupArgs { GemmGroupProb p[GEMM_GROUP_MAX]; int wg0[GEMM_GROUP_MAX + 1]; int n; size_t zstride; int xcd; int wt; };   // wt: slabs written through
 
+// (the body of k_gemm_group, and of the group form that takes the arguments from a device array: wg = the workgroup's index in
+// the launch of ONE set of problems)
 template <typename T, int TM, int TN>
-static __global__ __launch_bounds__(256) void k_gemm_group(const GemmGroupArgs g)
+__device__ __forceinline__ void gemm_group_body(const GemmGroupArgs& g, const int wg)
 {
     int q = 0;
 #pragma unroll
-    for (int i = 1; i < GEMM_GROUP_MAX; ++i) q += (i < g.n && (int)blockIdx.x >= g.wg0[i]) ? 1 : 0;
+    for (int i = 1; i < GEMM_GROUP_MAX; ++i) q += (i < g.n && wg >= g.wg0[i]) ? 1 : 0;
     const GemmGroupProb& pr = g.p[q];
-    int local = (int)blockIdx.x - g.wg0[q];
+    int local = wg - g.wg0[q];
     if (g.xcd) {
         // XCD-aware order inside a problem: hardware workgroup ids that differ by a multiple of 8 share an XCD; the n tiles of
         // the problem are dealt so that each of those 8 classes owns one contiguous run of logical tiles (x fastest: a run
@@ -735,6 +737,8 @@ static __global__ __launch_bounds__(256) void k_gemm_group(const GemmGroupArgs g
     const EpiF32W e{pr.out, pr.ldo, g.zstride, g.wt != 0};
     gemm_ft_body<T, TM, TN, EpiF32W>(static_cast<const T*>(pr.A), static_cast<const T*>(pr.B), pr.mt16, pr.nt16, pr.nkt_all, pr.nkt, e, bx, by, bz);
 }
+template <typename T, int TM, int TN>
+static __global__ __launch_bounds__(256) void k_gemm_group(const GemmGroupArgs g) { gemm_group_body<T, TM, TN>(g, (int)blockIdx.x); }
 
 // dynamic LDS of k_gemm_ft for a tile epilogue: 4 wave-private [16][16 TN + 8] tiles
 template <typename T, int TN> constexpr size_t gemm_ft_lds() { return (size_t)4 * 16 * (16 * TN + 8) * sizeof(T); }

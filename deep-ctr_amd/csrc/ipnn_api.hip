@@ -216,51 +216,7 @@ template <bool WV = false>
 static __global__ __launch_bounds__(256) void k_ip_bwd(const IpBwdArgs a, const float* __restrict__ dz, float* __restrict__ gxp,
                                                         float* __restrict__ gb_part)
 {
-    extern __shared__ __align__(16) unsigned char smem[];
-    float* se = reinterpret_cast<float*>(smem);                 // [16][F*16]
-    float* sd = se + 16 * a.F * SLOT;                           // [16][D0p]
-    float* sw = sd + 16 * a.D0p;                                // [16][F] value weights (WV only)
-    const int tid = threadIdx.x, t0 = blockIdx.x * 16, F = a.F, K = a.K, B = a.B, FS = F * SLOT;
-    const int P = a.P, CB = FS + P;
-    // both tiles are contiguous in memory (16 consecutive rows): 16-byte pieces, eight loads in flight per thread before the
-    // first LDS store (a copy loop of one load -> one store per trip pays one memory round trip per trip)
-    auto fill = [&](float* dst, const float* __restrict__ src, const int n4) {
-        for (int e0 = tid; e0 < n4; e0 += 256 * 8) {
-            float4 v[8];
-#pragma unroll
-            for (int k = 0; k < 8; ++k) { const int e = e0 + 256 * k; v[k] = e < n4 ? *reinterpret_cast<const float4*>(src + 4 * (size_t)e) : make_float4(0.f, 0.f, 0.f, 0.f); }
-#pragma unroll
-            for (int k = 0; k < 8; ++k) { const int e = e0 + 256 * k; if (e < n4) *reinterpret_cast<float4*>(dst + 4 * e) = v[k]; }
-        }
-    };
-    if (a.emb) fill(se, a.emb + (size_t)t0 * FS, 16 * FS / 4);       // the raw embeddings the forward gathered
-    else ip_gather16<SLOT, 256, WV>(se, a.ids, a.table16, a.n_rows, t0, B, F, nullptr, a.wts);
-    if (WV) for (int e = tid; e < 16 * F; e += 256) sw[e] = t0 + e / F < B ? a.wts[(size_t)t0 * F + e] : 1.0f;
-    fill(sd, dz + (size_t)t0 * a.D0p, 16 * a.D0p / 4);
-    __syncthreads();
-    for (int c = tid; c < FS; c += 256) {                        // a thread owns (field f, slot l) for all 16 examples:
-        const int f = c / SLOT, l = c % SLOT;                    // the pair index is computed once per partner field
-        float g[16];
-#pragma unroll
-        for (int r = 0; r < 16; ++r) g[r] = l < K ? sd[r * a.D0p + c] : 0.f;
-        if (l < K && P) {
-            for (int j = 0; j < F; ++j) {
-                // pair (i, j), i < j, sits at FS + i*(2F - i - 1)/2 + (j - i - 1); j == f contributes nothing
-                const int i0 = f < j ? f : j, j0 = f < j ? j : f;
-                const int n = j == f ? 0 : i0 * (2 * F - i0 - 1) / 2 + (j0 - i0 - 1);
-                const float on = j == f ? 0.f : 1.f;
-#pragma unroll
-                for (int r = 0; r < 16; ++r) g[r] = fmaf(sd[r * a.D0p + FS + n] * on, se[r * FS + j * SLOT + l], g[r]);
-            }
-        }
-        if (WV) {
-#pragma unroll
-            for (int r = 0; r < 16; ++r) g[r] *= sw[r * F + f];
-        }
-#pragma unroll
-        for (int r = 0; r < 16; ++r) gxp[(size_t)(t0 + r) * a.D0p + c] = g[r];
-    }
-    if (tid == 0) { float s = 0.f; for (int r = 0; r < 16; ++r) s += sd[r * a.D0p + CB]; gb_part[blockIdx.x] = s; }
+#include "ip_bwd_code.inc.h"
 }
 
 // ------------------------------------------------------------------------------------------
@@ -730,7 +686,9 @@ template <typename T> struct EpiIpOut {      // logits (column 0), loss, delta =
                 const float z = acc[r], p = 1.0f / (1.0f + expf(-z));
                 if (logits) logits[t] = z;
                 if (p_out) p_out[t] = p;
-                if (y) { x = (p - y[t]) * gscale; loss_t[t] = fmaxf(z, 0.f) - z * y[t] + log1pf(expf(-fabsf(z))); }
+                // (the fused product spelled out: left to the compiler, the solo strip kernels fuse it and the group forms, the same
+                // code in another kernel, did not -- one rounding apart for labels other than 0 and 1)
+                if (y) { x = (p - y[t]) * gscale; loss_t[t] = fmaf(-z, y[t], fmaxf(z, 0.f)) + log1pf(expf(-fabsf(z))); }
             } else if (col == 0 && loss_t) loss_t[t] = 0.f;
             v[r] = x;
         }
@@ -1332,7 +1290,9 @@ struct MaskTArgs {
     const uint8_t* src[IPNN_MAX_HIDDEN + 1]; uint8_t* dst[IPNN_MAX_HIDDEN + 1]; int d[IPNN_MAX_HIDDEN + 1], Dp[IPNN_MAX_HIDDEN + 1];
     int tile0[IPNN_MAX_HIDDEN + 2]; int n; const int* ref0; int B, Ba, ldT; bool wt;
 };
-static __global__ __launch_bounds__(256) void k_mask_T(const MaskTArgs a)
+// (the body of k_mask_T and of its group form k_mask_T_g.  A: how the arguments arrive -- `const MaskTArgs`, the kernel's own
+// parameter, in the solo kernel; `const MaskTArgs&`, the member's record in memory, in the group form.  mask_draw_body likewise.)
+template <typename A> __device__ __forceinline__ void mask_T_body(A a)
 {
     __shared__ __align__(4) uint8_t s[64][68];          // 17 dwords per row: the 64 lanes of a byte store (one row each) spread over all banks
     int t = 0;
@@ -1364,6 +1324,7 @@ static __global__ __launch_bounds__(256) void k_mask_T(const MaskTArgs a)
         store16_sel(a.wt, a.dst[t] + mask_off(c0 + cc, t0 + 16 * q, a.ldT), make_uint4(w[0], w[1], w[2], w[3]));
     }
 }
+static __global__ __launch_bounds__(256) void k_mask_T(const MaskTArgs a) { mask_T_body<const MaskTArgs>(a); }
 
 // Drawn keep-masks (ipnn_train_step_drawn / ipnn_draw_masks): the generator that stands where k_mask_T stands.  The mask of
 // (layer t, example ex, reference column c) is one 32-bit word of Philox4x32-10 (Salmon et al., SC'11) against a threshold:
@@ -1393,7 +1354,8 @@ struct MaskDrawArgs {
     int tile0[IPNN_MAX_HIDDEN + 2]; int n; const int* ref0; int B, Ba, ldT; bool wt;
     unsigned key0, key1, step0, step1, thr; bool all;      // all: keep_prob >= 1, every element is kept
 };
-static __global__ __launch_bounds__(256) void k_mask_draw(const MaskDrawArgs a)
+// (the body of k_mask_draw and of its group form k_mask_draw_g)
+template <typename A> __device__ __forceinline__ void mask_draw_body(A a)
 {
     __shared__ __align__(16) uint8_t s[64][68];         // [column][example], 17 dwords per row (k_mask_T's tile)
     int t = 0;
@@ -1439,6 +1401,7 @@ static __global__ __launch_bounds__(256) void k_mask_draw(const MaskDrawArgs a)
         if (ex < a.B) dR[(size_t)ex * d + sc] = s[cx][r];
     }
 }
+static __global__ __launch_bounds__(256) void k_mask_draw(const MaskDrawArgs a) { mask_draw_body<const MaskDrawArgs>(a); }
 
 // W_t <- W_t - lr * sum of slabs; refresh both tiled shadows.  Layer 1 rows are in slot layout.
 template <typename T>
@@ -1502,8 +1465,10 @@ struct IpUpdArgs {
 
 // The scalar b of z1 (python/FNN_IP_L7.py:104-114): its gradient is the sum of the per-workgroup partials of k_ip_bwd.  A launch
 // of its own on the side stream, right behind k_ip_bwd, so that the dense update on the main stream depends on nothing there.
-static __global__ __launch_bounds__(256) void k_ip_b_update(float* __restrict__ b, const float* __restrict__ gb_part, int ngb, int opt,
-                                                            float* __restrict__ bmv, float lr, float beta1, float beta2, float eps, const int* __restrict__ err)
+struct IpBArgs { float* b; const float* gb_part; int ngb, opt; float* bmv; float lr, beta1, beta2, eps; const int* err; };
+// (the body of k_ip_b_update and of its group form k_ip_b_update_g)
+__device__ __forceinline__ void ip_b_update_body(float* __restrict__ b, const float* __restrict__ gb_part, int ngb, int opt,
+                                                 float* __restrict__ bmv, float lr, float beta1, float beta2, float eps, const int* __restrict__ err)
 {
     __shared__ float sg[256];
     if (*err & 2) return;
@@ -1518,82 +1483,137 @@ static __global__ __launch_bounds__(256) void k_ip_b_update(float* __restrict__ 
         else *b -= lr * sg[0];
     }
 }
+static __global__ __launch_bounds__(256) void k_ip_b_update(float* __restrict__ b, const float* __restrict__ gb_part, int ngb, int opt,
+                                                            float* __restrict__ bmv, float lr, float beta1, float beta2, float eps, const int* __restrict__ err)
+{
+    ip_b_update_body(b, gb_part, ngb, opt, bmv, lr, beta1, beta2, eps, err);
+}
 
+#define UPDATE_ALL_DONE(loss) do { } while (0)
 template <typename T>
 static __global__ __launch_bounds__(256) void k_ip_update_all(const IpUpdArgs u)
 {
-    if (blockIdx.x == gridDim.x - 1) {               // scalar tail: the loss, a fixed-shape tree (b: k_ip_b_update)
-        __shared__ float sl[256];
-        sl[threadIdx.x] = strided_sum256(u.loss_t, u.Ba); __syncthreads();
-        for (int o = 128; o > 0; o >>= 1) {
-            if ((int)threadIdx.x < o) sl[threadIdx.x] += sl[threadIdx.x + o];
-            __syncthreads();
-        }
-        if (threadIdx.x == 0) *u.loss_sum = sl[0];
-        return;
-    }
-    // A workgroup owns a 64 x 64 tile of one layer's W (row lengths are multiples of 64); a thread 4 consecutive elements
-    // of 4 rows: 16-byte slab / master / state accesses and 8-byte pieces of the backward shadow (k = column).  The forward
-    // shadow has k = row: the tile goes through LDS transposed and leaves as whole 16-byte lane slots.
-    typedef typename Traits<T>::frag frag;
-    constexpr int EPL = Traits<T>::EPL;
-    __shared__ __align__(16) T sT[64][64 + EPL];                 // [column][row], padded
-    const size_t tile = blockIdx.x;
-    if (tile * 4096 >= u.off[u.n]) return;
-    if (*u.err & 2) return;                                      // a strip pair gave up (StripDuo): the gradients are garbage, the weights stay
-    int t = 0;
-#pragma unroll
-    for (int q = 1; q <= IPNN_MAX_HIDDEN; ++q) t += (q < u.n && tile * 4096 >= u.off[q]) ? 1 : 0;
-    const int Dout = u.Dout[t], Din = u.Din[t], ntc = Dout / 64;
-    const int lt = (int)(tile - u.off[t] / 4096), r0 = (lt / ntc) * 64, c0 = (lt % ntc) * 64;
-    const int cq = (threadIdx.x & 15) * 4, sk = u.sk[t];
-    T* wb = static_cast<T*>(u.wb[t]);
-    // the split-K slabs of the thread's 4 x 4 elements, summed in slab order: the loads of four slabs x four rows are issued
-    // together (a `for z: load, add` loop pays one memory round trip per slab and row: 21 -> 17 us for the whole launch)
-    float4 gs[4], ws[4];
-#pragma unroll
-    for (int k = 0; k < 4; ++k) {
-        gs[k] = make_float4(0.f, 0.f, 0.f, 0.f);
-        ws[k] = *reinterpret_cast<const float4*>(u.W[t] + (size_t)(r0 + (threadIdx.x >> 4) + 16 * k) * Dout + c0 + cq);
-    }
-    for (int z0 = 0; z0 < sk; z0 += 4) {
-        float4 v[4][4];
-#pragma unroll
-        for (int zz = 0; zz < 4; ++zz)
-#pragma unroll
-            for (int k = 0; k < 4; ++k) {
-                const size_t i = u.off[t] + (size_t)(r0 + (threadIdx.x >> 4) + 16 * k) * Dout + c0 + cq;
-                v[zz][k] = z0 + zz < sk ? *reinterpret_cast<const float4*>(u.slab + (size_t)(z0 + zz) * u.zstride + i) : make_float4(0.f, 0.f, 0.f, 0.f);
-            }
-#pragma unroll
-        for (int zz = 0; zz < 4; ++zz)
-#pragma unroll
-            for (int k = 0; k < 4; ++k) { gs[k].x += v[zz][k].x; gs[k].y += v[zz][k].y; gs[k].z += v[zz][k].z; gs[k].w += v[zz][k].w; }
-    }
-#pragma unroll
-    for (int k = 0; k < 4; ++k) {
-        const int r = r0 + (threadIdx.x >> 4) + 16 * k, c = c0 + cq;
-        const size_t j = (size_t)r * Dout + c;
-        const float4 g = gs[k];
-        float4 w = ws[k];
-        if (u.adam) {
-            float4 m = *reinterpret_cast<const float4*>(u.Wm[t] + j), v = *reinterpret_cast<const float4*>(u.Wv[t] + j);
-            w.x = opt_step(u.adam, w.x, g.x, m.x, v.x, u.lr, u.beta1, u.beta2, u.eps);
-            w.y = opt_step(u.adam, w.y, g.y, m.y, v.y, u.lr, u.beta1, u.beta2, u.eps);
-            w.z = opt_step(u.adam, w.z, g.z, m.z, v.z, u.lr, u.beta1, u.beta2, u.eps);
-            w.w = opt_step(u.adam, w.w, g.w, m.w, v.w, u.lr, u.beta1, u.beta2, u.eps);
-            *reinterpret_cast<float4*>(u.Wm[t] + j) = m; *reinterpret_cast<float4*>(u.Wv[t] + j) = v;
-        } else { w.x -= u.lr * g.x; w.y -= u.lr * g.y; w.z -= u.lr * g.z; w.w -= u.lr * g.w; }
-        store16_sel(u.wt, u.W[t] + j, w);                       // (written through: see store4_wt)
-        store4_sel(u.wt, wb + ft_off<T>(r, c, Dout), w.x, w.y, w.z, w.w);
-        const int rl = r - r0;
-        sT[cq][rl] = (T)w.x; sT[cq + 1][rl] = (T)w.y; sT[cq + 2][rl] = (T)w.z; sT[cq + 3][rl] = (T)w.w;
-    }
-    __syncthreads();
-    T* wf = static_cast<T*>(u.wf[t]);
-    for (int e = threadIdx.x; e < 64 * (64 / EPL); e += 256) {      // (column, group of EPL rows): one lane slot of wf
-        const int cl = e & 63, g8 = e >> 6;
-        store16_sel(u.wt, wf + ft_off<T>(c0 + cl, r0 + g8 * EPL, Din), *reinterpret_cast<const frag*>(&sT[cl][g8 * EPL]));
+#include "ip_update_all_code.inc.h"
+}
+#undef UPDATE_ALL_DONE
+
+// ------------------------------------------------------------------------------------------
+// Group forms of the training step (ipnn_train_step_multi): every stage of the step for the members of one launch class in ONE
+// launch, the MODEL as blockIdx.y.  A workgroup reads its member's record (IpStepArg, sent through hs[0]'s step ring) and runs
+// the body the solo kernel runs; blockIdx.x stays what it is in the solo launch.  A member whose extent in x is smaller than the
+// grid's returns at once.  The strips are the one-workgroup-per-strip form over the whole stack (duo.on = 0, no tail split,
+// warm = 0): a group grid holds more workgroups than the chip holds at once, so no workgroup may wait for another.
+// ------------------------------------------------------------------------------------------
+template <typename T> struct IpStepArg {
+    int model; float* pack;                                      // the member's place in the call; its two floats of the packed results (or null)
+    int n_mask, n_scat1, n_wg;                                   // the member's own extents in x: mask tiles, level-1 workgroups, weight-gradient tiles
+    int drawn;                                                   // 1: md (the library's draw), 0: mt (the caller's masks)
+    MaskDrawArgs md; MaskTArgs mt;
+    IpFwdArgs f; T* a0; T* a0T; float* emb;                      // the gather with its inner products
+    StripFwdArgs<T> s; StripBwdArgs<T> sb;                       // the stack, both directions
+    IpBwdArgs ib; const float* dz0; float* gxp; float* gb_part;  // the inner products' backward
+    IpBArgs bu;                                                  // b
+    ScatArgs sa;                                                 // the sparse rows, both levels
+    GemmGroupArgs g;                                             // the weight gradients
+    IpUpdArgs u;                                                 // the dense update and the loss sum
+};
+static_assert(sizeof(IpStepArg<float>) == sizeof(IpStepArg<bf16_t>), "one ring element for both element types");
+
+template <typename T>
+static __global__ __launch_bounds__(256) void k_mask_draw_g(const IpStepArg<T>* __restrict__ g)
+{
+    if ((int)blockIdx.x >= g[blockIdx.y].n_mask || !g[blockIdx.y].drawn) return;
+    mask_draw_body<const MaskDrawArgs&>(g[blockIdx.y].md);
+}
+template <typename T>
+static __global__ __launch_bounds__(256) void k_mask_T_g(const IpStepArg<T>* __restrict__ g)
+{
+    if ((int)blockIdx.x >= g[blockIdx.y].n_mask || g[blockIdx.y].drawn) return;
+    mask_T_body<const MaskTArgs&>(g[blockIdx.y].mt);
+}
+template <typename T, int NT, bool WV>
+static __global__ __launch_bounds__(NT) void k_ip_fwd_tg(const IpStepArg<T>* __restrict__ g)
+{
+    const IpFwdArgs a = g[blockIdx.y].f;
+    ip_fwd_body<T, NT, WV, true>(a, g[blockIdx.y].a0, g[blockIdx.y].a0T, g[blockIdx.y].emb);
+}
+template <typename T, int RT>
+static __global__ __launch_bounds__(64 * STRIP_NW) void k_ip_strip_fwd_tg(const IpStepArg<T>* __restrict__ g, const int maxD)
+{
+    strip_fwd_body<T, RT, 4, STRIP_NW>(g[blockIdx.y].s, maxD);
+}
+template <typename T, int RT>
+static __global__ __launch_bounds__(64 * STRIP_NW) void k_ip_strip_bwd_g(const IpStepArg<T>* __restrict__ g, const int maxD)
+{
+    strip_bwd_body<T, RT, 4, STRIP_NW>(g[blockIdx.y].sb, maxD);
+}
+template <typename T, bool WV>
+static __global__ __launch_bounds__(256) void k_ip_bwd_g(const IpStepArg<T>* __restrict__ g)
+{
+    const IpBwdArgs a = g[blockIdx.y].ib;
+    const float* __restrict__ dz = g[blockIdx.y].dz0;
+    float* __restrict__ gxp = g[blockIdx.y].gxp;
+    float* __restrict__ gb_part = g[blockIdx.y].gb_part;
+#include "ip_bwd_code.inc.h"
+}
+// b of the SGD members, one workgroup per member; and every member's owner count at the state the sort leaves its own (0), in
+// front of level 1: a grouping class's sort prepares the count of the buffers it is given only.  An Adam / FTRL member's b is
+// k_ip_b_update's own launch, one per such member beside its table pass: inlined here, opt_step came out with its moment updates
+// unfused where the solo kernel fuses them (v_pk_mul + v_pk_add against v_pk_fma), and b ended one rounding apart.
+template <typename T>
+static __global__ __launch_bounds__(256) void k_ip_b_update_g(const IpStepArg<T>* __restrict__ g)
+{
+    const IpBArgs a = g[blockIdx.x].bu;
+    int* const oc = g[blockIdx.x].sa.owner_cnt;
+    if (threadIdx.x == 0) *oc = 0;
+    if (a.opt) return;
+    ip_b_update_body(a.b, a.gb_part, a.ngb, a.opt, a.bmv, a.lr, a.beta1, a.beta2, a.eps, a.err);
+}
+template <typename T>
+static __global__ __launch_bounds__(256) void k_ip_scat1_g(const IpStepArg<T>* __restrict__ g)
+{
+    if ((int)blockIdx.x >= g[blockIdx.y].n_scat1) return;
+    const ScatArgs sa = g[blockIdx.y].sa;
+    if (sa.form == SCAT1_SLOT) scat1_body(sa, blockIdx.x);
+    else if (sa.form == SCAT1_HALF) scat1h_body(sa, blockIdx.x);
+    else scat1q_body(sa, blockIdx.x);
+}
+template <typename T>
+static __global__ __launch_bounds__(256) void k_ip_scat2_g(const IpStepArg<T>* __restrict__ g)
+{
+    __shared__ double s_sum[16][16];
+    const ScatArgs sa = g[blockIdx.y].sa;
+    if (sa.form2 == SCAT2_WAVE) scat2w_body(sa, blockIdx.x, gridDim.x);
+    else scat2_body(sa, blockIdx.x, gridDim.x, s_sum);
+}
+template <typename T>
+static __global__ __launch_bounds__(256) void k_ip_wgrad_g(const IpStepArg<T>* __restrict__ g)
+{
+    if ((int)blockIdx.x >= g[blockIdx.y].n_wg) return;
+    gemm_group_body<T, 4, 4>(g[blockIdx.y].g, (int)blockIdx.x);
+}
+template <typename T>
+static __global__ __launch_bounds__(256) void k_ip_update_all_g(const IpStepArg<T>* __restrict__ g)
+{
+    const IpUpdArgs& u = g[blockIdx.y].u;
+    float* const pack = g[blockIdx.y].pack;
+    // with loss_sum_out: the thread that writes the member's loss sum also writes it, and the member's error word behind it (bit 1:
+    // an id outside the table; bit 2: a strip pair gave up), into the call's packed results; the word is cleared here, as ipnn_sync
+    // clears it after a solo step that returns its loss
+#define UPDATE_ALL_DONE(loss) do { if (pack) { int* e_ = const_cast<int*>(u.err); const int f_ = *e_ & 3; pack[0] = (loss); pack[1] = (float)f_; \
+                                               if (f_) atomicAnd(e_, ~f_); } } while (0)
+#include "ip_update_all_code.inc.h"
+#undef UPDATE_ALL_DONE
+}
+// the loss sums and error words of members that ran their own step inside a group call, into the packed results (one workgroup)
+static __global__ __launch_bounds__(256) void k_ip_step_pack(const char* __restrict__ args, const size_t elem, const int n)
+{
+    for (int i = threadIdx.x; i < n; i += 256) {
+        const IpStepArg<float>* g = reinterpret_cast<const IpStepArg<float>*>(args + (size_t)i * elem);
+        int* e = const_cast<int*>(g->u.err);
+        const int f = *e & 3;
+        g->pack[0] = *g->u.loss_sum; g->pack[1] = (float)f;
+        if (f) atomicAnd(e, ~f);
     }
 }
 
@@ -1684,6 +1704,10 @@ struct ipnn_handle {
     // streams, and the scratch of one group of models (predictions, metric pass, results), kept while it is large enough
     ArgRing eval_ring{sizeof(IpGroupArg<float>), 4 * IPNN_EVAL_MAX_MODELS};
     hipEvent_t join = nullptr; char* ev_scratch = nullptr; size_t ev_scratch_bytes = 0;
+    // ipnn_train_step_multi, used when this handle is hs[0]: the members' records (four calls of IPNN_STEP_MAX_MODELS members)
+    // and the packed results of one call, [n_models][2] floats (loss sum, range flag), on the device and pinned on the host
+    ArgRing step_ring{sizeof(IpStepArg<float>), 4 * IPNN_STEP_MAX_MODELS};
+    float* step_pack = nullptr; float* step_pack_host = nullptr;
     std::map<std::string, std::vector<std::pair<hipEvent_t, hipEvent_t>>> prof_ev;
 };
 
@@ -1842,6 +1866,19 @@ template <typename T> IpKernel ip_gather_fwd_g_sel(IpRows rows, bool wv, int nt)
     return wv ? IP_K(IPF_NT, k_ip_fwd_g<T, IPF_NT, true>) : IP_K(IPF_NT, k_ip_fwd_g<T, IPF_NT, false>);
 }
 template <typename T> IpKernel ip_strip_g_sel() { return IP_K(64 * STRIP_NW, k_ip_strip_fwd_g<T, sizeof(T) == 2 ? 2 : 1>); }
+// the group forms of the training step (ipnn_train_step_multi; narrow rows, up to 32 fields): the gather that also writes the T
+// layout and the embeddings, the whole stack on single strips in either direction, the inner products' backward
+template <typename T> IpKernel ip_step_gather_sel(bool wv, int nt)
+{
+    if (nt == 1024) return wv ? IP_K(1024, k_ip_fwd_tg<T, 1024, true>) : IP_K(1024, k_ip_fwd_tg<T, 1024, false>);
+    return wv ? IP_K(IPF_NT, k_ip_fwd_tg<T, IPF_NT, true>) : IP_K(IPF_NT, k_ip_fwd_tg<T, IPF_NT, false>);
+}
+template <typename T> IpKernel ip_step_strip_sel(bool bwd)
+{
+    constexpr int RT = sizeof(T) == 2 ? 2 : 1;
+    return bwd ? IP_K(64 * STRIP_NW, k_ip_strip_bwd_g<T, RT>) : IP_K(64 * STRIP_NW, k_ip_strip_fwd_tg<T, RT>);
+}
+template <typename T> IpKernel ip_step_bwd_sel(bool wv) { return wv ? IP_K(256, k_ip_bwd_g<T, true>) : IP_K(256, k_ip_bwd_g<T, false>); }
 IpKernel ip_gather_bwd_sel(IpRows rows, bool wv)
 {
     if (rows == IP_WIDE) return wv ? IP_K(256, k_ip_bwd_w<true>) : IP_K(256, k_ip_bwd_w<false>);
@@ -1866,6 +1903,11 @@ template <typename T> int ip_opt_in(ipnn_handle* h)
         IHK(h, set(ip_gather_bwd_sel(r, wv != 0), ip_rows_lds_kib(r)));
     }
     IHK(h, set(ip_strip_g_sel<T>(), RT == 2 ? 128 : 160));
+    for (int wv = 0; wv < 2; ++wv) {
+        for (int nt : {512, 1024}) IHK(h, set(ip_step_gather_sel<T>(wv != 0, nt), ip_rows_lds_kib(IP_NARROW)));
+        IHK(h, set(ip_step_bwd_sel<T>(wv != 0), ip_rows_lds_kib(IP_NARROW)));
+    }
+    for (int bwd = 0; bwd < 2; ++bwd) IHK(h, set(ip_step_strip_sel<T>(bwd != 0), RT == 2 ? 128 : 160));
     return FNN_OK;
 }
 
@@ -1999,21 +2041,33 @@ MaskDrawArgs ip_draw_args(const ipnn_handle* h, const IpDraw& dr, int B, int* ti
 // On the MAIN stream by default: a cross-stream event on the way into the first strip kernel costs more (10-20 us of wait
 // resolution, measured on the kernel trace) than the 10 us the transposition takes in line (IPNN_MASK_SIDE=1; DESIGN.md section 4
 // also tells of transposing the NEXT step's masks ahead: not kept).
+// a training step's draw: every layer's transposed mask, and layer 0's row-major as well
+MaskDrawArgs ip_step_draw_args(const ipnn_handle* h, const IpCall& c, int* tiles_out)
+{
+    MaskDrawArgs da = ip_draw_args(h, *c.draw, c.B, tiles_out);
+    for (int t = 0; t <= h->L; ++t) da.dstT[t] = h->maskT[t];
+    da.dstR[0] = h->mask0;
+    return da;
+}
+// ... and the transposition of the caller's masks
+MaskTArgs ip_step_maskT_args(const ipnn_handle* h, const IpCall& c, int* tiles_out)
+{
+    MaskTArgs ma{};
+    *tiles_out = ip_mask_layout(h, c.B, ma);
+    for (int t = 0; t <= h->L; ++t) { ma.src[t] = c.masks[t]; ma.dst[t] = h->maskT[t]; }
+    return ma;
+}
 int ip_masks(ipnn_handle* h, const IpCall& c, IpSide& side)
 {
     if (!c.drop) return FNN_OK;
     hipStream_t ms = h->kn.mask_side ? side.s : h->st;
     IpProf pm(h, "mask_t", ms);
+    int tiles = 0;
     if (c.draw) {
-        int tiles = 0;
-        MaskDrawArgs da = ip_draw_args(h, *c.draw, c.B, &tiles);
-        for (int t = 0; t <= h->L; ++t) da.dstT[t] = h->maskT[t];
-        da.dstR[0] = h->mask0;
+        const MaskDrawArgs da = ip_step_draw_args(h, c, &tiles);
         hipLaunchKernelGGL(k_mask_draw, dim3(tiles), dim3(256), 0, ms, da);
     } else {
-        MaskTArgs ma{};
-        const int tiles = ip_mask_layout(h, c.B, ma);
-        for (int t = 0; t <= h->L; ++t) { ma.src[t] = c.masks[t]; ma.dst[t] = h->maskT[t]; }
+        const MaskTArgs ma = ip_step_maskT_args(h, c, &tiles);
         hipLaunchKernelGGL(k_mask_T, dim3(tiles), dim3(256), 0, ms, ma);
     }
     if (h->kn.mask_side) IRC(side.signal(h->ev.mask));
@@ -2026,6 +2080,13 @@ void ip_sort_ids(ipnn_handle* h, const IpCall& c, hipStream_t ss)
     SortArgs so{c.ids, c.B, h->F, h->n_rows, h->rg.rec, h->rg.owner_cnt, h->F, h->skeys};
     so.merge4 = h->kn.sort_merge4;
     launch_sort(ss, h->key64, so);
+}
+
+// the 16-example gather's arguments (narrow rows, up to 32 fields)
+IpFwdArgs ip_fwd_args(const ipnn_handle* h, const IpCall& c, const uint8_t* mask0, float inv_keep)
+{
+    return IpFwdArgs{h->P, c.ids, c.B, h->F, h->K, h->table16, h->n_rows, h->b, mask0, h->d[0],
+                     inv_keep, h->cfg.act, h->Dp[0], h->ldT, h->err_flag, h->kn.fwd_skip, h->kn.wt, c.wts};
 }
 
 IpManyArgs ip_many_args(const ipnn_handle* h, const IpCall& c, const uint8_t* mask0, float inv_keep)
@@ -2055,8 +2116,7 @@ template <typename T> int ip_gather_fwd(ipnn_handle* h, const IpCall& c)
         const IpManyArgs ma = ip_many_args(h, c, c.mask0, inv_keep);
         IHK(h, ip_launch(k, c.Ba / IPM_EX, ipm_fwd_lds(h->F), h->st, ma, a0, a0T, emb));
     } else {
-        const IpFwdArgs fa{h->P, c.ids, c.B, h->F, h->K, h->table16, h->n_rows, h->b, c.mask0, h->d[0],
-                           inv_keep, h->cfg.act, h->Dp[0], h->ldT, h->err_flag, h->kn.fwd_skip, h->kn.wt, c.wts};
+        const IpFwdArgs fa = ip_fwd_args(h, c, c.mask0, inv_keep);
         IHK(h, ip_launch(k, c.Ba / 16, ip16_lds(h->F, h->Dp[0]), h->st, fa, a0, a0T, emb));
     }
     return FNN_OK;
@@ -2134,13 +2194,11 @@ template <typename T> size_t ip_tail_weights(const ipnn_handle* h, const int* Dp
 // Forward through the stack by the strip kernels: one launch, or (c.tsplit) the wide products 1 .. cut as pairs of 32-example
 // strips, a[cut] through HBM, and the tail cut + 1 .. L + 1 as 16-example strips on every CU.  A fused tail is not launched here:
 // its arguments go to the backward (*fused_tail).
-template <typename T> int ip_strips_fwd(ipnn_handle* h, const IpCall& c, StripFwdArgs<T>* fused_tail)
+// The whole stack as one strip launch, forward: everything but the pair state (duo), which is the launch site's.
+template <typename T> StripFwdArgs<T> ip_stack_fwd_args(const ipnn_handle* h, const IpCall& c)
 {
-    IpProf ps(h, "fwd");
-    const IpPlan& p = h->plan;
     const IpKnobs& kn = h->kn;
-    const int L = h->L, cut = p.cut;
-    constexpr int RT = sizeof(T) == 2 ? 2 : 1;
+    const int L = h->L;
     StripFwdArgs<T> sa{};
     sa.a0 = (const T*)h->a[0]; sa.n = L + 1;
     for (int t = 0; t <= L + 1; ++t) sa.Dp[t] = h->Dp[t];
@@ -2150,6 +2208,31 @@ template <typename T> int ip_strips_fwd(ipnn_handle* h, const IpCall& c, StripFw
     sa.dbg = h->stamps; sa.rot = kn.strip_rot; sa.sel = kn.stamp_sel;
     sa.has_out = 1; sa.finalF = nullptr; sa.warm = kn.strip_warm;
     for (int t = 0; t < STRIP_MAXP; ++t) sa.wlds[t] = -1;
+    return sa;
+}
+// ... and backward
+template <typename T> StripBwdArgs<T> ip_stack_bwd_args(const ipnn_handle* h, const IpCall& c)
+{
+    const IpKnobs& kn = h->kn;
+    const int L = h->L;
+    StripBwdArgs<T> sb{};
+    sb.dlast = (const T*)h->dl[L]; sb.n = L + 1;
+    for (int t = 0; t <= L + 1; ++t) sb.Dp[t] = h->Dp[t];
+    for (int t = 1; t <= L + 1; ++t) { sb.W[t - 1] = (const T*)h->wb[t - 1]; sb.eb[t - 1] = ip_epi_bwd<T>(h, c, t, false); }
+    sb.dbg = h->stamps ? h->stamps + (size_t)(h->ldT / 16) * 16 : nullptr; sb.rot = kn.strip_rot;
+    sb.bottom = 1; sb.finalF = nullptr; sb.warm = kn.strip_warm;
+    for (int t = 0; t < STRIP_MAXP; ++t) sb.wlds[t] = -1;
+    return sb;
+}
+
+template <typename T> int ip_strips_fwd(ipnn_handle* h, const IpCall& c, StripFwdArgs<T>* fused_tail)
+{
+    IpProf ps(h, "fwd");
+    const IpPlan& p = h->plan;
+    const IpKnobs& kn = h->kn;
+    const int L = h->L, cut = p.cut;
+    constexpr int RT = sizeof(T) == 2 ? 2 : 1;
+    StripFwdArgs<T> sa = ip_stack_fwd_args<T>(h, c);
     if (!c.tsplit) {
         sa.duo = ip_strip_duo(h, false, c.duo);
         IHK(h, ip_launch(ip_strip_sel<T>(false, RT, 4, STRIP_NW), c.nstrips * (c.duo ? 2 : 1), p.strip_lds, h->st, sa, p.maxD));
@@ -2182,13 +2265,7 @@ template <typename T> int ip_strips_bwd(ipnn_handle* h, const IpCall& c, const S
     const IpKnobs& kn = h->kn;
     const int L = h->L, cut = p.cut;
     constexpr int RT = sizeof(T) == 2 ? 2 : 1;
-    StripBwdArgs<T> sb{};
-    sb.dlast = (const T*)h->dl[L]; sb.n = L + 1;
-    for (int t = 0; t <= L + 1; ++t) sb.Dp[t] = h->Dp[t];
-    for (int t = 1; t <= L + 1; ++t) { sb.W[t - 1] = (const T*)h->wb[t - 1]; sb.eb[t - 1] = ip_epi_bwd<T>(h, c, t, false); }
-    sb.dbg = h->stamps ? h->stamps + (size_t)(h->ldT / 16) * 16 : nullptr; sb.rot = kn.strip_rot;
-    sb.bottom = 1; sb.finalF = nullptr; sb.warm = kn.strip_warm;
-    for (int t = 0; t < STRIP_MAXP; ++t) sb.wlds[t] = -1;
+    StripBwdArgs<T> sb = ip_stack_bwd_args<T>(h, c);
     if (!c.tsplit) {
         sb.duo = ip_strip_duo(h, false, c.duo);
         IHK(h, ip_launch(ip_strip_sel<T>(true, RT, 4, STRIP_NW), c.nstrips * (c.duo ? 2 : 1), p.strip_lds, h->st, sb, p.maxD));
@@ -2257,6 +2334,44 @@ template <typename T> void ip_gemms_bwd(ipnn_handle* h, const IpCall& c)       /
 // ------------------------------------------------------------------------------------------------------- after the backward pass
 // The side chain: the backward of the inner products, b, the sparse-row update and (Adam / FTRL) the table pass.  They need dz1
 // only; the weight gradients, beside them on the main stream, need the transposed operands only.
+// the step size of the step that will be the handle's adam_t-th: Adam's bias-corrected lr_t, else lr
+float ip_lr_step(const ipnn_handle* h, int64_t adam_t)
+{
+    if (!h->adam || h->ftrl) return h->cfg.lr;
+    return (float)((double)h->cfg.lr * std::sqrt(1.0 - std::pow((double)h->cfg.adam_beta2, (double)adam_t)) /
+                   (1.0 - std::pow((double)h->cfg.adam_beta1, (double)adam_t)));
+}
+// The argument blocks of the side chain, filled here for the solo launches and for the group step's records alike.
+IpBwdArgs ip_bwd_args(const ipnn_handle* h, const IpCall& c)        // the 16-example backward of the inner products
+{
+    return IpBwdArgs{h->P, c.ids, c.B, h->F, h->K, h->table16, h->n_rows, h->Dp[0], h->emb, c.wts};
+}
+IpBArgs ip_b_args(const ipnn_handle* h, const IpCall& c, float lr_step)
+{
+    return IpBArgs{h->b, h->gb_part, c.Ba / ip_bwd_ex(h), h->adam ? (int)h->cfg.optimizer : 0, h->bmv, lr_step, h->cfg.adam_beta1,
+                   h->cfg.adam_beta2, h->cfg.adam_eps, h->err_flag};
+}
+// sparse rows: row -= lr * sum of its gradients (c = 1: the table of powers is all ones).  Adam / FTRL: the same sorted sums
+// land in the (zero) gradient table instead: G[row] = 0 * 1 - (-1) * sum.  Narrow rows: level 2 in the handle's form.
+ScatArgs ip_scat_args(const ipnn_handle* h)
+{
+    ScatArgs sa = scat_args(h->rg, SORT_N, h->F, h->K, h->gxp, h->Dp[0], h->cpow1, h->adam ? -1.0 : (double)h->cfg.lr,
+                            h->adam ? h->tG : h->table16, h->wide ? h->rw : SLOT);
+    if (!h->wide) sa.form2 = h->kn.scat2_form;
+    return sa;
+}
+void ip_b_update(const ipnn_handle* h, const IpCall& c, hipStream_t ss, float lr_step)
+{
+    const IpBArgs bu = ip_b_args(h, c, lr_step);                   // (ngb: one partial of db per workgroup of the backward)
+    hipLaunchKernelGGL(k_ip_b_update, dim3(1), dim3(256), 0, ss, bu.b, bu.gb_part, bu.ngb, bu.opt, bu.bmv, bu.lr, bu.beta1, bu.beta2, bu.eps, bu.err);
+}
+void ip_adam_table(ipnn_handle* h, hipStream_t ss, float lr_step)
+{
+    const size_t n = (size_t)h->n_rows * h->rw;
+    hipLaunchKernelGGL(k_adam_table, dim3((unsigned)((n / 4 + 255) / 256)), dim3(256), 0, ss, h->table16, h->tm, h->tv, h->tG, n,
+                       lr_step, h->cfg.adam_beta1, h->cfg.adam_beta2, h->cfg.adam_eps, (int)h->cfg.optimizer);
+}
+
 int ip_side_chain(ipnn_handle* h, const IpCall& c, hipStream_t ss, float lr_step)
 {
     const int F = h->F;
@@ -2273,39 +2388,44 @@ int ip_side_chain(ipnn_handle* h, const IpCall& c, hipStream_t ss, float lr_step
             const IpManyArgs ma = ip_many_args(h, c, nullptr, 1.0f);
             IHK(h, ip_launch(k, c.Ba / IPM_BEX, ipm_bwd_lds(F, h->P, wv), ss, ma, dz0, emb, h->gxp, h->gb_part));
         } else {
-            const IpBwdArgs ba{h->P, c.ids, c.B, F, h->K, h->table16, h->n_rows, h->Dp[0], h->emb, c.wts};
+            const IpBwdArgs ba = ip_bwd_args(h, c);
             IHK(h, ip_launch(k, c.Ba / 16, ip16_lds(F, h->Dp[0]), ss, ba, dz0, h->gxp, h->gb_part));
         }
-        const int ngb = c.Ba / ip_bwd_ex(h);                       // one partial of db per workgroup of the backward
-        hipLaunchKernelGGL(k_ip_b_update, dim3(1), dim3(256), 0, ss, h->b, h->gb_part, ngb, h->adam ? (int)h->cfg.optimizer : 0, h->bmv,
-                           lr_step, h->cfg.adam_beta1, h->cfg.adam_beta2, h->cfg.adam_eps, h->err_flag);
+        ip_b_update(h, c, ss, lr_step);
     }
-    {   // sparse rows: row -= lr * sum of its gradients (c = 1: the table of powers is all ones).  Adam / FTRL: the same sorted sums
-        // land in the (zero) gradient table instead: G[row] = 0 * 1 - (-1) * sum
+    {
         IpProf ps(h, "scatter", ss);
-        ScatArgs sa = scat_args(h->rg, SORT_N, F, h->K, h->gxp, h->Dp[0], h->cpow1, h->adam ? -1.0 : (double)h->cfg.lr,
-                                h->adam ? h->tG : h->table16, h->wide ? h->rw : SLOT);
+        ScatArgs sa = ip_scat_args(h);
         if (h->wide) {   // the bag table's wide scatter, gradient stride rw, row pitch Dp0
             sa.tag_shared = h->noshare; sa.stamp = 1; sa.gxf = h->rw;
             const int nthr = F * (SORT_N / WCH) * (h->rw / 4);
             hipLaunchKernelGGL(k_ip_scatw1, dim3((nthr + 255) / 256), dim3(256), 0, ss, sa);
             hipLaunchKernelGGL(k_ip_scatw2, dim3(256), dim3(256), 0, ss, sa);
-        } else {
-            sa.form2 = h->kn.scat2_form;
-            launch_scat_narrow(ss, sa, h->kn.scat_form, 256);
-        }
+        } else launch_scat_narrow(ss, sa, h->kn.scat_form, 256);
     }
     if (h->adam) {
         IpProf ps(h, "adam_table", ss);
-        const size_t n = (size_t)h->n_rows * h->rw;
-        hipLaunchKernelGGL(k_adam_table, dim3((unsigned)((n / 4 + 255) / 256)), dim3(256), 0, ss, h->table16, h->tm, h->tv, h->tG, n,
-                           lr_step, h->cfg.adam_beta1, h->cfg.adam_beta2, h->cfg.adam_eps, (int)h->cfg.optimizer);
+        ip_adam_table(h, ss, lr_step);
     }
     return FNN_OK;
 }
 
 // All weight gradients: gW_t [Dp_{t-1}][Dp_t] = a_{t-1}^T . delta l_t, contraction over the examples, into split-K slabs (the
 // split chosen per layer so that every product fills the chip): one grouped launch, or one launch per product
+// the grouped launch's arguments for a batch: the plan's, with every product's k-steps
+template <typename T> GemmGroupArgs ip_wgrad_args(const ipnn_handle* h, const IpCall& c)
+{
+    GemmGroupArgs g = h->plan.group;
+    for (int i = 0; i <= h->L; ++i) g.p[i].nkt = c.Ba / Traits<T>::KS / h->sk[h->plan.wg_order[i] - 1];
+    return g;
+}
+// ... and the dense update's
+IpUpdArgs ip_upd_args(const ipnn_handle* h, const IpCall& c, float lr_step)
+{
+    IpUpdArgs u = h->plan.upd;
+    u.lr = lr_step; u.ngb = c.Ba / ip_bwd_ex(h); u.Ba = c.Ba;
+    return u;
+}
 template <typename T> void ip_wgrad(ipnn_handle* h, const IpCall& c)
 {
     IpProf ps(h, "wgrad");
@@ -2313,8 +2433,7 @@ template <typename T> void ip_wgrad(ipnn_handle* h, const IpCall& c)
     const int L = h->L;
     constexpr int KS = Traits<T>::KS;
     if (h->kn.group_wgrad && L + 1 <= GEMM_GROUP_MAX) {
-        GemmGroupArgs g = p.group;
-        for (int i = 0; i <= L; ++i) g.p[i].nkt = c.Ba / KS / h->sk[p.wg_order[i] - 1];
+        const GemmGroupArgs g = ip_wgrad_args<T>(h, c);
         hipLaunchKernelGGL((k_gemm_group<T, 4, 4>), dim3(g.wg0[L + 1]), dim3(256), gemm_f32w_lds(), h->st, g);
         return;
     }
@@ -2329,8 +2448,7 @@ template <typename T> void ip_wgrad(ipnn_handle* h, const IpCall& c)
 template <typename T> void ip_dense_update(ipnn_handle* h, const IpCall& c, hipStream_t us, float lr_step)
 {
     IpProf ps(h, "update", us);
-    IpUpdArgs u = h->plan.upd;
-    u.lr = lr_step; u.ngb = c.Ba / ip_bwd_ex(h); u.Ba = c.Ba;
+    const IpUpdArgs u = ip_upd_args(h, c, lr_step);
     hipLaunchKernelGGL((k_ip_update_all<T>), dim3((unsigned)(u.off[h->L + 1] / 4096 + 1)), dim3(256), 0, us, u);
 }
 
@@ -2361,13 +2479,8 @@ int ip_run(ipnn_handle* h, IpCall c)
     if (p.strip) IRC(ip_strips_fwd<T>(h, c, &fused_tail)); else ip_gemms_fwd<T>(h, c);
     if (!c.train) { IHK(h, hipGetLastError()); return FNN_OK; }
     if (p.strip) IRC(ip_strips_bwd<T>(h, c, fused_tail)); else ip_gemms_bwd<T>(h, c);
-    float lr_step = h->cfg.lr;
-    if (h->adam) {
-        h->adam_t += 1;
-        if (!h->ftrl)
-            lr_step = (float)((double)h->cfg.lr * std::sqrt(1.0 - std::pow((double)h->cfg.adam_beta2, (double)h->adam_t)) /
-                              (1.0 - std::pow((double)h->cfg.adam_beta1, (double)h->adam_t)));
-    }
+    if (h->adam) h->adam_t += 1;
+    const float lr_step = ip_lr_step(h, h->adam_t);
     // Beside the weight gradients, on the side stream (after the id grouping, in stream order): the side chain
     const bool side_upd = side.on() && kn.upd_side;
     IRC(side.fork(h->ev.bwd));
@@ -2454,8 +2567,7 @@ template <typename T> void ip_fill_group_arg(const ipnn_handle* h, int model, co
     const IpRows rows = ip_fwd_rows(h);
     if (rows == IP_WIDE) g.w = ip_wide_args(h, c, nullptr, 1.0f);
     else if (rows == IP_MANY) g.m = ip_many_args(h, c, nullptr, 1.0f);
-    else g.f = IpFwdArgs{h->P, c.ids, c.B, h->F, h->K, h->table16, h->n_rows, h->b, nullptr, h->d[0],
-                         1.0f, h->cfg.act, h->Dp[0], h->ldT, h->err_flag, h->kn.fwd_skip, h->kn.wt, c.wts};
+    else g.f = ip_fwd_args(h, c, nullptr, 1.0f);
     StripFwdArgs<T>& sa = g.s;
     const int L = h->L;
     sa.a0 = (const T*)h->a[0]; sa.n = L + 1;
@@ -2550,6 +2662,96 @@ int ip_group_forward(const IpGroup& g, ipnn_handle* const* hs, int n, int base, 
         if (rc != FNN_OK) return g.member_failed(rc, h, base + m);
     }
     return FNN_OK;
+}
+
+// --------------------------------------------------------------------------------------------- many models, one mini-batch step
+// ipnn_train_step_multi ("A mini-batch step for many inner-product models").
+struct IpStepGroup : GroupCall<ipnn_handle> {
+    IpStepGroup(ipnn_handle* const* hs_, int n_) : GroupCall("ipnn_train_step_multi", hs_, n_, IPNN_STEP_MAX_MODELS, g_ip_err, ip_join) {}
+};
+// A member shares the group launches when every stage of its solo step has a group form that computes the same bits: the strip
+// kernels on narrow rows of up to 32 fields in both directions, the grouped weight-gradient launch, no diagnostic knob.
+bool ip_step_shares(const ipnn_handle* h)
+{
+    return h->plan.strip && ip_fwd_rows(h) == IP_NARROW && ip_bwd_rows(h) == IP_NARROW && h->kn.group_wgrad && h->L + 1 <= GEMM_GROUP_MAX &&
+           !h->kn.fwd_skip && !h->kn.stamps && !h->prof;
+}
+// A training LAUNCH CLASS: the prediction launch class (element type, depth, padded widths, the gather's block size, pairs,
+// weights given or not) and the tiles of the grouped weight-gradient launch (the split-K of every product).  Everything else that
+// differs between two members is a run-time field of their records: the scatter forms, wt, the optimiser, act, k, every value.
+struct IpStepClass {
+    IpPredClass pc; int n_wg;
+    bool same(const IpStepClass& o) const { return pc.same(o.pc) && n_wg == o.n_wg; }
+};
+// A GROUPING CLASS: members whose sparse-row updates read one grouping of the batch's ids -- the same keys (n_rows, key width)
+// sorted the same way (runs) -- made once, in the first member's buffers.
+struct IpSortClass { int64_t n_rows; bool key64; int merge4; ipnn_handle* first; };
+
+// member m's call of one group step: its masks or its draw, formed as the single-strip form of the step
+IpCall ip_step_call(const ipnn_handle* h, const int32_t* ids, const float* wts, const float* y, int B, const uint8_t* const* mk,
+                    const IpDraw* dr, float* logits)
+{
+    IpCall c{ids, wts, y, B, mk, dr, logits, nullptr, true};
+    ip_form(h, c);
+    c.duo = c.tsplit = c.fuse_tail = false;
+    return c;
+}
+template <typename T> void ip_fill_step_arg(ipnn_handle* h, int model, const IpCall& c, const int4* rec, float* pack, void* dst)
+{
+    IpStepArg<T> r{};
+    const int L = h->L;
+    r.model = model; r.pack = pack;
+    r.drawn = c.draw ? 1 : 0;
+    if (c.drop && c.draw) r.md = ip_step_draw_args(h, c, &r.n_mask);
+    else if (c.drop) r.mt = ip_step_maskT_args(h, c, &r.n_mask);
+    r.f = ip_fwd_args(h, c, c.mask0, c.drop ? 1.0f / h->cfg.keep_prob : 1.0f);
+    r.a0 = (T*)h->a[0]; r.a0T = (T*)h->aT[0]; r.emb = h->emb;
+    const StripDuo solo{0, nullptr, nullptr, 0, h->err_flag, 0, h->kn.duo_min};     // one workgroup per strip: nothing to wait for
+    r.s = ip_stack_fwd_args<T>(h, c); r.s.duo = solo; r.s.warm = 0; r.s.dbg = nullptr; r.s.sel = -1;
+    r.sb = ip_stack_bwd_args<T>(h, c); r.sb.duo = solo; r.sb.warm = 0; r.sb.dbg = nullptr;
+    r.ib = ip_bwd_args(h, c); r.dz0 = h->dz0; r.gxp = h->gxp; r.gb_part = h->gb_part;
+    const float lr_step = ip_lr_step(h, h->adam_t + (h->adam ? 1 : 0));
+    r.bu = ip_b_args(h, c, lr_step);
+    r.sa = ip_scat_args(h); r.sa.rec = rec;
+    r.n_scat1 = scat1_blocks(r.sa, h->kn.scat_form);
+    r.g = ip_wgrad_args<T>(h, c); r.n_wg = r.g.wg0[L + 1];
+    r.u = ip_upd_args(h, c, lr_step);
+    memcpy(dst, &r, sizeof(r));
+}
+// every stage of the step for one launch class, each ONE launch over (the stage's extent, the class's members); `d`: the members'
+// records on the device.  ext: the largest extents among the members (mask tiles of either kind, level-1 workgroups).
+struct IpStepExt { int n_draw = 0, n_maskT = 0, n_scat1 = 0; };
+template <typename T> hipError_t ip_launch_step_class(const ipnn_handle* h, const IpStepClass& c, const IpStepExt& x, unsigned M, const void* dev_args,
+                                                       int Ba, hipStream_t st)
+{
+    constexpr int RT = sizeof(T) == 2 ? 2 : 1;
+    const IpStepArg<T>* d = static_cast<const IpStepArg<T>*>(dev_args);
+    const size_t lds16 = ip16_lds(h->F, h->Dp[0]);
+    const int maxD = h->plan.maxD;
+    hipError_t e = hipSuccess;
+#define STEP_K(expr) do { if ((e = (expr)) != hipSuccess) return e; } while (0)
+    if (x.n_draw) STEP_K(ip_launch2(IP_K(256, k_mask_draw_g<T>), dim3((unsigned)x.n_draw, M), 0, st, d));
+    if (x.n_maskT) STEP_K(ip_launch2(IP_K(256, k_mask_T_g<T>), dim3((unsigned)x.n_maskT, M), 0, st, d));
+    STEP_K(ip_launch2(ip_step_gather_sel<T>(c.pc.wv, c.pc.nt), dim3((unsigned)(Ba / 16), M), lds16, st, d));
+    STEP_K(ip_launch2(ip_step_strip_sel<T>(false), dim3((unsigned)(Ba / (16 * RT)), M), h->plan.strip_lds, st, d, maxD));
+    STEP_K(ip_launch2(ip_step_strip_sel<T>(true), dim3((unsigned)(Ba / (16 * RT)), M), h->plan.strip_lds, st, d, maxD));
+    STEP_K(ip_launch2(ip_step_bwd_sel<T>(c.pc.wv), dim3((unsigned)(Ba / 16), M), lds16, st, d));
+    STEP_K(ip_launch2(IP_K(256, k_ip_b_update_g<T>), dim3(M), 0, st, d));
+    STEP_K(ip_launch2(IP_K(256, k_ip_scat1_g<T>), dim3((unsigned)x.n_scat1, M), 0, st, d));
+    STEP_K(ip_launch2(IP_K(256, k_ip_scat2_g<T>), dim3(256, M), 0, st, d));
+    STEP_K(ip_launch2(IP_K(256, k_ip_wgrad_g<T>), dim3((unsigned)c.n_wg, M), gemm_f32w_lds(), st, d));
+    STEP_K(ip_launch2(IP_K(256, k_ip_update_all_g<T>), dim3((unsigned)(h->plan.upd.off[h->L + 1] / 4096 + 1), M), 0, st, d));
+#undef STEP_K
+    return hipSuccess;
+}
+
+// one solo training step of h, as ipnn_train_step_w / ipnn_train_step_drawn enqueue it (no loss copy, no synchronisation)
+int ip_step_enqueue(ipnn_handle* h, const int32_t* ids, const float* wts, const float* y, int B, const uint8_t* const* masks, const IpDraw* draw,
+                    float* logits_out)
+{
+    if (draw && !h->mask0) IHK(h, hipMalloc((void**)&h->mask0, (size_t)h->Bmax * h->d[0]));      // every byte a step reads is drawn by that step
+    const IpCall c{ids, wts, y, B, masks, draw, logits_out, nullptr, true};
+    return h->bf16 ? ip_run<bf16_t>(h, c) : ip_run<float>(h, c);
 }
 
 }  // namespace
@@ -2683,6 +2885,9 @@ int ipnn_destroy(ipnn_handle* h)
     for (void* p : ptrs) if (p) hipFree(p);
     if (h->ev_scratch) hipFree(h->ev_scratch);
     ring_release(h->eval_ring);
+    ring_release(h->step_ring);
+    if (h->step_pack) hipFree(h->step_pack);
+    if (h->step_pack_host) hipHostFree(h->step_pack_host);
     if (h->join) hipEventDestroy(h->join);
     row_group_free(h->rg);
     for (auto& kv : h->prof_ev) for (auto& p : kv.second) { hipEventDestroy(p.first); hipEventDestroy(p.second); }
@@ -2841,9 +3046,7 @@ static int ip_train_step(ipnn_handle* h, const int32_t* ids, const float* wts, c
     if (!h->table16) IFAIL(h, FNN_ERR_STATE, "ipnn_set_table has not been called");
     if (h->duo_failed) IFAIL(h, FNN_ERR_STATE, "an earlier step failed (StripDuo swap timed out): re-create the handle");
     IHK(h, hipSetDevice(h->dev));
-    if (draw && !h->mask0) IHK(h, hipMalloc((void**)&h->mask0, (size_t)h->Bmax * h->d[0]));      // every byte a step reads is drawn by that step
-    const IpCall c{ids, wts, y, B, masks, draw, logits_out, nullptr, true};
-    IRC(h->bf16 ? ip_run<bf16_t>(h, c) : ip_run<float>(h, c));
+    IRC(ip_step_enqueue(h, ids, wts, y, B, masks, draw, logits_out));
     if (loss_sum_out) {                                      // (the loss is summed in the update launch: join it)
         IRC(ip_join(h));
         IHK(h, hipMemcpyAsync(loss_sum_out, h->loss_dev, 4, hipMemcpyDeviceToHost, h->st));
@@ -3009,6 +3212,151 @@ int ipnn_eval_multi(ipnn_handle* const* hs, int n_models, const int32_t* ids, co
     if (rj != FNN_OK) return rj;
     const std::string msg = eval_verdict(found.bad, found.range, found.n_pos, N, "[0, n_rows)");
     return msg.empty() ? FNN_OK : g.refuse(FNN_ERR_RANGE, msg);
+}
+
+// One training step of several handles on one feed.  Members on the group path (ip_step_shares): their records through hs[0]'s
+// step ring, one sort per grouping class, then per launch class every stage once; the others run their own step on the group's
+// stream.  What a member keeps of a step on the host (the step count) is written after the last launch was accepted.
+int ipnn_train_step_multi(ipnn_handle* const* hs, int n_models, const int32_t* ids, const float* wts, const float* y, int B,
+                          const uint8_t* const* const* masks, const uint64_t* seeds, const uint64_t* steps,
+                          float* const* logits_out, float* loss_sum_out)
+{
+    IpStepGroup g(hs, n_models);
+    IRC(g.check_list("it is written to"));
+    const int M = n_models;
+    if (!ids) return g.refuse(FNN_ERR_ARG, "null ids");
+    if (!y) return g.refuse(FNN_ERR_ARG, "null y");
+    if (B < 1) return g.refuse(FNN_ERR_ARG, "B must be at least 1");
+    for (int m = 0; m < M; ++m)
+        if (B > hs[m]->Bmax) return g.refuse(FNN_ERR_ARG, g.at("B = " + std::to_string(B) + " is above its max_batch = " + std::to_string(hs[m]->Bmax), m));
+    if (masks && seeds) return g.refuse(FNN_ERR_ARG, "masks and seeds both given: the caller's masks or the library's draw, not both");
+    if (seeds && !steps) return g.refuse(FNN_ERR_ARG, "seeds without steps");
+    if (steps && !seeds) return g.refuse(FNN_ERR_ARG, "steps without seeds");
+    if (masks) for (int m = 0; m < M; ++m) if (masks[m])
+        for (int t = 0; t <= hs[m]->L; ++t) if (!masks[m][t]) return g.refuse(FNN_ERR_ARG, g.at("masks: null entry for layer " + std::to_string(t), m));
+    for (int m = 0; m < M; ++m) {
+        if (!hs[m]->table16) return g.refuse(FNN_ERR_STATE, g.at("ipnn_set_table has not been called", m));
+        if (hs[m]->duo_failed) return g.refuse(FNN_ERR_STATE, g.at("an earlier step failed (StripDuo swap timed out): re-create the handle", m));
+    }
+    ipnn_handle* h0 = g.h0;
+    std::vector<IpDraw> draws((size_t)M);
+    if (seeds) for (int m = 0; m < M; ++m) draws[m] = IpDraw{seeds[m], steps[m]};
+    auto mask_of = [&](int m) { return masks ? masks[m] : nullptr; };
+    auto draw_of = [&](int m) { return seeds ? &draws[m] : nullptr; };
+    auto logits_of = [&](int m) { return logits_out ? logits_out[m] : nullptr; };
+    if (M == 1) {                                                     // one model: its solo step, reported as the group reports
+        const int rc = ip_train_step(h0, ids, wts, y, B, mask_of(0), draw_of(0), logits_of(0), loss_sum_out);
+        return rc == FNN_OK ? rc : g.refuse(rc, g.at(h0->err, 0));
+    }
+    IRC(g.enter());
+    const hipStream_t st = h0->st;
+    // the members by path and class
+    std::vector<IpStepClass> cls;
+    std::vector<std::vector<int>> mem;
+    std::vector<int> own;
+    for (int m = 0; m < M; ++m) {
+        if (!ip_step_shares(hs[m])) { own.push_back(m); continue; }
+        IpStepClass c{ip_pred_class_of(hs[m], wts != nullptr), hs[m]->plan.group.wg0[hs[m]->L + 1]};
+        size_t i = 0;
+        while (i < cls.size() && !cls[i].same(c)) ++i;
+        if (i == cls.size()) { cls.push_back(c); mem.emplace_back(); }
+        mem[i].push_back(m);
+    }
+    const int ng = M - (int)own.size();
+    if (seeds) for (int m = 0; m < M; ++m)                            // every byte a step reads is drawn by that step
+        if (!hs[m]->mask0) IHK(h0, hipMalloc((void**)&hs[m]->mask0, (size_t)hs[m]->Bmax * hs[m]->d[0]));
+    if (loss_sum_out && !h0->step_pack) {
+        IHK(h0, hipMalloc((void**)&h0->step_pack, (size_t)2 * IPNN_STEP_MAX_MODELS * 4));
+        IHK(h0, hipHostMalloc((void**)&h0->step_pack_host, (size_t)2 * IPNN_STEP_MAX_MODELS * 4, hipHostMallocDefault));
+    }
+    // one array per call: the group members' records class by class, then (with loss_sum_out) a header for every other member
+    const size_t elem = h0->step_ring.elem, nrec = (size_t)ng + (loss_sum_out ? own.size() : 0);
+    size_t slot = 0;
+    const char* d = nullptr;
+    std::vector<IpSortClass> sorts;
+    std::vector<IpStepExt> ext(cls.size());
+    int Ba = 0;
+    if (nrec) {
+        IHK(h0, ring_take(h0->step_ring, nrec, &slot));
+        char* a = static_cast<char*>(h0->step_ring.host) + slot * elem;
+        d = static_cast<const char*>(h0->step_ring.dev) + slot * elem;
+        size_t pos = 0;
+        for (size_t i = 0; i < cls.size(); ++i) for (int m : mem[i]) {
+            ipnn_handle* h = hs[m];
+            size_t s = 0;
+            while (s < sorts.size() && !(sorts[s].n_rows == h->n_rows && sorts[s].key64 == h->key64 && sorts[s].merge4 == h->kn.sort_merge4)) ++s;
+            if (s == sorts.size()) sorts.push_back(IpSortClass{h->n_rows, h->key64, h->kn.sort_merge4, h});
+            const IpCall c = ip_step_call(h, ids, wts, y, B, mask_of(m), draw_of(m), logits_of(m));
+            Ba = c.Ba;
+            float* pack = loss_sum_out ? h0->step_pack + 2 * m : nullptr;
+            if (h->bf16) ip_fill_step_arg<bf16_t>(h, m, c, sorts[s].first->rg.rec, pack, a + pos * elem);
+            else ip_fill_step_arg<float>(h, m, c, sorts[s].first->rg.rec, pack, a + pos * elem);
+            const IpStepArg<float>* r = reinterpret_cast<const IpStepArg<float>*>(a + pos * elem);      // (the extents sit in front of the typed fields)
+            if (r->drawn) ext[i].n_draw = std::max(ext[i].n_draw, r->n_mask); else ext[i].n_maskT = std::max(ext[i].n_maskT, r->n_mask);
+            ext[i].n_scat1 = std::max(ext[i].n_scat1, r->n_scat1);
+            ++pos;
+        }
+        if (loss_sum_out) for (int m : own) {
+            IpStepArg<float> r{};
+            r.model = m; r.pack = h0->step_pack + 2 * m; r.u.err = hs[m]->err_flag; r.u.loss_sum = hs[m]->loss_dev;
+            memcpy(a + pos * elem, &r, sizeof(r));
+            ++pos;
+        }
+        IHK(h0, ring_send(h0->step_ring, slot, nrec, st));
+    }
+    for (const IpSortClass& s : sorts) {                              // the batch's ids, grouped once per grouping class
+        const IpCall c = ip_step_call(s.first, ids, wts, y, B, nullptr, nullptr, nullptr);
+        ip_sort_ids(s.first, c, st);                                  // into the class's first member's buffers, as its solo step sorts
+    }
+    {
+        size_t pos = 0;
+        for (size_t i = 0; i < cls.size(); ++i) {
+            const ipnn_handle* h = hs[mem[i][0]];
+            const unsigned n = (unsigned)mem[i].size();
+            IHK(h0, cls[i].pc.bf16 ? ip_launch_step_class<bf16_t>(h, cls[i], ext[i], n, d + pos * elem, Ba, st)
+                                   : ip_launch_step_class<float>(h, cls[i], ext[i], n, d + pos * elem, Ba, st));
+            for (int m : mem[i]) if (hs[m]->adam) {                   // an Adam / FTRL member's b and table pass: the solo step's own launches
+                ipnn_handle* hm = hs[m];
+                const float lr_step = ip_lr_step(hm, hm->adam_t + 1);
+                const IpCall c = ip_step_call(hm, ids, wts, y, B, nullptr, nullptr, nullptr);
+                ip_b_update(hm, c, st, lr_step);
+                ip_adam_table(hm, st, lr_step);
+            }
+            pos += n;
+        }
+    }
+    IHK(h0, hipGetLastError());
+    for (size_t i = 0; i < cls.size(); ++i) for (int m : mem[i]) if (hs[m]->adam) hs[m]->adam_t += 1;      // accepted: the members have made a step
+    for (int m : own) {
+        ipnn_handle* h = hs[m];
+        const int rc = on_stream(h, st, [&] {
+            IRC(ip_step_enqueue(h, ids, wts, y, B, mask_of(m), draw_of(m), logits_of(m)));
+            return loss_sum_out ? ip_join(h) : FNN_OK;                // (the loss is summed in the update launch: join it)
+        });
+        if (rc != FNN_OK) return g.member_failed(rc, h, m);
+    }
+    if (!loss_sum_out) return g.leave();
+    if (!own.empty()) {
+        hipLaunchKernelGGL(k_ip_step_pack, dim3(1), dim3(256), 0, st, d + (size_t)ng * elem, elem, (int)own.size());
+        IHK(h0, hipGetLastError());
+    }
+    IHK(h0, hipMemcpyAsync(h0->step_pack_host, h0->step_pack, (size_t)2 * M * 4, hipMemcpyDeviceToHost, st));
+    const int rj = g.leave();
+    IHK(h0, hipStreamSynchronize(st));
+    if (rj != FNN_OK) return rj;
+    std::string bad, gave_up;
+    for (int m = 0; m < M; ++m) {
+        loss_sum_out[m] = h0->step_pack_host[2 * m];
+        const int f = (int)h0->step_pack_host[2 * m + 1];
+        if (f & 2) { hs[m]->duo_failed = true; gave_up += (gave_up.empty() ? "" : ", ") + std::to_string(m); }      // as ipnn_sync judges a solo step
+        else if (f & 1) bad += (bad.empty() ? "" : ", ") + std::to_string(m);
+    }
+    if (!gave_up.empty())
+        return g.refuse(FNN_ERR_HIP, "a strip workgroup gave up waiting for its partner (StripDuo swap) in model(s) " + gave_up +
+                        ": that step's outputs are invalid and its dense update was not applied; those handles refuse further train steps" +
+                        (bad.empty() ? "" : "; feature id outside [0, n_rows) of model(s) " + bad));
+    if (!bad.empty()) return g.refuse(FNN_ERR_RANGE, "feature id outside [0, n_rows) of model(s) " + bad);
+    return FNN_OK;
 }
 
 int ipnn_prof_enable(ipnn_handle* h, int on)

@@ -57,13 +57,14 @@ def criteo_feed(v_wts, c_ids, c_wts, offsets):
 
 class IPNNEngine(object):
     def __init__(self, n_fields, k, hidden, act='relu', max_batch=4096, precision='bf16', lr=1e-4, keep_prob=0.5, device=0,
-                 pairs=True, optimizer='sgd', adam_eps=1e-8, adam_betas=(0.9, 0.999), reduce='sum'):
+                 pairs=True, optimizer='sgd', adam_eps=1e-8, adam_betas=(0.9, 0.999), reduce='sum', stream=None):
+        """stream: a torch.cuda.Stream the engine enqueues on (several engines may share one); None: a stream of its own."""
         import torch
         if not torch.cuda.is_available():
             raise FNNError(_capi.FNN_ERR_HIP, "no HIP device visible to PyTorch-ROCm; no CPU fallback")
         self._torch, self.lib = torch, _capi.load()
         self.device = torch.device('cuda', device)
-        self.stream = torch.cuda.Stream(device=self.device)
+        self.stream = stream if stream is not None else torch.cuda.Stream(device=self.device)
         self.F, self.K, self.hidden = n_fields, k, list(hidden)
         self.max_batch = max_batch
         self.d = [n_fields * k + (n_fields * (n_fields - 1) // 2 if pairs else 0) + 1] + self.hidden + [1]
@@ -212,17 +213,21 @@ class IPNNEngine(object):
         self._ck(self.lib.ipnn_sync(self.h))
 
 
-def _many_feed(engines, ids, wts, y=None):
-    """The one feed of a group call on engines[0]'s device, and every engine's stream behind the caller's."""
+def _many_feed(engines, ids, wts, y=None, y_dtype=None, more=None):
+    """The one feed of a group call on engines[0]'s device, and every engine's stream behind the caller's.  Everything the call
+    reads is converted BEFORE the hand-shake -- a conversion of a device tensor is a kernel on the caller's stream -- so `more`,
+    a function of the converted ids that makes whatever else the call feeds (keep-masks), runs in front of it too; its value is
+    returned as the fourth entry."""
     e0 = engines[0]
     torch = e0._torch
     ids_t = e0._dev(ids, torch.int32)
     wts_t = e0._wts(wts, ids_t)
-    y_t = e0._dev(y, torch.int32) if y is not None else None
+    y_t = e0._dev(y, y_dtype if y_dtype is not None else torch.int32) if y is not None else None
+    extra = more(ids_t) if more is not None else None
     cur = torch.cuda.current_stream(e0.device)
     for e in engines:
         e.stream.wait_stream(cur)
-    return ids_t, wts_t, y_t
+    return ids_t, wts_t, y_t, extra
 
 
 def predict_many(engines, ids, wts=None):
@@ -232,7 +237,7 @@ def predict_many(engines, ids, wts=None):
     e0 = engines[0]
     torch = e0._torch
     M = len(engines)
-    ids_t, wts_t, _ = _many_feed(engines, ids, wts)
+    ids_t, wts_t, _, _ = _many_feed(engines, ids, wts)
     n = ids_t.shape[0]
     ps = [torch.empty(n, dtype=torch.float32, device=e0.device) for _ in engines]
     hs = (C.c_void_p * M)(*[e.h.value for e in engines])
@@ -259,7 +264,7 @@ def evaluate_many(engines, ids, y, wts=None, want_p=False):
     e0 = engines[0]
     torch = e0._torch
     M = len(engines)
-    ids_t, wts_t, y_t = _many_feed(engines, ids, wts, y)
+    ids_t, wts_t, y_t, _ = _many_feed(engines, ids, wts, y)
     n = ids_t.shape[0]
     ps = [torch.empty(n, dtype=torch.float32, device=e0.device) for _ in engines] if want_p else None
     auc, rmse, ll, status = (C.c_double * M)(), (C.c_double * M)(), (C.c_double * M)(), (C.c_int * M)()
@@ -283,6 +288,95 @@ def evaluate_many(engines, ids, y, wts=None, want_p=False):
             o['error'] = msg
         outs.append(o)
     return outs
+
+
+def _step_masks(engines, masks):
+    """The `masks` argument of train_step_many, checked before the library is called: None, or ('drawn' | 'arrays' | None, the
+    list).  Entries are None (no dropout for that engine), lists of arrays as train_step takes, or Drawn; arrays and Drawn may
+    not be mixed in one call (the library takes the caller's masks or its own draw, not both).  Nor may Drawn and None: the
+    library draws for every model of a call or for none (ipnn_train_step_multi's seeds are one array for the list), so an engine
+    that is to keep everything in a drawn call has keep_prob = 1 and its own Drawn."""
+    if masks is None:
+        return None, None
+    masks = list(masks)
+    if len(masks) != len(engines):
+        raise ValueError("masks has %d entries for %d engines" % (len(masks), len(engines)))
+    n_drawn = sum(isinstance(m, Drawn) for m in masks)
+    n_arrays = sum(m is not None and not isinstance(m, Drawn) for m in masks)
+    if n_drawn and n_arrays:
+        raise ValueError("masks mixes Drawn entries and arrays: one call takes the caller's masks or the library's draw, not both")
+    if n_drawn and n_drawn != len(masks):
+        raise ValueError("masks mixes Drawn entries and None: a drawn call draws for every engine (keep_prob = 1 keeps everything)")
+    return ('drawn' if n_drawn else 'arrays' if n_arrays else None), masks
+
+
+def train_step_many(engines, ids, y, masks=None, wts=None, want_logits=False, want_loss=True):
+    """train_step of every engine of a list on ONE feed, in one call (ipnn_train_step_multi).  masks: None, or a list with one
+    entry per engine -- None, a list of arrays as train_step takes, or a Drawn; arrays and Drawn may not be mixed, and a drawn
+    call has a Drawn for EVERY engine (the library draws for all models of a call or for none): ValueError otherwise.
+    Returns a list: entry m is {'loss', 'logits'} scaled by engines[m].reduce, and afterwards every engine holds bit for bit
+    what its own train_step(ids, y, masks[m], wts=wts) would have left.  Every refusal of the library raises FNNError."""
+    kind, masks = _step_masks(engines, masks)
+    e0 = engines[0]
+    torch = e0._torch
+    M = len(engines)
+
+    def device_masks(ids_t):                  # every engine's masks on the device, in front of the stream hand-shake
+        if kind != 'arrays':
+            return None
+        out = []
+        for e, mk in zip(engines, masks):
+            mts = [e0._dev(m, torch.uint8) for m in mk] if mk is not None else None
+            if mts is not None and (len(mts) != len(e.hidden) + 1 or any(tuple(m.shape) != (ids_t.shape[0], e.d[t]) for t, m in enumerate(mts))):
+                raise ValueError("masks: an engine takes len(hidden) + 1 arrays [B, d_t]")
+            out.append(mts)
+        return out
+    ids_t, wts_t, y_t, keep = _many_feed(engines, ids, wts, y, torch.float32, device_masks)
+    B = ids_t.shape[0]
+    marr, seeds, steps = None, None, None
+    if kind == 'arrays':
+        rows = [(C.c_void_p * len(mts))(*[m.data_ptr() for m in mts]) if mts is not None else None for mts in keep]
+        marr = (C.c_void_p * M)(*[C.cast(r, C.c_void_p).value if r is not None else None for r in rows])
+        keep = (keep, rows)
+    elif kind == 'drawn':
+        seeds = (C.c_uint64 * M)(*[m.seed for m in masks])
+        steps = (C.c_uint64 * M)(*[m.step for m in masks])
+    logits = [torch.empty(B, dtype=torch.float32, device=e0.device) for _ in engines] if want_logits else None
+    larr = (C.c_void_p * M)(*[t.data_ptr() for t in logits]) if want_logits else None
+    loss = (C.c_float * M)()
+    hs = (C.c_void_p * M)(*[e.h.value for e in engines])
+    rc = e0.lib.ipnn_train_step_multi(hs, M, ids_t.data_ptr(), wts_t.data_ptr() if wts_t is not None else None, y_t.data_ptr(), B,
+                                      marr, seeds, steps, larr, loss if want_loss else None)
+    if rc != 0:
+        raise FNNError(rc, (e0.lib.ipnn_last_error(e0.h) or b'').decode())
+    cur = torch.cuda.current_stream(e0.device)
+    for e in engines:
+        cur.wait_stream(e.stream)
+    e0._keep_many = (ids_t, wts_t, y_t, keep)
+    outs = []
+    for m, e in enumerate(engines):
+        scale = 1.0 if e.reduce == 'sum' else 1.0 / B     # the library returns the sum of the per-example losses
+        outs.append({'loss': float(loss[m]) * scale if want_loss else None, 'logits': logits[m] if want_logits else None})
+    return outs
+
+
+def train_epoch_many(engines, ids, y, batch_size, seeds=None, first_step=0, wts=None):
+    """One pass of every engine over resident arrays in batches of batch_size (the last one ragged), every step one
+    train_step_many.  With seeds, step s of engine m draws Drawn(seeds[m], first_step + s); without, no dropout.  Returns the
+    list of per-step loss lists; bit for bit the loop of train_step on each engine."""
+    e0 = engines[0]
+    torch = e0._torch
+    ids_t, y_t = e0._dev(ids, torch.int32), e0._dev(y, torch.float32)
+    wts_t = e0._wts(wts, ids_t)
+    if seeds is not None and len(seeds) != len(engines):
+        raise ValueError("seeds has %d entries for %d engines" % (len(seeds), len(engines)))
+    losses = []
+    for s, lo in enumerate(range(0, ids_t.shape[0], batch_size)):
+        hi = min(ids_t.shape[0], lo + batch_size)
+        mk = [Drawn(sd, first_step + s) for sd in seeds] if seeds is not None else None
+        out = train_step_many(engines, ids_t[lo:hi], y_t[lo:hi], masks=mk, wts=wts_t[lo:hi] if wts_t is not None else None)
+        losses.append([o['loss'] for o in out])
+    return losses
 
 
 class _IPFamily(object):

@@ -178,6 +178,42 @@ int ipnn_eval_multi(ipnn_handle* const* hs, int n_models, const int32_t* ids, co
                     const int32_t* y, int64_t N, double* auc, double* rmse, double* logloss,
                     int* status, float* const* p_out);
 
+/* One mini-batch step of many models on ONE feed in one call (a hyper-parameter search training its candidates; DESIGN.md
+ * section 4, "A mini-batch step for many inner-product models"): one ipnn_train_step_w or ipnn_train_step_drawn of every handle
+ * of the list.  ids [B, F] int32, wts [B, F] f32 (nullable: every weight 1) and y [B] f32 are DEVICE pointers; hs, masks, seeds,
+ * steps, logits_out and loss_sum_out are HOST arrays of n_models entries.  masks[m] is what ipnn_train_step_w takes for model m
+ * (L + 1 device pointers; a NULL entry: no dropout for that model); seeds[m] / steps[m] are what ipnn_train_step_drawn takes for
+ * model m.  masks and seeds both NULL: no dropout anywhere; both given: refused.  logits_out is nullable and so are its entries
+ * (device, [B] each).  loss_sum_out is nullable: when given it receives every model's loss sum through ONE packed device-to-host
+ * copy and ONE synchronisation for the whole call.
+ *   Contract: after the call every model's table rows, b, dense layers, optimiser state, Adam step count, logits_out[m] and
+ * loss_sum_out[m] are bit for bit what that handle's own solo call would have left.  Group steps, solo steps, predict, evaluate,
+ * the _multi evaluation calls, ipnn_set_* and ipnn_get_* interleave freely.  SGD, Adam and FTRL members may be mixed, and so may
+ * act, k, pairs, depths, widths, table sizes, lr, keep_prob, the mean / sum loss and both precisions.  A member's pending
+ * IPNN_UPDATE_SIDE=1 update is joined first; everything then runs on hs[0]'s stream, which first waits for every other member's
+ * stream, and they wait for the call's last launch.
+ *   Members on the strip kernels with narrow rows (k <= 16) and at most 32 fields share launches: per LAUNCH CLASS -- the
+ * prediction launch class of ipnn_predict_multi plus the split-K layout of the weight gradients -- every stage of the step runs
+ * ONCE with the model as a grid dimension (b and the table pass of an Adam / FTRL member are that member's own two launches), one workgroup per strip (no pair form, no tail split: no workgroup of a group launch
+ * waits for another).  Members that agree in n_rows, key width and sort runs share one grouping of the batch's ids.  Every other
+ * member (wide rows, 33 to 64 fields, a layer too wide for the strips, IPNN_STRIP=0, IPNN_GROUP_WGRAD=0, a diagnostic knob) runs
+ * its own solo step inside the call: no shape is refused.  n_models == 1 forwards to the solo step.
+ *   Refusals (before any launch and any write; the message starts with the function's name, names the model and is left with
+ * ipnn_last_error(hs[0]), or ipnn_last_error(NULL) without a usable hs[0]): FNN_ERR_ARG for null hs or a null entry, n_models
+ * outside 1..IPNN_STEP_MAX_MODELS, null ids or y, B < 1 or above a member's max_batch, n_fields or device differing from model
+ * 0's, a handle listed twice (it is written to), masks and seeds both given, seeds without steps or steps without seeds, a
+ * masks[m] with a null layer entry; FNN_ERR_STATE for a member without a table or one whose strip pair gave up earlier.  A
+ * member's step count and pending flags are committed only after the call's last launch was accepted.
+ *   An id outside a member's table behaves as in the solo step (the row reads as zero, the member's range flag is set).  With
+ * loss_sum_out the call then returns FNN_ERR_RANGE, names the models whose flag was set and clears those flags, as
+ * ipnn_eval_multi does; without it the flags stay for each handle's ipnn_sync.  A member that runs its own step inside the call
+ * and whose strip pair gave up is judged as ipnn_sync judges it after a solo step: with loss_sum_out the call returns
+ * FNN_ERR_HIP naming the model, its flag is cleared and the handle refuses further train steps. */
+#define IPNN_STEP_MAX_MODELS 256
+int ipnn_train_step_multi(ipnn_handle* const* hs, int n_models, const int32_t* ids, const float* wts, const float* y, int B,
+                          const uint8_t* const* const* masks, const uint64_t* seeds, const uint64_t* steps,
+                          float* const* logits_out, float* loss_sum_out);
+
 /* Measurement hook (bench.py): HIP events on the handle's stream around the segments of a train
  * step -- "mask_t" (the keep-masks: transposed, or drawn), "sort", "ip_fwd", "fwd", "bwd", "wgrad", "ip_bwd", "scatter", "update".  enable(1) clears
  * earlier samples; get returns the average device time of one segment in ms (0 if none). */
