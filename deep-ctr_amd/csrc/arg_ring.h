@@ -19,6 +19,9 @@ struct ArgRing {
     void* host = nullptr; void* dev = nullptr; size_t cur = 0; hipEvent_t copied = nullptr;
     template <typename T> T* at_host(size_t slot) const { return static_cast<T*>(host) + slot; }
     template <typename T> const T* at_dev(size_t slot) const { return static_cast<const T*>(dev) + slot; }
+    // (a ring whose element type is chosen per launch: by bytes, `elem` per slot)
+    char* host_bytes(size_t slot) const { return static_cast<char*>(host) + slot * elem; }
+    const char* dev_bytes(size_t slot) const { return static_cast<const char*>(dev) + slot * elem; }
 };
 
 // n elements of the ring, *slot the first of them.  Allocates on first use, every piece guarded, so that a call that failed half
@@ -40,8 +43,7 @@ inline hipError_t ring_take(ArgRing& r, size_t n, size_t* slot)
 // the n elements written at `slot` of the host ring, to the device image on stream `st` (hs[0]'s)
 inline hipError_t ring_send(ArgRing& r, size_t slot, size_t n, hipStream_t st)
 {
-    const hipError_t e = hipMemcpyAsync(static_cast<char*>(r.dev) + slot * r.elem, static_cast<const char*>(r.host) + slot * r.elem, n * r.elem,
-                                        hipMemcpyHostToDevice, st);
+    const hipError_t e = hipMemcpyAsync(static_cast<char*>(r.dev) + slot * r.elem, r.host_bytes(slot), n * r.elem, hipMemcpyHostToDevice, st);
     return e != hipSuccess ? e : hipEventRecord(r.copied, st);
 }
 inline void ring_release(ArgRing& r)

@@ -1,7 +1,8 @@
 // eval_group.h -- the host arithmetic of the calls that evaluate many models on one feed (fm_eval_multi, fnn_eval_multi,
 // ipnn_eval_multi), free of HIP so that a plain C++ program can test it (tests/test_host_eval_group.py): how many models share
 // one scratch allocation, what a model's sums become, and the call's final message.  The loop that uses them is eval_groups()
-// (metrics.hip.h).
+// (metrics.hip.h).  Also what every group call, the step calls included, does with its list of members on the host: their
+// launch classes (class_index) and the model list of a refusal (eval_list_add).
 #pragma once
 #include <stdint.h>
 
@@ -54,6 +55,21 @@ inline EvalValues eval_values(const MetricOut& o, unsigned long long n_pos, int6
 
 // "0, 3, 7": the list of models inside a clause of the verdict
 inline void eval_list_add(std::string& list, int model) { list += (list.empty() ? "" : ", ") + std::to_string(model); }
+
+// The class of `c` among `classes`: the index of the first one that same(classes[i], c) accepts, `c` appended when none does --
+// so classes stand in the order of their first members.
+template <class V, class T, class Same> size_t class_index(V& classes, const T& c, Same same)
+{
+    size_t i = 0;
+    while (i < classes.size() && !same(classes[i], c)) ++i;
+    if (i == classes.size()) classes.push_back(c);
+    return i;
+}
+// (classes that compare themselves: a.same(b))
+template <class V, class T> size_t class_index(V& classes, const T& c)
+{
+    return class_index(classes, c, [](const T& a, const T& b) { return a.same(b); });
+}
 
 // The message of an evaluation that returns FNN_ERR_RANGE, empty when nothing is wrong: up to three clauses joined by "; " --
 // the models (`bad`, a list as above) with predictions NaN or outside [0, 1], the models (`range`) that met a feature id outside

@@ -1168,7 +1168,7 @@ int fm_train_online_multi(fm_handle* const* hs, int n_models, const int32_t* ids
         fm_online::Out o{0.0, 0.f, 0.f};
         MHK(h0, hipMemcpyAsync(&o, h->online_out, sizeof(o), hipMemcpyDeviceToHost, h->st));
         const int rm = fm_sync(h);
-        if (rm == FNN_ERR_RANGE) bad += (bad.empty() ? "" : ", ") + std::to_string(m);
+        if (rm == FNN_ERR_RANGE) eval_list_add(bad, m);
         else if (rm != FNN_OK) return g.member_failed(rm, h, m);
         if (loss_sum_out) loss_sum_out[m] = o.loss_sum;
         if (loss_last_out) loss_last_out[m] = o.loss_last;
@@ -1218,12 +1218,9 @@ int fm_train_step_multi(fm_handle* const* hs, int n_models, const int32_t* ids, 
     struct Cls { fm_handle* lead; int stamp; };
     std::vector<Cls> cls;
     std::vector<int> cls_of(M);
-    for (int m = 0; m < M; ++m) {
-        int c = 0;
-        while (c < (int)cls.size() && (cls[c].lead->n_rows != hs[m]->n_rows || cls[c].lead->shared != hs[m]->shared)) ++c;
-        if (c == (int)cls.size()) cls.push_back(Cls{hs[m], 0});
-        cls_of[m] = c;
-    }
+    for (int m = 0; m < M; ++m)
+        cls_of[m] = (int)class_index(cls, Cls{hs[m], 0}, [](const Cls& a, const Cls& b) {
+            return a.lead->n_rows == b.lead->n_rows && a.lead->shared == b.lead->shared; });
     // the classes with the first one's key width have their rank merge in launch 2; the others a launch of their own
     std::vector<int> order;                                           // classes, the riders first
     for (int c = 0; c < (int)cls.size(); ++c) if (cls[c].lead->key64 == cls[0].lead->key64) order.push_back(c);
@@ -1310,7 +1307,7 @@ int fm_train_step_multi(fm_handle* const* hs, int n_models, const int32_t* ids, 
     std::string bad;
     for (int m = 0; m < M; ++m) {
         loss_out[m] = hp[m].loss;
-        if (hp[m].flag) bad += (bad.empty() ? "" : ", ") + std::to_string(m);
+        if (hp[m].flag) eval_list_add(bad, m);
     }
     if (!bad.empty()) return g.refuse(FNN_ERR_RANGE, "feature id outside [-1, n_rows) in model(s) " + bad);
     return FNN_OK;

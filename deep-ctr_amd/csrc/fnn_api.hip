@@ -1111,16 +1111,15 @@ int pred_forward(const FnnGroup& g, fnn_handle* const* hs, int n, int base, cons
     for (int m = 0; m < n; ++m) {
         if (!pred_in_group(hs[m])) { own.push_back(m); continue; }
         PredClass c = BY_PREC_RC(hs[m], pred_class_of, (hs[m]));
-        size_t i = 0;
-        while (i < cls.size() && !(cls[i].k.fn == c.k.fn && cls[i].k.threads == c.k.threads && cls[i].k.lds == c.k.lds && cls[i].prec == c.prec)) ++i;
-        if (i == cls.size()) cls.push_back(c);
+        const size_t i = class_index(cls, c, [](const PredClass& a, const PredClass& b) {
+            return a.k.fn == b.k.fn && a.k.threads == b.k.threads && a.k.lds == b.k.lds && a.prec == b.prec; });
         cls[i].members.push_back(m);
     }
     size_t slot = 0;
     HIPCHK(h0, ring_take(h0->eval_ring, (size_t)n, &slot));
     const size_t elem = h0->eval_ring.elem;
-    char* a = static_cast<char*>(h0->eval_ring.host) + slot * elem;
-    const char* d = static_cast<const char*>(h0->eval_ring.dev) + slot * elem;
+    char* a = h0->eval_ring.host_bytes(slot);
+    const char* d = h0->eval_ring.dev_bytes(slot);
     size_t pos = 0;
     auto fill = [&](int m) { BY_PREC(hs[m], fill_pred_arg, (hs[m], m, ids, h0->eval_y, ek.fb_len, p[m], a + pos * elem)); ++pos; };
     for (const PredClass& c : cls) for (int m : c.members) fill(m);
@@ -1920,15 +1919,12 @@ int fnn_train_step_multi(fnn_handle* const* hs, int n_models, const int32_t* ids
     std::vector<LaunchClass> cls;
     for (int m = 0; m < M; ++m) {
         LaunchClass c = BY_PREC_RC(hs[m], launch_class_of, (hs[m]));
-        size_t i = 0;
-        while (i < cls.size() && !cls[i].same(c)) ++i;
-        if (i == cls.size()) cls.push_back(c);
-        cls[i].members.push_back(m);
+        cls[class_index(cls, c)].members.push_back(m);
     }
     size_t slot = 0;
     HIPCHK(h0, ring_take(h0->step_ring, (size_t)M, &slot));
-    char* a = static_cast<char*>(h0->step_ring.host) + slot * h0->step_ring.elem;
-    const char* d = static_cast<const char*>(h0->step_ring.dev) + slot * h0->step_ring.elem;
+    char* a = h0->step_ring.host_bytes(slot);
+    const char* d = h0->step_ring.dev_bytes(slot);
     if (loss_sum_out && !h0->step_pack) HIPCHK(h0, hipMalloc((void**)&h0->step_pack, FNN_STEP_MAX_MODELS * sizeof(GroupPack)));
     GroupPack* pack = loss_sum_out ? h0->step_pack : nullptr;
 
@@ -1991,7 +1987,7 @@ int fnn_train_step_multi(fnn_handle* const* hs, int n_models, const int32_t* ids
     for (int m = 0; m < M; ++m) {
         loss_sum_out[m] = hp[m].loss;
         if (hp[m].flag) {
-            bad += (bad.empty() ? "" : ", ") + std::to_string(m);
+            eval_list_add(bad, m);
             HIPCHK(h0, hipMemsetAsync(hs[m]->err_flag, 0, sizeof(int), st));
         }
     }

@@ -1,5 +1,5 @@
-// ip_bwd_code.inc.h -- the code of k_ip_bwd<WV> (ipnn_api.hip), included inside the solo kernel and inside its group form
-// k_ip_bwd_g: `a` (IpBwdArgs), `dz`, `gxp` and `gb_part` are the including function's.  Text, not a __device__ function: as a
+// ip_bwd_code.inc.h -- the code of k_ip_bwd<WV> (ip_gather_kernels.hip.h), included inside the solo kernel and inside its group form
+// k_ip_bwd_g (ip_group_kernels.hip.h): `a` (IpBwdArgs), `dz`, `gxp` and `gb_part` are the including function's.  Text, not a __device__ function: as a
 // function inlined into both kernels it compiled the solo kernel to other instructions than its own code in place does, and the
 // solo step measured 0.7 % slower ("A mini-batch step for many inner-product models").
     extern __shared__ __align__(16) unsigned char smem[];

@@ -1,5 +1,5 @@
-// ip_update_all_code.inc.h -- the code of k_ip_update_all<T> (ipnn_api.hip), included inside the solo kernel and inside its group
-// form k_ip_update_all_g: `u` (IpUpdArgs) and T are the including function's; the last workgroup of x leaves through UPDATE_ALL_DONE.
+// ip_update_all_code.inc.h -- the code of k_ip_update_all<T> (ip_step_kernels.hip.h), included inside the solo kernel and inside its group
+// form k_ip_update_all_g (ip_group_kernels.hip.h): `u` (IpUpdArgs) and T are the including function's; the last workgroup of x leaves through UPDATE_ALL_DONE.
 // Text, not a __device__ function, for the reason ip_bwd_code.inc.h gives.
     if (blockIdx.x == gridDim.x - 1) {               // scalar tail: the loss, a fixed-shape tree (b: k_ip_b_update)
         __shared__ float sl[256];

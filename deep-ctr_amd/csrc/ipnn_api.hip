@@ -1,10 +1,13 @@
-// ipnn_api.hip -- the inner-product FNN family (FNN_IP_L3 / L5 / L7) on gfx950: kernels + C ABI
+// ipnn_api.hip -- the inner-product FNN family (FNN_IP_L3 / L5 / L7) on gfx950: the host side and the C ABI
 // (include/ipnn_hip.h).  Replaces the TensorFlow graph of python/FNN_IP_L7.py:102-133 (forward),
 // :82-88 (loss) and its gradient step (plain SGD).  Built from the FNN path's pieces: the
 // fragment-tiled MFMA GEMM with fused epilogues (k_gemm_ft: forward, backward-data and the split-K
 // weight-gradient product of every layer, 64 x 64 per wave, operands double-buffered in registers) and the
-// sorted, atomics-free sparse-row update (k_sortA / k_sortB / k_scat1 / k_scat2) -- plus two kernels of its
-// own for the inner-product layer.
+// sorted, atomics-free sparse-row update (k_sortA / k_sortB / k_scat1 / k_scat2) -- plus the family's own kernels,
+// which this unit alone includes: the inner-product layer (ip_gather_kernels.hip.h), the strip kernels of the deep
+// stack (ip_strip_kernels.hip.h), the masks and updates of a step (ip_step_kernels.hip.h) and the group forms of the
+// calls on many models (ip_group_kernels.hip.h).  Here: the handle, the knobs, the step plan, the kernel selectors,
+// one call (ip_run), the group calls and the C ABI.
 #include <hip/hip_runtime.h>
 
 #include <algorithm>
@@ -22,6 +25,10 @@
 #include "sparse_rows.hip.h"
 #include "metrics.hip.h"
 #include "optim.hip.h"
+#include "ip_gather_kernels.hip.h"
+#include "ip_strip_kernels.hip.h"
+#include "ip_step_kernels.hip.h"
+#include "ip_group_kernels.hip.h"
 
 using namespace fnn;
 
@@ -29,1597 +36,6 @@ namespace {
 
 thread_local std::string g_ip_err;
 inline int rup(int x, int m) { return (x + m - 1) / m * m; }
-
-constexpr int A_TANH = IPNN_ACT_TANH, A_SIG = IPNN_ACT_SIGMOID, A_RELU = IPNN_ACT_RELU;
-
-__device__ inline float ip_act(float z, int act) {
-    if (act == A_RELU) return fmaxf(z, 0.f);
-    if (act == A_TANH) return tanhf(z);
-    return 1.0f / (1.0f + expf(-z));
-}
-template <int ACT> __device__ inline float ip_act_c(float z) {
-    if (ACT == A_RELU) return fmaxf(z, 0.f);
-    if (ACT == A_TANH) return tanhf(z);
-    return 1.0f / (1.0f + expf(-z));
-}
-template <int ACT> __device__ inline float ip_dact_u_c(float u) {
-    if (ACT == A_RELU) return u > 0.f ? 1.0f : 0.0f;
-    if (ACT == A_TANH) return 1.0f - u * u;
-    return u * (1.0f - u);
-}
-// derivative of act at l, written in terms of u = act(l)
-__device__ inline float ip_dact_u(float u, int act) {
-    if (act == A_RELU) return u > 0.f ? 1.0f : 0.0f;
-    if (act == A_TANH) return 1.0f - u * u;
-    return u * (1.0f - u);
-}
-
-// ------------------------------------------------------------------------------------------
-// Inner-product layer, forward (python/FNN_IP_L7.py:104-114 + the first act/dropout of :115):
-// 16 examples per workgroup.  a0' [Ba][D0p] in "slot" layout: column 16 f + l = e_f[l],
-// columns 16F .. 16F+P-1 the P = F(F-1)/2 pair products (row-major i < j), column CB = b,
-// column CB+1 = 1 (carries h1_b); every real column goes through act and the keep-mask / keep.
-// a0 is written fragment-tiled twice: a0F (rows = examples, k = columns: the next forward product's
-// A operand) and a0T (rows = columns, k = examples: the weight-gradient product's A operand).
-// ------------------------------------------------------------------------------------------
-struct IpFwdArgs {
-    int P;                      // pair products: F (F - 1) / 2 (FNN_IP_L*) or 0 (the plain FNN class, python/FNN.py:80)
-    const int32_t* ids; int B, F, K; const float* table16; int64_t n_rows; const float* b;
-    const uint8_t* mask; int d0; float inv_keep; int act; int D0p, ldT; int* err;
-    int skip;                   // diagnostics (IPNN_FWD_SKIP bits: 1 gather, 2 embedding store, 4 compute, 8 output stores); 0 in production
-    bool wt;                    // outputs written through (IPNN_WT=0: plain stores; see store4_wt in fnn_kernels.hip.h)
-    const float* wts;           // value weights [B][F] (read by the WV variant only; NULL: every weight 1)
-};
-
-// gather of 16 examples' rows into an LDS tile [16][F*16]: all ids of a batch of 4 elements per thread first, then all
-// rows (two dependent round trips per batch instead of two per element)
-// STR: floats per field in the tile -- 16 (vector stores), or 17 for the forward's pair products: lanes that read slot l of
-// DIFFERENT fields then fall on different banks (with 16 all of them share two banks: a 32-way conflict per read)
-// WV: value weights (ipnn_*_w with wts != NULL): the weight of (example t, field f) sits at the id's own index, is loaded in the id's
-// round trip and scales the row's pieces in f32, so that the tile -- and emb, copied from it -- holds e_f = wts[t][f] * row
-template <int STR, int NT = 256, bool WV = false>
-__device__ __forceinline__ void ip_gather16(float* se, const int32_t* __restrict__ ids, const float* __restrict__ table16,
-                                            const int64_t n_rows, const int t0, const int B, const int F, int* err,
-                                            const float* __restrict__ wts = nullptr)
-{
-    const int n = 16 * F * 4, FS = F * STR;
-    for (int e0 = threadIdx.x; e0 < n; e0 += NT * 4) {
-        int64_t id[4];
-        float w[4];
-#pragma unroll
-        for (int j = 0; j < 4; ++j) {
-            const int e = e0 + NT * j, f = (e >> 2) % F, t = t0 + (e >> 2) / F;
-            id[j] = (e < n && t < B) ? (int64_t)ids[(size_t)t * F + f] : -1;
-            if (WV) w[j] = (e < n && t < B) ? wts[(size_t)t * F + f] : 0.f;
-        }
-        float4 v[4];
-#pragma unroll
-        for (int j = 0; j < 4; ++j) {
-            const int e = e0 + NT * j;
-            if (e < n && t0 + (e >> 2) / F < B && (id[j] < 0 || id[j] >= n_rows)) { if (err) atomicOr(err, 1); id[j] = -1; }
-            v[j] = id[j] >= 0 ? *reinterpret_cast<const float4*>(table16 + (size_t)id[j] * SLOT + 4 * (e & 3)) : make_float4(0.f, 0.f, 0.f, 0.f);
-            if (WV && id[j] >= 0) { v[j].x *= w[j]; v[j].y *= w[j]; v[j].z *= w[j]; v[j].w *= w[j]; }
-        }
-#pragma unroll
-        for (int j = 0; j < 4; ++j) {
-            const int e = e0 + NT * j;
-            if (e < n) {
-                float* d = se + ((e >> 2) / F) * FS + ((e >> 2) % F) * STR + 4 * (e & 3);
-                if (STR == SLOT) *reinterpret_cast<float4*>(d) = v[j];
-                else { d[0] = v[j].x; d[1] = v[j].y; d[2] = v[j].z; d[3] = v[j].w; }
-            }
-        }
-    }
-}
-
-constexpr int IPF_NT = 512;     // 8 waves: the kernel is bound by instruction issue, two waves per SIMD overlap it (IPNN_IPF_NT=1024: four)
-// (the body of k_ip_fwd and of its group form k_ip_fwd_g; TL = false: the T layout a0T is not written -- a prediction reads a0 only)
-template <typename T, int NT, bool WV, bool TL = true>
-__device__ __forceinline__ void ip_fwd_body(const IpFwdArgs& a, T* __restrict__ a0, T* __restrict__ a0T, float* __restrict__ emb)
-{
-    typedef typename Traits<T>::frag frag;
-    constexpr int EPL = Traits<T>::EPL;
-    extern __shared__ __align__(16) unsigned char smem[];
-    constexpr int SP = SLOT + 1;                                // padded field stride of the embedding tile
-    float* se = reinterpret_cast<float*>(smem);                 // [16][F*17] raw embeddings
-    float* sa = se + 16 * a.F * SP;                             // [16][D0p]  a0 values
-    const int tid = threadIdx.x, t0 = blockIdx.x * 16, F = a.F, K = a.K, B = a.B, FS = F * SLOT, FSP = F * SP;
-    const int P = a.P, CB = FS + P;
-    if (!(a.skip & 1)) ip_gather16<SP, NT, WV>(se, a.ids, a.table16, a.n_rows, t0, B, F, a.err, a.wts);
-    __syncthreads();
-    if (emb && !(a.skip & 2))                                                    // kept for the backward of the inner products (no second gather; WV: weighted)
-        for (int e = tid; e < 16 * FS / 4; e += NT) {
-            const int r = (4 * e) / FS, c = (4 * e) % FS;
-            const float* q = se + r * FSP + (c >> 4) * SP + (c & 15);
-            store16_sel(a.wt, emb + (size_t)t0 * FS + 4 * e, make_float4(q[0], q[1], q[2], q[3]));
-        }
-    const float bval = *a.b;
-    // a thread owns columns c = (tid & 63) + 64 k and rows r = (tid >> 6) + NWV i; 8 columns at a time: their pair indices,
-    // then all 8 RPT keep-mask bytes (one round trip), then the values
-    constexpr int NWV = NT / 64, RPT = 16 / NWV;
-    for (int c0 = tid & 63; c0 < ((a.skip & 4) ? 0 : a.D0p); c0 += 512) {
-        int ref[8], pi[8], pj[8];                               // ref: column in the reference's z1 order
-#pragma unroll
-        for (int k = 0; k < 8; ++k) {
-            const int c = c0 + 64 * k;
-            ref[k] = -1; pi[k] = 0; pj[k] = 0;
-            if (c < FS) { const int f = c / SLOT, l = c % SLOT; if (l < K) ref[k] = f * K + l; }
-            else if (c < CB) {
-                int n = c - FS, i = 0;                          // n-th pair (i, j), i < j, row-major
-                while (n >= F - 1 - i) { n -= F - 1 - i; ++i; }
-                pi[k] = i; pj[k] = i + 1 + n; ref[k] = F * K + (c - FS);
-            } else if (c == CB) ref[k] = a.d0 - 1;
-        }
-        float mk[8][RPT];
-#pragma unroll
-        for (int k = 0; k < 8; ++k)
-#pragma unroll
-            for (int i = 0; i < RPT; ++i) {
-                const int t = t0 + (tid >> 6) + NWV * i;
-                mk[k][i] = (a.mask && ref[k] >= 0 && t < B) ? (float)a.mask[(size_t)t * a.d0 + ref[k]] * a.inv_keep : 1.0f;
-            }
-#pragma unroll
-        for (int k = 0; k < 8; ++k) {
-            const int c = c0 + 64 * k;
-            if (c >= a.D0p) break;
-#pragma unroll
-            for (int i = 0; i < RPT; ++i) {
-                const int r = (tid >> 6) + NWV * i, t = t0 + r;
-                float z = 0.f;
-                if (c < FS) z = se[r * FSP + (c >> 4) * SP + (c & 15)];
-                else if (c < CB) {
-                    float s2 = 0.f;
-                    for (int l = 0; l < K; ++l) s2 = fmaf(se[r * FSP + pi[k] * SP + l], se[r * FSP + pj[k] * SP + l], s2);
-                    z = s2;
-                } else if (c == CB) z = bval;
-                float v = 0.f;
-                if (t < B) {
-                    if (ref[k] >= 0) v = ip_act(z, a.act) * mk[k][i];
-                    else if (c == CB + 1) v = 1.0f;
-                }
-                sa[r * a.D0p + c] = v;
-            }
-        }
-    }
-    __syncthreads();
-    // F layout: this workgroup's 16 rows are one row tile; a lane-slot of a fragment = EPL consecutive columns of one row
-    if (a.skip & 8) return;
-    for (int e = tid; e < 16 * a.D0p / EPL; e += NT) {
-        const int g = e >> 4, r = e & 15;                        // column group, row
-        frag fv;
-#pragma unroll
-        for (int x = 0; x < EPL; ++x) fv[x] = (T)sa[r * a.D0p + g * EPL + x];
-        store16_sel(a.wt, a0 + ft_off<T>(t0 + r, g * EPL, a.D0p), fv);
-    }
-    if (!TL) return;
-    for (int e = tid; e < a.D0p * 4; e += NT) {
-        const int c = e >> 2, tq = e & 3;
-        store4_sel(a.wt, a0T + ft_off<T>(c, t0 + 4 * tq, a.ldT), sa[(4 * tq) * a.D0p + c], sa[(4 * tq + 1) * a.D0p + c],
-                  sa[(4 * tq + 2) * a.D0p + c], sa[(4 * tq + 3) * a.D0p + c]);
-    }
-}
-template <typename T, int NT = IPF_NT, bool WV = false>
-static __global__ __launch_bounds__(NT) void k_ip_fwd(const IpFwdArgs a, T* __restrict__ a0, T* __restrict__ a0T, float* __restrict__ emb)
-{
-    ip_fwd_body<T, NT, WV>(a, a0, a0T, emb);
-}
-
-// Inner-product layer, backward: dz1' [Ba][D0p] f32 (already times mask/keep and act') ->
-// slot-layout embedding gradients gx' [Ba][D0p] (columns 16f + l) for the sparse-row update, and the
-// per-workgroup partial of db = sum_t dz1[b].
-// WV (value weights): emb holds the weighted embeddings, so the partner reads are unchanged; the finished gradient of (field f,
-// example t) is the gradient of e_f, and its row's is that times wts[t][f].  The 16 x F weights of the tile are staged in the F
-// floats per example that the launch's LDS size (k_ip_fwd's: a 17-float field stride) leaves behind sd.
-struct IpBwdArgs { int P; const int32_t* ids; int B, F, K; const float* table16; int64_t n_rows; int D0p; const float* emb; const float* wts; };
-
-template <bool WV = false>
-static __global__ __launch_bounds__(256) void k_ip_bwd(const IpBwdArgs a, const float* __restrict__ dz, float* __restrict__ gxp,
-                                                        float* __restrict__ gb_part)
-{
-#include "ip_bwd_code.inc.h"
-}
-
-// ------------------------------------------------------------------------------------------
-// Wide rows (k = 17 .. 128, FM50 / FM100 seeds): the same layer on rows of rw = rup(k, 4) floats.  Layer 0 column f rw + l
-// holds e_f[l], then the P pair products, b and the ones column: D0p = rup(F rw + P + 2, 64).  k_ip_fwd's tile (16 examples x
-// (17 F + D0p) floats) does not fit the LDS there -- 220 KB at F = 16, k = 101, ~560 KB at F rw = 4096 -- so a workgroup takes
-// IPW_EX = 8 examples and stages only their embeddings (F (rw + 1) floats each, <= 132 KB).  Each a0 value is computed in
-// registers: a thread owns EPL consecutive columns of the 8 examples, which is one lane slot of every example's F-layout row and
-// whole lane slots of the T layout (bf16: 8 examples = one 16-byte slot, so no slot is shared by two workgroups), so a0 needs no
-// LDS tile at all.
-// ------------------------------------------------------------------------------------------
-constexpr int IPW_EX = 8;       // examples per workgroup of the wide inner-product launches
-struct IpWideArgs {
-    int P; const int32_t* ids; int B, F, K, rw; const float* table; int64_t n_rows; const float* b;
-    const uint8_t* mask; int d0; float inv_keep; int act; int D0p, ldT; int* err;
-    bool wt;                    // outputs written through (IPNN_WT=0: plain stores)
-    unsigned a0_bytes, emb_bytes;   // sizes of a0 / a0T and of emb: the extent of the write-through stores' buffer resources
-    const float* wts;           // value weights [B][F] (read by the WV variants only; NULL: every weight 1)
-};
-// The wide kernels' write-through stores are raw buffer stores with the sc1 policy (aux 16), not the inline-asm store16_wt /
-// store4_wt: hipcc neither counts nor pads an asm store, so the instruction after a `global_store_dwordx4` there may overwrite its
-// data registers before the store has read them -- in k_ip_fwd_w<bf16_t> that happened (a0 differed between identical runs).
-typedef unsigned int ipw_u32x4 __attribute__((ext_vector_type(4)));
-typedef unsigned int ipw_u32x2 __attribute__((ext_vector_type(2)));
-__device__ __forceinline__ __amdgpu_buffer_rsrc_t ipw_rsrc(const void* p, unsigned bytes) {
-    return __builtin_amdgcn_make_buffer_rsrc(const_cast<void*>(p), 0, (int)bytes, 0x00020000);
-}
-template <typename V> __device__ __forceinline__ void ipw_store16(const bool wt, const __amdgpu_buffer_rsrc_t rs, void* base, const size_t off, const V& v) {
-    static_assert(sizeof(V) == 16, "ipw_store16: 16-byte values");
-    ipw_u32x4 w; __builtin_memcpy(&w, &v, 16);
-    if (wt) __builtin_amdgcn_raw_buffer_store_b128(w, rs, (int)off, 0, 16);
-    else *reinterpret_cast<ipw_u32x4*>(static_cast<char*>(base) + off) = w;
-}
-// four consecutive k of a fragment-tiled operand: 16 bytes (f32) or 8 (bf16)
-__device__ __forceinline__ void ipw_store4(const bool wt, const __amdgpu_buffer_rsrc_t rs, float* base, const size_t e, float a, float b, float c, float d) {
-    ipw_store16(wt, rs, base, e * 4, make_float4(a, b, c, d));
-}
-__device__ __forceinline__ void ipw_store4(const bool wt, const __amdgpu_buffer_rsrc_t rs, bf16_t* base, const size_t e, float a, float b, float c, float d) {
-    bf16x4 v = {(bf16_t)a, (bf16_t)b, (bf16_t)c, (bf16_t)d};
-    ipw_u32x2 w; __builtin_memcpy(&w, &v, 8);
-    if (wt) __builtin_amdgcn_raw_buffer_store_b64(w, rs, (int)(e * 2), 0, 16);
-    else *reinterpret_cast<ipw_u32x2*>(base + e) = w;
-}
-inline size_t ipw_fwd_lds(int F, int rw) { return (size_t)IPW_EX * F * (rw + 1) * sizeof(float); }
-inline size_t ipw_bwd_lds(int F, int rw, int P, bool wv) { return (size_t)IPW_EX * (F * rw + P + (wv ? F : 0)) * sizeof(float); }
-
-// WV (value weights, here and in k_ip_bwd_w / k_ip_fwd_m / k_ip_bwd_m): as in ip_gather16 and k_ip_bwd -- every 16-byte piece of a
-// gathered row is scaled by wts[t][f] before it goes to the tile and to emb; the backward scales its finished gradient once.
-template <typename T, bool WV, bool TL = true>
-__device__ __forceinline__ void ip_fwd_w_body(const IpWideArgs& a, T* __restrict__ a0, T* __restrict__ a0T, float* __restrict__ emb)
-{
-    typedef typename Traits<T>::frag frag;
-    constexpr int EPL = Traits<T>::EPL;
-    extern __shared__ __align__(16) unsigned char smem[];
-    float* se = reinterpret_cast<float*>(smem);                 // [IPW_EX][F][rw + 1]: the odd stride spreads the pair reads of a wave
-    const int F = a.F, K = a.K, rw = a.rw, SW = rw + 1, nq = rw >> 2, FW = F * rw, CB = FW + a.P, B = a.B;
-    const int t0 = blockIdx.x * IPW_EX;
-    const __amdgpu_buffer_rsrc_t r_emb = ipw_rsrc(emb, a.emb_bytes), r_a0 = ipw_rsrc(a0, a.a0_bytes), r_a0T = ipw_rsrc(a0T, a.a0_bytes);
-    // gather: IPW_EX x F rows of nq 16-byte pieces, four in flight per thread; the raw rows also go to emb (the backward's copy)
-    const int n = IPW_EX * F * nq;
-    for (int e0 = threadIdx.x; e0 < n; e0 += 256 * 4) {
-        int64_t id[4];
-        float w[4];
-#pragma unroll
-        for (int j = 0; j < 4; ++j) {
-            const int e = e0 + 256 * j, t = t0 + e / (F * nq), f = (e / nq) % F;
-            id[j] = (e < n && t < B) ? (int64_t)a.ids[(size_t)t * F + f] : -1;
-            if (WV) w[j] = (e < n && t < B) ? a.wts[(size_t)t * F + f] : 0.f;
-            if (e < n && t < B && (id[j] < 0 || id[j] >= a.n_rows)) { if (a.err) atomicOr(a.err, 1); id[j] = -1; }
-        }
-        float4 v[4];
-#pragma unroll
-        for (int j = 0; j < 4; ++j) {
-            const int e = e0 + 256 * j;
-            v[j] = id[j] >= 0 ? *reinterpret_cast<const float4*>(a.table + (size_t)id[j] * rw + 4 * (e % nq)) : make_float4(0.f, 0.f, 0.f, 0.f);
-            if (WV && id[j] >= 0) { v[j].x *= w[j]; v[j].y *= w[j]; v[j].z *= w[j]; v[j].w *= w[j]; }
-        }
-#pragma unroll
-        for (int j = 0; j < 4; ++j) {
-            const int e = e0 + 256 * j;
-            if (e >= n) continue;
-            const int r = e / (F * nq), f = (e / nq) % F, q = e % nq;
-            float* d = se + (r * F + f) * SW + 4 * q;
-            d[0] = v[j].x; d[1] = v[j].y; d[2] = v[j].z; d[3] = v[j].w;
-            if (emb) ipw_store16(a.wt, r_emb, emb, ((size_t)(t0 + r) * FW + f * rw + 4 * q) * 4, v[j]);
-        }
-    }
-    __syncthreads();
-    const float bval = *a.b;
-    for (int g = threadIdx.x; g < a.D0p / EPL; g += 256) {
-        float v[IPW_EX][EPL];
-#pragma unroll
-        for (int x = 0; x < EPL; ++x) {
-            const int c = g * EPL + x;
-            int ref = -1;
-            float z[IPW_EX];
-#pragma unroll
-            for (int r = 0; r < IPW_EX; ++r) z[r] = 0.f;
-            if (c < FW) {
-                const int f = c / rw, l = c - f * rw;
-                if (l < K) {
-                    ref = f * K + l;
-#pragma unroll
-                    for (int r = 0; r < IPW_EX; ++r) z[r] = se[(r * F + f) * SW + l];
-                }
-            } else if (c < CB) {
-                int m = c - FW, i = 0;                          // m-th pair (i, j), i < j, row-major
-                while (m >= F - 1 - i) { m -= F - 1 - i; ++i; }
-                const int j = i + 1 + m;
-                ref = F * K + (c - FW);
-#pragma unroll
-                for (int r = 0; r < IPW_EX; ++r) {
-                    const float* pi = se + (r * F + i) * SW;
-                    const float* pj = se + (r * F + j) * SW;
-                    float s2 = 0.f;
-                    for (int l = 0; l < K; ++l) s2 = fmaf(pi[l], pj[l], s2);
-                    z[r] = s2;
-                }
-            } else if (c == CB) {
-                ref = a.d0 - 1;
-#pragma unroll
-                for (int r = 0; r < IPW_EX; ++r) z[r] = bval;
-            }
-#pragma unroll
-            for (int r = 0; r < IPW_EX; ++r) {
-                const int t = t0 + r;
-                float val = 0.f;
-                if (t < B) {
-                    if (ref >= 0) val = ip_act(z[r], a.act) * (a.mask ? (float)a.mask[(size_t)t * a.d0 + ref] * a.inv_keep : 1.0f);
-                    else if (c == CB + 1) val = 1.0f;
-                }
-                v[r][x] = val;
-            }
-        }
-#pragma unroll
-        for (int r = 0; r < IPW_EX; ++r) {                       // F layout: the EPL columns of an example are one lane slot
-            frag fv;
-#pragma unroll
-            for (int x = 0; x < EPL; ++x) fv[x] = (T)v[r][x];
-            ipw_store16(a.wt, r_a0, a0, ft_off<T>(t0 + r, g * EPL, a.D0p) * sizeof(T), fv);
-        }
-#pragma unroll
-        for (int x = 0; x < EPL; ++x)                           // T layout: a column's examples are consecutive k
-#pragma unroll
-            for (int r = 0; r < IPW_EX; r += 4)
-                if (TL) ipw_store4(a.wt, r_a0T, a0T, ft_off<T>(g * EPL + x, t0 + r, a.ldT), v[r][x], v[r + 1][x], v[r + 2][x], v[r + 3][x]);
-    }
-}
-template <typename T, bool WV = false>
-static __global__ __launch_bounds__(256) void k_ip_fwd_w(const IpWideArgs a, T* __restrict__ a0, T* __restrict__ a0T, float* __restrict__ emb)
-{
-    ip_fwd_w_body<T, WV>(a, a0, a0T, emb);
-}
-
-// Wide backward: gx'[t][f rw + l] = dz[t][f rw + l] + sum_j dz[t][pair(f, j)] e_j[l] (l < k; pad columns 0), and the per-workgroup
-// partial of db.  The embeddings come from emb (the forward's copy); the pair deltas of the 8 examples are staged beside them.
-template <bool WV = false>
-static __global__ __launch_bounds__(256) void k_ip_bwd_w(const IpWideArgs a, const float* __restrict__ dz, const float* __restrict__ emb,
-                                                          float* __restrict__ gxp, float* __restrict__ gb_part)
-{
-    extern __shared__ __align__(16) unsigned char smem[];
-    const int F = a.F, K = a.K, rw = a.rw, FW = F * rw, P = a.P, CB = FW + P, D0p = a.D0p;
-    float* se = reinterpret_cast<float*>(smem);                 // [IPW_EX][F rw]
-    float* sp = se + IPW_EX * FW;                               // [IPW_EX][P]
-    float* sw = sp + IPW_EX * P;                                // [IPW_EX][F] value weights (WV only: ipw_bwd_lds)
-    const int t0 = blockIdx.x * IPW_EX;
-    {
-        const int n4 = IPW_EX * FW / 4;                         // the 8 examples' rows are contiguous in emb
-        const float4* src = reinterpret_cast<const float4*>(emb + (size_t)t0 * FW);
-        for (int e0 = threadIdx.x; e0 < n4; e0 += 256 * 4) {
-            float4 v[4];
-#pragma unroll
-            for (int k = 0; k < 4; ++k) { const int e = e0 + 256 * k; v[k] = e < n4 ? src[e] : make_float4(0.f, 0.f, 0.f, 0.f); }
-#pragma unroll
-            for (int k = 0; k < 4; ++k) { const int e = e0 + 256 * k; if (e < n4) reinterpret_cast<float4*>(se)[e] = v[k]; }
-        }
-        for (int e = threadIdx.x; e < IPW_EX * P; e += 256) sp[e] = dz[(size_t)(t0 + e / P) * D0p + FW + e % P];
-        if (WV) for (int e = threadIdx.x; e < IPW_EX * F; e += 256) sw[e] = t0 + e / F < a.B ? a.wts[(size_t)t0 * F + e] : 1.0f;
-    }
-    __syncthreads();
-    for (int c = threadIdx.x; c < FW; c += 256) {               // a thread owns (field f, lane l) for the 8 examples
-        const int f = c / rw, l = c - f * rw;
-        float g[IPW_EX];
-#pragma unroll
-        for (int r = 0; r < IPW_EX; ++r) g[r] = l < K ? dz[(size_t)(t0 + r) * D0p + c] : 0.f;
-        if (l < K && P) {
-            for (int j = 0; j < F; ++j) {
-                if (j == f) continue;
-                // pair (i, j), i < j, sits at FW + i (2F - i - 1) / 2 + (j - i - 1)
-                const int i0 = f < j ? f : j, j0 = f < j ? j : f, m = i0 * (2 * F - i0 - 1) / 2 + (j0 - i0 - 1);
-#pragma unroll
-                for (int r = 0; r < IPW_EX; ++r) g[r] = fmaf(sp[r * P + m], se[r * FW + j * rw + l], g[r]);
-            }
-        }
-        if (WV) {
-#pragma unroll
-            for (int r = 0; r < IPW_EX; ++r) g[r] *= sw[r * F + f];
-        }
-#pragma unroll
-        for (int r = 0; r < IPW_EX; ++r) gxp[(size_t)(t0 + r) * D0p + c] = g[r];
-    }
-    if (threadIdx.x == 0) { float s = 0.f; for (int r = 0; r < IPW_EX; ++r) s += dz[(size_t)(t0 + r) * D0p + CB]; gb_part[blockIdx.x] = s; }
-}
-
-// the bag table's wide sparse-row update (sparse_rows.hip.h) on wide rows: gradient of (example t, field f) at gx'[t][f rw + l]
-static __global__ __launch_bounds__(256) void k_ip_scatw1(const ScatArgs sa) { scatw1_body(sa, blockIdx.x); }
-static __global__ __launch_bounds__(256) void k_ip_scatw2(const ScatArgs sa)
-{
-    __shared__ double s_w[1024];
-    scatw2_body(sa, blockIdx.x, gridDim.x, s_w);
-}
-
-// ------------------------------------------------------------------------------------------
-// Many fields (33 .. 64 fields of narrow rows, k <= 16: the reference's own 39 columns): k_ip_fwd's tile of 16 examples x
-// (17 F + D0p) floats passes the LDS above 45 fields with pairs (164,736 B at 46, 266,240 B at 64), and where it still fits it
-// leaves one workgroup per CU.  These two kernels (each chosen on its own: ip_many_choice) stage the embeddings only, as the wide pair does, on the 16-float slots of
-// the narrow table: the forward takes IPM_EX = 8 examples per workgroup (8 x F x 17 floats: 34,816 B at 64 fields, four
-// workgroups per CU) and computes every a0 value in registers -- a thread owns EPL consecutive columns of the 8 examples: one
-// lane slot of each example's F-layout row and whole lane slots of the T layout.  At 64 fields 2016 of the 3042 used columns
-// are pair products, so the column -> (i, j) walk of k_ip_fwd (up to F - 1 trips per column) is a table here (ptab, written at
-// create beside ref0: i | j << 8).  The backward takes IPM_BEX = 4 examples: their embeddings and the pair slice of dz
-// (4 x (16 F + P) floats: 48,640 B at 64 fields, three workgroups per CU).
-// ------------------------------------------------------------------------------------------
-constexpr int IPM_EX = 8;       // examples per workgroup of the many-field forward
-constexpr int IPM_BEX = 4;      // ... and of the backward
-struct IpManyArgs {
-    int P; const int32_t* ids; int B, F, K; const float* table16; int64_t n_rows; const float* b;
-    const uint8_t* mask; int d0; float inv_keep; int act; int D0p, ldT; int* err;
-    const unsigned short* ptab; // [P]: pair n = (i, j), i < j, row-major, as i | j << 8
-    bool wt;                    // outputs written through (IPNN_WT=0: plain stores)
-    unsigned a0_bytes, emb_bytes;   // sizes of a0 / a0T and of emb: the extent of the write-through stores' buffer resources
-    const float* wts;           // value weights [B][F] (read by the WV variants only; NULL: every weight 1)
-};
-inline size_t ipm_fwd_lds(int F) { return (size_t)IPM_EX * F * (SLOT + 1) * sizeof(float); }
-inline size_t ipm_bwd_lds(int F, int P, bool wv) { return (size_t)IPM_BEX * (F * SLOT + P + (wv ? F : 0)) * sizeof(float); }
-
-template <typename T, bool WV, bool TL = true>
-__device__ __forceinline__ void ip_fwd_m_body(const IpManyArgs& a, T* __restrict__ a0, T* __restrict__ a0T, float* __restrict__ emb)
-{
-    typedef typename Traits<T>::frag frag;
-    constexpr int EPL = Traits<T>::EPL, SP = SLOT + 1;
-    extern __shared__ __align__(16) unsigned char smem[];
-    float* se = reinterpret_cast<float*>(smem);                 // [IPM_EX][F][17]: lanes reading slot l of different fields fall on different banks
-    const int F = a.F, K = a.K, FS = F * SLOT, FSP = F * SP, CB = FS + a.P, B = a.B;
-    const int t0 = blockIdx.x * IPM_EX;
-    const __amdgpu_buffer_rsrc_t r_emb = ipw_rsrc(emb, a.emb_bytes), r_a0 = ipw_rsrc(a0, a.a0_bytes), r_a0T = ipw_rsrc(a0T, a.a0_bytes);
-    // gather: IPM_EX x F rows of four 16-byte pieces, four in flight per thread; the raw rows also go to emb (the backward's copy)
-    const int n = IPM_EX * F * 4;
-    for (int e0 = threadIdx.x; e0 < n; e0 += 256 * 4) {
-        int64_t id[4];
-        float w[4];
-#pragma unroll
-        for (int j = 0; j < 4; ++j) {
-            const int e = e0 + 256 * j, t = t0 + (e >> 2) / F, f = (e >> 2) % F;
-            id[j] = (e < n && t < B) ? (int64_t)a.ids[(size_t)t * F + f] : -1;
-            if (WV) w[j] = (e < n && t < B) ? a.wts[(size_t)t * F + f] : 0.f;
-            if (e < n && t < B && (id[j] < 0 || id[j] >= a.n_rows)) { if (a.err) atomicOr(a.err, 1); id[j] = -1; }
-        }
-        float4 v[4];
-#pragma unroll
-        for (int j = 0; j < 4; ++j) {
-            const int e = e0 + 256 * j;
-            v[j] = id[j] >= 0 ? *reinterpret_cast<const float4*>(a.table16 + (size_t)id[j] * SLOT + 4 * (e & 3)) : make_float4(0.f, 0.f, 0.f, 0.f);
-            if (WV && id[j] >= 0) { v[j].x *= w[j]; v[j].y *= w[j]; v[j].z *= w[j]; v[j].w *= w[j]; }
-        }
-#pragma unroll
-        for (int j = 0; j < 4; ++j) {
-            const int e = e0 + 256 * j;
-            if (e >= n) continue;
-            const int r = (e >> 2) / F, f = (e >> 2) % F, q = e & 3;
-            float* d = se + r * FSP + f * SP + 4 * q;
-            d[0] = v[j].x; d[1] = v[j].y; d[2] = v[j].z; d[3] = v[j].w;
-            if (emb) ipw_store16(a.wt, r_emb, emb, ((size_t)(t0 + r) * FS + f * SLOT + 4 * q) * 4, v[j]);
-        }
-    }
-    __syncthreads();
-    const float bval = *a.b;
-    for (int g = threadIdx.x; g < a.D0p / EPL; g += 256) {
-        float v[IPM_EX][EPL];
-#pragma unroll
-        for (int x = 0; x < EPL; ++x) {
-            const int c = g * EPL + x;
-            int ref = -1, pi = 0, pj = 0;                       // ref: column in the reference's z1 order
-            if (c < FS) { if ((c & 15) < K) ref = (c >> 4) * K + (c & 15); }
-            else if (c < CB) { const unsigned pr = a.ptab[c - FS]; pi = (int)(pr & 255u); pj = (int)(pr >> 8); ref = F * K + (c - FS); }
-            else if (c == CB) ref = a.d0 - 1;
-            float mk[IPM_EX];                                   // the column's keep-mask bytes: one round trip, under the products
-#pragma unroll
-            for (int r = 0; r < IPM_EX; ++r)
-                mk[r] = (a.mask && ref >= 0 && t0 + r < B) ? (float)a.mask[(size_t)(t0 + r) * a.d0 + ref] * a.inv_keep : 1.0f;
-            float z[IPM_EX];
-#pragma unroll
-            for (int r = 0; r < IPM_EX; ++r) z[r] = 0.f;
-            if (c < FS) {
-#pragma unroll
-                for (int r = 0; r < IPM_EX; ++r) z[r] = se[r * FSP + (c >> 4) * SP + (c & 15)];
-            } else if (c < CB) {
-                const float* qi = se + pi * SP;
-                const float* qj = se + pj * SP;
-                for (int l = 0; l < K; ++l)
-#pragma unroll
-                    for (int r = 0; r < IPM_EX; ++r) z[r] = fmaf(qi[r * FSP + l], qj[r * FSP + l], z[r]);
-            } else if (c == CB) {
-#pragma unroll
-                for (int r = 0; r < IPM_EX; ++r) z[r] = bval;
-            }
-#pragma unroll
-            for (int r = 0; r < IPM_EX; ++r) {
-                float val = 0.f;
-                if (t0 + r < B) {
-                    if (ref >= 0) val = ip_act(z[r], a.act) * mk[r];
-                    else if (c == CB + 1) val = 1.0f;
-                }
-                v[r][x] = val;
-            }
-        }
-#pragma unroll
-        for (int r = 0; r < IPM_EX; ++r) {                       // F layout: the EPL columns of an example are one lane slot
-            frag fv;
-#pragma unroll
-            for (int x = 0; x < EPL; ++x) fv[x] = (T)v[r][x];
-            ipw_store16(a.wt, r_a0, a0, ft_off<T>(t0 + r, g * EPL, a.D0p) * sizeof(T), fv);
-        }
-#pragma unroll
-        for (int x = 0; x < EPL; ++x)                           // T layout: a column's examples are consecutive k
-#pragma unroll
-            for (int r = 0; r < IPM_EX; r += 4)
-                if (TL) ipw_store4(a.wt, r_a0T, a0T, ft_off<T>(g * EPL + x, t0 + r, a.ldT), v[r][x], v[r + 1][x], v[r + 2][x], v[r + 3][x]);
-    }
-}
-template <typename T, bool WV = false>
-static __global__ __launch_bounds__(256) void k_ip_fwd_m(const IpManyArgs a, T* __restrict__ a0, T* __restrict__ a0T, float* __restrict__ emb)
-{
-    ip_fwd_m_body<T, WV>(a, a0, a0T, emb);
-}
-
-// Many-field backward: gx'[t][16 f + l] = dz[t][16 f + l] + sum_{j != f} dz[t][pair(f, j)] e_j[l] (l < k; pad columns 0) and the
-// per-workgroup partial of db (one per IPM_BEX examples).  The embeddings come from emb (the forward's copy).  A wave holds four
-// fields x 16 slots: its read of e_j[l] is 16 addresses broadcast to the four fields, its read of the pair delta four addresses.
-template <bool WV = false>
-static __global__ __launch_bounds__(256) void k_ip_bwd_m(const IpManyArgs a, const float* __restrict__ dz, const float* __restrict__ emb,
-                                                          float* __restrict__ gxp, float* __restrict__ gb_part)
-{
-    extern __shared__ __align__(16) unsigned char smem[];
-    const int F = a.F, K = a.K, FS = F * SLOT, P = a.P, CB = FS + P, D0p = a.D0p;
-    float* se = reinterpret_cast<float*>(smem);                 // [IPM_BEX][16 F]
-    float* sp = se + IPM_BEX * FS;                              // [IPM_BEX][P]
-    float* sw = sp + IPM_BEX * P;                               // [IPM_BEX][F] value weights (WV only: ipm_bwd_lds)
-    const int t0 = blockIdx.x * IPM_BEX;
-    {
-        const int n4 = IPM_BEX * FS / 4;                        // the examples' rows are contiguous in emb
-        const float4* src = reinterpret_cast<const float4*>(emb + (size_t)t0 * FS);
-        for (int e0 = threadIdx.x; e0 < n4; e0 += 256 * 4) {
-            float4 v[4];
-#pragma unroll
-            for (int k = 0; k < 4; ++k) { const int e = e0 + 256 * k; v[k] = e < n4 ? src[e] : make_float4(0.f, 0.f, 0.f, 0.f); }
-#pragma unroll
-            for (int k = 0; k < 4; ++k) { const int e = e0 + 256 * k; if (e < n4) reinterpret_cast<float4*>(se)[e] = v[k]; }
-        }
-        // the pair slice of each example starts at column 16 F of a row of D0p floats: both multiples of 4, 16-byte pieces up to
-        // the last whole one, the rest one float at a time
-        const int p4 = P >> 2;
-        for (int e = threadIdx.x; e < IPM_BEX * p4; e += 256) {
-            const int r = e / p4, q = e - r * p4;
-            const float4 v = *reinterpret_cast<const float4*>(dz + (size_t)(t0 + r) * D0p + FS + 4 * q);
-            float* d = sp + r * P + 4 * q;
-            d[0] = v.x; d[1] = v.y; d[2] = v.z; d[3] = v.w;
-        }
-        const int rest = P & 3;
-        if ((int)threadIdx.x < IPM_BEX * rest) {
-            const int r = threadIdx.x / rest, q = 4 * p4 + threadIdx.x % rest;
-            sp[r * P + q] = dz[(size_t)(t0 + r) * D0p + FS + q];
-        }
-        if (WV) for (int e = threadIdx.x; e < IPM_BEX * F; e += 256) sw[e] = t0 + e / F < a.B ? a.wts[(size_t)t0 * F + e] : 1.0f;
-    }
-    __syncthreads();
-    for (int c = threadIdx.x; c < FS; c += 256) {               // a thread owns (field f, slot l) for the IPM_BEX examples
-        const int f = c >> 4, l = c & 15;
-        float g[IPM_BEX];
-#pragma unroll
-        for (int r = 0; r < IPM_BEX; ++r) g[r] = l < K ? dz[(size_t)(t0 + r) * D0p + c] : 0.f;
-        if (l < K && P) {
-            // pair (i, j), i < j, sits at i (2F - i - 1) / 2 + (j - i - 1): partners below f walk down the column of f, partners
-            // above it along its row
-            for (int j = 0; j < f; ++j) {
-                const int m = j * (2 * F - j - 1) / 2 + (f - j - 1);
-#pragma unroll
-                for (int r = 0; r < IPM_BEX; ++r) g[r] = fmaf(sp[r * P + m], se[r * FS + j * SLOT + l], g[r]);
-            }
-            const int m0 = f * (2 * F - f - 1) / 2 - f - 1;
-            for (int j = f + 1; j < F; ++j) {
-#pragma unroll
-                for (int r = 0; r < IPM_BEX; ++r) g[r] = fmaf(sp[r * P + m0 + j], se[r * FS + j * SLOT + l], g[r]);
-            }
-        }
-        if (WV) {
-#pragma unroll
-            for (int r = 0; r < IPM_BEX; ++r) g[r] *= sw[r * F + f];
-        }
-#pragma unroll
-        for (int r = 0; r < IPM_BEX; ++r) gxp[(size_t)(t0 + r) * D0p + c] = g[r];
-    }
-    if (threadIdx.x == 0) { float s = 0.f; for (int r = 0; r < IPM_BEX; ++r) s += dz[(size_t)(t0 + r) * D0p + CB]; gb_part[blockIdx.x] = s; }
-}
-
-// ------------------------------------------------------------------------------------------
-// GEMM epilogues of the deep stack.
-// ------------------------------------------------------------------------------------------
-// All activation / delta matrices of the stack are FRAGMENT-TILED (ft_off) in both orientations:
-// xF (rows = examples, k = units) feeds the next forward / backward-data product, xT (rows = units,
-// k = examples) the weight-gradient product.  Only dz1 (f32, for the inner-product backward) is row-major.
-// The epilogues compute the 4 values a lane owns (rows r0 .. r0+3 of one column); k_gemm_ft writes both
-// layouts.  Keep-masks are read TRANSPOSED ([unit][example], k_mask_T below): a lane's 4 rows are 4
-// consecutive bytes, one dword load; activations for act' come from xT the same way (one 8-byte load).
-// Transposed keep-masks are tiled like a fragment-tiled operand of bytes: 16 units x 32 examples = one 512-byte
-// block, so that a 32-example strip reads whole blocks (and a 128-row GEMM tile four of them per 16 units).
-__host__ __device__ inline size_t mask_off(int col, int row, int ldT) {
-    return ((size_t)(col >> 4) * (ldT >> 5) + (row >> 5)) * 512 + (col & 15) * 32 + (row & 31);
-}
-// Every epilogue is split in two: load() fetches what the lane's 4 values need from memory (it can be issued
-// before the product's k-loop), apply() turns the accumulator into the values; pre() is both.
-template <typename T> struct EpiIpFwd {      // a_t = mask/keep * act(l_t); ones column at d
-    static constexpr bool TILE = true;
-    T* outF; int ld; T* outT; int ldT; const uint8_t* maskT; float inv_keep; int act, d, B;
-    struct Aux { unsigned mb; };
-    __device__ Aux load(int r0, int col) const {
-        Aux x{0x01010101u};
-        if (maskT && col < d) x.mb = *reinterpret_cast<const unsigned*>(maskT + mask_off(col, r0, ldT));
-        return x;
-    }
-    __device__ void pre(int r0, int col, const f32x4& acc, float v[4]) const { apply(load(r0, col), r0, col, acc, v); }
-    // the activation is a wave-uniform run-time value: branch on it once per fragment (or once per block, applyA)
-    __device__ void apply(const Aux& ax, int r0, int col, const f32x4& acc, float v[4]) const {
-        if (act == A_RELU) applyA<A_RELU>(ax, r0, col, acc, v);
-        else if (act == A_TANH) applyA<A_TANH>(ax, r0, col, acc, v);
-        else applyA<A_SIG>(ax, r0, col, acc, v);
-    }
-    // PLAIN: every row of the block is an example (< B) and every column a real unit (< d): no edge selects
-    template <int ACT, bool PLAIN = false> __device__ void applyA(const Aux& ax, int r0, int col, const f32x4& acc, float v[4]) const {
-        const unsigned mb = ax.mb;
-        const float sc = maskT ? inv_keep : 1.0f;
-#pragma unroll
-        for (int r = 0; r < 4; ++r) {
-            float x = ip_act_c<ACT>(acc[r]) * ((float)((mb >> (8 * r)) & 0xffu) * sc);
-            if (!PLAIN) {
-                x = col < d ? x : (col == d ? 1.0f : 0.f);
-                x = (r0 + r < B) ? x : 0.f;
-            }
-            v[r] = x;
-        }
-    }
-    __device__ bool plain(int row_end, int col_end) const { return row_end <= B && col_end <= d; }
-};
-template <typename T> struct EpiIpOut {      // logits (column 0), loss, delta = sigmoid(logit) - y
-    static constexpr bool TILE = true;
-    T* outF; int ld; T* outT; int ldT; const float* y; float* logits; float* loss_t; float* p_out; int B;
-    float gscale;            // 1 for a summed loss, 1 / B for tf.reduce_mean (python/FNN_IP_L7.py:83-86): scales every gradient of the step
-    struct Aux { };
-    __device__ Aux load(int, int) const { return Aux{}; }
-    __device__ void pre(int r0, int col, const f32x4& acc, float v[4]) const { apply(Aux{}, r0, col, acc, v); }
-    __device__ void apply(const Aux&, int r0, int col, const f32x4& acc, float v[4]) const {
-#pragma unroll
-        for (int r = 0; r < 4; ++r) {
-            const int t = r0 + r;
-            float x = 0.f;
-            if (col == 0 && t < B) {
-                const float z = acc[r], p = 1.0f / (1.0f + expf(-z));
-                if (logits) logits[t] = z;
-                if (p_out) p_out[t] = p;
-                // (the fused product spelled out: left to the compiler, the solo strip kernels fuse it and the group forms, the same
-                // code in another kernel, did not -- one rounding apart for labels other than 0 and 1)
-                if (y) { x = (p - y[t]) * gscale; loss_t[t] = fmaf(-z, y[t], fmaxf(z, 0.f)) + log1pf(expf(-fabsf(z))); }
-            } else if (col == 0 && loss_t) loss_t[t] = 0.f;
-            v[r] = x;
-        }
-    }
-};
-template <typename T> struct EpiIpBwd {      // delta l_t = (delta l_{t+1} W^T) * mask/keep * act'(l_t)
-    static constexpr bool TILE = true;
-    T* outF; int ld; T* outT; int ldT; float* out32; int ld32; const T* aT; const uint8_t* maskT; float inv_keep, keep; int act, d, B;
-    const int* ref;          // layer 0 (out32 != null): slot column -> reference column, -1 = padding
-    struct Aux { unsigned mb; float4 u; bool real; };
-    __device__ Aux load(int r0, int col) const {
-        Aux x{0x01010101u, make_float4(0.f, 0.f, 0.f, 0.f), ref ? ref[col] >= 0 : col < d};
-        if (x.real) {
-            if (maskT) x.mb = *reinterpret_cast<const unsigned*>(maskT + mask_off(col, r0, ldT));
-            x.u = load4(aT + ft_off<T>(col, r0, ldT));
-        }
-        return x;
-    }
-    __device__ void pre(int r0, int col, const f32x4& acc, float v[4]) const { apply(load(r0, col), r0, col, acc, v); }
-    __device__ void apply(const Aux& ax, int r0, int col, const f32x4& acc, float v[4]) const {
-        if (act == A_RELU) applyA<A_RELU>(ax, r0, col, acc, v);
-        else if (act == A_TANH) applyA<A_TANH>(ax, r0, col, acc, v);
-        else applyA<A_SIG>(ax, r0, col, acc, v);
-    }
-    template <int ACT, bool PLAIN = false> __device__ void applyA(const Aux& ax, int r0, int col, const f32x4& acc, float v[4]) const {
-        const unsigned mb = ax.mb;
-        const float uu[4] = {ax.u.x, ax.u.y, ax.u.z, ax.u.w};
-        const float sc = maskT ? inv_keep : 1.0f, ks = maskT ? keep : 1.0f;
-#pragma unroll
-        for (int r = 0; r < 4; ++r) {
-            const float m = (float)((mb >> (8 * r)) & 0xffu);
-            float x = acc[r] * m * sc * ip_dact_u_c<ACT>(uu[r] * ks);                      // act(l_t) where m = 1
-            if (!PLAIN) x = (r0 + r < B && ax.real) ? x : 0.f;
-            v[r] = x;
-            if (out32) out32[(size_t)(r0 + r) * ld32 + col] = x;
-        }
-    }
-    __device__ bool plain(int row_end, int col_end) const { return !ref && !out32 && row_end <= B && col_end <= d; }
-};
-
-// ------------------------------------------------------------------------------------------
-// Strip kernels: the whole deep stack for a strip of 16 RT examples inside ONE workgroup, forward
-// (k_ip_strip_fwd: L + 1 products, activations, loss / output delta) and backward-data
-// (k_ip_strip_bwd: L + 1 products down to dz1).  As separate GEMM launches these products are bound by
-// fixed costs -- per launch ~4 us of launch, ~1.5 us of pipeline fill, ~5 us of epilogue writing both
-// operand layouts and ~5 us of cold operands, against 3-8 us of L2-bound main loop -- 16 times per step.
-// Here a strip's activations stay in LDS (two ping-pong tiles in fragment order, so an A fragment is
-// one conflict-free ds_read_b128 per lane), each wave owns 64-column blocks of a layer's output and
-// streams the weights (fragment-tiled, L2-resident) straight into B fragments, and only what the
-// weight-gradient products need goes to HBM: the transposed activations / deltas.  Every workgroup
-// reads every weight once per pass: 16 RT FLOP per L2 byte, which is what bounds these kernels.
-// ------------------------------------------------------------------------------------------
-constexpr int STRIP_MAXP = IPNN_MAX_HIDDEN + 1;                  // products of the stack
-// TWO workgroups per strip (h = blockIdx.x & 1; strip = blockIdx.x >> 1): a 32-example strip occupies one CU and at batch 4096
-// that is 128 of the chip's 256, each streaming every weight at the ~75 GB/s one CU draws from L2 -- the bound of these kernels.
-// The pair splits every WIDE product by output column blocks (block j belongs to workgroup j & 1), so each CU streams half the
-// weights, and swaps halves after it: a workgroup pushes its blocks of the new activation tile to `xch` with write-through
-// (sc1) 16-byte stores, drains them, raises its flag, polls its partner's and pulls the partner's blocks into its own LDS tile
-// with sc1 loads (MI355X_MICROARCH.md, "Valid forms": every store and load of the handed-off bytes sc1, stores drained before
-// the flag, one lane polls, the others load behind a workgroup barrier).  Narrow products (fewer than DUO_MIN_BLOCKS column
-// blocks) are computed by BOTH workgroups -- their weights are a few hundred KB, a swap costs more -- and workgroup 0 alone
-// writes their outputs.  Workgroups b and b + 8 share an XCD, so the even XCDs only ever stream the even blocks' weights and
-// the odd XCDs the odd ones: half the weight footprint per L2.  Flags hold launch_epoch * 16 + (swap index + 1): they only
-// grow, so nothing is reset between launches; a poll gives up after DUO_SPIN_LIMIT tries and raises `err` (no hang on a bug).
-struct StripDuo { int on; unsigned long long* xch; int* flags; int epoch; int* err; size_t xch_wg; int min_blocks; };
-constexpr int DUO_MIN_BLOCKS = 5;                                // default of StripDuo::min_blocks (IPNN_DUO_MIN)
-constexpr int DUO_SPIN_LIMIT = 1 << 22;
-template <typename T> struct StripFwdArgs {
-    const T* a0; int n;                                          // a0: F layout [Ba][Dp0]; n = L + 1
-    const T* W[STRIP_MAXP]; int Dp[STRIP_MAXP + 1];              // W[t-1] = wf[t-1]: fragment-tiled [Dp_t][Dp_{t-1}]
-    EpiIpFwd<T> ef[STRIP_MAXP]; EpiIpOut<T> eo;                  // ef[t-1], t = 1..L; eo: the output unit
-    long long* dbg;                                              // IPNN_STAMPS=1 (diagnostics): s_memtime per layer, 16 per workgroup
-    int rot;                                                     // rotate the block order per workgroup (IPNN_STRIP_ROT=0: off)
-    StripDuo duo;                                                // two workgroups per strip (see StripDuo); duo.on = 0: one
-    int sel;                                                     // IPNN_STAMPS: the product whose first block of wave 0 is stamped in detail (slots 10..14)
-    // A launch may cover a RANGE of the stack (round 3: the wide products as pairs of 32-example strips, the narrow tail as 16-example
-    // strips on every CU).  has_out = 0: the last product of this launch is a hidden layer whose tile leaves for HBM in the F layout
-    // (finalF: the next launch's a0), block by block as it is computed -- no swap, no barrier behind it.
-    int has_out; T* finalF;
-    // 16-example strips (RT = 1) only: products whose weights are copied into LDS behind the two tiles at the start of the launch
-    // (element offset there, or -1: streamed from L2 as usual).  The narrow products are chains of a few k-steps, each an L2 round
-    // trip long (~600 ticks with four in flight); from LDS a k-step costs what its MFMAs cost
-    int wlds[STRIP_MAXP];
-    int warm;                                                    // touch every line of these arguments at the start (see strip_warm_args)
-};
-template <typename T> struct StripBwdArgs {
-    const T* dlast; int n;                                       // delta of the output layer, F layout [Ba][64]
-    const T* W[STRIP_MAXP]; int Dp[STRIP_MAXP + 1];              // W[t-1] = wb[t-1]: fragment-tiled [Dp_{t-1}][Dp_t]
-    EpiIpBwd<T> eb[STRIP_MAXP];                                  // eb[t-1]: product t -> delta l_{t-1}
-    long long* dbg;
-    int rot;
-    StripDuo duo;
-    // bottom = 1: product 1 of this launch is the stack's first (its output is dz1, f32, no tile).  bottom = 0: the launch stops inside
-    // the stack and product 1's tile leaves for HBM in the F layout (finalF: the next launch's dlast)
-    int bottom; T* finalF;
-    int wlds[STRIP_MAXP];                                        // as in StripFwdArgs (index = product index t - 1 of this launch)
-    int warm;
-};
-// The kernels read their per-product arguments (ef[l] / eb[t - 1]: a different 64-byte line of the argument segment per product) with
-// scalar loads at the top of each product, behind the barrier: a scalar-cache miss on every wave's critical path, once per product.
-// One dword of every line at the start of the launch instead -- all misses in flight together, under the strip's own load.
-template <int BYTES> __device__ __forceinline__ void strip_warm_args()
-{
-    typedef const int __attribute__((address_space(4))) karg_int;
-    karg_int* p = (karg_int*)__builtin_amdgcn_kernarg_segment_ptr();
-    int s = 0;
-#pragma unroll
-    for (int o = 0; o < BYTES; o += 64) s |= p[o / 4];
-    asm volatile("" :: "s"(s));
-}
-
-// one 64-column block of one product: acc[m][n] = sum_k in[16 m ..][k] W[64 blk + 16 n ..][k].
-// Weights: five register stages (four k-steps in flight while one multiplies: with two waves per SIMD that
-// covers an L2 round trip at the rate the texture path delivers fragments); loads past the end are clamped
-// to the last k-step, so the loop has no branch.  The strip's own fragments come from LDS.
-// An ITEM of a product is NF of its 16-column fragments: NF = 4 (a 64-column block) everywhere but in the 16-example strips of
-// the narrow tail, whose kernels may take finer items (k_ip_strip_*<T, 1, NF>): a 64- or 128-wide product then occupies 4 / 8
-// waves instead of 1 / 2, and an item's epilogue is NF / 4 of a block's.  `blk` below is the item index: fragments blk NF + n.
-template <typename T, int NF = 4> struct StripB { typename Traits<T>::frag s[4][NF]; };     // k-steps 0..3 of an item's weights, in flight
-
-template <typename T, int NF = 4>
-__device__ __forceinline__ void strip_prefetch(StripB<T, NF>& pb, const T* __restrict__ W, const int nkt, const int blk, const int lane)
-{
-    typedef typename Traits<T>::frag frag;
-#pragma unroll
-    for (int j = 0; j < 4; ++j)
-#pragma unroll
-        for (int n = 0; n < NF; ++n) pb.s[j][n] = *reinterpret_cast<const frag*>(ft_frag<T>(W, blk * NF + n, min(j, nkt - 1), nkt, lane));
-}
-
-template <typename T, int RT, int NF = 4>
-__device__ __forceinline__ void strip_product(f32x4 (&acc)[RT][NF], StripB<T, NF>& pb, const T* in, const T* __restrict__ W, const int nkt,
-                                              const int blk, const int lane)
-{
-    typedef typename Traits<T>::frag frag;
-#pragma unroll
-    for (int m = 0; m < RT; ++m)
-#pragma unroll
-        for (int n = 0; n < NF; ++n) acc[m][n] = f32x4{0.f, 0.f, 0.f, 0.f};
-    frag b4[NF];
-    frag (&b0)[NF] = pb.s[0]; frag (&b1)[NF] = pb.s[1]; frag (&b2)[NF] = pb.s[2]; frag (&b3)[NF] = pb.s[3];
-    const int last = nkt - 1;
-    auto loadb = [&](frag* b, const int kt) {
-        const int k = min(kt, last);
-#pragma unroll
-        for (int n = 0; n < NF; ++n) b[n] = *reinterpret_cast<const frag*>(ft_frag<T>(W, blk * NF + n, k, nkt, lane));
-    };
-    auto mul = [&](const int kt, const frag* b) {
-        frag a[RT];
-#pragma unroll
-        for (int m = 0; m < RT; ++m) a[m] = *reinterpret_cast<const frag*>(ft_frag<T>(in, m, kt, nkt, lane));
-#pragma unroll
-        for (int m = 0; m < RT; ++m)
-#pragma unroll
-            for (int n = 0; n < NF; ++n) mma(acc[m][n], a[m], b[n]);
-    };
-    int kt = 0;
-    for (; kt + 5 <= nkt; kt += 5) {
-        loadb(b4, kt + 4); mul(kt, b0);
-        if (kt + 5 < nkt) loadb(b0, kt + 5);
-        mul(kt + 1, b1);
-        if (kt + 6 < nkt) loadb(b1, kt + 6);
-        mul(kt + 2, b2);
-        if (kt + 7 < nkt) loadb(b2, kt + 7);
-        mul(kt + 3, b3);
-        if (kt + 8 < nkt) loadb(b3, kt + 8);
-        mul(kt + 4, b4);
-    }
-    if (kt < nkt) mul(kt, b0);
-    if (kt + 1 < nkt) mul(kt + 1, b1);
-    if (kt + 2 < nkt) mul(kt + 2, b2);
-    if (kt + 3 < nkt) mul(kt + 3, b3);
-}
-
-// what the epilogue of a block reads from memory (keep-mask bytes, activations for act'), fetched before the k-loop
-template <typename T, int RT, int NF, typename Epi>
-__device__ __forceinline__ void strip_aux(typename Epi::Aux (&ax)[RT][NF], const Epi& epi, const int row0, const int blk, const int lane)
-{
-    const int rq = 4 * (lane >> 4), cl = lane & 15;
-#pragma unroll
-    for (int m = 0; m < RT; ++m)
-#pragma unroll
-        for (int n = 0; n < NF; ++n) ax[m][n] = epi.load(row0 + m * 16 + rq, (blk * NF + n) * 16 + cl);
-}
-
-// epilogue of a block: the lane's values through `epi.apply`, the transposed layout to HBM (8-byte pieces),
-// the strip's own layout to the LDS tile `out` (the next product's A operand) when there is a next product
-template <int ACT, bool PLAIN, typename T, int RT, int NF, typename Epi>
-__device__ __forceinline__ void strip_epilogue_a(f32x4 (&acc)[RT][NF], const typename Epi::Aux (&ax)[RT][NF], const Epi& epi, T* out, const int N,
-                                                 const int row0, const int blk, const int lane)
-{
-    const int rq = 4 * (lane >> 4), cl = lane & 15, col0 = blk * NF * 16;
-    T* const outT = epi.outT ? epi.outT + ft_off<T>(col0 + cl, row0 + rq, epi.ldT) : nullptr;   // + n * 16 units, + m * 16 examples
-    // (the item's first column is a multiple of 16 NF: with NF < 4 offsets of n * 16 columns still add without a carry into the k-step)
-    T* const outL = out ? out + ft_off<T>(rq, col0 + cl, N) : nullptr;
-    const size_t tn = ft_off<T>(16, 0, epi.ldT), tm = ft_off<T>(0, 16, epi.ldT);    // strides: 16 units, 16 examples (ldT % KS == 0)
-#pragma unroll
-    for (int m = 0; m < RT; ++m)
-#pragma unroll
-        for (int n = 0; n < NF; ++n) {
-            float v[4];
-            const int col = col0 + n * 16 + cl;
-            epi.template applyA<ACT, PLAIN>(ax[m][n], row0 + m * 16 + rq, col, acc[m][n], v);
-            if (outT) store4(outT + n * tn + m * tm, v[0], v[1], v[2], v[3]);
-            if (outL) {
-                T* o = outL + ft_off<T>(m * 16, n * 16, N);       // (row tile m, column offset 16 n): additive in this layout
-#pragma unroll
-                for (int r = 0; r < 4; ++r) o[r * Traits<T>::EPL] = (T)v[r];
-            }
-        }
-}
-template <typename T, int RT, int NF, typename Epi>
-__device__ __forceinline__ void strip_epilogue(f32x4 (&acc)[RT][NF], const typename Epi::Aux (&ax)[RT][NF], const Epi& epi, T* out, const int N,
-                                               const int row0, const int blk, const int lane)
-{   // one branch on the activation and on "interior block" per block
-    const bool pl = epi.plain(row0 + RT * 16, (blk + 1) * NF * 16);
-#define STRIP_EPI(ACT) do { if (pl) strip_epilogue_a<ACT, true, T, RT, NF, Epi>(acc, ax, epi, out, N, row0, blk, lane); \
-                            else strip_epilogue_a<ACT, false, T, RT, NF, Epi>(acc, ax, epi, out, N, row0, blk, lane); } while (0)
-    if (epi.act == A_RELU) STRIP_EPI(A_RELU);
-    else if (epi.act == A_TANH) STRIP_EPI(A_TANH);
-    else STRIP_EPI(A_SIG);
-#undef STRIP_EPI
-}
-
-template <typename T> __device__ __forceinline__ void strip_load(T* dst, const T* __restrict__ src, const int nfrag16)
-{   // nfrag16 16-byte pieces, contiguous in both
-    typedef typename Traits<T>::frag frag;
-    const int nt = blockDim.x;
-    for (int i0 = threadIdx.x; i0 < nfrag16; i0 += nt * 4) {     // four loads in flight per thread before the first LDS store
-        frag v[4];
-#pragma unroll
-        for (int k = 0; k < 4; ++k) { const int i = i0 + nt * k; if (i < nfrag16) v[k] = reinterpret_cast<const frag*>(src)[i]; }
-#pragma unroll
-        for (int k = 0; k < 4; ++k) { const int i = i0 + nt * k; if (i < nfrag16) reinterpret_cast<frag*>(dst)[i] = v[k]; }
-    }
-}
-
-#define STRIP_STAMP(i) do { if (a.dbg && threadIdx.x == 0) a.dbg[(size_t)blockIdx.x * 16 + (i)] = (long long)__builtin_amdgcn_s_memtime(); } while (0)
-constexpr int STRIP_NW = 8;                                      // waves per strip workgroup (2 per SIMD: 256 registers each)
-// A wave's blocks of the stack in order: (product p, list index w), (p, w + NW), ... then the next product it has a
-// block in.  The weights of the NEXT block are requested before the current block's epilogue (they do not
-// depend on the strip), so the barrier between two products and the epilogue hide their L2 round trip.
-// A workgroup's LIST of a product's column blocks: all nblk of them, or -- a wide product of a pair (StripDuo) -- the
-// (nblk - h + 1) / 2 blocks j with j & 1 == h.
-struct StripItem { int p, blk; };
-__device__ __forceinline__ bool duo_split(const StripDuo& d, const int nblk) { return d.on && nblk >= d.min_blocks; }
-__device__ __forceinline__ int duo_count(const bool split, const int nblk, const int h) { return split ? (nblk - h + 1) >> 1 : nblk; }
-// Workgroups walk their list in rotated order (list entry i of a workgroup with rotation g is entry (i + g) mod cnt), so
-// that the workgroups of an XCD do not all stream the same weights -- the same L2 channels -- at the same moment.
-// (per items per 64-column block: entry r of the list is sub-item r % per of the workgroup's own block r / per)
-__device__ __forceinline__ int strip_phys(const bool split, const int i, const int cnt, const int h, const int rot, const int per = 1) {
-    const int r = (i + rot) % cnt, ob = r / per;
-    return (split ? 2 * ob + h : ob) * per + r % per;
-}
-template <typename T> __device__ __forceinline__ bool strip_has_out(const StripFwdArgs<T>& a) { return a.has_out != 0; }
-template <typename T> __device__ __forceinline__ bool strip_has_out(const StripBwdArgs<T>&) { return false; }
-// items of a product in a workgroup's list: `per` items per 64-column block (4 / NF; pairs split whole blocks: per = 1 there);
-// the output unit is ONE item whatever its padded width (column 0 is the only unit)
-template <typename A> __device__ __forceinline__ int strip_items(const A& a, const int p, const bool fwd, const int h, const int per)
-{
-    const int nblk = fwd ? a.Dp[p + 1] / 64 : a.Dp[a.n - p - 1] / 64;
-    if (fwd && strip_has_out(a) && p == a.n - 1) return 1;
-    return duo_count(duo_split(a.duo, nblk), nblk, h) * per;
-}
-template <typename A> __device__ __forceinline__ StripItem strip_next(const A& a, StripItem it, const int wave, const bool fwd, const int h, const int per,
-                                                                     const int nw = STRIP_NW)
-{   // fwd: product p has Dp[p + 1] / 64 blocks (the output unit, p = n - 1: one); bwd: product index q = n - t, Dp[t - 1] / 64 blocks
-    it.blk += nw;
-    for (;;) {
-        if (it.p >= a.n) return it;
-        if (it.blk < strip_items(a, it.p, fwd, h, per)) return it;
-        it.p += 1; it.blk = wave;
-    }
-}
-
-// ---- the swap of a pair (StripDuo).  xch of workgroup (strip, h): [2 parities][own block r = j >> 1][RT][256] 8-byte words,
-// a block's RT x 2 KB in the order they have in the LDS tile (row tile m: k-steps 2 j and 2 j + 1 are adjacent there).
-typedef unsigned int duo_u32x4 __attribute__((ext_vector_type(4)));
-// 16-byte write-through stores / L1-bypassing loads of the swap buffer (raw buffer instructions with the sc1 cache policy: the
-// compiler keeps their wait counts, unlike inline assembly; 8-byte accesses run at 0.54-0.70 of the 16-byte rate)
-__device__ __forceinline__ __amdgpu_buffer_rsrc_t duo_rsrc(const StripDuo& d) {
-    return __builtin_amdgcn_make_buffer_rsrc((void*)d.xch, 0, (int)(d.xch_wg * 8 * (size_t)gridDim.x), 0x00020000);
-}
-template <typename T, int RT, int NF = 4>
-__device__ __forceinline__ void duo_push(const StripDuo& d, const T* out, const int N, const int item, const int parity, const int lane)
-{   // by the wave that has just written item `item` (NF fragments of block j = item NF / 4) of the tile `out` (LDS operations of one
-    // wave complete in order); a block's RT x 2 KB keep the order they have in the LDS tile, so an item's 16-byte pieces are a run of it
-    constexpr int PER = 4 / NF, PIECES = 16 * NF * (int)sizeof(T);       // 16-byte pieces per row tile: 128 (a block), 64, 32
-    const int j = item / PER, sub = item % PER;
-    const __amdgpu_buffer_rsrc_t rs = duo_rsrc(d);
-    const size_t dst = ((size_t)blockIdx.x * d.xch_wg + (size_t)parity * (d.xch_wg >> 1) + (size_t)(j >> 1) * (RT * 256)) * 8 + (size_t)sub * PIECES * 16;     // bytes
-#pragma unroll
-    for (int m = 0; m < RT; ++m) {
-        const duo_u32x4* src = reinterpret_cast<const duo_u32x4*>(out + ft_off<T>(m * 16, item * NF * 16, N));
-        if (PIECES >= 128) {
-            const duo_u32x4 v0 = src[lane], v1 = src[lane + 64];
-            __builtin_amdgcn_raw_buffer_store_b128(v0, rs, (int)(dst + m * 2048 + lane * 16), 0, 16);                // aux 16 = sc1: write-through
-            __builtin_amdgcn_raw_buffer_store_b128(v1, rs, (int)(dst + m * 2048 + (lane + 64) * 16), 0, 16);
-        } else if (lane < PIECES) {
-            const duo_u32x4 v0 = src[lane];
-            __builtin_amdgcn_raw_buffer_store_b128(v0, rs, (int)(dst + m * 2048 + lane * 16), 0, 16);
-        }
-    }
-}
-// block j of the tile `out`, just written by this wave, to its place in an F-layout operand in HBM (plain 16-byte stores; the
-// strip's row tiles are contiguous there, so the tile's own offsets apply): the hand-over between two launches of a split stack
-template <typename T, int RT, int NF = 4>
-__device__ __forceinline__ void strip_final_push(T* __restrict__ dstF, const T* out, const int N, const int sidx, const int j, const int lane)
-{   // item j = columns 16 NF j ..: per row tile 16 x 16 NF elements, contiguous in the fragment-tiled layout (NF = 1, bf16: half a fragment)
-    constexpr int PIECES = 16 * NF * (int)sizeof(T);             // 16-byte pieces per row tile
-    T* base = dstF + (size_t)sidx * RT * 16 * N;
-#pragma unroll
-    for (int m = 0; m < RT; ++m) {
-        const size_t o = ft_off<T>(m * 16, j * NF * 16, N);
-        const duo_u32x4* src = reinterpret_cast<const duo_u32x4*>(out + o);
-        duo_u32x4* dst = reinterpret_cast<duo_u32x4*>(base + o);
-        if (PIECES >= 128) {
-            duo_u32x4 v[PIECES / 64 > 0 ? PIECES / 64 : 1];
-#pragma unroll
-            for (int i = 0; i < PIECES / 64; ++i) v[i] = src[lane + 64 * i];
-#pragma unroll
-            for (int i = 0; i < PIECES / 64; ++i) dst[lane + 64 * i] = v[i];
-        } else if (lane < PIECES) dst[lane] = src[lane];
-    }
-}
-// every wave has drained its pushes -> flag -> the partner's flag -> the partner's blocks into `out`.  `pull` = false: this
-// workgroup has nothing left to compute (it only publishes).  All 64 NW threads call it.
-template <typename T, int RT, int NW = STRIP_NW>
-__device__ __forceinline__ void duo_swap(const StripDuo& d, T* out, const int N, const int nblk, const int h, const int parity, const int seq,
-                                         const bool pull, long long* dbg)
-{
-    long long ta = 0, tb = 0;
-    if (dbg && threadIdx.x == 0) ta = (long long)__builtin_amdgcn_s_memtime();
-    asm volatile("s_waitcnt vmcnt(0)" ::: "memory");             // this wave's sc1 stores have left (and whatever else it had in flight)
-    lds_barrier();
-    const int want = d.epoch * 16 + seq;
-    if (dbg && threadIdx.x == 0) { tb = (long long)__builtin_amdgcn_s_memtime(); dbg[11] += tb - ta; }    // drain + barrier
-    if (threadIdx.x == 0) {
-        __hip_atomic_store(d.flags + blockIdx.x, want, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-        if (pull) {
-            int n = 0;
-            while (__hip_atomic_load(d.flags + (blockIdx.x ^ 1), __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) < want) {
-                __builtin_amdgcn_s_sleep(2);
-                if (++n > DUO_SPIN_LIMIT) { atomicOr(d.err, 2); break; }      // a partner that never arrives: report, do not hang
-            }
-        }
-    }
-    if (!pull) return;
-    lds_barrier();
-    if (dbg && threadIdx.x == 0) { ta = (long long)__builtin_amdgcn_s_memtime(); dbg[12] += ta - tb; }    // flag + the partner's
-    // a block = RT x 2 KB = RT x 128 pieces of 16 bytes: threads 0..255 take the partner's blocks 0, 2, ..., threads 256..511 the odd ones
-    const int ph = h ^ 1, cntp = (nblk - ph + 1) >> 1, t = threadIdx.x, pc = t & 255, m = pc >> 7, idx = pc & 127;
-    constexpr int G = NW / 4;                                        // groups of 256 threads: group g takes the partner's blocks g, g + G, ...
-    const __amdgpu_buffer_rsrc_t rs = duo_rsrc(d);
-    const size_t src = ((size_t)(blockIdx.x ^ 1) * d.xch_wg + (size_t)parity * (d.xch_wg >> 1)) * 8 + (size_t)pc * 16;                 // bytes
-    for (int r0 = 0; r0 < cntp && m < RT; r0 += 4 * G) {             // four loads in flight per thread
-        duo_u32x4 v[4];
-#pragma unroll
-        for (int k = 0; k < 4; ++k) {
-            const int r = r0 + (t >> 8) + G * k;
-            if (r < cntp) v[k] = __builtin_amdgcn_raw_buffer_load_b128(rs, (int)(src + (size_t)r * (RT * 2048)), 0, 16);           // sc1: from L2
-        }
-#pragma unroll
-        for (int k = 0; k < 4; ++k) {
-            const int r = r0 + (t >> 8) + G * k;
-            if (r < cntp) reinterpret_cast<duo_u32x4*>(out + ft_off<T>(m * 16, (2 * r + ph) * 64, N))[idx] = v[k];
-        }
-    }
-    if (dbg && threadIdx.x == 0) dbg[13] += (long long)__builtin_amdgcn_s_memtime() - ta;                  // pull (thread 0's share)
-}
-
-extern __shared__ __align__(16) unsigned char strip_smem[];   // the strip kernels' dynamic LDS: two tiles [RT * 16][maxD] (+ LDS weight copies)
-template <typename T, int RT, int NF, int NW>
-__device__ __forceinline__ void strip_fwd_body(const StripFwdArgs<T>& a, const int maxD)
-{
-    constexpr int EPL = Traits<T>::EPL, KS = Traits<T>::KS, PER = 4 / NF;       // NF < 4: no pairs (the host launches those without StripDuo)
-    T* in = reinterpret_cast<T*>(strip_smem);
-    T* out = in + (size_t)RT * 16 * maxD;
-    T* wl = out + (size_t)RT * 16 * maxD;                        // RT = 1: LDS copies of the small products' weights (a.wlds)
-    const int wave = threadIdx.x >> 6, lane = threadIdx.x & 63;
-    const int h = a.duo.on ? (int)(blockIdx.x & 1) : 0, sidx = a.duo.on ? (int)(blockIdx.x >> 1) : (int)blockIdx.x;
-    const int row0 = sidx * RT * 16;
-    STRIP_STAMP(0);
-    if (a.warm) strip_warm_args<(int)sizeof(StripFwdArgs<T>)>();
-    if (a.dbg && threadIdx.x == 0) { for (int i = 10; i < 16; ++i) a.dbg[(size_t)blockIdx.x * 16 + i] = 0; }
-    StripB<T, NF> pb;
-    StripItem nx = strip_next(a, StripItem{0, wave - NW}, wave, true, h, PER, NW);
-    const int rot = (a.rot == 1) ? (sidx >> 3) : (a.rot == 2 ? sidx : 0);   // workgroups g, g + 8, ... share an XCD
-    // the last product this workgroup computes: the second of a pair stops behind the last product the pair splits
-    int last = a.n - 1;
-    if (h == 1) { last = -1; for (int p = 0; p < a.n; ++p) if (duo_split(a.duo, a.Dp[p + 1] / 64)) last = p; }
-    auto blocks = [&](const int p, bool& split, int& cnt) { split = duo_split(a.duo, a.Dp[p + 1] / 64); cnt = strip_items(a, p, true, h, PER); };
-    auto prefetch_next = [&]() {
-        if (nx.p < a.n && nx.p <= last) {
-            bool sp; int cn; blocks(nx.p, sp, cn);
-            const int wo = RT == 1 ? a.wlds[nx.p] : -1;
-            // (spelled from the LDS array itself: through the captured pointer the address space was lost and the loads came out flat_)
-            if (wo >= 0) strip_prefetch<T, NF>(pb, reinterpret_cast<const T*>(strip_smem) + (size_t)2 * RT * 16 * maxD + wo, a.Dp[nx.p] / KS, strip_phys(sp, nx.blk, cn, h, rot, PER), lane);
-            else strip_prefetch<T, NF>(pb, a.W[nx.p], a.Dp[nx.p] / KS, strip_phys(sp, nx.blk, cn, h, rot, PER), lane);
-        }
-    };
-    if (RT == 1) {                                               // the small products' weights -> LDS (contiguous, fragment-tiled: offsets carry over)
-        const bool first_lds = nx.p < a.n && a.wlds[nx.p] >= 0;
-        if (!first_lds) prefetch_next();                         // a first item streamed from L2 (the big first product) does not wait for the copy
-        bool any = false;
-        for (int p = 0; p < a.n; ++p)
-            if (a.wlds[p] >= 0) { strip_load<T>(wl + a.wlds[p], a.W[p], a.Dp[p] * a.Dp[p + 1] / EPL); any = true; }
-        if (any) lds_barrier();                                  // (uniform: `any` comes from the arguments)
-        if (first_lds) prefetch_next();
-    } else prefetch_next();
-    // the strip of a0: row tiles RT sidx .. of an F-layout operand are contiguous
-    strip_load<T>(in, a.a0 + (size_t)sidx * RT * 16 * a.Dp[0], RT * 16 * a.Dp[0] / EPL);
-    lds_barrier();
-    STRIP_STAMP(1);
-    f32x4 acc[RT][NF];
-    int seq = 0;
-    for (int l = 0; l <= last; ++l) {
-        const int nkt = a.Dp[l] / KS, N = a.Dp[l + 1];
-        const bool hidden = !a.has_out || l + 1 < a.n;
-        const bool fin = !a.has_out && l + 1 == a.n;            // the launch stops here: blocks go to HBM, nobody swaps
-        bool split; int cnt; blocks(l, split, cnt);
-        while (nx.p == l) {
-            const int blk = strip_phys(split, nx.blk, cnt, h, rot, PER);
-            const bool det = a.dbg && l == a.sel && threadIdx.x == 0;
-#define DET(i) do { if (det) a.dbg[(size_t)blockIdx.x * 16 + (i)] = (long long)__builtin_amdgcn_s_memtime(); } while (0)
-            DET(10);
-            if (hidden) {
-                EpiIpFwd<T> ef = a.ef[l];                       // the layer's epilogue parameters: scalar registers, loaded once
-                if (a.duo.on && !split && h == 1) ef.outT = nullptr;     // (not reached: the second workgroup computes split products only)
-                typename EpiIpFwd<T>::Aux ax[RT][NF];
-                strip_aux<T, RT, NF>(ax, ef, row0, blk, lane);
-                if (RT == 1 && a.wlds[l] >= 0) strip_product<T, RT, NF>(acc, pb, in, wl + a.wlds[l], nkt, blk, lane);
-                else strip_product<T, RT, NF>(acc, pb, in, a.W[l], nkt, blk, lane);
-                DET(11);
-                nx = strip_next(a, nx, wave, true, h, PER, NW);
-                prefetch_next();
-                DET(12);
-                strip_epilogue<T, RT, NF>(acc, ax, ef, out, N, row0, blk, lane);
-                DET(13);
-                if (fin) { if (split || h == 0) strip_final_push<T, RT, NF>(a.finalF, out, N, sidx, blk, lane); }
-                else if (split) duo_push<T, RT, NF>(a.duo, out, N, blk, seq & 1, lane);
-            } else {                                              // the output unit: logits, loss, delta (column 0): item 0 = fragment 0 ..
-                if (RT == 1 && a.wlds[l] >= 0) strip_product<T, RT, NF>(acc, pb, in, wl + a.wlds[l], nkt, blk, lane);
-                else strip_product<T, RT, NF>(acc, pb, in, a.W[l], nkt, blk, lane);
-                nx.p = a.n;
-                const EpiIpOut<T> eo = a.eo;
-                const int rq = 4 * (lane >> 4), cl = lane & 15;
-                // only column 0 is a unit: columns 1..63 of the delta (both layouts) are zero and stay zero -- the
-                // buffers are zero-filled at creation and these kernels are their only writers -- so one fragment per row tile
-#pragma unroll
-                for (int m = 0; m < RT; ++m) {
-                    float v[4];
-                    const int r0 = row0 + m * 16 + rq;
-                    eo.pre(r0, cl, acc[m][0], v);
-                    if (eo.outT) store4(eo.outT + ft_off<T>(cl, r0, eo.ldT), v[0], v[1], v[2], v[3]);
-                    if (eo.outF) {
-#pragma unroll
-                        for (int r = 0; r < 4; ++r) eo.outF[ft_off<T>(r0 + r, cl, eo.ld)] = (T)v[r];
-                    }
-                }
-            }
-        }
-        if (split && !fin) { duo_swap<T, RT, NW>(a.duo, out, N, N / 64, h, seq & 1, seq + 1, l < last, a.dbg ? a.dbg + (size_t)blockIdx.x * 16 : nullptr); ++seq; }
-        if (hidden && !fin) lds_barrier();
-        STRIP_STAMP(2 + l);
-        T* t = in; in = out; out = t;
-    }
-}
-template <typename T, int RT, int NF = 4, int NW = STRIP_NW>
-static __global__ __launch_bounds__(64 * NW) void k_ip_strip_fwd(const StripFwdArgs<T> a, const int maxD) { strip_fwd_body<T, RT, NF, NW>(a, maxD); }
-
-template <typename T, int RT, int NF, int NW>
-__device__ __forceinline__ void strip_bwd_body(const StripBwdArgs<T>& a, const int maxD)
-{
-    constexpr int EPL = Traits<T>::EPL, KS = Traits<T>::KS, PER = 4 / NF;
-    T* in = reinterpret_cast<T*>(strip_smem);
-    T* out = in + (size_t)RT * 16 * maxD;
-    const int wave = threadIdx.x >> 6, lane = threadIdx.x & 63;
-    const int h = a.duo.on ? (int)(blockIdx.x & 1) : 0, sidx = a.duo.on ? (int)(blockIdx.x >> 1) : (int)blockIdx.x;
-    const int row0 = sidx * RT * 16;
-    STRIP_STAMP(0);
-    if (a.warm) strip_warm_args<(int)sizeof(StripBwdArgs<T>)>();
-    if (a.dbg && threadIdx.x == 0) { for (int i = 10; i < 16; ++i) a.dbg[(size_t)blockIdx.x * 16 + i] = 0; }
-    T* wl = out + (size_t)RT * 16 * maxD;                        // RT = 1: LDS copies of the small products' weights (a.wlds)
-    StripB<T, NF> pb;                                             // item index q = n - t: product t = n - q
-    StripItem nx = strip_next(a, StripItem{0, wave - NW}, wave, false, h, PER, NW);
-    const int rot = (a.rot == 1) ? (sidx >> 3) : (a.rot == 2 ? sidx : 0);   // workgroups g, g + 8, ... share an XCD
-    auto blocks = [&](const int q, bool& split, int& cnt) { split = duo_split(a.duo, a.Dp[a.n - q - 1] / 64); cnt = strip_items(a, q, false, h, PER); };
-    auto prefetch_next = [&]() {
-        if (nx.p < a.n) {
-            bool sp; int cn; blocks(nx.p, sp, cn);
-            const int wo = RT == 1 ? a.wlds[a.n - nx.p - 1] : -1;
-            if (wo >= 0) strip_prefetch<T, NF>(pb, reinterpret_cast<const T*>(strip_smem) + (size_t)2 * RT * 16 * maxD + wo, a.Dp[a.n - nx.p] / KS, strip_phys(sp, nx.blk, cn, h, rot, PER), lane);
-            else strip_prefetch<T, NF>(pb, a.W[a.n - nx.p - 1], a.Dp[a.n - nx.p] / KS, strip_phys(sp, nx.blk, cn, h, rot, PER), lane);
-        }
-    };
-    if (RT == 1) {                                               // the small products' weights -> LDS; in the backward launch they are the FIRST products
-        bool any = false;
-        for (int p = 0; p < a.n; ++p)
-            if (a.wlds[p] >= 0) { strip_load<T>(wl + a.wlds[p], a.W[p], a.Dp[p] * a.Dp[p + 1] / EPL); any = true; }
-        if (any) lds_barrier();                                  // the first item's prefetch reads them
-    }
-    prefetch_next();
-    strip_load<T>(in, a.dlast + (size_t)sidx * RT * 16 * a.Dp[a.n], RT * 16 * a.Dp[a.n] / EPL);
-    lds_barrier();
-    STRIP_STAMP(1);
-    f32x4 acc[RT][NF];
-    int seq = 0;
-    for (int t = a.n; t >= 1; --t) {                              // delta l_{t-1} = (delta l_t . W_t^T) * mask * act'
-        const int nkt = a.Dp[t] / KS, N = a.Dp[t - 1], q = a.n - t;
-        bool split; int cnt; blocks(q, split, cnt);
-        while (nx.p == q) {
-            const int blk = strip_phys(split, nx.blk, cnt, h, rot, PER);
-            EpiIpBwd<T> eb = a.eb[t - 1];
-            if (a.duo.on && !split && h == 1) { eb.outT = nullptr; eb.out32 = nullptr; }   // a narrow product of a pair: both compute it, the first one stores it
-            typename EpiIpBwd<T>::Aux ax[RT][NF];
-            strip_aux<T, RT, NF>(ax, eb, row0, blk, lane);
-            if (RT == 1 && a.wlds[t - 1] >= 0) strip_product<T, RT, NF>(acc, pb, in, wl + a.wlds[t - 1], nkt, blk, lane);
-            else strip_product<T, RT, NF>(acc, pb, in, a.W[t - 1], nkt, blk, lane);
-            nx = strip_next(a, nx, wave, false, h, PER, NW);
-            prefetch_next();
-            strip_epilogue<T, RT, NF>(acc, ax, eb, (t > 1 || !a.bottom) ? out : nullptr, N, row0, blk, lane);
-            if (split && t > 1) duo_push<T, RT, NF>(a.duo, out, N, blk, seq & 1, lane);
-            if (t == 1 && !a.bottom && (split || h == 0)) strip_final_push<T, RT, NF>(a.finalF, out, N, sidx, blk, lane);
-        }
-        if (split && t > 1) { duo_swap<T, RT, NW>(a.duo, out, N, N / 64, h, seq & 1, seq + 1, true, a.dbg ? a.dbg + (size_t)blockIdx.x * 16 : nullptr); ++seq; }
-        if (t > 1) lds_barrier();
-        STRIP_STAMP(2 + q);
-        T* x = in; in = out; out = x;
-    }
-}
-template <typename T, int RT, int NF = 4, int NW = STRIP_NW>
-static __global__ __launch_bounds__(64 * NW) void k_ip_strip_bwd(const StripBwdArgs<T> a, const int maxD) { strip_bwd_body<T, RT, NF, NW>(a, maxD); }
-// The narrow tail of a training step, forward then backward, in ONE launch of 16-example strips: what the backward half reads of the
-// forward half -- the output delta (F layout, 16 x 64) and the transposed activations its act' needs -- was stored by this same
-// workgroup, so a drained store queue and a workgroup barrier order them (this CU's L1 holds none of those lines: the forward half
-// never read them; stores write through to the L2).  Saves a launch and the second tile load's cold start.
-template <typename T, int NF, int NW>
-static __global__ __launch_bounds__(64 * NW) void k_ip_strip_tail(const StripFwdArgs<T> fa, const StripBwdArgs<T> ba, const int maxD)
-{
-    strip_fwd_body<T, 1, NF, NW>(fa, maxD);
-    asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-    lds_barrier();
-    strip_bwd_body<T, 1, NF, NW>(ba, maxD);
-}
-
-// ------------------------------------------------------------------------------------------
-// Group forms (ipnn_predict_multi / ipnn_eval_multi): the prediction of several handles on one feed batch in two launches with
-// the MODEL as blockIdx.y.  A workgroup reads its member's arguments from a device array (IpGroupArg, sent through hs[0]'s
-// ArgRing) and runs the solo kernels' bodies on them: blockIdx.x stays the example tile / the strip, so the bodies are the solo
-// kernels' own.  The gather writes the F layout of the member's a[0] only (TL = false); the strip launch is the
-// one-workgroup-per-strip form over the whole stack (duo.on = 0: a grid of strips x models exceeds the chip, so no workgroup
-// may wait for another -- no swap, no flag).  warm = 0: the arguments are not in the kernel argument segment here.
-// ------------------------------------------------------------------------------------------
-template <typename T> struct IpGroupArg {
-    int* err; int model;                                         // the member's error word and its position in the call (k_ip_gflags)
-    IpFwdArgs f; IpManyArgs m; IpWideArgs w;                     // the one its row kind takes
-    T* a0;                                                       // the member's a[0]: the hand-off between the two launches
-    StripFwdArgs<T> s;
-};
-template <typename T, int NT, bool WV>
-static __global__ __launch_bounds__(NT) void k_ip_fwd_g(const IpGroupArg<T>* __restrict__ g)
-{
-    const IpFwdArgs a = g[blockIdx.y].f;
-    ip_fwd_body<T, NT, WV, false>(a, g[blockIdx.y].a0, nullptr, nullptr);
-}
-template <typename T, bool WV>
-static __global__ __launch_bounds__(256) void k_ip_fwd_m_g(const IpGroupArg<T>* __restrict__ g)
-{
-    const IpManyArgs a = g[blockIdx.y].m;
-    ip_fwd_m_body<T, WV, false>(a, g[blockIdx.y].a0, nullptr, nullptr);
-}
-template <typename T, bool WV>
-static __global__ __launch_bounds__(256) void k_ip_fwd_w_g(const IpGroupArg<T>* __restrict__ g)
-{
-    const IpWideArgs a = g[blockIdx.y].w;
-    ip_fwd_w_body<T, WV, false>(a, g[blockIdx.y].a0, nullptr, nullptr);
-}
-template <typename T, int RT>
-static __global__ __launch_bounds__(64 * STRIP_NW) void k_ip_strip_fwd_g(const IpGroupArg<T>* __restrict__ g, const int maxD)
-{
-    strip_fwd_body<T, RT, 4, STRIP_NW>(g[blockIdx.y].s, maxD);
-}
-// The range bits (bit 1 of each member's error word) of the n members behind `args` (element stride `elem` bytes: both element
-// types share the header) into flags[their position], then cleared.  One workgroup; no handle is listed twice.
-static __global__ __launch_bounds__(256) void k_ip_gflags(const char* __restrict__ args, const size_t elem, const int n, int* __restrict__ flags)
-{
-    for (int i = threadIdx.x; i < n; i += 256) {
-        const IpGroupArg<float>* g = reinterpret_cast<const IpGroupArg<float>*>(args + (size_t)i * elem);
-        const int f = *g->err & 1;
-        flags[g->model] = f;
-        if (f) atomicAnd(g->err, ~1);
-    }
-}
-
-// Keep-masks [B][d] uint8 (the ABI's layout, reference column order) -> [Dp][ldT] uint8, zero padded,
-// for every layer in one launch; layer 0's columns are mapped to the slot layout on the way.
-struct MaskTArgs {
-    const uint8_t* src[IPNN_MAX_HIDDEN + 1]; uint8_t* dst[IPNN_MAX_HIDDEN + 1]; int d[IPNN_MAX_HIDDEN + 1], Dp[IPNN_MAX_HIDDEN + 1];
-    int tile0[IPNN_MAX_HIDDEN + 2]; int n; const int* ref0; int B, Ba, ldT; bool wt;
-};
-// (the body of k_mask_T and of its group form k_mask_T_g.  A: how the arguments arrive -- `const MaskTArgs`, the kernel's own
-// parameter, in the solo kernel; `const MaskTArgs&`, the member's record in memory, in the group form.  mask_draw_body likewise.)
-template <typename A> __device__ __forceinline__ void mask_T_body(A a)
-{
-    __shared__ __align__(4) uint8_t s[64][68];          // 17 dwords per row: the 64 lanes of a byte store (one row each) spread over all banks
-    int t = 0;
-#pragma unroll
-    for (int q = 1; q <= IPNN_MAX_HIDDEN; ++q) t += (q < a.n && (int)blockIdx.x >= a.tile0[q]) ? 1 : 0;
-    const int local = (int)blockIdx.x - a.tile0[t], ntx = a.Ba / 64;
-    const int t0 = (local % ntx) * 64, c0 = (local / ntx) * 64;
-    {   // a thread's column is the same in all 16 of its elements (i = tid + 256 k): its source column once, then all
-        // 16 bytes in one round trip, then the LDS transposition
-        // (four such tiles per workgroup, 64 loads in flight per thread, changed nothing: 12.0 against 12.2 us -- not a latency chain)
-        const int cx = threadIdx.x & 63, c = c0 + cx, d = a.d[t];
-        int sc = c < a.Dp[t] ? c : -1;
-        if (t == 0) sc = sc >= 0 ? a.ref0[sc] : -1; else if (sc >= d) sc = -1;
-        const uint8_t* __restrict__ src = a.src[t] + (sc >= 0 ? sc : 0);
-        uint8_t v[16];
-#pragma unroll
-        for (int k = 0; k < 16; ++k) {
-            const int ex = t0 + (threadIdx.x >> 6) + 4 * k;
-            v[k] = (ex < a.B && sc >= 0) ? src[(size_t)ex * d] : (uint8_t)0;
-        }
-#pragma unroll
-        for (int k = 0; k < 16; ++k) s[cx][(threadIdx.x >> 6) + 4 * k] = v[k];
-    }
-    __syncthreads();
-    const int cc = threadIdx.x >> 2, q = threadIdx.x & 3;
-    if (c0 + cc < a.Dp[t])
-    {
-        const unsigned* w = reinterpret_cast<const unsigned*>(&s[cc][16 * q]);
-        store16_sel(a.wt, a.dst[t] + mask_off(c0 + cc, t0 + 16 * q, a.ldT), make_uint4(w[0], w[1], w[2], w[3]));
-    }
-}
-static __global__ __launch_bounds__(256) void k_mask_T(const MaskTArgs a) { mask_T_body<const MaskTArgs>(a); }
-
-// Drawn keep-masks (ipnn_train_step_drawn / ipnn_draw_masks): the generator that stands where k_mask_T stands.  The mask of
-// (layer t, example ex, reference column c) is one 32-bit word of Philox4x32-10 (Salmon et al., SC'11) against a threshold:
-//   key = (lo32(seed), hi32(seed)), counter = (c, t << 16 | ex >> 2, lo32(step), hi32(step)), word j <-> example 4 (ex >> 2) + j
-// (include/ipnn_hip.h; deep-ctr_amd/dropout.py restates it in NumPy and the tests hold the two equal byte for byte).
-__device__ __forceinline__ void philox4x32_10(unsigned c0, unsigned c1, unsigned c2, unsigned c3, unsigned k0, unsigned k1, unsigned w[4])
-{
-#pragma unroll
-    for (int r = 0; r < 10; ++r) {
-        const unsigned long long p0 = (unsigned long long)0xD2511F53u * c0, p1 = (unsigned long long)0xCD9E8D57u * c2;
-        const unsigned n0 = (unsigned)(p1 >> 32) ^ c1 ^ k0, n2 = (unsigned)(p0 >> 32) ^ c3 ^ k1;
-        c1 = (unsigned)p1; c3 = (unsigned)p0; c0 = n0; c2 = n2;
-        k0 += 0x9E3779B9u; k1 += 0xBB67AE85u;
-    }
-    w[0] = c0; w[1] = c1; w[2] = c2; w[3] = c3;
-}
-// One launch for every layer, tiled like k_mask_T (64 columns x 64 examples a workgroup).  A thread owns one column and 16
-// consecutive examples: four Philox calls, one 16-byte slot of the transposed layout dstT[t] ([Dp][ldT], mask_off; pad columns
-// and the examples from B on are zero, layer 0 in slot order with the draw taken at the slot's reference column) -- written
-// exactly as k_mask_T writes it, but with nothing read.  dstR[t], where set, takes the same bytes row-major in the ABI's layout
-// ([B][d_t], reference column order) through an LDS transposition: layer 0 of a training step (the inner-product forward reads
-// it through its `mask` argument), every layer for ipnn_draw_masks.  The stores are plain C++ or raw buffer stores with the sc1
-// policy (see ipw_store16), never inline assembly.
-struct MaskDrawArgs {
-    uint8_t* dstT[IPNN_MAX_HIDDEN + 1]; uint8_t* dstR[IPNN_MAX_HIDDEN + 1]; int d[IPNN_MAX_HIDDEN + 1], Dp[IPNN_MAX_HIDDEN + 1];
-    unsigned bytesT[IPNN_MAX_HIDDEN + 1];       // extent of dstT[t]: the write-through stores' buffer resource
-    int tile0[IPNN_MAX_HIDDEN + 2]; int n; const int* ref0; int B, Ba, ldT; bool wt;
-    unsigned key0, key1, step0, step1, thr; bool all;      // all: keep_prob >= 1, every element is kept
-};
-// (the body of k_mask_draw and of its group form k_mask_draw_g)
-template <typename A> __device__ __forceinline__ void mask_draw_body(A a)
-{
-    __shared__ __align__(16) uint8_t s[64][68];         // [column][example], 17 dwords per row (k_mask_T's tile)
-    int t = 0;
-#pragma unroll
-    for (int q = 1; q <= IPNN_MAX_HIDDEN; ++q) t += (q < a.n && (int)blockIdx.x >= a.tile0[q]) ? 1 : 0;
-    uint8_t* const dT = a.dstT[t];
-    uint8_t* const dR = a.dstR[t];
-    if (!dT && !dR) return;
-    const int local = (int)blockIdx.x - a.tile0[t], ntx = a.Ba / 64;
-    const int t0 = (local % ntx) * 64, c0 = (local / ntx) * 64, d = a.d[t];
-    {
-        const int cc = threadIdx.x >> 2, q = threadIdx.x & 3, c = c0 + cc, ex0 = t0 + 16 * q;
-        int sc = t == 0 ? a.ref0[c] : (c < d ? c : -1);             // c < Dp[t]: the tiles cover exactly the padded columns
-        ipw_u32x4 v = {0u, 0u, 0u, 0u};
-        if (sc >= 0) {
-#pragma unroll
-            for (int j = 0; j < 4; ++j) {
-                const int ex = ex0 + 4 * j;
-                if (ex >= a.B) continue;
-                unsigned w[4] = {0u, 0u, 0u, 0u};
-                if (!a.all) philox4x32_10((unsigned)sc, ((unsigned)t << 16) | (unsigned)(ex >> 2), a.step0, a.step1, a.key0, a.key1, w);
-                unsigned pk = 0;
-#pragma unroll
-                for (int i = 0; i < 4; ++i) pk |= ((ex + i < a.B && (a.all || w[i] < a.thr)) ? 1u : 0u) << (8 * i);
-                v[j] = pk;
-            }
-        }
-        if (dT) ipw_store16(a.wt, ipw_rsrc(dT, a.bytesT[t]), dT, mask_off(c, ex0, a.ldT), v);
-        if (dR) {                                                    // 68 cc + 16 q is a multiple of 4 only: four dword stores
-            unsigned* sw = reinterpret_cast<unsigned*>(&s[cc][16 * q]);
-#pragma unroll
-            for (int j = 0; j < 4; ++j) sw[j] = v[j];
-        }
-    }
-    if (!dR) return;
-    __syncthreads();
-    const int cx = threadIdx.x & 63, c = c0 + cx;
-    const int sc = t == 0 ? a.ref0[c] : (c < d ? c : -1);
-    if (sc < 0) return;
-#pragma unroll
-    for (int k = 0; k < 16; ++k) {                                   // a wave writes 64 columns of one example: one run per field
-        const int r = (threadIdx.x >> 6) + 4 * k, ex = t0 + r;
-        if (ex < a.B) dR[(size_t)ex * d + sc] = s[cx][r];
-    }
-}
-static __global__ __launch_bounds__(256) void k_mask_draw(const MaskDrawArgs a) { mask_draw_body<const MaskDrawArgs>(a); }
-
-// W_t <- W_t - lr * sum of slabs; refresh both tiled shadows.  Layer 1 rows are in slot layout.
-template <typename T>
-static __global__ void k_ip_update(float* __restrict__ W, const float* __restrict__ slab, int splitk, size_t zstride,
-                                   float lr, int Din, int Dout, T* __restrict__ wf, T* __restrict__ wb)
-{
-    const size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
-    if (i >= (size_t)Din * Dout) return;
-    float w = W[i];
-    if (slab) {
-        float g = 0.f;
-        for (int z = 0; z < splitk; ++z) g += slab[(size_t)z * zstride + i];
-        w -= lr * g; W[i] = w;
-    }
-    const int r = (int)(i / Dout), c = (int)(i % Dout);
-    wf[ft_off<T>(c, r, Din)] = (T)w;
-    wb[ft_off<T>(r, c, Dout)] = (T)w;
-}
-__device__ inline float opt_step(int opt, float w, float g, float& s0, float& s1, float lr, float b1, float b2, float eps) {
-    return opt == IPNN_OPT_FTRL ? ftrl_step(w, g, s0, s1, lr) : adam_step(w, g, s0, s1, lr, b1, b2, eps);
-}
-
-static __global__ void k_fill_f32(float* __restrict__ p, size_t n, float v)
-{
-    const size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
-    if (i < n) p[i] = v;
-}
-
-// Adam on the embedding table: TensorFlow's gradient through concat / slice is DENSE (zero for
-// untouched rows), so every row's moments decay and every row moves each step -- one streaming pass
-// over table, m, v and the per-row gradient sums G (which it zeroes again for the next step).
-// (FTRL: the same pass with (accum, linear) in place of the moments.)
-static __global__ void k_adam_table(float* __restrict__ tab, float* __restrict__ m, float* __restrict__ v, float* __restrict__ G,
-                                    size_t n, float lr_t, float b1, float b2, float eps, int opt)
-{
-    const size_t i = ((size_t)blockIdx.x * blockDim.x + threadIdx.x) * 4;
-    if (i >= n) return;
-    float4 w = *reinterpret_cast<float4*>(tab + i), mm = *reinterpret_cast<float4*>(m + i), vv = *reinterpret_cast<float4*>(v + i);
-    const float4 g = *reinterpret_cast<const float4*>(G + i);
-    w.x = opt_step(opt, w.x, g.x, mm.x, vv.x, lr_t, b1, b2, eps); w.y = opt_step(opt, w.y, g.y, mm.y, vv.y, lr_t, b1, b2, eps);
-    w.z = opt_step(opt, w.z, g.z, mm.z, vv.z, lr_t, b1, b2, eps); w.w = opt_step(opt, w.w, g.w, mm.w, vv.w, lr_t, b1, b2, eps);
-    *reinterpret_cast<float4*>(tab + i) = w; *reinterpret_cast<float4*>(m + i) = mm; *reinterpret_cast<float4*>(v + i) = vv;
-    *reinterpret_cast<float4*>(G + i) = make_float4(0.f, 0.f, 0.f, 0.f);
-}
-
-// One launch for the whole stack: W_t <- W_t - lr * (sum of its split-K slabs), both tiled shadows
-// refreshed; the last workgroup applies the bias-of-z1 gradient and reduces the per-example losses.
-struct IpUpdArgs {
-    bool wt;                                         // weights and shadows written through (IPNN_WT)
-    float* W[IPNN_MAX_HIDDEN + 1]; void* wf[IPNN_MAX_HIDDEN + 1]; void* wb[IPNN_MAX_HIDDEN + 1];
-    size_t off[IPNN_MAX_HIDDEN + 2];                 // element offset of every layer in a slab; off[n] = total
-    int Din[IPNN_MAX_HIDDEN + 1], Dout[IPNN_MAX_HIDDEN + 1], sk[IPNN_MAX_HIDDEN + 1]; int n;
-    const float* slab; size_t zstride; float lr;
-    float* b; const float* gb_part; int ngb; const float* loss_t; int Ba; float* loss_sum;
-    // Adam (python/tf_util.py:17-20, TensorFlow's AdamOptimizer): first / second moments beside every tensor;
-    // lr is then lr_t = lr * sqrt(1 - beta2^t) / (1 - beta1^t) of this step
-    int adam;                                        // 0 = SGD, else IPNN_OPT_ADAM / IPNN_OPT_FTRL (state = (accum, linear))
-    float beta1, beta2, eps; float* Wm[IPNN_MAX_HIDDEN + 1]; float* Wv[IPNN_MAX_HIDDEN + 1]; float* bmv;
-    const int* err;                                  // bit 1 set (a strip pair gave up its swap): the step's activations are invalid -- nothing is applied
-};
-
-// The scalar b of z1 (python/FNN_IP_L7.py:104-114): its gradient is the sum of the per-workgroup partials of k_ip_bwd.  A launch
-// of its own on the side stream, right behind k_ip_bwd, so that the dense update on the main stream depends on nothing there.
-struct IpBArgs { float* b; const float* gb_part; int ngb, opt; float* bmv; float lr, beta1, beta2, eps; const int* err; };
-// (the body of k_ip_b_update and of its group form k_ip_b_update_g)
-__device__ __forceinline__ void ip_b_update_body(float* __restrict__ b, const float* __restrict__ gb_part, int ngb, int opt,
-                                                 float* __restrict__ bmv, float lr, float beta1, float beta2, float eps, const int* __restrict__ err)
-{
-    __shared__ float sg[256];
-    if (*err & 2) return;
-    sg[threadIdx.x] = strided_sum256(gb_part, ngb);
-    __syncthreads();
-    for (int o = 128; o > 0; o >>= 1) {
-        if ((int)threadIdx.x < o) sg[threadIdx.x] += sg[threadIdx.x + o];
-        __syncthreads();
-    }
-    if (threadIdx.x == 0) {
-        if (opt) *b = opt_step(opt, *b, sg[0], bmv[0], bmv[1], lr, beta1, beta2, eps);
-        else *b -= lr * sg[0];
-    }
-}
-static __global__ __launch_bounds__(256) void k_ip_b_update(float* __restrict__ b, const float* __restrict__ gb_part, int ngb, int opt,
-                                                            float* __restrict__ bmv, float lr, float beta1, float beta2, float eps, const int* __restrict__ err)
-{
-    ip_b_update_body(b, gb_part, ngb, opt, bmv, lr, beta1, beta2, eps, err);
-}
-
-#define UPDATE_ALL_DONE(loss) do { } while (0)
-template <typename T>
-static __global__ __launch_bounds__(256) void k_ip_update_all(const IpUpdArgs u)
-{
-#include "ip_update_all_code.inc.h"
-}
-#undef UPDATE_ALL_DONE
-
-// ------------------------------------------------------------------------------------------
-// Group forms of the training step (ipnn_train_step_multi): every stage of the step for the members of one launch class in ONE
-// launch, the MODEL as blockIdx.y.  A workgroup reads its member's record (IpStepArg, sent through hs[0]'s step ring) and runs
-// the body the solo kernel runs; blockIdx.x stays what it is in the solo launch.  A member whose extent in x is smaller than the
-// grid's returns at once.  The strips are the one-workgroup-per-strip form over the whole stack (duo.on = 0, no tail split,
-// warm = 0): a group grid holds more workgroups than the chip holds at once, so no workgroup may wait for another.
-// ------------------------------------------------------------------------------------------
-template <typename T> struct IpStepArg {
-    int model; float* pack;                                      // the member's place in the call; its two floats of the packed results (or null)
-    int n_mask, n_scat1, n_wg;                                   // the member's own extents in x: mask tiles, level-1 workgroups, weight-gradient tiles
-    int drawn;                                                   // 1: md (the library's draw), 0: mt (the caller's masks)
-    MaskDrawArgs md; MaskTArgs mt;
-    IpFwdArgs f; T* a0; T* a0T; float* emb;                      // the gather with its inner products
-    StripFwdArgs<T> s; StripBwdArgs<T> sb;                       // the stack, both directions
-    IpBwdArgs ib; const float* dz0; float* gxp; float* gb_part;  // the inner products' backward
-    IpBArgs bu;                                                  // b
-    ScatArgs sa;                                                 // the sparse rows, both levels
-    GemmGroupArgs g;                                             // the weight gradients
-    IpUpdArgs u;                                                 // the dense update and the loss sum
-};
-static_assert(sizeof(IpStepArg<float>) == sizeof(IpStepArg<bf16_t>), "one ring element for both element types");
-
-template <typename T>
-static __global__ __launch_bounds__(256) void k_mask_draw_g(const IpStepArg<T>* __restrict__ g)
-{
-    if ((int)blockIdx.x >= g[blockIdx.y].n_mask || !g[blockIdx.y].drawn) return;
-    mask_draw_body<const MaskDrawArgs&>(g[blockIdx.y].md);
-}
-template <typename T>
-static __global__ __launch_bounds__(256) void k_mask_T_g(const IpStepArg<T>* __restrict__ g)
-{
-    if ((int)blockIdx.x >= g[blockIdx.y].n_mask || g[blockIdx.y].drawn) return;
-    mask_T_body<const MaskTArgs&>(g[blockIdx.y].mt);
-}
-template <typename T, int NT, bool WV>
-static __global__ __launch_bounds__(NT) void k_ip_fwd_tg(const IpStepArg<T>* __restrict__ g)
-{
-    const IpFwdArgs a = g[blockIdx.y].f;
-    ip_fwd_body<T, NT, WV, true>(a, g[blockIdx.y].a0, g[blockIdx.y].a0T, g[blockIdx.y].emb);
-}
-template <typename T, int RT>
-static __global__ __launch_bounds__(64 * STRIP_NW) void k_ip_strip_fwd_tg(const IpStepArg<T>* __restrict__ g, const int maxD)
-{
-    strip_fwd_body<T, RT, 4, STRIP_NW>(g[blockIdx.y].s, maxD);
-}
-template <typename T, int RT>
-static __global__ __launch_bounds__(64 * STRIP_NW) void k_ip_strip_bwd_g(const IpStepArg<T>* __restrict__ g, const int maxD)
-{
-    strip_bwd_body<T, RT, 4, STRIP_NW>(g[blockIdx.y].sb, maxD);
-}
-template <typename T, bool WV>
-static __global__ __launch_bounds__(256) void k_ip_bwd_g(const IpStepArg<T>* __restrict__ g)
-{
-    const IpBwdArgs a = g[blockIdx.y].ib;
-    const float* __restrict__ dz = g[blockIdx.y].dz0;
-    float* __restrict__ gxp = g[blockIdx.y].gxp;
-    float* __restrict__ gb_part = g[blockIdx.y].gb_part;
-#include "ip_bwd_code.inc.h"
-}
-// b of the SGD members, one workgroup per member; and every member's owner count at the state the sort leaves its own (0), in
-// front of level 1: a grouping class's sort prepares the count of the buffers it is given only.  An Adam / FTRL member's b is
-// k_ip_b_update's own launch, one per such member beside its table pass: inlined here, opt_step came out with its moment updates
-// unfused where the solo kernel fuses them (v_pk_mul + v_pk_add against v_pk_fma), and b ended one rounding apart.
-template <typename T>
-static __global__ __launch_bounds__(256) void k_ip_b_update_g(const IpStepArg<T>* __restrict__ g)
-{
-    const IpBArgs a = g[blockIdx.x].bu;
-    int* const oc = g[blockIdx.x].sa.owner_cnt;
-    if (threadIdx.x == 0) *oc = 0;
-    if (a.opt) return;
-    ip_b_update_body(a.b, a.gb_part, a.ngb, a.opt, a.bmv, a.lr, a.beta1, a.beta2, a.eps, a.err);
-}
-template <typename T>
-static __global__ __launch_bounds__(256) void k_ip_scat1_g(const IpStepArg<T>* __restrict__ g)
-{
-    if ((int)blockIdx.x >= g[blockIdx.y].n_scat1) return;
-    const ScatArgs sa = g[blockIdx.y].sa;
-    if (sa.form == SCAT1_SLOT) scat1_body(sa, blockIdx.x);
-    else if (sa.form == SCAT1_HALF) scat1h_body(sa, blockIdx.x);
-    else scat1q_body(sa, blockIdx.x);
-}
-template <typename T>
-static __global__ __launch_bounds__(256) void k_ip_scat2_g(const IpStepArg<T>* __restrict__ g)
-{
-    __shared__ double s_sum[16][16];
-    const ScatArgs sa = g[blockIdx.y].sa;
-    if (sa.form2 == SCAT2_WAVE) scat2w_body(sa, blockIdx.x, gridDim.x);
-    else scat2_body(sa, blockIdx.x, gridDim.x, s_sum);
-}
-template <typename T>
-static __global__ __launch_bounds__(256) void k_ip_wgrad_g(const IpStepArg<T>* __restrict__ g)
-{
-    if ((int)blockIdx.x >= g[blockIdx.y].n_wg) return;
-    gemm_group_body<T, 4, 4>(g[blockIdx.y].g, (int)blockIdx.x);
-}
-template <typename T>
-static __global__ __launch_bounds__(256) void k_ip_update_all_g(const IpStepArg<T>* __restrict__ g)
-{
-    const IpUpdArgs& u = g[blockIdx.y].u;
-    float* const pack = g[blockIdx.y].pack;
-    // with loss_sum_out: the thread that writes the member's loss sum also writes it, and the member's error word behind it (bit 1:
-    // an id outside the table; bit 2: a strip pair gave up), into the call's packed results; the word is cleared here, as ipnn_sync
-    // clears it after a solo step that returns its loss
-#define UPDATE_ALL_DONE(loss) do { if (pack) { int* e_ = const_cast<int*>(u.err); const int f_ = *e_ & 3; pack[0] = (loss); pack[1] = (float)f_; \
-                                               if (f_) atomicAnd(e_, ~f_); } } while (0)
-#include "ip_update_all_code.inc.h"
-#undef UPDATE_ALL_DONE
-}
-// the loss sums and error words of members that ran their own step inside a group call, into the packed results (one workgroup)
-static __global__ __launch_bounds__(256) void k_ip_step_pack(const char* __restrict__ args, const size_t elem, const int n)
-{
-    for (int i = threadIdx.x; i < n; i += 256) {
-        const IpStepArg<float>* g = reinterpret_cast<const IpStepArg<float>*>(args + (size_t)i * elem);
-        int* e = const_cast<int*>(g->u.err);
-        const int f = *e & 3;
-        g->pack[0] = *g->u.loss_sum; g->pack[1] = (float)f;
-        if (f) atomicAnd(e, ~f);
-    }
-}
-
-}  // namespace
-
-namespace {
 
 // The A/B knobs of a handle, read from the environment ONCE, by ip_read_knobs in ipnn_create: a variable changed while a handle
 // lives does nothing to it.  The forms measured slower stay: the tests hold the forms against each other through these knobs.
@@ -1811,10 +227,10 @@ struct IpKernel { const void* fn; int threads; };
 #define IP_K(threads, ...) IpKernel{reinterpret_cast<const void*>(&__VA_ARGS__), (threads)}
 
 // args: the kernel's parameters, in order and of exactly its parameter types
-template <typename... A> hipError_t ip_launch(const IpKernel& k, int grid, size_t lds, hipStream_t s, const A&... args)
+template <typename... A> hipError_t ip_launch(const IpKernel& k, dim3 grid, size_t lds, hipStream_t s, const A&... args)
 {
     void* p[] = {const_cast<void*>(static_cast<const void*>(&args))...};
-    return hipLaunchKernel(k.fn, dim3((unsigned)grid), dim3((unsigned)k.threads), p, lds, s);
+    return hipLaunchKernel(k.fn, grid, dim3((unsigned)k.threads), p, lds, s);
 }
 
 // The strip kernels of one direction by (rt: rows of 16 examples per strip, nf: 16-column fragments per item, nw: waves).  Built:
@@ -2580,11 +996,6 @@ template <typename T> void ip_fill_group_arg(const ipnn_handle* h, int model, co
     sa.duo = StripDuo{0, nullptr, nullptr, 0, h->err_flag, 0, h->kn.duo_min};
     memcpy(dst, &g, sizeof(g));
 }
-template <typename... A> hipError_t ip_launch2(const IpKernel& k, dim3 grid, size_t lds, hipStream_t s, const A&... args)
-{
-    void* p[] = {const_cast<void*>(static_cast<const void*>(&args))...};
-    return hipLaunchKernel(k.fn, grid, dim3((unsigned)k.threads), p, lds, s);
-}
 // one class's two launches for a feed batch of Ba padded lines: the gather with its inner products, then the whole stack
 template <typename T> hipError_t ip_launch_class(const ipnn_handle* h, const IpPredClass& c, const void* dev_args, int Ba, hipStream_t st)
 {
@@ -2593,10 +1004,10 @@ template <typename T> hipError_t ip_launch_class(const ipnn_handle* h, const IpP
     const unsigned M = (unsigned)c.members.size();
     const int ex = c.rows == IP_WIDE ? IPW_EX : c.rows == IP_MANY ? IPM_EX : 16;
     const size_t lds = c.rows == IP_WIDE ? ipw_fwd_lds(h->F, h->rw) : c.rows == IP_MANY ? ipm_fwd_lds(h->F) : ip16_lds(h->F, h->Dp[0]);
-    hipError_t e = ip_launch2(ip_gather_fwd_g_sel<T>(c.rows, c.wv, c.nt), dim3((unsigned)(Ba / ex), M), lds, st, d);
+    hipError_t e = ip_launch(ip_gather_fwd_g_sel<T>(c.rows, c.wv, c.nt), dim3((unsigned)(Ba / ex), M), lds, st, d);
     if (e != hipSuccess) return e;
     const int maxD = h->plan.maxD;
-    return ip_launch2(ip_strip_g_sel<T>(), dim3((unsigned)(Ba / (16 * RT)), M), h->plan.strip_lds, st, d, maxD);
+    return ip_launch(ip_strip_g_sel<T>(), dim3((unsigned)(Ba / (16 * RT)), M), h->plan.strip_lds, st, d, maxD);
 }
 
 // The predictions of the n members hs[0 .. n) of group `g` (positions base .. in the call) on the N lines, p[m] each.  Members on
@@ -2615,11 +1026,7 @@ int ip_group_forward(const IpGroup& g, ipnn_handle* const* hs, int n, int base, 
     int fb = 4096, ng = 0;
     for (int m = 0; m < n; ++m) {
         if (all_own || !hs[m]->plan.strip) { own.push_back(m); continue; }
-        const IpPredClass c = ip_pred_class_of(hs[m], wts != nullptr);
-        size_t i = 0;
-        while (i < cls.size() && !cls[i].same(c)) ++i;
-        if (i == cls.size()) cls.push_back(c);
-        cls[i].members.push_back(m);
+        cls[class_index(cls, ip_pred_class_of(hs[m], wts != nullptr))].members.push_back(m);
         fb = std::min(fb, hs[m]->ldT); ++ng;
     }
     const size_t elem = h0->eval_ring.elem;
@@ -2627,8 +1034,8 @@ int ip_group_forward(const IpGroup& g, ipnn_handle* const* hs, int n, int base, 
         const int B = (int)std::min<int64_t>(fb, N - lo);
         size_t slot = 0;
         IHK(h0, ring_take(h0->eval_ring, (size_t)ng, &slot));
-        char* a = static_cast<char*>(h0->eval_ring.host) + slot * elem;
-        const char* d = static_cast<const char*>(h0->eval_ring.dev) + slot * elem;
+        char* a = h0->eval_ring.host_bytes(slot);
+        const char* d = h0->eval_ring.dev_bytes(slot);
         size_t pos = 0;
         int Ba = 0;
         for (const IpPredClass& c : cls) for (int m : c.members) {
@@ -2679,6 +1086,7 @@ bool ip_step_shares(const ipnn_handle* h)
 // A training LAUNCH CLASS: the prediction launch class (element type, depth, padded widths, the gather's block size, pairs,
 // weights given or not) and the tiles of the grouped weight-gradient launch (the split-K of every product).  Everything else that
 // differs between two members is a run-time field of their records: the scatter forms, wt, the optimiser, act, k, every value.
+// Its members are pc.members.
 struct IpStepClass {
     IpPredClass pc; int n_wg;
     bool same(const IpStepClass& o) const { return pc.same(o.pc) && n_wg == o.n_wg; }
@@ -2721,26 +1129,27 @@ template <typename T> void ip_fill_step_arg(ipnn_handle* h, int model, const IpC
 // every stage of the step for one launch class, each ONE launch over (the stage's extent, the class's members); `d`: the members'
 // records on the device.  ext: the largest extents among the members (mask tiles of either kind, level-1 workgroups).
 struct IpStepExt { int n_draw = 0, n_maskT = 0, n_scat1 = 0; };
-template <typename T> hipError_t ip_launch_step_class(const ipnn_handle* h, const IpStepClass& c, const IpStepExt& x, unsigned M, const void* dev_args,
+template <typename T> hipError_t ip_launch_step_class(const ipnn_handle* h, const IpStepClass& c, const IpStepExt& x, const void* dev_args,
                                                        int Ba, hipStream_t st)
 {
     constexpr int RT = sizeof(T) == 2 ? 2 : 1;
     const IpStepArg<T>* d = static_cast<const IpStepArg<T>*>(dev_args);
+    const unsigned M = (unsigned)c.pc.members.size();
     const size_t lds16 = ip16_lds(h->F, h->Dp[0]);
     const int maxD = h->plan.maxD;
     hipError_t e = hipSuccess;
 #define STEP_K(expr) do { if ((e = (expr)) != hipSuccess) return e; } while (0)
-    if (x.n_draw) STEP_K(ip_launch2(IP_K(256, k_mask_draw_g<T>), dim3((unsigned)x.n_draw, M), 0, st, d));
-    if (x.n_maskT) STEP_K(ip_launch2(IP_K(256, k_mask_T_g<T>), dim3((unsigned)x.n_maskT, M), 0, st, d));
-    STEP_K(ip_launch2(ip_step_gather_sel<T>(c.pc.wv, c.pc.nt), dim3((unsigned)(Ba / 16), M), lds16, st, d));
-    STEP_K(ip_launch2(ip_step_strip_sel<T>(false), dim3((unsigned)(Ba / (16 * RT)), M), h->plan.strip_lds, st, d, maxD));
-    STEP_K(ip_launch2(ip_step_strip_sel<T>(true), dim3((unsigned)(Ba / (16 * RT)), M), h->plan.strip_lds, st, d, maxD));
-    STEP_K(ip_launch2(ip_step_bwd_sel<T>(c.pc.wv), dim3((unsigned)(Ba / 16), M), lds16, st, d));
-    STEP_K(ip_launch2(IP_K(256, k_ip_b_update_g<T>), dim3(M), 0, st, d));
-    STEP_K(ip_launch2(IP_K(256, k_ip_scat1_g<T>), dim3((unsigned)x.n_scat1, M), 0, st, d));
-    STEP_K(ip_launch2(IP_K(256, k_ip_scat2_g<T>), dim3(256, M), 0, st, d));
-    STEP_K(ip_launch2(IP_K(256, k_ip_wgrad_g<T>), dim3((unsigned)c.n_wg, M), gemm_f32w_lds(), st, d));
-    STEP_K(ip_launch2(IP_K(256, k_ip_update_all_g<T>), dim3((unsigned)(h->plan.upd.off[h->L + 1] / 4096 + 1), M), 0, st, d));
+    if (x.n_draw) STEP_K(ip_launch(IP_K(256, k_mask_draw_g<T>), dim3((unsigned)x.n_draw, M), 0, st, d));
+    if (x.n_maskT) STEP_K(ip_launch(IP_K(256, k_mask_T_g<T>), dim3((unsigned)x.n_maskT, M), 0, st, d));
+    STEP_K(ip_launch(ip_step_gather_sel<T>(c.pc.wv, c.pc.nt), dim3((unsigned)(Ba / 16), M), lds16, st, d));
+    STEP_K(ip_launch(ip_step_strip_sel<T>(false), dim3((unsigned)(Ba / (16 * RT)), M), h->plan.strip_lds, st, d, maxD));
+    STEP_K(ip_launch(ip_step_strip_sel<T>(true), dim3((unsigned)(Ba / (16 * RT)), M), h->plan.strip_lds, st, d, maxD));
+    STEP_K(ip_launch(ip_step_bwd_sel<T>(c.pc.wv), dim3((unsigned)(Ba / 16), M), lds16, st, d));
+    STEP_K(ip_launch(IP_K(256, k_ip_b_update_g<T>), dim3(M), 0, st, d));
+    STEP_K(ip_launch(IP_K(256, k_ip_scat1_g<T>), dim3((unsigned)x.n_scat1, M), 0, st, d));
+    STEP_K(ip_launch(IP_K(256, k_ip_scat2_g<T>), dim3(256, M), 0, st, d));
+    STEP_K(ip_launch(IP_K(256, k_ip_wgrad_g<T>), dim3((unsigned)c.n_wg, M), gemm_f32w_lds(), st, d));
+    STEP_K(ip_launch(IP_K(256, k_ip_update_all_g<T>), dim3((unsigned)(h->plan.upd.off[h->L + 1] / 4096 + 1), M), 0, st, d));
 #undef STEP_K
     return hipSuccess;
 }
@@ -3194,14 +1603,14 @@ int ipnn_eval_multi(ipnn_handle* const* hs, int n_models, const int32_t* ids, co
     const EvalFlags flags = [&](int g0, int n, int* flags_d) {        // the members' range bits, read and cleared on the device
         size_t slot = 0;
         IHK(h0, ring_take(h0->eval_ring, (size_t)n, &slot));
-        char* a = static_cast<char*>(h0->eval_ring.host) + slot * elem;
+        char* a = h0->eval_ring.host_bytes(slot);
         for (int m = 0; m < n; ++m) {
             IpGroupArg<float> fa{};
             fa.err = hs[g0 + m]->err_flag; fa.model = m;
             memcpy(a + (size_t)m * elem, &fa, sizeof(fa));
         }
         IHK(h0, ring_send(h0->eval_ring, slot, (size_t)n, st));
-        hipLaunchKernelGGL(k_ip_gflags, dim3(1), dim3(256), 0, st, static_cast<const char*>(h0->eval_ring.dev) + slot * elem, elem, n, flags_d);
+        hipLaunchKernelGGL(k_ip_gflags, dim3(1), dim3(256), 0, st, h0->eval_ring.dev_bytes(slot), elem, n, flags_d);
         IHK(h0, hipGetLastError());
         return FNN_OK;
     };
@@ -3252,15 +1661,11 @@ int ipnn_train_step_multi(ipnn_handle* const* hs, int n_models, const int32_t* i
     const hipStream_t st = h0->st;
     // the members by path and class
     std::vector<IpStepClass> cls;
-    std::vector<std::vector<int>> mem;
     std::vector<int> own;
     for (int m = 0; m < M; ++m) {
         if (!ip_step_shares(hs[m])) { own.push_back(m); continue; }
-        IpStepClass c{ip_pred_class_of(hs[m], wts != nullptr), hs[m]->plan.group.wg0[hs[m]->L + 1]};
-        size_t i = 0;
-        while (i < cls.size() && !cls[i].same(c)) ++i;
-        if (i == cls.size()) { cls.push_back(c); mem.emplace_back(); }
-        mem[i].push_back(m);
+        const IpStepClass c{ip_pred_class_of(hs[m], wts != nullptr), hs[m]->plan.group.wg0[hs[m]->L + 1]};
+        cls[class_index(cls, c)].pc.members.push_back(m);
     }
     const int ng = M - (int)own.size();
     if (seeds) for (int m = 0; m < M; ++m)                            // every byte a step reads is drawn by that step
@@ -3278,14 +1683,13 @@ int ipnn_train_step_multi(ipnn_handle* const* hs, int n_models, const int32_t* i
     int Ba = 0;
     if (nrec) {
         IHK(h0, ring_take(h0->step_ring, nrec, &slot));
-        char* a = static_cast<char*>(h0->step_ring.host) + slot * elem;
-        d = static_cast<const char*>(h0->step_ring.dev) + slot * elem;
+        char* a = h0->step_ring.host_bytes(slot);
+        d = h0->step_ring.dev_bytes(slot);
         size_t pos = 0;
-        for (size_t i = 0; i < cls.size(); ++i) for (int m : mem[i]) {
+        for (size_t i = 0; i < cls.size(); ++i) for (int m : cls[i].pc.members) {
             ipnn_handle* h = hs[m];
-            size_t s = 0;
-            while (s < sorts.size() && !(sorts[s].n_rows == h->n_rows && sorts[s].key64 == h->key64 && sorts[s].merge4 == h->kn.sort_merge4)) ++s;
-            if (s == sorts.size()) sorts.push_back(IpSortClass{h->n_rows, h->key64, h->kn.sort_merge4, h});
+            const size_t s = class_index(sorts, IpSortClass{h->n_rows, h->key64, h->kn.sort_merge4, h}, [](const IpSortClass& a, const IpSortClass& b) {
+                return a.n_rows == b.n_rows && a.key64 == b.key64 && a.merge4 == b.merge4; });
             const IpCall c = ip_step_call(h, ids, wts, y, B, mask_of(m), draw_of(m), logits_of(m));
             Ba = c.Ba;
             float* pack = loss_sum_out ? h0->step_pack + 2 * m : nullptr;
@@ -3311,22 +1715,22 @@ int ipnn_train_step_multi(ipnn_handle* const* hs, int n_models, const int32_t* i
     {
         size_t pos = 0;
         for (size_t i = 0; i < cls.size(); ++i) {
-            const ipnn_handle* h = hs[mem[i][0]];
-            const unsigned n = (unsigned)mem[i].size();
-            IHK(h0, cls[i].pc.bf16 ? ip_launch_step_class<bf16_t>(h, cls[i], ext[i], n, d + pos * elem, Ba, st)
-                                   : ip_launch_step_class<float>(h, cls[i], ext[i], n, d + pos * elem, Ba, st));
-            for (int m : mem[i]) if (hs[m]->adam) {                   // an Adam / FTRL member's b and table pass: the solo step's own launches
+            const std::vector<int>& mem = cls[i].pc.members;
+            const ipnn_handle* h = hs[mem[0]];
+            IHK(h0, cls[i].pc.bf16 ? ip_launch_step_class<bf16_t>(h, cls[i], ext[i], d + pos * elem, Ba, st)
+                                   : ip_launch_step_class<float>(h, cls[i], ext[i], d + pos * elem, Ba, st));
+            for (int m : mem) if (hs[m]->adam) {                      // an Adam / FTRL member's b and table pass: the solo step's own launches
                 ipnn_handle* hm = hs[m];
                 const float lr_step = ip_lr_step(hm, hm->adam_t + 1);
                 const IpCall c = ip_step_call(hm, ids, wts, y, B, nullptr, nullptr, nullptr);
                 ip_b_update(hm, c, st, lr_step);
                 ip_adam_table(hm, st, lr_step);
             }
-            pos += n;
+            pos += mem.size();
         }
     }
     IHK(h0, hipGetLastError());
-    for (size_t i = 0; i < cls.size(); ++i) for (int m : mem[i]) if (hs[m]->adam) hs[m]->adam_t += 1;      // accepted: the members have made a step
+    for (const IpStepClass& c : cls) for (int m : c.pc.members) if (hs[m]->adam) hs[m]->adam_t += 1;      // accepted: the members have made a step
     for (int m : own) {
         ipnn_handle* h = hs[m];
         const int rc = on_stream(h, st, [&] {
@@ -3348,8 +1752,8 @@ int ipnn_train_step_multi(ipnn_handle* const* hs, int n_models, const int32_t* i
     for (int m = 0; m < M; ++m) {
         loss_sum_out[m] = h0->step_pack_host[2 * m];
         const int f = (int)h0->step_pack_host[2 * m + 1];
-        if (f & 2) { hs[m]->duo_failed = true; gave_up += (gave_up.empty() ? "" : ", ") + std::to_string(m); }      // as ipnn_sync judges a solo step
-        else if (f & 1) bad += (bad.empty() ? "" : ", ") + std::to_string(m);
+        if (f & 2) { hs[m]->duo_failed = true; eval_list_add(gave_up, m); }      // as ipnn_sync judges a solo step
+        else if (f & 1) eval_list_add(bad, m);
     }
     if (!gave_up.empty())
         return g.refuse(FNN_ERR_HIP, "a strip workgroup gave up waiting for its partner (StripDuo swap) in model(s) " + gave_up +

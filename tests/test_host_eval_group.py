@@ -1,6 +1,7 @@
 """The host arithmetic of fm_eval_multi / fnn_eval_multi / ipnn_eval_multi (deep-ctr_amd/csrc/eval_group.h, free of HIP): the
-group size under the scratch cap, a model's metrics from its sums, and the call's final message.  A stand-alone C++ program
-with its own main, built with the address and undefined-behaviour sanitizers and run; nothing is loaded into Python."""
+group size under the scratch cap, a model's metrics from its sums, the call's final message, and the launch classes of a list of
+members (class_index, which the step calls use too).  A stand-alone C++ program with its own main, built with the address and
+undefined-behaviour sanitizers and run; nothing is loaded into Python."""
 import os
 import shutil
 import subprocess
@@ -14,6 +15,7 @@ PROGRAM = r"""
 
 #include <cstdio>
 #include <limits>
+#include <vector>
 
 using namespace fnn;
 
@@ -108,12 +110,61 @@ static void cap()
     CHECK(eval_scratch_cap("EVAL_GROUP_TEST_CAP") == (size_t)1 << 30);
 }
 
+// A launch class as the group calls have them: what is compared (key) and what is not (tag: who opened the class).
+struct Cls {
+    int key, tag;
+    bool same(const Cls& o) const { return key == o.key; }
+};
+
+static void classes()
+{
+    auto eq = [](const Cls& a, const Cls& b) { return a.key == b.key; };
+    // an empty list: the element opens class 0
+    std::vector<Cls> v;
+    CHECK(class_index(v, Cls{5, 0}, eq) == 0 && v.size() == 1 && v[0].key == 5 && v[0].tag == 0);
+    // every element new: one class each, in the order they came
+    v.clear();
+    for (int m = 0; m < 7; ++m) CHECK(class_index(v, Cls{10 * m, m}, eq) == (size_t)m);
+    CHECK(v.size() == 7);
+    for (int m = 0; m < 7; ++m) CHECK(v[m].key == 10 * m && v[m].tag == m);
+    // every element equal: class 0, which stays its first member's
+    v.clear();
+    for (int m = 0; m < 7; ++m) CHECK(class_index(v, Cls{4, m}, eq) == 0);
+    CHECK(v.size() == 1 && v[0].tag == 0);
+    // an element that equals only a later class gets that class's index, not a new one; nothing in front of it moves
+    v = {Cls{1, 0}, Cls{2, 1}, Cls{3, 2}};
+    CHECK(class_index(v, Cls{3, 9}, eq) == 2 && v.size() == 3);
+    CHECK(class_index(v, Cls{2, 9}, eq) == 1 && v.size() == 3);
+    CHECK(class_index(v, Cls{4, 3}, eq) == 3 && v.size() == 4);
+    for (int m = 0; m < 4; ++m) CHECK(v[m].key == m + 1 && v[m].tag == m);
+    // a predicate that accepts several classes: always the FIRST of them
+    auto parity = [](const Cls& a, const Cls& b) { return (a.key & 1) == (b.key & 1); };
+    v = {Cls{2, 0}, Cls{3, 1}, Cls{5, 2}, Cls{4, 3}};
+    CHECK(class_index(v, Cls{7, 9}, parity) == 1);
+    CHECK(class_index(v, Cls{8, 9}, parity) == 0);
+    CHECK(v.size() == 4);
+    for (int m = 0; m < 4; ++m) CHECK(v[m].tag == m);
+    // the form without a predicate is same() of the classes themselves
+    v.clear();
+    const int keys[] = {6, 8, 6, 7, 8, 6};
+    const size_t want[] = {0, 1, 0, 2, 1, 0};
+    for (int m = 0; m < 6; ++m) CHECK(class_index(v, Cls{keys[m], m}) == want[m]);
+    CHECK(v.size() == 3 && v[0].tag == 0 && v[1].tag == 1 && v[2].tag == 3);
+    // members appended through the index, as the calls do: first-member order of the classes, list order inside each
+    struct WithMembers { int key; std::vector<int> members; };
+    std::vector<WithMembers> w;
+    for (int m = 0; m < 6; ++m)
+        w[class_index(w, WithMembers{keys[m], {}}, [](const WithMembers& a, const WithMembers& b) { return a.key == b.key; })].members.push_back(m);
+    CHECK(w.size() == 3 && w[0].members == (std::vector<int>{0, 2, 5}) && w[1].members == (std::vector<int>{1, 4}) && w[2].members == (std::vector<int>{3}));
+}
+
 int main()
 {
     group_size();
     verdict();
     values();
     cap();
+    classes();
     if (failures) { std::fprintf(stderr, "%d check(s) failed\n", failures); return 1; }
     std::puts("eval_group OK");
     return 0;
