@@ -16,10 +16,22 @@ import deep_ctr_amd  # noqa: E402,F401
 from deep_ctr_amd import SNN_RBM  # noqa: E402
 
 
+def _pretrain_kw():
+    return dict(da_batch_size=int(os.environ.get('DEEPCTR_DAE_BATCH', 1)),
+                corruption_level=float(os.environ.get('DEEPCTR_DAE_CORRUPTION', 0)))
+
+
 def run(argv):
-    return SNN_RBM.run(argv, kind='dae', pretrain_kw=dict(da_batch_size=int(os.environ.get('DEEPCTR_DAE_BATCH', 1)),
-                                                          corruption_level=float(os.environ.get('DEEPCTR_DAE_CORRUPTION', 0))))
+    return SNN_RBM.run(argv, kind='dae', pretrain_kw=_pretrain_kw())
+
+
+def run_many(argv, specs, out=None):
+    """SNN_RBM.run_many with the denoising-autoencoder pre-trainer: every 'LR:DROPOUT:LAMBDA1' of `specs` in one pass."""
+    return SNN_RBM.run_many(argv, specs, kind='dae', pretrain_kw=_pretrain_kw(), out=out)
 
 
 if __name__ == '__main__':
-    run(sys.argv)
+    if len(sys.argv) > 1 and sys.argv[1] == 'many':           # python SNN_DAE.py many <advertiser> LR:DROPOUT:LAMBDA1 ...
+        run_many([sys.argv[0]] + sys.argv[2:3], sys.argv[3:])
+    else:
+        run(sys.argv)

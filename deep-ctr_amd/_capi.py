@@ -62,6 +62,7 @@ SIGNATURES = {
     "fnn_prefetch_ids": (_i, [_vp, _vp, _i]),
     # hs, mask1, mask2, p_out: host arrays of n_models pointers; loss_sum_out: host float [n_models]
     "fnn_train_step_multi": (_i, [_vp, _i, _vp, _vp, _i, _vp, _vp, _i, _vp, _i, _vp, C.POINTER(_f)]),
+    "fnn_bag_train_step_multi": (_i, [_vp, _i, _vp, _vp, _i, _vp, _vp, _i, _vp, _i, _vp, C.POINTER(_f)]),      # the same, bag handles
     "fnn_dp_unique_id": (_i, [_vp]),
     "fnn_dp_init": (_i, [_vp, _i, _i, _vp, _i]),
     "fnn_dp_init_custom": (_i, [_vp, _i, _i, _vp, _vp, _vp, _i]),

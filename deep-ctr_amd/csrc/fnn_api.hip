@@ -363,6 +363,16 @@ template <typename T> GroupKernel<T> gstep1_sel(const FnnPlan& p, const FnnKnobs
     return big ? GSTEP1(5, 2, 4, -1) : GSTEP1(1, 1, 4, -1);
 #undef GSTEP1
 }
+// ... and of fnn_bag_train_step_multi: the strips of bag rows, the instances that step1_sel(train = true) returns for a bag handle
+template <typename T> GroupKernel<T> gstep1_bag_sel(const FnnPlan& p, const FnnKnobs& kn)
+{
+#define GSTEP1B(C1, C2, CX, NW) GroupKernel<T>{k_gstep1<T, C1, C2, CX, NW, -1, true>, 64 * NW, mlp_lds_bytes<T, C1, C2, CX>(true, p.F, NW)}
+    const bool big = p.H1p / 64 == 5, x5 = p.K1p / 64 == 5;
+    if (big && kn.step1_waves == 8) return x5 ? GSTEP1B(5, 2, 5, 8) : GSTEP1B(5, 2, 4, 8);
+    if (x5) return GSTEP1B(5, 2, 5, 4);
+    return big ? GSTEP1B(5, 2, 4, 4) : GSTEP1B(1, 1, 4, 4);
+#undef GSTEP1B
+}
 // ---- the group kernel of fnn_predict_multi / fnn_eval_multi: the generic instance on FM rows that step1_sel(train = false)
 // returns, by the same conditions; the only place that names an instantiation of k_gpredict
 template <typename T> GroupPredKernel<T> gpredict_sel(const FnnPlan& p, const FnnKnobs& kn)
@@ -951,20 +961,22 @@ FnnPlan make_plan(const fnn_cfg& c, const FnnKnobs& kn)
     return p;
 }
 
-// ---- fnn_train_step_multi: one step of several handles on one feed (the kernels: k_gstep1 / k_gstep2 / k_gstep3)
+// ---- fnn_train_step_multi / fnn_bag_train_step_multi: one step of several handles on one feed (the kernels: k_gstep1 / k_gstep2 / k_gstep3)
 // A call on a list of handles: GroupCall (group_call.h), refusals without a usable hs[0] left with fnn_last_error(NULL).
 using FnnGroup = GroupCall<fnn_handle>;
 
 // What decides which handles one set of group launches serves: the three kernels with their block and LDS sizes, and what
 // shapes the grid -- a LAUNCH CLASS (include/fnn_hip.h).  The kernels follow from element type, padded shapes, key width, sort
-// runs, weight-gradient form and the strip kernel's knobs (gstep*_sel).
+// runs, weight-gradient form and the strip kernel's knobs (gstep*_sel).  Bag mode: `bag` itself; K is the width of a bag row (rw =
+// h0, which with K1p tells h0 192..252 from 256..316 and sizes level 1 of the row update) and F the columns of a line (2..64).
+// Key width and sort runs choose the kernels of launches 2 and 3, so members that agree in k[] agree in them.
 struct LaunchClass {
-    FnnKernel<> k[3]; int prec, F, K, K1p, H1p, H2p, splitk, wl, scat_form, scat2_form, scat2_wgs, wt_stores, role_off;
+    FnnKernel<> k[3]; int prec, bag, F, K, K1p, H1p, H2p, splitk, wl, scat_form, scat2_form, scat2_wgs, wt_stores, role_off;
     std::vector<int> members;                      // indices into hs, in the call's order
     bool same(const LaunchClass& o) const
     {
         for (int i = 0; i < 3; ++i) if (k[i].fn != o.k[i].fn || k[i].threads != o.k[i].threads || k[i].lds != o.k[i].lds) return false;
-        return prec == o.prec && F == o.F && K == o.K && K1p == o.K1p && H1p == o.H1p && H2p == o.H2p && splitk == o.splitk && wl == o.wl &&
+        return prec == o.prec && bag == o.bag && F == o.F && K == o.K && K1p == o.K1p && H1p == o.H1p && H2p == o.H2p && splitk == o.splitk && wl == o.wl &&
                scat_form == o.scat_form && scat2_form == o.scat2_form && scat2_wgs == o.scat2_wgs && wt_stores == o.wt_stores && role_off == o.role_off;
     }
 };
@@ -972,21 +984,23 @@ template <typename T> LaunchClass launch_class_of(const fnn_handle* h)
 {
     const bool m4 = h->kn.sort_merge4 != 0;
     const bool wl = !(h->kn.role_off & 2) && h->wgrad_lds && sizeof(T) == 2;       // launch_step2's choice
-    const GroupKernel<T> k1 = gstep1_sel<T>(*h, h->kn), k2 = gstep2_sel<T>(h->key64, m4, wl), k3 = gstep3_sel<T>(h->key64, m4);
+    const GroupKernel<T> k1 = h->bag ? gstep1_bag_sel<T>(*h, h->kn) : gstep1_sel<T>(*h, h->kn), k2 = gstep2_sel<T>(h->key64, m4, wl), k3 = gstep3_sel<T>(h->key64, m4);
     LaunchClass c{};
     c.k[0] = {reinterpret_cast<void (*)()>(k1.fn), k1.threads, k1.lds};
     c.k[1] = {reinterpret_cast<void (*)()>(k2.fn), k2.threads, std::max(k2.lds, wl ? WGRAD_LDS_BYTES : (size_t)0)};
     c.k[2] = {reinterpret_cast<void (*)()>(k3.fn), k3.threads, k3.lds};
-    c.prec = h->cfg.precision; c.F = h->F; c.K = h->K; c.K1p = h->K1p; c.H1p = h->H1p; c.H2p = h->H2p; c.splitk = h->splitk; c.wl = wl;
+    c.prec = h->cfg.precision; c.bag = h->bag ? 1 : 0; c.F = h->F; c.K = h->K; c.K1p = h->K1p; c.H1p = h->H1p; c.H2p = h->H2p; c.splitk = h->splitk; c.wl = wl;
     c.scat_form = h->kn.scat_form; c.scat2_form = h->kn.scat2_form; c.scat2_wgs = h->kn.scat2_wgs; c.wt_stores = h->kn.wt_stores;
     c.role_off = h->kn.role_off;
     return c;
 }
 // Member h's entry of the argument array: what launch_step1 / launch_step2 / launch_step3 would pass for it, with the grouping
-// class's records (`rec`: of the slot in which the class's first member holds the batch's grouping).  x2 / x3: the workgroups it needs in
-// launches 2 / 3.
+// class's grouping (`grp`: the slot in which the class's first member holds the batch's): its records and, in bag mode, its marks
+// of the rows that several columns of the batch hold, with the stamp they were written under -- a follower's own tag_shared / stamp
+// are those of some earlier batch, and with them a shared row would take the plain store and keep one column's sum of all.
+// x2 / x3: the workgroups it needs in launches 2 / 3.
 template <typename T>
-bool fill_group_arg(fnn_handle* h, const int4* rec, const int32_t* ids, const float* y, int B, const uint8_t* m1, const uint8_t* m2,
+bool fill_group_arg(fnn_handle* h, const fnn_handle::SortSlot& grp, const int32_t* ids, const float* y, int B, const uint8_t* m1, const uint8_t* m2,
                     float* p_out, GroupPack* pack, void* dst, int* x2, int* x3)
 {
     GroupArg<T>& g = *static_cast<GroupArg<T>*>(dst);
@@ -994,10 +1008,11 @@ bool fill_group_arg(fnn_handle* h, const int4* rec, const int32_t* ids, const fl
     g.ma = make_mlp_args<T>(h, ids, y, B, m1, m2, true, p_out);
     g.nmlp = h->pend_Ba / 16;
     Step23Args a = make_step23_args(h, r, false);
-    a.sa.rec = rec;
+    a.sa.rec = grp.rec; a.sa.tag_shared = grp.tag_shared; a.sa.stamp = grp.stamp;
     g.wa = make_wgrad_args<T>(h, h->pend_Ba);
     g.nwx = r.dense ? wgrad_blocks(g.wa) : 0; g.splitk = h->splitk;
-    g.nsc1 = r.sparse ? scat1_blocks(a.sa, h->kn.scat_form) : 0;
+    g.nsc1 = !r.sparse ? 0 : (h->bag ? (int)(((size_t)h->F * (SORT_N / WCH) * (h->rw / 4) + 255) / 256)      // launch_step2's count
+                                     : scat1_blocks(a.sa, h->kn.scat_form));
     g.so2 = a.so; g.sa = a.sa;
     g.so3 = make_step23_args(h, r, true).so;
     g.ta = make_tail_args(h, r);
@@ -1869,12 +1884,13 @@ int fnn_train_step(fnn_handle* h, const int32_t* ids, const float* y, int B, con
 }
 
 // One step of several handles on one feed: per launch class the three launches of run_step_fast with the model as a grid
-// dimension ("The FNN step for many models").
-int fnn_train_step_multi(fnn_handle* const* hs, int n_models, const int32_t* ids, const float* y, int B,
-                         const uint8_t* const* mask1, const uint8_t* const* mask2, int b_size,
-                         const int32_t* next_ids, int next_B, float* const* p_out, float* loss_sum_out)
+// dimension ("The FNN step for many models" and "The SNN fine-tune step for many models").  One body for
+// both families: `bag` says which one the entry point `name` takes, FNN_MODE_FM handles or FNN_MODE_BAG handles.
+static int train_step_group(const char* name, const bool bag, fnn_handle* const* hs, int n_models, const int32_t* ids, const float* y, int B,
+                            const uint8_t* const* mask1, const uint8_t* const* mask2, int b_size,
+                            const int32_t* next_ids, int next_B, float* const* p_out, float* loss_sum_out)
 {
-    FnnGroup g("fnn_train_step_multi", hs, n_models, FNN_STEP_MAX_MODELS, g_create_err);
+    FnnGroup g(name, hs, n_models, FNN_STEP_MAX_MODELS, g_create_err);
     const int M = n_models;
     // ---- refusals: all of them before anything is launched or written
     RCCHK(g.check_list("two updates would race on one model"));
@@ -1887,7 +1903,7 @@ int fnn_train_step_multi(fnn_handle* const* hs, int n_models, const int32_t* ids
     for (int m = 0; m < M; ++m) {
         const fnn_handle* h = hs[m];
         if (next_ids && next_B > h->Bmax) return g.refuse(FNN_ERR_ARG, g.at("next_B must be in [1, max_batch]", m));
-        if (h->bag) return g.refuse(FNN_ERR_ARG, g.at("FNN_MODE_BAG handles take fnn_train_step, one at a time", m));
+        if (h->bag != bag) return g.refuse(FNN_ERR_ARG, g.at(bag ? "FNN_MODE_FM handles take fnn_train_step_multi" : "FNN_MODE_BAG handles take fnn_train_step, one at a time", m));
         if (h->wide) return g.refuse(FNN_ERR_ARG, g.at("wide rows (k >= 17) take fnn_train_step, one at a time", m));
         if (!h->strip_ok) return g.refuse(FNN_ERR_ARG, g.at("the handle does not run the strip kernel (hidden sizes it is not built for, or FNN_NO_FUSE=1)", m));
         if (h->n_shadow > 0) return g.refuse(FNN_ERR_ARG, g.at("shadowed features pending (fnn_set_shadowed): such a batch takes fnn_train_step", m));
@@ -1935,12 +1951,10 @@ int fnn_train_step_multi(fnn_handle* const* hs, int n_models, const int32_t* ids
     for (LaunchClass& c : cls) {
         // grouping classes: the members of equal n_rows share the grouping of the first of them
         std::vector<fnn_handle*> lead(c.members.size());
-        std::vector<const int4*> rec(c.members.size());
         for (size_t i = 0; i < c.members.size(); ++i) {
             size_t j = 0;
             while (hs[c.members[j]]->n_rows != hs[c.members[i]]->n_rows) ++j;
             lead[i] = hs[c.members[j]];
-            rec[i] = lead[i]->slot[lead[i]->cur].rec;
         }
         Launch L{d + pos * h0->step_ring.elem, 0, 0, 0};
         for (size_t i = 0; i < c.members.size(); ++i) {
@@ -1953,7 +1967,8 @@ int fnn_train_step_multi(fnn_handle* const* hs, int n_models, const int32_t* ids
                 if (!(h->sorted_ids == ids && h->sorted_B == B)) {
                     h->prefetch_misses++;
                     fnn_handle::SortSlot& sl = h->slot[h->cur];
-                    on_stream(h, st, [&] { launch_sort16(h, SortArgs{ids, B, h->F, h->n_rows, sl.rec, sl.owner_cnt, h->F, h->skeys, h->tag_first, sl.tag_shared, 0}); return 0; });
+                    // (bag mode draws the slot's stamp, as run_step_fast does; on FM rows there are no marks and the stamp is 0)
+                    on_stream(h, st, [&] { launch_sort16(h, SortArgs{ids, B, h->F, h->n_rows, sl.rec, sl.owner_cnt, h->F, h->skeys, h->tag_first, sl.tag_shared, next_stamp(h, sl)}); return 0; });
                     h->sorted_ids = ids; h->sorted_B = B;             // what the slot holds from here on, whatever becomes of the call
                 } else h->prefetch_hits++;
                 if (next_ids) { h->next_ids = next_ids; h->next_B = next_B; }
@@ -1961,9 +1976,12 @@ int fnn_train_step_multi(fnn_handle* const* hs, int n_models, const int32_t* ids
             } else {
                 h->next_ids = nullptr; h->next_B = 0; h->pend_have_next = false;
             }
+            // (the first member comes before its followers: its slot holds the batch's grouping, stamp included, by now; the stamp of
+            // the NEXT batch's grouping is drawn on the group's stream too)
             int x2 = 0, x3 = 0;
-            have_next[m] = BY_PREC_RC(h, fill_group_arg, (h, rec[i], ids, y, B, mask1[m], mask2[m], p_out ? p_out[m] : nullptr,
-                                                                 pack ? pack + m : nullptr, a + (pos + i) * h0->step_ring.elem, &x2, &x3));
+            const fnn_handle::SortSlot& grp = lead[i]->slot[lead[i]->cur];
+            have_next[m] = on_stream(h, st, [&] { return BY_PREC_RC(h, fill_group_arg, (h, grp, ids, y, B, mask1[m], mask2[m], p_out ? p_out[m] : nullptr,
+                                                                 pack ? pack + m : nullptr, a + (pos + i) * h0->step_ring.elem, &x2, &x3)); });
             L.nmlp = h->pend_Ba / 16; L.x2 = std::max(L.x2, x2); L.x3 = std::max(L.x3, x3);
         }
         launches.push_back(L);
@@ -1996,6 +2014,20 @@ int fnn_train_step_multi(fnn_handle* const* hs, int n_models, const int32_t* ids
         return g.refuse(FNN_ERR_RANGE, "feature id outside [-1, n_rows) in model(s) " + bad);
     }
     return FNN_OK;
+}
+
+int fnn_train_step_multi(fnn_handle* const* hs, int n_models, const int32_t* ids, const float* y, int B,
+                         const uint8_t* const* mask1, const uint8_t* const* mask2, int b_size,
+                         const int32_t* next_ids, int next_B, float* const* p_out, float* loss_sum_out)
+{
+    return train_step_group("fnn_train_step_multi", false, hs, n_models, ids, y, B, mask1, mask2, b_size, next_ids, next_B, p_out, loss_sum_out);
+}
+
+int fnn_bag_train_step_multi(fnn_handle* const* hs, int n_models, const int32_t* ids, const float* y, int B,
+                             const uint8_t* const* mask1, const uint8_t* const* mask2, int b_size,
+                             const int32_t* next_ids, int next_B, float* const* p_out, float* loss_sum_out)
+{
+    return train_step_group("fnn_bag_train_step_multi", true, hs, n_models, ids, y, B, mask1, mask2, b_size, next_ids, next_B, p_out, loss_sum_out);
 }
 
 int fnn_predict(fnn_handle* h, const int32_t* ids, int B, float* p_out, int memkind)

@@ -192,11 +192,11 @@ static __global__ __launch_bounds__(256) void k_step3(const SortArgs so, const T
 }
 
 // ------------------------------------------------------------------------------------------
-// One step of several models on one feed (fnn_train_step_multi): the three launches with the model as blockIdx.y, the
+// One step of several models on one feed (fnn_train_step_multi, fnn_bag_train_step_multi): the three launches with the model as blockIdx.y, the
 // arguments of model y read from a device array, the SAME bodies on them as the solo kernels run.  The models of one launch
 // agree in the kernel and its launch shape (a launch class); a model whose role counts are smaller than the grid's returns.
 // Only the first member of a grouping class carries sort-role blocks (so2 / so3: nblk = 0 on the others), every member's
-// ScatArgs reads that member's rec.
+// ScatArgs reads that member's rec -- and, in bag mode, that member's marks of the rows under several columns (tag_shared / stamp).
 // ------------------------------------------------------------------------------------------
 struct GroupPack { float loss; int flag; };
 template <typename T> struct GroupArg {
@@ -209,7 +209,8 @@ template <typename T> struct GroupArg {
 };
 
 // (a member's owner count is cleared here, before level 1 counts into it: the rank merge clears only the slot it fills)
-template <typename T, int C1, int C2, int CX, int NW, int WTF>
+// BAG: the strips of bag rows (fnn_bag_train_step_multi), what k_step1<..., true, NW> runs for each member alone
+template <typename T, int C1, int C2, int CX, int NW, int WTF, bool BAG = false>
 static __global__ __launch_bounds__(64 * NW) void k_gstep1(const GroupArg<T>* __restrict__ args)
 {
     extern __shared__ __align__(16) unsigned char smem[];
@@ -219,7 +220,7 @@ static __global__ __launch_bounds__(64 * NW) void k_gstep1(const GroupArg<T>* __
     int* const owner_cnt = g.sa.owner_cnt;
     if ((int)blockIdx.x >= nmlp) return;
     if (blockIdx.x == 0 && threadIdx.x == 0) *owner_cnt = 0;
-    mlp_body<T, C1, C2, CX, false, NW, WTF>(a, blockIdx.x, smem);
+    mlp_body<T, C1, C2, CX, BAG, NW, WTF>(a, blockIdx.x, smem);
 }
 
 // (the grid's x extent is a multiple of 8, so that a model's blocks start on the XCD the solo launch's start on and the

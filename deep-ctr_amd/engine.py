@@ -435,17 +435,20 @@ class FNNEngine(object):
 
 
 def _group_call(engines, *args):
-    """fnn_train_step_multi on the engines' handles: every engine's stream joins the caller's, the refusal is engines[0]'s."""
+    """fnn_train_step_multi on the engines' handles (a list of bag engines: fnn_bag_train_step_multi; a mixed list gets
+    fnn_train_step_multi's refusal): every engine's stream joins the caller's, the refusal is engines[0]'s."""
     lib = engines[0].lib
     hs = (C.c_void_p * len(engines))(*[e.h.value for e in engines])
-    rc = lib.fnn_train_step_multi(hs, len(engines), *args)
+    call = lib.fnn_bag_train_step_multi if all(e.bag for e in engines) else lib.fnn_train_step_multi
+    rc = call(hs, len(engines), *args)
     if rc != 0:
         raise FNNError(rc, (lib.fnn_last_error(engines[0].h) or b'').decode())
 
 
 def train_step_many(engines, ids, y, masks1, masks2, b_size=0, next_ids=None, want_p=False, want_loss=True):
     """One train_step of every engine of a list on ONE feed, in one call (fnn_train_step_multi): engine m ends bit for bit as
-    engines[m].train_step(ids, y, masks1[m], masks2[m], b_size) alone would have left it.  next_ids: the device int32 tensor
+    engines[m].train_step(ids, y, masks1[m], masks2[m], b_size) alone would have left it (bag engines, the SNN fine-tune: through
+    fnn_bag_train_step_multi, and to the rounding of the float atomics on a row that two columns of the batch hold).  next_ids: the device int32 tensor
     of the NEXT call's ids (grouped during this one; a scheduling hint).  Returns a list of dicts shaped like train_step's:
     'loss' (float), 'p' [B]."""
     e0 = engines[0]
@@ -486,8 +489,10 @@ def train_epoch_many(engines, ids_d, yf_d, batch_size, masks1, masks2, first=0, 
     """FNNEngine.train_epoch's loop for a list of engines on one resident feed: masks1[m] [n, H1 of m] / masks2[m] [n, H2 of m]
     are engine m's dropout rows, every batch is ONE fnn_train_step_multi call with the next batch announced through next_ids.
     A batch with shadowed features (or longer than 4096) runs as solo steps of every engine, fnn_set_shadowed + fnn_train_step,
-    which the group call refuses: every engine's trajectory is that of its own train_epoch."""
+    which the group call refuses: every engine's trajectory is that of its own train_epoch.  Bag engines (SNN fine-tune) step
+    through fnn_bag_train_step_multi and have no shadowed features: `shadowed` must be None for them."""
     e0 = engines[0]
+    assert shadowed is None or not any(e.bag for e in engines), "shadowed features: FNN_MODE_FM only"
     torch = e0._torch
     M = len(engines)
     assert ids_d.is_cuda and ids_d.dtype == torch.int32 and ids_d.is_contiguous() and yf_d.is_cuda and yf_d.dtype == torch.float32

@@ -216,6 +216,28 @@ int fnn_train_step_multi(fnn_handle* const* hs, int n_models, const int32_t* ids
                          const uint8_t* const* mask1, const uint8_t* const* mask2, int b_size,
                          const int32_t* next_ids, int next_B, float* const* p_out, float* loss_sum_out);
 
+/* fnn_train_step_multi for FNN_MODE_BAG handles (the SNN fine-tune: one model per lr / dropout / lambda1 on the same pre-trained
+ * weights).  An entry point of its own because fnn_train_step_multi's refusal of a bag handle is part of its contract; the
+ * arguments, the limit FNN_STEP_MAX_MODELS, launch classes and grouping classes, next_ids, streams, n_models == 1, the loss
+ * packing and the per-model range flags are fnn_train_step_multi's -- the two are one body.  ids [B, F] holds a line's active
+ * features in line order, -1 where it has fewer than F.
+ *
+ * Accepted: the handles for which fnn_train_step trains a bag handle -- FNN_MODE_BAG on the strip kernel (h0 192..316 with the
+ * hidden sizes it is built for), B <= 4096.  A launch class is further told by h0 and n_fields; key width and sort runs choose
+ * the kernels of launches 2 and 3, so the members of a class agree in them.
+ *
+ * Model m ends as fnn_train_step(hs[m], ...) alone would have left it: BIT FOR BIT where no row lies under two columns of the
+ * batch.  A row that does is added into with float atomics by each of its columns, in the group call as in the solo step, so
+ * there both agree to the rounding of those additions and neither is reproducible to the bit.  The members of equal n_rows share
+ * the first one's grouping WITH its marks of such rows (the marks and their stamp belong to a grouping, not to a handle).
+ *
+ * A refused call launches nothing and writes nothing; its message starts with "fnn_bag_train_step_multi:" and names the model's
+ * index.  FNN_ERR_ARG: as fnn_train_step_multi, with "a FNN_MODE_FM handle" in the place of "a bag-mode handle" (no wide rows,
+ * no shadowed features in bag mode).  FNN_ERR_STATE and FNN_ERR_RANGE: as fnn_train_step_multi. */
+int fnn_bag_train_step_multi(fnn_handle* const* hs, int n_models, const int32_t* ids, const float* y, int B,
+                             const uint8_t* const* mask1, const uint8_t* const* mask2, int b_size,
+                             const int32_t* next_ids, int next_B, float* const* p_out, float* loss_sum_out);
+
 /* ---- Data parallelism (new: the reference has no distributed code).  One process per GPU; the global batch is cut into
  * contiguous shards; the loss is a batch SUM (python/FNN_wnzh.py:173), so the dense gradients of the shards add up exactly and
  * ONE collective per step is the whole exchange.  Tables are replicated.
