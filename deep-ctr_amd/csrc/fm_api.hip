@@ -11,12 +11,16 @@
 // a device array (k_fm_multi, k_fm_wide_multi), and the metric pass of metrics.hip with a model dimension (metrics_multi).
 // Several models, one mini-batch step (fm_train_step_multi): the models that agree in n_rows and the shared-rows mode share the
 // batch's run sort and rank merge, and the step's bodies run once per layout present with the model as a grid dimension (k_fm_step_*).
+// This file is the host half of the unit: the handle, the dispatch ladder, the calls and the C ABI.  The kernels are in
+// fm_kernels.hip.h (solo) and fm_group_kernels.hip.h (group forms), fm_online.hip.h (the online schedule); what n_fields and k
+// decide about them is the handle's FmPlan (fm_plan.h, free of HIP), computed once in fm_create.
 #include <hip/hip_runtime.h>
 
 #include <algorithm>
 #include <cmath>
 #include <cstring>
 #include <string>
+#include <type_traits>
 #include <vector>
 
 #include "../../include/fm_hip.h"
@@ -25,6 +29,9 @@
 #include "metrics.hip.h"
 #include "optim.hip.h"
 #include "fm_online.hip.h"
+#include "fm_plan.h"
+#include "fm_kernels.hip.h"
+#include "fm_group_kernels.hip.h"
 #include "arg_ring.h"
 #include "group_call.h"
 
@@ -34,559 +41,17 @@ namespace {
 
 thread_local std::string g_fm_err;
 inline int rup(int x, int m) { return (x + m - 1) / m * m; }
-
-// 16 lanes per example: lane f owns fields f, f + 16, .. (NF = ceil(F / 16) of them; NF = 1 up to 16 fields, lane = field) and
-// loads their 64-byte rows, sums them in registers, and the field sums S_l = sum_f v_f[l] are 4-step shuffle reductions inside
-// the 16-lane group.
-struct FmArgs {
-    const int32_t* ids; const float* y; int B, F, K; const float* table16; int64_t n_rows; const float* b;
-    float scale, dscale; int train; float* gxp; int K1p; float* p_out; float* loss_t; float* gb_part; int* err;
-    bool wt;                   // gx' written through (see store4_wt in fnn_kernels.hip.h)
-    int* stamp; int step;      // Adam / FTRL: stamp[row] = step for every row the batch touches (null: not kept)
-    int rw;                    // wide rows (fm_wide_body): the row stride in floats, a multiple of 4; gx' is [t][F][rw]
-    const float* wts;          // value weights [B, F] beside ids (the WV = true kernels), or null: every value is 1
-};
-
-// store16_sel and the two wait states gfx950 needs before a VALU instruction may overwrite the data VGPRs of a store wider than 8
-// bytes: the compiler provides them after its own stores, not after store16_wt's inline assembly.  With several fields per lane the
-// next field's gradients are computed into the registers the previous store reads (NF = 1 stores last: store16_sel as it was;
-// every weighted kernel, WV = true, stores through this one).
-__device__ __forceinline__ void store16_sel_ws(const bool wt, float* p, const float4 v)
-{
-    u32x4 w; __builtin_memcpy(&w, &v, 16);
-    if (wt) asm volatile("global_store_dwordx4 %0, %1, off sc1\n\ts_nop 1" :: "v"(p), "v"(w) : "memory");
-    else *reinterpret_cast<u32x4*>(p) = w;
-}
-// WV: value weights (python/FM.py:24-29's sp_wt_hldr).  x = wts[t][fld] is loaded beside the id, the row enters as e = x * row, and
-// lin, S and sq follow from e as they did from the row; d yhat / d w_f = x, d yhat / d v_f[l] = x (S_l - e_f[l]).  The weight of
-// an absent field or of a padding example is replaced by 0 (its row by zeros), so that no value there, NaN included, reaches e.
-template <int NF, bool WV>
-__device__ __forceinline__ void fm_body(const FmArgs& a, const int blk, float* s_gb)
-{
-    const int tid = threadIdx.x, f = tid & 15, grp = tid >> 4;
-    const int t = blk * 16 + grp;
-    int64_t id[NF];
-    float x[NF];
-#pragma unroll
-    for (int n = 0; n < NF; ++n) {                          // every id first: the row loads below do not wait behind a stamp
-        const int fld = f + 16 * n;
-        id[n] = -1;
-        x[n] = 0.f;
-        if (t < a.B && fld < a.F) {
-            id[n] = a.ids[(size_t)t * a.F + fld];
-            if (WV) x[n] = a.wts[(size_t)t * a.F + fld];    // in the id's round trip
-            if (id[n] < -1 || id[n] >= a.n_rows) { atomicOr(a.err, 1); id[n] = -1; }
-            if (a.stamp && id[n] >= 0) a.stamp[id[n]] = a.step;
-            if (WV && id[n] < 0) x[n] = 0.f;
-        }
-    }
-    float r[NF][16];
-#pragma unroll
-    for (int n = 0; n < NF; ++n) {
-#pragma unroll
-        for (int q = 0; q < 4; ++q) {
-            float4 v = make_float4(0.f, 0.f, 0.f, 0.f);
-            if (id[n] >= 0) v = *reinterpret_cast<const float4*>(a.table16 + (size_t)id[n] * SLOT + 4 * q);
-            r[n][4 * q] = v.x * a.scale; r[n][4 * q + 1] = v.y * a.scale; r[n][4 * q + 2] = v.z * a.scale; r[n][4 * q + 3] = v.w * a.scale;
-            if (WV) { r[n][4 * q] *= x[n]; r[n][4 * q + 1] *= x[n]; r[n][4 * q + 2] *= x[n]; r[n][4 * q + 3] *= x[n]; }
-        }
-    }
-    // yhat = b + sum_f w_f + 1/2 (sum_l S_l^2 - sum_f sum_l v_f[l]^2)                     (:56-63)
-    float lin = r[0][0], sq = 0.f, S[16];
-#pragma unroll
-    for (int l = 1; l < 16; ++l) { S[l] = r[0][l]; sq = fmaf(r[0][l], r[0][l], sq); }
-#pragma unroll
-    for (int n = 1; n < NF; ++n) {                          // the lane's further fields, in field order
-        lin += r[n][0];
-#pragma unroll
-        for (int l = 1; l < 16; ++l) { S[l] += r[n][l]; sq = fmaf(r[n][l], r[n][l], sq); }
-    }
-#pragma unroll
-    for (int o = 1; o < 16; o <<= 1) {
-        lin += __shfl_xor(lin, o, 16); sq += __shfl_xor(sq, o, 16);
-#pragma unroll
-        for (int l = 1; l < 16; ++l) S[l] += __shfl_xor(S[l], o, 16);
-    }
-    float ss = 0.f;
-#pragma unroll
-    for (int l = 1; l < 16; ++l) ss = fmaf(S[l], S[l], ss);
-    const float z = *a.b + lin + 0.5f * (ss - sq);
-    const float p = 1.0f / (1.0f + expf(-z));
-    float delta = 0.f;
-    if (t < a.B) {
-        if (a.p_out && f == 0) a.p_out[t] = p;
-        if (a.train) {
-            const float yy = a.y[t];
-            delta = (p - yy) * a.dscale;                         // dscale = 1 (sum) or 1/B (mean)
-            if (f == 0) a.loss_t[t] = fmaxf(z, 0.f) - z * yy + log1pf(expf(-fabsf(z)));
-        }
-    } else if (a.train && f == 0) a.loss_t[t] = 0.f;
-    if (!a.train) return;
-    // d yhat / d w_f = x_f ; d yhat / d v_f[l] = x_f (S_l - e_f[l])   (WV = false: x = 1)
-#pragma unroll
-    for (int n = 0; n < NF; ++n) {
-        const int fld = f + 16 * n;
-        const float dx = WV ? delta * x[n] : delta;
-        float g[16];
-        g[0] = (id[n] >= 0) ? dx : 0.f;
-#pragma unroll
-        for (int l = 1; l < 16; ++l) g[l] = (id[n] >= 0 && l < a.K) ? dx * (S[l] - r[n][l]) : 0.f;
-        float* out = a.gxp + (size_t)t * a.K1p + fld * SLOT;    // K1p = rup(F, 16) * SLOT
-        if (fld < a.F) {
-#pragma unroll
-            for (int q = 0; q < 4; ++q) {                   // (written through: FM_WT=0 for plain stores)
-                const float4 g4 = make_float4(g[4 * q], g[4 * q + 1], g[4 * q + 2], g[4 * q + 3]);
-                if (NF == 1 && !WV) store16_sel(a.wt, out + 4 * q, g4);
-                else store16_sel_ws(a.wt, out + 4 * q, g4);
-            }
-        }
-    }
-    if (f == 0) s_gb[grp] = delta;
-    __syncthreads();
-    if (tid == 0) { float s = 0.f; for (int i = 0; i < 16; ++i) s += s_gb[i]; a.gb_part[blk] = s; }
-}
-template <int NF, bool WV>
-__global__ __launch_bounds__(256) void k_fm(const FmArgs a)
-{
-    __shared__ float s_gb[16];
-    fm_body<NF, WV>(a, blockIdx.x, s_gb);
-}
-// Wide rows (k >= 17): L lanes per example (16 while the row's rw / 4 float4 pieces fit, else 32); lane q owns columns 4q..4q+3
-// of every field's row and issues its example's row loads 16 fields at a time, so that S_l = sum_f v_f[l] is a register sum and
-// only the example's scalar b + lin + 1/2 sum_l (S_l^2 - sum_f v_f[l]^2) crosses lanes.  Lane q reads, checks and stamps the ids
-// of fields q, q + L, .. (< F).  gx'[t][f] = delta * [1 | S - v_f], zero in the padding columns (>= K); absent fields are not
-// written (no record points at them).  More than 16 fields (NC = ceil(F / 16) chunks of 16): a rolled first pass sums every
-// chunk, the second reloads each chunk's rows and writes its gradients (holding the last chunk across the passes cost 30-40
-// VGPRs and an occupancy step).  NC = 1, up to 16 fields: the gradients from the rows still in registers, nothing reloaded.
-// WV (value weights, as in fm_body): lane q keeps the weights of its fields beside their ids (0 where the id is absent), a chunk's
-// weights x[16] are shuffled out with its ids, and the rows enter as e = (scale x) row in BOTH passes -- the second pass has to
-// reproduce the first pass's e bit for bit; x[] lives across one chunk only.
-template <int L, int NR, bool WV>
-__device__ __forceinline__ void fm_wide_chunk(const FmArgs& a, const int (&mine)[NR], const float (&minex)[NR], const int c, const int q,
-                                              const int nq, int (&id)[16], float (&x)[16], float4 (&v)[16])
-{
-    // fields 16 c .. 16 c + 15 lie in one round of ids (L = 16 or 32): round 16 c / L, lanes 16 c % L + f
-    int m = mine[0];
-    float mx = minex[0];
-#pragma unroll
-    for (int r = 1; r < NR; ++r) { m = (r == 16 * c / L) ? mine[r] : m; if (WV) mx = (r == 16 * c / L) ? minex[r] : mx; }
-#pragma unroll
-    for (int f = 0; f < 16; ++f) {
-        id[f] = __shfl(m, 16 * c % L + f, L);             // -1 for fields >= F
-        if (WV) x[f] = __shfl(mx, 16 * c % L + f, L);     // 0 where the id is -1
-        v[f] = (id[f] >= 0 && q < nq) ? *reinterpret_cast<const float4*>(a.table16 + (size_t)id[f] * a.rw + 4 * q)
-                                      : make_float4(0.f, 0.f, 0.f, 0.f);
-    }
-}
-template <bool WV>
-__device__ __forceinline__ void fm_wide_grads(const FmArgs& a, float* out, const int c, const int (&id)[16], const float (&x)[16],
-                                              const float4 (&v)[16], const float4 S, const float delta)
-{
-#pragma unroll
-    for (int f = 0; f < 16; ++f) {
-        if (id[f] < 0) continue;
-        const float dx = WV ? delta * x[f] : delta;
-        const float4 g = make_float4(c == 0 ? dx : (c < a.K ? dx * (S.x - v[f].x) : 0.f),
-                                     c + 1 < a.K ? dx * (S.y - v[f].y) : 0.f,
-                                     c + 2 < a.K ? dx * (S.z - v[f].z) : 0.f,
-                                     c + 3 < a.K ? dx * (S.w - v[f].w) : 0.f);
-        if (WV) store16_sel_ws(a.wt, out + (size_t)f * a.rw, g);
-        else store16_sel(a.wt, out + (size_t)f * a.rw, g);
-    }
-}
-template <int L, int NC, bool WV>
-__device__ __forceinline__ void fm_wide_body(const FmArgs& a, const int blk, float* s_gb /*[256 / L]*/)
-{
-    constexpr int EPB = 256 / L;                          // examples per workgroup
-    constexpr int NR = (16 * NC + L - 1) / L;             // id rounds: lane q holds the ids of fields q, q + L, ..
-    const int tid = threadIdx.x, q = tid % L, grp = tid / L, nq = a.rw >> 2;
-    const int t = blk * EPB + grp;
-    int mine[NR];
-    float minex[NR];
-#pragma unroll
-    for (int r = 0; r < NR; ++r) {
-        const int fld = q + r * L;
-        mine[r] = -1;
-        minex[r] = 0.f;
-        if (t < a.B && fld < a.F) {
-            const int64_t id = a.ids[(size_t)t * a.F + fld];
-            float w = 0.f;
-            if (WV) w = a.wts[(size_t)t * a.F + fld];       // in the id's round trip
-            if (id < -1 || id >= a.n_rows) atomicOr(a.err, 1);
-            else mine[r] = (int)id;
-            if (a.stamp && mine[r] >= 0) a.stamp[mine[r]] = a.step;
-            if (WV && mine[r] >= 0) minex[r] = w;
-        }
-    }
-    int id[16];
-    float x[16];
-    float4 v[16];
-    float lin = 0.f;
-    float4 S = make_float4(0.f, 0.f, 0.f, 0.f), sq = S;
-#pragma unroll 1
-    for (int c = 0; c < NC; ++c) {                        // rolled: one chunk's 16 rows in registers at a time
-        fm_wide_chunk<L, NR, WV>(a, mine, minex, c, q, nq, id, x, v);
-#pragma unroll
-        for (int f = 0; f < 16; ++f) {
-            const float s = WV ? a.scale * x[f] : a.scale;    // e = (scale x) row
-            v[f].x *= s; v[f].y *= s; v[f].z *= s; v[f].w *= s;
-            if (q == 0) { lin += v[f].x; v[f].x = 0.f; }      // column 0 is w_f
-            S.x += v[f].x; S.y += v[f].y; S.z += v[f].z; S.w += v[f].w;
-            sq.x = fmaf(v[f].x, v[f].x, sq.x); sq.y = fmaf(v[f].y, v[f].y, sq.y);
-            sq.z = fmaf(v[f].z, v[f].z, sq.z); sq.w = fmaf(v[f].w, v[f].w, sq.w);
-        }
-    }
-    // yhat = b + sum_f w_f + 1/2 (sum_l S_l^2 - sum_f sum_l v_f[l]^2)                     (:56-63)
-    float part = lin + 0.5f * ((fmaf(S.x, S.x, -sq.x) + fmaf(S.y, S.y, -sq.y)) + (fmaf(S.z, S.z, -sq.z) + fmaf(S.w, S.w, -sq.w)));
-#pragma unroll
-    for (int o = 1; o < L; o <<= 1) part += __shfl_xor(part, o, L);
-    const float z = *a.b + part;
-    const float p = 1.0f / (1.0f + expf(-z));
-    float delta = 0.f;
-    if (t < a.B) {
-        if (a.p_out && q == 0) a.p_out[t] = p;
-        if (a.train) {
-            const float yy = a.y[t];
-            delta = (p - yy) * a.dscale;                         // dscale = 1 (sum) or 1/B (mean)
-            if (q == 0) a.loss_t[t] = fmaxf(z, 0.f) - z * yy + log1pf(expf(-fabsf(z)));
-        }
-    } else if (a.train && q == 0) a.loss_t[t] = 0.f;
-    if (!a.train) return;
-    // d yhat / d w_f = x_f ; d yhat / d v_f[l] = x_f (S_l - e_f[l])   (WV = false: x = 1)
-    float* out = a.gxp + (size_t)t * a.K1p + 4 * q;
-    if (NC == 1) {                                        // up to 16 fields: the rows are still in registers
-        if (q < nq) fm_wide_grads<WV>(a, out, 4 * q, id, x, v, S, delta);
-    } else {
-#pragma unroll 1
-        for (int c = 0; c < NC; ++c) {                    // every chunk's rows again (the shuffles with the whole group)
-            fm_wide_chunk<L, NR, WV>(a, mine, minex, c, q, nq, id, x, v);
-#pragma unroll
-            for (int f = 0; f < 16; ++f) {
-                const float s = WV ? a.scale * x[f] : a.scale;
-                v[f].x *= s; v[f].y *= s; v[f].z *= s; v[f].w *= s;
-            }
-            if (q < nq) fm_wide_grads<WV>(a, out + (size_t)(16 * c) * a.rw, 4 * q, id, x, v, S, delta);
-        }
-    }
-    if (q == 0) s_gb[grp] = delta;
-    __syncthreads();
-    if (tid == 0) { float s = 0.f; for (int i = 0; i < EPB; ++i) s += s_gb[i]; a.gb_part[blk] = s; }
-}
-template <int L, int NC, bool WV>
-__global__ __launch_bounds__(256) void k_fm_wide(const FmArgs a)
-{
-    __shared__ float s_gb[256 / L];
-    fm_wide_body<L, NC, WV>(a, blockIdx.x, s_gb);
-}
-template <typename KT, int L, int NC, bool WV>
-__global__ __launch_bounds__(256) void k_fm_wide_merge_fwd(const SortArgs so, const FmArgs a)
-{
-    extern __shared__ __align__(16) unsigned char smem[];
-    __shared__ float s_gb[256 / L];
-    if ((int)blockIdx.x < so.nblk) { sortB_body<KT>(so, blockIdx.x, smem); return; }
-    fm_wide_body<L, NC, WV>(a, (int)blockIdx.x - so.nblk, s_gb);
-}
-
-// Predictions of several models on one feed (fm_predict_multi, fm_eval_multi): the forward bodies above with train = 0, the
-// arguments of model m read from a device array instead of the kernel's own (k_fm_online_multi's way), so p is bit for bit what
-// k_fm / k_fm_wide write for that model: an example's p depends on its own lines and rows only, not on the batch around it.
-// One launch per layout class present in a call (narrow; wide at 16 lanes an example; wide at 32), so that the narrow models do
-// not run at the wide bodies' register count: cls[0 .. nm) lists the class's models as indices into args.  The grid is the
-// (model, example tile) pairs flattened over x and y; model_fast: neighbouring workgroups take the same tile of different
-// models (the feed's lines are shared, the tables are not), else a model's tiles are neighbours (one table at a time).
-struct EvalArg { FmArgs a; int cls; };
-__device__ __forceinline__ bool eval_pick(const EvalArg* __restrict__ args, const int first, const int nm, const int64_t tiles,
-                                          const int model_fast, int& m, int& tile)
-{
-    const int64_t lin = (int64_t)blockIdx.y * gridDim.x + blockIdx.x;
-    if (lin >= tiles * nm) return false;
-    const int64_t j = model_fast ? lin % nm : lin / tiles;
-    tile = (int)(model_fast ? lin / nm : lin % tiles);
-    m = args[first + j].cls;
-    return true;
-}
-template <int NF, bool WV>
-__global__ __launch_bounds__(256) void k_fm_multi(const EvalArg* __restrict__ args, const int first, const int nm, const int64_t tiles,
-                                                  const int model_fast)
-{
-    __shared__ float s_gb[16];
-    int m, tile;
-    if (!eval_pick(args, first, nm, tiles, model_fast, m, tile)) return;
-    const FmArgs a = args[m].a;
-    fm_body<NF, WV>(a, tile, s_gb);
-}
-template <int L, int NC, bool WV>
-__global__ __launch_bounds__(256) void k_fm_wide_multi(const EvalArg* __restrict__ args, const int first, const int nm, const int64_t tiles,
-                                                       const int model_fast)
-{
-    __shared__ float s_gb[256 / L];
-    int m, tile;
-    if (!eval_pick(args, first, nm, tiles, model_fast, m, tile)) return;
-    const FmArgs a = args[m].a;
-    fm_wide_body<L, NC, WV>(a, tile, s_gb);
-}
-// fm_eval_multi: the range flags of a group's models, read and then cleared where set (fm_sync's rule); one workgroup, so that a
-// handle listed twice shows its flag in both places before either clears it.
-__global__ __launch_bounds__(256) void k_fm_eval_flags(const EvalArg* __restrict__ args, const int n, int* __restrict__ flags)
-{
-    for (int i = threadIdx.x; i < n; i += 256) flags[i] = *static_cast<volatile int*>(args[i].a.err);
-    __syncthreads();
-    for (int i = threadIdx.x; i < n; i += 256) if (flags[i]) *args[i].a.err = 0;
-}
-
-// A training step is four launches: run sorts of the batch's (row, t) keys; their rank merge BESIDE the forward + gradients
-// (both need only the ids: the merge takes 16 F workgroups, the examples the rest); level-1 sparse-row update; level-2 update
-// BESIDE the bias / loss tail.  As six launches in a row (sort, sort, forward, scatter, scatter, tail) the step took 49.6 us.
-template <typename KT, int NF, bool WV>
-__global__ __launch_bounds__(256) void k_fm_merge_fwd(const SortArgs so, const FmArgs a)
-{
-    extern __shared__ __align__(16) unsigned char smem[];
-    __shared__ float s_gb[16];
-    if ((int)blockIdx.x < so.nblk) { sortB_body<KT>(so, blockIdx.x, smem); return; }
-    fm_body<NF, WV>(a, (int)blockIdx.x - so.nblk, s_gb);
-}
-
-// The bias under Adam / FTRL: the state beside it (sb [2]) and this step's learning rate (Adam: lr_t).  opt = 0: SGD.
-struct FmBiasOpt { int opt; float* sb; float lr, b1, b2, eps; };
-__device__ __forceinline__ float fm_opt_step(int opt, float w, float g, float& s0, float& s1, float lr, float b1, float b2, float eps) {
-    return opt == FM_OPT_FTRL ? ftrl_step(w, g, s0, s1, lr) : adam_step(w, g, s0, s1, lr, b1, b2, eps);
-}
-
-// b <- b (1 - lr lambda) - lr sum(delta) (Adam / FTRL: the optimiser on g = sum(delta) + lambda b); loss sum (fixed-shape tree)
-__device__ __forceinline__ void fm_tail_body(float* b, const float* gb_part, int n, float lr, float lambda, const float* loss_t, int Ba, float lscale,
-                                             float* loss_out, float* sl, const FmBiasOpt& bo)
-{   // both sums as 256 strided partial sums and a fixed-shape tree (one thread walking the n partials paid a memory round trip
-    // per element: 19 us for 256 of them)
-    float v = strided_sum256(gb_part, n);
-    sl[threadIdx.x] = v; __syncthreads();
-    for (int o = 128; o > 0; o >>= 1) { if ((int)threadIdx.x < o) sl[threadIdx.x] += sl[threadIdx.x + o]; __syncthreads(); }
-    const float gsum = sl[0];
-    __syncthreads();
-    v = strided_sum256(loss_t, Ba);
-    sl[threadIdx.x] = v; __syncthreads();
-    for (int o = 128; o > 0; o >>= 1) { if ((int)threadIdx.x < o) sl[threadIdx.x] += sl[threadIdx.x + o]; __syncthreads(); }
-    if (threadIdx.x == 0) {
-        if (bo.opt) *b = fm_opt_step(bo.opt, *b, gsum + lambda * *b, bo.sb[0], bo.sb[1], bo.lr, bo.b1, bo.b2, bo.eps);
-        else *b = *b * (1.0f - lr * lambda) - lr * gsum;
-        *loss_out = sl[0] * lscale;
-    }
-}
-__global__ __launch_bounds__(256) void k_fm_scat2_tail(const ScatArgs sa, float* b, const float* gb_part, int n, float lr, float lambda,
-                                                       const float* loss_t, int Ba, float lscale, float* loss_out, const FmBiasOpt bo)
-{
-    __shared__ double s_sum[16][16];
-    if (blockIdx.x == 0) { fm_tail_body(b, gb_part, n, lr, lambda, loss_t, Ba, lscale, loss_out, reinterpret_cast<float*>(&s_sum[0][0]), bo); return; }
-    if (sa.form2 == SCAT2_WAVE) scat2w_body(sa, (int)blockIdx.x - 1, (int)gridDim.x - 1);
-    else scat2_body(sa, (int)blockIdx.x - 1, (int)gridDim.x - 1, s_sum);
-}
-// Shared rows (fm_set_shared_rows): the half-chunk level 1 and the wave-per-segment level 2 in their SHARED forms, whatever
-// FNN_SCAT1_FORM / FNN_SCAT2_FORM say -- rows the rank merge marked (SortArgs::tag_shared) take float atomics, the others the
-// stores of k_scat1 / k_fm_scat2_tail.  FM only: the FNN step's and the inner-product family's columns are fields.
-__global__ __launch_bounds__(256) void k_fm_scat1s(const ScatArgs sa) { scat1h_form<true>(sa, blockIdx.x); }
-__global__ __launch_bounds__(256) void k_fm_scat2s_tail(const ScatArgs sa, float* b, const float* gb_part, int n, float lr, float lambda,
-                                                        const float* loss_t, int Ba, float lscale, float* loss_out, const FmBiasOpt bo)
-{
-    __shared__ float s_l[256];
-    if (blockIdx.x == 0) { fm_tail_body(b, gb_part, n, lr, lambda, loss_t, Ba, lscale, loss_out, s_l, bo); return; }
-    scat2w_form<true>(sa, (int)blockIdx.x - 1, (int)gridDim.x - 1);
-}
-// fm_count_shared_rows: the rows the last step's rank merge marked
-__global__ __launch_bounds__(256) void k_fm_count_marks(const int* __restrict__ tag_shared, int64_t n_rows, int stamp, unsigned long long* out)
-{
-    __shared__ int s_c[256];
-    int c = 0;
-    for (int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x; i < n_rows; i += (int64_t)gridDim.x * 256) c += tag_shared[i] == stamp;
-    s_c[threadIdx.x] = c; __syncthreads();
-    for (int o = 128; o > 0; o >>= 1) { if ((int)threadIdx.x < o) s_c[threadIdx.x] += s_c[threadIdx.x + o]; __syncthreads(); }
-    if (threadIdx.x == 0 && s_c[0]) atomicAdd(out, (unsigned long long)s_c[0]);
-}
-// the same for wide rows: level 1 on its own, level 2 (8 KiB of LDS) beside the tail
-__global__ __launch_bounds__(256) void k_fm_scatw1(const ScatArgs sa) { scatw1_body(sa, blockIdx.x); }
-__global__ __launch_bounds__(256) void k_fm_scatw2_tail(const ScatArgs sa, float* b, const float* gb_part, int n, float lr, float lambda,
-                                                        const float* loss_t, int Ba, float lscale, float* loss_out, const FmBiasOpt bo)
-{
-    __shared__ double s_w[1024];
-    if (blockIdx.x == 0) { fm_tail_body(b, gb_part, n, lr, lambda, loss_t, Ba, lscale, loss_out, reinterpret_cast<float*>(s_w), bo); return; }
-    scatw2_body(sa, (int)blockIdx.x - 1, (int)gridDim.x - 1, s_w);
-}
-
-// One mini-batch step of several models on one feed (fm_train_step_multi): the bodies above, the arguments of model m read from a
-// device array (k_fm_multi's way), the model a grid dimension.  The grouping -- run sort and rank merge -- depends on the ids,
-// n_rows and the shared-rows mode only, so the models that agree in those (a grouping CLASS) share one: every model's update reads
-// the class's rec (and shared-row marks) with its own part / owners / owner_cnt, gx', table and scale.
-//   launch 1  the run sort of a class (k_sortA), as the solo step's
-//   launch 2  k_fm_step_fwd / k_fm_step_fwd_wide, one per layout present: the classes' rank merges (16 F workgroups each, in the
-//             first such launch) beside the forward + gradients of every (model, example tile) of the layout
-//   launch 3  k_fm_step_scat1 / k_fm_step_scatw1: level 1, grid (workgroups of the largest model, models)
-//   launch 4  k_fm_step_scat2_tail / k_fm_step_scatw2_tail: per model the bias / loss tail and 256 level-2 workgroups
-// The narrow rows take the half-chunk level 1 and the wave level 2 whatever FNN_SCAT1_FORM / FNN_SCAT2_FORM say: every form
-// gives the same bits (tests/test_gpu_scat1_half.py, test_gpu_scat2_forms.py).
-struct StepTail { float* b; const float* gb_part; int n; float lr, lambda; const float* loss_t; int Ba; float lscale; float* loss_out; FmBiasOpt bo; };
-struct StepPack { float loss; int flag; };
-struct StepArg {
-    FmArgs a; ScatArgs sa; StepTail t;
-    // a shared-rows model that is not its class's first: the class's marks (sa.tag_shared, sa.stamp) are copied into its own
-    // array under its own stamp (null: nothing to copy) -- what fm_count_shared_rows scans for this handle
-    int* own_marks; int own_stamp;
-    StepPack* pack;            // the call's loss and range flag of this model, for one copy to the host (null: not asked)
-    int nb1;                   // level-1 workgroups of this model
-    int fcls, scls;            // entry j: the j-th model in forward-layout order / in update-form order (indices into the array)
-    SortArgs so;               // entry c: the rank merge of the call's c-th grouping class
-};
-// launch 2.  Workgroups [0, ncls * mblk): class b / mblk's rank merge (mblk = 16 F); then the (model, tile) pairs, a model's tiles
-// neighbours as in the solo step.  A model's tile 0 clears its owner count (sortB_body clears the class's: the first model's).
-__device__ __forceinline__ void step_pick(const StepArg* __restrict__ args, const int ncls, const int mblk, const int first, const int tiles,
-                                          int& m, int& tile)
-{
-    const int lin = (int)blockIdx.x - ncls * mblk;
-    m = args[first + lin / tiles].fcls;
-    tile = lin % tiles;
-    if (tile == 0 && threadIdx.x == 0) *args[m].sa.owner_cnt = 0;
-}
-template <typename KT, int NF, bool WV>
-__global__ __launch_bounds__(256) void k_fm_step_fwd(const StepArg* __restrict__ args, const int ncls, const int mblk, const int first,
-                                                     const int tiles)
-{
-    extern __shared__ __align__(16) unsigned char smem[];
-    __shared__ float s_gb[16];
-    if ((int)blockIdx.x < ncls * mblk) { const SortArgs so = args[(int)blockIdx.x / mblk].so; sortB_body<KT>(so, (int)blockIdx.x % mblk, smem); return; }
-    int m, tile;
-    step_pick(args, ncls, mblk, first, tiles, m, tile);
-    const FmArgs a = args[m].a;
-    fm_body<NF, WV>(a, tile, s_gb);
-}
-template <typename KT, int L, int NC, bool WV>
-__global__ __launch_bounds__(256) void k_fm_step_fwd_wide(const StepArg* __restrict__ args, const int ncls, const int mblk, const int first,
-                                                          const int tiles)
-{
-    extern __shared__ __align__(16) unsigned char smem[];
-    __shared__ float s_gb[256 / L];
-    if ((int)blockIdx.x < ncls * mblk) { const SortArgs so = args[(int)blockIdx.x / mblk].so; sortB_body<KT>(so, (int)blockIdx.x % mblk, smem); return; }
-    int m, tile;
-    step_pick(args, ncls, mblk, first, tiles, m, tile);
-    const FmArgs a = args[m].a;
-    fm_wide_body<L, NC, WV>(a, tile, s_gb);
-}
-// the class's marks into the model's own array: a segment head whose row the rank merge (a launch earlier) marked
-__device__ __forceinline__ void step_copy_marks(const StepArg& g, const ScatArgs& sa, const int blk, const int nblk)
-{
-    if (!g.own_marks) return;
-    const int n = sa.F * sa.N2;
-    for (int i = blk * 256 + (int)threadIdx.x; i < n; i += nblk * 256) {
-        const int4 r = sa.rec[i];
-        if (r.x >= 0 && (i % sa.N2) == r.z && sa.tag_shared[r.x] == sa.stamp) g.own_marks[r.x] = g.own_stamp;
-    }
-}
-// launch 3: grid (nb1 of the largest model, models of the form)
-template <bool SHARED>
-__global__ __launch_bounds__(256) void k_fm_step_scat1(const StepArg* __restrict__ args, const int first)
-{
-    const int m = args[first + blockIdx.y].scls;
-    const int nb1 = args[m].nb1;
-    if ((int)blockIdx.x >= nb1) return;
-    const ScatArgs sa = args[m].sa;
-    if (SHARED) step_copy_marks(args[m], sa, blockIdx.x, nb1);
-    scat1h_form<SHARED>(sa, blockIdx.x);
-}
-__global__ __launch_bounds__(256) void k_fm_step_scatw1(const StepArg* __restrict__ args, const int first)
-{
-    const int m = args[first + blockIdx.y].scls;
-    const int nb1 = args[m].nb1;
-    if ((int)blockIdx.x >= nb1) return;
-    const ScatArgs sa = args[m].sa;
-    step_copy_marks(args[m], sa, blockIdx.x, nb1);
-    scatw1_body(sa, blockIdx.x);
-}
-// launch 4: grid (1 + 256, models of the form).  The tail's workgroup also hands the model's loss and range flag to the call's
-// packed array (the forwards that raise the flag ran two launches earlier) and clears a raised flag, as fm_sync does.
-__device__ __forceinline__ void step_tail(const StepArg& g, float* sl)
-{
-    const StepTail t = g.t;
-    fm_tail_body(t.b, t.gb_part, t.n, t.lr, t.lambda, t.loss_t, t.Ba, t.lscale, t.loss_out, sl, t.bo);
-    if (threadIdx.x == 0 && g.pack) {
-        const int flag = *static_cast<volatile int*>(g.a.err);
-        g.pack->loss = *t.loss_out; g.pack->flag = flag;
-        if (flag) *g.a.err = 0;
-    }
-}
-template <bool SHARED>
-__global__ __launch_bounds__(256) void k_fm_step_scat2_tail(const StepArg* __restrict__ args, const int first)
-{
-    __shared__ float s_l[256];
-    const int m = args[first + blockIdx.y].scls;
-    if (blockIdx.x == 0) { step_tail(args[m], s_l); return; }
-    const ScatArgs sa = args[m].sa;
-    scat2w_form<SHARED>(sa, (int)blockIdx.x - 1, (int)gridDim.x - 1);
-}
-__global__ __launch_bounds__(256) void k_fm_step_scatw2_tail(const StepArg* __restrict__ args, const int first)
-{
-    __shared__ double s_w[1024];
-    const int m = args[first + blockIdx.y].scls;
-    if (blockIdx.x == 0) { step_tail(args[m], reinterpret_cast<float*>(s_w)); return; }
-    const ScatArgs sa = args[m].sa;
-    scatw2_body(sa, (int)blockIdx.x - 1, (int)gridDim.x - 1, s_w);
-}
-
-__global__ void k_fm_rescale(float* table16, size_t n, float s)
-{
-    const size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
-    if (i < n) table16[i] *= s;
-}
-
-__global__ void k_fm_fill(float* p, size_t n, float v)
-{
-    const size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
-    if (i < n) p[i] = v;
-}
-
-// Adam / FTRL on the table: the L2 term makes TensorFlow's gradient DENSE, so every live element (row < n_rows, column < K)
-// moves each step: g = G + lambda w, the optimiser, w and both state values written back.  The state is compact [n_rows, K]
-// (s0 / s1 rounded up to a multiple of 4 floats): a thread owns 4 consecutive elements of it -- one 16-byte access per state
-// array -- and the matching 4 table / G elements at their padded-row addresses (row stride rw); padding columns are never touched.
-// G (the batch's per-row gradient sums, padded rows) is read and cleared only where it was written: DENSE_G = false reads a
-// row's G when stamp[row] == step (the rows this step's forward touched); DENSE_G = true reads and clears every element of G.
-template <bool DENSE_G>
-__global__ __launch_bounds__(256) void k_fm_opt_pass(float* __restrict__ table16, float* __restrict__ G, const int* __restrict__ stamp, int step,
-                                                     float* __restrict__ s0, float* __restrict__ s1, size_t nk, int K, int rw, float lambda,
-                                                     int opt, float lr, float b1, float b2, float eps)
-{
-    const size_t e0 = ((size_t)blockIdx.x * blockDim.x + threadIdx.x) * 4;
-    if (e0 >= nk) return;
-    size_t row = e0 / K;
-    int c = (int)(e0 - row * K);
-    const float4 m4 = *reinterpret_cast<const float4*>(s0 + e0), v4 = *reinterpret_cast<const float4*>(s1 + e0);
-    float m[4] = {m4.x, m4.y, m4.z, m4.w}, v[4] = {v4.x, v4.y, v4.z, v4.w}, w[4], g[4];
-    size_t off[4];
-    bool live[4], hit[4];
-#pragma unroll
-    for (int j = 0; j < 4; ++j) {                      // every load first, then the arithmetic, then the stores
-        live[j] = e0 + j < nk;
-        off[j] = row * rw + c;
-        w[j] = live[j] ? table16[off[j]] : 0.f;
-        hit[j] = live[j] && (DENSE_G || stamp[row] == step);
-        g[j] = hit[j] ? G[off[j]] : 0.f;
-        if (++c == K) { c = 0; ++row; }
-    }
-#pragma unroll
-    for (int j = 0; j < 4; ++j) {
-        if (!live[j]) continue;
-        w[j] = fm_opt_step(opt, w[j], g[j] + lambda * w[j], m[j], v[j], lr, b1, b2, eps);
-        table16[off[j]] = w[j];
-        if (hit[j]) G[off[j]] = 0.f;
-    }
-    *reinterpret_cast<float4*>(s0 + e0) = make_float4(m[0], m[1], m[2], m[3]);
-    *reinterpret_cast<float4*>(s1 + e0) = make_float4(v[0], v[1], v[2], v[3]);
-}
+static_assert(FM_SLOT == SLOT, "fm_plan.h's narrow row is the FNN path's slot");
 
 // (the argument arrays of the group calls reach the device through an ArgRing of the handle in front: arg_ring.h)
 
 }  // namespace
 
-struct fm_handle {
+// F, K, wide (k >= 17: fm_wide_body, scatw1_body / scatw2_body), rw (the row stride in floats: SLOT for k <= 16, rup(k, 4) on the
+// wide path), K1p, and the layout class, fields per lane, examples per workgroup and update form of its kernels: the FmPlan
+struct fm_handle : FmPlan {
     std::string err; int dev = 0; hipStream_t st = nullptr; bool own_stream = false;
-    int F = 0, K = 0, Bmax = 0, K1p = 0;
-    bool wide = false;         // k >= 17: wide rows (fm_wide_body, scatw1_body / scatw2_body)
-    int rw = SLOT;             // row stride in floats: SLOT for k <= 16, rup(k, 4) on the wide path
+    int Bmax = 0;
     int* noshare = nullptr;    // wide path: [n_rows] zeros, the scatter's tag_shared (every row takes the plain read-modify-write)
     float* table16 = nullptr; int64_t n_rows = 0; float* b = nullptr; double scale = 1.0;
     float *gxp = nullptr, *loss_t = nullptr, *gb_part = nullptr, *loss_dev = nullptr; int* err_flag = nullptr;
@@ -655,11 +120,18 @@ int fm_next_stamp(fm_handle* h)
     h->step_stamp = ++h->tag_stamp;
     return h->step_stamp;
 }
-// the claim of the rank merge (sortB_body): on only while the mode is
-void set_claim(fm_handle* h, SortArgs& so)
+// The grouping of a step's batch on handle h as arguments: the run sort (so: launch 1, launch_sort_runs) and its rank-merge
+// twin (sb: 16 F workgroups beside the forward, sortB_body), which claims a fresh stamp and marks the rows under several
+// columns while fm_set_shared_rows is on -- and only then.
+struct StepSort { SortArgs so, sb; };
+StepSort step_sort(fm_handle* h, const int32_t* ids, int B)
 {
-    if (!h->shared) return;
-    so.tag_first = h->tag_first; so.tag_shared = h->tag_shared; so.stamp = fm_next_stamp(h);
+    StepSort s;
+    s.so = SortArgs{ids, B, h->F, h->n_rows, h->rg.rec, h->rg.owner_cnt, 4 * h->F, h->skeys};
+    s.so.merge4 = h->sort_merge4;
+    s.sb = s.so; s.sb.nblk = 16 * h->F;
+    if (h->shared) { s.sb.tag_first = h->tag_first; s.sb.tag_shared = h->tag_shared; s.sb.stamp = fm_next_stamp(h); }
+    return s;
 }
 
 size_t opt_state_len(const fm_handle* h) { return ((size_t)h->n_rows * h->K + 3) & ~(size_t)3; }
@@ -686,83 +158,90 @@ int init_opt_state(fm_handle* h)
     return FNN_OK;
 }
 
-// The forwards of both layouts, one instantiation per 16 fields: NF = NC = ceil(F / 16) (1 up to 16 fields).  sb: the rank merge
-// of the batch's sort runs beside the forward (training), null: the forward alone (predictions).  nb: the examples' workgroups.
-// WV = (a.wts != nullptr): without weights the kernels are the ones that never read a weight.
-template <typename KT, int N, bool WV>
-void launch_fwd_nw(const fm_handle* h, const SortArgs* sb, const FmArgs& a, int nb)
+// The dispatch ladder, written once.  A plan's fields per lane (= chunks of 16 fields: NF = NC = ceil(F / 16), 1 up to 16 fields),
+// whether the feed carries value weights (without them the kernels are the ones that never read a weight) and the plan's layout
+// class reach fn as compile-time constants, fn(Rung<LAY, N, WV>{}); the keyed form adds the width of the sort keys, as a value
+// of the key type, where a rank merge rides beside the forward.  The three launch sites -- launch_fwd (the solo forward),
+// launch_step_fwd (launch 2 of the step group) and launch_eval_fwd (the evaluation group, beside eval_forward) -- each name their
+// own kernel family (its narrow kernel and its wide twin) and nothing else.  The kernel templates come out in the device code in
+// the order of their first use, site by site in the order of this file; tools/cmp_kernel_asm.py compares them by symbol, and
+// glues what follows a kernel in the plain .text section to it -- so fm_online.hip.h is included in front of the FM kernels'
+// headers and launch_eval_fwd stays the last site of the file, as in the commit the comparison was first made against.
+template <int LAY, int N, bool WV> struct Rung {
+    static constexpr int n = N, lanes = LAY == FM_WIDE32 ? 32 : 16;    // lanes an example on wide rows
+    static constexpr bool wide = LAY != FM_NARROW, wv = WV;
+};
+template <class Fn> void fm_ladder(const FmPlan& p, bool wv, Fn fn)
 {
-    if (!h->wide) {
-        if (!sb) hipLaunchKernelGGL((k_fm<N, WV>), dim3(nb), dim3(256), 0, h->st, a);
-        else hipLaunchKernelGGL((k_fm_merge_fwd<KT, N, WV>), dim3(sb->nblk + nb), dim3(256), sort_lds_bytes<KT>(), h->st, *sb, a);
-    } else if (h->rw <= 64) {         // L = 16 lanes per example while a row's float4 pieces fit (rank <= 63), else 32
-        if (!sb) hipLaunchKernelGGL((k_fm_wide<16, N, WV>), dim3(nb), dim3(256), 0, h->st, a);
-        else hipLaunchKernelGGL((k_fm_wide_merge_fwd<KT, 16, N, WV>), dim3(sb->nblk + nb), dim3(256), sort_lds_bytes<KT>(), h->st, *sb, a);
-    } else {
-        if (!sb) hipLaunchKernelGGL((k_fm_wide<32, N, WV>), dim3(nb), dim3(256), 0, h->st, a);
-        else hipLaunchKernelGGL((k_fm_wide_merge_fwd<KT, 32, N, WV>), dim3(sb->nblk + nb), dim3(256), sort_lds_bytes<KT>(), h->st, *sb, a);
+    auto by_layout = [&](auto n, auto w) {
+        constexpr int N = decltype(n)::value;
+        constexpr bool WV = decltype(w)::value;
+        if (p.layout == FM_NARROW) fn(Rung<FM_NARROW, N, WV>{});
+        else if (p.layout == FM_WIDE16) fn(Rung<FM_WIDE16, N, WV>{});
+        else fn(Rung<FM_WIDE32, N, WV>{});
+    };
+    auto by_weights = [&](auto n) { if (wv) by_layout(n, std::true_type{}); else by_layout(n, std::false_type{}); };
+    switch (p.nf) {
+    case 1: by_weights(std::integral_constant<int, 1>{}); break;
+    case 2: by_weights(std::integral_constant<int, 2>{}); break;
+    case 3: by_weights(std::integral_constant<int, 3>{}); break;
+    default: by_weights(std::integral_constant<int, 4>{}); break;
     }
 }
-template <typename KT, int N>
-void launch_fwd_n(const fm_handle* h, const SortArgs* sb, const FmArgs& a, int nb)
+template <class Fn> void fm_ladder_keyed(const FmPlan& p, bool wv, bool key64, Fn fn)
 {
-    if (a.wts) launch_fwd_nw<KT, N, true>(h, sb, a, nb);
-    else launch_fwd_nw<KT, N, false>(h, sb, a, nb);
+    fm_ladder(p, wv, [&](auto r) { if (key64) fn(r, (unsigned long long)0); else fn(r, 0u); });
 }
-template <typename KT>
+
+// The solo forward on nb workgroups of examples.  sb: the rank merge of the batch's sort runs beside it (training), null: the
+// forward alone (predictions).
 void launch_fwd(const fm_handle* h, const SortArgs* sb, const FmArgs& a, int nb)
 {
-    switch ((h->F + 15) / 16) {
-    case 1: launch_fwd_n<KT, 1>(h, sb, a, nb); break;
-    case 2: launch_fwd_n<KT, 2>(h, sb, a, nb); break;
-    case 3: launch_fwd_n<KT, 3>(h, sb, a, nb); break;
-    default: launch_fwd_n<KT, 4>(h, sb, a, nb); break;
+    if (!sb) {
+        fm_ladder(*h, a.wts != nullptr, [&](auto r) {
+            using R = decltype(r);
+            if constexpr (!R::wide) hipLaunchKernelGGL((k_fm<R::n, R::wv>), dim3(nb), dim3(256), 0, h->st, a);
+            else hipLaunchKernelGGL((k_fm_wide<R::lanes, R::n, R::wv>), dim3(nb), dim3(256), 0, h->st, a);
+        });
+        return;
     }
+    fm_ladder_keyed(*h, a.wts != nullptr, h->key64, [&](auto r, auto key) {
+        using R = decltype(r);
+        using KT = decltype(key);
+        const dim3 grid(sb->nblk + nb);
+        if constexpr (!R::wide) hipLaunchKernelGGL((k_fm_merge_fwd<KT, R::n, R::wv>), grid, dim3(256), sort_lds_bytes<KT>(), h->st, *sb, a);
+        else hipLaunchKernelGGL((k_fm_wide_merge_fwd<KT, R::lanes, R::n, R::wv>), grid, dim3(256), sort_lds_bytes<KT>(), h->st, *sb, a);
+    });
 }
-// The forwards of a group of models (eval_forward): cls 0 narrow rows, 1 wide at 16 lanes an example, 2 wide at 32.
-template <int N, bool WV>
-void launch_multi_nw(hipStream_t st, int cls, dim3 grid, const EvalArg* args, int first, int nm, int64_t tiles, int model_fast)
+// fm_train_step_multi, launch 2 of one layout class (p: the plan of one of its nm members, listed from place `first` on);
+// ncls > 0: the rank merges of that many grouping classes in front, mblk workgroups each
+void launch_step_fwd(hipStream_t st, const FmPlan& p, bool wv, bool key64, const StepArg* d, int ncls, int mblk, int first, int nm, int tiles)
 {
-    if (cls == 0) hipLaunchKernelGGL((k_fm_multi<N, WV>), grid, dim3(256), 0, st, args, first, nm, tiles, model_fast);
-    else if (cls == 1) hipLaunchKernelGGL((k_fm_wide_multi<16, N, WV>), grid, dim3(256), 0, st, args, first, nm, tiles, model_fast);
-    else hipLaunchKernelGGL((k_fm_wide_multi<32, N, WV>), grid, dim3(256), 0, st, args, first, nm, tiles, model_fast);
-}
-template <int N>
-void launch_multi_n(bool wv, hipStream_t st, int cls, dim3 grid, const EvalArg* args, int first, int nm, int64_t tiles, int model_fast)
-{
-    if (wv) launch_multi_nw<N, true>(st, cls, grid, args, first, nm, tiles, model_fast);
-    else launch_multi_nw<N, false>(st, cls, grid, args, first, nm, tiles, model_fast);
+    fm_ladder_keyed(p, wv, key64, [&](auto r, auto key) {
+        using R = decltype(r);
+        using KT = decltype(key);
+        const dim3 grid((unsigned)(ncls * mblk + nm * tiles));
+        const size_t lds = ncls ? sort_lds_bytes<KT>() : 0;
+        if constexpr (!R::wide) hipLaunchKernelGGL((k_fm_step_fwd<KT, R::n, R::wv>), grid, dim3(256), lds, st, d, ncls, mblk, first, tiles);
+        else hipLaunchKernelGGL((k_fm_step_fwd_wide<KT, R::lanes, R::n, R::wv>), grid, dim3(256), lds, st, d, ncls, mblk, first, tiles);
+    });
 }
 
-// The wide path's forward: 256 / L examples per workgroup (L = 16 while rank <= 63, else 32).
-int wide_epb(const fm_handle* h) { return h->rw <= 64 ? 16 : 8; }
-
-// Adam's / FTRL's pass over the table (k_fm_opt_pass).  Defined below fm_step: the kernel templates are instantiated in the order
-// of their first use, and that order is the order of the functions in the device code.
-void launch_opt_pass(fm_handle* h, float lambda, float lr_step);
-
-// fm_train_step_multi: launch 2 of a layout: lay 0 narrow rows, 1 wide at 16 lanes an example, 2 wide at 32; ncls > 0: the classes' rank merges in front
-template <typename KT, int N, bool WV>
-void launch_step_fwd_nw(hipStream_t st, int lay, const StepArg* d, int ncls, int mblk, int first, int nm, int tiles)
+// The end of a step, solo or a group member's: Adam's / FTRL's pass over the table (k_fm_opt_pass), or the fold of SGD's lazy
+// scale where it is due.
+int end_step(fm_handle* h, float lambda, float lr_step)
 {
-    const dim3 grid((unsigned)(ncls * mblk + nm * tiles));
-    const size_t lds = ncls ? sort_lds_bytes<KT>() : 0;
-    if (lay == 0) hipLaunchKernelGGL((k_fm_step_fwd<KT, N, WV>), grid, dim3(256), lds, st, d, ncls, mblk, first, tiles);
-    else if (lay == 1) hipLaunchKernelGGL((k_fm_step_fwd_wide<KT, 16, N, WV>), grid, dim3(256), lds, st, d, ncls, mblk, first, tiles);
-    else hipLaunchKernelGGL((k_fm_step_fwd_wide<KT, 32, N, WV>), grid, dim3(256), lds, st, d, ncls, mblk, first, tiles);
-}
-template <typename KT>
-void launch_step_fwd(hipStream_t st, int F, bool wv, int lay, const StepArg* d, int ncls, int mblk, int first, int nm, int tiles)
-{
-#define FM_STEP_FWD(N) do { if (wv) launch_step_fwd_nw<KT, N, true>(st, lay, d, ncls, mblk, first, nm, tiles); \
-                            else launch_step_fwd_nw<KT, N, false>(st, lay, d, ncls, mblk, first, nm, tiles); } while (0)
-    switch ((F + 15) / 16) {
-    case 1: FM_STEP_FWD(1); break;
-    case 2: FM_STEP_FWD(2); break;
-    case 3: FM_STEP_FWD(3); break;
-    default: FM_STEP_FWD(4); break;
-    }
-#undef FM_STEP_FWD
+    if (h->opt == FM_OPT_SGD) return fm_fold_due(h->scale) ? fold_scale(h) : FNN_OK;
+    const size_t nk = (size_t)h->n_rows * h->K;
+    const dim3 grid((unsigned)(((nk + 3) / 4 + 255) / 256));
+    if (h->dense_g)
+        hipLaunchKernelGGL(k_fm_opt_pass<true>, grid, dim3(256), 0, h->st, h->table16, h->G, h->stamp, (int)h->t, h->s0, h->s1, nk, h->K,
+                           h->rw, lambda, h->opt, lr_step, h->beta1, h->beta2, h->eps);
+    else
+        hipLaunchKernelGGL(k_fm_opt_pass<false>, grid, dim3(256), 0, h->st, h->table16, h->G, h->stamp, (int)h->t, h->s0, h->s1, nk, h->K,
+                           h->rw, lambda, h->opt, lr_step, h->beta1, h->beta2, h->eps);
+    MHK(h, hipGetLastError());
+    return FNN_OK;
 }
 
 bool fm_wt_env() { return !(getenv("FM_WT") && atoi(getenv("FM_WT")) == 0); }     // gx' written through unless FM_WT=0
@@ -776,8 +255,7 @@ FmArgs predict_args(const fm_handle* h, const int32_t* ids, const float* wts, in
 
 int fm_forward(fm_handle* h, const int32_t* ids, const float* wts, int B, float* p_out)
 {
-    const int ex = h->wide ? wide_epb(h) : 16;
-    launch_fwd<unsigned>(h, nullptr, predict_args(h, ids, wts, B, p_out, fm_wt_env()), rup(B, ex) / ex);
+    launch_fwd(h, nullptr, predict_args(h, ids, wts, B, p_out, fm_wt_env()), (int)fm_tiles(B, h->epb));
     MHK(h, hipGetLastError());
     return FNN_OK;
 }
@@ -797,7 +275,7 @@ StepPlan plan_step(fm_handle* h, const int32_t* ids, const float* wts, const flo
                    float* p_out, bool wt, const fm_handle* lead, int stamp, int form1, int form2)
 {
     StepPlan p;
-    const int F = h->F, ex = h->wide ? wide_epb(h) : 16, Ba = rup(B, ex);
+    const int F = h->F, ex = h->epb, Ba = rup(B, ex);
     const bool opt = h->opt != FM_OPT_SGD;
     const float dscale = reduce_mean ? 1.0f / (float)B : 1.0f;
     p.lr_step = lr;
@@ -828,45 +306,26 @@ StepPlan plan_step(fm_handle* h, const int32_t* ids, const float* wts, const flo
 }
 
 // The solo step, narrow and wide rows: the run sort; the forward + gradients beside the rank merge; level 1 of the sparse-row
-// update; level 2 beside the bias / loss tail; then Adam's / FTRL's pass over the table, or the fold of SGD's lazy scale where due.
+// update; level 2 beside the bias / loss tail; then the end of the step (end_step).
 int fm_step(fm_handle* h, const int32_t* ids, const float* wts, const float* y, int B, float lr, float lambda, int reduce_mean, float* p_out)
 {
-    const int F = h->F;
-    SortArgs so{ids, B, F, h->n_rows, h->rg.rec, h->rg.owner_cnt, 4 * F, h->skeys};
-    so.merge4 = h->sort_merge4;
-    SortArgs sb = so; sb.nblk = 16 * F;
-    set_claim(h, sb);
-    const bool own_forms = !h->wide && !h->shared;
-    const StepPlan p = plan_step(h, ids, wts, y, B, lr, lambda, reduce_mean, p_out, fm_wt_env(), h, sb.stamp,
+    const StepSort s = step_sort(h, ids, B);
+    const bool own_forms = h->form == FM_UPD_NARROW;
+    const StepPlan p = plan_step(h, ids, wts, y, B, lr, lambda, reduce_mean, p_out, fm_wt_env(), h, s.sb.stamp,
                                  own_forms ? h->scat_form : SCAT1_HALF, own_forms ? h->scat2_form : SCAT2_WAVE);
     const StepTail& t = p.t;
-    launch_sort_runs(h->st, h->key64, so);
-    if (h->key64) launch_fwd<unsigned long long>(h, &sb, p.a, t.n);
-    else launch_fwd<unsigned>(h, &sb, p.a, t.n);
+    launch_sort_runs(h->st, h->key64, s.so);
+    launch_fwd(h, &s.sb, p.a, t.n);
 #define FM_SCAT(k1, k2_tail) do { \
         hipLaunchKernelGGL(k1, dim3(p.nb1), dim3(256), 0, h->st, p.sa); \
         hipLaunchKernelGGL(k2_tail, dim3(1 + 256), dim3(256), 0, h->st, p.sa, t.b, t.gb_part, t.n, t.lr, t.lambda, t.loss_t, t.Ba, t.lscale, \
                            t.loss_out, t.bo); } while (0)
-    if (h->wide) FM_SCAT(k_fm_scatw1, k_fm_scatw2_tail);
-    else if (h->shared) FM_SCAT(k_fm_scat1s, k_fm_scat2s_tail);          // the SHARED forms, with the marks of this step's rank merge
+    if (h->form == FM_UPD_WIDE) FM_SCAT(k_fm_scatw1, k_fm_scatw2_tail);
+    else if (h->form == FM_UPD_SHARED) FM_SCAT(k_fm_scat1s, k_fm_scat2s_tail);   // the SHARED forms, with the marks of this step's rank merge
     else FM_SCAT(k_scat1, k_fm_scat2_tail);
 #undef FM_SCAT
     MHK(h, hipGetLastError());
-    if (h->opt != FM_OPT_SGD) { launch_opt_pass(h, lambda, p.lr_step); MHK(h, hipGetLastError()); return FNN_OK; }
-    if (h->scale < 5.96e-8 || h->scale > 1.0) return fold_scale(h);
-    return FNN_OK;
-}
-
-void launch_opt_pass(fm_handle* h, float lambda, float lr_step)
-{
-    const size_t nk = (size_t)h->n_rows * h->K;
-    const dim3 grid((unsigned)(((nk + 3) / 4 + 255) / 256));
-    if (h->dense_g)
-        hipLaunchKernelGGL(k_fm_opt_pass<true>, grid, dim3(256), 0, h->st, h->table16, h->G, h->stamp, (int)h->t, h->s0, h->s1, nk, h->K,
-                           h->rw, lambda, h->opt, lr_step, h->beta1, h->beta2, h->eps);
-    else
-        hipLaunchKernelGGL(k_fm_opt_pass<false>, grid, dim3(256), 0, h->st, h->table16, h->G, h->stamp, (int)h->t, h->s0, h->s1, nk, h->K,
-                           h->rw, lambda, h->opt, lr_step, h->beta1, h->beta2, h->eps);
+    return end_step(h, lambda, p.lr_step);
 }
 
 // ArgRing (arg_ring.h) with the failure's text left on the handle in front
@@ -882,7 +341,7 @@ int ring_send(fm_handle* h0, ArgRing& r, size_t slot, size_t n)
 }
 
 // A call on a list of fm handles: GroupCall (group_call.h), refusals without a usable hs[0] left with fm_last_error(NULL).
-// fold_scale(), fm_next_stamp() and launch_opt_pass() work on their handle's stream: on_stream() gives them hs[0]'s.
+// step_sort() (fm_next_stamp's wrap) and end_step() work on their handle's stream: on_stream() gives them hs[0]'s.
 using FmGroup = GroupCall<fm_handle>;
 int check_tables(const FmGroup& g)
 {
@@ -905,9 +364,8 @@ int fm_create(int n_fields, int k, int max_batch, int device, void* stream, fm_h
     int ndev = 0;
     if (hipGetDeviceCount(&ndev) != hipSuccess || ndev <= 0) { g_fm_err = "no HIP device (libfnn_hip.so has no CPU fallback)"; return FNN_ERR_HIP; }
     fm_handle* h = new fm_handle();
-    h->dev = device; h->F = n_fields; h->K = k; h->Bmax = max_batch;
-    h->wide = k > 16; h->rw = h->wide ? rup(k, 4) : SLOT;
-    h->K1p = h->wide ? n_fields * h->rw : rup(n_fields, 16) * SLOT;   // gx' of an example: a slot per field of rup(F, 16), or [F][rw]
+    static_cast<FmPlan&>(*h) = fm_make_plan(n_fields, k);
+    h->dev = device; h->Bmax = max_batch;
     auto fail = [&](int code) { g_fm_err = h->err; fm_destroy(h); return code; };
 #define FK(expr) do { hipError_t e2_ = (expr); if (e2_ != hipSuccess) { h->err = std::string(#expr) + ": " + hipGetErrorString(e2_); return fail(FNN_ERR_HIP); } } while (0)
     FK(hipSetDevice(h->dev));
@@ -1073,7 +531,7 @@ int fm_train_online(fm_handle* h, const int32_t* ids, const float* wts, const fl
         int64_t cnt = 0;
         double s = h->scale;
         bool fold = false;
-        while (n0 + cnt < N && cnt < h->online_chunk && !fold) { s *= dec; ++cnt; fold = s < 5.96e-8 || s > 1.0; }
+        while (n0 + cnt < N && cnt < h->online_chunk && !fold) { s *= dec; ++cnt; fold = fm_fold_due(s); }
         const fm_online::Args a{ids + n0 * h->F, wts ? wts + n0 * h->F : nullptr, y + n0, cnt, h->F, h->K, h->rw, h->table16, h->n_rows, h->b,
                                 h->scale, dec, lr, lambda, p_out ? p_out + n0 : nullptr, h->err_flag, h->online_out};
         hipLaunchKernelGGL(fm_online::k_fm_online, dim3(1), dim3(256), 0, h->st, a);
@@ -1136,7 +594,7 @@ int fm_train_online_multi(fm_handle* const* hs, int n_models, const int32_t* ids
         bool fold = false;
         for (int m = 0; m < n_models; ++m) s[m] = hs[m]->scale;
         while (n0 + cnt < N && cnt < chunk && !fold) {
-            for (int m = 0; m < n_models; ++m) { s[m] *= dec[m]; fold = fold || s[m] < 5.96e-8 || s[m] > 1.0; }
+            for (int m = 0; m < n_models; ++m) { s[m] *= dec[m]; fold = fold || fm_fold_due(s[m]); }
             ++cnt;
         }
         fm_online::Args* a = h0->online_ring.at_host<fm_online::Args>(slot);
@@ -1153,7 +611,7 @@ int fm_train_online_multi(fm_handle* const* hs, int n_models, const int32_t* ids
         for (int m = 0; m < n_models; ++m) {
             fm_handle* h = hs[m];
             h->scale = s[m];
-            if (s[m] < 5.96e-8 || s[m] > 1.0) {
+            if (fm_fold_due(s[m])) {
                 const int rf = on_stream(h, st, [&] { return fold_scale(h); });
                 if (rf != FNN_OK) return g.member_failed(rf, h, m);
             }
@@ -1222,37 +680,27 @@ int fm_train_step_multi(fm_handle* const* hs, int n_models, const int32_t* ids, 
         cls_of[m] = (int)class_index(cls, Cls{hs[m], 0}, [](const Cls& a, const Cls& b) {
             return a.lead->n_rows == b.lead->n_rows && a.lead->shared == b.lead->shared; });
     // the classes with the first one's key width have their rank merge in launch 2; the others a launch of their own
+    const bool key64 = cls[0].lead->key64;
     std::vector<int> order;                                           // classes, the riders first
-    for (int c = 0; c < (int)cls.size(); ++c) if (cls[c].lead->key64 == cls[0].lead->key64) order.push_back(c);
+    for (int c = 0; c < (int)cls.size(); ++c) if (cls[c].lead->key64 == key64) order.push_back(c);
     const int nride = (int)order.size();
-    for (int c = 0; c < (int)cls.size(); ++c) if (cls[c].lead->key64 != cls[0].lead->key64) order.push_back(c);
+    for (int c = 0; c < (int)cls.size(); ++c) if (cls[c].lead->key64 != key64) order.push_back(c);
     std::vector<SortArgs> sorts(cls.size());
     for (int i = 0; i < (int)order.size(); ++i) {
         Cls& k = cls[order[i]];
         fm_handle* h = k.lead;
-        SortArgs so{ids, B, F, h->n_rows, h->rg.rec, h->rg.owner_cnt, 4 * F, h->skeys};
-        so.merge4 = h->sort_merge4;
-        launch_sort_runs(st, h->key64, so);                           // launch 1
-        so.nblk = 16 * F;
-        if (h->shared) {
-            so.tag_first = h->tag_first; so.tag_shared = h->tag_shared;
-            so.stamp = k.stamp = on_stream(h, st, [&] { return fm_next_stamp(h); });
-        }
-        sorts[i] = so;
-        a[i].so = so;
+        const StepSort s = on_stream(h, st, [&] { return step_sort(h, ids, B); });
+        launch_sort_runs(st, h->key64, s.so);                         // launch 1
+        k.stamp = s.sb.stamp;
+        sorts[i] = a[i].so = s.sb;
     }
     MHK(h0, hipGetLastError());
 
+    // plans into the ring, the members listed by forward layout (launch 2) and by update form (launches 3 and 4)
     const bool wt = fm_wt_env();
-    auto lay_of = [](const fm_handle* h) { return !h->wide ? 0 : h->rw <= 64 ? 1 : 2; };          // launch_fwd_nw's choice of kernel
-    auto form_of = [](const fm_handle* h) { return h->wide ? 2 : h->shared ? 1 : 0; };              // level 1 / 2: narrow, narrow shared, wide
-    int fcnt[3] = {0, 0, 0}, scnt[3] = {0, 0, 0}, ffirst[3], sfirst[3], fpos[3], spos[3], nb1max[3] = {0, 0, 0};
-    for (int m = 0; m < M; ++m) { ++fcnt[lay_of(hs[m])]; ++scnt[form_of(hs[m])]; }
-    ffirst[0] = sfirst[0] = 0;
-    for (int c = 1; c < 3; ++c) { ffirst[c] = ffirst[c - 1] + fcnt[c - 1]; sfirst[c] = sfirst[c - 1] + scnt[c - 1]; }
-    for (int c = 0; c < 3; ++c) { fpos[c] = ffirst[c]; spos[c] = sfirst[c]; }
     std::vector<float> lr_step(M);
-    for (int m = 0; m < M; ++m) {                                     // plan, store into a[m], bucket by layout / form
+    int nb1max[FM_UPDATE_FORMS] = {0, 0, 0};
+    for (int m = 0; m < M; ++m) {
         fm_handle* h = hs[m];
         const Cls& k = cls[cls_of[m]];
         const StepPlan p = plan_step(h, ids, wts, y, B, lr[m], lambda[m], reduce_mean ? reduce_mean[m] : 0, p_out ? p_out[m] : nullptr, wt,
@@ -1262,42 +710,38 @@ int fm_train_step_multi(fm_handle* const* hs, int n_models, const int32_t* ids, 
         a[m].own_marks = nullptr; a[m].own_stamp = 0;
         if (h->shared && h != k.lead) { a[m].own_marks = h->tag_shared; a[m].own_stamp = on_stream(h, st, [&] { return fm_next_stamp(h); }); }
         a[m].pack = pack ? pack + m : nullptr;
-        a[fpos[lay_of(h)]++].fcls = m;
-        a[spos[form_of(h)]++].scls = m;
-        nb1max[form_of(h)] = std::max(nb1max[form_of(h)], p.nb1);
+        nb1max[h->form] = std::max(nb1max[h->form], p.nb1);
     }
+    const auto fw = members_in_class_order<FM_LAYOUTS>(M, [&](int m) { return hs[m]->layout; }, [&](int j, int m) { a[j].fcls = m; });
+    const auto up = members_in_class_order<FM_UPDATE_FORMS>(M, [&](int m) { return hs[m]->form; }, [&](int j, int m) { a[j].scls = m; });
     rc = ring_send(h0, h0->step_ring, slot, (size_t)M);
     if (rc != FNN_OK) return rc;
+
     for (int i = nride; i < (int)order.size(); ++i) {                 // the other key width: the plain rank merge
         const SortArgs& so = sorts[i];
-        if (cls[order[i]].lead->key64) hipLaunchKernelGGL((k_sortB<unsigned long long>), dim3(so.nblk), dim3(256), sort_lds_bytes<unsigned long long>(), st, so);
+        if (!key64) hipLaunchKernelGGL((k_sortB<unsigned long long>), dim3(so.nblk), dim3(256), sort_lds_bytes<unsigned long long>(), st, so);
         else hipLaunchKernelGGL((k_sortB<unsigned>), dim3(so.nblk), dim3(256), sort_lds_bytes<unsigned>(), st, so);
     }
     int ride = nride;                                                 // launch 2: the merges ride in the first layout present
-    for (int c = 0; c < 3; ++c) {
-        if (!fcnt[c]) continue;
-        const int tiles = (B + (c == 2 ? 8 : 16) - 1) / (c == 2 ? 8 : 16);
-        if (cls[0].lead->key64) launch_step_fwd<unsigned long long>(st, F, wts != nullptr, c, d, ride, 16 * F, ffirst[c], fcnt[c], tiles);
-        else launch_step_fwd<unsigned>(st, F, wts != nullptr, c, d, ride, 16 * F, ffirst[c], fcnt[c], tiles);
+    for (int c = 0; c < FM_LAYOUTS; ++c) {
+        if (!fw.cnt[c]) continue;
+        const FmPlan& pl = *hs[a[fw.first[c]].fcls];                  // a member of the layout
+        launch_step_fwd(st, pl, wts != nullptr, key64, d, ride, 16 * F, fw.first[c], fw.cnt[c], (int)fm_tiles(B, pl.epb));
         ride = 0;
     }
     MHK(h0, hipGetLastError());
-    if (scnt[0]) hipLaunchKernelGGL(k_fm_step_scat1<false>, dim3(nb1max[0], scnt[0]), dim3(256), 0, st, d, sfirst[0]);      // launch 3
-    if (scnt[1]) hipLaunchKernelGGL(k_fm_step_scat1<true>, dim3(nb1max[1], scnt[1]), dim3(256), 0, st, d, sfirst[1]);
-    if (scnt[2]) hipLaunchKernelGGL(k_fm_step_scatw1, dim3(nb1max[2], scnt[2]), dim3(256), 0, st, d, sfirst[2]);
-    if (scnt[0]) hipLaunchKernelGGL(k_fm_step_scat2_tail<false>, dim3(1 + 256, scnt[0]), dim3(256), 0, st, d, sfirst[0]);   // launch 4
-    if (scnt[1]) hipLaunchKernelGGL(k_fm_step_scat2_tail<true>, dim3(1 + 256, scnt[1]), dim3(256), 0, st, d, sfirst[1]);
-    if (scnt[2]) hipLaunchKernelGGL(k_fm_step_scatw2_tail, dim3(1 + 256, scnt[2]), dim3(256), 0, st, d, sfirst[2]);
+    using UpdateKernel = void (*)(const StepArg*, int);              // by FmUpdateForm: narrow, narrow shared, wide
+    const UpdateKernel level1[FM_UPDATE_FORMS] = {k_fm_step_scat1<false>, k_fm_step_scat1<true>, k_fm_step_scatw1};
+    const UpdateKernel level2_tail[FM_UPDATE_FORMS] = {k_fm_step_scat2_tail<false>, k_fm_step_scat2_tail<true>, k_fm_step_scatw2_tail};
+    for (int f = 0; f < FM_UPDATE_FORMS; ++f)                         // launch 3
+        if (up.cnt[f]) hipLaunchKernelGGL(level1[f], dim3(nb1max[f], up.cnt[f]), dim3(256), 0, st, d, up.first[f]);
+    for (int f = 0; f < FM_UPDATE_FORMS; ++f)                         // launch 4
+        if (up.cnt[f]) hipLaunchKernelGGL(level2_tail[f], dim3(1 + 256, up.cnt[f]), dim3(256), 0, st, d, up.first[f]);
     MHK(h0, hipGetLastError());
-    for (int m = 0; m < M; ++m) {                                     // Adam / FTRL: the dense pass; SGD: the fold where it is due
+    for (int m = 0; m < M; ++m) {                                     // the end of each member's step
         fm_handle* h = hs[m];
-        if (h->opt != FM_OPT_SGD) {
-            on_stream(h, st, [&] { launch_opt_pass(h, lambda[m], lr_step[m]); return 0; });
-            MHK(h0, hipGetLastError());
-        } else if (h->scale < 5.96e-8 || h->scale > 1.0) {
-            const int rf = on_stream(h, st, [&] { return fold_scale(h); });
-            if (rf != FNN_OK) return g.member_failed(rf, h, m);
-        }
+        const int re = on_stream(h, st, [&] { return end_step(h, lambda[m], lr_step[m]); });
+        if (re != FNN_OK) return g.member_failed(re, h, m);
     }
     rc = g.leave();
     if (rc != FNN_OK || !loss_out) return rc;
@@ -1363,7 +807,8 @@ int fm_set_shared_rows(fm_handle* h, int on)
     if (want == h->shared) return FNN_OK;
     MHK(h, hipStreamSynchronize(h->st));
     h->shared = want;
-    h->step_stamp = 0;                                            // no step has run under this setting
+    h->form = fm_update_form(*h, want);                           // the plan's one entry that is not n_fields' and k's alone
+    h->step_stamp = 0;                                           // no step has run under this setting
     if (want && h->table16 && !h->tag_first) return alloc_tags(h);
     return FNN_OK;
 }
@@ -1429,6 +874,17 @@ int eval_check(const FmGroup& g, const int32_t* ids, bool need_y, const int32_t*
     return check_tables(g);
 }
 
+// The forwards of the nm members of one layout class in an evaluation group (eval_forward), from place `first` of the array on;
+// p: the plan of one of them.
+void launch_eval_fwd(hipStream_t st, const FmPlan& p, bool wv, dim3 grid, const EvalArg* d, int first, int nm, int64_t tiles, int model_fast)
+{
+    fm_ladder(p, wv, [&](auto r) {
+        using R = decltype(r);
+        if constexpr (!R::wide) hipLaunchKernelGGL((k_fm_multi<R::n, R::wv>), grid, dim3(256), 0, st, d, first, nm, tiles, model_fast);
+        else hipLaunchKernelGGL((k_fm_wide_multi<R::lanes, R::n, R::wv>), grid, dim3(256), 0, st, d, first, nm, tiles, model_fast);
+    });
+}
+
 // The predictions of g models on the N lines, p[m] (nullable) each: the argument array into the ring, then one launch per layout
 // class present.  *dev_args: where the group's arguments are on the device (k_fm_eval_flags reads them again).
 int eval_forward(fm_handle* h0, fm_handle* const* hs, int g, const int32_t* ids, const float* wts, int64_t N, float* const* p,
@@ -1439,33 +895,21 @@ int eval_forward(fm_handle* h0, fm_handle* const* hs, int g, const int32_t* ids,
     if (rc != FNN_OK) return rc;
     EvalArg* a = h0->eval_ring.at_host<EvalArg>(slot);
     const EvalArg* d = h0->eval_ring.at_dev<EvalArg>(slot);
-    auto cls_of = [](const fm_handle* h) { return !h->wide ? 0 : h->rw <= 64 ? 1 : 2; };   // launch_fwd_nw's choice of kernel
-    int cnt[3] = {0, 0, 0}, first[3], pos[3];
-    for (int m = 0; m < g; ++m) ++cnt[cls_of(hs[m])];
-    first[0] = 0; first[1] = cnt[0]; first[2] = cnt[0] + cnt[1];
-    for (int c = 0; c < 3; ++c) pos[c] = first[c];
     const bool wt = fm_wt_env();
-    for (int m = 0; m < g; ++m) {
-        a[m].a = predict_args(hs[m], ids, wts, (int)N, p[m], wt);
-        a[pos[cls_of(hs[m])]++].cls = m;
-    }
+    for (int m = 0; m < g; ++m) a[m].a = predict_args(hs[m], ids, wts, (int)N, p[m], wt);
+    const auto lay = members_in_class_order<FM_LAYOUTS>(g, [&](int m) { return hs[m]->layout; }, [&](int j, int m) { a[j].cls = m; });
     const hipStream_t st = h0->st;
     rc = ring_send(h0, h0->eval_ring, slot, (size_t)g);
     if (rc != FNN_OK) return rc;
     const char* order = getenv("FM_EVAL_ORDER");                  // "model": the model is the fast index of the grid; default: the tile
     const int model_fast = order && !strcmp(order, "model");
-    for (int c = 0; c < 3; ++c) {
-        if (!cnt[c]) continue;
-        const int epb = c == 2 ? 8 : 16;                          // examples per workgroup: 256 / L, 16 on the narrow path
-        const int64_t tiles = (N + epb - 1) / epb, total = tiles * cnt[c];
+    for (int c = 0; c < FM_LAYOUTS; ++c) {
+        if (!lay.cnt[c]) continue;
+        const FmPlan& pl = *hs[a[lay.first[c]].cls];               // a member of the layout
+        const int64_t tiles = fm_tiles(N, pl.epb), total = tiles * lay.cnt[c];
         const int64_t gx = total < (1 << 22) ? total : (1 << 22);
         const dim3 grid((unsigned)gx, (unsigned)((total + gx - 1) / gx));
-        switch ((h0->F + 15) / 16) {
-        case 1: launch_multi_n<1>(wts != nullptr, st, c, grid, d, first[c], cnt[c], tiles, model_fast); break;
-        case 2: launch_multi_n<2>(wts != nullptr, st, c, grid, d, first[c], cnt[c], tiles, model_fast); break;
-        case 3: launch_multi_n<3>(wts != nullptr, st, c, grid, d, first[c], cnt[c], tiles, model_fast); break;
-        default: launch_multi_n<4>(wts != nullptr, st, c, grid, d, first[c], cnt[c], tiles, model_fast); break;
-        }
+        launch_eval_fwd(st, pl, wts != nullptr, grid, d, lay.first[c], lay.cnt[c], tiles, model_fast);
         MHK(h0, hipGetLastError());
     }
     *dev_args = d;

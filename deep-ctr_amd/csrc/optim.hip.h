@@ -1,5 +1,6 @@
 // optim.hip.h -- TensorFlow's Adam and FTRL updates of one variable element, shared by the inner-product family
-// (ip_step_kernels.hip.h, a part of the unit ipnn_api.hip) and factorisation-machine pre-training (fm_api.hip).  Internal, not installed.
+// (ip_step_kernels.hip.h, a part of the unit ipnn_api.hip) and factorisation-machine pre-training (fm_kernels.hip.h, a part of
+// the unit fm_api.hip).  Internal, not installed.
 #pragma once
 #include <hip/hip_runtime.h>
 
