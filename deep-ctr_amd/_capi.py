@@ -115,12 +115,28 @@ class ipnn_cfg(C.Structure):
                 ("adam_eps", C.c_float), ("device", C.c_int32), ("stream", C.c_void_p)]
 
 
+class ipnn_tiles(C.Structure):
+    _fields_ = [("cap_a", C.c_int32), ("cap_b", C.c_int32), ("lds_bytes", C.c_uint64)]
+
+
+IPNN_PLAN_LAUNCHES = ("stack_fwd", "stack_bwd", "wide_fwd", "wide_bwd", "tail_fwd", "tail_bwd", "tail_fused")
+
+
+class ipnn_plan_info(C.Structure):
+    _fields_ = [("strips", C.c_int32), ("pairs", C.c_int32), ("cut", C.c_int32), ("rows_fwd", C.c_int32), ("rows_bwd", C.c_int32),
+                ("shares_step", C.c_int32), ("shares_eval", C.c_int32), ("n_layers", C.c_int32), ("padded", C.c_int32 * 10)] + \
+               [(name, ipnn_tiles) for name in IPNN_PLAN_LAUNCHES] + [("lds_max", C.c_uint64)]
+
+
 IPNN_ACTS = {'tanh': 0, 'sigmoid': 1, 'relu': 3}
+IPNN_ROWS = {0: 'narrow', 1: 'wide', 2: 'many'}
 # every symbol include/ipnn_hip.h declares
 IPNN_SIGNATURES = {
     "ipnn_last_error": (C.c_char_p, [_vp]),
     "ipnn_cfg_size": (C.c_uint64, []),
     "ipnn_create": (_i, [C.POINTER(ipnn_cfg), C.POINTER(_vp)]),
+    "ipnn_plan_info_size": (C.c_uint64, []),
+    "ipnn_plan_query": (_i, [C.POINTER(ipnn_cfg), C.POINTER(ipnn_plan_info)]),
     "ipnn_destroy": (_i, [_vp]),
     "ipnn_sync": (_i, [_vp]),
     "ipnn_set_table": (_i, [_vp, _vp, _i64]),
@@ -234,7 +250,7 @@ def load():
         fn.restype = res
         fn.argtypes = args
     # the structs are declared twice (include/*.h and above): a mismatch would make *_create read past the caller's struct
-    for name, st in (("fnn_cfg_size", fnn_cfg), ("ipnn_cfg_size", ipnn_cfg)):
+    for name, st in (("fnn_cfg_size", fnn_cfg), ("ipnn_cfg_size", ipnn_cfg), ("ipnn_plan_info_size", ipnn_plan_info)):
         if getattr(lib, name)() != C.sizeof(st):
             raise ImportError("%s() = %d but ctypes declares %d bytes: _capi.py is out of date with include/*.h"
                               % (name, getattr(lib, name)(), C.sizeof(st)))

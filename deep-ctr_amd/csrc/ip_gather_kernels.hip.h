@@ -547,9 +547,10 @@ static __global__ __launch_bounds__(256) void k_ip_fwd_m(const IpManyArgs a, T* 
 // Many-field backward: gx'[t][16 f + l] = dz[t][16 f + l] + sum_{j != f} dz[t][pair(f, j)] e_j[l] (l < k; pad columns 0) and the
 // per-workgroup partial of db (one per IPM_BEX examples).  The embeddings come from emb (the forward's copy).  A wave holds four
 // fields x 16 slots: its read of e_j[l] is 16 addresses broadcast to the four fields, its read of the pair delta four addresses.
-template <bool WV = false>
-static __global__ __launch_bounds__(256) void k_ip_bwd_m(const IpManyArgs a, const float* __restrict__ dz, const float* __restrict__ emb,
-                                                          float* __restrict__ gxp, float* __restrict__ gb_part)
+// (the body of k_ip_bwd_m and of its group form k_ip_bwd_m_g)
+template <bool WV>
+__device__ __forceinline__ void ip_bwd_m_body(const IpManyArgs& a, const float* __restrict__ dz, const float* __restrict__ emb,
+                                              float* __restrict__ gxp, float* __restrict__ gb_part)
 {
     extern __shared__ __align__(16) unsigned char smem[];
     const int F = a.F, K = a.K, FS = F * SLOT, P = a.P, CB = FS + P, D0p = a.D0p;
@@ -611,6 +612,12 @@ static __global__ __launch_bounds__(256) void k_ip_bwd_m(const IpManyArgs a, con
         for (int r = 0; r < IPM_BEX; ++r) gxp[(size_t)(t0 + r) * D0p + c] = g[r];
     }
     if (threadIdx.x == 0) { float s = 0.f; for (int r = 0; r < IPM_BEX; ++r) s += dz[(size_t)(t0 + r) * D0p + CB]; gb_part[blockIdx.x] = s; }
+}
+template <bool WV = false>
+static __global__ __launch_bounds__(256) void k_ip_bwd_m(const IpManyArgs a, const float* __restrict__ dz, const float* __restrict__ emb,
+                                                          float* __restrict__ gxp, float* __restrict__ gb_part)
+{
+    ip_bwd_m_body<WV>(a, dz, emb, gxp, gb_part);
 }
 
 }  // namespace

@@ -52,9 +52,9 @@ static __global__ __launch_bounds__(256) void k_ip_fwd_w_g(const IpGroupArg<T>* 
     ip_fwd_w_body<T, WV, false>(a, g[blockIdx.y].a0, nullptr, nullptr);
 }
 template <typename T, int RT>
-static __global__ __launch_bounds__(64 * STRIP_NW) void k_ip_strip_fwd_g(const IpGroupArg<T>* __restrict__ g, const int maxD)
+static __global__ __launch_bounds__(64 * STRIP_NW) void k_ip_strip_fwd_g(const IpGroupArg<T>* __restrict__ g, const int capA, const int capB)
 {
-    strip_fwd_body<T, RT, 4, STRIP_NW>(g[blockIdx.y].s, maxD);
+    strip_fwd_body<T, RT, 4, STRIP_NW>(g[blockIdx.y].s, capA, capB);
 }
 // The range bits (bit 1 of each member's error word) of the n members behind `args` (element stride `elem` bytes: both element
 // types share the header) into flags[their position], then cleared.  One workgroup; no handle is listed twice.
@@ -81,6 +81,7 @@ template <typename T> struct IpStepArg {
     int drawn;                                                   // 1: md (the library's draw), 0: mt (the caller's masks)
     MaskDrawArgs md; MaskTArgs mt;
     IpFwdArgs f; T* a0; T* a0T; float* emb;                      // the gather with its inner products
+    IpManyArgs m;                                                // ... of a many-field member (33 .. 64 fields): the 8-example forward's, and what the 4-example backward reads of them
     StripFwdArgs<T> s; StripBwdArgs<T> sb;                       // the stack, both directions
     IpBwdArgs ib; const float* dz0; float* gxp; float* gb_part;  // the inner products' backward
     IpBArgs bu;                                                  // b
@@ -108,15 +109,21 @@ static __global__ __launch_bounds__(NT) void k_ip_fwd_tg(const IpStepArg<T>* __r
     const IpFwdArgs a = g[blockIdx.y].f;
     ip_fwd_body<T, NT, WV, true>(a, g[blockIdx.y].a0, g[blockIdx.y].a0T, g[blockIdx.y].emb);
 }
-template <typename T, int RT>
-static __global__ __launch_bounds__(64 * STRIP_NW) void k_ip_strip_fwd_tg(const IpStepArg<T>* __restrict__ g, const int maxD)
+template <typename T, bool WV>
+static __global__ __launch_bounds__(256) void k_ip_fwd_m_tg(const IpStepArg<T>* __restrict__ g)
 {
-    strip_fwd_body<T, RT, 4, STRIP_NW>(g[blockIdx.y].s, maxD);
+    const IpManyArgs a = g[blockIdx.y].m;
+    ip_fwd_m_body<T, WV, true>(a, g[blockIdx.y].a0, g[blockIdx.y].a0T, g[blockIdx.y].emb);
 }
 template <typename T, int RT>
-static __global__ __launch_bounds__(64 * STRIP_NW) void k_ip_strip_bwd_g(const IpStepArg<T>* __restrict__ g, const int maxD)
+static __global__ __launch_bounds__(64 * STRIP_NW) void k_ip_strip_fwd_tg(const IpStepArg<T>* __restrict__ g, const int capA, const int capB)
 {
-    strip_bwd_body<T, RT, 4, STRIP_NW>(g[blockIdx.y].sb, maxD);
+    strip_fwd_body<T, RT, 4, STRIP_NW>(g[blockIdx.y].s, capA, capB);
+}
+template <typename T, int RT>
+static __global__ __launch_bounds__(64 * STRIP_NW) void k_ip_strip_bwd_g(const IpStepArg<T>* __restrict__ g, const int capA, const int capB)
+{
+    strip_bwd_body<T, RT, 4, STRIP_NW>(g[blockIdx.y].sb, capA, capB);
 }
 template <typename T, bool WV>
 static __global__ __launch_bounds__(256) void k_ip_bwd_g(const IpStepArg<T>* __restrict__ g)
@@ -126,6 +133,12 @@ static __global__ __launch_bounds__(256) void k_ip_bwd_g(const IpStepArg<T>* __r
     float* __restrict__ gxp = g[blockIdx.y].gxp;
     float* __restrict__ gb_part = g[blockIdx.y].gb_part;
 #include "ip_bwd_code.inc.h"
+}
+template <typename T, bool WV>
+static __global__ __launch_bounds__(256) void k_ip_bwd_m_g(const IpStepArg<T>* __restrict__ g)
+{
+    const IpManyArgs a = g[blockIdx.y].m;
+    ip_bwd_m_body<WV>(a, g[blockIdx.y].dz0, g[blockIdx.y].emb, g[blockIdx.y].gxp, g[blockIdx.y].gb_part);
 }
 // b of the SGD members, one workgroup per member; and every member's owner count at the state the sort leaves its own (0), in
 // front of level 1: a grouping class's sort prepares the count of the buffers it is given only.  An Adam / FTRL member's b is

@@ -129,7 +129,7 @@ template <typename T> struct EpiIpBwd {      // delta l_t = (delta l_{t+1} W^T) 
 // fixed costs -- per launch ~4 us of launch, ~1.5 us of pipeline fill, ~5 us of epilogue writing both
 // operand layouts and ~5 us of cold operands, against 3-8 us of L2-bound main loop -- 16 times per step.
 // Here a strip's activations stay in LDS (two ping-pong tiles in fragment order, so an A fragment is
-// one conflict-free ds_read_b128 per lane), each wave owns 64-column blocks of a layer's output and
+// one conflict-free ds_read_b128 per lane; each tile as wide as the widest layer that lands in it: capA, capB), each wave owns 64-column blocks of a layer's output and
 // streams the weights (fragment-tiled, L2-resident) straight into B fragments, and only what the
 // weight-gradient products need goes to HBM: the transposed activations / deltas.  Every workgroup
 // reads every weight once per pass: 16 RT FLOP per L2 byte, which is what bounds these kernels.
@@ -453,14 +453,14 @@ __device__ __forceinline__ void duo_swap(const StripDuo& d, T* out, const int N,
     if (dbg && threadIdx.x == 0) dbg[13] += (long long)__builtin_amdgcn_s_memtime() - ta;                  // pull (thread 0's share)
 }
 
-extern __shared__ __align__(16) unsigned char strip_smem[];   // the strip kernels' dynamic LDS: two tiles [RT * 16][maxD] (+ LDS weight copies)
+extern __shared__ __align__(16) unsigned char strip_smem[];   // the strip kernels' dynamic LDS: tiles [RT * 16][capA] and [RT * 16][capB] (+ LDS weight copies)
 template <typename T, int RT, int NF, int NW>
-__device__ __forceinline__ void strip_fwd_body(const StripFwdArgs<T>& a, const int maxD)
+__device__ __forceinline__ void strip_fwd_body(const StripFwdArgs<T>& a, const int capA, const int capB)
 {
     constexpr int EPL = Traits<T>::EPL, KS = Traits<T>::KS, PER = 4 / NF;       // NF < 4: no pairs (the host launches those without StripDuo)
-    T* in = reinterpret_cast<T*>(strip_smem);
-    T* out = in + (size_t)RT * 16 * maxD;
-    T* wl = out + (size_t)RT * 16 * maxD;                        // RT = 1: LDS copies of the small products' weights (a.wlds)
+    T* in = reinterpret_cast<T*>(strip_smem);                    // tile A: the layers at even positions of the launch's range
+    T* out = in + (size_t)RT * 16 * capA;                        // tile B: the odd ones
+    T* wl = out + (size_t)RT * 16 * capB;                        // RT = 1: LDS copies of the small products' weights (a.wlds)
     const int wave = threadIdx.x >> 6, lane = threadIdx.x & 63;
     const int h = a.duo.on ? (int)(blockIdx.x & 1) : 0, sidx = a.duo.on ? (int)(blockIdx.x >> 1) : (int)blockIdx.x;
     const int row0 = sidx * RT * 16;
@@ -479,7 +479,7 @@ __device__ __forceinline__ void strip_fwd_body(const StripFwdArgs<T>& a, const i
             bool sp; int cn; blocks(nx.p, sp, cn);
             const int wo = RT == 1 ? a.wlds[nx.p] : -1;
             // (spelled from the LDS array itself: through the captured pointer the address space was lost and the loads came out flat_)
-            if (wo >= 0) strip_prefetch<T, NF>(pb, reinterpret_cast<const T*>(strip_smem) + (size_t)2 * RT * 16 * maxD + wo, a.Dp[nx.p] / KS, strip_phys(sp, nx.blk, cn, h, rot, PER), lane);
+            if (wo >= 0) strip_prefetch<T, NF>(pb, reinterpret_cast<const T*>(strip_smem) + (size_t)RT * 16 * (capA + capB) + wo, a.Dp[nx.p] / KS, strip_phys(sp, nx.blk, cn, h, rot, PER), lane);
             else strip_prefetch<T, NF>(pb, a.W[nx.p], a.Dp[nx.p] / KS, strip_phys(sp, nx.blk, cn, h, rot, PER), lane);
         }
     };
@@ -551,21 +551,21 @@ __device__ __forceinline__ void strip_fwd_body(const StripFwdArgs<T>& a, const i
     }
 }
 template <typename T, int RT, int NF = 4, int NW = STRIP_NW>
-static __global__ __launch_bounds__(64 * NW) void k_ip_strip_fwd(const StripFwdArgs<T> a, const int maxD) { strip_fwd_body<T, RT, NF, NW>(a, maxD); }
+static __global__ __launch_bounds__(64 * NW) void k_ip_strip_fwd(const StripFwdArgs<T> a, const int capA, const int capB) { strip_fwd_body<T, RT, NF, NW>(a, capA, capB); }
 
 template <typename T, int RT, int NF, int NW>
-__device__ __forceinline__ void strip_bwd_body(const StripBwdArgs<T>& a, const int maxD)
+__device__ __forceinline__ void strip_bwd_body(const StripBwdArgs<T>& a, const int capA, const int capB)
 {
     constexpr int EPL = Traits<T>::EPL, KS = Traits<T>::KS, PER = 4 / NF;
-    T* in = reinterpret_cast<T*>(strip_smem);
-    T* out = in + (size_t)RT * 16 * maxD;
+    T* in = reinterpret_cast<T*>(strip_smem);                    // tile A: delta l_n, delta l_{n-2}, ...
+    T* out = in + (size_t)RT * 16 * capA;                        // tile B: delta l_{n-1}, ...
     const int wave = threadIdx.x >> 6, lane = threadIdx.x & 63;
     const int h = a.duo.on ? (int)(blockIdx.x & 1) : 0, sidx = a.duo.on ? (int)(blockIdx.x >> 1) : (int)blockIdx.x;
     const int row0 = sidx * RT * 16;
     STRIP_STAMP(0);
     if (a.warm) strip_warm_args<(int)sizeof(StripBwdArgs<T>)>();
     if (a.dbg && threadIdx.x == 0) { for (int i = 10; i < 16; ++i) a.dbg[(size_t)blockIdx.x * 16 + i] = 0; }
-    T* wl = out + (size_t)RT * 16 * maxD;                        // RT = 1: LDS copies of the small products' weights (a.wlds)
+    T* wl = out + (size_t)RT * 16 * capB;                        // RT = 1: LDS copies of the small products' weights (a.wlds)
     StripB<T, NF> pb;                                             // item index q = n - t: product t = n - q
     StripItem nx = strip_next(a, StripItem{0, wave - NW}, wave, false, h, PER, NW);
     const int rot = (a.rot == 1) ? (sidx >> 3) : (a.rot == 2 ? sidx : 0);   // workgroups g, g + 8, ... share an XCD
@@ -574,7 +574,7 @@ __device__ __forceinline__ void strip_bwd_body(const StripBwdArgs<T>& a, const i
         if (nx.p < a.n) {
             bool sp; int cn; blocks(nx.p, sp, cn);
             const int wo = RT == 1 ? a.wlds[a.n - nx.p - 1] : -1;
-            if (wo >= 0) strip_prefetch<T, NF>(pb, reinterpret_cast<const T*>(strip_smem) + (size_t)2 * RT * 16 * maxD + wo, a.Dp[a.n - nx.p] / KS, strip_phys(sp, nx.blk, cn, h, rot, PER), lane);
+            if (wo >= 0) strip_prefetch<T, NF>(pb, reinterpret_cast<const T*>(strip_smem) + (size_t)RT * 16 * (capA + capB) + wo, a.Dp[a.n - nx.p] / KS, strip_phys(sp, nx.blk, cn, h, rot, PER), lane);
             else strip_prefetch<T, NF>(pb, a.W[a.n - nx.p - 1], a.Dp[a.n - nx.p] / KS, strip_phys(sp, nx.blk, cn, h, rot, PER), lane);
         }
     };
@@ -614,18 +614,18 @@ __device__ __forceinline__ void strip_bwd_body(const StripBwdArgs<T>& a, const i
     }
 }
 template <typename T, int RT, int NF = 4, int NW = STRIP_NW>
-static __global__ __launch_bounds__(64 * NW) void k_ip_strip_bwd(const StripBwdArgs<T> a, const int maxD) { strip_bwd_body<T, RT, NF, NW>(a, maxD); }
+static __global__ __launch_bounds__(64 * NW) void k_ip_strip_bwd(const StripBwdArgs<T> a, const int capA, const int capB) { strip_bwd_body<T, RT, NF, NW>(a, capA, capB); }
 // The narrow tail of a training step, forward then backward, in ONE launch of 16-example strips: what the backward half reads of the
 // forward half -- the output delta (F layout, 16 x 64) and the transposed activations its act' needs -- was stored by this same
 // workgroup, so a drained store queue and a workgroup barrier order them (this CU's L1 holds none of those lines: the forward half
 // never read them; stores write through to the L2).  Saves a launch and the second tile load's cold start.
 template <typename T, int NF, int NW>
-static __global__ __launch_bounds__(64 * NW) void k_ip_strip_tail(const StripFwdArgs<T> fa, const StripBwdArgs<T> ba, const int maxD)
+static __global__ __launch_bounds__(64 * NW) void k_ip_strip_tail(const StripFwdArgs<T> fa, const StripBwdArgs<T> ba, const int capA, const int capB)
 {
-    strip_fwd_body<T, 1, NF, NW>(fa, maxD);
+    strip_fwd_body<T, 1, NF, NW>(fa, capA, capB);
     asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
     lds_barrier();
-    strip_bwd_body<T, 1, NF, NW>(ba, maxD);
+    strip_bwd_body<T, 1, NF, NW>(ba, capA, capB);
 }
 
 }  // namespace

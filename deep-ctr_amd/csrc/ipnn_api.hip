@@ -44,6 +44,7 @@ struct IpKnobs {
     int upd_side = 0;                                // IPNN_UPDATE_SIDE=1: the dense update at the end of the side chain (ip_run; measured slower)
     int mask_side = 0;                               // IPNN_MASK_SIDE=1: the mask transposition on the side stream
     int strip = 1;                                   // IPNN_STRIP=0: one GEMM launch per product instead of the strip kernels
+    int strip_l0 = 1;                                // IPNN_STRIP_L0=0: no strips for a layer 0 wider than 1024 columns (two equal tiles only: ip_strip_plan)
     int gemm_lds = 0;                                // IPNN_GEMM_LDS=1: LDS-staged k_gemm_lds for the wide products (measured equal to k_gemm_ft: both L2-bound)
     int duo = 1, duo_min = DUO_MIN_BLOCKS;           // IPNN_STRIP_DUO=0: one workgroup per strip (StripDuo); IPNN_DUO_MIN: narrowest product a pair splits
     int tail_split = 1;                              // IPNN_TAIL_SPLIT=0: the whole stack in one strip launch per direction (round 2's form)
@@ -65,13 +66,30 @@ struct IpKnobs {
 // chain), tab (its table / bias half), mask (the masks).  wg and tab: IPNN_UPDATE_SIDE=1 only; mask: IPNN_MASK_SIDE=1 only.  See IpSide.
 struct IpEvents { hipEvent_t fork = nullptr, bwd = nullptr, wg = nullptr, join = nullptr, tab = nullptr, mask = nullptr; };
 
+// What a cfg alone decides of a handle's shape (ip_dims): no device, no knob but the two of ip_many_choice.
+struct IpDims {
+    int F = 0, K = 0, L = 0, P = 0, CB = 0, rw = SLOT; bool bf16 = false, wide = false, many_fwd = false, many_bwd = false;
+    int d[IPNN_MAX_HIDDEN + 2] = {}, Dp[IPNN_MAX_HIDDEN + 2] = {};     // layer widths 0 .. L + 1, and padded
+};
+// The two LDS tiles of one strip launch: a strip's layers alternate between tile A and tile B, so each is as wide as the widest
+// layer that lands in it over the launch's range; lds: both tiles of the launch's strip height.
+struct IpTiles { int capA = 0, capB = 0; size_t lds = 0; };
+constexpr size_t IP_STRIP_LDS_MAX = (size_t)160 * 1024;
+// The strip side of the plan: a function of the padded widths, the element type and the knobs (ip_strip_plan), shared by
+// ipnn_create and ipnn_plan_query.  Tiles of launches the handle never issues stay zero.
+struct IpStrips {
+    int maxD = 0;                                    // widest padded layer (sizes the pairs' exchange buffer)
+    bool strip = false;                              // the strip kernels run the stack: IPNN_STRIP, and every launch below fits the LDS
+    bool pairs = false;                              // ... on strips of 32 examples (bf16) with IPNN_STRIP_DUO: a batch whose pairs fit the chip takes them
+    int cut = 0, maxD2 = 0;                          // products 1 .. cut are wide enough for pairs; widest layer from `cut` on
+    bool splits = false;                             // a batch that runs pairs splits the stack at `cut` (IPNN_TAIL_SPLIT, 1 <= cut < L)
+    IpTiles fwd, bwd;                                // the whole stack in one launch per direction
+    IpTiles wide_fwd, wide_bwd;                      // products 1 .. cut as pairs of strips
+    IpTiles tail_fwd, tail_bwd, tail;                // products cut + 1 .. L + 1 on 16-example strips; tail: both directions in one launch
+};
 // What the handle's shape and knobs decide of a step: made once, at the end of ipnn_create (ip_make_plan).  What the batch length
 // adds is IpCall's (ip_form).  The cut between wide products and narrow tail: DESIGN.md section 4, round 3.
-struct IpPlan {
-    int maxD = 0; size_t strip_lds = 0;              // widest padded layer: the strips' tile width; two tiles of a strip
-    bool strip = false;                              // the strip kernels run the stack: IPNN_STRIP, and strip_lds <= 128 KiB
-    bool pairs = false;                              // ... on strips of 32 examples (bf16) with IPNN_STRIP_DUO: a batch whose pairs fit the chip takes them
-    int cut = 0, maxD2 = 0; size_t tail_lds = 0;     // products 1 .. cut are wide enough for pairs; widest layer from `cut` on, and the tail's two tiles
+struct IpPlan : IpStrips {
     size_t off[IPNN_MAX_HIDDEN + 2] = {};            // element offset of product t's gradient in a slab (index t - 1); off[L + 1]: a slab's elements
     int wg_order[IPNN_MAX_HIDDEN + 1] = {};          // the products by size, widest first: the order of the grouped weight-gradient launch
     GemmGroupArgs group{};                           // that launch's arguments, all but nkt (the batch's k-steps)
@@ -84,7 +102,7 @@ struct IpPlan {
 struct ipnn_handle {
     ipnn_cfg cfg{}; std::string err; int dev = 0; hipStream_t st = nullptr; bool own_stream = false;
     int F = 0, K = 0, L = 0, P = 0, CB = 0, Bmax = 0, ldT = 0; bool bf16 = false; int splitk = 8;   // splitk: slab capacity
-    IpKnobs kn; IpPlan plan;
+    IpKnobs kn; IpDims dims; IpPlan plan;             // dims: the cfg's shape (ip_dims), copied into F, K, L ... d, Dp below
     bool wide = false;                           // k >= 17: wide rows (k_ip_fwd_w / k_ip_bwd_w, k_ip_scatw1 / k_ip_scatw2), chosen at create
     int rw = SLOT;                               // row stride of the table and field stride of layer 0: SLOT, or rup(k, 4) when wide
     int* noshare = nullptr;                      // wide: [n_rows] zeros, the wide scatter's tag_shared (a row belongs to one field)
@@ -160,7 +178,7 @@ IpKnobs ip_read_knobs()
     IpKnobs k;
     const struct { const char* name; int* v; bool flag; } plain[] = {     // flag: 0 / 1, whatever number is given
         {"IPNN_SIDE_STREAM", &k.side_stream, true}, {"IPNN_UPDATE_SIDE", &k.upd_side, true}, {"IPNN_MASK_SIDE", &k.mask_side, false},
-        {"IPNN_STRIP", &k.strip, true}, {"IPNN_GEMM_LDS", &k.gemm_lds, true}, {"IPNN_STRIP_DUO", &k.duo, false}, {"IPNN_DUO_MIN", &k.duo_min, false},
+        {"IPNN_STRIP", &k.strip, true}, {"IPNN_STRIP_L0", &k.strip_l0, true}, {"IPNN_GEMM_LDS", &k.gemm_lds, true}, {"IPNN_STRIP_DUO", &k.duo, false}, {"IPNN_DUO_MIN", &k.duo_min, false},
         {"IPNN_TAIL_SPLIT", &k.tail_split, false}, {"IPNN_TAIL_FUSE", &k.tail_fuse, true}, {"IPNN_TAIL_LDS", &k.tail_w_lds, false},
         {"IPNN_STRIP_ROT", &k.strip_rot, false}, {"IPNN_FWD_SKIP", &k.fwd_skip, false}, {"IPNN_STRIP_WARM", &k.strip_warm, false},
         {"IPNN_GROUP_WGRAD", &k.group_wgrad, true}, {"IPNN_GROUP_XCD", &k.group_xcd, false}, {"IPNN_STAMP_SEL", &k.stamp_sel, false}};
@@ -282,10 +300,11 @@ template <typename T> IpKernel ip_gather_fwd_g_sel(IpRows rows, bool wv, int nt)
     return wv ? IP_K(IPF_NT, k_ip_fwd_g<T, IPF_NT, true>) : IP_K(IPF_NT, k_ip_fwd_g<T, IPF_NT, false>);
 }
 template <typename T> IpKernel ip_strip_g_sel() { return IP_K(64 * STRIP_NW, k_ip_strip_fwd_g<T, sizeof(T) == 2 ? 2 : 1>); }
-// the group forms of the training step (ipnn_train_step_multi; narrow rows, up to 32 fields): the gather that also writes the T
-// layout and the embeddings, the whole stack on single strips in either direction, the inner products' backward
-template <typename T> IpKernel ip_step_gather_sel(bool wv, int nt)
+// the group forms of the training step (ipnn_train_step_multi; narrow rows, by row kind per direction): the gather that also
+// writes the T layout and the embeddings, the whole stack on single strips in either direction, the inner products' backward
+template <typename T> IpKernel ip_step_gather_sel(IpRows rows, bool wv, int nt)
 {
+    if (rows == IP_MANY) return wv ? IP_K(256, k_ip_fwd_m_tg<T, true>) : IP_K(256, k_ip_fwd_m_tg<T, false>);
     if (nt == 1024) return wv ? IP_K(1024, k_ip_fwd_tg<T, 1024, true>) : IP_K(1024, k_ip_fwd_tg<T, 1024, false>);
     return wv ? IP_K(IPF_NT, k_ip_fwd_tg<T, IPF_NT, true>) : IP_K(IPF_NT, k_ip_fwd_tg<T, IPF_NT, false>);
 }
@@ -294,7 +313,11 @@ template <typename T> IpKernel ip_step_strip_sel(bool bwd)
     constexpr int RT = sizeof(T) == 2 ? 2 : 1;
     return bwd ? IP_K(64 * STRIP_NW, k_ip_strip_bwd_g<T, RT>) : IP_K(64 * STRIP_NW, k_ip_strip_fwd_tg<T, RT>);
 }
-template <typename T> IpKernel ip_step_bwd_sel(bool wv) { return wv ? IP_K(256, k_ip_bwd_g<T, true>) : IP_K(256, k_ip_bwd_g<T, false>); }
+template <typename T> IpKernel ip_step_bwd_sel(IpRows rows, bool wv)
+{
+    if (rows == IP_MANY) return wv ? IP_K(256, k_ip_bwd_m_g<T, true>) : IP_K(256, k_ip_bwd_m_g<T, false>);
+    return wv ? IP_K(256, k_ip_bwd_g<T, true>) : IP_K(256, k_ip_bwd_g<T, false>);
+}
 IpKernel ip_gather_bwd_sel(IpRows rows, bool wv)
 {
     if (rows == IP_WIDE) return wv ? IP_K(256, k_ip_bwd_w<true>) : IP_K(256, k_ip_bwd_w<false>);
@@ -303,27 +326,27 @@ IpKernel ip_gather_bwd_sel(IpRows rows, bool wv)
 }
 
 // > 64 KiB of dynamic LDS needs the opt-in, once per device: every kernel a selector can return for a form the knobs can name gets
-// its family's ceiling -- 128 KiB for the 32-example strips, 160 KiB for the 16-example ones and the fused tail, ip_rows_lds_kib for
-// the gathers.  (A form named twice is set twice: the same value.)
+// its family's ceiling -- 160 KiB for the strips and the fused tail (IP_STRIP_LDS_MAX: what ip_strip_plan holds every launch to),
+// ip_rows_lds_kib for the gathers.  (A form named twice is set twice: the same value.)
 template <typename T> int ip_opt_in(ipnn_handle* h)
 {
     constexpr int RT = sizeof(T) == 2 ? 2 : 1;
     auto set = [](const IpKernel& k, int kib) { return hipFuncSetAttribute(k.fn, hipFuncAttributeMaxDynamicSharedMemorySize, kib * 1024); };
     for (int bwd = 0; bwd < 2; ++bwd)
         for (int rt : {RT, 1}) for (int nf : {1, 2, 4}) for (int nw : {8, 12, 16})
-            IHK(h, set(ip_strip_sel<T>(bwd != 0, rt, nf, nw), rt == 2 ? 128 : 160));
+            IHK(h, set(ip_strip_sel<T>(bwd != 0, rt, nf, nw), 160));
     IHK(h, set(ip_strip_tail_sel<T>(), 160));
     for (IpRows r : {IP_NARROW, IP_WIDE, IP_MANY}) for (int wv = 0; wv < 2; ++wv) {
         for (int nt : {512, 1024}) IHK(h, set(ip_gather_fwd_sel<T>(r, wv != 0, nt), ip_rows_lds_kib(r)));
         for (int nt : {512, 1024}) IHK(h, set(ip_gather_fwd_g_sel<T>(r, wv != 0, nt), ip_rows_lds_kib(r)));
         IHK(h, set(ip_gather_bwd_sel(r, wv != 0), ip_rows_lds_kib(r)));
     }
-    IHK(h, set(ip_strip_g_sel<T>(), RT == 2 ? 128 : 160));
-    for (int wv = 0; wv < 2; ++wv) {
-        for (int nt : {512, 1024}) IHK(h, set(ip_step_gather_sel<T>(wv != 0, nt), ip_rows_lds_kib(IP_NARROW)));
-        IHK(h, set(ip_step_bwd_sel<T>(wv != 0), ip_rows_lds_kib(IP_NARROW)));
+    IHK(h, set(ip_strip_g_sel<T>(), 160));
+    for (IpRows r : {IP_NARROW, IP_MANY}) for (int wv = 0; wv < 2; ++wv) {
+        for (int nt : {512, 1024}) IHK(h, set(ip_step_gather_sel<T>(r, wv != 0, nt), ip_rows_lds_kib(r)));
+        IHK(h, set(ip_step_bwd_sel<T>(r, wv != 0), ip_rows_lds_kib(r)));
     }
-    for (int bwd = 0; bwd < 2; ++bwd) IHK(h, set(ip_step_strip_sel<T>(bwd != 0), RT == 2 ? 128 : 160));
+    for (int bwd = 0; bwd < 2; ++bwd) IHK(h, set(ip_step_strip_sel<T>(bwd != 0), 160));
     return FNN_OK;
 }
 
@@ -342,21 +365,108 @@ inline bool ip_many_choice(int F, int Dp0, int dflt, const char* knob)
     return F >= mn || ip16_lds(F, Dp0) > (size_t)160 * 1024;
 }
 
+// What ipnn_create refuses of a cfg for its shape (the message: g_ip_err).  No device is asked.
+int ip_cfg_check(const ipnn_cfg* cfg)
+{
+    if (cfg->k < 1 || cfg->k > 128) {
+        g_ip_err = "bad shape: k = " + std::to_string(cfg->k) + " (k = rank+1 must be 1..128)"; return FNN_ERR_ARG; }
+    if (cfg->n_fields < 2 || cfg->n_fields > 64) {
+        g_ip_err = "bad shape: n_fields = " + std::to_string(cfg->n_fields) + " (2..64 fields of k <= 16, 2..32 fields of k = 17..128: more is not built)"; return FNN_ERR_ARG; }
+    if (cfg->k > SLOT && cfg->n_fields > 32) {
+        g_ip_err = "bad shape: n_fields = " + std::to_string(cfg->n_fields) + " with k = " + std::to_string(cfg->k) +
+                   " (wide rows, k = 17..128, take 2..32 fields: more than 32 is not built; k <= 16 takes 2..64)"; return FNN_ERR_ARG; }
+    if (cfg->n_hidden < 1 || cfg->n_hidden > IPNN_MAX_HIDDEN ||
+        cfg->max_batch < 1 || cfg->max_batch > 4096 || !(cfg->keep_prob > 0.f && cfg->keep_prob <= 1.f)) {
+        g_ip_err = "bad shape (2..64 fields of k <= 16 or 2..32 fields of k = 17..128, 1..8 hidden layers, batch <= 4096, 0 < keep_prob <= 1)"; return FNN_ERR_ARG; }
+    if (cfg->act != A_TANH && cfg->act != A_SIG && cfg->act != A_RELU) { g_ip_err = "bad act"; return FNN_ERR_ARG; }
+    if (cfg->precision != FNN_PREC_F32 && cfg->precision != FNN_PREC_BF16) { g_ip_err = "bad precision (FNN_PREC_F32 or FNN_PREC_BF16; FNN_PREC_BF16X3 is the FNN / SNN engine's)"; return FNN_ERR_ARG; }
+    if (cfg->optimizer != IPNN_OPT_SGD && cfg->optimizer != IPNN_OPT_ADAM && cfg->optimizer != IPNN_OPT_FTRL) { g_ip_err = "bad optimizer"; return FNN_ERR_ARG; }
+    if (cfg->optimizer == IPNN_OPT_ADAM && !(cfg->adam_eps > 0.f)) { g_ip_err = "Adam needs adam_eps > 0"; return FNN_ERR_ARG; }
+    for (int t = 0; t < cfg->n_hidden; ++t) if (cfg->hidden[t] < 1 || cfg->hidden[t] > 4095) { g_ip_err = "hidden size out of range"; return FNN_ERR_ARG; }
+    return FNN_OK;
+}
+
+// the shape of a checked cfg: row layout, layer widths and their padding, the inner-product kernels per direction
+IpDims ip_dims(const ipnn_cfg& cfg)
+{
+    IpDims m;
+    m.F = cfg.n_fields; m.K = cfg.k; m.L = cfg.n_hidden; m.bf16 = cfg.precision == FNN_PREC_BF16;
+    m.wide = m.K > SLOT; m.rw = m.wide ? rup(m.K, 4) : SLOT;
+    m.P = cfg.pairs ? m.F * (m.F - 1) / 2 : 0; m.CB = m.F * m.rw + m.P;
+    m.d[0] = m.F * m.K + m.P + 1; m.Dp[0] = rup(m.CB + 2, 64);
+    for (int t = 1; t <= m.L; ++t) { m.d[t] = cfg.hidden[t - 1]; m.Dp[t] = rup(m.d[t] + 1, 64); }
+    m.d[m.L + 1] = 1; m.Dp[m.L + 1] = 64;
+    m.many_fwd = !m.wide && ip_many_choice(m.F, m.Dp[0], IPM_FWD_MIN_FIELDS, "IPNN_MANY_FWD_MIN");
+    m.many_bwd = !m.wide && ip_many_choice(m.F, m.Dp[0], IPM_BWD_MIN_FIELDS, "IPNN_MANY_MIN");
+    return m;
+}
+
+// The tiles of a launch that keeps m + 1 layers in LDS, the i-th of them Dp[first + i * dir] columns wide: even i in tile A, odd
+// i in tile B.  rows_bytes: a column of a strip (16 or 32 examples of the element type).
+IpTiles ip_tiles_of(const int* Dp, int first, int dir, int m, size_t rows_bytes)
+{
+    IpTiles t;
+    for (int i = 0; i <= m; ++i) { int& cap = (i & 1) ? t.capB : t.capA; cap = std::max(cap, Dp[first + i * dir]); }
+    t.lds = rows_bytes * (size_t)(t.capA + t.capB);
+    return t;
+}
+// Forward over Dp[lo .. lo + n]: the strip of layer lo in tile A, then one layer per product; the output unit (has_out) is never tiled.
+IpTiles ip_tiles_fwd(const int* Dp, int lo, int n, bool has_out, size_t rows_bytes) { return ip_tiles_of(Dp, lo, 1, has_out ? n - 1 : n, rows_bytes); }
+// Backward over Dp[lo .. lo + n]: delta l_{lo + n} in tile A, then downwards; the stack's bottom (dz1: f32, row-major, to memory) is never tiled.
+IpTiles ip_tiles_bwd(const int* Dp, int lo, int n, bool bottom, size_t rows_bytes) { return ip_tiles_of(Dp, lo + n, -1, bottom ? n - 1 : n, rows_bytes); }
+
+// Which launches run the deep stack, and their tiles.  Up to 32 fields, and up to a layer 0 of 1024 columns: two equal tiles as
+// wide as the widest layer of the launch's range, and strips while they fit 128 KiB.  A wider layer 0 of more than 32 fields
+// (33 and more with pairs, 64 without): each launch gets the two widths its own layers need -- layer 0 is in a tile only going forward, and then it
+// never shares one with layer 1 -- and the handle runs strips when every launch of its forms fits the 160 KiB of LDS.
+// IPNN_STRIP_L0=0 keeps the first rule for every handle.
+IpStrips ip_strip_plan(const IpDims& m, const IpKnobs& kn)
+{
+    IpStrips p;
+    const int L = m.L, *Dp = m.Dp;
+    const int RT = m.bf16 ? 2 : 1;                               // strip = 32 (bf16) / 16 (f32) examples
+    const size_t es = m.bf16 ? 2 : 4, rows = (size_t)RT * 16 * es, rows16 = 16 * es;
+    for (int t = 0; t <= L + 1; ++t) p.maxD = std::max(p.maxD, Dp[t]);
+    p.cut = L;
+    while (p.cut >= 1 && Dp[p.cut] / 64 < kn.duo_min) --p.cut;
+    for (int t = p.cut; t <= L + 1; ++t) p.maxD2 = std::max(p.maxD2, Dp[t]);
+    const bool pairs = kn.duo && RT == 2, splits = pairs && kn.tail_split && p.cut >= 1 && p.cut < L;
+    const bool equal_tiles = m.F <= 32 || Dp[0] <= 1024 || !kn.strip_l0;
+    auto equal = [](int w, size_t rb) { return IpTiles{w, w, 2 * rb * (size_t)w}; };
+    IpStrips q = p;
+    if (equal_tiles) {
+        q.fwd = q.bwd = equal(p.maxD, rows);
+        if (splits) { q.wide_fwd = q.wide_bwd = q.fwd; q.tail_fwd = q.tail_bwd = q.tail = equal(p.maxD2, rows16); }
+        q.strip = kn.strip && q.fwd.lds <= (size_t)128 * 1024;
+    } else {
+        q.fwd = ip_tiles_fwd(Dp, 0, L + 1, true, rows); q.bwd = ip_tiles_bwd(Dp, 0, L + 1, true, rows);
+        if (splits) {
+            q.wide_fwd = ip_tiles_fwd(Dp, 0, p.cut, false, rows); q.wide_bwd = ip_tiles_bwd(Dp, 0, p.cut, true, rows);
+            q.tail_fwd = ip_tiles_fwd(Dp, p.cut, L + 1 - p.cut, true, rows16); q.tail_bwd = ip_tiles_bwd(Dp, p.cut, L + 1 - p.cut, false, rows16);
+            q.tail.capA = std::max(q.tail_fwd.capA, q.tail_bwd.capA); q.tail.capB = std::max(q.tail_fwd.capB, q.tail_bwd.capB);
+            q.tail.lds = rows16 * (size_t)(q.tail.capA + q.tail.capB);
+        }
+        q.strip = kn.strip;
+        for (const IpTiles* t : {&q.fwd, &q.bwd, &q.wide_fwd, &q.wide_bwd, &q.tail_fwd, &q.tail_bwd, &q.tail}) q.strip = q.strip && t->lds <= IP_STRIP_LDS_MAX;
+    }
+    if (!q.strip) return p;                                      // the GEMM path: no strip launch, no tiles
+    q.pairs = pairs; q.splits = splits;
+    return q;
+}
+// a handle shares the launches of ipnn_train_step_multi when every stage of its solo step has a group form that computes the same
+// bits: the strip kernels on narrow rows (k <= 16, any field count), the grouped weight-gradient launch, no diagnostic knob
+bool ip_shares_step(const IpStrips& p, const IpDims& m, const IpKnobs& kn)
+{
+    return p.strip && !m.wide && kn.group_wgrad && m.L + 1 <= GEMM_GROUP_MAX && !kn.fwd_skip && !kn.stamps;
+}
+
 template <typename T> void ip_make_plan(ipnn_handle* h)
 {
     IpPlan& p = h->plan;
     const IpKnobs& kn = h->kn;
     const int L = h->L;
     constexpr int KS = Traits<T>::KS;
-    constexpr int RT = sizeof(T) == 2 ? 2 : 1;                   // strip = 32 (bf16) / 16 (f32) examples: two LDS tiles of 64 KiB at 1024 units
-    for (int t = 0; t <= L + 1; ++t) p.maxD = std::max(p.maxD, h->Dp[t]);
-    p.strip_lds = (size_t)2 * RT * 16 * p.maxD * sizeof(T);
-    p.strip = kn.strip && p.strip_lds <= 128 * 1024;
-    p.pairs = p.strip && kn.duo && RT == 2;
-    p.cut = L;
-    while (p.cut >= 1 && h->Dp[p.cut] / 64 < kn.duo_min) --p.cut;
-    for (int t = p.cut; t <= L + 1; ++t) p.maxD2 = std::max(p.maxD2, h->Dp[t]);
-    p.tail_lds = (size_t)2 * 16 * p.maxD2 * sizeof(T);
+    static_cast<IpStrips&>(p) = ip_strip_plan(h->dims, kn);
     for (int t = 0; t <= L; ++t) p.mask_cols64[t] = h->Dp[t] / 64;
     for (int t = 1; t <= L + 1; ++t) { p.off[t] = p.off[t - 1] + (size_t)h->Dp[t - 1] * h->Dp[t]; p.wg_order[t - 1] = t; }
     std::sort(p.wg_order, p.wg_order + L + 1, [&](int x, int y) { return (size_t)h->Dp[x - 1] * h->Dp[x] > (size_t)h->Dp[y - 1] * h->Dp[y]; });
@@ -421,7 +531,7 @@ void ip_form(const ipnn_handle* h, IpCall& c)
     // two workgroups per strip (StripDuo) where the pairs fit the chip at one workgroup per CU: both halves of a pair must be
     // resident to swap (bf16 strips of 32 examples: 256 workgroups at batch 4096)
     c.duo = p.pairs && 2 * c.nstrips <= h->n_cu;
-    c.tsplit = p.strip && c.duo && kn.tail_split && p.cut >= 1 && p.cut < h->L;
+    c.tsplit = c.duo && p.splits;
     // training steps: the forward tail rides in the backward tail's launch (k_ip_strip_tail; IPNN_TAIL_FUSE=0: two launches)
     c.fuse_tail = c.tsplit && c.train && kn.tail_fuse && kn.tail_nf == 1 && kn.tail_nw == 16 && !kn.tail_w_lds;
     c.drop = c.train && (c.masks || c.draw);
@@ -593,11 +703,9 @@ template <typename T> int ip_duo_ready(ipnn_handle* h)
 // IPNN_TAIL_LDS=1: small products of a 16-example-strip launch whose weights go to LDS behind the tiles: each up to 64 KB, all of them
 // within what is left of 152 KB.  Returns the bytes they take, fills the element offsets (-1: from memory).  OFF by default: measured
 // (profiles/r03d_ipnn_tail_lds_ab.json) the 88 KB copy costs more than the k-steps it shortens.
-template <typename T> size_t ip_tail_weights(const ipnn_handle* h, const int* Dp, int n, int* wlds)
+template <typename T> size_t ip_tail_weights(const ipnn_handle* h, const int* Dp, int n, size_t tiles, int* wlds)
 {
-    int maxd = 0;
-    for (int t = 0; t <= n; ++t) maxd = std::max(maxd, Dp[t]);
-    const size_t tiles = (size_t)2 * 16 * maxd * sizeof(T), budget = (size_t)152 * 1024 > tiles ? (size_t)152 * 1024 - tiles : 0;
+    const size_t budget = (size_t)152 * 1024 > tiles ? (size_t)152 * 1024 - tiles : 0;
     size_t used = 0;
     for (int p = 0; p < n; ++p) {
         const size_t b = (size_t)Dp[p] * Dp[p + 1] * sizeof(T);
@@ -651,14 +759,14 @@ template <typename T> int ip_strips_fwd(ipnn_handle* h, const IpCall& c, StripFw
     StripFwdArgs<T> sa = ip_stack_fwd_args<T>(h, c);
     if (!c.tsplit) {
         sa.duo = ip_strip_duo(h, false, c.duo);
-        IHK(h, ip_launch(ip_strip_sel<T>(false, RT, 4, STRIP_NW), c.nstrips * (c.duo ? 2 : 1), p.strip_lds, h->st, sa, p.maxD));
+        IHK(h, ip_launch(ip_strip_sel<T>(false, RT, 4, STRIP_NW), c.nstrips * (c.duo ? 2 : 1), p.fwd.lds, h->st, sa, p.fwd.capA, p.fwd.capB));
         return FNN_OK;
     }
     StripFwdArgs<T> s1 = sa;                                  // products 1 .. cut: pairs of 32-example strips; a[cut] -> HBM
     s1.n = cut; s1.has_out = 0; s1.finalF = (T*)h->a[cut];
     s1.duo = ip_strip_duo(h, false, true);
     if (kn.stamps == 2) s1.dbg = nullptr;
-    IHK(h, ip_launch(ip_strip_sel<T>(false, RT, kn.wide_nf, kn.wide_nw), c.nstrips * 2, p.strip_lds, h->st, s1, p.maxD));
+    IHK(h, ip_launch(ip_strip_sel<T>(false, RT, kn.wide_nf, kn.wide_nw), c.nstrips * 2, p.wide_fwd.lds, h->st, s1, p.wide_fwd.capA, p.wide_fwd.capB));
     StripFwdArgs<T> s2{};                                     // products cut + 1 .. L + 1: 16-example strips, every CU
     s2.a0 = (const T*)h->a[cut]; s2.n = L + 1 - cut;
     for (int t = cut; t <= L + 1; ++t) s2.Dp[t - cut] = h->Dp[t];
@@ -666,9 +774,9 @@ template <typename T> int ip_strips_fwd(ipnn_handle* h, const IpCall& c, StripFw
     for (int t = cut + 1; t <= L; ++t) s2.ef[t - cut - 1] = sa.ef[t - 1];
     s2.eo = sa.eo; s2.dbg = kn.stamps == 2 ? h->stamps : nullptr; s2.rot = kn.strip_rot; s2.sel = -1; s2.has_out = 1; s2.finalF = nullptr; s2.warm = sa.warm;
     s2.duo = ip_strip_duo(h, true, false);
-    const size_t wl2 = ip_tail_weights<T>(h, s2.Dp, s2.n, s2.wlds);
+    const size_t wl2 = ip_tail_weights<T>(h, s2.Dp, s2.n, p.tail_fwd.lds, s2.wlds);
     if (c.fuse_tail) *fused_tail = s2;
-    else IHK(h, ip_launch(ip_strip_sel<T>(false, 1, kn.tail_nf, kn.tail_nw), c.Ba / 16, p.tail_lds + wl2, h->st, s2, p.maxD2));
+    else IHK(h, ip_launch(ip_strip_sel<T>(false, 1, kn.tail_nf, kn.tail_nw), c.Ba / 16, p.tail_fwd.lds + wl2, h->st, s2, p.tail_fwd.capA, p.tail_fwd.capB));
     return FNN_OK;
 }
 
@@ -684,7 +792,7 @@ template <typename T> int ip_strips_bwd(ipnn_handle* h, const IpCall& c, const S
     StripBwdArgs<T> sb = ip_stack_bwd_args<T>(h, c);
     if (!c.tsplit) {
         sb.duo = ip_strip_duo(h, false, c.duo);
-        IHK(h, ip_launch(ip_strip_sel<T>(true, RT, 4, STRIP_NW), c.nstrips * (c.duo ? 2 : 1), p.strip_lds, h->st, sb, p.maxD));
+        IHK(h, ip_launch(ip_strip_sel<T>(true, RT, 4, STRIP_NW), c.nstrips * (c.duo ? 2 : 1), p.bwd.lds, h->st, sb, p.bwd.capA, p.bwd.capB));
         return FNN_OK;
     }
     StripBwdArgs<T> sA{};                                     // products L + 1 .. cut + 1 (the narrow ones come first): 16-example strips
@@ -693,14 +801,14 @@ template <typename T> int ip_strips_bwd(ipnn_handle* h, const IpCall& c, const S
     for (int t = cut + 1; t <= L + 1; ++t) { sA.W[t - cut - 1] = sb.W[t - 1]; sA.eb[t - cut - 1] = sb.eb[t - 1]; }
     sA.dbg = kn.stamps == 2 ? sb.dbg : nullptr; sA.rot = kn.strip_rot; sA.bottom = 0; sA.finalF = (T*)h->dl[cut - 1]; sA.warm = sb.warm;
     sA.duo = ip_strip_duo(h, true, false);
-    const size_t wlA = ip_tail_weights<T>(h, sA.Dp, sA.n, sA.wlds);
-    if (c.fuse_tail) IHK(h, ip_launch(ip_strip_tail_sel<T>(), c.Ba / 16, p.tail_lds, h->st, fused_tail, sA, p.maxD2));
-    else IHK(h, ip_launch(ip_strip_sel<T>(true, 1, kn.tail_nf, kn.tail_nw), c.Ba / 16, p.tail_lds + wlA, h->st, sA, p.maxD2));
+    const size_t wlA = ip_tail_weights<T>(h, sA.Dp, sA.n, p.tail_bwd.lds, sA.wlds);
+    if (c.fuse_tail) IHK(h, ip_launch(ip_strip_tail_sel<T>(), c.Ba / 16, p.tail.lds, h->st, fused_tail, sA, p.tail.capA, p.tail.capB));
+    else IHK(h, ip_launch(ip_strip_sel<T>(true, 1, kn.tail_nf, kn.tail_nw), c.Ba / 16, p.tail_bwd.lds + wlA, h->st, sA, p.tail_bwd.capA, p.tail_bwd.capB));
     StripBwdArgs<T> sB = sb;                                  // products cut .. 1: pairs of 32-example strips, from delta l_cut in HBM
     sB.dlast = (const T*)h->dl[cut - 1]; sB.n = cut;
     if (kn.stamps == 2) sB.dbg = nullptr;
     sB.duo = ip_strip_duo(h, false, true);
-    IHK(h, ip_launch(ip_strip_sel<T>(true, RT, kn.wide_nf, kn.wide_nw), c.nstrips * 2, p.strip_lds, h->st, sB, p.maxD));
+    IHK(h, ip_launch(ip_strip_sel<T>(true, RT, kn.wide_nf, kn.wide_nw), c.nstrips * 2, p.wide_bwd.lds, h->st, sB, p.wide_bwd.capA, p.wide_bwd.capB));
     return FNN_OK;
 }
 
@@ -958,11 +1066,12 @@ int ip_group_check(const IpGroup& g, const int32_t* ids, bool need_y, const int3
 // gather's row kind (with its block size, and the row width of wide rows: they size its LDS), pairs, weights given or not.
 // Activation, k, table size and every parameter value may differ inside a class.  members: positions in the list, in its order.
 struct IpPredClass {
-    bool bf16; int L; int Dp[STRIP_MAXP + 1]; IpRows rows; int nt, rw, P; bool wv;
+    bool bf16; int L; int Dp[STRIP_MAXP + 1]; IpRows rows; int nt, rw, P; bool wv; int capA, capB;      // capA, capB: the forward launch's tiles
     std::vector<int> members;
     bool same(const IpPredClass& o) const
     {
         if (bf16 != o.bf16 || L != o.L || rows != o.rows || nt != o.nt || rw != o.rw || P != o.P || wv != o.wv) return false;
+        if (capA != o.capA || capB != o.capB) return false;
         for (int t = 0; t <= L + 1; ++t) if (Dp[t] != o.Dp[t]) return false;
         return true;
     }
@@ -971,6 +1080,7 @@ IpPredClass ip_pred_class_of(const ipnn_handle* h, bool wv)
 {
     IpPredClass c{};
     c.bf16 = h->bf16; c.L = h->L; c.rows = ip_fwd_rows(h); c.nt = c.rows == IP_NARROW ? h->kn.ipf_nt : 256; c.rw = h->rw; c.P = h->P; c.wv = wv;
+    c.capA = h->plan.fwd.capA; c.capB = h->plan.fwd.capB;
     for (int t = 0; t <= h->L + 1; ++t) c.Dp[t] = h->Dp[t];
     return c;
 }
@@ -1006,8 +1116,8 @@ template <typename T> hipError_t ip_launch_class(const ipnn_handle* h, const IpP
     const size_t lds = c.rows == IP_WIDE ? ipw_fwd_lds(h->F, h->rw) : c.rows == IP_MANY ? ipm_fwd_lds(h->F) : ip16_lds(h->F, h->Dp[0]);
     hipError_t e = ip_launch(ip_gather_fwd_g_sel<T>(c.rows, c.wv, c.nt), dim3((unsigned)(Ba / ex), M), lds, st, d);
     if (e != hipSuccess) return e;
-    const int maxD = h->plan.maxD;
-    return ip_launch(ip_strip_g_sel<T>(), dim3((unsigned)(Ba / (16 * RT)), M), h->plan.strip_lds, st, d, maxD);
+    const IpTiles& tl = h->plan.fwd;
+    return ip_launch(ip_strip_g_sel<T>(), dim3((unsigned)(Ba / (16 * RT)), M), tl.lds, st, d, tl.capA, tl.capB);
 }
 
 // The predictions of the n members hs[0 .. n) of group `g` (positions base .. in the call) on the N lines, p[m] each.  Members on
@@ -1076,20 +1186,19 @@ int ip_group_forward(const IpGroup& g, ipnn_handle* const* hs, int n, int base, 
 struct IpStepGroup : GroupCall<ipnn_handle> {
     IpStepGroup(ipnn_handle* const* hs_, int n_) : GroupCall("ipnn_train_step_multi", hs_, n_, IPNN_STEP_MAX_MODELS, g_ip_err, ip_join) {}
 };
-// A member shares the group launches when every stage of its solo step has a group form that computes the same bits: the strip
-// kernels on narrow rows of up to 32 fields in both directions, the grouped weight-gradient launch, no diagnostic knob.
-bool ip_step_shares(const ipnn_handle* h)
-{
-    return h->plan.strip && ip_fwd_rows(h) == IP_NARROW && ip_bwd_rows(h) == IP_NARROW && h->kn.group_wgrad && h->L + 1 <= GEMM_GROUP_MAX &&
-           !h->kn.fwd_skip && !h->kn.stamps && !h->prof;
-}
-// A training LAUNCH CLASS: the prediction launch class (element type, depth, padded widths, the gather's block size, pairs,
-// weights given or not) and the tiles of the grouped weight-gradient launch (the split-K of every product).  Everything else that
+// A member shares the group launches when its plan says so (ip_shares_step) and its segments are not being timed.
+bool ip_step_shares(const ipnn_handle* h) { return ip_shares_step(h->plan, h->dims, h->kn) && !h->prof; }
+// A training LAUNCH CLASS: the prediction launch class (element type, depth, padded widths, the gather's row kind and block size,
+// pairs, weights given or not, the forward tiles), the row kind and the tiles of the backward, and the tiles of the grouped
+// weight-gradient launch (the split-K of every product).  Everything else that
 // differs between two members is a run-time field of their records: the scatter forms, wt, the optimiser, act, k, every value.
 // Its members are pc.members.
 struct IpStepClass {
-    IpPredClass pc; int n_wg;
-    bool same(const IpStepClass& o) const { return pc.same(o.pc) && n_wg == o.n_wg; }
+    IpPredClass pc; int n_wg; IpRows rows_bwd; int capA_bwd, capB_bwd;
+    bool same(const IpStepClass& o) const
+    {
+        return pc.same(o.pc) && n_wg == o.n_wg && rows_bwd == o.rows_bwd && capA_bwd == o.capA_bwd && capB_bwd == o.capB_bwd;
+    }
 };
 // A GROUPING CLASS: members whose sparse-row updates read one grouping of the batch's ids -- the same keys (n_rows, key width)
 // sorted the same way (runs) -- made once, in the first member's buffers.
@@ -1112,12 +1221,15 @@ template <typename T> void ip_fill_step_arg(ipnn_handle* h, int model, const IpC
     r.drawn = c.draw ? 1 : 0;
     if (c.drop && c.draw) r.md = ip_step_draw_args(h, c, &r.n_mask);
     else if (c.drop) r.mt = ip_step_maskT_args(h, c, &r.n_mask);
-    r.f = ip_fwd_args(h, c, c.mask0, c.drop ? 1.0f / h->cfg.keep_prob : 1.0f);
+    const float inv_keep = c.drop ? 1.0f / h->cfg.keep_prob : 1.0f;
+    if (ip_fwd_rows(h) == IP_NARROW) r.f = ip_fwd_args(h, c, c.mask0, inv_keep);
+    if (ip_fwd_rows(h) == IP_MANY || ip_bwd_rows(h) == IP_MANY) r.m = ip_many_args(h, c, c.mask0, inv_keep);      // (the backward reads neither the mask nor inv_keep)
     r.a0 = (T*)h->a[0]; r.a0T = (T*)h->aT[0]; r.emb = h->emb;
     const StripDuo solo{0, nullptr, nullptr, 0, h->err_flag, 0, h->kn.duo_min};     // one workgroup per strip: nothing to wait for
     r.s = ip_stack_fwd_args<T>(h, c); r.s.duo = solo; r.s.warm = 0; r.s.dbg = nullptr; r.s.sel = -1;
     r.sb = ip_stack_bwd_args<T>(h, c); r.sb.duo = solo; r.sb.warm = 0; r.sb.dbg = nullptr;
-    r.ib = ip_bwd_args(h, c); r.dz0 = h->dz0; r.gxp = h->gxp; r.gb_part = h->gb_part;
+    if (ip_bwd_rows(h) == IP_NARROW) r.ib = ip_bwd_args(h, c);
+    r.dz0 = h->dz0; r.gxp = h->gxp; r.gb_part = h->gb_part;
     const float lr_step = ip_lr_step(h, h->adam_t + (h->adam ? 1 : 0));
     r.bu = ip_b_args(h, c, lr_step);
     r.sa = ip_scat_args(h); r.sa.rec = rec;
@@ -1135,16 +1247,20 @@ template <typename T> hipError_t ip_launch_step_class(const ipnn_handle* h, cons
     constexpr int RT = sizeof(T) == 2 ? 2 : 1;
     const IpStepArg<T>* d = static_cast<const IpStepArg<T>*>(dev_args);
     const unsigned M = (unsigned)c.pc.members.size();
-    const size_t lds16 = ip16_lds(h->F, h->Dp[0]);
-    const int maxD = h->plan.maxD;
+    // the inner-product layer by row kind, per direction: examples per workgroup (the grid's unit) and dynamic LDS
+    const bool many_f = c.pc.rows == IP_MANY, many_b = c.rows_bwd == IP_MANY;
+    const int ex_f = many_f ? IPM_EX : 16, ex_b = many_b ? IPM_BEX : 16;
+    const size_t lds_f = many_f ? ipm_fwd_lds(h->F) : ip16_lds(h->F, h->Dp[0]);
+    const size_t lds_b = many_b ? ipm_bwd_lds(h->F, h->P, c.pc.wv) : ip16_lds(h->F, h->Dp[0]);
+    const IpTiles &tf = h->plan.fwd, &tb = h->plan.bwd;
     hipError_t e = hipSuccess;
 #define STEP_K(expr) do { if ((e = (expr)) != hipSuccess) return e; } while (0)
     if (x.n_draw) STEP_K(ip_launch(IP_K(256, k_mask_draw_g<T>), dim3((unsigned)x.n_draw, M), 0, st, d));
     if (x.n_maskT) STEP_K(ip_launch(IP_K(256, k_mask_T_g<T>), dim3((unsigned)x.n_maskT, M), 0, st, d));
-    STEP_K(ip_launch(ip_step_gather_sel<T>(c.pc.wv, c.pc.nt), dim3((unsigned)(Ba / 16), M), lds16, st, d));
-    STEP_K(ip_launch(ip_step_strip_sel<T>(false), dim3((unsigned)(Ba / (16 * RT)), M), h->plan.strip_lds, st, d, maxD));
-    STEP_K(ip_launch(ip_step_strip_sel<T>(true), dim3((unsigned)(Ba / (16 * RT)), M), h->plan.strip_lds, st, d, maxD));
-    STEP_K(ip_launch(ip_step_bwd_sel<T>(c.pc.wv), dim3((unsigned)(Ba / 16), M), lds16, st, d));
+    STEP_K(ip_launch(ip_step_gather_sel<T>(c.pc.rows, c.pc.wv, c.pc.nt), dim3((unsigned)(Ba / ex_f), M), lds_f, st, d));
+    STEP_K(ip_launch(ip_step_strip_sel<T>(false), dim3((unsigned)(Ba / (16 * RT)), M), tf.lds, st, d, tf.capA, tf.capB));
+    STEP_K(ip_launch(ip_step_strip_sel<T>(true), dim3((unsigned)(Ba / (16 * RT)), M), tb.lds, st, d, tb.capA, tb.capB));
+    STEP_K(ip_launch(ip_step_bwd_sel<T>(c.rows_bwd, c.pc.wv), dim3((unsigned)(Ba / ex_b), M), lds_b, st, d));
     STEP_K(ip_launch(IP_K(256, k_ip_b_update_g<T>), dim3(M), 0, st, d));
     STEP_K(ip_launch(IP_K(256, k_ip_scat1_g<T>), dim3((unsigned)x.n_scat1, M), 0, st, d));
     STEP_K(ip_launch(IP_K(256, k_ip_scat2_g<T>), dim3(256, M), 0, st, d));
@@ -1171,32 +1287,45 @@ const char* ipnn_last_error(const ipnn_handle* h) { return h ? h->err.c_str() : 
 
 uint64_t ipnn_cfg_size(void) { return (uint64_t)sizeof(ipnn_cfg); }
 
+uint64_t ipnn_plan_info_size(void) { return (uint64_t)sizeof(ipnn_plan_info); }
+
+// what ipnn_create would choose: its own check, knobs, shape and strip plan, with no device in between
+int ipnn_plan_query(const ipnn_cfg* cfg, ipnn_plan_info* out)
+{
+    if (!cfg || !out) { g_ip_err = "null argument"; return FNN_ERR_ARG; }
+    IRC(ip_cfg_check(cfg));
+    const IpKnobs kn = ip_read_knobs();
+    const IpDims dm = ip_dims(*cfg);
+    const IpStrips p = ip_strip_plan(dm, kn);
+    ipnn_plan_info o{};
+    o.strips = p.strip; o.pairs = p.pairs; o.cut = p.cut;
+    o.rows_fwd = dm.wide ? IPNN_ROWS_WIDE : dm.many_fwd ? IPNN_ROWS_MANY : IPNN_ROWS_NARROW;
+    o.rows_bwd = dm.wide ? IPNN_ROWS_WIDE : dm.many_bwd ? IPNN_ROWS_MANY : IPNN_ROWS_NARROW;
+    o.shares_step = ip_shares_step(p, dm, kn); o.shares_eval = p.strip;
+    o.n_layers = dm.L + 2;
+    for (int t = 0; t <= dm.L + 1; ++t) o.padded[t] = dm.Dp[t];
+    const struct { const IpTiles* t; ipnn_tiles* o; } tiles[] = {{&p.fwd, &o.stack_fwd}, {&p.bwd, &o.stack_bwd}, {&p.wide_fwd, &o.wide_fwd},
+        {&p.wide_bwd, &o.wide_bwd}, {&p.tail_fwd, &o.tail_fwd}, {&p.tail_bwd, &o.tail_bwd}, {&p.tail, &o.tail_fused}};
+    for (const auto& e : tiles) { *e.o = ipnn_tiles{e.t->capA, e.t->capB, (uint64_t)e.t->lds}; o.lds_max = std::max(o.lds_max, (uint64_t)e.t->lds); }
+    *out = o;
+    return FNN_OK;
+}
+
 int ipnn_create(const ipnn_cfg* cfg, ipnn_handle** out)
 {
     if (!cfg || !out) { g_ip_err = "null argument"; return FNN_ERR_ARG; }
     *out = nullptr;
-    if (cfg->k < 1 || cfg->k > 128) {
-        g_ip_err = "bad shape: k = " + std::to_string(cfg->k) + " (k = rank+1 must be 1..128)"; return FNN_ERR_ARG; }
-    if (cfg->n_fields < 2 || cfg->n_fields > 64) {
-        g_ip_err = "bad shape: n_fields = " + std::to_string(cfg->n_fields) + " (2..64 fields of k <= 16, 2..32 fields of k = 17..128: more is not built)"; return FNN_ERR_ARG; }
-    if (cfg->k > SLOT && cfg->n_fields > 32) {
-        g_ip_err = "bad shape: n_fields = " + std::to_string(cfg->n_fields) + " with k = " + std::to_string(cfg->k) +
-                   " (wide rows, k = 17..128, take 2..32 fields: more than 32 is not built; k <= 16 takes 2..64)"; return FNN_ERR_ARG; }
-    if (cfg->n_hidden < 1 || cfg->n_hidden > IPNN_MAX_HIDDEN ||
-        cfg->max_batch < 1 || cfg->max_batch > 4096 || !(cfg->keep_prob > 0.f && cfg->keep_prob <= 1.f)) {
-        g_ip_err = "bad shape (2..64 fields of k <= 16 or 2..32 fields of k = 17..128, 1..8 hidden layers, batch <= 4096, 0 < keep_prob <= 1)"; return FNN_ERR_ARG; }
-    if (cfg->act != A_TANH && cfg->act != A_SIG && cfg->act != A_RELU) { g_ip_err = "bad act"; return FNN_ERR_ARG; }
-    if (cfg->precision != FNN_PREC_F32 && cfg->precision != FNN_PREC_BF16) { g_ip_err = "bad precision (FNN_PREC_F32 or FNN_PREC_BF16; FNN_PREC_BF16X3 is the FNN / SNN engine's)"; return FNN_ERR_ARG; }
-    if (cfg->optimizer != IPNN_OPT_SGD && cfg->optimizer != IPNN_OPT_ADAM && cfg->optimizer != IPNN_OPT_FTRL) { g_ip_err = "bad optimizer"; return FNN_ERR_ARG; }
-    if (cfg->optimizer == IPNN_OPT_ADAM && !(cfg->adam_eps > 0.f)) { g_ip_err = "Adam needs adam_eps > 0"; return FNN_ERR_ARG; }
+    IRC(ip_cfg_check(cfg));
     int ndev = 0;
     if (hipGetDeviceCount(&ndev) != hipSuccess || ndev <= 0) { g_ip_err = "no HIP device (libfnn_hip.so has no CPU fallback)"; return FNN_ERR_HIP; }
     ipnn_handle* h = new ipnn_handle();
-    h->cfg = *cfg; h->dev = cfg->device; h->F = cfg->n_fields; h->K = cfg->k; h->L = cfg->n_hidden;
-    h->wide = h->K > SLOT; h->rw = h->wide ? rup(h->K, 4) : SLOT;
-    h->P = cfg->pairs ? h->F * (h->F - 1) / 2 : 0; h->CB = h->F * h->rw + h->P; h->bf16 = cfg->precision == FNN_PREC_BF16;
-    h->Bmax = cfg->max_batch; h->ldT = rup(h->Bmax, 256);
+    h->cfg = *cfg; h->dev = cfg->device;
     h->kn = ip_read_knobs();
+    const IpDims& dm = h->dims = ip_dims(*cfg);
+    h->F = dm.F; h->K = dm.K; h->L = dm.L; h->wide = dm.wide; h->rw = dm.rw; h->P = dm.P; h->CB = dm.CB; h->bf16 = dm.bf16;
+    h->many_fwd = dm.many_fwd; h->many_bwd = dm.many_bwd;
+    h->d.assign(dm.d, dm.d + dm.L + 2); h->Dp.assign(dm.Dp, dm.Dp + dm.L + 2);
+    h->Bmax = cfg->max_batch; h->ldT = rup(h->Bmax, 256);
     { int ncu = 0; if (hipDeviceGetAttribute(&ncu, hipDeviceAttributeMultiprocessorCount, cfg->device) == hipSuccess && ncu > 0) h->n_cu = ncu; }
     auto fail = [&](int code) { g_ip_err = h->err; ipnn_destroy(h); return code; };
 #define IK(expr) do { hipError_t e2_ = (expr); if (e2_ != hipSuccess) { h->err = std::string(#expr) + ": " + hipGetErrorString(e2_); return fail(FNN_ERR_HIP); } } while (0)
@@ -1206,12 +1335,6 @@ int ipnn_create(const ipnn_cfg* cfg, ipnn_handle** out)
         IK(hipStreamCreateWithFlags(&h->st2, hipStreamNonBlocking));
         for (hipEvent_t* e : {&h->ev.fork, &h->ev.bwd, &h->ev.wg, &h->ev.join, &h->ev.tab, &h->ev.mask}) IK(hipEventCreateWithFlags(e, hipEventDisableTiming));
     }
-    h->d.resize(h->L + 2); h->Dp.resize(h->L + 2);
-    h->d[0] = h->F * h->K + h->P + 1; h->Dp[0] = rup(h->CB + 2, 64);
-    for (int t = 1; t <= h->L; ++t) { h->d[t] = cfg->hidden[t - 1]; h->Dp[t] = rup(h->d[t] + 1, 64); if (h->d[t] < 1 || h->d[t] > 4095) { h->err = "hidden size out of range"; return fail(FNN_ERR_ARG); } }
-    h->d[h->L + 1] = 1; h->Dp[h->L + 1] = 64;
-    h->many_fwd = !h->wide && ip_many_choice(h->F, h->Dp[0], IPM_FWD_MIN_FIELDS, "IPNN_MANY_FWD_MIN");
-    h->many_bwd = !h->wide && ip_many_choice(h->F, h->Dp[0], IPM_BWD_MIN_FIELDS, "IPNN_MANY_MIN");
     h->sk.resize(h->L + 1);
     for (int t = 1; t <= h->L + 1; ++t) {                          // ~256 workgroups of 128 x 128 per product
         const int tiles = ((h->Dp[t - 1] + 127) / 128) * ((h->Dp[t] + 127) / 128);
@@ -1664,7 +1787,8 @@ int ipnn_train_step_multi(ipnn_handle* const* hs, int n_models, const int32_t* i
     std::vector<int> own;
     for (int m = 0; m < M; ++m) {
         if (!ip_step_shares(hs[m])) { own.push_back(m); continue; }
-        const IpStepClass c{ip_pred_class_of(hs[m], wts != nullptr), hs[m]->plan.group.wg0[hs[m]->L + 1]};
+        const IpStepClass c{ip_pred_class_of(hs[m], wts != nullptr), hs[m]->plan.group.wg0[hs[m]->L + 1], ip_bwd_rows(hs[m]),
+                            hs[m]->plan.bwd.capA, hs[m]->plan.bwd.capB};
         cls[class_index(cls, c)].pc.members.push_back(m);
     }
     const int ng = M - (int)own.size();

@@ -55,6 +55,36 @@ def criteo_feed(v_wts, c_ids, c_wts, offsets):
     return ids, np.concatenate([v_wts, c_wts], axis=1).astype(np.float32)
 
 
+def _cfg(n_fields, k, hidden, act, pairs, max_batch, precision, lr, keep_prob, optimizer, adam_betas, adam_eps, device, stream):
+    hidden = list(hidden)
+    hid = (C.c_int32 * 8)(*(hidden + [0] * (8 - len(hidden))))
+    return _capi.ipnn_cfg(n_fields, k, len(hidden), hid, _capi.IPNN_ACTS[act], 1 if pairs else 0, max_batch,
+                          1 if precision == 'bf16' else 0, lr, keep_prob, {'sgd': 0, 'adam': 1, 'ftrl': 2}[optimizer], adam_betas[0],
+                          adam_betas[1], adam_eps, device, stream)
+
+
+def plan_query(n_fields, k, hidden, precision='bf16', pairs=True, act='relu', max_batch=4096, optimizer='sgd'):
+    """What an IPNNEngine of this shape would choose under the environment's IPNN_* knobs (ipnn_plan_query): needs the library
+    but no device.  A dict: 'strips' (the strip kernels run the deep stack; False: one GEMM launch per product), 'pairs', 'cut',
+    'rows_fwd' / 'rows_bwd' ('narrow', 'wide' or 'many'), 'shares_step' / 'shares_eval' (the engine shares the launches of
+    train_step_many / of evaluate_many and predict_many), 'padded' (the layers' padded widths), 'lds_max', and per strip launch
+    -- 'stack_fwd', 'stack_bwd', 'wide_fwd', 'wide_bwd', 'tail_fwd', 'tail_bwd', 'tail_fused' -- a dict of 'cap_a', 'cap_b' (the
+    two LDS tiles' widths in columns) and 'lds_bytes'; all zero for a launch the engine never issues."""
+    lib = _capi.load()
+    cfg = _cfg(n_fields, k, hidden, act, pairs, max_batch, precision, 1e-4, 0.5, optimizer, (0.9, 0.999), 1e-8, 0, None)
+    info = _capi.ipnn_plan_info()
+    rc = lib.ipnn_plan_query(C.byref(cfg), C.byref(info))
+    if rc != 0:
+        raise FNNError(rc, (lib.ipnn_last_error(None) or b'').decode())
+    out = {name: bool(getattr(info, name)) for name in ('strips', 'pairs', 'shares_step', 'shares_eval')}
+    out.update(cut=info.cut, rows_fwd=_capi.IPNN_ROWS[info.rows_fwd], rows_bwd=_capi.IPNN_ROWS[info.rows_bwd],
+               padded=list(info.padded[:info.n_layers]), lds_max=int(info.lds_max))
+    for name in _capi.IPNN_PLAN_LAUNCHES:
+        t = getattr(info, name)
+        out[name] = {'cap_a': t.cap_a, 'cap_b': t.cap_b, 'lds_bytes': int(t.lds_bytes)}
+    return out
+
+
 class IPNNEngine(object):
     def __init__(self, n_fields, k, hidden, act='relu', max_batch=4096, precision='bf16', lr=1e-4, keep_prob=0.5, device=0,
                  pairs=True, optimizer='sgd', adam_eps=1e-8, adam_betas=(0.9, 0.999), reduce='sum', stream=None):
@@ -68,10 +98,9 @@ class IPNNEngine(object):
         self.F, self.K, self.hidden = n_fields, k, list(hidden)
         self.max_batch = max_batch
         self.d = [n_fields * k + (n_fields * (n_fields - 1) // 2 if pairs else 0) + 1] + self.hidden + [1]
-        hid = (C.c_int32 * 8)(*(self.hidden + [0] * (8 - len(self.hidden))))
-        cfg = _capi.ipnn_cfg(n_fields, k, len(self.hidden), hid, _capi.IPNN_ACTS[act], 1 if pairs else 0, max_batch,
-                             1 if precision == 'bf16' else 0, lr, keep_prob, {'sgd': 0, 'adam': 1, 'ftrl': 2}[optimizer], adam_betas[0],
-                             adam_betas[1], adam_eps, device, C.c_void_p(self.stream.cuda_stream))
+        self._shape = dict(precision='bf16' if precision == 'bf16' else 'f32', pairs=bool(pairs), act=act, max_batch=max_batch, optimizer=optimizer)
+        cfg = _cfg(n_fields, k, self.hidden, act, pairs, max_batch, precision, lr, keep_prob, optimizer, adam_betas, adam_eps, device,
+                   C.c_void_p(self.stream.cuda_stream))
         h = C.c_void_p()
         rc = self.lib.ipnn_create(C.byref(cfg), C.byref(h))
         if rc != 0:
@@ -83,6 +112,11 @@ class IPNNEngine(object):
     def _ck(self, rc):
         if rc != 0:
             raise FNNError(rc, (self.lib.ipnn_last_error(self.h) or b'').decode())
+
+    @property
+    def plan(self):
+        """plan_query of this engine's shape, under the knobs as the environment holds them now (the engine read them when it was made)."""
+        return plan_query(self.F, self.K, self.hidden, **self._shape)
 
     def close(self):
         if getattr(self, 'h', None):

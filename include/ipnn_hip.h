@@ -13,8 +13,13 @@
  * Field counts: narrow rows (k = 1..16) take 2..64 fields -- the reference's classes are 39-field models (X_feas = 13 +
  * len(cat_sizes), python/FNN_IP_L3.py) -- with and without `pairs`, in both precisions, under every optimiser; layer 0 then holds
  * 16 F + F(F-1)/2 + 2 columns padded to a multiple of 64: at most 3072 (64 fields with pairs; 1408 at 39).  Up to 32 fields the
- * inner-product layer runs 16 examples per workgroup; above, 8 (forward) and 4 (backward) with only the embeddings in LDS.  A
- * layer 0 wider than 1024 columns sends the deep stack to one GEMM launch per product.  Wide rows stay at 2..32 fields.
+ * inner-product layer runs 16 examples per workgroup; above, 8 (forward) and 4 (backward) with only the embeddings in LDS.  The
+ * deep stack runs on the strip kernels -- a strip of examples through every product inside one workgroup, the activations in two
+ * LDS tiles -- while the tiles fit: up to 32 fields two equal tiles of at most 1024 columns; above, with a layer 0 wider than
+ * that, two tiles of the widths each launch's layers need, 2560 columns together (every stack of the reference at its 39 fields;
+ * not 64 fields with pairs, not FNN_IP_L7 from 43 fields on).  Otherwise one GEMM launch per product.  ipnn_plan_query tells, and
+ * IPNN_STRIP_L0=0 in the environment of ipnn_create keeps the limit of 1024 columns for every handle.  Wide rows stay at 2..32
+ * fields.
  *
  * Wide rows (k = 17..128, any of 2..32 fields, both `pairs`, both precisions, every optimiser): the table keeps rows of
  * rw = rup(k, 4) floats (pad columns zero; under Adam / FTRL the state and gradient tables are [n_rows, rw] too) and layer 0
@@ -79,6 +84,37 @@ const char* ipnn_last_error(const ipnn_handle* h);
 /* sizeof(ipnn_cfg) as the library was compiled (a binding checks its own struct against it). */
 uint64_t ipnn_cfg_size(void);
 int ipnn_create(const ipnn_cfg* cfg, ipnn_handle** out);
+
+/* What ipnn_create would choose for a cfg under the environment's knobs, computed without a device (and without a handle): the
+ * code ipnn_create itself runs.  cfg's device and stream are not read.  A cfg that ipnn_create refuses for its shape is refused
+ * here with the same message (ipnn_last_error(NULL)).
+ *   A strip launch keeps a strip's activations in two LDS tiles, A and B, which alternate from layer to layer; cap_a / cap_b are
+ * their widths in padded columns (the widest layer that lands in each over the launch's range) and lds_bytes the launch's dynamic
+ * LDS.  The launches: the whole stack forward and backward (one launch per direction: every f32 step, a bf16 batch too long for
+ * pairs, every group call), the wide range forward and backward (products 1 .. cut, as pairs of workgroups) and the narrow tail
+ * (products cut + 1 .. n_hidden + 1) forward, backward and fused (both in one launch: the default form of a bf16 training step
+ * that splits).  Launches a handle never issues are all zero: every one on the GEMM path, the last five where 1 <= cut < n_hidden
+ * does not hold. */
+#define IPNN_ROWS_NARROW 0      /* 16 examples per workgroup (k_ip_fwd / k_ip_bwd)                         */
+#define IPNN_ROWS_WIDE   1      /* k = 17..128                                                             */
+#define IPNN_ROWS_MANY   2      /* 33..64 fields: 8 examples forward / 4 backward, the embeddings in LDS   */
+typedef struct ipnn_tiles { int32_t cap_a, cap_b; uint64_t lds_bytes; } ipnn_tiles;
+typedef struct ipnn_plan_info {
+    int32_t strips;                        /* 1: the strip kernels run the deep stack; 0: one GEMM launch per product */
+    int32_t pairs;                         /* 1: batches whose pairs fit the chip run two workgroups per strip (bf16)  */
+    int32_t cut;                           /* products 1 .. cut are wide enough for pairs                             */
+    int32_t rows_fwd, rows_bwd;            /* IPNN_ROWS_*: the inner-product layer's kernels, per direction           */
+    int32_t shares_step, shares_eval;      /* 1: the handle shares the launches of ipnn_train_step_multi / of
+                                              ipnn_predict_multi and ipnn_eval_multi; 0: it runs its own inside them  */
+    int32_t n_layers;                      /* n_hidden + 2                                                            */
+    int32_t padded[IPNN_MAX_HIDDEN + 2];   /* padded width of layer 0 .. n_hidden + 1                                 */
+    ipnn_tiles stack_fwd, stack_bwd, wide_fwd, wide_bwd, tail_fwd, tail_bwd, tail_fused;
+    uint64_t lds_max;                      /* the largest lds_bytes above                                             */
+} ipnn_plan_info;
+/* sizeof(ipnn_plan_info) as the library was compiled */
+uint64_t ipnn_plan_info_size(void);
+int ipnn_plan_query(const ipnn_cfg* cfg, ipnn_plan_info* out);
+
 int ipnn_destroy(ipnn_handle* h);
 int ipnn_sync(ipnn_handle* h);
 
@@ -160,7 +196,7 @@ int ipnn_eval_w(ipnn_handle* h, const int32_t* ids, const float* wts, const int3
  * multiple of 256) and LAUNCH CLASS -- element type, n_hidden, the padded widths, the gather's row kind, pairs, weights given
  * or not; activation, k, table size and values may differ -- one inner-product launch and one launch over the whole stack,
  * both with the model as a grid dimension, one workgroup per strip (no workgroup of a group launch waits for another).  The
- * other members (a layer too wide for the strips, IPNN_STRIP=0) run their own launches inside the call.  ipnn_eval_multi takes
+ * other members (a stack too wide for the strips' tiles, IPNN_STRIP=0) run their own launches inside the call.  ipnn_eval_multi takes
  * the models in groups of as many as fit $IPNN_EVAL_SCRATCH_BYTES (read per call, default 2^30, one model at the least; N * 4
  * bytes of predictions plus the metric pass's ~8.5 N per model) in one allocation hs[0] keeps while it is large enough; each
  * group costs one metric pass and one synchronisation.  Neither where the feed nor where the groups are cut changes a bit.
@@ -192,11 +228,11 @@ int ipnn_eval_multi(ipnn_handle* const* hs, int n_models, const int32_t* ids, co
  * act, k, pairs, depths, widths, table sizes, lr, keep_prob, the mean / sum loss and both precisions.  A member's pending
  * IPNN_UPDATE_SIDE=1 update is joined first; everything then runs on hs[0]'s stream, which first waits for every other member's
  * stream, and they wait for the call's last launch.
- *   Members on the strip kernels with narrow rows (k <= 16) and at most 32 fields share launches: per LAUNCH CLASS -- the
+ *   Members on the strip kernels with narrow rows (k <= 16, any field count) share launches: per LAUNCH CLASS -- the
  * prediction launch class of ipnn_predict_multi plus the split-K layout of the weight gradients -- every stage of the step runs
  * ONCE with the model as a grid dimension (b and the table pass of an Adam / FTRL member are that member's own two launches), one workgroup per strip (no pair form, no tail split: no workgroup of a group launch
  * waits for another).  Members that agree in n_rows, key width and sort runs share one grouping of the batch's ids.  Every other
- * member (wide rows, 33 to 64 fields, a layer too wide for the strips, IPNN_STRIP=0, IPNN_GROUP_WGRAD=0, a diagnostic knob) runs
+ * member (wide rows, a stack too wide for the strips' tiles, IPNN_STRIP=0, IPNN_GROUP_WGRAD=0, a diagnostic knob) runs
  * its own solo step inside the call: no shape is refused.  n_models == 1 forwards to the solo step.
  *   Refusals (before any launch and any write; the message starts with the function's name, names the model and is left with
  * ipnn_last_error(hs[0]), or ipnn_last_error(NULL) without a usable hs[0]): FNN_ERR_ARG for null hs or a null entry, n_models

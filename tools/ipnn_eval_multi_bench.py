@@ -101,7 +101,7 @@ def run(shapes, Ns, Ms, repeats, write):
            'repeats': repeats, 'max_batch': BMAX,
            'timing': 'microseconds, perf_counter around the synchronised call(s); median / min / max over the repeats, the two '
                      'variants alternating inside every repeat after a warm-up of each',
-           'not_measured': ['more than %d models' % max(Ms), 'field counts other than 16', 'wide rows (k >= 17)', 'value weights',
+           'not_measured': ['more than %d models' % max(Ms), 'field counts other than %d' % F, 'wide rows (k >= 17)', 'value weights',
                             'members off the strip kernels'],
            'points': {}}
     for shape in shapes:
@@ -131,15 +131,18 @@ def run(shapes, Ns, Ms, repeats, write):
 
 
 def main():
+    global F
     ap = argparse.ArgumentParser()
     ap.add_argument('--shapes', default='L3,L7')
     ap.add_argument('--n', default='100000,1000000')
     ap.add_argument('--models', default='1,4,16,64')
     ap.add_argument('--repeats', type=int, default=5)
+    ap.add_argument('--fields', type=int, default=F, help='fields of the feed and of every model (default 16; 39: the reference\'s columns)')
     ap.add_argument('--out', default=os.path.join(ROOT, 'profiles', 'ipnn_eval_multi_bench.json'))
     a = ap.parse_args()
     if a.repeats < 5:
         raise SystemExit('at least five repeats')
+    F = a.fields
 
     def write(res):
         with open(a.out, 'w') as f:

@@ -3,7 +3,10 @@
 FNN_IP_L7 (1000 / 800 / 600 / 400 / 200 / 100 / 50), relu, keep_prob 0.5, drawn masks.  Writes profiles/ipnn_step_multi_bench.json.
 
   python tools/ipnn_step_multi_bench.py [--archs L3,L7] [--models 1,2,4,16,64] [--batches 10,100,4096] [--repeats 5] [--steps 8]
-                                        [--call-first] [--out FILE]
+                                        [--call-first] [--fields 16] [--out FILE]
+
+--fields: another field count on the same table (synth.field_sizes_ipinyou deals its rows to that many fields): 39 is the
+reference's own column count, where layer 0 has 1408 columns.
 
 One process; the feed (--steps batches of ids, y) is resident on the device; every handle shares one stream (the events need
 one).  A point is (stack, precision, optimiser, B, M): SGD in both precisions, one Adam row (bf16, M = 16), and one mixed group of
@@ -101,7 +104,7 @@ def run(archs, Ms, Bs, repeats, steps, out, call_first=False):
                      '= between events on the stream; median / min / max over the repeats, the loop and the call alternating inside '
                      'every repeat after a warm-up of each; no loss read-back inside a sample',
            'not_measured': ['more than %d models' % Mmax, 'members on distinct streams (every handle here shares one stream)',
-                            '33 and more fields', 'wide rows (k > 16) inside a group', 'value weights', 'the caller\'s masks (every point draws them)',
+                            'field counts other than %d' % F, 'wide rows (k > 16) inside a group', 'value weights', 'the caller\'s masks (every point draws them)',
                             'the id grouping and the side chain on a side stream of the group call (built in line only)',
                             'ipnn.train_epoch_many end to end'],
            'points': {}}
@@ -173,6 +176,7 @@ def run(archs, Ms, Bs, repeats, steps, out, call_first=False):
 
 
 def main():
+    global F
     ap = argparse.ArgumentParser()
     ap.add_argument('--archs', default='L3,L7')
     ap.add_argument('--models', default='1,2,4,16,64')
@@ -180,10 +184,12 @@ def main():
     ap.add_argument('--repeats', type=int, default=5)
     ap.add_argument('--steps', type=int, default=8)
     ap.add_argument('--call-first', action='store_true', help='inside every repeat the call runs before the loop (default: the loop first)')
+    ap.add_argument('--fields', type=int, default=F, help='fields of the feed and of every model (default 16)')
     ap.add_argument('--out', default=os.path.join(ROOT, 'profiles', 'ipnn_step_multi_bench.json'))
     a = ap.parse_args()
     if a.repeats < 5:
         raise SystemExit('at least five repeats')
+    F = ob.F = a.fields                                           # (ob.data deals the table's rows to ob.F fields)
     res = run(a.archs.split(','), [int(v) for v in a.models.split(',')], [int(v) for v in a.batches.split(',')], a.repeats, a.steps, a.out, a.call_first)
     save(res, a.out)
     print(json.dumps(res))
